@@ -14,10 +14,14 @@ Multi-GPU: the path shards by independent units (SNR-sweep points / batches: SUR
 rank runs its own full step on its own batch, no data-path collective; the only communication is the final
 RCCL all-reduce of the BER/loss table, done once inside the timed region.  scaling = "weak".
 
-One JSON line is printed by rank 0; see the task contract for the fields.  Extra objects:
-  roofline      dominant kernel of the step vs the fp32 MFMA peak (157.3 TFLOP/s)
-  cpu_baseline  the reference-equivalent CPU graph (oracle/torch_ref.py, literal TF-style conv3d) on the host
-  kernels       per-operator average launch time (HIP events on the launch stream)
+One JSON line is printed by rank 0; see the task contract for the fields.  A plain run does only what that line's headline
+needs: set up, pre-warm, W warm-up steps, ONE timed region of exactly K steps (`ms_per_step`, `value`), the outputs of the last
+timed step when --dump-outputs DIR is given, the line.  --full adds the rest (7 timed regions and their median, unless
+--regions says otherwise), as extra objects:
+  step.boundaries  in-situ timeline of the step's launches          roofline / kernels  per-operator launch times vs peak
+  configs          the C3 / C4 configurations                       e2e                 generate-and-train loop
+  sweep            the 40-point SNR sweep, sharded over the ranks   cpu_baseline        the reference-equivalent CPU graph
+  device           clocks, box fingerprint, copy bandwidth
 """
 import argparse
 import json
@@ -430,6 +434,54 @@ def launch_ranks(n: int) -> int:
     return subprocess.call(cmd, env=env)
 
 
+DUMP_CAP = 1 << 20          # elements per array written by --dump-outputs; a larger array is written as a fixed, seeded sample
+DUMP_LIMIT = 64 << 20       # bytes written by --dump-outputs in all
+
+
+def step_outputs(eng, table):
+    """What the timed training step hands its caller after its last step (name -> tensor or array): the updated variables --
+    the 8 trainables, their Adam slots and the Adam scalars, i.e. the effect of `train_op` -- power_tx, ce_mean, berlin, log_ber
+    and the confusion matrix of that step, the float64 BER/loss table the region reduced, and output:0 when --store-prob keeps it."""
+    import numpy as np
+    from dl_ofdm_amd.engine import PARAM_NAMES
+    out = {}
+    for arena in ("params", "adam_m", "adam_v"):
+        for n in PARAM_NAMES:
+            out[arena + "." + n.replace("/", ".")] = eng.view(n, getattr(eng, arena))
+    out["adam_state"] = eng.adam_state
+    m = eng.metrics()
+    out["tx_power"] = eng.tx_power
+    for k in ("ce_mean", "berlin", "log_ber"):
+        out[k] = np.array([m[k]], dtype=np.float64)
+    out["conf"] = np.array(m["conf"], dtype=np.float64)
+    out["ber_table"] = table
+    if eng.prob is not None:
+        out["prob"] = eng.prob
+    return out
+
+
+def dump_outputs(arrays, out_dir):
+    """DIR/<name>.npy per array, float32 (float64 where the step's own value is float64).  An array of more than DUMP_CAP
+    elements is written flattened as the sample at DUMP_CAP sorted indices drawn with a fixed seed from its size alone, so that
+    two builds write the same elements."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        t = a.detach() if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))
+        if t.numel() > DUMP_CAP:
+            idx = np.sort(np.random.RandomState(20240611).randint(0, t.numel(), DUMP_CAP))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        t = t.cpu()
+        host[name] = t.numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    for name, v in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 class Watchdog:
     """`with Watchdog(seconds, what):` -- if the block has not finished in time, print what hung and end the process
     (rc 3): a collective that never completes cannot be interrupted from Python any other way."""
@@ -468,9 +520,15 @@ def main():
                     help="every step normalises its own batch first (6 launches) instead of normalising the next batch "
                          "behind its Adam update (5 launches; same results, DESIGN.md section 3.5)")
     ap.add_argument("--fork", action="store_true", help="two-stream graph (dense dW on a forked stream) instead of the grouped dX+dW launch")
-    ap.add_argument("--regions", type=int, default=7,
+    ap.add_argument("--regions", type=int, default=None,
                     help="how many times the timed K-step region is run back to back (each bracketed by barrier + synchronize); "
-                         "`value` is the MEDIAN region, all of them are listed in step.regions_ms")
+                         "`value` is the MEDIAN region, all of them are listed in step.regions_ms (default 1; 7 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline line: 7 regions, step.boundaries, per-kernel times and roofline, the C3 / "
+                         "C4 configurations, e2e, the SNR sweep, the CPU baseline, clocks and box fingerprint (the --no-* options "
+                         "below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (bench.step_outputs)")
     ap.add_argument("--store-prob", action="store_true",
                     help="also write `output:0` (the per-bit probabilities) to HBM in every training step; the reference's step does not fetch it")
     ap.add_argument("--no-boundaries", action="store_true", help="skip the in-situ step timeline (step.boundaries)")
@@ -535,6 +593,16 @@ def main():
     eng.bits.copy_(torch.randint(0, 2, eng.bits.shape, generator=g, device=dev, dtype=torch.int32))
     use_graph, fork = (args.graph or args.fork) and not args.no_graph, args.fork
     pipeline = not args.no_pipeline and not fork
+    n_regions = max(1, args.regions if args.regions is not None else (7 if args.full else 1))
+    # the state every timed region starts from: the parameters as initialised, Adam moments and scalars at zero.  Restored in
+    # front of each region, so that what the last timed step computes depends on K alone -- not on how many steps the time-
+    # bounded pre-warm ran -- and two builds can be compared output for output (--dump-outputs)
+    state = [t for t in (eng.params, eng.grads, eng.adam_m, eng.adam_v, eng.adam_state) if t is not None]
+    state0 = [t.clone() for t in state]
+
+    def restore_state():
+        for t, t0 in zip(state, state0):
+            t.copy_(t0)
 
     def step():
         if pipeline:
@@ -562,12 +630,12 @@ def main():
     reduce_table()          # first use loads torch's element-wise code objects / RCCL channels (tens of ms of GPU idleness, once)
     if world > 1:
         dist.barrier()
-    pci = hip_device_pci(dev)
+    pci = hip_device_pci(dev) if args.full else None
     # (read BEFORE the pre-warm: the sysfs DPM files are answered by the SMU and take tens of milliseconds for a node's
     # cards -- read between the pre-warm and the timed regions, as round 4 did, they left the GPU idle long enough to restart
     # it at its post-idle clock, and with the driver's K = 20 the seven 1.5-ms regions then measured the recovery:
-    # 0.0767, 0.0764, 0.0763, 0.0759, 0.0754, 0.0759, 0.0753 ms in gpurun_out/r05c)
-    clocks_before = gpu_clock_state(pci) if rank == 0 else None
+    # 0.0767, 0.0764, 0.0763, 0.0759, 0.0754, 0.0759, 0.0753 ms in the round-5 run)
+    clocks_before = gpu_clock_state(pci) if rank == 0 and args.full else None
     timer = HipTimer()
     regions, ev_regions, enq_regions = [], [], []
     # untimed pre-warm AFTER everything that leaves the GPU idle: continuous load until the clocks are where they stay
@@ -577,7 +645,10 @@ def main():
     # The timed region = EXACTLY K steps between barrier + synchronize pairs, MAX over ranks.  It is run `--regions` times
     # back to back and `value` is the median region: with the driver's K = 20 one region lasts 1.6 ms, and a single sample
     # of that length cannot tell a slow box from a slow moment (0.101 vs 0.079 ms on another box of the pool).
-    for _ in range(max(1, args.regions)):
+    # A plain run times ONE region, so that K is exactly the number of timed steps; a caller that wants a steadier figure
+    # chooses a larger K from ms_per_step.
+    for _ in range(n_regions):
+        restore_state()
         barrier()
         timer.start(eng._stream())
         t0 = time.perf_counter()
@@ -597,7 +668,9 @@ def main():
         if world > 1:
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         regions.append(float(tmax.item()))
-    clocks_after = gpu_clock_state(pci) if rank == 0 else None
+    clocks_after = gpu_clock_state(pci) if rank == 0 and args.full else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(step_outputs(eng, table), args.dump_outputs)
     order = sorted(range(len(regions)), key=lambda i: regions[i])
     mid = order[len(order) // 2]                                  # the median region (odd count: an actual sample)
     elapsed, ev_ms, t_enqueue = regions[mid], ev_regions[mid], enq_regions[mid]
@@ -638,7 +711,7 @@ def main():
                           "regions_ms": [round(r / args.steps * 1e3, 5) for r in regions],
                           "regions_hip_event_ms": [round(r / args.steps, 5) for r in ev_regions],
                           "ber_table": [float(v) for v in table.cpu()]}
-        if not args.no_boundaries and not use_graph:
+        if args.full and not args.no_boundaries and not use_graph:
             # in-situ timeline of the same step (dl_ofdm_amd/steptrace.py): per launch its duration inside the step, the idle
             # gap in front of it and the shader clock its workgroups saw -- the decomposition of ms_per_step
             from dl_ofdm_amd.steptrace import trace_steps
@@ -660,7 +733,7 @@ def main():
                 sclk = sum(u * c for u, c in w) / sum(u for u, _ in w)
                 result["step"]["sclk_mhz_in_step"] = round(sclk, 0)
                 result["step"]["mfma_frac_at_measured_sclk"] = result["step"]["mfma_frac"] * 2400.0 / sclk
-        if not args.no_kernel_times:
+        if args.full and not args.no_kernel_times:
             kt = time_ops(eng, iters=200, warmup=20)
             result["kernels"] = {k: {"us": round(v["ms"] * 1e3, 3), "tflops": round(v["tflops"], 2), "kernel": v["kernel"]}
                                  for k, v in kt.items()}
@@ -680,18 +753,18 @@ def main():
                                   "frac": kt[dom]["tflops"] / PEAK_F32_MFMA_TFLOPS, "traffic": traffic,
                                   "traffic_stale": stale, "traffic_build_id": build, "build_id": lib.dccn_build_id().decode(),
                                   "avg_launch_us": kt[dom]["ms"] * 1e3, "flops_per_launch": kt[dom]["flops"]}
-        if world == 1 and args.config == "c2" and not args.no_other_configs:
+        if args.full and world == 1 and args.config == "c2" and not args.no_other_configs:
             # the other BASELINE.json training configurations, measured in the same run (short: <= 20 steps each, hipGraph
             # replay, HIP events on the launch stream): C3 = config[2] shape (16-QAM), C4 = config[3] (N=1024, MFMA-bound)
             eng = None
             torch.cuda.empty_cache()
             result["configs"] = {k: measure_config(k, dev, steps=20, warmup=5, graph=use_graph, pipeline=pipeline, want_prob=args.store_prob) for k in ("c3", "c4")}
-    if rank == 0 and world == 1 and args.config == "c2" and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and args.config == "c2" and not args.no_e2e:
         eng = None
         torch.cuda.empty_cache()
         result["e2e"] = measure_e2e(dev, c)
     sweep_res = None
-    if args.config == "c2" and not args.no_sweep:
+    if args.full and args.config == "c2" and not args.no_sweep:
         # configs[2] on every rank count the driver launches: this is the curve north_star calls "1/2/4/8-GPU SNR-sweep
         # scaling" (the training value above is weak scaling of replicas by construction)
         eng = None
@@ -701,14 +774,15 @@ def main():
         if sweep_res is not None:
             result["sweep"] = sweep_res
             result["distributed"]["points_per_rank"] = sweep_res.get("points_per_rank")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(c)
-        cu, wf, hbm, arch = _lib.device_info()
-        result["device"] = {"arch": arch, "cus": cu, "clocks_before_timed_regions": clocks_before,
-                            "clocks_after_timed_regions": clocks_after, "box": box_fingerprint(pci),
-                            # the box's HBM speed as a plain device-to-device copy sees it (1 GiB, read + write): one box of the
-                            # round's pool ran the same build 11 % slower per step with its HBM-bound launches 50 % longer
-                            "copy_1GiB_TBps": copy_bandwidth_tbs(dev)}
+        if args.full:
+            cu, wf, hbm, arch = _lib.device_info()
+            result["device"] = {"arch": arch, "cus": cu, "clocks_before_timed_regions": clocks_before,
+                                "clocks_after_timed_regions": clocks_after, "box": box_fingerprint(pci),
+                                # the box's HBM speed as a plain device-to-device copy sees it (1 GiB, read + write): one box of
+                                # the round's pool ran the same build 11 % slower per step with its HBM-bound launches 50 % longer
+                                "copy_1GiB_TBps": copy_bandwidth_tbs(dev)}
         print(json.dumps(result))
     if world > 1:
         dist.barrier()

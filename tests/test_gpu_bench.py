@@ -31,7 +31,7 @@ def _copy_tbs():
 
 def test_bench_prints_one_json_line_with_the_contract_fields():
     copy_tbs = _copy_tbs()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "5"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "40", "--warmup", "5"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -107,3 +107,48 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
             pytest.xfail("slow-HBM box (device-to-device copy %.2f TB/s < 4.3): C2 step at %.1f %% of the fp32 MFMA peak; "
                          "the build's bar is 39 %% on a box whose copy runs at speed" % (copy_tbs, 100 * st["mfma_frac"]))
         raise AssertionError("C2 step below 39 %% of the fp32 MFMA peak (copy %.2f TB/s): %s" % (copy_tbs, diag))
+
+
+def _plain_run(tmp, warmup, steps=30):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup",
+                          str(warmup), "--dump-outputs", str(tmp)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+def test_plain_bench_times_k_steps_and_dumps_what_the_last_one_computed(tmp_path):
+    """a plain run: the headline line only, ONE timed region of exactly --steps steps; --dump-outputs writes the outputs of the
+    last timed step, the same whatever the warm-up was (every timed region starts from the initial state)"""
+    import numpy as np
+    from dl_ofdm_amd.engine import PARAM_NAMES, RxDims, glorot_init
+    a, b = _plain_run(tmp_path / "a", 5), _plain_run(tmp_path / "b", 9)
+    for d in (a, b):
+        assert d["steps"] == 30 and d["n_gpus"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert d["metric"] == "OFDM symbols/sec fwd+bwd, DCCN QPSK N=64" and d["unit"] == "OFDM symbols/s"
+        assert len(d["step"]["regions_ms"]) == 1 and abs(d["step"]["regions_ms"][0] - d["ms_per_step"]) < 1e-5
+        assert abs(d["value"] - 8190 / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+        for k in ("roofline", "kernels", "cpu_baseline", "configs", "e2e", "sweep", "device"):
+            assert k not in d, k
+        assert "boundaries" not in d["step"]
+    fa, fb = sorted(os.listdir(tmp_path / "a")), sorted(os.listdir(tmp_path / "b"))
+    assert fa == fb
+    assert {"tx_power.npy", "ce_mean.npy", "berlin.npy", "conf.npy", "ber_table.npy", "adam_state.npy"} <= set(fa)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in fa) <= 64 << 20
+    out = {}
+    for f in fa:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and x.dtype == y.dtype and x.shape == y.shape, f
+        np.testing.assert_array_equal(x, y, err_msg=f)
+        out[f[:-4]] = x
+    t = out["ber_table"]
+    assert t[5] == 1170 * 320 * 2 and out["conf"].sum() == t[5] and 0.0 < out["ce_mean"][0] < 2.0
+    assert out["adam_state"][0] == 30.0                               # global_step: the 30 timed steps, nothing before them
+    # the parameters are 30 Adam steps (lr 1e-3) away from the seed-1 initialisation the bench builds its engine with
+    p0 = glorot_init(RxDims(S=7, kin=80, F=64, D=320, nbits=2), seed=1)
+    moved = {}
+    for n in PARAM_NAMES:
+        p = out["params." + n.replace("/", ".")]
+        moved[n] = float(np.abs(p - np.asarray(p0[n], dtype=np.float32).reshape(p.shape)).max())
+    assert max(moved.values()) > 0.0 and all(v < 0.1 for v in moved.values()), moved

@@ -113,7 +113,7 @@ def test_bench_two_ranks_over_gloo_one_json_line():
     env = dict(os.environ, DCCN_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--no-cpu-baseline", "--no-kernel-times", "--sweep-frames", "1000"]
+           "--full", "--no-cpu-baseline", "--no-kernel-times", "--sweep-frames", "1000"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -126,8 +126,9 @@ def test_bench_two_ranks_over_gloo_one_json_line():
     t = out["step"]["ber_table"]
     bits_per_rank = 1170 * 320 * 2
     assert t[5] == 2 * bits_per_rank and sum(t[:4]) == 2 * bits_per_rank
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--no-cpu-baseline",
-                          "--no-kernel-times", "--sweep-frames", "1000"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "2",
+                          "--no-cpu-baseline", "--no-kernel-times", "--sweep-frames", "1000"],
+                         cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-3000:]
     o1 = json.loads([ln for ln in one.stdout.splitlines() if ln.startswith("{")][0])
     assert o1["n_gpus"] == 1 and o1["step"]["ber_table"][5] == bits_per_rank
@@ -143,7 +144,7 @@ def test_bench_launches_its_own_ranks():
     under torch.distributed.run, two ranks (gloo here, so that both may share this box's GPU), one JSON line."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_PORT")}
     env.update(DCCN_BENCH_BACKEND="gloo")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full",
                         "--no-cpu-baseline", "--no-kernel-times", "--no-other-configs", "--no-e2e", "--sweep-frames", "1000"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -179,7 +180,7 @@ def test_bench_two_ranks_over_rccl_one_json_line():
     env.update(MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--no-cpu-baseline", "--no-kernel-times", "--sweep-frames", "1000"]
+           "--full", "--no-cpu-baseline", "--no-kernel-times", "--sweep-frames", "1000"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

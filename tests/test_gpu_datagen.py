@@ -245,9 +245,10 @@ def test_doppler_channel_matches_host_given_the_same_phases(chan):
     assert np.abs((a - b).cpu().numpy()).max() <= 5e-5 * float(b.abs().max())
 
 
-def test_harness_trains_on_device_generated_data(tmp_path):
+def test_harness_trains_on_device_generated_data(tmp_path, monkeypatch):
     """receiver.train(device_data=True): data never touches the host; the receiver still learns AWGN QPSK"""
     from dl_ofdm_amd import receiver as R
+    monkeypatch.chdir(tmp_path)                                       # the sweep CSV goes to the working directory
     F = R.Flags(nbits=2, nfilter=64, channel="AWGN", SNR=10.0, msg_length=7 * 8192, batch_size=512, max_epoch_num=8,
                 early_stop=100, token="D", save_dir=str(tmp_path) + "/", seed=5, device_data=True,
                 test_frames=2000, snr_lo=0, snr_hi=10)
@@ -480,7 +481,7 @@ def test_generated_step_refuses_the_double_buffered_plan_and_apply_takes_no_nois
     assert npow is None and torch.isfinite(x).all() and float(x.abs().max()) > 0
 
 
-def test_generated_step_beyond_the_single_pass_normalisation_is_refused_before_anything_runs():
+def test_generated_step_beyond_the_single_pass_normalisation_is_refused_before_anything_runs(tmp_path):
     """receiver.train grows its batch with falling BER (ideal_batch_size: 2045 frames once BER < ~3e-4 at BPSK); the pipelined
     normalisation forms a batch from the fused generator's output for <= 1536 frames only.  The query says so
     (dccn_rx_gen_next_supported, FusedStaticGen.supported(gen, eng)), a step handed gen_next anyway returns
@@ -511,7 +512,7 @@ def test_generated_step_beyond_the_single_pass_normalisation_is_refused_before_a
         assert torch.equal(a, b)
     # the harness at a batch beyond the range: BPSK on AWGN at 10 dB reaches 2045 frames within a few epochs
     Ft = R.Flags(nbits=1, nfilter=64, channel="AWGN", SNR=10.0, max_epoch_num=6, early_stop=200, token="big_batch",
-                 save_dir="/tmp/dccn_big_batch/", device_data=True, seed=1)
+                 save_dir=str(tmp_path / "big_batch") + "/", device_data=True, seed=1)
     res = R.train(Ft, device="cuda", verbose=False, run_test=False)
     assert len(res["history"]) == 6 and np.isfinite(res["history"][-1]["train_loss"])
     assert max(h.get("batch_size", 0) for h in res["history"]) > 1536 or res["history"][-1]["test_ber"] > 3e-4

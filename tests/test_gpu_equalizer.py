@@ -338,16 +338,16 @@ def test_trainer_checkpoint_roundtrip_and_unsupported_variant(tmp_path):
         EqualizerTrainer(F, tx, pr)
 
 
-def test_equalizer_learns_a_flat_fading_channel():
+def test_equalizer_learns_a_flat_fading_channel(tmp_path):
     """End to end through the harness pieces: a receiver trained on AWGN cannot demodulate a random
     phase rotation (flat Rayleigh tap); a few hundred equaliser steps must cut its BER."""
     from dl_ofdm_amd import receiver as R, receiver_mp as H
     from dl_ofdm_amd import ofdm
     base = R.Flags(nbits=2, nfilter=64, channel="AWGN", SNR=10.0, msg_length=7 * 4096, batch_size=512,
-                   max_epoch_num=6, early_stop=100, token="B", save_dir="/tmp/_eq_test/", seed=5)
+                   max_epoch_num=6, early_stop=100, token="B", save_dir=str(tmp_path / "eq") + "/", seed=5)
     res = R.train(base, verbose=False, run_test=False)
     hf = H.Flags(nbits=2, nfilter=64, channel="Flat", msg_length=7 * 2048, batch_size=512, max_epoch_num=5,
-                 early_stop=100, token="B", save_dir="/tmp/_eq_test/", seed=6, eval_frames=2048)
+                 early_stop=100, token="B", save_dir=str(tmp_path / "eq") + "/", seed=6, eval_frames=2048)
     out = H.train(hf, verbose=False, run_test=False, rx_params=res["params"])
     hist = out["history"]
     assert hist[-1]["train_loss"] < hist[0]["train_loss"] - 0.02, hist
@@ -363,7 +363,7 @@ def test_equalizer_learns_a_flat_fading_channel():
     assert without > 0.25, without                       # random phase: the bare receiver is lost
     assert with_eq < without - 0.05, (with_eq, without)
     sw = H.test_model_cross(H.Flags(**{**hf.__dict__, "test_frames": 256, "snr_lo": 0, "snr_hi": 20, "snr_step": 10}),
-                            tr, tx, out_dir="/tmp/_eq_test", verbose=False, channels=("Flat", "EPA"))
+                            tr, tx, out_dir=str(tmp_path / "eq"), verbose=False, channels=("Flat", "EPA"))
     import os
     assert os.path.basename(sw["EPA"][3]) == "Test_DCCN_B_Equalizer0_Flat_test_chan_EPA.csv" and os.path.exists(sw["EPA"][3])
     assert len(sw["Flat"][1]) == 3
@@ -641,7 +641,7 @@ def test_monitor_launch_equals_the_framework_monitors(B, per_symbol):
     assert abs(ref - float(rms)) <= 1e-5 * max(want, 1e-3)
 
 
-def test_generator_on_a_side_stream_trains_the_same_equaliser():
+def test_generator_on_a_side_stream_trains_the_same_equaliser(tmp_path):
     """receiver_mp.DeviceEpochLoop: two resident buffer sets and the generator on its own HIP stream (batch i+1 produced while
     step i runs) against the one-stream loop: same seeds -> history and trained parameters identical bit for bit over 3 epochs
     of 28 steps (a missed dependency trains on a half-written batch, stale labels or the wrong SNR row)."""
@@ -651,7 +651,7 @@ def test_generator_on_a_side_stream_trains_the_same_equaliser():
     out = []
     for overlap in (False, True):
         hf = H.Flags(nbits=2, nfilter=64, channel="EPA", msg_length=7 * 2048, batch_size=512, max_epoch_num=3,
-                     early_stop=100, token="OV", save_dir="/tmp/_eq_overlap_%d/" % overlap, seed=6, eval_frames=512,
+                     early_stop=100, token="OV", save_dir=str(tmp_path / ("overlap_%d" % overlap)) + "/", seed=6, eval_frames=512,
                      device_data=True, overlap_generator=overlap)
         o = ofdm.ofdm_tx(hf)
         res = H.train(hf, verbose=False, run_test=False, rx_params=glorot_init(R.rx_dims(hf, o), 1))
@@ -660,7 +660,7 @@ def test_generator_on_a_side_stream_trains_the_same_equaliser():
     assert torch.equal(out[0][1], out[1][1])
 
 
-def test_next_batch_normalised_on_the_optimizer_launch_trains_the_same_equaliser():
+def test_next_batch_normalised_on_the_optimizer_launch_trains_the_same_equaliser(tmp_path):
     """include/dccn.h dccn_eq_buffers.x_next / x_prenormalised / norm_slot: step i normalises batch i+1 on leading workgroups
     of its optimizer launch and step i+1 starts at the layer norm (receiver_mp.DeviceEpochLoop pipeline, twin plans sharing
     one workspace).  (1) the C ABI directly: two pipelined steps == two plain steps, bit for bit (parameters, Adam state,
@@ -716,7 +716,7 @@ def test_next_batch_normalised_on_the_optimizer_launch_trains_the_same_equaliser
     out = []
     for pipe in (False, True):
         hf = H.Flags(nbits=2, nfilter=64, channel="EPA", msg_length=7 * 2048, batch_size=512, max_epoch_num=3,
-                     early_stop=100, token="PN", save_dir="/tmp/_eq_pipe_%d/" % pipe, seed=6, eval_frames=512,
+                     early_stop=100, token="PN", save_dir=str(tmp_path / ("pipe_%d" % pipe)) + "/", seed=6, eval_frames=512,
                      device_data=True, pipeline_norm=pipe)
         o = ofdm.ofdm_tx(hf)
         res = H.train(hf, verbose=False, run_test=False, rx_params=glorot_init(R.rx_dims(hf, o), 1))
@@ -725,7 +725,7 @@ def test_next_batch_normalised_on_the_optimizer_launch_trains_the_same_equaliser
     assert torch.equal(out[0][1], out[1][1])
 
 
-def test_virtual_next_batch_trains_the_same_equaliser_on_interleaved_profiles():
+def test_virtual_next_batch_trains_the_same_equaliser_on_interleaved_profiles(tmp_path):
     """include/dccn.h dccn_eq_buffers.x_next_virtual on the equaliser's own training channel (mixRayleigh: four static profiles
     frame by frame): the pipelined loop whose optimizer launch reads the next batch as the fused generator's (y, noise, power
     partials) -- x never written but for an epoch's first batch, the noise-power monitor finished by that launch -- against the
@@ -737,7 +737,7 @@ def test_virtual_next_batch_trains_the_same_equaliser_on_interleaved_profiles():
     out = []
     for virt, graph in ((False, False), (True, False), (True, True)):
         hf = H.Flags(nbits=2, nfilter=64, channel="mixRayleigh", msg_length=7 * 2048, batch_size=512, max_epoch_num=3,
-                     early_stop=100, token="VN", save_dir="/tmp/_eq_virt_%d%d/" % (virt, graph), seed=8, eval_frames=512,
+                     early_stop=100, token="VN", save_dir=str(tmp_path / ("virt_%d%d" % (virt, graph))) + "/", seed=8, eval_frames=512,
                      device_data=True, virtual_next=virt, step_graph=graph)
         o = ofdm.ofdm_tx(hf)
         res = H.train(hf, verbose=False, run_test=False, rx_params=glorot_init(R.rx_dims(hf, o), 1))
@@ -748,15 +748,16 @@ def test_virtual_next_batch_trains_the_same_equaliser_on_interleaved_profiles():
     assert all(np.isfinite(h["train_loss"]) and 0.0 < h["train_ber"] < 0.6 for h in out[0][0])
 
 
-def test_equalizer_harness_on_device_generated_data():
+def test_equalizer_harness_on_device_generated_data(tmp_path, monkeypatch):
     """receiver_mp.train(device_data=True): bits, frames, fading, noise and the true channel response all come
     from the GPU generator; same learning criterion as the host-data test above."""
     from dl_ofdm_amd import receiver as R, receiver_mp as H
+    monkeypatch.chdir(tmp_path)                                       # the sweep CSVs go to the working directory
     base = R.Flags(nbits=2, nfilter=64, channel="AWGN", SNR=10.0, msg_length=7 * 4096, batch_size=512,
-                   max_epoch_num=6, early_stop=100, token="B2", save_dir="/tmp/_eq_test2/", seed=5, device_data=True)
+                   max_epoch_num=6, early_stop=100, token="B2", save_dir=str(tmp_path / "eq2") + "/", seed=5, device_data=True)
     res = R.train(base, verbose=False, run_test=False)
     hf = H.Flags(nbits=2, nfilter=64, channel="Flat", msg_length=7 * 2048, batch_size=512, max_epoch_num=5,
-                 early_stop=100, token="B2", save_dir="/tmp/_eq_test2/", seed=6, eval_frames=2048, device_data=True,
+                 early_stop=100, token="B2", save_dir=str(tmp_path / "eq2") + "/", seed=6, eval_frames=2048, device_data=True,
                  test_frames=512, snr_lo=0, snr_hi=20, snr_step=10)
     out = H.train(hf, verbose=False, run_test=True, rx_params=res["params"])
     hist = out["history"]

@@ -10,7 +10,7 @@
 #   abc:<config>:<what>:<tunes>    the same on another BASELINE config (c3, c4)
 #   ablib:<what>:<lib>             this build against another build of the library (abl/*.so), alternating processes
 #   tl[:tunes]                     in-situ step timeline (tools/steptl.py --config c2)
-#   bench | benchd                 bench.py (defaults) | bench.py --steps 20 --warmup 5 (the driver's arguments)
+#   bench | benchd                 bench.py --full (defaults) | the same with --steps 20 --warmup 5 (the driver's arguments)
 #   kt                             rocprofv3 --kernel-trace --stats of the C2 bench loop  -> kernel_stats.txt
 #   pmc                            separate --pmc passes (never combined with sys/hip/hsa traces) -> pmc_counters.txt, pmc_traffic.json
 #   ktc                            kernel-trace summaries of C3 and C4
@@ -57,8 +57,8 @@ for sec in "$@"; do
 import json,sys
 for ln in sys.stdin:
     r=json.loads(ln); print(r.get('tunes'), 'period_us', r.get('period_us'), [(l.get('name'), l['us'], l.get('gap_before_us')) for l in r['launches']])" ;;
-    bench)  timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; python tools/bench_brief.py $O/bench_n1.json ;;
-    benchd) timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err; python tools/bench_brief.py $O/bench_driver_args.json ;;
+    bench)  timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; python tools/bench_brief.py $O/bench_n1.json ;;
+    benchd) timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_args.json 2> $O/bench_driver_args.err; python tools/bench_brief.py $O/bench_driver_args.json ;;
     kt)
       timeout 900 rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python bench.py --no-cpu-baseline --no-kernel-times --no-other-configs --no-sweep --no-e2e > $O/kt.log 2>&1
       python tools/profile_summary.py $(find $O/kt -name "*.db" | head -1) > $O/kernel_stats.txt 2>&1; rm -rf $O/kt; head -12 $O/kernel_stats.txt | cut -c1-160 ;;
