@@ -55,6 +55,18 @@ class RxBuffers(C.Structure):
                 ("gen_next", c_void_p), ("tuning", c_void_p)]
 
 
+class RxReceiveBuffers(C.Structure):
+    """dccn_rx_receive_buffers"""
+    _fields_ = [("x", c_void_p), ("params", c_void_p), ("x_norm", c_void_p), ("fft_out", c_void_p), ("z", c_void_p),
+                ("packed", c_void_p), ("llr", c_void_p), ("prob", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", c_size_t), ("tuning", c_void_p)]
+
+
+class ReceiveOut(C.Structure):
+    """dccn_receive_out"""
+    _fields_ = [("packed", c_void_p), ("llr", c_void_p), ("prob", c_void_p)]
+
+
 class GenStatic(C.Structure):
     """dccn_gen_static"""
     _fields_ = [("bits_out", c_void_p), ("cell_map", c_void_p), ("const_tab", c_void_p), ("pilot_re", c_float),
@@ -184,6 +196,14 @@ SIGNATURES = {
     "dccn_rx_workspace_size": (_sz, [POINTER(RxShape), _i]),
     "dccn_rx_eval_step": (_i, [POINTER(RxShape), POINTER(RxBuffers), _vp]),
     "dccn_rx_train_step": (_i, [POINTER(RxShape), POINTER(RxBuffers), AdamHParams, _vp]),
+    # receive path (IQ frames -> packed bits / LLRs, no labels)
+    "dccn_demod_decide": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "dccn_dense_decide_supported": (_i, [_i, _i, _i, _i]),
+    "dccn_dense_decide_fwd": (_i, [_vp] * 8 + [_i] * 4 + [_vp]),
+    "dccn_rx_receive_workspace_size": (_sz, [POINTER(RxShape)]),
+    "dccn_rx_receive_fused": (_i, [POINTER(RxShape)]),
+    "dccn_rx_receive_step": (_i, [POINTER(RxShape), POINTER(RxReceiveBuffers), _vp]),
+    "dccn_eq_receive_step": (_i, [POINTER(EqShape), POINTER(EqBuffers), POINTER(ReceiveOut), _vp]),
     "dccn_rx_normalise": (_i, [POINTER(RxShape), POINTER(RxBuffers), _vp]),
     "dccn_rx_graph_create": (_i, [POINTER(RxShape), POINTER(RxBuffers), _i, AdamHParams, _vp, POINTER(c_void_p)]),
     "dccn_rx_graph_launch": (_i, [_vp, _vp]),

@@ -192,6 +192,8 @@ int dense_bwd_grouped_impl(const float* x, const float* dy, const float* w, floa
 int dense_bwd_w_impl(const float* x, const float* dy, float* dw, float* dbias, int M, int K, int N, void* ws, size_t ws_bytes, hipStream_t s, DeferredSlabs* defer = nullptr, int ldx = 0);
 int dense_bwd_x_impl(const float* dy, const float* w, float* dx, int M, int K, int N, hipStream_t s);
 int dense_fwd_impl(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, hipStream_t s, int ldx = 0, int act = 1, bool* act_done = nullptr, const float* aux = nullptr, float* out2 = nullptr, float* out3 = nullptr);
+int decide_impl(const float* z, const float* tailp, unsigned char* packed, float* llr, float* prob, int frames, int D, int nbits, hipStream_t s);
+int dense_decide_impl(const float* x, const float* w, const float* bias, float* z, const float* tailp, unsigned char* packed, float* llr, float* prob, int M, int K, int N, int nbits, hipStream_t s);
 int dense_tail_impl(bool bwd, const float* x, const float* w, const float* bias, float* z, const int32_t* bits, const float* tailp, float* prob, dccn_metrics* metrics, float* dz, float* dtailp, int M, int K, int N, int nbits, const PowerPartials* pp, float* power_out, void* ws, size_t ws_bytes, hipStream_t s, TailFinalizeArgs* defer = nullptr);
 bool dense_tail_ok(const float* x, const float* w, int M, int K, int N, int nbits);
 bool dense_tail_planned(int nbits, bool train, int M = 0, int N = 0);

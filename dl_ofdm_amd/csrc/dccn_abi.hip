@@ -995,6 +995,81 @@ int dense_tail_impl(bool bwd, const float* x, const float* w, const float* bias,
     return DCCN_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// receive path: the decision stage (decide.h) as its own launch and in the dense forward's epilogue
+// ---------------------------------------------------------------------------------------
+static int decide_row_bytes(int D, int nbits) { return (D * nbits + 7) / 8; }
+// the decision stage stores a cell's llr as one vector (float2 at nbits = 2, float4 at nbits = 4) and prob as float2 pairs
+static bool decide_outputs_aligned(const float* llr, const float* prob, int nbits) {
+    const uintptr_t la = nbits == 4 ? 15u : (nbits == 2 ? 7u : 3u);
+    return (reinterpret_cast<uintptr_t>(llr) & la) == 0 && (reinterpret_cast<uintptr_t>(prob) & 7u) == 0;
+}
+
+int decide_impl(const float* z, const float* tailp, unsigned char* packed, float* llr, float* prob, int frames, int D,
+                int nbits, hipStream_t s) {
+    if (!z || !tailp || !packed || frames <= 0 || D <= 0 || nbits < 1 || nbits > 4) return DCCN_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(z) & 7u) != 0 || !decide_outputs_aligned(llr, prob, nbits)) return DCCN_ERR_INVALID_ARG;
+    const int gpr = ceil_div(D, 8), RB = decide_row_bytes(D, nbits);
+    const long long blocks = ceil_div_ll((long long)frames * gpr * 8, kDecideThreads);
+    if (blocks > 0x7fffffffLL) return DCCN_ERR_INVALID_ARG;
+    DCCN_NO_CHAINS();
+    const dim3 grid((unsigned)blocks), blk(kDecideThreads);
+    switch (nbits) {
+        case 1: hipLaunchKernelGGL(demod_decide_kernel<1>, grid, blk, 0, s, z, tailp, packed, llr, prob, frames, D, gpr, RB); break;
+        case 2: hipLaunchKernelGGL(demod_decide_kernel<2>, grid, blk, 0, s, z, tailp, packed, llr, prob, frames, D, gpr, RB); break;
+        case 3: hipLaunchKernelGGL(demod_decide_kernel<3>, grid, blk, 0, s, z, tailp, packed, llr, prob, frames, D, gpr, RB); break;
+        default: hipLaunchKernelGGL(demod_decide_kernel<4>, grid, blk, 0, s, z, tailp, packed, llr, prob, frames, D, gpr, RB); break;
+    }
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+// Dense forward + decision.  The plan mirrors dense_tail_impl launch for launch (few-row tiles, 48x64, 80x64, the ragged
+// two-shape grid), so z -- and with it every decision -- has the bits the evaluation step computes for the same operands.
+// nbits <= 2: ONE launch, z nullable.  nbits >= 3: the 48x64 tiles store z (same k order as the LDS-staged tail of the fused
+// evaluation launch), the stand-alone decision kernel follows; z must be given.
+int dense_decide_impl(const float* x, const float* w, const float* bias, float* z, const float* tailp, unsigned char* packed,
+                      float* llr, float* prob, int M, int K, int N, int nbits, hipStream_t s) {
+    if (!x || !w || !tailp || !packed || M <= 0 || K <= 0 || N <= 0 || (N & 1) || nbits < 1 || nbits > 4)
+        return DCCN_ERR_INVALID_ARG;
+    if (!dense_tail_ok(x, w, M, K, N, nbits)) return DCCN_ERR_INVALID_ARG;
+    if (nbits >= 3 && !z) return DCCN_ERR_INVALID_ARG;
+    if (!decide_outputs_aligned(llr, prob, nbits)) return DCCN_ERR_INVALID_ARG;
+    GemmParams p = gp_zero();
+    p.A = x; p.B = w; p.C = z; p.bias = bias;
+    p.M = M; p.N = N; p.K = K;
+    p.lda = K; p.ldb = N; p.ldc = N;
+    p.klen = round_k(K);
+    p.vecA = 1; p.vecB = 1;
+    if (nbits >= 3) {
+        DCCN_TRY((launch_gemm16<OP_KCONTIG, OP_ICONTIG, 1, 4, 3, 1, 64, 1, 0, TAG_DENSE_FWD, 2>(p, 1, s, tune_smem_min())));
+        return decide_impl(z, tailp, packed, llr, prob, M, N / 2, nbits, s);
+    }
+    DecideEpiParams dq;
+    dq.tailp = tailp; dq.packed = packed; dq.llr = llr; dq.prob = prob; dq.RB = decide_row_bytes(N / 2, nbits);
+    const int variant = ((long long)ceil_div(M, 48) * ceil_div(N, 64) >= 4LL * kCUs) ? 13 : 9;
+    const int few_tiles = ceil_div(M, 16) * (N / 16);
+    const bool few = g_tune[TUNE_FEWROW] && g_tune[TUNE_SKINNY] > 0 && M <= 96 && fewrow_ng_c(p, false) >= 10 &&
+                     few_tiles <= kTailBlocksMax && few_tiles <= dense_tail_max_blocks(M, N);
+    const size_t sm = tune_smem_min();
+    const int rag = (variant == 13 && g_tune[TUNE_DENSE_RAGGED] && M > 80) ? M % 80 : 0;
+    if (rag > 0 && rag <= 32) {
+        const int M1 = M - rag;
+        GemmParams p1 = p, p2 = p;
+        DecideEpiParams d1 = dq, d2 = dq;
+        p1.M = M1;
+        p2.M = rag; p2.A = p.A + (size_t)M1 * p.lda; p2.C = p.C ? p.C + (size_t)M1 * p.ldc : nullptr;
+        d2.packed = dq.packed + (size_t)M1 * dq.RB;
+        d2.llr = dq.llr ? dq.llr + (size_t)M1 * (N / 2) * nbits : nullptr;
+        d2.prob = dq.prob ? dq.prob + (size_t)M1 * (N / 2) * nbits * 2 : nullptr;
+        return nbits == 1 ? launch_dense_decide16_ragged<5, 2, 64, 1, 2>(p1, d1, p2, d2, s, sm)
+                          : launch_dense_decide16_ragged<5, 2, 64, 2, 2>(p1, d1, p2, d2, s, sm);
+    }
+    if (few) return nbits == 1 ? launch_fewrow_decide<1>(p, dq, s) : launch_fewrow_decide<2>(p, dq, s);
+    if (variant == 13) return nbits == 1 ? launch_dense_decide16<5, 64, 1, 2>(p, dq, s, sm) : launch_dense_decide16<5, 64, 2, 2>(p, dq, s, sm);
+    return nbits == 1 ? launch_dense_decide16<3, 64, 1, 2>(p, dq, s, sm) : launch_dense_decide16<3, 64, 2, 2>(p, dq, s, sm);
+}
+
 // prep = false: the per-step bookkeeping (alpha, beta powers, global_step) already rode on an earlier kernel of the step
 int adam_impl(float* param, const float* grad, float* m, float* v, const float* reg_coef,
                      const float* reg_gate, dccn_adam_state* st, dccn_adam_hparams hp, long long n, hipStream_t s,
@@ -1424,6 +1499,45 @@ static int rx_step_impl(const dccn_rx_shape* sh, const dccn_rx_buffers* b, bool 
     return DCCN_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// receive step: R0 -> C-Conv forward -> dense + decision (no labels, no loss, no metrics)
+// ---------------------------------------------------------------------------------------
+static size_t rx_receive_ws_bytes(const dccn_rx_shape* sh) {
+    const RxLayout L = rx_layout(sh);
+    return align_up(carve_size(0, L.ws_norm), 256);
+}
+// the dense forward + decision run as ONE launch for this shape under the current knobs (then z may be NULL)
+static bool rx_receive_fused(const dccn_rx_shape* sh, const float* fft_out, const float* wd) {
+    const RxLayout L = rx_layout(sh);
+    return sh->nbits <= 2 && dense_tail_planned(sh->nbits, false, sh->batch, L.dN) &&
+           dense_tail_ok(fft_out, wd, sh->batch, L.dK, L.dN, sh->nbits);
+}
+static int rx_receive_impl(const dccn_rx_shape* sh, const dccn_rx_receive_buffers* b, hipStream_t s) {
+    if (!shape_ok(sh) || !b) return DCCN_ERR_INVALID_ARG;
+    const TuneScope tune(b->tuning);
+    if (!b->x || !b->params || !b->x_norm || !b->fft_out || !b->packed) return DCCN_ERR_INVALID_ARG;
+    if (!b->workspace || b->workspace_bytes < rx_receive_ws_bytes(sh)) return DCCN_ERR_WORKSPACE;
+    const RxLayout L = rx_layout(sh);
+    const float* P = b->params;
+    const bool via_tail_plan = dense_tail_planned(sh->nbits, false, sh->batch, L.dN) &&
+                               dense_tail_ok(b->fft_out, P + L.o_dense_w, sh->batch, L.dK, L.dN, sh->nbits);
+    if (!(via_tail_plan && sh->nbits <= 2) && !b->z) return DCCN_ERR_INVALID_ARG;
+    Carver c(b->workspace, b->workspace_bytes);
+    void* ws_norm = c.take<char>(L.ws_norm);
+    dccn_adam_hparams hp;
+    memset(&hp, 0, sizeof(hp));
+    // R0, R1: the launches of the evaluation step
+    DCCN_TRY(norm_impl(b->x, b->x_norm, nullptr, nullptr, false, nullptr, sh->batch, L.cols, 1e-9f, 8.0f, nullptr, hp, ws_norm,
+                       L.ws_norm, s, 0));
+    DCCN_TRY(cconv_fwd_impl(b->x_norm, P + L.o_conv_w, P + L.o_conv_b, b->fft_out, L.rows, sh->kin, sh->F, s));
+    // R2 + decision: the dense forward runs the plan the evaluation step would take for this shape (same bits in z)
+    if (via_tail_plan)
+        return dense_decide_impl(b->fft_out, P + L.o_dense_w, P + L.o_dense_b, b->z, P + L.o_tail, b->packed, b->llr, b->prob,
+                                 sh->batch, L.dK, L.dN, sh->nbits, s);
+    DCCN_TRY(dense_fwd_impl(b->fft_out, P + L.o_dense_w, P + L.o_dense_b, b->z, sh->batch, L.dK, L.dN, s));
+    return decide_impl(b->z, P + L.o_tail, b->packed, b->llr, b->prob, sh->batch, sh->D, sh->nbits, s);
+}
+
 int eq_monitor_blocks(int B, int K) {
     long long n = ceil_div_ll((long long)B * K * 2, 256);
     if (n > 256) n = 256;
@@ -1740,6 +1854,33 @@ int dccn_dense_tail_fwd_bwd(const float* x, const float* w, const float* bias, f
                             int K, int N, int nbits, void* workspace, size_t workspace_bytes, dccn_stream_t stream) {
     return dense_tail_impl(true, x, w, bias, z, bits, tailp, prob, metrics, dz, dtailp, M, K, N, nbits, nullptr, nullptr,
                            workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int dccn_demod_decide(const float* z, const float* tailp, unsigned char* packed, float* llr, float* prob, int frames, int D,
+                      int nbits, dccn_stream_t stream) {
+    return decide_impl(z, tailp, packed, llr, prob, frames, D, nbits, (hipStream_t)stream);
+}
+int dccn_dense_decide_supported(int M, int K, int N, int nbits) {
+    const TuneScope tune;
+    return (nbits >= 1 && nbits <= 4 && N > 0 && (N & 1) == 0 && dense_tail_shape_ok(M, K, N, nbits)) ? 1 : 0;
+}
+int dccn_dense_decide_fwd(const float* x, const float* w, const float* bias, float* z, const float* tailp,
+                          unsigned char* packed, float* llr, float* prob, int M, int K, int N, int nbits,
+                          dccn_stream_t stream) {
+    const TuneScope tune;
+    return dense_decide_impl(x, w, bias, z, tailp, packed, llr, prob, M, K, N, nbits, (hipStream_t)stream);
+}
+size_t dccn_rx_receive_workspace_size(const dccn_rx_shape* shape) {
+    if (!shape_ok(shape)) return 0;
+    return rx_receive_ws_bytes(shape);
+}
+int dccn_rx_receive_fused(const dccn_rx_shape* shape) {
+    if (!shape_ok(shape)) return 0;
+    const TuneScope tune;
+    return rx_receive_fused(shape, nullptr, nullptr) ? 1 : 0;
+}
+int dccn_rx_receive_step(const dccn_rx_shape* shape, const dccn_rx_receive_buffers* buf, dccn_stream_t stream) {
+    return rx_receive_impl(shape, buf, (hipStream_t)stream);
 }
 
 int dccn_tail_param_count(int nbits) {

@@ -73,6 +73,11 @@ int dccn_eq_rx_fold(const dccn_eq_shape* shape, const float* rx_params, float* o
 int dccn_eq_eval_step(const dccn_eq_shape* shape, const dccn_eq_buffers* buf, dccn_stream_t stream) {
     return eq_step_impl(shape, buf, false, dccn_adam_hparams(), (hipStream_t)stream);
 }
+int dccn_eq_receive_step(const dccn_eq_shape* shape, const dccn_eq_buffers* buf, const dccn_receive_out* out,
+                         dccn_stream_t stream) {
+    if (!out || !out->packed) return DCCN_ERR_INVALID_ARG;
+    return eq_step_impl(shape, buf, false, dccn_adam_hparams(), (hipStream_t)stream, out);
+}
 int dccn_eq_train_step(const dccn_eq_shape* shape, const dccn_eq_buffers* buf, dccn_adam_hparams hp,
                        dccn_stream_t stream) {
     return eq_step_impl(shape, buf, true, hp, (hipStream_t)stream);

@@ -168,12 +168,16 @@ static void eq_opt_dense(EqOptBuilder& ob, const EqDims& d, int i, const Deferre
     else ob.plain(d.o[i + 1], d.sz[i + 1], uni);
 }
 
+// ro != nullptr: the receive path (dccn_eq_receive_step): the evaluation step's forward with the tail section replaced by the
+// decision stage (decide.h) -- no labels, no metrics; bits / metrics / prob / tx_power of `b` are not touched
 static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool train, dccn_adam_hparams hp,
-                        hipStream_t s) {
+                        hipStream_t s, const dccn_receive_out* ro = nullptr) {
     if (!eq_shape_ok(sh) || !b) return DCCN_ERR_INVALID_ARG;
     const TuneScope tune(b->tuning);
-    if (!b->x || !b->bits || !b->eq_params || !b->rx_params || !b->out_eq || !b->chest || !b->metrics)
+    if (!b->x || (!ro && !b->bits) || !b->eq_params || !b->rx_params || !b->out_eq || !b->chest || (!ro && !b->metrics))
         return DCCN_ERR_INVALID_ARG;
+    if (ro && (train || !ro->packed)) return DCCN_ERR_INVALID_ARG;
+    if (ro && tl_chain.G > 1) return DCCN_ERR_UNSUPPORTED;
     if (train && (!b->eq_grads || !b->adam_m || !b->adam_v || !b->adam)) return DCCN_ERR_INVALID_ARG;
     if (!b->workspace || b->workspace_bytes < eq_ws_bytes(sh, train ? 1 : 0)) return DCCN_ERR_WORKSPACE;
     const EqDims d = eq_dims(sh);
@@ -225,7 +229,7 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
     if (b->x_prenormalised != 0 && !pre) return DCCN_ERR_INVALID_ARG;
     const int nslot = b->norm_slot ? 1 : 0;
     if (pre) norm_power_partials(B, ncols, w.ws_norm, w.n_norm, b->x, w.x_norm, &pp, nslot);
-    else DCCN_TRY(norm_impl(b->x, w.x_norm, nullptr, nullptr, b->tx_power != nullptr, &pp, B, ncols, 1e-9f, 8.0f,
+    else DCCN_TRY(norm_impl(b->x, w.x_norm, nullptr, nullptr, !ro && b->tx_power != nullptr, &pp, B, ncols, 1e-9f, 8.0f,
                             train ? b->adam : nullptr, hp, w.ws_norm, w.n_norm, s, nslot));
     // model.py:363 layer_norm, :369 dense, :378 C-Conv "DFT"; the expansion of the :428 smoothing C-Conv (S x K, same)
     // into the block-Toeplitz matrix of a dense layer depends on the parameters only and shares the launch
@@ -357,6 +361,17 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
         }
         return DCCN_OK;
     };
+    if (ro) {
+        // the same choice between the one-launch form and dense + stand-alone kernel as tail_section makes: same bits in z
+        const int nbits = sh->nbits;
+        const bool few_tail = few_rx && nbits <= 2 && dense_tail_ok(rxA, rxW, B, rxK, L.dN, nbits);
+        if ((few_tail || !few_rx) && dense_tail_planned(nbits, false, B, L.dN) && dense_tail_ok(rxA, rxW, B, rxK, L.dN, nbits))
+            return dense_decide_impl(rxA, rxW, rxb, nbits >= 3 ? w.z : nullptr, Q + L.o_tail, ro->packed, ro->llr, ro->prob, B, rxK,
+                                     L.dN, nbits, s);
+        if (folded) DCCN_TRY(dense_fwd_impl(b->out_eq, Mf, Mf + (size_t)fK * L.dN, w.z, B, fK, L.dN, s));
+        else DCCN_TRY(dense_fwd_impl(w.fft, Q + L.o_dense_w, Q + L.o_dense_b, w.z, B, L.dK, L.dN, s));
+        return decide_impl(w.z, Q + L.o_tail, ro->packed, ro->llr, ro->prob, B, d.D, nbits, s);
+    }
     if (tl_chain.G == 1) {
         DCCN_TRY(tail_section(sh->nbits, &fin[0]));
         n_class = 1;

@@ -109,6 +109,64 @@ __device__ __forceinline__ void fewrow_tile(const GemmParams& p, const int L, co
     }
 }
 
+// What fewrow_tail_tile and fewrow_decide_tile share, in ONE place (z of the receive path must have the evaluation step's
+// bits): tile mapping + every operand of the wave requested up front (forward: A k-contiguous, B = W[k][n]) ...
+template <int NG>
+struct FewrowOperands {
+    float4 a[NG], b[NG];
+    int n0, m0;
+};
+template <int NG>
+__device__ __forceinline__ void fewrow_load_fwd(const GemmParams& p, const int L, const int T, FewrowOperands<NG>& o) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane & 15, kq = lane >> 4;
+    const int ntm = (p.M + 15) >> 4;
+    int tile;
+    {
+        const int xcd = L & 7, j = L >> 3, q = T >> 3, r = T & 7;
+        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
+    }
+    const int n0 = (tile / ntm) * 16, m0 = (tile % ntm) * 16;
+    o.n0 = n0;
+    o.m0 = m0;
+    const int row = min(m0 + c, p.M - 1);
+    const int G = p.K >> 4;
+    const float* Ap = p.A + (size_t)row * p.lda + 4 * kq;
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+        const int g = w + 4 * i;
+        const float4 t = *reinterpret_cast<const float4*>(Ap + 16 * min(g, G - 1));
+        o.a[i] = g < G ? t : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const float* Bp = p.B + (size_t)(4 * kq) * p.ldb + n0 + c;
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+        const float* q = Bp + (size_t)(16 * min(w + 4 * i, G - 1)) * p.ldb;
+        o.b[i].x = q[0];
+        o.b[i].y = q[(size_t)p.ldb];
+        o.b[i].z = q[(size_t)2 * p.ldb];
+        o.b[i].w = q[(size_t)3 * p.ldb];
+    }
+}
+// ... and the MFMA chain + the meeting of the four k quarters in LDS (fixed order): the value of tile row 4 kq + w,
+// column lane % 16, without the bias
+template <int NG>
+__device__ __forceinline__ float fewrow_mfma_meet(const FewrowOperands<NG>& o, float (&xch)[4][4][64]) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(o.a[i].x, o.b[i].x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(o.a[i].y, o.b[i].y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(o.a[i].z, o.b[i].z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(o.a[i].w, o.b[i].w, acc, 0, 0, 0);
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) xch[w][r][lane] = acc[r];
+    __syncthreads();
+    return ((xch[0][w][lane] + xch[1][w][lane]) + xch[2][w][lane]) + xch[3][w][lane];
+}
+
 // The same tile with the demodulation tail (R3-R6 forward, and backward to dz when BWD) behind it, for NB <= 2
 // (dev/py/model.py:1278-1291 on the frozen receiver of the equaliser step): after the k quarters have met, wave w holds
 // row 4 kq + w of the tile, lanes 2d / 2d+1 its columns 2d (I) and 2d+1 (Q) of data cell d -- the pair swaps halves on the
@@ -121,32 +179,9 @@ __device__ __forceinline__ void fewrow_tail_tile(const GemmParams& p, const Tail
     __shared__ __attribute__((aligned(8))) float red[tail_reduce_lds_floats<NB, BWD>(256)];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int c = lane & 15, kq = lane >> 4;
-    const int ntm = (p.M + 15) >> 4;
-    int tile;
-    {
-        const int xcd = L & 7, j = L >> 3, q = T >> 3, r = T & 7;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-    }
-    const int n0 = (tile / ntm) * 16, m0 = (tile % ntm) * 16;
-    const int row = min(m0 + c, p.M - 1);
-    const int G = p.K >> 4;
-    float4 a[NG], b[NG];
-    const float* Ap = p.A + (size_t)row * p.lda + 4 * kq;
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {
-        const int g = w + 4 * i;
-        const float4 t = *reinterpret_cast<const float4*>(Ap + 16 * min(g, G - 1));
-        a[i] = g < G ? t : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    const float* Bp = p.B + (size_t)(4 * kq) * p.ldb + n0 + c;
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {
-        const float* q = Bp + (size_t)(16 * min(w + 4 * i, G - 1)) * p.ldb;
-        b[i].x = q[0];
-        b[i].y = q[(size_t)p.ldb];
-        b[i].z = q[(size_t)2 * p.ldb];
-        b[i].w = q[(size_t)3 * p.ldb];
-    }
+    FewrowOperands<NG> ops;
+    fewrow_load_fwd<NG>(p, L, T, ops);
+    const int n0 = ops.n0, m0 = ops.m0;
     // this lane's cell: row orow, data cell (n0 + c) / 2 (even lanes run it); its labels and bias are requested now
     const int orow = m0 + 4 * kq + w, ocol = n0 + c;
     const int Dn = p.N >> 1;
@@ -156,18 +191,7 @@ __device__ __forceinline__ void fewrow_tail_tile(const GemmParams& p, const Tail
 #pragma unroll
     for (int j = 0; j < NB; ++j) lab[0][j] = tp.bits[cell * NB + j];
     const float bj = p.bias != nullptr ? p.bias[ocol] : 0.f;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].x, b[i].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].y, b[i].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].z, b[i].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i].w, b[i].w, acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) xch[w][r][lane] = acc[r];
-    __syncthreads();
-    const float o = (((xch[0][w][lane] + xch[1][w][lane]) + xch[2][w][lane]) + xch[3][w][lane]) + bj;
+    const float o = fewrow_mfma_meet<NG>(ops, xch) + bj;
     if (p.C != nullptr && orow < p.M) p.C[(size_t)orow * p.ldc + ocol] = o;          // z, when the caller wants it
     const float partner = __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, o), 0));      // quad_perm [1,0,3,2]
     const float z0[1] = {o}, z1[1] = {partner};
@@ -372,6 +396,55 @@ static int launch_fewrow_tail(const GemmParams& p, const TailEpiParams& tp, hipS
         case 18: DCCN_LAUNCH_CHAINS_Z((fewrow_tail_kernel<18, NB, BWD>), dim3(T), dim3(256), 0, s, p, tp); break;
         case 14: DCCN_LAUNCH_CHAINS_Z((fewrow_tail_kernel<14, NB, BWD>), dim3(T), dim3(256), 0, s, p, tp); break;
         case 10: DCCN_LAUNCH_CHAINS_Z((fewrow_tail_kernel<10, NB, BWD>), dim3(T), dim3(256), 0, s, p, tp); break;
+        default: return DCCN_ERR_INVALID_ARG;
+    }
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+// The same tile with the decision stage of the receive path behind it (decide.h), NB <= 2: the loads, the MFMA order and the
+// exchange are those of fewrow_tail_tile, so z has the same bits.  The even lanes of a DPP row hold the 8 cells of tile row
+// 4 kq + w: NB bytes, formed by an OR over the row and stored by its first NB lanes.
+template <int NG, int NB>
+__device__ __forceinline__ void fewrow_decide_tile(const GemmParams& p, const DecideEpiParams& dq, const int L, const int T) {
+    static_assert(NB == 1 || NB == 2, "register layout: BPSK / QPSK");
+    __shared__ float xch[4][4][64];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int c = lane & 15, kq = lane >> 4;
+    FewrowOperands<NG> ops;
+    fewrow_load_fwd<NG>(p, L, T, ops);
+    const int n0 = ops.n0, m0 = ops.m0;
+    const int orow = m0 + 4 * kq + w, ocol = n0 + c;
+    const int Dn = p.N >> 1;
+    const bool live = orow < p.M && (c & 1) == 0;
+    const long long cell = (long long)min(orow, p.M - 1) * Dn + (ocol >> 1);
+    const float bj = p.bias != nullptr ? p.bias[ocol] : 0.f;
+    const float o = fewrow_mfma_meet<NG>(ops, xch) + bj;
+    if (p.C != nullptr && orow < p.M) p.C[(size_t)orow * p.ldc + ocol] = o;          // z, when the caller wants it
+    const float partner = __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, o), 0));      // quad_perm [1,0,3,2]
+    const float z0[1] = {o}, z1[1] = {partner};
+    float* const pc[1] = {(dq.prob != nullptr && live) ? dq.prob + cell * NB * 2 : nullptr};
+    float* const lc[1] = {(dq.llr != nullptr && live) ? dq.llr + cell * NB : nullptr};
+    unsigned hard[1];
+    decide_cells<NB, 1>(z0, z1, dq.tailp, pc, lc, hard);
+    unsigned v = live ? hard[0] << (NB * (7 - (c >> 1))) : 0u;
+    v = row16_or(v);
+    const int b0 = (n0 >> 4) * NB;
+    if (orow < p.M && c < NB && b0 + c < dq.RB)
+        dq.packed[(size_t)orow * dq.RB + b0 + c] = (unsigned char)((v >> (8 * (NB - 1 - c))) & 0xffu);
+}
+template <int NG, int NB>
+__global__ __launch_bounds__(256) void fewrow_decide_kernel(const GemmParams p, const DecideEpiParams dq) {
+    fewrow_decide_tile<NG, NB>(p, dq, (int)blockIdx.x, (int)gridDim.x);
+}
+template <int NB>
+static int launch_fewrow_decide(const GemmParams& p, const DecideEpiParams& dq, hipStream_t s) {
+    const int T = ceil_div(p.M, 16) * (p.N / 16);
+    DCCN_NO_CHAINS();
+    switch (fewrow_ng_c(p, false)) {
+        case 18: hipLaunchKernelGGL((fewrow_decide_kernel<18, NB>), dim3(T), dim3(256), 0, s, p, dq); break;
+        case 14: hipLaunchKernelGGL((fewrow_decide_kernel<14, NB>), dim3(T), dim3(256), 0, s, p, dq); break;
+        case 10: hipLaunchKernelGGL((fewrow_decide_kernel<10, NB>), dim3(T), dim3(256), 0, s, p, dq); break;
         default: return DCCN_ERR_INVALID_ARG;
     }
     DCCN_LAUNCH_CHECK();

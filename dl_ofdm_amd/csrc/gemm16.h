@@ -21,9 +21,13 @@
 // EPI_TAIL: the dense forward's epilogue runs the demodulation tail (R3-R6 forward and backward, tail.h tail_cell) on
 // the output tile while it is in registers -- adjacent lanes hold the I and Q column of one data cell -- and writes
 // dz / prob / the per-block metric and gradient slabs instead of (or besides) z.
+// EPI_DECIDE (receive path, BPSK / QPSK): the same register layout, but only the forward of the tail and the hard decision
+// (decide.h decide_cells): packed bits / llr / prob leave the launch, z need not exist in memory.  A 64-column tile holds
+// 32 cells = 4 * nbits whole bytes per row, so tiles never share a byte.
 #pragma once
 #include "gemm_f32_mfma.h"
 #include "tail.h"
+#include "decide.h"
 
 // GEMM16_ABL: timing ablations for experiments (results are wrong by construction when set):
 // bit0 no global loads in the k-loop, bit1 no LDS stores, bit2 no per-k-tile barrier, bit3 no fragment re-reads,
@@ -36,7 +40,7 @@ namespace dccn {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-enum Epilogue16 : int { EPI_STORE = 0, EPI_TAIL = 1 };
+enum Epilogue16 : int { EPI_STORE = 0, EPI_TAIL = 1, EPI_DECIDE = 2 };
 
 struct TailEpiParams {
     const int32_t* bits;            // [M, N/2, NB]
@@ -204,7 +208,7 @@ struct Cfg16 {
 template <int KA, int KB, int WGM, int WGN, int TM, int TN, int BK, int KS, int COLSUM, int EPI, int NB, bool BWD,
           int PD = 1>
 __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiParams& tp, const int L, const int T,
-                                             const int z, const int slab) {
+                                             const int z, const int slab, const DecideEpiParams* dp = nullptr) {
     static_assert(WGM * WGN == 4, "four waves per wave set");
     using CF = Cfg16<KA, KB, WGM, WGN, TM, TN, BK, KS>;
     using TA = typename CF::TA;
@@ -287,8 +291,8 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
     }
 
     // EPI_TAIL: this lane's bias values are requested before the k-loop as well
-    float bjv[(EPI == EPI_TAIL) ? TN : 1];
-    if constexpr (EPI == EPI_TAIL) {
+    float bjv[(EPI != EPI_STORE) ? TN : 1];
+    if constexpr (EPI != EPI_STORE) {
 #pragma unroll
         for (int b = 0; b < TN; ++b) bjv[b] = p.bias != nullptr ? p.bias[min(n0 + wn0 + b * 16 + l15, p.N - 1)] : 0.f;
     }
@@ -531,6 +535,97 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
                     }
                 }
             }
+        }
+    } else if constexpr (EPI == EPI_DECIDE) {
+        // ---- decision stage on the register layout of the fused tail (lanes 2d, 2d+1 = columns I, Q of cell d) ----
+        static_assert(KS == 1 && NB <= 2 && WGM == 1 && WGN == 4 && TN == 1, "decision epilogue: 16 TM x 64 tiles, BPSK / QPSK");
+        const DecideEpiParams& dq = *dp;
+        const int odd = lane & 1;
+        const int Dn = p.N >> 1;
+        constexpr int NC = TM * 2;
+        float cz0[NC], cz1[NC];
+        bool cvalid[NC];
+        float* cprob[NC];
+        float* cllr[NC];
+        int crl[NC];
+#pragma unroll
+        for (int a = 0; a < TM; ++a) {
+            const int col = n0 + wn0 + l15;
+            const int colc = min(col, p.N - 1);
+            const float bj = bjv[0];
+            // (explicit scalars: an array indexed by a lane-dependent value would become a stack object)
+            const float o0 = acc[a][0][0] + bj, o1 = acc[a][0][1] + bj, o2 = acc[a][0][2] + bj, o3 = acc[a][0][3] + bj;
+            const float t0 = __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, o0), 0));
+            const float t1 = __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, o1), 0));
+            const float t2 = __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, o2), 0));
+            const float t3 = __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, o3), 0));
+            if (p.C != nullptr) {
+                const int row = m0 + wm0 + a * 16 + 4 * kg;
+                if (col < p.N) {
+                    if (row + 0 < p.M) p.C[(size_t)(row + 0) * p.ldc + col] = o0;
+                    if (row + 1 < p.M) p.C[(size_t)(row + 1) * p.ldc + col] = o1;
+                    if (row + 2 < p.M) p.C[(size_t)(row + 2) * p.ldc + col] = o2;
+                    if (row + 3 < p.M) p.C[(size_t)(row + 3) * p.ldc + col] = o3;
+                }
+            }
+            // the even lane takes the cells of registers 0, 1, the odd lane those of registers 2, 3
+            const float mine0 = odd ? o2 : o0, mine1 = odd ? o3 : o1;
+            const float othr0 = odd ? t2 : t0, othr1 = odd ? t3 : t1;
+#pragma unroll
+            for (int cc = 0; cc < 2; ++cc) {
+                const int ci = a * 2 + cc;
+                const float mine = cc ? mine1 : mine0, othr = cc ? othr1 : othr0;
+                cz0[ci] = odd ? othr : mine;
+                cz1[ci] = odd ? mine : othr;
+                const int rl = wm0 + a * 16 + 4 * kg + (odd ? 2 : 0) + cc;
+                const int row = m0 + rl;
+                const bool ok = row < p.M && col < p.N;
+                const long long cell = (long long)min(row, p.M - 1) * Dn + (colc >> 1);
+                crl[ci] = rl;
+                cvalid[ci] = ok;
+                cprob[ci] = (dq.prob != nullptr && ok) ? dq.prob + cell * NB * 2 : nullptr;
+                cllr[ci] = (dq.llr != nullptr && ok) ? dq.llr + cell * NB : nullptr;
+            }
+        }
+        unsigned hard[NC];
+        {
+            // (at most 8 cells share one interleaved instruction stream, as in the fused tail)
+            constexpr int TW = NC <= 8 ? NC : (NC % 8 == 0 ? 8 : (NC % 6 == 0 ? 6 : (NC % 5 == 0 ? 5 : 4)));
+            static_assert(NC % TW == 0, "decision batches");
+#pragma unroll
+            for (int g0 = 0; g0 < NC; g0 += TW) {
+                float a0[TW], a1[TW];
+                float* pc[TW];
+                float* lc[TW];
+                unsigned hd[TW];
+#pragma unroll
+                for (int u = 0; u < TW; ++u) { a0[u] = cz0[g0 + u]; a1[u] = cz1[g0 + u]; pc[u] = cprob[g0 + u]; lc[u] = cllr[g0 + u]; }
+                decide_cells<NB, TW>(a0, a1, dq.tailp, pc, lc, hd);
+#pragma unroll
+                for (int u = 0; u < TW; ++u) hard[g0 + u] = hd[u];
+            }
+        }
+        // a wave's 16 columns are 8 cells = NB bytes of a row; the even lanes of a DPP row hold one tile row, the odd lanes
+        // another: both are formed by one OR over the row (low / high half-word), then the block's four waves meet in LDS (the
+        // k-loop ended with a barrier: the tile buffers are free) and one thread per tile row stores its 4 * NB bytes
+        unsigned short* sb = reinterpret_cast<unsigned short*>(smem);          // [BM][4]
+#pragma unroll
+        for (int ci = 0; ci < NC; ++ci) {
+            unsigned v = cvalid[ci] ? hard[ci] << (NB * (7 - (l15 >> 1))) : 0u;
+            v = row16_or(v << (16 * odd));
+            if (l15 < 2) sb[crl[ci] * 4 + wid] = (unsigned short)(odd ? (v >> 16) : (v & 0xffffu));
+        }
+        __syncthreads();
+        if (tid < BM && m0 + tid < p.M) {
+            unsigned word[2] = {0u, 0u};
+#pragma unroll
+            for (int wv = 0; wv < 4; ++wv) {
+                const unsigned hv = sb[tid * 4 + wv];
+                if constexpr (NB == 1) word[0] |= (hv & 0xffu) << (8 * wv);
+                else word[wv >> 1] |= (((hv >> 8) & 0xffu) | ((hv & 0xffu) << 8)) << (16 * (wv & 1));
+            }
+            const int b0 = (n0 >> 4) * NB;
+            store_row_bytes(dq.packed + (size_t)(m0 + tid) * dq.RB + b0, word, min(4 * NB, dq.RB - b0));
         }
     } else {
         // ---- fused demodulation tail ------------------------------------------------------------------------
@@ -862,6 +957,50 @@ static int launch_bwd_w16_finalize(const GemmParams& p, int splits, const TailFi
     DCCN_NO_CHAINS();
     hipLaunchKernelGGL(kern, dim3(gemm_blocks + tail_finalize_blocks(fin.P)), dim3(256), smem, s, p, tiles, gemm_blocks,
                        fin);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+// dense forward + decision stage (receive path, NB <= 2): the tile shapes of the fused dense + tail launch
+template <int TM, int BK, int NB, int PD>
+__global__ __launch_bounds__(256) void dense_decide_kernel(const GemmParams p, const DecideEpiParams dq) {
+    TailEpiParams none{};
+    gemm16_block<OP_KCONTIG, OP_ICONTIG, 1, 4, TM, 1, BK, 1, 0, EPI_DECIDE, NB, false, PD>(p, none, (int)blockIdx.x, (int)gridDim.x, 0,
+                                                                                         0, &dq);
+}
+template <int TM, int BK, int NB, int PD>
+static int launch_dense_decide16(const GemmParams& p, const DecideEpiParams& dq, hipStream_t s, size_t smem_min = 0) {
+    using CF = Cfg16<OP_KCONTIG, OP_ICONTIG, 1, 4, TM, 1, BK, 1>;
+    auto kern = dense_decide_kernel<TM, BK, NB, PD>;
+    size_t smem = CF::smem_bytes(0);
+    if (smem < smem_min) smem = smem_min;
+    DCCN_TRY(set_smem_attr(kern, smem));
+    DCCN_NO_CHAINS();
+    hipLaunchKernelGGL(kern, dim3(ceil_div(p.N, CF::BN) * ceil_div(p.M, CF::BM)), dim3(256), smem, s, p, dq);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+// ... and the two-shape grid of dense_tail_ragged_kernel (a short last row tile of a large layer)
+template <int TM1, int TM2, int BK, int NB, int PD>
+__global__ __launch_bounds__(256) void dense_decide_ragged_kernel(const GemmParams p1, const DecideEpiParams d1, const GemmParams p2,
+                                                                  const DecideEpiParams d2, const int T1, const int T2) {
+    const int b = (int)blockIdx.x;
+    TailEpiParams none{};
+    if (b < T1) gemm16_block<OP_KCONTIG, OP_ICONTIG, 1, 4, TM1, 1, BK, 1, 0, EPI_DECIDE, NB, false, PD>(p1, none, b, T1, 0, 0, &d1);
+    else gemm16_block<OP_KCONTIG, OP_ICONTIG, 1, 4, TM2, 1, BK, 1, 0, EPI_DECIDE, NB, false, PD>(p2, none, b - T1, T2, 0, 0, &d2);
+}
+template <int TM1, int TM2, int BK, int NB, int PD>
+static int launch_dense_decide16_ragged(const GemmParams& p1, const DecideEpiParams& d1, const GemmParams& p2,
+                                        const DecideEpiParams& d2, hipStream_t s, size_t smem_min = 0) {
+    using C1 = Cfg16<OP_KCONTIG, OP_ICONTIG, 1, 4, TM1, 1, BK, 1>;
+    using C2 = Cfg16<OP_KCONTIG, OP_ICONTIG, 1, 4, TM2, 1, BK, 1>;
+    auto kern = dense_decide_ragged_kernel<TM1, TM2, BK, NB, PD>;
+    size_t smem = C1::smem_bytes(0) > C2::smem_bytes(0) ? C1::smem_bytes(0) : C2::smem_bytes(0);
+    if (smem < smem_min) smem = smem_min;
+    DCCN_TRY(set_smem_attr(kern, smem));
+    const int T1 = ceil_div(p1.N, 64) * ceil_div(p1.M, 16 * TM1), T2 = ceil_div(p2.N, 64) * ceil_div(p2.M, 16 * TM2);
+    DCCN_NO_CHAINS();
+    hipLaunchKernelGGL(kern, dim3(T1 + T2), dim3(256), smem, s, p1, d1, p2, d2, T1, T2);
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
 }

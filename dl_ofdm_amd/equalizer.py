@@ -69,6 +69,7 @@ class _FusedPlan:
             self.ws = A.empty(arena, self.nws, dtype=torch.uint8, device=dev)
         self.buffers = self._buffers()
         self._partner = None
+        self._receive_out: Dict[str, torch.Tensor] = {}      # receive(): packed / llr / prob, allocated on first use
         self.graphs: Dict[object, C.c_void_p] = {}
 
     def _buffers(self, x_next=None, pre: int = 0, slot: int = 0, virt: int = 0, gen_rides: bool = False, monitor: int = 0) -> EqBuffers:
@@ -146,6 +147,29 @@ class _FusedPlan:
                                            C.byref(g)), "dccn_eq_graph_create")
             self.graphs[key] = g
         check(lib.dccn_rx_graph_launch(self.graphs[key], self._stream()), "dccn_rx_graph_launch")
+
+    def receive(self, want_llr: bool = False, want_prob: bool = False):
+        """``dccn_eq_receive_step`` on the frames in ``self.x``: (packed, llr or None, prob or None), device tensors this plan
+        keeps.  The step normalises into the shared workspace, so a batch normalised ahead is gone afterwards."""
+        from ._lib import ReceiveOut
+        from .receive import row_bytes
+        tr = self.tr
+        D, nbits, dev = int(tr.ofdmobj.frame_size), int(tr.FLAGS.nbits), tr.device
+        out = self._receive_out
+        if "packed" not in out:
+            out["packed"] = torch.zeros(self.batch, row_bytes(D, nbits), dtype=torch.uint8, device=dev)
+        if want_llr and "llr" not in out:
+            out["llr"] = torch.empty(self.batch, D, nbits, dtype=torch.float32, device=dev)
+        if want_prob and "prob" not in out:
+            out["prob"] = torch.empty(self.batch, D, nbits, 2, dtype=torch.float32, device=dev)
+        llr = out["llr"] if want_llr else None
+        prob = out["prob"] if want_prob else None
+        ro = ReceiveOut(out["packed"].data_ptr(), None if llr is None else llr.data_ptr(),
+                        None if prob is None else prob.data_ptr())
+        self._ahead()[self.ws.data_ptr()] = None
+        check(tr.lib.dccn_eq_receive_step(C.byref(self.shape), C.byref(self.buffers), C.byref(ro), self._stream()),
+              "dccn_eq_receive_step")
+        return out["packed"], llr, prob
 
     def close(self):
         for g in self.graphs.values():
@@ -351,6 +375,13 @@ class EqualizerTrainer:
             return self._fused_step(x, bits, False, graph)
         ce, mbuf, tx_power, _, _, _, _ = self._forward(x, bits)
         return self._metrics(mbuf, tx_power)
+
+    def receive(self, x, want_llr: bool = False, want_prob: bool = False):
+        """Raw frames -> packed bits (and LLRs) through the equaliser + frozen receiver, no labels
+        (``dccn_eq_receive_step``; see :mod:`dl_ofdm_amd.receive` for the layout).  ``resident(batch).out_eq`` / ``.chest``
+        hold what ``eval_step`` writes for the same frames."""
+        from .receive import chain_receive
+        return chain_receive(self, x, want_llr, want_prob)
 
     def adam(self) -> dict:
         s = self.adam_state.cpu().numpy()

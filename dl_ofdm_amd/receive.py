@@ -1,0 +1,144 @@
+"""The label-free receive path: raw IQ frames -> packed bits (and LLRs for a channel decoder behind it).
+
+What ``sess.run(outputs, {x: frames})`` is in the reference (dev/py/test_v1/test_ofdm_cdnn_awgn.py:113-118; ``output:0``
+depends on ``tx_ofdm:0`` alone) plus the argmax of dev/py/ofdmreceiver_np.py:166, as one launch sequence of the library
+(``dccn_rx_receive_step``: R0 -> C-Conv forward -> dense forward with the decision stage in its epilogue): no label tensor,
+no cross entropy, no confusion counts, no metrics record.
+
+Row layout of ``packed`` ``uint8 [frames, ceil(D * nbits / 8)]``: row ``f`` is ``numpy.packbits(hard[f].reshape(-1))`` with
+``hard [frames, D, nbits]`` laid out like ``bits_in`` (data cell, then bit, most significant bit of the symbol first); the
+most significant bit of a byte comes first and the padding bits of a row's last byte are 0.
+
+The hard decision is the evaluation step's, bit for bit (argmax over the pair of ``output:0``, first index on ties).  One
+consequence: where ``llr = u1 - u0`` is positive but so small that ``exp(-llr)`` rounds to 1, ``p1 == p0`` and the bit is 0
+although ``llr > 0``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import RxReceiveBuffers, RxShape, check
+from .engine import PARAM_NAMES, RxDims, glorot_init, param_layout
+
+
+def row_bytes(D: int, nbits: int) -> int:
+    return (int(D) * int(nbits) + 7) // 8
+
+
+def pack_bits(hard) -> np.ndarray:
+    """``hard [frames, D, nbits]`` (0 / 1) -> ``uint8 [frames, ceil(D * nbits / 8)]`` in the row layout above (NumPy, host)."""
+    h = np.asarray(hard)
+    if h.ndim != 3:
+        raise ValueError("hard must be [frames, D, nbits]")
+    frames = h.shape[0]
+    flat = (h.reshape(frames, -1) != 0).astype(np.uint8)
+    nb = row_bytes(h.shape[1], h.shape[2])
+    out = np.zeros((frames, nb), np.uint8)
+    pad = nb * 8 - flat.shape[1]
+    if pad:
+        flat = np.concatenate([flat, np.zeros((frames, pad), np.uint8)], axis=1)
+    w = (1 << np.arange(7, -1, -1)).astype(np.uint16)
+    out[:] = (flat.reshape(frames, nb, 8).astype(np.uint16) * w).sum(axis=2).astype(np.uint8)
+    return out
+
+
+def unpack_bits(packed, D: int, nbits: int) -> np.ndarray:
+    """Inverse of :func:`pack_bits`: ``uint8 [frames, ceil(D * nbits / 8)]`` -> ``uint8 [frames, D, nbits]`` (NumPy, host)."""
+    p = np.ascontiguousarray(np.asarray(packed, dtype=np.uint8))
+    nb = row_bytes(D, nbits)
+    if p.ndim != 2 or p.shape[1] != nb:
+        raise ValueError("packed must be [frames, %d] for D=%d, nbits=%d" % (nb, D, nbits))
+    sh = np.arange(7, -1, -1).astype(np.uint8)
+    bits = (p[:, :, None] >> sh) & 1
+    return np.ascontiguousarray(bits.reshape(p.shape[0], nb * 8)[:, :D * nbits].reshape(p.shape[0], D, nbits))
+
+
+class ReceiveResult:
+    """Device tensors of one receive call (they are the receiver's resident buffers: the next call overwrites them)."""
+
+    def __init__(self, packed: torch.Tensor, llr: Optional[torch.Tensor], prob: Optional[torch.Tensor], D: int, nbits: int):
+        self.packed, self.llr, self.prob, self.D, self.nbits = packed, llr, prob, int(D), int(nbits)
+
+    def bits(self) -> torch.Tensor:
+        """``uint8 [frames, D, nbits]``, unpacked on the device."""
+        p = self.packed.to(torch.int32)
+        sh = torch.arange(7, -1, -1, dtype=torch.int32, device=p.device)
+        b = (p.unsqueeze(-1) >> sh) & 1
+        n = self.D * self.nbits
+        return b.reshape(p.shape[0], -1)[:, :n].reshape(p.shape[0], self.D, self.nbits).to(torch.uint8)
+
+
+class RxReceiver:
+    """Fixed-shape receive engine of the basic receiver on one GPU: ``receive(x)`` -> :class:`ReceiveResult`.
+
+    ``x``: host array or device tensor ``[batch, S, kin, 2]`` (as ``RxEngine.set_batch`` takes it).  ``x_norm`` (``input:0``)
+    and ``fft_out`` hold what the evaluation step writes for the same frames.
+    """
+
+    def __init__(self, dims: RxDims, batch: int, params: Optional[Dict[str, np.ndarray]] = None, device="cuda",
+                 want_llr: bool = False, want_prob: bool = False, seed: int = 1):
+        self.lib = _lib.load()
+        self.dims, self.batch = dims, int(batch)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.DccnError("RxReceiver needs a CUDA (ROCm) device; there is no CPU fallback")
+        self.shape = RxShape(self.batch, dims.S, dims.kin, dims.F, dims.D, dims.nbits)
+        self.layout, total = param_layout(dims)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        B, d = self.batch, dims
+        self.params = torch.zeros(total, **f32)
+        self.x = torch.zeros(B, d.S, d.kin, 2, **f32)
+        self.x_norm = torch.empty(B, d.S, d.kin, 2, **f32)
+        self.fft_out = torch.empty(B, d.S, d.F, 2, **f32)
+        # the dense output exists in memory only where the decision does not run inside the dense launch
+        self.fused = bool(self.lib.dccn_rx_receive_fused(C.byref(self.shape)))
+        self.z = None if self.fused else torch.empty(B, 2 * d.D, **f32)
+        self.packed = torch.zeros(B, row_bytes(d.D, d.nbits), dtype=torch.uint8, device=self.device)
+        self.llr = torch.empty(B, d.D, d.nbits, **f32) if want_llr else None
+        self.prob = torch.empty(B, d.D, d.nbits, 2, **f32) if want_prob else None
+        nws = self.lib.dccn_rx_receive_workspace_size(C.byref(self.shape))
+        if nws == 0:
+            raise _lib.DccnError("dccn_rx_receive_workspace_size refused the shape %r" % (dims,))
+        self.ws = torch.empty(nws, dtype=torch.uint8, device=self.device)
+        p = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
+        self.buffers = RxReceiveBuffers(p(self.x), p(self.params), p(self.x_norm), p(self.fft_out), p(self.z), p(self.packed),
+                                        p(self.llr), p(self.prob), p(self.ws), nws, None)
+        self.load_params(params if params is not None else glorot_init(dims, seed))
+
+    def view(self, name: str) -> torch.Tensor:
+        o, shp = self.layout[name]
+        return self.params[o:o + int(np.prod(shp))].view(*shp)
+
+    def load_params(self, params: Dict[str, np.ndarray]):
+        for n in PARAM_NAMES:
+            self.view(n).copy_(torch.as_tensor(np.asarray(params[n], dtype=np.float32)).reshape(self.layout[n][1]))
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close_graph(self):
+        """(nothing captured: lets a :class:`~dl_ofdm_amd.session.Session` keep receivers next to its engines)"""
+
+    def receive(self, x=None) -> ReceiveResult:
+        """Stage ``x`` (``None``: whatever ``self.x`` holds) and run one receive step on the current stream."""
+        if x is not None:
+            self.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(self.x.shape), non_blocking=True)
+        check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
+        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits)
+
+
+def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False) -> ReceiveResult:
+    """Equaliser + frozen receiver chain (``EqualizerTrainer.receive``): ``dccn_eq_receive_step`` on the trainer's resident
+    plan of this batch size.  ``out_eq`` / ``chest`` of the plan hold what ``eval_step`` writes for the same frames."""
+    if not tr.fused_ok:
+        raise _lib.DccnError("the chain's receive path needs the fused equaliser step")
+    batch = int(x.shape[0]) if isinstance(x, torch.Tensor) else int(np.shape(x)[0])
+    pl = tr.resident(batch)
+    pl.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(pl.x.shape), non_blocking=True)
+    packed, llr, prob = pl.receive(want_llr, want_prob)
+    return ReceiveResult(packed, llr, prob, int(tr.ofdmobj.frame_size), int(tr.FLAGS.nbits))

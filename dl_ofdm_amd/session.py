@@ -34,6 +34,8 @@ TENSOR_NAMES = PLACEHOLDERS + ("input:0", "output:0", "cost:0", "ce_mean:0", "lo
                                "tx_signal:0", "tx_power:0", "noise_power:0", "iq_rx:0", "iq_tx:0",
                                "receiver/fft_like/fft_out:0")
 SCOPES = ("transmitter", "channel", "receiver", "Equalizer", "optimizer")
+# what the graph computes from tx_ofdm:0 alone: served by the receive path when bits_in:0 is not fed
+LABEL_FREE = ("tx_ofdm:0", "SNR:0", "input:0", "receiver/fft_like/fft_out:0", "output:0")
 
 
 class Tensor:
@@ -132,12 +134,23 @@ class Session:
         for k in feed:
             if k not in PLACEHOLDERS:
                 raise KeyError("%r is not a placeholder of the receiver graph" % k)
-        if "tx_ofdm:0" not in feed or "bits_in:0" not in feed:
+        if "tx_ofdm:0" not in feed:
             raise ValueError("feed_dict must hold tx_ofdm:0 and bits_in:0")
+        if "bits_in:0" not in feed and not all(n in LABEL_FREE for n in names):
+            raise ValueError("feed_dict must hold tx_ofdm:0 and bits_in:0 (without bits_in:0 only %s can be fetched)"
+                             % ", ".join(LABEL_FREE))
         xs = np.asarray(feed["tx_ofdm:0"], dtype=np.float32)
         if self.crop is not None and xs.shape[2] != self.dims.kin:
             cp, k = self.crop
             xs = np.ascontiguousarray(xs[:, :, cp:cp + k, :])
+        if "bits_in:0" not in feed:
+            # dev/py/test_v1/test_ofdm_cdnn_awgn.py:113-118: sess.run(outputs, {x: frames}) -- the receive path, no labels
+            batch = xs.shape[0]
+            rcv = self._receiver(batch)
+            rcv.receive(xs)
+            snr = np.asarray(feed.get("SNR:0", np.zeros((batch, 1))), dtype=np.float32).reshape(batch)
+            out = [self._fetch(n, rcv, None, None, xs, None, snr) for n in names]
+            return out[0] if single else out
         ys = np.asarray(feed["bits_in:0"]).astype(np.int32)
         batch = xs.shape[0]
         eng = self._engine(batch)
@@ -151,6 +164,15 @@ class Session:
                 m = eng.metrics()
             out.append(self._fetch(n, eng, m, mon, xs, ys, snr))
         return out[0] if single else out
+
+    def _receiver(self, batch: int):
+        from .receive import RxReceiver
+        key = (batch, "receive")
+        if key not in self._engines:
+            if len(self._engines) >= 4:
+                self._engines.pop(next(iter(self._engines))).close_graph()
+            self._engines[key] = RxReceiver(self.dims, batch, params=self.params, device=self.device, want_prob=True)
+        return self._engines[key]
 
     def _monitor(self, eng: RxEngine, snr: np.ndarray):
         self._calls += 1

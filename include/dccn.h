@@ -504,6 +504,58 @@ size_t dccn_rx_workspace_size(const dccn_rx_shape* shape, int train);
  * weight-gradient launch.  Nothing changes for the caller: every effect of the step is ordered on `stream` when the call
  * returns, results are bit-identical, and dccn_rx_graph_create captures the fork and the join with the rest. */
 int dccn_rx_eval_step(const dccn_rx_shape* shape, const dccn_rx_buffers* buf, dccn_stream_t stream);
+
+/* ---- receive path: IQ frames -> packed bits and LLRs, no labels ---------------------------------------------------------
+ * The forward of the receiver with a decision stage instead of the loss: no bits_in, no cross entropy, no confusion counts,
+ * no reduction, no metrics (dev/py/test_v1/test_ofdm_cdnn_awgn.py:113-118 fetches `output:0` from `tx_ofdm:0` alone).
+ * Outputs for `frames` frames of D data cells with nbits (1..4) bits:
+ *   packed uint8 [frames, ceil(D*nbits/8)]  required.  Row f = numpy.packbits(hard[f].reshape(-1)), hard [frames, D, nbits] in
+ *          the layout of bits_in (cell, then bit, most significant bit of the symbol first); most significant bit of a byte
+ *          first, padding bits of a row's last byte 0.
+ *   llr    float [frames, D, nbits]         nullable.  u1 - u0 of the bit pair's two post-leaky-ReLU logits
+ *          (dev/py/model.py:1283-1291) = log(p1 / p0) of output:0; positive means bit 1.
+ *   prob   float [frames, D, nbits, 2]      nullable.  output:0, as the evaluation step writes it.
+ * The hard decision is argmax over the pair of output:0, first index on ties (dev/py/ofdmreceiver_np.py:166), computed with
+ * the expressions of the evaluation step's tail: it is bit for bit the decision that step tallies.  Note: where u1 - u0 is
+ * positive but so small that exp(-(u1 - u0)) rounds to 1, p1 == p0 and the bit is 0 although llr > 0.
+ * Every entry validates its arguments before it launches anything.
+ *
+ *   dccn_demod_decide            z [frames, D, 2] + tail weights (dccn_tail_param_count floats) -> packed / llr / prob: one launch,
+ *                                no workspace, every nbits, any D (rows of packed need no alignment).
+ *   dccn_dense_decide_supported  1: dccn_dense_decide_fwd accepts (M, K, N, nbits) with 16-byte aligned x / w (N = 2 D).
+ *                                It does NOT say that z may be NULL: that holds for nbits <= 2 only; for nbits 3 / 4 the call
+ *                                is two launches and a NULL z is refused with DCCN_ERR_INVALID_ARG.
+ * Alignment (checked, DCCN_ERR_INVALID_ARG otherwise): z and prob 8 bytes; llr 8 bytes at nbits = 2, 16 bytes at nbits = 4,
+ * 4 bytes otherwise (a cell's values leave as one vector store); packed: none.
+ *   dccn_dense_decide_fwd        z = x [M,K] . w [K,N] + bias and the decision.  nbits <= 2: ONE launch, the decision in the
+ *                                GEMM's epilogue; z nullable (not materialised then).  nbits >= 3: the GEMM stores z (required),
+ *                                the decision kernel follows.  z has the bits dccn_dense_tail_fwd computes for the same operands. */
+int dccn_demod_decide(const float* z, const float* tailp, unsigned char* packed, float* llr, float* prob, int frames, int D,
+                      int nbits, dccn_stream_t stream);
+int dccn_dense_decide_supported(int M, int K, int N, int nbits);
+int dccn_dense_decide_fwd(const float* x, const float* w, const float* bias, float* z, const float* tailp,
+                          unsigned char* packed, float* llr, float* prob, int M, int K, int N, int nbits,
+                          dccn_stream_t stream);
+/* The basic receiver's receive step: R0 -> C-Conv forward -> dense + decision.  Three launches where dccn_rx_receive_fused
+ * answers 1 (BPSK / QPSK wherever the evaluation step fuses its tail, up to 1536 frames), one more otherwise.  x_norm and
+ * fft_out are bitwise what dccn_rx_eval_step writes for the same x and params. */
+typedef struct dccn_rx_receive_buffers {
+    const float* x;            /* [batch, S, kin, 2] */
+    const float* params;       /* the receiver's arena (dccn_rx_param_offsets) */
+    float* x_norm;             /* [batch, S, kin, 2] */
+    float* fft_out;            /* [batch, S, F, 2] */
+    float* z;                  /* [batch, 2D]; nullable where dccn_rx_receive_fused answers 1 (not written then unless given) */
+    unsigned char* packed;
+    float* llr;                /* nullable */
+    float* prob;               /* nullable */
+    void* workspace;
+    size_t workspace_bytes;    /* >= dccn_rx_receive_workspace_size */
+    const int* tuning;         /* nullable: a plan's own knob table (dccn_tuning_snapshot), as dccn_rx_buffers.tuning */
+} dccn_rx_receive_buffers;
+size_t dccn_rx_receive_workspace_size(const dccn_rx_shape* shape);
+/* 1: the step runs the dense forward and the decision as ONE launch for this shape under the current knobs: z may be NULL */
+int dccn_rx_receive_fused(const dccn_rx_shape* shape);
+int dccn_rx_receive_step(const dccn_rx_shape* shape, const dccn_rx_receive_buffers* buf, dccn_stream_t stream);
 int dccn_rx_train_step(const dccn_rx_shape* shape, const dccn_rx_buffers* buf,
                        dccn_adam_hparams hp, dccn_stream_t stream);
 /* R0 (+R8 partial sums) of buf->x into buf->x_norm, as the first launch of a step does it: primes the pipelined
@@ -699,6 +751,17 @@ int dccn_eq_workspace_tensor(const dccn_eq_shape* shape, int train, const char* 
 int dccn_eq_eval_step(const dccn_eq_shape* shape, const dccn_eq_buffers* buf, dccn_stream_t stream);
 int dccn_eq_train_step(const dccn_eq_shape* shape, const dccn_eq_buffers* buf, dccn_adam_hparams hp,
                        dccn_stream_t stream);
+/* The chain's receive step (see "receive path" above): the equaliser forward exactly as dccn_eq_eval_step runs it -- out_eq,
+ * chest (and snr_db) are written as that step writes them -- and the frozen receiver with the decision stage in place of the
+ * tail: buf->bits, buf->metrics, buf->prob and buf->tx_power may be NULL and are not touched.  Workspace: the evaluation
+ * step's.  Chain groups are not supported here (DCCN_ERR_UNSUPPORTED). */
+typedef struct dccn_receive_out {
+    unsigned char* packed;     /* [batch, ceil(D*nbits/8)] */
+    float* llr;                /* [batch, D, nbits], nullable */
+    float* prob;               /* [batch, D, nbits, 2], nullable */
+} dccn_receive_out;
+int dccn_eq_receive_step(const dccn_eq_shape* shape, const dccn_eq_buffers* buf, const dccn_receive_out* out,
+                         dccn_stream_t stream);
 /* ---- chain groups: several independent equaliser training chains carried by ONE launch sequence ------------------------
  * The reference driver trains one (receiver -> equaliser) chain per modulation and per cp / longcp variant, each as an OS process
  * of its own (dev/py/run_local_ofdm.py:61-118, locals.py:28-38; the loop is ofdmreceiver_np_mp.py:394-466).  A 73-frame

@@ -1,0 +1,128 @@
+"""Receive path against what a user had to do before it existed, timed in ONE process, alternating:
+
+    (a) eval_step(want_prob=True) + the device-side argmax + pack a user writes in torch (labels are dummies)
+    (b) eval_step(want_prob=False)                (the metrics-only evaluation step: a subset of (a)'s launches)
+    (c) receive, bits only
+    (d) receive, bits + LLRs
+
+    python tools/rxbench.py [--iters 200] [--repeats 7]            -> one JSON line (all shapes)
+    python tools/rxbench.py --one 1170,2 --only c --iters 50        -> one shape, one variant (kernel-trace runs)
+
+Shapes: 1170 frames QPSK and 16-QAM, and one 20 000-frame QPSK sweep batch (N = 64).  Every shape runs in a child process of
+its own under a time limit; the parent never opens the GPU and stops at the first child that fails.  Times are medians over
+the repeats of the per-step mean of `iters` back-to-back steps (inputs resident on the device); `spread` is (max - min) /
+median over the repeats.  `bytes` is what each variant reads and writes beyond the receiver's own activations, from shapes.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = [(1170, 2), (1170, 4), (20000, 2)]
+S, KIN, F, D = 7, 80, 64, 320
+
+
+def io_bytes(frames, nbits):
+    cells = frames * D
+    labels, prob, llr = cells * nbits * 4, cells * nbits * 2 * 4, cells * nbits * 4
+    packed = frames * ((D * nbits + 7) // 8)
+    return {"a": {"in": labels, "out": prob + packed, "reread": prob}, "b": {"in": labels, "out": 64},
+            "c": {"in": 0, "out": packed}, "d": {"in": 0, "out": packed + llr}}
+
+
+def run_one(frames, nbits, iters, repeats, only):
+    import numpy as np
+    import torch
+    from dl_ofdm_amd.engine import RxDims, RxEngine, glorot_init
+    from dl_ofdm_amd.receive import RxReceiver
+    dims = RxDims(S, KIN, F, D, nbits)
+    p = glorot_init(dims, 1)
+    rng = np.random.RandomState(0)
+    x = torch.as_tensor(rng.randn(frames, S, KIN, 2).astype(np.float32), device="cuda")
+    variants = {}
+    if only in (None, "a"):
+        ea = RxEngine(dims, frames, train=False, params=p, want_prob=True, want_z=False)
+        ea.x.copy_(x)
+        sh = torch.arange(7, -1, -1, dtype=torch.int32, device="cuda")
+        n = D * nbits
+        pad = (-n) % 8
+
+        def va():
+            ea.eval_step()
+            h = (ea.prob[..., 1] > ea.prob[..., 0]).reshape(frames, n).to(torch.int32)
+            if pad:
+                h = torch.nn.functional.pad(h, (0, pad))
+            return (h.reshape(frames, -1, 8) << sh).sum(-1).to(torch.uint8)
+        variants["a"] = va
+    if only in (None, "b"):
+        eb = RxEngine(dims, frames, train=False, params=p, want_prob=False, want_z=False)
+        eb.x.copy_(x)
+        variants["b"] = eb.eval_step
+    if only in (None, "c"):
+        rc = RxReceiver(dims, frames, p)
+        rc.x.copy_(x)
+        variants["c"] = rc.receive
+    if only in (None, "d"):
+        rd = RxReceiver(dims, frames, p, want_llr=True)
+        rd.x.copy_(x)
+        variants["d"] = rd.receive
+    if only is None:                       # (a) and (c) must agree before anything is timed
+        assert torch.equal(variants["a"](), variants["c"]().packed)
+    for f in variants.values():            # warm-up: first-launch costs, clocks
+        for _ in range(20):
+            f()
+    torch.cuda.synchronize()
+    t = {k: [] for k in variants}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(repeats):
+        for k, f in variants.items():      # alternating: every repeat visits every variant
+            e0.record()
+            for _ in range(iters):
+                f()
+            e1.record()
+            e1.synchronize()
+            t[k].append(e0.elapsed_time(e1) * 1e3 / iters)
+    out = {"frames": frames, "nbits": nbits, "iters": iters, "repeats": repeats, "bytes": io_bytes(frames, nbits), "us": {}, "spread": {}}
+    for k, v in t.items():
+        v = sorted(v)
+        med = v[len(v) // 2]
+        out["us"][k] = round(med, 2)
+        out["spread"][k] = round((v[-1] - v[0]) / med, 4)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--one", default=None, help="frames,nbits: measure this shape in this process")
+    ap.add_argument("--only", default=None, choices=["a", "b", "c", "d"])
+    ap.add_argument("--limit", type=int, default=240, help="seconds per shape")
+    a = ap.parse_args()
+    if a.one:
+        fr, nb = (int(v) for v in a.one.split(","))
+        print(json.dumps(run_one(fr, nb, a.iters, a.repeats, a.only)))
+        return 0
+    res = []
+    for fr, nb in SHAPES:
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--one", "%d,%d" % (fr, nb),
+               "--iters", str(a.iters if fr < 10000 else max(a.iters // 5, 10)), "--repeats", str(a.repeats)]
+        if a.only:
+            cmd += ["--only", a.only]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        if r.returncode != 0:               # nothing more is started on the GPU after a failure
+            sys.stderr.write(r.stderr[-2000:])
+            print(json.dumps({"bench": "rxbench", "failed": [fr, nb], "rc": r.returncode, "shapes": res}))
+            return 1
+        res.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    print(json.dumps({"bench": "rxbench", "variants": {"a": "eval_step(want_prob) + torch argmax/pack", "b": "eval_step(no prob)",
+                                                       "c": "receive bits", "d": "receive bits+llr"}, "shapes": res}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
