@@ -176,7 +176,7 @@ struct RxLayout {
     long long o_conv_w, o_conv_b, o_dense_w, o_dense_b, o_tail, total;
     int rows, cols, dK, dN;
     long long cells;
-    size_t ws_norm, ws_tail, ws_dense_bw, ws_conv_bw, ws_sync;
+    size_t ws_norm, ws_tail, ws_dense_bw, ws_conv_bw;
 };
 
 // ---- launch planning of the operators (defined in dccn_abi.hip) -------------------------------------------------------

@@ -36,7 +36,6 @@ bool norm_fused_ok(const float* x, const float* y, int batch, int cols) {
     return (cols % 4 == 0) && batch <= 128 * kNormFusedRPT && aligned16(x) && aligned16(y);
 }
 
-
 // want_power: also emit the per-block partial sums of the clipped power (R8); adam != nullptr: the
 // optimizer bookkeeping of the fused training step rides on the first kernel
 // where norm_impl leaves the R8 partial sums for a [batch, cols] input in workspace `ws` (no launch)
@@ -280,9 +279,6 @@ int dense_bwd_w_impl(const float* x, const float* dy, float* dw, float* dbias, i
     return DCCN_OK;
 }
 
-// dense backward as ONE grouped launch: dx = dy.w^T together with the split-K slabs of dw = x^T.dy
-// (left un-reduced for the fused Adam kernel).  Falls back to two launches when the grouped
-// configuration does not apply (128x128 tiles, unaligned operands, single split).
 static int dense_bwd16_launch(int variant, const GemmParams& px, const GemmParams& pw, int splits, hipStream_t s) {
     const size_t sm = tune_smem_min();
     switch (variant) {
@@ -787,7 +783,6 @@ size_t tail_ws_bytes(long long cells, int nbits) {
     return align_up(o, 256);
 }
 
-
 template <int NB>
 static int tail_launch(bool bwd, const float* z, const int32_t* bits, const float* tailp, float* prob, float* dz,
                        long long cells, int nblk, TailBlockMetrics* bm, float* bg, hipStream_t s) {
@@ -1116,8 +1111,6 @@ RxLayout rx_layout(const dccn_rx_shape* sh) {
         if (f > L.ws_tail) L.ws_tail = f;
     }
     L.ws_dense_bw = splitk_ws_bytes(L.dK, L.dN, sh->batch);
-    // hand-off words of the update + prefetch launch: arrival counter + one flag per C-Conv forward tile, 256 B apart
-    L.ws_sync = 256 + (size_t)ceil_div(L.rows, 64) * ceil_div(2 * sh->F, 64) * kFlagStride * sizeof(unsigned);
     L.ws_conv_bw = cconv_bw_ws_bytes(L.rows, sh->kin, sh->F);
     {
         const size_t f = rx_bwd_fused_ws_bytes(sh->batch, sh->S, sh->kin, sh->F);
@@ -1133,7 +1126,6 @@ static size_t rx_ws_bytes(const dccn_rx_shape* sh, int train) {
     if (train) {
         o = carve_size(o, L.ws_dense_bw);
         o = carve_size(o, L.ws_conv_bw);
-        o = carve_size(o, L.ws_sync);
     }
     return align_up(o, 256);
 }
@@ -1241,245 +1233,279 @@ int gen_static_launch(const dccn_gen_static* g, hipStream_t s, const GenChainSca
     return DCCN_OK;
 }
 
+// ---- what a step launches for a shape: each condition is spelled ONCE.  The dccn_rx_* queries ask with null pointers
+// ("given 16-byte aligned buffers"), the step's plan asks with the caller's buffers. ----
+static bool rx_bwd_fused_ok(const dccn_rx_shape* sh, const float* x_norm, const float* fft_out, const float* dz, const float* wd) {
+    return rx_bwd_fused_ok(sh->batch, sh->S, sh->kin, sh->F, sh->D, x_norm, fft_out, dz, wd);
+}
+// R2..R6 as one launch, the dense forward with the tail in its epilogue: z may be NULL
+static bool rx_dense_tail_fused_ok(const dccn_rx_shape* sh, bool train, const float* fft_out, const float* wd) {
+    return dense_tail_planned(sh->nbits, train, sh->batch, 2 * sh->D) &&
+           dense_tail_ok(fft_out, wd, sh->batch, sh->S * 2 * sh->F, 2 * sh->D, sh->nbits);
+}
+// the receive step's dense forward + decision as ONE launch (then z may be NULL)
+static bool rx_receive_fused(const dccn_rx_shape* sh, bool eval_tail_fused) {
+    return sh->nbits <= 2 && eval_tail_fused;
+}
+// R0 of the next batch on the fused backward launch (fuse_bw), written to the second x_norm buffer
+static bool rx_norm_rides_bwd_ok(const dccn_rx_shape* sh, bool fuse_bw, const float* x_next, const float* x_norm_next) {
+    return g_tune[TUNE_NORM_ON_BWD] && fuse_bw && kNormFusedCG == 2 &&
+           norm_fused_ok(x_next, x_norm_next, sh->batch, sh->S * sh->kin * 2);
+}
 // batches whose pipelined normalisation can read the fused generator's (y, noise, partials) as its input: the single-pass R0
 // (norm_fused_kernel: <= 128 * kNormFusedRPT rows) and one power partial per generator block
-static bool rx_gen_next_shape_ok(int batch, int cols) {
-    return kNormFusedCG == 2 && (cols % 4) == 0 && batch > 0 && batch <= 128 * kNormFusedRPT &&
-           ceil_div(batch, kGenFramesPerBlock) <= kChanPartials;
+static bool rx_gen_next_ok(const dccn_rx_shape* sh, const float* y, const float* x_norm) {
+    return kNormFusedCG == 2 && ceil_div(sh->batch, kGenFramesPerBlock) <= kChanPartials &&
+           norm_fused_ok(y, x_norm, sh->batch, sh->S * sh->kin * 2);
 }
 
-// side != nullptr: run the dense weight-gradient branch on `side` (fork/join by events),
-// concurrently with dX -> C-Conv weight gradient on the main stream.
-static int rx_step_impl(const dccn_rx_shape* sh, const dccn_rx_buffers* b, bool train, dccn_adam_hparams hp,
-                        hipStream_t s, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join) {
-    if (!shape_ok(sh) || !b) return DCCN_ERR_INVALID_ARG;
-    const TuneScope tune(b->tuning);
+// R0 (+R8 partial sums into slot `slot`) of one batch as a step runs it; `ws_norm` is the carved region of L.ws_norm bytes
+static int rx_norm_r0(const dccn_rx_shape* sh, const RxLayout& L, const float* x, float* y, bool want_power, PowerPartials* pp,
+                      void* ws_norm, dccn_adam_hparams hp, int slot, hipStream_t s) {
+    return norm_impl(x, y, nullptr, nullptr, want_power, pp, sh->batch, L.cols, 1e-9f, 8.0f, nullptr, hp, ws_norm, L.ws_norm, s, slot);
+}
+
+// Everything a step decides, decided before its first launch: rx_step_plan checks every argument and fills this, the
+// rx_issue_* functions below only read it.  A refused step has launched nothing (also inside a stream capture).
+struct RxStepPlan {
+    RxLayout L;
+    void *ws_norm, *ws_tail, *ws_dbw, *ws_cbw;
+    bool train;
+    bool pre;                       // x_norm already holds this batch (dccn_rx_buffers.x_prenormalised)
+    int nslot;
+    bool fused_tail;                // R2..R6 as one launch (z nullable)
+    bool can_defer;                 // the optimizer launch takes over the C-Conv fold
+    bool fuse_bw;                   // the backward as one launch (dfft nullable)
+    bool ride_bw, ride_opt;         // R0 of the next batch on the backward / on the optimizer launch ...
+    bool norm_after;                // ... or as launches of its own (shapes the single-pass kernel does not take)
+    bool wait_x;                    // the launch that reads the next batch waits for the producer's event first
+    const dccn_gen_static* gen;     // the next batch comes from the fused generator (gen_next)
+    OverlapStreams branch;          // forked variant (dccn_rx_graph_create mode bit 1): dense dW/db on the caller's second stream
+    bool want_overlap;              // large layers: the dense kernel's update on the library's second stream (ovs)
+    OverlapStreams ovs;
+};
+// every return between a fork onto o->side and the join (a failed launch, a DCCN_TRY) still joins: the side stream never
+// keeps running behind a call that has returned, and a capture of `s` is never left with an un-joined branch
+struct OverlapJoin {
+    const OverlapStreams* o; hipStream_t s; bool forked = false, joined = false;
+    ~OverlapJoin() {
+        if (forked && !joined) {
+            (void)hipEventRecord(o->join, o->side);
+            (void)hipStreamWaitEvent(s, o->join, 0);
+        }
+    }
+};
+// what one phase of the step leaves for the next
+struct RxStepCarry {
+    TailFinalizeArgs fin;
+    DeferredSlabs ds;
+    FoldDefer fd;
+    int fold_tilew;
+};
+
+// launches nothing, records and waits on no event (overlap_streams only looks up what dccn_rx_workspace_size created)
+static int rx_step_plan(const dccn_rx_shape* sh, const dccn_rx_buffers* b, bool train, const OverlapStreams* fork,
+                        RxStepPlan* plan) {
     if (!b->x || !b->bits || !b->params || !b->x_norm || !b->fft_out || !b->metrics) return DCCN_ERR_INVALID_ARG;
     if (train && (!b->grads || !b->adam_m || !b->adam_v || !b->adam || !b->dz)) return DCCN_ERR_INVALID_ARG;
     if (!b->workspace || b->workspace_bytes < rx_ws_bytes(sh, train ? 1 : 0)) return DCCN_ERR_WORKSPACE;
-    const RxLayout L = rx_layout(sh);
+    if (b->x_prenormalised != 0 && b->x_prenormalised != 1) return DCCN_ERR_INVALID_ARG;
+    RxStepPlan& p = *plan;
+    p = RxStepPlan{};
+    const RxLayout& L = p.L = rx_layout(sh);
     Carver c(b->workspace, b->workspace_bytes);
-    void* ws_norm = c.take<char>(L.ws_norm);
-    void* ws_tail = c.take<char>(L.ws_tail);
-    void* ws_dbw = train ? c.take<char>(L.ws_dense_bw) : nullptr;
-    void* ws_cbw = train ? c.take<char>(L.ws_conv_bw) : nullptr;
-    if (train) (void)c.take<char>(L.ws_sync);       // (reserved: keeps the workspace layout of earlier builds)
-    float* P = b->params;
-    float* G = b->grads;
-    // step timeline (dccn_step_trace_enable): launch slots 1 C-Conv forward, 2 dense forward (+ tail), 3 tail (own launch),
-    // 4 backward (fused, or grouped dX+dW), 5 C-Conv weight gradient (own launch), 6 optimizer
-    const StepTraceScope trace;
+    p.ws_norm = c.take<char>(L.ws_norm);
+    p.ws_tail = c.take<char>(L.ws_tail);
+    p.ws_dbw = train ? c.take<char>(L.ws_dense_bw) : nullptr;
+    p.ws_cbw = train ? c.take<char>(L.ws_conv_bw) : nullptr;
+    const float* wd = b->params + L.o_dense_w;
+    p.train = train;
+    p.pre = train && b->x_prenormalised != 0;
+    p.nslot = b->norm_slot ? 1 : 0;
+    p.fused_tail = rx_dense_tail_fused_ok(sh, train, b->fft_out, wd);
+    if (!p.fused_tail && !b->z) return DCCN_ERR_INVALID_ARG;            // ask dccn_rx_dense_tail_fused first
+    if (!train) return DCCN_OK;
 
-    // the fused generator of the NEXT batch (dccn_rx_buffers.gen_next): first launch of the step, consumed by its last one
-    // (x_next_ready set as well: the caller has issued that launch itself on ANOTHER stream -- it then overlaps the first three
-    // launches of this step -- and the optimizer launch waits for the event)
-    if (train && b->gen_next != nullptr) {
-        if (b->gen_next->frames != sh->batch || b->gen_next->S != sh->S || 2 * (b->gen_next->K + b->gen_next->CP) * sh->S != L.cols)
+    const bool side = fork != nullptr;
+    if (side) p.branch = *fork;
+    p.can_defer = L.o_conv_w == 0 && (L.o_dense_w % 4) == 0;
+    // small layers: dX tiles + C-Conv weight-gradient partials in their epilogue + dW items + tail finalize: one launch
+    p.fuse_bw = !side && p.can_defer && rx_bwd_fused_ok(sh, b->x_norm, b->fft_out, b->dz, wd);
+    if (!p.fuse_bw && !b->dfft) return DCCN_ERR_INVALID_ARG;            // ask dccn_rx_bwd_fused_supported first
+    const bool second_buf = b->x_next != nullptr && b->x_norm_next != nullptr;
+    p.ride_bw = second_buf && rx_norm_rides_bwd_ok(sh, p.fuse_bw, b->x_next, b->x_norm_next);
+    if (second_buf && !p.ride_bw) return DCCN_ERR_INVALID_ARG;          // ask dccn_rx_norm_rides_backward first
+    // gen_next: the generator launch of the NEXT batch is the step's first launch and the optimizer launch, its last one, reads
+    // (y, noise, power partials) as R0's virtual input instead of a materialised x_next (x_next, when given too, receives x).
+    // x_next_ready set as well: the caller has issued the generator itself on ANOTHER stream.  The double-buffered pipelining
+    // has no virtual-input form: refuse rather than normalise a stale x_next (dccn_rx_gen_next_supported is the caller's query)
+    p.gen = b->gen_next;
+    if (p.gen != nullptr) {
+        if (p.gen->frames != sh->batch || p.gen->S != sh->S || 2 * (p.gen->K + p.gen->CP) * sh->S != L.cols)
             return DCCN_ERR_INVALID_ARG;
-        // (the double-buffered pipelining -- R0 on the backward launch, knob 18 -- has no virtual-input form: refuse rather than
-        // normalise a stale x_next)
-        if (b->x_norm_next != nullptr) return DCCN_ERR_INVALID_ARG;
-        // ... and everything the optimizer launch will need to form that batch is checked HERE, before the generator, the
-        // forward, the backward and the update have been issued (dccn_rx_gen_next_supported is the caller's query)
-        if (!rx_gen_next_shape_ok(sh->batch, L.cols) || !gen_static_ok(b->gen_next) ||
-            !norm_fused_ok(b->gen_next->y, b->x_norm, sh->batch, L.cols))
+        if (b->x_norm_next != nullptr || !gen_static_ok(p.gen) || !rx_gen_next_ok(sh, p.gen->y, b->x_norm))
             return DCCN_ERR_INVALID_ARG;
-        if (b->x_next_ready == nullptr) {
-            trace.launch(7);
-            DCCN_TRY(gen_static_launch(b->gen_next, s));
-        }
+    }
+    const float* rin = p.gen ? p.gen->y : b->x_next;
+    p.ride_opt = !p.ride_bw && rin != nullptr && kNormFusedCG == 2 && norm_fused_ok(rin, b->x_norm, sh->batch, L.cols);
+    p.norm_after = b->x_next != nullptr && !p.ride_opt && !p.ride_bw;
+    p.wait_x = rin != nullptr && b->x_next_ready != nullptr;
+    // Large layers whose dW tiles are unsplit (N = 1024: 585 rows are one k range), grouped backward: the dense kernel's Adam
+    // update runs as a launch of its own on the library's second stream next to the C-Conv weight-gradient launch
+    if (!p.fuse_bw && !side && g_tune[TUNE_ADAM_OVERLAP] && p.can_defer && (((long long)L.dK * L.dN) % 4) == 0 &&
+        (long long)ceil_div(L.dK, 128) * ceil_div(L.dN, 128) >= 2 * kCUs && dense_dw_plan(sh->batch, L.dK, L.dN).splits == 1)
+        p.want_overlap = overlap_streams(&p.ovs);
+    return DCCN_OK;
+}
+
+// step timeline (dccn_step_trace_enable): launch slots 1 C-Conv forward, 2 dense forward (+ tail), 3 tail (own launch),
+// 4 backward (fused, or grouped dX+dW), 5 C-Conv weight gradient (own launch), 6 optimizer, 7 generator of the next batch
+static int rx_issue_forward(const dccn_rx_shape* sh, const dccn_rx_buffers* b, const RxStepPlan& p, dccn_adam_hparams hp,
+                            hipStream_t s, const StepTraceScope& trace, TailFinalizeArgs* fin) {
+    const RxLayout& L = p.L;
+    const float* P = b->params;
+    float* gtail = p.train ? b->grads + L.o_tail : nullptr;
+    if (p.gen != nullptr && b->x_next_ready == nullptr) {
+        trace.launch(7);
+        DCCN_TRY(gen_static_launch(p.gen, s));
     }
     // R0 (+R8 partial sums) -- unless the previous call already normalised this batch behind its Adam update
     PowerPartials pp;
-    const bool pre = train && b->x_prenormalised != 0;
-    const int nslot = b->norm_slot ? 1 : 0;
-    if (pre) {
-        if (L.cols & 1) return DCCN_ERR_INVALID_ARG;
-        norm_power_partials(sh->batch, L.cols, ws_norm, L.ws_norm, b->x_next ? b->x_next : b->x, b->x_norm, &pp, nslot);
-    } else {
-        DCCN_TRY(norm_impl(b->x, b->x_norm, nullptr, nullptr, b->tx_power != nullptr, &pp, sh->batch, L.cols, 1e-9f, 8.0f,
-                           nullptr, hp, ws_norm, L.ws_norm, s, nslot));
-    }
+    if (p.pre) norm_power_partials(sh->batch, L.cols, p.ws_norm, L.ws_norm, b->x_next ? b->x_next : b->x, b->x_norm, &pp, p.nslot);
+    else DCCN_TRY(rx_norm_r0(sh, L, b->x, b->x_norm, b->tx_power != nullptr, &pp, p.ws_norm, hp, p.nslot, s));
     // R1
     trace.launch(1);
-    if (b->x_prenormalised != 0 && b->x_prenormalised != 1) return DCCN_ERR_INVALID_ARG;
     DCCN_TRY(cconv_fwd_impl(b->x_norm, P + L.o_conv_w, P + L.o_conv_b, b->fft_out, L.rows, sh->kin, sh->F, s));
-    TailFinalizeArgs fin;
     trace.launch(2);
-    if (dense_tail_planned(sh->nbits, train, sh->batch, L.dN) &&
-        dense_tail_ok(b->fft_out, P + L.o_dense_w, sh->batch, L.dK, L.dN, sh->nbits)) {
-        // R2 with R3-R6 (+ tail backward) in its epilogue; z is materialised only when the caller gave a buffer
-        DCCN_TRY(dense_tail_impl(train, b->fft_out, P + L.o_dense_w, P + L.o_dense_b, b->z, b->bits, P + L.o_tail, b->prob,
-                                 b->metrics, b->dz, train ? G + L.o_tail : nullptr, sh->batch, L.dK, L.dN, sh->nbits, &pp,
-                                 b->tx_power, ws_tail, L.ws_tail, s, train ? &fin : nullptr));
-    } else {
-        if (!b->z) return DCCN_ERR_INVALID_ARG;
-        // R2
-        DCCN_TRY(dense_fwd_impl(b->fft_out, P + L.o_dense_w, P + L.o_dense_b, b->z, sh->batch, L.dK, L.dN, s));
-        // R3-R6 (+ tail backward)
-        trace.launch(3);
-        DCCN_TRY(tail_impl(train, b->z, b->bits, P + L.o_tail, b->prob, b->metrics, b->dz, train ? G + L.o_tail : nullptr,
-                           L.cells, sh->nbits, &pp, b->tx_power, ws_tail, L.ws_tail, s, train ? &fin : nullptr));
-    }
-    if (!train) return DCCN_OK;
-    trace.launch(4);
-    fin.adam = b->adam;                 // the optimizer's per-step bookkeeping rides on the tail finalize stage
-    fin.hp = hp;
+    // R2 with R3-R6 (+ tail backward) in its epilogue; z is materialised only when the caller gave a buffer
+    if (p.fused_tail)
+        return dense_tail_impl(p.train, b->fft_out, P + L.o_dense_w, P + L.o_dense_b, b->z, b->bits, P + L.o_tail, b->prob,
+                               b->metrics, b->dz, gtail, sh->batch, L.dK, L.dN, sh->nbits, &pp, b->tx_power, p.ws_tail,
+                               L.ws_tail, s, p.train ? fin : nullptr);
+    // R2, then R3-R6 (+ tail backward)
+    DCCN_TRY(dense_fwd_impl(b->fft_out, P + L.o_dense_w, P + L.o_dense_b, b->z, sh->batch, L.dK, L.dN, s));
+    trace.launch(3);
+    return tail_impl(p.train, b->z, b->bits, P + L.o_tail, b->prob, b->metrics, b->dz, gtail, L.cells, sh->nbits, &pp,
+                     b->tx_power, p.ws_tail, L.ws_tail, s, p.train ? fin : nullptr);
+}
 
-    DeferredSlabs ds;
-    FoldDefer fd;
-    fd.slabs = nullptr;
-    OverlapStreams ovs{};
-    bool overlap = false;                 // the dense kernel's update runs on ovs.side (large layers)
-    // every return between the fork and the join below (a failed launch, a DCCN_TRY) still joins: the side stream never
-    // keeps running behind a call that has returned, and a capture of `s` is never left with an un-joined branch
-    struct OverlapJoin {
-        OverlapStreams* o; hipStream_t s; bool forked = false, joined = false;
-        ~OverlapJoin() {
-            if (forked && !joined) {
-                (void)hipEventRecord(o->join, o->side);
-                (void)hipStreamWaitEvent(s, o->join, 0);
-            }
-        }
-    } ojoin{&ovs, s};
-    int fold_tilew = 0;
-    const bool can_defer = L.o_conv_w == 0 && (L.o_dense_w % 4) == 0;     // optimizer kernel takes over the fold
-    // small layers: dX tiles + C-Conv weight-gradient partials in their epilogue + dW items + tail finalize: one launch
-    const bool fuse_bw = !side && can_defer &&
-                         rx_bwd_fused_ok(sh->batch, sh->S, sh->kin, sh->F, sh->D, b->x_norm, b->fft_out, b->dz, P + L.o_dense_w);
-    if (!fuse_bw && !b->dfft) return DCCN_ERR_INVALID_ARG;
-    // R0 of the next batch: on leading blocks of the fused backward launch when the caller gave the second x_norm buffer
-    const bool ride_bw = fuse_bw && b->x_next != nullptr && b->x_norm_next != nullptr && kNormFusedCG == 2 &&
-                         norm_fused_ok(b->x_next, b->x_norm_next, sh->batch, L.cols);
-    if (b->x_norm_next != nullptr && b->x_next != nullptr && !ride_bw) return DCCN_ERR_INVALID_ARG;   // ask dccn_rx_norm_rides_backward first
-    // a producer on another stream is filling x_next: the launch that reads it waits for the producer's event
-    const bool wait_x = (b->x_next != nullptr || b->gen_next != nullptr) && b->x_next_ready != nullptr;
-    if (fuse_bw) {
-        NormRideArgs nr;
-        memset(&nr, 0, sizeof(nr));
-        if (ride_bw && wait_x) DCCN_HIP(hipStreamWaitEvent(s, (hipEvent_t)b->x_next_ready, 0));
-        if (ride_bw) {
+// the optimizer launch's argument block: what the main launch and the dense kernel's update on the second stream share
+// (value-initialised: a field neither call site sets is zero on the device)
+static AdamRxArgs adam_rx_args(const dccn_rx_buffers* b, const RxLayout& L) {
+    AdamRxArgs a{};
+    a.param = b->params; a.grad = b->grads; a.m = b->adam_m; a.v = b->adam_v;
+    a.reg_coef = b->reg_coef; a.reg_gate = b->reg_coef ? &b->metrics->berlin : nullptr;
+    a.state = b->adam;
+    a.o_dw = L.o_dense_w; a.n_dw = (long long)L.dK * L.dN; a.o_db = L.o_dense_b; a.n_db = L.dN;
+    a.neps = 1e-9f; a.npeak = 8.0f;
+    a.reg_uniform_dw = b->reg_uniform_dense != 0 ? 1 : 0;
+    return a;
+}
+
+static int rx_issue_backward(const dccn_rx_shape* sh, const dccn_rx_buffers* b, const RxStepPlan& p, dccn_adam_hparams hp,
+                             hipStream_t s, RxStepCarry* k, OverlapJoin* ojoin) {
+    const RxLayout& L = p.L;
+    const float* wd = b->params + L.o_dense_w;
+    float* G = b->grads;
+    if (p.fuse_bw) {
+        // R0 of the next batch: on leading (or closing) blocks of this launch when the caller gave the second x_norm buffer
+        NormRideArgs nr{};
+        if (p.ride_bw) {
+            if (p.wait_x) DCCN_HIP(hipStreamWaitEvent(s, (hipEvent_t)b->x_next_ready, 0));
             PowerPartials np;
-            norm_power_partials(sh->batch, L.cols, ws_norm, L.ws_norm, b->x_next, b->x_norm_next, &np, nslot ^ 1);
+            norm_power_partials(sh->batch, L.cols, p.ws_norm, L.ws_norm, b->x_next, b->x_norm_next, &np, p.nslot ^ 1);
             nr.x = b->x_next; nr.y = b->x_norm_next; nr.power = b->tx_power ? const_cast<double*>(np.partial) : nullptr;
             nr.batch = sh->batch; nr.cols = L.cols; nr.blocks = norm_fused_blocks(L.cols);
             nr.eps = 1e-9f; nr.peak = 8.0f;
             nr.trail = g_tune[TUNE_NORM_ON_BWD] >= 2 ? 1 : 0;
         }
-        DCCN_TRY(rx_bwd_fused_impl(b->x_norm, b->fft_out, b->dz, P + L.o_dense_w, b->dfft, G + L.o_dense_b, sh->batch, sh->S,
-                                   sh->kin, sh->F, sh->D, ws_dbw, L.ws_dense_bw, ws_cbw, L.ws_conv_bw, nr, fin, hp, s, &ds, &fd,
-                                   &fold_tilew));
-    } else if (side) {
-        // two-stream variant: dense dW/db on `side`, dX -> C-Conv dW on the main stream
-        DCCN_HIP(hipEventRecord(ev_fork, s));
-        DCCN_HIP(hipStreamWaitEvent(side, ev_fork, 0));
-        DCCN_TRY(dense_bwd_w_impl(b->fft_out, b->dz, G + L.o_dense_w, G + L.o_dense_b, sh->batch, L.dK, L.dN, ws_dbw,
-                                  L.ws_dense_bw, side, &ds));
-        DCCN_HIP(hipEventRecord(ev_join, side));
-        DCCN_TRY(dense_bwd_x_impl(b->dz, P + L.o_dense_w, b->dfft, sh->batch, L.dK, L.dN, s));
-    } else {
-        // default: dense dX and dW/db in one grouped launch (independent GEMMs packed on the same grid)
-        // Large layers whose dW tiles are unsplit (N = 1024: 585 rows are one k range): the dense kernel's Adam update runs as a
-        // launch of its own on the library's second stream next to the C-Conv weight-gradient launch.  It needs this step's
-        // alpha and BER gate, so the tail's slab reduction (which otherwise rides on the C-Conv weight-gradient launch further
-        // down) runs first, as a launch of its own.
-        {
-            const SplitPlan sp = dense_dw_plan(sh->batch, L.dK, L.dN);
-            const long long bigw = (long long)ceil_div(L.dK, 128) * ceil_div(L.dN, 128);
-            // round 4: the same layers, the update as a launch of its own on the library's second stream, next to the C-Conv
-            // weight-gradient launch (same precondition: alpha and the BER gate must exist before it starts)
-            if (g_tune[TUNE_ADAM_OVERLAP] && sp.splits == 1 && bigw >= 2 * kCUs && can_defer &&
-                (L.o_dense_w % 4) == 0 && (((long long)L.dK * L.dN) % 4) == 0 && overlap_streams(&ovs)) {
-                hipLaunchKernelGGL(demod_tail_finalize_kernel, dim3(tail_finalize_blocks(fin.P)), dim3(256), 0, s, fin);
-                DCCN_LAUNCH_CHECK();
-                fin.metrics = nullptr;
-                overlap = true;
-            }
-        }
-        DCCN_TRY(dense_bwd_grouped_impl(b->fft_out, b->dz, P + L.o_dense_w, b->dfft, G + L.o_dense_w, G + L.o_dense_b,
-                                        sh->batch, L.dK, L.dN, ws_dbw, L.ws_dense_bw, s, &ds));
-        if (overlap && ds.dw_slabs != nullptr) overlap = false;
-        if (overlap) {
-            // the optimizer kernel itself, restricted to the dense kernel's segment: same arithmetic, same results
-            AdamRxArgs as;
-            memset(&as, 0, sizeof(as));
-            as.param = P; as.grad = G; as.m = b->adam_m; as.v = b->adam_v;
-            as.reg_coef = b->reg_coef; as.reg_gate = b->reg_coef ? &b->metrics->berlin : nullptr;
-            as.state = b->adam;
-            as.o_dw = L.o_dense_w; as.n_dw = (long long)L.dK * L.dN; as.o_db = L.o_dense_b; as.n_db = L.dN;
-            as.n = as.o_dw + as.n_dw;
-            as.skip_lo = 0; as.skip_hi = as.o_dw;                 // (everything in front of the dense kernel stays with the main launch)
-            as.splits = 1; as.neps = 1e-9f; as.npeak = 8.0f;
-            as.reg_uniform_dw = b->reg_uniform_dense != 0 ? 1 : 0;
-            as.nt = g_tune[TUNE_ADAM_OVERLAP] >= 2 ? 2 : 0;
-            long long sb = ceil_div_ll(ceil_div_ll(as.n, 4), 256);
-            if (sb > 8 * kCUs) sb = 8 * kCUs;                     // (2, 4, 16 per CU measured within 0.5 % of this)
-            DCCN_HIP(hipEventRecord(ovs.fork, s));
-            DCCN_HIP(hipStreamWaitEvent(ovs.side, ovs.fork, 0));
-            ojoin.forked = true;
-            hipLaunchKernelGGL(adam_rx_kernel<0>, dim3((unsigned)sb), dim3(256), 0, ovs.side, as, hp);
-            DCCN_LAUNCH_CHECK();
-            DCCN_HIP(hipEventRecord(ovs.join, ovs.side));
-        }
+        return rx_bwd_fused_impl(b->x_norm, b->fft_out, b->dz, wd, b->dfft, G + L.o_dense_b, sh->batch, sh->S, sh->kin, sh->F,
+                                 sh->D, p.ws_dbw, L.ws_dense_bw, p.ws_cbw, L.ws_conv_bw, nr, k->fin, hp, s, &k->ds, &k->fd,
+                                 &k->fold_tilew);
     }
+    if (p.branch.side) {
+        // two-stream variant: dense dW/db on `side`, dX -> C-Conv dW on the main stream (joined in rx_issue_update)
+        DCCN_HIP(hipEventRecord(p.branch.fork, s));
+        DCCN_HIP(hipStreamWaitEvent(p.branch.side, p.branch.fork, 0));
+        DCCN_TRY(dense_bwd_w_impl(b->fft_out, b->dz, G + L.o_dense_w, G + L.o_dense_b, sh->batch, L.dK, L.dN, p.ws_dbw,
+                                  L.ws_dense_bw, p.branch.side, &k->ds));
+        DCCN_HIP(hipEventRecord(p.branch.join, p.branch.side));
+        return dense_bwd_x_impl(b->dz, wd, b->dfft, sh->batch, L.dK, L.dN, s);
+    }
+    // default: dense dX and dW/db in one grouped launch (independent GEMMs packed on the same grid)
+    if (p.want_overlap) {
+        // the update on the second stream needs this step's alpha and BER gate, so the tail's slab reduction (which otherwise
+        // rides on the C-Conv weight-gradient launch) runs first, as a launch of its own
+        hipLaunchKernelGGL(demod_tail_finalize_kernel, dim3(tail_finalize_blocks(k->fin.P)), dim3(256), 0, s, k->fin);
+        DCCN_LAUNCH_CHECK();
+        k->fin.metrics = nullptr;
+    }
+    DCCN_TRY(dense_bwd_grouped_impl(b->fft_out, b->dz, wd, b->dfft, G + L.o_dense_w, G + L.o_dense_b, sh->batch, L.dK, L.dN,
+                                    p.ws_dbw, L.ws_dense_bw, s, &k->ds));
+    // (the plan saw an unsplit dW; knobs 1 and 4 can make the grouped launch split a very wide, very short dense kernel
+    // after all: its slabs are then summed by the main optimizer launch and nothing is forked)
+    if (!p.want_overlap || k->ds.dw_slabs != nullptr) return DCCN_OK;
+    // the optimizer kernel itself, restricted to the dense kernel's segment: same arithmetic, same results
+    AdamRxArgs as = adam_rx_args(b, L);
+    as.n = as.o_dw + as.n_dw;
+    as.skip_hi = as.o_dw;                       // (everything in front of the dense kernel stays with the main launch)
+    as.splits = 1;
+    as.nt = g_tune[TUNE_ADAM_OVERLAP] >= 2 ? 2 : 0;
+    long long sb = ceil_div_ll(ceil_div_ll(as.n, 4), 256);
+    if (sb > 8 * kCUs) sb = 8 * kCUs;           // (2, 4, 16 per CU measured within 0.5 % of this)
+    DCCN_HIP(hipEventRecord(p.ovs.fork, s));
+    DCCN_HIP(hipStreamWaitEvent(p.ovs.side, p.ovs.fork, 0));
+    ojoin->forked = true;
+    hipLaunchKernelGGL(adam_rx_kernel<0>, dim3((unsigned)sb), dim3(256), 0, p.ovs.side, as, hp);
+    DCCN_LAUNCH_CHECK();
+    DCCN_HIP(hipEventRecord(p.ovs.join, p.ovs.side));
+    return DCCN_OK;
+}
+
+static int rx_issue_update(const dccn_rx_shape* sh, const dccn_rx_buffers* b, const RxStepPlan& p, dccn_adam_hparams hp,
+                           hipStream_t s, const StepTraceScope& trace, RxStepCarry* k, OverlapJoin* ojoin) {
+    const RxLayout& L = p.L;
+    const FoldDefer& fd = k->fd;
     // C-Conv dW/db from dX (the C-Conv input is data: no dX of its own)
     // (its fold launch also carries the tail's slab reduction: metrics, tail gradients, tx_power)
     trace.launch(5);
-    if (!fuse_bw)
-        DCCN_TRY(cconv_bwd_w_impl(b->x_norm, b->dfft, G + L.o_conv_w, G + L.o_conv_b, L.rows, sh->kin, sh->F, ws_cbw,
-                                  L.ws_conv_bw, s, &fin, can_defer ? &fd : nullptr));
-    if (side) DCCN_HIP(hipStreamWaitEvent(s, ev_join, 0));
-    // (overlap: the dense kernel's update on the second stream is joined at the END of the call -- the optimizer launch below
-    // leaves that segment alone (skip_lo / skip_hi), reads the same read-only step state)
-    // R7 (+ BER-gated L2 term of R6), fused with the split-K reduction of the dense gradient
-    if (wait_x && !ride_bw) DCCN_HIP(hipStreamWaitEvent(s, (hipEvent_t)b->x_next_ready, 0));
+    if (!p.fuse_bw)
+        DCCN_TRY(cconv_bwd_w_impl(b->x_norm, b->dfft, b->grads + L.o_conv_w, b->grads + L.o_conv_b, L.rows, sh->kin, sh->F,
+                                  p.ws_cbw, L.ws_conv_bw, s, &k->fin, p.can_defer ? &k->fd : nullptr));
+    if (p.branch.side) DCCN_HIP(hipStreamWaitEvent(s, p.branch.join, 0));
+    if (p.wait_x && !p.ride_bw) DCCN_HIP(hipStreamWaitEvent(s, (hipEvent_t)b->x_next_ready, 0));
+    // R7 (+ BER-gated L2 term of R6), fused with the split-K reduction of the dense gradient and the C-Conv fold
     trace.launch(6);
-    AdamRxArgs aa;
+    AdamRxArgs aa = adam_rx_args(b, L);
     aa.stamp = tl_stamp;
-    aa.param = P; aa.grad = G; aa.m = b->adam_m; aa.v = b->adam_v;
-    aa.reg_coef = b->reg_coef; aa.reg_gate = b->reg_coef ? &b->metrics->berlin : nullptr;
-    aa.state = b->adam; aa.n = L.total;
-    aa.dw_slabs = ds.dw_slabs; aa.db_slabs = ds.db_slabs; aa.splits = ds.splits;
-    aa.o_dw = L.o_dense_w; aa.n_dw = (long long)L.dK * L.dN; aa.o_db = L.o_dense_b; aa.n_db = L.dN;
-    aa.cw_slabs = fd.slabs; aa.cw_colsum = fd.slabs ? fd.colsum : nullptr;
-    aa.cw_splits = fd.slabs ? fd.splits : 0; aa.cw_slab = fd.slabs ? fd.slab : 0;
-    aa.kin = sh->kin; aa.F = sh->F; aa.o_cw = L.o_conv_w; aa.cw_tilew = fd.slabs ? fold_tilew : 0;
+    aa.n = L.total;
+    aa.dw_slabs = k->ds.dw_slabs; aa.db_slabs = k->ds.db_slabs; aa.splits = k->ds.splits;
+    aa.kin = sh->kin; aa.F = sh->F; aa.o_cw = L.o_conv_w;
     aa.n_conv = L.o_dense_w;                      // C-Conv kernel + bias come first in the arena
-    aa.skip_lo = aa.skip_hi = 0;
-    aa.reg_uniform_dw = b->reg_uniform_dense != 0 ? 1 : 0;
+    if (fd.slabs) {
+        aa.cw_slabs = fd.slabs; aa.cw_colsum = fd.colsum; aa.cw_splits = fd.splits; aa.cw_slab = fd.slab;
+        aa.cw_tilew = k->fold_tilew;
+        aa.fold_blocks = ceil_div(sh->kin * sh->F + sh->F, k->fold_tilew > 0 ? kFoldLanesTiled : kRedLanes);
+    }
     aa.skip_dw_grad = b->keep_dense_grad < 0 ? 1 : 0;          // the caller never reads the summed dense gradient
-    aa.nt = 0;
-    if (overlap) { aa.skip_lo = L.o_dense_w; aa.skip_hi = L.o_dense_w + (long long)L.dK * L.dN; }
-    aa.fold_blocks = fd.slabs ? ceil_div(sh->kin * sh->F + sh->F, fold_tilew > 0 ? kFoldLanesTiled : kRedLanes) : 0;
+    // (the dense kernel's update forked onto the second stream is joined at the END of the call: this launch leaves that
+    // segment alone and reads the same read-only step state)
+    if (ojoin->forked) { aa.skip_lo = aa.o_dw; aa.skip_hi = aa.o_dw + aa.n_dw; }
     long long blocks = ceil_div_ll(ceil_div_ll(L.total - (aa.fold_blocks ? aa.n_conv : 0), 4), 256);
     if (blocks > 8 * kCUs) blocks = 8 * kCUs;
     blocks += aa.fold_blocks;
-    // R0 of the next batch on the leading blocks of this launch (dccn_rx_buffers.x_next)
-    aa.nx = nullptr; aa.ny = nullptr; aa.npower = nullptr; aa.nbatch = 0; aa.ncols = 0; aa.norm_blocks = 0;
-    aa.neps = 1e-9f; aa.npeak = 8.0f;
     aa.nv = norm_virtual_none();
-    // gen_next: the next batch is produced by the fused generator launch issued at the top of this step; R0 reads it as
-    // (y, noise, power partials) -- its virtual input -- instead of a materialised x_next (x_next, when given too, receives x)
-    const dccn_gen_static* gen = (!ride_bw && train) ? b->gen_next : nullptr;
-    const float* rin = gen ? gen->y : b->x_next;
-    const bool ride = !ride_bw && rin != nullptr && kNormFusedCG == 2 && norm_fused_ok(rin, b->x_norm, sh->batch, L.cols);
-    if (gen && !ride) return DCCN_ERR_INVALID_ARG;
-    if (ride) {
+    if (p.ride_opt) {
+        // R0 of the next batch on the leading blocks of this launch (x_next, or gen_next's virtual input)
+        const float* rin = p.gen ? p.gen->y : b->x_next;
         PowerPartials np;
-        norm_power_partials(sh->batch, L.cols, ws_norm, L.ws_norm, rin, b->x_norm, &np, nslot);
+        norm_power_partials(sh->batch, L.cols, p.ws_norm, L.ws_norm, rin, b->x_norm, &np, p.nslot);
         aa.nx = rin; aa.ny = b->x_norm; aa.npower = b->tx_power ? const_cast<double*>(np.partial) : nullptr;
         aa.nbatch = sh->batch; aa.ncols = L.cols; aa.norm_blocks = norm_fused_blocks(L.cols);
         blocks += aa.norm_blocks;
-        if (gen) {
-            aa.nv.y = gen->y; aa.nv.noise = gen->noise; aa.nv.ppart = gen->power_partial;
-            aa.nv.npart = ceil_div(gen->frames, kGenFramesPerBlock);
-            aa.nv.total = (double)gen->frames * (double)(gen->S * (gen->K + gen->CP));
-            aa.nv.x_out = const_cast<float*>(b->x_next);
-            aa.nv.npart_noise = gen->noise_partial; aa.nv.n_noise = aa.nv.npart;
-            aa.nv.npow_out = gen->noise_partial ? gen->noise_power_out : nullptr;
-        }
+        if (p.gen) aa.nv = norm_virtual_gen(p.gen, ceil_div(p.gen->frames, kGenFramesPerBlock), const_cast<float*>(b->x_next));
     }
-    switch (ds.splits) {
+    switch (k->ds.splits) {
         case 2: hipLaunchKernelGGL(adam_rx_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
         case 3: hipLaunchKernelGGL(adam_rx_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
         case 4: hipLaunchKernelGGL(adam_rx_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
@@ -1489,14 +1515,34 @@ static int rx_step_impl(const dccn_rx_shape* sh, const dccn_rx_buffers* b, bool 
     }
     DCCN_LAUNCH_CHECK();
     trace.none();
-    if (b->x_next != nullptr && !ride && !ride_bw) {
-        // shapes the single-pass kernel does not take: the same normalisation as launches of their own
+    if (p.norm_after) {
         PowerPartials np;
-        DCCN_TRY(norm_impl(b->x_next, b->x_norm, nullptr, nullptr, b->tx_power != nullptr, &np, sh->batch, L.cols, 1e-9f,
-                           8.0f, nullptr, hp, ws_norm, L.ws_norm, s, nslot));
+        DCCN_TRY(rx_norm_r0(sh, L, b->x_next, b->x_norm, b->tx_power != nullptr, &np, p.ws_norm, hp, p.nslot, s));
     }
-    if (overlap) { ojoin.joined = true; DCCN_HIP(hipStreamWaitEvent(s, ovs.join, 0)); }
+    if (ojoin->forked) { ojoin->joined = true; DCCN_HIP(hipStreamWaitEvent(s, p.ovs.join, 0)); }
     return DCCN_OK;
+}
+
+// fork != nullptr: run the dense weight-gradient branch on fork->side (fork/join by its events),
+// concurrently with dX -> C-Conv weight gradient on the main stream.
+static int rx_step_impl(const dccn_rx_shape* sh, const dccn_rx_buffers* b, bool train, dccn_adam_hparams hp,
+                        hipStream_t s, const OverlapStreams* fork) {
+    if (!shape_ok(sh) || !b) return DCCN_ERR_INVALID_ARG;
+    const TuneScope tune(b->tuning);
+    RxStepPlan plan;
+    DCCN_TRY(rx_step_plan(sh, b, train, fork, &plan));
+    const StepTraceScope trace;
+    RxStepCarry k;
+    k.fd.slabs = nullptr;
+    k.fold_tilew = 0;
+    DCCN_TRY(rx_issue_forward(sh, b, plan, hp, s, trace, &k.fin));
+    if (!train) return DCCN_OK;
+    trace.launch(4);
+    k.fin.adam = b->adam;               // the optimizer's per-step bookkeeping rides on the tail finalize stage
+    k.fin.hp = hp;
+    OverlapJoin ojoin{&plan.ovs, s};
+    DCCN_TRY(rx_issue_backward(sh, b, plan, hp, s, &k, &ojoin));
+    return rx_issue_update(sh, b, plan, hp, s, trace, &k, &ojoin);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1506,12 +1552,6 @@ static size_t rx_receive_ws_bytes(const dccn_rx_shape* sh) {
     const RxLayout L = rx_layout(sh);
     return align_up(carve_size(0, L.ws_norm), 256);
 }
-// the dense forward + decision run as ONE launch for this shape under the current knobs (then z may be NULL)
-static bool rx_receive_fused(const dccn_rx_shape* sh, const float* fft_out, const float* wd) {
-    const RxLayout L = rx_layout(sh);
-    return sh->nbits <= 2 && dense_tail_planned(sh->nbits, false, sh->batch, L.dN) &&
-           dense_tail_ok(fft_out, wd, sh->batch, L.dK, L.dN, sh->nbits);
-}
 static int rx_receive_impl(const dccn_rx_shape* sh, const dccn_rx_receive_buffers* b, hipStream_t s) {
     if (!shape_ok(sh) || !b) return DCCN_ERR_INVALID_ARG;
     const TuneScope tune(b->tuning);
@@ -1519,18 +1559,14 @@ static int rx_receive_impl(const dccn_rx_shape* sh, const dccn_rx_receive_buffer
     if (!b->workspace || b->workspace_bytes < rx_receive_ws_bytes(sh)) return DCCN_ERR_WORKSPACE;
     const RxLayout L = rx_layout(sh);
     const float* P = b->params;
-    const bool via_tail_plan = dense_tail_planned(sh->nbits, false, sh->batch, L.dN) &&
-                               dense_tail_ok(b->fft_out, P + L.o_dense_w, sh->batch, L.dK, L.dN, sh->nbits);
-    if (!(via_tail_plan && sh->nbits <= 2) && !b->z) return DCCN_ERR_INVALID_ARG;
-    Carver c(b->workspace, b->workspace_bytes);
-    void* ws_norm = c.take<char>(L.ws_norm);
-    dccn_adam_hparams hp;
-    memset(&hp, 0, sizeof(hp));
+    // the dense forward runs the plan the evaluation step would take for this shape (same bits in z)
+    const bool via_tail_plan = rx_dense_tail_fused_ok(sh, false, b->fft_out, P + L.o_dense_w);
+    if (!b->z && !rx_receive_fused(sh, via_tail_plan)) return DCCN_ERR_INVALID_ARG;
     // R0, R1: the launches of the evaluation step
-    DCCN_TRY(norm_impl(b->x, b->x_norm, nullptr, nullptr, false, nullptr, sh->batch, L.cols, 1e-9f, 8.0f, nullptr, hp, ws_norm,
-                       L.ws_norm, s, 0));
+    void* ws_norm = Carver(b->workspace, b->workspace_bytes).take<char>(L.ws_norm);
+    DCCN_TRY(rx_norm_r0(sh, L, b->x, b->x_norm, false, nullptr, ws_norm, dccn_adam_hparams{}, 0, s));
     DCCN_TRY(cconv_fwd_impl(b->x_norm, P + L.o_conv_w, P + L.o_conv_b, b->fft_out, L.rows, sh->kin, sh->F, s));
-    // R2 + decision: the dense forward runs the plan the evaluation step would take for this shape (same bits in z)
+    // R2 + decision
     if (via_tail_plan)
         return dense_decide_impl(b->fft_out, P + L.o_dense_w, P + L.o_dense_b, b->z, P + L.o_tail, b->packed, b->llr, b->prob,
                                  sh->batch, L.dK, L.dN, sh->nbits, s);
@@ -1763,17 +1799,11 @@ int dccn_rx_backward(const float* x_norm, const float* fft_out, const float* dz,
     Carver c(workspace, workspace_bytes);
     void* ws_d = c.take<char>(nd);
     void* ws_c = c.take<char>(nc);
-    NormRideArgs nr;
-    memset(&nr, 0, sizeof(nr));
-    TailFinalizeArgs fin;
-    memset(&fin, 0, sizeof(fin));
-    dccn_adam_hparams hp;
-    memset(&hp, 0, sizeof(hp));
     DeferredSlabs ds;
     FoldDefer fd;
     int tilew = 0;
     DCCN_TRY(rx_bwd_fused_impl(x_norm, fft_out, dz, w_dense, dfft, db_dense ? db_dense : dw_dense, batch, S, kin, F, D, ws_d, nd,
-                               ws_c, nc, nr, fin, hp, s, &ds, &fd, &tilew));
+                               ws_c, nc, NormRideArgs{}, TailFinalizeArgs{}, dccn_adam_hparams{}, s, &ds, &fd, &tilew));
     if (!reduce) return DCCN_OK;
     const long long n = (long long)dK * dN;
     if (db_dense) DCCN_TRY(launch_splitk_reduce2(ds.dw_slabs, ds.splits, n, dw_dense, n, ds.db_slabs, (long long)dN, db_dense, (long long)dN, s));
@@ -1818,25 +1848,17 @@ int dccn_debug_set_trace(unsigned long long* buf) {
 
 int dccn_dense_tail_supported(int M, int K, int N, int nbits) { return dense_tail_shape_ok(M, K, N, nbits) ? 1 : 0; }
 int dccn_rx_dense_tail_fused(const dccn_rx_shape* sh, int train) {
-    if (!shape_ok(sh)) return 0;
-    return dense_tail_planned(sh->nbits, train != 0, sh->batch, 2 * sh->D) &&
-           dense_tail_shape_ok(sh->batch, sh->S * 2 * sh->F, 2 * sh->D, sh->nbits) ? 1 : 0;
+    return shape_ok(sh) && rx_dense_tail_fused_ok(sh, train != 0, nullptr, nullptr) ? 1 : 0;
+}
+// (pointer alignment is checked again when a step is planned; the queries assume 16-byte aligned buffers)
+int dccn_rx_bwd_fused_supported(const dccn_rx_shape* sh) {
+    return shape_ok(sh) && rx_bwd_fused_ok(sh, nullptr, nullptr, nullptr, nullptr) ? 1 : 0;
 }
 int dccn_rx_norm_rides_backward(const dccn_rx_shape* sh) {
-    if (!shape_ok(sh)) return 0;
-    const int cols = sh->S * sh->kin * 2;
-    const bool ok = g_tune[TUNE_NORM_ON_BWD] && rx_bwd_fused_ok(sh->batch, sh->S, sh->kin, sh->F, sh->D, nullptr, nullptr, nullptr, nullptr) &&
-                    kNormFusedCG == 2 && norm_fused_ok(nullptr, nullptr, sh->batch, cols);
-    return ok ? 1 : 0;
+    return dccn_rx_bwd_fused_supported(sh) && rx_norm_rides_bwd_ok(sh, true, nullptr, nullptr) ? 1 : 0;
 }
 int dccn_rx_gen_next_supported(const dccn_rx_shape* sh) {
-    if (!shape_ok(sh) || dccn_rx_norm_rides_backward(sh) != 0) return 0;
-    return rx_gen_next_shape_ok(sh->batch, sh->S * sh->kin * 2) ? 1 : 0;
-}
-int dccn_rx_bwd_fused_supported(const dccn_rx_shape* sh) {
-    if (!shape_ok(sh)) return 0;
-    // (pointer alignment is checked again at launch time; the query assumes 16-byte aligned buffers)
-    return rx_bwd_fused_ok(sh->batch, sh->S, sh->kin, sh->F, sh->D, nullptr, nullptr, nullptr, nullptr) ? 1 : 0;
+    return shape_ok(sh) && !dccn_rx_norm_rides_backward(sh) && rx_gen_next_ok(sh, nullptr, nullptr) ? 1 : 0;
 }
 
 size_t dccn_dense_tail_workspace_size(int M, int N, int nbits) {
@@ -1877,7 +1899,7 @@ size_t dccn_rx_receive_workspace_size(const dccn_rx_shape* shape) {
 int dccn_rx_receive_fused(const dccn_rx_shape* shape) {
     if (!shape_ok(shape)) return 0;
     const TuneScope tune;
-    return rx_receive_fused(shape, nullptr, nullptr) ? 1 : 0;
+    return rx_receive_fused(shape, rx_dense_tail_fused_ok(shape, false, nullptr, nullptr)) ? 1 : 0;
 }
 int dccn_rx_receive_step(const dccn_rx_shape* shape, const dccn_rx_receive_buffers* buf, dccn_stream_t stream) {
     return rx_receive_impl(shape, buf, (hipStream_t)stream);
@@ -1925,27 +1947,22 @@ size_t dccn_rx_workspace_size(const dccn_rx_shape* shape, int train) {
     return rx_ws_bytes(shape, train);
 }
 int dccn_rx_eval_step(const dccn_rx_shape* shape, const dccn_rx_buffers* buf, dccn_stream_t stream) {
-    dccn_adam_hparams hp;
-    memset(&hp, 0, sizeof(hp));
-    return rx_step_impl(shape, buf, false, hp, (hipStream_t)stream, nullptr, nullptr, nullptr);
+    return rx_step_impl(shape, buf, false, dccn_adam_hparams{}, (hipStream_t)stream, nullptr);
 }
 int dccn_rx_train_step(const dccn_rx_shape* shape, const dccn_rx_buffers* buf, dccn_adam_hparams hp,
                        dccn_stream_t stream) {
-    return rx_step_impl(shape, buf, true, hp, (hipStream_t)stream, nullptr, nullptr, nullptr);
+    return rx_step_impl(shape, buf, true, hp, (hipStream_t)stream, nullptr);
 }
 // R0 (+R8 partial sums) of buf->x into buf->x_norm exactly as a step would run it: primes the pipelined mode
 // (dccn_rx_buffers.x_prenormalised) before the first call
 int dccn_rx_normalise(const dccn_rx_shape* shape, const dccn_rx_buffers* buf, dccn_stream_t stream) {
     if (!shape_ok(shape) || !buf || !buf->x || !buf->x_norm) return DCCN_ERR_INVALID_ARG;
     if (!buf->workspace || buf->workspace_bytes < rx_ws_bytes(shape, 1)) return DCCN_ERR_WORKSPACE;
-    const RxLayout L = rx_layout(shape);
-    Carver c(buf->workspace, buf->workspace_bytes);
-    void* ws_norm = c.take<char>(L.ws_norm);
     PowerPartials pp;
-    dccn_adam_hparams hp;
-    memset(&hp, 0, sizeof(hp));
-    return norm_impl(buf->x, buf->x_norm, nullptr, nullptr, buf->tx_power != nullptr, &pp, shape->batch, L.cols, 1e-9f,
-                     8.0f, nullptr, hp, ws_norm, L.ws_norm, (hipStream_t)stream, buf->norm_slot ? 1 : 0);
+    const RxLayout L = rx_layout(shape);
+    void* ws_norm = Carver(buf->workspace, buf->workspace_bytes).take<char>(L.ws_norm);
+    return rx_norm_r0(shape, L, buf->x, buf->x_norm, buf->tx_power != nullptr, &pp, ws_norm, dccn_adam_hparams{},
+                      buf->norm_slot ? 1 : 0, (hipStream_t)stream);
 }
 
 // mode: bit0 = train, bit1 = fork the dense weight-gradient branch onto a second stream
@@ -1974,7 +1991,8 @@ int dccn_rx_graph_create(const dccn_rx_shape* shape, const dccn_rx_buffers* buf,
         dccn_rx_graph_destroy(g);
         return hip_fail(e);
     }
-    const int st = rx_step_impl(shape, buf, train, hp, s, fork ? g->side : nullptr, g->ev_fork, g->ev_join);
+    const OverlapStreams branch{g->side, g->ev_fork, g->ev_join};
+    const int st = rx_step_impl(shape, buf, train, hp, s, fork ? &branch : nullptr);
     e = hipStreamEndCapture(s, &g->graph);
     if (st != DCCN_OK || e != hipSuccess) {
         dccn_rx_graph_destroy(g);

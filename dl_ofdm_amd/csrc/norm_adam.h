@@ -230,6 +230,16 @@ __device__ __host__ inline NormVirtual norm_virtual_none() {
     v.npart_noise = nullptr; v.n_noise = 0; v.npow_out = nullptr;
     return v;
 }
+// the fused generator's (y, noise, power partials of its npart blocks) as that input; x_out as above
+inline NormVirtual norm_virtual_gen(const dccn_gen_static* g, int npart, float* x_out) {
+    NormVirtual v = norm_virtual_none();
+    v.y = g->y; v.noise = g->noise; v.ppart = g->power_partial; v.npart = npart;
+    v.total = (double)g->frames * (double)(g->S * (g->K + g->CP));
+    v.x_out = x_out;
+    v.npart_noise = g->noise_partial; v.n_noise = npart;
+    v.npow_out = g->noise_partial ? g->noise_power_out : nullptr;
+    return v;
+}
 // 1 / sqrt(mean |y|^2): every block of a 256-thread launch adds the partial sums in the same fixed order (thread t: t, t + 256,
 // ...; DPP wave sum; the four wave sums as (0 + 1) + (2 + 3)), so all blocks -- and awgn_kernel, and R0 -- get the same bits
 __device__ __forceinline__ float batch_power_inv_scale(const double* __restrict__ ppart, const int npart, const double total,
@@ -551,23 +561,7 @@ struct AdamRxArgs {
 };
 
 // C-Conv parameters: fold the dWeff slabs (Appendix A.2) and apply the update right here.
-// PUBLISH: the updated parameters are handed to other workgroups of the SAME launch (the C-Conv forward of the next
-// batch, rx_update_prefetch_kernel): write-through (agent-scope relaxed atomic = sc1) stores, every wave drains its
-// stores, one lane bumps the arrival counter (cdna_hip_programming.md Guideline 16, recipe R1).
-// Hand-off words: ONE arrival counter for the producers; the last arriver fans the news out to one flag word per
-// consumer block, 256 bytes apart (256 blocks polling one address serialise on that address's memory channel: measured
-// 37 us for the launch instead of 13).  Flag value = the step's epoch (bits of the advanced global_step), so the flags
-// never need clearing; the counter is reset by the backward launch of the same step.
-struct HandoffWords {
-    unsigned* counter;
-    unsigned* flags;        // [n_flags] at a stride of kFlagStride words
-    unsigned expected;      // producers
-    int n_flags;
-};
-constexpr int kFlagStride = 64;
-template <bool PUBLISH>
-__device__ __forceinline__ void adam_fold_role(const AdamRxArgs& a, const dccn_adam_hparams& hp, const int bx,
-                                               const HandoffWords hw) {
+__device__ __forceinline__ void adam_fold_role(const AdamRxArgs& a, const dccn_adam_hparams& hp, const int bx) {
     const float alpha = a.state->alpha;
     const float gate = a.reg_gate ? a.reg_gate[0] : 1.0f;
     const float omb1 = 1.0f - hp.beta1, omb2 = 1.0f - hp.beta2;
@@ -605,23 +599,8 @@ __device__ __forceinline__ void adam_fold_role(const AdamRxArgs& a, const dccn_a
         mm += (ge - mm) * omb1;
         vv += (ge * ge - vv) * omb2;
         p -= (mm * alpha) / (sqrtf(vv) + hp.eps);
-        if constexpr (PUBLISH) __hip_atomic_store(a.param + j, p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else a.param[j] = p;
+        a.param[j] = p;
         a.m[j] = mm; a.v[j] = vv;
-    }
-    if constexpr (PUBLISH) {
-        __shared__ unsigned s_last;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // EVERY storing wave drains its write-through stores
-        __syncthreads();
-        if (threadIdx.x == 0)
-            s_last = __hip_atomic_fetch_add(hw.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == hw.expected - 1u ? 1u : 0u;
-        __syncthreads();
-        if (s_last) {
-            // every producer drained before it counted itself in: all parameters are at the coherence point now
-            const unsigned epoch = __builtin_bit_cast(unsigned, a.state->global_step);
-            for (int i = threadIdx.x; i < hw.n_flags; i += blockDim.x)
-                __hip_atomic_store(hw.flags + (size_t)i * kFlagStride, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
     }
 }
 
@@ -754,7 +733,7 @@ __global__ __launch_bounds__(256) void adam_rx_kernel(const AdamRxArgs a, const 
     }
     const int bx = (int)blockIdx.x - a.norm_blocks, nbx = (int)gridDim.x - a.norm_blocks;
     if (bx < a.fold_blocks) {
-        adam_fold_role<false>(a, hp, bx, HandoffWords{nullptr, nullptr, 0u, 0});
+        adam_fold_role(a, hp, bx);
         stamp_mark(a.stamp, 1);
         return;
     }

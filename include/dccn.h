@@ -42,10 +42,10 @@ typedef enum dccn_status {
 } dccn_status;
 
 const char* dccn_strerror(int status);
-int dccn_version(void);
+int dccn_version(void);                                       /* 100*major + minor */
 /* 16 hex digits: hash of the sources this library was built from (csrc/Makefile).  Measurements that are kept next to the code
  * (profiles/pmc_traffic.json) carry it, so a reader can tell whether they describe the library that is loaded. */
-const char* dccn_build_id(void);                              /* 100*major + minor */
+const char* dccn_build_id(void);
 int dccn_last_hip_error(void);                       /* hipError_t of the last failure */
 /* host out-params; returns DCCN_ERR_NO_DEVICE when no GPU is visible */
 int dccn_device_info(int* cu_count, int* wavefront, size_t* hbm_bytes, char* arch, int arch_len);
@@ -441,7 +441,8 @@ typedef struct dccn_rx_buffers {
        normalisation of x_next is written to x_norm_next by leading blocks of the BACKWARD launch of this step -- hidden
        behind 30 us of matrix work instead of stretching the optimizer launch -- and the caller passes that buffer as
        x_norm (and norm_slot ^ 1 as norm_slot) in the following call.  norm_slot (0/1) names the R8 partial-sum slot of
-       the workspace that belongs to x_norm; x_norm is read until the backward launch ends, hence the second buffer. */
+       the workspace that belongs to x_norm; x_norm is read until the backward launch ends, hence the second buffer.
+       Where that query answers 0, x_next + x_norm_next is refused (DCCN_ERR_INVALID_ARG) before anything is launched. */
     float* x_norm_next;
     int norm_slot;
     /* Large layers (dccn_get_tuning(16), N = 1024): the dense kernel's optimizer update runs in the epilogue of its
