@@ -1,6 +1,6 @@
 // libdccn.so -- what the translation units of the C ABI share (round 6: dccn_abi.hip was one 3100-line unit):
 //   dccn_abi.hip        globals, tuning table, the operators' launch planning (*_impl), the basic receiver's step and its entry points
-//   dccn_abi_eq.hip     the equaliser step (eq_step.h), chain groups, equaliser stage operators, monitors
+//   dccn_abi_eq.hip     the equaliser step (eq_step.h: its plan, then the phases that issue it), chain groups, equaliser stage operators, monitors
 //   dccn_abi_gen.hip    device-side generator, classical receivers, in-graph AWGN branch
 //   dccn_abi_conv.hip   general-k complex convolutions (patch gather, implicit GEMMs, few-channel kernels), CRC32C
 // Kernels live in the headers; a non-template kernel is `static`, so a unit compiles only the kernels it launches.
@@ -192,6 +192,7 @@ int dense_bwd_grouped_impl(const float* x, const float* dy, const float* w, floa
 int dense_bwd_w_impl(const float* x, const float* dy, float* dw, float* dbias, int M, int K, int N, void* ws, size_t ws_bytes, hipStream_t s, DeferredSlabs* defer = nullptr, int ldx = 0);
 int dense_bwd_x_impl(const float* dy, const float* w, float* dx, int M, int K, int N, hipStream_t s);
 int dense_fwd_impl(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, hipStream_t s, int ldx = 0, int act = 1, bool* act_done = nullptr, const float* aux = nullptr, float* out2 = nullptr, float* out3 = nullptr);
+bool decide_outputs_aligned(const float* llr, const float* prob, int nbits);
 int decide_impl(const float* z, const float* tailp, unsigned char* packed, float* llr, float* prob, int frames, int D, int nbits, hipStream_t s);
 int dense_decide_impl(const float* x, const float* w, const float* bias, float* z, const float* tailp, unsigned char* packed, float* llr, float* prob, int M, int K, int N, int nbits, hipStream_t s);
 int dense_tail_impl(bool bwd, const float* x, const float* w, const float* bias, float* z, const int32_t* bits, const float* tailp, float* prob, dccn_metrics* metrics, float* dz, float* dtailp, int M, int K, int N, int nbits, const PowerPartials* pp, float* power_out, void* ws, size_t ws_bytes, hipStream_t s, TailFinalizeArgs* defer = nullptr);

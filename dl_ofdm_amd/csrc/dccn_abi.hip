@@ -995,7 +995,7 @@ int dense_tail_impl(bool bwd, const float* x, const float* w, const float* bias,
 // ---------------------------------------------------------------------------------------
 static int decide_row_bytes(int D, int nbits) { return (D * nbits + 7) / 8; }
 // the decision stage stores a cell's llr as one vector (float2 at nbits = 2, float4 at nbits = 4) and prob as float2 pairs
-static bool decide_outputs_aligned(const float* llr, const float* prob, int nbits) {
+bool decide_outputs_aligned(const float* llr, const float* prob, int nbits) {
     const uintptr_t la = nbits == 4 ? 15u : (nbits == 2 ? 7u : 3u);
     return (reinterpret_cast<uintptr_t>(llr) & la) == 0 && (reinterpret_cast<uintptr_t>(prob) & 7u) == 0;
 }
@@ -1561,7 +1561,12 @@ static int rx_receive_impl(const dccn_rx_shape* sh, const dccn_rx_receive_buffer
     const float* P = b->params;
     // the dense forward runs the plan the evaluation step would take for this shape (same bits in z)
     const bool via_tail_plan = rx_dense_tail_fused_ok(sh, false, b->fft_out, P + L.o_dense_w);
-    if (!b->z && !rx_receive_fused(sh, via_tail_plan)) return DCCN_ERR_INVALID_ARG;
+    const bool one_launch = rx_receive_fused(sh, via_tail_plan);
+    if (!b->z && !one_launch) return DCCN_ERR_INVALID_ARG;
+    // what dense_decide_impl / decide_impl ask of the buffers (the stand-alone decision kernel reads z as float2), asked
+    // before the first launch
+    if (!decide_outputs_aligned(b->llr, b->prob, sh->nbits) || (!one_launch && (reinterpret_cast<uintptr_t>(b->z) & 7u) != 0))
+        return DCCN_ERR_INVALID_ARG;
     // R0, R1: the launches of the evaluation step
     void* ws_norm = Carver(b->workspace, b->workspace_bytes).take<char>(L.ws_norm);
     DCCN_TRY(rx_norm_r0(sh, L, b->x, b->x_norm, false, nullptr, ws_norm, dccn_adam_hparams{}, 0, s));

@@ -60,8 +60,7 @@ size_t dccn_eq_rx_folded_floats(const dccn_eq_shape* shape) {
 int dccn_eq_rx_fold(const dccn_eq_shape* shape, const float* rx_params, float* out, dccn_stream_t stream) {
     if (!eq_shape_ok(shape) || !rx_params || !out) return DCCN_ERR_INVALID_ARG;
     const EqDims d = eq_dims(shape);
-    dccn_rx_shape rsh;
-    rsh.batch = 1; rsh.S = d.S; rsh.kin = d.cp ? d.nsc : d.K; rsh.F = d.F; rsh.D = d.D; rsh.nbits = shape->nbits;
+    const dccn_rx_shape rsh = eq_rx_shape(d, shape->nbits);
     const RxLayout L = rx_layout(&rsh);
     const int N2 = 2 * d.nsc, rows = d.S * N2;
     hipLaunchKernelGGL(eq_rx_fold_kernel, dim3(rows + 1), dim3(256), 0, (hipStream_t)stream, rx_params + L.o_conv_w,
@@ -177,12 +176,14 @@ int dccn_gen_static_apply_grouped(int n_chains, const dccn_gen_static* const* g,
 }
 
 int dccn_eq_group_supported(const dccn_eq_shape* shape) {
-    if (!eq_shape_ok(shape) || g_tune[TUNE_EQ_REPLAN] != 1 || !g_tune[TUNE_FEWROW] || g_tune[TUNE_SKINNY] <= 0) return 0;
+    if (!eq_shape_ok(shape)) return 0;
     const EqDims d = eq_dims(shape);
-    // the launches that carry a chain index: the few-row plan of the fused step (<= 96 frames), the pilot bottleneck as one
-    // launch per direction, the frozen receiver folded into one matrix
-    return (d.B <= 96 && (d.Pp == 16 || d.Pp == 32) && dccn_eq_norm_rides(shape) == 1 && (d.S * 2 * d.nsc) % 16 == 0 &&
-            d.S * 2 * d.nsc <= 1152) ? 1 : 0;
+    const dccn_rx_shape rsh = eq_rx_shape(d, shape->nbits);
+    const RxLayout L = rx_layout(&rsh);
+    // the step's own predicates, given 16-byte aligned buffers (and rx_folded): 1 exactly where a grouped step is accepted
+    const bool few_rx = eq_few_rx_ok(d, L, nullptr, nullptr, nullptr);
+    return eq_group_ok(eq_norm_rides_ok(d, true, nullptr, nullptr), eq_bn_ok(d, nullptr, nullptr, nullptr, nullptr),
+                       eq_rx_folded_ok(d, few_rx, nullptr, nullptr)) ? 1 : 0;
 }
 
 int dccn_eq_train_step_grouped(int n_chains, const dccn_eq_shape* const* shapes, const dccn_eq_buffers* const* bufs,
@@ -283,9 +284,7 @@ int dccn_eq_monitor_accumulate_grouped(int n_chains, const dccn_eq_monitor* cons
 
 int dccn_eq_norm_rides(const dccn_eq_shape* shape) {
     if (!eq_shape_ok(shape)) return 0;
-    const EqDims d = eq_dims(shape);
-    const int ncols = d.S * 2 * d.nsc;
-    return (g_tune[TUNE_EQ_REPLAN] != 0 && kNormFusedCG == 2 && (ncols % 4) == 0 && d.B <= 128 * kNormFusedRPT) ? 1 : 0;
+    return eq_norm_rides_ok(eq_dims(shape), true, nullptr, nullptr) ? 1 : 0;
 }
 int dccn_eq_graph_create(const dccn_eq_shape* shape, const dccn_eq_buffers* buf, int mode, dccn_adam_hparams hp,
                          dccn_stream_t stream, dccn_rx_graph** out) {
@@ -458,11 +457,10 @@ int dccn_eq_bottleneck_bwd(const float* dd2, const float* d1, const float* y, co
         return DCCN_ERR_INVALID_ARG;
     if (!workspace || workspace_bytes < dccn_eq_bottleneck_workspace_size(B, SK2, P)) return DCCN_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int tiles = ceil_div(B, 16), q = eq_bottleneck_q(B, SK2);
-    float* pw2 = static_cast<float*>(workspace);
-    float* pb2 = pw2 + (size_t)tiles * P * SK2;
-    float* pw1 = pb2 + (size_t)tiles * SK2;
-    float* pb1 = pw1 + (size_t)tiles * SK2 * P;
+    const int q = eq_bottleneck_q(B, SK2);
+    const EqBnParts pt = eq_bn_parts(static_cast<float*>(workspace), B, SK2, P);
+    const int tiles = pt.tiles;
+    float *pw2 = pt.w2, *pb2 = pt.b2, *pw1 = pt.w1, *pb1 = pt.b1;
     auto kern = P == 32 ? eq_bottleneck_bwd_kernel<2> : eq_bottleneck_bwd_kernel<1>;
     EqRideArgs no_ride;
     memset(&no_ride, 0, sizeof(no_ride));

@@ -3,6 +3,8 @@
 //   R0 normalise -> equalizer_ofdm (model.py:349-478) -> frozen basic receiver -> loss/BER
 //   -> backward to the Equalizer/* variables only -> TF Adam on the equaliser arena.
 // Included inside namespace dccn of dccn_abi_eq.hip, behind abi_impl.h (the operators' *_impl launch planning it is built from).
+// eq_step_plan checks every argument and makes every decision (EqStepPlan) and launches nothing; eq_issue_forward / _rx /
+// _backward / _update only read the plan.  The dccn_eq_* queries ask the plan's own predicates.
 // FLAGS.cp=False (model.py:364-366, 1236-1240): the equaliser's first dense layer and the receiver's C-Conv read
 // the K-sample window behind the cyclic prefix of [.., n_sc, 2] rows -- a column window of the same buffers.
 
@@ -168,86 +170,232 @@ static void eq_opt_dense(EqOptBuilder& ob, const EqDims& d, int i, const Deferre
     else ob.plain(d.o[i + 1], d.sz[i + 1], uni);
 }
 
-// ro != nullptr: the receive path (dccn_eq_receive_step): the evaluation step's forward with the tail section replaced by the
-// decision stage (decide.h) -- no labels, no metrics; bits / metrics / prob / tx_power of `b` are not touched
-static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool train, dccn_adam_hparams hp,
-                        hipStream_t s, const dccn_receive_out* ro = nullptr) {
-    if (!eq_shape_ok(sh) || !b) return DCCN_ERR_INVALID_ARG;
-    const TuneScope tune(b->tuning);
+// ---- what a step launches for a shape: each condition is spelled ONCE.  The dccn_eq_* queries ask with null pointers
+// ("given 16-byte aligned buffers"), the step's plan asks with the caller's buffers. ----
+// the frozen receiver as the equaliser feeds it (cp = 0: the K-sample window behind the cyclic prefix)
+static dccn_rx_shape eq_rx_shape(const EqDims& d, int nbits) {
+    return dccn_rx_shape{d.B, d.S, d.cp ? d.nsc : d.K, d.F, d.D, nbits};
+}
+// `input:0` by the single-pass kernel: the optimizer launch of a training step can then run it for the NEXT batch
+static bool eq_norm_rides_ok(const EqDims& d, bool train, const float* x, const float* x_norm) {
+    return g_tune[TUNE_EQ_REPLAN] != 0 && train && kNormFusedCG == 2 && norm_fused_ok(x, x_norm, d.B, d.S * 2 * d.nsc);
+}
+// both layers of the pilot bottleneck in one launch per direction (eq_bottleneck.h); W1 / W2: the dense_1 / dense_2 kernels
+static bool eq_bn_ok(const EqDims& d, const float* y, const float* W1, const float* W2, const float* d1) {
+    return g_tune[TUNE_EQ_REPLAN] == 1 && eq_bottleneck_ok(d.B, d.SK2, d.Pp, y, W1, W2) && aligned16(d1);
+}
+// few rows (73 frames): the fused dense + tail launch is 20 tiles of 48x64 behind a 14-tile k-loop (23 us); the
+// one-latency 16x16 tiles of fewrow.h (200 blocks) followed by the stand-alone tail launch take about half of that
+static bool eq_few_rx_ok(const EqDims& d, const RxLayout& L, const float* fft, const float* rx_params, const float* z) {
+    return g_tune[TUNE_FEWROW] && g_tune[TUNE_SKINNY] > 0 && d.B <= 96 && (L.dK % 16) == 0 && L.dK >= 128 && L.dK <= 1152 &&
+           (L.dN % 16) == 0 && aligned16(fft) && aligned16(z) &&
+           ((reinterpret_cast<uintptr_t>(rx_params) + 4 * (uintptr_t)L.o_dense_w) & 15u) == 0;      // (the dense kernel)
+}
+// ... and with the receiver's C-Conv and dense layer folded into one matrix (dccn_eq_rx_fold: the receiver is frozen)
+// both run as ONE such GEMM over the flattened frame, K = S * 2 n_sc
+static bool eq_rx_folded_ok(const EqDims& d, bool few_rx, const float* Mf, const float* out_eq) {
+    const int fK = d.S * 2 * d.nsc;
+    return few_rx && g_tune[TUNE_FEWROW] >= 1 && aligned16(Mf) && aligned16(out_eq) && (fK % 16) == 0 && fK <= 1152;
+}
+// a chain group (common.h ChainCtx) runs on the launches that carry a chain index: the single-pass normalisation, the
+// bottleneck as one launch per direction, the few-row plan with the receiver folded into one matrix
+static bool eq_group_ok(bool rides, bool bn, bool folded) { return rides && bn && folded; }
+// per-block weight-gradient partials of the fused bottleneck backward, summed by a later launch
+struct EqBnParts { float *w2, *b2, *w1, *b1; int tiles; };      // [tiles][P][SK2], [tiles][SK2], [tiles][SK2][P], [tiles][P]
+static EqBnParts eq_bn_parts(float* base, int B, int SK2, int P) {
+    const size_t t = ceil_div(B, 16);
+    float *w2 = base, *b2 = w2 + t * P * SK2, *w1 = b2 + t * SK2, *b1 = w1 + t * SK2 * P;
+    return EqBnParts{w2, b2, w1, b1, (int)t};
+}
+
+// Everything a step decides, decided before its first launch: eq_step_plan checks every argument and fills this, the
+// eq_issue_* functions below only read it.  A refused step has launched nothing (also inside a stream capture).
+struct EqStepPlan {
+    EqDims d;
+    EqWs w;
+    EqBnParts bnp;
+    bool train;
+    const dccn_receive_out* ro;     // the receive path (dccn_eq_receive_step): no labels, no metrics
+    // round-3 plan (TUNE_EQ_REPLAN): merged element-wise launches, the corr / eq C-Conv pair as grouped launches with the
+    // concat / split of model.py:456 in the GEMM stores, ONE job-table launch for every gradient reduction + Adam
+    // TUNE_EQ_REPLAN: 0 launch-per-stage plan, 1 re-plan, 2 re-plan with every dense split-K sum as its own launch
+    // (debugging), 3 re-plan without the fused pilot bottleneck (bit-identical gradients to plan 0)
+    bool replan, keep_slabs, bn, pair;
+    long long g_in, g_w, g_b;       // the pair's strides: eq -> corr tensors, conv3d_3 (eq) -> conv3d_2 (corr) kernels / biases
+    bool rides;                     // `input:0` is the single-pass kernel's (eq_norm_rides_ok)
+    bool pre;                       // the previous step ran it for this batch on its optimizer launch (x_prenormalised)
+    int nslot;
+    // the next batch's generator as a rider of this step (dccn_eq_buffers.gen_next_rides): on the bottleneck backward launch
+    // when the plan has it (ga: its argument block), else as the step's first launch (same batch either way)
+    bool gen_wanted, gen_rides;
+    GenStaticArgs ga;
+    bool want_snr;
+    // the frozen receiver: its layout and its linear part as this step runs it (input rows, weights, bias, k extent)
+    dccn_rx_shape rsh;
+    RxLayout L;
+    bool few_rx, folded;
+    const float *rxA, *rxW, *rxb;
+    int rxK;
+    bool fin_deferred;              // training: the tail's metric reduction rides on the optimizer launch
+    // the tail is the one stage whose kernels depend on the modulation: the chains of a group run it class by class -- one
+    // launch (pair) per distinct nbits, carrying the chains cls[c] of that modulation -- everything else is one launch for
+    // all of them.  fin_class: the metric reduction each chain's optimizer-launch job runs.
+    int n_class, fin_class[kMaxChains], cls_nbits[4];
+    bool cls_fused[4];              // dense + tail (or + decision) in one launch, else dense and then a stand-alone kernel
+    ChainCtx cls[4];
+    // `input:0` of the next batch on the optimizer launch: x_next, or (y, noise, partials) of the fused generator (nv)
+    bool next_rides;
+    const float* rin;
+    NormVirtual nv;
+    bool has_mon;                   // the training loop's per-step monitors on the optimizer launch (dccn_eq_buffers.monitor)
+    EqMonitorArgs mon;
+};
+// what one phase of the step leaves for the next: where the launches put their partial results, and which element-wise
+// stages the GEMMs took onto their stores
+struct EqStepCarry {
+    PowerPartials pp;
+    TailFinalizeArgs fin[4];
+    bool snr_pending;               // the pilot monitor runs on the optimizer launch
+    DeferredSlabs ds5, dsT, ds4, ds3, ds2, ds1, ds0;        // (null slabs: the gradient arena holds the result)
+    FoldDefer fpair[2], fconv;
+    bool rode_T, rode[2];           // the smoothing kernel's fold / dense_4 / dense_3 were updated by riders of the bottleneck backward
+};
+
+// launches nothing
+static int eq_step_plan(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool train, const dccn_receive_out* ro,
+                        EqStepPlan* plan) {
     if (!b->x || (!ro && !b->bits) || !b->eq_params || !b->rx_params || !b->out_eq || !b->chest || (!ro && !b->metrics))
         return DCCN_ERR_INVALID_ARG;
     if (ro && (train || !ro->packed)) return DCCN_ERR_INVALID_ARG;
     if (ro && tl_chain.G > 1) return DCCN_ERR_UNSUPPORTED;
     if (train && (!b->eq_grads || !b->adam_m || !b->adam_v || !b->adam)) return DCCN_ERR_INVALID_ARG;
-    if (!b->workspace || b->workspace_bytes < eq_ws_bytes(sh, train ? 1 : 0)) return DCCN_ERR_WORKSPACE;
-    const EqDims d = eq_dims(sh);
+    EqStepPlan& p = *plan;
+    p = EqStepPlan{};
+    const EqDims& d = p.d = eq_dims(sh);
     Carver c(b->workspace, b->workspace_bytes);
-    EqWs w;
-    eq_carve(c, sh, d, train, w);
-    const float* P = b->eq_params;
-    float* G = b->eq_grads;
-    const int B = d.B, R = d.R, K = d.K, SK2 = d.SK2, K2 = 2 * d.K, N2 = 2 * d.nsc;
-    const long long nBK = (long long)B * SK2;          // floats in a [B,S,K,2] tensor
-    dccn_rx_shape rsh;
-    rsh.batch = B; rsh.S = d.S; rsh.kin = d.cp ? d.nsc : K; rsh.F = d.F; rsh.D = d.D; rsh.nbits = sh->nbits;
-    const int kin0 = d.cp ? N2 : K2;                   // K extent of the first dense layer
-    const RxLayout L = rx_layout(&rsh);
-    const float* Q = b->rx_params;
-    float* h = b->chest;
-
-    // round-3 plan (TUNE_EQ_REPLAN): merged element-wise launches, the corr / eq C-Conv pair as grouped launches with the
-    // concat / split of model.py:456 in the GEMM stores, ONE job-table launch for every gradient reduction + Adam
-    // TUNE_EQ_REPLAN: 0 launch-per-stage plan, 1 re-plan, 2 re-plan with every dense split-K sum as its own launch
-    // (debugging), 3 re-plan without the fused pilot bottleneck (bit-identical gradients to plan 0)
-    const int plan = g_tune[TUNE_EQ_REPLAN];
-    const bool replan = plan != 0;
-    const bool keep_slabs = plan == 1 || plan == 3;
-    const bool bn = plan == 1 && eq_bottleneck_ok(B, SK2, d.Pp, w.y, P + d.o[4], P + d.o[6]) && aligned16(w.d1);
-    const long long g_in = w.corr - w.eq;                                  // eq -> corr stride of the pair's tensors
-    const long long g_w = d.o[14] - d.o[16], g_b = d.o[15] - d.o[17];      // conv3d_3 (eq) -> conv3d_2 (corr)
-    const bool pair = replan && cconv_pair_ok(w.eq, P + d.o[16], w.cat, R, K, K, g_in, g_w, 2) && aligned16(w.corr) &&
-                      (g_b % 2 == 0);
-
-    // the next batch's generator as a rider of this step (dccn_eq_buffers.gen_next_rides): on the bottleneck backward launch
-    // when the plan has it, else as a launch of its own right here (same batch either way)
-    bool gen_done = false;
-    const bool gen_wanted = train && b->gen_next_rides != 0;
-    if (gen_wanted && b->x_next_virtual == nullptr) return DCCN_ERR_INVALID_ARG;
-    const bool gen_rides = gen_wanted && bn && gen_static_ok(b->x_next_virtual);
-    if (gen_wanted && !gen_rides) {
-        if (tl_chain.G > 1) return DCCN_ERR_UNSUPPORTED;
-        DCCN_TRY(gen_static_launch(b->x_next_virtual, s));
-        gen_done = true;
+    eq_carve(c, sh, d, train, p.w);
+    if (!b->workspace || b->workspace_bytes < align_up(c.off, 256)) return DCCN_ERR_WORKSPACE;
+    const EqWs& w = p.w;
+    const float *P = b->eq_params, *Q = b->rx_params;
+    const int B = d.B, ncols = d.S * 2 * d.nsc;
+    p.train = train; p.ro = ro;
+    const int knob = g_tune[TUNE_EQ_REPLAN];
+    p.replan = knob != 0; p.keep_slabs = knob == 1 || knob == 3;
+    p.bn = eq_bn_ok(d, w.y, P + d.o[4], P + d.o[6], w.d1);
+    if (train) p.bnp = eq_bn_parts(w.bn_part, B, d.SK2, d.Pp);
+    p.g_in = w.corr - w.eq; p.g_w = d.o[14] - d.o[16]; p.g_b = d.o[15] - d.o[17];
+    p.pair = p.replan && cconv_pair_ok(w.eq, P + d.o[16], w.cat, d.R, d.K, d.K, p.g_in, p.g_w, 2) && aligned16(w.corr) &&
+             (p.g_b % 2 == 0);
+    const dccn_gen_static* gv = b->x_next_virtual;
+    p.gen_wanted = train && b->gen_next_rides != 0;
+    if (p.gen_wanted && gv == nullptr) return DCCN_ERR_INVALID_ARG;
+    p.gen_rides = p.gen_wanted && p.bn && gen_static_ok(gv);
+    if (p.gen_wanted && !p.gen_rides && tl_chain.G > 1) return DCCN_ERR_UNSUPPORTED;
+    if (p.gen_wanted) DCCN_TRY(gen_static_args(gv, &p.ga));
+    p.rides = eq_norm_rides_ok(d, train, b->x, w.x_norm);
+    p.pre = p.rides && b->x_prenormalised != 0;
+    if (b->x_prenormalised != 0 && !p.pre) return DCCN_ERR_INVALID_ARG;
+    p.nslot = b->norm_slot ? 1 : 0;
+    p.want_snr = b->snr_db && b->pilot_carriers && sh->P > 0;
+    p.rsh = eq_rx_shape(d, sh->nbits);
+    const RxLayout& L = p.L = rx_layout(&p.rsh);
+    const float* Mf = b->rx_folded;
+    p.few_rx = eq_few_rx_ok(d, L, w.fft, Q, w.z);
+    p.folded = Mf != nullptr && eq_rx_folded_ok(d, p.few_rx, Mf, b->out_eq);
+    p.rxA = p.folded ? b->out_eq : w.fft;
+    p.rxW = p.folded ? Mf : Q + L.o_dense_w;
+    p.rxb = p.folded ? Mf + (size_t)ncols * L.dN : Q + L.o_dense_b;
+    p.rxK = p.folded ? ncols : L.dK;
+    p.fin_deferred = p.replan && train;
+    const ChainCtx& all = tl_chain;
+    if (all.G > 1 && !eq_group_ok(p.rides, p.bn, p.folded)) return DCCN_ERR_UNSUPPORTED;
+    bool done[kMaxChains] = {false, false, false, false, false, false, false, false};
+    for (int g = 0; g < all.G; ++g) {
+        if (done[g]) continue;
+        if (p.n_class >= 4) return DCCN_ERR_INVALID_ARG;
+        const int nbits = all.G == 1 ? sh->nbits : all.nbits[g];
+        ChainCtx& sub = p.cls[p.n_class];
+        sub = all;
+        sub.G = 0;
+        for (int h = g; h < all.G; ++h) {
+            if (all.nbits[h] != all.nbits[g]) continue;
+            sub.co.off[sub.G] = all.co.off[h]; sub.nbits[sub.G] = all.nbits[h];
+            ++sub.G;
+            done[h] = true;
+            p.fin_class[h] = p.n_class;
+        }
+        p.cls_nbits[p.n_class] = nbits;
+        // BPSK / QPSK: the tail rides on the few-row tiles themselves (dense_tail_impl picks the fewrow.h form for <= 96 rows)
+        p.cls_fused[p.n_class] = (!p.few_rx || nbits <= 2) && dense_tail_planned(nbits, train, B, L.dN) &&
+                                 dense_tail_ok(p.rxA, p.rxW, B, p.rxK, L.dN, nbits);
+        ++p.n_class;
     }
+    if (ro) {
+        // what dense_decide_impl / decide_impl ask of the outputs; the stand-alone decision kernel reads z as float2
+        if (!decide_outputs_aligned(ro->llr, ro->prob, sh->nbits)) return DCCN_ERR_INVALID_ARG;
+        if (!(p.cls_fused[0] && sh->nbits <= 2) && (reinterpret_cast<uintptr_t>(w.z) & 7u) != 0) return DCCN_ERR_INVALID_ARG;
+    }
+    p.nv = norm_virtual_none();
+    if (p.fin_deferred) {               // (the launch-per-stage plan has no optimizer launch that could carry either)
+        if (gv != nullptr && (!gv->y || !gv->noise || !gv->power_partial || gv->frames != B ||
+                              2 * (gv->K + gv->CP) * gv->S != ncols))
+            return DCCN_ERR_INVALID_ARG;
+        p.rin = gv ? gv->y : b->x_next;
+        p.next_rides = p.rides && p.rin != nullptr && norm_fused_ok(p.rin, w.x_norm, B, ncols);
+        if (gv != nullptr && !p.next_rides) return DCCN_ERR_INVALID_ARG;    // nothing else would form that batch: ask dccn_eq_norm_rides first
+        if (gv != nullptr) p.nv = norm_virtual_gen(gv, ceil_div(gv->frames, kGenFramesPerBlock), nullptr);
+        if (const dccn_eq_monitor* m = b->monitor) {
+            if (!m->chan || !m->acc5 || m->chest != b->chest || m->metrics != b->metrics || m->tx_power != b->tx_power || m->B != B ||
+                m->S != d.S || m->K != d.K || !m->workspace || m->workspace_bytes < dccn_eq_monitor_workspace_size(B, d.S, d.K))
+                return DCCN_ERR_INVALID_ARG;
+            EqMonitorArgs& ma = p.mon;
+            ma.chest = m->chest; ma.chan = m->chan; ma.gt_per_symbol = m->chan_per_symbol ? 1 : 0; ma.B = B; ma.S = d.S; ma.K = d.K;
+            ma.metrics = m->metrics; ma.tx_power = m->tx_power; ma.noise_power = m->noise_power; ma.acc = m->acc5; ma.rms_out = m->rms_out;
+            ma.counter = static_cast<unsigned*>(m->workspace);
+            ma.partial = reinterpret_cast<double*>(static_cast<char*>(m->workspace) + 256);
+            p.has_mon = true;
+        }
+    }
+    // invariants of the step's own carve and plan: the gradients of the pair's tensors lie as far apart as the tensors, and a
+    // generator that rides has the bottleneck backward launch to ride on
+    if (train && p.pair && w.dcorr - w.deq != p.g_in) return DCCN_ERR_STATE;
+    if (p.gen_rides && !p.bn) return DCCN_ERR_STATE;
+    return DCCN_OK;
+}
+
+// the generator / R0 launch through dense_5: equalizer_ofdm (model.py:349-478)
+static int eq_issue_forward(const dccn_eq_shape* sh, const dccn_eq_buffers* b, const EqStepPlan& p, dccn_adam_hparams hp,
+                            hipStream_t s, EqStepCarry* k) {
+    const EqDims& d = p.d;
+    const EqWs& w = p.w;
+    const float* P = b->eq_params;
+    float* h = b->chest;
+    const int B = d.B, R = d.R, K = d.K, SK2 = d.SK2, K2 = 2 * d.K, N2 = 2 * d.nsc, ncols = d.S * N2;
+    const long long nBK = (long long)B * SK2;          // floats in a [B,S,K,2] tensor
+    if (p.gen_wanted && !p.gen_rides) DCCN_TRY(gen_static_launch(b->x_next_virtual, s));
     // `input:0` (ofdmreceiver_np.py:128-137) + tx_power partials
-    PowerPartials pp;
     // (training: the optimizer's per-step bookkeeping rides on this first launch)
     // pipelined: the previous step ran this launch for us on its optimizer launch (dccn_eq_buffers.x_next)
-    const int ncols = d.S * N2;
-    const bool rides = replan && train && norm_fused_ok(b->x, w.x_norm, B, ncols) && kNormFusedCG == 2;
-    const bool pre = rides && b->x_prenormalised != 0;
-    if (b->x_prenormalised != 0 && !pre) return DCCN_ERR_INVALID_ARG;
-    const int nslot = b->norm_slot ? 1 : 0;
-    if (pre) norm_power_partials(B, ncols, w.ws_norm, w.n_norm, b->x, w.x_norm, &pp, nslot);
-    else DCCN_TRY(norm_impl(b->x, w.x_norm, nullptr, nullptr, !ro && b->tx_power != nullptr, &pp, B, ncols, 1e-9f, 8.0f,
-                            train ? b->adam : nullptr, hp, w.ws_norm, w.n_norm, s, nslot));
+    if (p.pre) norm_power_partials(B, ncols, w.ws_norm, w.n_norm, b->x, w.x_norm, &k->pp, p.nslot);
+    else DCCN_TRY(norm_impl(b->x, w.x_norm, nullptr, nullptr, !p.ro && b->tx_power != nullptr, &k->pp, B, ncols, 1e-9f, 8.0f,
+                            p.train ? b->adam : nullptr, hp, w.ws_norm, w.n_norm, s, p.nslot));
     // model.py:363 layer_norm, :369 dense, :378 C-Conv "DFT"; the expansion of the :428 smoothing C-Conv (S x K, same)
     // into the block-Toeplitz matrix of a dense layer depends on the parameters only and shares the launch
-    if (replan) {
+    if (p.replan) {
         DCCN_LAUNCH_CHAINS_Z(eq_prep_kernel, dim3(B + ew_blocks_n((long long)SK2 * SK2)), dim3(256), 0, s, (const float*)w.x_norm,
-                             w.ln, B, d.S * N2, 1e-12f, P + d.o[12], P + d.o[13], w.T, w.be, d.S, K,
-                             pre ? b->adam : (dccn_adam_state*)nullptr, hp);
+                             w.ln, B, ncols, 1e-12f, P + d.o[12], P + d.o[13], w.T, w.be, d.S, K,
+                             p.pre ? b->adam : (dccn_adam_state*)nullptr, hp);
         DCCN_LAUNCH_CHECK();
     } else {
         DCCN_NO_CHAINS();
         hipLaunchKernelGGL(layer_norm_fwd_kernel, dim3(B), dim3(256), 0, s, (const float*)w.x_norm, w.ln, (float*)nullptr,
-                           (float*)nullptr, d.S * N2, 1e-12f);
+                           (float*)nullptr, ncols, 1e-12f);
         DCCN_LAUNCH_CHECK();
     }
-    DCCN_TRY(dense_fwd_impl(w.ln + d.win, P + d.o[0], P + d.o[1], w.t1, R, kin0, K2, s, N2));
+    DCCN_TRY(dense_fwd_impl(w.ln + d.win, P + d.o[0], P + d.o[1], w.t1, R, d.cp ? N2 : K2, K2, s, N2));
     DCCN_TRY(cconv_fwd_impl(w.t1, P + d.o[2], P + d.o[3], w.y, R, K, K, s));
     // :394-426 pilot bottleneck
-    if (bn) {                               // both layers of the bottleneck in one launch (eq_bottleneck.h)
+    if (p.bn) {                             // both layers of the bottleneck in one launch (eq_bottleneck.h)
         auto kern = d.Pp == 32 ? eq_bottleneck_fwd_kernel<2> : eq_bottleneck_fwd_kernel<1>;
         const int q = eq_bottleneck_q(B, SK2);
         DCCN_LAUNCH_CHAINS_Z(kern, dim3(ceil_div(SK2 / 16, q), ceil_div(B, 16)), dim3(256), 0, s, (const float*)w.y, P + d.o[4],
@@ -268,7 +416,7 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
         }
     }
     // :428 smoothing C-Conv as a dense layer -> channel estimate
-    if (!replan) {
+    if (!p.replan) {
         DCCN_NO_CHAINS();
         hipLaunchKernelGGL(cconv2d_same_expand_kernel, dim3(ew_blocks_n((long long)SK2 * SK2)), dim3(256), 0, s,
                            P + d.o[12], P + d.o[13], w.T, w.be, d.S, K, d.S, K);
@@ -276,20 +424,13 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
     }
     // :431-438 equalise + autocorrelation ride on the store of this GEMM when the plan has the stage; the :465-475 pilot
     // monitor then runs on the optimizer launch (training) or as its own small launch (evaluation)
-    const bool want_snr = b->snr_db && b->pilot_carriers && sh->P > 0;
-    bool eq_fused = false, snr_pending = false;
-    if (replan) DCCN_TRY(dense_fwd_impl(w.d4, w.T, w.be, h, B, SK2, SK2, s, 0, 5, &eq_fused, w.y, w.eq, w.corr));
+    bool eq_fused = false, snr_now = false;
+    if (p.replan) DCCN_TRY(dense_fwd_impl(w.d4, w.T, w.be, h, B, SK2, SK2, s, 0, 5, &eq_fused, w.y, w.eq, w.corr));
     else DCCN_TRY(dense_fwd_impl(w.d4, w.T, w.be, h, B, SK2, SK2, s));
     if (eq_fused) {
-        if (want_snr && train) {
-            snr_pending = true;
-        } else if (want_snr) {
-            DCCN_NO_CHAINS();
-            hipLaunchKernelGGL(pilot_snr_kernel, dim3(B), dim3(64), 0, s, (const float2*)w.eq, b->pilot_carriers, b->snr_db,
-                               d.S, K, sh->P);
-            DCCN_LAUNCH_CHECK();
-        }
-    } else if (replan && want_snr) {
+        k->snr_pending = p.want_snr && p.train;
+        snr_now = p.want_snr && !p.train;
+    } else if (p.replan && p.want_snr) {
         const int eb = (int)ew_blocks_n(nBK / 2);
         DCCN_NO_CHAINS();
         hipLaunchKernelGGL(equalize_fwd_snr_kernel, dim3(eb + ceil_div(B, 4)), dim3(256), 0, s, (const float2*)w.y,
@@ -301,17 +442,18 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
         hipLaunchKernelGGL(equalize_fwd_kernel, dim3(ew_blocks_n(nBK / 2)), dim3(256), 0, s, (const float2*)w.y,
                            (const float2*)h, (float2*)w.eq, (float2*)w.corr, nBK / 2);
         DCCN_LAUNCH_CHECK();
-        if (want_snr) {
-            DCCN_NO_CHAINS();
-            hipLaunchKernelGGL(pilot_snr_kernel, dim3(B), dim3(64), 0, s, (const float2*)w.eq, b->pilot_carriers, b->snr_db,
-                               d.S, K, sh->P);
-            DCCN_LAUNCH_CHECK();
-        }
+        snr_now = p.want_snr;
+    }
+    if (snr_now) {
+        DCCN_NO_CHAINS();
+        hipLaunchKernelGGL(pilot_snr_kernel, dim3(B), dim3(64), 0, s, (const float2*)w.eq, b->pilot_carriers, b->snr_db, d.S, K,
+                           sh->P);
+        DCCN_LAUNCH_CHECK();
     }
     // :439-449 C-Conv "IDFT" of corr and eq, :456-463 concat + dense back to the receiver's input
-    if (pair) {
+    if (p.pair) {
         // both C-Convs in one grid; their stores interleave the two IQ-pair streams into cat = [.., K, (eq, corr)]
-        DCCN_TRY(cconv_fwd_grouped_impl(w.eq, P + d.o[16], P + d.o[17], w.cat, R, K, K, 2, g_in, g_w, g_b, true, s));
+        DCCN_TRY(cconv_fwd_grouped_impl(w.eq, P + d.o[16], P + d.o[17], w.cat, R, K, K, 2, p.g_in, p.g_w, p.g_b, true, s));
     } else {
         DCCN_TRY(cconv_fwd_impl(w.corr, P + d.o[14], P + d.o[15], w.corc, R, K, K, s));
         DCCN_TRY(cconv_fwd_impl(w.eq, P + d.o[16], P + d.o[17], w.eqc, R, K, K, s));
@@ -320,88 +462,48 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
                            (const float2*)w.corc, (float4*)w.cat, (long long)R * K);
         DCCN_LAUNCH_CHECK();
     }
-    DCCN_TRY(dense_fwd_impl(w.cat, P + d.o[18], P + d.o[19], b->out_eq, R, 4 * K, N2, s));
-    // frozen basic receiver (model.py:1222-1292) + loss/BER
-    // few rows (73 frames): the fused dense + tail launch is 20 tiles of 48x64 behind a 14-tile k-loop (23 us); the
-    // one-latency 16x16 tiles of fewrow.h (200 blocks) followed by the stand-alone tail launch take about half of that
-    const bool few_rx = g_tune[TUNE_FEWROW] && g_tune[TUNE_SKINNY] > 0 && B <= 96 && (L.dK % 16) == 0 && L.dK >= 128 &&
-                        L.dK <= 1152 && (L.dN % 16) == 0 && aligned16(w.fft) && aligned16(Q + L.o_dense_w) && aligned16(w.z);
-    // ... and with the receiver's C-Conv and dense layer folded into one matrix (dccn_eq_rx_fold: the receiver is frozen)
-    // both run as ONE such GEMM over the flattened frame, K = S * 2 n_sc
-    const float* Mf = b->rx_folded;
-    const int fK = d.S * N2;
-    const bool folded = few_rx && Mf != nullptr && g_tune[TUNE_FEWROW] >= 1 && aligned16(Mf) && aligned16(b->out_eq) &&
-                        (fK % 16) == 0 && fK <= 1152;
-    if (!folded) DCCN_TRY(cconv_fwd_impl(b->out_eq + d.win, Q + L.o_conv_w, Q + L.o_conv_b, w.fft, R, rsh.kin, d.F, s, N2));
-    // the tail is the one stage whose kernels depend on the modulation: the chains of a group (common.h ChainCtx) run it class by
-    // class -- one launch (pair) per distinct nbits, carrying the chains of that modulation -- everything else is one launch
-    // for all of them.  fin[c] / fin_class: the metric reduction each chain's optimizer-launch job runs.
-    TailFinalizeArgs fin[4];
-    int fin_class[kMaxChains] = {0, 0, 0, 0, 0, 0, 0, 0}, n_class = 0;
-    const bool fin_deferred = replan && train;   // training: the tail's metric reduction rides on the optimizer launch
-    // the receiver's linear part as this step runs it: (input rows, weights, bias, k extent)
-    const float* rxA = folded ? b->out_eq : w.fft;
-    const float* rxW = folded ? Mf : Q + L.o_dense_w;
-    const float* rxb = folded ? Mf + (size_t)fK * L.dN : Q + L.o_dense_b;
-    const int rxK = folded ? fK : L.dK;
-    auto tail_section = [&](const int nbits, TailFinalizeArgs* fin_out) -> int {
-        // BPSK / QPSK: the tail rides on the few-row tiles themselves (dense_tail_impl picks the fewrow.h form for <= 96 rows)
-        const bool few_tail = few_rx && nbits <= 2 && dense_tail_ok(rxA, rxW, B, rxK, L.dN, nbits);
-        if ((few_tail || !few_rx) && dense_tail_planned(nbits, train, B, L.dN) &&
-            dense_tail_ok(rxA, rxW, B, rxK, L.dN, nbits)) {                      // dense + tail in one launch
-            DCCN_TRY(dense_tail_impl(train, rxA, rxW, rxb, nullptr, b->bits, Q + L.o_tail, b->prob,
-                                     b->metrics, train ? w.dz : nullptr, train ? w.dtail : nullptr, B, rxK, L.dN, nbits,
-                                     &pp, b->tx_power, w.ws_tail, w.n_tail, s, fin_deferred ? fin_out : nullptr));
-        } else {
-            if (folded) DCCN_TRY(dense_fwd_impl(b->out_eq, Mf, Mf + (size_t)fK * L.dN, w.z, B, fK, L.dN, s));
-            else DCCN_TRY(dense_fwd_impl(w.fft, Q + L.o_dense_w, Q + L.o_dense_b, w.z, B, L.dK, L.dN, s));
-            DCCN_TRY(tail_impl(train, w.z, b->bits, Q + L.o_tail, b->prob, b->metrics, train ? w.dz : nullptr,
-                               train ? w.dtail : nullptr, L.cells, nbits, &pp, b->tx_power, w.ws_tail, w.n_tail, s,
-                               fin_deferred ? fin_out : nullptr));
-        }
-        return DCCN_OK;
-    };
-    if (ro) {
-        // the same choice between the one-launch form and dense + stand-alone kernel as tail_section makes: same bits in z
-        const int nbits = sh->nbits;
-        const bool few_tail = few_rx && nbits <= 2 && dense_tail_ok(rxA, rxW, B, rxK, L.dN, nbits);
-        if ((few_tail || !few_rx) && dense_tail_planned(nbits, false, B, L.dN) && dense_tail_ok(rxA, rxW, B, rxK, L.dN, nbits))
-            return dense_decide_impl(rxA, rxW, rxb, nbits >= 3 ? w.z : nullptr, Q + L.o_tail, ro->packed, ro->llr, ro->prob, B, rxK,
-                                     L.dN, nbits, s);
-        if (folded) DCCN_TRY(dense_fwd_impl(b->out_eq, Mf, Mf + (size_t)fK * L.dN, w.z, B, fK, L.dN, s));
-        else DCCN_TRY(dense_fwd_impl(w.fft, Q + L.o_dense_w, Q + L.o_dense_b, w.z, B, L.dK, L.dN, s));
-        return decide_impl(w.z, Q + L.o_tail, ro->packed, ro->llr, ro->prob, B, d.D, nbits, s);
-    }
-    if (tl_chain.G == 1) {
-        DCCN_TRY(tail_section(sh->nbits, &fin[0]));
-        n_class = 1;
-    } else {
-        if (!folded || !fin_deferred) return DCCN_ERR_UNSUPPORTED;
-        const ChainCtx all = tl_chain;
-        bool done[kMaxChains] = {false, false, false, false, false, false, false, false};
-        for (int g = 0; g < all.G; ++g) {
-            if (done[g]) continue;
-            if (n_class >= 4) return DCCN_ERR_INVALID_ARG;
-            ChainCtx sub = all;
-            sub.G = 0;
-            for (int h = g; h < all.G; ++h) {
-                if (all.nbits[h] != all.nbits[g]) continue;
-                sub.co.off[sub.G] = all.co.off[h]; sub.nbits[sub.G] = all.nbits[h];
-                ++sub.G;
-                done[h] = true;
-                fin_class[h] = n_class;
-            }
-            ChainScope scope(sub);
-            DCCN_TRY(tail_section(all.nbits[g], &fin[n_class]));
-            ++n_class;
-        }
-    }
-    if (!train) return DCCN_OK;
+    return dense_fwd_impl(w.cat, P + d.o[18], P + d.o[19], b->out_eq, R, 4 * K, N2, s);
+}
 
-    // ---- backward: through the frozen receiver to its input ...
-    if (folded) {
+// the frozen basic receiver (model.py:1222-1292) for the chains of modulation class c: + loss/BER through the tail (evaluation,
+// training), or the decision stage in its place (receive: the same route, so z has the bits the evaluation step computes)
+static int eq_issue_rx(const dccn_eq_buffers* b, const EqStepPlan& p, int c, hipStream_t s, EqStepCarry* k) {
+    const EqWs& w = p.w;
+    const RxLayout& L = p.L;
+    const float* Q = b->rx_params;
+    const dccn_receive_out* ro = p.ro;
+    const int B = p.d.B, nbits = p.cls_nbits[c];
+    const bool train = p.train;
+    TailFinalizeArgs* fin = p.fin_deferred ? &k->fin[c] : nullptr;
+    const ChainScope scope(p.cls[c]);
+    if (!p.folded)
+        DCCN_TRY(cconv_fwd_impl(b->out_eq + p.d.win, Q + L.o_conv_w, Q + L.o_conv_b, w.fft, p.d.R, p.rsh.kin, p.d.F, s, 2 * p.d.nsc));
+    if (p.cls_fused[c]) {
+        if (ro)
+            return dense_decide_impl(p.rxA, p.rxW, p.rxb, nbits >= 3 ? w.z : nullptr, Q + L.o_tail, ro->packed, ro->llr, ro->prob, B,
+                                     p.rxK, L.dN, nbits, s);
+        return dense_tail_impl(train, p.rxA, p.rxW, p.rxb, nullptr, b->bits, Q + L.o_tail, b->prob, b->metrics, train ? w.dz : nullptr,
+                               train ? w.dtail : nullptr, B, p.rxK, L.dN, nbits, &k->pp, b->tx_power, w.ws_tail, w.n_tail, s, fin);
+    }
+    DCCN_TRY(dense_fwd_impl(p.rxA, p.rxW, p.rxb, w.z, B, p.rxK, L.dN, s));
+    if (ro) return decide_impl(w.z, Q + L.o_tail, ro->packed, ro->llr, ro->prob, B, p.d.D, nbits, s);
+    return tail_impl(train, w.z, b->bits, Q + L.o_tail, b->prob, b->metrics, train ? w.dz : nullptr, train ? w.dtail : nullptr,
+                     L.cells, nbits, &k->pp, b->tx_power, w.ws_tail, w.n_tail, s, fin);
+}
+
+// through the frozen receiver to its input, then the equaliser, last layer first
+static int eq_issue_backward(const dccn_eq_buffers* b, const EqStepPlan& p, dccn_adam_hparams hp, hipStream_t s, EqStepCarry* k) {
+    const EqDims& d = p.d;
+    const EqWs& w = p.w;
+    const RxLayout& L = p.L;
+    const float *P = b->eq_params, *Q = b->rx_params;
+    float* G = b->eq_grads;
+    const int B = d.B, R = d.R, K = d.K, SK2 = d.SK2, K2 = 2 * d.K, N2 = 2 * d.nsc;
+    const long long nBK = (long long)B * SK2;
+    const bool keep_slabs = p.keep_slabs, pair = p.pair;
+    if (p.folded) {
         // dout = dz . Mf^T in one GEMM (the zero rows of Mf leave zeros in the cyclic-prefix samples when cp = 0)
-        DCCN_TRY(dense_bwd_x_impl(w.dz, Mf, w.dout, B, fK, L.dN, s));
+        DCCN_TRY(dense_bwd_x_impl(w.dz, p.rxW, w.dout, B, p.rxK, L.dN, s));
     } else {
         DCCN_TRY(dense_bwd_x_impl(w.dz, Q + L.o_dense_w, w.dfft, B, L.dK, L.dN, s));
         if (!d.cp) {                                        // nothing flows back into the cyclic-prefix samples
@@ -410,16 +512,13 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
                                (long long)R * N2);
             DCCN_LAUNCH_CHECK();
         }
-        DCCN_TRY(cconv_bwd_x_impl(w.dfft, Q + L.o_conv_w, w.dout + d.win, R, rsh.kin, d.F, s, N2));
+        DCCN_TRY(cconv_bwd_x_impl(w.dfft, Q + L.o_conv_w, w.dout + d.win, R, p.rsh.kin, d.F, s, N2));
     }
-    // ... then the equaliser, last layer first.  replan: every weight gradient stays where its GEMM left it (finished
-    // in the gradient arena, or as split-K slabs in the layer's own workspace) until the optimizer launch
-    DeferredSlabs ds5{}, dsT{}, ds4{}, ds3{}, ds2{}, ds1{}, ds0{};       // (null slabs: the gradient arena holds the result)
-    FoldDefer fpair[2], fconv;
-    fpair[0].slabs = fpair[1].slabs = fconv.slabs = nullptr;
+    // replan: every weight gradient stays where its GEMM left it (finished in the gradient arena, or as split-K slabs in the
+    // layer's own workspace) until the optimizer launch
     bool split_done = false;                // dcat's stores write deqc / dcorc themselves (when the plan has the stage)
     DCCN_TRY(dense_bwd_full_impl(w.cat, w.dout, P + d.o[18], w.dcat, G + d.o[18], G + d.o[19], R, 4 * K, N2,
-                                 w.ws_l[EQL_DENSE5], w.n_l[EQL_DENSE5], s, 1, nullptr, nullptr, keep_slabs ? &ds5 : nullptr,
+                                 w.ws_l[EQL_DENSE5], w.n_l[EQL_DENSE5], s, 1, nullptr, nullptr, keep_slabs ? &k->ds5 : nullptr,
                                  pair ? w.deqc : nullptr, pair ? (long long)(w.dcorc - w.deqc) : 0, pair ? &split_done : nullptr));
     if (!split_done) {
         DCCN_NO_CHAINS();
@@ -429,9 +528,8 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
     }
     if (pair) {
         // dX and dWeff slabs of both C-Convs in one grid (group 0 = eq, 1 = corr)
-        DCCN_TRY(cconv_bwd_grouped_impl(w.eq, w.deqc, P + d.o[16], w.deq, R, K, K, 2, g_in, w.dcorc - w.deqc, g_w,
-                                        w.ws_l[EQL_PAIR], w.n_l[EQL_PAIR], fpair, s));
-        if (w.dcorr - w.deq != g_in) return DCCN_ERR_STATE;
+        DCCN_TRY(cconv_bwd_grouped_impl(w.eq, w.deqc, P + d.o[16], w.deq, R, K, K, 2, p.g_in, w.dcorc - w.deqc, p.g_w,
+                                        w.ws_l[EQL_PAIR], w.n_l[EQL_PAIR], k->fpair, s));
     } else {
         DCCN_TRY(cconv_bwd_x_impl(w.deqc, P + d.o[16], w.deq, R, K, K, s));
         DCCN_TRY(cconv_bwd_w_impl(w.eq, w.deqc, G + d.o[16], G + d.o[17], R, K, K, w.ws_l[EQL_PAIR], w.n_l[EQL_PAIR], s));
@@ -439,10 +537,11 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
         DCCN_TRY(cconv_bwd_w_impl(w.corr, w.dcorc, G + d.o[14], G + d.o[15], R, K, K, w.ws_l[EQL_PAIR], w.n_l[EQL_PAIR], s));
     }
     DCCN_LAUNCH_CHAINS_Z(equalize_bwd_kernel, dim3(ew_blocks_n(nBK / 2)), dim3(256), 0, s, (const float2*)w.y,
-                         (const float2*)h, (const float2*)w.deq, (const float2*)w.dcorr, (float2*)w.dy, (float2*)w.dh,
+                         (const float2*)b->chest, (const float2*)w.deq, (const float2*)w.dcorr, (float2*)w.dy, (float2*)w.dh,
                          nBK / 2);
     DCCN_LAUNCH_CHECK();
     bool tg_fused = false;                  // tanh gradient on the dX store: dd4 = (dh . T^T) (1 - d4^2)
+    DeferredSlabs& dsT = k->dsT;
     DCCN_TRY(dense_bwd_full_impl(w.d4, w.dh, w.T, w.dd4, w.dT, w.dbe, B, SK2, SK2, w.ws_l[EQL_SMOOTH], w.n_l[EQL_SMOOTH], s, 3,
                                  w.d4, &tg_fused, keep_slabs ? &dsT : nullptr));
     if (dsT.dw_slabs) {
@@ -452,7 +551,7 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
         DCCN_TRY(launch_splitk_reduce2(dsT.dw_slabs, dsT.splits, n, w.dT, n, dsT.db_slabs, (long long)SK2, w.dbe, (long long)SK2, s));
         dsT.dw_slabs = dsT.db_slabs = nullptr;
     }
-    if (!replan) {
+    if (!p.replan) {
         DCCN_NO_CHAINS();
         hipLaunchKernelGGL(cconv2d_same_reduce_kernel, dim3(d.S * K + 1), dim3(64), 0, s, (const float*)w.dT,
                            (const float*)w.dbe, G + d.o[12], G + d.o[13], d.S, K, d.S, K);
@@ -465,18 +564,11 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
         DCCN_LAUNCH_CHECK();
     }
     DCCN_TRY(dense_bwd_full_impl(w.d3, w.dd4, P + d.o[10], w.dd3, G + d.o[10], G + d.o[11], B, SK2, SK2, w.ws_l[EQL_DENSE4],
-                                 w.n_l[EQL_DENSE4], s, 1, nullptr, nullptr, keep_slabs ? &ds4 : nullptr));
+                                 w.n_l[EQL_DENSE4], s, 1, nullptr, nullptr, keep_slabs ? &k->ds4 : nullptr));
     DCCN_TRY(dense_bwd_full_impl(w.d2, w.dd3, P + d.o[8], w.dd2, G + d.o[8], G + d.o[9], B, SK2, SK2, w.ws_l[EQL_DENSE3],
-                                 w.n_l[EQL_DENSE3], s, 1, nullptr, nullptr, keep_slabs ? &ds3 : nullptr));
+                                 w.n_l[EQL_DENSE3], s, 1, nullptr, nullptr, keep_slabs ? &k->ds3 : nullptr));
     const float* dy_sum;
-    bool rode_T = false;                                        // the smoothing kernel's fold rode as well
-    bool rode[2] = {false, false};                              // dense_4 / dense_3 kernels updated by riders (below)
-    const int bn_tiles = ceil_div(B, 16);
-    float* bn_w2 = w.bn_part;                                   // [tiles][P][SK2]
-    float* bn_b2 = bn_w2 + (size_t)bn_tiles * d.Pp * SK2;       // [tiles][SK2]
-    float* bn_w1 = bn_b2 + (size_t)bn_tiles * SK2;              // [tiles][SK2][P]
-    float* bn_b1 = bn_w1 + (size_t)bn_tiles * SK2 * d.Pp;       // [tiles][P]
-    if (bn) {
+    if (p.bn) {
         // both layers' backward in one launch: dd1, the branch's input gradient added to dy, per-block partials of the
         // four weight / bias gradients (summed by the optimizer launch)
         auto kern = d.Pp == 32 ? eq_bottleneck_bwd_kernel<2> : eq_bottleneck_bwd_kernel<1>;
@@ -496,31 +588,27 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
                 J.off = d.o[12]; J.off_b = d.o[13]; J.src = w.dT; J.src2 = w.dbe; J.slab = (long long)SK2 * SK2; J.slab2 = SK2;
                 J.kin = d.S; J.F = K;
                 ride.blocks += J.blocks;
-                rode_T = true;
+                k->rode_T = true;
             }
             for (int li = 0; li < 2; ++li) {
                 const int i = li == 0 ? 10 : 8;
-                const DeferredSlabs& dsl = li == 0 ? ds4 : ds3;
+                const DeferredSlabs& dsl = li == 0 ? k->ds4 : k->ds3;
                 if (dsl.dw_slabs != nullptr || (d.sz[i] % 4) != 0) continue;
                 if (g_tune[TUNE_EQ_RIDERS] == 2 + li) continue;          // 2: only dense_3 rides, 3: only dense_4
-
                 EqOptJob& J = ride.job[ride.njobs++];
                 J.kind = EQJ_SUM; J.block0 = ride.blocks; J.blocks = EqOptBuilder::stream_blocks(d.sz[i]); J.splits = 1;
                 J.off = d.o[i]; J.n = d.sz[i]; J.vec = 1; J.reg_uniform = (b->reg_uniform != 0 && b->reg_coef != nullptr) ? 1 : 0;
                 ride.blocks += J.blocks;
-                rode[li] = true;
+                k->rode[li] = true;
             }
         }
         // the NEXT batch's generator rides here as well (dccn_eq_buffers.gen_next_rides): its workgroups are the first grid rows
-        GenStaticArgs ga;
         GenChainScalars gc;
-        memset(&ga, 0, sizeof(ga));
         memset(&gc, 0, sizeof(gc));
         int gen_rows = 0, gen_blocks = 0;
         size_t gen_smem = 0;
-        if (gen_rides) {
-            DCCN_TRY(gen_static_args(b->x_next_virtual, &ga));
-            gen_blocks = ceil_div(b->x_next_virtual->frames, kGenFramesPerBlock);
+        if (p.gen_rides) {
+            gen_blocks = ceil_div(p.ga.frames, kGenFramesPerBlock);
             gen_rows = ceil_div(gen_blocks, nx);
             gen_smem = gen_static_smem_bytes<7, 64, 16>();
             if (tl_chain.G > 1) {
@@ -529,21 +617,21 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
                     gc.nbits[g] = tl_chain.gen_nbits[g]; gc.offset[g] = tl_chain.gen_offset[g]; gc.seed[g] = tl_chain.gen_seed[g];
                 }
             }
-            gen_done = true;
         }
-        DCCN_LAUNCH_CHAINS_Z(kern, dim3(nx, gen_rows + bn_tiles + ceil_div(ride.blocks, nx)), dim3(256), gen_smem, s,
+        DCCN_LAUNCH_CHAINS_Z(kern, dim3(nx, gen_rows + p.bnp.tiles + ceil_div(ride.blocks, nx)), dim3(256), gen_smem, s,
                              (const float*)w.dd2, (const float*)w.d1, (const float*)w.y, P + d.o[4], P + d.o[6], (const float*)w.dy,
-                             w.dflat, bn_w2, bn_b2, bn_w1, bn_b1, B, SK2, q, bn_tiles, ride, hp, gen_rows, gen_blocks, ga, gc);
+                             w.dflat, p.bnp.w2, p.bnp.b2, p.bnp.w1, p.bnp.b1, B, SK2, q, p.bnp.tiles, ride, hp, gen_rows, gen_blocks,
+                             p.ga, gc);
         DCCN_LAUNCH_CHECK();
         dy_sum = w.dflat;
     } else {
         DCCN_TRY(dense_bwd_full_impl(w.d1, w.dd2, P + d.o[6], w.dd1, G + d.o[6], G + d.o[7], B, d.Pp, SK2, w.ws_l[EQL_DENSE2],
-                                     w.n_l[EQL_DENSE2], s, 1, nullptr, nullptr, keep_slabs ? &ds2 : nullptr));
+                                     w.n_l[EQL_DENSE2], s, 1, nullptr, nullptr, keep_slabs ? &k->ds2 : nullptr));
         // dy += (gradient through the pilot branch): by the dX stores themselves when the launch plan has the stage (the sum
         // then lands in dflat), else by a launch of its own
         bool add_fused = false;
         DCCN_TRY(dense_bwd_full_impl(w.y, w.dd1, P + d.o[4], w.dflat, G + d.o[4], G + d.o[5], B, SK2, d.Pp, w.ws_l[EQL_DENSE1],
-                                     w.n_l[EQL_DENSE1], s, 4, w.dy, &add_fused, keep_slabs ? &ds1 : nullptr));
+                                     w.n_l[EQL_DENSE1], s, 4, w.dy, &add_fused, keep_slabs ? &k->ds1 : nullptr));
         if (!add_fused) {
             DCCN_NO_CHAINS();
             hipLaunchKernelGGL(add_inplace_kernel, dim3(ew_blocks_n(nBK)), dim3(256), 0, s, w.dy, (const float*)w.dflat, nBK);
@@ -551,85 +639,87 @@ static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
         }
         dy_sum = add_fused ? w.dflat : w.dy;
     }
-    const bool conv_grouped = replan && cconv_pair_ok(w.t1, P + d.o[2], w.dt1, R, K, K, 0, 0, 0) && aligned16(dy_sum);
+    const bool conv_grouped = p.replan && cconv_pair_ok(w.t1, P + d.o[2], w.dt1, R, K, K, 0, 0, 0) && aligned16(dy_sum);
     if (conv_grouped) {
         DCCN_TRY(cconv_bwd_grouped_impl(w.t1, dy_sum, P + d.o[2], w.dt1, R, K, K, 1, 0, 0, 0, w.ws_l[EQL_CONV], w.n_l[EQL_CONV],
-                                        &fconv, s));
+                                        &k->fconv, s));
     } else {
         DCCN_TRY(cconv_bwd_x_impl(dy_sum, P + d.o[2], w.dt1, R, K, K, s));
         DCCN_TRY(cconv_bwd_w_impl(w.t1, dy_sum, G + d.o[2], G + d.o[3], R, K, K, w.ws_l[EQL_CONV], w.n_l[EQL_CONV], s));
     }
-    DCCN_TRY(dense_bwd_w_impl(w.ln + d.win, w.dt1, G + d.o[0], G + d.o[1], R, kin0, K2, w.ws_l[EQL_DENSE], w.n_l[EQL_DENSE], s,
-                              keep_slabs ? &ds0 : nullptr, N2));
-    // optimizer: Equalizer/* only (ofdmreceiver_np_mp.py:330), L2 terms enter through reg_coef
-    if (!replan) return adam_impl(b->eq_params, G, b->adam_m, b->adam_v, b->reg_coef, nullptr, b->adam, hp, d.o[20], s, false);
+    return dense_bwd_w_impl(w.ln + d.win, w.dt1, G + d.o[0], G + d.o[1], R, d.cp ? N2 : K2, K2, w.ws_l[EQL_DENSE], w.n_l[EQL_DENSE], s,
+                            keep_slabs ? &k->ds0 : nullptr, N2);
+}
+
+// optimizer: Equalizer/* only (ofdmreceiver_np_mp.py:330), L2 terms enter through reg_coef.  The re-plan's ONE launch walks a
+// job table: every gradient reduction + Adam, `input:0` of the next batch, the monitors, the tail's metric reduction
+static int eq_issue_update(const dccn_eq_shape* sh, const dccn_eq_buffers* b, const EqStepPlan& p, dccn_adam_hparams hp,
+                           hipStream_t s, EqStepCarry* k) {
+    const EqDims& d = p.d;
+    const EqWs& w = p.w;
+    const int B = d.B, K = d.K, SK2 = d.SK2, ncols = d.S * 2 * d.nsc;
+    if (!p.replan)
+        return adam_impl(b->eq_params, b->eq_grads, b->adam_m, b->adam_v, b->reg_coef, nullptr, b->adam, hp, d.o[20], s, false);
     EqOptBuilder ob;
     memset(&ob.a, 0, sizeof(ob.a));
-    ob.a.param = b->eq_params; ob.a.grad = G; ob.a.m = b->adam_m; ob.a.v = b->adam_v; ob.a.reg_coef = b->reg_coef;
+    ob.a.param = b->eq_params; ob.a.grad = b->eq_grads; ob.a.m = b->adam_m; ob.a.v = b->adam_v; ob.a.reg_coef = b->reg_coef;
     ob.a.state = b->adam;
     const bool uni = b->reg_uniform != 0 && b->reg_coef != nullptr;
-    const dccn_gen_static* gv = b->x_next_virtual;
-    if (gv != nullptr && (!gv->y || !gv->noise || !gv->power_partial || gv->frames != B ||
-                          2 * (gv->K + gv->CP) * gv->S != ncols))
-        return DCCN_ERR_INVALID_ARG;
-    const float* rin = gv ? gv->y : b->x_next;
-    if (rides && rin != nullptr && norm_fused_ok(rin, w.x_norm, B, ncols)) {
-        // `input:0` of the next batch: x_norm is read by the layer norm only, long before this launch
+    if (p.next_rides) {
+        // x_norm is read by the layer norm only, long before this launch
         PowerPartials pn;
-        norm_power_partials(B, ncols, w.ws_norm, w.n_norm, rin, w.x_norm, &pn, nslot ^ 1);
-        NormVirtual nv = norm_virtual_none();
-        if (gv) {                                       // (y, noise, partials) of the fused generator as the input: norm_adam.h
-            nv.y = gv->y; nv.noise = gv->noise; nv.ppart = gv->power_partial;
-            nv.npart = ceil_div(gv->frames, kGenFramesPerBlock);
-            nv.total = (double)gv->frames * (double)(gv->S * (gv->K + gv->CP));
-            nv.npart_noise = gv->noise_partial; nv.n_noise = nv.npart;
-            nv.npow_out = gv->noise_partial ? gv->noise_power_out : nullptr;
-        }
-        ob.norm_next(rin, w.x_norm, B, ncols, b->tx_power != nullptr ? const_cast<double*>(pn.partial) : nullptr,
-                     norm_fused_blocks(ncols), nv);
-    } else if (gv != nullptr) {
-        return DCCN_ERR_INVALID_ARG;                    // nothing else would form that batch: ask dccn_eq_norm_rides first
+        norm_power_partials(B, ncols, w.ws_norm, w.n_norm, p.rin, w.x_norm, &pn, p.nslot ^ 1);
+        ob.norm_next(p.rin, w.x_norm, B, ncols, b->tx_power != nullptr ? const_cast<double*>(pn.partial) : nullptr,
+                     norm_fused_blocks(ncols), p.nv);
     }
-    eq_opt_dense(ob, d, 0, ds0, K2, uni);
+    eq_opt_dense(ob, d, 0, k->ds0, 2 * K, uni);
+    const FoldDefer& fconv = k->fconv;
     if (fconv.slabs) ob.cconv_fold(d.o[2], d.o[3], fconv.slabs, fconv.colsum, fconv.splits, fconv.slab, K, K);
     else { ob.plain(d.o[2], d.sz[2]); ob.plain(d.o[3], d.sz[3]); }
-    if (bn) {
-        ob.slabs(d.o[4], d.sz[4], bn_w1, bn_tiles, (long long)SK2 * d.Pp, uni);
-        ob.slabs(d.o[5], d.sz[5], bn_b1, bn_tiles, d.Pp, uni);
-        ob.slabs(d.o[6], d.sz[6], bn_w2, bn_tiles, (long long)d.Pp * SK2, uni);
-        ob.slabs(d.o[7], d.sz[7], bn_b2, bn_tiles, SK2, uni);
+    if (p.bn) {
+        const EqBnParts& q = p.bnp;
+        ob.slabs(d.o[4], d.sz[4], q.w1, q.tiles, (long long)SK2 * d.Pp, uni);
+        ob.slabs(d.o[5], d.sz[5], q.b1, q.tiles, d.Pp, uni);
+        ob.slabs(d.o[6], d.sz[6], q.w2, q.tiles, (long long)d.Pp * SK2, uni);
+        ob.slabs(d.o[7], d.sz[7], q.b2, q.tiles, SK2, uni);
     } else {
-        eq_opt_dense(ob, d, 4, ds1, d.Pp, uni);
-        eq_opt_dense(ob, d, 6, ds2, SK2, uni);
+        eq_opt_dense(ob, d, 4, k->ds1, d.Pp, uni);
+        eq_opt_dense(ob, d, 6, k->ds2, SK2, uni);
     }
-    eq_opt_dense(ob, d, 8, ds3, SK2, uni, rode[1]);
-    eq_opt_dense(ob, d, 10, ds4, SK2, uni, rode[0]);
-    if (!rode_T)
-    ob.conv2d_fold(d.o[12], d.o[13], dsT.dw_slabs ? dsT.dw_slabs : w.dT, (dsT.dw_slabs && dsT.db_slabs) ? dsT.db_slabs : w.dbe,
-                   dsT.dw_slabs ? dsT.splits : 1, (long long)SK2 * SK2, SK2, d.S, K);
+    eq_opt_dense(ob, d, 8, k->ds3, SK2, uni, k->rode[1]);
+    eq_opt_dense(ob, d, 10, k->ds4, SK2, uni, k->rode[0]);
+    const DeferredSlabs& dsT = k->dsT;
+    if (!k->rode_T)
+        ob.conv2d_fold(d.o[12], d.o[13], dsT.dw_slabs ? dsT.dw_slabs : w.dT, (dsT.dw_slabs && dsT.db_slabs) ? dsT.db_slabs : w.dbe,
+                       dsT.dw_slabs ? dsT.splits : 1, (long long)SK2 * SK2, SK2, d.S, K);
     for (int g = 1; g >= 0; --g) {          // arena order: conv3d_2 (corr, group 1), then conv3d_3 (eq, group 0)
         const int i = g == 1 ? 14 : 16;
-        if (fpair[g].slabs) ob.cconv_fold(d.o[i], d.o[i + 1], fpair[g].slabs, fpair[g].colsum, fpair[g].splits, fpair[g].slab, K, K);
+        const FoldDefer& f = k->fpair[g];
+        if (f.slabs) ob.cconv_fold(d.o[i], d.o[i + 1], f.slabs, f.colsum, f.splits, f.slab, K, K);
         else { ob.plain(d.o[i], d.sz[i]); ob.plain(d.o[i + 1], d.sz[i + 1]); }
     }
-    eq_opt_dense(ob, d, 18, ds5, N2, uni);
-    // the training loop's per-step monitors (dccn_eq_monitor_accumulate) as part of this launch: dccn_eq_buffers.monitor
-    if (b->monitor != nullptr) {
-        const dccn_eq_monitor* m = b->monitor;
-        if (!fin_deferred || !m->chan || !m->acc5 || m->chest != b->chest || m->metrics != b->metrics || m->B != B || m->S != d.S ||
-            m->K != K || !m->workspace || m->workspace_bytes < dccn_eq_monitor_workspace_size(B, d.S, K))
-            return DCCN_ERR_INVALID_ARG;
-        EqMonitorArgs ma;
-        ma.chest = m->chest; ma.chan = m->chan; ma.gt_per_symbol = m->chan_per_symbol ? 1 : 0; ma.B = B; ma.S = d.S; ma.K = K;
-        ma.metrics = m->metrics; ma.tx_power = m->tx_power; ma.noise_power = m->noise_power; ma.acc = m->acc5; ma.rms_out = m->rms_out;
-        ma.counter = static_cast<unsigned*>(m->workspace);
-        ma.partial = reinterpret_cast<double*>(static_cast<char*>(m->workspace) + 256);
-        ob.monitor(ma, eq_monitor_blocks(B, K));
-        for (int c = 0; c < n_class; ++c) { fin[c].mon_acc = m->acc5; fin[c].mon_noise = m->noise_power; }
-        if (m->tx_power != b->tx_power) return DCCN_ERR_INVALID_ARG;
+    eq_opt_dense(ob, d, 18, k->ds5, 2 * d.nsc, uni);
+    if (p.has_mon) {
+        ob.monitor(p.mon, eq_monitor_blocks(B, K));
+        for (int c = 0; c < p.n_class; ++c) { k->fin[c].mon_acc = p.mon.acc; k->fin[c].mon_noise = p.mon.noise_power; }
     }
-    if (fin_deferred) ob.tail_finalize(fin, n_class, fin_class);
-    if (snr_pending) ob.pilot_snr(w.eq, b->pilot_carriers, b->snr_db, B, d.S, K, sh->P);
-    if (gen_wanted && !gen_done) return DCCN_ERR_STATE;
+    ob.tail_finalize(k->fin, p.n_class, p.fin_class);
+    if (k->snr_pending) ob.pilot_snr(w.eq, b->pilot_carriers, b->snr_db, B, d.S, K, sh->P);
     return launch_eq_opt(ob, hp, s);
+}
+
+// ro != nullptr: the receive path (dccn_eq_receive_step): the evaluation step's forward with the tail section replaced by the
+// decision stage (decide.h) -- no labels, no metrics; bits / metrics / prob / tx_power of `b` are not touched
+static int eq_step_impl(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool train, dccn_adam_hparams hp,
+                        hipStream_t s, const dccn_receive_out* ro = nullptr) {
+    if (!eq_shape_ok(sh) || !b) return DCCN_ERR_INVALID_ARG;
+    const TuneScope tune(b->tuning);
+    EqStepPlan plan;
+    DCCN_TRY(eq_step_plan(sh, b, train, ro, &plan));
+    EqStepCarry k{};
+    DCCN_TRY(eq_issue_forward(sh, b, plan, hp, s, &k));
+    for (int c = 0; c < plan.n_class; ++c) DCCN_TRY(eq_issue_rx(b, plan, c, s, &k));
+    if (!train) return DCCN_OK;
+    DCCN_TRY(eq_issue_backward(b, plan, hp, s, &k));
+    return eq_issue_update(sh, b, plan, hp, s, &k);
 }

@@ -539,7 +539,8 @@ int dccn_dense_decide_fwd(const float* x, const float* w, const float* bias, flo
                           dccn_stream_t stream);
 /* The basic receiver's receive step: R0 -> C-Conv forward -> dense + decision.  Three launches where dccn_rx_receive_fused
  * answers 1 (BPSK / QPSK wherever the evaluation step fuses its tail, up to 1536 frames), one more otherwise.  x_norm and
- * fft_out are bitwise what dccn_rx_eval_step writes for the same x and params. */
+ * fft_out are bitwise what dccn_rx_eval_step writes for the same x and params.  A buffer set that misses the alignment above, or
+ * lacks z where it is needed, is refused (DCCN_ERR_INVALID_ARG) before anything is launched. */
 typedef struct dccn_rx_receive_buffers {
     const float* x;            /* [batch, S, kin, 2] */
     const float* params;       /* the receiver's arena (dccn_rx_param_offsets) */
@@ -662,6 +663,8 @@ typedef struct dccn_eq_shape {
 } dccn_eq_shape;
 
 struct dccn_eq_monitor;
+/* Every step that takes a dccn_eq_buffers (eager, grouped, or captured by dccn_eq_graph_create) checks all of it first: a
+ * call that is refused (any status but DCCN_OK for something the caller passed in) is refused before anything is launched. */
 typedef struct dccn_eq_buffers {
     const float* x;               /* [batch,S,n_sc,2] raw `tx_ofdm` */
     const int32_t* bits;          /* [batch,D,nbits] */
@@ -755,7 +758,8 @@ int dccn_eq_train_step(const dccn_eq_shape* shape, const dccn_eq_buffers* buf, d
 /* The chain's receive step (see "receive path" above): the equaliser forward exactly as dccn_eq_eval_step runs it -- out_eq,
  * chest (and snr_db) are written as that step writes them -- and the frozen receiver with the decision stage in place of the
  * tail: buf->bits, buf->metrics, buf->prob and buf->tx_power may be NULL and are not touched.  Workspace: the evaluation
- * step's.  Chain groups are not supported here (DCCN_ERR_UNSUPPORTED). */
+ * step's.  Chain groups are not supported here (DCCN_ERR_UNSUPPORTED).  llr / prob that miss the alignment of the decision
+ * stage (see "receive path" above) are refused (DCCN_ERR_INVALID_ARG) before anything is launched. */
 typedef struct dccn_receive_out {
     unsigned char* packed;     /* [batch, ceil(D*nbits/8)] */
     float* llr;                /* [batch, D, nbits], nullable */
@@ -777,8 +781,10 @@ int dccn_eq_receive_step(const dccn_eq_shape* shape, const dccn_eq_buffers* buf,
  * ChainArena).  `prob` must be NULL; rx_folded must be given.  Every chain computes exactly what dccn_eq_train_step would
  * compute for it alone: same kernels, same blocks, same summation orders -- bitwise equal parameters, Adam slots and
  * metrics (tests/test_gpu_chain_groups.py).  n_chains == 1 is dccn_eq_train_step.
- * dccn_eq_group_supported: 1 for the shapes whose step consists of group-capable launches only (<= 96 frames: the few-row plan);
- * a grouped call that would reach any other launch returns DCCN_ERR_UNSUPPORTED before issuing it. */
+ * dccn_eq_group_supported: 1 exactly for the shapes whose grouped step is accepted under the current knobs, given 16-byte aligned
+ * buffers: the step consists of group-capable launches only (<= 96 frames: the few-row plan with the pilot bottleneck as one
+ * launch per direction and the receiver folded).  Elsewhere a grouped call returns DCCN_ERR_UNSUPPORTED before anything is
+ * launched. */
 int dccn_chain_group_max(void);
 int dccn_eq_group_supported(const dccn_eq_shape* shape);
 int dccn_eq_train_step_grouped(int n_chains, const dccn_eq_shape* const* shapes, const dccn_eq_buffers* const* bufs,
