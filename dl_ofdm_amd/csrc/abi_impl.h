@@ -203,6 +203,7 @@ int eq_monitor_blocks(int B, int K);
 int gen_static_args(const dccn_gen_static* g, GenStaticArgs* out);
 int gen_static_launch(const dccn_gen_static* g, hipStream_t s, const GenChainScalars* chains = nullptr);
 bool gen_static_ok(const dccn_gen_static* g);
+bool gen_static_doppler(const dccn_gen_static* g);       // the frame plan holds Doppler frames (the Doppler instantiation)
 int norm_fused_blocks(int cols);
 bool norm_fused_ok(const float* x, const float* y, int batch, int cols);
 int norm_impl(const float* x, float* y, float* mean, float* var, bool want_power, PowerPartials* pp, int batch, int cols, float eps, float peak, dccn_adam_state* adam, dccn_adam_hparams hp, void* ws, size_t ws_bytes, hipStream_t s, int slot = 0);

@@ -15,6 +15,7 @@ namespace dccn {
 
 constexpr unsigned kPhiloxM0 = 0xD2511F53u, kPhiloxM1 = 0xCD9E8D57u, kPhiloxW0 = 0x9E3779B9u, kPhiloxW1 = 0xBB67AE85u;
 constexpr int kStreamBits = 0, kStreamTaps = 1, kStreamNoise = 2, kStreamDoppler = 3;
+constexpr int kSinusoids = 48;            // Jakes sum-of-sinusoids terms (radio.py:376-407)
 
 struct Philox4 {
     unsigned v[4];
@@ -290,8 +291,8 @@ static __global__ __launch_bounds__(256) void awgn_kernel(const float2* __restri
 // the receiver step reads (y, noise, partials) as its virtual input (norm_adam.h NormVirtual), or gen_static_apply_kernel
 // materialises x where a buffer is wanted.
 constexpr int kGenMaxProfiles = 6;
-struct GenProfile {                 // one static fading profile: tap amplitudes, sinc interpolation [n_taps, L]; identity: g = [1]
-    const float* coeff; const float* alpha; int n_taps, L, identity, pad_;
+struct GenProfile {                 // one fading profile: tap amplitudes, sinc interpolation [n_taps, L]; identity: g = [1];
+    const float* coeff; const float* alpha; int n_taps, L, identity; float Fd;      // Fd: its Doppler frequency (Doppler frames)
 };
 struct GenStaticArgs {
     int32_t* bits_out; const int* cell_map; const float2* const_tab; float2 pilot; const float* idft;
@@ -299,12 +300,16 @@ struct GenStaticArgs {
     // tap_stride: taps per frame in the Philox index of the tap draws (channel_taps_kernel's)
     GenProfile prof[kGenMaxProfiles]; int n_prof, tap_stride;
     float2* H; int h_rep;           // nullable: fft(g, K) per frame, h_rep copies (channel_taps_kernel's arithmetic)
+    // Doppler frames (radio.py:376-407, 438-452; the Doppler instantiation only): frame f is one when dop_period > 0,
+    // f % dop_period == 0 and its profile has Fd > 0.1 and is not the identity; t_sym: seconds per OFDM symbol
+    int dop_period;
     const float* snr_db;
     float2* y; float2* noise; double* power_partial; double* noise_partial; float* tx_out;
     int frames, S, K, CP, D, nbits;
     unsigned offset; unsigned long long seed;
     int abl;            // timing ablations (DCCN_GEN_ABL, experiments only: results are wrong when set): 1 no noise draws, 2 no
                         // label draws, 4 no ifft matrix loads, 8 no FIR
+    float t_sym;        // (dop_period and t_sym sit where the struct had padding: the static launch's argument block is unchanged)
     __device__ __forceinline__ GenStaticArgs at_chain(const long long coff) const {     // chain groups (common.h)
         GenStaticArgs q = *this;
         q.bits_out = chain_at(bits_out, coff); q.cell_map = chain_at(cell_map, coff); q.const_tab = chain_at(const_tab, coff);
@@ -348,7 +353,14 @@ constexpr int kGenFirPad = 64;             // >= the longest channel response th
     GenProfile P1 = (a0).prof[((block) * kGenFramesPerBlock + (((a0).frames - (block) * kGenFramesPerBlock) > 1 ? 1 : 0)) % (a0).n_prof]; \
     P0.coeff = chain_at(P0.coeff, coff); P0.alpha = chain_at(P0.alpha, coff);                                   \
     P1.coeff = chain_at(P1.coeff, coff); P1.alpha = chain_at(P1.alpha, coff);
-template <int S, int K, int CP>
+// DOPPLER (its own instantiation; static descriptors keep launching the DOPPLER = false code): a frame of the block can be a
+// Doppler frame (GenStaticArgs::dop_period; block-uniform per frame, as its profile is).  Such a frame takes, in the arithmetic
+// of doppler_taps_kernel / fir_doppler_kernel: its 2 x 48 x n_taps uniform phases (Philox stream 3, drawn once per frame, spread
+// over the block, into LDS next to Fd cos(a_n +- a0_k), which depends on (n, k) only); per symbol and tap the two 48-term cosine
+// sums (same order over n); g[s] = taps[s] . alpha (same order over k); H[s] = fft(g[s], K) from the twiddle table; and the
+// per-symbol 'same' FIR with n_taps samples of history on the time-domain frame in LDS.  Labels, ifft, noise, the partial sums
+// and the static frames of the same block are the code of the static instantiation.
+template <int S, int K, int CP, bool DOPPLER = false>
 __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, const GenProfile P0, const GenProfile P1, const int block) {
     extern __shared__ __attribute__((aligned(16))) float gsm[];
     constexpr int K2 = 2 * K, N2 = 2 * (K + CP), T = S * (K + CP), LDG = K2 + 4;
@@ -372,6 +384,22 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
     const int f0 = block * kGenFramesPerBlock;
     const int nfr = min(kGenFramesPerBlock, a.frames - f0);
     const int L0 = P0.identity ? 1 : P0.L, L1 = P1.identity ? 1 : P1.L;
+    // Doppler frames of the block (DeviceDataGen.frame_plan); dynamic LDS behind the time-domain frames:
+    bool dop0 = false, dop1 = false;
+    float2* sGd = nullptr;      // [2][S][64]      per-symbol impulse responses
+    float2* sTapD = nullptr;    // [2][S][16]      per-symbol taps
+    float* sTh = nullptr;       // [2][2][48][16]  phases theta[c][n][k]
+    float* sFc = nullptr;       // [2][2][48][16]  Fd cos(a_n + a0_k) (c = 0), Fd cos(a_n - a0_k) (c = 1)
+    if constexpr (DOPPLER) {
+        if (a.dop_period > 0) {
+            dop0 = (f0 % a.dop_period) == 0 && !P0.identity && P0.Fd > 0.1f;
+            dop1 = nfr > 1 && ((f0 + 1) % a.dop_period) == 0 && !P1.identity && P1.Fd > 0.1f;
+        }
+        sGd = sTX + kGenFramesPerBlock * TP;
+        sTapD = sGd + kGenFramesPerBlock * S * 64;
+        sTh = reinterpret_cast<float*>(sTapD + kGenFramesPerBlock * S * 16);
+        sFc = sTh + kGenFramesPerBlock * 2 * kSinusoids * 16;
+    }
     if (a.H != nullptr && tid < K) {
         float sn, cs;
         sincosf(-6.2831853071795864769f * (float)tid / (float)K, &sn, &cs);
@@ -427,11 +455,32 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
     }
     // 3 (early). static taps of the block's frames (threads 0..n_taps-1 of waves 0 / 1 draw frame 0 / 1)
     const GenProfile Pw = w == 0 ? P0 : P1;            // (waves 0 / 1 own the taps of frames 0 / 1)
-    if (w < nfr && !Pw.identity && lane < Pw.n_taps) {
+    const bool dopw = w == 0 ? dop0 : dop1;            // (false in the static instantiation)
+    if (w < nfr && !Pw.identity && lane < Pw.n_taps && !dopw) {
         const Philox4 p = philox4x32_10((unsigned long long)(f0 + w) * a.tap_stride + lane, kStreamTaps, a.offset, a.seed);
         const float2 z = box_muller(p.v[0], p.v[1]);
         const float cf = Pw.coeff[lane] * 0.70710678118654752440f;
         tap[w][lane] = make_float2(z.x * cf, z.y * cf);
+    }
+    // 3d (early). phases of the block's Doppler frames: theta[c][n][k] at index ((f 2 + c) 48 + n) tap_stride + k of stream 3
+    // (doppler_taps_kernel's draws), and the Doppler shift of sinusoid (n, k)
+    if constexpr (DOPPLER) {
+        const float step = 3.14159265358979323846f / (4.0f * kSinusoids);
+#pragma unroll
+        for (int j = 0; j < kGenFramesPerBlock; ++j) {
+            if (!(j == 0 ? dop0 : dop1)) continue;                      // (block-uniform)
+            const int nt = j == 0 ? P0.n_taps : P1.n_taps;
+            const float Fd = j == 0 ? P0.Fd : P1.Fd;
+            for (int e = tid; e < 2 * kSinusoids * nt; e += 256) {
+                const int cn = e / nt, k = e - cn * nt, cc = cn / kSinusoids, n = cn - cc * kSinusoids;
+                const unsigned long long pi = ((unsigned long long)(f0 + j) * 2 * kSinusoids + cn) * a.tap_stride + k;
+                const float th = 6.2831853071795864769f * uniform01(philox4x32_10(pi, kStreamDoppler, a.offset, a.seed).v[0]);
+                const float an = ((float)(n + 1) - 0.5f) * step, a0 = (float)(k + 1) * step;
+                const int o = (j * 2 * kSinusoids + cn) * 16 + k;
+                sTh[o] = th;
+                sFc[o] = Fd * cosf(cc == 0 ? an + a0 : an - a0);
+            }
+        }
     }
     // 1. resource grid: label bits (Philox word 0 of the cell), constellation / pilot / guard value
     {
@@ -463,7 +512,7 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
     if (w < kGenFramesPerBlock) {                      // g = taps . alpha (same order as channel_taps_kernel); zeros behind L:
         float2 acc = make_float2(0.f, 0.f);            // the FIR below runs both frames over the longer of the two responses
         const int Lw = w == 0 ? L0 : L1;
-        if (w < nfr && lane < Lw) {
+        if (w < nfr && lane < Lw && !dopw) {
             if (Pw.identity) {
                 acc = make_float2(lane == 0 ? 1.f : 0.f, 0.f);
             } else {
@@ -509,7 +558,39 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
             }
         }
     }
+    // 3d. Jakes taps of the Doppler frames: one (frame, re|im, symbol, tap) sum of 48 cosines per thread, n ascending
+    if constexpr (DOPPLER) {
+        const int nt0 = P0.n_taps, nt1 = P1.n_taps;
+        const int n0 = dop0 ? 2 * S * nt0 : 0, n1 = dop1 ? 2 * S * nt1 : 0;
+        for (int e = tid; e < n0 + n1; e += 256) {
+            const int j = e >= n0 ? 1 : 0, r = e - (j ? n0 : 0), nt = j ? nt1 : nt0;
+            const int cs = r / nt, k = r - cs * nt, cc = cs / S, sym = cs - cc * S;
+            const float t = (float)sym * a.t_sym;
+            const float* th = sTh + (j * 2 + cc) * kSinusoids * 16 + k;
+            const float* fc = sFc + (j * 2 + cc) * kSinusoids * 16 + k;
+            float sum = 0.f;
+            for (int n = 0; n < kSinusoids; ++n) sum += cosf(6.2831853071795864769f * t * fc[n * 16] + th[n * 16]);
+            const float cf = (j ? P1.coeff : P0.coeff)[k] * 0.14433756729740644113f;          // sqrt(1/48)
+            reinterpret_cast<float*>(sTapD + (j * S + sym) * 16 + k)[cc] = sum * cf;
+        }
+    }
     __syncthreads();
+    if constexpr (DOPPLER) {       // g[s] = taps[s] . alpha (k ascending)
+        const int n0 = dop0 ? S * P0.L : 0, n1 = dop1 ? S * P1.L : 0;
+        for (int e = tid; e < n0 + n1; e += 256) {
+            const int j = e >= n0 ? 1 : 0, r = e - (j ? n0 : 0), Lj = j ? P1.L : P0.L, nt = j ? P1.n_taps : P0.n_taps;
+            const int sym = r / Lj, l = r - sym * Lj;
+            const float* al = (j ? P1.alpha : P0.alpha) + l;
+            const float2* tp = sTapD + (j * S + sym) * 16;
+            float2 acc = make_float2(0.f, 0.f);
+            for (int k = 0; k < nt; ++k) {
+                const float wgt = al[k * Lj];
+                acc.x += tp[k].x * wgt;
+                acc.y += tp[k].y * wgt;
+            }
+            sGd[(j * S + sym) * 64 + l] = acc;
+        }
+    }
     if (a.tx_out != nullptr)
         for (int i = tid; i < nfr * 2 * T; i += 256) {
             const int fr = i / (2 * T);
@@ -517,9 +598,11 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
         }
     // 4. 'same' FIR (the loop of fir_same_kernel) and its power
     // frequency response of the block's frames (channel_taps_kernel's sum, its twiddles from the table: same arguments, same bits)
+    if constexpr (DOPPLER) __syncthreads();            // the per-symbol responses are complete
     if (a.H != nullptr) {
         for (int idx = tid; idx < nfr * K; idx += 256) {
             const int fr = idx / K, f = idx - fr * K, Lf = fr == 0 ? L0 : L1;
+            if (fr == 0 ? dop0 : dop1) continue;       // (a Doppler frame writes S distinct responses: below)
             float2 acc = make_float2(0.f, 0.f);
             for (int l = 0; l < Lf; ++l) {
                 const float2 t2 = tw[(f * l) % K], gl = gs[fr][l];
@@ -527,6 +610,20 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
                 acc.y += gl.x * t2.y + gl.y * t2.x;
             }
             for (int r = 0; r < a.h_rep; ++r) a.H[((size_t)(f0 + fr) * a.h_rep + r) * K + f] = acc;
+        }
+        if constexpr (DOPPLER) {                       // H[f, s] = fft(g[s], K) (doppler_taps_kernel's sum; h_rep == S)
+            for (int idx = tid; idx < nfr * S * K; idx += 256) {
+                const int fs = idx / K, f = idx - fs * K, fr = fs / S, Lf = fr == 0 ? L0 : L1;
+                if (!(fr == 0 ? dop0 : dop1)) continue;
+                const float2* gp = sGd + fs * 64;
+                float2 acc = make_float2(0.f, 0.f);
+                for (int l = 0; l < Lf; ++l) {
+                    const float2 t2 = tw[(f * l) % K], gl = gp[l];
+                    acc.x += gl.x * t2.x - gl.y * t2.y;
+                    acc.y += gl.x * t2.y + gl.y * t2.x;
+                }
+                a.H[((size_t)(f0 + fr) * S + (fs - fr * S)) * K + f] = acc;
+            }
         }
     }
     const int off0 = (L0 - 1) / 2, off1 = (L1 - 1) / 2, Lmax = max(L0, nfr > 1 ? L1 : 0);
@@ -538,10 +635,27 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
             const int i = min(tid + 256 * q, nfr * T - 1), fr = i / T, t = i - fr * T;
             const float2* xf = sTX + fr * TP + kGenFirPad + t + (fr == 0 ? off0 : off1);
             float2 acc = make_float2(0.f, 0.f);
-            for (int l = 0; l < ((a.abl & 8) ? 1 : Lmax); ++l) {
-                const float2 v = xf[-l], gl = gs[fr][l];
-                acc.x += gl.x * v.x - gl.y * v.y;
-                acc.y += gl.x * v.y + gl.y * v.x;
+            if constexpr (DOPPLER) {
+                // a static frame: its own L taps (the terms the static instantiation adds behind L are zeros).  A Doppler frame:
+                // fir_doppler_kernel's window r = tl + off - l in [-n_taps, n_sc) of symbol t / n_sc, l ascending; what lies
+                // before the frame's first sample is the zero pad
+                constexpr int NSC = K + CP;
+                const bool dp = fr == 0 ? dop0 : dop1;
+                const int Lf = fr == 0 ? L0 : L1, sym = t / NSC, r0 = t - sym * NSC + (fr == 0 ? off0 : off1);
+                const int ntf = fr == 0 ? P0.n_taps : P1.n_taps;
+                const int lo = dp ? max(0, r0 - NSC + 1) : 0, hi = dp ? min(Lf - 1, r0 + ntf) : Lf - 1;
+                const float2* gp = dp ? sGd + (fr * S + sym) * 64 : gs[fr];
+                for (int l = lo; l <= hi; ++l) {
+                    const float2 v = xf[-l], gl = gp[l];
+                    acc.x += gl.x * v.x - gl.y * v.y;
+                    acc.y += gl.x * v.y + gl.y * v.x;
+                }
+            } else {
+                for (int l = 0; l < ((a.abl & 8) ? 1 : Lmax); ++l) {
+                    const float2 v = xf[-l], gl = gs[fr][l];
+                    acc.x += gl.x * v.x - gl.y * v.y;
+                    acc.y += gl.x * v.y + gl.y * v.x;
+                }
             }
             yv[q] = acc;
         }
@@ -572,6 +686,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                                                                                                            const ChainOffs co) {
     DCCN_GEN_ARGS_OF_CHAIN(a, P0, P1, a0, gc, co.off[blockIdx.z], blockIdx.z, (int)blockIdx.x)
     gen_static_frames_body<S, K, CP>(a, P0, P1, (int)blockIdx.x);
+}
+// the launch for descriptors with Doppler frames.  33.5 KB of LDS more than the static launch (per-symbol responses 7 KB, taps
+// 1.75 KB, phases 12 KB, Doppler shifts 12 KB): 54.9 KB per workgroup, two workgroups per CU instead of the static launch's
+// three -- 512 resident workgroups, which a 73-frame batch (37) never reaches and a 1170-frame batch (585) passes either way
+template <int S, int K, int CP>
+constexpr size_t gen_doppler_smem_bytes() {
+    return gen_static_smem_bytes<S, K, CP>() + (size_t)kGenFramesPerBlock * (S * 64 + S * 16) * sizeof(float2) +
+           (size_t)2 * kGenFramesPerBlock * 2 * kSinusoids * 16 * sizeof(float);
+}
+template <int S, int K, int CP>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gen_doppler_frames_kernel(const GenStaticArgs a0, const GenChainScalars gc,
+                                                                                                            const ChainOffs co) {
+    DCCN_GEN_ARGS_OF_CHAIN(a, P0, P1, a0, gc, co.off[blockIdx.z], blockIdx.z, (int)blockIdx.x)
+    gen_static_frames_body<S, K, CP, true>(a, P0, P1, (int)blockIdx.x);
 }
 // x = y / sqrt(mean |y|^2) + noise where a buffer is wanted (the first batch of a pipelined loop, tests, iq dumps): the
 // expression of awgn_kernel on the generator's y and noise.  grid: any; 256 threads.
@@ -643,7 +771,6 @@ static __global__ __launch_bounds__(256) void ingraph_awgn_kernel(const float2* 
 //   mu_re = sqrt(1/48) sum_n cos(2 pi t Fd cos(a_n + a0_k) + th_re[n,k]),  a_n = (n - 0.5) pi / (4*48), a0_k = k pi/(4*48)
 //   mu_im likewise with cos(a_n - a0_k) and th_im;  tap = (mu_re + i mu_im) coeff_k;  g[s] = taps[s] . alpha;  H[s] = fft(g[s])
 // theta_in [frames, 2, 48, n_taps] (uniform phases in [0, 2 pi)) == nullptr: draw them.  One block per frame.
-constexpr int kSinusoids = 48;
 static __global__ __launch_bounds__(64) void doppler_taps_kernel(const float* __restrict__ theta_in,
                                                           const float* __restrict__ coeff,
                                                           const float* __restrict__ alpha, float2* __restrict__ g,

@@ -1160,7 +1160,16 @@ static bool overlap_streams(OverlapStreams* o) {
     return true;
 }
 
-// ---- fused static-channel generator launch (datagen.h gen_static_frames_kernel; ABI entry points further down) ----
+// ---- fused generator launch (datagen.h gen_static_frames_kernel / gen_doppler_frames_kernel; ABI entry points further down) ----
+// does the descriptor's frame plan hold Doppler frames?  (doppler_period > 0 and a profile that is not the identity with
+// Fd > 0.1: DeviceDataGen.frame_plan.)  Such a descriptor takes the Doppler instantiation of the launch.
+bool gen_static_doppler(const dccn_gen_static* g) {
+    if (!g || g->doppler_period <= 0) return false;
+    if (g->n_profiles == 0) return !g->identity && g->Fd > 0.1f;
+    for (int i = 0; i < g->n_profiles; ++i)
+        if (!g->profiles[i].identity && g->profiles[i].Fd > 0.1f) return true;
+    return false;
+}
 bool gen_static_ok(const dccn_gen_static* g) {
     if (!g || !g->bits_out || !g->cell_map || !g->const_tab || !g->idft || !g->snr_db || !g->y || !g->noise || !g->power_partial)
         return false;
@@ -1179,6 +1188,15 @@ bool gen_static_ok(const dccn_gen_static* g) {
         if (q.L <= 0 || q.L > 64) return false;
         if (!q.identity && (!q.coeff || !q.alpha || q.n_taps <= 0 || q.n_taps > 16 || g->tap_stride < q.n_taps)) return false;
     }
+    // Doppler frames: a period, a symbol time and finite Doppler frequencies; a Doppler frame writes S distinct responses
+    if (g->doppler_period < 0) return false;
+    if (g->doppler_period > 0) {
+        if (!(g->t_sym > 0.f) || !std::isfinite(g->t_sym)) return false;
+        if (g->n_profiles == 0 && !std::isfinite(g->Fd)) return false;
+        for (int i = 0; i < g->n_profiles; ++i)
+            if (!std::isfinite(g->profiles[i].Fd)) return false;
+        if (gen_static_doppler(g) && g->H_out && g->h_rep != g->S) return false;
+    }
     // the instantiated shape: the reference's N = 64 frame with the long cyclic prefix, 7 symbols x (64 + 16) samples
     return g->S == 7 && g->K == 64 && g->CP == 16 && aligned16(g->y) && aligned16(g->noise);
 }
@@ -1193,18 +1211,20 @@ int gen_static_args(const dccn_gen_static* g, GenStaticArgs* out) {
     memset(a.prof, 0, sizeof(a.prof));
     if (g->n_profiles == 0) {
         a.prof[0].coeff = g->coeff; a.prof[0].alpha = g->alpha; a.prof[0].n_taps = g->n_taps; a.prof[0].L = g->L;
-        a.prof[0].identity = g->identity;
+        a.prof[0].identity = g->identity; a.prof[0].Fd = g->Fd;
         a.n_prof = 1;
         a.tap_stride = g->tap_stride > 0 ? g->tap_stride : g->n_taps;
     } else {
         for (int i = 0; i < g->n_profiles; ++i) {
             a.prof[i].coeff = g->profiles[i].coeff; a.prof[i].alpha = g->profiles[i].alpha;
             a.prof[i].n_taps = g->profiles[i].n_taps; a.prof[i].L = g->profiles[i].L; a.prof[i].identity = g->profiles[i].identity;
+            a.prof[i].Fd = g->profiles[i].Fd;
         }
         a.n_prof = g->n_profiles;
         a.tap_stride = g->tap_stride;
     }
     a.H = reinterpret_cast<float2*>(g->H_out); a.h_rep = g->h_rep;
+    a.dop_period = gen_static_doppler(g) ? g->doppler_period : 0; a.t_sym = g->t_sym;
     a.snr_db = g->snr_db; a.y = reinterpret_cast<float2*>(g->y); a.noise = reinterpret_cast<float2*>(g->noise);
     a.power_partial = g->power_partial; a.noise_partial = g->noise_partial; a.tx_out = g->tx_out;
     a.frames = g->frames; a.S = g->S; a.K = g->K; a.CP = g->CP; a.D = g->D; a.nbits = g->nbits;
@@ -1222,13 +1242,16 @@ int gen_static_args(const dccn_gen_static* g, GenStaticArgs* out) {
 int gen_static_launch(const dccn_gen_static* g, hipStream_t s, const GenChainScalars* chains) {
     GenStaticArgs a;
     DCCN_TRY(gen_static_args(g, &a));
-    const size_t smem = gen_static_smem_bytes<7, 64, 16>();
     const int blocks = ceil_div(g->frames, kGenFramesPerBlock);
     GenChainScalars gc;
     if (chains) gc = *chains;
     else memset(&gc, 0, sizeof(gc));
     if (tl_chain.G > 1 && gc.n != tl_chain.G) return DCCN_ERR_UNSUPPORTED;      // (a group needs every chain's seed / offset)
-    DCCN_LAUNCH_CHAINS_Z((gen_static_frames_kernel<7, 64, 16>), dim3(blocks), dim3(256), smem, s, a, gc);
+    if (a.dop_period > 0) {       // (static descriptors keep the launch they had)
+        DCCN_LAUNCH_CHAINS_Z((gen_doppler_frames_kernel<7, 64, 16>), dim3(blocks), dim3(256), (gen_doppler_smem_bytes<7, 64, 16>()), s, a, gc);
+    } else {
+        DCCN_LAUNCH_CHAINS_Z((gen_static_frames_kernel<7, 64, 16>), dim3(blocks), dim3(256), (gen_static_smem_bytes<7, 64, 16>()), s, a, gc);
+    }
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
 }

@@ -120,11 +120,12 @@ struct ChainOffsetCheck {
 static bool gen_static_same_plan(const dccn_gen_static* a, const dccn_gen_static* b) {
     if (a->frames != b->frames || a->S != b->S || a->K != b->K || a->CP != b->CP || a->D != b->D || a->n_taps != b->n_taps ||
         a->L != b->L || a->identity != b->identity || a->n_profiles != b->n_profiles || a->tap_stride != b->tap_stride ||
-        a->h_rep != b->h_rep || a->pilot_re != b->pilot_re || a->pilot_im != b->pilot_im)
+        a->h_rep != b->h_rep || a->pilot_re != b->pilot_re || a->pilot_im != b->pilot_im ||
+        a->doppler_period != b->doppler_period || a->t_sym != b->t_sym || a->Fd != b->Fd)
         return false;
     for (int i = 0; i < a->n_profiles; ++i)
         if (a->profiles[i].n_taps != b->profiles[i].n_taps || a->profiles[i].L != b->profiles[i].L ||
-            a->profiles[i].identity != b->profiles[i].identity)
+            a->profiles[i].identity != b->profiles[i].identity || a->profiles[i].Fd != b->profiles[i].Fd)
             return false;
     return true;
 }

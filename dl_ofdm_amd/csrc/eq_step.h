@@ -226,9 +226,11 @@ struct EqStepPlan {
     bool pre;                       // the previous step ran it for this batch on its optimizer launch (x_prenormalised)
     int nslot;
     // the next batch's generator as a rider of this step (dccn_eq_buffers.gen_next_rides): on the bottleneck backward launch
-    // when the plan has it (ga: its argument block), else as the step's first launch (same batch either way)
+    // when the plan has it and the descriptor has no Doppler frames (ga: its argument block), else as the step's first launch
+    // (same batch either way); gsc: every chain's (nbits, offset, seed) for either launch (n == 0: one chain)
     bool gen_wanted, gen_rides;
     GenStaticArgs ga;
+    GenChainScalars gsc;
     bool want_snr;
     // the frozen receiver: its layout and its linear part as this step runs it (input rows, weights, bias, k extent)
     dccn_rx_shape rsh;
@@ -289,9 +291,16 @@ static int eq_step_plan(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
     const dccn_gen_static* gv = b->x_next_virtual;
     p.gen_wanted = train && b->gen_next_rides != 0;
     if (p.gen_wanted && gv == nullptr) return DCCN_ERR_INVALID_ARG;
-    p.gen_rides = p.gen_wanted && p.bn && gen_static_ok(gv);
-    if (p.gen_wanted && !p.gen_rides && tl_chain.G > 1) return DCCN_ERR_UNSUPPORTED;
+    // (the bottleneck backward launch carries the static generator body only: a descriptor with Doppler frames is the step's
+    // first launch, with the chain scalars of a group)
+    p.gen_rides = p.gen_wanted && p.bn && gen_static_ok(gv) && !gen_static_doppler(gv);
     if (p.gen_wanted) DCCN_TRY(gen_static_args(gv, &p.ga));
+    if (p.gen_wanted && tl_chain.G > 1) {
+        p.gsc.n = tl_chain.G;
+        for (int g = 0; g < tl_chain.G; ++g) {
+            p.gsc.nbits[g] = tl_chain.gen_nbits[g]; p.gsc.offset[g] = tl_chain.gen_offset[g]; p.gsc.seed[g] = tl_chain.gen_seed[g];
+        }
+    }
     p.rides = eq_norm_rides_ok(d, train, b->x, w.x_norm);
     p.pre = p.rides && b->x_prenormalised != 0;
     if (b->x_prenormalised != 0 && !p.pre) return DCCN_ERR_INVALID_ARG;
@@ -372,7 +381,7 @@ static int eq_issue_forward(const dccn_eq_shape* sh, const dccn_eq_buffers* b, c
     float* h = b->chest;
     const int B = d.B, R = d.R, K = d.K, SK2 = d.SK2, K2 = 2 * d.K, N2 = 2 * d.nsc, ncols = d.S * N2;
     const long long nBK = (long long)B * SK2;          // floats in a [B,S,K,2] tensor
-    if (p.gen_wanted && !p.gen_rides) DCCN_TRY(gen_static_launch(b->x_next_virtual, s));
+    if (p.gen_wanted && !p.gen_rides) DCCN_TRY(gen_static_launch(b->x_next_virtual, s, p.gsc.n > 0 ? &p.gsc : nullptr));
     // `input:0` (ofdmreceiver_np.py:128-137) + tx_power partials
     // (training: the optimizer's per-step bookkeeping rides on this first launch)
     // pipelined: the previous step ran this launch for us on its optimizer launch (dccn_eq_buffers.x_next)
@@ -603,20 +612,13 @@ static int eq_issue_backward(const dccn_eq_buffers* b, const EqStepPlan& p, dccn
             }
         }
         // the NEXT batch's generator rides here as well (dccn_eq_buffers.gen_next_rides): its workgroups are the first grid rows
-        GenChainScalars gc;
-        memset(&gc, 0, sizeof(gc));
+        const GenChainScalars& gc = p.gsc;
         int gen_rows = 0, gen_blocks = 0;
         size_t gen_smem = 0;
         if (p.gen_rides) {
             gen_blocks = ceil_div(p.ga.frames, kGenFramesPerBlock);
             gen_rows = ceil_div(gen_blocks, nx);
             gen_smem = gen_static_smem_bytes<7, 64, 16>();
-            if (tl_chain.G > 1) {
-                gc.n = tl_chain.G;
-                for (int g = 0; g < tl_chain.G; ++g) {
-                    gc.nbits[g] = tl_chain.gen_nbits[g]; gc.offset[g] = tl_chain.gen_offset[g]; gc.seed[g] = tl_chain.gen_seed[g];
-                }
-            }
         }
         DCCN_LAUNCH_CHAINS_Z(kern, dim3(nx, gen_rows + p.bnp.tiles + ceil_div(ride.blocks, nx)), dim3(256), gen_smem, s,
                              (const float*)w.dd2, (const float*)w.d1, (const float*)w.y, P + d.o[4], P + d.o[6], (const float*)w.dy,

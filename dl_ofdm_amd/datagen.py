@@ -14,7 +14,8 @@ Scope: every channel of ``rayleigh_chan_lte``: the single-profile ones ('AWGN', 
 'Custom'), static or mobile (Jakes Doppler, radio.py:376-407: per-symbol taps, per-symbol FIR with n_taps samples
 of history), and the frame-interleaved 'mixRayleigh' / 'mixAll' (radio.py:438-470: profile = frame index modulo 4
 or 5, Doppler on every 3rd / 4th frame when ``mix``) -- those run one launch pair per (profile, static|Doppler)
-group over a frame-index list.
+group over a frame-index list.  ``FusedStaticGen`` is the same chain as ONE launch on the N = 64 grid, Doppler frames
+included: what the training loops use.
 """
 from __future__ import annotations
 
@@ -241,9 +242,12 @@ class DeviceDataGen:
 
 
 class FusedStaticGen:
-    """``DeviceDataGen.make_batch`` of a static single-profile channel as ONE launch (include/dccn.h dccn_gen_static,
-    csrc/datagen.h gen_static_frames_kernel): bits -> grid -> ifft + CP -> taps -> 'same' FIR -> (y, frame-scaled noise, power
-    partials).  The receiver's input x = y / sqrt(mean |y|^2) + noise is formed by the consumer: ``RxEngine.
+    """``DeviceDataGen.make_batch`` as ONE launch (include/dccn.h dccn_gen_static; csrc/datagen.h gen_static_frames_kernel, or
+    gen_doppler_frames_kernel when the frame plan has Doppler frames): bits -> grid -> ifft + CP -> per frame static taps and
+    the 'same' FIR, or Jakes taps per symbol and the per-symbol FIR -> (y, frame-scaled noise, power partials).  Channels: one
+    profile, static or mobile (every frame a Doppler frame), and the frame-interleaved mixRayleigh / mixAll with or without
+    ``mix`` (Doppler on every 3rd / 4th frame) -- the reference driver's ``--mobile=True`` default among them.  The
+    receiver's input x = y / sqrt(mean |y|^2) + noise is formed by the consumer: ``RxEngine.
     train_step_generated`` hands the descriptor to ``dccn_rx_train_step``, which issues the generator launch itself and reads
     (y, noise, partials) as the virtual input of its pipelined normalisation -- one C call and five launches per generated-and-
     trained batch instead of two or three calls and eight or nine launches; ``make_batch`` materialises x (one more launch)
@@ -251,8 +255,8 @@ class FusedStaticGen:
 
     def __init__(self, gen: DeviceDataGen, n_frames: int, snr_db, want_noise_power: bool = False, arena=None):
         if not self.supported(gen):
-            raise _lib.DccnError("FusedStaticGen: static N = 64 channels only (one profile, or the frame-interleaved profiles of "
-                                 "mixRayleigh / mixAll without Doppler frames)")
+            raise _lib.DccnError("FusedStaticGen: N = 64 channels without align_window only (one profile, static or mobile, or the "
+                                 "frame-interleaved profiles of mixRayleigh / mixAll; L <= 64, n_taps <= 16, at most 6 profiles)")
         from . import arena as A
         self.gen, self.n = gen, int(n_frames)
         self.arena = arena
@@ -272,16 +276,29 @@ class FusedStaticGen:
                       A.place(arena, gen.coeff), A.place(arena, gen.alpha)]
         self.desc = _lib.GenStatic(0, p(self._tabs[0]), p(self._tabs[1]), float(gen.pilot.real), float(gen.pilot.imag),
                                    p(self._tabs[2]), p(self._tabs[3]), p(self._tabs[4]), gen.n_taps, gen.L, 1 if gen.identity else 0,
-                                   p(self.snr), p(self.y), p(self.noise), p(self.ppart), p(self.npart), None, None,
+                                   0.0, p(self.snr), p(self.y), p(self.noise), p(self.ppart), p(self.npart), None, None,
                                    self.n, gen.S, gen.K, gen.CP, gen.D, gen.nbits, gen.seed, 0)
         if gen.mixed:
             # radio.py:438-452: frame f runs profile f % n_profiles; the launch-per-stage path draws 16 tap slots per frame
             self._ptabs = [(A.place(arena, pr["coeff"]), A.place(arena, pr["alpha"])) for pr in gen.profiles]
             self._profiles = (_lib.GenProfile * len(gen.profiles))(*[
-                _lib.GenProfile(p(tc), p(ta), pr["n_taps"], pr["L"], 1 if pr["identity"] else 0, 0)
+                _lib.GenProfile(p(tc), p(ta), pr["n_taps"], pr["L"], 1 if pr["identity"] else 0, float(pr["Fd"]))
                 for pr, (tc, ta) in zip(gen.profiles, self._ptabs)])
             self.desc.n_profiles, self.desc.tap_stride = len(gen.profiles), 16
             self.desc.profiles = C.addressof(self._profiles)
+        # Doppler frames (radio.py:376-407, 438-452; DeviceDataGen.frame_plan): every frame of a mobile single-profile channel,
+        # every ``period``-th frame of the mixed channels under ``mix`` whose profile has Fd > 0.1 and is not the identity
+        self.has_doppler = self.doppler_plan(gen)
+        if self.has_doppler:
+            self.desc.doppler_period = int(gen.period) if gen.mixed else 1
+            self.desc.Fd, self.desc.t_sym = float(gen.Fd), float(gen.t_sym)
+
+    @staticmethod
+    def doppler_plan(gen: DeviceDataGen) -> bool:
+        """does any batch of this generator hold a Doppler frame?"""
+        if gen.mixed:
+            return bool(gen.mix) and any(pr["Fd"] > 0.1 and not pr["identity"] for pr in gen.profiles)
+        return bool(gen.doppler)
 
     @staticmethod
     def supported(gen: DeviceDataGen, eng=None) -> bool:
@@ -290,10 +307,10 @@ class FusedStaticGen:
         with falling BER in receiver.train and leaves that range beyond 1536 frames)"""
         if eng is not None and not bool(gen.lib.dccn_rx_gen_next_supported(C.byref(eng.shape))):
             return False
-        if gen.doppler or gen.align_window or not bool(gen.lib.dccn_gen_static_supported(gen.S, gen.K, gen.CP)):
+        if gen.align_window or not bool(gen.lib.dccn_gen_static_supported(gen.S, gen.K, gen.CP)):
             return False
-        if gen.mixed:                       # static frames only: no (profile, Doppler) pair in any frame plan
-            return (not gen.mix) and len(gen.profiles) <= 6 and all(pr["L"] <= 64 and pr["n_taps"] <= 16 for pr in gen.profiles)
+        if gen.mixed:                       # with or without Doppler frames (``mix``)
+            return len(gen.profiles) <= 6 and all(pr["L"] <= 64 and pr["n_taps"] <= 16 for pr in gen.profiles)
         return True
 
     def set_snr(self, snr_db):
@@ -307,13 +324,15 @@ class FusedStaticGen:
             out_H: Optional[torch.Tensor] = None, snr: Optional[torch.Tensor] = None, into=None) -> "_lib.GenStatic":
         """the descriptor for the NEXT launch: labels go to ``out_bits``, the batch offset is the generator's current one (which
         is advanced: call once per batch).  ``out_H`` float32 [n, K, 2] or [n, S, K, 2]: the frequency response per frame (per
-        symbol); ``snr``: a float32 device tensor of n per-frame SNRs to read instead of the generator's own copy."""
+        symbol; a plan with Doppler frames has S distinct responses per frame and takes [n, S, K, 2] only); ``snr``: a float32 device tensor of n per-frame SNRs to read instead of the generator's own copy."""
         # ``into``: a copy of the descriptor to arm instead of the generator's own (the one a step's buffers point to when the
         # step produces the batch itself: dccn_eq_buffers.gen_next_rides)
         g, d = self.gen, (self.desc if into is None else into)
         d.bits_out = out_bits.data_ptr()
         if out_H is not None:
             per = (self.n, g.S, g.K, 2)
+            if self.has_doppler and tuple(out_H.shape) != per:
+                raise ValueError("out_H must have shape %s: the plan has Doppler frames (one response per symbol)" % (per,))
             if tuple(out_H.shape) not in (per, (self.n, g.K, 2)) or out_H.dtype != torch.float32 or not out_H.is_contiguous():
                 raise ValueError("out_H must be a contiguous float32 tensor of shape %s or %s" % (per, (self.n, g.K, 2)))
             d.H_out, d.h_rep = out_H.data_ptr(), (g.S if out_H.dim() == 4 else 1)

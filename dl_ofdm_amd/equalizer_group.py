@@ -5,7 +5,7 @@ The reference driver runs one (receiver -> equaliser) chain per modulation and p
 73-frame steps of ~21 dependent launches that keeps a few percent of the chip busy, and the host spends as long issuing a step
 as the GPU spends running it.  Here G chains of the same shape share every launch (include/dccn.h "chain groups": the chain
 index is a grid dimension): per group step ONE C call carries all G chains' batches -- the step, with the next batch's generator
-riding on its bottleneck backward launch and the loop's monitors on its optimizer launch (three calls without those riders).  Every chain keeps its own seeds, draws, early stopping and best-model snapshot: the trained model of a chain
+riding on its bottleneck backward launch (``mobile`` chains: as the step's first launch) and the loop's monitors on its optimizer launch (three calls without those riders).  Every chain keeps its own seeds, draws, early stopping and best-model snapshot: the trained model of a chain
 is bit for bit the one :func:`dl_ofdm_amd.receiver_mp.train` produces for it alone (tests/test_gpu_chain_groups.py).
 
     results = train_group([flags_bpsk, flags_qpsk, ...], [rx_params_bpsk, rx_params_qpsk, ...])
@@ -48,7 +48,7 @@ class _Chain:
         self.steps = (FLAGS.msg_length // FLAGS.nsymbol) // self.B
         self.gen = DeviceDataGen(FLAGS, self.o, device=self.tr.device, seed=FLAGS.seed, mobile=FLAGS.mobile, mix=FLAGS.mobile)
         if not FusedStaticGen.supported(self.gen):
-            raise _lib.DccnError("chain groups need the fused static-channel generator (no Doppler frames)")
+            raise _lib.DccnError("chain groups need the fused generator (N = 64 grid, no align_window)")
         self.pl = _FusedPlan(self.tr, self.B, arena=self.arena)
         self.tr._plans[self.B] = self.pl
         self.ev = self.tr.resident(FLAGS.eval_frames)                      # evaluation runs per chain, outside the group
@@ -215,6 +215,6 @@ class EqualizerChainGroup:
 
 def train_group(flags_list: Sequence, rx_params_list: Sequence[Dict[str, np.ndarray]], device="cuda",
                 verbose: bool = False) -> List[dict]:
-    """:func:`dl_ofdm_amd.receiver_mp.train` (device_data, static channels) for several chains at once; returns one result dict
+    """:func:`dl_ofdm_amd.receiver_mp.train` (device_data; static or ``mobile`` channels) for several chains at once; returns one result dict
     per chain (history, best_path, trainer) -- the bits the per-chain function returns"""
     return EqualizerChainGroup(flags_list, rx_params_list, device=device).train(verbose=verbose)

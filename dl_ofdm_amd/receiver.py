@@ -333,7 +333,7 @@ def train(FLAGS: Flags, device="cuda", verbose: bool = True, run_test: bool = Tr
                 # and backward launches of step i run; the step's last launch waits for it
                 from .datagen import FusedStaticGen, SideStreamFeeder
                 if FLAGS.cp and FusedStaticGen.supported(gen, eng) and not getattr(FLAGS, "no_fused_generator", False):
-                    # round 5: static single-profile channels -- ONE C call per batch: the fused generator launch of the next batch
+                    # round 5: single-profile channels, static or mobile -- ONE C call per batch: the fused generator launch of the next batch
                     # + the four step launches, whose pipelined normalisation reads (y, noise, power partials) as its virtual
                     # input (include/dccn.h dccn_gen_static; datagen.FusedStaticGen).  Same batches as the loop below.
                     fg = fused.get(batch_size)

@@ -358,10 +358,17 @@ typedef struct dccn_rx_shape {
     int nbits;     /* 1..4 */
 } dccn_rx_shape;
 
-/* The fused device-side generator of a static single-profile channel (round 5; the chain of dccn_ofdm_tx_frames +
- * dccn_channel_awgn below in ONE launch, csrc/datagen.h gen_static_frames_kernel): label bits -> resource grid -> ifft + cyclic
- * prefix -> static Rayleigh taps -> 'same' FIR (dev/py/util.py:25-29, ofdm.py:328-380, radio.py:352-372) -> y, plus the
- * frame-scaled noise of radio.py:513-526 and per-block partial sums of |y|^2 and |noise|^2.  The receiver's input is
+/* The fused device-side generator: a whole batch of any channel of rayleigh_chan_lte on the N = 64 grid in ONE launch (the
+ * chain of dccn_ofdm_tx_frames + dccn_channel_awgn / _doppler_awgn / _groups_awgn below; csrc/datagen.h
+ * gen_static_frames_kernel, gen_doppler_frames_kernel): label bits -> resource grid -> ifft + cyclic prefix -> per frame
+ * either static Rayleigh taps and the 'same' FIR, or (Doppler frames) Jakes taps per symbol and the per-symbol FIR with n_taps
+ * samples of history (dev/py/util.py:25-29, ofdm.py:328-380, radio.py:352-407, 438-452) -> y, plus the frame-scaled noise of
+ * radio.py:513-526 and per-block partial sums of |y|^2 and |noise|^2.  It covers the single-profile channels, static or
+ * mobile (every frame a Doppler frame), and the frame-interleaved mixRayleigh / mixAll with or without their Doppler frames
+ * (every 3rd / 4th frame): the reference driver's default training channel.  Descriptors without Doppler frames launch the
+ * code they launched before that was added.
+ * CALLERS MUST ZERO-INITIALISE THE STRUCT (memset / = {0}): fields added later sit in what used to be padding, and all-zero
+ * new fields mean the earlier behaviour, bit for bit.  The receiver's input is
  * x = y / sqrt(mean |y|^2 over the batch) + noise: formed by the consumer -- dccn_rx_train_step reads the descriptor as the
  * virtual input of its pipelined normalisation (dccn_rx_buffers.gen_next) -- or materialised by dccn_gen_static_apply.
  * Same Philox streams and draws as the separate launches (a batch is a pure function of (seed, offset)); the ifft runs on
@@ -376,6 +383,7 @@ typedef struct dccn_gen_static {
     const float* coeff;           /* [n_taps] tap amplitudes (null when identity) */
     const float* alpha;           /* [n_taps, L] sinc interpolation */
     int n_taps, L, identity;      /* identity: AWGN channel (g = [1]) */
+    float Fd;                     /* the single profile's Doppler frequency in Hz (read when doppler_period > 0) */
     const float* snr_db;          /* [frames] */
     float* y;                     /* [frames, S, K+CP, 2] channel output */
     float* noise;                 /* [frames, S, K+CP, 2] noise, already scaled per frame */
@@ -391,16 +399,26 @@ typedef struct dccn_gen_static {
        (coeff, alpha, n_taps, L, identity) above.  tap_stride: taps per frame in the Philox index of the tap draws (0 = n_taps;
        16 reproduces the draws of dccn_channel_groups_awgn). */
     int n_profiles, tap_stride;
+    /* Doppler frames (radio.py:376-407): 0 none; 1 every frame (single-profile mobile channels); p: the frames with
+       f % p == 0 (3 for mixRayleigh, 4 for mixAll with `mix`).  Such a frame is a Doppler frame when its profile is not the
+       identity and has Fd > 0.1; its phases are Philox stream 3 at index ((f*2 + c)*48 + n)*tap_stride + k (the draws of
+       dccn_channel_doppler_awgn with tap_stride = n_taps, of dccn_channel_groups_awgn with 16).  Nonzero: t_sym > 0 and every
+       Fd finite, else the descriptor is refused. */
+    int doppler_period;
     const struct dccn_gen_profile* profiles;
     /* nullable: H [frames * h_rep, K, 2] = fft(g, K) of every frame's impulse response, h_rep copies per frame (the mixed
        channels report the response per symbol: h_rep = S) -- the values dccn_channel_awgn / _groups_awgn put into `H` */
+    /* a Doppler frame writes S DISTINCT responses [f, s, K]: a descriptor with Doppler frames and H_out needs h_rep == S
+       (refused otherwise); its static frames keep writing h_rep copies */
     float* H_out;
     int h_rep;
+    float t_sym;                  /* seconds per OFDM symbol, (K + CP) / Fs (read when doppler_period > 0) */
 } dccn_gen_static;
 typedef struct dccn_gen_profile {
     const float* coeff;           /* [n_taps] (null when identity) */
     const float* alpha;           /* [n_taps, L] */
-    int n_taps, L, identity, reserved;
+    int n_taps, L, identity;
+    float Fd;                     /* this profile's Doppler frequency in Hz (was `reserved`: a float's zero is the int's zero) */
 } dccn_gen_profile;
 int dccn_gen_static_supported(int S, int K, int CP);      /* 1: shapes the fused launch is instantiated for (N = 64) */
 int dccn_gen_static_partials(int frames);
@@ -714,7 +732,10 @@ typedef struct dccn_eq_buffers {
     /* Round 6: 1 = the step ALSO produces the batch x_next_virtual describes (the descriptor fully armed: bits_out, snr_db,
        offset, seed, H_out ...): the generator's workgroups ride on the step's pilot-bottleneck backward launch (15 us of VALU
        work beside MFMA tiles and HBM streams instead of a launch of its own in front of the step; a launch of its own when the
-       plan has no such launch).  The caller no longer issues dccn_gen_static_frames for that batch.  Same draws, same bits. */
+       plan has no such launch).  The caller no longer issues dccn_gen_static_frames for that batch.  Same draws, same bits.
+       A descriptor with Doppler frames does not ride: its generator is the step's own FIRST launch (also for a chain group,
+       one launch for all chains).  The bottleneck backward launch keeps the static generator as its only rider: the Doppler
+       body needs 54.9 KB of LDS beside that kernel's 10.6 KB and is several times the launch's longest work item. */
     int gen_next_rides;
     /* Round 6, nullable: the training loop's per-step monitors (dccn_eq_monitor_accumulate: chan_rms of THIS step's channel
        estimate against `chan`, and {ce_mean, berlin, tx_power, noise_power, chan_rms} added onto acc5) as part of the step's

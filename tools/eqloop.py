@@ -4,6 +4,7 @@ it goes: the loop as the harness runs it, the same loop without the torch-side m
 alone.  One JSON line per variant.
 
     python tools/eqloop.py [--nbits 2] [--channel EPA] [--steps 300]
+    python tools/eqloop.py --channel mixRayleigh --mobile 1 --only r04_loop_next [--fused 0]      (the reference driver's default channel)
 """
 import argparse
 import json
@@ -24,6 +25,8 @@ def main():
     ap.add_argument("--fused", type=int, default=1, help="0: the launch-per-stage generator chain in the loop variants")
     ap.add_argument("--graph", type=int, default=0, help="1: the loop variants replay the step's hipGraph instead of issuing it eagerly")
     ap.add_argument("--virtual", type=int, default=1, help="0: the pipelined loop materialises every batch (no x_next_virtual)")
+    ap.add_argument("--mobile", type=int, default=0, help="1: the mobile channel (mixed channels: Doppler on every 3rd / 4th frame)")
+    ap.add_argument("--only", default="", help="run the variants whose name contains this")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -37,10 +40,11 @@ def main():
     F.fused_generator = bool(args.fused)
     F.virtual_next = bool(args.virtual)
     F.step_graph = bool(args.graph)
+    F.mobile = bool(args.mobile)
     o = ofdm.ofdm_tx(F)
     rx_params = glorot_init(R.rx_dims(F, o), 1)
     tr = EqualizerTrainer(F, o, rx_params, device="cuda", seed=1)
-    gen = DeviceDataGen(F, o, device=tr.device, seed=1, mobile=False, mix=False)
+    gen = DeviceDataGen(F, o, device=tr.device, seed=1, mobile=bool(args.mobile), mix=bool(args.mobile))
     B = F.batch_size // F.nsymbol
     pl = tr.resident(B)
     mview = pl.metrics_buf.view(torch.float32)
@@ -86,6 +90,8 @@ def main():
         except TypeError:                                             # (an older package)
             variants.insert(0, ("r04_loop", M.device_epoch_runner(F, o, tr, gen, pl)))
     for name, fn in variants:
+        if args.only not in name:
+            continue
         for _ in range(30):
             fn()
         torch.cuda.synchronize()
@@ -95,7 +101,7 @@ def main():
         t_host = time.perf_counter() - t0
         torch.cuda.synchronize()
         t_all = time.perf_counter() - t0
-        rec = {"variant": name, "frames": B, "ms_per_step_wall": round(t_all / args.steps * 1e3, 4),
+        rec = {"variant": name, "frames": B, "channel": args.channel, "mobile": args.mobile, "fused": args.fused, "ms_per_step_wall": round(t_all / args.steps * 1e3, 4),
                "ms_per_step_host_issue": round(t_host / args.steps * 1e3, 4)}
         line = json.dumps(rec)
         print(line, flush=True)
