@@ -201,6 +201,23 @@ struct Cfg16 {
     }
 };
 
+// Output policy of tail_cells_out (tail.h) for a tile that lies completely inside the matrix: cell u of the lane's batch
+// stores at the block-uniform pointers pb[u] (prob) / db[u] (dz) plus ONE per-lane 32-bit float offset each -- scalar base
+// + vector offset addressing, no 64-bit address arithmetic per cell, no per-lane null tests; dz leaves cell by cell.
+template <int W, bool DZ>
+struct TailOutTile {
+    float* pb[W];           // nullptr (all of them) = prob not wanted
+    float* db[W];
+    unsigned lp, ld;
+    __device__ __forceinline__ bool any_prob() const { return pb[0] != nullptr; }
+    __device__ __forceinline__ void prob(const int u, const int j, const float p0, const float p1) const {
+        *reinterpret_cast<float2*>(pb[u] + lp + 2 * j) = make_float2(p0, p1);
+    }
+    __device__ __forceinline__ void dz(const int u, const float d0, const float d1) const {
+        if constexpr (DZ) out_store2<1>(db[u] + ld, d0, d1);
+    }
+};
+
 // One BM x BN output tile (block `L` of `T` tiles, grid split `z`) of C = A.B
 // PD = 2: global loads run TWO k-tiles ahead of the MFMAs (second staging register set, loop unrolled by two): with a
 // single block per CU nothing else covers the ~0.6 us load latency, which is longer than half a 48x64x64 tile's MFMA
@@ -711,15 +728,11 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
         TailLaneAcc<NB, BWD> A;
         A.clear();
         float cz0[NCELL], cz1[NCELL];
-        bool cvalid[NCELL];
-        float* cprob[NCELL];
-        float* cdz[NCELL];
 #pragma unroll
         for (int a = 0; a < TM; ++a) {
 #pragma unroll
             for (int b = 0; b < TN; ++b) {
                 const int col = n0 + wn0 + b * 16 + l15;   // this lane's own column
-                const int colc = min(col, p.N - 1);
                 const float bj = bjv[b];
                 float own[4], oth[4];
                 if constexpr (KS == 1) {
@@ -754,64 +767,120 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
                 for (int cc = 0; cc < 2 / KS; ++cc) {
                     const int ci = (a * TN + b) * (2 / KS) + cc;
                     float mine, othr;
-                    int rsel;
+                    // (the four candidates are read into values first: `odd ? own[2 + cc] : own[cc]` selects between two
+                    // array ELEMENTS, which the compiler kept as a dynamically indexed stack array -- a scratch store and
+                    // load round trip in front of every tail)
                     if constexpr (KS > 1) {              // c = set
-                        mine = set ? (odd ? own[3] : own[1]) : (odd ? own[2] : own[0]);
-                        othr = set ? (odd ? oth[3] : oth[1]) : (odd ? oth[2] : oth[0]);
-                        rsel = (odd ? 2 : 0) + set;
+                        const float w0 = own[0], w1 = own[1], w2 = own[2], w3 = own[3];
+                        const float t0 = oth[0], t1 = oth[1], t2 = oth[2], t3 = oth[3];
+                        mine = set ? (odd ? w3 : w1) : (odd ? w2 : w0);
+                        othr = set ? (odd ? t3 : t1) : (odd ? t2 : t0);
                     } else {
-                        mine = odd ? own[2 + cc] : own[cc];
-                        othr = odd ? oth[2 + cc] : oth[cc];
-                        rsel = (odd ? 2 : 0) + cc;
+                        const float wlo = own[cc], whi = own[2 + cc], tlo = oth[cc], thi = oth[2 + cc];
+                        mine = odd ? whi : wlo;
+                        othr = odd ? thi : tlo;
                     }
                     cz0[ci] = odd ? othr : mine;
                     cz1[ci] = odd ? mine : othr;
-                    const int row = m0 + wm0 + a * 16 + 4 * kg + rsel;
-                    const bool ok = row < p.M && col < p.N;
-                    const long long cell = (long long)min(row, p.M - 1) * Dn + (colc >> 1);
-                    cvalid[ci] = ok;
-                    cprob[ci] = (tp.prob != nullptr && ok) ? tp.prob + cell * NB * 2 : nullptr;
-                    cdz[ci] = BWD ? tp.dz + cell * 2 : nullptr;
                 }
             }
         }
-        // all cells of the lane in one interleaved instruction stream (tail.h tail_cells)
-        float2 cdzv[NCELL];
-        if constexpr (GEMM16_ABL & 16) {
-#pragma unroll
-            for (int ci = 0; ci < NCELL; ++ci) cprob[ci] = nullptr;
-        }
         // (at most 8 cells share one interleaved instruction stream: larger tiles run the tail in batches -- same
         // per-cell arithmetic and the same accumulation order as one batch)
-        if constexpr (!(GEMM16_ABL & 64)) {
-            constexpr int TW = NCELL <= 8 ? NCELL : (NCELL % 8 == 0 ? 8 : (NCELL % 6 == 0 ? 6 : (NCELL % 5 == 0 ? 5 : 4)));
-            static_assert(NCELL % TW == 0, "tail batches");
-            if constexpr (TW == NCELL) {
-                tail_cells<NB, BWD, NCELL>(cz0, cz1, labs, cvalid, sw, tp.inv_count, cprob, A, cdzv);
-            } else {
+        constexpr int TW = NCELL <= 8 ? NCELL : (NCELL % 8 == 0 ? 8 : (NCELL % 6 == 0 ? 6 : (NCELL % 5 == 0 ? 5 : 4)));
+        static_assert(NCELL % TW == 0, "tail batches");
+        // Interior tiles (block-uniform; all but the last tile row / column of a launch): every cell is valid, so the tail
+        // runs without validity selects and masks, and cell (a, b, cc) stores at a uniform base -- the tile's origin plus
+        // (a * 16 + cc) rows and b * 8 cells -- plus one per-lane offset shared by all the lane's cells.
+        const bool interior = m0 + BM <= p.M && n0 + BN <= p.N && (long long)BM * Dn < (1LL << 26);
+        if (interior) {
+            if constexpr (!(GEMM16_ABL & 64)) {
+                const unsigned lcell = (unsigned)(wm0 + 4 * kg + (odd ? 2 : 0) + (KS > 1 ? set : 0)) * (unsigned)Dn +
+                                       (unsigned)((wn0 + l15) >> 1);
+                const size_t origin = (size_t)m0 * Dn + (n0 >> 1);
+                float* const pbase = (tp.prob != nullptr && !(GEMM16_ABL & 16)) ? tp.prob + origin * NB * 2 : nullptr;
+                float* const dbase = BWD ? tp.dz + origin * 2 : nullptr;
+                bool vd[TW];
+#pragma unroll
+                for (int u = 0; u < TW; ++u) vd[u] = true;
 #pragma unroll
                 for (int g0 = 0; g0 < NCELL; g0 += TW) {
                     float a0[TW], a1[TW];
                     int lb[TW][NB];
-                    bool vd[TW];
-                    float* pc[TW];
-                    float2 dv[TW];
+                    TailOutTile<TW, BWD && !(GEMM16_ABL & 32)> out;
+                    out.lp = lcell * NB * 2;
+                    out.ld = lcell * 2;
 #pragma unroll
                     for (int u = 0; u < TW; ++u) {
-                        a0[u] = cz0[g0 + u]; a1[u] = cz1[g0 + u]; vd[u] = cvalid[g0 + u]; pc[u] = cprob[g0 + u];
+                        const int ci = g0 + u, ab = ci / (2 / KS), cc = ci % (2 / KS);
+                        const size_t ucell = (size_t)((ab / TN) * 16 + (KS > 1 ? 0 : cc)) * Dn + (ab % TN) * 8;
+                        a0[u] = cz0[ci]; a1[u] = cz1[ci];
+                        out.pb[u] = pbase != nullptr ? pbase + ucell * NB * 2 : nullptr;
+                        out.db[u] = BWD ? dbase + ucell * 2 : nullptr;
 #pragma unroll
-                        for (int j = 0; j < NB; ++j) lb[u][j] = labs[g0 + u][j];
+                        for (int j = 0; j < NB; ++j) lb[u][j] = labs[ci][j];
                     }
-                    tail_cells<NB, BWD, TW>(a0, a1, lb, vd, sw, tp.inv_count, pc, A, dv);
-#pragma unroll
-                    for (int u = 0; u < TW; ++u) cdzv[g0 + u] = dv[u];
+                    tail_cells_out<NB, BWD, TW, true>(a0, a1, lb, vd, sw, tp.inv_count, A, out);
                 }
             }
-        }
-        if constexpr (BWD && !(GEMM16_ABL & 32)) {
+        } else {
+            // ragged tiles: per-cell validity, clamped addresses, dz stored behind the tail
+            bool cvalid[NCELL];
+            float* cprob[NCELL];
+            float* cdz[NCELL];
 #pragma unroll
-            for (int ci = 0; ci < NCELL; ++ci)
-                if (cvalid[ci]) out_store2<1>(cdz[ci], cdzv[ci].x, cdzv[ci].y);
+            for (int a = 0; a < TM; ++a) {
+#pragma unroll
+                for (int b = 0; b < TN; ++b) {
+                    const int col = n0 + wn0 + b * 16 + l15;   // this lane's own column
+                    const int colc = min(col, p.N - 1);
+#pragma unroll
+                    for (int cc = 0; cc < 2 / KS; ++cc) {
+                        const int ci = (a * TN + b) * (2 / KS) + cc;
+                        const int rsel = (odd ? 2 : 0) + (KS > 1 ? set : cc);
+                        const int row = m0 + wm0 + a * 16 + 4 * kg + rsel;
+                        const bool ok = row < p.M && col < p.N;
+                        const long long cell = (long long)min(row, p.M - 1) * Dn + (colc >> 1);
+                        cvalid[ci] = ok;
+                        cprob[ci] = (tp.prob != nullptr && ok) ? tp.prob + cell * NB * 2 : nullptr;
+                        cdz[ci] = BWD ? tp.dz + cell * 2 : nullptr;
+                    }
+                }
+            }
+            // all cells of the lane in one interleaved instruction stream (tail.h tail_cells)
+            float2 cdzv[NCELL];
+            if constexpr (GEMM16_ABL & 16) {
+#pragma unroll
+                for (int ci = 0; ci < NCELL; ++ci) cprob[ci] = nullptr;
+            }
+            if constexpr (!(GEMM16_ABL & 64)) {
+                if constexpr (TW == NCELL) {
+                    tail_cells<NB, BWD, NCELL>(cz0, cz1, labs, cvalid, sw, tp.inv_count, cprob, A, cdzv);
+                } else {
+#pragma unroll
+                    for (int g0 = 0; g0 < NCELL; g0 += TW) {
+                        float a0[TW], a1[TW];
+                        int lb[TW][NB];
+                        bool vd[TW];
+                        float* pc[TW];
+                        float2 dv[TW];
+#pragma unroll
+                        for (int u = 0; u < TW; ++u) {
+                            a0[u] = cz0[g0 + u]; a1[u] = cz1[g0 + u]; vd[u] = cvalid[g0 + u]; pc[u] = cprob[g0 + u];
+#pragma unroll
+                            for (int j = 0; j < NB; ++j) lb[u][j] = labs[g0 + u][j];
+                        }
+                        tail_cells<NB, BWD, TW>(a0, a1, lb, vd, sw, tp.inv_count, pc, A, dv);
+#pragma unroll
+                        for (int u = 0; u < TW; ++u) cdzv[g0 + u] = dv[u];
+                    }
+                }
+            }
+            if constexpr (BWD && !(GEMM16_ABL & 32)) {
+#pragma unroll
+                for (int ci = 0; ci < NCELL; ++ci)
+                    if (cvalid[ci]) out_store2<1>(cdz[ci], cdzv[ci].x, cdzv[ci].y);
+            }
         }
         // (KS == 1: the k-loop ended with a barrier, nobody reads the tile buffers any more; KS > 1: red lies behind the
         // exchange region, which is only read above)

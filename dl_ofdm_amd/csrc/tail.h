@@ -76,20 +76,39 @@ struct TailLaneAcc {
     }
 };
 
+// Where a batch of W cells leaves its per-cell results.  TailOutPtrs: one pointer per cell (nullptr = no store), dz handed
+// back to the caller -- the form for callers whose cells may be invalid or scattered.  A caller whose cells are all valid and
+// lie at 32-bit offsets from block-uniform bases brings its own policy (gemm16.h TailOutTile): prob stores under ONE uniform
+// branch instead of a per-lane null test per store, and every dz store issued the moment the cell's d0 / d1 are final.
+template <int W>
+struct TailOutPtrs {
+    float* const (&prob_cell)[W];
+    float2 (&dzv)[W];
+    __device__ __forceinline__ bool any_prob() const { return true; }
+    __device__ __forceinline__ void prob(const int u, const int j, const float p0, const float p1) const {
+        if (prob_cell[u] != nullptr) *reinterpret_cast<float2*>(prob_cell[u] + 2 * j) = make_float2(p0, p1);
+    }
+    __device__ __forceinline__ void dz(const int u, const float d0, const float d1) const { dzv[u] = make_float2(d0, d1); }
+};
+
 // W data cells through R3-R6 (and back) in one instruction stream: z = (I,Q) of the dense output, lab = the NB label
 // bits, sw = tail weights (uniform address: scalar loads for NB <= 2, an LDS copy for NB >= 3).  Every statement is
-// written for all W cells before the next one, so the W independent dependency chains sit next to each other and the
-// long-latency steps (exp, log, reciprocal refinement) of one cell are covered by the others even with a single wave
-// per SIMD; per cell the operations and their order are those of the W = 1 form, so any W gives the same bits.
-// valid[u] == false: the cell contributes nothing to the sums (its dz is 0); prob_cell[u] (nullable) -> NB float2.
+// written for all W cells AND all NB bits before the next one, so the NB * W independent dependency chains (exp -> rcp ->
+// exp -> log -> rcp per (cell, bit), all quarter rate) sit next to each other and the long-latency steps of one chain are
+// covered by the others even with a single wave per SIMD; per (cell, bit) the operations and their order are those of the
+// W = 1 form, and every sum (A.ce: j ascending, u ascending within j; A.g[i]: u ascending) receives its terms in the same
+// order, so any W gives the same bits.
+// valid[u] == false: the cell contributes nothing to the sums (its dz is 0).  ALLV: the caller guarantees every cell valid
+// (`valid` is not read): no inv_count / ce selects, no masks in the tallies.
 // Shared by demod_tail_kernel and the fused dense-forward epilogue (gemm16.h).
-template <int NB, bool BWD, int W>
-__device__ __forceinline__ void tail_cells(const float (&z0)[W], const float (&z1)[W], const int (&lab)[W][NB],
-                                           const bool (&valid)[W], const float* __restrict__ sw, const float inv_count,
-                                           float* const (&prob_cell)[W], TailLaneAcc<NB, BWD>& A, float2 (&dzv)[W]) {
+template <int NB, bool BWD, int W, bool ALLV, typename Out>
+__device__ __forceinline__ void tail_cells_out(const float (&z0)[W], const float (&z1)[W], const int (&lab)[W][NB],
+                                               const bool (&valid)[W], const float* __restrict__ sw, const float inv_count,
+                                               TailLaneAcc<NB, BWD>& A, const Out& out) {
     constexpr int M = 1 << NB;
     constexpr int O = 2 * NB;
     constexpr int oW1 = 0, oB1 = 2 * M, oW2 = 3 * M, oB2 = 3 * M + (M + 2) * O;
+    static_assert(NB * W < 256, "packed tallies: 8-bit fields");
     // the two small matrix products of the forward are fused multiply-adds with the bias as the chain's start value
     // (36 VALU instructions fewer per QPSK cell); demod_tail_quad4_kernel evaluates the same expressions, so training
     // and evaluation produce identical probabilities for every modulation
@@ -127,68 +146,83 @@ __device__ __forceinline__ void tail_cells(const float (&z0)[W], const float (&z
 #pragma unroll
         for (int u = 0; u < W; ++u) pre2[o][u] = FMA_FWD ? s[u] : s[u] + sw[oB2 + o];
     }
-    float dpre2[O][W];
-    float inv_eff[W];
-#pragma unroll
-    for (int u = 0; u < W; ++u) inv_eff[u] = valid[u] ? inv_count : 0.f;
+    float p0[NB][W], p1[NB][W];
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-        float p0[W], p1[W], f0[W], f1[W], fs[W];
-        bool big[W];
 #pragma unroll
         for (int u = 0; u < W; ++u) {
             const float u0 = leaky_relu(pre2[2 * j][u]), u1 = leaky_relu(pre2[2 * j + 1][u]);
             // softmax over the pair: exp(u - max) is exactly 1 for the larger logit, so one expf suffices
             // (bit-identical to evaluating both); likewise for the second softmax on the probabilities
             // (the smaller logit minus the larger one is -|u0 - u1| either way: abs/neg are free source modifiers)
-            big[u] = u1 > u0;
+            const bool big = u1 > u0;
             const float eo = exp_nonpos(-fabsf(u0 - u1));
-            const float e0 = big[u] ? eo : 1.0f, e1 = big[u] ? 1.0f : eo;
+            const float e0 = big ? eo : 1.0f, e1 = big ? 1.0f : eo;
             const float res = rcp_fast(e0 + e1);
-            p0[u] = e0 * res;
-            p1[u] = e1 * res;
+            p0[j][u] = e0 * res;
+            p1[j][u] = e1 * res;
         }
+    }
+    if (out.any_prob()) {
 #pragma unroll
-        for (int u = 0; u < W; ++u) {
-            if (prob_cell[u] != nullptr) *reinterpret_cast<float2*>(prob_cell[u] + 2 * j) = make_float2(p0[u], p1[u]);
-        }
+        for (int j = 0; j < NB; ++j)
+#pragma unroll
+            for (int u = 0; u < W; ++u) out.prob(u, j, p0[j][u], p1[j][u]);
+    }
+    float f0[NB][W], f1[NB][W], fs[NB][W], cev[NB][W];
+    // confusion tallies: one word of four 8-bit fields per call, field 2 * label + pred (at most NB * W increments)
+    unsigned tally = 0u;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
 #pragma unroll
         for (int u = 0; u < W; ++u) {
             const int label = lab[u][j];
             // second softmax on the probabilities (softmax_cross_entropy_with_logits_v2)
-            const bool p1_big = p1[u] > p0[u];
-            const float mx2 = p1_big ? p1[u] : p0[u];
-            const float fo = exp_nonpos(-fabsf(p0[u] - p1[u]));
-            f0[u] = p1_big ? fo : 1.0f;
-            f1[u] = p1_big ? 1.0f : fo;
-            fs[u] = f0[u] + f1[u];
-            const float lse = log_1_2(fs[u]) + mx2;
-            const float ce = lse - (label ? p1[u] : p0[u]);
-            A.ce += (double)(valid[u] ? ce : 0.f);
-            const int pred = (p1[u] > p0[u]) ? 1 : 0;    // argmax, first index on ties
-            const int l1 = label != 0 ? 1 : 0;           // branch-free tallies (divergent ifs cost exec-mask regions)
-            const int vb = valid[u] ? 1 : 0;
-            A.c00 += (1 - l1) & (1 - pred) & vb;
-            A.c01 += (1 - l1) & pred & vb;
-            A.c10 += l1 & (1 - pred) & vb;
-            A.c11 += l1 & pred & vb;
+            const bool p1_big = p1[j][u] > p0[j][u];         // also the decision: argmax, first index on ties
+            const float mx2 = p1_big ? p1[j][u] : p0[j][u];
+            const float fo = exp_nonpos(-fabsf(p0[j][u] - p1[j][u]));
+            f0[j][u] = p1_big ? fo : 1.0f;
+            f1[j][u] = p1_big ? 1.0f : fo;
+            fs[j][u] = f0[j][u] + f1[j][u];
+            const float lse = log_1_2(fs[j][u]) + mx2;
+            const float ce = lse - (label ? p1[j][u] : p0[j][u]);
+            const unsigned inc_l = label != 0 ? 0x10000u : 1u;
+            const unsigned inc = p1_big ? inc_l << 8 : inc_l;
+            if constexpr (ALLV) {
+                cev[j][u] = ce;
+                tally += inc;
+            } else {
+                cev[j][u] = valid[u] ? ce : 0.f;
+                tally += valid[u] ? inc : 0u;
+            }
         }
-        if constexpr (BWD) {
+    }
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+        for (int u = 0; u < W; ++u) A.ce += (double)cev[j][u];
+    A.c00 += (int)(tally & 0xffu);
+    A.c01 += (int)((tally >> 8) & 0xffu);
+    A.c10 += (int)((tally >> 16) & 0xffu);
+    A.c11 += (int)(tally >> 24);
+    if constexpr (BWD) {
+        float dpre2[O][W];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
 #pragma unroll
             for (int u = 0; u < W; ++u) {
                 const int label = lab[u][j];
-                const float rfs = rcp_fast(fs[u]);
-                const float q0 = f0[u] * rfs, q1 = f1[u] * rfs;
-                const float g0 = (q0 - (label ? 0.f : 1.f)) * inv_eff[u];
-                const float g1 = (q1 - (label ? 1.f : 0.f)) * inv_eff[u];
-                const float dot = g0 * p0[u] + g1 * p1[u];
-                const float du0 = p0[u] * (g0 - dot), du1 = p1[u] * (g1 - dot);
+                const float inv_eff = ALLV ? inv_count : (valid[u] ? inv_count : 0.f);
+                const float rfs = rcp_fast(fs[j][u]);
+                const float q0 = f0[j][u] * rfs, q1 = f1[j][u] * rfs;
+                const float g0 = (q0 - (label ? 0.f : 1.f)) * inv_eff;
+                const float g1 = (q1 - (label ? 1.f : 0.f)) * inv_eff;
+                const float dot = g0 * p0[j][u] + g1 * p1[j][u];
+                const float du0 = p0[j][u] * (g0 - dot), du1 = p1[j][u] * (g1 - dot);
                 dpre2[2 * j][u] = du0 * (pre2[2 * j][u] > 0.f ? 1.f : kLeaky);
                 dpre2[2 * j + 1][u] = du1 * (pre2[2 * j + 1][u] > 0.f ? 1.f : kLeaky);
             }
         }
-    }
-    if constexpr (BWD) {
         float dc[M + 2][W];
 #pragma unroll
         for (int i = 0; i < M + 2; ++i) {
@@ -212,30 +246,35 @@ __device__ __forceinline__ void tail_cells(const float (&z0)[W], const float (&z
         for (int o = 0; o < O; ++o)
 #pragma unroll
             for (int u = 0; u < W; ++u) A.g[oB2 + o] += dpre2[o][u];
-        float d0[W], d1[W];
+        // cell by cell, so that a cell's dz leaves as soon as its two sums are final (every accumulator still takes its
+        // terms with u ascending)
 #pragma unroll
         for (int u = 0; u < W; ++u) {
-            d0[u] = dc[M][u];
-            d1[u] = dc[M + 1][u];
-        }
+            float d0 = dc[M][u], d1 = dc[M + 1][u];
 #pragma unroll
-        for (int j = 0; j < M; ++j) {
-#pragma unroll
-            for (int u = 0; u < W; ++u) {
+            for (int j = 0; j < M; ++j) {
                 const float dp = dc[j][u] * (pre1[j][u] > 0.f ? 1.f : kLeaky);
                 A.g[oW1 + j] = __builtin_fmaf(z0[u], dp, A.g[oW1 + j]);
                 A.g[oW1 + M + j] = __builtin_fmaf(z1[u], dp, A.g[oW1 + M + j]);
                 A.g[oB1 + j] += dp;
-                d0[u] = __builtin_fmaf(dp, sw[oW1 + j], d0[u]);
-                d1[u] = __builtin_fmaf(dp, sw[oW1 + M + j], d1[u]);
+                d0 = __builtin_fmaf(dp, sw[oW1 + j], d0);
+                d1 = __builtin_fmaf(dp, sw[oW1 + M + j], d1);
             }
+            out.dz(u, d0, d1);
         }
-#pragma unroll
-        for (int u = 0; u < W; ++u) dzv[u] = make_float2(d0[u], d1[u]);
     } else {
 #pragma unroll
-        for (int u = 0; u < W; ++u) dzv[u] = make_float2(0.f, 0.f);
+        for (int u = 0; u < W; ++u) out.dz(u, 0.f, 0.f);
     }
+}
+
+// the pointer-per-cell form: prob_cell[u] (nullable) -> NB float2, dz of cell u -> dzv[u]
+template <int NB, bool BWD, int W>
+__device__ __forceinline__ void tail_cells(const float (&z0)[W], const float (&z1)[W], const int (&lab)[W][NB],
+                                           const bool (&valid)[W], const float* __restrict__ sw, const float inv_count,
+                                           float* const (&prob_cell)[W], TailLaneAcc<NB, BWD>& A, float2 (&dzv)[W]) {
+    const TailOutPtrs<W> out{prob_cell, dzv};
+    tail_cells_out<NB, BWD, W, false>(z0, z1, lab, valid, sw, inv_count, A, out);
 }
 
 // one cell (W = 1)
