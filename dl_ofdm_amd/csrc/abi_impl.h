@@ -202,6 +202,7 @@ size_t dense_tail_ws_bytes(int M, int N, int nbits);
 int eq_monitor_blocks(int B, int K);
 int gen_static_args(const dccn_gen_static* g, GenStaticArgs* out);
 int gen_static_launch(const dccn_gen_static* g, hipStream_t s, const GenChainScalars* chains = nullptr);
+bool gen_static_shape_ok(int S, int K, int CP);            // the instantiated shapes: (7, 64, 16) and (7, 64, 4)
 bool gen_static_ok(const dccn_gen_static* g);
 bool gen_static_doppler(const dccn_gen_static* g);       // the frame plan holds Doppler frames (the Doppler instantiation)
 int norm_fused_blocks(int cols);

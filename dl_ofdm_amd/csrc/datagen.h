@@ -333,8 +333,9 @@ struct GenChainScalars {
 typedef float gen_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kGenFramesPerBlock = 2;
 constexpr int kGenFirPad = 64;             // >= the longest channel response the launch accepts (L <= 64)
-// S, K, CP are compile-time (the N = 64 grid of the reference: 7 symbols, 64 + 16 samples): every index split is a division by a
-// constant, and the per-thread loops over a block's 1024 grid cells and 1120 samples are unrolled -- a thread's cells / samples
+// S, K, CP are compile-time (the N = 64 grid of the reference: 7 symbols, 64 + 16 samples, or 64 + 4 at the short prefix): every
+// index split is a division by a constant, and the per-thread loops over a block's 1024 grid cells and 1120 (952) samples are
+// unrolled -- a thread's cells / samples
 // are INDEPENDENT chains (Philox -> Box-Muller -> store; cell map -> Philox -> constellation table) whose latencies then
 // overlap instead of adding up (the first version walked them one after the other with run-time divisions: 26.8 us per launch;
 // profiles/r05_e2e_kernel_stats.txt has this one)
@@ -365,12 +366,19 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
     extern __shared__ __attribute__((aligned(16))) float gsm[];
     constexpr int K2 = 2 * K, N2 = 2 * (K + CP), T = S * (K + CP), LDG = K2 + 4;
     // the cyclic-prefix columns of the ifft matrix are bitwise copies of its last 2 CP columns (t = (t' - CP) mod K,
-    // datagen.py idft_cp_matrix): only the K2 / 16 tiles behind the prefix are multiplied, the prefix is stored twice
-    constexpr int G16 = K2 / 16, NTILE = N2 / 16, CPT = 2 * CP / 16, NMUL = NTILE - CPT, TPW = (NMUL + 3) / 4;
-    static_assert((2 * CP) % 16 == 0 && CPT <= NMUL, "cyclic prefix: whole 16-column tiles");
-    constexpr int NSMP = (kGenFramesPerBlock * T + 255) / 256;          // samples per thread (5)
+    // datagen.py idft_cp_matrix): only the K2 / 16 tiles behind the prefix are multiplied, the prefix is stored twice.
+    // TILED (CP = 16): the prefix is CPT whole tiles of a 16-aligned grid over the N2 columns, the multiplied tiles are
+    // CPT..NTILE-1 and the last CPT of them are stored twice.  Otherwise (CP = 4: 8 prefix columns, N2 = 136) the same K2 / 16
+    // tiles are anchored at column 2 CP -- body tile t covers columns 2 CP + 16 t .. -- and a column whose index behind the
+    // prefix is >= K2 - 2 CP goes to the prefix too: a per-lane condition inside the last tile.  (Two forms of one index
+    // computation under `if constexpr`: the tiled instantiations keep the code objects they had.)
+    constexpr bool TILED = (2 * CP) % 16 == 0;
+    constexpr int G16 = K2 / 16, CP2 = 2 * CP, NTILE = N2 / 16, CPT = CP2 / 16, NMUL = TILED ? NTILE - CPT : G16, TPW = (NMUL + 3) / 4;
+    static_assert(TILED ? (N2 % 16 == 0 && CPT <= NMUL) : (CP2 < 16 && NMUL % 4 == 0),
+                  "cyclic prefix: whole 16-column tiles, or less than one tile with every wave multiplying TPW whole tiles");
+    constexpr int NSMP = (kGenFramesPerBlock * T + 255) / 256;          // samples per thread (CP = 16: 5, CP = 4: 4)
     constexpr int NCELL = 16 * K / 256;                                  // grid cells per thread (4)
-    static_assert(kGenFramesPerBlock * S <= 16 && K2 % 16 == 0 && N2 % 16 == 0 && (16 * K) % 256 == 0, "generator tile shape");
+    static_assert(kGenFramesPerBlock * S <= 16 && K2 % 16 == 0 && (16 * K) % 256 == 0, "generator tile shape");
     // the time-domain frames sit between two runs of kGenFirPad zeros: the 'same' FIR then reads its out-of-range neighbours
     // as zeros instead of branching around them (adding +-0 leaves every partial sum as it was: same bits as the skipped form)
     constexpr int TP = T + 2 * kGenFirPad;
@@ -408,13 +416,19 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
     static_assert(kGenFramesPerBlock * 2 * kGenFirPad == 256, "one pad cell per thread");
     sTX[(tid >> 7) * TP + ((tid >> 6) & 1) * (kGenFirPad + T) + (tid & 63)] = make_float2(0.f, 0.f);
 
-    // 2 (early). this wave's share of the ifft matrix: tiles w, w + 4, ... ; lane (c, kq) needs idft[16 g + 4 kq + j][16 tile + c]
+    // 2 (early). this wave's share of the ifft matrix: body tiles w, w + 4, ... ; lane (c, kq) needs
+    // idft[16 g + 4 kq + j][2 CP + 16 tile + c] (per-lane scalar loads: the column origin needs no alignment)
     const int c = lane & 15, kq = lane >> 4;
     float bfr[TPW][G16][4];
 #pragma unroll
     for (int ti = 0; ti < TPW; ++ti) {
-        const int tile = min(CPT + w + 4 * ti, NTILE - 1);
-        const float* B = a.idft + (size_t)(4 * kq) * N2 + 16 * tile + c;
+        const float* B;
+        if constexpr (TILED) {
+            const int tile = min(CPT + w + 4 * ti, NTILE - 1);
+            B = a.idft + (size_t)(4 * kq) * N2 + 16 * tile + c;
+        } else {
+            B = a.idft + (size_t)(4 * kq) * N2 + CP2 + 16 * (w + 4 * ti) + c;
+        }
 #pragma unroll
         for (int g = 0; g < G16; ++g)
 #pragma unroll
@@ -544,15 +558,28 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
         float* txf = reinterpret_cast<float*>(sTX);
 #pragma unroll
         for (int ti = 0; ti < TPW; ++ti) {
-            const int tile = CPT + w + 4 * ti;
-            if (tile < NTILE) {
+            if constexpr (TILED) {
+                const int tile = CPT + w + 4 * ti;
+                if (tile < NTILE) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int row = 4 * kq + r, fr = row / S;
+                        if (fr < nfr) {
+                            float* o = txf + fr * 2 * TP + 2 * kGenFirPad + (row - fr * S) * N2 + 16 * tile + c;
+                            o[0] = acc[ti][r];
+                            if (tile >= NTILE - CPT) o[-K2] = acc[ti][r];          // the prefix: columns 2K.. are columns 0..
+                        }
+                    }
+                }
+            } else {
+                const int col = 16 * (w + 4 * ti) + c;                             // behind the prefix: 0 .. K2 - 1
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = 4 * kq + r, fr = row / S;
                     if (fr < nfr) {
-                        float* o = txf + fr * 2 * TP + 2 * kGenFirPad + (row - fr * S) * N2 + 16 * tile + c;
+                        float* o = txf + fr * 2 * TP + 2 * kGenFirPad + (row - fr * S) * N2 + CP2 + col;
                         o[0] = acc[ti][r];
-                        if (tile >= NTILE - CPT) o[-K2] = acc[ti][r];              // the prefix: columns 2K.. are columns 0..
+                        if (col >= K2 - CP2) o[-K2] = acc[ti][r];                  // the prefix, as above
                     }
                 }
             }
@@ -688,8 +715,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     gen_static_frames_body<S, K, CP>(a, P0, P1, (int)blockIdx.x);
 }
 // the launch for descriptors with Doppler frames.  33.5 KB of LDS more than the static launch (per-symbol responses 7 KB, taps
-// 1.75 KB, phases 12 KB, Doppler shifts 12 KB): 54.9 KB per workgroup, two workgroups per CU instead of the static launch's
-// three -- 512 resident workgroups, which a 73-frame batch (37) never reaches and a 1170-frame batch (585) passes either way
+// 1.75 KB, phases 12 KB, Doppler shifts 12 KB): 54.9 KB per workgroup (CP = 4: 53.5 KB), two workgroups per CU instead of the
+// static launch's three -- 512 resident workgroups, which a 73-frame batch (37) never reaches and a 1170-frame batch (585) passes either way
 template <int S, int K, int CP>
 constexpr size_t gen_doppler_smem_bytes() {
     return gen_static_smem_bytes<S, K, CP>() + (size_t)kGenFramesPerBlock * (S * 64 + S * 16) * sizeof(float2) +

@@ -1170,6 +1170,9 @@ bool gen_static_doppler(const dccn_gen_static* g) {
         if (!g->profiles[i].identity && g->profiles[i].Fd > 0.1f) return true;
     return false;
 }
+// the shapes the launch is instantiated for (dccn_gen_static_supported is this)
+bool gen_static_shape_ok(int S, int K, int CP) { return S == 7 && K == 64 && (CP == 16 || CP == 4); }
+static_assert(gen_static_smem_bytes<7, 64, 4>() == 18112, "short prefix: 16 x 132 grid floats + 2 x (476 + 128) samples");
 bool gen_static_ok(const dccn_gen_static* g) {
     if (!g || !g->bits_out || !g->cell_map || !g->const_tab || !g->idft || !g->snr_db || !g->y || !g->noise || !g->power_partial)
         return false;
@@ -1197,8 +1200,9 @@ bool gen_static_ok(const dccn_gen_static* g) {
             if (!std::isfinite(g->profiles[i].Fd)) return false;
         if (gen_static_doppler(g) && g->H_out && g->h_rep != g->S) return false;
     }
-    // the instantiated shape: the reference's N = 64 frame with the long cyclic prefix, 7 symbols x (64 + 16) samples
-    return g->S == 7 && g->K == 64 && g->CP == 16 && aligned16(g->y) && aligned16(g->noise);
+    // the instantiated shapes: the reference's N = 64 frame, 7 symbols x (64 + 16) samples at the long cyclic prefix and
+    // 7 x (64 + 4) at the short one
+    return gen_static_shape_ok(g->S, g->K, g->CP) && aligned16(g->y) && aligned16(g->noise);
 }
 // the generator launch's argument block from its descriptor (also used by launches that carry the generator's workgroups as
 // riders: eq_step.h)
@@ -1247,10 +1251,17 @@ int gen_static_launch(const dccn_gen_static* g, hipStream_t s, const GenChainSca
     if (chains) gc = *chains;
     else memset(&gc, 0, sizeof(gc));
     if (tl_chain.G > 1 && gc.n != tl_chain.G) return DCCN_ERR_UNSUPPORTED;      // (a group needs every chain's seed / offset)
+    // (gen_static_ok: CP is 16 or 4)
     if (a.dop_period > 0) {       // (static descriptors keep the launch they had)
-        DCCN_LAUNCH_CHAINS_Z((gen_doppler_frames_kernel<7, 64, 16>), dim3(blocks), dim3(256), (gen_doppler_smem_bytes<7, 64, 16>()), s, a, gc);
-    } else {
+        if (g->CP == 16) {
+            DCCN_LAUNCH_CHAINS_Z((gen_doppler_frames_kernel<7, 64, 16>), dim3(blocks), dim3(256), (gen_doppler_smem_bytes<7, 64, 16>()), s, a, gc);
+        } else {
+            DCCN_LAUNCH_CHAINS_Z((gen_doppler_frames_kernel<7, 64, 4>), dim3(blocks), dim3(256), (gen_doppler_smem_bytes<7, 64, 4>()), s, a, gc);
+        }
+    } else if (g->CP == 16) {
         DCCN_LAUNCH_CHAINS_Z((gen_static_frames_kernel<7, 64, 16>), dim3(blocks), dim3(256), (gen_static_smem_bytes<7, 64, 16>()), s, a, gc);
+    } else {
+        DCCN_LAUNCH_CHAINS_Z((gen_static_frames_kernel<7, 64, 4>), dim3(blocks), dim3(256), (gen_static_smem_bytes<7, 64, 4>()), s, a, gc);
     }
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;

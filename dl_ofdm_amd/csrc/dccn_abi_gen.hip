@@ -104,7 +104,7 @@ int dccn_channel_awgn(const float* tx, const float* taps_in, const float* coeff,
 static_assert(sizeof(dccn_gen_static) == 200 && sizeof(dccn_rx_buffers) == 208 && sizeof(dccn_eq_buffers) == 208 &&
               sizeof(dccn_eq_monitor) == 88, "ctypes mirrors in dl_ofdm_amd/_lib.py");
 int dccn_gen_static_supported(int S, int K, int CP) {
-    return (S == 7 && K == 64 && CP == 16) ? 1 : 0;
+    return gen_static_shape_ok(S, K, CP) ? 1 : 0;
 }
 int dccn_gen_static_partials(int frames) { return frames > 0 ? ceil_div(frames, kGenFramesPerBlock) : 0; }
 int dccn_gen_static_frames(const dccn_gen_static* g, dccn_stream_t stream) { return gen_static_launch(g, (hipStream_t)stream); }

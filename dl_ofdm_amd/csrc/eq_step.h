@@ -291,9 +291,9 @@ static int eq_step_plan(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
     const dccn_gen_static* gv = b->x_next_virtual;
     p.gen_wanted = train && b->gen_next_rides != 0;
     if (p.gen_wanted && gv == nullptr) return DCCN_ERR_INVALID_ARG;
-    // (the bottleneck backward launch carries the static generator body only: a descriptor with Doppler frames is the step's
-    // first launch, with the chain scalars of a group)
-    p.gen_rides = p.gen_wanted && p.bn && gen_static_ok(gv) && !gen_static_doppler(gv);
+    // (the bottleneck backward launch carries the static generator body of the long prefix only: a descriptor with Doppler
+    // frames or with the short prefix is the step's first launch, with the chain scalars of a group)
+    p.gen_rides = p.gen_wanted && p.bn && gen_static_ok(gv) && !gen_static_doppler(gv) && gv->CP == 16;
     if (p.gen_wanted) DCCN_TRY(gen_static_args(gv, &p.ga));
     if (p.gen_wanted && tl_chain.G > 1) {
         p.gsc.n = tl_chain.G;

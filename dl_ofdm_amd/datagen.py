@@ -14,8 +14,8 @@ Scope: every channel of ``rayleigh_chan_lte``: the single-profile ones ('AWGN', 
 'Custom'), static or mobile (Jakes Doppler, radio.py:376-407: per-symbol taps, per-symbol FIR with n_taps samples
 of history), and the frame-interleaved 'mixRayleigh' / 'mixAll' (radio.py:438-470: profile = frame index modulo 4
 or 5, Doppler on every 3rd / 4th frame when ``mix``) -- those run one launch pair per (profile, static|Doppler)
-group over a frame-index list.  ``FusedStaticGen`` is the same chain as ONE launch on the N = 64 grid, Doppler frames
-included: what the training loops use.
+group over a frame-index list.  ``FusedStaticGen`` is the same chain as ONE launch on the N = 64 grid at either cyclic
+prefix length of the reference driver (``longcp``: CP = 16, else CP = 4), Doppler frames included: what the training loops use.
 """
 from __future__ import annotations
 
@@ -246,7 +246,8 @@ class FusedStaticGen:
     gen_doppler_frames_kernel when the frame plan has Doppler frames): bits -> grid -> ifft + CP -> per frame static taps and
     the 'same' FIR, or Jakes taps per symbol and the per-symbol FIR -> (y, frame-scaled noise, power partials).  Channels: one
     profile, static or mobile (every frame a Doppler frame), and the frame-interleaved mixRayleigh / mixAll with or without
-    ``mix`` (Doppler on every 3rd / 4th frame) -- the reference driver's ``--mobile=True`` default among them.  The
+    ``mix`` (Doppler on every 3rd / 4th frame) -- the reference driver's ``--mobile=True`` default among them -- on the
+    N = 64 grid at both prefix lengths the driver trains at (``longcp``: 64 + 16 samples per symbol, else 64 + 4).  The
     receiver's input x = y / sqrt(mean |y|^2) + noise is formed by the consumer: ``RxEngine.
     train_step_generated`` hands the descriptor to ``dccn_rx_train_step``, which issues the generator launch itself and reads
     (y, noise, partials) as the virtual input of its pipelined normalisation -- one C call and five launches per generated-and-
@@ -255,8 +256,9 @@ class FusedStaticGen:
 
     def __init__(self, gen: DeviceDataGen, n_frames: int, snr_db, want_noise_power: bool = False, arena=None):
         if not self.supported(gen):
-            raise _lib.DccnError("FusedStaticGen: N = 64 channels without align_window only (one profile, static or mobile, or the "
-                                 "frame-interleaved profiles of mixRayleigh / mixAll; L <= 64, n_taps <= 16, at most 6 profiles)")
+            raise _lib.DccnError("FusedStaticGen: N = 64 channels at the long or the short cyclic prefix (CP = 16 / CP = 4) without "
+                                 "align_window only (one profile, static or mobile, or the frame-interleaved profiles of "
+                                 "mixRayleigh / mixAll; L <= 64, n_taps <= 16, at most 6 profiles)")
         from . import arena as A
         self.gen, self.n = gen, int(n_frames)
         self.arena = arena

@@ -48,7 +48,7 @@ class _Chain:
         self.steps = (FLAGS.msg_length // FLAGS.nsymbol) // self.B
         self.gen = DeviceDataGen(FLAGS, self.o, device=self.tr.device, seed=FLAGS.seed, mobile=FLAGS.mobile, mix=FLAGS.mobile)
         if not FusedStaticGen.supported(self.gen):
-            raise _lib.DccnError("chain groups need the fused generator (N = 64 grid, no align_window)")
+            raise _lib.DccnError("chain groups need the fused generator (N = 64 grid at CP = 16 or CP = 4, no align_window)")
         self.pl = _FusedPlan(self.tr, self.B, arena=self.arena)
         self.tr._plans[self.B] = self.pl
         self.ev = self.tr.resident(FLAGS.eval_frames)                      # evaluation runs per chain, outside the group

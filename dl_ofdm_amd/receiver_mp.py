@@ -314,8 +314,8 @@ class DeviceEpochLoop:
         self.acc = A.zeros(arena, 5, dtype=torch.float32, device=dev)
         self.snr = A.zeros(arena, self.steps, B, dtype=torch.float32, device=dev)
         self.snr_rows = [self.snr[i] for i in range(self.steps)]
-        # N = 64 channels, static or mobile (one profile, or the frame-interleaved profiles of mixRayleigh / mixAll with their
-        # Doppler frames: the reference driver's --mobile=True default): the whole generator chain of a batch is ONE launch +
+        # N = 64 channels at either cyclic prefix length (longcp or not), static or mobile (one profile, or the frame-interleaved
+        # profiles of mixRayleigh / mixAll with their Doppler frames: the reference driver's --mobile=True default): the whole generator chain of a batch is ONE launch +
         # the launch that forms x (datagen.FusedStaticGen) instead of 5 to 12
         self.fg = None
         if getattr(FLAGS, "fused_generator", True):

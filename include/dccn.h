@@ -358,8 +358,8 @@ typedef struct dccn_rx_shape {
     int nbits;     /* 1..4 */
 } dccn_rx_shape;
 
-/* The fused device-side generator: a whole batch of any channel of rayleigh_chan_lte on the N = 64 grid in ONE launch (the
- * chain of dccn_ofdm_tx_frames + dccn_channel_awgn / _doppler_awgn / _groups_awgn below; csrc/datagen.h
+/* The fused device-side generator: a whole batch of any channel of rayleigh_chan_lte on the N = 64 grid, at either cyclic
+ * prefix length of the reference driver (CP = 16 / CP = 4: dccn_gen_static_supported), in ONE launch (the chain of dccn_ofdm_tx_frames + dccn_channel_awgn / _doppler_awgn / _groups_awgn below; csrc/datagen.h
  * gen_static_frames_kernel, gen_doppler_frames_kernel): label bits -> resource grid -> ifft + cyclic prefix -> per frame
  * either static Rayleigh taps and the 'same' FIR, or (Doppler frames) Jakes taps per symbol and the per-symbol FIR with n_taps
  * samples of history (dev/py/util.py:25-29, ofdm.py:328-380, radio.py:352-407, 438-452) -> y, plus the frame-scaled noise of
@@ -420,7 +420,9 @@ typedef struct dccn_gen_profile {
     int n_taps, L, identity;
     float Fd;                     /* this profile's Doppler frequency in Hz (was `reserved`: a float's zero is the int's zero) */
 } dccn_gen_profile;
-int dccn_gen_static_supported(int S, int K, int CP);      /* 1: shapes the fused launch is instantiated for (N = 64) */
+/* 1: shapes the fused launch is instantiated for -- the N = 64 grid of 7 symbols at the long cyclic prefix (7, 64, 16) and at
+ * the short one (7, 64, 4); 0 for everything else (such a descriptor is refused with DCCN_ERR_INVALID_ARG, nothing launched) */
+int dccn_gen_static_supported(int S, int K, int CP);
 int dccn_gen_static_partials(int frames);
 int dccn_gen_static_frames(const dccn_gen_static* g, dccn_stream_t stream);
 /* x_out [frames, S, K+CP, 2] = y / sqrt(mean |y|^2) + noise; noise_power (nullable) = mean |noise|^2 */
@@ -735,7 +737,10 @@ typedef struct dccn_eq_buffers {
        plan has no such launch).  The caller no longer issues dccn_gen_static_frames for that batch.  Same draws, same bits.
        A descriptor with Doppler frames does not ride: its generator is the step's own FIRST launch (also for a chain group,
        one launch for all chains).  The bottleneck backward launch keeps the static generator as its only rider: the Doppler
-       body needs 54.9 KB of LDS beside that kernel's 10.6 KB and is several times the launch's longest work item. */
+       body needs 54.9 KB of LDS beside that kernel's 10.6 KB and is several times the launch's longest work item.
+       A descriptor at the short cyclic prefix (CP = 4) does not ride either, with or without Doppler frames: the rider is the
+       (7, 64, 16) instantiation only, so its generator takes the same route -- the step's own first launch.  Same draws,
+       same bits as a launch issued by the caller. */
     int gen_next_rides;
     /* Round 6, nullable: the training loop's per-step monitors (dccn_eq_monitor_accumulate: chan_rms of THIS step's channel
        estimate against `chan`, and {ce_mean, berlin, tx_power, noise_power, chan_rms} added onto acc5) as part of the step's

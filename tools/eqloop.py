@@ -5,6 +5,8 @@ alone.  One JSON line per variant.
 
     python tools/eqloop.py [--nbits 2] [--channel EPA] [--steps 300]
     python tools/eqloop.py --channel mixRayleigh --mobile 1 --only r04_loop_next [--fused 0]      (the reference driver's default channel)
+    python tools/eqloop.py --longcp 0 [--mobile 1 --channel mixRayleigh] --ab 7      (the short cyclic prefix; the pipelined loop with
+                                            --fused 1 and --fused 0 alternating in this process, 7 repeats of --steps steps each)
 """
 import argparse
 import json
@@ -27,6 +29,8 @@ def main():
     ap.add_argument("--virtual", type=int, default=1, help="0: the pipelined loop materialises every batch (no x_next_virtual)")
     ap.add_argument("--mobile", type=int, default=0, help="1: the mobile channel (mixed channels: Doppler on every 3rd / 4th frame)")
     ap.add_argument("--only", default="", help="run the variants whose name contains this")
+    ap.add_argument("--longcp", type=int, default=1, help="0: the short cyclic prefix (N = 64: CP = 4)")
+    ap.add_argument("--ab", type=int, default=0, help="> 0: the harness's loop with and without the fused generator, alternating, this many repeats")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -41,7 +45,10 @@ def main():
     F.virtual_next = bool(args.virtual)
     F.step_graph = bool(args.graph)
     F.mobile = bool(args.mobile)
+    F.longcp = bool(args.longcp)
     o = ofdm.ofdm_tx(F)
+    if args.ab > 0:
+        return ab(args, F, o)
     rx_params = glorot_init(R.rx_dims(F, o), 1)
     tr = EqualizerTrainer(F, o, rx_params, device="cuda", seed=1)
     gen = DeviceDataGen(F, o, device=tr.device, seed=1, mobile=bool(args.mobile), mix=bool(args.mobile))
@@ -107,6 +114,54 @@ def main():
         print(line, flush=True)
         if out:
             out.write(line + "\n")
+
+
+def ab(args, F, o):
+    """two complete loops (trainer, generator, plans) in one process, one per generator path: ms per step of every repeat,
+    median and repeat-to-repeat spread (max - min) / median"""
+    import copy
+    import numpy as np
+    import torch
+    from dl_ofdm_amd import receiver as R, receiver_mp as M
+    from dl_ofdm_amd.datagen import DeviceDataGen
+    from dl_ofdm_amd.engine import glorot_init
+    from dl_ofdm_amd.equalizer import EqualizerTrainer
+    rx_params = glorot_init(R.rx_dims(F, o), 1)
+    B = F.batch_size // F.nsymbol
+    runs = []
+    for fused in (1, 0):
+        Fv = copy.copy(F)
+        Fv.fused_generator = bool(fused)
+        tr = EqualizerTrainer(Fv, o, rx_params, device="cuda", seed=1)
+        gen = DeviceDataGen(Fv, o, device=tr.device, seed=1, mobile=bool(args.mobile), mix=bool(args.mobile))
+        loop = M.DeviceEpochLoop(Fv, o, tr, gen, tr.resident(B), args.steps)
+        assert (loop.fg is not None) == bool(fused)
+        runs.append((fused, loop, []))
+
+    def epoch(loop):
+        loop.begin_epoch(np.random.choice(M.TRAIN_SNR_GRID, [args.steps, B], p=M.TRAIN_SNR_PROB))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            loop.step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps * 1e3
+
+    for _, loop, _ in runs:
+        epoch(loop)                                                   # warm-up
+    for _ in range(args.ab):
+        for _, loop, ms in runs:
+            ms.append(epoch(loop))
+    for fused, loop, ms in runs:
+        v = sorted(ms)
+        med = v[len(v) // 2]
+        rec = {"variant": "harness_loop_ab", "frames": B, "channel": args.channel, "mobile": args.mobile, "CP": o.CP, "fused": fused,
+               "virtual_next": loop.virt is not None, "generator_issued_by_step": bool(getattr(loop, "ride_gen", False)) and loop.virt is not None,
+               "ms_per_step_wall": [round(t, 4) for t in ms], "median": round(med, 4), "spread": round((v[-1] - v[0]) / med, 4)}
+        print(json.dumps(rec), flush=True)
+        if args.out:
+            with open(args.out, "a") as f:
+                f.write(json.dumps(rec) + "\n")
 
 
 if __name__ == "__main__":
