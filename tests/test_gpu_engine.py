@@ -115,6 +115,10 @@ def staged_checks(eng, p, x, bits, cfg, rtol=RTOL, grad_rtol=RTOL, cos_tol=1e-5)
 
 @pytest.mark.parametrize("name,batch,nbits,kin,F,D", CASES)
 def test_train_step_matches_oracle(name, batch, nbits, kin, F, D):
+    """Forward, losses and every backward stage against the oracle, then the parameters after the first Adam step.  That
+    last check starts from m = v = 0, where the update is +-lr whatever the gradient's magnitude is: it cannot see a wrongly
+    scaled gradient, a dropped slab or a missing L2 term.  tests/test_gpu_optimizer.py carries that check, from a resumed
+    non-zero optimizer state."""
     from dl_ofdm_amd.engine import RxEngine
     dims, cfg, x, bits, p = make_case(batch, nbits, kin, F, D)
     eng = RxEngine(dims, batch, params=p, train=True)
