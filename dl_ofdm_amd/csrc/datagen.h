@@ -757,6 +757,34 @@ static __global__ __launch_bounds__(256) void gen_static_apply_kernel(const floa
         if (threadIdx.x == 0) npow_out[0] = (float)(((sh4[0] + sh4[1]) + (sh4[2] + sh4[3])) / total);
     }
 }
+// the same for a cp=False receiver (model.py:1236-1240 drops the cyclic prefix inside the graph): x_out [frames, S, K, 2] holds
+// the K samples behind the prefix of every symbol, x_out[f, s, 0:K] = y[f, s, CP:CP+K] * inv + noise[f, s, CP:CP+K] -- the scale
+// still that of the whole frames (total = frames * S * (K + CP)), the expression that of the full kernel: the bits of its output,
+// cropped.  In float4s: output i is element i % kw4 of symbol i / kw4 (symbols of all frames are consecutive), whose source
+// symbol has sym4 = 2 (K + CP) / 4 float4s with the window off4 = 2 CP / 4 into it.  grid: any; 256 threads.
+static __global__ __launch_bounds__(256) void gen_static_apply_window_kernel(const float4* __restrict__ y, const float4* __restrict__ noise,
+                                                                      const double* __restrict__ ppart, int npart, double total,
+                                                                      float4* __restrict__ x, long long n4, int kw4, int sym4, int off4,
+                                                                      const double* __restrict__ npart_noise, int n_noise,
+                                                                      float* __restrict__ npow_out) {
+    __shared__ double sh4[4];
+    __shared__ float s_inv;
+    const float inv = batch_power_inv_scale(ppart, npart, total, sh4, &s_inv);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const long long sym = i / kw4, src = sym * sym4 + off4 + (i - sym * kw4);
+        const float4 v = y[src], z = noise[src];
+        x[i] = make_float4(v.x * inv + z.x, v.y * inv + z.y, v.z * inv + z.z, v.w * inv + z.w);
+    }
+    if (npow_out != nullptr && blockIdx.x == 0) {
+        __syncthreads();
+        double a = 0.0;
+        for (int i = threadIdx.x; i < n_noise; i += 256) a += npart_noise[i];
+        a = wave_sum(a);
+        if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = a;
+        __syncthreads();
+        if (threadIdx.x == 0) npow_out[0] = (float)(((sh4[0] + sh4[1]) + (sh4[2] + sh4[3])) / total);
+    }
+}
 
 // radio.py:62-88 AWGN_channel, the *in-graph* monitor branch of the receiver graph (ofdmreceiver_np.py:136,151-152):
 // xn = batch-normalised (eps 1e-8) clipped signal / sqrt(2) (computed by the caller with the R0 kernel),

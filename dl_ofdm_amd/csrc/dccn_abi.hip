@@ -1314,6 +1314,7 @@ struct RxStepPlan {
     bool norm_after;                // ... or as launches of its own (shapes the single-pass kernel does not take)
     bool wait_x;                    // the launch that reads the next batch waits for the producer's event first
     const dccn_gen_static* gen;     // the next batch comes from the fused generator (gen_next)
+    bool gen_window;                // ... read through the window behind the cyclic prefix (kin == K: a cp=False receiver)
     OverlapStreams branch;          // forked variant (dccn_rx_graph_create mode bit 1): dense dW/db on the caller's second stream
     bool want_overlap;              // large layers: the dense kernel's update on the library's second stream (ovs)
     OverlapStreams ovs;
@@ -1373,12 +1374,21 @@ static int rx_step_plan(const dccn_rx_shape* sh, const dccn_rx_buffers* b, bool 
     // (y, noise, power partials) as R0's virtual input instead of a materialised x_next (x_next, when given too, receives x).
     // x_next_ready set as well: the caller has issued the generator itself on ANOTHER stream.  The double-buffered pipelining
     // has no virtual-input form: refuse rather than normalise a stale x_next (dccn_rx_gen_next_supported is the caller's query)
+    // kin == K + CP: R0 reads the generator's whole symbols.  kin == K (a cp=False receiver, model.py:1236-1240): R0 reads the K
+    // samples behind the cyclic prefix of every symbol (norm_adam.h NormVirtual, the windowed instantiation; x_next, when given,
+    // receives that window).  Any other kin is refused.
     p.gen = b->gen_next;
     if (p.gen != nullptr) {
-        if (p.gen->frames != sh->batch || p.gen->S != sh->S || 2 * (p.gen->K + p.gen->CP) * sh->S != L.cols)
-            return DCCN_ERR_INVALID_ARG;
+        const bool whole = sh->kin == p.gen->K + p.gen->CP, window = !whole && sh->kin == p.gen->K;
+        if (p.gen->frames != sh->batch || p.gen->S != sh->S || !(whole || window)) return DCCN_ERR_INVALID_ARG;
         if (b->x_norm_next != nullptr || !gen_static_ok(p.gen) || !rx_gen_next_ok(sh, p.gen->y, b->x_norm))
             return DCCN_ERR_INVALID_ARG;
+        // the source as the window reads it: rows of S * 2 (K + CP) floats, 2 K floats from 2 CP floats into each symbol -- whole
+        // float4s, and the 2 K = 128 the windowed kernel is instantiated for
+        if (window && (2 * p.gen->K != kWinK2 || (2 * p.gen->CP) % 4 != 0 ||
+                       !norm_fused_ok(p.gen->y, b->x_norm, sh->batch, sh->S * 2 * (p.gen->K + p.gen->CP))))
+            return DCCN_ERR_INVALID_ARG;
+        p.gen_window = window;
     }
     const float* rin = p.gen ? p.gen->y : b->x_next;
     p.ride_opt = !p.ride_bw && rin != nullptr && kNormFusedCG == 2 && norm_fused_ok(rin, b->x_norm, sh->batch, L.cols);
@@ -1537,9 +1547,19 @@ static int rx_issue_update(const dccn_rx_shape* sh, const dccn_rx_buffers* b, co
         aa.nx = rin; aa.ny = b->x_norm; aa.npower = b->tx_power ? const_cast<double*>(np.partial) : nullptr;
         aa.nbatch = sh->batch; aa.ncols = L.cols; aa.norm_blocks = norm_fused_blocks(L.cols);
         blocks += aa.norm_blocks;
-        if (p.gen) aa.nv = norm_virtual_gen(p.gen, ceil_div(p.gen->frames, kGenFramesPerBlock), const_cast<float*>(b->x_next));
+        const int npart = p.gen ? ceil_div(p.gen->frames, kGenFramesPerBlock) : 0;
+        if (p.gen_window) aa.nv = norm_virtual_gen_window(p.gen, npart, const_cast<float*>(b->x_next));
+        else if (p.gen) aa.nv = norm_virtual_gen(p.gen, npart, const_cast<float*>(b->x_next));
     }
-    switch (k->ds.splits) {
+    if (p.ride_opt && p.gen_window) {
+        // the windowed instantiation of R0 rides: a kernel of its own (every other step launches what it launched before)
+        switch (k->ds.splits) {
+            case 2: hipLaunchKernelGGL(adam_rx_window_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
+            case 3: hipLaunchKernelGGL(adam_rx_window_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
+            case 4: hipLaunchKernelGGL(adam_rx_window_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
+            default: hipLaunchKernelGGL(adam_rx_window_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
+        }
+    } else switch (k->ds.splits) {
         case 2: hipLaunchKernelGGL(adam_rx_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
         case 3: hipLaunchKernelGGL(adam_rx_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
         case 4: hipLaunchKernelGGL(adam_rx_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;

@@ -124,6 +124,26 @@ int dccn_gen_static_apply(const dccn_gen_static* g, float* x_out, float* noise_p
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
 }
+// the batch of a cp=False receiver: the K samples behind the cyclic prefix of every symbol (gen_static_apply_window_kernel)
+int dccn_gen_static_apply_window(const dccn_gen_static* g, float* x_out, float* noise_power, dccn_stream_t stream) {
+    if (!gen_static_ok(g) || !x_out || !aligned16(x_out)) return DCCN_ERR_INVALID_ARG;
+    // (gen_static_ok: K = 64 and CP = 16 or 4, so a symbol, its window and the window's offset are whole float4s)
+    if ((2 * g->K) % 4 != 0 || (2 * g->CP) % 4 != 0) return DCCN_ERR_INVALID_ARG;
+    DCCN_NO_CHAINS();             // (the launch carries no chain table: inside a group it would serve chain 0 only)
+    const int T = g->S * (g->K + g->CP), kw4 = 2 * g->K / 4;
+    const long long n4 = (long long)g->frames * g->S * kw4;
+    const int np = dccn_gen_static_partials(g->frames);
+    long long blocks = ceil_div_ll(n4, 256);
+    if (blocks > 4 * kCUs) blocks = 4 * kCUs;
+    hipLaunchKernelGGL(gen_static_apply_window_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const float4*>(g->y), reinterpret_cast<const float4*>(g->noise),
+                       (const double*)g->power_partial, np, (double)g->frames * (double)T, reinterpret_cast<float4*>(x_out), n4, kw4,
+                       2 * (g->K + g->CP) / 4, 2 * g->CP / 4,
+                       (const double*)((noise_power && g->noise_partial) ? g->noise_partial : nullptr), np,
+                       (noise_power && g->noise_partial) ? noise_power : nullptr);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
 
 size_t dccn_channel_doppler_awgn_workspace_size(int frames, int T, int L, int S) {
     if (frames <= 0 || T <= 0 || L <= 0 || S <= 0) return 0;

@@ -212,11 +212,22 @@ static __global__ __launch_bounds__(256) void normalise_kernel(const float* __re
 // output, noise already scaled per frame, the batch power as <= 2048 per-block partial sums of the generator launch.  R0 forms
 // x in registers on the way in (the expression and the order of awgn_kernel: the same bits as the materialised input), so
 // the AWGN launch and a 5 MB round trip of x disappear.  y == nullptr: plain input.
+// Windowed virtual input (cp=False receivers, model.py:1236-1240: the graph drops the cyclic prefix and the C-Conv sees K
+// samples per symbol): the generator still writes whole symbols of wsym = 2 (K + CP) floats, R0 reads the 2 K floats that
+// start woff = 2 CP floats into each -- output column c of [0, S 2K) comes from source float (c / 2K) wsym + woff + c % 2K of a
+// row of (cols / 2K) wsym floats.  The power scale stays that of the WHOLE frames (total, ppart): what the materialised path
+// computes before it crops.  Only the WIN instantiation of norm_fused_body reads wsym / woff (they sit where the struct had
+// padding: the argument blocks of the launches that carry a NormVirtual are unchanged).
+constexpr int kWinK2 = 128;                       // 2 K floats per windowed symbol (the N = 64 grid)
 struct NormVirtual {
-    const float* y; const float* noise;           // [batch, cols] each
-    const double* ppart; int npart; double total; // partial sums of |y|^2, batch * T (complex samples)
-    float* x_out;                                 // nullable: also store x (tx_ofdm) -- tests, iq dumps
-    const double* npart_noise; int n_noise; float* npow_out;      // nullable: `noise_power:0` monitor, summed by block 0
+    const float* y; const float* noise;           // [batch, cols] each (windowed: [batch, (cols / 2K) wsym])
+    const double* ppart; int npart;               // partial sums of |y|^2
+    int wsym;                                     // windowed: source floats per symbol, 2 (K + CP)
+    double total;                                 // batch * T (complex samples of the whole frames)
+    float* x_out;                                 // nullable: also store x (tx_ofdm; windowed: the window) -- tests, iq dumps
+    const double* npart_noise; int n_noise;       // nullable: `noise_power:0` monitor, summed by block 0
+    int woff;                                     // windowed: first source float of a symbol's window, 2 CP
+    float* npow_out;
     __device__ __forceinline__ NormVirtual at_chain(const long long coff) const {        // chain groups (common.h)
         NormVirtual q = *this;
         q.y = chain_at(y, coff); q.noise = chain_at(noise, coff); q.ppart = chain_at(ppart, coff); q.x_out = chain_at(x_out, coff);
@@ -228,8 +239,10 @@ __device__ __host__ inline NormVirtual norm_virtual_none() {
     NormVirtual v;
     v.y = nullptr; v.noise = nullptr; v.ppart = nullptr; v.npart = 0; v.total = 1.0; v.x_out = nullptr;
     v.npart_noise = nullptr; v.n_noise = 0; v.npow_out = nullptr;
+    v.wsym = 0; v.woff = 0;
     return v;
 }
+static_assert(sizeof(NormVirtual) == 72, "wsym / woff fill padding: kernel argument blocks keep their layout");
 // the fused generator's (y, noise, power partials of its npart blocks) as that input; x_out as above
 inline NormVirtual norm_virtual_gen(const dccn_gen_static* g, int npart, float* x_out) {
     NormVirtual v = norm_virtual_none();
@@ -238,6 +251,12 @@ inline NormVirtual norm_virtual_gen(const dccn_gen_static* g, int npart, float* 
     v.x_out = x_out;
     v.npart_noise = g->noise_partial; v.n_noise = npart;
     v.npow_out = g->noise_partial ? g->noise_power_out : nullptr;
+    return v;
+}
+// ... read through the window behind the cyclic prefix (x_out, when given, is [batch, S, K, 2])
+inline NormVirtual norm_virtual_gen_window(const dccn_gen_static* g, int npart, float* x_out) {
+    NormVirtual v = norm_virtual_gen(g, npart, x_out);
+    v.wsym = 2 * (g->K + g->CP); v.woff = 2 * g->CP;
     return v;
 }
 // 1 / sqrt(mean |y|^2): every block of a 256-thread launch adds the partial sums in the same fixed order (thread t: t, t + 256,
@@ -254,7 +273,9 @@ __device__ __forceinline__ float batch_power_inv_scale(const double* __restrict_
     return *s_inv;
 }
 
-template <int CG, int RPT>
+// WIN: the windowed virtual input (always virtual; its own instantiation, carried by adam_rx_window_kernel only -- every other
+// caller keeps the code it had)
+template <int CG, int RPT, bool WIN = false>
 __device__ __forceinline__ void norm_fused_body(const float* __restrict__ x, float* __restrict__ y, int batch, int cols,
                                                 float eps, float peak, double* __restrict__ power_partial,
                                                 float* __restrict__ mean_out, float* __restrict__ var_out,
@@ -267,7 +288,8 @@ __device__ __forceinline__ void norm_fused_body(const float* __restrict__ x, flo
     __shared__ double pred[NW > 4 ? NW : 4];
     __shared__ float s_inv;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const bool virt = NW == 4 && nv.y != nullptr;     // (kernel argument: block-uniform; 256-thread blocks only)
+    static_assert(!WIN || (NW == 4 && kWinK2 % (4 * CG) == 0), "windowed input: 256-thread blocks whose columns share a symbol");
+    const bool virt = WIN || (NW == 4 && nv.y != nullptr);     // (kernel argument: block-uniform; 256-thread blocks only)
     float inv_scale = 1.0f;
     if (virt) inv_scale = batch_power_inv_scale(nv.ppart, nv.npart, nv.total, pred, &s_inv);
     if (adam != nullptr && bidx == 0 && t == 0) {
@@ -287,9 +309,15 @@ __device__ __forceinline__ void norm_fused_body(const float* __restrict__ x, flo
     const int c4c = live ? c4 : 0;                    // clamped addresses: every load issues, none branches
     if (virt) {
         float4 nz[RPT];
+        int pitch = cols, src = c4c;                  // source row pitch and float index within a row
+        if constexpr (WIN) {
+            const int sym = c4c / kWinK2;             // (c4c is a multiple of 4 and so are wsym, woff: aligned float4s)
+            pitch = (cols / kWinK2) * nv.wsym;
+            src = sym * nv.wsym + nv.woff + (c4c - sym * kWinK2);
+        }
 #pragma unroll
         for (int p = 0; p < RPT; ++p) {
-            const size_t o = (size_t)min(slot + 128 * p, batch - 1) * cols + c4c;
+            const size_t o = (size_t)min(slot + 128 * p, batch - 1) * pitch + src;
             v[p] = *reinterpret_cast<const float4*>(nv.y + o);
             nz[p] = *reinterpret_cast<const float4*>(nv.noise + o);
         }
@@ -728,6 +756,29 @@ __global__ __launch_bounds__(256) void adam_rx_kernel(const AdamRxArgs a, const 
     if ((int)blockIdx.x < a.norm_blocks) {
         norm_fused_body<kNormFusedCG, kNormFusedRPT>(a.nx, a.ny, a.nbatch, a.ncols, a.neps, a.npeak, a.npower, nullptr, nullptr,
                                            nullptr, hp, (int)blockIdx.x, a.norm_blocks, a.nv);
+        stamp_mark(a.stamp, 1);
+        return;
+    }
+    const int bx = (int)blockIdx.x - a.norm_blocks, nbx = (int)gridDim.x - a.norm_blocks;
+    if (bx < a.fold_blocks) {
+        adam_fold_role(a, hp, bx);
+        stamp_mark(a.stamp, 1);
+        return;
+    }
+    adam_stream_role<SPLITS>(a, hp, bx - a.fold_blocks, nbx - a.fold_blocks);
+    stamp_mark(a.stamp, 1);
+}
+// the optimizer launch of a step whose next batch comes from the fused generator through the window (dccn_rx_buffers.gen_next
+// with kin == K; a.norm_blocks > 0, a.nv windowed): adam_rx_kernel with the WIN instantiation of R0 on its leading blocks, a
+// kernel of its own so that adam_rx_kernel stays the code it was, launched for such descriptors only.  SPLITS 2..4 and 0 are
+// instantiated -- what the dense gradient's plan gives a batch of at most 1536 frames (<= 4 ranges of 448 rows); any other
+// count takes the runtime form, which adds the same terms in the same order
+template <int SPLITS>
+__global__ __launch_bounds__(256) void adam_rx_window_kernel(const AdamRxArgs a, const dccn_adam_hparams hp) {
+    stamp_mark(a.stamp, 0);
+    if ((int)blockIdx.x < a.norm_blocks) {
+        norm_fused_body<kNormFusedCG, kNormFusedRPT, true>(a.nx, a.ny, a.nbatch, a.ncols, a.neps, a.npeak, a.npower, nullptr,
+                                                           nullptr, nullptr, hp, (int)blockIdx.x, a.norm_blocks, a.nv);
         stamp_mark(a.stamp, 1);
         return;
     }

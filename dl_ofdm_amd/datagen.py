@@ -252,7 +252,9 @@ class FusedStaticGen:
     train_step_generated`` hands the descriptor to ``dccn_rx_train_step``, which issues the generator launch itself and reads
     (y, noise, partials) as the virtual input of its pipelined normalisation -- one C call and five launches per generated-and-
     trained batch instead of two or three calls and eight or nine launches; ``make_batch`` materialises x (one more launch)
-    where a buffer is wanted.  Same Philox streams, draws and batch offsets as ``DeviceDataGen`` (it advances ``gen.offset``)."""
+    where a buffer is wanted.  A ``cp=False`` receiver (``kin = K``: the graph drops the cyclic prefix, model.py:1236-1240) takes
+    the same descriptor: its step reads, and ``make_batch`` writes, the K samples behind the prefix of every symbol, scaled by the
+    power of the whole frames.  Same Philox streams, draws and batch offsets as ``DeviceDataGen`` (it advances ``gen.offset``)."""
 
     def __init__(self, gen: DeviceDataGen, n_frames: int, snr_db, want_noise_power: bool = False, arena=None):
         if not self.supported(gen):
@@ -306,8 +308,11 @@ class FusedStaticGen:
     def supported(gen: DeviceDataGen, eng=None) -> bool:
         """``eng``: the training engine whose steps would take this generator as ``gen_next`` (train_step_generated): its batch
         must be one the pipelined normalisation can form from the generator's output (dccn_rx_gen_next_supported: the batch grows
-        with falling BER in receiver.train and leaves that range beyond 1536 frames)"""
+        with falling BER in receiver.train and leaves that range beyond 1536 frames), and its C-Conv must see whole symbols
+        (``kin = K + CP``) or the samples behind the cyclic prefix (``kin = K``, a ``cp=False`` receiver)"""
         if eng is not None and not bool(gen.lib.dccn_rx_gen_next_supported(C.byref(eng.shape))):
+            return False
+        if eng is not None and eng.dims.kin not in (gen.K + gen.CP, gen.K):
             return False
         if gen.align_window or not bool(gen.lib.dccn_gen_static_supported(gen.S, gen.K, gen.CP)):
             return False
@@ -351,13 +356,19 @@ class FusedStaticGen:
     def make_batch(self, out_x: torch.Tensor, out_bits: torch.Tensor, slot: int = 0, tx_out: Optional[torch.Tensor] = None,
                    out_H: Optional[torch.Tensor] = None, snr: Optional[torch.Tensor] = None):
         """generate + materialise: (x, bits, noise power or None), two launches (the first batch of a pipelined loop, the
-        equaliser's epoch loop, tests)"""
+        equaliser's epoch loop, tests).  ``out_x``: [n, S, K+CP, 2], the whole symbols, or [n, S, K, 2], the samples behind the
+        cyclic prefix (a ``cp=False`` receiver's input); anything else raises ValueError before a launch."""
+        g = self.gen
+        whole, window = self.n * g.S * (g.K + g.CP) * 2, self.n * g.S * g.K * 2
+        if out_x.numel() not in (whole, window):
+            raise ValueError("out_x must hold %d (whole symbols) or %d (behind the cyclic prefix) floats, got shape %s"
+                             % (whole, window, tuple(out_x.shape)))
+        apply = "dccn_gen_static_apply" if out_x.numel() == whole else "dccn_gen_static_apply_window"
         d = self.arm(out_bits, slot, tx_out, out_H, snr)
-        st = self.gen._stream()
-        check(self.gen.lib.dccn_gen_static_frames(C.byref(d), st), "dccn_gen_static_frames")
+        st = g._stream()
+        check(g.lib.dccn_gen_static_frames(C.byref(d), st), "dccn_gen_static_frames")
         npw = self.npow[slot & 1] if self.npow is not None else None
-        check(self.gen.lib.dccn_gen_static_apply(C.byref(d), out_x.data_ptr(), None if npw is None else npw.data_ptr(), st),
-              "dccn_gen_static_apply")
+        check(getattr(g.lib, apply)(C.byref(d), out_x.data_ptr(), None if npw is None else npw.data_ptr(), st), apply)
         return out_x, out_bits, npw
 
 

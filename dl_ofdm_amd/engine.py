@@ -296,7 +296,11 @@ class RxEngine:
         the batch normalised ahead (labels in ``label_slot(slot)``), issues the generator launch of the NEXT batch as its first
         launch (labels to the other slot) and normalises that batch -- read as (y, noise, power partials), never written as x
         unless ``keep_x`` -- on its optimizer launch.  The first call generates, materialises and normalises batch 0 itself.
-        Bit-identical to ``train_step_pipelined`` on the materialised batches (tests/test_gpu_datagen.py)."""
+        Bit-identical to ``train_step_pipelined`` on the materialised batches (tests/test_gpu_datagen.py).
+        A ``cp=False`` engine (``dims.kin = K``) takes the same call: batch 0 is materialised through the windowed apply
+        (``FusedStaticGen.make_batch`` picks it by the size of ``eng.x``) and every later batch is read by the optimizer launch
+        through the window behind the cyclic prefix -- ``eng.x``, with ``keep_x``, then holds the windowed [batch, S, K, 2]
+        batch.  Bit-identical to the pipelined loop on the full batches cropped (tests/test_gpu_rx_window_loop.py)."""
         if not self.train:
             raise _lib.DccnError("engine built with train=False")
         if self._ride:

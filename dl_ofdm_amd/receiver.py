@@ -332,10 +332,11 @@ def train(FLAGS: Flags, device="cuda", verbose: bool = True, run_test: bool = Tr
                 # ... and the generator runs on its own stream (datagen.SideStreamFeeder): batch i+1 is produced while the forward
                 # and backward launches of step i run; the step's last launch waits for it
                 from .datagen import FusedStaticGen, SideStreamFeeder
-                if FLAGS.cp and FusedStaticGen.supported(gen, eng) and not getattr(FLAGS, "no_fused_generator", False):
+                if FusedStaticGen.supported(gen, eng) and not getattr(FLAGS, "no_fused_generator", False):
                     # round 5: single-profile channels, static or mobile -- ONE C call per batch: the fused generator launch of the next batch
                     # + the four step launches, whose pipelined normalisation reads (y, noise, power partials) as its virtual
                     # input (include/dccn.h dccn_gen_static; datagen.FusedStaticGen).  Same batches as the loop below.
+                    # (cp=False receivers too: that normalisation then reads the samples behind the cyclic prefix itself)
                     fg = fused.get(batch_size)
                     if fg is None:
                         fg = fused[batch_size] = FusedStaticGen(gen, batch_size, FLAGS.SNR, want_noise_power=True)

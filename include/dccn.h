@@ -352,7 +352,8 @@ int dccn_adam_tf_step(float* param, const float* grad, float* m, float* v,
 typedef struct dccn_rx_shape {
     int batch;     /* frames (Bf) */
     int S;         /* OFDM symbols per frame (7) */
-    int kin;       /* samples per symbol seen by the C-Conv (N+CP, or N when cp=False) */
+    int kin;       /* samples per symbol seen by the C-Conv (N+CP, or N when cp=False: the caller crops the cyclic prefix, or
+                      hands the step a gen_next descriptor, which then reads the N samples behind the prefix itself) */
     int F;         /* nfilter */
     int D;         /* data cells per frame (frame_size) */
     int nbits;     /* 1..4 */
@@ -425,8 +426,15 @@ typedef struct dccn_gen_profile {
 int dccn_gen_static_supported(int S, int K, int CP);
 int dccn_gen_static_partials(int frames);
 int dccn_gen_static_frames(const dccn_gen_static* g, dccn_stream_t stream);
-/* x_out [frames, S, K+CP, 2] = y / sqrt(mean |y|^2) + noise; noise_power (nullable) = mean |noise|^2 */
+/* x_out [frames, S, K+CP, 2] = y / sqrt(mean |y|^2) + noise; noise_power (nullable) = mean |noise|^2.  Writes exactly
+ * frames * S * (K+CP) * 2 floats: a cp=False receiver's [frames, S, K, 2] buffer takes dccn_gen_static_apply_window. */
 int dccn_gen_static_apply(const dccn_gen_static* g, float* x_out, float* noise_power, dccn_stream_t stream);
+/* The same batch as a cp=False receiver sees it (dev/py/model.py:1236-1240 slices the cyclic prefix off inside the graph):
+ * x_out [frames, S, K, 2], x_out[f, s, 0:K] = y[f, s, CP:CP+K] / sqrt(mean |y|^2) + noise[f, s, CP:CP+K].  The mean is still
+ * taken over the WHOLE frames, prefix included, so the result is dccn_gen_static_apply's output cropped, bit for bit; noise_power
+ * is the same value too.  Refused like dccn_gen_static_apply (DCCN_ERR_INVALID_ARG); inside a chain group DCCN_ERR_UNSUPPORTED
+ * (the launch carries no chain table). */
+int dccn_gen_static_apply_window(const dccn_gen_static* g, float* x_out, float* noise_power, dccn_stream_t stream);
 
 typedef struct dccn_rx_buffers {
     const float* x;            /* [batch, S, kin, 2] raw input (tx_ofdm) */
@@ -483,7 +491,11 @@ typedef struct dccn_rx_buffers {
        x_next = y / sqrt(mean |y|^2) + noise (bit-identical to normalising the materialised batch).  x_next, when non-null as
        well, receives that batch (tx_ofdm); the labels go to gen_next->bits_out (the caller's OTHER label slot).  Training
        calls on the single-buffer pipelining only (dccn_rx_norm_rides_backward(shape) == 0); one C call per generated-and-
-       trained batch. */
+       trained batch.
+       shape.kin == K + CP: the step reads the generator's whole symbols.  shape.kin == K (a cp=False receiver): its last launch
+       reads the K samples behind the cyclic prefix of every symbol -- the batch power still that of the whole frames -- which is
+       bit-identical to normalising dccn_gen_static_apply_window's output; x_next, when given, is [batch, S, kin, 2] either way.
+       Any other kin is refused (DCCN_ERR_INVALID_ARG) before anything is launched. */
     const dccn_gen_static* gen_next;
     /* nullable: the plan's OWN tuning table (dccn_tuning_count() ints, captured with dccn_tuning_snapshot when the plan was
        built): the call plans its launches from it instead of the process-global knobs, so dccn_set_tuning on another thread
