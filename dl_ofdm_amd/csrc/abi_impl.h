@@ -45,7 +45,14 @@ struct Carver {
     }
     bool ok() const { return off <= cap && (base != nullptr || off == 0); }
 };
-static size_t carve_size(size_t off, size_t bytes) { return align_up(off, 256) + bytes; }
+// Each workspace layout is described once, by a carve function that takes its pieces from a Carver; the layout's size is that
+// function run on a null base.
+template <typename Fn>
+static size_t carved_bytes(Fn&& carve) {
+    Carver c(nullptr, 0);
+    carve(c);
+    return align_up(c.off, 256);
+}
 
 // Kernel-configuration knobs (dccn_set_tuning): which tile configuration the GEMM-shaped operators launch.
 // 0 = the 32x32x2 family of gemm_f32_mfma.h, > 0 = a gemm16.h configuration (see the *_impl functions).
@@ -161,6 +168,12 @@ struct PowerPartials {      // where normalise left the R8 partial sums (finishe
     double denom;
 };
 
+// split-K slabs of an [Mo, No] weight gradient and their column sums: `splits` slabs, `slab` = Mo * No floats apart
+struct SlabWs {
+    float* slabs; float* colsum;
+    int splits; long long slab;
+};
+
 struct DeferredSlabs {
     const float* dw_slabs;
     const float* db_slabs;
@@ -211,6 +224,7 @@ int norm_impl(const float* x, float* y, float* mean, float* var, bool want_power
 void norm_power_partials(int batch, int cols, void* ws, size_t ws_bytes, const float* x, const float* y, PowerPartials* pp, int slot = 0);
 size_t norm_ws_bytes(int batch, int cols);
 RxLayout rx_layout(const dccn_rx_shape* sh);
+bool slab_carve(Carver& c, int splits, int Mo, int No, SlabWs* w);
 size_t splitk_ws_bytes(int Mo, int No, int Kr);
 int tail_impl(bool bwd, const float* z, const int32_t* bits, const float* tailp, float* prob, dccn_metrics* metrics, float* dz, float* dtailp, long long cells, int nbits, const PowerPartials* pp, float* power_out, void* ws, size_t ws_bytes, hipStream_t s, TailFinalizeArgs* defer = nullptr);
 size_t tail_ws_bytes(long long cells, int nbits);

@@ -21,16 +21,19 @@ static int norm_grid_x(int cols) { return ceil_div(ceil_div(cols, 4), 64); }
 static int norm_grid_y(int batch) { return ceil_div(batch, kNormRowsPerBlock); }
 
 int norm_fused_blocks(int cols) { return ceil_div(ceil_div(cols, 4 * kNormFusedCG), 8) * 8; }
-static size_t norm_power_slots(int batch, int cols) {
-    const size_t a = (size_t)norm_grid_x(cols) * norm_grid_y(batch), b = (size_t)norm_fused_blocks(cols);
-    return a > b ? a : b;
+// moments: per-chunk column sums of the two-pass form; power: R8 partial sums, two buffers (dccn_rx_buffers.norm_slot) of
+// `slots` each, the larger of the two forms' block counts
+struct NormWs {
+    double *moments, *power;
+    size_t slots;
+    double* power_slot(int slot) const { return power + (slot ? slots : 0); }
+};
+static NormWs norm_carve(Carver& c, int batch, int cols) {
+    const size_t a = (size_t)norm_grid_x(cols) * norm_grid_y(batch), b = (size_t)norm_fused_blocks(cols), slots = a > b ? a : b;
+    double* moments = c.take<double>((size_t)kNormRowChunks * cols * 2);
+    return NormWs{moments, c.take<double>(2 * slots), slots};
 }
-size_t norm_ws_bytes(int batch, int cols) {
-    size_t o = 0;
-    o = carve_size(o, (size_t)kNormRowChunks * cols * 2 * sizeof(double));
-    o = carve_size(o, 2 * norm_power_slots(batch, cols) * sizeof(double));      // two slots: dccn_rx_buffers.norm_slot
-    return align_up(o, 256);
-}
+size_t norm_ws_bytes(int batch, int cols) { return carved_bytes([&](Carver& c) { norm_carve(c, batch, cols); }); }
 
 bool norm_fused_ok(const float* x, const float* y, int batch, int cols) {
     return (cols % 4 == 0) && batch <= 128 * kNormFusedRPT && aligned16(x) && aligned16(y);
@@ -42,8 +45,7 @@ bool norm_fused_ok(const float* x, const float* y, int batch, int cols) {
 void norm_power_partials(int batch, int cols, void* ws, size_t ws_bytes, const float* x, const float* y,
                                 PowerPartials* pp, int slot) {
     Carver c(ws, ws_bytes);
-    c.take<double>((size_t)kNormRowChunks * cols * 2);
-    pp->partial = c.take<double>(2 * norm_power_slots(batch, cols)) + (slot ? norm_power_slots(batch, cols) : 0);
+    pp->partial = norm_carve(c, batch, cols).power_slot(slot);
     pp->n = norm_fused_ok(x, y, batch, cols) ? norm_fused_blocks(cols) : norm_grid_x(cols) * norm_grid_y(batch);
     pp->denom = (double)batch * (double)(cols / 2);
 }
@@ -54,9 +56,9 @@ int norm_impl(const float* x, float* y, float* mean, float* var, bool want_power
     if (!x || !y || batch <= 0 || cols <= 0 || (want_power && (cols & 1))) return DCCN_ERR_INVALID_ARG;
     if (ws_bytes < norm_ws_bytes(batch, cols) || !ws) return DCCN_ERR_WORKSPACE;
     Carver c(ws, ws_bytes);
-    double* partial = c.take<double>((size_t)kNormRowChunks * cols * 2);
+    const NormWs w = norm_carve(c, batch, cols);
+    double *partial = w.moments, *pw = w.power_slot(slot);
     const int gx = norm_grid_x(cols), gy = norm_grid_y(batch);
-    double* pw = c.take<double>(2 * norm_power_slots(batch, cols)) + (slot ? norm_power_slots(batch, cols) : 0);
     if (norm_fused_ok(x, y, batch, cols)) {
         // the whole batch of a column strip fits in one block's registers: single pass, single launch
         const int blocks = norm_fused_blocks(cols);
@@ -182,15 +184,29 @@ static int max_splits16(int Mo, int No) {
     long long m = (1024 + tiles - 1) / tiles;
     return (int)(m < 1 ? 1 : (m > 8 ? 8 : m));
 }
-size_t splitk_ws_bytes(int Mo, int No, int Kr) {
-    const SplitPlan sp = plan_splitk(Mo, No, Kr);
-    const int ms = max_splits16(Mo, No);
-    const int n = sp.splits > ms ? sp.splits : ms;
-    size_t o = 0;
-    o = carve_size(o, (size_t)n * Mo * No * sizeof(float));
-    o = carve_size(o, (size_t)n * No * sizeof(float));
-    return align_up(o, 256);
+// The slab workspaces are sized for a capacity and carved for the count a launch planned: false when that count does not fit
+// the caller's bytes (every site returns DCCN_ERR_WORKSPACE then, before its first launch)
+bool slab_carve(Carver& c, int splits, int Mo, int No, SlabWs* w) {
+    w->splits = splits;
+    w->slab = (long long)Mo * No;
+    w->slabs = c.take<float>((size_t)splits * Mo * No);
+    w->colsum = c.take<float>((size_t)splits * No);
+    return c.ok();
 }
+static int splitk_capacity(int Mo, int No, int Kr) {
+    const int planned = plan_splitk(Mo, No, Kr).splits, ms = max_splits16(Mo, No);
+    return planned > ms ? planned : ms;
+}
+size_t splitk_ws_bytes(int Mo, int No, int Kr) {
+    SlabWs w;
+    return carved_bytes([&](Carver& c) { slab_carve(c, splitk_capacity(Mo, No, Kr), Mo, No, &w); });
+}
+// what a weight-gradient launch leaves for the launch that sums its slabs.  live = false: it wrote the gradient itself (a single
+// k range outside the fused backward launch, whose dW items always write slabs)
+static DeferredSlabs deferred_slabs(const SlabWs& w, bool bias, bool live) {
+    return live ? DeferredSlabs{w.slabs, bias ? w.colsum : nullptr, w.splits} : DeferredSlabs{nullptr, nullptr, 1};
+}
+static FoldDefer fold_defer(const SlabWs& w) { return FoldDefer{w.slabs, w.colsum, w.splits, w.slab}; }
 
 // split plan of the dense weight gradient dw[K,N] = x[M,K]^T . dy[M,N] (one rule for the stand-alone operator and the
 // grouped launch: the composed and the fused step must sum in the same order)
@@ -244,38 +260,36 @@ int dense_bwd_w_impl(const float* x, const float* dy, float* dw, float* dbias, i
     if (!ws || ws_bytes < splitk_ws_bytes(K, N, M)) return DCCN_ERR_WORKSPACE;
     const SplitPlan sp = dense_dw_plan(M, K, N);
     Carver c(ws, ws_bytes);
-    float* slabs = c.take<float>((size_t)sp.splits * K * N);
-    float* cs = c.take<float>((size_t)sp.splits * N);
+    SlabWs sw;
+    if (!slab_carve(c, sp.splits, K, N, &sw)) return DCCN_ERR_WORKSPACE;
     GemmParams p = gp_zero();                 // dw[K,N] = x[M,K]^T . dy[M,N]
     p.A = x; p.B = dy;
     p.M = K; p.N = N; p.K = M;
     p.lda = ldx > 0 ? ldx : K; p.ldb = N; p.ldc = N;
     p.klen = sp.klen;
-    p.slab = (long long)K * N;
+    p.slab = sw.slab;
     p.vecA = (K % 4 == 0) && (p.lda % 4 == 0) && aligned16(x) && small_enough(M, p.lda);
     p.vecB = (N % 4 == 0) && aligned16(dy) && small_enough(M, N);
-    if (defer) { defer->dw_slabs = nullptr; defer->db_slabs = nullptr; defer->splits = 1; }
+    if (defer) *defer = deferred_slabs(sw, false, false);
     if (sp.splits == 1) {
         p.C = dw;
         p.colsum = dbias;
         return launch_gemm<OP_ICONTIG, OP_ICONTIG, 1, TAG_DENSE_BWD_W>(p, 1, s);
     }
-    p.C = slabs;
-    p.colsum = dbias ? cs : nullptr;
+    p.C = sw.slabs;
+    p.colsum = dbias ? sw.colsum : nullptr;
     const long long big = (long long)ceil_div(p.M, 128) * ceil_div(p.N, 128) * sp.splits;
     if (g_tune[TUNE_DENSE_BWD] == kVariantKmajor && kmajor_ok(p) && big < 2 * kCUs)
         DCCN_TRY((launch_kmajor<1, TAG_DENSE_BWD_W>(p, sp.splits, s)));
     else
         DCCN_TRY((launch_gemm<OP_ICONTIG, OP_ICONTIG, 1, TAG_DENSE_BWD_W>(p, sp.splits, s)));
     if (defer) {
-        defer->dw_slabs = slabs;
-        defer->db_slabs = dbias ? cs : nullptr;
-        defer->splits = sp.splits;
+        *defer = deferred_slabs(sw, dbias != nullptr, true);
         return DCCN_OK;
     }
     const long long n = (long long)K * N;
-    if (dbias) DCCN_TRY(launch_splitk_reduce2(slabs, sp.splits, n, dw, n, cs, (long long)N, dbias, (long long)N, s));
-    else DCCN_TRY(launch_splitk_reduce(slabs, sp.splits, n, dw, n, s));
+    if (dbias) DCCN_TRY(launch_splitk_reduce2(sw.slabs, sp.splits, n, dw, n, sw.colsum, (long long)N, dbias, (long long)N, s));
+    else DCCN_TRY(launch_splitk_reduce(sw.slabs, sp.splits, n, dw, n, s));
     return DCCN_OK;
 }
 
@@ -339,7 +353,7 @@ int dense_bwd_grouped_impl(const float* x, const float* dy, const float* w, floa
         } else
         DCCN_TRY(few ? launch_dense_bwd_fewrow<1>(px, pw, s)
                      : (launch_dense_bwd16<1, 4, 1, 1, 64, 2, 2, 2, 2>(px, pw, 1, s, tune_smem_min())));
-        defer->dw_slabs = nullptr; defer->db_slabs = nullptr; defer->splits = 1;
+        *defer = deferred_slabs(SlabWs{}, false, false);
         return DCCN_OK;
     }
     const int variant = g_tune[TUNE_DENSE_BWD] == kVariantKmajor ? 0 : g_tune[TUNE_DENSE_BWD];
@@ -354,33 +368,29 @@ int dense_bwd_grouped_impl(const float* x, const float* dy, const float* w, floa
         if (want > cap) want = cap;
         const SplitPlan sp = plan_splitk_n(M, want, dense_bwd16_bk(variant));
         Carver c(ws, ws_bytes);
-        float* slabs = c.take<float>((size_t)sp.splits * K * N);
-        float* cs = c.take<float>((size_t)sp.splits * N);
+        SlabWs sw;
+        if (!slab_carve(c, sp.splits, K, N, &sw)) return DCCN_ERR_WORKSPACE;
         pw.klen = sp.klen;
         if (sp.splits == 1) {
             pw.C = dw; pw.colsum = dbias;
         } else {
-            pw.C = slabs; pw.colsum = dbias ? cs : nullptr;
+            pw.C = sw.slabs; pw.colsum = dbias ? sw.colsum : nullptr;
         }
         DCCN_TRY(dense_bwd16_launch(variant, px, pw, sp.splits, s));
-        defer->dw_slabs = sp.splits > 1 ? slabs : nullptr;
-        defer->db_slabs = (sp.splits > 1 && dbias) ? cs : nullptr;
-        defer->splits = sp.splits;
+        *defer = deferred_slabs(sw, dbias != nullptr, sp.splits > 1);
         return DCCN_OK;
     }
     const SplitPlan sp = dense_dw_plan(M, K, N);
     Carver c(ws, ws_bytes);
-    float* slabs = c.take<float>((size_t)sp.splits * K * N);
-    float* cs = c.take<float>((size_t)sp.splits * N);
-    pw.C = slabs; pw.colsum = dbias ? cs : nullptr;
+    SlabWs sw;
+    if (!slab_carve(c, sp.splits, K, N, &sw)) return DCCN_ERR_WORKSPACE;
+    pw.C = sw.slabs; pw.colsum = dbias ? sw.colsum : nullptr;
     pw.klen = sp.klen;
     if (vec && g_tune[TUNE_DENSE_BWD_BIG] && grouped_big_ok(px, pw, sp.splits)) {
         pw.ldc = N;
         if (sp.splits == 1) { pw.C = dw; pw.colsum = dbias; pw.slab = 0; }
         DCCN_TRY((launch_dense_bwd_grouped<true, 128, 128, 32>(px, pw, sp.splits, s)));
-        defer->dw_slabs = sp.splits > 1 ? slabs : nullptr;
-        defer->db_slabs = (sp.splits > 1 && dbias) ? cs : nullptr;
-        defer->splits = sp.splits;
+        *defer = deferred_slabs(sw, dbias != nullptr, sp.splits > 1);
         return DCCN_OK;
     }
     if (sp.splits < 2 || !vec || !grouped_ok(px, pw, sp.splits)) {
@@ -406,9 +416,7 @@ int dense_bwd_grouped_impl(const float* x, const float* dy, const float* w, floa
             DCCN_TRY(launch_dense_bwd_grouped_km<64>(px, pw, sp.splits, s));
         }
     } else DCCN_TRY(launch_dense_bwd_grouped<true>(px, pw, sp.splits, s));
-    defer->dw_slabs = slabs;
-    defer->db_slabs = dbias ? cs : nullptr;
-    defer->splits = sp.splits;
+    *defer = deferred_slabs(sw, dbias != nullptr, true);
     return DCCN_OK;
 }
 
@@ -509,15 +517,14 @@ static void cconv_bw16_tiles(int variant, int& tm, int& tn) {
     if (variant == 3) { tm = 80; tn = 128; }
     if (variant == 4) { tm = 32; tn = 128; }
 }
-// workspace of the C-Conv weight gradient: the legacy split plan or up to kCconvBwMaxSplits slabs of a small output
+// slab capacity of the C-Conv weight gradient: the legacy split plan, and at least kCconvBwMaxSplits slabs of a small output
+static int cconv_bw_capacity(int rows, int kin, int F) {
+    const int legacy = splitk_capacity(2 * kin, 2 * F, rows);
+    return (4LL * kin * F > 512 * 512 || legacy > kCconvBwMaxSplits) ? legacy : kCconvBwMaxSplits;
+}
 size_t cconv_bw_ws_bytes(int rows, int kin, int F) {
-    const size_t legacy = splitk_ws_bytes(2 * kin, 2 * F, rows);
-    if (4LL * kin * F > 512 * 512) return legacy;
-    size_t o = 0;
-    o = carve_size(o, (size_t)kCconvBwMaxSplits * 4 * kin * F * sizeof(float));
-    o = carve_size(o, (size_t)kCconvBwMaxSplits * 2 * F * sizeof(float));
-    o = align_up(o, 256);
-    return o > legacy ? o : legacy;
+    SlabWs w;
+    return carved_bytes([&](Carver& c) { slab_carve(c, cconv_bw_capacity(rows, kin, F), 2 * kin, 2 * F, &w); });
 }
 
 
@@ -544,14 +551,15 @@ int cconv_bwd_w_impl(const float* x, const float* dout, float* dw, float* dbias,
         sp = plan_splitk_n(rows, want, 32);
     }
     Carver c(ws, ws_bytes);
-    float* slabs = c.take<float>((size_t)sp.splits * 4 * kin * F);
-    float* cs = c.take<float>((size_t)sp.splits * 2 * F);
+    SlabWs sw;
+    if (!slab_carve(c, sp.splits, 2 * kin, 2 * F, &sw)) return DCCN_ERR_WORKSPACE;
+    float *slabs = sw.slabs, *cs = sw.colsum;
     GemmParams p = gp_zero();                 // dWeff[2kin,2F] = x[rows,2kin]^T . dout[rows,2F]
     p.A = x; p.B = dout; p.C = slabs; p.colsum = cs;
     p.M = 2 * kin; p.N = 2 * F; p.K = rows;
     p.lda = 2 * kin; p.ldb = 2 * F; p.ldc = 2 * F;
     p.klen = sp.klen;
-    p.slab = (long long)4 * kin * F;
+    p.slab = sw.slab;
     p.vecA = (kin % 2 == 0) && aligned16(x) && small_enough(rows, 2LL * kin);
     p.vecB = (F % 2 == 0) && aligned16(dout) && small_enough(rows, 2LL * F);
     if (v16) {
@@ -562,7 +570,7 @@ int cconv_bwd_w_impl(const float* x, const float* dout, float* dw, float* dbias,
             case 4: DCCN_TRY((launch_bwd_w16_finalize<2, 2, 1, 4, 32>(p, sp.splits, *fin, s))); break;     // 32x128
             default: return DCCN_ERR_INVALID_ARG;
         }
-        defer->slabs = slabs; defer->colsum = cs; defer->splits = sp.splits; defer->slab = p.slab;
+        *defer = fold_defer(sw);
         return DCCN_OK;
     }
     if (defer && fin && p.vecA && p.vecB && (F % 2 == 0)) {
@@ -589,7 +597,7 @@ int cconv_bwd_w_impl(const float* x, const float* dout, float* dw, float* dbias,
             hipLaunchKernelGGL(kern, grid, dim3(kGemmThreads), smem, s, p, tiles, gemm_blocks, *fin);
         }
         DCCN_LAUNCH_CHECK();
-        defer->slabs = slabs; defer->colsum = cs; defer->splits = sp.splits; defer->slab = p.slab;
+        *defer = fold_defer(sw);
         return DCCN_OK;
     }
     if (defer) defer->slabs = nullptr;
@@ -598,7 +606,7 @@ int cconv_bwd_w_impl(const float* x, const float* dout, float* dw, float* dbias,
     else
         DCCN_TRY((launch_gemm<OP_ICONTIG, OP_ICONTIG, 1, TAG_CCONV_BWD_W>(p, sp.splits, s)));
     if (defer && !fin) {                     // the caller's optimizer launch folds the slabs (eq_opt.h)
-        defer->slabs = slabs; defer->colsum = cs; defer->splits = sp.splits; defer->slab = p.slab;
+        *defer = fold_defer(sw);
         return DCCN_OK;
     }
     const int nthreads = kin * F + F;
@@ -659,12 +667,14 @@ int cconv_bwd_grouped_impl(const float* x, const float* dout, const float* w, fl
     if (!x || !dout || !w || !dx || !defer || rows <= 0 || groups < 1 || groups > 2) return DCCN_ERR_INVALID_ARG;
     if (!ws || ws_bytes < cconv_bwd_grouped_ws_bytes(rows, kin, F, groups)) return DCCN_ERR_WORKSPACE;
     SplitPlan sp = plan_splitk(2 * kin, 2 * F, rows);
-    // (one output tile and > 16 384 rows would plan more slabs than the workspace holds: clamp like cconv_bwd_w_impl does)
+    // (one output tile and > 16 384 rows: at most kCconvBwMaxSplits k ranges)
     if (sp.splits > kCconvBwMaxSplits) sp = plan_splitk_n(rows, kCconvBwMaxSplits, 64);
     if (sp.splits > kCconvBwMaxSplits) return DCCN_ERR_STATE;
-    const size_t per = cconv_bw_ws_bytes(rows, kin, F) / sizeof(float);
-    float* slabs = static_cast<float*>(ws);
-    float* cs = slabs + (size_t)sp.splits * 4 * kin * F;
+    // group 0's share of the workspace; group g's lies `per` floats further
+    const size_t per_bytes = cconv_bw_ws_bytes(rows, kin, F), per = per_bytes / sizeof(float);
+    Carver c(ws, per_bytes);
+    SlabWs sw;
+    if (!slab_carve(c, sp.splits, 2 * kin, 2 * F, &sw)) return DCCN_ERR_WORKSPACE;
     GemmParams px = gp_zero();                // dx[rows,2kin] = dout[rows,2F] . Weff^T
     px.A = dout; px.B = w; px.C = dx;
     px.M = rows; px.N = 2 * kin; px.K = 2 * F;
@@ -675,19 +685,19 @@ int cconv_bwd_grouped_impl(const float* x, const float* dout, const float* w, fl
     GroupStride g1;
     g1.a = gd; g1.b = gw; g1.c = gx; g1.bias = 0; g1.colsum = 0;
     GemmParams pw = gp_zero();                // dWeff[2kin,2F] = x[rows,2kin]^T . dout[rows,2F]
-    pw.A = x; pw.B = dout; pw.C = slabs; pw.colsum = cs;
+    pw.A = x; pw.B = dout; pw.C = sw.slabs; pw.colsum = sw.colsum;
     pw.M = 2 * kin; pw.N = 2 * F; pw.K = rows;
     pw.lda = 2 * kin; pw.ldb = 2 * F; pw.ldc = 2 * F;
     pw.klen = sp.klen;
-    pw.slab = (long long)4 * kin * F;
+    pw.slab = sw.slab;
     pw.vecA = 1; pw.vecB = 1;
     if (!kmajor_ok(pw)) return DCCN_ERR_STATE;
     GroupStride g2;
     g2.a = gx; g2.b = gd; g2.c = (long long)per; g2.bias = 0; g2.colsum = (long long)per;
     DCCN_TRY(launch_cconv_bwd_grouped_km<64>(px, g1, pw, g2, sp.splits, groups, s));
     for (int g = 0; g < groups; ++g) {
-        defer[g].slabs = slabs + (size_t)g * per; defer[g].colsum = cs + (size_t)g * per;
-        defer[g].splits = sp.splits; defer[g].slab = pw.slab;
+        defer[g] = fold_defer(sw);
+        defer[g].slabs += (size_t)g * per; defer[g].colsum += (size_t)g * per;
     }
     return DCCN_OK;
 }
@@ -696,12 +706,14 @@ int cconv_bwd_grouped_impl(const float* x, const float* dout, const float* w, fl
 // backward of the basic receiver's training step in one launch (rx_bwd.h)
 // ---------------------------------------------------------------------------------------
 static int rx_bwd_fused_tiles(int batch, int S, int F) { return ceil_div(batch, 64) * ceil_div(S * 2 * F, 64); }
-static size_t rx_bwd_fused_ws_bytes(int batch, int S, int kin, int F) {
+struct RxBwdWs { float *partial, *colsum; };     // dWeff partials, folded per dX tile: [kin][32][{a, b}] (rx_bwd.h); column sums
+static RxBwdWs rx_bwd_fused_carve(Carver& c, int batch, int S, int kin, int F) {
     const size_t tiles = (size_t)rx_bwd_fused_tiles(batch, S, F);
-    size_t o = 0;
-    o = carve_size(o, tiles * kin * 64 * sizeof(float));        // folded per tile: [kin][32][{a, b}] (rx_bwd.h)
-    o = carve_size(o, tiles * 64 * sizeof(float));
-    return align_up(o, 256);
+    float* partial = c.take<float>(tiles * kin * 64);
+    return RxBwdWs{partial, c.take<float>(tiles * 64)};
+}
+static size_t rx_bwd_fused_ws_bytes(int batch, int S, int kin, int F) {
+    return carved_bytes([&](Carver& c) { rx_bwd_fused_carve(c, batch, S, kin, F); });
 }
 // applicable: 64x64 dX tiles that lie inside one symbol's 2F columns, 2kin = 128 or 160 (N = 64 without / with the
 // cyclic prefix), the grouped k-major plan for the dense gradients, vector-legal operands
@@ -740,24 +752,21 @@ static int rx_bwd_fused_impl(const float* x_norm, const float* fft_out, const fl
         const int n = graded_ranges(g_tune[TUNE_DW_GRADED], batch, pw.koff);
         if (n > 1 && n <= max_splits16(dK, dN)) { pw.nranges = n; nsplit = n; }
     }
-    Carver c(ws_dense, ws_dense_bytes);                   // (sized for max_splits16 slabs: splitk_ws_bytes)
-    float* slabs = c.take<float>((size_t)nsplit * dK * dN);
-    float* cs = c.take<float>((size_t)nsplit * dN);
-    if (!c.ok()) return DCCN_ERR_WORKSPACE;
-    pw.C = slabs; pw.colsum = dbias_dense ? cs : nullptr;
+    Carver c(ws_dense, ws_dense_bytes);
+    SlabWs sw;
+    if (!slab_carve(c, nsplit, dK, dN, &sw)) return DCCN_ERR_WORKSPACE;
+    pw.C = sw.slabs; pw.colsum = dbias_dense ? sw.colsum : nullptr;
     if (!kmajor_ok(pw)) return DCCN_ERR_INVALID_ARG;
-    const int tiles = rx_bwd_fused_tiles(batch, S, F);
     Carver cc(ws_conv, ws_conv_bytes);
+    const RxBwdWs cw = rx_bwd_fused_carve(cc, batch, S, kin, F);
     DweffArgs de;
-    de.xn = x_norm;
-    de.partial = cc.take<float>((size_t)tiles * kin * 64);
-    de.colsum = cc.take<float>((size_t)tiles * 64);
+    de.xn = x_norm; de.partial = cw.partial; de.colsum = cw.colsum;
     de.batch = batch; de.ldx = S * 2 * kin; de.two_kin = 2 * kin; de.two_F = 2 * F;
     de.prio = g_tune[TUNE_BWD_PRIO];
     if (2 * kin == 160) DCCN_TRY(launch_rx_bwd_fused<5>(px, pw, de, nsplit, nr, fin, hp, s));
     else DCCN_TRY(launch_rx_bwd_fused<4>(px, pw, de, nsplit, nr, fin, hp, s));
-    ds->dw_slabs = slabs; ds->db_slabs = dbias_dense ? cs : nullptr; ds->splits = nsplit;
-    fd->slabs = de.partial; fd->colsum = de.colsum;
+    *ds = deferred_slabs(sw, dbias_dense != nullptr, true);
+    fd->slabs = cw.partial; fd->colsum = cw.colsum;
     fd->splits = ceil_div(batch, 64) * S;                       // terms per element: (row tile, symbol)
     fd->slab = (long long)((2 * F) / 64) * kin * 64;            // distance between consecutive terms (tiles folded: [kin][32][2])
     *fold_tilew = 64;
@@ -775,12 +784,36 @@ static int tail_blocks(long long cells, bool quad4 = false) {
     if (b < 1) b = 1;
     return (int)b;
 }
+// per-block metrics and tail-gradient slabs of `nblocks` blocks (the tail's own launch, or the tiles of the fused dense + tail)
+struct TailWs { TailBlockMetrics* blk_metrics; float* blk_grads; };
+static TailWs tail_carve(Carver& c, size_t nblocks, int nbits) {
+    TailBlockMetrics* bm = c.take<TailBlockMetrics>(nblocks);
+    return TailWs{bm, c.take<float>(nblocks * tail_param_count(nbits))};
+}
 size_t tail_ws_bytes(long long cells, int nbits) {
-    size_t o = 0;
-    o = carve_size(o, (size_t)kTailBlocksMax * sizeof(TailBlockMetrics));
-    o = carve_size(o, (size_t)kTailBlocksMax * tail_param_count(nbits) * sizeof(float));
     (void)cells;
-    return align_up(o, 256);
+    return carved_bytes([&](Carver& c) { tail_carve(c, kTailBlocksMax, nbits); });
+}
+// the slab reduction's arguments for the `nblocks` blocks a tail launch ran.  pp / power_out: optional R8 finish riding on it
+static TailFinalizeArgs tail_finalize_args(const TailWs& w, int nblocks, bool bwd, int nbits, long long cells, dccn_metrics* metrics,
+                                           float* dtailp, const PowerPartials* pp, float* power_out) {
+    const bool pw = pp != nullptr && power_out != nullptr;
+    TailFinalizeArgs fa{};          // (no optimizer bookkeeping, hand-off words or monitors: the fused steps add theirs)
+    fa.blk_metrics = w.blk_metrics; fa.blk_grads = bwd ? w.blk_grads : nullptr; fa.nblocks = nblocks;
+    fa.P = bwd ? tail_param_count(nbits) : 0; fa.count = cells * nbits;
+    fa.metrics = metrics; fa.dtailp = bwd ? dtailp : nullptr; fa.power_partial = pw ? pp->partial : nullptr;
+    fa.n_power = pw ? pp->n : 0; fa.power_denom = pw ? pp->denom : 1.0; fa.power_out = pw ? power_out : nullptr;
+    return fa;
+}
+// defer != nullptr: do not launch the slab reduction; hand its arguments to the caller (fused steps)
+static int tail_finish(const TailFinalizeArgs& fa, TailFinalizeArgs* defer, hipStream_t s) {
+    if (defer) {
+        *defer = fa;
+        return DCCN_OK;
+    }
+    hipLaunchKernelGGL(demod_tail_finalize_kernel, dim3(tail_finalize_blocks(fa.P)), dim3(256), 0, s, fa);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
 }
 
 template <int NB>
@@ -796,8 +829,7 @@ static int tail_launch(bool bwd, const float* z, const int32_t* bits, const floa
     return DCCN_OK;
 }
 
-// pp/power_out: optional R8 finish riding on the slab-reduction kernel (fused receiver step)
-// defer != nullptr: do not launch the slab reduction; hand its arguments to the caller (fused receiver step)
+// pp / power_out, defer: as tail_finalize_args / tail_finish
 int tail_impl(bool bwd, const float* z, const int32_t* bits, const float* tailp, float* prob,
                      dccn_metrics* metrics, float* dz, float* dtailp, long long cells, int nbits,
                      const PowerPartials* pp, float* power_out, void* ws, size_t ws_bytes, hipStream_t s,
@@ -806,8 +838,8 @@ int tail_impl(bool bwd, const float* z, const int32_t* bits, const float* tailp,
     if (bwd && (!dz || !dtailp)) return DCCN_ERR_INVALID_ARG;
     if (!ws || ws_bytes < tail_ws_bytes(cells, nbits)) return DCCN_ERR_WORKSPACE;
     Carver c(ws, ws_bytes);
-    TailBlockMetrics* bm = c.take<TailBlockMetrics>(kTailBlocksMax);
-    float* bg = c.take<float>((size_t)kTailBlocksMax * tail_param_count(nbits));
+    const TailWs tw = tail_carve(c, kTailBlocksMax, nbits);
+    TailBlockMetrics* bm = tw.blk_metrics; float* bg = tw.blk_grads;
     const int nblk = tail_blocks(cells, bwd && nbits == 4);
     int st = DCCN_ERR_INVALID_ARG;
     switch (nbits) {
@@ -830,21 +862,8 @@ int tail_impl(bool bwd, const float* z, const int32_t* bits, const float* tailp,
             break;
     }
     DCCN_TRY(st);
-    const int P = bwd ? tail_param_count(nbits) : 0;
-    const bool pw = pp != nullptr && power_out != nullptr;
-    TailFinalizeArgs fa;
-    fa.blk_metrics = bm; fa.blk_grads = bwd ? bg : nullptr; fa.nblocks = nblk; fa.P = P; fa.count = cells * nbits;
-    fa.metrics = metrics; fa.dtailp = bwd ? dtailp : nullptr; fa.power_partial = pw ? pp->partial : nullptr;
-    fa.n_power = pw ? pp->n : 0; fa.power_denom = pw ? pp->denom : 1.0; fa.power_out = pw ? power_out : nullptr;
-    fa.adam = nullptr; memset(&fa.hp, 0, sizeof(fa.hp)); fa.zero_word = nullptr; fa.zero_flags = nullptr; fa.n_zero_flags = 0; fa.zero_stride = 0; fa.mon_acc = nullptr; fa.mon_noise = nullptr;
-    if (defer) {
-        *defer = fa;
-        return DCCN_OK;
-    }
-    DCCN_NO_CHAINS();
-    hipLaunchKernelGGL(demod_tail_finalize_kernel, dim3(tail_finalize_blocks(P)), dim3(256), 0, s, fa);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    if (!defer) DCCN_NO_CHAINS();
+    return tail_finish(tail_finalize_args(tw, nblk, bwd, nbits, cells, metrics, dtailp, pp, power_out), defer, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -862,11 +881,7 @@ static int dense_tail_max_blocks(int M, int N) {
     return few > b && few <= kTailBlocksMax ? few : b;
 }
 size_t dense_tail_ws_bytes(int M, int N, int nbits) {
-    const size_t nb = (size_t)dense_tail_max_blocks(M, N);
-    size_t o = 0;
-    o = carve_size(o, nb * sizeof(TailBlockMetrics));
-    o = carve_size(o, nb * tail_param_count(nbits) * sizeof(float));
-    return align_up(o, 256);
+    return carved_bytes([&](Carver& c) { tail_carve(c, (size_t)dense_tail_max_blocks(M, N), nbits); });
 }
 static bool dense_tail_shape_ok(int M, int K, int N, int nbits) {
     // nbits >= 3 (tail weights in LDS; nbits = 4 training in the quad-lane form): knob 13
@@ -886,20 +901,13 @@ bool dense_tail_planned(int nbits, bool train, int M, int N) {
     return (nbits == 4 && train) ? (k & 2) != 0 : (k & 1) != 0;
 }
 
-// the two tile shapes the fused dense + tail launch runs: 48x64 with loads two k-tiles ahead (small layers), 80x64 (large layers)
+// the two tile shapes the fused dense + tail launch runs, at every nbits: 48x64 with loads two k-tiles ahead (small layers),
+// 80x64 (large layers)
 template <int NB, bool BWD>
 static int dense_tail_launch(int variant, const GemmParams& p, const TailEpiParams& tp, hipStream_t s) {
     const size_t sm = tune_smem_min();
     if (variant == 13) return launch_dense_tail16<1, 4, 5, 1, 64, 1, NB, BWD, 2>(p, tp, s, sm);    // 80x64 (large layers)
     return launch_dense_tail16<1, 4, 3, 1, 64, 1, NB, BWD, 2>(p, tp, s, sm);                        // 48x64
-}
-
-// nbits >= 3: the two tile shapes the training / sweep steps use (every other variant number runs 48x64)
-template <int NB, bool BWD>
-static int dense_tail_hi_launch(int variant, const GemmParams& p, const TailEpiParams& tp, hipStream_t s) {
-    const size_t sm = tune_smem_min();
-    if (variant == 13) return launch_dense_tail16<1, 4, 5, 1, 64, 1, NB, BWD, 2>(p, tp, s, sm);      // 80x64 (large layers)
-    return launch_dense_tail16<1, 4, 3, 1, 64, 1, NB, BWD, 2>(p, tp, s, sm);                          // 48x64
 }
 
 // z nullable (not materialised then).  defer: as tail_impl.
@@ -919,8 +927,7 @@ int dense_tail_impl(bool bwd, const float* x, const float* w, const float* bias,
     dense_tail_tiles(variant, bm, bn);
     const int nblk = ceil_div(M, bm) * ceil_div(N, bn);
     Carver c(ws, ws_bytes);
-    TailBlockMetrics* bmx = c.take<TailBlockMetrics>((size_t)dense_tail_max_blocks(M, N));
-    float* bg = c.take<float>((size_t)dense_tail_max_blocks(M, N) * tail_param_count(nbits));
+    const TailWs tw = tail_carve(c, (size_t)dense_tail_max_blocks(M, N), nbits);
     GemmParams p = gp_zero();
     p.A = x; p.B = w; p.C = z; p.bias = bias;
     p.M = M; p.N = N; p.K = K;
@@ -929,7 +936,7 @@ int dense_tail_impl(bool bwd, const float* x, const float* w, const float* bias,
     p.vecA = 1; p.vecB = 1;
     const long long cells = (long long)M * (N / 2);
     TailEpiParams tp;
-    tp.bits = bits; tp.tailp = tailp; tp.prob = prob; tp.dz = dz; tp.blk_metrics = bmx; tp.blk_grads = bg;
+    tp.bits = bits; tp.tailp = tailp; tp.prob = prob; tp.dz = dz; tp.blk_metrics = tw.blk_metrics; tp.blk_grads = tw.blk_grads;
     tp.inv_count = 1.0f / (float)(cells * nbits);
     // few rows, BPSK / QPSK: every operand of a 16x16 tile requested at once, the tail on the tile's own registers (fewrow.h)
     const int few_tiles = ceil_div(M, 16) * (N / 16);
@@ -952,42 +959,16 @@ int dense_tail_impl(bool bwd, const float* x, const float* w, const float* bias,
         else st = bwd ? launch_dense_tail16_ragged<5, 2, 64, 2, true, 2>(p1, t1, p2, t2, s, sm) : launch_dense_tail16_ragged<5, 2, 64, 2, false, 2>(p1, t1, p2, t2, s, sm);
         DCCN_TRY(st);
         const int nrag = (M1 / 80) * ceil_div(N, 64) + ceil_div(N, 64);
-        const int P = bwd ? tail_param_count(nbits) : 0;
-        const bool pw = pp != nullptr && power_out != nullptr;
-        TailFinalizeArgs fa;
-        fa.blk_metrics = bmx; fa.blk_grads = bwd ? bg : nullptr; fa.nblocks = nrag; fa.P = P; fa.count = cells * nbits;
-        fa.metrics = metrics; fa.dtailp = bwd ? dtailp : nullptr; fa.power_partial = pw ? pp->partial : nullptr;
-        fa.n_power = pw ? pp->n : 0; fa.power_denom = pw ? pp->denom : 1.0; fa.power_out = pw ? power_out : nullptr;
-        fa.adam = nullptr; memset(&fa.hp, 0, sizeof(fa.hp)); fa.zero_word = nullptr; fa.zero_flags = nullptr; fa.n_zero_flags = 0; fa.zero_stride = 0; fa.mon_acc = nullptr; fa.mon_noise = nullptr;
-        if (defer) {
-            *defer = fa;
-            return DCCN_OK;
-        }
-        hipLaunchKernelGGL(demod_tail_finalize_kernel, dim3(tail_finalize_blocks(P)), dim3(256), 0, s, fa);
-        DCCN_LAUNCH_CHECK();
-        return DCCN_OK;
+        return tail_finish(tail_finalize_args(tw, nrag, bwd, nbits, cells, metrics, dtailp, pp, power_out), defer, s);
     }
     if (few && nbits == 1) st = bwd ? launch_fewrow_tail<1, true>(p, tp, s) : launch_fewrow_tail<1, false>(p, tp, s);
     else if (few && nbits == 2) st = bwd ? launch_fewrow_tail<2, true>(p, tp, s) : launch_fewrow_tail<2, false>(p, tp, s);
     else if (nbits == 1) st = bwd ? dense_tail_launch<1, true>(variant, p, tp, s) : dense_tail_launch<1, false>(variant, p, tp, s);
     else if (nbits == 2) st = bwd ? dense_tail_launch<2, true>(variant, p, tp, s) : dense_tail_launch<2, false>(variant, p, tp, s);
-    else if (nbits == 3) st = bwd ? dense_tail_hi_launch<3, true>(variant, p, tp, s) : dense_tail_hi_launch<3, false>(variant, p, tp, s);
-    else st = bwd ? dense_tail_hi_launch<4, true>(variant, p, tp, s) : dense_tail_hi_launch<4, false>(variant, p, tp, s);
+    else if (nbits == 3) st = bwd ? dense_tail_launch<3, true>(variant, p, tp, s) : dense_tail_launch<3, false>(variant, p, tp, s);
+    else st = bwd ? dense_tail_launch<4, true>(variant, p, tp, s) : dense_tail_launch<4, false>(variant, p, tp, s);
     DCCN_TRY(st);
-    const int P = bwd ? tail_param_count(nbits) : 0;
-    const bool pw = pp != nullptr && power_out != nullptr;
-    TailFinalizeArgs fa;
-    fa.blk_metrics = bmx; fa.blk_grads = bwd ? bg : nullptr; fa.nblocks = few ? few_tiles : nblk; fa.P = P; fa.count = cells * nbits;
-    fa.metrics = metrics; fa.dtailp = bwd ? dtailp : nullptr; fa.power_partial = pw ? pp->partial : nullptr;
-    fa.n_power = pw ? pp->n : 0; fa.power_denom = pw ? pp->denom : 1.0; fa.power_out = pw ? power_out : nullptr;
-    fa.adam = nullptr; memset(&fa.hp, 0, sizeof(fa.hp)); fa.zero_word = nullptr; fa.zero_flags = nullptr; fa.n_zero_flags = 0; fa.zero_stride = 0; fa.mon_acc = nullptr; fa.mon_noise = nullptr;
-    if (defer) {
-        *defer = fa;
-        return DCCN_OK;
-    }
-    hipLaunchKernelGGL(demod_tail_finalize_kernel, dim3(tail_finalize_blocks(P)), dim3(256), 0, s, fa);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return tail_finish(tail_finalize_args(tw, few ? few_tiles : nblk, bwd, nbits, cells, metrics, dtailp, pp, power_out), defer, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1118,16 +1099,23 @@ RxLayout rx_layout(const dccn_rx_shape* sh) {
     }
     return L;
 }
-static size_t rx_ws_bytes(const dccn_rx_shape* sh, int train) {
-    const RxLayout L = rx_layout(sh);
-    size_t o = 0;
-    o = carve_size(o, L.ws_norm);
-    o = carve_size(o, L.ws_tail);
-    if (train) {
-        o = carve_size(o, L.ws_dense_bw);
-        o = carve_size(o, L.ws_conv_bw);
+// the step's workspace: the regions of L.ws_* bytes its operators carve for themselves.  The receive step has R0's alone,
+// an evaluation step also the tail's, a training step all four.
+enum RxMode : int { RX_RECEIVE = 0, RX_EVAL, RX_TRAIN };
+struct RxWs { void *norm, *tail, *dense_bw, *conv_bw; };
+static RxWs rx_carve(Carver& c, const RxLayout& L, RxMode mode) {
+    RxWs w{};
+    w.norm = c.take<char>(L.ws_norm);
+    if (mode >= RX_EVAL) w.tail = c.take<char>(L.ws_tail);
+    if (mode == RX_TRAIN) {
+        w.dense_bw = c.take<char>(L.ws_dense_bw);
+        w.conv_bw = c.take<char>(L.ws_conv_bw);
     }
-    return align_up(o, 256);
+    return w;
+}
+static size_t rx_ws_bytes(const dccn_rx_shape* sh, RxMode mode) {
+    const RxLayout L = rx_layout(sh);
+    return carved_bytes([&](Carver& c) { rx_carve(c, L, mode); });
 }
 
 // The library's own second stream (one per device) and a pair of events per host thread: large layers run the dense kernel's
@@ -1303,7 +1291,7 @@ static int rx_norm_r0(const dccn_rx_shape* sh, const RxLayout& L, const float* x
 // rx_issue_* functions below only read it.  A refused step has launched nothing (also inside a stream capture).
 struct RxStepPlan {
     RxLayout L;
-    void *ws_norm, *ws_tail, *ws_dbw, *ws_cbw;
+    RxWs ws;
     bool train;
     bool pre;                       // x_norm already holds this batch (dccn_rx_buffers.x_prenormalised)
     int nslot;
@@ -1343,16 +1331,13 @@ static int rx_step_plan(const dccn_rx_shape* sh, const dccn_rx_buffers* b, bool 
                         RxStepPlan* plan) {
     if (!b->x || !b->bits || !b->params || !b->x_norm || !b->fft_out || !b->metrics) return DCCN_ERR_INVALID_ARG;
     if (train && (!b->grads || !b->adam_m || !b->adam_v || !b->adam || !b->dz)) return DCCN_ERR_INVALID_ARG;
-    if (!b->workspace || b->workspace_bytes < rx_ws_bytes(sh, train ? 1 : 0)) return DCCN_ERR_WORKSPACE;
+    if (!b->workspace || b->workspace_bytes < rx_ws_bytes(sh, train ? RX_TRAIN : RX_EVAL)) return DCCN_ERR_WORKSPACE;
     if (b->x_prenormalised != 0 && b->x_prenormalised != 1) return DCCN_ERR_INVALID_ARG;
     RxStepPlan& p = *plan;
     p = RxStepPlan{};
     const RxLayout& L = p.L = rx_layout(sh);
     Carver c(b->workspace, b->workspace_bytes);
-    p.ws_norm = c.take<char>(L.ws_norm);
-    p.ws_tail = c.take<char>(L.ws_tail);
-    p.ws_dbw = train ? c.take<char>(L.ws_dense_bw) : nullptr;
-    p.ws_cbw = train ? c.take<char>(L.ws_conv_bw) : nullptr;
+    p.ws = rx_carve(c, L, train ? RX_TRAIN : RX_EVAL);
     const float* wd = b->params + L.o_dense_w;
     p.train = train;
     p.pre = train && b->x_prenormalised != 0;
@@ -1415,8 +1400,8 @@ static int rx_issue_forward(const dccn_rx_shape* sh, const dccn_rx_buffers* b, c
     }
     // R0 (+R8 partial sums) -- unless the previous call already normalised this batch behind its Adam update
     PowerPartials pp;
-    if (p.pre) norm_power_partials(sh->batch, L.cols, p.ws_norm, L.ws_norm, b->x_next ? b->x_next : b->x, b->x_norm, &pp, p.nslot);
-    else DCCN_TRY(rx_norm_r0(sh, L, b->x, b->x_norm, b->tx_power != nullptr, &pp, p.ws_norm, hp, p.nslot, s));
+    if (p.pre) norm_power_partials(sh->batch, L.cols, p.ws.norm, L.ws_norm, b->x_next ? b->x_next : b->x, b->x_norm, &pp, p.nslot);
+    else DCCN_TRY(rx_norm_r0(sh, L, b->x, b->x_norm, b->tx_power != nullptr, &pp, p.ws.norm, hp, p.nslot, s));
     // R1
     trace.launch(1);
     DCCN_TRY(cconv_fwd_impl(b->x_norm, P + L.o_conv_w, P + L.o_conv_b, b->fft_out, L.rows, sh->kin, sh->F, s));
@@ -1424,13 +1409,13 @@ static int rx_issue_forward(const dccn_rx_shape* sh, const dccn_rx_buffers* b, c
     // R2 with R3-R6 (+ tail backward) in its epilogue; z is materialised only when the caller gave a buffer
     if (p.fused_tail)
         return dense_tail_impl(p.train, b->fft_out, P + L.o_dense_w, P + L.o_dense_b, b->z, b->bits, P + L.o_tail, b->prob,
-                               b->metrics, b->dz, gtail, sh->batch, L.dK, L.dN, sh->nbits, &pp, b->tx_power, p.ws_tail,
+                               b->metrics, b->dz, gtail, sh->batch, L.dK, L.dN, sh->nbits, &pp, b->tx_power, p.ws.tail,
                                L.ws_tail, s, p.train ? fin : nullptr);
     // R2, then R3-R6 (+ tail backward)
     DCCN_TRY(dense_fwd_impl(b->fft_out, P + L.o_dense_w, P + L.o_dense_b, b->z, sh->batch, L.dK, L.dN, s));
     trace.launch(3);
     return tail_impl(p.train, b->z, b->bits, P + L.o_tail, b->prob, b->metrics, b->dz, gtail, L.cells, sh->nbits, &pp,
-                     b->tx_power, p.ws_tail, L.ws_tail, s, p.train ? fin : nullptr);
+                     b->tx_power, p.ws.tail, L.ws_tail, s, p.train ? fin : nullptr);
 }
 
 // the optimizer launch's argument block: what the main launch and the dense kernel's update on the second stream share
@@ -1457,21 +1442,21 @@ static int rx_issue_backward(const dccn_rx_shape* sh, const dccn_rx_buffers* b, 
         if (p.ride_bw) {
             if (p.wait_x) DCCN_HIP(hipStreamWaitEvent(s, (hipEvent_t)b->x_next_ready, 0));
             PowerPartials np;
-            norm_power_partials(sh->batch, L.cols, p.ws_norm, L.ws_norm, b->x_next, b->x_norm_next, &np, p.nslot ^ 1);
+            norm_power_partials(sh->batch, L.cols, p.ws.norm, L.ws_norm, b->x_next, b->x_norm_next, &np, p.nslot ^ 1);
             nr.x = b->x_next; nr.y = b->x_norm_next; nr.power = b->tx_power ? const_cast<double*>(np.partial) : nullptr;
             nr.batch = sh->batch; nr.cols = L.cols; nr.blocks = norm_fused_blocks(L.cols);
             nr.eps = 1e-9f; nr.peak = 8.0f;
             nr.trail = g_tune[TUNE_NORM_ON_BWD] >= 2 ? 1 : 0;
         }
         return rx_bwd_fused_impl(b->x_norm, b->fft_out, b->dz, wd, b->dfft, G + L.o_dense_b, sh->batch, sh->S, sh->kin, sh->F,
-                                 sh->D, p.ws_dbw, L.ws_dense_bw, p.ws_cbw, L.ws_conv_bw, nr, k->fin, hp, s, &k->ds, &k->fd,
+                                 sh->D, p.ws.dense_bw, L.ws_dense_bw, p.ws.conv_bw, L.ws_conv_bw, nr, k->fin, hp, s, &k->ds, &k->fd,
                                  &k->fold_tilew);
     }
     if (p.branch.side) {
         // two-stream variant: dense dW/db on `side`, dX -> C-Conv dW on the main stream (joined in rx_issue_update)
         DCCN_HIP(hipEventRecord(p.branch.fork, s));
         DCCN_HIP(hipStreamWaitEvent(p.branch.side, p.branch.fork, 0));
-        DCCN_TRY(dense_bwd_w_impl(b->fft_out, b->dz, G + L.o_dense_w, G + L.o_dense_b, sh->batch, L.dK, L.dN, p.ws_dbw,
+        DCCN_TRY(dense_bwd_w_impl(b->fft_out, b->dz, G + L.o_dense_w, G + L.o_dense_b, sh->batch, L.dK, L.dN, p.ws.dense_bw,
                                   L.ws_dense_bw, p.branch.side, &k->ds));
         DCCN_HIP(hipEventRecord(p.branch.join, p.branch.side));
         return dense_bwd_x_impl(b->dz, wd, b->dfft, sh->batch, L.dK, L.dN, s);
@@ -1485,7 +1470,7 @@ static int rx_issue_backward(const dccn_rx_shape* sh, const dccn_rx_buffers* b, 
         k->fin.metrics = nullptr;
     }
     DCCN_TRY(dense_bwd_grouped_impl(b->fft_out, b->dz, wd, b->dfft, G + L.o_dense_w, G + L.o_dense_b, sh->batch, L.dK, L.dN,
-                                    p.ws_dbw, L.ws_dense_bw, s, &k->ds));
+                                    p.ws.dense_bw, L.ws_dense_bw, s, &k->ds));
     // (the plan saw an unsplit dW; knobs 1 and 4 can make the grouped launch split a very wide, very short dense kernel
     // after all: its slabs are then summed by the main optimizer launch and nothing is forked)
     if (!p.want_overlap || k->ds.dw_slabs != nullptr) return DCCN_OK;
@@ -1515,7 +1500,7 @@ static int rx_issue_update(const dccn_rx_shape* sh, const dccn_rx_buffers* b, co
     trace.launch(5);
     if (!p.fuse_bw)
         DCCN_TRY(cconv_bwd_w_impl(b->x_norm, b->dfft, b->grads + L.o_conv_w, b->grads + L.o_conv_b, L.rows, sh->kin, sh->F,
-                                  p.ws_cbw, L.ws_conv_bw, s, &k->fin, p.can_defer ? &k->fd : nullptr));
+                                  p.ws.conv_bw, L.ws_conv_bw, s, &k->fin, p.can_defer ? &k->fd : nullptr));
     if (p.branch.side) DCCN_HIP(hipStreamWaitEvent(s, p.branch.join, 0));
     if (p.wait_x && !p.ride_bw) DCCN_HIP(hipStreamWaitEvent(s, (hipEvent_t)b->x_next_ready, 0));
     // R7 (+ BER-gated L2 term of R6), fused with the split-K reduction of the dense gradient and the C-Conv fold
@@ -1543,7 +1528,7 @@ static int rx_issue_update(const dccn_rx_shape* sh, const dccn_rx_buffers* b, co
         // R0 of the next batch on the leading blocks of this launch (x_next, or gen_next's virtual input)
         const float* rin = p.gen ? p.gen->y : b->x_next;
         PowerPartials np;
-        norm_power_partials(sh->batch, L.cols, p.ws_norm, L.ws_norm, rin, b->x_norm, &np, p.nslot);
+        norm_power_partials(sh->batch, L.cols, p.ws.norm, L.ws_norm, rin, b->x_norm, &np, p.nslot);
         aa.nx = rin; aa.ny = b->x_norm; aa.npower = b->tx_power ? const_cast<double*>(np.partial) : nullptr;
         aa.nbatch = sh->batch; aa.ncols = L.cols; aa.norm_blocks = norm_fused_blocks(L.cols);
         blocks += aa.norm_blocks;
@@ -1571,7 +1556,7 @@ static int rx_issue_update(const dccn_rx_shape* sh, const dccn_rx_buffers* b, co
     trace.none();
     if (p.norm_after) {
         PowerPartials np;
-        DCCN_TRY(rx_norm_r0(sh, L, b->x_next, b->x_norm, b->tx_power != nullptr, &np, p.ws_norm, hp, p.nslot, s));
+        DCCN_TRY(rx_norm_r0(sh, L, b->x_next, b->x_norm, b->tx_power != nullptr, &np, p.ws.norm, hp, p.nslot, s));
     }
     if (ojoin->forked) { ojoin->joined = true; DCCN_HIP(hipStreamWaitEvent(s, p.ovs.join, 0)); }
     return DCCN_OK;
@@ -1602,15 +1587,11 @@ static int rx_step_impl(const dccn_rx_shape* sh, const dccn_rx_buffers* b, bool 
 // ---------------------------------------------------------------------------------------
 // receive step: R0 -> C-Conv forward -> dense + decision (no labels, no loss, no metrics)
 // ---------------------------------------------------------------------------------------
-static size_t rx_receive_ws_bytes(const dccn_rx_shape* sh) {
-    const RxLayout L = rx_layout(sh);
-    return align_up(carve_size(0, L.ws_norm), 256);
-}
 static int rx_receive_impl(const dccn_rx_shape* sh, const dccn_rx_receive_buffers* b, hipStream_t s) {
     if (!shape_ok(sh) || !b) return DCCN_ERR_INVALID_ARG;
     const TuneScope tune(b->tuning);
     if (!b->x || !b->params || !b->x_norm || !b->fft_out || !b->packed) return DCCN_ERR_INVALID_ARG;
-    if (!b->workspace || b->workspace_bytes < rx_receive_ws_bytes(sh)) return DCCN_ERR_WORKSPACE;
+    if (!b->workspace || b->workspace_bytes < rx_ws_bytes(sh, RX_RECEIVE)) return DCCN_ERR_WORKSPACE;
     const RxLayout L = rx_layout(sh);
     const float* P = b->params;
     // the dense forward runs the plan the evaluation step would take for this shape (same bits in z)
@@ -1622,8 +1603,8 @@ static int rx_receive_impl(const dccn_rx_shape* sh, const dccn_rx_receive_buffer
     if (!decide_outputs_aligned(b->llr, b->prob, sh->nbits) || (!one_launch && (reinterpret_cast<uintptr_t>(b->z) & 7u) != 0))
         return DCCN_ERR_INVALID_ARG;
     // R0, R1: the launches of the evaluation step
-    void* ws_norm = Carver(b->workspace, b->workspace_bytes).take<char>(L.ws_norm);
-    DCCN_TRY(rx_norm_r0(sh, L, b->x, b->x_norm, false, nullptr, ws_norm, dccn_adam_hparams{}, 0, s));
+    Carver c(b->workspace, b->workspace_bytes);
+    DCCN_TRY(rx_norm_r0(sh, L, b->x, b->x_norm, false, nullptr, rx_carve(c, L, RX_RECEIVE).norm, dccn_adam_hparams{}, 0, s));
     DCCN_TRY(cconv_fwd_impl(b->x_norm, P + L.o_conv_w, P + L.o_conv_b, b->fft_out, L.rows, sh->kin, sh->F, s));
     // R2 + decision
     if (via_tail_plan)
@@ -1631,6 +1612,14 @@ static int rx_receive_impl(const dccn_rx_shape* sh, const dccn_rx_receive_buffer
                                  sh->batch, L.dK, L.dN, sh->nbits, s);
     DCCN_TRY(dense_fwd_impl(b->fft_out, P + L.o_dense_w, P + L.o_dense_b, b->z, sh->batch, L.dK, L.dN, s));
     return decide_impl(b->z, P + L.o_tail, b->packed, b->llr, b->prob, sh->batch, sh->D, sh->nbits, s);
+}
+
+// the stand-alone fused backward: the dense slabs' region, then the C-Conv partials' region
+struct RxBackwardWs { void *dense, *conv; size_t n_dense, n_conv; };
+static RxBackwardWs rx_backward_carve(Carver& c, int batch, int S, int kin, int F, int D) {
+    const size_t nd = splitk_ws_bytes(S * 2 * F, 2 * D, batch), nc = rx_bwd_fused_ws_bytes(batch, S, kin, F);
+    void* dense = c.take<char>(nd);
+    return RxBackwardWs{dense, c.take<char>(nc), nd, nc};
 }
 
 int eq_monitor_blocks(int B, int K) {
@@ -1839,10 +1828,7 @@ int dccn_tuning_snapshot(int* table, int n) {
 
 size_t dccn_rx_backward_workspace_size(int batch, int S, int kin, int F, int D) {
     if (batch <= 0 || S <= 0 || kin <= 0 || F <= 0 || D <= 0) return 0;
-    size_t o = 0;
-    o = carve_size(o, splitk_ws_bytes(S * 2 * F, 2 * D, batch));
-    o = carve_size(o, rx_bwd_fused_ws_bytes(batch, S, kin, F));
-    return align_up(o, 256);
+    return carved_bytes([&](Carver& c) { rx_backward_carve(c, batch, S, kin, F, D); });
 }
 int dccn_rx_backward(const float* x_norm, const float* fft_out, const float* dz, const float* w_dense, float* dfft,
                      float* dw_dense, float* db_dense, float* dw_conv, float* db_conv, int batch, int S, int kin, int F,
@@ -1854,15 +1840,13 @@ int dccn_rx_backward(const float* x_norm, const float* fft_out, const float* dz,
     if (!workspace || workspace_bytes < dccn_rx_backward_workspace_size(batch, S, kin, F, D)) return DCCN_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int dK = S * 2 * F, dN = 2 * D;
-    const size_t nd = splitk_ws_bytes(dK, dN, batch), nc = rx_bwd_fused_ws_bytes(batch, S, kin, F);
     Carver c(workspace, workspace_bytes);
-    void* ws_d = c.take<char>(nd);
-    void* ws_c = c.take<char>(nc);
+    const RxBackwardWs w = rx_backward_carve(c, batch, S, kin, F, D);
     DeferredSlabs ds;
     FoldDefer fd;
     int tilew = 0;
-    DCCN_TRY(rx_bwd_fused_impl(x_norm, fft_out, dz, w_dense, dfft, db_dense ? db_dense : dw_dense, batch, S, kin, F, D, ws_d, nd,
-                               ws_c, nc, NormRideArgs{}, TailFinalizeArgs{}, dccn_adam_hparams{}, s, &ds, &fd, &tilew));
+    DCCN_TRY(rx_bwd_fused_impl(x_norm, fft_out, dz, w_dense, dfft, db_dense ? db_dense : dw_dense, batch, S, kin, F, D, w.dense,
+                               w.n_dense, w.conv, w.n_conv, NormRideArgs{}, TailFinalizeArgs{}, dccn_adam_hparams{}, s, &ds, &fd, &tilew));
     if (!reduce) return DCCN_OK;
     const long long n = (long long)dK * dN;
     if (db_dense) DCCN_TRY(launch_splitk_reduce2(ds.dw_slabs, ds.splits, n, dw_dense, n, ds.db_slabs, (long long)dN, db_dense, (long long)dN, s));
@@ -1953,7 +1937,7 @@ int dccn_dense_decide_fwd(const float* x, const float* w, const float* bias, flo
 }
 size_t dccn_rx_receive_workspace_size(const dccn_rx_shape* shape) {
     if (!shape_ok(shape)) return 0;
-    return rx_receive_ws_bytes(shape);
+    return rx_ws_bytes(shape, RX_RECEIVE);
 }
 int dccn_rx_receive_fused(const dccn_rx_shape* shape) {
     if (!shape_ok(shape)) return 0;
@@ -2003,7 +1987,7 @@ size_t dccn_rx_workspace_size(const dccn_rx_shape* shape, int train) {
     // any stream capture (every caller sizes its workspace first); rx_step_impl only looks them up
     if (train && shape_ok(shape) && g_tune[TUNE_ADAM_OVERLAP]) { OverlapStreams o; (void)overlap_streams(&o); }
     if (!shape_ok(shape)) return 0;
-    return rx_ws_bytes(shape, train);
+    return rx_ws_bytes(shape, train ? RX_TRAIN : RX_EVAL);
 }
 int dccn_rx_eval_step(const dccn_rx_shape* shape, const dccn_rx_buffers* buf, dccn_stream_t stream) {
     return rx_step_impl(shape, buf, false, dccn_adam_hparams{}, (hipStream_t)stream, nullptr);
@@ -2016,11 +2000,11 @@ int dccn_rx_train_step(const dccn_rx_shape* shape, const dccn_rx_buffers* buf, d
 // (dccn_rx_buffers.x_prenormalised) before the first call
 int dccn_rx_normalise(const dccn_rx_shape* shape, const dccn_rx_buffers* buf, dccn_stream_t stream) {
     if (!shape_ok(shape) || !buf || !buf->x || !buf->x_norm) return DCCN_ERR_INVALID_ARG;
-    if (!buf->workspace || buf->workspace_bytes < rx_ws_bytes(shape, 1)) return DCCN_ERR_WORKSPACE;
+    if (!buf->workspace || buf->workspace_bytes < rx_ws_bytes(shape, RX_TRAIN)) return DCCN_ERR_WORKSPACE;
     PowerPartials pp;
     const RxLayout L = rx_layout(shape);
-    void* ws_norm = Carver(buf->workspace, buf->workspace_bytes).take<char>(L.ws_norm);
-    return rx_norm_r0(shape, L, buf->x, buf->x_norm, buf->tx_power != nullptr, &pp, ws_norm, dccn_adam_hparams{},
+    Carver c(buf->workspace, buf->workspace_bytes);
+    return rx_norm_r0(shape, L, buf->x, buf->x_norm, buf->tx_power != nullptr, &pp, rx_carve(c, L, RX_TRAIN).norm, dccn_adam_hparams{},
                       buf->norm_slot ? 1 : 0, (hipStream_t)stream);
 }
 

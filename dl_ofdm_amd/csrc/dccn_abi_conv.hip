@@ -85,14 +85,15 @@ int dccn_cconv_patch_bwd_w(const float* x, const float* dout, float* dw, float* 
     hipStream_t s = (hipStream_t)stream;
     const SplitPlan sp = plan_splitk(2 * kin, 2 * F, rows);
     Carver c(workspace, workspace_bytes);
-    float* slabs = c.take<float>((size_t)sp.splits * 4 * kin * F);
-    float* cs = c.take<float>((size_t)sp.splits * 2 * F);
+    SlabWs sw;
+    if (!slab_carve(c, sp.splits, 2 * kin, 2 * F, &sw)) return DCCN_ERR_WORKSPACE;
+    float *slabs = sw.slabs, *cs = sw.colsum;
     GemmParams p = gp_zero();                 // dWeff[2kin,2F] = patches(x)[rows,2kin]^T . dout[rows,2F]
     p.A = x; p.B = dout; p.C = slabs; p.colsum = cs;
     p.M = 2 * kin; p.N = 2 * F; p.K = rows;
     p.lda = 0; p.ldb = 2 * F; p.ldc = 2 * F;
     p.klen = sp.klen;
-    p.slab = (long long)4 * kin * F;
+    p.slab = sw.slab;
     p.vecA = 1; p.vecB = 1;
     p.pg.L = L; p.pg.Wd = Wd; p.pg.c2 = 2 * C; p.pg.Lo = Lo; p.pg.Wo = Wo; p.pg.ntl = ntl; p.pg.ntw = ntw;
     p.pg.sL = sL; p.pg.sW = sW; p.pg.l0 = tl0 - pl0; p.pg.w0 = tw0 - pw0;
@@ -126,9 +127,11 @@ __global__ __launch_bounds__(256) void cconv_flip_wt_kernel(const float* __restr
     // Weff[2n, 2f] = Wa, [2n, 2f+1] = Wb, [2n+1, 2f] = -Wb, [2n+1, 2f+1] = -Wa (gemm_f32_mfma.h OP_CCONV_W)
     bt[i] = iq == 0 ? (oq == 0 ? wa : wb) : (oq == 0 ? -wb : -wa);
 }
+// the one piece of its workspace: Bt, the tap-flipped transposed weights (cconv_flip_wt_kernel)
+static float* patch_bwd_x_carve(Carver& c, int C, int ntl, int ntw, int F) { return c.take<float>((size_t)4 * C * ntl * ntw * F); }
 size_t dccn_cconv_patch_bwd_x_workspace_size(int C, int ntl, int ntw, int F) {
     if (C <= 0 || ntl <= 0 || ntw <= 0 || F <= 0) return 0;
-    return align_up((size_t)4 * C * ntl * ntw * F * sizeof(float), 256);
+    return carved_bytes([&](Carver& c) { patch_bwd_x_carve(c, C, ntl, ntw, F); });
 }
 int dccn_cconv_patch_bwd_x(const float* dout, const float* w, float* dx, int B, int L, int Wd, int C, int Lo, int Wo, int ntl,
                            int ntw, int tl0, int tw0, int sL, int sW, int pl0, int pw0, int F, void* workspace,
@@ -140,7 +143,8 @@ int dccn_cconv_patch_bwd_x(const float* dout, const float* w, float* dx, int B, 
     if (!workspace || workspace_bytes < dccn_cconv_patch_bwd_x_workspace_size(C, ntl, ntw, F) || !aligned16(workspace))
         return DCCN_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    float* bt = reinterpret_cast<float*>(workspace);
+    Carver c(workspace, workspace_bytes);
+    float* bt = patch_bwd_x_carve(c, C, ntl, ntw, F);
     const long long total = 4LL * C * ntl * ntw * F;
     hipLaunchKernelGGL(cconv_flip_wt_kernel, dim3((unsigned)ceil_div_ll(total, 256)), dim3(256), 0, s, w, bt, C, ntl, ntw, F);
     DCCN_LAUNCH_CHECK();
@@ -175,12 +179,15 @@ int dccn_cconv1d_bwd_supported(int B, int L, int C, int Lo, int ntl, int sL, int
     if ((long long)B * L * C * 2 >= (1LL << 31) || (long long)B * Lo * F * 2 >= (1LL << 31)) return 0;
     return 1;
 }
+// per-block weight-gradient slabs ([32][2F], the fold's k rows) and column sums of up to kConv1dMaxBlocks blocks
+struct Conv1dWs { float *slabs, *colsum; };
+static Conv1dWs conv1d_carve(Carver& c, int F) {
+    float* slabs = c.take<float>((size_t)kConv1dMaxBlocks * 32 * 2 * F);
+    return Conv1dWs{slabs, c.take<float>((size_t)kConv1dMaxBlocks * 2 * F)};
+}
 size_t dccn_cconv1d_bwd_workspace_size(int F) {
     if (F <= 0) return 0;
-    size_t o = 0;
-    o = carve_size(o, (size_t)kConv1dMaxBlocks * 32 * 2 * F * sizeof(float));
-    o = carve_size(o, (size_t)kConv1dMaxBlocks * 2 * F * sizeof(float));
-    return align_up(o, 256);
+    return carved_bytes([&](Carver& c) { conv1d_carve(c, F); });
 }
 int dccn_cconv1d_bwd(const float* x, const float* dout, const float* w, float* dx, float* dw, float* dbias, int B, int L, int C,
                      int Lo, int ntl, int tl0, int sL, int pl0, int F, void* workspace, size_t workspace_bytes,
@@ -190,11 +197,11 @@ int dccn_cconv1d_bwd(const float* x, const float* dout, const float* w, float* d
     if (!workspace || workspace_bytes < dccn_cconv1d_bwd_workspace_size(F)) return DCCN_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
+    const Conv1dWs cw = conv1d_carve(c, F);
     Conv1dBwdArgs a;
     memset(&a, 0, sizeof(a));
     a.x = x; a.dout = dout; a.w = w; a.dx = dx;
-    a.slabs = c.take<float>((size_t)kConv1dMaxBlocks * 32 * 2 * F);
-    a.colsum = c.take<float>((size_t)kConv1dMaxBlocks * 2 * F);
+    a.slabs = cw.slabs; a.colsum = cw.colsum;
     a.B = B; a.L = L; a.C2 = 2 * C; a.Lo = Lo; a.nt = ntl; a.F2 = 2 * F; a.NC = 2 * ntl * C;
     a.o = tl0 - pl0; a.s = sL;
     a.PL = conv1d_bwd_pl(ntl, sL);

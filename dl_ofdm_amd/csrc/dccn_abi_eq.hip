@@ -413,9 +413,14 @@ int dccn_cconv2d_same_reduce(const float* dT, const float* dbias_eff, float* dw,
 }
 
 // ---- per-step monitors of the equaliser harness in one launch (equalizer.h eq_monitor_kernel) --------------------
+struct EqMonitorWs { unsigned* counter; double* partial; };     // the blocks' arrival counter; one partial sum per block
+static EqMonitorWs eq_monitor_carve(Carver& c, int B, int K) {
+    unsigned* counter = c.take<unsigned>(1);
+    return EqMonitorWs{counter, c.take<double>((size_t)eq_monitor_blocks(B, K))};
+}
 size_t dccn_eq_monitor_workspace_size(int B, int S, int K) {
     if (B <= 0 || S <= 0 || K <= 0) return 0;
-    return align_up(256 + (size_t)eq_monitor_blocks(B, K) * sizeof(double), 256);
+    return carved_bytes([&](Carver& c) { eq_monitor_carve(c, B, K); });
 }
 int dccn_eq_monitor_accumulate(const float* chest, const float* chan, int chan_per_symbol, int B, int S, int K,
                                const dccn_metrics* metrics, const float* tx_power, const float* noise_power, float* acc5,
@@ -425,8 +430,9 @@ int dccn_eq_monitor_accumulate(const float* chest, const float* chan, int chan_p
     EqMonitorArgs a;
     a.chest = chest; a.chan = chan; a.gt_per_symbol = chan_per_symbol ? 1 : 0; a.B = B; a.S = S; a.K = K;
     a.metrics = metrics; a.tx_power = tx_power; a.noise_power = noise_power; a.acc = acc5; a.rms_out = rms_out;
-    a.counter = static_cast<unsigned*>(workspace);
-    a.partial = reinterpret_cast<double*>(static_cast<char*>(workspace) + 256);
+    Carver c(workspace, workspace_bytes);
+    const EqMonitorWs w = eq_monitor_carve(c, B, K);
+    a.counter = w.counter; a.partial = w.partial;
     DCCN_LAUNCH_CHAINS_Z(eq_monitor_kernel, dim3(eq_monitor_blocks(B, K)), dim3(256), 0, (hipStream_t)stream, a);
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;

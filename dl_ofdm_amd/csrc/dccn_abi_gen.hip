@@ -47,15 +47,37 @@ static FirPlan fir_plan(int items, int bx, int cap) {
     p.blocks = ceil_div(items, p.ipb);
     return p;
 }
+// workspace of the channel stage, one layout for the three entry points (gstride = complex taps per frame: L, S * L, 64 * S)
+// g: the frames' tap responses; y: FIR output, before the noise; partial: signal-power partials of the FIR blocks (kChanPartials
+// slots); npartial: noise-power partials, one per AWGN block (bx per frame)
+struct ChanWs { float *g, *y; double *partial, *npartial; int bx; };
+static ChanWs chan_carve(Carver& c, int frames, int T, int gstride) {
+    ChanWs w;
+    w.bx = chan_blocks_x(T);
+    w.g = c.take<float>((size_t)frames * gstride * 2);
+    w.y = c.take<float>((size_t)frames * T * 2);
+    w.partial = c.take<double>((size_t)kChanPartials);
+    w.npartial = c.take<double>((size_t)frames * w.bx);
+    c.take<float>(4);       // (four floats no launch uses: part of the size the callers allocate)
+    return w;
+}
 size_t dccn_channel_awgn_workspace_size(int frames, int T, int L) {
     if (frames <= 0 || T <= 0 || L <= 0) return 0;
-    size_t o = 0;
-    o = carve_size(o, (size_t)frames * L * 2 * sizeof(float));
-    o = carve_size(o, (size_t)frames * T * 2 * sizeof(float));
-    o = carve_size(o, (size_t)kChanPartials * sizeof(double));
-    o = carve_size(o, (size_t)frames * chan_blocks_x(T) * sizeof(double));
-    o = carve_size(o, 4 * sizeof(float));
-    return align_up(o, 256);
+    return carved_bytes([&](Carver& c) { chan_carve(c, frames, T, L); });
+}
+// the stage's tail: AWGN at the power the `n_partial` FIR partials sum to, then the noise power when the caller wants it
+static int chan_awgn_tail(const ChanWs& w, int n_partial, const float* snr_db, const float* noise_in, float* out, float* noise_power,
+                          int frames, int T, unsigned long long seed, unsigned offset, hipStream_t s) {
+    const double total = (double)frames * (double)T;
+    hipLaunchKernelGGL(awgn_kernel, dim3(w.bx, frames), dim3(256), 0, s, (const float2*)w.y, (const double*)w.partial, n_partial,
+                       total, snr_db, noise_in, (float2*)out, noise_power ? w.npartial : nullptr, T, offset, seed);
+    DCCN_LAUNCH_CHECK();
+    if (noise_power) {
+        hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, (const double*)w.npartial, frames * w.bx, total,
+                           noise_power);
+        DCCN_LAUNCH_CHECK();
+    }
+    return DCCN_OK;
 }
 int dccn_channel_awgn(const float* tx, const float* taps_in, const float* coeff, const float* alpha, int n_taps,
                       int L, int identity, const float* snr_db, const float* noise_in, float* out, float* H, int nfft,
@@ -67,11 +89,8 @@ int dccn_channel_awgn(const float* tx, const float* taps_in, const float* coeff,
     if (!workspace || workspace_bytes < dccn_channel_awgn_workspace_size(frames, T, L)) return DCCN_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
-    float* g = c.take<float>((size_t)frames * L * 2);
-    float* y = c.take<float>((size_t)frames * T * 2);
-    const int bx = chan_blocks_x(T);
-    double* partial = c.take<double>((size_t)kChanPartials);
-    double* npartial = c.take<double>((size_t)frames * bx);
+    const ChanWs w = chan_carve(c, frames, T, L);
+    float *g = w.g, *y = w.y; double* partial = w.partial; const int bx = w.bx;
     // nobody wants the frequency response and the taps are drawn here: the FIR blocks draw them themselves
     TapGen tg;
     memset(&tg, 0, sizeof(tg));
@@ -88,16 +107,7 @@ int dccn_channel_awgn(const float* tx, const float* taps_in, const float* coeff,
     hipLaunchKernelGGL(fir_same_kernel, dim3(nfb), dim3(256), 0, s, (const float2*)tx, (const float2*)g,
                        (float2*)y, partial, T, L, (const int*)nullptr, L, frames, 0, tg, fp.ipb);
     DCCN_LAUNCH_CHECK();
-    const double total = (double)frames * (double)T;
-    hipLaunchKernelGGL(awgn_kernel, dim3(bx, frames), dim3(256), 0, s, (const float2*)y, (const double*)partial, nfb, total,
-                       snr_db, noise_in, (float2*)out, noise_power ? npartial : nullptr, T, offset, seed);
-    DCCN_LAUNCH_CHECK();
-    if (noise_power) {
-        hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, (const double*)npartial, frames * bx, total,
-                           noise_power);
-        DCCN_LAUNCH_CHECK();
-    }
-    return DCCN_OK;
+    return chan_awgn_tail(w, nfb, snr_db, noise_in, out, noise_power, frames, T, seed, offset, s);
 }
 
 // ---- fused static-channel generator (datagen.h gen_static_frames_kernel) ----------------------------------------------
@@ -162,11 +172,8 @@ int dccn_channel_doppler_awgn(const float* tx, const float* theta_in, const floa
         return DCCN_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
-    float* g = c.take<float>((size_t)frames * S * L * 2);
-    float* y = c.take<float>((size_t)frames * T * 2);
-    const int bx = chan_blocks_x(T);
-    double* partial = c.take<double>((size_t)kChanPartials);
-    double* npartial = c.take<double>((size_t)frames * bx);
+    const ChanWs w = chan_carve(c, frames, T, S * L);
+    float *g = w.g, *y = w.y; double* partial = w.partial; const int bx = w.bx;
     hipLaunchKernelGGL(doppler_taps_kernel, dim3(frames), dim3(64), 0, s, theta_in, coeff, alpha, (float2*)g, (float2*)H,
                        n_taps, L, nfft, S, Fd, t_sym, offset, seed, (const int*)nullptr, n_taps, S * L);
     DCCN_LAUNCH_CHECK();
@@ -174,16 +181,7 @@ int dccn_channel_doppler_awgn(const float* tx, const float* theta_in, const floa
     hipLaunchKernelGGL(fir_doppler_kernel, dim3(nfb), dim3(256), 0, s, (const float2*)tx, (const float2*)g,
                        (float2*)y, partial, T, L, n_sc, n_taps, (const int*)nullptr, S * L, frames, 0);
     DCCN_LAUNCH_CHECK();
-    const double total = (double)frames * (double)T;
-    hipLaunchKernelGGL(awgn_kernel, dim3(bx, frames), dim3(256), 0, s, (const float2*)y, (const double*)partial, nfb, total,
-                       snr_db, noise_in, (float2*)out, noise_power ? npartial : nullptr, T, offset, seed);
-    DCCN_LAUNCH_CHECK();
-    if (noise_power) {
-        hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, (const double*)npartial, frames * bx, total,
-                           noise_power);
-        DCCN_LAUNCH_CHECK();
-    }
-    return DCCN_OK;
+    return chan_awgn_tail(w, nfb, snr_db, noise_in, out, noise_power, frames, T, seed, offset, s);
 }
 
 size_t dccn_channel_groups_awgn_workspace_size(int frames, int T, int S) {
@@ -212,11 +210,8 @@ int dccn_channel_groups_awgn(const float* tx, const dccn_channel_group* groups, 
     hipStream_t s = (hipStream_t)stream;
     Carver c(workspace, workspace_bytes);
     const int gstride = 64 * S;
-    float* g = c.take<float>((size_t)frames * gstride * 2);
-    float* y = c.take<float>((size_t)frames * T * 2);
-    const int bx = chan_blocks_x(T);
-    double* partial = c.take<double>((size_t)kChanPartials);
-    double* npartial = c.take<double>((size_t)frames * bx);
+    const ChanWs w = chan_carve(c, frames, T, gstride);
+    float *g = w.g, *y = w.y; double* partial = w.partial; const int bx = w.bx;
     int live = 0;
     for (int i = 0; i < n_groups; ++i) live += groups[i].n_frames > 0 ? 1 : 0;
     const int pcap = kChanPartials / (live > 0 ? live : 1);       // partial slots per group launch
@@ -253,25 +248,18 @@ int dccn_channel_groups_awgn(const float* tx, const dccn_channel_group* groups, 
             pbase += nfb;
         }
     }
-    const double total = (double)frames * (double)T;
-    hipLaunchKernelGGL(awgn_kernel, dim3(bx, frames), dim3(256), 0, s, (const float2*)y, (const double*)partial, pbase, total,
-                       snr_db, noise_in, (float2*)out, noise_power ? npartial : nullptr, T, offset, seed);
-    DCCN_LAUNCH_CHECK();
-    if (noise_power) {
-        hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, (const double*)npartial, frames * bx, total,
-                           noise_power);
-        DCCN_LAUNCH_CHECK();
-    }
-    return DCCN_OK;
+    return chan_awgn_tail(w, pbase, snr_db, noise_in, out, noise_power, frames, T, seed, offset, s);
 }
 
 // ---- classical pilot-aided receivers (classical.h) -----------------------------------------------------------------
-size_t dccn_classical_workspace_size(void) {
-    size_t o = 0;
-    o = carve_size(o, (size_t)kClassicalPartials * 4 * sizeof(double));
-    o = carve_size(o, (size_t)kClassicalPartials * sizeof(long long));
-    return align_up(o, 256);
+// gain: per-block sums of dccn_classical_gain (dccn_classical_estimate modes 1 / 3 read them); errors: per-block bit errors of
+// dccn_classical_detect
+struct ClassicalWs { double* gain; long long* errors; };
+static ClassicalWs classical_carve(Carver& c) {
+    double* gain = c.take<double>((size_t)kClassicalPartials * 4);
+    return ClassicalWs{gain, c.take<long long>((size_t)kClassicalPartials)};
 }
+size_t dccn_classical_workspace_size(void) { return carved_bytes([](Carver& c) { classical_carve(c); }); }
 static int classical_blocks(long long items) {
     long long b = items < 2 * kCUs ? items : 2 * kCUs;
     if (b > kClassicalPartials) b = kClassicalPartials;
@@ -295,7 +283,7 @@ int dccn_classical_gain(const float* Y, const float* H, const float* Gls, const 
     if (!Y || !Gls || !pil || n <= 0 || SK <= 0 || P <= 0) return DCCN_ERR_INVALID_ARG;
     if (!workspace || workspace_bytes < dccn_classical_workspace_size()) return DCCN_ERR_WORKSPACE;
     Carver c(workspace, workspace_bytes);
-    double* partial = c.take<double>((size_t)kClassicalPartials * 4);
+    double* partial = classical_carve(c).gain;
     const int nblk = classical_blocks(n);       // (dccn_classical_estimate modes 1 / 3 read these partials: dccn.h order contract)
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(classical_gain_kernel, dim3(nblk), dim3(256), 0, s, (const float2*)Y, (const float2*)H, Gls, pil, partial,
@@ -314,7 +302,7 @@ int dccn_classical_estimate(const float* Gls, const float* H, float* G, int n, i
     if ((mode == CE_LMMSE || mode == CE_PERFECT) && !H) return DCCN_ERR_INVALID_ARG;
     if (!workspace || workspace_bytes < dccn_classical_workspace_size()) return DCCN_ERR_WORKSPACE;
     Carver c(workspace, workspace_bytes);
-    double* partial = c.take<double>((size_t)kClassicalPartials * 4);
+    double* partial = classical_carve(c).gain;
     hipLaunchKernelGGL(classical_estimate_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, Gls, (const float2*)H,
                        (const double*)partial, classical_blocks(n), (float2*)G, n, S, K, mode, c_var);
     DCCN_LAUNCH_CHECK();
@@ -328,8 +316,7 @@ int dccn_classical_detect(const float* Y, const float* G, const int* dat, const 
         return DCCN_ERR_INVALID_ARG;
     if (!workspace || workspace_bytes < dccn_classical_workspace_size()) return DCCN_ERR_WORKSPACE;
     Carver c(workspace, workspace_bytes);
-    c.take<double>((size_t)kClassicalPartials * 4);
-    long long* ep = c.take<long long>((size_t)kClassicalPartials);
+    long long* ep = classical_carve(c).errors;
     const int nblk = classical_blocks(ceil_div_ll((long long)n * D, 256));
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(classical_detect_kernel, dim3(nblk), dim3(256), 0, s, (const float2*)Y, (const float2*)G, dat,
@@ -342,16 +329,26 @@ int dccn_classical_detect(const float* Y, const float* G, const int* dat, const 
 }
 
 // ---- in-graph AWGN monitor branch (`iq_tx:0`, `iq_rx:0`, `noise_power:0`) -----------------------------------
+// clipped / xn: the clipped and the re-normalised signal; norm / clip: the two operators' own workspaces; partial: noise-power
+// partials, gx per frame; scratch_pw: complex_clip's power output is `tx_power:0`, served elsewhere
+struct IngraphWs { float *clipped, *xn; void *norm, *clip; size_t n_norm, n_clip; double* partial; int gx; float* scratch_pw; };
+static IngraphWs ingraph_carve(Carver& c, int frames, int pairs_per_frame) {
+    const size_t n_pairs = (size_t)frames * pairs_per_frame;
+    IngraphWs w;
+    w.clipped = c.take<float>(n_pairs * 2);
+    w.xn = c.take<float>(n_pairs * 2);
+    w.n_norm = norm_ws_bytes(frames, 2 * pairs_per_frame);
+    w.norm = c.take<char>(w.n_norm);
+    w.n_clip = dccn_clip_power_workspace_size((long long)n_pairs);
+    w.clip = c.take<char>(w.n_clip);
+    w.gx = ceil_div(pairs_per_frame, 256);
+    w.partial = c.take<double>((size_t)frames * w.gx);
+    w.scratch_pw = c.take<float>(64);
+    return w;
+}
 size_t dccn_ingraph_awgn_workspace_size(int frames, int pairs_per_frame) {
     if (frames <= 0 || pairs_per_frame <= 0) return 0;
-    size_t o = 0;
-    o = carve_size(o, (size_t)frames * pairs_per_frame * 2 * sizeof(float));                   // clipped
-    o = carve_size(o, (size_t)frames * pairs_per_frame * 2 * sizeof(float));                   // re-normalised
-    o = carve_size(o, norm_ws_bytes(frames, 2 * pairs_per_frame));
-    o = carve_size(o, dccn_clip_power_workspace_size((long long)frames * pairs_per_frame));
-    o = carve_size(o, (size_t)frames * ceil_div(pairs_per_frame, 256) * sizeof(double));
-    o = carve_size(o, 256);
-    return align_up(o, 256);
+    return carved_bytes([&](Carver& c) { ingraph_carve(c, frames, pairs_per_frame); });
 }
 int dccn_ingraph_awgn(const float* x_norm, const float* snr_db, float* tx_signal, uint16_t* iq_tx_f16,
                       uint16_t* iq_rx_f16, float* noise_power, int frames, int pairs_per_frame, float peak,
@@ -362,21 +359,14 @@ int dccn_ingraph_awgn(const float* x_norm, const float* snr_db, float* tx_signal
     hipStream_t s = (hipStream_t)stream;
     const long long n_pairs = (long long)frames * pairs_per_frame;
     Carver c(workspace, workspace_bytes);
-    float* clipped = c.take<float>((size_t)n_pairs * 2);
-    float* xn = c.take<float>((size_t)n_pairs * 2);
-    const size_t nws = norm_ws_bytes(frames, 2 * pairs_per_frame);
-    void* ws_norm = c.take<char>(nws);
-    const size_t cws = dccn_clip_power_workspace_size(n_pairs);
-    void* ws_clip = c.take<char>(cws);
-    const int gx = ceil_div(pairs_per_frame, 256);
-    double* partial = c.take<double>((size_t)frames * gx);
-    float* scratch_pw = c.take<float>(64);            // complex_clip's power output is `tx_power:0`, served elsewhere
-    float* clip_dst = tx_signal ? tx_signal : clipped;
-    DCCN_TRY(dccn_clip_power(x_norm, clip_dst, scratch_pw, n_pairs, peak, ws_clip, cws, stream));
+    const IngraphWs w = ingraph_carve(c, frames, pairs_per_frame);
+    float* xn = w.xn; double* partial = w.partial; const int gx = w.gx;
+    float* clip_dst = tx_signal ? tx_signal : w.clipped;
+    DCCN_TRY(dccn_clip_power(x_norm, clip_dst, w.scratch_pw, n_pairs, peak, w.clip, w.n_clip, stream));
     dccn_adam_hparams hp;
     memset(&hp, 0, sizeof(hp));
     DCCN_TRY(norm_impl(clip_dst, xn, nullptr, nullptr, false, nullptr, frames, 2 * pairs_per_frame, 1e-8f, peak, nullptr, hp,
-                       ws_norm, nws, s));
+                       w.norm, w.n_norm, s));
     hipLaunchKernelGGL(ingraph_awgn_kernel, dim3(gx, frames), dim3(256), 0, s, (const float2*)clip_dst, (const float2*)xn,
                        snr_db, reinterpret_cast<__half2*>(iq_tx_f16), reinterpret_cast<__half2*>(iq_rx_f16), partial,
                        pairs_per_frame, offset, seed);

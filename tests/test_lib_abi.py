@@ -87,6 +87,107 @@ def test_eq_workspace_tensor_lookup(lib):
     assert lib.dccn_eq_workspace_tensor(C.byref(sh), 1, None, C.byref(off), C.byref(cnt)) == -1
 
 
+def test_short_workspace_is_refused_before_device_work(lib):
+    """Every entry point that takes a workspace, called with otherwise valid arguments and one byte less than its size query
+    asks for, answers DCCN_ERR_WORKSPACE (-2) -- before anything touches a device: the pointers are small host buffers that a
+    refused call never dereferences (this runs on a box without a GPU).  (dccn_rx_graph_create / dccn_eq_graph_create open a
+    stream capture around the same step and need a device for that; the step they capture is the one checked here.)"""
+    from dl_ofdm_amd import _lib
+    store = (C.c_char * 8192)()
+    p = C.c_void_p((C.addressof(store) + 255) // 256 * 256)          # 256-byte aligned, like every device allocation
+    hp = _lib.AdamHParams.default()
+    got = {}
+
+    def short(name, query, call):
+        n = query()
+        assert n > 0, name
+        got[name] = call(n - 1)
+
+    L = lib
+    short("batch_moment_norm_fwd", lambda: L.dccn_batch_moment_norm_workspace_size(36, 1120),
+          lambda n: L.dccn_batch_moment_norm_fwd(p, p, p, p, 36, 1120, 1e-9, p, n, None))
+    short("clip_power", lambda: L.dccn_clip_power_workspace_size(2240), lambda n: L.dccn_clip_power(p, p, p, 2240, 8.0, p, n, None))
+    short("cconv_gemm_bwd_w", lambda: L.dccn_cconv_gemm_bwd_w_workspace_size(511, 80, 64),
+          lambda n: L.dccn_cconv_gemm_bwd_w(p, p, p, p, 511, 80, 64, p, n, None))
+    for M, K, N in ((73, 896, 896), (300, 896, 640)):
+        q = lambda: L.dccn_dense_bwd_w_workspace_size(M, K, N)      # noqa: E731
+        short("dense_bwd_w %d" % M, q, lambda n: L.dccn_dense_bwd_w(p, p, p, p, M, K, N, p, n, None))
+        short("dense_bwd %d" % M, q, lambda n: L.dccn_dense_bwd(p, p, p, p, p, p, M, K, N, p, n, None))
+        short("dense_bwd_slabs %d" % M, q, lambda n: L.dccn_dense_bwd_slabs(p, p, p, p, p, p, M, K, N, p, n, None, None))
+    for nb in (2, 4):
+        q = lambda: L.dccn_demod_tail_workspace_size(36 * 320, nb)      # noqa: E731
+        short("demod_tail_loss_fwd %d" % nb, q, lambda n: L.dccn_demod_tail_loss_fwd(p, p, p, p, p, 36 * 320, nb, p, n, None))
+        short("demod_tail_loss_fwd_bwd %d" % nb, q,
+              lambda n: L.dccn_demod_tail_loss_fwd_bwd(p, p, p, p, p, p, p, 36 * 320, nb, p, n, None))
+        q = lambda: L.dccn_dense_tail_workspace_size(36, 640, nb)      # noqa: E731
+        short("dense_tail_fwd %d" % nb, q, lambda n: L.dccn_dense_tail_fwd(p, p, p, p, p, p, p, p, 36, 896, 640, nb, p, n, None))
+        short("dense_tail_fwd_bwd %d" % nb, q,
+              lambda n: L.dccn_dense_tail_fwd_bwd(p, p, p, p, p, p, p, p, p, p, 36, 896, 640, nb, p, n, None))
+    short("rx_backward", lambda: L.dccn_rx_backward_workspace_size(64, 7, 80, 64, 320),
+          lambda n: L.dccn_rx_backward(p, p, p, p, p, p, p, p, p, 64, 7, 80, 64, 320, 1, p, n, None))
+    for nb in (2, 4):
+        sh = _lib.RxShape(36, 7, 80, 64, 320, nb)
+
+        def rx_buffers(n):
+            b = _lib.RxBuffers()
+            for f in ("x", "bits", "params", "grads", "adam_m", "adam_v", "adam", "x_norm", "fft_out", "z", "prob", "dz", "dfft",
+                      "metrics", "workspace"):
+                setattr(b, f, p.value)
+            b.workspace_bytes = n
+            return b
+        short("rx_eval_step %d" % nb, lambda: L.dccn_rx_workspace_size(C.byref(sh), 0),
+              lambda n: L.dccn_rx_eval_step(C.byref(sh), C.byref(rx_buffers(n)), None))
+        short("rx_train_step %d" % nb, lambda: L.dccn_rx_workspace_size(C.byref(sh), 1),
+              lambda n: L.dccn_rx_train_step(C.byref(sh), C.byref(rx_buffers(n)), hp, None))
+        short("rx_normalise %d" % nb, lambda: L.dccn_rx_workspace_size(C.byref(sh), 1),
+              lambda n: L.dccn_rx_normalise(C.byref(sh), C.byref(rx_buffers(n)), None))
+        short("rx_receive_step %d" % nb, lambda: L.dccn_rx_receive_workspace_size(C.byref(sh)),
+              lambda n: L.dccn_rx_receive_step(C.byref(sh), C.byref(_lib.RxReceiveBuffers(p.value, p.value, p.value, p.value, p.value,
+                                                                                         p.value, None, None, p.value, n, None)), None))
+    geo = (2, 12, 10, 2, 10, 8, 3, 3, 0, 0, 1, 1, 0, 0, 16)             # B, L, Wd, C, Lo, Wo, ntl, ntw, tl0, tw0, sL, sW, pl0, pw0, F
+    short("cconv_patch_bwd_w", lambda: L.dccn_cconv_patch_bwd_w_workspace_size(2, 10, 8, 2, 3, 3, 16),
+          lambda n: L.dccn_cconv_patch_bwd_w(p, p, p, p, *geo, p, n, None))
+    short("cconv_patch_bwd_x", lambda: L.dccn_cconv_patch_bwd_x_workspace_size(2, 3, 3, 16),
+          lambda n: L.dccn_cconv_patch_bwd_x(p, p, p, *geo, p, n, None))
+    assert L.dccn_cconv1d_bwd_supported(2, 64, 2, 64, 3, 1, 32) == 1
+    short("cconv1d_bwd", lambda: L.dccn_cconv1d_bwd_workspace_size(32),
+          lambda n: L.dccn_cconv1d_bwd(p, p, p, p, p, p, 2, 64, 2, 64, 3, 0, 1, 0, 32, p, n, None))
+    short("channel_awgn", lambda: L.dccn_channel_awgn_workspace_size(6, 560, 9),
+          lambda n: L.dccn_channel_awgn(p, None, p, p, 9, 9, 0, p, None, p, None, 0, p, 6, 560, 1, 0, p, n, None))
+    short("channel_doppler_awgn", lambda: L.dccn_channel_doppler_awgn_workspace_size(6, 560, 9, 7),
+          lambda n: L.dccn_channel_doppler_awgn(p, None, p, p, 9, 9, 70.0, 7e-5, 7, 80, p, None, p, None, 0, p, 6, 1, 0, p, n, None))
+    grp = (_lib.ChannelGroup * 1)(_lib.ChannelGroup(None, 6, p.value, p.value, 9, 9, 0, 70.0))
+    short("channel_groups_awgn", lambda: L.dccn_channel_groups_awgn_workspace_size(6, 560, 7),
+          lambda n: L.dccn_channel_groups_awgn(p, grp, 1, None, None, 7e-5, 7, 80, p, None, p, None, 0, p, 6, 1, 0, p, n, None))
+    cq = L.dccn_classical_workspace_size
+    short("classical_gain", cq, lambda n: L.dccn_classical_gain(p, p, p, p, 4, 448, 8, 1.0, 0.0, p, p, n, None))
+    short("classical_estimate", cq, lambda n: L.dccn_classical_estimate(p, p, p, 4, 7, 64, 0, 0.0, p, n, None))
+    short("classical_detect", cq, lambda n: L.dccn_classical_detect(p, p, p, p, p, p, p, p, 4, 448, 320, 4, 2, 448, 1, p, n, None))
+    short("ingraph_awgn", lambda: L.dccn_ingraph_awgn_workspace_size(4, 560),
+          lambda n: L.dccn_ingraph_awgn(p, p, p, p, p, p, 4, 560, 8.0, 1, 0, p, n, None))
+    short("eq_monitor_accumulate", lambda: L.dccn_eq_monitor_workspace_size(12, 7, 64),
+          lambda n: L.dccn_eq_monitor_accumulate(p, p, 0, 12, 7, 64, p, p, p, p, p, p, n, None))
+    assert L.dccn_eq_bottleneck_supported(12, 896, 16) == 1
+    short("eq_bottleneck_bwd", lambda: L.dccn_eq_bottleneck_workspace_size(12, 896, 16),
+          lambda n: L.dccn_eq_bottleneck_bwd(*([p] * 11), 12, 896, 16, p, n, None))
+    es = _lib.EqShape(12, 7, 64, 16, 1, 64, 320, 2, 16, 8)
+
+    def eq_buffers(n):
+        b = _lib.EqBuffers()
+        for f in ("x", "bits", "eq_params", "eq_grads", "adam_m", "adam_v", "adam", "rx_params", "out_eq", "chest", "snr_db",
+                  "pilot_carriers", "prob", "metrics", "workspace"):
+            setattr(b, f, p.value)
+        b.workspace_bytes = n
+        return b
+    short("eq_eval_step", lambda: L.dccn_eq_workspace_size(C.byref(es), 0),
+          lambda n: L.dccn_eq_eval_step(C.byref(es), C.byref(eq_buffers(n)), None))
+    short("eq_train_step", lambda: L.dccn_eq_workspace_size(C.byref(es), 1),
+          lambda n: L.dccn_eq_train_step(C.byref(es), C.byref(eq_buffers(n)), hp, None))
+    short("eq_receive_step", lambda: L.dccn_eq_workspace_size(C.byref(es), 0),
+          lambda n: L.dccn_eq_receive_step(C.byref(es), C.byref(eq_buffers(n)), C.byref(_lib.ReceiveOut(p.value, None, None)), None))
+    assert len(got) == 41 and all(v == -2 for v in got.values()), {k: v for k, v in got.items() if v != -2}
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from dl_ofdm_amd import _lib, ops
