@@ -99,7 +99,95 @@ int round_k(int K) { return ceil_div(K, 64) * 64; }
 // the fast GEMM loaders use 32-bit byte offsets from a uniform base: operand must be < 2 GiB
 static bool small_enough(long long rows, long long ld) { return rows * ld * 4 < (1LL << 31); }
 
-// ldx > 0: x is a column window of a wider row-major matrix (row stride ldx)
+// ---- one description per GEMM role: extents, leading dimensions, the whole-k klen, the slab distance of a weight gradient and
+// the two vector-legality flags.  A site adds only what it alone knows: the output pointer or slab target, colsum, the klen
+// of a split plan, nranges / koff, aux / out2 / out3, gC.
+// may the fast loaders read the operand at p as vectors?  div: the divisibility its layout asks for
+static bool vec_ok(const float* p, bool div, long long rows, long long ld) { return div && aligned16(p) && small_enough(rows, ld); }
+// a site whose kernels have no scalar loaders refuses, before its first launch, operands that are not vector-legal
+static bool vec_both(const GemmParams& p) { return p.vecA && p.vecB; }
+
+// extents, leading dimensions and the whole-k klen of C[M,N] = A . B over a contraction of K
+static GemmParams gemm_role(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc) {
+    GemmParams p = gp_zero();
+    p.A = A; p.B = B; p.C = C;
+    p.M = M; p.N = N; p.K = K;
+    p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    p.klen = round_k(K);
+    return p;
+}
+// y[M,N] = x[M,K] . w[K,N] + bias.  ldx > 0: x is a column window of a wider row-major matrix (row stride ldx)
+static GemmParams dense_fwd_params(const float* x, const float* w, const float* bias, float* y, int M, int K, int N, int ldx = 0) {
+    GemmParams p = gemm_role(x, w, y, M, N, K, ldx > 0 ? ldx : K, N, N);
+    p.bias = bias;
+    p.vecA = vec_ok(x, (K % 4 == 0) && (p.lda % 4 == 0), M, p.lda);      // KCONTIG: k extent K
+    p.vecB = vec_ok(w, N % 4 == 0, K, N);                                 // ICONTIG: ld = N, i extent N
+    return p;
+}
+// dx[M,K] = dy[M,N] . w[K,N]^T
+static GemmParams dense_bwd_x_params(const float* dy, const float* w, float* dx, int M, int K, int N) {
+    GemmParams p = gemm_role(dy, w, dx, M, K, N, N, N, K);
+    p.vecA = vec_ok(dy, N % 4 == 0, M, N);
+    p.vecB = vec_ok(w, N % 4 == 0, K, N);
+    return p;
+}
+// dw[K,N] = x[M,K]^T . dy[M,N].  ldx as dense_fwd_params
+static GemmParams dense_bwd_w_params(const float* x, const float* dy, int M, int K, int N, int ldx = 0) {
+    GemmParams p = gemm_role(x, dy, nullptr, K, N, M, ldx > 0 ? ldx : K, N, N);
+    p.slab = (long long)K * N;
+    p.vecA = vec_ok(x, (K % 4 == 0) && (p.lda % 4 == 0), M, p.lda);
+    p.vecB = vec_ok(dy, N % 4 == 0, M, N);
+    return p;
+}
+// out[rows,2F] = x[rows,2kin] . Weff[2kin,2F] + bias.  ldx: row stride of x; ldc: row stride of out (the joined pairs)
+static GemmParams cconv_fwd_params(const float* x, const float* w, const float* bias, float* out, int rows, int kin, int F,
+                                   int ldx = 0, int ldc = 0) {
+    GemmParams p = gemm_role(x, w, out, rows, 2 * F, 2 * kin, ldx > 0 ? ldx : 2 * kin, 2 * F, ldc > 0 ? ldc : 2 * F);
+    p.bias = bias; p.cbias = 1; p.cF = F;
+    p.vecA = vec_ok(x, (kin % 2 == 0) && (p.lda % 4 == 0), rows, p.lda);
+    p.vecB = vec_ok(w, F % 2 == 0, kin, 2LL * F);                         // float2 loads of [Wa|Wb] rows
+    return p;
+}
+// dx[rows,2kin] = dout[rows,2F] . Weff^T.  ldc: row stride of dx
+static GemmParams cconv_bwd_x_params(const float* dout, const float* w, float* dx, int rows, int kin, int F, int ldc = 0) {
+    GemmParams p = gemm_role(dout, w, dx, rows, 2 * kin, 2 * F, 2 * F, 2 * F, ldc > 0 ? ldc : 2 * kin);
+    p.cF = F;
+    p.vecA = vec_ok(dout, F % 2 == 0, rows, 2LL * F);
+    p.vecB = vec_ok(w, F % 2 == 0, kin, 2LL * F);
+    return p;
+}
+// dWeff[2kin,2F] = x[rows,2kin]^T . dout[rows,2F]
+static GemmParams cconv_bwd_w_params(const float* x, const float* dout, int rows, int kin, int F) {
+    GemmParams p = gemm_role(x, dout, nullptr, 2 * kin, 2 * F, rows, 2 * kin, 2 * F, 2 * F);
+    p.slab = 4LL * kin * F;
+    p.vecA = vec_ok(x, kin % 2 == 0, rows, 2LL * kin);
+    p.vecB = vec_ok(dout, F % 2 == 0, rows, 2LL * F);
+    return p;
+}
+
+// ---- one table per variant family: a variant's gemm16.h template arguments are written once; the launcher instantiation,
+// the tile's rows and columns and its k-tile depth all read them
+struct Tile16Cfg {
+    int wgm, wgn, tm, tn, bk, ks;     // WGM x WGN waves of TM x TN 16x16 tiles each, k-tiles BK deep, KS k-slices
+    constexpr int rows() const { return wgm * tm * 16; }
+    constexpr int cols() const { return wgn * tn * 16; }
+};
+// (a family's launcher is a template over the variant number that reads its row; a table of its instantiations, indexed by
+// the variant, sits next to the rows)
+
+// the tiles the plain and the fused (tail / decision) dense forward run on: 48x64 with loads two k-tiles ahead (small layers),
+// 80x64 (large layers), 32x64 for a short last tile row next to the 80x64 tiles
+constexpr Tile16Cfg kDense48 = {1, 4, 3, 1, 64, 1}, kDense80 = {1, 4, 5, 1, 64, 1}, kDense32 = {1, 4, 2, 1, 64, 1};
+static_assert(kDense48.cols() == 64 && kDense80.cols() == 64 && kDense32.cols() == 64 && kDense48.bk == kDense80.bk &&
+              kDense32.bk == kDense80.bk, "the fused dense forward kernels are written for 1 x 4 waves of TM x 1 tiles");
+// ACT: element-wise stage in the store (2 = tanh, 5 = the equaliser stage)
+template <int ACT = 1>
+static int dense48_launch(const GemmParams& p, hipStream_t s, size_t smem_min = 0) {
+    constexpr Tile16Cfg c = kDense48;
+    return launch_gemm16<OP_KCONTIG, OP_ICONTIG, c.wgm, c.wgn, c.tm, c.tn, c.bk, c.ks, 0, TAG_DENSE_FWD, 2, ACT>(p, 1, s, smem_min);
+}
+
+// ldx: as dense_fwd_params
 // act = 2: y = tanh(x.w + bias) when the launch plan has the stage (few-row 16x64 tiles); *act_done tells
 // act = 5 (+ aux = the received cells, out2 / out3): the output is a channel estimate; eq and corr of model.py:431-438
 // leave the same launch
@@ -108,66 +196,39 @@ int dense_fwd_impl(const float* x, const float* w, const float* bias, float* y, 
                           float* out2, float* out3) {
     if (act_done) *act_done = false;
     if (!x || !w || !y || M <= 0 || K <= 0 || N <= 0) return DCCN_ERR_INVALID_ARG;
-    const int lda = ldx > 0 ? ldx : K;
-    GemmParams p = gp_zero();
-    p.A = x; p.B = w; p.C = y; p.bias = bias;
-    p.M = M; p.N = N; p.K = K;
-    p.lda = lda; p.ldb = N; p.ldc = N;
-    p.klen = round_k(K);
-    p.vecA = (K % 4 == 0) && (lda % 4 == 0) && aligned16(x) && small_enough(M, lda);     // KCONTIG: k extent K
-    p.vecB = (N % 4 == 0) && aligned16(w) && small_enough(K, N);     // ICONTIG: ld = N, i extent N
+    GemmParams p = dense_fwd_params(x, w, bias, y, M, K, N, ldx);
     const bool eq_stage = act == 5 && act_done && aux && out2 && out3 && g_tune[TUNE_EQ_EPILOGUES] && (N % 2 == 0) &&
                           aligned16(aux) && aligned16(out2) && aligned16(out3);
     if (eq_stage) { p.aux = aux; p.out2 = out2; p.out3 = out3; }
-    if (g_tune[TUNE_FEWROW] && g_tune[TUNE_SKINNY] > 0 && fewrow_ng(p) && aligned16(y)) {
-        // few rows, K = 640 / 896: every operand of a 16x16 tile requested at once, no LDS staging (fewrow.h)
-        if (eq_stage) {
-            *act_done = true;
-            return launch_fewrow<OP_ICONTIG, 5, TAG_DENSE_FWD>(p, s);
-        }
-        if (act == 2 && act_done && g_tune[TUNE_EQ_EPILOGUES]) {
-            *act_done = true;
-            return launch_fewrow<OP_ICONTIG, 2, TAG_DENSE_FWD>(p, s);
-        }
-        return launch_fewrow<OP_ICONTIG, 1, TAG_DENSE_FWD>(p, s);
+    // the element-wise stage the caller asks for, and the one a tile family carries: the few-row and skinny tiles from knob
+    // level 1, the 48x64 tiles from level 2.  *act_done is set exactly when the launch carries a stage.
+    const int asked = eq_stage ? 5 : (act == 2 && act_done) ? 2 : 1;
+    const auto stage_from = [&](int level) {
+        const int st = g_tune[TUNE_EQ_EPILOGUES] >= level ? asked : 1;
+        if (st != 1) *act_done = true;
+        return st;
+    };
+    // few rows, K = 640 / 896: every operand of a 16x16 tile requested at once, no LDS staging (fewrow.h)
+    if (g_tune[TUNE_FEWROW] && g_tune[TUNE_SKINNY] > 0 && fewrow_ng(p) && aligned16(y)) switch (stage_from(1)) {
+        case 5: return launch_fewrow<OP_ICONTIG, 5, TAG_DENSE_FWD>(p, s);
+        case 2: return launch_fewrow<OP_ICONTIG, 2, TAG_DENSE_FWD>(p, s);
+        default: return launch_fewrow<OP_ICONTIG, 1, TAG_DENSE_FWD>(p, s);
     }
-    if (skinny_ok(p)) {
-        if (eq_stage) {
-            *act_done = true;
-            return skinny_launch<OP_KCONTIG, OP_ICONTIG, TAG_DENSE_FWD, 5>(1, p, s);
-        }
-        if (act == 2 && act_done && g_tune[TUNE_EQ_EPILOGUES]) {
-            *act_done = true;
-            return skinny_launch<OP_KCONTIG, OP_ICONTIG, TAG_DENSE_FWD, 2>(1, p, s);
-        }
-        return skinny_launch<OP_KCONTIG, OP_ICONTIG, TAG_DENSE_FWD>(g_tune[TUNE_SKINNY], p, s);
+    // (skinny_launch: a stage runs on variant 1 whatever the knob says)
+    if (skinny_ok(p)) switch (stage_from(1)) {
+        case 5: return skinny_launch<OP_KCONTIG, OP_ICONTIG, TAG_DENSE_FWD, 5>(g_tune[TUNE_SKINNY], p, s);
+        case 2: return skinny_launch<OP_KCONTIG, OP_ICONTIG, TAG_DENSE_FWD, 2>(g_tune[TUNE_SKINNY], p, s);
+        default: return skinny_launch<OP_KCONTIG, OP_ICONTIG, TAG_DENSE_FWD>(g_tune[TUNE_SKINNY], p, s);
     }
     // small layers (64x64 tiles would leave CUs without a block: 1170x640 = 190 tiles): the 48x64 tiles of the fused
     // kernel, loads two k-tiles ahead
-    if (g_tune[TUNE_DENSE_FWD_PLAIN] && p.vecA && p.vecB && (K % 4 == 0) && (N % 4 == 0) && K >= 128 &&
-        (long long)ceil_div(M, 128) * ceil_div(N, 128) < 2 * kCUs) {
-        if (eq_stage && g_tune[TUNE_EQ_EPILOGUES] >= 2) {
-            *act_done = true;
-            return launch_gemm16<OP_KCONTIG, OP_ICONTIG, 1, 4, 3, 1, 64, 1, 0, TAG_DENSE_FWD, 2, 5>(p, 1, s);
-        }
-        if (act == 2 && act_done && g_tune[TUNE_EQ_EPILOGUES] >= 2) {
-            *act_done = true;                       // tanh in the store of the same tiles
-            return launch_gemm16<OP_KCONTIG, OP_ICONTIG, 1, 4, 3, 1, 64, 1, 0, TAG_DENSE_FWD, 2, 2>(p, 1, s);
-        }
-        return launch_gemm16<OP_KCONTIG, OP_ICONTIG, 1, 4, 3, 1, 64, 1, 0, TAG_DENSE_FWD, 2>(p, 1, s);
+    if (g_tune[TUNE_DENSE_FWD_PLAIN] && vec_both(p) && (K % 4 == 0) && (N % 4 == 0) && K >= 128 &&
+        (long long)ceil_div(M, 128) * ceil_div(N, 128) < 2 * kCUs) switch (stage_from(2)) {
+        case 5: return dense48_launch<5>(p, s);
+        case 2: return dense48_launch<2>(p, s);
+        default: return dense48_launch<1>(p, s);
     }
     return launch_gemm<OP_KCONTIG, OP_ICONTIG, 0, TAG_DENSE_FWD>(p, 1, s);
-}
-
-static GemmParams dense_bwd_x_params(const float* dy, const float* w, float* dx, int M, int K, int N) {
-    GemmParams p = gp_zero();                 // dx[M,K] = dy[M,N] . w[K,N]^T
-    p.A = dy; p.B = w; p.C = dx;
-    p.M = M; p.N = K; p.K = N;
-    p.lda = N; p.ldb = N; p.ldc = K;
-    p.klen = round_k(N);
-    p.vecA = (N % 4 == 0) && aligned16(dy) && small_enough(M, N);
-    p.vecB = (N % 4 == 0) && aligned16(w) && small_enough(K, N);
-    return p;
 }
 
 int dense_bwd_x_impl(const float* dy, const float* w, float* dx, int M, int K, int N, hipStream_t s) {
@@ -262,14 +323,8 @@ int dense_bwd_w_impl(const float* x, const float* dy, float* dw, float* dbias, i
     Carver c(ws, ws_bytes);
     SlabWs sw;
     if (!slab_carve(c, sp.splits, K, N, &sw)) return DCCN_ERR_WORKSPACE;
-    GemmParams p = gp_zero();                 // dw[K,N] = x[M,K]^T . dy[M,N]
-    p.A = x; p.B = dy;
-    p.M = K; p.N = N; p.K = M;
-    p.lda = ldx > 0 ? ldx : K; p.ldb = N; p.ldc = N;
+    GemmParams p = dense_bwd_w_params(x, dy, M, K, N, ldx);
     p.klen = sp.klen;
-    p.slab = sw.slab;
-    p.vecA = (K % 4 == 0) && (p.lda % 4 == 0) && aligned16(x) && small_enough(M, p.lda);
-    p.vecB = (N % 4 == 0) && aligned16(dy) && small_enough(M, N);
     if (defer) *defer = deferred_slabs(sw, false, false);
     if (sp.splits == 1) {
         p.C = dw;
@@ -293,26 +348,23 @@ int dense_bwd_w_impl(const float* x, const float* dy, float* dw, float* dbias, i
     return DCCN_OK;
 }
 
-static int dense_bwd16_launch(int variant, const GemmParams& px, const GemmParams& pw, int splits, hipStream_t s) {
-    const size_t sm = tune_smem_min();
-    switch (variant) {
-        case 1: return launch_dense_bwd16<2, 2, 2, 2, 32, 2, 2, 2, 2>(px, pw, splits, s, sm);     // dX 64x64, dW 64x64
-        case 2: return launch_dense_bwd16<1, 4, 3, 1, 32, 2, 2, 2, 2>(px, pw, splits, s, sm);     // dX 48x64
-        case 3: return launch_dense_bwd16<2, 2, 2, 2, 64, 2, 2, 2, 2>(px, pw, splits, s, sm);     // 64-deep k-tiles
-        case 4: return launch_dense_bwd16<2, 2, 3, 2, 32, 2, 2, 2, 2>(px, pw, splits, s, sm);     // dX 96x64
-        case 5: return launch_dense_bwd16<2, 2, 2, 4, 32, 2, 2, 2, 4>(px, pw, splits, s, sm);     // 64x128 both
-        case 6: return launch_dense_bwd16<2, 2, 2, 2, 32, 2, 2, 2, 4>(px, pw, splits, s, sm);     // dX 64x64, dW 64x128
-        default: return DCCN_ERR_INVALID_ARG;
-    }
+// TUNE_DENSE_BWD 1-6: the dX and the dW tiles of the grouped gemm16 launch (one k-tile depth for both: x.bk)
+struct DenseBwd16Cfg { Tile16Cfg x, w; };
+constexpr DenseBwd16Cfg kDenseBwd16[7] = {{},
+    {{2, 2, 2, 2, 32, 1}, {2, 2, 2, 2, 32, 1}},     // dX 64x64, dW 64x64
+    {{1, 4, 3, 1, 32, 1}, {2, 2, 2, 2, 32, 1}},     // dX 48x64
+    {{2, 2, 2, 2, 64, 1}, {2, 2, 2, 2, 64, 1}},     // 64-deep k-tiles
+    {{2, 2, 3, 2, 32, 1}, {2, 2, 2, 2, 32, 1}},     // dX 96x64
+    {{2, 2, 2, 4, 32, 1}, {2, 2, 2, 4, 32, 1}},     // 64x128 both
+    {{2, 2, 2, 2, 32, 1}, {2, 2, 2, 4, 32, 1}}};    // dX 64x64, dW 64x128
+template <int V>
+static int dense_bwd16_launch(const GemmParams& px, const GemmParams& pw, int splits, hipStream_t s) {
+    constexpr Tile16Cfg x = kDenseBwd16[V].x, w = kDenseBwd16[V].w;
+    static_assert(x.bk == w.bk, "one k-tile depth for the dX and the dW tiles");
+    return launch_dense_bwd16<x.wgm, x.wgn, x.tm, x.tn, x.bk, w.wgm, w.wgn, w.tm, w.tn>(px, pw, splits, s, tune_smem_min());
 }
-static int dense_bwd16_bk(int variant) { return variant == 3 ? 64 : 32; }
-static void dense_bwd16_tiles(int variant, int& xm, int& xn, int& wm, int& wn) {
-    xm = 64; xn = 64; wm = 64; wn = 64;
-    if (variant == 2) xm = 48;
-    if (variant == 4) xm = 96;
-    if (variant == 5) { xn = 128; wn = 128; }
-    if (variant == 6) wn = 128;
-}
+constexpr int (*kDenseBwd16Launch[7])(const GemmParams&, const GemmParams&, int, hipStream_t) = {nullptr,
+    dense_bwd16_launch<1>, dense_bwd16_launch<2>, dense_bwd16_launch<3>, dense_bwd16_launch<4>, dense_bwd16_launch<5>, dense_bwd16_launch<6>};
 
 // dense backward as ONE grouped launch: dx = dy.w^T together with the split-K slabs of dw = x^T.dy
 // (left un-reduced for the fused Adam kernel).  Falls back to two launches when the grouped
@@ -326,19 +378,12 @@ int dense_bwd_grouped_impl(const float* x, const float* dy, const float* w, floa
     if (!x || !dy || !w || !dx || !dw || !defer || M <= 0 || K <= 0 || N <= 0) return DCCN_ERR_INVALID_ARG;
     if (!ws || ws_bytes < splitk_ws_bytes(K, N, M)) return DCCN_ERR_WORKSPACE;
     GemmParams px = dense_bwd_x_params(dy, w, dx, M, K, N);
-    GemmParams pw = gp_zero();                // dw[K,N] = x[M,K]^T . dy[M,N]
-    pw.A = x; pw.B = dy;
-    pw.M = K; pw.N = N; pw.K = M;
-    pw.lda = K; pw.ldb = N; pw.ldc = N;
-    pw.slab = (long long)K * N;
-    pw.vecA = (K % 4 == 0) && aligned16(x) && small_enough(M, K);
-    pw.vecB = (N % 4 == 0) && aligned16(dy) && small_enough(M, N);
-    const bool vec = px.vecA && px.vecB && pw.vecA && pw.vecB;
+    GemmParams pw = dense_bwd_w_params(x, dy, M, K, N);       // (klen: the whole k range until a branch plans its split)
+    const bool vec = vec_both(px) && vec_both(pw);
     // few rows (the equaliser's 73-frame batch): dX on 16x64 tiles and the unsplit dW (k = the few rows: one or two
     // k-tiles) in ONE grid -- round 2 ran them as two launches of 6-10 us each, almost all of it launch ramp and drain
     if (g_tune[TUNE_SKINNY] > 0 && g_tune[TUNE_SKINNY_GROUPED] && vec && M <= 96 && (K % 4 == 0) && (N % 4 == 0)) {
-        pw.klen = round_k(M);
-        pw.C = dw; pw.colsum = dbias; pw.slab = 0;
+        pw.C = dw; pw.colsum = dbias; pw.slab = 0;       // (klen = the few rows, as built)
         // the dX tiles may carry an element-wise stage of the caller's graph: 3 = times (1 - aux^2) (tanh gradient),
         // 4 = plus aux (gradient accumulation): two 5 us launches of the equaliser step less
         const bool few = g_tune[TUNE_FEWROW] && fewrow_ng(px) != 0;        // dX on the one-latency 16x16 tiles of fewrow.h
@@ -359,14 +404,14 @@ int dense_bwd_grouped_impl(const float* x, const float* dy, const float* w, floa
     const int variant = g_tune[TUNE_DENSE_BWD] == kVariantKmajor ? 0 : g_tune[TUNE_DENSE_BWD];
     const long long big = (long long)ceil_div(M, 128) * ceil_div(K, 128);
     if (variant > 0 && vec && big < 2 * kCUs) {
-        int xm, xn, wm, wn;
-        dense_bwd16_tiles(variant, xm, xn, wm, wn);
-        const int nx = ceil_div(px.M, xm) * ceil_div(px.N, xn), tw = ceil_div(pw.M, wm) * ceil_div(pw.N, wn);
+        if (variant > 6) return DCCN_ERR_INVALID_ARG;       // (no such row; the carve below cannot fail after the size check above)
+        const Tile16Cfg cx = kDenseBwd16[variant].x, cw = kDenseBwd16[variant].w;
+        const int nx = ceil_div(px.M, cx.rows()) * ceil_div(px.N, cx.cols()), tw = ceil_div(pw.M, cw.rows()) * ceil_div(pw.N, cw.cols());
         int want = g_tune[TUNE_DENSE_BWD_SPLITS];
         if (want <= 0) want = (3 * kCUs - nx + tw / 2) / tw;            // about three resident blocks per CU in all
         const int cap = max_splits16(K, N);
         if (want > cap) want = cap;
-        const SplitPlan sp = plan_splitk_n(M, want, dense_bwd16_bk(variant));
+        const SplitPlan sp = plan_splitk_n(M, want, cx.bk);
         Carver c(ws, ws_bytes);
         SlabWs sw;
         if (!slab_carve(c, sp.splits, K, N, &sw)) return DCCN_ERR_WORKSPACE;
@@ -376,7 +421,7 @@ int dense_bwd_grouped_impl(const float* x, const float* dy, const float* w, floa
         } else {
             pw.C = sw.slabs; pw.colsum = dbias ? sw.colsum : nullptr;
         }
-        DCCN_TRY(dense_bwd16_launch(variant, px, pw, sp.splits, s));
+        DCCN_TRY(kDenseBwd16Launch[variant](px, pw, sp.splits, s));
         *defer = deferred_slabs(sw, dbias != nullptr, sp.splits > 1);
         return DCCN_OK;
     }
@@ -420,17 +465,25 @@ int dense_bwd_grouped_impl(const float* x, const float* dy, const float* w, floa
     return DCCN_OK;
 }
 
+// TUNE_CCONV_FWD 1-6: gemm16 tiles of the C-Conv forward
+constexpr Tile16Cfg kCconvFwd16[7] = {{},
+    {2, 2, 1, 4, 32, 1},      // 32x128
+    {1, 4, 2, 2, 32, 1},      // 32x128, wave 32x32
+    {1, 4, 1, 2, 32, 1},      // 16x128
+    {2, 2, 2, 2, 32, 1},      // 64x64
+    {1, 4, 1, 2, 32, 2},      // 16x128, 8 waves
+    {2, 2, 1, 2, 32, 1}};     // 32x64
+template <int V>
+static int cconv_fwd16_launch(const GemmParams& p, hipStream_t s) {
+    constexpr Tile16Cfg c = kCconvFwd16[V];
+    return launch_gemm16<OP_KCONTIG, OP_CCONV_W, c.wgm, c.wgn, c.tm, c.tn, c.bk, c.ks, 0, TAG_CCONV_FWD>(p, 1, s, tune_smem_min());
+}
+constexpr int (*kCconvFwd16Launch[7])(const GemmParams&, hipStream_t) = {nullptr,
+    cconv_fwd16_launch<1>, cconv_fwd16_launch<2>, cconv_fwd16_launch<3>, cconv_fwd16_launch<4>, cconv_fwd16_launch<5>, cconv_fwd16_launch<6>};
 int cconv_fwd_impl(const float* x, const float* w, const float* bias, float* out, int rows, int kin, int F,
                           hipStream_t s, int ldx) {
     if (!x || !w || !out || rows <= 0 || kin <= 0 || F <= 0) return DCCN_ERR_INVALID_ARG;
-    GemmParams p = gp_zero();                 // out[rows,2F] = x[rows,2kin] . Weff[2kin,2F]
-    p.A = x; p.B = w; p.C = out; p.bias = bias; p.cbias = 1;
-    p.M = rows; p.N = 2 * F; p.K = 2 * kin;
-    p.lda = ldx > 0 ? ldx : 2 * kin; p.ldb = 2 * F; p.ldc = 2 * F;
-    p.klen = round_k(2 * kin);
-    p.cF = F;
-    p.vecA = (kin % 2 == 0) && (p.lda % 4 == 0) && aligned16(x) && small_enough(rows, (long long)p.lda);
-    p.vecB = (F % 2 == 0) && aligned16(w) && small_enough(kin, 2LL * F);      // float2 loads of [Wa|Wb] rows
+    const GemmParams p = cconv_fwd_params(x, w, bias, out, rows, kin, F, ldx);
     const int variant = g_tune[TUNE_CCONV_FWD];
     const long long big = (long long)ceil_div(p.M, 128) * ceil_div(p.N, 128);
     // 7-11 (default 7): the staged whole-k tile of cconv_fwd.h (K = 160 / 128, i.e. N = 64 with / without the cyclic
@@ -444,33 +497,14 @@ int cconv_fwd_impl(const float* x, const float* w, const float* bias, float* out
         return launch_cconv_fwd_staged<4, 32, 128>(p, s);
     }
     if (variant >= 7) return launch_gemm<OP_KCONTIG, OP_CCONV_W, 0, TAG_CCONV_FWD>(p, 1, s);
-    if (variant > 0 && p.vecA && p.vecB && big < 2 * kCUs && kin % 2 == 0) {
-        const size_t sm = tune_smem_min();
-        switch (variant) {
-            case 1: return launch_gemm16<OP_KCONTIG, OP_CCONV_W, 2, 2, 1, 4, 32, 1, 0, TAG_CCONV_FWD>(p, 1, s, sm);   // 32x128
-            case 2: return launch_gemm16<OP_KCONTIG, OP_CCONV_W, 1, 4, 2, 2, 32, 1, 0, TAG_CCONV_FWD>(p, 1, s, sm);   // 32x128, wave 32x32
-            case 3: return launch_gemm16<OP_KCONTIG, OP_CCONV_W, 1, 4, 1, 2, 32, 1, 0, TAG_CCONV_FWD>(p, 1, s, sm);   // 16x128
-            case 4: return launch_gemm16<OP_KCONTIG, OP_CCONV_W, 2, 2, 2, 2, 32, 1, 0, TAG_CCONV_FWD>(p, 1, s, sm);   // 64x64
-            case 5: return launch_gemm16<OP_KCONTIG, OP_CCONV_W, 1, 4, 1, 2, 32, 2, 0, TAG_CCONV_FWD>(p, 1, s, sm);   // 16x128, 8 waves
-            case 6: return launch_gemm16<OP_KCONTIG, OP_CCONV_W, 2, 2, 1, 2, 32, 1, 0, TAG_CCONV_FWD>(p, 1, s, sm);   // 32x64
-            default: return DCCN_ERR_INVALID_ARG;
-        }
-    }
+    if (variant > 0 && vec_both(p) && big < 2 * kCUs && kin % 2 == 0) return kCconvFwd16Launch[variant](p, s);      // (1 .. 6 here)
     return launch_gemm<OP_KCONTIG, OP_CCONV_W, 0, TAG_CCONV_FWD>(p, 1, s);
 }
 
 int cconv_bwd_x_impl(const float* dout, const float* w, float* dx, int rows, int kin, int F, hipStream_t s,
                             int ldc) {
     if (!dout || !w || !dx || rows <= 0 || kin <= 0 || F <= 0) return DCCN_ERR_INVALID_ARG;
-    GemmParams p = gp_zero();                 // dx[rows,2kin] = dout[rows,2F] . Weff^T
-    p.A = dout; p.B = w; p.C = dx;
-    p.M = rows; p.N = 2 * kin; p.K = 2 * F;
-    p.lda = 2 * F; p.ldb = 2 * F; p.ldc = ldc > 0 ? ldc : 2 * kin;
-    p.klen = round_k(2 * F);
-    p.cF = F;
-    p.vecA = (F % 2 == 0) && aligned16(dout) && small_enough(rows, 2LL * F);
-    p.vecB = (F % 2 == 0) && aligned16(w) && small_enough(kin, 2LL * F);
-    return launch_gemm<OP_KCONTIG, OP_CCONV_WT, 0, TAG_CCONV_BWD_X>(p, 1, s);
+    return launch_gemm<OP_KCONTIG, OP_CCONV_WT, 0, TAG_CCONV_BWD_X>(cconv_bwd_x_params(dout, w, dx, rows, kin, F, ldc), 1, s);
 }
 
 // C-Conv fold and the tail's slab reduction in one launch: both are tiny, and the reduction has no consumer
@@ -511,12 +545,19 @@ __global__ __launch_bounds__(kGemmThreads) void cconv_bwd_w_km_finalize_kernel(c
 }
 
 constexpr int kCconvBwMaxSplits = 128;
-static void cconv_bw16_tiles(int variant, int& tm, int& tn) {
-    tm = 64; tn = 64;
-    if (variant == 2) tm = 32;
-    if (variant == 3) { tm = 80; tn = 128; }
-    if (variant == 4) { tm = 32; tn = 128; }
+// TUNE_CCONV_BWD_W 1-4: gemm16 tiles of the C-Conv weight gradient
+constexpr Tile16Cfg kCconvBw16[5] = {{},
+    {2, 2, 2, 2, 32, 1},      // 64x64
+    {2, 2, 1, 2, 32, 1},      // 32x64
+    {1, 4, 5, 2, 32, 1},      // 80x128
+    {2, 2, 1, 4, 32, 1}};     // 32x128
+template <int V>
+static int cconv_bw16_launch(const GemmParams& p, int splits, const TailFinalizeArgs& fin, hipStream_t s) {
+    constexpr Tile16Cfg c = kCconvBw16[V];
+    return launch_bwd_w16_finalize<c.wgm, c.wgn, c.tm, c.tn, c.bk>(p, splits, fin, s);
 }
+constexpr int (*kCconvBw16Launch[5])(const GemmParams&, int, const TailFinalizeArgs&, hipStream_t) = {nullptr,
+    cconv_bw16_launch<1>, cconv_bw16_launch<2>, cconv_bw16_launch<3>, cconv_bw16_launch<4>};
 // slab capacity of the C-Conv weight gradient: the legacy split plan, and at least kCconvBwMaxSplits slabs of a small output
 static int cconv_bw_capacity(int rows, int kin, int F) {
     const int legacy = splitk_capacity(2 * kin, 2 * F, rows);
@@ -534,8 +575,9 @@ int cconv_bwd_w_impl(const float* x, const float* dout, float* dw, float* dbias,
     if (!x || !dout || !dw || rows <= 0 || kin <= 0 || F <= 0) return DCCN_ERR_INVALID_ARG;
     if (!ws || ws_bytes < cconv_bw_ws_bytes(rows, kin, F)) return DCCN_ERR_WORKSPACE;
     const int variant = g_tune[TUNE_CCONV_BWD_W] == kVariantKmajor ? 0 : g_tune[TUNE_CCONV_BWD_W];
-    const bool v16 = variant > 0 && defer && fin && (kin % 2 == 0) && (F % 2 == 0) && aligned16(x) && aligned16(dout) &&
-                     small_enough(rows, 2LL * kin) && small_enough(rows, 2LL * F) && 4LL * kin * F <= 512 * 512;
+    GemmParams p = cconv_bwd_w_params(x, dout, rows, kin, F);
+    const bool v16 = variant > 0 && defer && fin && vec_both(p) && 4LL * kin * F <= 512 * 512;
+    if (v16 && variant > 4) return DCCN_ERR_INVALID_ARG;
     SplitPlan sp = plan_splitk(2 * kin, 2 * F, rows);
     if (!v16 && g_tune[TUNE_CCONV_BWD_SPLITS] > 0 && defer && fin && 4LL * kin * F <= 512 * 512) {
         const int want = g_tune[TUNE_CCONV_BWD_SPLITS];
@@ -543,37 +585,24 @@ int cconv_bwd_w_impl(const float* x, const float* dout, float* dw, float* dbias,
     }
     if (v16) {
         int want = g_tune[TUNE_CCONV_BWD_SPLITS];
-        int tm, tn;
-        cconv_bw16_tiles(variant, tm, tn);
-        const int tiles = ceil_div(2 * kin, tm) * ceil_div(2 * F, tn);
+        const Tile16Cfg c16 = kCconvBw16[variant];
+        const int tiles = ceil_div(2 * kin, c16.rows()) * ceil_div(2 * F, c16.cols());
         if (want <= 0) want = (2 * kCUs + tiles - 1) / tiles;
         if (want > kCconvBwMaxSplits) want = kCconvBwMaxSplits;
-        sp = plan_splitk_n(rows, want, 32);
+        sp = plan_splitk_n(rows, want, c16.bk);
     }
     Carver c(ws, ws_bytes);
     SlabWs sw;
     if (!slab_carve(c, sp.splits, 2 * kin, 2 * F, &sw)) return DCCN_ERR_WORKSPACE;
     float *slabs = sw.slabs, *cs = sw.colsum;
-    GemmParams p = gp_zero();                 // dWeff[2kin,2F] = x[rows,2kin]^T . dout[rows,2F]
-    p.A = x; p.B = dout; p.C = slabs; p.colsum = cs;
-    p.M = 2 * kin; p.N = 2 * F; p.K = rows;
-    p.lda = 2 * kin; p.ldb = 2 * F; p.ldc = 2 * F;
+    p.C = slabs; p.colsum = cs;
     p.klen = sp.klen;
-    p.slab = sw.slab;
-    p.vecA = (kin % 2 == 0) && aligned16(x) && small_enough(rows, 2LL * kin);
-    p.vecB = (F % 2 == 0) && aligned16(dout) && small_enough(rows, 2LL * F);
     if (v16) {
-        switch (variant) {
-            case 1: DCCN_TRY((launch_bwd_w16_finalize<2, 2, 2, 2, 32>(p, sp.splits, *fin, s))); break;     // 64x64
-            case 2: DCCN_TRY((launch_bwd_w16_finalize<2, 2, 1, 2, 32>(p, sp.splits, *fin, s))); break;     // 32x64
-            case 3: DCCN_TRY((launch_bwd_w16_finalize<1, 4, 5, 2, 32>(p, sp.splits, *fin, s))); break;     // 80x128
-            case 4: DCCN_TRY((launch_bwd_w16_finalize<2, 2, 1, 4, 32>(p, sp.splits, *fin, s))); break;     // 32x128
-            default: return DCCN_ERR_INVALID_ARG;
-        }
+        DCCN_TRY(kCconvBw16Launch[variant](p, sp.splits, *fin, s));
         *defer = fold_defer(sw);
         return DCCN_OK;
     }
-    if (defer && fin && p.vecA && p.vecB && (F % 2 == 0)) {
+    if (defer && fin && vec_both(p)) {
         // fused step: GEMM + tail finalize in one launch; the fold happens inside the optimizer kernel
         const int tiles = ceil_div(p.N, 64) * ceil_div(p.M, 64), gemm_blocks = tiles * sp.splits;
         const dim3 grid(gemm_blocks + tail_finalize_blocks(fin->P));
@@ -637,13 +666,9 @@ bool cconv_pair_ok(const float* x, const float* w, const float* o, int rows, int
 int cconv_fwd_grouped_impl(const float* x, const float* w, const float* bias, float* out, int rows, int kin, int F,
                                   int groups, long long gx, long long gw, long long gb, bool join_pairs, hipStream_t s) {
     if (!x || !w || !out || rows <= 0 || groups < 1 || groups > 2 || (join_pairs && groups != 2)) return DCCN_ERR_INVALID_ARG;
-    GemmParams p = gp_zero();                 // out_g[rows,2F] = x_g[rows,2kin] . Weff_g[2kin,2F]
-    p.A = x; p.B = w; p.C = out; p.bias = bias; p.cbias = 1;
-    p.M = rows; p.N = 2 * F; p.K = 2 * kin;
-    p.lda = 2 * kin; p.ldb = 2 * F; p.ldc = join_pairs ? 4 * F : 2 * F;
-    p.klen = round_k(2 * kin);
-    p.cF = F;
-    p.vecA = 1; p.vecB = 1;
+    // group 0's operands (cconv_pair_ok: the strides keep every group's as legal)
+    const GemmParams p = cconv_fwd_params(x, w, bias, out, rows, kin, F, 0, join_pairs ? 4 * F : 0);
+    if (!vec_both(p)) return DCCN_ERR_INVALID_ARG;
     GroupStride gs;
     gs.a = gx; gs.b = gw; gs.bias = gb; gs.colsum = 0;
     gs.c = join_pairs ? 2 : (long long)rows * 2 * F;
@@ -675,22 +700,13 @@ int cconv_bwd_grouped_impl(const float* x, const float* dout, const float* w, fl
     Carver c(ws, per_bytes);
     SlabWs sw;
     if (!slab_carve(c, sp.splits, 2 * kin, 2 * F, &sw)) return DCCN_ERR_WORKSPACE;
-    GemmParams px = gp_zero();                // dx[rows,2kin] = dout[rows,2F] . Weff^T
-    px.A = dout; px.B = w; px.C = dx;
-    px.M = rows; px.N = 2 * kin; px.K = 2 * F;
-    px.lda = 2 * F; px.ldb = 2 * F; px.ldc = 2 * kin;
-    px.klen = round_k(2 * F);
-    px.cF = F;
-    px.vecA = 1; px.vecB = 1;
+    const GemmParams px = cconv_bwd_x_params(dout, w, dx, rows, kin, F);
     GroupStride g1;
     g1.a = gd; g1.b = gw; g1.c = gx; g1.bias = 0; g1.colsum = 0;
-    GemmParams pw = gp_zero();                // dWeff[2kin,2F] = x[rows,2kin]^T . dout[rows,2F]
-    pw.A = x; pw.B = dout; pw.C = sw.slabs; pw.colsum = sw.colsum;
-    pw.M = 2 * kin; pw.N = 2 * F; pw.K = rows;
-    pw.lda = 2 * kin; pw.ldb = 2 * F; pw.ldc = 2 * F;
+    GemmParams pw = cconv_bwd_w_params(x, dout, rows, kin, F);
+    pw.C = sw.slabs; pw.colsum = sw.colsum;
     pw.klen = sp.klen;
-    pw.slab = sw.slab;
-    pw.vecA = 1; pw.vecB = 1;
+    if (!vec_both(px) || !vec_both(pw)) return DCCN_ERR_INVALID_ARG;
     if (!kmajor_ok(pw)) return DCCN_ERR_STATE;
     GroupStride g2;
     g2.a = gx; g2.b = gd; g2.c = (long long)per; g2.bias = 0; g2.colsum = (long long)per;
@@ -723,7 +739,10 @@ static bool rx_bwd_fused_ok(int batch, int S, int kin, int F, int D, const float
     if (!g_tune[TUNE_FUSED_BWD] || g_tune[TUNE_DENSE_BWD] != kVariantKmajor) return false;
     if ((2 * F) % 64 != 0 || (2 * kin != 128 && 2 * kin != 160)) return false;
     if (dN % 4 != 0 || !aligned16(x_norm) || !aligned16(fft_out) || !aligned16(dz) || !aligned16(wd)) return false;
-    if (!small_enough(batch, (long long)S * 2 * kin) || !small_enough(batch, dK) || !small_enough(dK, dN)) return false;
+    // (batch x dN: dz, the dW items' B operand -- a short, very wide dense layer under a long batch can pass every test below)
+    if (!small_enough(batch, (long long)S * 2 * kin) || !small_enough(batch, dK) || !small_enough(dK, dN) ||
+        !small_enough(batch, dN))
+        return false;
     const long long big = (long long)ceil_div(batch, 128) * ceil_div(dK, 128);
     if (big >= 2 * kCUs) return false;
     const SplitPlan sp = dense_dw_plan(batch, dK, dN, kFusedBwdRangeRows);
@@ -739,12 +758,8 @@ static int rx_bwd_fused_impl(const float* x_norm, const float* fft_out, const fl
     if (!ws_dense || ws_dense_bytes < splitk_ws_bytes(dK, dN, batch)) return DCCN_ERR_WORKSPACE;
     if (!ws_conv || ws_conv_bytes < rx_bwd_fused_ws_bytes(batch, S, kin, F)) return DCCN_ERR_WORKSPACE;
     GemmParams px = dense_bwd_x_params(dz, wd, dfft, batch, dK, dN);
-    GemmParams pw = gp_zero();                // dw[K,N] = x[M,K]^T . dy[M,N]
-    pw.A = fft_out; pw.B = dz;
-    pw.M = dK; pw.N = dN; pw.K = batch;
-    pw.lda = dK; pw.ldb = dN; pw.ldc = dN;
-    pw.slab = (long long)dK * dN;
-    pw.vecA = 1; pw.vecB = 1;
+    GemmParams pw = dense_bwd_w_params(fft_out, dz, batch, dK, dN);
+    if (!vec_both(pw)) return DCCN_ERR_INVALID_ARG;             // (rx_bwd_fused_ok asks for exactly these)
     const SplitPlan sp = dense_dw_plan(batch, dK, dN, kFusedBwdRangeRows);
     pw.klen = sp.klen;
     int nsplit = sp.splits;
@@ -870,10 +885,6 @@ int tail_impl(bool bwd, const float* z, const int32_t* bits, const float* tailp,
 // dense forward with the tail fused into its epilogue (gemm16.h EPI_TAIL: register layout for nbits <= 2, tile staged
 // through LDS for nbits >= 3)
 // ---------------------------------------------------------------------------------------
-static void dense_tail_tiles(int variant, int& bm, int& bn) {
-    bn = 64;
-    bm = variant == 13 ? 80 : 48;
-}
 static int dense_tail_max_blocks(int M, int N) {
     const int b = ceil_div(M, 32) * ceil_div(N, 64);
     // few rows: the one-latency 16x16 tiles of fewrow.h carry the tail as well (one slab per tile)
@@ -901,13 +912,51 @@ bool dense_tail_planned(int nbits, bool train, int M, int N) {
     return (nbits == 4 && train) ? (k & 2) != 0 : (k & 1) != 0;
 }
 
-// the two tile shapes the fused dense + tail launch runs, at every nbits: 48x64 with loads two k-tiles ahead (small layers),
-// 80x64 (large layers)
+// The grid a fused dense forward runs, decided ONCE for dense_tail_impl and dense_decide_impl (nbits <= 2): both launch the
+// same tiles over the same rows, so z -- and with it every decision -- has the bits the evaluation step computes
+enum DenseGrid : int { DG_TILES = 0, DG_FEWROW, DG_RAGGED };
+struct DenseRoute {
+    DenseGrid grid;
+    bool large;         // DG_TILES: 80x64 tiles, else 48x64
+    int rag;            // DG_RAGGED: rows of the short last tile row
+    int blocks;         // blocks of the launch (the tail writes one slab each)
+};
+static DenseRoute dense_tail_route(const GemmParams& p, int nbits) {
+    const int M = p.M, N = p.N, ncol = ceil_div(N, 64);
+    DenseRoute r{};
+    // large layers (several rounds of 48x64 tiles): 80x64 tiles re-use the B tile for five row blocks instead of three
+    // (C4: 1.42 -> 1.34 ms); the lane's ten cells go through the tail in two batches of five
+    r.large = (long long)ceil_div(M, kDense48.rows()) * ncol >= 4LL * kCUs;
+    // 80x64 tiles over a row count that leaves <= 32 rows for the last tile row (C4: 585 = 7 x 80 + 25): that row as 32x64 blocks
+    constexpr int R = kDense80.rows();
+    const int rag = (r.large && nbits <= 2 && g_tune[TUNE_DENSE_RAGGED] && M > R) ? M % R : 0;
+    // few rows, BPSK / QPSK: every operand of a 16x16 tile requested at once, the tail on the tile's own registers (fewrow.h)
+    const int few_tiles = ceil_div(M, 16) * (N / 16);
+    const bool few = g_tune[TUNE_FEWROW] && g_tune[TUNE_SKINNY] > 0 && nbits <= 2 && M <= 96 && fewrow_ng_c(p, false) >= 10 &&
+                     few_tiles <= kTailBlocksMax && few_tiles <= dense_tail_max_blocks(M, N);
+    if (rag > 0 && rag <= kDense32.rows()) {
+        r.grid = DG_RAGGED; r.rag = rag; r.blocks = ((M - rag) / R) * ncol + ncol;
+    } else if (few) {
+        r.grid = DG_FEWROW; r.blocks = few_tiles;
+    } else {
+        r.grid = DG_TILES; r.blocks = ceil_div(M, r.large ? R : kDense48.rows()) * ncol;
+    }
+    return r;
+}
+// the last `rag` rows of p as a description of their own (A and C advanced); p keeps the rows in front of them
+static GemmParams split_last_rows(GemmParams& p, int rag) {
+    GemmParams q = p;
+    p.M -= rag;
+    q.M = rag; q.A = p.A + (size_t)p.M * p.lda; q.C = p.C ? p.C + (size_t)p.M * p.ldc : nullptr;
+    return q;
+}
+
 template <int NB, bool BWD>
-static int dense_tail_launch(int variant, const GemmParams& p, const TailEpiParams& tp, hipStream_t s) {
+static int dense_tail_launch(bool large, const GemmParams& p, const TailEpiParams& tp, hipStream_t s) {
+    constexpr Tile16Cfg a = kDense48, b = kDense80;
     const size_t sm = tune_smem_min();
-    if (variant == 13) return launch_dense_tail16<1, 4, 5, 1, 64, 1, NB, BWD, 2>(p, tp, s, sm);    // 80x64 (large layers)
-    return launch_dense_tail16<1, 4, 3, 1, 64, 1, NB, BWD, 2>(p, tp, s, sm);                        // 48x64
+    if (large) return launch_dense_tail16<b.wgm, b.wgn, b.tm, b.tn, b.bk, b.ks, NB, BWD, 2>(p, tp, s, sm);
+    return launch_dense_tail16<a.wgm, a.wgn, a.tm, a.tn, a.bk, a.ks, NB, BWD, 2>(p, tp, s, sm);
 }
 
 // z nullable (not materialised then).  defer: as tail_impl.
@@ -920,55 +969,38 @@ int dense_tail_impl(bool bwd, const float* x, const float* w, const float* bias,
     if (bwd && (!dz || !dtailp)) return DCCN_ERR_INVALID_ARG;
     if (!dense_tail_ok(x, w, M, K, N, nbits)) return DCCN_ERR_INVALID_ARG;
     if (!ws || ws_bytes < dense_tail_ws_bytes(M, N, nbits)) return DCCN_ERR_WORKSPACE;
-    // large layers (several rounds of 48x64 tiles): 80x64 tiles re-use the B tile for five row blocks instead of three
-    // (C4: 1.42 -> 1.34 ms); the lane's ten cells go through the tail in two batches of five
-    const int variant = ((long long)ceil_div(M, 48) * ceil_div(N, 64) >= 4LL * kCUs) ? 13 : 9;
-    int bm, bn;
-    dense_tail_tiles(variant, bm, bn);
-    const int nblk = ceil_div(M, bm) * ceil_div(N, bn);
+    const GemmParams p = dense_fwd_params(x, w, bias, z, M, K, N);
+    if (!vec_both(p)) return DCCN_ERR_INVALID_ARG;          // (dense_tail_ok asks for exactly these)
+    const DenseRoute r = dense_tail_route(p, nbits);
     Carver c(ws, ws_bytes);
     const TailWs tw = tail_carve(c, (size_t)dense_tail_max_blocks(M, N), nbits);
-    GemmParams p = gp_zero();
-    p.A = x; p.B = w; p.C = z; p.bias = bias;
-    p.M = M; p.N = N; p.K = K;
-    p.lda = K; p.ldb = N; p.ldc = N;
-    p.klen = round_k(K);
-    p.vecA = 1; p.vecB = 1;
     const long long cells = (long long)M * (N / 2);
     TailEpiParams tp;
     tp.bits = bits; tp.tailp = tailp; tp.prob = prob; tp.dz = dz; tp.blk_metrics = tw.blk_metrics; tp.blk_grads = tw.blk_grads;
     tp.inv_count = 1.0f / (float)(cells * nbits);
-    // few rows, BPSK / QPSK: every operand of a 16x16 tile requested at once, the tail on the tile's own registers (fewrow.h)
-    const int few_tiles = ceil_div(M, 16) * (N / 16);
-    const bool few = g_tune[TUNE_FEWROW] && g_tune[TUNE_SKINNY] > 0 && nbits <= 2 && M <= 96 && fewrow_ng_c(p, false) >= 10 &&
-                     few_tiles <= kTailBlocksMax && few_tiles <= dense_tail_max_blocks(M, N);
     int st;
-    // 80x64 tiles over a row count that leaves <= 32 rows for the last tile row (C4: 585 = 7 x 80 + 25): that row as 32x64 blocks
-    const int rag = (variant == 13 && nbits <= 2 && g_tune[TUNE_DENSE_RAGGED] && M > 80) ? M % 80 : 0;
-    if (rag > 0 && rag <= 32) {
-        const int M1 = M - rag;
-        GemmParams p1 = p, p2 = p;
-        TailEpiParams t1 = tp, t2 = tp;
-        p1.M = M1;
-        p2.M = rag; p2.A = p.A + (size_t)M1 * p.lda; p2.C = p.C ? p.C + (size_t)M1 * p.ldc : nullptr;
+    if (r.grid == DG_RAGGED) {                      // (nbits <= 2)
+        GemmParams p1 = p;
+        const GemmParams p2 = split_last_rows(p1, r.rag);
+        const int M1 = p1.M;
+        TailEpiParams t2 = tp;
         t2.bits = tp.bits + (size_t)M1 * (N / 2) * nbits;
         t2.prob = tp.prob ? tp.prob + (size_t)M1 * (N / 2) * nbits * 2 : nullptr;
         t2.dz = tp.dz ? tp.dz + (size_t)M1 * N : nullptr;
+        constexpr Tile16Cfg c80 = kDense80, c32 = kDense32;       // (the two-shape grid, as in dense_decide_impl)
         const size_t sm = tune_smem_min();
-        if (nbits == 1) st = bwd ? launch_dense_tail16_ragged<5, 2, 64, 1, true, 2>(p1, t1, p2, t2, s, sm) : launch_dense_tail16_ragged<5, 2, 64, 1, false, 2>(p1, t1, p2, t2, s, sm);
-        else st = bwd ? launch_dense_tail16_ragged<5, 2, 64, 2, true, 2>(p1, t1, p2, t2, s, sm) : launch_dense_tail16_ragged<5, 2, 64, 2, false, 2>(p1, t1, p2, t2, s, sm);
-        DCCN_TRY(st);
-        const int nrag = (M1 / 80) * ceil_div(N, 64) + ceil_div(N, 64);
-        return tail_finish(tail_finalize_args(tw, nrag, bwd, nbits, cells, metrics, dtailp, pp, power_out), defer, s);
+        if (nbits == 1) st = bwd ? launch_dense_tail16_ragged<c80.tm, c32.tm, c80.bk, 1, true, 2>(p1, tp, p2, t2, s, sm) : launch_dense_tail16_ragged<c80.tm, c32.tm, c80.bk, 1, false, 2>(p1, tp, p2, t2, s, sm);
+        else st = bwd ? launch_dense_tail16_ragged<c80.tm, c32.tm, c80.bk, 2, true, 2>(p1, tp, p2, t2, s, sm) : launch_dense_tail16_ragged<c80.tm, c32.tm, c80.bk, 2, false, 2>(p1, tp, p2, t2, s, sm);
+    } else if (r.grid == DG_FEWROW) {               // (nbits <= 2)
+        if (nbits == 1) st = bwd ? launch_fewrow_tail<1, true>(p, tp, s) : launch_fewrow_tail<1, false>(p, tp, s);
+        else st = bwd ? launch_fewrow_tail<2, true>(p, tp, s) : launch_fewrow_tail<2, false>(p, tp, s);
     }
-    if (few && nbits == 1) st = bwd ? launch_fewrow_tail<1, true>(p, tp, s) : launch_fewrow_tail<1, false>(p, tp, s);
-    else if (few && nbits == 2) st = bwd ? launch_fewrow_tail<2, true>(p, tp, s) : launch_fewrow_tail<2, false>(p, tp, s);
-    else if (nbits == 1) st = bwd ? dense_tail_launch<1, true>(variant, p, tp, s) : dense_tail_launch<1, false>(variant, p, tp, s);
-    else if (nbits == 2) st = bwd ? dense_tail_launch<2, true>(variant, p, tp, s) : dense_tail_launch<2, false>(variant, p, tp, s);
-    else if (nbits == 3) st = bwd ? dense_tail_launch<3, true>(variant, p, tp, s) : dense_tail_launch<3, false>(variant, p, tp, s);
-    else st = bwd ? dense_tail_launch<4, true>(variant, p, tp, s) : dense_tail_launch<4, false>(variant, p, tp, s);
+    else if (nbits == 1) st = bwd ? dense_tail_launch<1, true>(r.large, p, tp, s) : dense_tail_launch<1, false>(r.large, p, tp, s);
+    else if (nbits == 2) st = bwd ? dense_tail_launch<2, true>(r.large, p, tp, s) : dense_tail_launch<2, false>(r.large, p, tp, s);
+    else if (nbits == 3) st = bwd ? dense_tail_launch<3, true>(r.large, p, tp, s) : dense_tail_launch<3, false>(r.large, p, tp, s);
+    else st = bwd ? dense_tail_launch<4, true>(r.large, p, tp, s) : dense_tail_launch<4, false>(r.large, p, tp, s);
     DCCN_TRY(st);
-    return tail_finish(tail_finalize_args(tw, few ? few_tiles : nblk, bwd, nbits, cells, metrics, dtailp, pp, power_out), defer, s);
+    return tail_finish(tail_finalize_args(tw, r.blocks, bwd, nbits, cells, metrics, dtailp, pp, power_out), defer, s);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1000,8 +1032,8 @@ int decide_impl(const float* z, const float* tailp, unsigned char* packed, float
     return DCCN_OK;
 }
 
-// Dense forward + decision.  The plan mirrors dense_tail_impl launch for launch (few-row tiles, 48x64, 80x64, the ragged
-// two-shape grid), so z -- and with it every decision -- has the bits the evaluation step computes for the same operands.
+// Dense forward + decision on the grid dense_tail_route gives dense_tail_impl for the same operands (few-row tiles, 48x64,
+// 80x64, the ragged two-shape grid).
 // nbits <= 2: ONE launch, z nullable.  nbits >= 3: the 48x64 tiles store z (same k order as the LDS-staged tail of the fused
 // evaluation launch), the stand-alone decision kernel follows; z must be given.
 int dense_decide_impl(const float* x, const float* w, const float* bias, float* z, const float* tailp, unsigned char* packed,
@@ -1011,39 +1043,31 @@ int dense_decide_impl(const float* x, const float* w, const float* bias, float* 
     if (!dense_tail_ok(x, w, M, K, N, nbits)) return DCCN_ERR_INVALID_ARG;
     if (nbits >= 3 && !z) return DCCN_ERR_INVALID_ARG;
     if (!decide_outputs_aligned(llr, prob, nbits)) return DCCN_ERR_INVALID_ARG;
-    GemmParams p = gp_zero();
-    p.A = x; p.B = w; p.C = z; p.bias = bias;
-    p.M = M; p.N = N; p.K = K;
-    p.lda = K; p.ldb = N; p.ldc = N;
-    p.klen = round_k(K);
-    p.vecA = 1; p.vecB = 1;
+    const GemmParams p = dense_fwd_params(x, w, bias, z, M, K, N);
+    if (!vec_both(p)) return DCCN_ERR_INVALID_ARG;          // (dense_tail_ok asks for exactly these)
+    const size_t sm = tune_smem_min();
     if (nbits >= 3) {
-        DCCN_TRY((launch_gemm16<OP_KCONTIG, OP_ICONTIG, 1, 4, 3, 1, 64, 1, 0, TAG_DENSE_FWD, 2>(p, 1, s, tune_smem_min())));
+        DCCN_TRY(dense48_launch(p, s, sm));
         return decide_impl(z, tailp, packed, llr, prob, M, N / 2, nbits, s);
     }
     DecideEpiParams dq;
     dq.tailp = tailp; dq.packed = packed; dq.llr = llr; dq.prob = prob; dq.RB = decide_row_bytes(N / 2, nbits);
-    const int variant = ((long long)ceil_div(M, 48) * ceil_div(N, 64) >= 4LL * kCUs) ? 13 : 9;
-    const int few_tiles = ceil_div(M, 16) * (N / 16);
-    const bool few = g_tune[TUNE_FEWROW] && g_tune[TUNE_SKINNY] > 0 && M <= 96 && fewrow_ng_c(p, false) >= 10 &&
-                     few_tiles <= kTailBlocksMax && few_tiles <= dense_tail_max_blocks(M, N);
-    const size_t sm = tune_smem_min();
-    const int rag = (variant == 13 && g_tune[TUNE_DENSE_RAGGED] && M > 80) ? M % 80 : 0;
-    if (rag > 0 && rag <= 32) {
-        const int M1 = M - rag;
-        GemmParams p1 = p, p2 = p;
-        DecideEpiParams d1 = dq, d2 = dq;
-        p1.M = M1;
-        p2.M = rag; p2.A = p.A + (size_t)M1 * p.lda; p2.C = p.C ? p.C + (size_t)M1 * p.ldc : nullptr;
+    const DenseRoute r = dense_tail_route(p, nbits);
+    constexpr Tile16Cfg c48 = kDense48, c80 = kDense80, c32 = kDense32;
+    if (r.grid == DG_RAGGED) {
+        GemmParams p1 = p;
+        const GemmParams p2 = split_last_rows(p1, r.rag);
+        const int M1 = p1.M;
+        DecideEpiParams d2 = dq;
         d2.packed = dq.packed + (size_t)M1 * dq.RB;
         d2.llr = dq.llr ? dq.llr + (size_t)M1 * (N / 2) * nbits : nullptr;
         d2.prob = dq.prob ? dq.prob + (size_t)M1 * (N / 2) * nbits * 2 : nullptr;
-        return nbits == 1 ? launch_dense_decide16_ragged<5, 2, 64, 1, 2>(p1, d1, p2, d2, s, sm)
-                          : launch_dense_decide16_ragged<5, 2, 64, 2, 2>(p1, d1, p2, d2, s, sm);
+        return nbits == 1 ? launch_dense_decide16_ragged<c80.tm, c32.tm, c80.bk, 1, 2>(p1, dq, p2, d2, s, sm)
+                          : launch_dense_decide16_ragged<c80.tm, c32.tm, c80.bk, 2, 2>(p1, dq, p2, d2, s, sm);
     }
-    if (few) return nbits == 1 ? launch_fewrow_decide<1>(p, dq, s) : launch_fewrow_decide<2>(p, dq, s);
-    if (variant == 13) return nbits == 1 ? launch_dense_decide16<5, 64, 1, 2>(p, dq, s, sm) : launch_dense_decide16<5, 64, 2, 2>(p, dq, s, sm);
-    return nbits == 1 ? launch_dense_decide16<3, 64, 1, 2>(p, dq, s, sm) : launch_dense_decide16<3, 64, 2, 2>(p, dq, s, sm);
+    if (r.grid == DG_FEWROW) return nbits == 1 ? launch_fewrow_decide<1>(p, dq, s) : launch_fewrow_decide<2>(p, dq, s);
+    if (r.large) return nbits == 1 ? launch_dense_decide16<c80.tm, c80.bk, 1, 2>(p, dq, s, sm) : launch_dense_decide16<c80.tm, c80.bk, 2, 2>(p, dq, s, sm);
+    return nbits == 1 ? launch_dense_decide16<c48.tm, c48.bk, 1, 2>(p, dq, s, sm) : launch_dense_decide16<c48.tm, c48.bk, 2, 2>(p, dq, s, sm);
 }
 
 // prep = false: the per-step bookkeeping (alpha, beta powers, global_step) already rode on an earlier kernel of the step

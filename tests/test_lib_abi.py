@@ -188,6 +188,52 @@ def test_short_workspace_is_refused_before_device_work(lib):
     assert len(got) == 41 and all(v == -2 for v in got.values()), {k: v for k, v in got.items() if v != -2}
 
 
+def test_fused_dense_forward_refuses_operands_that_are_not_vector_legal(lib):
+    """The fused dense forward (+ tail, + decision) runs on tiles without scalar loaders: x or w one float off a 16-byte
+    boundary, or a K that is no multiple of 4, is answered DCCN_ERR_INVALID_ARG (-1) before anything touches a device (host
+    buffers that a refused call never dereferences), and dccn_dense_tail_supported says the same of the shape.  The same
+    arguments with aligned operands pass the argument checks: with a workspace one byte short they get as far as
+    DCCN_ERR_WORKSPACE (-2)."""
+    store = (C.c_char * 8192)()
+    a = (C.addressof(store) + 255) // 256 * 256
+    p = C.c_void_p(a)
+    L = lib
+    M, K, N, nb = 36, 128, 64, 2
+    n = L.dccn_dense_tail_workspace_size(M, N, nb)
+    assert n > 0 and L.dccn_dense_tail_supported(M, K, N, nb) == 1 and L.dccn_dense_decide_supported(M, K, N, nb) == 1
+
+    def tails(x, w, k, nbytes):
+        return {"dense_tail_fwd": L.dccn_dense_tail_fwd(x, w, p, p, p, p, p, p, M, k, N, nb, p, nbytes, None),
+                "dense_tail_fwd_bwd": L.dccn_dense_tail_fwd_bwd(x, w, p, p, p, p, p, p, p, p, M, k, N, nb, p, nbytes, None)}
+
+    # (aligned operands: only the two calls that a short workspace stops -- dccn_dense_decide_fwd takes none and would launch)
+    got = tails(p, p, K, n - 1)
+    assert all(v == -2 for v in got.values()), got
+    off = C.c_void_p(a + 4)                                        # 4-byte aligned, not 16
+    for what, x, w, k in (("x off by one float", off, p, K), ("w off by one float", p, off, K), ("K = 130", p, p, 130)):
+        got = tails(x, w, k, n)
+        got["dense_decide_fwd"] = L.dccn_dense_decide_fwd(x, w, p, p, p, p, p, p, M, k, N, nb, None)
+        assert all(v == -1 for v in got.values()), (what, got)
+    assert L.dccn_dense_tail_supported(M, 130, N, nb) == 0
+
+
+def test_fused_backward_is_not_offered_where_dz_outgrows_the_fast_loaders(lib):
+    """The one-launch backward reads dz [batch, 2 D] through loaders with 32-bit byte offsets.  A short (S x 2 F = 64), very wide
+    dense layer under a long batch passes every tile-count test of the plan while dz is 2 GiB or more: the plan must not
+    offer the launch there (the step then takes the composed backward), and dccn_rx_backward refuses before any launch.  One
+    row less of D and dz fits: offered."""
+    from dl_ofdm_amd import _lib
+    wide = _lib.RxShape(65408, 1, 64, 32, 32704, 2)                 # dz: 65408 x 65408 floats = 16 GiB
+    assert 4 * wide.batch * 2 * wide.D >= 2 ** 31
+    assert lib.dccn_rx_bwd_fused_supported(C.byref(wide)) == 0
+    store = (C.c_char * 1024)()
+    p = C.c_void_p((C.addressof(store) + 255) // 256 * 256)
+    assert lib.dccn_rx_backward(p, p, p, p, p, p, p, p, p, 65408, 1, 64, 32, 32704, 1, p, 1 << 40, None) == -1
+    fits = _lib.RxShape(8192, 1, 64, 32, 32704, 2)                  # the same layer, dz just under 2 GiB
+    assert 4 * fits.batch * 2 * fits.D < 2 ** 31
+    assert lib.dccn_rx_bwd_fused_supported(C.byref(fits)) == 1
+
+
 def test_ops_refuse_cpu_tensors():
     import torch
     from dl_ofdm_amd import _lib, ops
