@@ -14,8 +14,8 @@
 //   * EVERY load of the block is issued before the first MFMA: one memory latency per launch instead of fourteen.
 // B operand kinds: OP_ICONTIG (forward, W[k][n]: four dword loads per k group, 64-byte segments; the tiles of one 16-column
 // strip and of its neighbour in the same 128-byte lines run on the same XCD, so each line leaves HBM/MALL once) and
-// OP_KCONTIG (dX = dY . W^T, W[n][k]: float4 loads).  Store stages as in gemm16.h EPI_STORE: 1 plain (+ bias), 2 tanh,
-// 3 times (1 - aux^2), 4 plus aux, 5 equalise (model.py:431-438).
+// OP_KCONTIG (dX = dY . W^T, W[n][k]: float4 loads).  Store stages: the StoreStage values of gemm_f32_mfma.h (NB of
+// fewrow_tile is one of them, not a bit count); the element-wise ones go through store_stage like gemm16.h EPI_STORE.
 #pragma once
 #include "gemm16.h"
 
@@ -72,7 +72,7 @@ __device__ __forceinline__ void fewrow_tile(const GemmParams& p, const int L, co
     float bj = 0.f, auxv = 0.f;
     float2 yv = make_float2(0.f, 0.f);
     if (p.bias != nullptr) bj = p.bias[ocol];
-    if constexpr (NB == 3 || NB == 4) auxv = p.aux[ci];
+    if constexpr (store_stage_reads_aux(NB)) auxv = p.aux[ci];
     if constexpr (NB == 5) yv = *reinterpret_cast<const float2*>(p.aux + (ci - (size_t)(ocol & 1)));
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -102,9 +102,7 @@ __device__ __forceinline__ void fewrow_tile(const GemmParams& p, const int L, co
             else *reinterpret_cast<float2*>(p.out3 + c0) = make_float2(er * er - ei * (-ei), er * (-ei) + ei * er);
         }
     } else {
-        if constexpr (NB == 2) o = tanhf(o);
-        else if constexpr (NB == 3) o = o * (1.0f - auxv * auxv);
-        else if constexpr (NB == 4) o = auxv + o;
+        o = store_stage<NB>(o, auxv);
         if (live) p.C[ci] = o;
     }
 }

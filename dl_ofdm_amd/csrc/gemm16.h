@@ -25,6 +25,7 @@
 // (decide.h decide_cells): packed bits / llr / prob leave the launch, z need not exist in memory.  A 64-column tile holds
 // 32 cells = 4 * nbits whole bytes per row, so tiles never share a byte.
 #pragma once
+#include <algorithm>
 #include "gemm_f32_mfma.h"
 #include "tail.h"
 #include "decide.h"
@@ -201,6 +202,25 @@ struct Cfg16 {
     }
 };
 
+// What the dynamic LDS of an EPI_TAIL launch holds after the k-loop (float offsets from its start), stated ONCE for the
+// kernel's carve and the host's size.  NB <= 2: the block reduction's scratch, behind the exchange region when KS > 1.
+// NB >= 3 (LDS-staged tail): [staged tile][packed labels][tail weights][reduction scratch].
+template <class CF, int NB, bool BWD>
+struct TailLds16 {
+    static constexpr bool STAGED = NB >= 3;
+    static constexpr bool QUAD4 = NB == 4 && BWD;         // a quad of lanes per cell (tail.h tail_quad4_cell)
+    static_assert(!STAGED || CF::xchg_bytes == 0, "LDS-staged tail: one wave set");
+    static constexpr int ZS = CF::BN + 2;                 // row stride of the staged tile (even: float2 reads)
+    static constexpr int TCELLS = CF::BM * (CF::BN / 2);
+    static constexpr int PW = tail_param_count(NB);
+    static constexpr int zt = 0;                          // [BM][ZS]
+    static constexpr int lt = CF::BM * ZS;                // [TCELLS] packed label bits (ints)
+    static constexpr int swl = lt + TCELLS;               // [PW] tail weights (90 / 200 do not fit the SGPR file)
+    static constexpr int red = STAGED ? swl + ((PW + 3) & ~3) : (int)(CF::xchg_bytes / sizeof(float));
+    static constexpr int red_floats = QUAD4 ? tail_quad4_lds_floats(CF::NT) : tail_reduce_lds_floats<NB, BWD>(CF::NT);
+    static constexpr size_t bytes = CF::smem_bytes((STAGED ? red : 0) + red_floats);
+};
+
 // Output policy of tail_cells_out (tail.h) for a tile that lies completely inside the matrix: cell u of the lane's batch
 // stores at the block-uniform pointers pb[u] (prob) / db[u] (dz) plus ONE per-lane 32-bit float offset each -- scalar base
 // + vector offset addressing, no 64-bit address arithmetic per cell, no per-lane null tests; dz leaves cell by cell.
@@ -217,6 +237,12 @@ struct TailOutTile {
         if constexpr (DZ) out_store2<1>(db[u] + ld, d0, d1);
     }
 };
+
+// (at most 8 cells share one interleaved instruction stream: larger tiles run the tail / the decision in batches -- same
+// per-cell arithmetic and the same accumulation order as one batch)
+constexpr int tail_batch_width(const int ncell) {
+    return ncell <= 8 ? ncell : (ncell % 8 == 0 ? 8 : (ncell % 6 == 0 ? 6 : (ncell % 5 == 0 ? 5 : 4)));
+}
 
 // One BM x BN output tile (block `L` of `T` tiles, grid split `z`) of C = A.B
 // PD = 2: global loads run TWO k-tiles ahead of the MFMAs (second staging register set, loop unrolled by two): with a
@@ -266,6 +292,7 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
 
     // EPI_TAIL: the label bits of this lane's cells are requested before the k-loop (no exposed latency afterwards).
     // Cell (tile a,b ; c): row 4*kg + (odd ? 2+c : c) of the tile, data cell col/2; KS == 2: set s owns c == s.
+    static_assert(EPI == EPI_STORE || (NB >= 1 && NB <= 4), "EPI_TAIL / EPI_DECIDE: NB is bits per symbol");
     constexpr int NCELL = (EPI == EPI_TAIL) ? TM * TN * 2 / KS : 1;
     // NB >= 3: the tail does not run on the MFMA register layout (90 / 200 gradient accumulators per cell-lane leave no
     // room for it): the finished tile goes through LDS and the block walks its BM x BN/2 cells like the stand-alone
@@ -326,13 +353,17 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
     constexpr int HALF = NSTEP / 2;
     constexpr int LPS = (PA + PB + HALF - 1) / HALF;     // global loads (first half) / LDS stores (second half) per step
 
-    auto load_ab = [&](auto mode_tag, int q, int k0) {
-        constexpr int MODE = decltype(mode_tag)::value;
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using I2 = std::integral_constant<int, 2>;
+    // piece q of the k-tile at k0 (A pieces first, then B) into staging register set set_tag (masked loads only know set 0)
+    auto load_ab = [&](auto mode_tag, auto set_tag, int q, int k0) {
+        constexpr int MODE = decltype(mode_tag)::value, RS = decltype(set_tag)::value;
         if (q < PA) {
-            if constexpr (MODE == PF_FAST) ta.load_fast(q, TA::tile_base(p.A, p.lda, k0, p.cF), p.cF);
+            if constexpr (MODE == PF_FAST) ta.load_fast(q, TA::tile_base(p.A, p.lda, k0, p.cF), p.cF, RS);
             else ta.load_masked(q, p.A, p.lda, k0, kend, p.K, m0, p.M, p.cF, tid);
         } else {
-            if constexpr (MODE == PF_FAST) tb.load_fast(q - PA, TB::tile_base(p.B, p.ldb, k0, p.cF), p.cF);
+            if constexpr (MODE == PF_FAST) tb.load_fast(q - PA, TB::tile_base(p.B, p.ldb, k0, p.cF), p.cF, RS);
             else tb.load_masked(q - PA, p.B, p.ldb, k0, kend, p.K, n0, p.N, p.cF, tid);
         }
     };
@@ -343,7 +374,7 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
     };
     auto stage_first = [&](auto mode_tag) {
 #pragma unroll
-        for (int q = 0; q < PA + PB; ++q) load_ab(mode_tag, q, kbeg);
+        for (int q = 0; q < PA + PB; ++q) load_ab(mode_tag, I0{}, q, kbeg);
 #pragma unroll
         for (int q = 0; q < PA + PB; ++q) store_ab(mode_tag, q, sA, sB);
     };
@@ -359,7 +390,7 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
     int t = 0;
     auto ktile2 = [&](auto load_tag, auto store_tag, auto lset_tag, auto sset_tag, auto dist_tag) {
         constexpr int LMODE = decltype(load_tag)::value, SMODE = decltype(store_tag)::value;
-        constexpr int LSET = decltype(lset_tag)::value, SSET = decltype(sset_tag)::value, DIST = decltype(dist_tag)::value;
+        constexpr int SSET = decltype(sset_tag)::value, DIST = decltype(dist_tag)::value;
         const int cur = t & 1;
         const int k0n = kbeg + (t + DIST) * BK;
         const float* As = sA + cur * BM * LDA + (wm0 + l15) * LDA + 4 * kg + 16 * NGS * set;
@@ -387,14 +418,7 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
                 if constexpr (LMODE != PF_NONE && !(GEMM16_ABL & 1)) {
                     if (step < HALF) {
 #pragma unroll
-                        for (int q = step * LPS; q < (step + 1) * LPS && q < PA + PB; ++q) {
-                            if constexpr (LMODE == PF_FAST) {
-                                if (q < PA) ta.load_fast(q, TA::tile_base(p.A, p.lda, k0n, p.cF), p.cF, LSET);
-                                else tb.load_fast(q - PA, TB::tile_base(p.B, p.ldb, k0n, p.cF), p.cF, LSET);
-                            } else {
-                                load_ab(load_tag, q, k0n);
-                            }
-                        }
+                        for (int q = step * LPS; q < (step + 1) * LPS && q < PA + PB; ++q) load_ab(load_tag, lset_tag, q, k0n);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -427,9 +451,6 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
         if constexpr (!(GEMM16_ABL & 4)) __syncthreads();
         ++t;
     };
-    using I0 = std::integral_constant<int, 0>;
-    using I1 = std::integral_constant<int, 1>;
-    using I2 = std::integral_constant<int, 2>;
     using TF = std::integral_constant<int, PF_FAST>;
     using TM_ = std::integral_constant<int, PF_MASKED>;
     using TN_ = std::integral_constant<int, PF_NONE>;
@@ -438,10 +459,7 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
     if (deep) {
         // k-tile n travels through register set n & 1; tile 1 is already in flight when the first MFMA issues
 #pragma unroll
-        for (int q = 0; q < PA + PB; ++q) {
-            if (q < PA) ta.load_fast(q, TA::tile_base(p.A, p.lda, kbeg + BK, p.cF), p.cF, 1);
-            else tb.load_fast(q - PA, TB::tile_base(p.B, p.ldb, kbeg + BK, p.cF), p.cF, 1);
-        }
+        for (int q = 0; q < PA + PB; ++q) load_ab(TF{}, I1{}, q, kbeg + BK);
         while (t + 3 < ntiles) {                              // t even here
             ktile2(TF{}, TF{}, I0{}, I1{}, I2{});
             ktile2(TF{}, TF{}, I1{}, I0{}, I2{});
@@ -497,6 +515,8 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
 
     // C/D layout of the 16x16 MFMA: col = lane & 15, row = 4 * (lane >> 4) + r
     if constexpr (EPI == EPI_STORE) {
+        constexpr int STAGE = NB;                          // EPI_STORE: the template argument is a StoreStage, no bit count
+        static_assert(STAGE >= STORE_PLAIN && STAGE <= STORE_EQUALISE, "EPI_STORE: a StoreStage");
         float* Cz = p.C + (size_t)z * p.slab;
 #pragma unroll
         for (int a = 0; a < TM; ++a) {
@@ -520,7 +540,7 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
                     float v;
                     if constexpr (KS > 1) v = set == 0 ? tile_val(a, b, rr, lane) : tile_val(a, b, 2 + rr, lane);
                     else v = acc[a][b][rr];
-                    if constexpr (NB == 5) {
+                    if constexpr (STAGE == STORE_EQUALISE) {
                         // the channel estimate h leaves the GEMM together with what model.py:431-438 computes from it:
                         // eq = y conj(h)/|h| and corr = eq conj(eq).  Adjacent lanes hold re and im of one cell: they
                         // swap halves, the even lane stores the cell of eq, the odd lane that of corr (aux = y, out2 = eq,
@@ -541,14 +561,11 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
                         }
                     } else
                     if (row < p.M && col < p.N) {
-                        // EPI_STORE: NB selects an element-wise stage on the way out (compile time: the plain store pays
-                        // nothing): the equaliser's tanh, its gradient, and "add to what is there" (model.py:424, 393-462)
+                        // an element-wise stage on the way out (gemm_f32_mfma.h StoreStage)
                         const size_t ci = (size_t)row * p.ldc + col;
-                        float o = v + bj;
-                        if constexpr (NB == 2) o = tanhf(o);
-                        else if constexpr (NB == 3) { const float y = p.aux[ci]; o = o * (1.0f - y * y); }
-                        else if constexpr (NB == 4) o = p.aux[ci] + o;
-                        Cz[ci] = o;
+                        float auxv = 0.f;
+                        if constexpr (store_stage_reads_aux(STAGE)) auxv = p.aux[ci];
+                        Cz[ci] = store_stage<STAGE>(v + bj, auxv);
                     }
                 }
             }
@@ -606,8 +623,7 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
         }
         unsigned hard[NC];
         {
-            // (at most 8 cells share one interleaved instruction stream, as in the fused tail)
-            constexpr int TW = NC <= 8 ? NC : (NC % 8 == 0 ? 8 : (NC % 6 == 0 ? 6 : (NC % 5 == 0 ? 5 : 4)));
+            constexpr int TW = tail_batch_width(NC);
             static_assert(NC % TW == 0, "decision batches");
 #pragma unroll
             for (int g0 = 0; g0 < NC; g0 += TW) {
@@ -654,12 +670,12 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
         const int Dn = p.N >> 1;                           // cells per row
         if constexpr (TAIL_LDS) {
             // ---- tile -> LDS, then the tail over the tile's cells (see the label prefetch above) ----
-            constexpr int PW = tail_param_count(NB);
-            constexpr int ZS = BN + 2;                          // row stride of the staged tile (even: float2 reads)
-            float* zt = smem;                                   // [BM][ZS]
-            int* lt = reinterpret_cast<int*>(smem + BM * ZS);   // [TCELLS] packed label bits
-            float* swl = smem + BM * ZS + TCELLS;               // [PW] tail weights (90 / 200 do not fit the SGPR file)
-            float* red = swl + ((PW + 3) & ~3);
+            using LY = TailLds16<CF, NB, BWD>;                  // the post-loop layout, shared with the host's size
+            constexpr int PW = LY::PW, ZS = LY::ZS;
+            float* zt = smem + LY::zt;
+            int* lt = reinterpret_cast<int*>(smem + LY::lt);
+            float* swl = smem + LY::swl;
+            float* red = smem + LY::red;
 #pragma unroll
             for (int a = 0; a < TM; ++a) {
 #pragma unroll
@@ -724,7 +740,7 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
             return;
         }
         const float* __restrict__ sw = tp.tailp;
-        float* red = smem + (KS > 1 ? (int)(CF::xchg_bytes / sizeof(float)) : 0);
+        float* red = smem + TailLds16<CF, NB, BWD>::red;
         TailLaneAcc<NB, BWD> A;
         A.clear();
         float cz0[NCELL], cz1[NCELL];
@@ -785,9 +801,7 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
                 }
             }
         }
-        // (at most 8 cells share one interleaved instruction stream: larger tiles run the tail in batches -- same
-        // per-cell arithmetic and the same accumulation order as one batch)
-        constexpr int TW = NCELL <= 8 ? NCELL : (NCELL % 8 == 0 ? 8 : (NCELL % 6 == 0 ? 6 : (NCELL % 5 == 0 ? 5 : 4)));
+        constexpr int TW = tail_batch_width(NCELL);
         static_assert(NCELL % TW == 0, "tail batches");
         // Interior tiles (block-uniform; all but the last tile row / column of a launch): every cell is valid, so the tail
         // runs without validity selects and masks, and cell (a, b, cc) stores at a uniform base -- the tile's origin plus
@@ -932,21 +946,25 @@ template <typename K>
 static int set_smem_attr(K kern, size_t smem) {         // once per (device, kernel, size): common.h
     return set_max_dynamic_smem(reinterpret_cast<const void*>(kern), smem);
 }
-
-// plain launch of one configuration; smem_pad lets a caller force fewer resident blocks per CU (experiments)
-template <int KA, int KB, int WGM, int WGN, int TM, int TN, int BK, int KS, int COLSUM, int TAG, int PD = 1, int ACT = 1>
-static int launch_gemm16(const GemmParams& p, int splits, hipStream_t s, size_t smem_min = 0) {
-    using CF = Cfg16<KA, KB, WGM, WGN, TM, TN, BK, KS>;
-    auto kern = gemm16_kernel<KA, KB, WGM, WGN, TM, TN, BK, KS, COLSUM, EPI_STORE, ACT, false, TAG, PD>;
-    size_t smem = CF::smem_bytes(0);
+// what every launcher below ends with: at least smem_min bytes of dynamic LDS (a caller can force fewer resident blocks per
+// CU: experiments), the kernel's attribute, the launch
+template <typename K, typename... Args>
+static int launch16(K kern, const dim3 grid, const int nt, size_t smem, const size_t smem_min, hipStream_t s, const Args&... args) {
     if (smem < smem_min) smem = smem_min;
     DCCN_TRY(set_smem_attr(kern, smem));
-    TailEpiParams none{};
-    dim3 grid(ceil_div(p.N, CF::BN) * ceil_div(p.M, CF::BM), 1, splits);
     DCCN_NO_CHAINS();
-    hipLaunchKernelGGL(kern, grid, dim3(CF::NT), smem, s, p, none);
+    hipLaunchKernelGGL(kern, grid, dim3(nt), smem, s, args...);
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
+}
+
+// plain launch of one configuration
+template <int KA, int KB, int WGM, int WGN, int TM, int TN, int BK, int KS, int COLSUM, int TAG, int PD = 1, int STAGE = STORE_PLAIN>
+static int launch_gemm16(const GemmParams& p, int splits, hipStream_t s, size_t smem_min = 0) {
+    using CF = Cfg16<KA, KB, WGM, WGN, TM, TN, BK, KS>;
+    auto kern = gemm16_kernel<KA, KB, WGM, WGN, TM, TN, BK, KS, COLSUM, EPI_STORE, STAGE, false, TAG, PD>;
+    dim3 grid(ceil_div(p.N, CF::BN) * ceil_div(p.M, CF::BM), 1, splits);
+    return launch16(kern, grid, CF::NT, CF::smem_bytes(0), smem_min, s, p, TailEpiParams{});
 }
 
 // dense forward + fused tail
@@ -954,17 +972,8 @@ template <int WGM, int WGN, int TM, int TN, int BK, int KS, int NB, bool BWD, in
 static int launch_dense_tail16(const GemmParams& p, const TailEpiParams& tp, hipStream_t s, size_t smem_min = 0) {
     using CF = Cfg16<OP_KCONTIG, OP_ICONTIG, WGM, WGN, TM, TN, BK, KS>;
     auto kern = gemm16_kernel<OP_KCONTIG, OP_ICONTIG, WGM, WGN, TM, TN, BK, KS, 0, EPI_TAIL, NB, BWD, TAG_DENSE_FWD, PD>;
-    // after the k-loop: NB >= 3: [staged tile][packed labels][tail weights] + the block reduction's scratch
-    constexpr int wfl = NB >= 3 ? CF::BM * (CF::BN + 2) + CF::BM * (CF::BN / 2) + ((tail_param_count(NB) + 3) & ~3) : 0;
-    constexpr int rfl = (NB == 4 && BWD) ? tail_quad4_lds_floats(CF::NT) : tail_reduce_lds_floats<NB, BWD>(CF::NT);
-    size_t smem = CF::smem_bytes(wfl + rfl);
-    if (smem < smem_min) smem = smem_min;
-    DCCN_TRY(set_smem_attr(kern, smem));
     dim3 grid(ceil_div(p.N, CF::BN) * ceil_div(p.M, CF::BM), 1, 1);
-    DCCN_NO_CHAINS();
-    hipLaunchKernelGGL(kern, grid, dim3(CF::NT), smem, s, p, tp);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return launch16(kern, grid, CF::NT, TailLds16<CF, NB, BWD>::bytes, smem_min, s, p, tp);
 }
 
 // Large layers whose row count leaves a short last row tile (N = 1024: 585 frames = 7 x 80 + 25): the last tile row runs
@@ -979,55 +988,34 @@ __global__ __launch_bounds__(256) void dense_tail_ragged_kernel(const GemmParams
 }
 template <int TM, int BK, int NB, bool BWD>
 constexpr size_t dense_tail16_smem() {
-    using CF = Cfg16<OP_KCONTIG, OP_ICONTIG, 1, 4, TM, 1, BK, 1>;
-    constexpr int wfl = NB >= 3 ? CF::BM * (CF::BN + 2) + CF::BM * (CF::BN / 2) + ((tail_param_count(NB) + 3) & ~3) : 0;
-    constexpr int rfl = (NB == 4 && BWD) ? tail_quad4_lds_floats(CF::NT) : tail_reduce_lds_floats<NB, BWD>(CF::NT);
-    return CF::smem_bytes(wfl + rfl);
+    return TailLds16<Cfg16<OP_KCONTIG, OP_ICONTIG, 1, 4, TM, 1, BK, 1>, NB, BWD>::bytes;
 }
 template <int TM1, int TM2, int BK, int NB, bool BWD, int PD>
 static int launch_dense_tail16_ragged(const GemmParams& p1, const TailEpiParams& t1, const GemmParams& p2, const TailEpiParams& t2,
                                       hipStream_t s, size_t smem_min = 0) {
     auto kern = dense_tail_ragged_kernel<TM1, TM2, BK, NB, BWD, PD>;
-    size_t smem = dense_tail16_smem<TM1, BK, NB, BWD>();
-    if (dense_tail16_smem<TM2, BK, NB, BWD>() > smem) smem = dense_tail16_smem<TM2, BK, NB, BWD>();
-    if (smem < smem_min) smem = smem_min;
-    DCCN_TRY(set_smem_attr(kern, smem));
+    const size_t smem = std::max(dense_tail16_smem<TM1, BK, NB, BWD>(), dense_tail16_smem<TM2, BK, NB, BWD>());
     const int T1 = ceil_div(p1.N, 64) * ceil_div(p1.M, 16 * TM1), T2 = ceil_div(p2.N, 64) * ceil_div(p2.M, 16 * TM2);
-    DCCN_NO_CHAINS();
-    hipLaunchKernelGGL(kern, dim3(T1 + T2), dim3(256), smem, s, p1, t1, p2, t2, T1, T2);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return launch16(kern, dim3(T1 + T2), 256, smem, smem_min, s, p1, t1, p2, t2, T1, T2);
 }
 
-template <int WGM, int WGN, int TM, int TN, int BK, int WWGM, int WWGN, int WTM, int WTN, int ACTX = 1>
+template <int WGM, int WGN, int TM, int TN, int BK, int WWGM, int WWGN, int WTM, int WTN, int STAGEX = STORE_PLAIN>
 static int launch_dense_bwd16(const GemmParams& px, const GemmParams& pw, int splits_w, hipStream_t s,
                               size_t smem_min = 0) {
     using CX = Cfg16<OP_KCONTIG, OP_KCONTIG, WGM, WGN, TM, TN, BK, 1>;
     using CW = Cfg16<OP_ICONTIG, OP_ICONTIG, WWGM, WWGN, WTM, WTN, BK, 1>;
-    auto kern = dense_bwd16_kernel<WGM, WGN, TM, TN, BK, WWGM, WWGN, WTM, WTN, ACTX>;
-    size_t smem = CX::smem_bytes(0) > CW::smem_bytes(0) ? CX::smem_bytes(0) : CW::smem_bytes(0);
-    if (smem < smem_min) smem = smem_min;
-    DCCN_TRY(set_smem_attr(kern, smem));
+    auto kern = dense_bwd16_kernel<WGM, WGN, TM, TN, BK, WWGM, WWGN, WTM, WTN, STAGEX>;
     const int nx = ceil_div(px.N, CX::BN) * ceil_div(px.M, CX::BM);
     const int tw = ceil_div(pw.N, CW::BN) * ceil_div(pw.M, CW::BM);
-    DCCN_NO_CHAINS();
-    hipLaunchKernelGGL(kern, dim3(nx + tw * splits_w), dim3(256), smem, s, px, pw, nx, tw);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return launch16(kern, dim3(nx + tw * splits_w), 256, std::max(CX::smem_bytes(0), CW::smem_bytes(0)), smem_min, s, px, pw, nx, tw);
 }
 
 template <int WGM, int WGN, int TM, int TN, int BK>
 static int launch_bwd_w16_finalize(const GemmParams& p, int splits, const TailFinalizeArgs& fin, hipStream_t s) {
     using CF = Cfg16<OP_ICONTIG, OP_ICONTIG, WGM, WGN, TM, TN, BK, 1>;
     auto kern = gemm16_bwd_w_finalize_kernel<WGM, WGN, TM, TN, BK>;
-    const size_t smem = CF::smem_bytes(0);
-    DCCN_TRY(set_smem_attr(kern, smem));
     const int tiles = ceil_div(p.N, CF::BN) * ceil_div(p.M, CF::BM), gemm_blocks = tiles * splits;
-    DCCN_NO_CHAINS();
-    hipLaunchKernelGGL(kern, dim3(gemm_blocks + tail_finalize_blocks(fin.P)), dim3(256), smem, s, p, tiles, gemm_blocks,
-                       fin);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return launch16(kern, dim3(gemm_blocks + tail_finalize_blocks(fin.P)), 256, CF::smem_bytes(0), 0, s, p, tiles, gemm_blocks, fin);
 }
 
 // dense forward + decision stage (receive path, NB <= 2): the tile shapes of the fused dense + tail launch
@@ -1041,13 +1029,7 @@ template <int TM, int BK, int NB, int PD>
 static int launch_dense_decide16(const GemmParams& p, const DecideEpiParams& dq, hipStream_t s, size_t smem_min = 0) {
     using CF = Cfg16<OP_KCONTIG, OP_ICONTIG, 1, 4, TM, 1, BK, 1>;
     auto kern = dense_decide_kernel<TM, BK, NB, PD>;
-    size_t smem = CF::smem_bytes(0);
-    if (smem < smem_min) smem = smem_min;
-    DCCN_TRY(set_smem_attr(kern, smem));
-    DCCN_NO_CHAINS();
-    hipLaunchKernelGGL(kern, dim3(ceil_div(p.N, CF::BN) * ceil_div(p.M, CF::BM)), dim3(256), smem, s, p, dq);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return launch16(kern, dim3(ceil_div(p.N, CF::BN) * ceil_div(p.M, CF::BM)), 256, CF::smem_bytes(0), smem_min, s, p, dq);
 }
 // ... and the two-shape grid of dense_tail_ragged_kernel (a short last row tile of a large layer)
 template <int TM1, int TM2, int BK, int NB, int PD>
@@ -1064,14 +1046,8 @@ static int launch_dense_decide16_ragged(const GemmParams& p1, const DecideEpiPar
     using C1 = Cfg16<OP_KCONTIG, OP_ICONTIG, 1, 4, TM1, 1, BK, 1>;
     using C2 = Cfg16<OP_KCONTIG, OP_ICONTIG, 1, 4, TM2, 1, BK, 1>;
     auto kern = dense_decide_ragged_kernel<TM1, TM2, BK, NB, PD>;
-    size_t smem = C1::smem_bytes(0) > C2::smem_bytes(0) ? C1::smem_bytes(0) : C2::smem_bytes(0);
-    if (smem < smem_min) smem = smem_min;
-    DCCN_TRY(set_smem_attr(kern, smem));
     const int T1 = ceil_div(p1.N, 64) * ceil_div(p1.M, 16 * TM1), T2 = ceil_div(p2.N, 64) * ceil_div(p2.M, 16 * TM2);
-    DCCN_NO_CHAINS();
-    hipLaunchKernelGGL(kern, dim3(T1 + T2), dim3(256), smem, s, p1, d1, p2, d2, T1, T2);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return launch16(kern, dim3(T1 + T2), 256, std::max(C1::smem_bytes(0), C2::smem_bytes(0)), smem_min, s, p1, d1, p2, d2, T1, T2);
 }
 
 // split-K plan with an explicit split count (k ranges are multiples of BK; the last one may be ragged)

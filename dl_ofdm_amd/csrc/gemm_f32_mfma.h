@@ -80,10 +80,10 @@ struct GemmParams {
     // (graded ranges: long items first, short ones last, so that the grid's tail is made of short items)
     int nranges;
     int koff[9];
-    // gemm16.h store epilogue with an element-wise stage (template parameter NB of EPI_STORE: 2 tanh, 3 v (1 - aux^2),
-    // 4 v + aux): the other operand of stages 3 and 4, same shape and row stride as C
+    // store epilogues with an element-wise stage (StoreStage below): the other operand of STORE_TANHGRAD and STORE_ADD,
+    // same shape and row stride as C
     const float* aux;
-    float* out2; float* out3;   // gemm16.h EPI_STORE<5> (equalise stage): eq and corr next to C = h, aux = y
+    float* out2; float* out3;   // STORE_EQUALISE: eq and corr next to C = h, aux = y
     long long gC;        // CMAP_SPLIT_PAIRS stores (gemm_store): elements between the two destination buffers
     PatchGeom pg;        // OP_KPATCH operand A
     unsigned long long* stamp;   // step timeline stamps of this launch (common.h stamp_mark), nullptr = none
@@ -523,10 +523,27 @@ __device__ __forceinline__ void gemm_mainloop(const GemmParams& p, const int L, 
 //   CMAP_TANHGRAD / CMAP_ADD  no column map, an element-wise stage instead: v (1 - aux^2) (the gradient through
 //                     tanh, aux = its output) / aux + v (gradient accumulation); aux has C's shape and row stride
 enum ColumnMap : int { CMAP_NONE = 0, CMAP_JOIN_PAIRS = 1, CMAP_SPLIT_PAIRS = 2, CMAP_TANHGRAD = 3, CMAP_ADD = 4 };
+
+// Element-wise stage of a store epilogue (compile time: the plain store pays nothing): the equaliser's tanh, its gradient,
+// "add to what is there" and the equalise stage (model.py:424, 393-462).  store_stage is the ONE definition of the
+// element-wise expressions for the three GEMM families that store through them (gemm_store below, gemm16.h EPI_STORE,
+// fewrow.h fewrow_tile): same bits.  The equalise stage is written out in gemm16.h and fewrow.h.
+enum StoreStage : int { STORE_PLAIN = 1, STORE_TANH = 2, STORE_TANHGRAD = 3, STORE_ADD = 4, STORE_EQUALISE = 5 };
+constexpr bool store_stage_reads_aux(const int stage) { return stage == STORE_TANHGRAD || stage == STORE_ADD; }
+// o = accumulator + bias; aux = p.aux at the element (read only by the stages that store_stage_reads_aux; the caller
+// decides when to request it)
+template <int STAGE>
+__device__ __forceinline__ float store_stage(const float o, const float aux) {
+    static_assert(STAGE >= STORE_PLAIN && STAGE < STORE_EQUALISE, "element-wise store stage");
+    if constexpr (STAGE == STORE_TANH) return tanhf(o);
+    else if constexpr (STAGE == STORE_TANHGRAD) return o * (1.0f - aux * aux);
+    else if constexpr (STAGE == STORE_ADD) return aux + o;
+    else return o;
+}
 template <int CMAP>
 __device__ __forceinline__ float cmap_stage(const GemmParams& p, const size_t i, const float v) {
-    if constexpr (CMAP == CMAP_TANHGRAD) { const float y = p.aux[i]; return v * (1.0f - y * y); }
-    else if constexpr (CMAP == CMAP_ADD) return p.aux[i] + v;
+    if constexpr (CMAP == CMAP_TANHGRAD) return store_stage<STORE_TANHGRAD>(v, p.aux[i]);
+    else if constexpr (CMAP == CMAP_ADD) return store_stage<STORE_ADD>(v, p.aux[i]);
     else return v;
 }
 template <int CMAP>

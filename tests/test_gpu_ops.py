@@ -288,6 +288,9 @@ def test_demod_tail_loss(ops, nbits, cells):
 # ---- R2 + R3-R6 in one launch (gemm16 EPI_TAIL) -----------------------------------------------------
 @pytest.mark.parametrize("nbits,M,K,N", [(2, 36, 896, 640), (1, 36, 896, 640), (2, 1170, 896, 640), (2, 53, 100, 36),
                                          (1, 130, 64, 132), (2, 585, 128, 64),
+                                         # odd k-tile counts of the two-ahead schedule (BK = 64): the drain of three with no loop
+                                         # pass, and one loop pass plus the drain of three; N = one full tile + a ragged one
+                                         (2, 53, 192, 100), (2, 53, 320, 100),
                                          # 8-QAM / 16-QAM: tile staged through LDS, lane-per-cell / quad-lane tail
                                          (3, 36, 896, 640), (4, 36, 896, 640), (4, 300, 896, 640), (3, 300, 896, 640),
                                          (4, 53, 100, 36), (3, 130, 64, 132)])

@@ -155,7 +155,9 @@ def test_stand_alone_decision_kernel(nbits, frames, D):
 
 
 @pytest.mark.parametrize("M,K,N,nbits", [(1170, 896, 640, 1), (1170, 896, 640, 2), (36, 896, 640, 1), (73, 896, 640, 2),
-                                         (13, 168, 100, 2), (100, 896, 640, 3), (1170, 896, 640, 4)])
+                                         (13, 168, 100, 2), (100, 896, 640, 3), (1170, 896, 640, 4),
+                                         # odd k-tile counts of the two-ahead schedule (3 and 5 tiles of 64)
+                                         (53, 192, 100, 2), (53, 320, 100, 2)])
 def test_dense_decide_equals_dense_then_decide(M, K, N, nbits):
     from dl_ofdm_amd import _lib
     from dl_ofdm_amd.receive import row_bytes
