@@ -271,5 +271,15 @@ __device__ __forceinline__ long long wave_sum(long long v) {
     }
     return r;
 }
+// sum of a double over the four waves of a 256-thread block (tid: the thread's linear index), in the fixed order
+// (wave 0 + wave 1) + (wave 2 + wave 3), returned in every thread.  sh4: four doubles of LDS; a caller that has read them for
+// something else puts its own barrier in front.
+__device__ __forceinline__ double block_sum4(double v, double* sh4, const int tid) {
+    v = wave_sum(v);
+    if ((tid & 63) == 0) sh4[tid >> 6] = v;
+    __syncthreads();
+    return (sh4[0] + sh4[1]) + (sh4[2] + sh4[3]);
+}
+__device__ __forceinline__ double block_sum4(double v, double* sh4) { return block_sum4(v, sh4, (int)threadIdx.x); }
 
 }  // namespace dccn

@@ -44,6 +44,74 @@ __device__ __forceinline__ float2 box_muller(unsigned w0, unsigned w1) {
     sincosf(6.2831853071795864769f * uniform01(w1), &sn, &cs);
     return make_float2(r * cs, r * sn);
 }
+// two independent standard normals of counter (index, stream, offset)
+__device__ __forceinline__ float2 normal_pair(unsigned long long index, unsigned stream, unsigned offset, unsigned long long seed) {
+    const Philox4 p = philox4x32_10(index, stream, offset, seed);
+    return box_muller(p.v[0], p.v[1]);
+}
+
+// ---- the channel's arithmetic, each piece once: the per-stage kernels, the fused generator body and (through norm_adam.h) R0's
+// virtual input call these, which is what makes their outputs the same bits ----
+// acc += a * b (complex); -ffp-contract=off: two roundings per product and sum, the terms of each component in this order
+__device__ __forceinline__ void cmac(float2& acc, const float2 a, const float2 b) {
+    acc.x += a.x * b.x - a.y * b.y;
+    acc.y += a.x * b.y + a.y * b.x;
+}
+// radio.py:352-372 static tap k of frame fr: (z0 + i z1) / sqrt(2) * coeff_k, z from Philox stream 1 at index fr * tap_stride + k
+__device__ __forceinline__ float2 scaled_tap(const float2 z, const float coeff_k) {
+    const float c = coeff_k * 0.70710678118654752440f;
+    return make_float2(z.x * c, z.y * c);
+}
+__device__ __forceinline__ float2 static_tap(const int fr, const int k, const int tap_stride, const float* __restrict__ coeff,
+                                             unsigned offset, unsigned long long seed) {
+    return scaled_tap(normal_pair((unsigned long long)fr * tap_stride + k, kStreamTaps, offset, seed), coeff[k]);
+}
+// impulse response g[l] = sum_k tap[k] alpha[k, l] (alpha: [n_taps, L] sinc interpolation), k ascending
+__device__ __forceinline__ float2 taps_dot_alpha(const float2* tap, const float* __restrict__ alpha, const int n_taps, const int L,
+                                                 const int l) {
+    float2 a = make_float2(0.f, 0.f);
+    for (int k = 0; k < n_taps; ++k) {
+        const float w = alpha[k * L + l];
+        a.x += tap[k].x * w;
+        a.y += tap[k].y * w;
+    }
+    return a;
+}
+// frequency response H[f] = sum_l g[l] w^((f l) mod nfft), l ascending; twiddle(m) = w^m = (cos, sin)(-2 pi m / nfft), computed
+// (twiddle_of) or read from a table of those values
+__device__ __forceinline__ float2 twiddle_of(const int m, const int nfft) {
+    float sn, cs;
+    sincosf(-6.2831853071795864769f * (float)m / (float)nfft, &sn, &cs);
+    return make_float2(cs, sn);
+}
+template <typename TW>
+__device__ __forceinline__ float2 freq_response(const float2* g, const int L, const int f, const int nfft, TW twiddle) {
+    float2 a = make_float2(0.f, 0.f);
+    for (int l = 0; l < L; ++l) {
+        const float2 w = twiddle((f * l) % nfft);
+        cmac(a, g[l], w);
+    }
+    return a;
+}
+// radio.py:513-526 noise level of a frame: sqrt(.5) 10^(-SNR/20)
+__device__ __forceinline__ float frame_noise_std(const float snr_db) { return 0.70710678118654752440f * exp10f(-snr_db * 0.05f); }
+// radio.py:376-407 Jakes sum of sinusoids: tap k of symbol time t is coeff_k sqrt(1/48) (mu_0 + i mu_1),
+// mu_c = sum_n cos(2 pi t Fd cos(a_n +- a0_k) + theta[c][n][k]) (c = 0: +, c = 1: -), a_n = (n + .5) pi / (4 * 48), a0_k = (k + 1) pi / (4 * 48),
+// theta uniform in [0, 2 pi) from Philox stream 3 at index ((fr 2 + c) 48 + n) tap_stride + k
+constexpr float kJakesNorm = 0.14433756729740644113f;          // sqrt(1/48)
+__device__ __forceinline__ float doppler_phase(const int fr, const int c, const int n, const int k, const int tap_stride, unsigned offset,
+                                               unsigned long long seed) {
+    const unsigned long long i = (((unsigned long long)fr * 2 + c) * kSinusoids + n) * tap_stride + k;
+    return 6.2831853071795864769f * uniform01(philox4x32_10(i, kStreamDoppler, offset, seed).v[0]);
+}
+__device__ __forceinline__ float jakes_shift(const float Fd, const int c, const int n, const int k) {
+    const float step = 3.14159265358979323846f / (4.0f * kSinusoids);
+    const float an = ((float)(n + 1) - 0.5f) * step, a0 = (float)(k + 1) * step;
+    return Fd * cosf(c == 0 ? an + a0 : an - a0);
+}
+__device__ __forceinline__ float jakes_cos(const float t, const float shift, const float theta) {
+    return cosf(6.2831853071795864769f * t * shift + theta);
+}
 
 // test hook: out[i] = the four words of counter (i, stream, offset)
 static __global__ __launch_bounds__(256) void philox_fill_kernel(unsigned* __restrict__ out, long long n, unsigned stream,
@@ -106,38 +174,19 @@ static __global__ __launch_bounds__(64) void channel_taps_kernel(const float* __
         if (t < L) gs[t] = make_float2(t == 0 ? 1.f : 0.f, 0.f);
     } else {
         if (t < n_taps) {
-            float2 z;
-            if (taps_in) {
-                z = make_float2(taps_in[((size_t)fr * tap_stride + t) * 2], taps_in[((size_t)fr * tap_stride + t) * 2 + 1]);
-            } else {
-                const Philox4 p = philox4x32_10((unsigned long long)fr * tap_stride + t, kStreamTaps, offset, seed);
-                z = box_muller(p.v[0], p.v[1]);
-            }
-            const float c = coeff[t] * 0.70710678118654752440f;
-            tap[t] = make_float2(z.x * c, z.y * c);
+            float2 z;                                        // (static_tap with the normals from the caller when given)
+            if (taps_in) z = make_float2(taps_in[((size_t)fr * tap_stride + t) * 2], taps_in[((size_t)fr * tap_stride + t) * 2 + 1]);
+            else z = normal_pair((unsigned long long)fr * tap_stride + t, kStreamTaps, offset, seed);
+            tap[t] = scaled_tap(z, coeff[t]);
         }
         __syncthreads();
-        if (t < L) {
-            float2 a = make_float2(0.f, 0.f);
-            for (int k = 0; k < n_taps; ++k) {
-                const float w = alpha[k * L + t];
-                a.x += tap[k].x * w;
-                a.y += tap[k].y * w;
-            }
-            gs[t] = a;
-        }
+        if (t < L) gs[t] = taps_dot_alpha(tap, alpha, n_taps, L, t);
     }
     __syncthreads();
     if (t < L) g[(size_t)fr * g_stride + t] = gs[t];
     if (H) {
         for (int f = t; f < nfft; f += 64) {
-            float2 a = make_float2(0.f, 0.f);
-            for (int l = 0; l < L; ++l) {
-                float sn, cs;
-                sincosf(-6.2831853071795864769f * (float)((f * l) % nfft) / (float)nfft, &sn, &cs);
-                a.x += gs[l].x * cs - gs[l].y * sn;
-                a.y += gs[l].x * sn + gs[l].y * cs;
-            }
+            const float2 a = freq_response(gs, L, f, nfft, [nfft](int m) { return twiddle_of(m, nfft); });
             for (int r = 0; r < h_rep; ++r) H[((size_t)fr * h_rep + r) * nfft + f] = a;
         }
     }
@@ -150,9 +199,9 @@ static __global__ __launch_bounds__(64) void channel_taps_kernel(const float* __
 // (frame, 256-sample chunk) items and leave ONE partial sum of |y|^2 each, in a fixed order -- few enough for the AWGN kernel to add
 // them up itself (the separate sum_partials launch of rounds 1-2 is gone).  pbase: this launch's first slot in `partial`.
 constexpr int kChanPartials = 2048;
-// TapGen (enabled): the block draws the static taps of a frame itself when it moves to that frame -- the same Philox
-// draws, coefficients and summation order as channel_taps_kernel, so the impulse response has the same bits; the taps
-// launch disappears when nobody asked for H (the generate-and-train loop of the basic receiver).
+// TapGen (enabled): the block draws the static taps of a frame itself when it moves to that frame -- static_tap and
+// taps_dot_alpha, as channel_taps_kernel, so the impulse response has the same bits; the taps launch disappears when nobody
+// asked for H (the generate-and-train loop of the basic receiver).
 struct TapGen {
     const float* coeff; const float* alpha;
     int enabled, n_taps, identity, tap_stride;
@@ -183,22 +232,9 @@ static __global__ __launch_bounds__(256) void fir_same_kernel(const float2* __re
                 if (threadIdx.x < L) gs[threadIdx.x] = make_float2(threadIdx.x == 0 ? 1.f : 0.f, 0.f);
             } else {
                 const int t = threadIdx.x;
-                if (t < tg.n_taps) {
-                    const Philox4 p = philox4x32_10((unsigned long long)fr * tg.tap_stride + t, kStreamTaps, tg.offset, tg.seed);
-                    const float2 z = box_muller(p.v[0], p.v[1]);
-                    const float c = tg.coeff[t] * 0.70710678118654752440f;
-                    tap[t] = make_float2(z.x * c, z.y * c);
-                }
+                if (t < tg.n_taps) tap[t] = static_tap(fr, t, tg.tap_stride, tg.coeff, tg.offset, tg.seed);
                 __syncthreads();
-                if (t < L) {
-                    float2 a = make_float2(0.f, 0.f);
-                    for (int k = 0; k < tg.n_taps; ++k) {
-                        const float w = tg.alpha[k * L + t];
-                        a.x += tap[k].x * w;
-                        a.y += tap[k].y * w;
-                    }
-                    gs[t] = a;
-                }
+                if (t < L) gs[t] = taps_dot_alpha(tap, tg.alpha, tg.n_taps, L, t);
             }
             __syncthreads();
             cur = fr;
@@ -211,17 +247,14 @@ static __global__ __launch_bounds__(256) void fir_same_kernel(const float2* __re
                 const int u = t + off - l;
                 if (u < 0 || u >= T) continue;
                 const float2 v = xf[u];
-                a.x += gs[l].x * v.x - gs[l].y * v.y;
-                a.y += gs[l].x * v.y + gs[l].y * v.x;
+                cmac(a, gs[l], v);
             }
             y[(size_t)fr * T + t] = a;
             pw += (double)a.x * a.x + (double)a.y * a.y;
         }
     }
-    pw = wave_sum(pw);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = pw;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[pbase + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    pw = block_sum4(pw, sh);
+    if (threadIdx.x == 0) partial[pbase + blockIdx.x] = pw;
 }
 
 // radio.py:513-526 AWGN_channel_np: out = y / sqrt(mean |y|^2 over the batch) + noise * sqrt(0.5) 10^(-SNR/20),
@@ -236,41 +269,23 @@ static __global__ __launch_bounds__(256) void awgn_kernel(const float2* __restri
                                                    unsigned long long seed) {
     __shared__ double sh[4];
     __shared__ float s_inv;
-    {   // mean |y|^2 over the batch from the FIR stage's <= kChanPartials block sums: every block adds them in the
-        // same fixed order (thread t: t, t+256; DPP wave sum; four wave sums), so all blocks get the same bits
-        double a = 0.0;
-        for (int i = threadIdx.x; i < n_partial; i += 256) a += power_partial[i];
-        a = wave_sum(a);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
-        __syncthreads();
-        if (threadIdx.x == 0) s_inv = 1.0f / sqrtf((float)(((sh[0] + sh[1]) + (sh[2] + sh[3])) / total));
-        __syncthreads();
-    }
-    const float inv_scale = s_inv;
+    // mean |y|^2 over the batch from the FIR stage's <= kChanPartials block sums, added up by every block
+    const float inv_scale = batch_power_inv_scale(power_partial, n_partial, total, sh, &s_inv);
     const int fr = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x;
     double pw = 0.0;
     if (t < T) {
         const size_t i = (size_t)fr * T + t;
-        const float std_ = 0.70710678118654752440f * exp10f(-snr_db[fr] * 0.05f);
-        float2 z;
-        if (noise_in) {
-            z = make_float2(noise_in[2 * i], noise_in[2 * i + 1]);
-        } else {
-            const Philox4 p = philox4x32_10((unsigned long long)i, kStreamNoise, offset, seed);
-            z = box_muller(p.v[0], p.v[1]);
-        }
+        const float std_ = frame_noise_std(snr_db[fr]);
+        float2 z = noise_in ? make_float2(noise_in[2 * i], noise_in[2 * i + 1]) : normal_pair((unsigned long long)i, kStreamNoise, offset, seed);
         z.x *= std_;
         z.y *= std_;
-        const float2 v = y[i];
-        out[i] = make_float2(v.x * inv_scale + z.x, v.y * inv_scale + z.y);
+        out[i] = scale_add_noise(y[i], inv_scale, z);
         pw = (double)z.x * z.x + (double)z.y * z.y;
     }
     if (noise_partial) {                                 // (kernel argument: block-uniform)
-        pw = wave_sum(pw);
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = pw;
-        __syncthreads();
-        if (threadIdx.x == 0) noise_partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+        __syncthreads();                                 // (sh held the batch power's wave sums)
+        pw = block_sum4(pw, sh);
+        if (threadIdx.x == 0) noise_partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = pw;
     }
 }
 
@@ -282,11 +297,11 @@ static __global__ __launch_bounds__(256) void awgn_kernel(const float2* __restri
 //   2. ifft + cyclic prefix (ofdm.py:357-362) as a 16 x 2K x 2(K+CP) product on v_mfma_f32_16x16x4_f32 with the constant
 //      matrix of DeviceDataGen.idft_cp_matrix read straight from L2 into the MFMA registers (every load of a wave is issued
 //      before its first MFMA), the time-domain frames land in LDS;
-//   3. the frames' static taps (radio.py:352-372, Philox stream 1; the arithmetic of channel_taps_kernel);
-//   4. y = np.convolve(frame, g, 'same') (radio.py:360-366; the loop of fir_same_kernel) -> y, and ONE partial sum of |y|^2
-//      per block;
-//   5. the frame-scaled noise of radio.py:513-526 (Philox stream 2, sqrt(.5) 10^(-SNR/20) per frame; the draws and
-//      expressions of awgn_kernel) -> noise, and one partial sum of |noise|^2 per block.
+//   3. the frames' static taps (radio.py:352-372, Philox stream 1: static_tap, taps_dot_alpha, freq_response);
+//   4. y = np.convolve(frame, g, 'same') (radio.py:360-366; cmac over l ascending, as fir_same_kernel) -> y, and ONE partial
+//      sum of |y|^2 per block;
+//   5. the frame-scaled noise of radio.py:513-526 (Philox stream 2: normal_pair's draw times frame_noise_std) -> noise, and one
+//      partial sum of |noise|^2 per block.
 // What cannot be finished here is the batch-wide 1 / sqrt(mean |y|^2): x = y * that + noise is formed by the consumer -- R0 of
 // the receiver step reads (y, noise, partials) as its virtual input (norm_adam.h NormVirtual), or gen_static_apply_kernel
 // materialises x where a buffer is wanted.
@@ -297,9 +312,9 @@ struct GenProfile {                 // one fading profile: tap amplitudes, sinc 
 struct GenStaticArgs {
     int32_t* bits_out; const int* cell_map; const float2* const_tab; float2 pilot; const float* idft;
     // frame f runs profile f % n_prof (radio.py:438-452 without Doppler frames; n_prof = 1: one channel for the batch);
-    // tap_stride: taps per frame in the Philox index of the tap draws (channel_taps_kernel's)
+    // tap_stride: taps per frame in the Philox index of the tap draws (static_tap)
     GenProfile prof[kGenMaxProfiles]; int n_prof, tap_stride;
-    float2* H; int h_rep;           // nullable: fft(g, K) per frame, h_rep copies (channel_taps_kernel's arithmetic)
+    float2* H; int h_rep;           // nullable: fft(g, K) per frame, h_rep copies (freq_response)
     // Doppler frames (radio.py:376-407, 438-452; the Doppler instantiation only): frame f is one when dop_period > 0,
     // f % dop_period == 0 and its profile has Fd > 0.1 and is not the identity; t_sym: seconds per OFDM symbol
     int dop_period;
@@ -408,11 +423,7 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
         sTh = reinterpret_cast<float*>(sTapD + kGenFramesPerBlock * S * 16);
         sFc = sTh + kGenFramesPerBlock * 2 * kSinusoids * 16;
     }
-    if (a.H != nullptr && tid < K) {
-        float sn, cs;
-        sincosf(-6.2831853071795864769f * (float)tid / (float)K, &sn, &cs);
-        tw[tid] = make_float2(cs, sn);
-    }
+    if (a.H != nullptr && tid < K) tw[tid] = twiddle_of(tid, K);
     static_assert(kGenFramesPerBlock * 2 * kGenFirPad == 256, "one pad cell per thread");
     sTX[(tid >> 7) * TP + ((tid >> 6) & 1) * (kGenFirPad + T) + (tid & 63)] = make_float2(0.f, 0.f);
 
@@ -444,8 +455,7 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
     // 5. the frame-scaled noise (depends on nothing else: its Philox / Box-Muller chains run under the loads above)
     double nw = 0.0;
     {
-        const float std0 = 0.70710678118654752440f * exp10f(-a.snr_db[f0] * 0.05f);
-        const float std1 = 0.70710678118654752440f * exp10f(-a.snr_db[f0 + (nfr > 1 ? 1 : 0)] * 0.05f);
+        const float std0 = frame_noise_std(a.snr_db[f0]), std1 = frame_noise_std(a.snr_db[f0 + (nfr > 1 ? 1 : 0)]);
         float2 z[NSMP];
 #pragma unroll
         for (int q = 0; q < NSMP; ++q) {
@@ -453,7 +463,7 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
             const size_t o = (size_t)f0 * T + i;                         // (f0 + fr) * T + (i - fr * T)
             if (a.abl & 1) { z[q] = make_float2(0.3f, 0.1f); continue; }
             const Philox4 p = philox4x32_10((unsigned long long)o, kStreamNoise, a.offset, a.seed);
-            z[q] = box_muller(p.v[0], p.v[1]);
+            z[q] = box_muller(p.v[0], p.v[1]);          // (normal_pair, written out: the call changes this kernel's schedule)
             const float sd = fr == 0 ? std0 : std1;
             z[q].x *= sd;
             z[q].y *= sd;
@@ -470,14 +480,10 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
     // 3 (early). static taps of the block's frames (threads 0..n_taps-1 of waves 0 / 1 draw frame 0 / 1)
     const GenProfile Pw = w == 0 ? P0 : P1;            // (waves 0 / 1 own the taps of frames 0 / 1)
     const bool dopw = w == 0 ? dop0 : dop1;            // (false in the static instantiation)
-    if (w < nfr && !Pw.identity && lane < Pw.n_taps && !dopw) {
-        const Philox4 p = philox4x32_10((unsigned long long)(f0 + w) * a.tap_stride + lane, kStreamTaps, a.offset, a.seed);
-        const float2 z = box_muller(p.v[0], p.v[1]);
-        const float cf = Pw.coeff[lane] * 0.70710678118654752440f;
-        tap[w][lane] = make_float2(z.x * cf, z.y * cf);
-    }
-    // 3d (early). phases of the block's Doppler frames: theta[c][n][k] at index ((f 2 + c) 48 + n) tap_stride + k of stream 3
-    // (doppler_taps_kernel's draws), and the Doppler shift of sinusoid (n, k)
+    if (w < nfr && !Pw.identity && lane < Pw.n_taps && !dopw)
+        tap[w][lane] = static_tap(f0 + w, lane, a.tap_stride, Pw.coeff, a.offset, a.seed);
+    // 3d (early). phases of the block's Doppler frames and the Doppler shift of sinusoid (n, k): doppler_phase and jakes_shift,
+    // written out (with either call this kernel's instruction stream changes)
     if constexpr (DOPPLER) {
         const float step = 3.14159265358979323846f / (4.0f * kSinusoids);
 #pragma unroll
@@ -523,13 +529,12 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
         }
     }
     __syncthreads();
-    if (w < kGenFramesPerBlock) {                      // g = taps . alpha (same order as channel_taps_kernel); zeros behind L:
-        float2 acc = make_float2(0.f, 0.f);            // the FIR below runs both frames over the longer of the two responses
+    if (w < kGenFramesPerBlock) {                      // g = taps . alpha; zeros behind L: the FIR below runs both frames over
+        float2 acc = make_float2(0.f, 0.f);            // the longer of the two responses
         const int Lw = w == 0 ? L0 : L1;
         if (w < nfr && lane < Lw && !dopw) {
-            if (Pw.identity) {
-                acc = make_float2(lane == 0 ? 1.f : 0.f, 0.f);
-            } else {
+            if (Pw.identity) acc = make_float2(lane == 0 ? 1.f : 0.f, 0.f);
+            else {                                     // (taps_dot_alpha, written out: the call changes this kernel's exec-mask code)
                 for (int k = 0; k < Pw.n_taps; ++k) {
                     const float wgt = Pw.alpha[k * Pw.L + lane];
                     acc.x += tap[w][k].x * wgt;
@@ -596,8 +601,8 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
             const float* th = sTh + (j * 2 + cc) * kSinusoids * 16 + k;
             const float* fc = sFc + (j * 2 + cc) * kSinusoids * 16 + k;
             float sum = 0.f;
-            for (int n = 0; n < kSinusoids; ++n) sum += cosf(6.2831853071795864769f * t * fc[n * 16] + th[n * 16]);
-            const float cf = (j ? P1.coeff : P0.coeff)[k] * 0.14433756729740644113f;          // sqrt(1/48)
+            for (int n = 0; n < kSinusoids; ++n) sum += jakes_cos(t, fc[n * 16], th[n * 16]);
+            const float cf = (j ? P1.coeff : P0.coeff)[k] * kJakesNorm;
             reinterpret_cast<float*>(sTapD + (j * S + sym) * 16 + k)[cc] = sum * cf;
         }
     }
@@ -607,8 +612,8 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
         for (int e = tid; e < n0 + n1; e += 256) {
             const int j = e >= n0 ? 1 : 0, r = e - (j ? n0 : 0), Lj = j ? P1.L : P0.L, nt = j ? P1.n_taps : P0.n_taps;
             const int sym = r / Lj, l = r - sym * Lj;
-            const float* al = (j ? P1.alpha : P0.alpha) + l;
-            const float2* tp = sTapD + (j * S + sym) * 16;
+            const float* al = (j ? P1.alpha : P0.alpha) + l;      // (taps_dot_alpha, written out: the call changes the registers
+            const float2* tp = sTapD + (j * S + sym) * 16;        // this kernel gets)
             float2 acc = make_float2(0.f, 0.f);
             for (int k = 0; k < nt; ++k) {
                 const float wgt = al[k * Lj];
@@ -623,36 +628,31 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
             const int fr = i / (2 * T);
             a.tx_out[(size_t)f0 * 2 * T + i] = reinterpret_cast<const float*>(sTX)[fr * 2 * TP + 2 * kGenFirPad + (i - fr * 2 * T)];
         }
-    // 4. 'same' FIR (the loop of fir_same_kernel) and its power
-    // frequency response of the block's frames (channel_taps_kernel's sum, its twiddles from the table: same arguments, same bits)
+    // frequency response of the block's frames (freq_response, its twiddles from the table: same arguments, same bits)
     if constexpr (DOPPLER) __syncthreads();            // the per-symbol responses are complete
     if (a.H != nullptr) {
+        const auto twt = [](int m) { return tw[m]; };         // (tw is in LDS: static storage, nothing to capture)
         for (int idx = tid; idx < nfr * K; idx += 256) {
             const int fr = idx / K, f = idx - fr * K, Lf = fr == 0 ? L0 : L1;
             if (fr == 0 ? dop0 : dop1) continue;       // (a Doppler frame writes S distinct responses: below)
-            float2 acc = make_float2(0.f, 0.f);
-            for (int l = 0; l < Lf; ++l) {
-                const float2 t2 = tw[(f * l) % K], gl = gs[fr][l];
-                acc.x += gl.x * t2.x - gl.y * t2.y;
-                acc.y += gl.x * t2.y + gl.y * t2.x;
-            }
+            const float2 acc = freq_response(gs[fr], Lf, f, K, twt);
             for (int r = 0; r < a.h_rep; ++r) a.H[((size_t)(f0 + fr) * a.h_rep + r) * K + f] = acc;
         }
-        if constexpr (DOPPLER) {                       // H[f, s] = fft(g[s], K) (doppler_taps_kernel's sum; h_rep == S)
+        if constexpr (DOPPLER) {                       // H[f, s] = fft(g[s], K) (h_rep == S)
             for (int idx = tid; idx < nfr * S * K; idx += 256) {
                 const int fs = idx / K, f = idx - fs * K, fr = fs / S, Lf = fr == 0 ? L0 : L1;
                 if (!(fr == 0 ? dop0 : dop1)) continue;
                 const float2* gp = sGd + fs * 64;
-                float2 acc = make_float2(0.f, 0.f);
+                float2 acc = make_float2(0.f, 0.f);           // (freq_response, written out: the call moves one instruction)
                 for (int l = 0; l < Lf; ++l) {
-                    const float2 t2 = tw[(f * l) % K], gl = gp[l];
-                    acc.x += gl.x * t2.x - gl.y * t2.y;
-                    acc.y += gl.x * t2.y + gl.y * t2.x;
+                    const float2 t2 = tw[(f * l) % K];
+                    cmac(acc, gp[l], t2);
                 }
                 a.H[((size_t)(f0 + fr) * S + (fs - fr * S)) * K + f] = acc;
             }
         }
     }
+    // 4. 'same' FIR and its power
     const int off0 = (L0 - 1) / 2, off1 = (L1 - 1) / 2, Lmax = max(L0, nfr > 1 ? L1 : 0);
     double pw = 0.0;
     {
@@ -673,15 +673,13 @@ __device__ __forceinline__ void gen_static_frames_body(const GenStaticArgs a, co
                 const int lo = dp ? max(0, r0 - NSC + 1) : 0, hi = dp ? min(Lf - 1, r0 + ntf) : Lf - 1;
                 const float2* gp = dp ? sGd + (fr * S + sym) * 64 : gs[fr];
                 for (int l = lo; l <= hi; ++l) {
-                    const float2 v = xf[-l], gl = gp[l];
-                    acc.x += gl.x * v.x - gl.y * v.y;
-                    acc.y += gl.x * v.y + gl.y * v.x;
+                    const float2 v = xf[-l];
+                    cmac(acc, gp[l], v);
                 }
             } else {
                 for (int l = 0; l < ((a.abl & 8) ? 1 : Lmax); ++l) {
-                    const float2 v = xf[-l], gl = gs[fr][l];
-                    acc.x += gl.x * v.x - gl.y * v.y;
-                    acc.y += gl.x * v.y + gl.y * v.x;
+                    const float2 v = xf[-l];
+                    cmac(acc, gs[fr][l], v);
                 }
             }
             yv[q] = acc;
@@ -728,12 +726,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     DCCN_GEN_ARGS_OF_CHAIN(a, P0, P1, a0, gc, co.off[blockIdx.z], blockIdx.z, (int)blockIdx.x)
     gen_static_frames_body<S, K, CP, true>(a, P0, P1, (int)blockIdx.x);
 }
-// x = y / sqrt(mean |y|^2) + noise where a buffer is wanted (the first batch of a pipelined loop, tests, iq dumps): the
-// expression of awgn_kernel on the generator's y and noise.  grid: any; 256 threads.
+// x = y / sqrt(mean |y|^2) + noise where a buffer is wanted (the first batch of a pipelined loop, tests, iq dumps):
+// scale_add_noise on the generator's y and noise, and `noise_power:0` from its partials when npow_out is given.
+// grid: any; 256 threads.  This kernel serves chain groups (common.h).
 static __global__ __launch_bounds__(256) void gen_static_apply_kernel(const float4* y_, const float4* noise_, const double* ppart_, int npart,
                                                                double total, float4* x_, long long n4, const double* npart_noise_,
                                                                int n_noise, float* npow_out_, const ChainOffs co) {
-    const long long coff = co.off[blockIdx.z];                     // chain groups (common.h)
+    const long long coff = co.off[blockIdx.z];
     const float4* __restrict__ y = chain_at(y_, coff);
     const float4* __restrict__ noise = chain_at(noise_, coff);
     const double* __restrict__ ppart = chain_at(ppart_, coff);
@@ -743,25 +742,16 @@ static __global__ __launch_bounds__(256) void gen_static_apply_kernel(const floa
     __shared__ double sh4[4];
     __shared__ float s_inv;
     const float inv = batch_power_inv_scale(ppart, npart, total, sh4, &s_inv);
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-        const float4 v = y[i], z = noise[i];
-        x[i] = make_float4(v.x * inv + z.x, v.y * inv + z.y, v.z * inv + z.z, v.w * inv + z.w);
-    }
-    if (npow_out != nullptr && blockIdx.x == 0) {
-        __syncthreads();
-        double a = 0.0;
-        for (int i = threadIdx.x; i < n_noise; i += 256) a += npart_noise[i];
-        a = wave_sum(a);
-        if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = a;
-        __syncthreads();
-        if (threadIdx.x == 0) npow_out[0] = (float)(((sh4[0] + sh4[1]) + (sh4[2] + sh4[3])) / total);
-    }
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256)
+        x[i] = scale_add_noise(y[i], inv, noise[i]);
+    if (npow_out != nullptr && blockIdx.x == 0) noise_power_from_partials(npart_noise, n_noise, total, sh4, npow_out);
 }
-// the same for a cp=False receiver (model.py:1236-1240 drops the cyclic prefix inside the graph): x_out [frames, S, K, 2] holds
-// the K samples behind the prefix of every symbol, x_out[f, s, 0:K] = y[f, s, CP:CP+K] * inv + noise[f, s, CP:CP+K] -- the scale
-// still that of the whole frames (total = frames * S * (K + CP)), the expression that of the full kernel: the bits of its output,
-// cropped.  In float4s: output i is element i % kw4 of symbol i / kw4 (symbols of all frames are consecutive), whose source
-// symbol has sym4 = 2 (K + CP) / 4 float4s with the window off4 = 2 CP / 4 into it.  grid: any; 256 threads.
+// the same for a cp=False receiver (model.py:1236-1240 drops the cyclic prefix inside the graph): x [frames, S, K, 2] holds the K
+// samples behind the prefix of every symbol, x[f, s, 0:K] = y[f, s, CP:CP+K] * inv + noise[f, s, CP:CP+K] -- the scale still that
+// of the whole frames (total = frames * S * (K + CP)): the bits of the full output, cropped.  In float4s: output i is element
+// i % kw4 of symbol i / kw4 (symbols of all frames are consecutive), whose source symbol has sym4 = 2 (K + CP) / 4 float4s
+// with the window off4 = 2 CP / 4 into it.  Its own loop, not a shared body with a flag: the plain kernel pays no division per
+// element, and behind a common body this kernel's address arithmetic changes.  No chain table.  grid: any; 256 threads.
 static __global__ __launch_bounds__(256) void gen_static_apply_window_kernel(const float4* __restrict__ y, const float4* __restrict__ noise,
                                                                       const double* __restrict__ ppart, int npart, double total,
                                                                       float4* __restrict__ x, long long n4, int kw4, int sym4, int off4,
@@ -772,18 +762,9 @@ static __global__ __launch_bounds__(256) void gen_static_apply_window_kernel(con
     const float inv = batch_power_inv_scale(ppart, npart, total, sh4, &s_inv);
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
         const long long sym = i / kw4, src = sym * sym4 + off4 + (i - sym * kw4);
-        const float4 v = y[src], z = noise[src];
-        x[i] = make_float4(v.x * inv + z.x, v.y * inv + z.y, v.z * inv + z.z, v.w * inv + z.w);
+        x[i] = scale_add_noise(y[src], inv, noise[src]);
     }
-    if (npow_out != nullptr && blockIdx.x == 0) {
-        __syncthreads();
-        double a = 0.0;
-        for (int i = threadIdx.x; i < n_noise; i += 256) a += npart_noise[i];
-        a = wave_sum(a);
-        if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = a;
-        __syncthreads();
-        if (threadIdx.x == 0) npow_out[0] = (float)(((sh4[0] + sh4[1]) + (sh4[2] + sh4[3])) / total);
-    }
+    if (npow_out != nullptr && blockIdx.x == 0) noise_power_from_partials(npart_noise, n_noise, total, sh4, npow_out);
 }
 
 // radio.py:62-88 AWGN_channel, the *in-graph* monitor branch of the receiver graph (ofdmreceiver_np.py:136,151-152):
@@ -802,8 +783,8 @@ static __global__ __launch_bounds__(256) void ingraph_awgn_kernel(const float2* 
     double pw = 0.0;
     if (t < T) {
         const size_t i = (size_t)fr * T + t;
-        const float level = 0.70710678118654752440f * exp10f(-snr_db[fr] * 0.05f);
-        const Philox4 p = philox4x32_10((unsigned long long)i, kStreamNoise, offset, seed);
+        const float level = frame_noise_std(snr_db[fr]);
+        const Philox4 p = philox4x32_10((unsigned long long)i, kStreamNoise, offset, seed);     // (word 2 is used as well: not normal_pair)
         const float amp = fabsf(level * box_muller(p.v[0], p.v[1]).x);
         float sn, cs;
         sincosf(6.2831853071795864769f * uniform01(p.v[2]), &sn, &cs);
@@ -816,15 +797,12 @@ static __global__ __launch_bounds__(256) void ingraph_awgn_kernel(const float2* 
         }
         pw = (double)nr * nr + (double)ni * ni;
     }
-    pw = wave_sum(pw);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = pw;
-    __syncthreads();
-    if (threadIdx.x == 0) noise_partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    pw = block_sum4(pw, sh);
+    if (threadIdx.x == 0) noise_partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = pw;
 }
 
-// radio.py:376-407 Jakes sum-of-sinusoids Doppler: per OFDM symbol s (t = s * n_sc / Fs) and tap k
-//   mu_re = sqrt(1/48) sum_n cos(2 pi t Fd cos(a_n + a0_k) + th_re[n,k]),  a_n = (n - 0.5) pi / (4*48), a0_k = k pi/(4*48)
-//   mu_im likewise with cos(a_n - a0_k) and th_im;  tap = (mu_re + i mu_im) coeff_k;  g[s] = taps[s] . alpha;  H[s] = fft(g[s])
+// radio.py:376-407 Jakes sum-of-sinusoids Doppler (doppler_phase, jakes_shift, jakes_cos above): per OFDM symbol s
+// (t = s * n_sc / Fs) and tap k the tap (mu_re + i mu_im) coeff_k sqrt(1/48);  g[s] = taps[s] . alpha;  H[s] = fft(g[s])
 // theta_in [frames, 2, 48, n_taps] (uniform phases in [0, 2 pi)) == nullptr: draw them.  One block per frame.
 static __global__ __launch_bounds__(64) void doppler_taps_kernel(const float* __restrict__ theta_in,
                                                           const float* __restrict__ coeff,
@@ -836,39 +814,29 @@ static __global__ __launch_bounds__(64) void doppler_taps_kernel(const float* __
     __shared__ float2 tap[16 * 16];          // [S][n_taps], S <= 16
     __shared__ float2 gs[16 * 64];           // [S][L]
     const int fr = frames ? frames[blockIdx.x] : (int)blockIdx.x;
-    const float step = 3.14159265358979323846f / (4.0f * kSinusoids);
     for (int e = threadIdx.x; e < S * n_taps; e += 64) {
         const int sym = e / n_taps, k = e % n_taps;
-        const float t = (float)sym * t_sym, a0 = (float)(k + 1) * step;
+        const float t = (float)sym * t_sym;
         float sr = 0.f, si = 0.f;
         for (int n = 0; n < kSinusoids; ++n) {
-            const float an = ((float)(n + 1) - 0.5f) * step;
             float thr, thi;
             if (theta_in) {
                 thr = theta_in[(((size_t)fr * 2 + 0) * kSinusoids + n) * tap_stride + k];
                 thi = theta_in[(((size_t)fr * 2 + 1) * kSinusoids + n) * tap_stride + k];
             } else {
-                const unsigned long long base = ((unsigned long long)fr * 2 * kSinusoids + n) * tap_stride + k;
-                thr = 6.2831853071795864769f *
-                      uniform01(philox4x32_10(base, kStreamDoppler, offset, seed).v[0]);
-                thi = 6.2831853071795864769f *
-                      uniform01(philox4x32_10(base + (unsigned long long)kSinusoids * tap_stride, kStreamDoppler, offset, seed).v[0]);
+                thr = doppler_phase(fr, 0, n, k, tap_stride, offset, seed);
+                thi = doppler_phase(fr, 1, n, k, tap_stride, offset, seed);
             }
-            sr += cosf(6.2831853071795864769f * t * (Fd * cosf(an + a0)) + thr);
-            si += cosf(6.2831853071795864769f * t * (Fd * cosf(an - a0)) + thi);
+            sr += jakes_cos(t, jakes_shift(Fd, 0, n, k), thr);
+            si += jakes_cos(t, jakes_shift(Fd, 1, n, k), thi);
         }
-        const float c = coeff[k] * 0.14433756729740644113f;          // sqrt(1/48)
+        const float c = coeff[k] * kJakesNorm;
         tap[sym * n_taps + k] = make_float2(sr * c, si * c);
     }
     __syncthreads();
     for (int e = threadIdx.x; e < S * L; e += 64) {
         const int sym = e / L, l = e % L;
-        float2 a = make_float2(0.f, 0.f);
-        for (int k = 0; k < n_taps; ++k) {
-            const float w = alpha[k * L + l];
-            a.x += tap[sym * n_taps + k].x * w;
-            a.y += tap[sym * n_taps + k].y * w;
-        }
+        const float2 a = taps_dot_alpha(tap + sym * n_taps, alpha, n_taps, L, l);
         gs[e] = a;
         g[(size_t)fr * g_stride + sym * L + l] = a;
     }
@@ -876,13 +844,10 @@ static __global__ __launch_bounds__(64) void doppler_taps_kernel(const float* __
     if (H) {
         for (int e = threadIdx.x; e < S * nfft; e += 64) {
             const int sym = e / nfft, f = e % nfft;
-            float2 a = make_float2(0.f, 0.f);
-            for (int l = 0; l < L; ++l) {
-                float sn, cs;
-                sincosf(-6.2831853071795864769f * (float)((f * l) % nfft) / (float)nfft, &sn, &cs);
-                const float2 v = gs[sym * L + l];
-                a.x += v.x * cs - v.y * sn;
-                a.y += v.x * sn + v.y * cs;
+            float2 a = make_float2(0.f, 0.f);              // (freq_response, written out on gs[sym * L + l]: called on the
+            for (int l = 0; l < L; ++l) {                  // pointer gs + sym * L, this kernel loses a wait state)
+                const float2 w = twiddle_of((f * l) % nfft, nfft);
+                cmac(a, gs[sym * L + l], w);
             }
             H[((size_t)fr * S + sym) * nfft + f] = a;
         }
@@ -915,18 +880,15 @@ static __global__ __launch_bounds__(256) void fir_doppler_kernel(const float2* _
                 const int r = tl + off - l;                     // position relative to the symbol start
                 const int u = sym * n_sc + r;
                 if (r < -n_taps || r >= n_sc || u < 0) continue;
-                const float2 v = xf[u], c = gf[l];
-                a.x += c.x * v.x - c.y * v.y;
-                a.y += c.x * v.y + c.y * v.x;
+                const float2 v = xf[u];
+                cmac(a, gf[l], v);
             }
             y[(size_t)fr * T + t] = a;
             pw += (double)a.x * a.x + (double)a.y * a.y;
         }
     }
-    pw = wave_sum(pw);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = pw;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[pbase + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    pw = block_sum4(pw, sh);
+    if (threadIdx.x == 0) partial[pbase + blockIdx.x] = pw;
 }
 
 }  // namespace dccn

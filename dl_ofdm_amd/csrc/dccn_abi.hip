@@ -1515,6 +1515,19 @@ static int rx_issue_backward(const dccn_rx_shape* sh, const dccn_rx_buffers* b, 
     return DCCN_OK;
 }
 
+// the optimizer launch: the instantiation for the dense gradient's split count (2..6, windowed 2..4; any other count takes
+// the runtime form).  win: the windowed instantiation of R0 rides, a kernel of its own, launched by such steps only
+static void launch_adam_rx(bool win, int splits, long long blocks, hipStream_t s, const AdamRxArgs& aa, const dccn_adam_hparams& hp) {
+    void (*kern)(const AdamRxArgs, const dccn_adam_hparams) = win ? adam_rx_window_kernel<0> : adam_rx_kernel<0>;
+    switch (splits) {
+        case 2: kern = win ? adam_rx_window_kernel<2> : adam_rx_kernel<2>; break;
+        case 3: kern = win ? adam_rx_window_kernel<3> : adam_rx_kernel<3>; break;
+        case 4: kern = win ? adam_rx_window_kernel<4> : adam_rx_kernel<4>; break;
+        case 5: if (!win) kern = adam_rx_kernel<5>; break;
+        case 6: if (!win) kern = adam_rx_kernel<6>; break;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp);
+}
 static int rx_issue_update(const dccn_rx_shape* sh, const dccn_rx_buffers* b, const RxStepPlan& p, dccn_adam_hparams hp,
                            hipStream_t s, const StepTraceScope& trace, RxStepCarry* k, OverlapJoin* ojoin) {
     const RxLayout& L = p.L;
@@ -1560,22 +1573,7 @@ static int rx_issue_update(const dccn_rx_shape* sh, const dccn_rx_buffers* b, co
         if (p.gen_window) aa.nv = norm_virtual_gen_window(p.gen, npart, const_cast<float*>(b->x_next));
         else if (p.gen) aa.nv = norm_virtual_gen(p.gen, npart, const_cast<float*>(b->x_next));
     }
-    if (p.ride_opt && p.gen_window) {
-        // the windowed instantiation of R0 rides: a kernel of its own (every other step launches what it launched before)
-        switch (k->ds.splits) {
-            case 2: hipLaunchKernelGGL(adam_rx_window_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
-            case 3: hipLaunchKernelGGL(adam_rx_window_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
-            case 4: hipLaunchKernelGGL(adam_rx_window_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
-            default: hipLaunchKernelGGL(adam_rx_window_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
-        }
-    } else switch (k->ds.splits) {
-        case 2: hipLaunchKernelGGL(adam_rx_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
-        case 3: hipLaunchKernelGGL(adam_rx_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
-        case 4: hipLaunchKernelGGL(adam_rx_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
-        case 5: hipLaunchKernelGGL(adam_rx_kernel<5>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
-        case 6: hipLaunchKernelGGL(adam_rx_kernel<6>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
-        default: hipLaunchKernelGGL(adam_rx_kernel<0>, dim3((unsigned)blocks), dim3(256), 0, s, aa, hp); break;
-    }
+    launch_adam_rx(p.ride_opt && p.gen_window, k->ds.splits, blocks, s, aa, hp);
     DCCN_LAUNCH_CHECK();
     trace.none();
     if (p.norm_after) {

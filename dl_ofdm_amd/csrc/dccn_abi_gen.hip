@@ -61,6 +61,16 @@ static ChanWs chan_carve(Carver& c, int frames, int T, int gstride) {
     c.take<float>(4);       // (four floats no launch uses: part of the size the callers allocate)
     return w;
 }
+// enabled (nobody wants the frequency response and the taps are drawn here): the FIR blocks draw the taps themselves
+static TapGen tap_gen_of(bool enabled, const float* coeff, const float* alpha, int n_taps, int identity, int tap_stride,
+                         unsigned offset, unsigned long long seed) {
+    TapGen tg;
+    memset(&tg, 0, sizeof(tg));
+    tg.enabled = enabled ? 1 : 0;
+    tg.coeff = coeff; tg.alpha = alpha; tg.n_taps = n_taps; tg.identity = identity; tg.tap_stride = tap_stride;
+    tg.offset = offset; tg.seed = seed;
+    return tg;
+}
 size_t dccn_channel_awgn_workspace_size(int frames, int T, int L) {
     if (frames <= 0 || T <= 0 || L <= 0) return 0;
     return carved_bytes([&](Carver& c) { chan_carve(c, frames, T, L); });
@@ -91,12 +101,7 @@ int dccn_channel_awgn(const float* tx, const float* taps_in, const float* coeff,
     Carver c(workspace, workspace_bytes);
     const ChanWs w = chan_carve(c, frames, T, L);
     float *g = w.g, *y = w.y; double* partial = w.partial; const int bx = w.bx;
-    // nobody wants the frequency response and the taps are drawn here: the FIR blocks draw them themselves
-    TapGen tg;
-    memset(&tg, 0, sizeof(tg));
-    tg.enabled = (H == nullptr && taps_in == nullptr) ? 1 : 0;
-    tg.coeff = coeff; tg.alpha = alpha; tg.n_taps = n_taps; tg.identity = identity; tg.tap_stride = n_taps;
-    tg.offset = offset; tg.seed = seed;
+    const TapGen tg = tap_gen_of(H == nullptr && taps_in == nullptr, coeff, alpha, n_taps, identity, n_taps, offset, seed);
     if (!tg.enabled) {
         hipLaunchKernelGGL(channel_taps_kernel, dim3(frames), dim3(64), 0, s, taps_in, coeff, alpha, (float2*)g, (float2*)H,
                            n_taps, L, nfft, identity, offset, seed, (const int*)nullptr, n_taps, L, 1);
@@ -118,41 +123,44 @@ int dccn_gen_static_supported(int S, int K, int CP) {
 }
 int dccn_gen_static_partials(int frames) { return frames > 0 ? ceil_div(frames, kGenFramesPerBlock) : 0; }
 int dccn_gen_static_frames(const dccn_gen_static* g, dccn_stream_t stream) { return gen_static_launch(g, (hipStream_t)stream); }
-int dccn_gen_static_apply(const dccn_gen_static* g, float* x_out, float* noise_power, dccn_stream_t stream) {
+// x = y / sqrt(mean |y|^2) + noise into x_out: the whole frames, or (window) the batch of a cp=False receiver, the K samples
+// behind the cyclic prefix of every symbol.  noise_power is served when the generator launch left noise partials.
+static int gen_static_apply_launch(const dccn_gen_static* g, float* x_out, float* noise_power, bool window, hipStream_t s) {
     if (!gen_static_ok(g) || !x_out || !aligned16(x_out)) return DCCN_ERR_INVALID_ARG;
     const int T = g->S * (g->K + g->CP);
-    const long long n4 = (long long)g->frames * T * 2 / 4;
-    if (((long long)g->frames * T * 2) % 4 != 0) return DCCN_ERR_INVALID_ARG;
+    long long n4;                             // float4s of x_out
+    if (window) {
+        // (gen_static_ok: K = 64 and CP = 16 or 4, so a symbol, its window and the window's offset are whole float4s)
+        if ((2 * g->K) % 4 != 0 || (2 * g->CP) % 4 != 0) return DCCN_ERR_INVALID_ARG;
+        DCCN_NO_CHAINS();                     // (that launch carries no chain table: inside a group it would serve chain 0 only)
+        n4 = (long long)g->frames * g->S * (2 * g->K / 4);
+    } else {
+        if (((long long)g->frames * T * 2) % 4 != 0) return DCCN_ERR_INVALID_ARG;
+        n4 = (long long)g->frames * T * 2 / 4;
+    }
     const int np = dccn_gen_static_partials(g->frames);
     long long blocks = ceil_div_ll(n4, 256);
     if (blocks > 4 * kCUs) blocks = 4 * kCUs;
-    DCCN_LAUNCH_CHAINS_Z(gen_static_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                         reinterpret_cast<const float4*>(g->y), reinterpret_cast<const float4*>(g->noise),
-                         (const double*)g->power_partial, np, (double)g->frames * (double)T, reinterpret_cast<float4*>(x_out), n4,
-                         (const double*)((noise_power && g->noise_partial) ? g->noise_partial : nullptr), np,
-                         (noise_power && g->noise_partial) ? noise_power : nullptr);
+    const float4 *y = reinterpret_cast<const float4*>(g->y), *noise = reinterpret_cast<const float4*>(g->noise);
+    const double total = (double)g->frames * (double)T;
+    const bool want_np = noise_power && g->noise_partial;
+    const double* npart = want_np ? g->noise_partial : nullptr;
+    float* npow = want_np ? noise_power : nullptr;
+    if (window)
+        hipLaunchKernelGGL(gen_static_apply_window_kernel, dim3((unsigned)blocks), dim3(256), 0, s, y, noise, (const double*)g->power_partial,
+                           np, total, reinterpret_cast<float4*>(x_out), n4, 2 * g->K / 4, 2 * (g->K + g->CP) / 4, 2 * g->CP / 4, npart,
+                           np, npow);
+    else
+        DCCN_LAUNCH_CHAINS_Z(gen_static_apply_kernel, dim3((unsigned)blocks), dim3(256), 0, s, y, noise, (const double*)g->power_partial,
+                             np, total, reinterpret_cast<float4*>(x_out), n4, npart, np, npow);
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
 }
-// the batch of a cp=False receiver: the K samples behind the cyclic prefix of every symbol (gen_static_apply_window_kernel)
+int dccn_gen_static_apply(const dccn_gen_static* g, float* x_out, float* noise_power, dccn_stream_t stream) {
+    return gen_static_apply_launch(g, x_out, noise_power, false, (hipStream_t)stream);
+}
 int dccn_gen_static_apply_window(const dccn_gen_static* g, float* x_out, float* noise_power, dccn_stream_t stream) {
-    if (!gen_static_ok(g) || !x_out || !aligned16(x_out)) return DCCN_ERR_INVALID_ARG;
-    // (gen_static_ok: K = 64 and CP = 16 or 4, so a symbol, its window and the window's offset are whole float4s)
-    if ((2 * g->K) % 4 != 0 || (2 * g->CP) % 4 != 0) return DCCN_ERR_INVALID_ARG;
-    DCCN_NO_CHAINS();             // (the launch carries no chain table: inside a group it would serve chain 0 only)
-    const int T = g->S * (g->K + g->CP), kw4 = 2 * g->K / 4;
-    const long long n4 = (long long)g->frames * g->S * kw4;
-    const int np = dccn_gen_static_partials(g->frames);
-    long long blocks = ceil_div_ll(n4, 256);
-    if (blocks > 4 * kCUs) blocks = 4 * kCUs;
-    hipLaunchKernelGGL(gen_static_apply_window_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const float4*>(g->y), reinterpret_cast<const float4*>(g->noise),
-                       (const double*)g->power_partial, np, (double)g->frames * (double)T, reinterpret_cast<float4*>(x_out), n4, kw4,
-                       2 * (g->K + g->CP) / 4, 2 * g->CP / 4,
-                       (const double*)((noise_power && g->noise_partial) ? g->noise_partial : nullptr), np,
-                       (noise_power && g->noise_partial) ? noise_power : nullptr);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return gen_static_apply_launch(g, x_out, noise_power, true, (hipStream_t)stream);
 }
 
 size_t dccn_channel_doppler_awgn_workspace_size(int frames, int T, int L, int S) {
@@ -221,11 +229,7 @@ int dccn_channel_groups_awgn(const float* tx, const dccn_channel_group* groups, 
         if (q.n_frames == 0) continue;
         if (q.identity || q.Fd <= 0.f) {
             const int L = q.identity ? 1 : q.L;
-            TapGen tg;                          // (see dccn_channel_awgn)
-            memset(&tg, 0, sizeof(tg));
-            tg.enabled = (H == nullptr && taps_in == nullptr) ? 1 : 0;
-            tg.coeff = q.coeff; tg.alpha = q.alpha; tg.n_taps = q.n_taps; tg.identity = q.identity; tg.tap_stride = 16;
-            tg.offset = offset; tg.seed = seed;
+            const TapGen tg = tap_gen_of(H == nullptr && taps_in == nullptr, q.coeff, q.alpha, q.n_taps, q.identity, 16, offset, seed);
             if (!tg.enabled) {
                 hipLaunchKernelGGL(channel_taps_kernel, dim3(q.n_frames), dim3(64), 0, s, taps_in, q.coeff, q.alpha, (float2*)g,
                                    (float2*)H, q.n_taps, L, nfft, q.identity, offset, seed, q.frames, 16, gstride, S);

@@ -66,15 +66,9 @@ struct EqOptArgs : EqOptPtrs {
 };
 static_assert(sizeof(EqOptArgs) + sizeof(dccn_adam_hparams) + sizeof(ChainOffs) <= 4096, "kernel argument block");
 
-struct AdamCoef {
-    float alpha, omb1, omb2, eps;
-};
 __device__ __forceinline__ void eq_adam_one(const EqOptPtrs& a, const AdamCoef& k, const long long j, const float g) {
     float p = a.param[j], mm = a.m[j], vv = a.v[j];
-    const float ge = g + (a.reg_coef ? a.reg_coef[j] : 0.f) * p;
-    mm += (ge - mm) * k.omb1;
-    vv += (ge * ge - vv) * k.omb2;
-    p -= (mm * k.alpha) / (sqrtf(vv) + k.eps);
+    adam_update(p, mm, vv, g, a.reg_coef ? a.reg_coef[j] : 0.f, 1.0f, k);      // (no gate: norm_adam.h)
     a.param[j] = p; a.m[j] = mm; a.v[j] = vv;
 }
 
@@ -138,12 +132,7 @@ __device__ __forceinline__ void eq_opt_sum(const EqOptPtrs& a, const EqOptJob& J
             float p[4] = {p4.x, p4.y, p4.z, p4.w}, mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
             const float g[4] = {g4.x, g4.y, g4.z, g4.w}, cc[4] = {c4.x, c4.y, c4.z, c4.w};
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float ge = g[e] + cc[e] * p[e];
-                mm[e] += (ge - mm[e]) * k.omb1;
-                vv[e] += (ge * ge - vv[e]) * k.omb2;
-                p[e] -= (mm[e] * k.alpha) / (sqrtf(vv[e]) + k.eps);
-            }
+            for (int e = 0; e < 4; ++e) adam_update(p[e], mm[e], vv[e], g[e], cc[e], 1.0f, k);
             *reinterpret_cast<float4*>(a.param + j) = make_float4(p[0], p[1], p[2], p[3]);
             *reinterpret_cast<float4*>(a.m + j) = make_float4(mm[0], mm[1], mm[2], mm[3]);
             *reinterpret_cast<float4*>(a.v + j) = make_float4(vv[0], vv[1], vv[2], vv[3]);
@@ -286,8 +275,7 @@ __device__ __forceinline__ void eq_ride_body(const EqRideArgs& r, const dccn_ada
     const EqOptJob J = r.job[j].at_chain(coff);
     EqOptPtrs p = r.p;
     p.move_to_chain(coff);
-    AdamCoef k;
-    k.alpha = p.state->alpha; k.omb1 = 1.0f - hp.beta1; k.omb2 = 1.0f - hp.beta2; k.eps = hp.eps;
+    const AdamCoef k = adam_coef(p.state, hp);
     if (J.kind == EQJ_CONV2D_FOLD) eq_opt_conv2d(p, J, k, bx - J.block0);
     else eq_opt_sum(p, J, k, bx - J.block0);
 }
@@ -323,8 +311,7 @@ static __global__ __launch_bounds__(256) void eq_opt_kernel(const EqOptArgs a0, 
     }
     EqOptPtrs a = a0;
     a.move_to_chain(coff);
-    AdamCoef k;
-    k.alpha = a.state->alpha; k.omb1 = 1.0f - hp.beta1; k.omb2 = 1.0f - hp.beta2; k.eps = hp.eps;
+    const AdamCoef k = adam_coef(a.state, hp);
     if (J.kind == EQJ_SUM) {
         eq_opt_sum(a, J, k, bx);
     } else if (J.kind == EQJ_CCONV_FOLD) {

@@ -371,12 +371,7 @@ static __global__ __launch_bounds__(256) void eq_prep_kernel(const float* x_, fl
     float* __restrict__ T = chain_at(T_, coff);
     float* __restrict__ bias_eff = chain_at(bias_eff_, coff);
     dccn_adam_state* __restrict__ adam = chain_at(adam_, coff);
-    if (adam != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-        adam->alpha = adam_alpha(adam, hp);
-        adam->beta1_power = adam->beta1_power * hp.beta1;
-        adam->beta2_power = adam->beta2_power * hp.beta2;
-        adam->global_step = adam->global_step + 1.0f;
-    }
+    if (adam != nullptr && blockIdx.x == 0 && threadIdx.x == 0) adam_advance(adam, hp);
     if ((int)blockIdx.x < frames) layer_norm_fwd_body(x, y, nullptr, nullptr, cols, eps, (int)blockIdx.x);
     else cconv2d_same_expand_body(w, bias, T, bias_eff, L, W, L, W, (int)blockIdx.x - frames, (int)gridDim.x - frames);
 }

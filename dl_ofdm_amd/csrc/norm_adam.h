@@ -18,27 +18,54 @@ constexpr int kNormRowsPerBlock = 32;   // rows handled by one normalise block
 #endif
 constexpr int kNormFusedCG = DCCN_NORM_CG, kNormFusedRPT = DCCN_NORM_RPT;
 
-__device__ __forceinline__ float adam_alpha(const dccn_adam_state* st, const dccn_adam_hparams& hp) {
+// the optimizer's per-step bookkeeping, by exactly one thread of a step's first launch: alpha = lr*sqrt(1-b2p)/(1-b1p) for THIS
+// step with lr = lr0*rate^floor(step/decay_steps), then the state advances (beta powers *= beta, global_step += 1)
+__device__ __forceinline__ void adam_advance(dccn_adam_state* st, const dccn_adam_hparams& hp) {
     const float lr = hp.lr0 * powf(hp.decay_rate, floorf(st->global_step / hp.decay_steps));
-    return lr * sqrtf(1.0f - st->beta2_power) / (1.0f - st->beta1_power);
+    st->alpha = lr * sqrtf(1.0f - st->beta2_power) / (1.0f - st->beta1_power);
+    st->beta1_power = st->beta1_power * hp.beta1;
+    st->beta2_power = st->beta2_power * hp.beta2;
+    st->global_step = st->global_step + 1.0f;
+}
+// one element of TF ApplyAdam: m += (g-m)*(1-b1); v += (g*g-v)*(1-b2); p -= m*alpha/(sqrt(v)+eps), g = grad + gate*c*param
+// (c: the element's regulariser coefficient)
+struct AdamCoef {
+    float alpha, omb1, omb2, eps;
+};
+__device__ __forceinline__ AdamCoef adam_coef(const dccn_adam_state* st, const dccn_adam_hparams& hp) {
+    AdamCoef k;
+    k.alpha = st->alpha; k.omb1 = 1.0f - hp.beta1; k.omb2 = 1.0f - hp.beta2; k.eps = hp.eps;
+    return k;
+}
+__device__ __forceinline__ void adam_update(float& p, float& m, float& v, const float g, const float c, const float gate,
+                                            const AdamCoef& k) {
+    const float ge = g + (gate * c) * p;
+    m += (ge - m) * k.omb1;
+    v += (ge * ge - v) * k.omb2;
+    p -= (m * k.alpha) / (sqrtf(v) + k.eps);
+}
+// complex_clip (dev/py/complex.py:24-26) of one (I, Q) pair, and the power of the clipped pair
+__device__ __forceinline__ float2 clip_pair(const float i, const float q, const float peak) {
+    const float l2 = sqrtf(i * i + q * q);
+    const float sc = peak / fmaxf(l2, peak);
+    return make_float2(i * sc, q * sc);
+}
+__device__ __forceinline__ float pair_power(const float2 c) { return c.x * c.x + c.y * c.y; }
+__device__ __forceinline__ float clip_pair_power(const float i, const float q, const float peak) {
+    return pair_power(clip_pair(i, q, peak));
 }
 
 // ---- R0 stage 1: per-column partial sum / sum of squares in fp64 ------------------------
 // grid (ceil(cols/4/64), kNormRowChunks), block (64,4).  partial[(chunk*cols + c)*2 + {0,1}]
 // In the fused training step the first thread of the first block also does the optimizer's
 // per-step bookkeeping (it runs long before the Adam kernel of this step and after the one of the
-// previous step): alpha for THIS step from the current global_step / beta powers, then advance them.
+// previous step): adam_advance.
 static __global__ __launch_bounds__(256) void moments_kernel(const float* __restrict__ x, int batch, int cols,
                                                       double* __restrict__ partial,
                                                       dccn_adam_state* __restrict__ adam, dccn_adam_hparams hp) {
     __shared__ double red[4][64][8];
     const int tx = threadIdx.x, ty = threadIdx.y;
-    if (adam != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && tx == 0 && ty == 0) {
-        adam->alpha = adam_alpha(adam, hp);
-        adam->beta1_power = adam->beta1_power * hp.beta1;
-        adam->beta2_power = adam->beta2_power * hp.beta2;
-        adam->global_step = adam->global_step + 1.0f;
-    }
+    if (adam != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && tx == 0 && ty == 0) adam_advance(adam, hp);
     const int c4 = (blockIdx.x * 64 + tx) * 4;
     const int rows_per_chunk = (batch + kNormRowChunks - 1) / kNormRowChunks;
     const int r0 = blockIdx.y * rows_per_chunk;
@@ -176,24 +203,16 @@ static __global__ __launch_bounds__(256) void normalise_kernel(const float* __re
                     if (c4 + e < cols) y[off + e] = o[e];
             }
             if (power_partial != nullptr) {
-                // complex_clip (dev/py/complex.py:24-26): pairs (I,Q) = (o0,o1), (o2,o3); cols is even
+                // pairs (I,Q) = (o0,o1), (o2,o3); cols is even
 #pragma unroll
-                for (int e = 0; e < 4; e += 2) {
-                    if (c4 + e + 1 < cols) {
-                        const float l2 = sqrtf(o[e] * o[e] + o[e + 1] * o[e + 1]);
-                        const float sc = peak / fmaxf(l2, peak);
-                        const float ci = o[e] * sc, cq = o[e + 1] * sc;
-                        pw += (double)(ci * ci + cq * cq);
-                    }
-                }
+                for (int e = 0; e < 4; e += 2)
+                    if (c4 + e + 1 < cols) pw += (double)clip_pair_power(o[e], o[e + 1], peak);
             }
         }
     }
     if (power_partial != nullptr) {
-        pw = wave_sum(pw);
-        if ((lin & 63) == 0) red[lin >> 6] = pw;
-        __syncthreads();
-        if (lin == 0) power_partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        pw = block_sum4(pw, red, lin);
+        if (lin == 0) power_partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = pw;
     }
 }
 
@@ -210,7 +229,7 @@ static __global__ __launch_bounds__(256) void normalise_kernel(const float* __re
 // Virtual input (round 5, the fused device generator of datagen.h): the batch to normalise is not in memory as x but as the
 // two terms of dev/py/radio.py:513-526 AWGN_channel_np, x = y / sqrt(mean |y|^2 over the batch) + noise -- y the channel
 // output, noise already scaled per frame, the batch power as <= 2048 per-block partial sums of the generator launch.  R0 forms
-// x in registers on the way in (the expression and the order of awgn_kernel: the same bits as the materialised input), so
+// x in registers on the way in (batch_power_inv_scale and scale_add_noise, as awgn_kernel: the same bits as the materialised input), so
 // the AWGN launch and a 5 MB round trip of x disappear.  y == nullptr: plain input.
 // Windowed virtual input (cp=False receivers, model.py:1236-1240: the graph drops the cyclic prefix and the C-Conv sees K
 // samples per symbol): the generator still writes whole symbols of wsym = 2 (K + CP) floats, R0 reads the 2 K floats that
@@ -260,7 +279,8 @@ inline NormVirtual norm_virtual_gen_window(const dccn_gen_static* g, int npart, 
     return v;
 }
 // 1 / sqrt(mean |y|^2): every block of a 256-thread launch adds the partial sums in the same fixed order (thread t: t, t + 256,
-// ...; DPP wave sum; the four wave sums as (0 + 1) + (2 + 3)), so all blocks -- and awgn_kernel, and R0 -- get the same bits
+// ...; the block sum of common.h block_sum4), so all blocks -- awgn_kernel's, the apply kernels', R0's -- get the same bits
+// (block_sum4 written out: R0 rides on the optimizer launches, whose register assignment the call changes)
 __device__ __forceinline__ float batch_power_inv_scale(const double* __restrict__ ppart, const int npart, const double total,
                                                        double* sh4, float* s_inv) {
     double a = 0.0;
@@ -272,6 +292,24 @@ __device__ __forceinline__ float batch_power_inv_scale(const double* __restrict_
     __syncthreads();
     return *s_inv;
 }
+// radio.py:524-526 AWGN_channel_np: x = y / sqrt(mean |y|^2) + noise, one multiply and one add per float (awgn_kernel, the
+// apply kernels and R0's virtual input form the batch with this expression: the same bits)
+__device__ __forceinline__ float2 scale_add_noise(const float2 y, const float inv, const float2 z) {
+    return make_float2(y.x * inv + z.x, y.y * inv + z.y);
+}
+__device__ __forceinline__ float4 scale_add_noise(const float4 y, const float inv, const float4 z) {
+    return make_float4(y.x * inv + z.x, y.y * inv + z.y, y.z * inv + z.z, y.w * inv + z.w);
+}
+// `noise_power:0` = mean |noise|^2 from the generator's per-block partials, by one block of a 256-thread launch (the condition is
+// the caller's, block-uniform); sh4 is the array the block used for the sum above, hence the barrier in front
+__device__ __forceinline__ void noise_power_from_partials(const double* __restrict__ npart_noise, const int n_noise,
+                                                          const double total, double* sh4, float* __restrict__ npow_out) {
+    __syncthreads();
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n_noise; i += 256) a += npart_noise[i];
+    a = block_sum4(a, sh4);
+    if (threadIdx.x == 0) npow_out[0] = (float)(a / total);
+}
 
 // WIN: the windowed virtual input (always virtual; its own instantiation, carried by adam_rx_window_kernel only -- every other
 // caller keeps the code it had)
@@ -282,7 +320,6 @@ __device__ __forceinline__ void norm_fused_body(const float* __restrict__ x, flo
                                                 dccn_adam_state* __restrict__ adam, dccn_adam_hparams hp,
                                                 const int bidx, const int nblk, const NormVirtual nv = norm_virtual_none()) {
     constexpr int NW = 2 * CG;                        // waves per block
-    constexpr int RS = 64 / CG;                       // row slots per wave
     __shared__ double red[NW][CG][8];
     __shared__ double stat[CG][8];
     __shared__ double pred[NW > 4 ? NW : 4];
@@ -292,12 +329,7 @@ __device__ __forceinline__ void norm_fused_body(const float* __restrict__ x, flo
     const bool virt = WIN || (NW == 4 && nv.y != nullptr);     // (kernel argument: block-uniform; 256-thread blocks only)
     float inv_scale = 1.0f;
     if (virt) inv_scale = batch_power_inv_scale(nv.ppart, nv.npart, nv.total, pred, &s_inv);
-    if (adam != nullptr && bidx == 0 && t == 0) {
-        adam->alpha = adam_alpha(adam, hp);
-        adam->beta1_power = adam->beta1_power * hp.beta1;
-        adam->beta2_power = adam->beta2_power * hp.beta2;
-        adam->global_step = adam->global_step + 1.0f;
-    }
+    if (adam != nullptr && bidx == 0 && t == 0) adam_advance(adam, hp);
     // XCD-aware strip order: workgroups go round-robin over the 8 XCDs (each with its own L2), and strips that
     // share 128-byte lines of x are neighbours -- so XCD k takes the k-th run of consecutive strips
     const int per_xcd = nblk / 8;
@@ -323,9 +355,8 @@ __device__ __forceinline__ void norm_fused_body(const float* __restrict__ x, flo
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int p = 0; p < RPT; ++p) {               // radio.py:524-526, as awgn_kernel evaluates it
-            v[p] = make_float4(v[p].x * inv_scale + nz[p].x, v[p].y * inv_scale + nz[p].y, v[p].z * inv_scale + nz[p].z,
-                               v[p].w * inv_scale + nz[p].w);
+        for (int p = 0; p < RPT; ++p) {
+            v[p] = scale_add_noise(v[p], inv_scale, nz[p]);
             if (nv.x_out != nullptr && live && slot + 128 * p < batch)
                 *reinterpret_cast<float4*>(nv.x_out + (size_t)(slot + 128 * p) * cols + c4) = v[p];
         }
@@ -368,9 +399,8 @@ __device__ __forceinline__ void norm_fused_body(const float* __restrict__ x, flo
     for (int e = 0; e < 4; ++e) {
         mean[e] = stat[cg][e] / (double)batch;
         double var = stat[cg][4 + e] / (double)batch - mean[e] * mean[e];
-        q[e] = (var < 0.0 ? 0.0 : var) * (double)batch;
-    }
-    (void)RS;
+        q[e] = (var < 0.0 ? 0.0 : var) * (double)batch;     // (times batch here, divided by it below: two fp64 roundings,
+    }                                                       // not an identity -- they decide the bits of varf)
     float inv[4], sh[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -405,14 +435,7 @@ __device__ __forceinline__ void norm_fused_body(const float* __restrict__ x, flo
                     // peak / peak = 1, so the clipped power is the sum of squares already at hand -- same bits as the
                     // general form below, without its square root and division
                     const float sq = o[e] * o[e] + o[e + 1] * o[e + 1];
-                    if (sq <= peak * peak) {
-                        pw += (double)sq;
-                    } else {
-                        const float l2 = sqrtf(sq);
-                        const float sc = peak / fmaxf(l2, peak);
-                        const float ci = o[e] * sc, cq = o[e + 1] * sc;
-                        pw += (double)(ci * ci + cq * cq);
-                    }
+                    pw += (double)(sq <= peak * peak ? sq : clip_pair_power(o[e], o[e + 1], peak));
                 }
             }
         }
@@ -428,7 +451,7 @@ __device__ __forceinline__ void norm_fused_body(const float* __restrict__ x, flo
             power_partial[bidx] = a;              // (idle strips past the last column contribute 0)
         }
     }
-    if (virt && nv.npow_out != nullptr && bidx == 0) {          // `noise_power:0`: mean |noise|^2 from the generator's partials
+    if (virt && nv.npow_out != nullptr && bidx == 0) {          // noise_power_from_partials, written out (see batch_power_inv_scale)
         __syncthreads();
         double a = 0.0;
         for (int i = t; i < nv.n_noise; i += 256) a += nv.npart_noise[i];
@@ -475,11 +498,9 @@ static __global__ __launch_bounds__(256) void clip_power_kernel(const float* __r
     const long long stride = (long long)gridDim.x * blockDim.x;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_pairs; i += stride) {
         const float2 v = *reinterpret_cast<const float2*>(x + 2 * i);
-        const float l2 = sqrtf(v.x * v.x + v.y * v.y);
-        const float sc = peak / fmaxf(l2, peak);
-        const float ci = v.x * sc, cq = v.y * sc;
-        if (y != nullptr) *reinterpret_cast<float2*>(y + 2 * i) = make_float2(ci, cq);
-        pw += (double)(ci * ci + cq * cq);
+        const float2 c = clip_pair(v.x, v.y, peak);
+        if (y != nullptr) *reinterpret_cast<float2*>(y + 2 * i) = c;
+        pw += (double)pair_power(c);
     }
     pw = wave_sum(pw);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = pw;
@@ -488,31 +509,20 @@ static __global__ __launch_bounds__(256) void clip_power_kernel(const float* __r
 }
 
 // ---- R7: TF Adam -----------------------------------------------------------------------
-// prep: alpha = lr*sqrt(1-b2p)/(1-b1p) with lr = lr0*rate^floor(step/decay_steps); then the
-// state advances (beta powers *= beta, global_step += 1) -- exactly one thread.
+// prep: adam_advance as a launch of its own
 static __global__ void adam_prep_kernel(dccn_adam_state* __restrict__ st, dccn_adam_hparams hp) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        const float step = st->global_step;
-        const float lr = hp.lr0 * powf(hp.decay_rate, floorf(step / hp.decay_steps));
-        const float b1p = st->beta1_power, b2p = st->beta2_power;
-        st->alpha = lr * sqrtf(1.0f - b2p) / (1.0f - b1p);
-        st->beta1_power = b1p * hp.beta1;
-        st->beta2_power = b2p * hp.beta2;
-        st->global_step = step + 1.0f;
-    }
+    if (threadIdx.x == 0 && blockIdx.x == 0) adam_advance(st, hp);
 }
 
-// m += (g-m)*(1-b1); v += (g*g-v)*(1-b2); p -= m*alpha/(sqrt(v)+eps)   (TF ApplyAdam form)
-// g = grad + gate*reg_coef*param
+// adam_update over a flat arena
 static __global__ __launch_bounds__(256) void adam_apply_kernel(float* __restrict__ param, const float* __restrict__ grad,
                                                          float* __restrict__ m, float* __restrict__ v,
                                                          const float* __restrict__ reg_coef,
                                                          const float* __restrict__ reg_gate,
                                                          const dccn_adam_state* __restrict__ st,
                                                          dccn_adam_hparams hp, long long n) {
-    const float alpha = st->alpha;
+    const AdamCoef k = adam_coef(st, hp);
     const float gate = reg_gate ? reg_gate[0] : 1.0f;
-    const float omb1 = 1.0f - hp.beta1, omb2 = 1.0f - hp.beta2;
     const long long stride = (long long)gridDim.x * blockDim.x * 4;
     for (long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
         if (i + 3 < n) {
@@ -528,23 +538,16 @@ static __global__ __launch_bounds__(256) void adam_apply_kernel(float* __restric
             float* vv = reinterpret_cast<float*>(&v4);
             const float* cc = reinterpret_cast<const float*>(&c4);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float g = gg[e] + (gate * cc[e]) * pp[e];
-                mm[e] += (g - mm[e]) * omb1;
-                vv[e] += (g * g - vv[e]) * omb2;
-                pp[e] -= (mm[e] * alpha) / (sqrtf(vv[e]) + hp.eps);
-            }
+            for (int e = 0; e < 4; ++e) adam_update(pp[e], mm[e], vv[e], gg[e], cc[e], gate, k);
             *reinterpret_cast<float4*>(param + i) = p4;
             *reinterpret_cast<float4*>(m + i) = m4;
             *reinterpret_cast<float4*>(v + i) = v4;
         } else {
             for (long long j = i; j < n; ++j) {
-                const float c = reg_coef ? reg_coef[j] : 0.f;
-                const float g = grad[j] + (gate * c) * param[j];
-                float mj = m[j], vj = v[j];
-                mj += (g - mj) * omb1;
-                vj += (g * g - vj) * omb2;
-                param[j] -= (mj * alpha) / (sqrtf(vj) + hp.eps);
+                const float c = reg_coef ? reg_coef[j] : 0.f, g = grad[j];
+                float pj = param[j], mj = m[j], vj = v[j];
+                adam_update(pj, mj, vj, g, c, gate, k);
+                param[j] = pj;
                 m[j] = mj;
                 v[j] = vj;
             }
@@ -590,9 +593,8 @@ struct AdamRxArgs {
 
 // C-Conv parameters: fold the dWeff slabs (Appendix A.2) and apply the update right here.
 __device__ __forceinline__ void adam_fold_role(const AdamRxArgs& a, const dccn_adam_hparams& hp, const int bx) {
-    const float alpha = a.state->alpha;
+    const AdamCoef k = adam_coef(a.state, hp);
     const float gate = a.reg_gate ? a.reg_gate[0] : 1.0f;
-    const float omb1 = 1.0f - hp.beta1, omb2 = 1.0f - hp.beta2;
     long long idx[2];
     float gv[2];
     // the two parameters this thread will update (group 0 of the fold: the same (n, f) / bias mapping as cconv_fold_body) are
@@ -623,10 +625,7 @@ __device__ __forceinline__ void adam_fold_role(const AdamRxArgs& a, const dccn_a
         if (idx[e] < 0) continue;
         const long long j = a.o_cw + idx[e];
         float p = pre_p[e], mm = pre_m[e], vv = pre_v[e];
-        const float ge = gv[e] + (gate * pre_c[e]) * p;
-        mm += (ge - mm) * omb1;
-        vv += (ge * ge - vv) * omb2;
-        p -= (mm * alpha) / (sqrtf(vv) + hp.eps);
+        adam_update(p, mm, vv, gv[e], pre_c[e], gate, k);
         a.param[j] = p;
         a.m[j] = mm; a.v[j] = vv;
     }
@@ -635,9 +634,8 @@ __device__ __forceinline__ void adam_fold_role(const AdamRxArgs& a, const dccn_a
 // the rest of the arena (dense kernel / bias with their split-K slabs, tail weights): block bx of nbx streams it
 template <int SPLITS>     // 0: runtime count
 __device__ __forceinline__ void adam_stream_role(const AdamRxArgs& a, const dccn_adam_hparams& hp, const int bx, const int nbx) {
-    const float alpha = a.state->alpha;
+    const AdamCoef k = adam_coef(a.state, hp);
     const float gate = a.reg_gate ? a.reg_gate[0] : 1.0f;
-    const float omb1 = 1.0f - hp.beta1, omb2 = 1.0f - hp.beta2;
     const bool seg4 = ((a.o_dw | a.n_dw | a.o_db | a.n_db) & 3) == 0;
     const bool uni = a.reg_uniform_dw != 0 && a.reg_coef != nullptr && seg4;
     const float cdw = uni ? a.reg_coef[a.o_dw] : 0.f;          // (uniform address: one scalar load)
@@ -729,12 +727,7 @@ __device__ __forceinline__ void adam_stream_role(const AdamRxArgs& a, const dccn
             }
         }
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float ge = g[e] + (gate * cc[e]) * p[e];
-            mm[e] += (ge - mm[e]) * omb1;
-            vv[e] += (ge * ge - vv[e]) * omb2;
-            p[e] -= (mm[e] * alpha) / (sqrtf(vv[e]) + hp.eps);
-        }
+        for (int e = 0; e < 4; ++e) adam_update(p[e], mm[e], vv[e], g[e], cc[e], gate, k);
         if (full && a.nt >= 2) {
             nt_f32x4 sp = {p[0], p[1], p[2], p[3]}, sm = {mm[0], mm[1], mm[2], mm[3]}, sv = {vv[0], vv[1], vv[2], vv[3]};
             __builtin_nontemporal_store(sp, reinterpret_cast<nt_f32x4*>(a.param + i));

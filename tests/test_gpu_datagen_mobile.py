@@ -36,13 +36,14 @@ def doppler_frames(gen, n):
     return [bool(gen.doppler)] * n
 
 
-@pytest.mark.parametrize("chan,mix,nbits,n", [("mixRayleigh", True, 2, 1), ("mixRayleigh", True, 2, 7), ("mixRayleigh", True, 4, 27),
-                                              ("mixRayleigh", True, 2, 73), ("mixAll", True, 1, 10), ("EPA", False, 2, 9),
-                                              ("ETU", False, 3, 2), ("Flat", False, 1, 3)])
+@pytest.mark.parametrize("chan,mix,nbits,n", [("mixRayleigh", True, 2, 1), ("mixRayleigh", True, 2, 3), ("mixRayleigh", True, 2, 7),
+                                              ("mixRayleigh", True, 4, 27), ("mixRayleigh", True, 2, 73), ("mixAll", True, 1, 10),
+                                              ("EPA", False, 2, 9), ("ETU", False, 3, 2), ("Flat", False, 1, 3)])
 def test_fused_generator_with_doppler_frames_matches_the_launch_per_stage_chain(chan, mix, nbits, n):
     """dccn_gen_static_frames + dccn_gen_static_apply on a plan with Doppler frames against dccn_ofdm_tx_frames +
     dccn_channel_groups_awgn / dccn_channel_doppler_awgn: per-frame SNRs from a caller's tensor, a nonzero batch offset, the
-    noise-power monitor.  mixRayleigh n = 1: a flat Doppler frame (L = 1) alone in its block; n = 7: the last block holds a
+    noise-power monitor.  mixRayleigh n = 1: a flat Doppler frame (L = 1) alone in its block; n = 3: a full block (Doppler + static)
+    followed by a one-frame block, whose second profile repeats the first; n = 7: the last block holds a
     Doppler EVA frame alone, blocks (0, 1) and (2, 3) hold Doppler and static frames in both orders; n = 27: every profile
     appears as a Doppler frame; n = 73: the reference's batch; mixAll: the identity profile is never a Doppler frame; EPA / ETU /
     Flat: every frame a Doppler frame, both frames of a block.  Bounds: those tests/test_gpu_datagen.py holds the static launch

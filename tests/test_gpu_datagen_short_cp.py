@@ -127,11 +127,13 @@ def test_fused_static_generator_matches_the_launch_per_stage_chain_at_the_short_
 
 # ---- 3. Doppler frames ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("chan,mix,nbits,n", [("mixRayleigh", True, 2, 7), ("mixRayleigh", True, 4, 27), ("ETU", False, 3, 2),
-                                              ("Flat", False, 1, 1)])
+                                              ("Flat", False, 1, 1), ("ETU", False, 3, 1), ("ETU", False, 3, 3),
+                                              ("mixRayleigh", True, 2, 3)])
 def test_fused_generator_with_doppler_frames_matches_the_launch_per_stage_chain_at_the_short_prefix(chan, mix, nbits, n):
     """tests/test_gpu_datagen_mobile.py test_fused_generator_with_doppler_frames_matches_the_launch_per_stage_chain at CP = 4,
     its assertions and bounds (H <= 5e-5).  ETU: 9 taps of history against a 4-sample prefix -- the per-symbol FIR window reaches
-    into the previous symbol's body; n = 27: every mixRayleigh profile appears as a Doppler frame."""
+    into the previous symbol's body; n = 27: every mixRayleigh profile appears as a Doppler frame; n = 1: a one-frame block (the
+    second profile repeats the first); n = 3: a full block followed by a one-frame last block."""
     from dl_ofdm_amd.datagen import FusedStaticGen
     ga, gb = gens(chan, nbits, 21, mobile=True, mix=mix)
     assert gb.CP == 4

@@ -35,3 +35,29 @@ for chan, nbits, n, longcp, mobile in (("EPA", 2, 1170, True, False), ("ETU", 4,
     _, _, npow = fg.make_batch(x, bits, slot=0, tx_out=tx)
     torch.cuda.synchronize()
     print(chan, nbits, n, *(() if longcp else ("CP", gen.CP, "mobile", int(mobile))), "x", h(x), "bits", h(bits), "tx", h(tx), "y", h(fg.y), "noise", h(fg.noise), "npow", h(npow))
+
+# the launch-per-stage chain (tx grid, IDFT GEMM, taps, FIR, AWGN kernels): a static, a Doppler and a frame-interleaved descriptor
+for chan, nbits, mobile, mix in (("EPA", 2, False, False), ("ETU", 3, True, False), ("mixRayleigh", 2, True, True)):
+    F = R.Flags(nbits=nbits, nfilter=64, channel=chan, SNR=10.0)
+    gen = DeviceDataGen(F, ofdm.ofdm_tx(F), seed=5, mobile=mobile, mix=mix)
+    gen.offset = 9
+    tx, bits = gen.transmit(9)
+    x, npow, H = gen.channel(tx, torch.linspace(0, 25, 9, device="cuda"), want_H=True)
+    torch.cuda.synchronize()
+    print("per-stage", chan, nbits, 9, "mobile", int(mobile), "mix", int(mix), "x", h(x), "H", h(torch.view_as_real(H)), "npow", h(npow))
+
+# the optimizer side: three generated pipelined steps at 73 frames, cp=True and cp=False (the windowed optimizer launch)
+from dl_ofdm_amd.engine import RxEngine      # noqa: E402
+for cp in (True, False):
+    F = R.Flags(nbits=2, nfilter=64, channel="EPA", SNR=10.0, cp=cp)
+    o = ofdm.ofdm_tx(F)
+    gen = DeviceDataGen(F, o, seed=5)
+    eng = RxEngine(R.rx_dims(F, o), 73, train=True, seed=5, want_prob=False, want_z=False)
+    if not FusedStaticGen.supported(gen, eng):
+        print("steps cp", int(cp), "not taken by this library's generated loop")
+        continue
+    fg = FusedStaticGen(gen, 73, 7.0, want_noise_power=True)
+    for i in range(3):
+        eng.train_step_generated(fg, slot=i & 1, last=(i == 2))
+    torch.cuda.synchronize()
+    print("steps cp", int(cp), "kin", eng.shape.kin, "params", h(eng.params), "adam_m", h(eng.adam_m), "adam_v", h(eng.adam_v))
