@@ -187,6 +187,7 @@ SIGNATURES = {
     "dccn_set_tuning": (_i, [_i, _i]),
     "dccn_get_tuning": (_i, [_i]),
     "dccn_dense_tail_supported": (_i, [_i, _i, _i, _i]),
+    "dccn_dense_tail_grid": (_i, [_i, _i, _i, _i] + [POINTER(c_int)] * 4),
     "dccn_rx_bwd_fused_supported": (_i, [POINTER(RxShape)]),
     "dccn_rx_dense_tail_fused": (_i, [POINTER(RxShape), _i]),
     "dccn_rx_norm_rides_backward": (_i, [POINTER(RxShape)]),

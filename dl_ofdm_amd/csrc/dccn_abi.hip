@@ -1912,6 +1912,17 @@ int dccn_debug_set_trace(unsigned long long* buf) {
 #endif
 
 int dccn_dense_tail_supported(int M, int K, int N, int nbits) { return dense_tail_shape_ok(M, K, N, nbits) ? 1 : 0; }
+// (the description dense_tail_impl / dense_decide_impl build, on null -- 16-byte aligned -- operands: nothing is read)
+int dccn_dense_tail_grid(int M, int K, int N, int nbits, int* grid, int* tile_rows, int* ragged_rows, int* blocks) {
+    const TuneScope tune;
+    if (!dense_tail_ok(nullptr, nullptr, M, K, N, nbits)) return DCCN_ERR_INVALID_ARG;
+    const DenseRoute r = dense_tail_route(dense_fwd_params(nullptr, nullptr, nullptr, nullptr, M, K, N), nbits);
+    if (grid) *grid = r.grid;
+    if (tile_rows) *tile_rows = r.grid == DG_FEWROW ? 16 : (r.grid == DG_RAGGED || r.large) ? kDense80.rows() : kDense48.rows();
+    if (ragged_rows) *ragged_rows = r.grid == DG_RAGGED ? r.rag : 0;
+    if (blocks) *blocks = r.blocks;
+    return DCCN_OK;
+}
 int dccn_rx_dense_tail_fused(const dccn_rx_shape* sh, int train) {
     return shape_ok(sh) && rx_dense_tail_fused_ok(sh, train != 0, nullptr, nullptr) ? 1 : 0;
 }

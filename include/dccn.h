@@ -311,8 +311,15 @@ int dccn_tuning_snapshot(int* table, int n);
  *   dccn_dense_tail_supported   1: dccn_dense_tail_fwd[_bwd] accepts (M, K, N, nbits) with 16-byte aligned operands
  *                               (the fused receiver step then runs R2..R6 as one launch and `z` may be NULL);
  *   dccn_rx_bwd_fused_supported 1: the training step runs its backward half as one launch (dense dX tiles with the
- *                               C-Conv weight gradient in their epilogue + dense dW items): `dfft` may be NULL. */
+ *                               C-Conv weight gradient in their epilogue + dense dW items): `dfft` may be NULL.
+ *   dccn_dense_tail_grid        which grid dccn_dense_tail_fwd[_bwd] (and, for nbits <= 2, dccn_dense_decide_fwd) launches for
+ *                               (M, K, N, nbits) with 16-byte aligned operands: *grid = 0 uniform tiles, 1 few-row 16x16 tiles,
+ *                               2 ragged (80x64 tiles + one row of 32x64 blocks); *tile_rows = 48 or 80 (16 for the few-row
+ *                               tiles); *ragged_rows = rows of the short last tile row of the ragged grid, else 0; *blocks =
+ *                               blocks of the launch.  Outputs are nullable.  Host-only, launches nothing.  Returns
+ *                               DCCN_ERR_INVALID_ARG, outputs untouched, exactly where dccn_dense_tail_supported answers 0. */
 int dccn_dense_tail_supported(int M, int K, int N, int nbits);
+int dccn_dense_tail_grid(int M, int K, int N, int nbits, int* grid, int* tile_rows, int* ragged_rows, int* blocks);
 
 /* ---- R7: optimizer -----------------------------------------------------------------
  * dev/py/ofdmreceiver_np.py:185-189  exponential_decay(1e-3, step, 500, 0.98, staircase)

@@ -195,6 +195,79 @@ def test_dense_decide_equals_dense_then_decide(M, K, N, nbits):
                   + b.cpu().numpy().astype(np.float64)) <= RTOL
 
 
+@pytest.fixture(scope="module")
+def large_cases():
+    """The cached operands and float64 references of tests/test_gpu_dense_tail_large.py (built here when that module did not
+    run first; released when this module is done)."""
+    import test_gpu_dense_tail_large as T
+    yield T
+    T._cases.clear()
+
+
+@pytest.mark.parametrize("M,K,N,nbits,route", [(4960, 192, 640, 1, (0, 80, 0, 620)),      # uniform 80x64 tiles
+                                               (4960, 192, 640, 2, (0, 80, 0, 620)),
+                                               (4961, 192, 640, 2, (2, 80, 1, 630)),      # ragged grid, one row
+                                               (4992, 192, 640, 1, (2, 80, 32, 630)),     # ragged grid, a full 32-row block
+                                               (4960, 192, 640, 4, (0, 80, 0, 620))])     # two launches
+def test_dense_decide_on_the_grids_of_large_layers(large_cases, M, K, N, nbits, route):
+    """dccn_dense_decide_fwd where dense_tail_route leaves the 48x64 tiles (dccn_dense_tail_grid proves it).  There
+    dccn_dense_fwd may run another tile family, so z is held to what the header promises instead: the bits of
+    dccn_dense_tail_fwd's z.  prob likewise; packed is numpy.packbits of that prob's decisions and -- the tail-side test
+    holds that prob to the oracle, and no cell of these inputs is near a tie -- of the oracle's; llr, prob and packed are those
+    of the stand-alone decision kernel on that z; all-NULL optional outputs (nbits <= 2) give the same packed; 64 guard
+    bytes behind packed stay untouched."""
+    from dl_ofdm_amd import _lib
+    from dl_ofdm_amd.receive import row_bytes
+    T = large_cases
+    lib = _lib.load()
+    assert T.grid_of(lib, M, K, N, nbits) == route
+    assert lib.dccn_dense_decide_supported(M, K, N, nbits) == 1
+    c = T.large_case(M, K, N, nbits)
+    tail = T.run_tail(lib, c, bwd=False)
+    D, RB, GB = N // 2, row_bytes(N // 2, nbits), 64
+    dev = "cuda"
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    x, w, b, tp = (c[k].data_ptr() for k in ("d_x", "d_w", "d_b", "d_flat"))
+
+    def outputs(fill):
+        return (torch.full((M * RB + GB,), fill, dtype=torch.uint8, device=dev), T.Guarded(M * D * nbits),
+                T.Guarded(M * D * nbits * 2))
+
+    def packed_rows(pk, fill, what):
+        h = pk.cpu().numpy()
+        assert (h[M * RB:] == fill).all(), "%s: bytes behind packed written" % what
+        return h[:M * RB].reshape(M, RB)
+
+    z1 = T.Guarded(M * N)
+    pk1, l1, q1 = outputs(0x55)
+    _lib.check(lib.dccn_dense_decide_fwd(x, w, b, z1.ptr, tp, pk1.data_ptr(), l1.ptr, q1.ptr, M, K, N, nbits, st),
+               "dccn_dense_decide_fwd")
+    torch.cuda.synchronize()
+    zh = z1.get("z")
+    T.assert_same_bits(zh.reshape(M, N), tail["z"], "z against dccn_dense_tail_fwd")
+    qh = q1.get("prob").reshape(M, D, nbits, 2)
+    T.assert_same_bits(qh, tail["prob"], "prob against dccn_dense_tail_fwd")
+    ph = packed_rows(pk1, 0x55, "decide")
+    hard = tail["prob"][..., 1] > tail["prob"][..., 0]
+    # (numpy.packbits pads a row's last byte with zero bits)
+    assert np.array_equal(ph, np.packbits(hard.reshape(M, D * nbits), axis=1))
+    assert np.array_equal(ph, np.packbits(c["hard"].reshape(M, D * nbits), axis=1))
+    # the stand-alone decision kernel on the same z
+    z2 = torch.as_tensor(zh, device=dev)
+    pk2, l2, q2 = outputs(0xAA)
+    _lib.check(lib.dccn_demod_decide(z2.data_ptr(), tp, pk2.data_ptr(), l2.ptr, q2.ptr, M, D, nbits, st), "dccn_demod_decide")
+    torch.cuda.synchronize()
+    assert np.array_equal(packed_rows(pk2, 0xAA, "stand-alone"), ph)
+    T.assert_same_bits(l2.get("llr"), l1.get("llr"), "llr against dccn_demod_decide")
+    T.assert_same_bits(q2.get("prob").reshape(qh.shape), qh, "prob against dccn_demod_decide")
+    if nbits <= 2:
+        pk3 = torch.full((M * RB + GB,), 0x33, dtype=torch.uint8, device=dev)
+        _lib.check(lib.dccn_dense_decide_fwd(x, w, b, None, tp, pk3.data_ptr(), None, None, M, K, N, nbits, st),
+                   "dccn_dense_decide_fwd")
+        torch.cuda.synchronize()
+        assert np.array_equal(packed_rows(pk3, 0x33, "packed only"), ph)
+
+
 @pytest.mark.parametrize("name,batch,nbits,kin,F,D", CASES)
 def test_sign_coherence_and_nullable_outputs(name, batch, nbits, kin, F, D):
     from dl_ofdm_amd import _lib

@@ -65,6 +65,45 @@ def test_host_side_queries(lib):
     assert lib.dccn_cconv_gemm_fwd(None, None, None, None, 0, 80, 64, None) == -1
 
 
+def test_dense_tail_grid_query(lib):
+    """dccn_dense_tail_grid against the route worked out by hand from the comments on dense_tail_route (256 CUs): 80x64 tiles
+    from ceil(M / 48) * ceil(N / 64) >= 1024 tiles on; there, BPSK / QPSK with 1 <= M % 80 <= 32 rows left over run those
+    rows as one row of 32x64 blocks (knob 27); M <= 96 on BPSK / QPSK runs the few-row 16x16 tiles."""
+    TILES, FEWROW, RAGGED = 0, 1, 2
+
+    def q(M, K, N, nbits):
+        g = [C.c_int(-7) for _ in range(4)]
+        st = lib.dccn_dense_tail_grid(M, K, N, nbits, *[C.byref(v) for v in g])
+        assert (st == 0) == (lib.dccn_dense_tail_supported(M, K, N, nbits) == 1)
+        return st, tuple(v.value for v in g)
+
+    assert q(1170, 896, 640, 2) == (0, (TILES, 48, 0, 250))             # 25 x 10 tiles of 48x64
+    # 13 x 125 = 1625 >= 1024; 585 = 7 x 80 + 25: 7 x 125 blocks of 80x64 + 125 of 32x64
+    assert q(585, 14336, 8000, 2) == (0, (RAGGED, 80, 25, 1000))
+    assert q(585, 14336, 8000, 4) == (0, (TILES, 80, 0, 1000))          # the ragged grid is BPSK / QPSK only: 8 x 125
+    default = lib.dccn_get_tuning(27)
+    try:
+        assert lib.dccn_set_tuning(27, 0) == 0
+        assert q(585, 14336, 8000, 2) == (0, (TILES, 80, 0, 1000))
+    finally:
+        lib.dccn_set_tuning(27, default)
+    assert lib.dccn_get_tuning(27) == default == 1
+    assert q(4960, 192, 640, 2) == (0, (TILES, 80, 0, 620))             # 104 x 10 = 1040 >= 1024; 62 x 10 blocks
+    assert q(4880, 192, 640, 2) == (0, (TILES, 48, 0, 1020))            # 102 x 10 = 1020 < 1024: just below the threshold
+    assert q(4961, 192, 640, 2) == (0, (RAGGED, 80, 1, 630))            # 62 x 10 + 10
+    assert q(4992, 192, 640, 1) == (0, (RAGGED, 80, 32, 630))
+    assert q(4993, 192, 640, 2) == (0, (TILES, 80, 0, 630))             # 33 rows left: 63 x 10 uniform tiles
+    assert q(4976, 896, 580, 2) == (0, (RAGGED, 80, 16, 630))           # 10 column tiles, the last of 4 columns
+    assert q(4976, 192, 640, 4) == (0, (TILES, 80, 0, 630))
+    assert q(36, 896, 640, 2) == (0, (FEWROW, 16, 0, 3 * 40))           # 3 x 40 tiles of 16x16
+    assert q(36, 896, 640, 4)[1][:3] == (TILES, 48, 0)                  # few-row tiles carry the tail at BPSK / QPSK only
+    # refused exactly where dccn_dense_tail_supported answers 0; the outputs stay as they were
+    for bad in ((1170, 898, 640, 2), (1170, 896, 642, 2), (1170, 896, 640, 5), (0, 896, 640, 2)):
+        assert q(*bad) == (-1, (-7, -7, -7, -7)), bad
+    # the outputs are nullable
+    assert lib.dccn_dense_tail_grid(1170, 896, 640, 2, None, None, None, None) == 0
+
+
 def test_eq_workspace_tensor_lookup(lib):
     """dccn_eq_workspace_tensor: a host-side query (no device work): named intermediates of the fused equaliser step lie
     inside the sized workspace on 256-byte boundaries; unknown names and training-only tensors of an evaluation workspace
