@@ -163,6 +163,8 @@ SIGNATURES = {
     "dccn_chain_group_max": (_i, []),
     "dccn_eq_group_supported": (_i, [POINTER(EqShape)]),
     "dccn_eq_train_step_grouped": (_i, [_i, _vp, _vp, AdamHParams, _vp]),
+    "dccn_eq_receive_group_supported": (_i, [POINTER(EqShape)]),
+    "dccn_eq_receive_step_grouped": (_i, [_i, _vp, _vp, _vp, _vp]),
     "dccn_gen_static_frames_grouped": (_i, [_i, _vp, _vp]),
     "dccn_gen_static_apply_grouped": (_i, [_i, _vp, _vp, _vp, _vp]),
     "dccn_eq_monitor_accumulate_grouped": (_i, [_i, _vp, _vp]),

@@ -1020,13 +1020,12 @@ int decide_impl(const float* z, const float* tailp, unsigned char* packed, float
     const int gpr = ceil_div(D, 8), RB = decide_row_bytes(D, nbits);
     const long long blocks = ceil_div_ll((long long)frames * gpr * 8, kDecideThreads);
     if (blocks > 0x7fffffffLL) return DCCN_ERR_INVALID_ARG;
-    DCCN_NO_CHAINS();
     const dim3 grid((unsigned)blocks), blk(kDecideThreads);
     switch (nbits) {
-        case 1: hipLaunchKernelGGL(demod_decide_kernel<1>, grid, blk, 0, s, z, tailp, packed, llr, prob, frames, D, gpr, RB); break;
-        case 2: hipLaunchKernelGGL(demod_decide_kernel<2>, grid, blk, 0, s, z, tailp, packed, llr, prob, frames, D, gpr, RB); break;
-        case 3: hipLaunchKernelGGL(demod_decide_kernel<3>, grid, blk, 0, s, z, tailp, packed, llr, prob, frames, D, gpr, RB); break;
-        default: hipLaunchKernelGGL(demod_decide_kernel<4>, grid, blk, 0, s, z, tailp, packed, llr, prob, frames, D, gpr, RB); break;
+        case 1: DCCN_LAUNCH_CHAINS_Z(demod_decide_kernel<1>, grid, blk, 0, s, z, tailp, packed, llr, prob, frames, D, gpr, RB); break;
+        case 2: DCCN_LAUNCH_CHAINS_Z(demod_decide_kernel<2>, grid, blk, 0, s, z, tailp, packed, llr, prob, frames, D, gpr, RB); break;
+        case 3: DCCN_LAUNCH_CHAINS_Z(demod_decide_kernel<3>, grid, blk, 0, s, z, tailp, packed, llr, prob, frames, D, gpr, RB); break;
+        default: DCCN_LAUNCH_CHAINS_Z(demod_decide_kernel<4>, grid, blk, 0, s, z, tailp, packed, llr, prob, frames, D, gpr, RB); break;
     }
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;

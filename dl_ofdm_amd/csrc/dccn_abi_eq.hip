@@ -260,6 +260,46 @@ int dccn_eq_train_step_grouped(int n_chains, const dccn_eq_shape* const* shapes,
     return eq_step_impl(shapes[0], bufs[0], true, hp, (hipStream_t)stream);
 }
 
+int dccn_eq_receive_group_supported(const dccn_eq_shape* shape) {
+    if (!eq_shape_ok(shape)) return 0;
+    const EqDims d = eq_dims(shape);
+    const dccn_rx_shape rsh = eq_rx_shape(d, shape->nbits);
+    const RxLayout L = rx_layout(&rsh);
+    // the step's own predicates, given 16-byte aligned buffers (and rx_folded): 1 exactly where a grouped receive step is accepted
+    const bool few_rx = eq_few_rx_ok(d, L, nullptr, nullptr, nullptr);
+    return eq_receive_group_ok(eq_norm_single_ok(d, nullptr, nullptr), eq_bn_ok(d, nullptr, nullptr, nullptr, nullptr),
+                               eq_rx_folded_ok(d, few_rx, nullptr, nullptr)) ? 1 : 0;
+}
+
+int dccn_eq_receive_step_grouped(int n_chains, const dccn_eq_shape* const* shapes, const dccn_eq_buffers* const* bufs,
+                                 const dccn_receive_out* const* outs, dccn_stream_t stream) {
+    if (n_chains < 1 || n_chains > kMaxChains || !shapes || !bufs || !outs) return DCCN_ERR_INVALID_ARG;
+    for (int i = 0; i < n_chains; ++i) {
+        if (!shapes[i] || !bufs[i] || !outs[i] || !outs[i]->packed || !eq_shape_ok(shapes[i])) return DCCN_ERR_INVALID_ARG;
+        const dccn_eq_shape *a = shapes[0], *c = shapes[i];
+        // one launch plan: everything but the modulation agrees
+        if (a->batch != c->batch || a->S != c->S || a->K != c->K || a->CP != c->CP || a->cp != c->cp || a->F != c->F || a->D != c->D ||
+            a->pilot_size != c->pilot_size || a->P != c->P)
+            return DCCN_ERR_INVALID_ARG;
+        const dccn_eq_buffers *p = bufs[0], *q = bufs[i];
+        if (p->workspace_bytes != q->workspace_bytes || p->norm_slot != q->norm_slot || q->x_prenormalised != 0)
+            return DCCN_ERR_INVALID_ARG;
+    }
+    if (n_chains == 1) return dccn_eq_receive_step(shapes[0], bufs[0], outs[0], stream);
+    if (!dccn_eq_receive_group_supported(shapes[0])) return DCCN_ERR_UNSUPPORTED;
+    // what the forward-only step reads or writes (labels, metrics, gradients and optimizer state are not touched)
+    ChainOffsetCheck chk(n_chains);
+    CHAIN_FIELD(chk, bufs, n_chains, x); CHAIN_FIELD(chk, bufs, n_chains, eq_params); CHAIN_FIELD(chk, bufs, n_chains, rx_params);
+    CHAIN_FIELD(chk, bufs, n_chains, rx_folded); CHAIN_FIELD(chk, bufs, n_chains, out_eq); CHAIN_FIELD(chk, bufs, n_chains, chest);
+    CHAIN_FIELD(chk, bufs, n_chains, snr_db); CHAIN_FIELD(chk, bufs, n_chains, pilot_carriers); CHAIN_FIELD(chk, bufs, n_chains, workspace);
+    CHAIN_FIELD(chk, outs, n_chains, packed); CHAIN_FIELD(chk, outs, n_chains, llr); CHAIN_FIELD(chk, outs, n_chains, prob);
+    ChainCtx ctx;
+    if (!chk.finish(&ctx) || bufs[0]->rx_folded == nullptr) return DCCN_ERR_INVALID_ARG;
+    for (int i = 0; i < n_chains; ++i) ctx.nbits[i] = shapes[i]->nbits;
+    ChainScope scope(ctx);
+    return eq_step_impl(shapes[0], bufs[0], false, dccn_adam_hparams(), (hipStream_t)stream, outs[0]);
+}
+
 int dccn_eq_monitor_accumulate_grouped(int n_chains, const dccn_eq_monitor* const* m, dccn_stream_t stream) {
     if (n_chains < 1 || n_chains > kMaxChains || !m) return DCCN_ERR_INVALID_ARG;
     for (int i = 0; i < n_chains; ++i) {
@@ -388,8 +428,8 @@ int dccn_equalize_bwd(const float* y, const float* h, const float* d_eq, const f
 int dccn_pilot_snr(const float* eq, const int* carriers, float* snr_db, int frames, int S, int K, int P,
                    dccn_stream_t stream) {
     if (!eq || !carriers || !snr_db || frames <= 0 || S <= 0 || K <= 0 || P <= 0) return DCCN_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(pilot_snr_kernel, dim3(frames), dim3(64), 0, (hipStream_t)stream, (const float2*)eq, carriers,
-                       snr_db, S, K, P);
+    DCCN_LAUNCH_CHAINS_Z(pilot_snr_kernel, dim3(frames), dim3(64), 0, (hipStream_t)stream, (const float2*)eq, carriers,
+                         snr_db, S, K, P);
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
 }

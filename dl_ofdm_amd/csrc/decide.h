@@ -23,6 +23,11 @@ struct DecideEpiParams {
     float* llr;                     // [M, N/2, NB], nullable
     float* prob;                    // [M, N/2, NB, 2], nullable
     int RB;                         // bytes per row = ceil(N/2 * NB / 8)
+    __device__ __forceinline__ DecideEpiParams at_chain(const long long off) const {   // chain groups (common.h)
+        DecideEpiParams q = *this;
+        q.tailp = chain_at(tailp, off); q.packed = chain_at(packed, off); q.llr = chain_at(llr, off); q.prob = chain_at(prob, off);
+        return q;
+    }
 };
 
 // OR over the 16 lanes of a DPP row / over each group of 8 lanes; the result is in every lane of the row / group
@@ -123,10 +128,18 @@ constexpr int kDecideThreads = 256;
 // Stand-alone decision kernel: z [frames, D, 2] + tail weights -> packed / llr / prob.  A lane per cell; lanes 8g .. 8g+7 own
 // the eight cells 8 grp .. 8 grp + 7 of one frame (a frame has gpr = ceil(D / 8) such groups; cells past D are masked), i.e.
 // NB whole bytes of that frame's row, whatever D and NB are: no byte is shared between groups, rows need no alignment.
+// (chain groups, common.h: blockIdx.z = chain, every pointer moves by that chain's arena offset; frames, D, RB and NB are the
+// launch's -- a group runs this kernel once per modulation, on the chains of that modulation)
 template <int NB>
 __global__ __launch_bounds__(kDecideThreads) void demod_decide_kernel(
-    const float* __restrict__ z, const float* __restrict__ tailp, unsigned char* __restrict__ packed, float* __restrict__ llr,
-    float* __restrict__ prob, const int frames, const int D, const int gpr, const int RB) {
+    const float* __restrict__ z0, const float* __restrict__ tailp0, unsigned char* __restrict__ packed0, float* __restrict__ llr0,
+    float* __restrict__ prob0, const int frames, const int D, const int gpr, const int RB, const ChainOffs co) {
+    const long long coff = co.off[blockIdx.z];
+    const float* __restrict__ z = chain_at(z0, coff);
+    const float* __restrict__ tailp = chain_at(tailp0, coff);
+    unsigned char* __restrict__ packed = chain_at(packed0, coff);
+    float* __restrict__ llr = chain_at(llr0, coff);
+    float* __restrict__ prob = chain_at(prob0, coff);
     constexpr int P = tail_param_count(NB);
     // nbits >= 3: 90 / 200 weights do not fit the SGPR file: staged in LDS, re-read as broadcast loads (as tail.h does)
     constexpr bool LDSW = NB >= 3;

@@ -176,9 +176,13 @@ static void eq_opt_dense(EqOptBuilder& ob, const EqDims& d, int i, const Deferre
 static dccn_rx_shape eq_rx_shape(const EqDims& d, int nbits) {
     return dccn_rx_shape{d.B, d.S, d.cp ? d.nsc : d.K, d.F, d.D, nbits};
 }
-// `input:0` by the single-pass kernel: the optimizer launch of a training step can then run it for the NEXT batch
+// `input:0` by the single-pass kernel (one launch, and one that carries a chain index) ...
+static bool eq_norm_single_ok(const EqDims& d, const float* x, const float* x_norm) {
+    return g_tune[TUNE_EQ_REPLAN] != 0 && kNormFusedCG == 2 && norm_fused_ok(x, x_norm, d.B, d.S * 2 * d.nsc);
+}
+// ... the optimizer launch of a training step can then run it for the NEXT batch
 static bool eq_norm_rides_ok(const EqDims& d, bool train, const float* x, const float* x_norm) {
-    return g_tune[TUNE_EQ_REPLAN] != 0 && train && kNormFusedCG == 2 && norm_fused_ok(x, x_norm, d.B, d.S * 2 * d.nsc);
+    return train && eq_norm_single_ok(d, x, x_norm);
 }
 // both layers of the pilot bottleneck in one launch per direction (eq_bottleneck.h); W1 / W2: the dense_1 / dense_2 kernels
 static bool eq_bn_ok(const EqDims& d, const float* y, const float* W1, const float* W2, const float* d1) {
@@ -200,6 +204,9 @@ static bool eq_rx_folded_ok(const EqDims& d, bool few_rx, const float* Mf, const
 // a chain group (common.h ChainCtx) runs on the launches that carry a chain index: the single-pass normalisation, the
 // bottleneck as one launch per direction, the few-row plan with the receiver folded into one matrix
 static bool eq_group_ok(bool rides, bool bn, bool folded) { return rides && bn && folded; }
+// ... and a forward-only group (dccn_eq_receive_step_grouped) on the same forward launches: no optimizer launch, so the
+// normalisation is asked for as the step's own single-pass launch
+static bool eq_receive_group_ok(bool norm_single, bool bn, bool folded) { return norm_single && bn && folded; }
 // per-block weight-gradient partials of the fused bottleneck backward, summed by a later launch
 struct EqBnParts { float *w2, *b2, *w1, *b1; int tiles; };      // [tiles][P][SK2], [tiles][SK2], [tiles][SK2][P], [tiles][P]
 static EqBnParts eq_bn_parts(float* base, int B, int SK2, int P) {
@@ -269,7 +276,6 @@ static int eq_step_plan(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
     if (!b->x || (!ro && !b->bits) || !b->eq_params || !b->rx_params || !b->out_eq || !b->chest || (!ro && !b->metrics))
         return DCCN_ERR_INVALID_ARG;
     if (ro && (train || !ro->packed)) return DCCN_ERR_INVALID_ARG;
-    if (ro && tl_chain.G > 1) return DCCN_ERR_UNSUPPORTED;
     if (train && (!b->eq_grads || !b->adam_m || !b->adam_v || !b->adam)) return DCCN_ERR_INVALID_ARG;
     EqStepPlan& p = *plan;
     p = EqStepPlan{};
@@ -317,7 +323,9 @@ static int eq_step_plan(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
     p.rxK = p.folded ? ncols : L.dK;
     p.fin_deferred = p.replan && train;
     const ChainCtx& all = tl_chain;
-    if (all.G > 1 && !eq_group_ok(p.rides, p.bn, p.folded)) return DCCN_ERR_UNSUPPORTED;
+    if (all.G > 1 && !(ro ? eq_receive_group_ok(eq_norm_single_ok(d, b->x, w.x_norm), p.bn, p.folded)
+                          : eq_group_ok(p.rides, p.bn, p.folded)))
+        return DCCN_ERR_UNSUPPORTED;
     bool done[kMaxChains] = {false, false, false, false, false, false, false, false};
     for (int g = 0; g < all.G; ++g) {
         if (done[g]) continue;
@@ -341,8 +349,16 @@ static int eq_step_plan(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
     }
     if (ro) {
         // what dense_decide_impl / decide_impl ask of the outputs; the stand-alone decision kernel reads z as float2
-        if (!decide_outputs_aligned(ro->llr, ro->prob, sh->nbits)) return DCCN_ERR_INVALID_ARG;
-        if (!(p.cls_fused[0] && sh->nbits <= 2) && (reinterpret_cast<uintptr_t>(w.z) & 7u) != 0) return DCCN_ERR_INVALID_ARG;
+        // (a group: asked per chain, with that chain's own pointers and modulation)
+        for (int g = 0; g < all.G; ++g) {
+            const int nbits = all.G == 1 ? sh->nbits : all.nbits[g];
+            const long long off = all.co.off[g];
+            const float* llr = ro->llr ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(ro->llr) + off) : nullptr;
+            const float* prob = ro->prob ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(ro->prob) + off) : nullptr;
+            if (!decide_outputs_aligned(llr, prob, nbits)) return DCCN_ERR_INVALID_ARG;
+            if (!(p.cls_fused[p.fin_class[g]] && nbits <= 2) && ((reinterpret_cast<uintptr_t>(w.z) + (uintptr_t)off) & 7u) != 0)
+                return DCCN_ERR_INVALID_ARG;
+        }
     }
     p.nv = norm_virtual_none();
     if (p.fin_deferred) {               // (the launch-per-stage plan has no optimizer launch that could carry either)
@@ -454,9 +470,8 @@ static int eq_issue_forward(const dccn_eq_shape* sh, const dccn_eq_buffers* b, c
         snr_now = p.want_snr;
     }
     if (snr_now) {
-        DCCN_NO_CHAINS();
-        hipLaunchKernelGGL(pilot_snr_kernel, dim3(B), dim3(64), 0, s, (const float2*)w.eq, b->pilot_carriers, b->snr_db, d.S, K,
-                           sh->P);
+        DCCN_LAUNCH_CHAINS_Z(pilot_snr_kernel, dim3(B), dim3(64), 0, s, (const float2*)w.eq, b->pilot_carriers, b->snr_db, d.S, K,
+                             sh->P);
         DCCN_LAUNCH_CHECK();
     }
     // :439-449 C-Conv "IDFT" of corr and eq, :456-463 concat + dense back to the receiver's input

@@ -178,9 +178,12 @@ __device__ __forceinline__ void pilot_snr_body(const float2* __restrict__ eq, co
     const float ratio = fminf(fmaxf(mean / var, 0.001f), 10000.0f);
     if (lane == 0) snr_db[frame] = logf(ratio) / logf(10.0f);
 }
+// (chain groups, common.h: blockIdx.z = chain, every pointer moves by that chain's arena offset)
 static __global__ __launch_bounds__(64) void pilot_snr_kernel(const float2* __restrict__ eq, const int* __restrict__ carriers,
-                                                       float* __restrict__ snr_db, int S, int K, int P) {
-    pilot_snr_body<false>(eq, nullptr, nullptr, carriers, snr_db, S, K, P, (int)blockIdx.x, (int)threadIdx.x);
+                                                       float* __restrict__ snr_db, int S, int K, int P, const ChainOffs co) {
+    const long long coff = co.off[blockIdx.z];
+    pilot_snr_body<false>(chain_at(eq, coff), nullptr, nullptr, chain_at(carriers, coff), chain_at(snr_db, coff), S, K, P,
+                          (int)blockIdx.x, (int)threadIdx.x);
 }
 // equalise + the pilot monitor in one launch: blocks [0, eq_blocks) equalise, each later block serves four frames
 static __global__ __launch_bounds__(256) void equalize_fwd_snr_kernel(const float2* __restrict__ y, const float2* __restrict__ h,

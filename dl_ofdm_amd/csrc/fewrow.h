@@ -431,18 +431,21 @@ __device__ __forceinline__ void fewrow_decide_tile(const GemmParams& p, const De
     if (orow < p.M && c < NB && b0 + c < dq.RB)
         dq.packed[(size_t)orow * dq.RB + b0 + c] = (unsigned char)((v >> (8 * (NB - 1 - c))) & 0xffu);
 }
+// (chain groups, common.h: blockIdx.z = chain, every pointer moves by that chain's arena offset; RB and NB are the launch's)
 template <int NG, int NB>
-__global__ __launch_bounds__(256) void fewrow_decide_kernel(const GemmParams p, const DecideEpiParams dq) {
+__global__ __launch_bounds__(256) void fewrow_decide_kernel(const GemmParams p0, const DecideEpiParams dq0, const ChainOffs co) {
+    const long long coff = co.off[blockIdx.z];
+    const GemmParams p = p0.at_chain(coff);
+    const DecideEpiParams dq = dq0.at_chain(coff);
     fewrow_decide_tile<NG, NB>(p, dq, (int)blockIdx.x, (int)gridDim.x);
 }
 template <int NB>
 static int launch_fewrow_decide(const GemmParams& p, const DecideEpiParams& dq, hipStream_t s) {
     const int T = ceil_div(p.M, 16) * (p.N / 16);
-    DCCN_NO_CHAINS();
     switch (fewrow_ng_c(p, false)) {
-        case 18: hipLaunchKernelGGL((fewrow_decide_kernel<18, NB>), dim3(T), dim3(256), 0, s, p, dq); break;
-        case 14: hipLaunchKernelGGL((fewrow_decide_kernel<14, NB>), dim3(T), dim3(256), 0, s, p, dq); break;
-        case 10: hipLaunchKernelGGL((fewrow_decide_kernel<10, NB>), dim3(T), dim3(256), 0, s, p, dq); break;
+        case 18: DCCN_LAUNCH_CHAINS_Z((fewrow_decide_kernel<18, NB>), dim3(T), dim3(256), 0, s, p, dq); break;
+        case 14: DCCN_LAUNCH_CHAINS_Z((fewrow_decide_kernel<14, NB>), dim3(T), dim3(256), 0, s, p, dq); break;
+        case 10: DCCN_LAUNCH_CHAINS_Z((fewrow_decide_kernel<10, NB>), dim3(T), dim3(256), 0, s, p, dq); break;
         default: return DCCN_ERR_INVALID_ARG;
     }
     DCCN_LAUNCH_CHECK();

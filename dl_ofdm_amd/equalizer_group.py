@@ -9,6 +9,9 @@ riding on its bottleneck backward launch (``mobile`` chains: as the step's first
 is bit for bit the one :func:`dl_ofdm_amd.receiver_mp.train` produces for it alone (tests/test_gpu_chain_groups.py).
 
     results = train_group([flags_bpsk, flags_qpsk, ...], [rx_params_bpsk, rx_params_qpsk, ...])
+
+The deployed side of the same chains -- label-free receive calls for several links at once -- is :class:`ChainReceiveGroup`
+(``dccn_eq_receive_step_grouped``), at the end of this module.
 """
 from __future__ import annotations
 
@@ -218,3 +221,114 @@ def train_group(flags_list: Sequence, rx_params_list: Sequence[Dict[str, np.ndar
     """:func:`dl_ofdm_amd.receiver_mp.train` (device_data; static or ``mobile`` channels) for several chains at once; returns one result dict
     per chain (history, best_path, trainer) -- the bits the per-chain function returns"""
     return EqualizerChainGroup(flags_list, rx_params_list, device=device).train(verbose=verbose)
+
+
+# ---- the receive path of a group: several links' frames per launch sequence ---------------------------------------------------
+def _eq_shape(FLAGS, o, batch: int, nbits: int) -> "_lib.EqShape":
+    return _lib.EqShape(int(batch), FLAGS.nsymbol, o.K, o.CP, 1 if FLAGS.cp else 0, FLAGS.nfilter, o.frame_size, nbits, o.pilot_size,
+                        len(o.pilotCarriers))
+
+
+def receive_arena_bytes_for(FLAGS, batch: int, lib=None) -> int:
+    """a receiving chain's arena: the trainer's five parameter-sized arrays, the fused step's workspace, the folded and the frozen
+    receiver, one plan's inputs and outputs, and packed / llr / prob set aside for 16-QAM"""
+    from .receive import row_bytes
+    lib = lib or _lib.load()
+    o = ofdm.ofdm_tx(FLAGS)
+    B, S, D, n_sc = int(batch), FLAGS.nsymbol, o.frame_size, o.K + o.CP
+    shape = _eq_shape(FLAGS, o, B, 4)
+    offs = (C.c_longlong * 21)()
+    check(lib.dccn_eq_param_offsets(C.byref(shape), offs), "dccn_eq_param_offsets")
+    n = 5 * 4 * int(offs[20]) + int(lib.dccn_eq_workspace_size(C.byref(shape), 1)) + 4 * int(lib.dccn_eq_rx_folded_floats(C.byref(shape)))
+    n += 4 * (2 * S * FLAGS.nfilter * 2 * D + n_sc * 2 * FLAGS.nfilter) + 4096      # frozen receiver
+    n += 3 * B * S * n_sc * 2 * 4 + B * D * 4 * 4                                   # x, out_eq, chest; label buffer of the plan
+    n += B * row_bytes(D, 4) + B * D * 4 * 4 + B * D * 4 * 2 * 4                    # packed, llr, prob
+    return (n + (1 << 20)) // 256 * 256
+
+
+class _ReceiveChain:
+    """one link: its arena, the trainer that holds the chain's parameters, the resident plan and the receive outputs"""
+
+    def __init__(self, FLAGS, rx_params, batch: int, device, arena_bytes: int, want_llr: bool, want_prob: bool):
+        from .equalizer import EqualizerTrainer, _FusedPlan
+        from .receive import row_bytes
+        self.F = FLAGS
+        self.o = ofdm.ofdm_tx(FLAGS)
+        self.arena = ChainArena(arena_bytes, device)
+        self.tr = EqualizerTrainer(FLAGS, self.o, rx_params, device=device, seed=int(getattr(FLAGS, "seed", 1)), arena=self.arena)
+        self.pl = _FusedPlan(self.tr, batch, arena=self.arena)
+        self.tr._plans[int(batch)] = self.pl
+        B, D, nbits = int(batch), int(self.o.frame_size), int(FLAGS.nbits)
+        self.D, self.nbits = D, nbits
+        # set aside for 16-QAM whatever this chain's modulation (the arena layout must not depend on it); each chain's rows keep
+        # their own length row_bytes(D, nbits)
+        self.packed = self.arena.zeros(B, row_bytes(D, nbits), dtype=torch.uint8, reserve=B * row_bytes(D, 4))
+        self.llr = self.arena.empty(B, D, nbits, dtype=torch.float32, reserve=B * D * 4) if want_llr else None
+        self.prob = self.arena.empty(B, D, nbits, 2, dtype=torch.float32, reserve=B * D * 4 * 2) if want_prob else None
+
+    def out(self, want_llr: bool, want_prob: bool) -> "_lib.ReceiveOut":
+        return _lib.ReceiveOut(self.packed.data_ptr(), self.llr.data_ptr() if want_llr else None,
+                               self.prob.data_ptr() if want_prob else None)
+
+
+class ChainReceiveGroup:
+    """Up to ``dccn_chain_group_max()`` (equaliser -> frozen receiver) chains of one shape and any mix of modulations whose
+    receive steps share ONE launch sequence (``dccn_eq_receive_step_grouped``): a host that serves several links, each with its
+    own trained chain, issues one call per round of frames.  Chain i's results are bit for bit what
+    ``EqualizerTrainer.receive`` returns for it alone.
+
+        group = ChainReceiveGroup([flags_bpsk, flags_16qam], [rx_bpsk, rx_16qam], batch=73, want_llr=True)
+        receiver_mp.load_checkpoint(path, group.chains[0].tr)          # or .tr.load_params(...): the trained equaliser
+        results = group.receive([frames_bpsk, frames_16qam])           # one ReceiveResult per chain
+
+    ``.chains[i].pl.out_eq`` / ``.chest`` / ``.snr_db`` hold what the chain's ``eval_step`` writes for the same frames."""
+
+    def __init__(self, flags_list: Sequence, rx_params_list: Sequence[Dict[str, np.ndarray]], batch: int, device="cuda",
+                 want_llr: bool = False, want_prob: bool = False):
+        self.lib = _lib.load()
+        gmax = int(self.lib.dccn_chain_group_max())
+        if not (1 <= len(flags_list) <= gmax) or len(rx_params_list) != len(flags_list):
+            raise ValueError("1..%d chains per group, one receiver per chain" % gmax)
+        self.batch = int(batch)
+        F0 = flags_list[0]
+        if len(flags_list) > 1 and not bool(self.lib.dccn_eq_receive_group_supported(
+                C.byref(_eq_shape(F0, ofdm.ofdm_tx(F0), self.batch, int(F0.nbits))))):
+            raise _lib.DccnError("dccn_eq_receive_group_supported: a receive step of %d frames of this shape has launches that "
+                                 "cannot carry several chains (receive the links one by one)" % self.batch)
+        nbytes = max(receive_arena_bytes_for(F, self.batch, self.lib) for F in flags_list)
+        self.chains: List[_ReceiveChain] = [_ReceiveChain(F, rx, self.batch, device, nbytes, want_llr, want_prob)
+                                            for F, rx in zip(flags_list, rx_params_list)]
+        check_same_layout([c.arena for c in self.chains])
+        self.device = self.chains[0].tr.device
+        self._shapes = _ptr_array([c.pl.shape for c in self.chains])
+        self._bufs = _ptr_array([c.pl.buffers for c in self.chains])
+        self.want_llr, self.want_prob = bool(want_llr), bool(want_prob)
+        self._outs = {}                                        # (llr, prob) asked for -> (the chains' dccn_receive_out, their table)
+
+    def _out_table(self, want_llr: bool, want_prob: bool):
+        key = (want_llr, want_prob)
+        if key not in self._outs:
+            structs = [c.out(want_llr, want_prob) for c in self.chains]
+            self._outs[key] = (structs, _ptr_array(structs))
+        return self._outs[key][1]
+
+    def receive(self, xs: Sequence, want_llr: Optional[bool] = None, want_prob: Optional[bool] = None) -> list:
+        """``xs[i]``: chain i's frames ``[batch, S, K + CP, 2]`` (host array or device tensor; ``None``: what ``.chains[i].pl.x``
+        holds).  ``want_llr`` / ``want_prob``: as the group was built (default), or ``False`` to leave that output out of this
+        call.  Returns one :class:`~dl_ofdm_amd.receive.ReceiveResult` per chain -- the chains' resident buffers: the next
+        call overwrites them."""
+        from .receive import ReceiveResult
+        if len(xs) != len(self.chains):
+            raise ValueError("one batch of frames per chain")
+        want_llr = self.want_llr if want_llr is None else bool(want_llr)
+        want_prob = self.want_prob if want_prob is None else bool(want_prob)
+        if (want_llr and not self.want_llr) or (want_prob and not self.want_prob):
+            raise ValueError("llr / prob were not set aside when the group was built (want_llr / want_prob)")
+        for c, x in zip(self.chains, xs):
+            if x is not None:
+                c.pl.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(c.pl.x.shape), non_blocking=True)
+            c.pl._ahead()[c.pl.ws.data_ptr()] = None           # (the step normalises into the chain's workspace)
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        check(self.lib.dccn_eq_receive_step_grouped(len(self.chains), self._shapes, self._bufs, self._out_table(want_llr, want_prob), st),
+              "dccn_eq_receive_step_grouped")
+        return [ReceiveResult(c.packed, c.llr if want_llr else None, c.prob if want_prob else None, c.D, c.nbits) for c in self.chains]

@@ -142,3 +142,10 @@ def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False) -> Rec
     pl.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(pl.x.shape), non_blocking=True)
     packed, llr, prob = pl.receive(want_llr, want_prob)
     return ReceiveResult(packed, llr, prob, int(tr.ofdmobj.frame_size), int(tr.FLAGS.nbits))
+
+
+def group_receive(group, xs) -> list:
+    """Several links' chains in ONE launch sequence (``dccn_eq_receive_step_grouped``): ``group`` is a
+    :class:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup`, ``xs`` one ``[batch, S, K + CP, 2]`` batch of frames per chain.
+    One :class:`ReceiveResult` per chain, bit for bit what :func:`chain_receive` returns for that chain alone."""
+    return group.receive(xs)

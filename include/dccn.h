@@ -803,8 +803,8 @@ int dccn_eq_train_step(const dccn_eq_shape* shape, const dccn_eq_buffers* buf, d
 /* The chain's receive step (see "receive path" above): the equaliser forward exactly as dccn_eq_eval_step runs it -- out_eq,
  * chest (and snr_db) are written as that step writes them -- and the frozen receiver with the decision stage in place of the
  * tail: buf->bits, buf->metrics, buf->prob and buf->tx_power may be NULL and are not touched.  Workspace: the evaluation
- * step's.  Chain groups are not supported here (DCCN_ERR_UNSUPPORTED).  llr / prob that miss the alignment of the decision
- * stage (see "receive path" above) are refused (DCCN_ERR_INVALID_ARG) before anything is launched. */
+ * step's.  Several chains per launch sequence: dccn_eq_receive_step_grouped ("chain groups" below).  llr / prob that miss the
+ * alignment of the decision stage (see "receive path" above) are refused (DCCN_ERR_INVALID_ARG) before anything is launched. */
 typedef struct dccn_receive_out {
     unsigned char* packed;     /* [batch, ceil(D*nbits/8)] */
     float* llr;                /* [batch, D, nbits], nullable */
@@ -834,6 +834,24 @@ int dccn_chain_group_max(void);
 int dccn_eq_group_supported(const dccn_eq_shape* shape);
 int dccn_eq_train_step_grouped(int n_chains, const dccn_eq_shape* const* shapes, const dccn_eq_buffers* const* bufs,
                                dccn_adam_hparams hp, dccn_stream_t stream);
+/* dccn_eq_receive_step for the chains of a group -- a host that serves several links, each with its own trained chain and
+ * modulation, issues ONE launch sequence per round of frames: every launch of the forward carries the chain index, the decision
+ * stage is launched once per distinct nbits on the chains of that modulation (its row stride ceil(D*nbits/8) and its kernels
+ * depend on it).  Chain g's packed / llr / prob, out_eq, chest and snr_db are bit for bit what dccn_eq_receive_step writes for
+ * chain g alone (tests/test_gpu_group_receive.py).
+ * Contract as dccn_eq_train_step_grouped: the shapes agree in everything but nbits; every pointer field of bufs[g] that the
+ * forward-only step uses (x, eq_params, rx_params, rx_folded, out_eq, chest, snr_db, pilot_carriers, workspace) and every
+ * pointer field of outs[g] (packed, llr, prob) lies at ONE byte offset, a multiple of 256, from chain 0's; a nullable field is
+ * NULL for all chains or for none; rx_folded must be given; x_prenormalised must be 0.  A violation returns
+ * DCCN_ERR_INVALID_ARG, nothing launched.  Each chain's packed keeps its own row length; a caller that wants one arena layout
+ * for every modulation sets packed / llr / prob aside for nbits = 4.  n_chains == 1 is dccn_eq_receive_step.
+ * dccn_eq_receive_group_supported (host only, launches nothing): 1 exactly for the shapes whose grouped receive step is accepted
+ * under the current knobs, given aligned buffers -- the forward of a training group without its optimizer launch (<= 96 frames,
+ * single-pass normalisation, the pilot bottleneck as one launch, the receiver folded).  Elsewhere the grouped call returns
+ * DCCN_ERR_UNSUPPORTED before anything is launched.  Grouped evaluation is not offered. */
+int dccn_eq_receive_group_supported(const dccn_eq_shape* shape);
+int dccn_eq_receive_step_grouped(int n_chains, const dccn_eq_shape* const* shapes, const dccn_eq_buffers* const* bufs,
+                                 const dccn_receive_out* const* outs, dccn_stream_t stream);
 /* the fused generator launch (dccn_gen_static_frames) / the launch that materialises x (dccn_gen_static_apply) for every chain of
  * a group: per-chain seed, offset and nbits, same layout contract on the descriptors' pointers (x_out / noise_power included) */
 int dccn_gen_static_frames_grouped(int n_chains, const dccn_gen_static* const* g, dccn_stream_t stream);

@@ -7,6 +7,9 @@
 
     python tools/rxbench.py [--iters 200] [--repeats 7]            -> one JSON line (all shapes)
     python tools/rxbench.py --one 1170,2 --only c --iters 50        -> one shape, one variant (kernel-trace runs)
+    python tools/rxbench.py --chains 2 4 8 [--mods 1 2 3 4] [--frames 73] [--out FILE]
+        several links, each with its own (equaliser -> frozen receiver) chain: (a) G solo receive calls back to back on one
+        stream against (b) ONE grouped call (dccn_eq_receive_step_grouped), per group size G; same alternation and repeats
 
 Shapes: 1170 frames QPSK and 16-QAM, and one 20 000-frame QPSK sweep batch (N = 64).  Every shape runs in a child process of
 its own under a time limit; the parent never opens the GPU and stops at the first child that fails.  Times are medians over
@@ -95,6 +98,83 @@ def run_one(frames, nbits, iters, repeats, only):
     return out
 
 
+def run_chains(mods, frames, iters, repeats):
+    """G (equaliser -> frozen receiver) chains, one per link, `frames` frames each: (a) G solo receive calls back to back on one
+    stream, (b) one grouped call -- same parameters, same frames, inputs resident; the two must agree before anything is timed"""
+    import numpy as np
+    import torch
+    from dl_ofdm_amd import ofdm, receiver as R, receiver_mp as H
+    from dl_ofdm_amd.engine import glorot_init
+    from dl_ofdm_amd.equalizer import EqualizerTrainer
+    from dl_ofdm_amd.equalizer_group import ChainReceiveGroup
+    fl = [H.Flags(nbits=nb, nfilter=F, seed=10 + i) for i, nb in enumerate(mods)]
+    rx = [glorot_init(R.rx_dims(f, ofdm.ofdm_tx(f)), 3 + i) for i, f in enumerate(fl)]
+    solo = [EqualizerTrainer(f, ofdm.ofdm_tx(f), r, seed=f.seed) for f, r in zip(fl, rx)]
+    grp = ChainReceiveGroup(fl, rx, frames)
+    rng = np.random.RandomState(0)
+    plans = []
+    for tr, ch in zip(solo, grp.chains):
+        ch.tr.load_params(tr.get_params())
+        pl = tr.resident(frames)
+        pl.x.copy_(torch.as_tensor((rng.standard_normal(tuple(pl.x.shape)) * 2).astype(np.float32)))
+        ch.pl.x.copy_(pl.x)
+        plans.append(pl)
+    none = [None] * len(mods)
+
+    def va():
+        return [pl.receive()[0] for pl in plans]
+
+    def vb():
+        return [r.packed for r in grp.receive(none)]
+    variants = {"a": va, "b": vb}
+    assert all(torch.equal(p, q) for p, q in zip(va(), vb()))
+    for f in variants.values():
+        for _ in range(20):
+            f()
+    torch.cuda.synchronize()
+    t = {k: [] for k in variants}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(repeats):
+        for k, f in variants.items():
+            e0.record()
+            for _ in range(iters):
+                f()
+            e1.record()
+            e1.synchronize()
+            t[k].append(e0.elapsed_time(e1) * 1e3 / iters)
+    out = {"chains": len(mods), "mods": list(mods), "frames": frames, "iters": iters, "repeats": repeats, "us": {}, "spread": {}}
+    for k, v in t.items():
+        v = sorted(v)
+        med = v[len(v) // 2]
+        out["us"][k] = round(med, 2)
+        out["spread"][k] = round((v[-1] - v[0]) / med, 4)
+    return out
+
+
+def main_chains(a):
+    """one child process per group size, under a time limit; the parent never opens the GPU and stops at the first failure"""
+    res = []
+    for G in a.chains:
+        mods = [a.mods[i % len(a.mods)] for i in range(G)]
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--one-chains", ",".join(map(str, mods)),
+               "--frames", str(a.frames), "--iters", str(a.iters), "--repeats", str(a.repeats)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        if r.returncode != 0:
+            sys.stderr.write(r.stderr[-2000:])
+            print(json.dumps({"bench": "rxbench.chains", "failed": G, "rc": r.returncode, "groups": res}))
+            return 1
+        res.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    doc = {"bench": "rxbench.chains", "variants": {"a": "G solo receive calls back to back, one stream", "b": "one grouped receive call"},
+           "unit": "us per round of G links (median over repeats of the mean of `iters` back-to-back rounds); spread = (max - min) / median",
+           "groups": res}
+    print(json.dumps(doc))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
@@ -102,7 +182,17 @@ def main():
     ap.add_argument("--one", default=None, help="frames,nbits: measure this shape in this process")
     ap.add_argument("--only", default=None, choices=["a", "b", "c", "d"])
     ap.add_argument("--limit", type=int, default=240, help="seconds per shape")
+    ap.add_argument("--chains", type=int, nargs="+", default=None, help="group sizes: G solo chain receive calls against one grouped call")
+    ap.add_argument("--mods", type=int, nargs="+", default=[1, 2, 3, 4], help="--chains: bits per cell of the links, cycled")
+    ap.add_argument("--frames", type=int, default=73, help="--chains: frames per link and call")
+    ap.add_argument("--one-chains", default=None, help="nbits,nbits,...: measure this group in this process")
+    ap.add_argument("--out", default=None, help="--chains: also write the result document to this file")
     a = ap.parse_args()
+    if a.one_chains:
+        print(json.dumps(run_chains([int(v) for v in a.one_chains.split(",")], a.frames, a.iters, a.repeats)))
+        return 0
+    if a.chains:
+        return main_chains(a)
     if a.one:
         fr, nb = (int(v) for v in a.one.split(","))
         print(json.dumps(run_one(fr, nb, a.iters, a.repeats, a.only)))
