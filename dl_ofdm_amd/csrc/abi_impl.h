@@ -212,7 +212,6 @@ int dense_tail_impl(bool bwd, const float* x, const float* w, const float* bias,
 bool dense_tail_ok(const float* x, const float* w, int M, int K, int N, int nbits);
 bool dense_tail_planned(int nbits, bool train, int M = 0, int N = 0);
 size_t dense_tail_ws_bytes(int M, int N, int nbits);
-int eq_monitor_blocks(int B, int K);
 int gen_static_args(const dccn_gen_static* g, GenStaticArgs* out);
 int gen_static_launch(const dccn_gen_static* g, hipStream_t s, const GenChainScalars* chains = nullptr);
 bool gen_static_shape_ok(int S, int K, int CP);            // the instantiated shapes: (7, 64, 16) and (7, 64, 4)
@@ -242,3 +241,32 @@ struct dccn_rx_graph {
     hipStream_t side;
     hipEvent_t ev_fork, ev_join;
 };
+
+namespace dccn {
+// One step captured into an instantiated graph: the handle and its capture stream, the side stream and the fork / join events
+// when the step forks, then issue(handle) -- the step's launches on handle.cap -- between begin and end of the capture.  Whatever
+// fails, the handle is destroyed and the step's own status (if it has one) is the one returned.
+template <typename Issue>
+static int graph_capture(bool fork, dccn_rx_graph** out, Issue&& issue) {
+    dccn_rx_graph* g = new dccn_rx_graph();
+    memset(g, 0, sizeof(*g));
+    const auto fail = [g](int status) {
+        dccn_rx_graph_destroy(g);
+        return status;
+    };
+    if (hipStreamCreateWithFlags(&g->cap, hipStreamNonBlocking) != hipSuccess) return fail(DCCN_ERR_LAUNCH);
+    if (fork && (hipStreamCreateWithFlags(&g->side, hipStreamNonBlocking) != hipSuccess ||
+                 hipEventCreateWithFlags(&g->ev_fork, hipEventDisableTiming) != hipSuccess ||
+                 hipEventCreateWithFlags(&g->ev_join, hipEventDisableTiming) != hipSuccess))
+        return fail(DCCN_ERR_LAUNCH);
+    hipError_t e = hipStreamBeginCapture(g->cap, hipStreamCaptureModeRelaxed);
+    if (e != hipSuccess) return fail(hip_fail(e));
+    const int st = issue(*g);
+    e = hipStreamEndCapture(g->cap, &g->graph);
+    if (st != DCCN_OK || e != hipSuccess) return fail(st != DCCN_OK ? st : hip_fail(e));
+    e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
+    if (e != hipSuccess) return fail(hip_fail(e));
+    *out = g;
+    return DCCN_OK;
+}
+}  // namespace dccn

@@ -1642,12 +1642,6 @@ static RxBackwardWs rx_backward_carve(Carver& c, int batch, int S, int kin, int 
     void* dense = c.take<char>(nd);
     return RxBackwardWs{dense, c.take<char>(nc), nd, nc};
 }
-
-int eq_monitor_blocks(int B, int K) {
-    long long n = ceil_div_ll((long long)B * K * 2, 256);
-    if (n > 256) n = 256;
-    return (int)(n < 1 ? 1 : n);
-}
 }  // namespace dccn
 
 using namespace dccn;
@@ -2046,40 +2040,10 @@ int dccn_rx_graph_create(const dccn_rx_shape* shape, const dccn_rx_buffers* buf,
     if (!out || !shape_ok(shape) || !buf) return DCCN_ERR_INVALID_ARG;
     const bool train = mode & 1, fork = (mode & 2) && train;
     (void)stream;
-    dccn_rx_graph* g = new dccn_rx_graph();
-    memset(g, 0, sizeof(*g));
-    if (hipStreamCreateWithFlags(&g->cap, hipStreamNonBlocking) != hipSuccess) {
-        dccn_rx_graph_destroy(g);
-        return DCCN_ERR_LAUNCH;
-    }
-    hipStream_t s = g->cap;
-    if (fork) {
-        if (hipStreamCreateWithFlags(&g->side, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&g->ev_fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&g->ev_join, hipEventDisableTiming) != hipSuccess) {
-            dccn_rx_graph_destroy(g);
-            return DCCN_ERR_LAUNCH;
-        }
-    }
-    hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
-    if (e != hipSuccess) {
-        dccn_rx_graph_destroy(g);
-        return hip_fail(e);
-    }
-    const OverlapStreams branch{g->side, g->ev_fork, g->ev_join};
-    const int st = rx_step_impl(shape, buf, train, hp, s, fork ? &branch : nullptr);
-    e = hipStreamEndCapture(s, &g->graph);
-    if (st != DCCN_OK || e != hipSuccess) {
-        dccn_rx_graph_destroy(g);
-        return st != DCCN_OK ? st : hip_fail(e);
-    }
-    e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) {
-        dccn_rx_graph_destroy(g);
-        return hip_fail(e);
-    }
-    *out = g;
-    return DCCN_OK;
+    return graph_capture(fork, out, [&](const dccn_rx_graph& g) {
+        const OverlapStreams branch{g.side, g.ev_fork, g.ev_join};
+        return rx_step_impl(shape, buf, train, hp, g.cap, fork ? &branch : nullptr);
+    });
 }
 // ---- HIP-event timers on the caller's stream ------------------------------------------------------------------
 int dccn_timer_create(dccn_timer** out) {

@@ -22,35 +22,16 @@ size_t dccn_eq_workspace_size(const dccn_eq_shape* shape, int train) {
 }
 int dccn_eq_workspace_tensor(const dccn_eq_shape* shape, int train, const char* name, size_t* byte_offset, size_t* count) {
     if (!eq_shape_ok(shape) || !name || !byte_offset || !count) return DCCN_ERR_INVALID_ARG;
-    const EqDims d = eq_dims(shape);
-    // carve a dummy base so that every pointer is base + offset (the Carver hands out nullptr for a null base)
-    char* const base = reinterpret_cast<char*>(static_cast<uintptr_t>(1) << 40);
-    Carver c(base, ~static_cast<size_t>(0) >> 2);
+    int status = DCCN_ERR_INVALID_ARG;          // (an unknown name; a training-only tensor of an evaluation workspace is not carved)
+    Carver c(nullptr, 0);
     EqWs w;
-    memset(&w, 0, sizeof(w));
-    eq_carve(c, shape, d, train != 0, w);
-    const size_t B = d.B, R = d.R, SK2 = d.SK2, K2 = 2 * (size_t)d.K, N2 = 2 * (size_t)d.nsc;
-    struct Ent { const char* n; const float* p; size_t cnt; bool tr; };
-    const Ent tab[] = {
-        {"x_norm", w.x_norm, R * N2, false}, {"ln", w.ln, R * N2, false}, {"t1", w.t1, R * K2, false}, {"y", w.y, R * K2, false},
-        {"d1", w.d1, B * d.Pp, false}, {"d2", w.d2, B * SK2, false}, {"d3", w.d3, B * SK2, false}, {"d4", w.d4, B * SK2, false},
-        {"T", w.T, SK2 * SK2, false}, {"be", w.be, SK2, false}, {"eq", w.eq, B * SK2, false}, {"corr", w.corr, B * SK2, false},
-        {"eqc", w.eqc, R * K2, false}, {"corc", w.corc, R * K2, false}, {"cat", w.cat, R * 2 * K2, false},
-        {"fft", w.fft, R * 2 * (size_t)d.F, false}, {"z", w.z, B * 2 * (size_t)d.D, false},
-        {"dz", w.dz, B * 2 * (size_t)d.D, true}, {"dfft", w.dfft, R * 2 * (size_t)d.F, true}, {"dout", w.dout, R * N2, true},
-        {"dcat", w.dcat, R * 2 * K2, true}, {"deqc", w.deqc, R * K2, true}, {"dcorc", w.dcorc, R * K2, true},
-        {"deq", w.deq, B * SK2, true}, {"dcorr", w.dcorr, B * SK2, true}, {"dy", w.dy, B * SK2, true}, {"dh", w.dh, B * SK2, true},
-        {"dT", w.dT, SK2 * SK2, true}, {"dbe", w.dbe, SK2, true}, {"dd4", w.dd4, B * SK2, true}, {"dd3", w.dd3, B * SK2, true},
-        {"dd2", w.dd2, B * SK2, true}, {"dd1", w.dd1, B * d.Pp, true}, {"dflat", w.dflat, B * SK2, true}, {"dt1", w.dt1, R * K2, true},
-    };
-    for (const Ent& e : tab) {
-        if (strcmp(e.n, name) != 0) continue;
-        if (e.tr && !train) return DCCN_ERR_INVALID_ARG;
-        *byte_offset = (size_t)(reinterpret_cast<const char*>(e.p) - base);
-        *count = e.cnt;
-        return DCCN_OK;
-    }
-    return DCCN_ERR_INVALID_ARG;
+    eq_carve(c, eq_dims(shape), train != 0, w, [&](const EqWsTensor& t, size_t off, size_t n) {
+        if (t.name == nullptr || strcmp(t.name, name) != 0) return;
+        *byte_offset = off;
+        *count = n;
+        status = DCCN_OK;
+    });
+    return status;
 }
 size_t dccn_eq_rx_folded_floats(const dccn_eq_shape* shape) {
     if (!eq_shape_ok(shape)) return 0;
@@ -81,8 +62,44 @@ int dccn_eq_train_step(const dccn_eq_shape* shape, const dccn_eq_buffers* buf, d
                        dccn_stream_t stream) {
     return eq_step_impl(shape, buf, true, hp, (hipStream_t)stream);
 }
+}  // extern "C"
+
 // ---- chain groups: G independent equaliser chains per launch sequence (common.h ChainCtx) ------------------------------
-// every device pointer of chain g must lie at ONE byte offset from chain 0's (the chains' arenas have the same layout)
+// every device pointer of chain g must lie at ONE byte offset from chain 0's (the chains' arenas have the same layout).
+// Each struct's device-pointer fields are listed ONCE, by a function that hands them to a PtrList in a fixed order; where an entry
+// point holds only some of them to the contract, that subset is a list of its own which the full list starts with.
+struct PtrList {
+    const void* p[32];
+    int n = 0;
+    bool ok = true;
+    void operator()(const void* q) {
+        if (n < 32) p[n++] = q;
+        else ok = false;
+    }
+};
+// what the forward-only step reads or writes (dccn_eq_receive_step: labels, metrics, gradients and optimizer state are not touched)
+static void eq_buffers_forward_pointers(const dccn_eq_buffers& b, PtrList& f) {
+    f(b.x); f(b.eq_params); f(b.rx_params); f(b.rx_folded); f(b.out_eq); f(b.chest); f(b.snr_db); f(b.pilot_carriers); f(b.workspace);
+}
+// (prob is no part of the arena -- its size depends on the modulation -- and a training group refuses it)
+static void eq_buffers_pointers(const dccn_eq_buffers& b, PtrList& f) {
+    eq_buffers_forward_pointers(b, f);
+    f(b.bits); f(b.eq_grads); f(b.adam_m); f(b.adam_v); f(b.reg_coef); f(b.adam); f(b.metrics); f(b.tx_power); f(b.x_next);
+}
+static void receive_out_pointers(const dccn_receive_out& o, PtrList& f) { f(o.packed); f(o.llr); f(o.prob); }
+static void eq_monitor_pointers(const dccn_eq_monitor& m, PtrList& f) {
+    f(m.chest); f(m.chan); f(m.metrics); f(m.tx_power); f(m.noise_power); f(m.acc5); f(m.rms_out); f(m.workspace);
+}
+// what the normalisation of the next batch reads from a descriptor (dccn_eq_buffers.x_next_virtual)
+static void gen_static_norm_pointers(const dccn_gen_static& g, PtrList& f) {
+    f(g.y); f(g.noise); f(g.power_partial); f(g.noise_partial); f(g.noise_power_out);
+}
+static void gen_static_pointers(const dccn_gen_static& g, PtrList& f) {
+    gen_static_norm_pointers(g, f);
+    f(g.bits_out); f(g.cell_map); f(g.const_tab); f(g.idft); f(g.coeff); f(g.alpha); f(g.snr_db); f(g.tx_out); f(g.H_out);
+    for (int i = 0; i < g.n_profiles; ++i) { f(g.profiles[i].coeff); f(g.profiles[i].alpha); }
+}
+
 struct ChainOffsetCheck {
     long long off[kMaxChains];
     bool have[kMaxChains];
@@ -99,6 +116,20 @@ struct ChainOffsetCheck {
             else if (off[g] != d) ok = false;
         }
     }
+    // every field `list` names, of the chains' structs s[g]
+    template <typename T>
+    void fields(const T* const* s, void (*list)(const T&, PtrList&)) {
+        PtrList v[kMaxChains];
+        for (int g = 0; g < n; ++g) {
+            list(*s[g], v[g]);
+            if (!v[g].ok || v[g].n != v[0].n) { ok = false; return; }
+        }
+        for (int f = 0; f < v[0].n; ++f) {
+            const void* p[kMaxChains];
+            for (int g = 0; g < n; ++g) p[g] = v[g].p[f];
+            field(p);
+        }
+    }
     bool finish(ChainCtx* ctx) {
         if (!ok) return false;
         ctx->G = n;
@@ -110,12 +141,32 @@ struct ChainOffsetCheck {
         return true;
     }
 };
-#define CHAIN_FIELD(chk, arr, n, member)                                             \
-    do {                                                                             \
-        const void* f__[kMaxChains];                                                 \
-        for (int g__ = 0; g__ < (n); ++g__) f__[g__] = (const void*)((arr)[g__]->member); \
-        (chk).field(f__);                                                            \
-    } while (0)
+
+// What every grouped entry point does, in this order; the callables are what is the entry point's own:
+//   the count and the tables are there                                                      else DCCN_ERR_INVALID_ARG
+//   valid(i)       chain i's structs are there, valid, and of chain 0's launch plan         else DCCN_ERR_INVALID_ARG
+//   solo()         n_chains == 1 is the single-chain entry
+//   supported()    the launches can carry a chain index (asked under the global knobs)      else DCCN_ERR_UNSUPPORTED
+//   fields(chk)    the pointer lists under the layout contract; false: a refusal of its own  else DCCN_ERR_INVALID_ARG
+//   scalars(ctx)   what is checked once the offsets stand, and the per-chain scalars; returns a status
+//   issue()        the single-chain launch sequence on chain 0's structs, inside the group's ChainScope
+template <typename Valid, typename Solo, typename Supported, typename Fields, typename Scalars, typename Issue>
+static int chain_group_call(int n_chains, bool tables, Valid valid, Solo solo, Supported supported, Fields fields, Scalars scalars,
+                            Issue issue) {
+    if (n_chains < 1 || n_chains > kMaxChains || !tables) return DCCN_ERR_INVALID_ARG;
+    for (int i = 0; i < n_chains; ++i)
+        if (!valid(i)) return DCCN_ERR_INVALID_ARG;
+    if (n_chains == 1) return solo();
+    if (!supported()) return DCCN_ERR_UNSUPPORTED;
+    ChainOffsetCheck chk(n_chains);
+    ChainCtx ctx;
+    if (!fields(chk) || !chk.finish(&ctx)) return DCCN_ERR_INVALID_ARG;
+    DCCN_TRY(scalars(ctx));
+    ChainScope scope(ctx);
+    return issue();
+}
+static bool group_always() { return true; }
+static int group_no_scalars(ChainCtx&) { return DCCN_OK; }
 
 static bool gen_static_same_plan(const dccn_gen_static* a, const dccn_gen_static* b) {
     if (a->frames != b->frames || a->S != b->S || a->K != b->K || a->CP != b->CP || a->D != b->D || a->n_taps != b->n_taps ||
@@ -129,198 +180,156 @@ static bool gen_static_same_plan(const dccn_gen_static* a, const dccn_gen_static
             return false;
     return true;
 }
-static void gen_static_chain_fields(ChainOffsetCheck& chk, const dccn_gen_static* const* g, int n) {
-    CHAIN_FIELD(chk, g, n, bits_out); CHAIN_FIELD(chk, g, n, cell_map); CHAIN_FIELD(chk, g, n, const_tab);
-    CHAIN_FIELD(chk, g, n, idft); CHAIN_FIELD(chk, g, n, coeff); CHAIN_FIELD(chk, g, n, alpha); CHAIN_FIELD(chk, g, n, snr_db);
-    CHAIN_FIELD(chk, g, n, y); CHAIN_FIELD(chk, g, n, noise); CHAIN_FIELD(chk, g, n, power_partial);
-    CHAIN_FIELD(chk, g, n, noise_partial); CHAIN_FIELD(chk, g, n, noise_power_out); CHAIN_FIELD(chk, g, n, tx_out);
-    CHAIN_FIELD(chk, g, n, H_out);
-    for (int i = 0; i < g[0]->n_profiles && chk.ok; ++i) {
-        CHAIN_FIELD(chk, g, n, profiles[i].coeff);
-        CHAIN_FIELD(chk, g, n, profiles[i].alpha);
-    }
+// one launch plan: everything but the modulation agrees
+static bool eq_shapes_one_plan(const dccn_eq_shape* a, const dccn_eq_shape* c) {
+    return a->batch == c->batch && a->S == c->S && a->K == c->K && a->CP == c->CP && a->cp == c->cp && a->F == c->F && a->D == c->D &&
+           a->pilot_size == c->pilot_size && a->P == c->P;
 }
+static bool eq_monitors_one_plan(const dccn_eq_monitor* a, const dccn_eq_monitor* b) {
+    return a->chan_per_symbol == b->chan_per_symbol && a->B == b->B && a->S == b->S && a->K == b->K &&
+           a->workspace_bytes == b->workspace_bytes;
+}
+// the step's own predicates, given 16-byte aligned buffers (and rx_folded): 1 exactly where a grouped training step / a grouped
+// receive step is accepted
+static int eq_group_query(const dccn_eq_shape* shape, bool receive) {
+    if (!eq_shape_ok(shape)) return 0;
+    const EqDims d = eq_dims(shape);
+    const dccn_rx_shape rsh = eq_rx_shape(d, shape->nbits);
+    const RxLayout L = rx_layout(&rsh);
+    const bool bn = eq_bn_ok(d, nullptr, nullptr, nullptr, nullptr);
+    const bool folded = eq_rx_folded_ok(d, eq_few_rx_ok(d, L, nullptr, nullptr, nullptr), nullptr, nullptr);
+    return (receive ? eq_receive_group_ok(eq_norm_single_ok(d, nullptr, nullptr), bn, folded)
+                    : eq_group_ok(eq_norm_rides_ok(d, true, nullptr, nullptr), bn, folded)) ? 1 : 0;
+}
+// the monitors' own launch (the step's optimizer launch carries the same argument block: eq_step_plan)
+static int eq_monitor_accumulate(const dccn_eq_monitor& m, hipStream_t s) {
+    if (!m.chest || !m.chan || m.B <= 0 || m.S <= 0 || m.K <= 0 || (m.acc5 && !m.metrics) || (!m.acc5 && !m.rms_out))
+        return DCCN_ERR_INVALID_ARG;
+    if (!m.workspace || m.workspace_bytes < dccn_eq_monitor_workspace_size(m.B, m.S, m.K)) return DCCN_ERR_WORKSPACE;
+    DCCN_LAUNCH_CHAINS_Z(eq_monitor_kernel, dim3(eq_monitor_blocks(m.B, m.K)), dim3(256), 0, s, eq_monitor_args(m));
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+extern "C" {
 
 int dccn_chain_group_max(void) { return kMaxChains; }
 
 int dccn_gen_static_frames_grouped(int n_chains, const dccn_gen_static* const* g, dccn_stream_t stream) {
-    if (n_chains < 1 || n_chains > kMaxChains || !g) return DCCN_ERR_INVALID_ARG;
-    for (int i = 0; i < n_chains; ++i)
-        if (!g[i] || !gen_static_ok(g[i]) || !gen_static_same_plan(g[0], g[i])) return DCCN_ERR_INVALID_ARG;
-    if (n_chains == 1) return gen_static_launch(g[0], (hipStream_t)stream);
-    ChainOffsetCheck chk(n_chains);
-    gen_static_chain_fields(chk, g, n_chains);
-    ChainCtx ctx;
-    if (!chk.finish(&ctx)) return DCCN_ERR_INVALID_ARG;
     GenChainScalars gc;
     memset(&gc, 0, sizeof(gc));
-    gc.n = n_chains;
-    for (int i = 0; i < n_chains; ++i) { gc.nbits[i] = g[i]->nbits; gc.offset[i] = g[i]->offset; gc.seed[i] = g[i]->seed; ctx.nbits[i] = g[i]->nbits; }
-    ChainScope scope(ctx);
-    return gen_static_launch(g[0], (hipStream_t)stream, &gc);
+    return chain_group_call(
+        n_chains, g != nullptr, [&](int i) { return g[i] && gen_static_ok(g[i]) && gen_static_same_plan(g[0], g[i]); },
+        [&] { return gen_static_launch(g[0], (hipStream_t)stream); }, group_always,
+        [&](ChainOffsetCheck& chk) { chk.fields(g, gen_static_pointers); return true; },
+        [&](ChainCtx& ctx) -> int {
+            gc.n = n_chains;
+            for (int i = 0; i < n_chains; ++i) { gc.nbits[i] = g[i]->nbits; gc.offset[i] = g[i]->offset; gc.seed[i] = g[i]->seed; ctx.nbits[i] = g[i]->nbits; }
+            return DCCN_OK;
+        },
+        [&] { return gen_static_launch(g[0], (hipStream_t)stream, &gc); });
 }
 
 int dccn_gen_static_apply_grouped(int n_chains, const dccn_gen_static* const* g, float* const* x_out, float* const* noise_power,
                                   dccn_stream_t stream) {
-    if (n_chains < 1 || n_chains > kMaxChains || !g || !x_out) return DCCN_ERR_INVALID_ARG;
-    for (int i = 0; i < n_chains; ++i)
-        if (!g[i] || !x_out[i] || !gen_static_ok(g[i]) || !gen_static_same_plan(g[0], g[i])) return DCCN_ERR_INVALID_ARG;
-    if (n_chains == 1) return dccn_gen_static_apply(g[0], x_out[0], noise_power ? noise_power[0] : nullptr, stream);
-    ChainOffsetCheck chk(n_chains);
-    gen_static_chain_fields(chk, g, n_chains);
-    chk.field(reinterpret_cast<const void* const*>(x_out));
-    if (noise_power) chk.field(reinterpret_cast<const void* const*>(noise_power));
-    ChainCtx ctx;
-    if (!chk.finish(&ctx)) return DCCN_ERR_INVALID_ARG;
-    ChainScope scope(ctx);
-    return dccn_gen_static_apply(g[0], x_out[0], noise_power ? noise_power[0] : nullptr, stream);
+    const auto apply = [&] { return dccn_gen_static_apply(g[0], x_out[0], noise_power ? noise_power[0] : nullptr, stream); };
+    return chain_group_call(
+        n_chains, g && x_out, [&](int i) { return g[i] && x_out[i] && gen_static_ok(g[i]) && gen_static_same_plan(g[0], g[i]); }, apply,
+        group_always,
+        [&](ChainOffsetCheck& chk) {
+            chk.fields(g, gen_static_pointers);
+            chk.field(reinterpret_cast<const void* const*>(x_out));
+            if (noise_power) chk.field(reinterpret_cast<const void* const*>(noise_power));
+            return true;
+        },
+        group_no_scalars, apply);
 }
 
-int dccn_eq_group_supported(const dccn_eq_shape* shape) {
-    if (!eq_shape_ok(shape)) return 0;
-    const EqDims d = eq_dims(shape);
-    const dccn_rx_shape rsh = eq_rx_shape(d, shape->nbits);
-    const RxLayout L = rx_layout(&rsh);
-    // the step's own predicates, given 16-byte aligned buffers (and rx_folded): 1 exactly where a grouped step is accepted
-    const bool few_rx = eq_few_rx_ok(d, L, nullptr, nullptr, nullptr);
-    return eq_group_ok(eq_norm_rides_ok(d, true, nullptr, nullptr), eq_bn_ok(d, nullptr, nullptr, nullptr, nullptr),
-                       eq_rx_folded_ok(d, few_rx, nullptr, nullptr)) ? 1 : 0;
-}
+int dccn_eq_group_supported(const dccn_eq_shape* shape) { return eq_group_query(shape, false); }
 
 int dccn_eq_train_step_grouped(int n_chains, const dccn_eq_shape* const* shapes, const dccn_eq_buffers* const* bufs,
                                dccn_adam_hparams hp, dccn_stream_t stream) {
-    if (n_chains < 1 || n_chains > kMaxChains || !shapes || !bufs) return DCCN_ERR_INVALID_ARG;
-    for (int i = 0; i < n_chains; ++i) {
-        if (!shapes[i] || !bufs[i] || !eq_shape_ok(shapes[i])) return DCCN_ERR_INVALID_ARG;
-        const dccn_eq_shape *a = shapes[0], *c = shapes[i];
-        // one launch plan: everything but the modulation agrees
-        if (a->batch != c->batch || a->S != c->S || a->K != c->K || a->CP != c->CP || a->cp != c->cp || a->F != c->F || a->D != c->D ||
-            a->pilot_size != c->pilot_size || a->P != c->P)
-            return DCCN_ERR_INVALID_ARG;
-        const dccn_eq_buffers *p = bufs[0], *q = bufs[i];
-        if (p->workspace_bytes != q->workspace_bytes || p->reg_uniform != q->reg_uniform || p->x_prenormalised != q->x_prenormalised ||
-            p->norm_slot != q->norm_slot || (p->x_next_virtual == nullptr) != (q->x_next_virtual == nullptr))
-            return DCCN_ERR_INVALID_ARG;
-        if (q->prob != nullptr) return DCCN_ERR_INVALID_ARG;          // (its size depends on the modulation: not part of the arena)
-    }
-    if (n_chains == 1) return eq_step_impl(shapes[0], bufs[0], true, hp, (hipStream_t)stream);
-    if (!dccn_eq_group_supported(shapes[0])) return DCCN_ERR_UNSUPPORTED;
-    ChainOffsetCheck chk(n_chains);
-    CHAIN_FIELD(chk, bufs, n_chains, x); CHAIN_FIELD(chk, bufs, n_chains, bits); CHAIN_FIELD(chk, bufs, n_chains, eq_params);
-    CHAIN_FIELD(chk, bufs, n_chains, eq_grads); CHAIN_FIELD(chk, bufs, n_chains, adam_m); CHAIN_FIELD(chk, bufs, n_chains, adam_v);
-    CHAIN_FIELD(chk, bufs, n_chains, reg_coef); CHAIN_FIELD(chk, bufs, n_chains, adam); CHAIN_FIELD(chk, bufs, n_chains, rx_params);
-    CHAIN_FIELD(chk, bufs, n_chains, out_eq); CHAIN_FIELD(chk, bufs, n_chains, chest); CHAIN_FIELD(chk, bufs, n_chains, snr_db);
-    CHAIN_FIELD(chk, bufs, n_chains, pilot_carriers); CHAIN_FIELD(chk, bufs, n_chains, metrics); CHAIN_FIELD(chk, bufs, n_chains, tx_power);
-    CHAIN_FIELD(chk, bufs, n_chains, workspace); CHAIN_FIELD(chk, bufs, n_chains, rx_folded); CHAIN_FIELD(chk, bufs, n_chains, x_next);
-    if (bufs[0]->x_next_virtual != nullptr) {
-        const dccn_gen_static* gv[kMaxChains];
-        for (int i = 0; i < n_chains; ++i) {
-            gv[i] = bufs[i]->x_next_virtual;
-            if (!gen_static_same_plan(gv[0], gv[i])) return DCCN_ERR_INVALID_ARG;
-        }
-        CHAIN_FIELD(chk, gv, n_chains, y); CHAIN_FIELD(chk, gv, n_chains, noise); CHAIN_FIELD(chk, gv, n_chains, power_partial);
-        CHAIN_FIELD(chk, gv, n_chains, noise_partial); CHAIN_FIELD(chk, gv, n_chains, noise_power_out);
-    }
-    for (int i = 0; i < n_chains; ++i)
-        if ((bufs[i]->monitor == nullptr) != (bufs[0]->monitor == nullptr)) return DCCN_ERR_INVALID_ARG;
-    if (bufs[0]->monitor != nullptr) {
-        const dccn_eq_monitor* mm[kMaxChains];
-        for (int i = 0; i < n_chains; ++i) {
-            mm[i] = bufs[i]->monitor;
-            if (mm[i]->chan_per_symbol != mm[0]->chan_per_symbol || mm[i]->workspace_bytes != mm[0]->workspace_bytes)
-                return DCCN_ERR_INVALID_ARG;
-        }
-        CHAIN_FIELD(chk, mm, n_chains, chest); CHAIN_FIELD(chk, mm, n_chains, chan); CHAIN_FIELD(chk, mm, n_chains, metrics);
-        CHAIN_FIELD(chk, mm, n_chains, tx_power); CHAIN_FIELD(chk, mm, n_chains, noise_power); CHAIN_FIELD(chk, mm, n_chains, acc5);
-        CHAIN_FIELD(chk, mm, n_chains, rms_out); CHAIN_FIELD(chk, mm, n_chains, workspace);
-    }
-    ChainCtx ctx;
-    if (!chk.finish(&ctx)) return DCCN_ERR_INVALID_ARG;
-    if (bufs[0]->rx_folded == nullptr) return DCCN_ERR_UNSUPPORTED;
-    for (int i = 0; i < n_chains; ++i) {
-        ctx.nbits[i] = shapes[i]->nbits;
-        if (bufs[i]->gen_next_rides != bufs[0]->gen_next_rides) return DCCN_ERR_INVALID_ARG;
-        if (bufs[0]->gen_next_rides) {                     // (the generator's per-chain scalars travel with the group)
-            const dccn_gen_static* gv = bufs[i]->x_next_virtual;
-            if (!gv) return DCCN_ERR_INVALID_ARG;
-            ctx.gen_seed[i] = gv->seed; ctx.gen_offset[i] = gv->offset; ctx.gen_nbits[i] = gv->nbits;
-        }
-    }
-    if (bufs[0]->gen_next_rides) {
-        const dccn_gen_static* gv[kMaxChains];
-        for (int i = 0; i < n_chains; ++i) gv[i] = bufs[i]->x_next_virtual;
-        ChainOffsetCheck chk2(n_chains);
-        gen_static_chain_fields(chk2, gv, n_chains);
-        ChainCtx same;
-        if (!chk2.finish(&same)) return DCCN_ERR_INVALID_ARG;
-        for (int i = 0; i < n_chains; ++i)
-            if (same.co.off[i] != ctx.co.off[i]) return DCCN_ERR_INVALID_ARG;
-    }
-    ChainScope scope(ctx);
-    return eq_step_impl(shapes[0], bufs[0], true, hp, (hipStream_t)stream);
+    const auto step = [&] { return eq_step_impl(shapes[0], bufs[0], true, hp, (hipStream_t)stream); };
+    return chain_group_call(
+        n_chains, shapes && bufs,
+        [&](int i) {
+            if (!shapes[i] || !bufs[i] || !eq_shape_ok(shapes[i]) || !eq_shapes_one_plan(shapes[0], shapes[i])) return false;
+            const dccn_eq_buffers *p = bufs[0], *q = bufs[i];
+            return p->workspace_bytes == q->workspace_bytes && p->reg_uniform == q->reg_uniform &&
+                   p->x_prenormalised == q->x_prenormalised && p->norm_slot == q->norm_slot &&
+                   (p->x_next_virtual == nullptr) == (q->x_next_virtual == nullptr) && q->prob == nullptr;
+        },
+        step, [&] { return dccn_eq_group_supported(shapes[0]) != 0; },
+        [&](ChainOffsetCheck& chk) {
+            chk.fields(bufs, eq_buffers_pointers);
+            if (bufs[0]->x_next_virtual != nullptr) {
+                const dccn_gen_static* gv[kMaxChains];
+                for (int i = 0; i < n_chains; ++i) {
+                    gv[i] = bufs[i]->x_next_virtual;
+                    if (!gen_static_same_plan(gv[0], gv[i])) return false;
+                }
+                // a descriptor the step arms itself (gen_next_rides: its generator runs inside the step) is held to the contract
+                // whole, one that the caller's own launch filled in what the step reads of it
+                chk.fields(gv, bufs[0]->gen_next_rides ? gen_static_pointers : gen_static_norm_pointers);
+            }
+            const dccn_eq_monitor* mm[kMaxChains];
+            for (int i = 0; i < n_chains; ++i)
+                if (((mm[i] = bufs[i]->monitor) == nullptr) != (mm[0] == nullptr)) return false;
+            if (mm[0] == nullptr) return true;
+            for (int i = 0; i < n_chains; ++i)
+                if (!eq_monitors_one_plan(mm[0], mm[i])) return false;
+            chk.fields(mm, eq_monitor_pointers);
+            return true;
+        },
+        [&](ChainCtx& ctx) -> int {
+            if (bufs[0]->rx_folded == nullptr) return DCCN_ERR_UNSUPPORTED;
+            for (int i = 0; i < n_chains; ++i) {
+                ctx.nbits[i] = shapes[i]->nbits;
+                if (bufs[i]->gen_next_rides != bufs[0]->gen_next_rides) return DCCN_ERR_INVALID_ARG;
+                if (bufs[0]->gen_next_rides) {                     // (the generator's per-chain scalars travel with the group)
+                    const dccn_gen_static* gv = bufs[i]->x_next_virtual;
+                    if (!gv) return DCCN_ERR_INVALID_ARG;
+                    ctx.gen_seed[i] = gv->seed; ctx.gen_offset[i] = gv->offset; ctx.gen_nbits[i] = gv->nbits;
+                }
+            }
+            return DCCN_OK;
+        },
+        step);
 }
 
-int dccn_eq_receive_group_supported(const dccn_eq_shape* shape) {
-    if (!eq_shape_ok(shape)) return 0;
-    const EqDims d = eq_dims(shape);
-    const dccn_rx_shape rsh = eq_rx_shape(d, shape->nbits);
-    const RxLayout L = rx_layout(&rsh);
-    // the step's own predicates, given 16-byte aligned buffers (and rx_folded): 1 exactly where a grouped receive step is accepted
-    const bool few_rx = eq_few_rx_ok(d, L, nullptr, nullptr, nullptr);
-    return eq_receive_group_ok(eq_norm_single_ok(d, nullptr, nullptr), eq_bn_ok(d, nullptr, nullptr, nullptr, nullptr),
-                               eq_rx_folded_ok(d, few_rx, nullptr, nullptr)) ? 1 : 0;
-}
+int dccn_eq_receive_group_supported(const dccn_eq_shape* shape) { return eq_group_query(shape, true); }
 
 int dccn_eq_receive_step_grouped(int n_chains, const dccn_eq_shape* const* shapes, const dccn_eq_buffers* const* bufs,
                                  const dccn_receive_out* const* outs, dccn_stream_t stream) {
-    if (n_chains < 1 || n_chains > kMaxChains || !shapes || !bufs || !outs) return DCCN_ERR_INVALID_ARG;
-    for (int i = 0; i < n_chains; ++i) {
-        if (!shapes[i] || !bufs[i] || !outs[i] || !outs[i]->packed || !eq_shape_ok(shapes[i])) return DCCN_ERR_INVALID_ARG;
-        const dccn_eq_shape *a = shapes[0], *c = shapes[i];
-        // one launch plan: everything but the modulation agrees
-        if (a->batch != c->batch || a->S != c->S || a->K != c->K || a->CP != c->CP || a->cp != c->cp || a->F != c->F || a->D != c->D ||
-            a->pilot_size != c->pilot_size || a->P != c->P)
-            return DCCN_ERR_INVALID_ARG;
-        const dccn_eq_buffers *p = bufs[0], *q = bufs[i];
-        if (p->workspace_bytes != q->workspace_bytes || p->norm_slot != q->norm_slot || q->x_prenormalised != 0)
-            return DCCN_ERR_INVALID_ARG;
-    }
-    if (n_chains == 1) return dccn_eq_receive_step(shapes[0], bufs[0], outs[0], stream);
-    if (!dccn_eq_receive_group_supported(shapes[0])) return DCCN_ERR_UNSUPPORTED;
-    // what the forward-only step reads or writes (labels, metrics, gradients and optimizer state are not touched)
-    ChainOffsetCheck chk(n_chains);
-    CHAIN_FIELD(chk, bufs, n_chains, x); CHAIN_FIELD(chk, bufs, n_chains, eq_params); CHAIN_FIELD(chk, bufs, n_chains, rx_params);
-    CHAIN_FIELD(chk, bufs, n_chains, rx_folded); CHAIN_FIELD(chk, bufs, n_chains, out_eq); CHAIN_FIELD(chk, bufs, n_chains, chest);
-    CHAIN_FIELD(chk, bufs, n_chains, snr_db); CHAIN_FIELD(chk, bufs, n_chains, pilot_carriers); CHAIN_FIELD(chk, bufs, n_chains, workspace);
-    CHAIN_FIELD(chk, outs, n_chains, packed); CHAIN_FIELD(chk, outs, n_chains, llr); CHAIN_FIELD(chk, outs, n_chains, prob);
-    ChainCtx ctx;
-    if (!chk.finish(&ctx) || bufs[0]->rx_folded == nullptr) return DCCN_ERR_INVALID_ARG;
-    for (int i = 0; i < n_chains; ++i) ctx.nbits[i] = shapes[i]->nbits;
-    ChainScope scope(ctx);
-    return eq_step_impl(shapes[0], bufs[0], false, dccn_adam_hparams(), (hipStream_t)stream, outs[0]);
+    return chain_group_call(
+        n_chains, shapes && bufs && outs,
+        [&](int i) {
+            if (!shapes[i] || !bufs[i] || !outs[i] || !outs[i]->packed || !eq_shape_ok(shapes[i]) ||
+                !eq_shapes_one_plan(shapes[0], shapes[i]))
+                return false;
+            const dccn_eq_buffers *p = bufs[0], *q = bufs[i];
+            return p->workspace_bytes == q->workspace_bytes && p->norm_slot == q->norm_slot && q->x_prenormalised == 0;
+        },
+        [&] { return dccn_eq_receive_step(shapes[0], bufs[0], outs[0], stream); },
+        [&] { return dccn_eq_receive_group_supported(shapes[0]) != 0; },
+        [&](ChainOffsetCheck& chk) {
+            chk.fields(bufs, eq_buffers_forward_pointers);
+            chk.fields(outs, receive_out_pointers);
+            return true;
+        },
+        [&](ChainCtx& ctx) -> int {
+            if (bufs[0]->rx_folded == nullptr) return DCCN_ERR_INVALID_ARG;
+            for (int i = 0; i < n_chains; ++i) ctx.nbits[i] = shapes[i]->nbits;
+            return DCCN_OK;
+        },
+        [&] { return eq_step_impl(shapes[0], bufs[0], false, dccn_adam_hparams(), (hipStream_t)stream, outs[0]); });
 }
 
 int dccn_eq_monitor_accumulate_grouped(int n_chains, const dccn_eq_monitor* const* m, dccn_stream_t stream) {
-    if (n_chains < 1 || n_chains > kMaxChains || !m) return DCCN_ERR_INVALID_ARG;
-    for (int i = 0; i < n_chains; ++i) {
-        if (!m[i]) return DCCN_ERR_INVALID_ARG;
-        if (m[i]->chan_per_symbol != m[0]->chan_per_symbol || m[i]->B != m[0]->B || m[i]->S != m[0]->S || m[i]->K != m[0]->K ||
-            m[i]->workspace_bytes != m[0]->workspace_bytes)
-            return DCCN_ERR_INVALID_ARG;
-    }
-    const dccn_eq_monitor* a = m[0];
-    if (n_chains == 1)
-        return dccn_eq_monitor_accumulate(a->chest, a->chan, a->chan_per_symbol, a->B, a->S, a->K, a->metrics, a->tx_power,
-                                          a->noise_power, a->acc5, a->rms_out, a->workspace, a->workspace_bytes, stream);
-    ChainOffsetCheck chk(n_chains);
-    CHAIN_FIELD(chk, m, n_chains, chest); CHAIN_FIELD(chk, m, n_chains, chan); CHAIN_FIELD(chk, m, n_chains, metrics);
-    CHAIN_FIELD(chk, m, n_chains, tx_power); CHAIN_FIELD(chk, m, n_chains, noise_power); CHAIN_FIELD(chk, m, n_chains, acc5);
-    CHAIN_FIELD(chk, m, n_chains, rms_out); CHAIN_FIELD(chk, m, n_chains, workspace);
-    ChainCtx ctx;
-    if (!chk.finish(&ctx)) return DCCN_ERR_INVALID_ARG;
-    ChainScope scope(ctx);
-    return dccn_eq_monitor_accumulate(a->chest, a->chan, a->chan_per_symbol, a->B, a->S, a->K, a->metrics, a->tx_power,
-                                      a->noise_power, a->acc5, a->rms_out, a->workspace, a->workspace_bytes, stream);
+    const auto accumulate = [&] { return eq_monitor_accumulate(*m[0], (hipStream_t)stream); };
+    return chain_group_call(
+        n_chains, m != nullptr, [&](int i) { return m[i] && eq_monitors_one_plan(m[0], m[i]); }, accumulate, group_always,
+        [&](ChainOffsetCheck& chk) { chk.fields(m, eq_monitor_pointers); return true; }, group_no_scalars, accumulate);
 }
 
 int dccn_eq_norm_rides(const dccn_eq_shape* shape) {
@@ -331,30 +340,7 @@ int dccn_eq_graph_create(const dccn_eq_shape* shape, const dccn_eq_buffers* buf,
                          dccn_stream_t stream, dccn_rx_graph** out) {
     if (!out || !eq_shape_ok(shape) || !buf) return DCCN_ERR_INVALID_ARG;
     (void)stream;
-    dccn_rx_graph* g = new dccn_rx_graph();
-    memset(g, 0, sizeof(*g));
-    if (hipStreamCreateWithFlags(&g->cap, hipStreamNonBlocking) != hipSuccess) {
-        dccn_rx_graph_destroy(g);
-        return DCCN_ERR_LAUNCH;
-    }
-    hipError_t e = hipStreamBeginCapture(g->cap, hipStreamCaptureModeRelaxed);
-    if (e != hipSuccess) {
-        dccn_rx_graph_destroy(g);
-        return hip_fail(e);
-    }
-    const int st = eq_step_impl(shape, buf, (mode & 1) != 0, hp, g->cap);
-    e = hipStreamEndCapture(g->cap, &g->graph);
-    if (st != DCCN_OK || e != hipSuccess) {
-        dccn_rx_graph_destroy(g);
-        return st != DCCN_OK ? st : hip_fail(e);
-    }
-    e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);
-    if (e != hipSuccess) {
-        dccn_rx_graph_destroy(g);
-        return hip_fail(e);
-    }
-    *out = g;
-    return DCCN_OK;
+    return graph_capture(false, out, [&](const dccn_rx_graph& g) { return eq_step_impl(shape, buf, (mode & 1) != 0, hp, g.cap); });
 }
 
 int dccn_rx_graph_launch(dccn_rx_graph* g, dccn_stream_t stream) {
@@ -452,12 +438,7 @@ int dccn_cconv2d_same_reduce(const float* dT, const float* dbias_eff, float* dw,
     return DCCN_OK;
 }
 
-// ---- per-step monitors of the equaliser harness in one launch (equalizer.h eq_monitor_kernel) --------------------
-struct EqMonitorWs { unsigned* counter; double* partial; };     // the blocks' arrival counter; one partial sum per block
-static EqMonitorWs eq_monitor_carve(Carver& c, int B, int K) {
-    unsigned* counter = c.take<unsigned>(1);
-    return EqMonitorWs{counter, c.take<double>((size_t)eq_monitor_blocks(B, K))};
-}
+// ---- per-step monitors of the equaliser harness in one launch (equalizer.h eq_monitor_kernel; eq_step.h eq_monitor_args) --------
 size_t dccn_eq_monitor_workspace_size(int B, int S, int K) {
     if (B <= 0 || S <= 0 || K <= 0) return 0;
     return carved_bytes([&](Carver& c) { eq_monitor_carve(c, B, K); });
@@ -465,20 +446,11 @@ size_t dccn_eq_monitor_workspace_size(int B, int S, int K) {
 int dccn_eq_monitor_accumulate(const float* chest, const float* chan, int chan_per_symbol, int B, int S, int K,
                                const dccn_metrics* metrics, const float* tx_power, const float* noise_power, float* acc5,
                                float* rms_out, void* workspace, size_t workspace_bytes, dccn_stream_t stream) {
-    if (!chest || !chan || B <= 0 || S <= 0 || K <= 0 || (acc5 && !metrics) || (!acc5 && !rms_out)) return DCCN_ERR_INVALID_ARG;
-    if (!workspace || workspace_bytes < dccn_eq_monitor_workspace_size(B, S, K)) return DCCN_ERR_WORKSPACE;
-    EqMonitorArgs a;
-    a.chest = chest; a.chan = chan; a.gt_per_symbol = chan_per_symbol ? 1 : 0; a.B = B; a.S = S; a.K = K;
-    a.metrics = metrics; a.tx_power = tx_power; a.noise_power = noise_power; a.acc = acc5; a.rms_out = rms_out;
-    Carver c(workspace, workspace_bytes);
-    const EqMonitorWs w = eq_monitor_carve(c, B, K);
-    a.counter = w.counter; a.partial = w.partial;
-    DCCN_LAUNCH_CHAINS_Z(eq_monitor_kernel, dim3(eq_monitor_blocks(B, K)), dim3(256), 0, (hipStream_t)stream, a);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return eq_monitor_accumulate(dccn_eq_monitor{chest, chan, chan_per_symbol, B, S, K, metrics, tx_power, noise_power, acc5, rms_out,
+                                                 workspace, workspace_bytes}, (hipStream_t)stream);
 }
 
-// ---- the equaliser's pilot bottleneck as one launch per direction (eq_bottleneck.h) ---------------------------
+// ---- the equaliser's pilot bottleneck as one launch per direction (eq_bottleneck.h; eq_step.h eq_bottleneck_*_launch) ----------
 int dccn_eq_bottleneck_supported(int B, int SK2, int P) {
     return ((P == 16 || P == 32) && B > 0 && SK2 >= 64 && (SK2 % 64) == 0) ? 1 : 0;
 }
@@ -489,12 +461,7 @@ size_t dccn_eq_bottleneck_workspace_size(int B, int SK2, int P) {
 int dccn_eq_bottleneck_fwd(const float* y, const float* W1, const float* b1, const float* W2, const float* b2, float* d1,
                            float* d2, int B, int SK2, int P, dccn_stream_t stream) {
     if (!y || !W1 || !W2 || !d1 || !d2 || !eq_bottleneck_ok(B, SK2, P, y, W1, W2) || !aligned16(d1)) return DCCN_ERR_INVALID_ARG;
-    const int q = eq_bottleneck_q(B, SK2);
-    auto kern = P == 32 ? eq_bottleneck_fwd_kernel<2> : eq_bottleneck_fwd_kernel<1>;
-    DCCN_LAUNCH_CHAINS_Z(kern, dim3(ceil_div(SK2 / 16, q), ceil_div(B, 16)), dim3(256), 0, (hipStream_t)stream, y, W1, b1, W2, b2,
-                         d1, d2, B, SK2, q);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return eq_bottleneck_fwd_launch(y, W1, b1, W2, b2, d1, d2, B, SK2, P, (hipStream_t)stream);
 }
 int dccn_eq_bottleneck_bwd(const float* dd2, const float* d1, const float* y, const float* W1, const float* W2,
                            const float* dy_in, float* dy_out, float* dW1, float* db1, float* dW2, float* db2, int B, int SK2,
@@ -504,25 +471,11 @@ int dccn_eq_bottleneck_bwd(const float* dd2, const float* d1, const float* y, co
         return DCCN_ERR_INVALID_ARG;
     if (!workspace || workspace_bytes < dccn_eq_bottleneck_workspace_size(B, SK2, P)) return DCCN_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int q = eq_bottleneck_q(B, SK2);
     const EqBnParts pt = eq_bn_parts(static_cast<float*>(workspace), B, SK2, P);
-    const int tiles = pt.tiles;
-    float *pw2 = pt.w2, *pb2 = pt.b2, *pw1 = pt.w1, *pb1 = pt.b1;
-    auto kern = P == 32 ? eq_bottleneck_bwd_kernel<2> : eq_bottleneck_bwd_kernel<1>;
-    EqRideArgs no_ride;
-    memset(&no_ride, 0, sizeof(no_ride));
-    dccn_adam_hparams no_hp;
-    memset(&no_hp, 0, sizeof(no_hp));
-    GenStaticArgs no_gen;
-    GenChainScalars no_gc;
-    memset(&no_gen, 0, sizeof(no_gen));
-    memset(&no_gc, 0, sizeof(no_gc));
-    DCCN_LAUNCH_CHAINS_Z(kern, dim3(ceil_div(SK2 / 16, q), tiles), dim3(256), 0, s, dd2, d1, y, W1, W2, dy_in, dy_out, pw2, pb2,
-                         pw1, pb1, B, SK2, q, tiles, no_ride, no_hp, 0, 0, no_gen, no_gc);
-    DCCN_LAUNCH_CHECK();
+    DCCN_TRY(eq_bottleneck_bwd_launch(dd2, d1, y, W1, W2, dy_in, dy_out, pt, B, SK2, P, eq_bn_no_riders(), s));
     // (the fused equaliser step leaves these sums to its optimizer launch)
-    DCCN_TRY(launch_splitk_reduce2(pw2, tiles, (long long)P * SK2, dW2, (long long)P * SK2, pb2, (long long)SK2, db2, (long long)SK2, s));
-    DCCN_TRY(launch_splitk_reduce2(pw1, tiles, (long long)SK2 * P, dW1, (long long)SK2 * P, pb1, (long long)P, db1, (long long)P, s));
+    DCCN_TRY(launch_splitk_reduce2(pt.w2, pt.tiles, (long long)P * SK2, dW2, (long long)P * SK2, pt.b2, (long long)SK2, db2, (long long)SK2, s));
+    DCCN_TRY(launch_splitk_reduce2(pt.w1, pt.tiles, (long long)SK2 * P, dW1, (long long)SK2 * P, pt.b1, (long long)P, db1, (long long)P, s));
     return DCCN_OK;
 }
 

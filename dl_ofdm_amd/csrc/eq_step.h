@@ -64,8 +64,38 @@ static void eq_layer_ws(const EqDims& d, size_t (&n)[EQL_COUNT]) {
     n[EQL_PAIR] = cconv_bwd_grouped_ws_bytes(d.R, d.K, d.K, 2);           // corr and eq C-Convs
     n[EQL_DENSE5] = splitk_ws_bytes(4 * d.K, 2 * d.nsc, d.R);
 }
-static void eq_carve(Carver& c, const dccn_eq_shape* sh, const EqDims& d, bool train, EqWs& w) {
-    const size_t B = d.B, R = d.R, SK2 = d.SK2, K2 = 2 * (size_t)d.K, N2 = 2 * (size_t)d.nsc;
+// The float tensors of the workspace, in carve order (the order IS the layout): name (dccn_eq_workspace_tensor; null: not offered
+// by name), member, element count for a shape, training only.  eq_carve and the lookup by name both walk this table.
+struct EqWsTensor { const char* name; float* EqWs::*member; size_t (*count)(const EqDims&); bool train; };
+static size_t eqn_rows_nsc(const EqDims& d) { return (size_t)d.R * 2 * d.nsc; }         // [B, S, n_sc, 2]
+static size_t eqn_rows_k(const EqDims& d) { return (size_t)d.R * 2 * d.K; }             // [B*S, K, 2]
+static size_t eqn_rows_2k(const EqDims& d) { return (size_t)d.R * 4 * d.K; }            // [B*S, K, 4]
+static size_t eqn_rows_f(const EqDims& d) { return (size_t)d.R * 2 * d.F; }
+static size_t eqn_frames(const EqDims& d) { return (size_t)d.B * d.SK2; }               // [B, S*K*2]
+static size_t eqn_pilots(const EqDims& d) { return (size_t)d.B * d.Pp; }
+static size_t eqn_cells(const EqDims& d) { return (size_t)d.B * 2 * d.D; }
+static size_t eqn_smooth(const EqDims& d) { return (size_t)d.SK2 * d.SK2; }
+static size_t eqn_smooth_b(const EqDims& d) { return (size_t)d.SK2; }
+static size_t eqn_tail(const EqDims&) { return (size_t)tail_param_count(4); }
+static size_t eqn_bn_part(const EqDims& d) { return (d.Pp == 16 || d.Pp == 32) ? eq_bottleneck_part_floats(d.B, d.SK2, d.Pp) : 0; }
+static const EqWsTensor kEqWsTensors[] = {
+    {"x_norm", &EqWs::x_norm, eqn_rows_nsc, false}, {"ln", &EqWs::ln, eqn_rows_nsc, false}, {"t1", &EqWs::t1, eqn_rows_k, false},
+    {"y", &EqWs::y, eqn_rows_k, false}, {"d1", &EqWs::d1, eqn_pilots, false}, {"d2", &EqWs::d2, eqn_frames, false},
+    {"d3", &EqWs::d3, eqn_frames, false}, {"d4", &EqWs::d4, eqn_frames, false}, {"T", &EqWs::T, eqn_smooth, false},
+    {"be", &EqWs::be, eqn_smooth_b, false}, {"eq", &EqWs::eq, eqn_frames, false}, {"corr", &EqWs::corr, eqn_frames, false},
+    {"eqc", &EqWs::eqc, eqn_rows_k, false}, {"corc", &EqWs::corc, eqn_rows_k, false}, {"cat", &EqWs::cat, eqn_rows_2k, false},
+    {"fft", &EqWs::fft, eqn_rows_f, false}, {"z", &EqWs::z, eqn_cells, false},
+    {"dz", &EqWs::dz, eqn_cells, true}, {"dfft", &EqWs::dfft, eqn_rows_f, true}, {"dout", &EqWs::dout, eqn_rows_nsc, true},
+    {"dcat", &EqWs::dcat, eqn_rows_2k, true}, {"deqc", &EqWs::deqc, eqn_rows_k, true}, {"dcorc", &EqWs::dcorc, eqn_rows_k, true},
+    {"deq", &EqWs::deq, eqn_frames, true}, {"dcorr", &EqWs::dcorr, eqn_frames, true}, {"dy", &EqWs::dy, eqn_frames, true},
+    {"dh", &EqWs::dh, eqn_frames, true}, {"dT", &EqWs::dT, eqn_smooth, true}, {"dbe", &EqWs::dbe, eqn_smooth_b, true},
+    {"dd4", &EqWs::dd4, eqn_frames, true}, {"dd3", &EqWs::dd3, eqn_frames, true}, {"dd2", &EqWs::dd2, eqn_frames, true},
+    {"dd1", &EqWs::dd1, eqn_pilots, true}, {"dflat", &EqWs::dflat, eqn_frames, true}, {"dt1", &EqWs::dt1, eqn_rows_k, true},
+    {nullptr, &EqWs::dtail, eqn_tail, true}, {nullptr, &EqWs::bn_part, eqn_bn_part, true},
+};
+// each(tensor, byte offset, count): called for every float tensor the workspace holds
+template <typename Each>
+static void eq_carve(Carver& c, const EqDims& d, bool train, EqWs& w, Each&& each) {
     w.n_norm = norm_ws_bytes(d.B, d.S * d.nsc * 2);
     // the layout does not depend on the modulation (the tail's slabs and gradient are sized for 16-QAM): chains of different
     // modulations carried by one launch sequence (dccn_eq_train_step_grouped) see the same offsets
@@ -79,51 +109,18 @@ static void eq_carve(Carver& c, const dccn_eq_shape* sh, const EqDims& d, bool t
     w.ws_tail = c.take<char>(w.n_tail);
     eq_layer_ws(d, w.n_l);
     for (int l = 0; l < EQL_COUNT; ++l) w.ws_l[l] = train ? c.take<char>(w.n_l[l]) : nullptr;
-    w.x_norm = c.take<float>(R * N2);
-    w.ln = c.take<float>(R * N2);
-    w.t1 = c.take<float>(R * K2);
-    w.y = c.take<float>(R * K2);
-    w.d1 = c.take<float>(B * d.Pp);
-    w.d2 = c.take<float>(B * SK2);
-    w.d3 = c.take<float>(B * SK2);
-    w.d4 = c.take<float>(B * SK2);
-    w.T = c.take<float>(SK2 * SK2);
-    w.be = c.take<float>(SK2);
-    w.eq = c.take<float>(B * SK2);
-    w.corr = c.take<float>(B * SK2);
-    w.eqc = c.take<float>(R * K2);
-    w.corc = c.take<float>(R * K2);
-    w.cat = c.take<float>(R * 2 * K2);
-    w.fft = c.take<float>(R * 2 * (size_t)d.F);
-    w.z = c.take<float>(B * 2 * (size_t)d.D);
-    if (!train) return;
-    w.dz = c.take<float>(B * 2 * (size_t)d.D);
-    w.dfft = c.take<float>(R * 2 * (size_t)d.F);
-    w.dout = c.take<float>(R * N2);
-    w.dcat = c.take<float>(R * 2 * K2);
-    w.deqc = c.take<float>(R * K2);
-    w.dcorc = c.take<float>(R * K2);
-    w.deq = c.take<float>(B * SK2);
-    w.dcorr = c.take<float>(B * SK2);
-    w.dy = c.take<float>(B * SK2);
-    w.dh = c.take<float>(B * SK2);
-    w.dT = c.take<float>(SK2 * SK2);
-    w.dbe = c.take<float>(SK2);
-    w.dd4 = c.take<float>(B * SK2);
-    w.dd3 = c.take<float>(B * SK2);
-    w.dd2 = c.take<float>(B * SK2);
-    w.dd1 = c.take<float>(B * d.Pp);
-    w.dflat = c.take<float>(B * SK2);
-    w.dt1 = c.take<float>(R * K2);
-    w.dtail = c.take<float>(tail_param_count(4));
-    w.bn_part = c.take<float>((d.Pp == 16 || d.Pp == 32) ? eq_bottleneck_part_floats(d.B, d.SK2, d.Pp) : 0);
+    for (const EqWsTensor& t : kEqWsTensors) {
+        if (t.train && !train) continue;
+        const size_t n = t.count(d);
+        w.*t.member = c.take<float>(n);
+        each(t, c.off - n * sizeof(float), n);
+    }
+}
+static void eq_carve(Carver& c, const EqDims& d, bool train, EqWs& w) {
+    eq_carve(c, d, train, w, [](const EqWsTensor&, size_t, size_t) {});
 }
 static size_t eq_ws_bytes(const dccn_eq_shape* sh, int train) {
-    const EqDims d = eq_dims(sh);
-    Carver c(nullptr, 0);
-    EqWs w;
-    eq_carve(c, sh, d, train != 0, w);
-    return align_up(c.off, 256);
+    return carved_bytes([&](Carver& c) { EqWs w; eq_carve(c, eq_dims(sh), train != 0, w); });
 }
 
 // dense backward with reduced outputs: dx (nullable: weight gradient only), dw, dbias
@@ -215,6 +212,64 @@ static EqBnParts eq_bn_parts(float* base, int B, int SK2, int P) {
     return EqBnParts{w2, b2, w1, b1, (int)t};
 }
 
+// the two launches of the pilot bottleneck: kernel by P, q, the grid and the argument order.  The backward launch can carry riders
+// (EqRideArgs jobs behind its own blocks, the next batch's generator in front of them: eq_issue_backward); the stage operators
+// pass eq_bn_no_riders()
+static int eq_bottleneck_fwd_launch(const float* y, const float* W1, const float* b1, const float* W2, const float* b2, float* d1,
+                                    float* d2, int B, int SK2, int P, hipStream_t s) {
+    auto kern = P == 32 ? eq_bottleneck_fwd_kernel<2> : eq_bottleneck_fwd_kernel<1>;
+    const int q = eq_bottleneck_q(B, SK2);
+    DCCN_LAUNCH_CHAINS_Z(kern, dim3(ceil_div(SK2 / 16, q), ceil_div(B, 16)), dim3(256), 0, s, y, W1, b1, W2, b2, d1, d2, B, SK2, q);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+struct EqBnRiders {
+    EqRideArgs ride;
+    dccn_adam_hparams hp;
+    int gen_blocks;                 // workgroups of the generator (they fill the first grid rows), 0: none
+    size_t gen_smem;
+    GenStaticArgs ga;
+    GenChainScalars gc;
+};
+static EqBnRiders eq_bn_no_riders() {
+    EqBnRiders r;
+    memset(&r, 0, sizeof(r));
+    return r;
+}
+static int eq_bottleneck_bwd_launch(const float* dd2, const float* d1, const float* y, const float* W1, const float* W2,
+                                    const float* dy_in, float* dy_out, const EqBnParts& pt, int B, int SK2, int P, const EqBnRiders& r,
+                                    hipStream_t s) {
+    auto kern = P == 32 ? eq_bottleneck_bwd_kernel<2> : eq_bottleneck_bwd_kernel<1>;
+    const int q = eq_bottleneck_q(B, SK2);
+    const int nx = ceil_div(SK2 / 16, q), gen_rows = ceil_div(r.gen_blocks, nx);
+    DCCN_LAUNCH_CHAINS_Z(kern, dim3(nx, gen_rows + pt.tiles + ceil_div(r.ride.blocks, nx)), dim3(256), r.gen_smem, s, dd2, d1, y, W1, W2,
+                         dy_in, dy_out, pt.w2, pt.b2, pt.w1, pt.b1, B, SK2, q, pt.tiles, r.ride, r.hp, gen_rows, r.gen_blocks, r.ga, r.gc);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+// the monitors' launch (equalizer.h eq_monitor_kernel): its grid, its workspace -- the blocks' arrival counter, one partial sum per
+// block -- and its argument block from the caller's descriptor, for the stand-alone launch and for the step's optimizer launch
+static int eq_monitor_blocks(int B, int K) {
+    long long n = ceil_div_ll((long long)B * K * 2, 256);
+    if (n > 256) n = 256;
+    return (int)(n < 1 ? 1 : n);
+}
+struct EqMonitorWs { unsigned* counter; double* partial; };
+static EqMonitorWs eq_monitor_carve(Carver& c, int B, int K) {
+    unsigned* counter = c.take<unsigned>(1);
+    return EqMonitorWs{counter, c.take<double>((size_t)eq_monitor_blocks(B, K))};
+}
+static EqMonitorArgs eq_monitor_args(const dccn_eq_monitor& m) {
+    EqMonitorArgs a{};
+    a.chest = m.chest; a.chan = m.chan; a.gt_per_symbol = m.chan_per_symbol ? 1 : 0; a.B = m.B; a.S = m.S; a.K = m.K;
+    a.metrics = m.metrics; a.tx_power = m.tx_power; a.noise_power = m.noise_power; a.acc = m.acc5; a.rms_out = m.rms_out;
+    Carver c(m.workspace, m.workspace_bytes);
+    const EqMonitorWs w = eq_monitor_carve(c, m.B, m.K);
+    a.counter = w.counter; a.partial = w.partial;
+    return a;
+}
+
 // Everything a step decides, decided before its first launch: eq_step_plan checks every argument and fills this, the
 // eq_issue_* functions below only read it.  A refused step has launched nothing (also inside a stream capture).
 struct EqStepPlan {
@@ -281,7 +336,7 @@ static int eq_step_plan(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
     p = EqStepPlan{};
     const EqDims& d = p.d = eq_dims(sh);
     Carver c(b->workspace, b->workspace_bytes);
-    eq_carve(c, sh, d, train, p.w);
+    eq_carve(c, d, train, p.w);
     if (!b->workspace || b->workspace_bytes < align_up(c.off, 256)) return DCCN_ERR_WORKSPACE;
     const EqWs& w = p.w;
     const float *P = b->eq_params, *Q = b->rx_params;
@@ -373,11 +428,7 @@ static int eq_step_plan(const dccn_eq_shape* sh, const dccn_eq_buffers* b, bool 
             if (!m->chan || !m->acc5 || m->chest != b->chest || m->metrics != b->metrics || m->tx_power != b->tx_power || m->B != B ||
                 m->S != d.S || m->K != d.K || !m->workspace || m->workspace_bytes < dccn_eq_monitor_workspace_size(B, d.S, d.K))
                 return DCCN_ERR_INVALID_ARG;
-            EqMonitorArgs& ma = p.mon;
-            ma.chest = m->chest; ma.chan = m->chan; ma.gt_per_symbol = m->chan_per_symbol ? 1 : 0; ma.B = B; ma.S = d.S; ma.K = d.K;
-            ma.metrics = m->metrics; ma.tx_power = m->tx_power; ma.noise_power = m->noise_power; ma.acc = m->acc5; ma.rms_out = m->rms_out;
-            ma.counter = static_cast<unsigned*>(m->workspace);
-            ma.partial = reinterpret_cast<double*>(static_cast<char*>(m->workspace) + 256);
+            p.mon = eq_monitor_args(*m);
             p.has_mon = true;
         }
     }
@@ -421,11 +472,7 @@ static int eq_issue_forward(const dccn_eq_shape* sh, const dccn_eq_buffers* b, c
     DCCN_TRY(cconv_fwd_impl(w.t1, P + d.o[2], P + d.o[3], w.y, R, K, K, s));
     // :394-426 pilot bottleneck
     if (p.bn) {                             // both layers of the bottleneck in one launch (eq_bottleneck.h)
-        auto kern = d.Pp == 32 ? eq_bottleneck_fwd_kernel<2> : eq_bottleneck_fwd_kernel<1>;
-        const int q = eq_bottleneck_q(B, SK2);
-        DCCN_LAUNCH_CHAINS_Z(kern, dim3(ceil_div(SK2 / 16, q), ceil_div(B, 16)), dim3(256), 0, s, (const float*)w.y, P + d.o[4],
-                             P + d.o[5], P + d.o[6], P + d.o[7], w.d1, w.d2, B, SK2, q);
-        DCCN_LAUNCH_CHECK();
+        DCCN_TRY(eq_bottleneck_fwd_launch(w.y, P + d.o[4], P + d.o[5], P + d.o[6], P + d.o[7], w.d1, w.d2, B, SK2, d.Pp, s));
     } else {
         DCCN_TRY(dense_fwd_impl(w.y, P + d.o[4], P + d.o[5], w.d1, B, SK2, d.Pp, s));
         DCCN_TRY(dense_fwd_impl(w.d1, P + d.o[6], P + d.o[7], w.d2, B, d.Pp, SK2, s));
@@ -595,13 +642,11 @@ static int eq_issue_backward(const dccn_eq_buffers* b, const EqStepPlan& p, dccn
     if (p.bn) {
         // both layers' backward in one launch: dd1, the branch's input gradient added to dy, per-block partials of the
         // four weight / bias gradients (summed by the optimizer launch)
-        auto kern = d.Pp == 32 ? eq_bottleneck_bwd_kernel<2> : eq_bottleneck_bwd_kernel<1>;
-        const int q = eq_bottleneck_q(B, SK2);
-        const int nx = ceil_div(SK2 / 16, q);
         // riders: the Adam updates of dense_3 / dense_4 (their gradients are complete in the arena, nothing from here to the
         // end of the step touches those kernels) stream behind this launch's own blocks instead of in the optimizer launch
-        EqRideArgs ride;
-        memset(&ride, 0, sizeof(ride));
+        EqBnRiders rd = eq_bn_no_riders();
+        EqRideArgs& ride = rd.ride;
+        rd.hp = hp;
         if (g_tune[TUNE_EQ_RIDERS]) {
             ride.p.param = b->eq_params; ride.p.grad = G; ride.p.m = b->adam_m; ride.p.v = b->adam_v;
             ride.p.reg_coef = b->reg_coef; ride.p.state = b->adam;
@@ -627,19 +672,12 @@ static int eq_issue_backward(const dccn_eq_buffers* b, const EqStepPlan& p, dccn
             }
         }
         // the NEXT batch's generator rides here as well (dccn_eq_buffers.gen_next_rides): its workgroups are the first grid rows
-        const GenChainScalars& gc = p.gsc;
-        int gen_rows = 0, gen_blocks = 0;
-        size_t gen_smem = 0;
+        rd.ga = p.ga; rd.gc = p.gsc;
         if (p.gen_rides) {
-            gen_blocks = ceil_div(p.ga.frames, kGenFramesPerBlock);
-            gen_rows = ceil_div(gen_blocks, nx);
-            gen_smem = gen_static_smem_bytes<7, 64, 16>();
+            rd.gen_blocks = ceil_div(p.ga.frames, kGenFramesPerBlock);
+            rd.gen_smem = gen_static_smem_bytes<7, 64, 16>();
         }
-        DCCN_LAUNCH_CHAINS_Z(kern, dim3(nx, gen_rows + p.bnp.tiles + ceil_div(ride.blocks, nx)), dim3(256), gen_smem, s,
-                             (const float*)w.dd2, (const float*)w.d1, (const float*)w.y, P + d.o[4], P + d.o[6], (const float*)w.dy,
-                             w.dflat, p.bnp.w2, p.bnp.b2, p.bnp.w1, p.bnp.b1, B, SK2, q, p.bnp.tiles, ride, hp, gen_rows, gen_blocks,
-                             p.ga, gc);
-        DCCN_LAUNCH_CHECK();
+        DCCN_TRY(eq_bottleneck_bwd_launch(w.dd2, w.d1, w.y, P + d.o[4], P + d.o[6], w.dy, w.dflat, p.bnp, B, SK2, d.Pp, rd, s));
         dy_sum = w.dflat;
     } else {
         DCCN_TRY(dense_bwd_full_impl(w.d1, w.dd2, P + d.o[6], w.dd1, G + d.o[6], G + d.o[7], B, d.Pp, SK2, w.ws_l[EQL_DENSE2],
