@@ -831,10 +831,17 @@ static int tail_finish(const TailFinalizeArgs& fa, TailFinalizeArgs* defer, hipS
     return DCCN_OK;
 }
 
+// the tail's own launch.  16-QAM training runs four lanes per cell (tail.h): 50 accumulators per lane, not 200
 template <int NB>
 static int tail_launch(bool bwd, const float* z, const int32_t* bits, const float* tailp, float* prob, float* dz,
-                       long long cells, int nblk, TailBlockMetrics* bm, float* bg, hipStream_t s) {
-    if (bwd)
+                       long long cells, int nblk, TailBlockMetrics* bm, float* bg, unsigned long long* stamp, hipStream_t s) {
+    if (bwd && NB == 4 && prob)
+        DCCN_LAUNCH_CHAINS_Z(demod_tail_quad4_kernel<true>, dim3(nblk), dim3(kTailThreads), 0, s, z, bits, tailp, prob, dz,
+                             cells, bm, bg, stamp);
+    else if (bwd && NB == 4)
+        DCCN_LAUNCH_CHAINS_Z(demod_tail_quad4_kernel<false>, dim3(nblk), dim3(kTailThreads), 0, s, z, bits, tailp, prob, dz,
+                             cells, bm, bg, stamp);
+    else if (bwd)
         DCCN_LAUNCH_CHAINS_Z((demod_tail_kernel<NB, true>), dim3(nblk), dim3(kTailThreads), 0, s, z, bits, tailp, prob,
                              dz, cells, bm, bg);
     else
@@ -858,23 +865,10 @@ int tail_impl(bool bwd, const float* z, const int32_t* bits, const float* tailp,
     const int nblk = tail_blocks(cells, bwd && nbits == 4);
     int st = DCCN_ERR_INVALID_ARG;
     switch (nbits) {
-        case 1: st = tail_launch<1>(bwd, z, bits, tailp, prob, dz, cells, nblk, bm, bg, s); break;
-        case 2: st = tail_launch<2>(bwd, z, bits, tailp, prob, dz, cells, nblk, bm, bg, s); break;
-        case 3: st = tail_launch<3>(bwd, z, bits, tailp, prob, dz, cells, nblk, bm, bg, s); break;
-        case 4:
-            if (bwd) {                                   // four lanes per cell (tail.h): 50 accumulators per lane, not 200
-                if (prob)
-                    DCCN_LAUNCH_CHAINS_Z(demod_tail_quad4_kernel<true>, dim3(nblk), dim3(kTailThreads), 0, s, z, bits, tailp,
-                                         prob, dz, cells, bm, bg, tl_stamp);
-                else
-                    DCCN_LAUNCH_CHAINS_Z(demod_tail_quad4_kernel<false>, dim3(nblk), dim3(kTailThreads), 0, s, z, bits,
-                                         tailp, prob, dz, cells, bm, bg, tl_stamp);
-                DCCN_LAUNCH_CHECK();
-                st = DCCN_OK;
-            } else {
-                st = tail_launch<4>(bwd, z, bits, tailp, prob, dz, cells, nblk, bm, bg, s);
-            }
-            break;
+        case 1: st = tail_launch<1>(bwd, z, bits, tailp, prob, dz, cells, nblk, bm, bg, tl_stamp, s); break;
+        case 2: st = tail_launch<2>(bwd, z, bits, tailp, prob, dz, cells, nblk, bm, bg, tl_stamp, s); break;
+        case 3: st = tail_launch<3>(bwd, z, bits, tailp, prob, dz, cells, nblk, bm, bg, tl_stamp, s); break;
+        case 4: st = tail_launch<4>(bwd, z, bits, tailp, prob, dz, cells, nblk, bm, bg, tl_stamp, s); break;
     }
     DCCN_TRY(st);
     if (!defer) DCCN_NO_CHAINS();

@@ -3,10 +3,10 @@
 // no workspace.  Per data cell: z = (I, Q) of the dense output -> the NB bit pairs' probabilities (`output:0`, nullable),
 // llr = u1 - u0 of the two post-leaky-ReLU logits (= log(p1 / p0), nullable) and the NB hard bits, packed MSB first.
 //
-// The arithmetic is tail.h tail_cells' forward, expression for expression (fused multiply-add chains with the bias as the
-// start value, `big`, exp_nonpos, rcp_fast, p1 > p0), so a decision here is bit for bit the decision the evaluation step
-// tallies.  Consequence: where u1 - u0 is positive but so small that exp rounds to 1, p1 == p0 and the bit is 0 (argmax takes
-// the first index on ties) although llr > 0.
+// The arithmetic is tail.h's own: tail_fwd_logits to the logits and tail_softmax over each bit pair, the functions the
+// evaluation step (tail_cells_out) calls, and the same p1 > p0 -- so a decision here is bit for bit the decision the evaluation
+// step tallies.  Consequence: where u1 - u0 is positive but so small that exp rounds to 1, p1 == p0 and the bit is 0 (argmax
+// takes the first index on ties) although llr > 0.
 //
 // Packed layout: row f of `packed` [frames, ceil(D * NB / 8)] is numpy.packbits(hard[f].reshape(-1)) -- bit (d, j) of the
 // frame sits at bit position d * NB + j, most significant bit of a byte first, padding bits of the last byte 0.  Eight
@@ -48,35 +48,11 @@ template <int NB, int W>
 __device__ __forceinline__ void decide_cells(const float (&z0)[W], const float (&z1)[W], const float* __restrict__ sw,
                                              float* const (&prob_cell)[W], float* const (&llr_cell)[W],
                                              unsigned (&hard)[W]) {
-    constexpr int M = 1 << NB;
-    constexpr int O = 2 * NB;
-    constexpr int oW1 = 0, oB1 = 2 * M, oW2 = 3 * M, oB2 = 3 * M + (M + 2) * O;
-    float c[M + 2][W];
+    using L = TailLayout<NB>;
+    float c[L::M + 2][W], pre1[L::M][W], pre2[L::O][W];
+    tail_fwd_logits<NB, W>(z0, z1, sw, c, pre1, pre2);          // (pre1 is the backward's: not read here)
 #pragma unroll
-    for (int j = 0; j < M; ++j) {
-#pragma unroll
-        for (int u = 0; u < W; ++u)
-            c[j][u] = leaky_relu(__builtin_fmaf(z1[u], sw[oW1 + M + j], __builtin_fmaf(z0[u], sw[oW1 + j], sw[oB1 + j])));
-    }
-#pragma unroll
-    for (int u = 0; u < W; ++u) {
-        c[M][u] = z0[u];
-        c[M + 1][u] = z1[u];
-        hard[u] = 0u;
-    }
-    float pre2[O][W];
-#pragma unroll
-    for (int o = 0; o < O; ++o) {
-        float s[W];
-#pragma unroll
-        for (int u = 0; u < W; ++u) s[u] = sw[oB2 + o];
-#pragma unroll
-        for (int i = 0; i < M + 2; ++i)
-#pragma unroll
-            for (int u = 0; u < W; ++u) s[u] = __builtin_fmaf(c[i][u], sw[oW2 + i * O + o], s[u]);
-#pragma unroll
-        for (int u = 0; u < W; ++u) pre2[o][u] = s[u];
-    }
+    for (int u = 0; u < W; ++u) hard[u] = 0u;
     float lv[W][NB];
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
@@ -84,12 +60,9 @@ __device__ __forceinline__ void decide_cells(const float (&z0)[W], const float (
 #pragma unroll
         for (int u = 0; u < W; ++u) {
             const float u0 = leaky_relu(pre2[2 * j][u]), u1 = leaky_relu(pre2[2 * j + 1][u]);
-            const bool big = u1 > u0;
-            const float eo = exp_nonpos(-fabsf(u0 - u1));
-            const float e0 = big ? eo : 1.0f, e1 = big ? 1.0f : eo;
-            const float res = rcp_fast(e0 + e1);
-            p0[u] = e0 * res;
-            p1[u] = e1 * res;
+            const float2 p = tail_softmax(u0, u1);
+            p0[u] = p.x;
+            p1[u] = p.y;
             lv[u][j] = u1 - u0;
         }
 #pragma unroll
@@ -140,15 +113,7 @@ __global__ __launch_bounds__(kDecideThreads) void demod_decide_kernel(
     unsigned char* __restrict__ packed = chain_at(packed0, coff);
     float* __restrict__ llr = chain_at(llr0, coff);
     float* __restrict__ prob = chain_at(prob0, coff);
-    constexpr int P = tail_param_count(NB);
-    // nbits >= 3: 90 / 200 weights do not fit the SGPR file: staged in LDS, re-read as broadcast loads (as tail.h does)
-    constexpr bool LDSW = NB >= 3;
-    __shared__ float swl[LDSW ? P : 1];
-    if constexpr (LDSW) {
-        for (int i = threadIdx.x; i < P; i += kDecideThreads) swl[i] = tailp[i];
-        __syncthreads();
-    }
-    const float* __restrict__ sw = LDSW ? swl : tailp;
+    const float* __restrict__ sw = tail_stage_weights<NB, kDecideThreads>(tailp);
     const long long t = (long long)blockIdx.x * kDecideThreads + threadIdx.x;
     const long long g = t >> 3;
     const int ci = (int)(t & 7);

@@ -18,7 +18,7 @@
 // Inside a 16-deep group the MFMA with float4 component j multiplies k = {j, 4+j, 8+j, 12+j} (same permutation on A
 // and B, so the sum is unchanged).
 //
-// EPI_TAIL: the dense forward's epilogue runs the demodulation tail (R3-R6 forward and backward, tail.h tail_cell) on
+// EPI_TAIL: the dense forward's epilogue runs the demodulation tail (R3-R6 forward and backward, tail.h tail_cells_out) on
 // the output tile while it is in registers -- adjacent lanes hold the I and Q column of one data cell -- and writes
 // dz / prob / the per-block metric and gradient slabs instead of (or besides) z.
 // EPI_DECIDE (receive path, BPSK / QPSK): the same register layout, but only the forward of the tail and the hard decision
@@ -212,12 +212,12 @@ struct TailLds16 {
     static_assert(!STAGED || CF::xchg_bytes == 0, "LDS-staged tail: one wave set");
     static constexpr int ZS = CF::BN + 2;                 // row stride of the staged tile (even: float2 reads)
     static constexpr int TCELLS = CF::BM * (CF::BN / 2);
-    static constexpr int PW = tail_param_count(NB);
+    static constexpr int PW = TailLayout<NB>::P;
     static constexpr int zt = 0;                          // [BM][ZS]
     static constexpr int lt = CF::BM * ZS;                // [TCELLS] packed label bits (ints)
     static constexpr int swl = lt + TCELLS;               // [PW] tail weights (90 / 200 do not fit the SGPR file)
     static constexpr int red = STAGED ? swl + ((PW + 3) & ~3) : (int)(CF::xchg_bytes / sizeof(float));
-    static constexpr int red_floats = QUAD4 ? tail_quad4_lds_floats(CF::NT) : tail_reduce_lds_floats<NB, BWD>(CF::NT);
+    static constexpr int red_floats = tail_reduce_lds_floats<NB, BWD>(CF::NT);      // both forms (tail.h)
     static constexpr size_t bytes = CF::smem_bytes((STAGED ? red : 0) + red_floats);
 };
 

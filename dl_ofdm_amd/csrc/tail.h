@@ -19,9 +19,21 @@ constexpr int kTailBlocksMax = 512;   // slab capacity of the workspace / finali
 constexpr int kTailBlocks = 256;      // one block per CU (two per CU measured no better for nbits<=2 and worse for nbits>=3: 256 VGPRs)
 constexpr int kTailThreads = 256;
 
-__host__ __device__ constexpr int tail_param_count(int nb) {
-    return 2 * (1 << nb) + (1 << nb) + ((1 << nb) + 2) * 2 * nb + 2 * nb;
+// The tail's weights in the parameter arena, stated ONCE: the 1x1 conv W1 [2][M] and its bias [M] (M = 2^nb hidden units), then
+// dense_1 W2 [M + 2][O] over the concatenation (hidden units, I, Q) and its bias [O] (O = 2 nb logits, a pair per bit).
+struct TailOffsets { int M, O, oW1, oB1, oW2, oB2, P; };
+__host__ __device__ constexpr TailOffsets tail_offsets(int nb) {
+    const int M = 1 << nb, O = 2 * nb;
+    const int oW1 = 0, oB1 = oW1 + 2 * M, oW2 = oB1 + M, oB2 = oW2 + (M + 2) * O;
+    return TailOffsets{M, O, oW1, oB1, oW2, oB2, oB2 + O};
 }
+template <int NB>
+struct TailLayout {
+    static constexpr int M = tail_offsets(NB).M, O = tail_offsets(NB).O, P = tail_offsets(NB).P;
+    static constexpr int oW1 = tail_offsets(NB).oW1, oB1 = tail_offsets(NB).oB1, oW2 = tail_offsets(NB).oW2, oB2 = tail_offsets(NB).oB2;
+};
+__host__ __device__ constexpr int tail_param_count(int nb) { return tail_offsets(nb).P; }
+static_assert(TailLayout<1>::P == 16 && TailLayout<2>::P == 40 && TailLayout<3>::P == 90 && TailLayout<4>::P == 200, "tail weights");
 
 __device__ __forceinline__ float leaky_relu(float x) { return fmaxf(kLeaky * x, x); }
 
@@ -34,6 +46,32 @@ __device__ __forceinline__ float leaky_relu(float x) { return fmaxf(kLeaky * x, 
 __device__ __forceinline__ float exp_nonpos(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 __device__ __forceinline__ float log_1_2(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994530942f; }
 __device__ __forceinline__ float rcp_fast(float x) { return __builtin_amdgcn_rcpf(x); }
+
+// ---- arithmetic of one bit pair that has ONE statement (profiles/tail_once.md lists the sites that repeat a piece, and why) ----
+// First softmax: (p0, p1) of the two post-leaky-ReLU logits of a bit.  exp(u - max) is exactly 1 for the larger logit, so one exp
+// suffices (bit-identical to evaluating both); the smaller logit minus the larger one is -|u0 - u1| (abs / neg are free source
+// modifiers).  tail_quad4_cell selects between u0 - u1 and u1 - u0 instead: the same float for every non-NaN input (a +-0
+// argument gives exp = 1 either way).  Called by tail_cells_out and decide.h decide_cells.
+__device__ __forceinline__ float2 tail_softmax(const float u0, const float u1) {
+    const bool big = u1 > u0;
+    const float eo = exp_nonpos(-fabsf(u0 - u1));
+    const float e0 = big ? eo : 1.0f, e1 = big ? 1.0f : eo;
+    const float res = rcp_fast(e0 + e1);
+    return make_float2(e0 * res, e1 * res);
+}
+// Backward of one bit, from the second softmax's f0 / f1 / fs = f0 + f1 and the loss scale inv_eff to its two pre-activation
+// logits pre20 / pre21.  Called by tail_cells_out and tail_quad4_cell.  (label is a bool the CALLER compares: with the int
+// compared in here, the quad-lane kernels came out with other instructions.)
+__device__ __forceinline__ float2 tail_bit_bwd(const float f0, const float f1, const float fs, const float p0, const float p1,
+                                               const bool label, const float inv_eff, const float pre20, const float pre21) {
+    const float rfs = rcp_fast(fs);
+    const float q0 = f0 * rfs, q1 = f1 * rfs;
+    const float g0 = (q0 - (label ? 0.f : 1.f)) * inv_eff;
+    const float g1 = (q1 - (label ? 1.f : 0.f)) * inv_eff;
+    const float dot = g0 * p0 + g1 * p1;
+    const float du0 = p0 * (g0 - dot), du1 = p1 * (g1 - dot);
+    return make_float2(du0 * (pre20 > 0.f ? 1.f : kLeaky), du1 * (pre21 > 0.f ? 1.f : kLeaky));
+}
 
 struct TailBlockMetrics {      // one per block in the workspace
     double ce_sum;
@@ -60,7 +98,7 @@ __device__ __forceinline__ TailCellIn<NB> tail_load_cell(const float* __restrict
 // Per-lane running sums of the tail: weight gradients (training), CE sum, confusion tallies.
 template <int NB, bool BWD>
 struct TailLaneAcc {
-    static constexpr int P = tail_param_count(NB);
+    static constexpr int P = TailLayout<NB>::P;
     float g[BWD ? P : 1];
     double ce;
     int c00, c01, c10, c11;
@@ -91,6 +129,43 @@ struct TailOutPtrs {
     __device__ __forceinline__ void dz(const int u, const float d0, const float d1) const { dzv[u] = make_float2(d0, d1); }
 };
 
+// Forward of W cells to the logits: the 1x1 conv (pre1, before its leaky ReLU), the concatenation c = (hidden units, I, Q) and
+// dense_1 (pre2, before its leaky ReLU).  Both small matrix products are fused multiply-add chains with the bias as the chain's
+// start value (36 VALU instructions fewer per QPSK cell).  The ONE forward of the lane-per-cell training / evaluation form and
+// of the decision stage (which does not read pre1); tail_quad4_cell splits the conv over a quad's lanes and evaluates the same
+// expressions per hidden unit and per logit.
+template <int NB, int W>
+__device__ __forceinline__ void tail_fwd_logits(const float (&z0)[W], const float (&z1)[W], const float* __restrict__ sw,
+                                                float (&c)[TailLayout<NB>::M + 2][W], float (&pre1)[TailLayout<NB>::M][W],
+                                                float (&pre2)[TailLayout<NB>::O][W]) {
+    using L = TailLayout<NB>;
+#pragma unroll
+    for (int j = 0; j < L::M; ++j) {
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+            pre1[j][u] = __builtin_fmaf(z1[u], sw[L::oW1 + L::M + j], __builtin_fmaf(z0[u], sw[L::oW1 + j], sw[L::oB1 + j]));
+            c[j][u] = leaky_relu(pre1[j][u]);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < W; ++u) {
+        c[L::M][u] = z0[u];
+        c[L::M + 1][u] = z1[u];
+    }
+#pragma unroll
+    for (int o = 0; o < L::O; ++o) {
+        float s[W];
+#pragma unroll
+        for (int u = 0; u < W; ++u) s[u] = sw[L::oB2 + o];
+#pragma unroll
+        for (int i = 0; i < L::M + 2; ++i)
+#pragma unroll
+            for (int u = 0; u < W; ++u) s[u] = __builtin_fmaf(c[i][u], sw[L::oW2 + i * L::O + o], s[u]);
+#pragma unroll
+        for (int u = 0; u < W; ++u) pre2[o][u] = s[u];
+    }
+}
+
 // W data cells through R3-R6 (and back) in one instruction stream: z = (I,Q) of the dense output, lab = the NB label
 // bits, sw = tail weights (uniform address: scalar loads for NB <= 2, an LDS copy for NB >= 3).  Every statement is
 // written for all W cells AND all NB bits before the next one, so the NB * W independent dependency chains (exp -> rcp ->
@@ -100,67 +175,24 @@ struct TailOutPtrs {
 // order, so any W gives the same bits.
 // valid[u] == false: the cell contributes nothing to the sums (its dz is 0).  ALLV: the caller guarantees every cell valid
 // (`valid` is not read): no inv_count / ce selects, no masks in the tallies.
-// Shared by demod_tail_kernel and the fused dense-forward epilogue (gemm16.h).
+// Shared by demod_tail_kernel, the fused dense-forward epilogue (gemm16.h) and the few-row tiles (fewrow.h).
 template <int NB, bool BWD, int W, bool ALLV, typename Out>
 __device__ __forceinline__ void tail_cells_out(const float (&z0)[W], const float (&z1)[W], const int (&lab)[W][NB],
                                                const bool (&valid)[W], const float* __restrict__ sw, const float inv_count,
                                                TailLaneAcc<NB, BWD>& A, const Out& out) {
-    constexpr int M = 1 << NB;
-    constexpr int O = 2 * NB;
-    constexpr int oW1 = 0, oB1 = 2 * M, oW2 = 3 * M, oB2 = 3 * M + (M + 2) * O;
+    using L = TailLayout<NB>;
+    constexpr int M = L::M, O = L::O, oW1 = L::oW1, oB1 = L::oB1, oW2 = L::oW2, oB2 = L::oB2;
     static_assert(NB * W < 256, "packed tallies: 8-bit fields");
-    // the two small matrix products of the forward are fused multiply-adds with the bias as the chain's start value
-    // (36 VALU instructions fewer per QPSK cell); demod_tail_quad4_kernel evaluates the same expressions, so training
-    // and evaluation produce identical probabilities for every modulation
-    constexpr bool FMA_FWD = true;
-    float c[M + 2][W], pre1[M][W];
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-#pragma unroll
-        for (int u = 0; u < W; ++u) {
-            if constexpr (FMA_FWD)
-                pre1[j][u] = __builtin_fmaf(z1[u], sw[oW1 + M + j], __builtin_fmaf(z0[u], sw[oW1 + j], sw[oB1 + j]));
-            else
-                pre1[j][u] = (z0[u] * sw[oW1 + j] + z1[u] * sw[oW1 + M + j]) + sw[oB1 + j];
-            c[j][u] = leaky_relu(pre1[j][u]);
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < W; ++u) {
-        c[M][u] = z0[u];
-        c[M + 1][u] = z1[u];
-    }
-    float pre2[O][W];
-#pragma unroll
-    for (int o = 0; o < O; ++o) {
-        float s[W];
-#pragma unroll
-        for (int u = 0; u < W; ++u) s[u] = FMA_FWD ? sw[oB2 + o] : 0.f;
-#pragma unroll
-        for (int i = 0; i < M + 2; ++i)
-#pragma unroll
-            for (int u = 0; u < W; ++u) {
-                if constexpr (FMA_FWD) s[u] = __builtin_fmaf(c[i][u], sw[oW2 + i * O + o], s[u]);
-                else s[u] += c[i][u] * sw[oW2 + i * O + o];
-            }
-#pragma unroll
-        for (int u = 0; u < W; ++u) pre2[o][u] = FMA_FWD ? s[u] : s[u] + sw[oB2 + o];
-    }
+    float c[M + 2][W], pre1[M][W], pre2[O][W];
+    tail_fwd_logits<NB, W>(z0, z1, sw, c, pre1, pre2);
     float p0[NB][W], p1[NB][W];
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
 #pragma unroll
         for (int u = 0; u < W; ++u) {
-            const float u0 = leaky_relu(pre2[2 * j][u]), u1 = leaky_relu(pre2[2 * j + 1][u]);
-            // softmax over the pair: exp(u - max) is exactly 1 for the larger logit, so one expf suffices
-            // (bit-identical to evaluating both); likewise for the second softmax on the probabilities
-            // (the smaller logit minus the larger one is -|u0 - u1| either way: abs/neg are free source modifiers)
-            const bool big = u1 > u0;
-            const float eo = exp_nonpos(-fabsf(u0 - u1));
-            const float e0 = big ? eo : 1.0f, e1 = big ? 1.0f : eo;
-            const float res = rcp_fast(e0 + e1);
-            p0[j][u] = e0 * res;
-            p1[j][u] = e1 * res;
+            const float2 p = tail_softmax(leaky_relu(pre2[2 * j][u]), leaky_relu(pre2[2 * j + 1][u]));
+            p0[j][u] = p.x;
+            p1[j][u] = p.y;
         }
     }
     if (out.any_prob()) {
@@ -177,7 +209,8 @@ __device__ __forceinline__ void tail_cells_out(const float (&z0)[W], const float
 #pragma unroll
         for (int u = 0; u < W; ++u) {
             const int label = lab[u][j];
-            // second softmax on the probabilities (softmax_cross_entropy_with_logits_v2)
+            // second softmax on the probabilities (softmax_cross_entropy_with_logits_v2) and the cross entropy; tail_quad4_cell
+            // repeats these statements (as a function of their own they reorder every kernel that runs this one)
             const bool p1_big = p1[j][u] > p0[j][u];         // also the decision: argmax, first index on ties
             const float mx2 = p1_big ? p1[j][u] : p0[j][u];
             const float fo = exp_nonpos(-fabsf(p0[j][u] - p1[j][u]));
@@ -213,14 +246,10 @@ __device__ __forceinline__ void tail_cells_out(const float (&z0)[W], const float
             for (int u = 0; u < W; ++u) {
                 const int label = lab[u][j];
                 const float inv_eff = ALLV ? inv_count : (valid[u] ? inv_count : 0.f);
-                const float rfs = rcp_fast(fs[j][u]);
-                const float q0 = f0[j][u] * rfs, q1 = f1[j][u] * rfs;
-                const float g0 = (q0 - (label ? 0.f : 1.f)) * inv_eff;
-                const float g1 = (q1 - (label ? 1.f : 0.f)) * inv_eff;
-                const float dot = g0 * p0[j][u] + g1 * p1[j][u];
-                const float du0 = p0[j][u] * (g0 - dot), du1 = p1[j][u] * (g1 - dot);
-                dpre2[2 * j][u] = du0 * (pre2[2 * j][u] > 0.f ? 1.f : kLeaky);
-                dpre2[2 * j + 1][u] = du1 * (pre2[2 * j + 1][u] > 0.f ? 1.f : kLeaky);
+                const float2 d = tail_bit_bwd(f0[j][u], f1[j][u], fs[j][u], p0[j][u], p1[j][u], label != 0, inv_eff,
+                                              pre2[2 * j][u], pre2[2 * j + 1][u]);
+                dpre2[2 * j][u] = d.x;
+                dpre2[2 * j + 1][u] = d.y;
             }
         }
         float dc[M + 2][W];
@@ -231,8 +260,7 @@ __device__ __forceinline__ void tail_cells_out(const float (&z0)[W], const float
             for (int u = 0; u < W; ++u) s[u] = 0.f;
 #pragma unroll
             for (int o = 0; o < O; ++o) {
-                // backward-only sums use fused multiply-adds (one rounding, half the VALU instructions); the
-                // forward stays unfused so that training and evaluation produce identical probabilities
+                // the backward's sums are fused multiply-adds too (one rounding, half the VALU instructions)
 #pragma unroll
                 for (int u = 0; u < W; ++u) {
                     A.g[oW2 + i * O + o] = __builtin_fmaf(c[i][u], dpre2[o][u], A.g[oW2 + i * O + o]);
@@ -277,41 +305,32 @@ __device__ __forceinline__ void tail_cells(const float (&z0)[W], const float (&z
     tail_cells_out<NB, BWD, W, false>(z0, z1, lab, valid, sw, inv_count, A, out);
 }
 
-// one cell (W = 1)
-template <int NB, bool BWD>
-__device__ __forceinline__ float2 tail_cell(const float z0, const float z1, const int (&lab)[NB],
-                                            const float* __restrict__ sw, const float inv_count,
-                                            float* __restrict__ prob_cell, TailLaneAcc<NB, BWD>& A) {
-    const float a0[1] = {z0}, a1[1] = {z1};
-    int l[1][NB];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) l[0][j] = lab[j];
-    const bool v[1] = {true};
-    float* const pc[1] = {prob_cell};
-    float2 d[1];
-    tail_cells<NB, BWD, 1>(a0, a1, l, v, sw, inv_count, pc, A, d);
-    return d[0];
+// lane k of every quad to all four lanes / the sum over a quad's four lanes in all of them (DPP crossbar)
+template <int K>
+__device__ __forceinline__ float quad_bcast(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), K * 0x55, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float quad_sum(float v) {
+    v += __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, v), 0));
+    v += __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, v), 1));
+    return v;
 }
 
-// LDS the block reduction of the lane accumulators needs (floats), for NT threads
+// ---- block reduction of the lane accumulators: DPP within the wave, LDS across the waves, fixed order (deterministic); writes
+// the block's slab.  Three parts, the same for the lane-per-cell form (tail_block_reduce) and the quad-lane form
+// (tail_quad4_block_reduce); only the way a lane's gradient sums reach the LDS matrix in between differs.  Parts 1 and 2 are
+// functions; part 3 and the three-line carve of `lds` stand written out in both reducers (as functions they changed the
+// instructions of training kernels).
+// LDS (floats) for NT threads: per-wave ce (double) and conf (4 ints), then -- training -- smat [NT / 4][P | 1], a row per quad
+// (odd row stride: column reads spread over the banks).  The ONE size for both forms (the quad form is <4, true>).
+constexpr int tail_reduce_head_floats(int nt) { return (nt / 64) * 2 + (nt / 64) * 4 + 2; }
 template <int NB, bool BWD>
 constexpr int tail_reduce_lds_floats(int nt) {
-    // smat [nt/4][P|1] floats + per-wave ce (double) + per-wave conf (4 ints)
-    return (BWD ? (nt / 4) * (tail_param_count(NB) | 1) : 0) + (nt / 64) * 2 + (nt / 64) * 4 + 2;
+    return (BWD ? (nt / 4) * (TailLayout<NB>::P | 1) : 0) + tail_reduce_head_floats(nt);
 }
-
-// Block reduction: DPP within the wave, LDS across the waves, fixed order (deterministic); writes the block's slab.
-// lds must hold tail_reduce_lds_floats<NB,BWD>(NT) floats, 8-byte aligned.  Starts and ends with barriers of its own.
-template <int NB, bool BWD, int NT>
-__device__ __forceinline__ void tail_block_reduce(TailLaneAcc<NB, BWD>& A, float* __restrict__ lds,
-                                                  TailBlockMetrics* __restrict__ blk_metrics,
-                                                  float* __restrict__ blk_grads, const int slab) {
-    constexpr int P = tail_param_count(NB);
-    constexpr int PS = P | 1;                                  // odd row stride: column reads spread over the banks
-    constexpr int NW = NT / 64, NQ = NT / 4;
-    double* sce = reinterpret_cast<double*>(lds);              // [NW]
-    int* sconf = reinterpret_cast<int*>(lds + 2 * NW);         // [NW][4]
-    float* smat = lds + 2 * NW + 4 * NW + 2;                   // [NQ][PS] partial gradient sums
+// part 1: wave sums of ce / confusion, parked by lane 0
+template <class Acc>
+__device__ __forceinline__ void tail_park_wave_sums(const Acc& A, double* sce, int* sconf) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const double ce = wave_sum(A.ce);
     const int c00 = wave_sum(A.c00), c01 = wave_sum(A.c01), c10 = wave_sum(A.c10), c11 = wave_sum(A.c11);
@@ -319,28 +338,16 @@ __device__ __forceinline__ void tail_block_reduce(TailLaneAcc<NB, BWD>& A, float
         sce[wid] = ce;
         sconf[wid * 4 + 0] = c00; sconf[wid * 4 + 1] = c01; sconf[wid * 4 + 2] = c10; sconf[wid * 4 + 3] = c11;
     }
-    if constexpr (BWD) {
-        // gradients: sum over the 4 lanes of a quad on the DPP crossbar (2 adds per value instead of a full wave
-        // reduction per value), park the quad sums per parameter in LDS ...
-        // (the stores stand in ONE exec-mask region behind the sums: written inside the loop above, each of the P conditional
-        // stores was its own s_and_saveexec / s_or pair -- 92 of them for 8-QAM)
-        const int quad = threadIdx.x >> 2;
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-            float v = A.g[i];
-            v += __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, v), 0));
-            v += __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, v), 1));
-            A.g[i] = v;
-        }
-        if ((lane & 3) == 0) {
-#pragma unroll
-            for (int i = 0; i < P; ++i) smat[quad * PS + i] = A.g[i];
-        }
-    }
-    __syncthreads();
+}
+// part 2 (behind the barrier): thread 0 adds the waves' sums, ce in fours as (0+1)+(2+3), and writes the block's record.
+// FROM_ZERO: the fours are added onto 0.0 even when there is one four -- one instruction more, the same double (a sum that
+// started at +0.0 is never -0.0).  The quad form has always done so, the lane form only for more than four waves.
+template <int NW, bool FROM_ZERO>
+__device__ __forceinline__ void tail_block_totals(const double* sce, const int* sconf, TailBlockMetrics* __restrict__ blk_metrics,
+                                                  const int slab) {
     if (threadIdx.x == 0) {
         TailBlockMetrics bm;
-        if constexpr (NW == 4) {
+        if constexpr (NW == 4 && !FROM_ZERO) {
             bm.ce_sum = (sce[0] + sce[1]) + (sce[2] + sce[3]);
         } else {
             double t = 0.0;
@@ -354,8 +361,38 @@ __device__ __forceinline__ void tail_block_reduce(TailLaneAcc<NB, BWD>& A, float
         }
         blk_metrics[slab] = bm;
     }
+}
+
+// The lane-per-cell form.  lds must hold tail_reduce_lds_floats<NB,BWD>(NT) floats, 8-byte aligned.  Barriers: none in front
+// (the caller must have finished with `lds`), one between parking and summing, none behind.
+template <int NB, bool BWD, int NT>
+__device__ __forceinline__ void tail_block_reduce(TailLaneAcc<NB, BWD>& A, float* __restrict__ lds,
+                                                  TailBlockMetrics* __restrict__ blk_metrics,
+                                                  float* __restrict__ blk_grads, const int slab) {
+    constexpr int P = TailLayout<NB>::P, PS = P | 1, NQ = NT / 4;
+    double* sce = reinterpret_cast<double*>(lds);                      // [NT / 64]
+    int* sconf = reinterpret_cast<int*>(lds + 2 * (NT / 64));          // [NT / 64][4]
+    float* smat = lds + tail_reduce_head_floats(NT);                   // [NQ][PS] partial gradient sums
+    const int lane = threadIdx.x & 63;
+    tail_park_wave_sums(A, sce, sconf);
     if constexpr (BWD) {
-        // ... then 4 threads per parameter column add NQ/4 quad sums each (fixed order) and combine on the crossbar
+        // gradients: sum over the 4 lanes of a quad on the DPP crossbar (2 adds per value instead of a full wave
+        // reduction per value), park the quad sums per parameter in LDS
+        // (the stores stand in ONE exec-mask region behind the sums: written inside the loop above, each of the P conditional
+        // stores was its own s_and_saveexec / s_or pair -- 92 of them for 8-QAM)
+        const int quad = threadIdx.x >> 2;
+#pragma unroll
+        for (int i = 0; i < P; ++i) A.g[i] = quad_sum(A.g[i]);
+        if ((lane & 3) == 0) {
+#pragma unroll
+            for (int i = 0; i < P; ++i) smat[quad * PS + i] = A.g[i];
+        }
+    }
+    __syncthreads();
+    tail_block_totals<NT / 64, false>(sce, sconf, blk_metrics, slab);
+    if constexpr (BWD) {
+        // part 3: 4 threads per parameter column add NQ / 4 rows of smat each (fixed order) and combine on the crossbar
+        // (the same statements close tail_quad4_block_reduce)
         const int slot = threadIdx.x >> 2, part = threadIdx.x & 3;
         for (int col0 = 0; col0 < P; col0 += NQ) {
             const int col = col0 + slot;
@@ -363,10 +400,24 @@ __device__ __forceinline__ void tail_block_reduce(TailLaneAcc<NB, BWD>& A, float
             float v = 0.f;
 #pragma unroll
             for (int r = 0; r < NQ / 4; ++r) v += smat[(part * (NQ / 4) + r) * PS + cc];
-            v += __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, v), 0));
-            v += __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, v), 1));
+            v = quad_sum(v);
             if (part == 0 && col < P) blk_grads[(size_t)slab * P + col] = v;
         }
+    }
+}
+
+// One LDS staging of the tail weights for the stand-alone kernels (NT threads): nbits <= 2: the <= 40 weights are read through
+// uniform addresses -> scalar (SGPR) loads.  nbits >= 3: 90 / 200 weights do not fit the SGPR file (the compiler spilled hundreds
+// of them into VGPR lanes); they are staged in LDS once and re-read each cell as broadcast loads.  Returns where to read them.
+template <int NB, int NT>
+__device__ __forceinline__ const float* tail_stage_weights(const float* __restrict__ tailp) {
+    if constexpr (NB >= 3) {
+        __shared__ float swl[TailLayout<NB>::P];
+        for (int i = threadIdx.x; i < TailLayout<NB>::P; i += NT) swl[i] = tailp[i];
+        __syncthreads();
+        return swl;
+    } else {
+        return tailp;
     }
 }
 
@@ -382,20 +433,8 @@ __global__ __launch_bounds__(kTailThreads) void demod_tail_kernel(
     float* __restrict__ dz = chain_at(dz_, coff);
     TailBlockMetrics* __restrict__ blk_metrics = chain_at(blk_metrics_, coff);
     float* __restrict__ blk_grads = chain_at(blk_grads_, coff);
-    constexpr int P = tail_param_count(NB);
     __shared__ __attribute__((aligned(8))) float sred[tail_reduce_lds_floats<NB, BWD>(kTailThreads)];
-
-    // nbits <= 2: the <= 40 weights are read through uniform addresses -> scalar (SGPR) loads.  nbits >= 3: 90 / 200
-    // weights do not fit the SGPR file (the compiler spilled hundreds of them into VGPR lanes); they are staged in
-    // LDS once and re-read each cell as broadcast loads (the per-iteration compiler barrier keeps them from being
-    // hoisted into 200 live VGPRs).
-    constexpr bool LDSW = NB >= 3;
-    __shared__ float swl[LDSW ? P : 1];
-    if constexpr (LDSW) {
-        for (int i = threadIdx.x; i < P; i += kTailThreads) swl[i] = tailp[i];
-        __syncthreads();
-    }
-    const float* __restrict__ sw = LDSW ? swl : tailp;
+    const float* __restrict__ sw = tail_stage_weights<NB, kTailThreads>(tailp);
 
     TailLaneAcc<NB, BWD> A;
     A.clear();
@@ -409,7 +448,7 @@ __global__ __launch_bounds__(kTailThreads) void demod_tail_kernel(
 #pragma unroll
     for (int u = 0; u < W; ++u) cur[u] = tail_load_cell<NB>(z, bits, cell + u * stride, cells);
     while (cell < cells) {
-        if constexpr (LDSW) asm volatile("" ::: "memory");
+        if constexpr (NB >= 3) asm volatile("" ::: "memory");      // keeps the LDS weights from being hoisted into 200 live VGPRs
         TailCellIn<NB> nxt[W];
 #pragma unroll
         for (int u = 0; u < W; ++u) nxt[u] = tail_load_cell<NB>(z, bits, cell + (W + u) * stride, cells);     // prefetch
@@ -446,12 +485,12 @@ __global__ __launch_bounds__(kTailThreads) void demod_tail_kernel(
 // a quad owns bit q of the cell: the two logits (2q, 2q+1), their softmax / cross-entropy / decision, the matching
 // two columns of the dense_1 gradient (36 + 2 accumulators) and hidden units 4q..4q+3 of the 1x1-conv gradient (12):
 // 50 accumulators per lane.  What a lane does not own it gets from its quad on the DPP crossbar (the backward into
-// the 18 concatenated features and the two dz sums).  The forward uses the same operations in the same order as
-// demod_tail_kernel, so training and evaluation probabilities stay bit-identical.
+// the 18 concatenated features and the two dz sums).  The forward evaluates tail_fwd_logits' expressions per hidden unit and
+// per logit, in the same order, so training and evaluation probabilities stay bit-identical.
 // Shared by demod_tail_quad4_kernel (z from memory) and the fused dense-forward epilogue (gemm16.h: z from the
 // accumulators of the quad's lanes).
 struct TailQuad4Acc {
-    static constexpr int M = 16, O = 8;
+    static constexpr int M = TailLayout<4>::M;
     float g2[M + 2][2], gb2[2], gw1a[4], gw1b[4], gb1[4];
     double ce;
     int c00, c01, c10, c11;
@@ -469,11 +508,11 @@ struct TailQuad4Acc {
 // of dense_1 and their bias, the 1x1-conv rows and bias of its four hidden units) -- re-reading them from LDS for every
 // cell (~80 broadcast reads, each a full LDS latency for the single wave of a SIMD) was most of a cell's time
 struct TailQuad4W {
-    static constexpr int M = 16, O = 8;
+    using L = TailLayout<4>;
+    static constexpr int M = L::M, O = L::O, oW1 = L::oW1, oB1 = L::oB1, oW2 = L::oW2, oB2 = L::oB2;
     float w2[M + 2][2], b2[2];
     float own_a[4], own_b[4], own_b1[4];
     __device__ __forceinline__ void load(const float* __restrict__ sw, const int q) {
-        constexpr int oW1 = 0, oB1 = 2 * M, oW2 = 3 * M, oB2 = 3 * M + (M + 2) * O;
 #pragma unroll
         for (int i = 0; i < M + 2; ++i) { w2[i][0] = sw[oW2 + i * O + 2 * q]; w2[i][1] = sw[oW2 + i * O + 2 * q + 1]; }
         b2[0] = sw[oB2 + 2 * q];
@@ -486,24 +525,12 @@ struct TailQuad4W {
         }
     }
 };
-// lane k of every quad to all four lanes
-template <int K>
-__device__ __forceinline__ float quad_bcast(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), K * 0x55, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float quad_sum(float v) {
-    v += __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, v), 0));
-    v += __builtin_bit_cast(float, dpp_mov_i32(__builtin_bit_cast(int, v), 1));
-    return v;
-}
-constexpr int tail_quad4_lds_floats(int nt) { return (nt / 4) * (tail_param_count(4) | 1) + (nt / 64) * 2 + (nt / 64) * 4 + 2; }
-
 // one cell through R3-R6 and back on a quad of lanes: (z0, z1) and `valid` are quad-uniform, `label` is bit q of the
 // cell, swl the tail weights in LDS, prob_q (nullable) this lane's float2 of `output`; returns dz of the cell (quad-uniform)
 __device__ __forceinline__ float2 tail_quad4_cell(const float z0, const float z1, const int label, const bool valid,
                                                   const TailQuad4W& W, const float inv_count,
                                                   float* __restrict__ prob_q, const int q, TailQuad4Acc& A) {
-    constexpr int M = 16;
+    constexpr int M = TailLayout<4>::M;
     // a[4*q + u] without dynamic register indexing: three lane-mask selects.  (Written as ?: the compiler turned the
     // eight picks into nested exec-mask regions -- 130 scalar instructions per cell around ~330 vector ones -- although
     // every quad takes all four paths.)
@@ -515,7 +542,7 @@ __device__ __forceinline__ float2 tail_quad4_cell(const float z0, const float z1
         return r;
     };
     auto pick4 = [&](const float* a, int u) { return sel(sel(sel(a[u], a[4 + u], qm1), a[8 + u], qm2), a[12 + u], qm3); };
-    // the 1x1 conv: every lane evaluates its own four hidden units (same expression as tail_cells) and the quad trades them
+    // the 1x1 conv: every lane evaluates its own four hidden units (tail_fwd_logits' expression) and the quad trades them
     // on the DPP crossbar -- 16 + 16 instructions where four redundant evaluations of all 16 units took 64
     float c[M + 2], pre_own[4], c_own[4];
 #pragma unroll
@@ -539,6 +566,8 @@ __device__ __forceinline__ float2 tail_quad4_cell(const float z0, const float z1
         s1 = __builtin_fmaf(c[i], W.w2[i][1], s1);
     }
     const float p20 = s0, p21 = s1;
+    // repeats tail_softmax, then the second softmax / cross entropy of tail_cells_out, with both exponents as a select of the two
+    // differences (the same floats, see tail_softmax; through the shared function this kernel's instructions change)
     const float u0 = leaky_relu(p20), u1 = leaky_relu(p21);
     const bool u1_big = u1 > u0;
     const float eo = exp_nonpos(u1_big ? (u0 - u1) : (u1 - u0));
@@ -563,13 +592,8 @@ __device__ __forceinline__ float2 tail_quad4_cell(const float z0, const float z1
     A.c11 += l1 & pred & vb;
     // backward of this lane's bit
     const float inv_eff = valid ? inv_count : 0.f;
-    const float rfs = rcp_fast(fs);
-    const float q0 = f0 * rfs, q1 = f1 * rfs;
-    const float ga = (q0 - (label ? 0.f : 1.f)) * inv_eff;
-    const float gb = (q1 - (label ? 1.f : 0.f)) * inv_eff;
-    const float dot = ga * p0 + gb * p1;
-    const float du0 = p0 * (ga - dot), du1 = p1 * (gb - dot);
-    const float d20 = du0 * (p20 > 0.f ? 1.f : kLeaky), d21 = du1 * (p21 > 0.f ? 1.f : kLeaky);
+    const float2 d2 = tail_bit_bwd(f0, f1, fs, p0, p1, label != 0, inv_eff, p20, p21);
+    const float d20 = d2.x, d21 = d2.y;
     A.gb2[0] += d20;
     A.gb2[1] += d21;
     float dc[M + 2];
@@ -593,52 +617,36 @@ __device__ __forceinline__ float2 tail_quad4_cell(const float z0, const float z1
 }
 
 // block reduction of the quad-lane accumulators: every quad row of the LDS matrix gets each parameter column from the
-// lane that owns it; lds holds tail_quad4_lds_floats(NT) floats (8-byte aligned).  Starts with no barrier of its own:
-// the caller must have finished with `lds`; ends without one.
+// lane that owns it; lds holds tail_reduce_lds_floats<4, true>(NT) floats (8-byte aligned).  Barrier contract: starts with no
+// barrier of its own: the caller must have finished with `lds`; one barrier inside; ends without one.
 template <int NT>
 __device__ __forceinline__ void tail_quad4_block_reduce(TailQuad4Acc& A, float* __restrict__ lds,
                                                         TailBlockMetrics* __restrict__ blk_metrics,
                                                         float* __restrict__ blk_grads, const int slab) {
-    constexpr int M = 16, O = 8, P = tail_param_count(4);
-    constexpr int oW1 = 0, oB1 = 2 * M, oW2 = 3 * M, oB2 = 3 * M + (M + 2) * O;
-    constexpr int PS = P | 1, NW = NT / 64, NQ = NT / 4;
-    double* sce = reinterpret_cast<double*>(lds);              // [NW]
-    int* sconf = reinterpret_cast<int*>(lds + 2 * NW);         // [NW][4]
-    float* smat = lds + 2 * NW + 4 * NW + 2;                   // [NQ][PS]
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, q = threadIdx.x & 3;
-    const double ce = wave_sum(A.ce);
-    const int c00 = wave_sum(A.c00), c01 = wave_sum(A.c01), c10 = wave_sum(A.c10), c11 = wave_sum(A.c11);
-    if (lane == 0) {
-        sce[wid] = ce;
-        sconf[wid * 4 + 0] = c00; sconf[wid * 4 + 1] = c01; sconf[wid * 4 + 2] = c10; sconf[wid * 4 + 3] = c11;
-    }
+    using L = TailLayout<4>;
+    constexpr int P = L::P, PS = P | 1, NQ = NT / 4;
+    double* sce = reinterpret_cast<double*>(lds);                      // [NT / 64]
+    int* sconf = reinterpret_cast<int*>(lds + 2 * (NT / 64));          // [NT / 64][4]
+    float* smat = lds + tail_reduce_head_floats(NT);                   // [NQ][PS] partial gradient sums
+    const int q = threadIdx.x & 3;
+    tail_park_wave_sums(A, sce, sconf);
     float* row = smat + (threadIdx.x >> 2) * PS;
 #pragma unroll
-    for (int i = 0; i < M + 2; ++i) {
-        row[oW2 + i * O + 2 * q] = A.g2[i][0];
-        row[oW2 + i * O + 2 * q + 1] = A.g2[i][1];
+    for (int i = 0; i < L::M + 2; ++i) {
+        row[L::oW2 + i * L::O + 2 * q] = A.g2[i][0];
+        row[L::oW2 + i * L::O + 2 * q + 1] = A.g2[i][1];
     }
-    row[oB2 + 2 * q] = A.gb2[0];
-    row[oB2 + 2 * q + 1] = A.gb2[1];
+    row[L::oB2 + 2 * q] = A.gb2[0];
+    row[L::oB2 + 2 * q + 1] = A.gb2[1];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
-        row[oW1 + 4 * q + u] = A.gw1a[u];
-        row[oW1 + M + 4 * q + u] = A.gw1b[u];
-        row[oB1 + 4 * q + u] = A.gb1[u];
+        row[L::oW1 + 4 * q + u] = A.gw1a[u];
+        row[L::oW1 + L::M + 4 * q + u] = A.gw1b[u];
+        row[L::oB1 + 4 * q + u] = A.gb1[u];
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        TailBlockMetrics bm;
-        double t = 0.0;
-        for (int w = 0; w < NW; w += 4) t += (sce[w] + sce[w + 1]) + (sce[w + 2] + sce[w + 3]);
-        bm.ce_sum = t;
-        for (int k = 0; k < 4; ++k) {
-            long long c = 0;
-            for (int w = 0; w < NW; ++w) c += sconf[w * 4 + k];
-            bm.conf[k] = c;
-        }
-        blk_metrics[slab] = bm;
-    }
+    tail_block_totals<NT / 64, true>(sce, sconf, blk_metrics, slab);
+    // part 3, the statements that close tail_block_reduce
     const int slot = threadIdx.x >> 2, part = threadIdx.x & 3;
     for (int col0 = 0; col0 < P; col0 += NQ) {
         const int col = col0 + slot;
@@ -665,7 +673,7 @@ __global__ __launch_bounds__(kTailThreads) void demod_tail_quad4_kernel(
     float* __restrict__ blk_grads = chain_at(blk_grads_, coff);
     constexpr int NB = 4;
     stamp_mark(stamp, 0);
-    __shared__ __attribute__((aligned(8))) float sred[tail_quad4_lds_floats(kTailThreads)];
+    __shared__ __attribute__((aligned(8))) float sred[tail_reduce_lds_floats<NB, true>(kTailThreads)];
     const int q = threadIdx.x & 3;
     TailQuad4W W;
     W.load(tailp, q);

@@ -256,7 +256,9 @@ def _tail_case(nbits, cells, rng):
 
 
 @pytest.mark.parametrize("nbits,cells", [(1, 36 * 320), (2, 36 * 320), (3, 36 * 320), (4, 36 * 320),
-                                         (2, 1170 * 320), (4, 1170 * 320), (2, 1), (3, 77)])
+                                         (2, 1170 * 320), (4, 1170 * 320), (2, 1), (3, 77),
+                                         # the quad-lane form with one cell and with a cell count off the quad stride
+                                         (4, 1), (4, 77), (1, 77)])
 def test_demod_tail_loss(ops, nbits, cells):
     rng = np.random.RandomState(10 * nbits + cells % 7)
     tp, z, bits, r = _tail_case(nbits, cells, rng)

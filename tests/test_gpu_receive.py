@@ -114,7 +114,7 @@ def _tail_arena(p):
 @pytest.mark.parametrize("nbits", [1, 2, 3, 4])
 @pytest.mark.parametrize("frames,D", [(13, 50), (37, 320)])
 def test_stand_alone_decision_kernel(nbits, frames, D):
-    from dl_ofdm_amd import _lib
+    from dl_ofdm_amd import _lib, ops
     from dl_ofdm_amd.receive import row_bytes, unpack_bits
     lib = _lib.load()
     cfg = O.RxConfig(S=7, kin=80, F=64, D=D, nbits=nbits)
@@ -125,6 +125,7 @@ def test_stand_alone_decision_kernel(nbits, frames, D):
             p[k] = rng.uniform(-0.05, 0.05, p[k].shape).astype(np.float32)
     assert lib.dccn_tail_param_count(nbits) == _tail_arena(p).size
     z = (rng.randn(frames * D, 2) * 1.5).astype(np.float32)
+    labels = rng.randint(0, 2, (frames * D, nbits)).astype(np.int32)     # for the evaluation tail: the oracle comparison ignores them
     dev = "cuda"
     zt, tp = torch.as_tensor(z, device=dev), torch.as_tensor(_tail_arena(p), device=dev)
     packed = torch.full((frames, row_bytes(D, nbits)), 0xAA, dtype=torch.uint8, device=dev)
@@ -135,7 +136,7 @@ def test_stand_alone_decision_kernel(nbits, frames, D):
                                      nbits, st), "dccn_demod_decide")
     torch.cuda.synchronize()
     p64 = {k: v.astype(np.float64) for k, v in p.items()}
-    tl = O.tail_forward_backward(z.astype(np.float64), np.zeros((frames * D, nbits), np.int32), p64["demodulation/conv2d/kernel"],
+    tl = O.tail_forward_backward(z.astype(np.float64), labels, p64["demodulation/conv2d/kernel"],
                                  p64["demodulation/conv2d/bias"], p64["demodulation/dense_1/kernel"],
                                  p64["demodulation/dense_1/bias"], nbits)
     pt = tl["prob"].reshape(-1, 2)
@@ -152,6 +153,15 @@ def test_stand_alone_decision_kernel(nbits, frames, D):
     lv = llr.cpu().numpy().reshape(-1)
     big = np.abs(lv) > 1e-6
     assert np.array_equal(hard[big], (lv > 0)[big].astype(np.uint8))
+    # the decision kernel and the evaluation tail call the same forward and softmax (tail.h tail_fwd_logits / tail_softmax): the
+    # same floats, so the same decisions at EVERY cell (no tie mask) and the confusion table the evaluation tallies
+    _, prob_eval, mbuf = ops.demod_tail_eval(zt, tp, torch.as_tensor(labels, device=dev), nbits)
+    assert torch.equal(prob.reshape(-1, nbits, 2), prob_eval.reshape(-1, nbits, 2))
+    pe = prob_eval.cpu().numpy().reshape(-1, 2)
+    assert np.array_equal(hard, (pe[:, 1] > pe[:, 0]).astype(np.uint8))
+    lab = labels.reshape(-1)
+    conf = [[int(((lab == l) & (hard == h)).sum()) for h in (0, 1)] for l in (0, 1)]
+    assert conf == ops.read_metrics(mbuf)["conf"]
 
 
 @pytest.mark.parametrize("M,K,N,nbits", [(1170, 896, 640, 1), (1170, 896, 640, 2), (36, 896, 640, 1), (73, 896, 640, 2),
