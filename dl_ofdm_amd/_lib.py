@@ -43,6 +43,18 @@ class RxShape(C.Structure):
     _fields_ = [("batch", c_int), ("S", c_int), ("kin", c_int), ("F", c_int), ("D", c_int), ("nbits", c_int)]
 
 
+class GemmRoute(C.Structure):
+    """dccn_gemm_route: what dccn_gemm_route_query reports (ops and families: the DCCN_ROUTE_* / DCCN_FAMILY_* ids of dccn.h)"""
+    _fields_ = [("family", c_int), ("variant", c_int), ("tile_rows", c_int), ("tile_cols", c_int), ("tile_k", c_int),
+                ("w_tile_rows", c_int), ("w_tile_cols", c_int), ("splits", c_int), ("klen", c_int), ("nranges", c_int),
+                ("koff", c_int * 9), ("stage", c_int)]
+
+
+ROUTE_OPS = dict(dense_fwd=0, dense_bwd_x=1, dense_bwd_w=2, dense_bwd=3, cconv_fwd=4, cconv_bwd_w=5, rx_backward=6)
+ROUTE_FAMILIES = dict(generic=0, gemm16=1, skinny=2, fewrow=3, kmajor=4, staged=5, grouped_big=6, grouped_kmajor=7, grouped=8,
+                      two_launch=9, rx_fused=10)
+
+
 class RxBuffers(C.Structure):
     """dccn_rx_buffers"""
     _fields_ = [("x", c_void_p), ("bits", c_void_p), ("params", c_void_p), ("grads", c_void_p),
@@ -190,6 +202,7 @@ SIGNATURES = {
     "dccn_get_tuning": (_i, [_i]),
     "dccn_dense_tail_supported": (_i, [_i, _i, _i, _i]),
     "dccn_dense_tail_grid": (_i, [_i, _i, _i, _i] + [POINTER(c_int)] * 4),
+    "dccn_gemm_route_query": (_i, [_i] * 6 + [POINTER(GemmRoute)]),
     "dccn_rx_bwd_fused_supported": (_i, [POINTER(RxShape)]),
     "dccn_rx_dense_tail_fused": (_i, [POINTER(RxShape), _i]),
     "dccn_rx_norm_rides_backward": (_i, [POINTER(RxShape)]),

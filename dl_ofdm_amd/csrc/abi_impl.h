@@ -143,14 +143,34 @@ struct TuneScope {
 
 // few output rows, long k: 64x64 tiles leave most CUs without a block (73x896 = 28 tiles); 16- or 32-row tiles give 2-5x
 // the blocks, and loads two k-tiles ahead cover the latency that the short MFMA phases cannot
+// ---- one table per variant family: a variant's gemm16.h template arguments are written once; the launcher instantiation,
+// the tile's rows and columns and its k-tile depth (and what dccn_gemm_route_query reports) all read them
+struct Tile16Cfg {
+    int wgm, wgn, tm, tn, bk, ks;     // WGM x WGN waves of TM x TN 16x16 tiles each, k-tiles BK deep, KS k-slices
+    constexpr int rows() const { return wgm * tm * 16; }
+    constexpr int cols() const { return wgn * tn * 16; }
+};
+// TUNE_SKINNY 1-4
+constexpr int kSkinnyVariants = 4;
+constexpr Tile16Cfg kSkinny16[kSkinnyVariants + 1] = {{},
+    {1, 4, 1, 1, 64, 1},      // 16x64
+    {1, 4, 2, 1, 64, 1},      // 32x64
+    {2, 2, 1, 1, 64, 1},      // 32x32
+    {1, 4, 1, 1, 64, 2}};     // 16x64, 8 waves
+template <int KA, int KB, int TAG, int ACT, int V>
+static int skinny16_launch(const GemmParams& p, hipStream_t s) {
+    constexpr Tile16Cfg c = kSkinny16[V];
+    return launch_gemm16<KA, KB, c.wgm, c.wgn, c.tm, c.tn, c.bk, c.ks, 0, TAG, 2, ACT>(p, 1, s);
+}
+// (an element-wise stage runs on variant 1 whatever the knob says: the route says so)
 template <int KA, int KB, int TAG, int ACT = 1>
 static int skinny_launch(int variant, const GemmParams& p, hipStream_t s) {
-    if constexpr (ACT != 1) return launch_gemm16<KA, KB, 1, 4, 1, 1, 64, 1, 0, TAG, 2, ACT>(p, 1, s);   // 16x64 + element-wise stage
+    if constexpr (ACT != 1) return skinny16_launch<KA, KB, TAG, ACT, 1>(p, s);
     switch (variant) {
-        case 1: return launch_gemm16<KA, KB, 1, 4, 1, 1, 64, 1, 0, TAG, 2>(p, 1, s);       // 16x64
-        case 2: return launch_gemm16<KA, KB, 1, 4, 2, 1, 64, 1, 0, TAG, 2>(p, 1, s);       // 32x64
-        case 3: return launch_gemm16<KA, KB, 2, 2, 1, 1, 64, 1, 0, TAG, 2>(p, 1, s);       // 32x32
-        case 4: return launch_gemm16<KA, KB, 1, 4, 1, 1, 64, 2, 0, TAG, 2>(p, 1, s);       // 16x64, 8 waves
+        case 1: return skinny16_launch<KA, KB, TAG, 1, 1>(p, s);
+        case 2: return skinny16_launch<KA, KB, TAG, 1, 2>(p, s);
+        case 3: return skinny16_launch<KA, KB, TAG, 1, 3>(p, s);
+        case 4: return skinny16_launch<KA, KB, TAG, 1, 4>(p, s);
         default: return DCCN_ERR_INVALID_ARG;
     }
 }

@@ -165,15 +165,37 @@ static GemmParams cconv_bwd_w_params(const float* x, const float* dout, int rows
     return p;
 }
 
-// ---- one table per variant family: a variant's gemm16.h template arguments are written once; the launcher instantiation,
-// the tile's rows and columns and its k-tile depth all read them
-struct Tile16Cfg {
-    int wgm, wgn, tm, tn, bk, ks;     // WGM x WGN waves of TM x TN 16x16 tiles each, k-tiles BK deep, KS k-slices
-    constexpr int rows() const { return wgm * tm * 16; }
-    constexpr int cols() const { return wgn * tn * 16; }
-};
-// (a family's launcher is a template over the variant number that reads its row; a table of its instantiations, indexed by
-// the variant, sits next to the rows)
+// ---- one table per variant family (Tile16Cfg, abi_impl.h): a family's launcher is a template over the variant number that
+// reads its row; a table of its instantiations, indexed by the variant, sits next to the rows
+
+// ---- the launch an operator issues, decided ONCE per operator by its *_route function: the *_impl function issues what the
+// route names, dccn_gemm_route_query reports it (include/dccn.h: dccn_gemm_route, the DCCN_FAMILY_* ids).  A route function
+// returns DCCN_ERR_INVALID_ARG where the operator refuses -- before any launch.
+using Route = dccn_gemm_route;
+enum RouteStage : int { STAGE_SPLIT_PAIRS = 6 };      // (after the StoreStage values: the dX stores of a concat's gradient)
+static Route route_of(int family, int variant, int rows, int cols, int bk) {
+    Route r;
+    memset(&r, 0, sizeof(r));
+    r.family = family; r.variant = variant;
+    r.tile_rows = rows; r.tile_cols = cols; r.tile_k = bk;
+    r.splits = 1; r.stage = STORE_PLAIN;
+    return r;
+}
+static Route route16(int family, int variant, const Tile16Cfg& c) { return route_of(family, variant, c.rows(), c.cols(), c.bk); }
+static Route with_split(Route r, const SplitPlan& sp) {
+    r.splits = sp.splits; r.klen = sp.klen;
+    return r;
+}
+// the tile launch_gemm picks (gemm_f32_mfma.h)
+template <int KA, int KB>
+static Route route_generic(const GemmParams& p, int splits = 1) {
+    const GemmTile t = gemm_tile<KA, KB>(p, splits);
+    Route r = route_of(DCCN_FAMILY_GENERIC, 0, t.bm, t.bn, t.bk);
+    r.splits = splits; r.klen = p.klen;
+    return r;
+}
+// the one-latency 16x16 tiles of fewrow.h: ng slots of 64 k each
+static Route route_fewrow(int ng) { return route_of(DCCN_FAMILY_FEWROW, 0, 16, 16, 64 * ng); }
 
 // the tiles the plain and the fused (tail / decision) dense forward run on: 48x64 with loads two k-tiles ahead (small layers),
 // 80x64 (large layers), 32x64 for a short last tile row next to the 80x64 tiles
@@ -185,6 +207,32 @@ template <int ACT = 1>
 static int dense48_launch(const GemmParams& p, hipStream_t s, size_t smem_min = 0) {
     constexpr Tile16Cfg c = kDense48;
     return launch_gemm16<OP_KCONTIG, OP_ICONTIG, c.wgm, c.wgn, c.tm, c.tn, c.bk, c.ks, 0, TAG_DENSE_FWD, 2, ACT>(p, 1, s, smem_min);
+}
+
+// asked: the element-wise stage the caller asks for; route.stage: the one the launch carries -- a tile family carries stages
+// from a level of knob 19 on: the few-row and skinny tiles from level 1, the 48x64 tiles from level 2
+static int dense_fwd_route(const GemmParams& p, int asked, Route* out) {
+    const auto stage_from = [&](int level) { return g_tune[TUNE_EQ_EPILOGUES] >= level ? asked : (int)STORE_PLAIN; };
+    // few rows, K = 640 / 896: every operand of a 16x16 tile requested at once, no LDS staging (fewrow.h)
+    if (g_tune[TUNE_FEWROW] && g_tune[TUNE_SKINNY] > 0 && fewrow_ng(p) && aligned16(p.C)) {
+        *out = route_fewrow(fewrow_ng(p));
+        out->stage = stage_from(1);
+    } else if (skinny_ok(p)) {
+        // (a stage runs on variant 1 whatever the knob says)
+        const int st = stage_from(1), v = st != STORE_PLAIN ? 1 : g_tune[TUNE_SKINNY];
+        if (v > kSkinnyVariants) return DCCN_ERR_INVALID_ARG;
+        *out = route16(DCCN_FAMILY_SKINNY, v, kSkinny16[v]);
+        out->stage = st;
+    } else if (g_tune[TUNE_DENSE_FWD_PLAIN] && vec_both(p) && (p.K % 4 == 0) && (p.N % 4 == 0) && p.K >= 128 &&
+               (long long)ceil_div(p.M, 128) * ceil_div(p.N, 128) < 2 * kCUs) {
+        // small layers (64x64 tiles would leave CUs without a block: 1170x640 = 190 tiles): the 48x64 tiles of the fused
+        // kernel, loads two k-tiles ahead
+        *out = route16(DCCN_FAMILY_GEMM16, 0, kDense48);
+        out->stage = stage_from(2);
+    } else {
+        *out = route_generic<OP_KCONTIG, OP_ICONTIG>(p);
+    }
+    return DCCN_OK;
 }
 
 // ldx: as dense_fwd_params
@@ -200,43 +248,54 @@ int dense_fwd_impl(const float* x, const float* w, const float* bias, float* y, 
     const bool eq_stage = act == 5 && act_done && aux && out2 && out3 && g_tune[TUNE_EQ_EPILOGUES] && (N % 2 == 0) &&
                           aligned16(aux) && aligned16(out2) && aligned16(out3);
     if (eq_stage) { p.aux = aux; p.out2 = out2; p.out3 = out3; }
-    // the element-wise stage the caller asks for, and the one a tile family carries: the few-row and skinny tiles from knob
-    // level 1, the 48x64 tiles from level 2.  *act_done is set exactly when the launch carries a stage.
+    // the element-wise stage the caller asks for (dense_fwd_route: which one the launch carries)
     const int asked = eq_stage ? 5 : (act == 2 && act_done) ? 2 : 1;
-    const auto stage_from = [&](int level) {
-        const int st = g_tune[TUNE_EQ_EPILOGUES] >= level ? asked : 1;
-        if (st != 1) *act_done = true;
-        return st;
-    };
-    // few rows, K = 640 / 896: every operand of a 16x16 tile requested at once, no LDS staging (fewrow.h)
-    if (g_tune[TUNE_FEWROW] && g_tune[TUNE_SKINNY] > 0 && fewrow_ng(p) && aligned16(y)) switch (stage_from(1)) {
-        case 5: return launch_fewrow<OP_ICONTIG, 5, TAG_DENSE_FWD>(p, s);
-        case 2: return launch_fewrow<OP_ICONTIG, 2, TAG_DENSE_FWD>(p, s);
-        default: return launch_fewrow<OP_ICONTIG, 1, TAG_DENSE_FWD>(p, s);
+    Route r;
+    DCCN_TRY(dense_fwd_route(p, asked, &r));
+    if (r.stage != STORE_PLAIN) *act_done = true;       // set exactly when the launch carries a stage
+    switch (r.family) {
+        case DCCN_FAMILY_FEWROW: switch (r.stage) {
+            case 5: return launch_fewrow<OP_ICONTIG, 5, TAG_DENSE_FWD>(p, s);
+            case 2: return launch_fewrow<OP_ICONTIG, 2, TAG_DENSE_FWD>(p, s);
+            default: return launch_fewrow<OP_ICONTIG, 1, TAG_DENSE_FWD>(p, s);
+        }
+        case DCCN_FAMILY_SKINNY: switch (r.stage) {
+            case 5: return skinny_launch<OP_KCONTIG, OP_ICONTIG, TAG_DENSE_FWD, 5>(r.variant, p, s);
+            case 2: return skinny_launch<OP_KCONTIG, OP_ICONTIG, TAG_DENSE_FWD, 2>(r.variant, p, s);
+            default: return skinny_launch<OP_KCONTIG, OP_ICONTIG, TAG_DENSE_FWD>(r.variant, p, s);
+        }
+        case DCCN_FAMILY_GEMM16: switch (r.stage) {
+            case 5: return dense48_launch<5>(p, s);
+            case 2: return dense48_launch<2>(p, s);
+            default: return dense48_launch<1>(p, s);
+        }
+        default: return launch_gemm<OP_KCONTIG, OP_ICONTIG, 0, TAG_DENSE_FWD>(p, 1, s);
     }
-    // (skinny_launch: a stage runs on variant 1 whatever the knob says)
-    if (skinny_ok(p)) switch (stage_from(1)) {
-        case 5: return skinny_launch<OP_KCONTIG, OP_ICONTIG, TAG_DENSE_FWD, 5>(g_tune[TUNE_SKINNY], p, s);
-        case 2: return skinny_launch<OP_KCONTIG, OP_ICONTIG, TAG_DENSE_FWD, 2>(g_tune[TUNE_SKINNY], p, s);
-        default: return skinny_launch<OP_KCONTIG, OP_ICONTIG, TAG_DENSE_FWD>(g_tune[TUNE_SKINNY], p, s);
-    }
-    // small layers (64x64 tiles would leave CUs without a block: 1170x640 = 190 tiles): the 48x64 tiles of the fused
-    // kernel, loads two k-tiles ahead
-    if (g_tune[TUNE_DENSE_FWD_PLAIN] && vec_both(p) && (K % 4 == 0) && (N % 4 == 0) && K >= 128 &&
-        (long long)ceil_div(M, 128) * ceil_div(N, 128) < 2 * kCUs) switch (stage_from(2)) {
-        case 5: return dense48_launch<5>(p, s);
-        case 2: return dense48_launch<2>(p, s);
-        default: return dense48_launch<1>(p, s);
-    }
-    return launch_gemm<OP_KCONTIG, OP_ICONTIG, 0, TAG_DENSE_FWD>(p, 1, s);
 }
 
+// (p.C = dx: the few-row tiles ask for an output)
+static int dense_bwd_x_route(const GemmParams& p, Route* out) {
+    if (g_tune[TUNE_FEWROW] && g_tune[TUNE_SKINNY] > 0 && fewrow_ng(p)) {
+        *out = route_fewrow(fewrow_ng(p));
+    } else if (skinny_ok(p)) {
+        const int v = g_tune[TUNE_SKINNY];
+        if (v > kSkinnyVariants) return DCCN_ERR_INVALID_ARG;
+        *out = route16(DCCN_FAMILY_SKINNY, v, kSkinny16[v]);
+    } else {
+        *out = route_generic<OP_KCONTIG, OP_KCONTIG>(p);
+    }
+    return DCCN_OK;
+}
 int dense_bwd_x_impl(const float* dy, const float* w, float* dx, int M, int K, int N, hipStream_t s) {
     if (!dy || !w || !dx || M <= 0 || K <= 0 || N <= 0) return DCCN_ERR_INVALID_ARG;
     const GemmParams p = dense_bwd_x_params(dy, w, dx, M, K, N);
-    if (g_tune[TUNE_FEWROW] && g_tune[TUNE_SKINNY] > 0 && fewrow_ng(p)) return launch_fewrow<OP_KCONTIG, 1, TAG_DENSE_BWD_X>(p, s);
-    if (skinny_ok(p)) return skinny_launch<OP_KCONTIG, OP_KCONTIG, TAG_DENSE_BWD_X>(g_tune[TUNE_SKINNY], p, s);
-    return launch_gemm<OP_KCONTIG, OP_KCONTIG, 0, TAG_DENSE_BWD_X>(p, 1, s);
+    Route r;
+    DCCN_TRY(dense_bwd_x_route(p, &r));
+    switch (r.family) {
+        case DCCN_FAMILY_FEWROW: return launch_fewrow<OP_KCONTIG, 1, TAG_DENSE_BWD_X>(p, s);
+        case DCCN_FAMILY_SKINNY: return skinny_launch<OP_KCONTIG, OP_KCONTIG, TAG_DENSE_BWD_X>(r.variant, p, s);
+        default: return launch_gemm<OP_KCONTIG, OP_KCONTIG, 0, TAG_DENSE_BWD_X>(p, 1, s);
+    }
 }
 
 // slab capacity for the weight-gradient split-K plans: small outputs may be cut into up to 8 k ranges (gemm16 paths)
@@ -314,6 +373,13 @@ static int graded_ranges(int preset, int M, int off[9]) {
     return cnt;
 }
 
+// the stand-alone dense weight gradient under split plan sp.  p.C = the slabs, p.klen = sp.klen
+static Route dense_bwd_w_route(const GemmParams& p, const SplitPlan& sp) {
+    const long long big = (long long)ceil_div(p.M, 128) * ceil_div(p.N, 128) * sp.splits;
+    if (sp.splits > 1 && g_tune[TUNE_DENSE_BWD] == kVariantKmajor && kmajor_ok(p) && big < 2 * kCUs)
+        return with_split(route_of(DCCN_FAMILY_KMAJOR, 0, 64, 64, 64), sp);
+    return route_generic<OP_ICONTIG, OP_ICONTIG>(p, sp.splits);
+}
 // defer != nullptr: leave the split-K slabs un-reduced (the fused Adam kernel sums them) and report them
 int dense_bwd_w_impl(const float* x, const float* dy, float* dw, float* dbias, int M, int K, int N, void* ws,
                             size_t ws_bytes, hipStream_t s, DeferredSlabs* defer, int ldx) {
@@ -325,16 +391,16 @@ int dense_bwd_w_impl(const float* x, const float* dy, float* dw, float* dbias, i
     if (!slab_carve(c, sp.splits, K, N, &sw)) return DCCN_ERR_WORKSPACE;
     GemmParams p = dense_bwd_w_params(x, dy, M, K, N, ldx);
     p.klen = sp.klen;
+    p.C = sw.slabs;
+    const Route r = dense_bwd_w_route(p, sp);
     if (defer) *defer = deferred_slabs(sw, false, false);
     if (sp.splits == 1) {
         p.C = dw;
         p.colsum = dbias;
         return launch_gemm<OP_ICONTIG, OP_ICONTIG, 1, TAG_DENSE_BWD_W>(p, 1, s);
     }
-    p.C = sw.slabs;
     p.colsum = dbias ? sw.colsum : nullptr;
-    const long long big = (long long)ceil_div(p.M, 128) * ceil_div(p.N, 128) * sp.splits;
-    if (g_tune[TUNE_DENSE_BWD] == kVariantKmajor && kmajor_ok(p) && big < 2 * kCUs)
+    if (r.family == DCCN_FAMILY_KMAJOR)
         DCCN_TRY((launch_kmajor<1, TAG_DENSE_BWD_W>(p, sp.splits, s)));
     else
         DCCN_TRY((launch_gemm<OP_ICONTIG, OP_ICONTIG, 1, TAG_DENSE_BWD_W>(p, sp.splits, s)));
@@ -350,7 +416,8 @@ int dense_bwd_w_impl(const float* x, const float* dy, float* dw, float* dbias, i
 
 // TUNE_DENSE_BWD 1-6: the dX and the dW tiles of the grouped gemm16 launch (one k-tile depth for both: x.bk)
 struct DenseBwd16Cfg { Tile16Cfg x, w; };
-constexpr DenseBwd16Cfg kDenseBwd16[7] = {{},
+constexpr int kDenseBwd16Rows = 6;
+constexpr DenseBwd16Cfg kDenseBwd16[kDenseBwd16Rows + 1] = {{},
     {{2, 2, 2, 2, 32, 1}, {2, 2, 2, 2, 32, 1}},     // dX 64x64, dW 64x64
     {{1, 4, 3, 1, 32, 1}, {2, 2, 2, 2, 32, 1}},     // dX 48x64
     {{2, 2, 2, 2, 64, 1}, {2, 2, 2, 2, 64, 1}},     // 64-deep k-tiles
@@ -365,6 +432,72 @@ static int dense_bwd16_launch(const GemmParams& px, const GemmParams& pw, int sp
 }
 constexpr int (*kDenseBwd16Launch[7])(const GemmParams&, const GemmParams&, int, hipStream_t) = {nullptr,
     dense_bwd16_launch<1>, dense_bwd16_launch<2>, dense_bwd16_launch<3>, dense_bwd16_launch<4>, dense_bwd16_launch<5>, dense_bwd16_launch<6>};
+// few rows: dX on the 16x64 skinny tiles, the unsplit dW on 64x64 tiles.  STAGE: element-wise stage of the dX stores
+constexpr DenseBwd16Cfg kDenseBwdSkinny = {kSkinny16[1], {2, 2, 2, 2, 64, 1}};
+template <int STAGE>
+static int dense_bwd_skinny_launch(const GemmParams& px, const GemmParams& pw, hipStream_t s) {
+    constexpr Tile16Cfg x = kDenseBwdSkinny.x, w = kDenseBwdSkinny.w;
+    return launch_dense_bwd16<x.wgm, x.wgn, x.tm, x.tn, x.bk, w.wgm, w.wgn, w.tm, w.tn, STAGE>(px, pw, 1, s, tune_smem_min());
+}
+
+// px, pw as dense_bwd_x_params / dense_bwd_w_params build them, pw.C = where the slabs will lie (the head of the workspace).
+// actx: the element-wise stage the caller asks of the dX stores (1 = none, 3 = times (1 - aux^2), 4 = plus aux); split_pairs:
+// dx is the gradient of a concat of two IQ-pair streams and the caller asks the stores to write the streams' own buffers.
+// route.splits / klen: the split plan of dW; route.stage: what the dX stores carry.
+static int dense_bwd_route(const GemmParams& px, GemmParams pw, int M, int K, int N, int actx, bool split_pairs, Route* out) {
+    const bool vec = vec_both(px) && vec_both(pw);
+    // few rows (the equaliser's 73-frame batch): dX on 16x64 tiles and the unsplit dW (k = the few rows: one or two
+    // k-tiles) in ONE grid -- round 2 ran them as two launches of 6-10 us each, almost all of it launch ramp and drain
+    if (g_tune[TUNE_SKINNY] > 0 && g_tune[TUNE_SKINNY_GROUPED] && vec && M <= 96 && (K % 4 == 0) && (N % 4 == 0)) {
+        const int ng = g_tune[TUNE_FEWROW] ? fewrow_ng(px) : 0;       // dX on the one-latency 16x16 tiles of fewrow.h
+        Route r = ng ? route_fewrow(ng) : route16(DCCN_FAMILY_SKINNY, 1, kDenseBwdSkinny.x);
+        r.w_tile_rows = kDenseBwdSkinny.w.rows(); r.w_tile_cols = kDenseBwdSkinny.w.cols();
+        r.klen = pw.klen;                                             // (the few rows, as built)
+        if (actx != 1 && g_tune[TUNE_EQ_EPILOGUES]) {
+            if (actx != 3 && actx != 4) return DCCN_ERR_INVALID_ARG;
+            r.stage = actx;
+        }
+        *out = r;
+        return DCCN_OK;
+    }
+    const int variant = g_tune[TUNE_DENSE_BWD] == kVariantKmajor ? 0 : g_tune[TUNE_DENSE_BWD];
+    const long long big = (long long)ceil_div(M, 128) * ceil_div(K, 128);
+    if (variant > 0 && vec && big < 2 * kCUs) {
+        if (variant > kDenseBwd16Rows) return DCCN_ERR_INVALID_ARG;       // (no such row)
+        const Tile16Cfg cx = kDenseBwd16[variant].x, cw = kDenseBwd16[variant].w;
+        const int nx = ceil_div(px.M, cx.rows()) * ceil_div(px.N, cx.cols()), tw = ceil_div(pw.M, cw.rows()) * ceil_div(pw.N, cw.cols());
+        int want = g_tune[TUNE_DENSE_BWD_SPLITS];
+        if (want <= 0) want = (3 * kCUs - nx + tw / 2) / tw;            // about three resident blocks per CU in all
+        const int cap = max_splits16(K, N);
+        if (want > cap) want = cap;
+        Route r = with_split(route16(DCCN_FAMILY_GEMM16, variant, cx), plan_splitk_n(M, want, cx.bk));
+        r.w_tile_rows = cw.rows(); r.w_tile_cols = cw.cols();
+        *out = r;
+        return DCCN_OK;
+    }
+    const SplitPlan sp = dense_dw_plan(M, K, N);
+    pw.klen = sp.klen;
+    Route r;
+    if (vec && g_tune[TUNE_DENSE_BWD_BIG] && grouped_big_ok(px, pw, sp.splits)) {
+        r = route_of(DCCN_FAMILY_GROUPED_BIG, 0, 128, 128, 32);
+        r.w_tile_rows = r.w_tile_cols = 128;
+    } else if (sp.splits < 2 || !vec || !grouped_ok(px, pw, sp.splits)) {
+        r = route_of(DCCN_FAMILY_TWO_LAUNCH, 0, 0, 0, 0);
+    } else {
+        pw.ldc = N;
+        const bool km = g_tune[TUNE_DENSE_BWD] == kVariantKmajor && kmajor_ok(pw);
+        r = route_of(km ? DCCN_FAMILY_GROUPED_KMAJOR : DCCN_FAMILY_GROUPED, 0, 64, 64, 64);
+        r.w_tile_rows = r.w_tile_cols = 64;
+        if (km && split_pairs && (K % 4 == 0)) {
+            r.stage = STAGE_SPLIT_PAIRS;
+        } else if (km && actx != 1 && g_tune[TUNE_EQ_EPILOGUES] >= 2) {
+            if (actx != 3 && actx != 4) return DCCN_ERR_INVALID_ARG;
+            r.stage = actx;
+        }
+    }
+    *out = with_split(r, sp);
+    return DCCN_OK;
+}
 
 // dense backward as ONE grouped launch: dx = dy.w^T together with the split-K slabs of dw = x^T.dy
 // (left un-reduced for the fused Adam kernel).  Falls back to two launches when the grouped
@@ -379,94 +512,68 @@ int dense_bwd_grouped_impl(const float* x, const float* dy, const float* w, floa
     if (!ws || ws_bytes < splitk_ws_bytes(K, N, M)) return DCCN_ERR_WORKSPACE;
     GemmParams px = dense_bwd_x_params(dy, w, dx, M, K, N);
     GemmParams pw = dense_bwd_w_params(x, dy, M, K, N);       // (klen: the whole k range until a branch plans its split)
-    const bool vec = vec_both(px) && vec_both(pw);
-    // few rows (the equaliser's 73-frame batch): dX on 16x64 tiles and the unsplit dW (k = the few rows: one or two
-    // k-tiles) in ONE grid -- round 2 ran them as two launches of 6-10 us each, almost all of it launch ramp and drain
-    if (g_tune[TUNE_SKINNY] > 0 && g_tune[TUNE_SKINNY_GROUPED] && vec && M <= 96 && (K % 4 == 0) && (N % 4 == 0)) {
+    Route r;
+    {
+        GemmParams pq = pw;
+        pq.C = static_cast<float*>(ws);             // (slab_carve's first piece lies at the head of the workspace)
+        DCCN_TRY(dense_bwd_route(px, pq, M, K, N, (act_done && aux) ? actx : 1, split_done && split_dst && split_pairs_gc != 0, &r));
+    }
+    // the dX tiles may carry an element-wise stage of the caller's graph: 3 = times (1 - aux^2) (tanh gradient),
+    // 4 = plus aux (gradient accumulation): two 5 us launches of the equaliser step less
+    if (r.stage == STORE_TANHGRAD || r.stage == STORE_ADD) {
+        px.aux = aux;
+        *act_done = true;
+    }
+    if (r.family == DCCN_FAMILY_FEWROW || r.family == DCCN_FAMILY_SKINNY) {
         pw.C = dw; pw.colsum = dbias; pw.slab = 0;       // (klen = the few rows, as built)
-        // the dX tiles may carry an element-wise stage of the caller's graph: 3 = times (1 - aux^2) (tanh gradient),
-        // 4 = plus aux (gradient accumulation): two 5 us launches of the equaliser step less
-        const bool few = g_tune[TUNE_FEWROW] && fewrow_ng(px) != 0;        // dX on the one-latency 16x16 tiles of fewrow.h
-        if (actx != 1 && act_done && aux && g_tune[TUNE_EQ_EPILOGUES]) {
-            px.aux = aux;
-            *act_done = true;
-            if (actx == 3) DCCN_TRY(few ? launch_dense_bwd_fewrow<3>(px, pw, s)
-                                        : (launch_dense_bwd16<1, 4, 1, 1, 64, 2, 2, 2, 2, 3>(px, pw, 1, s, tune_smem_min())));
-            else if (actx == 4) DCCN_TRY(few ? launch_dense_bwd_fewrow<4>(px, pw, s)
-                                             : (launch_dense_bwd16<1, 4, 1, 1, 64, 2, 2, 2, 2, 4>(px, pw, 1, s, tune_smem_min())));
-            else return DCCN_ERR_INVALID_ARG;
-        } else
-        DCCN_TRY(few ? launch_dense_bwd_fewrow<1>(px, pw, s)
-                     : (launch_dense_bwd16<1, 4, 1, 1, 64, 2, 2, 2, 2>(px, pw, 1, s, tune_smem_min())));
+        const bool few = r.family == DCCN_FAMILY_FEWROW;
+        if (r.stage == STORE_TANHGRAD) DCCN_TRY(few ? launch_dense_bwd_fewrow<3>(px, pw, s) : dense_bwd_skinny_launch<3>(px, pw, s));
+        else if (r.stage == STORE_ADD) DCCN_TRY(few ? launch_dense_bwd_fewrow<4>(px, pw, s) : dense_bwd_skinny_launch<4>(px, pw, s));
+        else DCCN_TRY(few ? launch_dense_bwd_fewrow<1>(px, pw, s) : dense_bwd_skinny_launch<1>(px, pw, s));
         *defer = deferred_slabs(SlabWs{}, false, false);
         return DCCN_OK;
     }
-    const int variant = g_tune[TUNE_DENSE_BWD] == kVariantKmajor ? 0 : g_tune[TUNE_DENSE_BWD];
-    const long long big = (long long)ceil_div(M, 128) * ceil_div(K, 128);
-    if (variant > 0 && vec && big < 2 * kCUs) {
-        if (variant > 6) return DCCN_ERR_INVALID_ARG;       // (no such row; the carve below cannot fail after the size check above)
-        const Tile16Cfg cx = kDenseBwd16[variant].x, cw = kDenseBwd16[variant].w;
-        const int nx = ceil_div(px.M, cx.rows()) * ceil_div(px.N, cx.cols()), tw = ceil_div(pw.M, cw.rows()) * ceil_div(pw.N, cw.cols());
-        int want = g_tune[TUNE_DENSE_BWD_SPLITS];
-        if (want <= 0) want = (3 * kCUs - nx + tw / 2) / tw;            // about three resident blocks per CU in all
-        const int cap = max_splits16(K, N);
-        if (want > cap) want = cap;
-        const SplitPlan sp = plan_splitk_n(M, want, cx.bk);
-        Carver c(ws, ws_bytes);
-        SlabWs sw;
-        if (!slab_carve(c, sp.splits, K, N, &sw)) return DCCN_ERR_WORKSPACE;
-        pw.klen = sp.klen;
-        if (sp.splits == 1) {
-            pw.C = dw; pw.colsum = dbias;
-        } else {
-            pw.C = sw.slabs; pw.colsum = dbias ? sw.colsum : nullptr;
-        }
-        DCCN_TRY(kDenseBwd16Launch[variant](px, pw, sp.splits, s));
-        *defer = deferred_slabs(sw, dbias != nullptr, sp.splits > 1);
-        return DCCN_OK;
-    }
-    const SplitPlan sp = dense_dw_plan(M, K, N);
-    Carver c(ws, ws_bytes);
-    SlabWs sw;
-    if (!slab_carve(c, sp.splits, K, N, &sw)) return DCCN_ERR_WORKSPACE;
-    pw.C = sw.slabs; pw.colsum = dbias ? sw.colsum : nullptr;
-    pw.klen = sp.klen;
-    if (vec && g_tune[TUNE_DENSE_BWD_BIG] && grouped_big_ok(px, pw, sp.splits)) {
-        pw.ldc = N;
-        if (sp.splits == 1) { pw.C = dw; pw.colsum = dbias; pw.slab = 0; }
-        DCCN_TRY((launch_dense_bwd_grouped<true, 128, 128, 32>(px, pw, sp.splits, s)));
-        *defer = deferred_slabs(sw, dbias != nullptr, sp.splits > 1);
-        return DCCN_OK;
-    }
-    if (sp.splits < 2 || !vec || !grouped_ok(px, pw, sp.splits)) {
+    if (r.family == DCCN_FAMILY_TWO_LAUNCH) {
         DCCN_TRY(dense_bwd_w_impl(x, dy, dw, dbias, M, K, N, ws, ws_bytes, s, defer));
         return dense_bwd_x_impl(dy, w, dx, M, K, N, s);
     }
+    Carver c(ws, ws_bytes);
+    SlabWs sw;
+    if (!slab_carve(c, r.splits, K, N, &sw)) return DCCN_ERR_WORKSPACE;
+    pw.C = sw.slabs; pw.colsum = dbias ? sw.colsum : nullptr;
+    pw.klen = r.klen;
+    if (r.family == DCCN_FAMILY_GEMM16) {
+        if (r.splits == 1) { pw.C = dw; pw.colsum = dbias; }
+        DCCN_TRY(kDenseBwd16Launch[r.variant](px, pw, r.splits, s));
+        *defer = deferred_slabs(sw, dbias != nullptr, r.splits > 1);
+        return DCCN_OK;
+    }
     pw.ldc = N;
-    if (g_tune[TUNE_DENSE_BWD] == kVariantKmajor && kmajor_ok(pw)) {
-        if (split_done && split_dst && split_pairs_gc != 0 && (K % 4 == 0)) {
+    if (r.family == DCCN_FAMILY_GROUPED_BIG) {
+        if (r.splits == 1) { pw.C = dw; pw.colsum = dbias; pw.slab = 0; }
+        DCCN_TRY((launch_dense_bwd_grouped<true, 128, 128, 32>(px, pw, r.splits, s)));
+        *defer = deferred_slabs(sw, dbias != nullptr, r.splits > 1);
+        return DCCN_OK;
+    }
+    if (r.family == DCCN_FAMILY_GROUPED_KMAJOR) {
+        if (r.stage == STAGE_SPLIT_PAIRS) {
             // dx is the gradient of a concat of two IQ-pair streams: the stores write the two streams' own buffers
             // instead of dx (split_dst = stream 0, [M, K/2]; stream 1 split_pairs_gc elements further)
             px.C = split_dst; px.ldc = K / 2; px.gC = split_pairs_gc;
             *split_done = true;
-            DCCN_TRY((launch_dense_bwd_grouped_km<64, CMAP_SPLIT_PAIRS>(px, pw, sp.splits, s)));
-        } else if (actx != 1 && act_done && aux && g_tune[TUNE_EQ_EPILOGUES] >= 2) {
-            // element-wise stage of the caller's graph on the dX stores (as in the few-row grid above)
-            px.aux = aux;
-            *act_done = true;
-            if (actx == 3) DCCN_TRY((launch_dense_bwd_grouped_km<64, CMAP_TANHGRAD>(px, pw, sp.splits, s)));
-            else if (actx == 4) DCCN_TRY((launch_dense_bwd_grouped_km<64, CMAP_ADD>(px, pw, sp.splits, s)));
-            else return DCCN_ERR_INVALID_ARG;
-        } else {
-            DCCN_TRY(launch_dense_bwd_grouped_km<64>(px, pw, sp.splits, s));
+            DCCN_TRY((launch_dense_bwd_grouped_km<64, CMAP_SPLIT_PAIRS>(px, pw, r.splits, s)));
         }
-    } else DCCN_TRY(launch_dense_bwd_grouped<true>(px, pw, sp.splits, s));
+        else if (r.stage == STORE_TANHGRAD) DCCN_TRY((launch_dense_bwd_grouped_km<64, CMAP_TANHGRAD>(px, pw, r.splits, s)));
+        else if (r.stage == STORE_ADD) DCCN_TRY((launch_dense_bwd_grouped_km<64, CMAP_ADD>(px, pw, r.splits, s)));
+        else DCCN_TRY(launch_dense_bwd_grouped_km<64>(px, pw, r.splits, s));
+    } else DCCN_TRY(launch_dense_bwd_grouped<true>(px, pw, r.splits, s));
     *defer = deferred_slabs(sw, dbias != nullptr, true);
     return DCCN_OK;
 }
 
 // TUNE_CCONV_FWD 1-6: gemm16 tiles of the C-Conv forward
-constexpr Tile16Cfg kCconvFwd16[7] = {{},
+constexpr int kCconvFwd16Rows = 6;
+constexpr Tile16Cfg kCconvFwd16[kCconvFwd16Rows + 1] = {{},
     {2, 2, 1, 4, 32, 1},      // 32x128
     {1, 4, 2, 2, 32, 1},      // 32x128, wave 32x32
     {1, 4, 1, 2, 32, 1},      // 16x128
@@ -480,24 +587,32 @@ static int cconv_fwd16_launch(const GemmParams& p, hipStream_t s) {
 }
 constexpr int (*kCconvFwd16Launch[7])(const GemmParams&, hipStream_t) = {nullptr,
     cconv_fwd16_launch<1>, cconv_fwd16_launch<2>, cconv_fwd16_launch<3>, cconv_fwd16_launch<4>, cconv_fwd16_launch<5>, cconv_fwd16_launch<6>};
-int cconv_fwd_impl(const float* x, const float* w, const float* bias, float* out, int rows, int kin, int F,
-                          hipStream_t s, int ldx) {
-    if (!x || !w || !out || rows <= 0 || kin <= 0 || F <= 0) return DCCN_ERR_INVALID_ARG;
-    const GemmParams p = cconv_fwd_params(x, w, bias, out, rows, kin, F, ldx);
+// (a value past 11 runs the 32x32x2 family, as 0 does: no table is indexed with it)
+static Route cconv_fwd_route(const GemmParams& p, int kin) {
     const int variant = g_tune[TUNE_CCONV_FWD];
     const long long big = (long long)ceil_div(p.M, 128) * ceil_div(p.N, 128);
     // 7-11 (default 7): the staged whole-k tile of cconv_fwd.h (K = 160 / 128, i.e. N = 64 with / without the cyclic
     // prefix): bit-identical to the whole-k tile of gemm_f32_mfma.h it replaces; 8 / 9 = other LDS-store slots
     // 10 / 11: 32 x 128 tiles (every x row read by one block)
-    if (variant >= 7 && variant <= 11 && big < 2 * kCUs && cconv_fwd_staged_ok(p)) {
-        if (variant == 7) return launch_cconv_fwd_staged<8>(p, s);
-        if (variant == 8) return launch_cconv_fwd_staged<4>(p, s);
-        if (variant == 9) return launch_cconv_fwd_staged<10>(p, s);
-        if (variant == 10) return launch_cconv_fwd_staged<8, 32, 128>(p, s);
-        return launch_cconv_fwd_staged<4, 32, 128>(p, s);
+    if (variant >= 7 && variant <= 11 && big < 2 * kCUs && cconv_fwd_staged_ok(p))
+        return variant >= 10 ? route_of(DCCN_FAMILY_STAGED, variant, 32, 128, p.K) : route_of(DCCN_FAMILY_STAGED, variant, 64, 64, p.K);
+    if (variant >= 1 && variant <= kCconvFwd16Rows && vec_both(p) && big < 2 * kCUs && kin % 2 == 0)
+        return route16(DCCN_FAMILY_GEMM16, variant, kCconvFwd16[variant]);
+    return route_generic<OP_KCONTIG, OP_CCONV_W>(p);
+}
+int cconv_fwd_impl(const float* x, const float* w, const float* bias, float* out, int rows, int kin, int F,
+                          hipStream_t s, int ldx) {
+    if (!x || !w || !out || rows <= 0 || kin <= 0 || F <= 0) return DCCN_ERR_INVALID_ARG;
+    const GemmParams p = cconv_fwd_params(x, w, bias, out, rows, kin, F, ldx);
+    const Route r = cconv_fwd_route(p, kin);
+    if (r.family == DCCN_FAMILY_STAGED) switch (r.variant) {
+        case 7: return launch_cconv_fwd_staged<8>(p, s);
+        case 8: return launch_cconv_fwd_staged<4>(p, s);
+        case 9: return launch_cconv_fwd_staged<10>(p, s);
+        case 10: return launch_cconv_fwd_staged<8, 32, 128>(p, s);
+        default: return launch_cconv_fwd_staged<4, 32, 128>(p, s);
     }
-    if (variant >= 7) return launch_gemm<OP_KCONTIG, OP_CCONV_W, 0, TAG_CCONV_FWD>(p, 1, s);
-    if (variant > 0 && vec_both(p) && big < 2 * kCUs && kin % 2 == 0) return kCconvFwd16Launch[variant](p, s);      // (1 .. 6 here)
+    if (r.family == DCCN_FAMILY_GEMM16) return kCconvFwd16Launch[r.variant](p, s);
     return launch_gemm<OP_KCONTIG, OP_CCONV_W, 0, TAG_CCONV_FWD>(p, 1, s);
 }
 
@@ -546,7 +661,8 @@ __global__ __launch_bounds__(kGemmThreads) void cconv_bwd_w_km_finalize_kernel(c
 
 constexpr int kCconvBwMaxSplits = 128;
 // TUNE_CCONV_BWD_W 1-4: gemm16 tiles of the C-Conv weight gradient
-constexpr Tile16Cfg kCconvBw16[5] = {{},
+constexpr int kCconvBw16Rows = 4;
+constexpr Tile16Cfg kCconvBw16[kCconvBw16Rows + 1] = {{},
     {2, 2, 2, 2, 32, 1},      // 64x64
     {2, 2, 1, 2, 32, 1},      // 32x64
     {1, 4, 5, 2, 32, 1},      // 80x128
@@ -568,52 +684,73 @@ size_t cconv_bw_ws_bytes(int rows, int kin, int F) {
     return carved_bytes([&](Carver& c) { slab_carve(c, cconv_bw_capacity(rows, kin, F), 2 * kin, 2 * F, &w); });
 }
 
+// p.C = where the slabs will lie.  in_step: the training step's form -- the tail's slab reduction rides on the launch and the
+// optimizer launch folds the slabs; only it takes the gemm16 rows and the split count of knob 5.
+static int cconv_bwd_w_route(const GemmParams& p, int rows, int kin, int F, bool in_step, Route* out) {
+    const int variant = g_tune[TUNE_CCONV_BWD_W] == kVariantKmajor ? 0 : g_tune[TUNE_CCONV_BWD_W];
+    const bool small = 4LL * kin * F <= 512 * 512;
+    const bool v16 = variant > 0 && in_step && vec_both(p) && small;
+    if (v16) {
+        if (variant > kCconvBw16Rows) return DCCN_ERR_INVALID_ARG;       // (no such row)
+        int want = g_tune[TUNE_CCONV_BWD_SPLITS];
+        const Tile16Cfg c16 = kCconvBw16[variant];
+        const int tiles = ceil_div(2 * kin, c16.rows()) * ceil_div(2 * F, c16.cols());
+        if (want <= 0) want = (2 * kCUs + tiles - 1) / tiles;
+        if (want > kCconvBwMaxSplits) want = kCconvBwMaxSplits;
+        *out = with_split(route16(DCCN_FAMILY_GEMM16, variant, c16), plan_splitk_n(rows, want, c16.bk));
+        return DCCN_OK;
+    }
+    SplitPlan sp = plan_splitk(2 * kin, 2 * F, rows);
+    if (g_tune[TUNE_CCONV_BWD_SPLITS] > 0 && in_step && small) {
+        const int want = g_tune[TUNE_CCONV_BWD_SPLITS];
+        sp = plan_splitk_n(rows, want < kCconvBwMaxSplits ? want : kCconvBwMaxSplits, 64);
+    }
+    // (large outputs, e.g. N = 1024: the 32x32x2 form measured 0.7 % faster per step -- the k-major form pays off where
+    // the k-loops are short)
+    const bool km = g_tune[TUNE_CCONV_BWD_W] == kVariantKmajor && kmajor_ok(p) && ceil_div(p.N, 64) * ceil_div(p.M, 64) <= 2 * kCUs;
+    if (km) *out = with_split(route_of(DCCN_FAMILY_KMAJOR, 0, 64, 64, 64), sp);
+    // the step's own launch of the 32x32x2 family: 128 rows per split run as one k-tile
+    else if (in_step && vec_both(p)) *out = with_split(route_of(DCCN_FAMILY_GENERIC, 0, 64, 64, (sp.klen == 128 && g_whole_k) ? 128 : 64), sp);
+    else {
+        GemmParams q = p;
+        q.klen = sp.klen;
+        *out = route_generic<OP_ICONTIG, OP_ICONTIG>(q, sp.splits);
+    }
+    return DCCN_OK;
+}
 
 int cconv_bwd_w_impl(const float* x, const float* dout, float* dw, float* dbias, int rows, int kin, int F,
                             void* ws, size_t ws_bytes, hipStream_t s, const TailFinalizeArgs* fin,
                             FoldDefer* defer) {
     if (!x || !dout || !dw || rows <= 0 || kin <= 0 || F <= 0) return DCCN_ERR_INVALID_ARG;
     if (!ws || ws_bytes < cconv_bw_ws_bytes(rows, kin, F)) return DCCN_ERR_WORKSPACE;
-    const int variant = g_tune[TUNE_CCONV_BWD_W] == kVariantKmajor ? 0 : g_tune[TUNE_CCONV_BWD_W];
     GemmParams p = cconv_bwd_w_params(x, dout, rows, kin, F);
-    const bool v16 = variant > 0 && defer && fin && vec_both(p) && 4LL * kin * F <= 512 * 512;
-    if (v16 && variant > 4) return DCCN_ERR_INVALID_ARG;
-    SplitPlan sp = plan_splitk(2 * kin, 2 * F, rows);
-    if (!v16 && g_tune[TUNE_CCONV_BWD_SPLITS] > 0 && defer && fin && 4LL * kin * F <= 512 * 512) {
-        const int want = g_tune[TUNE_CCONV_BWD_SPLITS];
-        sp = plan_splitk_n(rows, want < kCconvBwMaxSplits ? want : kCconvBwMaxSplits, 64);
-    }
-    if (v16) {
-        int want = g_tune[TUNE_CCONV_BWD_SPLITS];
-        const Tile16Cfg c16 = kCconvBw16[variant];
-        const int tiles = ceil_div(2 * kin, c16.rows()) * ceil_div(2 * F, c16.cols());
-        if (want <= 0) want = (2 * kCUs + tiles - 1) / tiles;
-        if (want > kCconvBwMaxSplits) want = kCconvBwMaxSplits;
-        sp = plan_splitk_n(rows, want, c16.bk);
-    }
+    const bool in_step = defer && fin;
+    p.C = static_cast<float*>(ws);                  // (slab_carve's first piece lies at the head of the workspace)
+    Route r;
+    DCCN_TRY(cconv_bwd_w_route(p, rows, kin, F, in_step, &r));
+    const SplitPlan sp{r.splits, r.klen};
     Carver c(ws, ws_bytes);
     SlabWs sw;
     if (!slab_carve(c, sp.splits, 2 * kin, 2 * F, &sw)) return DCCN_ERR_WORKSPACE;
     float *slabs = sw.slabs, *cs = sw.colsum;
     p.C = slabs; p.colsum = cs;
     p.klen = sp.klen;
-    if (v16) {
-        DCCN_TRY(kCconvBw16Launch[variant](p, sp.splits, *fin, s));
+    if (r.family == DCCN_FAMILY_GEMM16) {
+        DCCN_TRY(kCconvBw16Launch[r.variant](p, sp.splits, *fin, s));
         *defer = fold_defer(sw);
         return DCCN_OK;
     }
-    if (defer && fin && vec_both(p)) {
+    if (in_step && vec_both(p)) {
         // fused step: GEMM + tail finalize in one launch; the fold happens inside the optimizer kernel
         const int tiles = ceil_div(p.N, 64) * ceil_div(p.M, 64), gemm_blocks = tiles * sp.splits;
         const dim3 grid(gemm_blocks + tail_finalize_blocks(fin->P));
-        // (large outputs, e.g. N = 1024: the 32x32x2 form measured 0.7 % faster per step -- the k-major form pays off where
-        // the k-loops are short)
-        if (g_tune[TUNE_CCONV_BWD_W] == kVariantKmajor && kmajor_ok(p) && tiles <= 2 * kCUs) {
+        if (r.family == DCCN_FAMILY_KMAJOR) {
             auto kern = cconv_bwd_w_km_finalize_kernel<64>;
             constexpr size_t smem = kmajor_smem_bytes<64>();
             DCCN_TRY(set_max_dynamic_smem(reinterpret_cast<const void*>(kern), smem));
             hipLaunchKernelGGL(kern, grid, dim3(kGemmThreads), smem, s, p, tiles, gemm_blocks, *fin);
-        } else if (sp.klen == 128 && g_whole_k) {
+        } else if (r.tile_k == 128) {
             // 128 rows per split: the whole k range of a block as one tile (all loads in flight at once, no k-tile barrier)
             auto kern = cconv_bwd_w_finalize_kernel<true, 128, 1>;
             constexpr size_t smem = gemm_smem_bytes<OP_ICONTIG, OP_ICONTIG, 64, 64, 128, 1>();
@@ -630,7 +767,7 @@ int cconv_bwd_w_impl(const float* x, const float* dout, float* dw, float* dbias,
         return DCCN_OK;
     }
     if (defer) defer->slabs = nullptr;
-    if (g_tune[TUNE_CCONV_BWD_W] == kVariantKmajor && kmajor_ok(p) && ceil_div(p.N, 64) * ceil_div(p.M, 64) <= 2 * kCUs)
+    if (r.family == DCCN_FAMILY_KMAJOR)
         DCCN_TRY((launch_kmajor<1, TAG_CCONV_BWD_W>(p, sp.splits, s)));
     else
         DCCN_TRY((launch_gemm<OP_ICONTIG, OP_ICONTIG, 1, TAG_CCONV_BWD_W>(p, sp.splits, s)));
@@ -749,6 +886,26 @@ static bool rx_bwd_fused_ok(int batch, int S, int kin, int F, int D, const float
     return (long long)ceil_div(dK, 128) * ceil_div(dN, 128) * sp.splits < 2 * kCUs;
 }
 
+// the dense dW items of the fused backward launch: pw as dense_bwd_w_params builds it, pw.C = where the slabs will lie.
+// route.splits = the slabs the launch writes; route.klen = the uniform plan's range length (what the items use unless
+// route.nranges > 0: then the graded ranges koff[0 .. nranges] of knob 14)
+static int rx_bwd_route(const GemmParams& pw, int batch, int dK, int dN, Route* out) {
+    if (!kmajor_ok(pw)) return DCCN_ERR_INVALID_ARG;
+    const SplitPlan sp = dense_dw_plan(batch, dK, dN, kFusedBwdRangeRows);
+    Route r = with_split(route_of(DCCN_FAMILY_RX_FUSED, 0, 64, 64, 64), sp);
+    r.w_tile_rows = r.w_tile_cols = 64;
+    if (g_tune[TUNE_DW_GRADED] > 0 && sp.splits > 1 && batch >= 768) {        // (>= 12 k-tiles: else the last ranges get too short)
+        int off[9];
+        const int n = graded_ranges(g_tune[TUNE_DW_GRADED], batch, off);
+        if (n > 1 && n <= max_splits16(dK, dN)) {
+            r.nranges = n; r.splits = n;
+            memcpy(r.koff, off, sizeof(int) * (n + 1));
+        }
+    }
+    *out = r;
+    return DCCN_OK;
+}
+
 // dfft nullable: the dX tiles then only feed their epilogue
 static int rx_bwd_fused_impl(const float* x_norm, const float* fft_out, const float* dz, const float* wd, float* dfft,
                              float* dbias_dense, int batch, int S, int kin, int F, int D, void* ws_dense, size_t ws_dense_bytes,
@@ -759,19 +916,19 @@ static int rx_bwd_fused_impl(const float* x_norm, const float* fft_out, const fl
     if (!ws_conv || ws_conv_bytes < rx_bwd_fused_ws_bytes(batch, S, kin, F)) return DCCN_ERR_WORKSPACE;
     GemmParams px = dense_bwd_x_params(dz, wd, dfft, batch, dK, dN);
     GemmParams pw = dense_bwd_w_params(fft_out, dz, batch, dK, dN);
-    if (!vec_both(pw)) return DCCN_ERR_INVALID_ARG;             // (rx_bwd_fused_ok asks for exactly these)
-    const SplitPlan sp = dense_dw_plan(batch, dK, dN, kFusedBwdRangeRows);
-    pw.klen = sp.klen;
-    int nsplit = sp.splits;
-    if (g_tune[TUNE_DW_GRADED] > 0 && sp.splits > 1 && batch >= 768) {        // (>= 12 k-tiles: else the last ranges get too short)
-        const int n = graded_ranges(g_tune[TUNE_DW_GRADED], batch, pw.koff);
-        if (n > 1 && n <= max_splits16(dK, dN)) { pw.nranges = n; nsplit = n; }
+    Route r;
+    pw.C = static_cast<float*>(ws_dense);           // (slab_carve's first piece lies at the head of the workspace)
+    DCCN_TRY(rx_bwd_route(pw, batch, dK, dN, &r));
+    pw.klen = r.klen;
+    const int nsplit = r.splits;
+    if (r.nranges > 0) {
+        pw.nranges = r.nranges;
+        memcpy(pw.koff, r.koff, sizeof(pw.koff));
     }
     Carver c(ws_dense, ws_dense_bytes);
     SlabWs sw;
     if (!slab_carve(c, nsplit, dK, dN, &sw)) return DCCN_ERR_WORKSPACE;
     pw.C = sw.slabs; pw.colsum = dbias_dense ? sw.colsum : nullptr;
-    if (!kmajor_ok(pw)) return DCCN_ERR_INVALID_ARG;
     Carver cc(ws_conv, ws_conv_bytes);
     const RxBwdWs cw = rx_bwd_fused_carve(cc, batch, S, kin, F);
     DweffArgs de;
@@ -1908,6 +2065,56 @@ int dccn_dense_tail_grid(int M, int K, int N, int nbits, int* grid, int* tile_ro
     if (tile_rows) *tile_rows = r.grid == DG_FEWROW ? 16 : (r.grid == DG_RAGGED || r.large) ? kDense80.rows() : kDense48.rows();
     if (ragged_rows) *ragged_rows = r.grid == DG_RAGGED ? r.rag : 0;
     if (blocks) *blocks = r.blocks;
+    return DCCN_OK;
+}
+// (the descriptions the *_impl functions build, on null -- 16-byte aligned -- inputs and a 16-byte aligned output address that
+// nothing dereferences: the few-row and k-major tiles ask for an output and its alignment)
+int dccn_gemm_route_query(int op, int d0, int d1, int d2, int d3, int d4, dccn_gemm_route* route) {
+    const TuneScope tune;
+    float* const out = reinterpret_cast<float*>(static_cast<uintptr_t>(256));
+    if (!route || d0 <= 0 || d1 <= 0 || d2 <= 0) return DCCN_ERR_INVALID_ARG;
+    Route r;
+    switch (op) {
+        case DCCN_ROUTE_DENSE_FWD:
+            DCCN_TRY(dense_fwd_route(dense_fwd_params(nullptr, nullptr, nullptr, out, d0, d1, d2), STORE_PLAIN, &r));
+            break;
+        case DCCN_ROUTE_DENSE_BWD_X:
+            DCCN_TRY(dense_bwd_x_route(dense_bwd_x_params(nullptr, nullptr, out, d0, d1, d2), &r));
+            break;
+        case DCCN_ROUTE_DENSE_BWD_W: {
+            const SplitPlan sp = dense_dw_plan(d0, d1, d2);
+            GemmParams p = dense_bwd_w_params(nullptr, nullptr, d0, d1, d2);
+            p.klen = sp.klen; p.C = out;
+            r = dense_bwd_w_route(p, sp);
+            break;
+        }
+        case DCCN_ROUTE_DENSE_BWD: {
+            GemmParams pw = dense_bwd_w_params(nullptr, nullptr, d0, d1, d2);
+            pw.C = out;
+            DCCN_TRY(dense_bwd_route(dense_bwd_x_params(nullptr, nullptr, out, d0, d1, d2), pw, d0, d1, d2, 1, false, &r));
+            break;
+        }
+        case DCCN_ROUTE_CCONV_FWD:
+            r = cconv_fwd_route(cconv_fwd_params(nullptr, nullptr, nullptr, out, d0, d1, d2), d1);
+            break;
+        case DCCN_ROUTE_CCONV_BWD_W: {
+            GemmParams p = cconv_bwd_w_params(nullptr, nullptr, d0, d1, d2);
+            p.C = out;
+            DCCN_TRY(cconv_bwd_w_route(p, d0, d1, d2, true, &r));
+            break;
+        }
+        case DCCN_ROUTE_RX_BACKWARD: {
+            if (d3 <= 0 || d4 <= 0 || !rx_bwd_fused_ok(d0, d1, d2, d3, d4, nullptr, nullptr, nullptr, nullptr)) return DCCN_ERR_INVALID_ARG;
+            const int dK = d1 * 2 * d3, dN = 2 * d4;
+            GemmParams pw = dense_bwd_w_params(nullptr, nullptr, d0, dK, dN);
+            if (!vec_both(pw)) return DCCN_ERR_INVALID_ARG;
+            pw.C = out;
+            DCCN_TRY(rx_bwd_route(pw, d0, dK, dN, &r));
+            break;
+        }
+        default: return DCCN_ERR_INVALID_ARG;
+    }
+    *route = r;
     return DCCN_OK;
 }
 int dccn_rx_dense_tail_fused(const dccn_rx_shape* sh, int train) {

@@ -724,24 +724,37 @@ static inline bool grouped_big_ok(const GemmParams& px, const GemmParams& pw, in
 
 // tile choice: 128x128x32 (four accumulators per wave) only when it still yields >= 2 blocks per CU,
 // else 64x64x64
-template <int KA, int KB, int COLSUM, int TAG>
-static int launch_gemm(const GemmParams& p, int splits, hipStream_t s) {
+struct GemmTile {
+    int bm, bn, bk;     // bk = K: the whole k range as one tile
+};
+// (decided once: launch_gemm issues the tile this names, the route query of dccn_abi.hip reports it)
+template <int KA, int KB>
+static inline GemmTile gemm_tile(const GemmParams& p, int splits) {
     const long long big = (long long)ceil_div(p.M, 128) * ceil_div(p.N, 128) * splits;
     // (an output of <= 64 columns or rows would leave half of every 128-wide tile empty)
-    if (big >= 2 * kCUs && p.N > 64 && p.M > 64) return launch_gemm_cfg<KA, KB, 128, 128, 32, COLSUM, TAG>(p, splits, s);
+    if (big >= 2 * kCUs && p.N > 64 && p.M > 64) return GemmTile{128, 128, 32};
     // the N=64 C-Conv forward (K = 2*(N+CP) = 160, or 128 without the cyclic prefix): the whole k range as ONE tile --
     // all of a block's loads are issued together (one exposed memory latency instead of five) and no k-tile barrier
     if constexpr (KA == OP_KCONTIG && KB == OP_CCONV_W) {
-        if (splits == 1 && p.vecA && p.vecB && g_whole_k) {
-            if (p.K == 160) return launch_gemm_cfg2<KA, KB, 64, 64, 160, COLSUM, TAG, true, 1>(p, splits, s);
-            if (p.K == 128) return launch_gemm_cfg2<KA, KB, 64, 64, 128, COLSUM, TAG, true, 1>(p, splits, s);
-        }
+        if (splits == 1 && p.vecA && p.vecB && g_whole_k && (p.K == 160 || p.K == 128)) return GemmTile{64, 64, p.K};
     }
     // short k ranges that are a multiple of 32 but not of 64 (the C-Conv: K = 2*(N+CP) = 160): 32-deep k-tiles keep
     // every tile on the fast unmasked loaders and do not multiply zeros in a half-empty last tile
     if constexpr (KA != OP_ICONTIG && KB != OP_ICONTIG) {
-        if (splits == 1 && p.K % 64 != 0 && p.K % 32 == 0 && p.K <= 512)
-            return launch_gemm_cfg<KA, KB, 64, 64, 32, COLSUM, TAG>(p, splits, s);
+        if (splits == 1 && p.K % 64 != 0 && p.K % 32 == 0 && p.K <= 512) return GemmTile{64, 64, 32};
+    }
+    return GemmTile{64, 64, 64};
+}
+template <int KA, int KB, int COLSUM, int TAG>
+static int launch_gemm(const GemmParams& p, int splits, hipStream_t s) {
+    const GemmTile t = gemm_tile<KA, KB>(p, splits);
+    if (t.bm == 128) return launch_gemm_cfg<KA, KB, 128, 128, 32, COLSUM, TAG>(p, splits, s);
+    if constexpr (KA == OP_KCONTIG && KB == OP_CCONV_W) {
+        if (t.bk == 160) return launch_gemm_cfg2<KA, KB, 64, 64, 160, COLSUM, TAG, true, 1>(p, splits, s);
+        if (t.bk == 128) return launch_gemm_cfg2<KA, KB, 64, 64, 128, COLSUM, TAG, true, 1>(p, splits, s);
+    }
+    if constexpr (KA != OP_ICONTIG && KB != OP_ICONTIG) {
+        if (t.bk == 32) return launch_gemm_cfg<KA, KB, 64, 64, 32, COLSUM, TAG>(p, splits, s);
     }
     return launch_gemm_cfg<KA, KB, 64, 64, 64, COLSUM, TAG>(p, splits, s);
 }

@@ -279,14 +279,27 @@ int dccn_metrics_table_set(const dccn_metrics* metrics, double* row6, dccn_strea
 /* Kernel-configuration knobs for experiments and profiling.  The table is a process-wide set of DEFAULTS; a call copies it once
  * when it begins (never mid-plan), and a plan that captured its own table (dccn_tuning_snapshot -> dccn_rx_buffers.tuning /
  * dccn_eq_buffers.tuning) is not affected by later changes at all.
- *  0 dense forward with the tail in its epilogue (> 0 on; 0: separate launches)      1 grouped dense backward (7 = k-major dW)
- *  2 C-Conv forward (7 = staged whole-k tile, default; 8-11 its other store slots / 32x128 tiles; 1-6 gemm16 tiles; 0 = 32x32x2)
- *  3 C-Conv weight gradient (7 = k-major)      4 / 5 split-K counts of the two weight gradients (0 = automatic)
- *  6 minimum LDS per block in KiB      7 single-tile launches for short k ranges (default 1)      8 skinny dispatch
+ *  0 dense forward with the tail in its epilogue (> 0 on; 0: separate launches)
+ *  1 grouped dense backward: 0 = 32x32x2 family; 1-6 = gemm16 dX / dW tile pairs (64x64 / 64x64, 48x64 / 64x64, 64x64 / 64x64
+ *    with 64-deep k-tiles, 96x64 / 64x64, 64x128 / 64x128, 64x64 / 64x128) for layers of more than 96 rows and fewer than
+ *    2 x CUs 128x128 tiles with vector-legal operands; 7 = k-major dW (default).  8 and above: DCCN_ERR_INVALID_ARG where a
+ *    table row would have run, elsewhere as 0
+ *  2 C-Conv forward: 0 = 32x32x2 family; 1-6 = gemm16 tiles (32x128, 32x128 with 32x32 waves, 16x128, 64x64, 16x128 on 8
+ *    waves, 32x64); 7 = staged whole-k tile (default), 8 / 9 its other store slots, 10 / 11 its 32x128 tiles.  12 and above: as 0
+ *  3 C-Conv weight gradient: 0 = 32x32x2 family; 1-4 = gemm16 tiles (64x64, 32x64, 80x128, 32x128), taken only by the receiver
+ *    step's own launch (outputs up to 512 x 512); 7 = k-major (default).  5, 6, 8 and above: the step returns
+ *    DCCN_ERR_INVALID_ARG where a table row would have run; dccn_cconv_gemm_bwd_w runs them as 0
+ *  4 / 5 split-K counts of the two weight gradients (0 = automatic; cut to the slab capacity: 8 / 128)
+ *  6 minimum LDS per block in KiB      7 single-tile launches for short k ranges (default 1)
+ *  8 GEMMs of at most 96 rows: 0 = as every other; 1-4 = skinny gemm16 tiles (16x64 = default, 32x64, 32x32, 16x64 on 8 waves)
+ *    where the few-row tiles of knob 21 do not apply; any value > 0 also enables those and the one-grid backward of knob 17.
+ *    5 and above: DCCN_ERR_INVALID_ARG where a skinny tile would have run
+ *  (dccn_gemm_route_query answers which of these a shape takes)
  *  9 grouped backward of large layers      10 gemm16 tiles for the un-fused dense forward
  * 11 C-Conv weight gradient in the epilogue of the dense dX tiles (default 1)      12 wave priority of those tiles
  * 13 fused dense + tail launch for 8-QAM / 16-QAM steps (bit 0 lane-per-cell forms, bit 1 quad-lane training form)
- * 14 graded k ranges of the dense weight-gradient items in the fused backward launch (presets 1-24, default 14 = {9,5,2,2,1}/19)
+ * 14 graded k ranges of the dense weight-gradient items in the fused backward launch (presets 1-24, default 14 = {9,5,2,2,1}/19;
+ *    0, 25 and above, or fewer than 768 frames: the uniform split plan)
  * 17 few-row dense backward as one grid (default 1)
  * 18 R0 of the next batch on the backward launch of double-buffered pipelined steps (default 0)
  * 19 equaliser step: element-wise stages in GEMM stores (1 few-row tiles, 2 = default: also larger batches)
@@ -320,6 +333,59 @@ int dccn_tuning_snapshot(int* table, int n);
  *                               DCCN_ERR_INVALID_ARG, outputs untouched, exactly where dccn_dense_tail_supported answers 0. */
 int dccn_dense_tail_supported(int M, int K, int N, int nbits);
 int dccn_dense_tail_grid(int M, int K, int N, int nbits, int* grid, int* tile_rows, int* ragged_rows, int* blocks);
+
+/* Which launch a stand-alone GEMM-shaped operator issues for a shape under the current knob table, with 16-byte aligned
+ * operands.  Host-only: launches nothing.  The operators decide their launch from the same route value this reports.
+ *   op, (d0 .. d4)                       operator
+ *   DCCN_ROUTE_DENSE_FWD     (M, K, N)               dccn_dense_fwd
+ *   DCCN_ROUTE_DENSE_BWD_X   (M, K, N)               dccn_dense_bwd_x
+ *   DCCN_ROUTE_DENSE_BWD_W   (M, K, N)               dccn_dense_bwd_w
+ *   DCCN_ROUTE_DENSE_BWD     (M, K, N)               dccn_dense_bwd / dccn_dense_bwd_slabs (grouped dX + dW)
+ *   DCCN_ROUTE_CCONV_FWD     (rows, kin, F)          dccn_cconv_gemm_fwd
+ *   DCCN_ROUTE_CCONV_BWD_W   (rows, kin, F)          the C-Conv weight gradient as the receiver's training step launches it (the
+ *                                                    tail's slab reduction rides on the launch, the optimizer launch folds the
+ *                                                    slabs); dccn_cconv_gemm_bwd_w itself never takes the gemm16 rows of knob 3
+ *   DCCN_ROUTE_RX_BACKWARD   (batch, S, kin, F, D)   dccn_rx_backward
+ * unused d's are ignored.  family:
+ *   DCCN_FAMILY_GENERIC         gemm_f32_mfma.h: 64x64 tiles, k-tiles 64 (or 32) deep, or the whole k range (tile_k = K) as
+ *                               one tile; 128x128x32 when that still gives two blocks per CU
+ *   DCCN_FAMILY_GEMM16          a row of the knob's gemm16 table (variant = the row; the 48x64 tiles of knob 10: variant 0)
+ *   DCCN_FAMILY_SKINNY          <= 96 rows: the small gemm16 tiles of knob 8 (variant 1-4).  DENSE_BWD: dX on 16x64 tiles and
+ *                               the unsplit dW on 64x64 tiles in one grid
+ *   DCCN_FAMILY_FEWROW          <= 96 rows: one-latency 16x16 tiles (tile_k = the k depth in 64-k slots x 64).  DENSE_BWD: dX
+ *                               on them and the unsplit dW in one grid
+ *   DCCN_FAMILY_KMAJOR          split-K weight gradient in the k-major form, 64x64 tiles
+ *   DCCN_FAMILY_STAGED          staged whole-k C-Conv forward (variant 7-11)
+ *   DCCN_FAMILY_GROUPED_BIG     DENSE_BWD: dX and dW on 128x128x32 tiles in one grid
+ *   DCCN_FAMILY_GROUPED_KMAJOR  DENSE_BWD: dX on 64x64x64 tiles and the k-major dW items in one grid
+ *   DCCN_FAMILY_GROUPED         DENSE_BWD: dX and dW on 64x64x64 tiles in one grid
+ *   DCCN_FAMILY_TWO_LAUNCH      DENSE_BWD: the DENSE_BWD_W route, then the DENSE_BWD_X route, as two launches
+ *   DCCN_FAMILY_RX_FUSED        the fused backward launch of rx_bwd.h
+ * tile_rows x tile_cols: the output tile (of dX where a grid holds both); w_tile_rows x w_tile_cols: the dW tile of a grouped
+ * grid, else 0; tile_k: k-tile depth; splits: k ranges of the weight gradient (1 elsewhere; > 1: slabs that a later launch
+ * sums); klen: length of a k range, the last one may be shorter (RX_BACKWARD with graded ranges: the uniform plan's, unused);
+ * nranges / koff: RX_BACKWARD with graded dW ranges (knob 14): their count (= splits) and the nranges + 1 offsets into the
+ * batch, else 0.
+ * Returns DCCN_ERR_INVALID_ARG, *route untouched, exactly where the operator refuses the shape or the knob value (a table-backed
+ * knob one past its last row where that row would have run). */
+enum {
+    DCCN_ROUTE_DENSE_FWD = 0, DCCN_ROUTE_DENSE_BWD_X = 1, DCCN_ROUTE_DENSE_BWD_W = 2, DCCN_ROUTE_DENSE_BWD = 3,
+    DCCN_ROUTE_CCONV_FWD = 4, DCCN_ROUTE_CCONV_BWD_W = 5, DCCN_ROUTE_RX_BACKWARD = 6
+};
+enum {
+    DCCN_FAMILY_GENERIC = 0, DCCN_FAMILY_GEMM16 = 1, DCCN_FAMILY_SKINNY = 2, DCCN_FAMILY_FEWROW = 3, DCCN_FAMILY_KMAJOR = 4,
+    DCCN_FAMILY_STAGED = 5, DCCN_FAMILY_GROUPED_BIG = 6, DCCN_FAMILY_GROUPED_KMAJOR = 7, DCCN_FAMILY_GROUPED = 8,
+    DCCN_FAMILY_TWO_LAUNCH = 9, DCCN_FAMILY_RX_FUSED = 10
+};
+typedef struct dccn_gemm_route {
+    int family, variant;
+    int tile_rows, tile_cols, tile_k;
+    int w_tile_rows, w_tile_cols;
+    int splits, klen;
+    int nranges, koff[9];
+    int stage;          /* element-wise stage riding in the stores (the equaliser step's calls); the query: always 1 = none */
+} dccn_gemm_route;
+int dccn_gemm_route_query(int op, int d0, int d1, int d2, int d3, int d4, dccn_gemm_route* route);
 
 /* ---- R7: optimizer -----------------------------------------------------------------
  * dev/py/ofdmreceiver_np.py:185-189  exponential_decay(1e-3, step, 500, 0.98, staircase)

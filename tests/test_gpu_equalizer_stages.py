@@ -207,29 +207,51 @@ WS_NAMES = ("x_norm", "ln", "t1", "y", "d1", "d2", "d3", "d4", "eq", "corr", "ca
             "dy", "dh", "dd4", "dd3", "dd2", "dflat", "dt1")
 
 
-@pytest.mark.parametrize("nbits,B,plan", [(2, 73, 1), (2, 12, 1), (2, 200, 1), (4, 73, 1), (2, 73, 0), (2, 73, 3), (2, 200, 0),
-                                          (1, 73, 1)])
-def test_fused_step_stage_by_stage_at_1e5(nbits, B, plan):
+def _case(nbits, B, plan, knobs=None):
+    """(a case without knobs keeps the id it always had: nbits-B-plan)"""
+    knobs = dict(knobs or {})
+    return pytest.param(nbits, B, plan, knobs, id="-".join(["%d-%d-%d" % (nbits, B, plan)] + ["k%d=%d" % kv for kv in sorted(knobs.items())]))
+
+
+# knobs (all on the shipped plan): 21 = 0: the skinny 16x64 tiles carry the tanh / equalise stages, the few-row dense backward
+# runs launch_dense_bwd16 with the tanh-gradient / add stage; with 19 = 0 the stages are launches of their own; 17 = 0: dX and
+# dW of the few-row backward as two launches; 8 = 0: no skinny / few-row tiles at all; 24: the Adam riders of the bottleneck
+# backward launch; at 200 frames 19 = 1 / 0: the k-major grouped launch without the tanh-gradient / add column maps
+@pytest.mark.parametrize("nbits,B,plan,knobs", [
+    _case(2, 73, 1), _case(2, 12, 1), _case(2, 200, 1), _case(4, 73, 1), _case(2, 73, 0), _case(2, 73, 3), _case(2, 200, 0), _case(1, 73, 1),
+    _case(2, 73, 1, {21: 0}), _case(2, 73, 1, {21: 0, 19: 0}), _case(2, 73, 1, {17: 0}), _case(2, 73, 1, {8: 0}),
+    _case(2, 73, 1, {24: 0}), _case(2, 73, 1, {24: 2}), _case(2, 73, 1, {24: 3}), _case(2, 73, 1, {24: 4}),
+    _case(2, 200, 1, {19: 1}), _case(2, 200, 1, {19: 0})])
+def test_fused_step_stage_by_stage_at_1e5(nbits, B, plan, knobs):
     """plan = tuning key 20: 1 the shipped launch plan (few-row tiles, fused pilot bottleneck, grouped C-Conv pairs, job-table
     optimizer launch), 0 the launch-per-stage plan, 3 the re-plan without the fused bottleneck; 73 frames = the reference's
-    training batch (few-row kernels, folded receiver), 200 = split-K gradients, 12 = direct ones."""
+    training batch (few-row kernels, folded receiver), 200 = split-K gradients, 12 = direct ones.  knobs: further tuning keys,
+    set before the trainer builds its plan and put back whatever happens."""
     from dl_ofdm_amd import _lib
     lib = _lib.load()
-    F, tx, ecfg, rcfg, pe, pr, tr = _trainer(nbits, B, seed=51 + B)
-    rng = np.random.RandomState(300 + B + nbits)
-    x = (rng.standard_normal((B, ecfg.S, ecfg.n_sc, 2)) * 2).astype(np.float32)
-    bits = rng.randint(0, 2, (B, tx.frame_size, nbits)).astype(np.int32)
-    shp = E.param_shapes(ecfg)
-    P = {n: a.astype(np.float64).reshape(shp[n]) for n, a in tr.get_params().items()}     # the step's own parameters
+    saved = {k: lib.dccn_get_tuning(k) for k in knobs}
     try:
-        assert lib.dccn_set_tuning(20, plan) == 0
-        tr.train_step(x, bits, fused=True, graph=False)
-        torch.cuda.synchronize()
+        for k, val in knobs.items():
+            assert lib.dccn_set_tuning(k, val) == 0, (k, val)
+        F, tx, ecfg, rcfg, pe, pr, tr = _trainer(nbits, B, seed=51 + B)
+        rng = np.random.RandomState(300 + B + nbits)
+        x = (rng.standard_normal((B, ecfg.S, ecfg.n_sc, 2)) * 2).astype(np.float32)
+        bits = rng.randint(0, 2, (B, tx.frame_size, nbits)).astype(np.int32)
+        shp = E.param_shapes(ecfg)
+        P = {n: a.astype(np.float64).reshape(shp[n]) for n, a in tr.get_params().items()}     # the step's own parameters
+        try:
+            assert lib.dccn_set_tuning(20, plan) == 0
+            tr.train_step(x, bits, fused=True, graph=False)
+            torch.cuda.synchronize()
+        finally:
+            lib.dccn_set_tuning(20, 1)
+        pl = tr._plan(B)
+        G = {n: a.astype(np.float64).reshape(shp[n]) for n, a in tr.get_grads().items()}      # without the L2 term (reg_coef)
+        v = {n: _ws(tr, pl, n) for n in WS_NAMES}
     finally:
-        lib.dccn_set_tuning(20, 1)
-    pl = tr._plan(B)
-    G = {n: a.astype(np.float64).reshape(shp[n]) for n, a in tr.get_grads().items()}      # without the L2 term (reg_coef)
-    v = {n: _ws(tr, pl, n) for n in WS_NAMES}
+        for k, val in saved.items():
+            lib.dccn_set_tuning(k, val)
+    assert all(lib.dccn_get_tuning(k) == val for k, val in saved.items())
     v["x"] = x
     v["h"] = pl.chest.detach().cpu().numpy().astype(np.float64)
     v["out_eq"] = pl.out_eq.detach().cpu().numpy().astype(np.float64)
