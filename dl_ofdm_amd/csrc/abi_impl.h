@@ -3,6 +3,7 @@
 //   dccn_abi_eq.hip     the equaliser step (eq_step.h: its plan, then the phases that issue it), chain groups, equaliser stage operators, monitors
 //   dccn_abi_gen.hip    device-side generator, classical receivers, in-graph AWGN branch
 //   dccn_abi_conv.hip   general-k complex convolutions (patch gather, implicit GEMMs, few-channel kernels), CRC32C
+//   dccn_abi_sync.hip   per-frame timing alignment from the cyclic prefix (frame_sync.h; needs common.h only)
 // Kernels live in the headers; a non-template kernel is `static`, so a unit compiles only the kernels it launches.
 #pragma once
 #include <math.h>

@@ -1,0 +1,53 @@
+// libdccn.so -- per-frame timing alignment from the cyclic prefix (see abi_impl.h for how the library is cut into units)
+#include <math.h>
+
+#include "common.h"
+#include "frame_sync.h"
+
+using namespace dccn;
+
+namespace {
+// Everything a call decides, before its one launch: a refused call launches nothing.
+struct FrameSyncPlan {
+    FrameSyncArgs args;
+    unsigned blocks;
+    size_t lds;
+};
+
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+int frame_sync_plan(const float* x, int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset,
+                    float* metric, FrameSyncPlan* plan) {
+    if (!frame_sync_shape_ok(S, K, CP, W) || frames <= 0 || !x || !offset) return DCCN_ERR_INVALID_ARG;
+    if (out_kin != K + CP && out_kin != K) return DCCN_ERR_INVALID_ARG;
+    if (!aligned16(x) || !aligned16(x_out) || !aligned16(metric)) return DCCN_ERR_INVALID_ARG;
+    const int T = S * (K + CP);
+    // the cropped rows leave as 16-byte stores too: S * K complex samples per frame, an even count
+    if (x_out && out_kin == K && (S * K) % 2 != 0) return DCCN_ERR_INVALID_ARG;
+    if (x_out && ranges_overlap(x, (size_t)frames * T * 8, x_out, (size_t)frames * S * out_kin * 8)) return DCCN_ERR_INVALID_ARG;
+    plan->args = FrameSyncArgs{x, x_out, offset, metric, frames, S, K, CP, W, out_kin == K ? 1 : 0};
+    plan->blocks = (unsigned)ceil_div(frames, kSyncWaves);
+    plan->lds = kSyncWaves * frame_sync_lds_per_frame(T);
+    return DCCN_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int dccn_frame_sync_supported(int S, int K, int CP, int W) { return frame_sync_shape_ok(S, K, CP, W) ? 1 : 0; }
+
+int dccn_frame_sync(const float* x, int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset,
+                    float* metric, dccn_stream_t stream) {
+    FrameSyncPlan plan;
+    DCCN_TRY(frame_sync_plan(x, frames, S, K, CP, W, out_kin, x_out, offset, metric, &plan));
+    DCCN_TRY(set_max_dynamic_smem((const void*)frame_sync_kernel, plan.lds));
+    hipLaunchKernelGGL(frame_sync_kernel, dim3(plan.blocks), dim3(kSyncWaves * kSyncLanes), plan.lds, (hipStream_t)stream,
+                       plan.args);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,125 @@
+// Per-frame timing alignment from the cyclic prefix (dccn_frame_sync).
+//
+// A frame is T = S * (K + CP) complex samples y[n], taken as circular (indices mod T).  With N = K + CP:
+//     p[n] = y[n] * conj(y[n + K])                  e[n] = (|y[n]|^2 + |y[n + K]|^2) / 2
+//     Gamma(t) = sum_{s < S} sum_{n < CP} p[s N + t + n]      Phi(t) likewise over e
+//     Lambda(t) = |Gamma(t)| - Phi(t)               (<= 0: the rho = 1 form of the ML cyclic-prefix estimator)
+//     offset = the smallest t in [-W, W] with the largest Lambda(t);  aligned[n] = y[(n + offset) mod T]
+//
+// One wave per frame, four frames per 256-thread block; no atomics, no workspace, every sum in a fixed order (two runs give
+// the same bits).  The frame is read once (16-byte loads) into the wave's own LDS region, every later step reads LDS, and the
+// rotated frame leaves with 16-byte stores: the traffic of the copy the launch stands in for.
+#pragma once
+#include "common.h"
+
+namespace dccn {
+
+constexpr int kSyncWaves = 4;               // frames per block
+constexpr int kSyncLanes = 64;              // one lane per j in [-W, W + CP): 2 W + CP <= 64
+constexpr size_t kSyncLdsMax = 64 * 1024;   // a block's LDS (set_max_dynamic_smem raises the kernel's limit past 48 KB)
+
+// LDS of one frame: T complex samples, then (P.re, P.im, E, -) per j
+__host__ __device__ static inline size_t frame_sync_lds_per_frame(int T) { return (size_t)T * 8 + (size_t)kSyncLanes * 16; }
+
+static inline bool frame_sync_shape_ok(int S, int K, int CP, int W) {
+    if (S < 1 || K < 1 || CP < 1 || W < 1 || W > CP || 2 * W + CP > kSyncLanes) return false;
+    const long long T = (long long)S * ((long long)K + CP);
+    if (T % 2 != 0 || T > (1 << 20)) return false;
+    return kSyncWaves * frame_sync_lds_per_frame((int)T) <= kSyncLdsMax;
+}
+
+struct FrameSyncArgs {
+    const float* x;     // [frames, T, 2]
+    float* x_out;       // nullable: [frames, S, out_kin, 2]
+    int32_t* offset;    // [frames]
+    float* metric;      // nullable: [frames, 2 W + 1]
+    int frames, S, K, CP, W;
+    int crop;           // 1: x_out rows are the K samples behind each symbol's prefix (out_kin == K)
+};
+
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) frame_sync_kernel(const FrameSyncArgs a) {
+    extern __shared__ float4 sync_lds[];
+    const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
+    const int N = a.K + a.CP, T = a.S * N, W = a.W;
+    const long long f = (long long)blockIdx.x * kSyncWaves + wave;
+    const bool live = f < a.frames;          // (a ragged last block: the wave still meets the block's barriers)
+    float4* const region = sync_lds + (size_t)wave * (frame_sync_lds_per_frame(T) / 16);
+    float2* const y = reinterpret_cast<float2*>(region);
+    float4* const pe = region + T / 2;
+
+    // 1. the frame, once, into LDS
+    if (live) {
+        const float4* src = reinterpret_cast<const float4*>(a.x + (size_t)f * T * 2);
+        for (int i = lane; i < T / 2; i += kSyncLanes) region[i] = src[i];
+    }
+    __syncthreads();
+
+    // 2. P[j], E[j] for j = lane - W in [-W, W + CP): the S symbols in order
+    if (live && lane < 2 * W + a.CP) {
+        float pr = 0.f, pi = 0.f, e = 0.f;
+        int n = (lane - W + T) % T;                     // (W <= CP < T)
+        for (int s = 0; s < a.S; ++s) {
+            const float2 u = y[n], v = y[(n + a.K) % T];
+            pr += u.x * v.x + u.y * v.y;
+            pi += u.y * v.x - u.x * v.y;
+            e += 0.5f * ((u.x * u.x + u.y * u.y) + (v.x * v.x + v.y * v.y));
+            n = (n + N) % T;
+        }
+        pe[lane] = make_float4(pr, pi, e, 0.f);
+    }
+    __syncthreads();
+
+    // 3. one lane per candidate t = lane - W: its CP terms in order
+    float lam = -INFINITY;
+    if (live && lane <= 2 * W) {
+        float gr = 0.f, gi = 0.f, phi = 0.f;
+        for (int n = 0; n < a.CP; ++n) {
+            const float4 t = pe[lane + n];
+            gr += t.x;
+            gi += t.y;
+            phi += t.z;
+        }
+        lam = sqrtf(gr * gr + gi * gi) - phi;
+        if (a.metric) a.metric[(size_t)f * (2 * W + 1) + lane] = lam;
+    }
+
+    // 4. the wave's maximum, the smallest candidate on ties (every lane takes part; lanes past 2 W hold -inf)
+    int best = lane;
+    for (int d = 1; d < kSyncLanes; d <<= 1) {
+        const float ol = __shfl_xor(lam, d);
+        const int ob = __shfl_xor(best, d);
+        if (ol > lam || (ol == lam && ob < best)) {
+            lam = ol;
+            best = ob;
+        }
+    }
+    // lane 0's view, for every lane; kept inside the candidates whatever the samples were (NaN compares false everywhere)
+    best = __shfl(best, 0);
+    best = best < 0 ? 0 : (best > 2 * W ? 2 * W : best);
+    const int theta = best - W;
+    if (!live) return;
+    if (lane == 0) a.offset[f] = theta;
+
+    // 5. the rotated frame from LDS: two complex samples per 16-byte store, each read at its own (shifted) place
+    if (a.x_out) {
+        const int rot = (theta + T) % T;
+        if (a.crop) {
+            const int M = a.S * a.K;
+            float4* dst = reinterpret_cast<float4*>(a.x_out + (size_t)f * M * 2);
+            for (int i = lane; i < M / 2; i += kSyncLanes) {
+                const int m0 = 2 * i, m1 = 2 * i + 1;
+                const float2 u = y[((m0 / a.K) * N + a.CP + m0 % a.K + rot) % T];
+                const float2 v = y[((m1 / a.K) * N + a.CP + m1 % a.K + rot) % T];
+                dst[i] = make_float4(u.x, u.y, v.x, v.y);
+            }
+        } else {
+            float4* dst = reinterpret_cast<float4*>(a.x_out + (size_t)f * T * 2);
+            for (int i = lane; i < T / 2; i += kSyncLanes) {
+                const float2 u = y[(2 * i + rot) % T], v = y[(2 * i + 1 + rot) % T];
+                dst[i] = make_float4(u.x, u.y, v.x, v.y);
+            }
+        }
+    }
+}
+
+}  // namespace dccn

@@ -61,8 +61,10 @@ def unpack_bits(packed, D: int, nbits: int) -> np.ndarray:
 class ReceiveResult:
     """Device tensors of one receive call (they are the receiver's resident buffers: the next call overwrites them)."""
 
-    def __init__(self, packed: torch.Tensor, llr: Optional[torch.Tensor], prob: Optional[torch.Tensor], D: int, nbits: int):
+    def __init__(self, packed: torch.Tensor, llr: Optional[torch.Tensor], prob: Optional[torch.Tensor], D: int, nbits: int,
+                 offset: Optional[torch.Tensor] = None):
         self.packed, self.llr, self.prob, self.D, self.nbits = packed, llr, prob, int(D), int(nbits)
+        self.offset = offset        # int32 [frames]: the timing offsets of a call with sync > 0 (None otherwise)
 
     def bits(self) -> torch.Tensor:
         """``uint8 [frames, D, nbits]``, unpacked on the device."""
@@ -81,8 +83,13 @@ class RxReceiver:
     """
 
     def __init__(self, dims: RxDims, batch: int, params: Optional[Dict[str, np.ndarray]] = None, device="cuda",
-                 want_llr: bool = False, want_prob: bool = False, seed: int = 1):
+                 want_llr: bool = False, want_prob: bool = False, seed: int = 1, CP: Optional[int] = None):
+        """``CP``: the frames' cyclic-prefix length, for ``receive(x, sync=W)`` of a receiver that takes whole symbols
+        (``dims.kin == K + CP``: K cannot be read off the shape).  A ``cp=False`` receiver (``dims.kin == K``) finds it from
+        the frames it is given."""
         self.lib = _lib.load()
+        self.CP = None if CP is None else int(CP)
+        self._syncs: Dict[tuple, object] = {}
         self.dims, self.batch = dims, int(batch)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -124,28 +131,71 @@ class RxReceiver:
     def close_graph(self):
         """(nothing captured: lets a :class:`~dl_ofdm_amd.session.Session` keep receivers next to its engines)"""
 
-    def receive(self, x=None) -> ReceiveResult:
-        """Stage ``x`` (``None``: whatever ``self.x`` holds) and run one receive step on the current stream."""
-        if x is not None:
+    def _frame_sync(self, n_sc: int, W: int):
+        """the alignment stage for full frames of ``n_sc`` samples per symbol, writing this receiver's ``x``"""
+        from .sync import FrameSync
+        kin = self.dims.kin
+        if self.CP is not None:
+            CP = self.CP
+        elif n_sc > kin:
+            CP = n_sc - kin
+        else:
+            raise _lib.DccnError("receive(sync=W) of a receiver that takes whole symbols needs RxReceiver(..., CP=...)")
+        K = n_sc - CP
+        if kin not in (n_sc, K):
+            raise _lib.DccnError("receive(sync=W): frames of %d samples per symbol (CP = %d) do not fit kin = %d" % (n_sc, CP, kin))
+        key = (K, CP, W)
+        if key not in self._syncs:
+            self._syncs[key] = FrameSync(self.dims.S, K, CP, W, self.batch, self.device, out_kin=kin, want_metric=False)
+        return self._syncs[key]
+
+    def receive(self, x=None, sync: int = 0) -> ReceiveResult:
+        """Stage ``x`` (``None``: whatever ``self.x`` holds) and run one receive step on the current stream.
+
+        ``sync = W > 0``: ``x`` is a device tensor of FULL frames ``[batch, S, K + CP, 2]`` that may sit up to ``W`` samples off
+        the FFT window.  The alignment launch (:class:`~dl_ofdm_amd.sync.FrameSync`) takes the place of the copy: it writes
+        each frame, rotated by its own estimated offset, straight into ``self.x`` (only the K samples behind each prefix when
+        ``dims.kin == K``); the receive step behind it is unchanged.  ``result.offset`` holds the offsets."""
+        offset = None
+        if sync:
+            if not isinstance(x, torch.Tensor) or x.dim() != 4:
+                raise _lib.DccnError("receive(sync=W) takes a device tensor [batch, S, K + CP, 2]")
+            _, offset = self._frame_sync(int(x.shape[2]), int(sync)).run(x, out=self.x)
+        elif x is not None:
             self.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(self.x.shape), non_blocking=True)
         check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
-        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits)
+        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset)
 
 
-def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False) -> ReceiveResult:
+def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: int = 0) -> ReceiveResult:
     """Equaliser + frozen receiver chain (``EqualizerTrainer.receive``): ``dccn_eq_receive_step`` on the trainer's resident
-    plan of this batch size.  ``out_eq`` / ``chest`` of the plan hold what ``eval_step`` writes for the same frames."""
+    plan of this batch size.  ``out_eq`` / ``chest`` of the plan hold what ``eval_step`` writes for the same frames.
+
+    ``sync = W > 0``: as :meth:`RxReceiver.receive` -- ``x`` is a device tensor ``[batch, S, K + CP, 2]``, and the alignment
+    launch writes the rotated frames into the plan's ``x`` in place of the copy; ``result.offset`` holds the offsets."""
     if not tr.fused_ok:
         raise _lib.DccnError("the chain's receive path needs the fused equaliser step")
     batch = int(x.shape[0]) if isinstance(x, torch.Tensor) else int(np.shape(x)[0])
     pl = tr.resident(batch)
-    pl.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(pl.x.shape), non_blocking=True)
+    offset = None
+    if sync:
+        from .sync import FrameSync
+        syncs = pl.__dict__.setdefault("_frame_syncs", {})
+        if int(sync) not in syncs:
+            o = tr.ofdmobj
+            syncs[int(sync)] = FrameSync(int(tr.FLAGS.nsymbol), int(o.K), int(o.CP), int(sync), batch, tr.device, want_metric=False)
+        _, offset = syncs[int(sync)].run(x, out=pl.x)
+    else:
+        pl.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(pl.x.shape), non_blocking=True)
     packed, llr, prob = pl.receive(want_llr, want_prob)
-    return ReceiveResult(packed, llr, prob, int(tr.ofdmobj.frame_size), int(tr.FLAGS.nbits))
+    return ReceiveResult(packed, llr, prob, int(tr.ofdmobj.frame_size), int(tr.FLAGS.nbits), offset)
 
 
 def group_receive(group, xs) -> list:
     """Several links' chains in ONE launch sequence (``dccn_eq_receive_step_grouped``): ``group`` is a
     :class:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup`, ``xs`` one ``[batch, S, K + CP, 2]`` batch of frames per chain.
-    One :class:`ReceiveResult` per chain, bit for bit what :func:`chain_receive` returns for that chain alone."""
+    One :class:`ReceiveResult` per chain, bit for bit what :func:`chain_receive` returns for that chain alone.
+
+    The grouped call has no ``sync`` argument: a caller whose links need timing alignment keeps one
+    :class:`~dl_ofdm_amd.sync.FrameSync` per link and aligns each link's frames in front of this call."""
     return group.receive(xs)

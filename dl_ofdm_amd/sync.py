@@ -1,0 +1,84 @@
+"""Per-frame timing alignment from the cyclic prefix (``dccn_frame_sync``; include/dccn.h).
+
+The receive path takes frames that sit on the FFT window.  The centred L-tap response of the LTE profiles makes a frame arrive
+``(L - 1) // 2`` samples early (datagen.py), and ``align_window`` undoes that on the generator side with the KNOWN advance.
+:class:`FrameSync` is the receiver-side stage: every frame's prefix samples repeat K samples later, and the lag in ``[-W, W]`` at
+which they correlate best is the frame's own timing -- per frame, so it also serves channels whose advance differs from frame to
+frame (``mixRayleigh``).  The frame is taken as circular, exactly as ``align_window``'s ``torch.roll`` treats it:
+``aligned[f] = torch.roll(x[f].view(T, 2), -offset[f], 0)``.
+
+There is no CPU or PyTorch fallback: an unsupported shape or a tensor that is not on the GPU raises :class:`DccnError`.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+from ._lib import DccnError, check
+
+
+class FrameSync:
+    """Fixed-shape alignment stage on one GPU: ``run(x) -> (aligned, offset)``.
+
+    ``x``: device tensor ``float32 [frames, S, K + CP, 2]``.  ``out_kin``: ``K + CP`` (default: the aligned frames) or ``K`` (the
+    ``K`` samples behind each symbol's prefix, the input of a receiver built with ``cp=False``).  ``offset`` (``int32
+    [frames]``), ``metric`` (``float32 [frames, 2 W + 1]``: the estimator's value at the lags ``-W .. W``) and the output
+    buffer are resident: the next ``run`` overwrites them.
+    """
+
+    def __init__(self, S: int, K: int, CP: int, W: int, frames: int, device="cuda", out_kin: Optional[int] = None,
+                 want_metric: bool = True):
+        self.lib = _lib.load()
+        self.S, self.K, self.CP, self.W, self.frames = int(S), int(K), int(CP), int(W), int(frames)
+        self.out_kin = self.K + self.CP if out_kin is None else int(out_kin)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise DccnError("FrameSync needs a CUDA (ROCm) device; there is no CPU fallback")
+        if not self.lib.dccn_frame_sync_supported(self.S, self.K, self.CP, self.W):
+            raise DccnError("dccn_frame_sync_supported refused S=%d K=%d CP=%d W=%d (needs 1 <= W <= CP, 2 W + CP <= 64, an even "
+                            "frame length)" % (self.S, self.K, self.CP, self.W))
+        if self.out_kin not in (self.K + self.CP, self.K) or self.frames <= 0:
+            raise DccnError("FrameSync: out_kin must be K + CP or K and frames positive (got out_kin=%d, frames=%d)"
+                            % (self.out_kin, self.frames))
+        self.offset = torch.zeros(self.frames, dtype=torch.int32, device=self.device)
+        self.metric = (torch.zeros(self.frames, 2 * self.W + 1, dtype=torch.float32, device=self.device) if want_metric else None)
+        self.out = None         # allocated by the first run() that is not given a destination
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _device_frames(self, x) -> torch.Tensor:
+        if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+            raise DccnError("FrameSync.run takes a device tensor; there is no CPU fallback")
+        want = (self.frames, self.S, self.K + self.CP, 2)
+        if x.dtype != torch.float32 or tuple(x.shape) != want or not x.is_contiguous():
+            raise DccnError("FrameSync.run: x must be a contiguous float32 %r tensor, got %s %r" % (want, x.dtype, tuple(x.shape)))
+        return x
+
+    def run(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Estimate every frame's offset and write the aligned frames to ``out`` (``None``: this object's own buffer), on the
+        current stream.  ``out`` must not overlap ``x``."""
+        x = self._device_frames(x)
+        want = (self.frames, self.S, self.out_kin, 2)
+        if out is None:
+            if self.out is None:
+                self.out = torch.empty(*want, dtype=torch.float32, device=self.device)
+            out = self.out
+        elif (not isinstance(out, torch.Tensor) or out.device != x.device or out.dtype != torch.float32
+              or tuple(out.shape) != want or not out.is_contiguous()):
+            raise DccnError("FrameSync.run: out must be a contiguous float32 %r tensor on %s" % (want, x.device))
+        check(self.lib.dccn_frame_sync(x.data_ptr(), self.frames, self.S, self.K, self.CP, self.W, self.out_kin, out.data_ptr(),
+                                       self.offset.data_ptr(), None if self.metric is None else self.metric.data_ptr(),
+                                       self._stream()), "dccn_frame_sync")
+        return out, self.offset
+
+    def offsets(self, x: torch.Tensor) -> torch.Tensor:
+        """The offsets alone (no frame is written)."""
+        x = self._device_frames(x)
+        check(self.lib.dccn_frame_sync(x.data_ptr(), self.frames, self.S, self.K, self.CP, self.W, self.out_kin, None,
+                                       self.offset.data_ptr(), None if self.metric is None else self.metric.data_ptr(),
+                                       self._stream()), "dccn_frame_sync")
+        return self.offset

@@ -1001,6 +1001,28 @@ int dccn_channel_groups_awgn(const float* tx, const dccn_channel_group* groups /
                              float* noise_power, int frames, unsigned long long seed, unsigned offset,
                              void* workspace, size_t workspace_bytes, dccn_stream_t stream);
 
+/* ==== per-frame timing alignment from the cyclic prefix =========================
+ * The receive path (dccn_rx_receive_step, dccn_eq_receive_step) takes frames that sit on the FFT window; this stage puts
+ * them there.  A frame is T = S*(K+CP) complex samples y[n], taken as CIRCULAR (indices mod T, as a torch.roll of the frame
+ * treats it).  With N = K+CP:
+ *     p[n] = y[n] * conj(y[n+K])                 e[n] = (|y[n]|^2 + |y[n+K]|^2) / 2
+ *     Gamma(t) = sum_{s<S} sum_{n<CP} p[s*N + t + n]          Phi(t) likewise over e
+ *     Lambda(t) = |Gamma(t)| - Phi(t)            (<= 0: the rho = 1 form of the ML cyclic-prefix estimator)
+ *     offset = the smallest t in [-W, W] with the largest Lambda(t)            aligned[n] = y[(n + offset) mod T]
+ * x [frames,S,K+CP,2]; offset int32[frames]; metric [frames, 2W+1] nullable = Lambda(-W .. W);
+ * x_out nullable (offsets only), [frames,S,out_kin,2]: out_kin == K+CP the aligned frame, out_kin == K its samples behind each
+ * symbol's prefix (x_out[f,s,0:K] = aligned_f[s, CP:CP+K], the input of a receiver built with cp = False).
+ * One launch, no workspace, no atomics; every sum runs in a fixed order, so two runs give the same bits.  x is read once and
+ * x_out written once.
+ * dccn_frame_sync_supported (host only): 1 exactly where dccn_frame_sync accepts the shape: S >= 1, 1 <= W <= CP,
+ * 2W + CP <= 64 (one lane per lag), T even (16-byte frame rows), four frames and their lag sums within 64 KB of LDS.
+ * Refused with DCCN_ERR_INVALID_ARG before anything is launched: an unsupported shape; frames <= 0; x or offset NULL; x, x_out
+ * or metric off a 16-byte boundary; out_kin neither K+CP nor K (nor K with S*K odd: those rows are no multiple of 16 bytes);
+ * x_out overlapping x. */
+int dccn_frame_sync_supported(int S, int K, int CP, int W);
+int dccn_frame_sync(const float* x, int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset,
+                    float* metric, dccn_stream_t stream);
+
 /* ==== host utility: CRC32C (Castagnoli), the checksum of TensorFlow's tensor-bundle checkpoints =========
  * (tf.train.Saver files the reference writes at dev/py/ofdmreceiver_np.py:271).
  * Returns the CRC of (previous data ++ data) given the CRC of the previous data (0 to start).  Host code. */

@@ -10,6 +10,10 @@
     python tools/rxbench.py --chains 2 4 8 [--mods 1 2 3 4] [--frames 73] [--out FILE]
         several links, each with its own (equaliser -> frozen receiver) chain: (a) G solo receive calls back to back on one
         stream against (b) ONE grouped call (dccn_eq_receive_step_grouped), per group size G; same alternation and repeats
+    python tools/rxbench.py --sync 3 [--out FILE]
+        the same receive call on full frames resident on the device: (copy) receive(x), whose first launch copies the frames
+        into the receiver, against (sync) receive(x, sync=W), where the alignment launch (dccn_frame_sync) takes the copy's
+        place, and (step) receive() with neither; same shapes, alternation and repeats
 
 Shapes: 1170 frames QPSK and 16-QAM, and one 20 000-frame QPSK sweep batch (N = 64).  Every shape runs in a child process of
 its own under a time limit; the parent never opens the GPU and stops at the first child that fails.  Times are medians over
@@ -96,6 +100,58 @@ def run_one(frames, nbits, iters, repeats, only):
         out["us"][k] = round(med, 2)
         out["spread"][k] = round((v[-1] - v[0]) / med, 4)
     return out
+
+
+def timed(variants, iters, repeats):
+    """warm up, then `repeats` rounds that visit every variant in turn: (median us per call, (max - min) / median) per variant"""
+    import torch
+    for f in variants.values():
+        for _ in range(20):
+            f()
+    torch.cuda.synchronize()
+    t = {k: [] for k in variants}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(repeats):
+        for k, f in variants.items():
+            e0.record()
+            for _ in range(iters):
+                f()
+            e1.record()
+            e1.synchronize()
+            t[k].append(e0.elapsed_time(e1) * 1e3 / iters)
+    us, spread = {}, {}
+    for k, v in t.items():
+        v = sorted(v)
+        med = v[len(v) // 2]
+        us[k], spread[k] = round(med, 2), round((v[-1] - v[0]) / med, 4)
+    return us, spread
+
+
+def run_sync(frames, nbits, W, iters, repeats):
+    """receive(x) (copy + step) against receive(x, sync=W) (alignment launch + step) and receive() (the step alone), on full
+    frames [frames, S, K + CP, 2] resident on the device; the first two must agree where every offset is 0 before anything is timed"""
+    import numpy as np
+    import torch
+    from dl_ofdm_amd import _lib
+    from dl_ofdm_amd.engine import RxDims, glorot_init
+    from dl_ofdm_amd.receive import RxReceiver
+    from dl_ofdm_amd.sync import FrameSync
+    CP = KIN - F
+    dims = RxDims(S, KIN, F, D, nbits)
+    rc = RxReceiver(dims, frames, glorot_init(dims, 1), CP=CP)
+    rng = np.random.RandomState(0)
+    # frames with a true cyclic prefix (so the estimate is 0 and both calls must return the same bits)
+    body = rng.randn(frames, S, F, 2).astype(np.float32)
+    x = torch.as_tensor(np.concatenate([body[:, :, F - CP:], body], axis=2), device="cuda")
+    a, b = rc.receive(x).packed.clone(), rc.receive(x, sync=W)
+    assert int(b.offset.abs().max()) == 0 and torch.equal(a, b.packed)
+    fs = FrameSync(S, F, CP, W, frames, "cuda", want_metric=False)
+    variants = {"copy": lambda: rc.receive(x), "sync": lambda: rc.receive(x, sync=W), "step": rc.receive,
+                "sync_alone": lambda: fs.run(x), "copy_alone": lambda: rc.x.copy_(x)}
+    us, spread = timed(variants, iters, repeats)
+    moved = 2 * frames * S * KIN * 2 * 4
+    return {"frames": frames, "nbits": nbits, "W": W, "iters": iters, "repeats": repeats, "us": us, "spread": spread,
+            "bytes_moved_by_copy_or_sync": moved, "build_id": _lib.load().dccn_build_id().decode()}
 
 
 def run_chains(mods, frames, iters, repeats):
@@ -186,7 +242,8 @@ def main():
     ap.add_argument("--mods", type=int, nargs="+", default=[1, 2, 3, 4], help="--chains: bits per cell of the links, cycled")
     ap.add_argument("--frames", type=int, default=73, help="--chains: frames per link and call")
     ap.add_argument("--one-chains", default=None, help="nbits,nbits,...: measure this group in this process")
-    ap.add_argument("--out", default=None, help="--chains: also write the result document to this file")
+    ap.add_argument("--out", default=None, help="--chains / --sync: also write the result document to this file")
+    ap.add_argument("--sync", type=int, default=0, help="W: time receive(x) against receive(x, sync=W) on every shape")
     a = ap.parse_args()
     if a.one_chains:
         print(json.dumps(run_chains([int(v) for v in a.one_chains.split(",")], a.frames, a.iters, a.repeats)))
@@ -195,7 +252,7 @@ def main():
         return main_chains(a)
     if a.one:
         fr, nb = (int(v) for v in a.one.split(","))
-        print(json.dumps(run_one(fr, nb, a.iters, a.repeats, a.only)))
+        print(json.dumps(run_sync(fr, nb, a.sync, a.iters, a.repeats) if a.sync else run_one(fr, nb, a.iters, a.repeats, a.only)))
         return 0
     res = []
     for fr, nb in SHAPES:
@@ -203,12 +260,26 @@ def main():
                "--iters", str(a.iters if fr < 10000 else max(a.iters // 5, 10)), "--repeats", str(a.repeats)]
         if a.only:
             cmd += ["--only", a.only]
+        if a.sync:
+            cmd += ["--sync", str(a.sync)]
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         if r.returncode != 0:               # nothing more is started on the GPU after a failure
             sys.stderr.write(r.stderr[-2000:])
             print(json.dumps({"bench": "rxbench", "failed": [fr, nb], "rc": r.returncode, "shapes": res}))
             return 1
         res.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    if a.sync:
+        doc = {"bench": "rxbench.sync", "variants": {"copy": "receive(x): copy + step", "sync": "receive(x, sync=W): alignment launch + step",
+                                                     "step": "receive(): the step alone", "sync_alone": "FrameSync.run(x)",
+                                                     "copy_alone": "x.copy_ alone"},
+               "unit": "us per call (median over repeats of the mean of `iters` back-to-back calls); spread = (max - min) / median",
+               "shapes": res}
+        print(json.dumps(doc))
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(doc, f, indent=1)
+                f.write("\n")
+        return 0
     print(json.dumps({"bench": "rxbench", "variants": {"a": "eval_step(want_prob) + torch argmax/pack", "b": "eval_step(no prob)",
                                                        "c": "receive bits", "d": "receive bits+llr"}, "shapes": res}))
     return 0

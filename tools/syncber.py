@@ -1,0 +1,132 @@
+#!/usr/bin/env python
+"""Does per-frame timing alignment from the cyclic prefix (dl_ofdm_amd.sync.FrameSync) change the BER of a trained chain?
+
+One modulation; the basic receiver trained with the reference driver's recipe (AWGN at 5 dB per bit) and the equaliser trained
+on --train_channel (default mixRayleigh, the reference driver's stage 2) -- or a chain loaded with --load -- then evaluated on
+EPA / EVA / ETU / mixRayleigh at --snrs, the SAME frames three ways:
+
+    plain     the frames as the generator writes them (they arrive (L - 1) // 2 samples early: datagen.py)
+    sync      every frame rotated by its own estimated offset (FrameSync, window --W) in front of the evaluation step
+    known     every frame delayed by the channel's known advance (what align_window does; single-profile channels only)
+
+next to the share of frames per estimated offset.  The chain is NOT retrained on aligned frames: this measures what the stage
+does for a chain trained as the reference trains it.  No threshold: the numbers are the result.
+
+    python tools/syncber.py --nbits 2 --out syncber_out [--load CKPT --rx_load CKPT] [--seeds 3]
+"""
+import argparse
+import copy
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+CHANNELS = ("EPA", "EVA", "ETU", "mixRayleigh")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--nbits", type=int, default=2)
+    ap.add_argument("--train_channel", default="mixRayleigh")
+    ap.add_argument("--snrs", default="5,11,20,29,40")
+    ap.add_argument("--frames", type=int, default=20000, help="frames per point and seed")
+    ap.add_argument("--seeds", type=int, default=3, help="independent evaluation batches per point (the spread is over them)")
+    ap.add_argument("--W", type=int, default=3)
+    ap.add_argument("--rx_epochs", type=int, default=0)
+    ap.add_argument("--eq_epochs", type=int, default=0)
+    ap.add_argument("--load", default=None, help="equaliser checkpoint (receiver_mp.save_checkpoint) instead of training")
+    ap.add_argument("--rx_load", default=None, help="basic-receiver checkpoint stem that goes with --load")
+    ap.add_argument("--out", default="syncber_out")
+    a = ap.parse_args()
+    import torch
+    from dl_ofdm_amd import _lib, ofdm, receiver as R, receiver_mp as H
+    from dl_ofdm_amd.datagen import DeviceDataGen
+    from dl_ofdm_amd.sync import FrameSync
+    os.makedirs(a.out, exist_ok=True)
+    nb, snrs = a.nbits, [float(s) for s in a.snrs.split(",")]
+    save = tempfile.mkdtemp(prefix="dccn_syncber_") + "/"
+    t0 = time.time()
+    log = {"build_id": _lib.load().dccn_build_id().decode(), "nbits": nb, "W": a.W, "frames": a.frames, "seeds": a.seeds,
+           "train_channel": a.train_channel, "snrs": snrs}
+    hf = H.Flags(nbits=nb, nfilter=64, channel=a.train_channel, max_epoch_num=a.eq_epochs if a.eq_epochs > 0 else 4000 * nb,
+                 early_stop=200, token="syncber", save_dir=save, device_data=True, seed=10 + nb, test_frames=a.frames)
+    if a.load:
+        from dl_ofdm_amd.equalizer import EqualizerTrainer
+        from dl_ofdm_amd.session import Session, load_model_np
+        sess = Session(device="cuda", seed=1)
+        load_model_np(a.rx_load, sess)
+        tr = EqualizerTrainer(hf, ofdm.ofdm_tx(hf), dict(sess.params), seed=hf.seed)
+        H.load_checkpoint(a.load, tr, with_optimizer=False)
+        log["loaded"] = [a.rx_load, a.load]
+    else:
+        rf = R.Flags(nbits=nb, nfilter=64, channel="AWGN", SNR=5.0 * nb, max_epoch_num=a.rx_epochs if a.rx_epochs > 0 else 1200 * nb,
+                     early_stop=200, token="syncber_%dmod" % nb, save_dir=save, device_data=True, seed=nb)
+        res = R.train(rf, verbose=False, run_test=False)
+        log["receiver"] = {"epochs": len(res["history"]), "seconds": round(time.time() - t0, 1),
+                           "best_train_loss": min(h["train_loss"] for h in res["history"])}
+        t1 = time.time()
+        out = H.train(hf, verbose=False, run_test=False, rx_params=res["params"])
+        H.load_checkpoint(out["best_path"], out["trainer"], with_optimizer=False)
+        tr = out["trainer"]
+        best = min(out["history"], key=lambda h: h["train_loss"])
+        log["equalizer"] = {"epochs": len(out["history"]), "seconds": round(time.time() - t1, 1), "best_train_loss": best["train_loss"],
+                            "best_epoch": best["epoch"], "test_ber_at_best": best["test_ber"]}
+    print(json.dumps(log), flush=True)
+    o = tr.ofdmobj
+    S, K, CP = int(hf.nsymbol), int(o.K), int(o.CP)
+    pl = tr.resident(a.frames)
+    scratch = torch.empty_like(pl.x)
+    fs = FrameSync(S, K, CP, a.W, a.frames, tr.device, want_metric=False)
+
+    def ber():
+        pl.run(False)
+        return float(tr._metrics(pl.metrics_buf, pl.tx_power)["berlin"])
+
+    rows = []
+    for ch in CHANNELS:
+        fl = copy.deepcopy(hf)
+        fl.channel = ch
+        gen = DeviceDataGen(fl, ofdm.ofdm_tx(fl), device=tr.device, seed=77)
+        gen.want_noise_power = False
+        adv = 0 if gen.mixed else (gen.L - 1) // 2
+        for i, snr in enumerate(snrs):
+            got = {"plain": [], "sync": [], "known": []}
+            hist = {}
+            for sd in range(a.seeds):
+                gen.seed, gen.offset = 77 + 13 * i + 1009 * sd, 0
+                gen.make_batch(a.frames, snr, out_x=scratch, out_bits=pl.bits)
+                pl.x.copy_(scratch)
+                got["plain"].append(ber())
+                _, off = fs.run(scratch, out=pl.x)
+                got["sync"].append(ber())
+                for v, c in zip(*[t.tolist() for t in torch.unique(off, return_counts=True)]):
+                    hist[int(v)] = hist.get(int(v), 0) + int(c)
+                if not gen.mixed:
+                    pl.x.copy_(torch.roll(scratch.view(a.frames, -1, 2), adv, dims=1).view_as(pl.x))
+                    got["known"].append(ber())
+            row = {"channel": ch, "snr_db": snr, "known_advance": None if gen.mixed else adv,
+                   "offset_share": {str(k): round(v / (a.frames * a.seeds), 4) for k, v in sorted(hist.items())}}
+            for k, v in got.items():
+                row[k] = None if not v else {"ber": float(np.mean(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    log["rows"] = rows
+    log["total_seconds"] = round(time.time() - t0, 1)
+    with open(os.path.join(a.out, "syncber_%dmod.json" % nb), "w") as f:
+        json.dump(log, f, indent=1)
+        f.write("\n")
+    with open(os.path.join(a.out, "syncber_%dmod.md" % nb), "w") as f:
+        f.write("| channel | SNR [dB] | BER plain | BER sync (W = %d) | BER known advance | offsets (share of frames) |\n|---|---|---|---|---|---|\n" % a.W)
+        cell = lambda c: "-" if c is None else "%.3g (%.3g .. %.3g)" % (c["ber"], c["min"], c["max"])      # noqa: E731
+        for r in rows:
+            f.write("| %s | %g | %s | %s | %s | %s |\n" % (r["channel"], r["snr_db"], cell(r["plain"]), cell(r["sync"]), cell(r["known"]),
+                                                        ", ".join("%s: %.1f %%" % (k, 100 * v) for k, v in r["offset_share"].items())))
+
+
+if __name__ == "__main__":
+    main()
