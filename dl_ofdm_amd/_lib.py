@@ -260,6 +260,8 @@ SIGNATURES = {
     "dccn_gen_static_frames": (_i, [POINTER(GenStatic), _vp]),
     "dccn_gen_static_apply": (_i, [POINTER(GenStatic), _vp, _vp, _vp]),
     "dccn_gen_static_apply_window": (_i, [POINTER(GenStatic), _vp, _vp, _vp]),
+    "dccn_gen_static_apply_sync_supported": (_i, [_i] * 4),
+    "dccn_gen_static_apply_sync": (_i, [POINTER(GenStatic), _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "dccn_eq_workspace_tensor": (_i, [POINTER(EqShape), _i, C.c_char_p, POINTER(C.c_size_t), POINTER(C.c_size_t)]),
     "dccn_eq_eval_step": (_i, [POINTER(EqShape), POINTER(EqBuffers), _vp]),
     "dccn_eq_train_step": (_i, [POINTER(EqShape), POINTER(EqBuffers), AdamHParams, _vp]),

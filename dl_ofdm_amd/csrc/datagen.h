@@ -10,6 +10,7 @@
 #include "common.h"
 #include "gemm_f32_mfma.h"
 #include "norm_adam.h"
+#include "frame_sync.h"
 
 namespace dccn {
 
@@ -765,6 +766,57 @@ static __global__ __launch_bounds__(256) void gen_static_apply_window_kernel(con
         x[i] = scale_add_noise(y[src], inv, noise[src]);
     }
     if (npow_out != nullptr && blockIdx.x == 0) noise_power_from_partials(npart_noise, n_noise, total, sh4, npow_out);
+}
+// gen_static_apply_kernel and frame_sync_kernel (frame_sync.h) as ONE launch (dccn_gen_static_apply_sync): a training batch
+// aligned by the cyclic-prefix estimator without x going to memory and back in between.  frame_sync_kernel's geometry (one wave
+// per frame, kSyncWaves frames per 256-thread block, its LDS region per frame, no atomics, no workspace); in place of its step 1
+// the wave forms its frame in LDS with batch_power_inv_scale / scale_add_noise -- the fp32 values gen_static_apply_kernel writes
+// -- and steps 2-5 are frame_sync.h's device functions, so x_out and offset carry the bits of the two-launch sequence.  Block 0
+// serves `noise_power:0` as the apply kernels do.  H (nullable, [frames, h_rep, K] complex: the generator's freq_response rows,
+// column k = DFT bin k) is rotated with the frame: aligned[n] = x[n + theta] has the response H[k] exp(+2 pi i k theta / K), the
+// integer k theta reduced mod K first and the factor from sincospif, so it is exact at every multiple of a quarter turn.  No
+// chain table.
+struct GenApplySyncArgs {
+    const float4* y; const float4* noise; const double* ppart; int npart; double total;
+    float* x_out; int32_t* offset; float2* H; int h_rep;
+    const double* npart_noise; int n_noise; float* npow_out;
+    int frames, S, K, CP, W, crop;
+};
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) gen_apply_sync_kernel(const GenApplySyncArgs a) {
+    extern __shared__ float4 sync_lds[];
+    __shared__ double sh4[4];
+    __shared__ float s_inv;
+    const float inv = batch_power_inv_scale(a.ppart, a.npart, a.total, sh4, &s_inv);
+    if (a.npow_out != nullptr && blockIdx.x == 0) noise_power_from_partials(a.npart_noise, a.n_noise, a.total, sh4, a.npow_out);
+    const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
+    const int T = a.S * (a.K + a.CP);
+    const long long f = (long long)blockIdx.x * kSyncWaves + wave;
+    const bool live = f < a.frames;          // (a ragged last block: the wave still meets the block's barriers)
+    float4* const region = sync_lds + (size_t)wave * (frame_sync_lds_per_frame(T) / 16);
+    float2* const yf = reinterpret_cast<float2*>(region);
+    float4* const pe = region + T / 2;
+
+    // 1. the frame x = y * inv + noise, formed once, into LDS
+    if (live) {
+        const float4* __restrict__ ys = a.y + (size_t)f * (T / 2);
+        const float4* __restrict__ zs = a.noise + (size_t)f * (T / 2);
+        for (int i = lane; i < T / 2; i += kSyncLanes) region[i] = scale_add_noise(ys[i], inv, zs[i]);
+    }
+    const int theta = frame_sync_estimate(yf, pe, lane, live, a.S, a.K, a.CP, a.W, nullptr);
+    if (!live) return;
+    if (lane == 0) a.offset[f] = theta;
+    frame_sync_store(yf, a.x_out + (size_t)f * a.S * (a.crop ? a.K : a.K + a.CP) * 2, theta, lane, a.S, a.K, a.CP, a.crop);
+    if (a.H != nullptr) {
+        float2* __restrict__ Hf = a.H + (size_t)f * a.h_rep * a.K;
+        for (int i = lane; i < a.h_rep * a.K; i += kSyncLanes) {
+            const int k = i % a.K;
+            const int m = ((k * theta) % a.K + a.K) % a.K;          // (|k theta| < K W: no overflow)
+            float sn, cs;
+            sincospif(2.0f * (float)m / (float)a.K, &sn, &cs);
+            const float2 h = Hf[i];
+            Hf[i] = make_float2(h.x * cs - h.y * sn, h.x * sn + h.y * cs);
+        }
+    }
 }
 
 // radio.py:62-88 AWGN_channel, the *in-graph* monitor branch of the receiver graph (ofdmreceiver_np.py:136,151-152):

@@ -163,6 +163,54 @@ int dccn_gen_static_apply_window(const dccn_gen_static* g, float* x_out, float* 
     return gen_static_apply_launch(g, x_out, noise_power, true, (hipStream_t)stream);
 }
 
+// apply + frame alignment as one launch (datagen.h gen_apply_sync_kernel).  Everything the call decides, before its one launch:
+// a refused call launches nothing.
+struct GenApplySyncPlan {
+    GenApplySyncArgs args;
+    unsigned blocks;
+    size_t lds;
+};
+static bool byte_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+static int gen_apply_sync_plan(const dccn_gen_static* g, int W, int out_kin, float* x_out, int32_t* offset, float* H_inout, int h_rep,
+                               float* noise_power, GenApplySyncPlan* plan) {
+    if (!gen_static_ok(g) || !frame_sync_shape_ok(g->S, g->K, g->CP, W)) return DCCN_ERR_INVALID_ARG;
+    if (!x_out || !aligned16(x_out) || !offset) return DCCN_ERR_INVALID_ARG;
+    if (out_kin != g->K + g->CP && out_kin != g->K) return DCCN_ERR_INVALID_ARG;
+    if (out_kin == g->K && (g->S * g->K) % 2 != 0) return DCCN_ERR_INVALID_ARG;      // (cropped rows leave as 16-byte stores too)
+    if (H_inout && ((h_rep != 1 && h_rep != g->S) || reinterpret_cast<uintptr_t>(H_inout) % 8 != 0)) return DCCN_ERR_INVALID_ARG;
+    const int T = g->S * (g->K + g->CP);
+    const size_t in_bytes = (size_t)g->frames * T * 8, out_bytes = (size_t)g->frames * g->S * out_kin * 8;
+    if (byte_ranges_overlap(g->y, in_bytes, x_out, out_bytes) || byte_ranges_overlap(g->noise, in_bytes, x_out, out_bytes))
+        return DCCN_ERR_INVALID_ARG;
+    const int np = dccn_gen_static_partials(g->frames);
+    const bool want_np = noise_power && g->noise_partial;
+    GenApplySyncArgs& a = plan->args;
+    a.y = reinterpret_cast<const float4*>(g->y); a.noise = reinterpret_cast<const float4*>(g->noise);
+    a.ppart = g->power_partial; a.npart = np; a.total = (double)g->frames * (double)T;
+    a.x_out = x_out; a.offset = offset; a.H = reinterpret_cast<float2*>(H_inout); a.h_rep = H_inout ? h_rep : 0;
+    a.npart_noise = want_np ? g->noise_partial : nullptr; a.n_noise = np; a.npow_out = want_np ? noise_power : nullptr;
+    a.frames = g->frames; a.S = g->S; a.K = g->K; a.CP = g->CP; a.W = W; a.crop = out_kin == g->K ? 1 : 0;
+    plan->blocks = (unsigned)ceil_div(g->frames, kSyncWaves);
+    plan->lds = kSyncWaves * frame_sync_lds_per_frame(T);
+    return DCCN_OK;
+}
+int dccn_gen_static_apply_sync_supported(int S, int K, int CP, int W) {
+    return (gen_static_shape_ok(S, K, CP) && frame_sync_shape_ok(S, K, CP, W)) ? 1 : 0;
+}
+int dccn_gen_static_apply_sync(const dccn_gen_static* g, int W, int out_kin, float* x_out, int32_t* offset, float* H_inout, int h_rep,
+                               float* noise_power, dccn_stream_t stream) {
+    GenApplySyncPlan plan;
+    DCCN_TRY(gen_apply_sync_plan(g, W, out_kin, x_out, offset, H_inout, h_rep, noise_power, &plan));
+    DCCN_NO_CHAINS();                         // (the launch carries no chain table: inside a group it would serve chain 0 only)
+    DCCN_TRY(set_max_dynamic_smem((const void*)gen_apply_sync_kernel, plan.lds));
+    hipLaunchKernelGGL(gen_apply_sync_kernel, dim3(plan.blocks), dim3(kSyncWaves * kSyncLanes), plan.lds, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
 size_t dccn_channel_doppler_awgn_workspace_size(int frames, int T, int L, int S) {
     if (frames <= 0 || T <= 0 || L <= 0 || S <= 0) return 0;
     return dccn_channel_awgn_workspace_size(frames, T, L * S);

@@ -37,29 +37,20 @@ struct FrameSyncArgs {
     int crop;           // 1: x_out rows are the K samples behind each symbol's prefix (out_kin == K)
 };
 
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) frame_sync_kernel(const FrameSyncArgs a) {
-    extern __shared__ float4 sync_lds[];
-    const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
-    const int N = a.K + a.CP, T = a.S * N, W = a.W;
-    const long long f = (long long)blockIdx.x * kSyncWaves + wave;
-    const bool live = f < a.frames;          // (a ragged last block: the wave still meets the block's barriers)
-    float4* const region = sync_lds + (size_t)wave * (frame_sync_lds_per_frame(T) / 16);
-    float2* const y = reinterpret_cast<float2*>(region);
-    float4* const pe = region + T / 2;
-
-    // 1. the frame, once, into LDS
-    if (live) {
-        const float4* src = reinterpret_cast<const float4*>(a.x + (size_t)f * T * 2);
-        for (int i = lane; i < T / 2; i += kSyncLanes) region[i] = src[i];
-    }
-    __syncthreads();
+// Steps 2-4 on a frame that sits in the wave's LDS region (y: its T samples, pe: the kSyncLanes (P, E) slots behind them):
+// the frame's offset, the same value in every lane.  The block's barriers are inside: every wave of the block calls this, live or
+// not.  Shared by frame_sync_kernel and gen_apply_sync_kernel (datagen.h): one statement of the sums and their order.
+__device__ __forceinline__ int frame_sync_estimate(const float2* y, float4* pe, const int lane, const bool live, const int S,
+                                                   const int K, const int CP, const int W, float* metric_row) {
+    const int N = K + CP, T = S * N;
+    __syncthreads();                                    // (the frame is complete in LDS)
 
     // 2. P[j], E[j] for j = lane - W in [-W, W + CP): the S symbols in order
-    if (live && lane < 2 * W + a.CP) {
+    if (live && lane < 2 * W + CP) {
         float pr = 0.f, pi = 0.f, e = 0.f;
         int n = (lane - W + T) % T;                     // (W <= CP < T)
-        for (int s = 0; s < a.S; ++s) {
-            const float2 u = y[n], v = y[(n + a.K) % T];
+        for (int s = 0; s < S; ++s) {
+            const float2 u = y[n], v = y[(n + K) % T];
             pr += u.x * v.x + u.y * v.y;
             pi += u.y * v.x - u.x * v.y;
             e += 0.5f * ((u.x * u.x + u.y * u.y) + (v.x * v.x + v.y * v.y));
@@ -73,14 +64,14 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) frame_sync_ker
     float lam = -INFINITY;
     if (live && lane <= 2 * W) {
         float gr = 0.f, gi = 0.f, phi = 0.f;
-        for (int n = 0; n < a.CP; ++n) {
+        for (int n = 0; n < CP; ++n) {
             const float4 t = pe[lane + n];
             gr += t.x;
             gi += t.y;
             phi += t.z;
         }
         lam = sqrtf(gr * gr + gi * gi) - phi;
-        if (a.metric) a.metric[(size_t)f * (2 * W + 1) + lane] = lam;
+        if (metric_row) metric_row[lane] = lam;
     }
 
     // 4. the wave's maximum, the smallest candidate on ties (every lane takes part; lanes past 2 W hold -inf)
@@ -96,30 +87,52 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) frame_sync_ker
     // lane 0's view, for every lane; kept inside the candidates whatever the samples were (NaN compares false everywhere)
     best = __shfl(best, 0);
     best = best < 0 ? 0 : (best > 2 * W ? 2 * W : best);
-    const int theta = best - W;
-    if (!live) return;
-    if (lane == 0) a.offset[f] = theta;
+    return best - W;
+}
 
-    // 5. the rotated frame from LDS: two complex samples per 16-byte store, each read at its own (shifted) place
-    if (a.x_out) {
-        const int rot = (theta + T) % T;
-        if (a.crop) {
-            const int M = a.S * a.K;
-            float4* dst = reinterpret_cast<float4*>(a.x_out + (size_t)f * M * 2);
-            for (int i = lane; i < M / 2; i += kSyncLanes) {
-                const int m0 = 2 * i, m1 = 2 * i + 1;
-                const float2 u = y[((m0 / a.K) * N + a.CP + m0 % a.K + rot) % T];
-                const float2 v = y[((m1 / a.K) * N + a.CP + m1 % a.K + rot) % T];
-                dst[i] = make_float4(u.x, u.y, v.x, v.y);
-            }
-        } else {
-            float4* dst = reinterpret_cast<float4*>(a.x_out + (size_t)f * T * 2);
-            for (int i = lane; i < T / 2; i += kSyncLanes) {
-                const float2 u = y[(2 * i + rot) % T], v = y[(2 * i + 1 + rot) % T];
-                dst[i] = make_float4(u.x, u.y, v.x, v.y);
-            }
+// Step 5: the frame rotated by theta, from LDS to dst (the frame's [S, K + CP, 2] rows, or crop: its [S, K, 2] rows behind each
+// symbol's prefix): two complex samples per 16-byte store, each read at its own (shifted) place
+__device__ __forceinline__ void frame_sync_store(const float2* y, float* dst_, const int theta, const int lane, const int S,
+                                                 const int K, const int CP, const int crop) {
+    const int N = K + CP, T = S * N;
+    const int rot = (theta + T) % T;
+    float4* dst = reinterpret_cast<float4*>(dst_);
+    if (crop) {
+        const int M = S * K;
+        for (int i = lane; i < M / 2; i += kSyncLanes) {
+            const int m0 = 2 * i, m1 = 2 * i + 1;
+            const float2 u = y[((m0 / K) * N + CP + m0 % K + rot) % T];
+            const float2 v = y[((m1 / K) * N + CP + m1 % K + rot) % T];
+            dst[i] = make_float4(u.x, u.y, v.x, v.y);
+        }
+    } else {
+        for (int i = lane; i < T / 2; i += kSyncLanes) {
+            const float2 u = y[(2 * i + rot) % T], v = y[(2 * i + 1 + rot) % T];
+            dst[i] = make_float4(u.x, u.y, v.x, v.y);
         }
     }
+}
+
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) frame_sync_kernel(const FrameSyncArgs a) {
+    extern __shared__ float4 sync_lds[];
+    const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
+    const int T = a.S * (a.K + a.CP), W = a.W;
+    const long long f = (long long)blockIdx.x * kSyncWaves + wave;
+    const bool live = f < a.frames;          // (a ragged last block: the wave still meets the block's barriers)
+    float4* const region = sync_lds + (size_t)wave * (frame_sync_lds_per_frame(T) / 16);
+    float2* const y = reinterpret_cast<float2*>(region);
+    float4* const pe = region + T / 2;
+
+    // 1. the frame, once, into LDS
+    if (live) {
+        const float4* src = reinterpret_cast<const float4*>(a.x + (size_t)f * T * 2);
+        for (int i = lane; i < T / 2; i += kSyncLanes) region[i] = src[i];
+    }
+    const int theta = frame_sync_estimate(y, pe, lane, live, a.S, a.K, a.CP, W,
+                                          (live && a.metric) ? a.metric + (size_t)f * (2 * W + 1) : nullptr);
+    if (!live) return;
+    if (lane == 0) a.offset[f] = theta;
+    if (a.x_out) frame_sync_store(y, a.x_out + (size_t)f * a.S * (a.crop ? a.K : a.K + a.CP) * 2, theta, lane, a.S, a.K, a.CP, a.crop);
 }
 
 }  // namespace dccn

@@ -82,6 +82,7 @@ class DeviceDataGen:
         if self.identity:
             self.L = 1
         self._ws = {}
+        self._syncs, self.sync_offset = {}, None      # make_batch(sync=W): alignment stages per (frames, W, out_kin), last offsets
 
     @staticmethod
     def idft_cp_matrix(K: int, CP: int) -> np.ndarray:
@@ -232,13 +233,42 @@ class DeviceDataGen:
         return self._groups[n]
 
     def make_batch(self, n_frames: int, snr_db, out_x: Optional[torch.Tensor] = None,
-                   out_bits: Optional[torch.Tensor] = None, want_H: bool = False):
+                   out_bits: Optional[torch.Tensor] = None, want_H: bool = False, sync: int = 0, out_kin: Optional[int] = None,
+                   out_H: Optional[torch.Tensor] = None, out_npow: Optional[torch.Tensor] = None):
         """receiver.make_batch on the device: (x float32 [n,S,n_sc,2], bits int32 [n,D,nbits], noise power[, H]);
-        advances the batch offset so consecutive calls draw fresh data."""
+        advances the batch offset so consecutive calls draw fresh data.
+
+        ``sync = W > 0``: every frame is then aligned by its own cyclic-prefix estimate (sync.FrameSync, window W) -- the
+        launch-per-stage form of ``FusedStaticGen.make_batch(..., sync=W)``, for sweep batches and shapes the fused generator
+        does not take.  ``x`` is ``[n, S, out_kin, 2]`` (``out_kin``: K + CP, the default, or K: the samples behind each
+        symbol's prefix), ``H`` gets the ramp of the frame's offset (sync.rotate_response_) and the offsets stay in
+        ``self.sync_offset``.  The alignment runs through a STAGING buffer, not in place: the channel stage writes the frames
+        to a buffer this generator keeps per batch size and ``dccn_frame_sync`` reads that and writes ``out_x``.  The entry
+        point refuses overlapping input and output (and the cropped output has another shape anyway); the staging buffer is
+        written and read on the caller's stream only, each batch after the previous batch's alignment launch in stream order, so
+        nothing reads it while it is rewritten."""
+        if not sync:
+            tx, bits = self.transmit(n_frames, out_bits=out_bits)
+            x, npow, H = self.channel(tx, snr_db, out_x=out_x, want_H=want_H, out_H=out_H, out_npow=out_npow)
+            self.offset = (self.offset + 1) & 0xFFFFFFFF
+            return (x, bits, npow, H) if (want_H or out_H is not None) else (x, bits, npow)
+        from .sync import FrameSync, rotate_response_
+        if self.align_window:
+            raise ValueError("sync > 0 and align_window both move the frames: choose one")
+        kin = self.n_sc if out_kin is None else int(out_kin)
+        key = (n_frames, int(sync), kin)
+        if key not in self._syncs:          # (refuses a bad W / out_kin before anything is launched)
+            self._syncs[key] = FrameSync(self.S, self.K, self.CP, int(sync), n_frames, self.device, out_kin=kin, want_metric=False)
+        fs, w = self._syncs[key], self._workspace(n_frames)
+        if "stage" not in w:
+            w["stage"] = torch.empty(n_frames, self.S, self.n_sc, 2, dtype=torch.float32, device=self.device)
         tx, bits = self.transmit(n_frames, out_bits=out_bits)
-        x, npow, H = self.channel(tx, snr_db, out_x=out_x, want_H=want_H)
+        _, npow, H = self.channel(tx, snr_db, out_x=w["stage"], want_H=want_H, out_H=out_H, out_npow=out_npow)
+        x, self.sync_offset = fs.run(w["stage"], out=out_x)
+        if H is not None:
+            rotate_response_(torch.view_as_real(H), self.sync_offset)
         self.offset = (self.offset + 1) & 0xFFFFFFFF
-        return (x, bits, npow, H) if want_H else (x, bits, npow)
+        return (x, bits, npow, H) if (want_H or out_H is not None) else (x, bits, npow)
 
 
 class FusedStaticGen:
@@ -264,6 +294,7 @@ class FusedStaticGen:
         from . import arena as A
         self.gen, self.n = gen, int(n_frames)
         self.arena = arena
+        self._sync_offset = self._sync_stage = None     # make_batch(sync=W): its own offsets / the three-launch form's staging buffer
         dev, f32 = gen.device, dict(dtype=torch.float32, device=gen.device)
         self.snr = A.empty(arena, self.n, **f32)
         self.set_snr(snr_db)
@@ -354,22 +385,57 @@ class FusedStaticGen:
         return d
 
     def make_batch(self, out_x: torch.Tensor, out_bits: torch.Tensor, slot: int = 0, tx_out: Optional[torch.Tensor] = None,
-                   out_H: Optional[torch.Tensor] = None, snr: Optional[torch.Tensor] = None):
+                   out_H: Optional[torch.Tensor] = None, snr: Optional[torch.Tensor] = None, sync: int = 0,
+                   offset_out: Optional[torch.Tensor] = None, fused_sync: bool = True):
         """generate + materialise: (x, bits, noise power or None), two launches (the first batch of a pipelined loop, the
         equaliser's epoch loop, tests).  ``out_x``: [n, S, K+CP, 2], the whole symbols, or [n, S, K, 2], the samples behind the
-        cyclic prefix (a ``cp=False`` receiver's input); anything else raises ValueError before a launch."""
+        cyclic prefix (a ``cp=False`` receiver's input); anything else raises ValueError before a launch.
+
+        ``sync = W > 0``: every frame aligned by its own cyclic-prefix estimate (window W), still two launches -- the generator
+        and ``dccn_gen_static_apply_sync``, which forms x in LDS, estimates and writes the rotated frame (whole or behind the
+        prefix, by ``out_x``'s shape) once, and rotates ``out_H`` with it.  Returns (x, bits, noise power or None, offsets):
+        the offsets int32 [n] in ``offset_out`` or this object's own buffer.  ``fused_sync=False``: the same batch as three
+        launches (apply into a staging buffer, then ``dccn_frame_sync``: the same bits) with the ramp on ``out_H`` as a torch
+        expression -- for tests and A/B timing."""
         g = self.gen
         whole, window = self.n * g.S * (g.K + g.CP) * 2, self.n * g.S * g.K * 2
         if out_x.numel() not in (whole, window):
             raise ValueError("out_x must hold %d (whole symbols) or %d (behind the cyclic prefix) floats, got shape %s"
                              % (whole, window, tuple(out_x.shape)))
-        apply = "dccn_gen_static_apply" if out_x.numel() == whole else "dccn_gen_static_apply_window"
+        sync = int(sync or 0)
+        if sync and not bool(g.lib.dccn_gen_static_apply_sync_supported(g.S, g.K, g.CP, sync)):
+            raise ValueError("sync=%d: dccn_gen_static_apply_sync_supported refuses it (1 <= W <= CP = %d, 2 W + CP <= 64)" % (sync, g.CP))
+        if sync:
+            if offset_out is None:
+                if self._sync_offset is None:
+                    self._sync_offset = torch.zeros(self.n, dtype=torch.int32, device=g.device)
+                offset_out = self._sync_offset
+            elif offset_out.dtype != torch.int32 or offset_out.numel() != self.n or not offset_out.is_contiguous():
+                raise ValueError("offset_out must be a contiguous int32 tensor of %d elements" % self.n)
+            if not fused_sync and self._sync_stage is None:
+                self._sync_stage = torch.empty(self.n, g.S, g.n_sc, 2, dtype=torch.float32, device=g.device)
+        apply = "dccn_gen_static_apply" if (out_x.numel() == whole or sync) else "dccn_gen_static_apply_window"
         d = self.arm(out_bits, slot, tx_out, out_H, snr)
         st = g._stream()
         check(g.lib.dccn_gen_static_frames(C.byref(d), st), "dccn_gen_static_frames")
         npw = self.npow[slot & 1] if self.npow is not None else None
-        check(getattr(g.lib, apply)(C.byref(d), out_x.data_ptr(), None if npw is None else npw.data_ptr(), st), apply)
-        return out_x, out_bits, npw
+        npw_p = None if npw is None else npw.data_ptr()
+        if not sync:
+            check(getattr(g.lib, apply)(C.byref(d), out_x.data_ptr(), npw_p, st), apply)
+            return out_x, out_bits, npw
+        out_kin = g.K + g.CP if out_x.numel() == whole else g.K
+        if fused_sync:
+            check(g.lib.dccn_gen_static_apply_sync(C.byref(d), sync, out_kin, out_x.data_ptr(), offset_out.data_ptr(),
+                                                   None if out_H is None else out_H.data_ptr(), d.h_rep, npw_p, st),
+                  "dccn_gen_static_apply_sync")
+        else:
+            check(g.lib.dccn_gen_static_apply(C.byref(d), self._sync_stage.data_ptr(), npw_p, st), apply)
+            check(g.lib.dccn_frame_sync(self._sync_stage.data_ptr(), self.n, g.S, g.K, g.CP, sync, out_kin, out_x.data_ptr(),
+                                        offset_out.data_ptr(), None, st), "dccn_frame_sync")
+            if out_H is not None:
+                from .sync import rotate_response_
+                rotate_response_(out_H, offset_out)
+        return out_x, out_bits, npw, offset_out
 
 
 class SideStreamFeeder:

@@ -128,6 +128,10 @@ class EqualizerChainGroup:
         self.lib = _lib.load()
         if not (1 <= len(flags_list) <= int(self.lib.dccn_chain_group_max())):
             raise ValueError("1..%d chains per group" % int(self.lib.dccn_chain_group_max()))
+        if any(int(getattr(F, "sync", 0) or 0) > 0 for F in flags_list):
+            # (a sync loop materialises every batch: no virtual next batch, no riding generator -- what a group step is built on)
+            raise _lib.DccnError("chain groups do not take sync > 0: the aligned batch is materialised per chain "
+                                 "(dccn_gen_static_apply_sync carries no chain table); train such chains with receiver_mp.train")
         nbytes = max(arena_bytes_for(F, self.lib) for F in flags_list)
         self.chains: List[_Chain] = [_Chain(F, rx, device, nbytes) for F, rx in zip(flags_list, rx_params_list)]
         check_same_layout([c.arena for c in self.chains])

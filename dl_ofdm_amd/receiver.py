@@ -33,6 +33,10 @@ def _bool(v):
 @dataclass
 class Flags:
     """tf.app.flags of ofdmreceiver_np.py:30-53 (same names, same defaults)."""
+
+    def __post_init__(self):
+        check_sync(self)
+
     save_dir: str = "./output/"
     nbits: int = 1
     msg_length: int = 100800
@@ -62,9 +66,22 @@ class Flags:
     snr_hi: int = 30                # inclusive (:72)
     device_data: bool = False       # generate bits/frames/channel/noise on the GPU (datagen.py) instead of NumPy
     align_window: bool = False      # extension: delay generated frames by the channel's centre-tap advance (datagen.py)
+    sync: int = 0                   # extension, device_data: align every generated frame by its own cyclic-prefix estimate, window
+    #                                 +-sync samples (sync.FrameSync) -- training, per-epoch evaluation and the sweep; 0: off
     tf_checkpoint: bool = False     # also write <save_dir>/<token>.index/.data-00000-of-00001 (tf.train.Saver format)
     iq_dump: bool = False           # per-epoch <token>_txiq.csv / _rxiq.csv constellation dumps (ofdmreceiver_np.py:264-265),
     #                                 written into save_dir; off by default: two syncs + two files per epoch
+
+
+def check_sync(FLAGS) -> int:
+    """the ``sync`` flag of either harness, checked before anything is launched: W >= 0, not together with ``align_window`` (both
+    move the frames), and only on device-generated data (the stage is a GPU launch: there is no host fallback)"""
+    W = int(getattr(FLAGS, "sync", 0) or 0)
+    if W < 0:
+        raise ValueError("sync must be >= 0 (the estimator's window in samples), got %d" % W)
+    if W > 0 and bool(getattr(FLAGS, "align_window", False)):
+        raise ValueError("sync=%d and align_window=True both move the generated frames: choose one" % W)
+    return W
 
 
 def parse_flags(argv=None) -> Flags:
@@ -197,8 +214,13 @@ def _device_gen(FLAGS: Flags, ofdmobj, device):
 
 def _gen_into(gen, eng, FLAGS: Flags, ofdmobj, n_frames: int, snr_db, slot: int = 0):
     """make_batch on the GPU, written into the engine's resident input buffers (cropped when cp=False); ``slot`` picks
-    the label buffer (RxEngine.label_slot: the pipelined training loop fills one while a step reads the other)."""
+    the label buffer (RxEngine.label_slot: the pipelined training loop fills one while a step reads the other).
+    ``FLAGS.sync = W > 0``: the frames aligned by the cyclic-prefix estimator; the alignment launch crops (out_kin = K) itself."""
     bits = eng.label_slot(slot) if slot else eng.bits
+    W = int(getattr(FLAGS, "sync", 0) or 0)
+    if W > 0:
+        return gen.make_batch(n_frames, snr_db, out_x=eng.x, out_bits=bits, sync=W,
+                              out_kin=(ofdmobj.K + ofdmobj.CP) if FLAGS.cp else ofdmobj.K)[2]
     if FLAGS.cp:
         return gen.make_batch(n_frames, snr_db, out_x=eng.x, out_bits=bits)[2]
     x, _, npow = gen.make_batch(n_frames, snr_db, out_bits=bits)
@@ -216,6 +238,7 @@ def test_model(FLAGS: Flags, model, ofdmobj=None, rank: int = 0, world: int = 1,
     (``load_model_np(path, session)`` then ``session.run([conf_matrix, berlin, ...], {x, y, SNR})``, :60,80), or an
     already loaded name -> array dict."""
     from .session import Session, load_model_np
+    _require_device_sync(FLAGS)
     ofdmobj = ofdmobj or ofdm.ofdm_tx(FLAGS)
     snrs = list(range(FLAGS.snr_lo, FLAGS.snr_hi + 1))
     pts = sweep.make_points([FLAGS.nbits], [FLAGS.channel], snrs, base_seed=FLAGS.seed)
@@ -279,8 +302,14 @@ def test_model(FLAGS: Flags, model, ofdmobj=None, rank: int = 0, world: int = 1,
 
 
 # ---- training (H2, H3) ---------------------------------------------------------------------------
+def _require_device_sync(FLAGS):
+    if check_sync(FLAGS) > 0 and not bool(getattr(FLAGS, "device_data", False)):
+        raise ValueError("sync > 0 needs device_data=True: the alignment stage is a GPU launch on device-generated frames")
+
+
 def train(FLAGS: Flags, device="cuda", verbose: bool = True, run_test: bool = True):
     from .engine import RxEngine
+    _require_device_sync(FLAGS)
     ofdmobj = ofdm.ofdm_tx(FLAGS)
     dims = rx_dims(FLAGS, ofdmobj)
     frame_cnt = FLAGS.msg_length // FLAGS.nsymbol
@@ -332,7 +361,9 @@ def train(FLAGS: Flags, device="cuda", verbose: bool = True, run_test: bool = Tr
                 # ... and the generator runs on its own stream (datagen.SideStreamFeeder): batch i+1 is produced while the forward
                 # and backward launches of step i run; the step's last launch waits for it
                 from .datagen import FusedStaticGen, SideStreamFeeder
-                if FusedStaticGen.supported(gen, eng) and not getattr(FLAGS, "no_fused_generator", False):
+                # (sync > 0: every batch is materialised and aligned -- the loop below, whose _gen_into route aligns; the step
+                # that reads the generator's output as its virtual input would see the frames as generated)
+                if FusedStaticGen.supported(gen, eng) and not getattr(FLAGS, "no_fused_generator", False) and not check_sync(FLAGS):
                     # round 5: single-profile channels, static or mobile -- ONE C call per batch: the fused generator launch of the next batch
                     # + the four step launches, whose pipelined normalisation reads (y, noise, power partials) as its virtual
                     # input (include/dccn.h dccn_gen_static; datagen.FusedStaticGen).  Same batches as the loop below.

@@ -30,7 +30,7 @@ import numpy as np
 
 from . import ofdm, radio, sweep, util
 from .engine import PARAM_NAMES
-from .receiver import _bool
+from .receiver import _bool, check_sync
 
 TRAIN_SNR_GRID = np.linspace(0, 27, 10, dtype=np.float32)                      # :387 aa_milne_arr
 TRAIN_SNR_PROB = [0.01, 0.01, 0.02, 0.02, 0.02, 0.02, 0.1, 0.5, 0.2, 0.1]      # :407
@@ -40,6 +40,9 @@ TEST_CHANNELS = ("ETU", "EVA", "EPA", "Flat", "Custom")                        #
 @dataclass
 class Flags:
     """tf.app.flags of ofdmreceiver_np_mp.py:32-59."""
+
+    def __post_init__(self):
+        check_sync(self)
     save_dir: str = "./output/"
     nbits: int = 1
     msg_length: int = 100800
@@ -74,6 +77,10 @@ class Flags:
     snr_step: int = 5               # :81
     device_data: bool = False       # generate bits/frames/channel/noise on the GPU (datagen.py)
     align_window: bool = False      # extension: delay generated frames by the channel's centre-tap advance (datagen.py)
+    sync: int = 0                   # extension, device_data: align every generated frame by its own cyclic-prefix estimate, window
+                                    # +-sync samples (training batches, per-epoch evaluation, the final sweep); 0: off
+    fused_sync: bool = True         # sync > 0, fused generator: x is formed, aligned and written by ONE launch
+                                    # (dccn_gen_static_apply_sync); False: apply + dccn_frame_sync, the same bits in three launches
     pipeline_norm: Optional[bool] = None  # device_data: step i normalises batch i+1 on its optimizer launch (None: when the library can)
     overlap_generator: bool = False  # device_data: generate batch i+1 on a second stream while step i runs (same results, not faster)
     step_graph: bool = False         # device_data: replay the equaliser step as a hipGraph instead of 21 eager launches (same results)
@@ -150,6 +157,7 @@ def test_model_cross(FLAGS, trainer, ofdmobj, rank: int = 0, world: int = 1, out
     fadings = {}
 
     on_device = bool(getattr(FLAGS, "device_data", False)) and trainer.fused_ok
+    W = _device_sync(FLAGS, on_device)
 
     def evaluate(p):
         if p.channel not in fadings:
@@ -165,7 +173,7 @@ def test_model_cross(FLAGS, trainer, ofdmobj, rank: int = 0, world: int = 1, out
         if on_device:
             gen, pl = fadings[p.channel], trainer.resident(FLAGS.test_frames)
             gen.seed, gen.offset = p.seed, 0
-            gen.make_batch(FLAGS.test_frames, p.snr_db, out_x=pl.x, out_bits=pl.bits)
+            gen.make_batch(FLAGS.test_frames, p.snr_db, out_x=pl.x, out_bits=pl.bits, sync=W)
             pl.run(False)
             m = trainer._metrics(pl.metrics_buf, pl.tx_power)
         else:
@@ -191,6 +199,14 @@ def test_model_cross(FLAGS, trainer, ofdmobj, rank: int = 0, world: int = 1, out
     return out
 
 
+def _device_sync(FLAGS, on_device: bool) -> int:
+    """the ``sync`` window, checked before anything is launched; the stage is a GPU launch on device-generated frames"""
+    W = check_sync(FLAGS)
+    if W > 0 and not on_device:
+        raise ValueError("sync > 0 needs device_data=True and the fused equaliser step: there is no host alignment stage")
+    return W
+
+
 def save_checkpoint(path: str, trainer, FLAGS):
     os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
     out = trainer.state_dict_tf()
@@ -214,6 +230,8 @@ def load_checkpoint(path: str, trainer, with_optimizer: bool = True):
 
 def train(FLAGS, device="cuda", verbose: bool = True, run_test: bool = True, rx_params=None):
     from .equalizer import EqualizerTrainer
+    if check_sync(FLAGS) > 0 and not FLAGS.device_data:           # (before anything is built or launched)
+        raise ValueError("sync > 0 needs device_data=True: there is no host alignment stage")
     ofdmobj = ofdm.ofdm_tx(FLAGS)
     frame_cnt = FLAGS.msg_length // FLAGS.nsymbol
     np.random.seed(FLAGS.seed)
@@ -225,6 +243,7 @@ def train(FLAGS, device="cuda", verbose: bool = True, run_test: bool = True, rx_
     phase2 = True                                                      # :393
     loss_min, epoch_min, best_path, history = 100.0, 0, "", []
     on_device = bool(FLAGS.device_data) and trainer.fused_ok
+    _device_sync(FLAGS, on_device)
     if on_device:
         return _train_on_device(FLAGS, ofdmobj, trainer, batch_size, frame_cnt, verbose, run_test)
     for epoch in range(FLAGS.max_epoch_num):
@@ -295,6 +314,13 @@ class DeviceEpochLoop:
         self.F, self.o, self.tr, self.gen, self.steps = FLAGS, ofdmobj, trainer, gen, int(steps)
         self.arena = arena
         dev, B = trainer.device, pl.batch
+        # sync = W > 0: every batch is materialised and aligned by the cyclic-prefix estimator (the route virtual_next=False takes,
+        # with dccn_gen_static_apply_sync in place of the apply launch); the pipelined normalisation reads the real x_next
+        self.sync = check_sync(FLAGS)
+        self.fused_sync = bool(getattr(FLAGS, "fused_sync", True))
+        if self.sync and arena is not None:
+            from ._lib import DccnError
+            raise DccnError("chain groups do not take sync > 0 (the aligned batch is materialised per chain)")
         self.overlap = bool(overlap)
         if pipeline is None:
             pipeline = not self.overlap and bool(trainer.lib.dccn_eq_norm_rides(C.byref(pl.shape)))
@@ -327,7 +353,7 @@ class DeviceEpochLoop:
         # ... and in the pipelined loop the second of those launches goes too: the optimizer launch of step i reads batch i + 1
         # as (y, noise, power partials) -- dccn_eq_buffers.x_next_virtual; only an epoch's first batch is materialised
         self.virt = None
-        if self.fg is not None and self.pipeline and getattr(FLAGS, "virtual_next", True):
+        if self.fg is not None and self.pipeline and getattr(FLAGS, "virtual_next", True) and not self.sync:
             from . import _lib
             self.virt = []
             for q in range(2):                                       # plan q normalises plan q ^ 1's batch (monitor slot q ^ 1)
@@ -372,6 +398,14 @@ class DeviceEpochLoop:
     def _generate(self, i: int, q: int):
         from ._lib import check
         pl, gen = self.pls[q], self.gen
+        if self.sync:
+            if self.fg is not None:         # generator launch + ONE launch that forms, aligns and writes x (and rotates H)
+                self.fg.make_batch(pl.x, pl.bits, slot=q, out_H=self.H[q], snr=self.snr_rows[i], sync=self.sync,
+                                   fused_sync=self.fused_sync)
+            else:                           # launch per stage: channel into a staging buffer, then dccn_frame_sync
+                gen.make_batch(pl.batch, self.snr_rows[i], out_x=pl.x, out_bits=pl.bits, sync=self.sync, out_H=self.H[q],
+                               out_npow=self.npow[q])
+            return
         if self.fg is not None:
             if self.virt is not None and i > 0:                      # frames only: the running step forms x in registers
                 if getattr(self, "ride_gen", False):                 # ... and produces them: arm the descriptor ITS buffers hold
@@ -527,9 +561,12 @@ def _train_on_device(FLAGS, ofdmobj, trainer, batch_size, frame_cnt, verbose, ru
             a = loop.epoch_means()
             train_loss_epoch = float(a[0])
             snr = rs.choice(TRAIN_SNR_GRID, [FLAGS.eval_frames], p=TRAIN_SNR_PROB)              # :438
-            tx, _ = gen.transmit(FLAGS.eval_frames, out_bits=ev.bits)
-            gen.channel(tx, snr, out_x=ev.x)
-            gen.offset += 1
+            if loop.sync:
+                gen.make_batch(FLAGS.eval_frames, snr, out_x=ev.x, out_bits=ev.bits, sync=loop.sync)
+            else:
+                tx, _ = gen.transmit(FLAGS.eval_frames, out_bits=ev.bits)
+                gen.channel(tx, snr, out_x=ev.x)
+                gen.offset += 1
             ev.run(False)
             em = trainer._metrics(ev.metrics_buf, ev.tx_power)
             history.append(dict(epoch=epoch, train_loss=train_loss_epoch, train_ber=float(a[1]), chan_rms=float(a[4]),

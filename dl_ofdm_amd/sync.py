@@ -20,6 +20,21 @@ from . import _lib
 from ._lib import DccnError, check
 
 
+def rotate_response_(H: torch.Tensor, offset: torch.Tensor) -> torch.Tensor:
+    """The frequency response of frames aligned by ``offset``, in place: ``aligned[n] = x[n + offset]`` has the response
+    ``H[k] * exp(+2 pi i k offset / K)`` (column ``k`` = DFT bin ``k``, the generator's numbering).  ``H``: float32
+    ``[frames, K, 2]`` or ``[frames, S, K, 2]``; ``offset``: int32 ``[frames]``.  The torch statement of what
+    ``dccn_gen_static_apply_sync`` does to ``H_inout`` (the integer ``k * offset`` reduced mod K first)."""
+    K = H.shape[-2]
+    k = torch.arange(K, device=H.device, dtype=torch.int64)
+    m = torch.remainder(k[None, :] * offset.to(torch.int64)[:, None], K)
+    ang = m.to(torch.float32) * (2.0 / K)
+    ramp = torch.complex(torch.cos(ang * torch.pi), torch.sin(ang * torch.pi))
+    Hc = torch.view_as_complex(H)
+    Hc.mul_(ramp[:, None, :] if Hc.dim() == 3 else ramp)
+    return H
+
+
 class FrameSync:
     """Fixed-shape alignment stage on one GPU: ``run(x) -> (aligned, offset)``.
 

@@ -508,6 +508,18 @@ int dccn_gen_static_apply(const dccn_gen_static* g, float* x_out, float* noise_p
  * is the same value too.  Refused like dccn_gen_static_apply (DCCN_ERR_INVALID_ARG); inside a chain group DCCN_ERR_UNSUPPORTED
  * (the launch carries no chain table). */
 int dccn_gen_static_apply_window(const dccn_gen_static* g, float* x_out, float* noise_power, dccn_stream_t stream);
+/* dccn_gen_static_apply followed by dccn_frame_sync (below: window W, out_kin = K+CP or K) as ONE launch, for training loops that
+ * align every generated batch: x is formed in LDS, the estimator runs on it and the rotated frame is written once.  x_out
+ * [frames, S, out_kin, 2], offset int32 [frames] and noise_power carry the bits of that two-launch sequence on the same
+ * descriptor.  H_inout (nullable): the [frames, h_rep, K, 2] responses the generator launch wrote (dccn_gen_static.H_out,
+ * h_rep = 1 or S), multiplied in place by exp(+2 pi i k offset / K) per column k -- the response of the frame as aligned.
+ * dccn_gen_static_apply_sync_supported (host only) = dccn_gen_static_supported && dccn_frame_sync_supported.
+ * Refused with DCCN_ERR_INVALID_ARG before anything is launched: a descriptor dccn_gen_static_apply refuses; W or out_kin that
+ * dccn_frame_sync refuses; x_out or offset NULL; x_out off a 16-byte boundary or overlapping g->y / g->noise; H_inout with
+ * h_rep neither 1 nor S.  Inside a chain group DCCN_ERR_UNSUPPORTED (the launch carries no chain table). */
+int dccn_gen_static_apply_sync_supported(int S, int K, int CP, int W);
+int dccn_gen_static_apply_sync(const dccn_gen_static* g, int W, int out_kin, float* x_out, int32_t* offset, float* H_inout,
+                               int h_rep, float* noise_power, dccn_stream_t stream);
 
 typedef struct dccn_rx_buffers {
     const float* x;            /* [batch, S, kin, 2] raw input (tx_ofdm) */

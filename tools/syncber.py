@@ -9,10 +9,16 @@ EPA / EVA / ETU / mixRayleigh at --snrs, the SAME frames three ways:
     sync      every frame rotated by its own estimated offset (FrameSync, window --W) in front of the evaluation step
     known     every frame delayed by the channel's known advance (what align_window does; single-profile channels only)
 
-next to the share of frames per estimated offset.  The chain is NOT retrained on aligned frames: this measures what the stage
-does for a chain trained as the reference trains it.  No threshold: the numbers are the result.
+next to the share of frames per estimated offset.  That chain is NOT retrained on aligned frames: the three columns measure what
+the stage does for a chain trained as the reference trains it.  ``--train_sync W`` trains a SECOND equaliser with ``sync=W`` (every
+training batch aligned by the estimator inside the loop: receiver_mp.Flags.sync) on the same basic receiver -- or, ``--rx_sync``,
+on a basic receiver whose own training frames were aligned too -- and adds the column
 
-    python tools/syncber.py --nbits 2 --out syncber_out [--load CKPT --rx_load CKPT] [--seeds 3]
+    sync-trained    that chain on the aligned frames
+
+No threshold: the numbers are the result.
+
+    python tools/syncber.py --nbits 2 --out syncber_out [--load CKPT --rx_load CKPT] [--seeds 3] [--train_sync 3 [--rx_sync]]
 """
 import argparse
 import copy
@@ -41,6 +47,8 @@ def main():
     ap.add_argument("--eq_epochs", type=int, default=0)
     ap.add_argument("--load", default=None, help="equaliser checkpoint (receiver_mp.save_checkpoint) instead of training")
     ap.add_argument("--rx_load", default=None, help="basic-receiver checkpoint stem that goes with --load")
+    ap.add_argument("--train_sync", type=int, default=0, help="W > 0: also train an equaliser with sync=W and evaluate it on aligned frames")
+    ap.add_argument("--rx_sync", action="store_true", help="with --train_sync: the second chain's basic receiver trains on aligned frames too")
     ap.add_argument("--out", default="syncber_out")
     a = ap.parse_args()
     import torch
@@ -76,6 +84,27 @@ def main():
         best = min(out["history"], key=lambda h: h["train_loss"])
         log["equalizer"] = {"epochs": len(out["history"]), "seconds": round(time.time() - t1, 1), "best_train_loss": best["train_loss"],
                             "best_epoch": best["epoch"], "test_ber_at_best": best["test_ber"]}
+    tr2 = None
+    if a.train_sync > 0:
+        if a.load:
+            raise SystemExit("--train_sync trains its own chains: not together with --load")
+        t2 = time.time()
+        rx2 = res["params"]
+        if a.rx_sync:
+            rf2 = copy.deepcopy(rf)
+            rf2.sync, rf2.token = a.train_sync, rf.token + "_sync"
+            res2 = R.train(rf2, verbose=False, run_test=False)
+            rx2 = res2["params"]
+            log["receiver_sync"] = {"epochs": len(res2["history"]), "best_train_loss": min(h["train_loss"] for h in res2["history"])}
+        hf2 = copy.deepcopy(hf)
+        hf2.sync, hf2.token = a.train_sync, hf.token + "_sync"
+        out2 = H.train(hf2, verbose=False, run_test=False, rx_params=rx2)
+        H.load_checkpoint(out2["best_path"], out2["trainer"], with_optimizer=False)
+        tr2 = out2["trainer"]
+        best2 = min(out2["history"], key=lambda h: h["train_loss"])
+        log["equalizer_sync"] = {"W": a.train_sync, "rx_sync": bool(a.rx_sync), "epochs": len(out2["history"]),
+                                 "seconds": round(time.time() - t2, 1), "best_train_loss": best2["train_loss"],
+                                 "best_epoch": best2["epoch"], "test_ber_at_best": best2["test_ber"]}
     print(json.dumps(log), flush=True)
     o = tr.ofdmobj
     S, K, CP = int(hf.nsymbol), int(o.K), int(o.CP)
@@ -87,6 +116,16 @@ def main():
         pl.run(False)
         return float(tr._metrics(pl.metrics_buf, pl.tx_power)["berlin"])
 
+    pl2 = tr2.resident(a.frames) if tr2 is not None else None
+    fs2 = FrameSync(S, K, CP, a.train_sync, a.frames, tr.device, want_metric=False) if (tr2 is not None and a.train_sync != a.W) else fs
+
+    def ber2():
+        """the sync-trained chain on the frames aligned with ITS window"""
+        fs2.run(scratch, out=pl2.x)
+        pl2.bits.copy_(pl.bits)
+        pl2.run(False)
+        return float(tr2._metrics(pl2.metrics_buf, pl2.tx_power)["berlin"])
+
     rows = []
     for ch in CHANNELS:
         fl = copy.deepcopy(hf)
@@ -95,7 +134,7 @@ def main():
         gen.want_noise_power = False
         adv = 0 if gen.mixed else (gen.L - 1) // 2
         for i, snr in enumerate(snrs):
-            got = {"plain": [], "sync": [], "known": []}
+            got = {"plain": [], "sync": [], "known": [], "sync_trained": []}
             hist = {}
             for sd in range(a.seeds):
                 gen.seed, gen.offset = 77 + 13 * i + 1009 * sd, 0
@@ -104,6 +143,8 @@ def main():
                 got["plain"].append(ber())
                 _, off = fs.run(scratch, out=pl.x)
                 got["sync"].append(ber())
+                if tr2 is not None:
+                    got["sync_trained"].append(ber2())
                 for v, c in zip(*[t.tolist() for t in torch.unique(off, return_counts=True)]):
                     hist[int(v)] = hist.get(int(v), 0) + int(c)
                 if not gen.mixed:
@@ -121,11 +162,17 @@ def main():
         json.dump(log, f, indent=1)
         f.write("\n")
     with open(os.path.join(a.out, "syncber_%dmod.md" % nb), "w") as f:
-        f.write("| channel | SNR [dB] | BER plain | BER sync (W = %d) | BER known advance | offsets (share of frames) |\n|---|---|---|---|---|---|\n" % a.W)
         cell = lambda c: "-" if c is None else "%.3g (%.3g .. %.3g)" % (c["ber"], c["min"], c["max"])      # noqa: E731
-        for r in rows:
-            f.write("| %s | %g | %s | %s | %s | %s |\n" % (r["channel"], r["snr_db"], cell(r["plain"]), cell(r["sync"]), cell(r["known"]),
-                                                        ", ".join("%s: %.1f %%" % (k, 100 * v) for k, v in r["offset_share"].items())))
+        shares = lambda r: ", ".join("%s: %.1f %%" % (k, 100 * v) for k, v in r["offset_share"].items())   # noqa: E731
+        if tr2 is None:
+            f.write("| channel | SNR [dB] | BER plain | BER sync (W = %d) | BER known advance | offsets (share of frames) |\n|---|---|---|---|---|---|\n" % a.W)
+            for r in rows:
+                f.write("| %s | %g | %s | %s | %s | %s |\n" % (r["channel"], r["snr_db"], cell(r["plain"]), cell(r["sync"]), cell(r["known"]), shares(r)))
+        else:
+            f.write("| channel | SNR [dB] | plain-trained, plain frames | plain-trained, aligned frames (W = %d) | sync-trained (W = %d), aligned frames |\n"
+                    "|---|---|---|---|---|\n" % (a.W, a.train_sync))
+            for r in rows:
+                f.write("| %s | %g | %s | %s | %s |\n" % (r["channel"], r["snr_db"], cell(r["plain"]), cell(r["sync"]), cell(r["sync_trained"])))
 
 
 if __name__ == "__main__":
