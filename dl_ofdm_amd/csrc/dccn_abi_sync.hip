@@ -50,4 +50,17 @@ int dccn_frame_sync(const float* x, int frames, int S, int K, int CP, int W, int
     return DCCN_OK;
 }
 
+int dccn_frame_sync_cfo(const float* x, int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset,
+                        float* cfo, float* metric, dccn_stream_t stream) {
+    FrameSyncPlan plan;
+    DCCN_TRY(frame_sync_plan(x, frames, S, K, CP, W, out_kin, x_out, offset, metric, &plan));
+    if (!cfo) return DCCN_ERR_INVALID_ARG;
+    DCCN_NO_CHAINS();                         // (the launch carries no chain table: inside a group it would serve chain 0 only)
+    DCCN_TRY(set_max_dynamic_smem((const void*)frame_sync_cfo_kernel, plan.lds));
+    hipLaunchKernelGGL(frame_sync_cfo_kernel, dim3(plan.blocks), dim3(kSyncWaves * kSyncLanes), plan.lds, (hipStream_t)stream,
+                       FrameSyncCfoArgs{plan.args, cfo});
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
 }  // extern "C"

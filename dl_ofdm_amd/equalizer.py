@@ -376,13 +376,13 @@ class EqualizerTrainer:
         ce, mbuf, tx_power, _, _, _, _ = self._forward(x, bits)
         return self._metrics(mbuf, tx_power)
 
-    def receive(self, x, want_llr: bool = False, want_prob: bool = False, sync: int = 0):
+    def receive(self, x, want_llr: bool = False, want_prob: bool = False, sync: int = 0, cfo: bool = False):
         """Raw frames -> packed bits (and LLRs) through the equaliser + frozen receiver, no labels
         (``dccn_eq_receive_step``; see :mod:`dl_ofdm_amd.receive` for the layout).  ``resident(batch).out_eq`` / ``.chest``
         hold what ``eval_step`` writes for the same frames.  ``sync = W > 0``: per-frame timing alignment in front of the step
-        (:func:`dl_ofdm_amd.receive.chain_receive`)."""
+        (:func:`dl_ofdm_amd.receive.chain_receive`); ``cfo=True``: that launch also takes the carrier-frequency offset out."""
         from .receive import chain_receive
-        return chain_receive(self, x, want_llr, want_prob, sync)
+        return chain_receive(self, x, want_llr, want_prob, sync, cfo)
 
     def adam(self) -> dict:
         s = self.adam_state.cpu().numpy()

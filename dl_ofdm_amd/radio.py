@@ -168,6 +168,18 @@ class rayleigh_chan_lte:
         return self.run(inputs)
 
 
+def apply_cfo(x: np.ndarray, eps, K: int) -> np.ndarray:
+    """A carrier-frequency offset of ``eps`` subcarrier spacings (scalar or ``[frames]``) on frames ``x [frames, S, K + CP, 2]``:
+    float32 of ``x[n] * exp(+2 pi i eps n / K)``, n running over the whole frame (0 .. S (K + CP) - 1), multiplied in fp64.
+    The reference models no such impairment; it is what ``dccn_frame_sync_cfo`` estimates and removes."""
+    x = np.asarray(x)
+    frames = x.shape[0]
+    y = (x[..., 0].astype(np.float64) + 1j * x[..., 1].astype(np.float64)).reshape(frames, -1)
+    e = np.broadcast_to(np.asarray(eps, dtype=np.float64).reshape(-1, 1), (frames, 1))
+    y = y * np.exp(2j * np.pi * e * np.arange(y.shape[1], dtype=np.float64)[None, :] / float(K))
+    return np.stack([y.real, y.imag], axis=-1).reshape(x.shape).astype(np.float32)
+
+
 def AWGN_channel_np(inputs: np.ndarray, SNR):
     """Normalise the batch to unit mean IQ power, add complex white noise at ``SNR`` dB
     (per frame, [n,1]); returns (noisy float64 [n,S,n_sc,2], mean noise power)  (radio.py:513-526)."""

@@ -62,9 +62,10 @@ class ReceiveResult:
     """Device tensors of one receive call (they are the receiver's resident buffers: the next call overwrites them)."""
 
     def __init__(self, packed: torch.Tensor, llr: Optional[torch.Tensor], prob: Optional[torch.Tensor], D: int, nbits: int,
-                 offset: Optional[torch.Tensor] = None):
+                 offset: Optional[torch.Tensor] = None, cfo: Optional[torch.Tensor] = None):
         self.packed, self.llr, self.prob, self.D, self.nbits = packed, llr, prob, int(D), int(nbits)
         self.offset = offset        # int32 [frames]: the timing offsets of a call with sync > 0 (None otherwise)
+        self.cfo = cfo              # float32 [frames]: the carrier-frequency offsets of a call with cfo=True (None otherwise)
 
     def bits(self) -> torch.Tensor:
         """``uint8 [frames, D, nbits]``, unpacked on the device."""
@@ -131,8 +132,9 @@ class RxReceiver:
     def close_graph(self):
         """(nothing captured: lets a :class:`~dl_ofdm_amd.session.Session` keep receivers next to its engines)"""
 
-    def _frame_sync(self, n_sc: int, W: int):
-        """the alignment stage for full frames of ``n_sc`` samples per symbol, writing this receiver's ``x``"""
+    def _frame_sync(self, n_sc: int, W: int, cfo: bool = False):
+        """the alignment stage (``cfo``: with the carrier-frequency offset taken out) for full frames of ``n_sc`` samples per
+        symbol, writing this receiver's ``x``"""
         from .sync import FrameSync
         kin = self.dims.kin
         if self.CP is not None:
@@ -144,51 +146,65 @@ class RxReceiver:
         K = n_sc - CP
         if kin not in (n_sc, K):
             raise _lib.DccnError("receive(sync=W): frames of %d samples per symbol (CP = %d) do not fit kin = %d" % (n_sc, CP, kin))
-        key = (K, CP, W)
+        key = (K, CP, W, bool(cfo))
         if key not in self._syncs:
-            self._syncs[key] = FrameSync(self.dims.S, K, CP, W, self.batch, self.device, out_kin=kin, want_metric=False)
+            self._syncs[key] = FrameSync(self.dims.S, K, CP, W, self.batch, self.device, out_kin=kin, want_metric=False, cfo=cfo)
         return self._syncs[key]
 
-    def receive(self, x=None, sync: int = 0) -> ReceiveResult:
+    def receive(self, x=None, sync: int = 0, cfo: bool = False) -> ReceiveResult:
         """Stage ``x`` (``None``: whatever ``self.x`` holds) and run one receive step on the current stream.
 
         ``sync = W > 0``: ``x`` is a device tensor of FULL frames ``[batch, S, K + CP, 2]`` that may sit up to ``W`` samples off
         the FFT window.  The alignment launch (:class:`~dl_ofdm_amd.sync.FrameSync`) takes the place of the copy: it writes
         each frame, rotated by its own estimated offset, straight into ``self.x`` (only the K samples behind each prefix when
-        ``dims.kin == K``); the receive step behind it is unchanged.  ``result.offset`` holds the offsets."""
-        offset = None
+        ``dims.kin == K``); the receive step behind it is unchanged.  ``result.offset`` holds the offsets.
+
+        ``cfo=True`` (needs ``sync > 0``): the same launch also estimates each frame's carrier-frequency offset from its prefix
+        and writes the frames with it taken out (``FrameSync(..., cfo=True)``); ``result.cfo`` holds the estimates, in
+        subcarrier spacings."""
+        offset = est = None
+        if cfo and not sync:
+            raise _lib.DccnError("receive(cfo=True) needs sync = W > 0: the offset is read off the timing correlation")
         if sync:
             if not isinstance(x, torch.Tensor) or x.dim() != 4:
                 raise _lib.DccnError("receive(sync=W) takes a device tensor [batch, S, K + CP, 2]")
-            _, offset = self._frame_sync(int(x.shape[2]), int(sync)).run(x, out=self.x)
+            fs = self._frame_sync(int(x.shape[2]), int(sync), bool(cfo))
+            _, offset = fs.run(x, out=self.x)
+            est = fs.cfo
         elif x is not None:
             self.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(self.x.shape), non_blocking=True)
         check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
-        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset)
+        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, est)
 
 
-def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: int = 0) -> ReceiveResult:
+def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: int = 0, cfo: bool = False) -> ReceiveResult:
     """Equaliser + frozen receiver chain (``EqualizerTrainer.receive``): ``dccn_eq_receive_step`` on the trainer's resident
     plan of this batch size.  ``out_eq`` / ``chest`` of the plan hold what ``eval_step`` writes for the same frames.
 
     ``sync = W > 0``: as :meth:`RxReceiver.receive` -- ``x`` is a device tensor ``[batch, S, K + CP, 2]``, and the alignment
-    launch writes the rotated frames into the plan's ``x`` in place of the copy; ``result.offset`` holds the offsets."""
+    launch writes the rotated frames into the plan's ``x`` in place of the copy; ``result.offset`` holds the offsets.
+    ``cfo=True`` (needs ``sync > 0``): that launch also takes each frame's carrier-frequency offset out; ``result.cfo``."""
     if not tr.fused_ok:
         raise _lib.DccnError("the chain's receive path needs the fused equaliser step")
+    if cfo and not sync:
+        raise _lib.DccnError("chain_receive(cfo=True) needs sync = W > 0: the offset is read off the timing correlation")
     batch = int(x.shape[0]) if isinstance(x, torch.Tensor) else int(np.shape(x)[0])
     pl = tr.resident(batch)
-    offset = None
+    offset = est = None
     if sync:
         from .sync import FrameSync
         syncs = pl.__dict__.setdefault("_frame_syncs", {})
-        if int(sync) not in syncs:
+        key = (int(sync), True) if cfo else int(sync)
+        if key not in syncs:
             o = tr.ofdmobj
-            syncs[int(sync)] = FrameSync(int(tr.FLAGS.nsymbol), int(o.K), int(o.CP), int(sync), batch, tr.device, want_metric=False)
-        _, offset = syncs[int(sync)].run(x, out=pl.x)
+            syncs[key] = FrameSync(int(tr.FLAGS.nsymbol), int(o.K), int(o.CP), int(sync), batch, tr.device, want_metric=False,
+                                   cfo=bool(cfo))
+        _, offset = syncs[key].run(x, out=pl.x)
+        est = syncs[key].cfo
     else:
         pl.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(pl.x.shape), non_blocking=True)
     packed, llr, prob = pl.receive(want_llr, want_prob)
-    return ReceiveResult(packed, llr, prob, int(tr.ofdmobj.frame_size), int(tr.FLAGS.nbits), offset)
+    return ReceiveResult(packed, llr, prob, int(tr.ofdmobj.frame_size), int(tr.FLAGS.nbits), offset, est)
 
 
 def group_receive(group, xs) -> list:
@@ -197,5 +213,6 @@ def group_receive(group, xs) -> list:
     One :class:`ReceiveResult` per chain, bit for bit what :func:`chain_receive` returns for that chain alone.
 
     The grouped call has no ``sync`` argument: a caller whose links need timing alignment keeps one
-    :class:`~dl_ofdm_amd.sync.FrameSync` per link and aligns each link's frames in front of this call."""
+    :class:`~dl_ofdm_amd.sync.FrameSync` per link (``cfo=True`` where the link's carrier-frequency offset is to go as well) and
+    aligns each link's frames in front of this call."""
     return group.receive(xs)

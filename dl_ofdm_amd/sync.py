@@ -7,6 +7,12 @@ which they correlate best is the frame's own timing -- per frame, so it also ser
 frame (``mixRayleigh``).  The frame is taken as circular, exactly as ``align_window``'s ``torch.roll`` treats it:
 ``aligned[f] = torch.roll(x[f].view(T, 2), -offset[f], 0)``.
 
+``FrameSync(..., cfo=True)`` is the same launch with the carrier-frequency offset taken out as well (``dccn_frame_sync_cfo``): a
+frame ``s[n] exp(+2 pi i eps n / K)`` turns the prefix correlation by ``exp(-2 pi i eps)``, so the angle of the correlation at the
+chosen lag estimates ``eps`` (in subcarrier spacings, unambiguous for ``|eps| < 1/2``), and sample ``n`` of the aligned frame
+leaves multiplied by ``exp(-2 pi i cfo n / K)``.  The frame is circular here too: the ``|offset|`` samples that wrap carry a phase
+step of ``2 pi eps T / K`` against their neighbours.
+
 There is no CPU or PyTorch fallback: an unsupported shape or a tensor that is not on the GPU raises :class:`DccnError`.
 """
 from __future__ import annotations
@@ -41,11 +47,13 @@ class FrameSync:
     ``x``: device tensor ``float32 [frames, S, K + CP, 2]``.  ``out_kin``: ``K + CP`` (default: the aligned frames) or ``K`` (the
     ``K`` samples behind each symbol's prefix, the input of a receiver built with ``cp=False``).  ``offset`` (``int32
     [frames]``), ``metric`` (``float32 [frames, 2 W + 1]``: the estimator's value at the lags ``-W .. W``) and the output
-    buffer are resident: the next ``run`` overwrites them.
+    buffer are resident: the next ``run`` overwrites them.  ``cfo=True``: ``run`` and ``offsets`` also estimate every frame's
+    carrier-frequency offset into ``self.cfo`` (``float32 [frames]``, subcarrier spacings, resident) and ``run`` writes the
+    frames with it taken out; ``run`` keeps returning ``(aligned, offset)``.
     """
 
     def __init__(self, S: int, K: int, CP: int, W: int, frames: int, device="cuda", out_kin: Optional[int] = None,
-                 want_metric: bool = True):
+                 want_metric: bool = True, cfo: bool = False):
         self.lib = _lib.load()
         self.S, self.K, self.CP, self.W, self.frames = int(S), int(K), int(CP), int(W), int(frames)
         self.out_kin = self.K + self.CP if out_kin is None else int(out_kin)
@@ -60,6 +68,7 @@ class FrameSync:
                             % (self.out_kin, self.frames))
         self.offset = torch.zeros(self.frames, dtype=torch.int32, device=self.device)
         self.metric = (torch.zeros(self.frames, 2 * self.W + 1, dtype=torch.float32, device=self.device) if want_metric else None)
+        self.cfo = torch.zeros(self.frames, dtype=torch.float32, device=self.device) if cfo else None
         self.out = None         # allocated by the first run() that is not given a destination
 
     def _stream(self):
@@ -73,6 +82,16 @@ class FrameSync:
             raise DccnError("FrameSync.run: x must be a contiguous float32 %r tensor, got %s %r" % (want, x.dtype, tuple(x.shape)))
         return x
 
+    def _launch(self, x: torch.Tensor, out: Optional[torch.Tensor]) -> None:
+        """the one launch: ``dccn_frame_sync``, or ``dccn_frame_sync_cfo`` of a stage built with ``cfo=True``"""
+        head = (x.data_ptr(), self.frames, self.S, self.K, self.CP, self.W, self.out_kin, None if out is None else out.data_ptr(),
+                self.offset.data_ptr())
+        tail = (None if self.metric is None else self.metric.data_ptr(), self._stream())
+        if self.cfo is None:
+            check(self.lib.dccn_frame_sync(*head, *tail), "dccn_frame_sync")
+        else:
+            check(self.lib.dccn_frame_sync_cfo(*head, self.cfo.data_ptr(), *tail), "dccn_frame_sync_cfo")
+
     def run(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Estimate every frame's offset and write the aligned frames to ``out`` (``None``: this object's own buffer), on the
         current stream.  ``out`` must not overlap ``x``."""
@@ -85,15 +104,10 @@ class FrameSync:
         elif (not isinstance(out, torch.Tensor) or out.device != x.device or out.dtype != torch.float32
               or tuple(out.shape) != want or not out.is_contiguous()):
             raise DccnError("FrameSync.run: out must be a contiguous float32 %r tensor on %s" % (want, x.device))
-        check(self.lib.dccn_frame_sync(x.data_ptr(), self.frames, self.S, self.K, self.CP, self.W, self.out_kin, out.data_ptr(),
-                                       self.offset.data_ptr(), None if self.metric is None else self.metric.data_ptr(),
-                                       self._stream()), "dccn_frame_sync")
+        self._launch(x, out)
         return out, self.offset
 
     def offsets(self, x: torch.Tensor) -> torch.Tensor:
-        """The offsets alone (no frame is written)."""
-        x = self._device_frames(x)
-        check(self.lib.dccn_frame_sync(x.data_ptr(), self.frames, self.S, self.K, self.CP, self.W, self.out_kin, None,
-                                       self.offset.data_ptr(), None if self.metric is None else self.metric.data_ptr(),
-                                       self._stream()), "dccn_frame_sync")
+        """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``."""
+        self._launch(self._device_frames(x), None)
         return self.offset

@@ -1034,6 +1034,20 @@ int dccn_channel_groups_awgn(const float* tx, const dccn_channel_group* groups /
 int dccn_frame_sync_supported(int S, int K, int CP, int W);
 int dccn_frame_sync(const float* x, int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset,
                     float* metric, dccn_stream_t stream);
+/* The same launch with the carrier-frequency offset (CFO) estimated from the angle the timing metric throws away, and taken out
+ * of the frame on its way to x_out.  A frame y[n] = s[n] exp(+2 pi i eps n / K) has p[n] = |s[n]|^2 exp(-2 pi i eps) on its
+ * prefix, so (van de Beek's ML estimate of the fractional offset)
+ *     cfo = -atan2(Im Gamma(offset), Re Gamma(offset)) / (2 pi)       [subcarrier spacings; 0 where Gamma = 0]
+ *     out[n] = y[(n + offset) mod T] * exp(-2 pi i cfo n / K)         n = 0 .. T-1, the position in the ALIGNED frame
+ * offset and metric are dccn_frame_sync's, bit for bit; cfo float32[frames]; x_out as above (out_kin == K stores the same
+ * out[n], only the K samples behind each symbol's prefix).  Unambiguous for |eps| < 1/2.  The frame is taken as circular: the
+ * |offset| samples that wrap carry a phase step of 2 pi eps T / K against their neighbours.  A frame of NaN / Inf samples does
+ * not fault: its offset stays inside [-W, W] and its cfo is whatever atan2f returns.  One launch, no workspace, no atomics, the
+ * sums and the phase in a fixed order (two runs give the same bits).
+ * Refused with DCCN_ERR_INVALID_ARG before anything is launched wherever dccn_frame_sync refuses, and for cfo NULL; inside a
+ * chain group DCCN_ERR_UNSUPPORTED (the launch carries no chain table). */
+int dccn_frame_sync_cfo(const float* x, int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset,
+                        float* cfo, float* metric, dccn_stream_t stream);
 
 /* ==== host utility: CRC32C (Castagnoli), the checksum of TensorFlow's tensor-bundle checkpoints =========
  * (tf.train.Saver files the reference writes at dev/py/ofdmreceiver_np.py:271).

@@ -14,6 +14,9 @@
         the same receive call on full frames resident on the device: (copy) receive(x), whose first launch copies the frames
         into the receiver, against (sync) receive(x, sync=W), where the alignment launch (dccn_frame_sync) takes the copy's
         place, and (step) receive() with neither; same shapes, alternation and repeats
+    python tools/rxbench.py --sync 3 --cfo [--out FILE]
+        the same, plus (cfo) receive(x, sync=W, cfo=True): the launch that also estimates and removes the carrier-frequency
+        offset (dccn_frame_sync_cfo) in the alignment launch's place, and that launch alone
 
 Shapes: 1170 frames QPSK and 16-QAM, and one 20 000-frame QPSK sweep batch (N = 64).  Every shape runs in a child process of
 its own under a time limit; the parent never opens the GPU and stops at the first child that fails.  Times are medians over
@@ -127,9 +130,10 @@ def timed(variants, iters, repeats):
     return us, spread
 
 
-def run_sync(frames, nbits, W, iters, repeats):
+def run_sync(frames, nbits, W, iters, repeats, cfo=False):
     """receive(x) (copy + step) against receive(x, sync=W) (alignment launch + step) and receive() (the step alone), on full
-    frames [frames, S, K + CP, 2] resident on the device; the first two must agree where every offset is 0 before anything is timed"""
+    frames [frames, S, K + CP, 2] resident on the device; the first two must agree where every offset is 0 before anything is timed.
+    ``cfo``: also receive(x, sync=W, cfo=True), which must agree too (an exact prefix has no offset of either kind)"""
     import numpy as np
     import torch
     from dl_ofdm_amd import _lib
@@ -148,6 +152,12 @@ def run_sync(frames, nbits, W, iters, repeats):
     fs = FrameSync(S, F, CP, W, frames, "cuda", want_metric=False)
     variants = {"copy": lambda: rc.receive(x), "sync": lambda: rc.receive(x, sync=W), "step": rc.receive,
                 "sync_alone": lambda: fs.run(x), "copy_alone": lambda: rc.x.copy_(x)}
+    if cfo:
+        c = rc.receive(x, sync=W, cfo=True)
+        assert int(c.offset.abs().max()) == 0 and float(c.cfo.abs().max()) == 0.0 and torch.equal(a, c.packed)
+        fc = FrameSync(S, F, CP, W, frames, "cuda", want_metric=False, cfo=True)
+        variants["cfo"] = lambda: rc.receive(x, sync=W, cfo=True)
+        variants["cfo_alone"] = lambda: fc.run(x)
     us, spread = timed(variants, iters, repeats)
     moved = 2 * frames * S * KIN * 2 * 4
     return {"frames": frames, "nbits": nbits, "W": W, "iters": iters, "repeats": repeats, "us": us, "spread": spread,
@@ -244,15 +254,18 @@ def main():
     ap.add_argument("--one-chains", default=None, help="nbits,nbits,...: measure this group in this process")
     ap.add_argument("--out", default=None, help="--chains / --sync: also write the result document to this file")
     ap.add_argument("--sync", type=int, default=0, help="W: time receive(x) against receive(x, sync=W) on every shape")
+    ap.add_argument("--cfo", action="store_true", help="with --sync: also time receive(x, sync=W, cfo=True)")
     a = ap.parse_args()
     if a.one_chains:
         print(json.dumps(run_chains([int(v) for v in a.one_chains.split(",")], a.frames, a.iters, a.repeats)))
         return 0
     if a.chains:
         return main_chains(a)
+    if a.cfo and not a.sync:
+        ap.error("--cfo needs --sync W")
     if a.one:
         fr, nb = (int(v) for v in a.one.split(","))
-        print(json.dumps(run_sync(fr, nb, a.sync, a.iters, a.repeats) if a.sync else run_one(fr, nb, a.iters, a.repeats, a.only)))
+        print(json.dumps(run_sync(fr, nb, a.sync, a.iters, a.repeats, a.cfo) if a.sync else run_one(fr, nb, a.iters, a.repeats, a.only)))
         return 0
     res = []
     for fr, nb in SHAPES:
@@ -261,7 +274,7 @@ def main():
         if a.only:
             cmd += ["--only", a.only]
         if a.sync:
-            cmd += ["--sync", str(a.sync)]
+            cmd += ["--sync", str(a.sync)] + (["--cfo"] if a.cfo else [])
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         if r.returncode != 0:               # nothing more is started on the GPU after a failure
             sys.stderr.write(r.stderr[-2000:])
@@ -271,7 +284,9 @@ def main():
     if a.sync:
         doc = {"bench": "rxbench.sync", "variants": {"copy": "receive(x): copy + step", "sync": "receive(x, sync=W): alignment launch + step",
                                                      "step": "receive(): the step alone", "sync_alone": "FrameSync.run(x)",
-                                                     "copy_alone": "x.copy_ alone"},
+                                                     "copy_alone": "x.copy_ alone",
+                                                     "cfo": "receive(x, sync=W, cfo=True): alignment + CFO launch + step (--cfo)",
+                                                     "cfo_alone": "FrameSync(cfo=True).run(x) (--cfo)"},
                "unit": "us per call (median over repeats of the mean of `iters` back-to-back calls); spread = (max - min) / median",
                "shapes": res}
         print(json.dumps(doc))

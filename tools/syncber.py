@@ -16,9 +16,22 @@ on a basic receiver whose own training frames were aligned too -- and adds the c
 
     sync-trained    that chain on the aligned frames
 
+``--cfo EPS[,EPS...]`` asks another question of the same trained chain, through the label-free receive path: every evaluation frame
+gets a carrier-frequency offset of its own, eps ~ U(-EPS, EPS) subcarrier spacings (radio.apply_cfo's statement, on the device in
+fp64), and the chain's BER is reported on AWGN / EPA / EVA / ETU for
+
+    no offset      receive(x) on the frames before the impairment (the JSON also carries ``no_offset_eval``: the labelled
+                   evaluation step's BER on the same frames, which the receive path's bits must reproduce)
+    plain          receive(x) on the impaired frames
+    sync           receive(x, sync=W)
+    sync + cfo     receive(x, sync=W, cfo=True): the launch that estimates the offset from the prefix correlation and removes it
+
+next to the median and the 95th percentile of |estimate - eps| over the frames.
+
 No threshold: the numbers are the result.
 
     python tools/syncber.py --nbits 2 --out syncber_out [--load CKPT --rx_load CKPT] [--seeds 3] [--train_sync 3 [--rx_sync]]
+    python tools/syncber.py --nbits 2 --cfo 0.05,0.2 --out syncber_out
 """
 import argparse
 import copy
@@ -33,6 +46,76 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 CHANNELS = ("EPA", "EVA", "ETU", "mixRayleigh")
+CFO_CHANNELS = ("AWGN", "EPA", "EVA", "ETU")
+
+
+def apply_cfo_device(x, eps, K):
+    """radio.apply_cfo on the device: float32 of x[n] exp(+2 pi i eps n / K), n over the whole frame, multiplied in fp64"""
+    import torch
+    frames = x.shape[0]
+    y = torch.view_as_complex(x.to(torch.float64).reshape(frames, -1, 2))
+    n = torch.arange(y.shape[1], dtype=torch.float64, device=x.device)
+    ang = 2.0 * torch.pi * eps.to(torch.float64)[:, None] * n[None, :] / float(K)
+    return torch.view_as_real(y * torch.polar(torch.ones_like(ang), ang)).to(torch.float32).reshape(x.shape)
+
+
+def cfo_rows(a, tr, hf, snrs, log):
+    """the --cfo table: one row per (EPS, channel, SNR)"""
+    import torch
+    from dl_ofdm_amd import ofdm
+    from dl_ofdm_amd.datagen import DeviceDataGen
+    K = int(tr.ofdmobj.K)
+    pl = tr.resident(a.frames)
+    clean = torch.empty_like(pl.x)
+    rows = []
+
+    def ber(res):
+        return float((res.bits().to(torch.int32) != pl.bits).to(torch.float32).mean())
+
+    for EPS in [float(v) for v in a.cfo.split(",")]:
+        for ch in CFO_CHANNELS:
+            fl = copy.deepcopy(hf)
+            fl.channel = ch
+            gen = DeviceDataGen(fl, ofdm.ofdm_tx(fl), device=tr.device, seed=77)
+            gen.want_noise_power = False
+            for i, snr in enumerate(snrs):
+                got = {"no_offset": [], "no_offset_eval": [], "plain": [], "sync": [], "sync_cfo": []}
+                errs = []
+                for sd in range(a.seeds):
+                    gen.seed, gen.offset = 77 + 13 * i + 1009 * sd, 0
+                    gen.make_batch(a.frames, snr, out_x=clean, out_bits=pl.bits)
+                    g = torch.Generator(device=tr.device)
+                    g.manual_seed(4242 + 13 * i + 1009 * sd)
+                    eps = (torch.rand(a.frames, generator=g, device=tr.device, dtype=torch.float64) * 2.0 - 1.0) * EPS
+                    x = apply_cfo_device(clean, eps, K)
+                    got["no_offset"].append(ber(tr.receive(clean)))
+                    pl.run(False)       # cross-check: the labelled evaluation step on the frames that receive call staged
+                    got["no_offset_eval"].append(float(tr._metrics(pl.metrics_buf, pl.tx_power)["berlin"]))
+                    got["plain"].append(ber(tr.receive(x)))
+                    got["sync"].append(ber(tr.receive(x, sync=a.W)))
+                    res = tr.receive(x, sync=a.W, cfo=True)
+                    got["sync_cfo"].append(ber(res))
+                    d = res.cfo.to(torch.float64) - eps
+                    errs.append((d - torch.round(d)).abs())
+                e = torch.cat(errs)
+                row = {"eps_max": EPS, "channel": ch, "snr_db": snr,
+                       "cfo_abs_err": {"median": float(e.median()), "p95": float(torch.quantile(e, 0.95))}}
+                for k, v in got.items():
+                    row[k] = {"ber": float(np.mean(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    log["cfo_rows"] = rows
+    with open(os.path.join(a.out, "syncber_cfo_%dmod.json" % a.nbits), "w") as f:
+        json.dump(log, f, indent=1)
+        f.write("\n")
+    with open(os.path.join(a.out, "syncber_cfo_%dmod.md" % a.nbits), "w") as f:
+        cell = lambda c: "%.3g (%.3g .. %.3g)" % (c["ber"], c["min"], c["max"])      # noqa: E731
+        f.write("| EPS | channel | SNR [dB] | BER no offset | BER plain | BER sync (W = %d) | BER sync + cfo | abs(est - eps): median, p95 |\n"
+                "|---|---|---|---|---|---|---|---|\n" % a.W)
+        for r in rows:
+            f.write("| %g | %s | %g | %s | %s | %s | %s | %.2g, %.2g |\n"
+                    % (r["eps_max"], r["channel"], r["snr_db"], cell(r["no_offset"]), cell(r["plain"]), cell(r["sync"]),
+                       cell(r["sync_cfo"]), r["cfo_abs_err"]["median"], r["cfo_abs_err"]["p95"]))
 
 
 def main():
@@ -49,6 +132,8 @@ def main():
     ap.add_argument("--rx_load", default=None, help="basic-receiver checkpoint stem that goes with --load")
     ap.add_argument("--train_sync", type=int, default=0, help="W > 0: also train an equaliser with sync=W and evaluate it on aligned frames")
     ap.add_argument("--rx_sync", action="store_true", help="with --train_sync: the second chain's basic receiver trains on aligned frames too")
+    ap.add_argument("--cfo", default=None, help="EPS[,EPS...]: per-frame carrier-frequency offsets ~ U(-EPS, EPS) subcarrier spacings "
+                                                "on the evaluation frames; reports the receive path with and without cfo=True")
     ap.add_argument("--out", default="syncber_out")
     a = ap.parse_args()
     import torch
@@ -106,6 +191,9 @@ def main():
                                  "seconds": round(time.time() - t2, 1), "best_train_loss": best2["train_loss"],
                                  "best_epoch": best2["epoch"], "test_ber_at_best": best2["test_ber"]}
     print(json.dumps(log), flush=True)
+    if a.cfo:
+        cfo_rows(a, tr, hf, snrs, log)
+        return
     o = tr.ofdmobj
     S, K, CP = int(hf.nsymbol), int(o.K), int(o.CP)
     pl = tr.resident(a.frames)
