@@ -163,6 +163,23 @@ struct Tile16 {
         }
     }
 
+    // ICONTIG, in front of the first store_piece of a unit: the unit's four loaded float4s of set s become opaque HERE.
+    // A store_piece row takes one component of each of them, so its ds_write_b128 is issued from a register tuple that
+    // has to be assembled with moves.  In a loop that carries the staging registers the compiler otherwise places part of
+    // those moves at the end of the PREVIOUS iteration, and with them a wait for loads that were only just issued
+    // (s_waitcnt vmcnt(0) on the back edge).  Behind this point the moves depend on the asm's results: they, and the
+    // counted wait for the unit's loads, stay at the store site.  No instruction, same values.
+    __device__ __forceinline__ void pin_unit(int v, int s) {
+        if constexpr (IC) {
+            if ((v & 3) != 0) return;
+            f32x4 c0 = __builtin_bit_cast(f32x4, r[s][v]), c1 = __builtin_bit_cast(f32x4, r[s][v + 1]);
+            f32x4 c2 = __builtin_bit_cast(f32x4, r[s][v + 2]), c3 = __builtin_bit_cast(f32x4, r[s][v + 3]);
+            asm volatile("" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3));
+            r[s][v] = __builtin_bit_cast(float4, c0); r[s][v + 1] = __builtin_bit_cast(float4, c1);
+            r[s][v + 2] = __builtin_bit_cast(float4, c2); r[s][v + 3] = __builtin_bit_cast(float4, c3);
+        }
+    }
+
     // v must be a compile-time constant after unrolling
     template <bool MASKED>
     __device__ __forceinline__ void store_piece(int v, float* __restrict__ lds, int s = 0) const {
@@ -248,6 +265,13 @@ constexpr int tail_batch_width(const int ncell) {
 // PD = 2: global loads run TWO k-tiles ahead of the MFMAs (second staging register set, loop unrolled by two): with a
 // single block per CU nothing else covers the ~0.6 us load latency, which is longer than half a 48x64x64 tile's MFMA
 // time; needs the whole k range on the fast loaders (else the block falls back to the PD = 1 schedule).
+// The PD = 2 schedule as compiled for the 48x64 dense forward + tail (profiles/dense_kloop.md): per k-tile 16 steps of 3
+// MFMAs; the 7 loads of k-tile t+2 go out in front of steps 0..6; the 7 LDS stores of k-tile t+1 stand behind steps 8..14,
+// each behind a counted vmcnt (13, 12, 11 for the A pieces, 7 for the B unit) -- nothing in the paired loop waits for
+// vmcnt(0), the transposed B unit is assembled at its store (Tile16::pin_unit); the k-tile ends with lgkmcnt(0) + s_barrier, the next
+// one requests group 0's four fragments, then group 1's, and its first MFMA waits for its own four (lgkmcnt(4)).
+// Measured and NOT kept: the barrier inside the k-tile (stores behind steps 3..9 or 6..12, barrier behind step 10 / 13,
+// the next k-tile's first fragments read behind it into registers of their own) -- 0.6 to 1.4 us slower per launch.
 template <int KA, int KB, int WGM, int WGN, int TM, int TN, int BK, int KS, int COLSUM, int EPI, int NB, bool BWD,
           int PD = 1>
 __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiParams& tp, const int L, const int T,
@@ -402,6 +426,9 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
         for (int a = 0; a < TM; ++a) fa[0][a] = *reinterpret_cast<const float4*>(As + a * 16 * LDA);
 #pragma unroll
         for (int b = 0; b < TN; ++b) fb[0][b] = *reinterpret_cast<const float4*>(Bs + b * 16 * LDB);
+        // PD = 2 kernels: group 0's own fragments are requested first, so its MFMAs wait for these TM + TN reads only; left
+        // to itself the compiler orders the reads of groups 0 and 1 by address and the first MFMA waits for all but one
+        if constexpr (PD == 2) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int g = 0; g < NGS; ++g) {
             if (g + 1 < NGS && !(GEMM16_ABL & 8)) {
@@ -433,8 +460,12 @@ __device__ __forceinline__ void gemm16_block(const GemmParams& p, const TailEpiP
                     if (step >= HALF) {
 #pragma unroll
                         for (int q = (step - HALF) * LPS; q < (step - HALF + 1) * LPS && q < PA + PB; ++q) {
-                            if (q < PA) ta.template store_piece<SMODE == PF_MASKED>(q, An, SSET);
-                            else tb.template store_piece<SMODE == PF_MASKED>(q - PA, Bn, SSET);
+                            if (q < PA) {
+                                ta.template store_piece<SMODE == PF_MASKED>(q, An, SSET);
+                            } else {
+                                if constexpr (PD == 2) tb.pin_unit(q - PA, SSET);
+                                tb.template store_piece<SMODE == PF_MASKED>(q - PA, Bn, SSET);
+                            }
                         }
                     }
                 }
