@@ -279,6 +279,8 @@ def _trainer(nbits=2, seed=21, cp=True, nfft=64, longcp=True, rx_bias=0.0):
 
 @pytest.mark.parametrize("mode", ["fused-graph", "fused-eager", "composed"])
 def test_trainer_step_gradients_and_adam(mode):
+    """(the optimizer launch itself -- v, every element, every branch of its job table, the riders, the stair, the coefficient
+    forms, chains at different steps -- is held to the oracle from a resumed state in tests/test_gpu_eq_optimizer.py)"""
     fused, graph = mode != "composed", mode == "fused-graph"
     F, tx, ecfg, rcfg, pe, pr, tr = _trainer()
     rng = np.random.RandomState(7)
