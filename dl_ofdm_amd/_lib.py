@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -313,6 +314,13 @@ def load() -> C.CDLL:
         if lib.dccn_set_tuning(int(k), int(v)) != 0:
             raise DccnError("DCCN_TUNE: bad tuning pair %r" % kv)
     return lib
+
+
+# Held over "device synchronize + dccn_*_graph_create".  hipDeviceSynchronize fails with hipErrorStreamCaptureUnsupported
+# while ANY stream of the process is capturing, whatever the capture mode and whichever thread began it, so two host threads
+# that each train on a stream of their own (config5.train_models) must not interleave one's capture with the other's
+# synchronize.  Captures are rare (once per plan and mode) and short: the lock orders nothing else.
+capture_lock = threading.Lock()
 
 
 def check(status: int, what: str = "dccn call") -> None:

@@ -9,7 +9,8 @@
 // of it launch ramp + drain) behind a 4.2 MB dfft round trip through HBM.  Here the same 0.335 GFLOP ride on tiles that
 // already hold dfft in registers: one launch, one boundary and the dfft write + read less per step.
 //
-// Epilogue of a dX tile (64 frames x 64 columns of dfft, columns = one half of symbol s):
+// Epilogue of a dX tile (64 frames x 64 columns of dfft; 2F is a multiple of 64, so the columns [n0, n0 + 64) lie inside ONE
+// symbol s = n0 / 2F: tile n0 / 64 - s * (2F / 64) of its 2F / 64 -- one half of symbol s at F = 64, all of it at F = 32):
 //   dfft tile (accumulators)      -> LDS D[k = frame][n]           (rows past the batch zeroed)
 //   x_norm[frame, s, 0..2kin)     -> LDS X[k = frame][m]           (float4 copies)
 //   partial[m][n] = sum_k X[k][m] * D[k][n]   on v_mfma_f32_16x16x4_f32 in the k-major form of gemm_kmajor.h:

@@ -349,10 +349,11 @@ class RxEngine:
         if self._graph is None or self._graph_mode != mode:
             self.close_graph()
             g = C.c_void_p(0)
-            torch.cuda.synchronize(self.device)
             bufs = self._pipe_buffers(0, False, 1 if mode & 8 else 0, False) if mode & 4 else self.buffers
-            check(self.lib.dccn_rx_graph_create(C.byref(self.shape), C.byref(bufs), mode & 3, self.hp,
-                                                self._stream(), C.byref(g)), "dccn_rx_graph_create")
+            with _lib.capture_lock:
+                torch.cuda.synchronize(self.device)
+                check(self.lib.dccn_rx_graph_create(C.byref(self.shape), C.byref(bufs), mode & 3, self.hp,
+                                                    self._stream(), C.byref(g)), "dccn_rx_graph_create")
             self._graph, self._graph_mode = g, mode
         check(self.lib.dccn_rx_graph_launch(self._graph, self._stream()), "dccn_rx_graph_launch")
 

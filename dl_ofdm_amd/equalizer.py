@@ -142,9 +142,10 @@ class _FusedPlan:
         key = mode if pipe is None else (mode, pipe)
         if key not in self.graphs:
             g = C.c_void_p(0)
-            torch.cuda.synchronize(tr.device)
-            check(lib.dccn_eq_graph_create(C.byref(self.shape), C.byref(bufs), mode, tr.hp, self._stream(),
-                                           C.byref(g)), "dccn_eq_graph_create")
+            with _lib.capture_lock:
+                torch.cuda.synchronize(tr.device)
+                check(lib.dccn_eq_graph_create(C.byref(self.shape), C.byref(bufs), mode, tr.hp, self._stream(),
+                                               C.byref(g)), "dccn_eq_graph_create")
             self.graphs[key] = g
         check(lib.dccn_rx_graph_launch(self.graphs[key], self._stream()), "dccn_rx_graph_launch")
 

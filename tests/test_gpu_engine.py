@@ -33,13 +33,22 @@ def make_case(batch, nbits, kin=80, F=64, D=320, S=7, seed=0):
     return dims, cfg, x, bits, p
 
 
-CASES = [  # (name, batch frames, nbits, kin, F, D)
-    ("C1_bpsk_256sym", 36, 1, 80, 64, 320),
-    ("C2_qpsk_8192sym", 1170, 2, 80, 64, 320),
-    ("C3_16qam", 1170, 4, 80, 64, 320),
-    ("qam8_nocp", 100, 3, 64, 64, 320),
-    ("ragged", 13, 2, 20, 12, 50),
+CASES = [  # (name, batch frames, nbits, kin, F, D, S)
+    ("C1_bpsk_256sym", 36, 1, 80, 64, 320, 7),
+    ("C2_qpsk_8192sym", 1170, 2, 80, 64, 320, 7),
+    ("C3_16qam", 1170, 4, 80, 64, 320, 7),
+    ("qam8_nocp", 100, 3, 64, 64, 320, 7),
+    ("ragged", 13, 2, 20, 12, 50, 7),
+    # filter counts and frame lengths away from F = 64, S = 7: one, four, three and five 64-column dX tiles per symbol in the
+    # fused backward launch (tests/test_gpu_rx_backward_shapes.py), and the receiver's default F = 80 on the grouped backward
+    ("F32", 100, 2, 80, 32, 320, 7),
+    ("F128_nocp", 70, 2, 64, 128, 100, 7),
+    ("S3_F96_bpsk", 65, 1, 80, 96, 24, 3),
+    ("S1_F160_16qam", 70, 4, 64, 160, 10, 1),
+    ("F80_default", 100, 2, 80, 80, 320, 7),
 ]
+# (the ids of before the S column: name and the five extents)
+CASE_IDS = ["-".join(map(str, c[:6])) + ("" if c[6] == 7 else "-S%d" % c[6]) for c in CASES]
 
 
 def staged_checks(eng, p, x, bits, cfg, rtol=RTOL, grad_rtol=RTOL, cos_tol=1e-5):
@@ -113,14 +122,14 @@ def staged_checks(eng, p, x, bits, cfg, rtol=RTOL, grad_rtol=RTOL, cos_tol=1e-5)
     return m, g, info
 
 
-@pytest.mark.parametrize("name,batch,nbits,kin,F,D", CASES)
-def test_train_step_matches_oracle(name, batch, nbits, kin, F, D):
+@pytest.mark.parametrize("name,batch,nbits,kin,F,D,S", CASES, ids=CASE_IDS)
+def test_train_step_matches_oracle(name, batch, nbits, kin, F, D, S):
     """Forward, losses and every backward stage against the oracle, then the parameters after the first Adam step.  That
     last check starts from m = v = 0, where the update is +-lr whatever the gradient's magnitude is: it cannot see a wrongly
     scaled gradient, a dropped slab or a missing L2 term.  tests/test_gpu_optimizer.py carries that check, from a resumed
     non-zero optimizer state."""
     from dl_ofdm_amd.engine import RxEngine
-    dims, cfg, x, bits, p = make_case(batch, nbits, kin, F, D)
+    dims, cfg, x, bits, p = make_case(batch, nbits, kin, F, D, S)
     eng = RxEngine(dims, batch, params=p, train=True)
     eng.train_step(x, bits)
     torch.cuda.synchronize()
@@ -296,12 +305,12 @@ def test_pipelined_normalisation_is_bitwise_the_plain_step(frames, nbits, kin, F
     b.train_step(xs[0], bs[0])
 
 
-@pytest.mark.parametrize("placement", [1, 2])
-def test_double_buffered_normalisation_on_the_backward_launch_is_bitwise(placement):
+@pytest.mark.parametrize("placement,F", [(1, 64), (2, 64), (1, 32), (2, 32)], ids=["1", "2", "1-F32", "2-F32"])
+def test_double_buffered_normalisation_on_the_backward_launch_is_bitwise(placement, F):
     """Tuning knob 18: R0 of the next batch rides on the backward launch into a second x_norm buffer instead of the optimizer
     launch (1: on the leading workgroups of that grid, 2: on its closing ones, in the slots the last dW items free); eager
     double-buffered steps, captured single-buffer replays of either parity and the closing step interleave freely and stay
-    bit-identical to plain steps."""
+    bit-identical to plain steps.  F = 32: one dX tile per symbol behind the shifted block index, not two."""
     from dl_ofdm_amd import _lib
     from dl_ofdm_amd.engine import RxDims, RxEngine
     lib = _lib.load()
@@ -309,7 +318,7 @@ def test_double_buffered_normalisation_on_the_backward_launch_is_bitwise(placeme
     try:
         assert lib.dccn_set_tuning(18, placement) == 0
         frames, nbits = 300, 2
-        dims = RxDims(S=7, kin=80, F=64, D=320, nbits=nbits)
+        dims = RxDims(S=7, kin=80, F=F, D=320, nbits=nbits)
         rng = np.random.RandomState(10)
         xs = [rng.standard_normal((frames, 7, 80, 2)).astype(np.float32) for _ in range(8)]
         bs = [rng.randint(0, 2, (frames, 320, nbits)).astype(np.int32) for _ in range(8)]

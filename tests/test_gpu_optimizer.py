@@ -108,11 +108,29 @@ def check_step(eng, before, coef, step, what):
     return after
 
 
-def run_case(batch, kin=80, F=64, D=50, mode="plain", reg="uniform", fused_bwd=True, seed=0, what="", check=True):
+def check_conv_grads(eng, x_norm, what):
+    """The C-Conv gradient of the step just run -- in the fused plans the sum adam_rx_kernel takes over the per-tile partials of
+    the backward launch -- against O.cconv_gemm_bwd on the GPU's own dfft and on `x_norm`, the normalised batch that step ran
+    on: staged_checks' own check at its own tolerance (check_step does not look at this gradient)."""
+    torch.cuda.synchronize()
+    g = eng.get_grads()
+    batch, S, kin, _ = x_norm.shape
+    F = eng.dfft.shape[-2]
+    _, gw, gb = O.cconv_gemm_bwd(x_norm.cpu().numpy().astype(np.float64).reshape(batch * S, kin, 2), np.zeros((kin, 2 * F)),
+                                 eng.dfft.cpu().numpy().astype(np.float64).reshape(batch * S, F, 2))
+    for name, ref in (("fft_like/conv3d/kernel", gw), ("fft_like/conv3d/bias", gb)):
+        err = relerr(g[name], ref)
+        assert err <= 1e-5, (what, name, err)
+
+
+def run_case(batch, kin=80, F=64, D=50, mode="plain", reg="uniform", fused_bwd=True, seed=0, what="", check=True, S=7,
+             each_step=None):
     """mode: plain | pipe (train_step_pipelined, eager) | pipe-graph.  Returns the engine after N_STEPS steps, each one checked
-    (check=False: the same run, unchecked -- for a second engine that is compared with a checked one bit by bit)."""
+    (check=False: the same run, unchecked -- for a second engine that is compared with a checked one bit by bit).
+    each_step(eng, x_norm, what): called after every step with the normalised batch that step ran on (a pipelined step leaves
+    the NEXT batch in the engine's buffer, so a copy is taken before it)."""
     from dl_ofdm_amd.engine import RxEngine
-    dims, cfg, x, bits, p = make_case(batch, 2, kin, F, D, seed=seed)
+    dims, cfg, x, bits, p = make_case(batch, 2, kin, F, D, S=S, seed=seed)
     eng = RxEngine(dims, batch, params=p, train=True, want_prob=True, want_grads=True)
     assert bool(eng.lib.dccn_rx_bwd_fused_supported(C.byref(eng.shape))) == fused_bwd
     xs, bs = _batches(x, bits, N_STEPS + 1, seed + 17)
@@ -121,6 +139,7 @@ def run_case(batch, kin=80, F=64, D=50, mode="plain", reg="uniform", fused_bwd=T
     if mode != "plain":
         eng.prime(xs[0])
     for t in range(N_STEPS):
+        xn = eng._norm_bufs[eng._norm_parity].clone() if (each_step and mode != "plain") else None
         if mode == "plain":
             eng.train_step(xs[t], bs[t])
         elif mode == "pipe":
@@ -129,6 +148,8 @@ def run_case(batch, kin=80, F=64, D=50, mode="plain", reg="uniform", fused_bwd=T
             eng.train_step_pipelined(next_x=xs[t + 1], bits=bs[t], graph=True)
         if check:
             before = check_step(eng, before, coef, t, (what, batch, kin, mode, reg))
+        if each_step:
+            each_step(eng, eng.x_norm if xn is None else xn, (what, batch, S, kin, F, mode, t))
     torch.cuda.synchronize()
     eng.drop_prefetch()
     return eng
@@ -156,6 +177,24 @@ def test_slab_counts_of_the_fused_backward(name, batch, kin, knobs):
         for k, v in defaults.items():
             lib.dccn_set_tuning(k, v)
     assert all(lib.dccn_get_tuning(k) == v for k, v in defaults.items())
+
+
+# ---- filter counts and frame lengths other than F = 64, S = 7 ------------------------------------------------------------------
+# adam_rx_kernel folds the per-tile partials of the fused backward launch (cw_tilew = 64, cw_slab = (2F / 64) tiles,
+# cw_splits = ceil(batch / 64) * S terms) and applies Adam in the same pass: one, three and four tiles per symbol, S = 3, one /
+# two / graded dense dW ranges, and -- pipe -- R0 of the next batch on the same launch.  F = 80 is the receiver's default filter
+# count: 2F = 160 is no multiple of 64, the grouped backward's split-K fold.  tests/test_rx_backward_ref.py: what these see.
+GEOMETRY_CASES = [("F32-1slab", 300, dict(kin=80, F=32)), ("F32-2slabs", 500, dict(kin=64, F=32)),
+                  ("F128", 300, dict(kin=64, F=128)), ("F96-S3", 300, dict(kin=80, F=96, S=3)),
+                  ("F32-graded-pipe", 800, dict(kin=80, F=32, mode="pipe")),
+                  ("F80-grouped", 300, dict(kin=80, F=80, fused_bwd=False))]
+
+
+@pytest.mark.parametrize("name,batch,kw", GEOMETRY_CASES, ids=[c[0] for c in GEOMETRY_CASES])
+def test_other_filter_counts_and_frame_lengths(name, batch, kw):
+    """check_step holds the dense kernel's gradient and every Adam slot of every tensor, from the resumed state; the C-Conv
+    gradient itself -- the fold -- is held by check_conv_grads after each of the four steps."""
+    run_case(batch, D=50, what=name, each_step=check_conv_grads, **kw)
 
 
 # ---- who advances the state --------------------------------------------------------------------------------------------------

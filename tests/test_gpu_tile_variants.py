@@ -94,9 +94,9 @@ def cconv_case(rows, kin, F):
 
 
 def rx_case(batch, kin, D=320, S=7, F=64):
-    key = ("rx", batch, kin, D)
+    key = ("rx", batch, kin, D, S, F)
     if key not in _cache:
-        rng = np.random.RandomState(batch + kin + D)
+        rng = np.random.RandomState(batch + kin + D + (S - 7) + (F - 64))          # (S = 7, F = 64: the seeds of before)
         xn = rng.randn(batch, S, kin, 2).astype(np.float32)
         a = rng.randn(batch, S * 2 * F).astype(np.float32)
         dz = rng.randn(batch, 2 * D).astype(np.float32)
@@ -203,12 +203,14 @@ def test_dense_bwd_w_split_count(lib, M, K, N, form, splits):
 
 
 # ---- knob 14: graded k ranges of the dense dW items of the fused backward launch --------------------------------------
-def run_rx_backward(lib, c, batch, kin, reduce, S=7, F=64, D=320):
+def run_rx_backward(lib, c, batch, kin, reduce, S=7, F=64, D=320, want_dfft=True):
+    """want_dfft = False: dfft = NULL (the dX tiles only feed their epilogue); its guarded buffer must then stay NaN"""
     nws = lib.dccn_rx_backward_workspace_size(batch, S, kin, F, D)
     ws = torch.full((nws // 4,), float("nan"), dtype=torch.float32, device="cuda")
     g = dict(dfft=Guarded(batch * S * 2 * F), dw=Guarded(S * 2 * F * 2 * D), db=Guarded(2 * D), dcw=Guarded(kin * 2 * F), dcb=Guarded(2 * F))
     p = (lambda k: g[k].ptr) if reduce else (lambda k: None)
-    st = lib.dccn_rx_backward(c["xn"].data_ptr(), c["a"].data_ptr(), c["dz"].data_ptr(), c["w"].data_ptr(), g["dfft"].ptr, p("dw"),
+    st = lib.dccn_rx_backward(c["xn"].data_ptr(), c["a"].data_ptr(), c["dz"].data_ptr(), c["w"].data_ptr(),
+                              g["dfft"].ptr if want_dfft else None, p("dw"),
                               p("db"), p("dcw"), p("dcb"), batch, S, kin, F, D, 1 if reduce else 0, ws.data_ptr(), nws * 1, None)
     torch.cuda.synchronize()
     return st, g, ws
