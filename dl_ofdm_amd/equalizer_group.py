@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, ofdm
+from . import _lib, epochs, ofdm
 from . import receiver_mp as H
 from ._lib import check
 from .arena import ChainArena, check_same_layout
@@ -58,48 +58,30 @@ class _Chain:
         self.loop = H.DeviceEpochLoop(FLAGS, self.o, self.tr, self.gen, self.pl, self.steps, arena=self.arena)
         if not (self.loop.pipeline and self.loop.virt is not None):
             raise _lib.DccnError("chain groups need the pipelined loop with the virtual next batch (dccn_eq_norm_rides)")
-        self.best = H.BestSnapshot(self.tr, os.path.join(FLAGS.save_dir, H.save_model_name(FLAGS)), FLAGS)
-        self.loss_min, self.epoch_min, self.best_path, self.history = 100.0, 0, "", []
+        self.best = epochs.BestSnapshot(os.path.join(FLAGS.save_dir, H.save_model_name(FLAGS)), FLAGS, H.save_checkpoint)
+        self.rule, self.best_path, self.history = epochs.BestEpoch(FLAGS.early_stop), "", []
         self.epoch, self.done = 0, False
         self.rs = None
-        lp = self.loop
-        self.monitors = []
-        for q in range(2):
-            pl = lp.pls[q]
-            npow = lp.npow[q] if self.gen.want_noise_power else None
-            self.monitors.append(_lib.EqMonitor(pl.chest.data_ptr(), lp.H[q].data_ptr(), lp.per_symbol, pl.batch, FLAGS.nsymbol,
-                                                self.o.K, pl.metrics_buf.data_ptr(), pl.tx_power.data_ptr(),
-                                                None if npow is None else npow.data_ptr(), lp.acc.data_ptr(), None,
-                                                lp.ws.data_ptr(), lp.nws))
+        self.monitors = [self.loop.monitor_of(q) for q in range(2)]
 
-    # the pieces of receiver_mp._train_on_device, per chain -------------------------------------------------------------------
+    # an epoch of receiver_mp._train_on_device around the group's steps: the same helpers (epochs.py), stepped from outside ------
     def begin_epoch(self):
         F = self.F
         self.rs = np.random.RandomState((F.seed + 1000003 * (self.epoch + 1)) & 0xFFFFFFFF)
         self.loop.begin_epoch(self.rs.choice(H.TRAIN_SNR_GRID, [self.steps, self.B], p=H.TRAIN_SNR_PROB))
 
     def end_epoch(self, verbose: bool):
-        F, gen, ev, tr = self.F, self.gen, self.ev, self.tr
+        F = self.F
         a = self.loop.epoch_means()
-        train_loss_epoch = float(a[0])
         snr = self.rs.choice(H.TRAIN_SNR_GRID, [F.eval_frames], p=H.TRAIN_SNR_PROB)           # ofdmreceiver_np_mp.py:438
-        tx, _ = gen.transmit(F.eval_frames, out_bits=ev.bits)
-        gen.channel(tx, snr, out_x=ev.x)
-        gen.offset += 1
-        ev.run(False)
-        em = tr._metrics(ev.metrics_buf, ev.tx_power)
-        self.history.append(dict(epoch=self.epoch, train_loss=train_loss_epoch, train_ber=float(a[1]), chan_rms=float(a[4]),
-                                 test_loss=em["ce_mean"], test_ber=em["berlin"]))
-        if verbose:
-            print("[%s] Epoch: %d  Train Loss: %f  Tx Power: %f  Noise Power: %f  SNR MSE: %f | Test Loss: %f  Test BER: %.8f"
-                  % (F.token, self.epoch, train_loss_epoch, a[2], a[3], a[4], em["ce_mean"], em["berlin"]))
-        if train_loss_epoch < self.loss_min:
-            self.epoch_min, self.loss_min = self.epoch, train_loss_epoch
-            self.best.take()
+        em = epochs.eq_evaluate_on_device(F, self.tr, self.gen, self.ev, snr, self.loop.sync)
+        self.history.append(epochs.eq_epoch_record(self.epoch, a, em, verbose, tag="[%s] " % F.token))
+        improved, stop = self.rule.update(self.epoch, float(a[0]))
+        if improved:
+            self.best.take(self.tr)
         else:
-            self.best.maybe_flush()
-        if self.epoch - F.early_stop > self.epoch_min or self.epoch + 1 >= F.max_epoch_num:
-            self.done = True
+            self.best.maybe_flush(self.tr)
+        self.done = stop or self.epoch + 1 >= F.max_epoch_num
         self.epoch += 1
 
     def result(self) -> dict:
@@ -169,7 +151,7 @@ class EqualizerChainGroup:
         """batch i of the epoch for every chain: ONE fused generator launch (+ one that forms x for an epoch's first batch) -- or
         none at all: the group step that normalises the batch produces it too (dccn_eq_buffers.gen_next_rides), the descriptors
         its buffers hold are armed here"""
-        if not materialise and all(getattr(c.loop, "ride_gen", False) for c in act):
+        if not materialise and all(c.loop.ride_gen for c in act):
             for c in act:
                 lp = c.loop
                 lp.fg.arm(lp.pls[q].bits, q, None, lp.H[q], lp.snr_rows[i], into=lp.virt[q ^ 1])
@@ -216,7 +198,7 @@ class EqualizerChainGroup:
                 act = [c for c in act if not c.done]
         finally:
             for c in self.chains:
-                c.best_path = c.best.flush()                          # also on exceptions / KeyboardInterrupt
+                c.best_path = c.best.flush(c.tr)                        # also on exceptions / KeyboardInterrupt
         return [c.result() for c in self.chains]
 
 

@@ -20,7 +20,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from . import _lib, ofdm, radio, sweep, util
+from . import _lib, epochs, ofdm, radio, sweep, tf_bundle, util
 from .engine import PARAM_NAMES, RxDims
 
 
@@ -112,19 +112,14 @@ def crop_cp(xs: np.ndarray, FLAGS: Flags, ofdmobj) -> np.ndarray:
 
 def make_batch(FLAGS: Flags, ofdmobj, fading, n_frames: int, snr_db):
     """bits -> OFDM frames -> fading -> AWGN  (ofdmreceiver_np.py:220-229, 73-79)."""
-    ys = util.bit_source(FLAGS.nbits, ofdmobj.frame_size, n_frames)
-    iq_cpx, _, _ = ofdmobj.ofdm_tx_frame_np(ys)
-    xs, _ = fading.run(iq_cpx)
-    snr = snr_db * np.ones((n_frames, 1)) if np.isscalar(snr_db) else snr_db
-    xs, noise_pwr = radio.AWGN_channel_np(xs, snr)
-    return crop_cp(xs.astype(np.float32), FLAGS, ofdmobj), ys.astype(np.int32), noise_pwr
+    xs, ys, _, noise_pwr = epochs.make_batch(FLAGS, ofdmobj, fading, n_frames, snr_db)
+    return crop_cp(xs, FLAGS, ofdmobj), ys, noise_pwr
 
 
 # ---- checkpoints (reference variable names, SURVEY.md Appendix B) ------------------------------
 def save_checkpoint(path: str, eng, FLAGS: Flags):
     """<save_dir>/<token>.npz holding every variable tf.train.Saver would store: the 8 trainables, their
     Adam slots ``<var>/Adam`` / ``<var>/Adam_1``, ``global_step``, ``beta1_power``, ``beta2_power``."""
-    os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
     out: Dict[str, np.ndarray] = {}
     for n in PARAM_NAMES:
         out[n] = eng.view(n).detach().cpu().numpy()
@@ -134,64 +129,13 @@ def save_checkpoint(path: str, eng, FLAGS: Flags):
     out["global_step"] = np.float32(a["global_step"])
     out["beta1_power"] = np.float32(a["beta1_power"])
     out["beta2_power"] = np.float32(a["beta2_power"])
-    if getattr(FLAGS, "tf_checkpoint", False):                  # the reference's own format (tf.train.Saver, :191,271)
-        from . import tf_bundle
-        tf_bundle.write_checkpoint(path[:-4] if path.endswith(".npz") else path, tf_bundle.rx_to_tf(out, eng.dims.kin))
-    out["__flags__"] = np.array(repr(asdict(FLAGS)))
-    np.savez(path if path.endswith(".npz") else path + ".npz", **out)
-    return path
-
-
-class BestSnapshot:
-    """The best-train-loss model of ofdmreceiver_np.py:268-272, kept on the DEVICE: the reference calls ``saver.save`` every time
-    the epoch loss improves; here an improvement is a device-to-device copy of the four arenas and the file is written when
-    training ends (also when it ends with an exception: the epoch loop flushes in a ``finally``) and, checked once per epoch,
-    every ``interval`` seconds in between.  Writing the file on every improvement is 25 blocking device-to-host copies and a
-    7 MB archive -- hundreds of times per run, a third of a BPSK receiver's training time, and (chains training in threads of
-    one process, config5.train_models) time spent holding the interpreter lock.  The file holds the same bytes either way."""
-    NAMES = ("params", "adam_m", "adam_v", "adam_state")
-
-    def __init__(self, path: str, FLAGS, interval: float = 60.0):
-        self.path, self.FLAGS, self.interval = path, FLAGS, float(interval)
-        self.bufs, self.dirty, self.written, self.t_last = None, False, False, time.time()
-
-    def take(self, eng):
-        import torch
-        if self.bufs is None:
-            self.bufs = {n: torch.empty_like(getattr(eng, n)) for n in self.NAMES}
-        for n, b in self.bufs.items():
-            b.copy_(getattr(eng, n))
-        self.dirty = True
-        self.maybe_flush(eng)
-
-    def maybe_flush(self, eng):
-        if self.dirty and time.time() - self.t_last > self.interval:
-            self.flush(eng)
-
-    def flush(self, eng) -> str:
-        """write the snapshot (not the engine's current state) to ``path``; the engine is left as it was"""
-        if self.dirty:
-            import torch
-            with torch.no_grad():
-                cur = {n: getattr(eng, n).clone() for n in self.NAMES}
-                for n, b in self.bufs.items():
-                    getattr(eng, n).copy_(b)
-                save_checkpoint(self.path, eng, self.FLAGS)
-                for n, c in cur.items():
-                    getattr(eng, n).copy_(c)
-            self.dirty, self.written, self.t_last = False, True, time.time()
-        return self.path if self.written else ""
+    return epochs.write_checkpoint(path, out, FLAGS, lambda t: tf_bundle.rx_to_tf(t, eng.dims.kin))   # (tf.train.Saver, :191,271)
 
 
 def read_checkpoint_file(path: str) -> Dict[str, np.ndarray]:
     """<path>.npz, or -- when only the TensorFlow bundle <path>.index/.data-* exists (a receiver trained by
     the reference) -- that, mapped to the engine's layouts."""
-    stem = path[:-4] if path.endswith(".npz") else path
-    if not os.path.exists(stem + ".npz") and os.path.exists(stem + ".index"):
-        from . import tf_bundle
-        return tf_bundle.rx_from_tf(tf_bundle.read_checkpoint(stem))
-    z = np.load(stem + ".npz", allow_pickle=False)
-    return {k: z[k] for k in z.files}
+    return epochs.read_checkpoint(path, tf_bundle.rx_from_tf)
 
 
 def load_checkpoint(path: str, eng, with_optimizer: bool = True):
@@ -256,13 +200,17 @@ def test_model(FLAGS: Flags, model, ofdmobj=None, rank: int = 0, world: int = 1,
     if gen is not None:
         gen.want_noise_power = False          # the sweep table has no noise-power column
 
+    def evaluate_on_device(p):
+        """the point's frames drawn on the GPU and evaluated: the engine that holds the result"""
+        eng = sess.engine_for(FLAGS.test_frames, want_prob=False)
+        gen.seed, gen.offset = p.seed, 0
+        _gen_into(gen, eng, FLAGS, ofdmobj, FLAGS.test_frames, p.snr_db)
+        eng.eval_step()
+        return eng
+
     def evaluate(p):
         if gen is not None:
-            eng = sess.engine_for(FLAGS.test_frames, want_prob=False)
-            gen.seed, gen.offset = p.seed, 0
-            _gen_into(gen, eng, FLAGS, ofdmobj, FLAGS.test_frames, p.snr_db)
-            eng.eval_step()
-            m = eng.metrics()          # the float64 / int64 record itself: no fp32 ce_mean * count, no int32 counts
+            m = evaluate_on_device(p).metrics()   # the float64 / int64 record itself: no fp32 ce_mean * count, no int32 counts
             if verbose:
                 print("SNR: %.2f, BER: %.8f, Loss: %f" % (p.snr_db, m["berlin"], m["ce_mean"]))
             c = m["conf"]
@@ -285,10 +233,7 @@ def test_model(FLAGS: Flags, model, ofdmobj=None, rank: int = 0, world: int = 1,
         lib = _lib.load()
 
         def evaluate_into(p, row):
-            eng = sess.engine_for(FLAGS.test_frames, want_prob=False)
-            gen.seed, gen.offset = p.seed, 0
-            _gen_into(gen, eng, FLAGS, ofdmobj, FLAGS.test_frames, p.snr_db)
-            eng.eval_step()
+            eng = evaluate_on_device(p)
             _lib.check(lib.dccn_metrics_table_add(eng.metrics_buf.data_ptr(), row.data_ptr(), eng._stream()), "table_add")
         table = sweep.run_sweep_device(pts, evaluate_into, rank, world, device=sess.device, group=group).cpu().numpy()
     else:
@@ -305,6 +250,98 @@ def test_model(FLAGS: Flags, model, ofdmobj=None, rank: int = 0, world: int = 1,
 def _require_device_sync(FLAGS):
     if check_sync(FLAGS) > 0 and not bool(getattr(FLAGS, "device_data", False)):
         raise ValueError("sync > 0 needs device_data=True: the alignment stage is a GPU launch on device-generated frames")
+
+
+# One epoch's training steps, by where the batches come from.  Each route takes the engine, the batch size and the step count and
+# returns the epoch's (train loss, tx power, noise power, last step's linear BER).  On the two device routes every step draws its
+# own batch on the GPU into the engine's buffers; the per-step scalars the reference fetches are accumulated on the device and
+# read once per epoch (no per-step sync).
+def _device_epoch_means(eng, acc, steps: int):
+    a = acc.cpu().numpy() / max(steps, 1)
+    return float(a[0]), float(a[1]), float(a[2]), eng.metrics()["berlin"]
+
+
+def _takes_fused_generator(gen, eng, FLAGS) -> bool:
+    """the fused-generator route, where the library forms this engine's batches from the one-launch generator's output.  Not with
+    sync > 0: every batch is materialised and aligned -- the side-stream route, whose _gen_into aligns; the step that reads the
+    generator's output as its virtual input would see the frames as generated."""
+    from .datagen import FusedStaticGen
+    return FusedStaticGen.supported(gen, eng) and not getattr(FLAGS, "no_fused_generator", False) and not check_sync(FLAGS)
+
+
+def _epoch_on_fused_generator(eng, batch_size: int, steps: int, fg):
+    """round 5: single-profile channels, static or mobile -- ONE C call per batch: the fused generator launch of the next batch
+    + the four step launches, whose pipelined normalisation reads (y, noise, power partials) as its virtual input
+    (include/dccn.h dccn_gen_static; ``fg``: the datagen.FusedStaticGen of this batch size).  Same batches as the side-stream
+    route.  (cp=False receivers too: that normalisation then reads the samples behind the cyclic prefix itself)"""
+    import torch
+    acc = torch.zeros(3, dtype=torch.float32, device=eng.device)
+    eng.drop_prefetch()
+    # (the three per-step monitors go onto the epoch accumulators in ONE stream-ordered library launch: three
+    # framework calls per step kept the interpreter lock for longer than the step's own C call, which is what
+    # several chains training in threads of one process -- config5.train_models -- then queue up behind)
+    mon = (eng.metrics_buf.data_ptr(), eng.tx_power.data_ptr(), (fg.npow[0].data_ptr(), fg.npow[1].data_ptr()),
+           acc.data_ptr())
+    for i in range(steps):
+        eng.train_step_generated(fg, slot=i & 1, last=(i + 1 == steps))
+        _lib.check(eng.lib.dccn_step_monitor_add(mon[0], mon[1], mon[2][i & 1], mon[3], eng._stream()),
+                   "dccn_step_monitor_add")
+    return _device_epoch_means(eng, acc, steps)
+
+
+def _epoch_on_side_stream_feeder(eng, batch_size: int, steps: int, gen, FLAGS, ofdmobj, feeds: dict):
+    """R0 is software-pipelined across the steps (RxEngine.train_step_pipelined): batch i+1 is generated into eng.x / the other
+    label slot before step i is issued, and normalised behind step i's Adam update ... and the generator runs on its own stream
+    (datagen.SideStreamFeeder): batch i+1 is produced while the forward and backward launches of step i run; the step's last
+    launch waits for it.  ``feeds``: batch size -> feeder, kept by the caller across epochs."""
+    import torch
+    from .datagen import SideStreamFeeder
+    acc = torch.zeros(3, dtype=torch.float32, device=eng.device)
+    # the generator's noise-power monitor is reused per batch: each batch's value goes to one of two preallocated
+    # slots (allocated on the main stream, never handed back to the caching allocator while a step may read them)
+    noise_slots = torch.zeros(2, 1, dtype=torch.float32, device=eng.device)
+
+    def make(slot):
+        npow = _gen_into(gen, eng, FLAGS, ofdmobj, batch_size, FLAGS.SNR, slot=slot)
+        if npow is None:
+            return None
+        noise_slots[slot].copy_(npow.reshape(1))
+        return noise_slots[slot]
+    if batch_size not in feeds:                                  # one side stream + event pair per engine, not per epoch
+        feeds.clear()                                            # (a smaller batch's feeder holds the engine train() released)
+        feeds[batch_size] = SideStreamFeeder(eng, make)
+    else:
+        feeds[batch_size].rebind(make)
+    feed = feeds[batch_size]
+    noise_t = make(0)
+    eng.prime()
+    for i in range(steps):
+        last = i + 1 == steps
+        noise_next = None if last else feed.next((i + 1) & 1)
+        eng.train_step_pipelined(slot=i & 1, last=last, x_ready=None if last else feed.ready)
+        _lib.check(eng.lib.dccn_step_monitor_add(eng.metrics_buf.data_ptr(), eng.tx_power.data_ptr(),
+                                                 None if noise_t is None else noise_t.data_ptr(), acc.data_ptr(),
+                                                 eng._stream()), "dccn_step_monitor_add")
+        feed.step_issued()            # (after the monitor reads: the generator may now overwrite slot i & 1's values)
+        noise_t = noise_next
+    return _device_epoch_means(eng, acc, steps)
+
+
+def _epoch_of_host_batches(eng, batch_size: int, steps: int, batch):
+    """``batch`` = (frames, labels, noise power) of the whole epoch from :func:`make_batch`; every step's scalars are fetched,
+    as the reference does"""
+    xs, ys, noise_pwr = batch
+    losses, pwrs, berl = [], [], 0.5
+    for i in range(steps):
+        sl = slice(i * batch_size, (i + 1) * batch_size)
+        if i == 0:
+            eng.prime(xs[sl])
+        last = i + 1 == steps
+        eng.train_step_pipelined(next_x=None if last else xs[(i + 1) * batch_size:(i + 2) * batch_size],
+                                 bits=ys[sl], last=last)
+        m = eng.metrics()
+        losses.append(m["ce_mean"]); pwrs.append(m["tx_power"]); berl = m["berlin"]
+    return float(np.mean(losses)), float(np.mean(pwrs)), noise_pwr, berl
 
 
 def train(FLAGS: Flags, device="cuda", verbose: bool = True, run_test: bool = True):
@@ -335,101 +372,29 @@ def train(FLAGS: Flags, device="cuda", verbose: bool = True, run_test: bool = Tr
 
     eng = engine_for(batch_size, None)
     ev = RxEngine(dims, FLAGS.eval_frames, device=device, train=False, want_prob=False).pin_tuning()
-    loss_min, epoch_min, best_path = 100.0, 0, ""
+    rule, best_path = epochs.BestEpoch(FLAGS.early_stop), ""
     history = []
     gen = _device_gen(FLAGS, ofdmobj, device) if FLAGS.device_data else None
-    feed = None
-    fused = {}                       # batch size -> datagen.FusedStaticGen
-    import torch
+    fused, feeds = {}, {}            # batch size -> datagen.FusedStaticGen / datagen.SideStreamFeeder
     # device-generated runs keep the best model on the device and write it at the end (BestSnapshot); host-generated runs save
     # on every improvement as before
-    best = BestSnapshot(os.path.join(FLAGS.save_dir, FLAGS.token), FLAGS) if gen is not None else None
+    best = epochs.BestSnapshot(os.path.join(FLAGS.save_dir, FLAGS.token), FLAGS, save_checkpoint) if gen is not None else None
     try:
         for epoch in range(FLAGS.max_epoch_num):
             np.random.seed(FLAGS.seed + 1000003 * (epoch + 1))           # reference: int(time.time()) + epoch
             train_snr = FLAGS.SNR + np.repeat(snr_seq, frame_cnt // 8, axis=0)
             n_use = train_snr.shape[0]
-            losses, pwrs, berl = [], [], 0.5
-            if gen is not None:
-                # every step draws its own batch on the GPU into the engine's buffers; the per-step scalars the
-                # reference fetches are accumulated on the device and read once per epoch (no per-step sync)
-                mview = eng.metrics_buf.view(torch.float32)              # dccn_metrics: [12] ce_mean, [13] berlin
-                acc = torch.zeros(3, dtype=torch.float32, device=eng.device)
-                steps = n_use // batch_size
-                # R0 is software-pipelined across the steps (RxEngine.train_step_pipelined): batch i+1 is generated into
-                # eng.x / the other label slot before step i is issued, and normalised behind step i's Adam update
-                # ... and the generator runs on its own stream (datagen.SideStreamFeeder): batch i+1 is produced while the forward
-                # and backward launches of step i run; the step's last launch waits for it
-                from .datagen import FusedStaticGen, SideStreamFeeder
-                # (sync > 0: every batch is materialised and aligned -- the loop below, whose _gen_into route aligns; the step
-                # that reads the generator's output as its virtual input would see the frames as generated)
-                if FusedStaticGen.supported(gen, eng) and not getattr(FLAGS, "no_fused_generator", False) and not check_sync(FLAGS):
-                    # round 5: single-profile channels, static or mobile -- ONE C call per batch: the fused generator launch of the next batch
-                    # + the four step launches, whose pipelined normalisation reads (y, noise, power partials) as its virtual
-                    # input (include/dccn.h dccn_gen_static; datagen.FusedStaticGen).  Same batches as the loop below.
-                    # (cp=False receivers too: that normalisation then reads the samples behind the cyclic prefix itself)
-                    fg = fused.get(batch_size)
-                    if fg is None:
-                        fg = fused[batch_size] = FusedStaticGen(gen, batch_size, FLAGS.SNR, want_noise_power=True)
-                    eng.drop_prefetch()
-                    # (the three per-step monitors go onto the epoch accumulators in ONE stream-ordered library launch: three
-                    # framework calls per step kept the interpreter lock for longer than the step's own C call, which is what
-                    # several chains training in threads of one process -- config5.train_models -- then queue up behind)
-                    mon = (eng.metrics_buf.data_ptr(), eng.tx_power.data_ptr(), (fg.npow[0].data_ptr(), fg.npow[1].data_ptr()),
-                           acc.data_ptr())
-                    for i in range(steps):
-                        eng.train_step_generated(fg, slot=i & 1, last=(i + 1 == steps))
-                        _lib.check(eng.lib.dccn_step_monitor_add(mon[0], mon[1], mon[2][i & 1], mon[3], eng._stream()),
-                                   "dccn_step_monitor_add")
-                    a = acc.cpu().numpy() / max(steps, 1)
-                    losses, pwrs, noise_pwr = [float(a[0])], [float(a[1])], float(a[2])
-                    berl = eng.metrics()["berlin"]
-                    steps = 0                                            # (the loop below has nothing left to do)
-
-                # the generator's noise-power monitor is reused per batch: each batch's value goes to one of two preallocated
-                # slots (allocated on the main stream, never handed back to the caching allocator while a step may read them)
-                noise_slots = torch.zeros(2, 1, dtype=torch.float32, device=eng.device)
-
-                def make(slot, eng=eng, bs=batch_size):
-                    npow = _gen_into(gen, eng, FLAGS, ofdmobj, bs, FLAGS.SNR, slot=slot)
-                    if npow is None:
-                        return None
-                    noise_slots[slot].copy_(npow.reshape(1))
-                    return noise_slots[slot]
-                if feed is None or feed.eng is not eng:                  # one side stream + event pair per engine, not per epoch
-                    feed = SideStreamFeeder(eng, make)
-                else:
-                    feed.rebind(make)
-                noise_t = None
-                if steps:
-                    noise_t = make(0)
-                    eng.prime()
-                for i in range(steps):
-                    last = i + 1 == steps
-                    noise_next = None if last else feed.next((i + 1) & 1)
-                    eng.train_step_pipelined(slot=i & 1, last=last, x_ready=None if last else feed.ready)
-                    _lib.check(eng.lib.dccn_step_monitor_add(eng.metrics_buf.data_ptr(), eng.tx_power.data_ptr(),
-                                                             None if noise_t is None else noise_t.data_ptr(), acc.data_ptr(),
-                                                             eng._stream()), "dccn_step_monitor_add")
-                    feed.step_issued()            # (after the monitor reads: the generator may now overwrite slot i & 1's values)
-                    noise_t = noise_next
-                if steps:
-                    a = acc.cpu().numpy() / max(steps, 1)
-                    losses, pwrs, noise_pwr = [float(a[0])], [float(a[1])], float(a[2])
-                    berl = eng.metrics()["berlin"]
+            steps = n_use // batch_size
+            if gen is None:
+                means = _epoch_of_host_batches(eng, batch_size, steps, make_batch(FLAGS, ofdmobj, fading, n_use, train_snr))
+            elif _takes_fused_generator(gen, eng, FLAGS):
+                if batch_size not in fused:
+                    from .datagen import FusedStaticGen
+                    fused[batch_size] = FusedStaticGen(gen, batch_size, FLAGS.SNR, want_noise_power=True)
+                means = _epoch_on_fused_generator(eng, batch_size, steps, fused[batch_size])
             else:
-                xs, ys, noise_pwr = make_batch(FLAGS, ofdmobj, fading, n_use, train_snr)
-                nb = n_use // batch_size
-                for i in range(nb):
-                    sl = slice(i * batch_size, (i + 1) * batch_size)
-                    if i == 0:
-                        eng.prime(xs[sl])
-                    last = i + 1 == nb
-                    eng.train_step_pipelined(next_x=None if last else xs[(i + 1) * batch_size:(i + 2) * batch_size],
-                                             bits=ys[sl], last=last)
-                    m = eng.metrics()
-                    losses.append(m["ce_mean"]); pwrs.append(m["tx_power"]); berl = m["berlin"]
-            train_loss_epoch = float(np.mean(losses))
+                means = _epoch_on_side_stream_feeder(eng, batch_size, steps, gen, FLAGS, ofdmobj, feeds)
+            train_loss_epoch, tx_power, noise_pwr, berl = means
             new_bs = max(batch_size, ideal_batch_size(berl, FLAGS.nbits))
             new_bs = min(new_bs, n_use)
             if new_bs != batch_size:
@@ -456,16 +421,16 @@ def train(FLAGS: Flags, device="cuda", verbose: bool = True, run_test: bool = Tr
                                 batch_size=batch_size))
             if verbose:
                 print("Epoch: %d  Train Loss: %f  Tx Power: %f  Noise Power: %f | Test Loss: %f  Test BER: %.8f  next batch %d"
-                      % (epoch, train_loss_epoch, float(np.mean(pwrs)), noise_pwr, em["ce_mean"], em["berlin"], batch_size))
-            if train_loss_epoch < loss_min:                                # :268-272 (train loss selects the checkpoint)
-                epoch_min, loss_min = epoch, train_loss_epoch
+                      % (epoch, train_loss_epoch, tx_power, noise_pwr, em["ce_mean"], em["berlin"], batch_size))
+            improved, stop = rule.update(epoch, train_loss_epoch)          # :268-274 (train loss selects the checkpoint)
+            if improved:
                 if best is not None:
                     best.take(eng)                                         # (device snapshot; the file is written below)
                 else:
                     best_path = save_checkpoint(os.path.join(FLAGS.save_dir, FLAGS.token), eng, FLAGS)
             elif best is not None:
                 best.maybe_flush(eng)
-            if epoch - FLAGS.early_stop > epoch_min:
+            if stop:
                 break
     finally:
         if best is not None:

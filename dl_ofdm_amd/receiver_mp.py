@@ -28,7 +28,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from . import ofdm, radio, sweep, util
+from . import epochs, ofdm, radio, sweep, tf_bundle
 from .engine import PARAM_NAMES
 from .receiver import _bool, check_sync
 
@@ -82,7 +82,6 @@ class Flags:
     fused_sync: bool = True         # sync > 0, fused generator: x is formed, aligned and written by ONE launch
                                     # (dccn_gen_static_apply_sync); False: apply + dccn_frame_sync, the same bits in three launches
     pipeline_norm: Optional[bool] = None  # device_data: step i normalises batch i+1 on its optimizer launch (None: when the library can)
-    overlap_generator: bool = False  # device_data: generate batch i+1 on a second stream while step i runs (same results, not faster)
     step_graph: bool = False         # device_data: replay the equaliser step as a hipGraph instead of 21 eager launches (same results)
     virtual_next: bool = True        # ... and the pipelined loop never writes x for any batch but an epoch's first (x_next_virtual)
     monitor_rides: bool = True       # device_data, pipelined loop: the per-step monitors are a job of the step's optimizer launch
@@ -139,14 +138,7 @@ def load_rx_params(FLAGS) -> Dict[str, np.ndarray]:
     return dict(sess.params)
 
 
-def make_batch(FLAGS, ofdmobj, fading, n_frames: int, snr_db):
-    """bits -> OFDM frames -> fading -> AWGN (:405-413); also returns the true channel response."""
-    ys = util.bit_source(FLAGS.nbits, ofdmobj.frame_size, n_frames)
-    iq_cpx, _, _ = ofdmobj.ofdm_tx_frame_np(ys)
-    xs, chan = fading.run(iq_cpx)
-    snr = snr_db * np.ones((n_frames, 1)) if np.isscalar(snr_db) else snr_db
-    xs, noise_pwr = radio.AWGN_channel_np(xs, snr)
-    return xs.astype(np.float32), ys.astype(np.int32), chan, noise_pwr
+make_batch = epochs.make_batch          # bits -> OFDM frames -> fading -> AWGN (:405-413): frames, labels, true channel, noise power
 
 
 def test_model_cross(FLAGS, trainer, ofdmobj, rank: int = 0, world: int = 1, out_dir: str = ".",
@@ -208,24 +200,11 @@ def _device_sync(FLAGS, on_device: bool) -> int:
 
 
 def save_checkpoint(path: str, trainer, FLAGS):
-    os.makedirs(os.path.dirname(os.path.abspath(path)) or ".", exist_ok=True)
-    out = trainer.state_dict_tf()
-    if getattr(FLAGS, "tf_checkpoint", False):
-        from . import tf_bundle
-        tf_bundle.write_checkpoint(path[:-4] if path.endswith(".npz") else path, tf_bundle.eq_to_tf(out))
-    out["__flags__"] = np.array(repr(asdict(FLAGS)))
-    np.savez(path if path.endswith(".npz") else path + ".npz", **out)
-    return path
+    return epochs.write_checkpoint(path, trainer.state_dict_tf(), FLAGS, tf_bundle.eq_to_tf)
 
 
 def load_checkpoint(path: str, trainer, with_optimizer: bool = True):
-    stem = path[:-4] if path.endswith(".npz") else path
-    if not os.path.exists(stem + ".npz") and os.path.exists(stem + ".index"):
-        from . import tf_bundle
-        z = tf_bundle.eq_from_tf(tf_bundle.read_checkpoint(stem))
-    else:
-        z = np.load(stem + ".npz", allow_pickle=False)
-    trainer.load_state_dict_tf(z, with_optimizer)
+    trainer.load_state_dict_tf(epochs.read_checkpoint(path, tf_bundle.eq_from_tf), with_optimizer)
 
 
 def train(FLAGS, device="cuda", verbose: bool = True, run_test: bool = True, rx_params=None):
@@ -241,7 +220,7 @@ def train(FLAGS, device="cuda", verbose: bool = True, run_test: bool = True, rx_
     fading0 = RayleighChanParallel(FLAGS, ofdmobj.Fs, mobile=False)    # :389
     fading1 = RayleighChanParallel(FLAGS, ofdmobj.Fs, mobile=True, mix=True) if FLAGS.mobile else None
     phase2 = True                                                      # :393
-    loss_min, epoch_min, best_path, history = 100.0, 0, "", []
+    rule, best_path, history = epochs.BestEpoch(FLAGS.early_stop), "", []
     on_device = bool(FLAGS.device_data) and trainer.fused_ok
     _device_sync(FLAGS, on_device)
     if on_device:
@@ -250,30 +229,20 @@ def train(FLAGS, device="cuda", verbose: bool = True, run_test: bool = True, rx_
         np.random.seed(FLAGS.seed + 1000003 * (epoch + 1))              # reference: int(time.time()) + epoch
         train_snr = np.random.choice(TRAIN_SNR_GRID, [frame_cnt, 1], p=TRAIN_SNR_PROB)     # :407
         fading = fading1 if (phase2 and FLAGS.mobile) else fading0
-        ys = util.bit_source(FLAGS.nbits, ofdmobj.frame_size, frame_cnt)
-        iq_cpx, _, _ = ofdmobj.ofdm_tx_frame_np(ys)
-        xs, chan = fading.run(iq_cpx)
-        xs, noise_pwr = radio.AWGN_channel_np(xs, train_snr)
-        xs, ys = xs.astype(np.float32), ys.astype(np.int32)
+        xs, ys, chan, noise_pwr = make_batch(FLAGS, ofdmobj, fading, frame_cnt, train_snr)
         losses, pwrs, bers, rmss = [], [], [], []
         for i in range(frame_cnt // batch_size):
             sl = slice(i * batch_size, (i + 1) * batch_size)
             m = trainer.train_step(xs[sl], ys[sl], chan[sl])
             losses.append(m["ce_mean"]); pwrs.append(m["tx_power"]); bers.append(m["berlin"]); rmss.append(m["chan_rms"])
-        train_loss_epoch = float(np.mean(losses))
+        a = [float(np.mean(v)) for v in (losses, bers, pwrs, noise_pwr, rmss)]
         test_snr = np.random.choice(TRAIN_SNR_GRID, [FLAGS.eval_frames, 1], p=TRAIN_SNR_PROB)   # :438
         txs, tys, _, _ = make_batch(FLAGS, ofdmobj, fading, FLAGS.eval_frames, test_snr)
-        em = trainer.eval_step(txs, tys)
-        history.append(dict(epoch=epoch, train_loss=train_loss_epoch, train_ber=float(np.mean(bers)),
-                            chan_rms=float(np.mean(rmss)), test_loss=em["ce_mean"], test_ber=em["berlin"]))
-        if verbose:
-            print("Epoch: %d  Train Loss: %f  Tx Power: %f  Noise Power: %f  SNR MSE: %f | Test Loss: %f  Test BER: %.8f"
-                  % (epoch, train_loss_epoch, float(np.mean(pwrs)), float(np.mean(noise_pwr)), float(np.mean(rmss)),
-                     em["ce_mean"], em["berlin"]))
-        if train_loss_epoch < loss_min:                                  # :456-459
-            epoch_min, loss_min = epoch, train_loss_epoch
+        history.append(epochs.eq_epoch_record(epoch, a, trainer.eval_step(txs, tys), verbose))
+        improved, stop = rule.update(epoch, a[0])                        # :456-466
+        if improved:
             best_path = save_checkpoint(os.path.join(FLAGS.save_dir, save_model_name(FLAGS)), trainer, FLAGS)
-        if epoch - FLAGS.early_stop > epoch_min:                         # :460-466
+        if stop:
             break
     if verbose:
         print("Training Done!, Best model saved to\n%s" % best_path)
@@ -291,19 +260,12 @@ class DeviceEpochLoop:
     accumulators.  Round 3 did the last part with ~25 framework launches and a host-to-device copy per step, which made the
     loop host-bound at twice the fused step's own time (tools/eqloop.py).
 
-    ``overlap`` (built, bitwise-tested, measured, OFF by default): two resident buffer sets (input, labels, channel truth,
-    noise power, step workspace) and the generator on its own HIP stream -- batch i+1 is produced into the other set while
-    step i runs; two events per set order producer and consumer.  Same batches, same step: the trained model is bit-identical
-    to the one-stream loop (tests/test_gpu_equalizer.py) -- but not faster: 0.2222 vs 0.2172 ms per step (tools/eqloop.py);
-    the two cross-stream edges per step cost what hiding the generator's 26 us gains.
-
     ``pipeline`` (default: on when the library honours ``dccn_eq_buffers.x_next`` for this shape): two twin plans (own input
     and labels, shared workspace and outputs) hold consecutive batches; batch i+1 is generated BEFORE step i is issued, and
     step i normalises it on leading workgroups of its optimizer launch, so every step but the first of an epoch starts at
     the layer norm -- one launch (6 us) off a 21-launch chain.  Same kernels on the same data: bit-identical training."""
 
-    def __init__(self, FLAGS, ofdmobj, trainer, gen, pl, steps: int, overlap: bool = False, pipeline: Optional[bool] = None,
-                 arena=None):
+    def __init__(self, FLAGS, ofdmobj, trainer, gen, pl, steps: int, pipeline: Optional[bool] = None, arena=None):
         """arena: the chain's :class:`~dl_ofdm_amd.arena.ChainArena` (chain groups, equalizer_group.py): every buffer a launch of
         the loop touches is placed there"""
         import ctypes as C
@@ -321,16 +283,10 @@ class DeviceEpochLoop:
         if self.sync and arena is not None:
             from ._lib import DccnError
             raise DccnError("chain groups do not take sync > 0 (the aligned batch is materialised per chain)")
-        self.overlap = bool(overlap)
         if pipeline is None:
-            pipeline = not self.overlap and bool(trainer.lib.dccn_eq_norm_rides(C.byref(pl.shape)))
-        self.pipeline = bool(pipeline) and not self.overlap
-        if self.pipeline:
-            self.pls = [pl, _FusedPlan(trainer, B, twin_of=pl, arena=arena)]
-            self.pls[0].pipe_with(self.pls[1], 0)
-            self.pls[1].pipe_with(self.pls[0], 1)
-        else:
-            self.pls = [pl, _FusedPlan(trainer, B)] if self.overlap else [pl]
+            pipeline = bool(trainer.lib.dccn_eq_norm_rides(C.byref(pl.shape)))
+        self.pipeline = bool(pipeline)
+        self.pls = [pl, _FusedPlan(trainer, B, twin_of=pl, arena=arena)] if self.pipeline else [pl]
         self.pl = pl
         self.per_symbol = 1 if (gen.doppler or gen.mixed) else 0
         hshape = (B, FLAGS.nsymbol, ofdmobj.K, 2) if self.per_symbol else (B, ofdmobj.K, 2)
@@ -360,40 +316,36 @@ class DeviceEpochLoop:
                 d = _lib.GenStatic.from_buffer_copy(self.fg.desc)
                 d.noise_power_out = self.fg.npow[q ^ 1].data_ptr() if self.fg.npow is not None else None
                 self.virt.append(d)
-            # round 6: ... and the generator launch goes as well -- its workgroups ride on the step's bottleneck backward launch
-            # (dccn_eq_buffers.gen_next_rides): the loop only ARMS the descriptor the step reads (labels, SNR row, batch offset)
-            # (not under hipGraph replay of the step: the generator's per-batch arguments must stay outside a captured graph)
-            self.ride_gen = bool(getattr(FLAGS, "generator_rides", True)) and not bool(getattr(FLAGS, "step_graph", False))
-            self.pls[0].pipe_with(self.pls[1], 0, virt=self.virt[0], gen_rides=self.ride_gen)
-            self.pls[1].pipe_with(self.pls[0], 1, virt=self.virt[1], gen_rides=self.ride_gen)
+        # round 6: ... and the generator launch goes as well -- its workgroups ride on the step's bottleneck backward launch
+        # (dccn_eq_buffers.gen_next_rides): the loop only ARMS the descriptor the step reads (labels, SNR row, batch offset)
+        # (not under hipGraph replay of the step: the generator's per-batch arguments must stay outside a captured graph)
+        self.ride_gen = (self.virt is not None and bool(getattr(FLAGS, "generator_rides", True))
+                         and not bool(getattr(FLAGS, "step_graph", False)))
         self.nws = int(trainer.lib.dccn_eq_monitor_workspace_size(B, FLAGS.nsymbol, ofdmobj.K))
         self.ws = A.zeros(arena, self.nws, dtype=torch.uint8, device=dev)
         # round 6: in the pipelined loop the monitors are a job of the step's own optimizer launch (dccn_eq_buffers.monitor)
         self.mon = None
         if self.pipeline and getattr(FLAGS, "monitor_rides", True):
-            from . import _lib as L_
-            self.mon = []
+            self.mon = [self.monitor_of(q) for q in range(2)]
+        # everything the twins' pipelined steps read is decided: each is wired to the other once
+        if self.pipeline:
             for q in range(2):
-                plq = self.pls[q]
-                npw = self.npow[q] if gen.want_noise_power else None
-                self.mon.append(L_.EqMonitor(plq.chest.data_ptr(), self.H[q].data_ptr(), self.per_symbol, B, FLAGS.nsymbol, ofdmobj.K,
-                                             plq.metrics_buf.data_ptr(), plq.tx_power.data_ptr(),
-                                             None if npw is None else npw.data_ptr(), self.acc.data_ptr(), None,
-                                             self.ws.data_ptr(), self.nws))
-            kw = [dict(virt=self.virt[q], gen_rides=self.ride_gen) if self.virt is not None else {} for q in range(2)]
-            self.pls[0].pipe_with(self.pls[1], 0, monitor=self.mon[0], **kw[0])
-            self.pls[1].pipe_with(self.pls[0], 1, monitor=self.mon[1], **kw[1])
+                self.pls[q].pipe_with(self.pls[q ^ 1], q, virt=None if self.virt is None else self.virt[q], gen_rides=self.ride_gen,
+                                      monitor=None if self.mon is None else self.mon[q])
         self.i = 0
         # the step as 21 eager launches per call (default) or as a hipGraph replay: 0.188 vs 0.196 ms per loop step (tools/eqloop.py
         # --graph 0 / 1; host issue 0.156 vs 0.125 ms) -- the replay costs the GPU 3-7 us per step, the eager calls cost the host 30
         self.step_graph = bool(getattr(FLAGS, "step_graph", False))
-        if self.overlap:
-            self.side = torch.cuda.Stream(device=dev)
-            self.ready = [torch.cuda.Event() for _ in range(2)]      # set q holds a finished batch
-            self.done = [torch.cuda.Event() for _ in range(2)]       # the step that read set q has completed
-            self.used = [False, False]
-        self.pending = -1                                            # index (within the epoch) of the batch already generated
-        self.fresh_epoch = True
+
+    def monitor_of(self, q: int):
+        """the ``_lib.EqMonitor`` of buffer set q (the caller keeps it alive): what a step of plan q leaves for the epoch's
+        accumulators -- carried by that step's optimizer launch (``mon``), or handed to dccn_eq_monitor_accumulate_grouped"""
+        from . import _lib
+        pl, F = self.pls[q], self.F
+        npow = self.npow[q] if self.gen.want_noise_power else None
+        return _lib.EqMonitor(pl.chest.data_ptr(), self.H[q].data_ptr(), self.per_symbol, pl.batch, F.nsymbol, self.o.K,
+                              pl.metrics_buf.data_ptr(), pl.tx_power.data_ptr(), None if npow is None else npow.data_ptr(),
+                              self.acc.data_ptr(), None, self.ws.data_ptr(), self.nws)
 
     def _generate(self, i: int, q: int):
         from ._lib import check
@@ -408,7 +360,7 @@ class DeviceEpochLoop:
             return
         if self.fg is not None:
             if self.virt is not None and i > 0:                      # frames only: the running step forms x in registers
-                if getattr(self, "ride_gen", False):                 # ... and produces them: arm the descriptor ITS buffers hold
+                if self.ride_gen:              # ... and produces them: arm the descriptor ITS buffers hold
                     self.fg.arm(pl.bits, q, None, self.H[q], self.snr_rows[i], into=self.virt[q ^ 1])
                     return
                 d = self.fg.arm(pl.bits, q, None, self.H[q], self.snr_rows[i])
@@ -422,28 +374,9 @@ class DeviceEpochLoop:
 
     def begin_epoch(self, snr_table: np.ndarray):
         """snr_table [steps, B]: the epoch's per-frame training SNRs (one host draw + ONE copy per epoch, :407)"""
-        torch = self.torch
-        if self.overlap:
-            torch.cuda.current_stream(self.tr.device).wait_stream(self.side)     # (nothing of the last epoch is in flight)
-        self.snr.copy_(torch.from_numpy(np.ascontiguousarray(snr_table, dtype=np.float32).reshape(self.steps, -1)))
+        self.snr.copy_(self.torch.from_numpy(np.ascontiguousarray(snr_table, dtype=np.float32).reshape(self.steps, -1)))
         self.acc.zero_()
         self.i = 0
-        self.pending = -1
-        self.fresh_epoch = True                                      # the side stream has not seen this epoch's SNR table yet
-
-    def _produce(self, i: int, q: int):
-        """batch i of the epoch into buffer set q, on the side stream"""
-        torch = self.torch
-        main = torch.cuda.current_stream(self.tr.device)
-        if self.used[q]:
-            self.side.wait_event(self.done[q])
-        if self.fresh_epoch or not self.used[q]:
-            self.side.wait_stream(main)                              # the SNR table copy / first use: the plan's construction
-            self.fresh_epoch = False
-        with torch.cuda.stream(self.side):
-            self._generate(i, q)
-            self.ready[q].record(self.side)
-        self.pending = i
 
     def step(self):
         from ._lib import check
@@ -459,16 +392,9 @@ class DeviceEpochLoop:
                 self._generate(i + 1, q ^ 1)                         # before step i: its optimizer launch normalises it
             last = i + 1 == self.steps                               # the epoch's last step normalises nothing ahead
             pipe = (3 if last else 0) if i == 0 else (2 if last else 1)
-        elif not self.overlap:
+        else:
             q = 0
             self._generate(i, 0)
-        else:
-            q = i & 1
-            if self.pending != i:                                    # first step of an epoch: nothing was produced ahead
-                self._produce(i, q)
-            if i + 1 < self.steps:
-                self._produce(i + 1, q ^ 1)                          # the next batch, while this step runs
-            self.torch.cuda.current_stream(tr.device).wait_event(self.ready[q])
         pl = self.pls[q]
         pl.run(True, pipe=pipe, graph=self.step_graph)
         if self.mon is not None and pipe is not None:
@@ -478,60 +404,14 @@ class DeviceEpochLoop:
                                                 self.F.nsymbol, self.o.K, pl.metrics_buf.data_ptr(), pl.tx_power.data_ptr(),
                                                 None if npow is None else npow.data_ptr(), self.acc.data_ptr(), None,
                                                 self.ws.data_ptr(), self.nws, pl._stream()), "dccn_eq_monitor_accumulate")
-        if self.overlap:
-            self.done[q].record(self.torch.cuda.current_stream(tr.device))
-            self.used[q] = True
 
     def epoch_means(self) -> np.ndarray:
         return self.acc.cpu().numpy() / max(self.steps, 1)
 
 
-class BestSnapshot:
-    """The best-train-loss model of :456-459, kept on the DEVICE: the reference calls ``saver.save`` every time the epoch loss
-    improves; here that is a 28 MB device-to-device copy of the four arenas (microseconds) and the file is written when
-    training ends (also when it ends with an exception or Ctrl-C: the epoch loop flushes in a ``finally``) -- and, checked
-    once per epoch, every ``interval`` seconds in between, so a killed run loses at most that much plus one epoch.  Writing the
-    checkpoint file on every improvement (60 small device-to-host copies + a 21 MB archive) cost as much as half an epoch
-    of training steps."""
-    NAMES = ("params", "adam_m", "adam_v", "adam_state")
-
-    def __init__(self, trainer, path: str, FLAGS, interval: float = 60.0):
-        import torch
-        self.torch, self.tr, self.path, self.FLAGS, self.interval = torch, trainer, path, FLAGS, float(interval)
-        self.bufs = {n: torch.empty_like(getattr(trainer, n)) for n in self.NAMES}
-        self.dirty, self.written, self.t_last = False, False, time.time()
-
-    def take(self):
-        for n, b in self.bufs.items():
-            b.copy_(getattr(self.tr, n))
-        self.dirty = True
-        self.maybe_flush()
-
-    def maybe_flush(self):
-        """call once per epoch, improved or not: a snapshot taken less than ``interval`` seconds after the last write is
-        written by the first later epoch that finds the interval over"""
-        if self.dirty and time.time() - self.t_last > self.interval:
-            self.flush()
-
-    def flush(self) -> str:
-        """write the snapshot (not the trainer's current state) to ``path``; the trainer is left as it was"""
-        if self.dirty:
-            torch = self.torch
-            with torch.no_grad():
-                cur = {n: getattr(self.tr, n).clone() for n in self.NAMES}
-                for n, b in self.bufs.items():
-                    getattr(self.tr, n).copy_(b)
-                save_checkpoint(self.path, self.tr, self.FLAGS)
-                for n, c in cur.items():
-                    getattr(self.tr, n).copy_(c)
-            self.dirty, self.written, self.t_last = False, True, time.time()
-        return self.path if self.written else ""
-
-
-def device_epoch_runner(FLAGS, ofdmobj, trainer, gen, pl, steps: int = 197, overlap: bool = False,
-                        pipeline: Optional[bool] = None):
+def device_epoch_runner(FLAGS, ofdmobj, trainer, gen, pl, steps: int = 197, pipeline: Optional[bool] = None):
     """tools/eqloop.py: one step of the loop below as a callable (SNR table drawn once)"""
-    loop = DeviceEpochLoop(FLAGS, ofdmobj, trainer, gen, pl, steps, overlap=overlap, pipeline=pipeline)
+    loop = DeviceEpochLoop(FLAGS, ofdmobj, trainer, gen, pl, steps, pipeline=pipeline)
     loop.begin_epoch(np.random.choice(TRAIN_SNR_GRID, [steps, pl.batch], p=TRAIN_SNR_PROB))
     return loop.step
 
@@ -544,11 +424,10 @@ def _train_on_device(FLAGS, ofdmobj, trainer, batch_size, frame_cnt, verbose, ru
     # :389-392,409: fading0 (static) unless --mobile, then the mixed-Doppler simulator (mobile=True, mix=True)
     gen = DeviceDataGen(FLAGS, ofdmobj, device=trainer.device, seed=FLAGS.seed, mobile=FLAGS.mobile, mix=FLAGS.mobile)
     pl, ev = trainer.resident(batch_size), trainer.resident(FLAGS.eval_frames)
-    loss_min, epoch_min, best_path, history = 100.0, 0, "", []
+    rule, best_path, history = epochs.BestEpoch(FLAGS.early_stop), "", []
     steps = frame_cnt // batch_size
-    loop = DeviceEpochLoop(FLAGS, ofdmobj, trainer, gen, pl, steps, overlap=bool(getattr(FLAGS, "overlap_generator", False)),
-                           pipeline=getattr(FLAGS, "pipeline_norm", None))
-    best = BestSnapshot(trainer, os.path.join(FLAGS.save_dir, save_model_name(FLAGS)), FLAGS)
+    loop = DeviceEpochLoop(FLAGS, ofdmobj, trainer, gen, pl, steps, pipeline=getattr(FLAGS, "pipeline_norm", None))
+    best = epochs.BestSnapshot(os.path.join(FLAGS.save_dir, save_model_name(FLAGS)), FLAGS, save_checkpoint)
     try:
         for epoch in range(FLAGS.max_epoch_num):
             # (a RandomState of its own -- the same values as np.random.seed + np.random.choice -- so that chains training in
@@ -559,30 +438,18 @@ def _train_on_device(FLAGS, ofdmobj, trainer, batch_size, frame_cnt, verbose, ru
             for i in range(steps):
                 loop.step()
             a = loop.epoch_means()
-            train_loss_epoch = float(a[0])
             snr = rs.choice(TRAIN_SNR_GRID, [FLAGS.eval_frames], p=TRAIN_SNR_PROB)              # :438
-            if loop.sync:
-                gen.make_batch(FLAGS.eval_frames, snr, out_x=ev.x, out_bits=ev.bits, sync=loop.sync)
+            em = epochs.eq_evaluate_on_device(FLAGS, trainer, gen, ev, snr, loop.sync)
+            history.append(epochs.eq_epoch_record(epoch, a, em, verbose))
+            improved, stop = rule.update(epoch, float(a[0]))
+            if improved:
+                best.take(trainer)                                       # :456-459 (device snapshot; file written below)
             else:
-                tx, _ = gen.transmit(FLAGS.eval_frames, out_bits=ev.bits)
-                gen.channel(tx, snr, out_x=ev.x)
-                gen.offset += 1
-            ev.run(False)
-            em = trainer._metrics(ev.metrics_buf, ev.tx_power)
-            history.append(dict(epoch=epoch, train_loss=train_loss_epoch, train_ber=float(a[1]), chan_rms=float(a[4]),
-                                test_loss=em["ce_mean"], test_ber=em["berlin"]))
-            if verbose:
-                print("Epoch: %d  Train Loss: %f  Tx Power: %f  Noise Power: %f  SNR MSE: %f | Test Loss: %f  Test BER: %.8f"
-                      % (epoch, train_loss_epoch, a[2], a[3], a[4], em["ce_mean"], em["berlin"]))
-            if train_loss_epoch < loss_min:
-                epoch_min, loss_min = epoch, train_loss_epoch
-                best.take()                                              # :456-459 (device snapshot; file written below)
-            else:
-                best.maybe_flush()                                       # an older snapshot whose interval has run out
-            if epoch - FLAGS.early_stop > epoch_min:
+                best.maybe_flush(trainer)                                # an older snapshot whose interval has run out
+            if stop:
                 break
     finally:
-        best_path = best.flush()                                         # also on exceptions / KeyboardInterrupt
+        best_path = best.flush(trainer)                                  # also on exceptions / KeyboardInterrupt
     if verbose:
         print("Training Done!, Best model saved to\n%s" % best_path)
     result = dict(history=history, best_path=best_path, trainer=trainer)

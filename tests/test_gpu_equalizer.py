@@ -653,25 +653,6 @@ def test_monitor_launch_equals_the_framework_monitors(B, per_symbol):
     assert abs(ref - float(rms)) <= 1e-5 * max(want, 1e-3)
 
 
-def test_generator_on_a_side_stream_trains_the_same_equaliser(tmp_path):
-    """receiver_mp.DeviceEpochLoop: two resident buffer sets and the generator on its own HIP stream (batch i+1 produced while
-    step i runs) against the one-stream loop: same seeds -> history and trained parameters identical bit for bit over 3 epochs
-    of 28 steps (a missed dependency trains on a half-written batch, stale labels or the wrong SNR row)."""
-    from dl_ofdm_amd import receiver as R, receiver_mp as H
-    from dl_ofdm_amd.engine import glorot_init
-    from dl_ofdm_amd import ofdm
-    out = []
-    for overlap in (False, True):
-        hf = H.Flags(nbits=2, nfilter=64, channel="EPA", msg_length=7 * 2048, batch_size=512, max_epoch_num=3,
-                     early_stop=100, token="OV", save_dir=str(tmp_path / ("overlap_%d" % overlap)) + "/", seed=6, eval_frames=512,
-                     device_data=True, overlap_generator=overlap)
-        o = ofdm.ofdm_tx(hf)
-        res = H.train(hf, verbose=False, run_test=False, rx_params=glorot_init(R.rx_dims(hf, o), 1))
-        out.append((res["history"], res["trainer"].params.detach().clone()))
-    assert out[0][0] == out[1][0]
-    assert torch.equal(out[0][1], out[1][1])
-
-
 def test_next_batch_normalised_on_the_optimizer_launch_trains_the_same_equaliser(tmp_path):
     """include/dccn.h dccn_eq_buffers.x_next / x_prenormalised / norm_slot: step i normalises batch i+1 on leading workgroups
     of its optimizer launch and step i+1 starts at the layer norm (receiver_mp.DeviceEpochLoop pipeline, twin plans sharing

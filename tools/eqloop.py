@@ -89,7 +89,6 @@ def main():
     variants = [("harness_loop", full), ("no_monitor", no_monitor), ("generator_only", gen_only), ("step_graph", step_graph),
                 ("step_eager", step_eager)]
     if hasattr(M, "device_epoch_runner"):
-        variants.insert(0, ("r04_loop_generator_on_side_stream", M.device_epoch_runner(F, o, tr, gen, pl, overlap=True)))
         try:
             variants.insert(0, ("r04_loop_next_batch_normalised_on_the_optimizer_launch",
                                 M.device_epoch_runner(F, o, tr, gen, pl, pipeline=True)))
@@ -156,7 +155,7 @@ def ab(args, F, o):
         v = sorted(ms)
         med = v[len(v) // 2]
         rec = {"variant": "harness_loop_ab", "frames": B, "channel": args.channel, "mobile": args.mobile, "CP": o.CP, "fused": fused,
-               "virtual_next": loop.virt is not None, "generator_issued_by_step": bool(getattr(loop, "ride_gen", False)) and loop.virt is not None,
+               "virtual_next": loop.virt is not None, "generator_issued_by_step": loop.ride_gen,
                "ms_per_step_wall": [round(t, 4) for t in ms], "median": round(med, 4), "spread": round((v[-1] - v[0]) / med, 4)}
         print(json.dumps(rec), flush=True)
         if args.out:

@@ -61,3 +61,47 @@ for cp in (True, False):
         eng.train_step_generated(fg, slot=i & 1, last=(i == 2))
     torch.cuda.synchronize()
     print("steps cp", int(cp), "kin", eng.shape.kin, "params", h(eng.params), "adam_m", h(eng.adam_m), "adam_v", h(eng.adam_v))
+
+# the driver: receiver.train over each feeding route, 2 epochs of 4 steps of 73 frames -- and one BPSK run at the default epoch
+# length whose batch grows after the first epoch (the engine is swapped under the optimizer state and the best-model snapshot);
+# every row also hashes the arrays of the best-model file
+import tempfile      # noqa: E402
+
+import numpy as np      # noqa: E402
+
+import dl_ofdm_amd.engine as E      # noqa: E402
+
+made = []
+
+
+class Recording(RxEngine):
+    """receiver.train returns the parameters only: keep the engines it builds, for their optimizer state"""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        made.append(self)
+
+
+E.RxEngine = Recording              # (receiver.train looks the class up when it is called)
+
+small = dict(nbits=2, msg_length=7 * 73 * 5, max_epoch_num=2, eval_frames=128)
+for name, kw in (("fused generator", dict(device_data=True, **small)),
+                 ("side-stream feeder", dict(device_data=True, no_fused_generator=True, **small)),
+                 ("host batches", dict(device_data=False, **small)),
+                 ("cp off", dict(device_data=True, cp=False, **small)),
+                 ("batch grows", dict(device_data=True, nbits=1, channel="AWGN", max_epoch_num=2))):
+    with tempfile.TemporaryDirectory() as tmp:
+        kw = dict(dict(nfilter=64, channel="EPA", SNR=10.0, seed=7, early_stop=200, token="t", save_dir=tmp + "/"), **kw)
+        extra = {k: kw.pop(k) for k in ("no_fused_generator",) if k in kw}      # (read by the driver, not a declared flag)
+        F = R.Flags(**kw)
+        for k, v in extra.items():
+            setattr(F, k, v)
+        del made[:]
+        res = R.train(F, verbose=False, run_test=False)
+        torch.cuda.synchronize()
+        eng = [e for e in made if e.train][-1]               # (the batch only grows: the last training engine holds the final state)
+        z = np.load(res["best_path"] + ".npz", allow_pickle=False)
+        saved = hashlib.sha256(b"".join(z[k].tobytes() for k in sorted(z.files) if k != "__flags__")).hexdigest()[:16]
+        print("train", name, "batch", [e["batch_size"] for e in res["history"]], *sum(((n, h(getattr(eng, n))) for n in
+              ("params", "adam_m", "adam_v", "adam_state")), ()), "history",
+              hashlib.sha256(repr(res["history"]).encode()).hexdigest()[:16], "saved", saved)
