@@ -226,6 +226,8 @@ SIGNATURES = {
     "dccn_frame_sync_supported": (_i, [_i] * 4),
     "dccn_frame_sync": (_i, [_vp] + [_i] * 6 + [_vp] * 4),
     "dccn_frame_sync_cfo": (_i, [_vp] + [_i] * 6 + [_vp] * 5),
+    "dccn_capture_sync_supported": (_i, [_i] * 4),
+    "dccn_capture_sync": (_i, [_vp] + [c_longlong] * 3 + [_i] * 6 + [_vp] * 5),
     "dccn_rx_normalise": (_i, [POINTER(RxShape), POINTER(RxBuffers), _vp]),
     "dccn_rx_graph_create": (_i, [POINTER(RxShape), POINTER(RxBuffers), _i, AdamHParams, _vp, POINTER(c_void_p)]),
     "dccn_rx_graph_launch": (_i, [_vp, _vp]),

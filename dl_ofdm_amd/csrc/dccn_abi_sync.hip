@@ -33,6 +33,40 @@ int frame_sync_plan(const float* x, int frames, int S, int K, int CP, int W, int
     plan->lds = kSyncWaves * frame_sync_lds_per_frame(T);
     return DCCN_OK;
 }
+
+struct CaptureSyncPlan {
+    CaptureSyncArgs args;
+    unsigned blocks;
+    size_t lds;
+};
+
+int capture_sync_plan(const float* cap, long long n_samples, long long first, long long stride, int frames, int S, int K, int CP,
+                      int W, int out_kin, float* x_out, int32_t* offset, float* cfo, float* metric, CaptureSyncPlan* plan) {
+    if (!capture_sync_shape_ok(S, K, CP, W) || frames <= 0 || !cap || !offset) return DCCN_ERR_INVALID_ARG;
+    if (out_kin != K + CP && out_kin != K) return DCCN_ERR_INVALID_ARG;
+    if (!aligned16(cap) || !aligned16(x_out) || !aligned16(metric)) return DCCN_ERR_INVALID_ARG;
+    const long long T = (long long)S * (K + CP);
+    if (x_out && out_kin == K && (S * K) % 2 != 0) return DCCN_ERR_INVALID_ARG;
+    // every window [b_f - W, b_f + T + W) inside the capture, frames not overlapping: first - W >= 0 and
+    // first + (frames - 1) stride + T + W <= n_samples, the product taken as a quotient so nothing overflows
+    if (n_samples <= 0 || n_samples > (1LL << 58) || stride < T || first < W || first > n_samples) return DCCN_ERR_INVALID_ARG;
+    const long long room = n_samples - first - T - W;
+    if (room < 0 || (frames > 1 && stride > room / (frames - 1))) return DCCN_ERR_INVALID_ARG;
+    if (x_out && ranges_overlap(cap, (size_t)n_samples * 8, x_out, (size_t)frames * S * out_kin * 8)) return DCCN_ERR_INVALID_ARG;
+    plan->args = CaptureSyncArgs{cap, first, stride, x_out, offset, metric, cfo, frames, S, K, CP, W, out_kin == K ? 1 : 0};
+    plan->blocks = (unsigned)ceil_div(frames, kSyncWaves);
+    plan->lds = kSyncWaves * capture_sync_lds_per_frame((int)T, W);
+    return DCCN_OK;
+}
+
+template <bool CFO>
+int capture_sync_launch(const CaptureSyncPlan& plan, dccn_stream_t stream) {
+    DCCN_TRY(set_max_dynamic_smem((const void*)capture_sync_kernel<CFO>, plan.lds));
+    hipLaunchKernelGGL(capture_sync_kernel<CFO>, dim3(plan.blocks), dim3(kSyncWaves * kSyncLanes), plan.lds, (hipStream_t)stream,
+                       plan.args);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -61,6 +95,16 @@ int dccn_frame_sync_cfo(const float* x, int frames, int S, int K, int CP, int W,
                        FrameSyncCfoArgs{plan.args, cfo});
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
+}
+
+int dccn_capture_sync_supported(int S, int K, int CP, int W) { return capture_sync_shape_ok(S, K, CP, W) ? 1 : 0; }
+
+int dccn_capture_sync(const float* cap, long long n_samples, long long first, long long stride, int frames, int S, int K, int CP,
+                      int W, int out_kin, float* x_out, int32_t* offset, float* cfo, float* metric, dccn_stream_t stream) {
+    CaptureSyncPlan plan;
+    DCCN_TRY(capture_sync_plan(cap, n_samples, first, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo, metric, &plan));
+    DCCN_NO_CHAINS();
+    return cfo ? capture_sync_launch<true>(plan, stream) : capture_sync_launch<false>(plan, stream);
 }
 
 }  // extern "C"

@@ -13,6 +13,12 @@
 // One wave per frame, four frames per 256-thread block; no atomics, no workspace, every sum in a fixed order (two runs give
 // the same bits).  The frame is read once (16-byte loads) into the wave's own LDS region, every later step reads LDS, and the
 // rotated frame leaves with 16-byte stores: the traffic of the copy the launch stands in for.
+//
+// dccn_capture_sync (capture_sync_kernel, at the end) is the same estimator on frames that still sit inside one contiguous capture
+// c[n]: frame f nominally starts at b = first + f * stride, its window [b - W, b + T + W) is indexed linearly (nothing wraps: the
+// samples around the frame are its neighbours in the air), and out[n] = c[b + offset + n].  The sums, their order, the stores and
+// the derotation are stated once (sync_estimate, sync_store, sync_cfo_store); the two families differ in the index mapping alone
+// (SyncCircular, SyncLinear: where a sample of the frame sits in the wave's LDS region).
 #pragma once
 #include "common.h"
 
@@ -32,6 +38,19 @@ static inline bool frame_sync_shape_ok(int S, int K, int CP, int W) {
     return kSyncWaves * frame_sync_lds_per_frame((int)T) <= kSyncLdsMax;
 }
 
+// The index mapping: slot(j) is the LDS slot of sample j of the nominal frame, j in [-W, W + CP); ahead(slot, d) the slot of the
+// sample d in [0, T) further on.
+struct SyncCircular {       // the region holds the frame's T samples and indices wrap (W <= CP < T)
+    int T;
+    __device__ __forceinline__ int slot(const int j) const { return (j + T) % T; }
+    __device__ __forceinline__ int ahead(const int slot, const int d) const { return (slot + d) % T; }
+};
+struct SyncLinear {         // the region holds the window's T + 2 W samples, sample -W in slot 0; nothing wraps
+    int W;
+    __device__ __forceinline__ int slot(const int j) const { return j + W; }
+    __device__ __forceinline__ int ahead(const int slot, const int d) const { return slot + d; }
+};
+
 struct FrameSyncArgs {
     const float* x;     // [frames, T, 2]
     float* x_out;       // nullable: [frames, S, out_kin, 2]
@@ -41,26 +60,26 @@ struct FrameSyncArgs {
     int crop;           // 1: x_out rows are the K samples behind each symbol's prefix (out_kin == K)
 };
 
-// Steps 2-4 on a frame that sits in the wave's LDS region (y: its T samples, pe: the kSyncLanes (P, E) slots behind them):
-// the frame's offset, the same value in every lane.  The block's barriers are inside: every wave of the block calls this, live or
-// not.  Shared by the frame_sync kernels and gen_apply_sync_kernel (datagen.h): one statement of the sums and their order.
-// gamma_out (nullable): Gamma at the returned offset, the winning lane's sums handed to every lane.
-__device__ __forceinline__ int frame_sync_estimate(const float2* y, float4* pe, const int lane, const bool live, const int S,
-                                                   const int K, const int CP, const int W, float* metric_row,
-                                                   float2* gamma_out = nullptr) {
-    const int N = K + CP, T = S * N;
+// Steps 2-4 on a frame that sits in the wave's LDS region (y: its samples, placed as `at` says; pe: the kSyncLanes (P, E) slots
+// behind them): the frame's offset, the same value in every lane.  The block's barriers are inside: every wave of the block calls
+// this, live or not.  Shared by the frame_sync kernels, capture_sync_kernel and gen_apply_sync_kernel (datagen.h): one statement
+// of the sums and their order.  gamma_out (nullable): Gamma at the returned offset, the winning lane's sums handed to every lane.
+template <class At>
+__device__ __forceinline__ int sync_estimate(const At at, const float2* y, float4* pe, const int lane, const bool live, const int S,
+                                             const int K, const int CP, const int W, float* metric_row, float2* gamma_out) {
+    const int N = K + CP;
     __syncthreads();                                    // (the frame is complete in LDS)
 
     // 2. P[j], E[j] for j = lane - W in [-W, W + CP): the S symbols in order
     if (live && lane < 2 * W + CP) {
         float pr = 0.f, pi = 0.f, e = 0.f;
-        int n = (lane - W + T) % T;                     // (W <= CP < T)
+        int n = at.slot(lane - W);
         for (int s = 0; s < S; ++s) {
-            const float2 u = y[n], v = y[(n + K) % T];
+            const float2 u = y[n], v = y[at.ahead(n, K)];
             pr += u.x * v.x + u.y * v.y;
             pi += u.y * v.x - u.x * v.y;
             e += 0.5f * ((u.x * u.x + u.y * u.y) + (v.x * v.x + v.y * v.y));
-            n = (n + N) % T;
+            n = at.ahead(n, N);
         }
         pe[lane] = make_float4(pr, pi, e, 0.f);
     }
@@ -98,28 +117,39 @@ __device__ __forceinline__ int frame_sync_estimate(const float2* y, float4* pe, 
     if (gamma_out) *gamma_out = make_float2(__shfl(gam.x, best), __shfl(gam.y, best));
     return best - W;
 }
+// the circular frame (the frame_sync kernels and gen_apply_sync_kernel)
+__device__ __forceinline__ int frame_sync_estimate(const float2* y, float4* pe, const int lane, const bool live, const int S,
+                                                   const int K, const int CP, const int W, float* metric_row,
+                                                   float2* gamma_out = nullptr) {
+    return sync_estimate(SyncCircular{S * (K + CP)}, y, pe, lane, live, S, K, CP, W, metric_row, gamma_out);
+}
 
-// Step 5: the frame rotated by theta, from LDS to dst (the frame's [S, K + CP, 2] rows, or crop: its [S, K, 2] rows behind each
-// symbol's prefix): two complex samples per 16-byte store, each read at its own (shifted) place
-__device__ __forceinline__ void frame_sync_store(const float2* y, float* dst_, const int theta, const int lane, const int S,
-                                                 const int K, const int CP, const int crop) {
+// Step 5: the frame from its sample theta on, from LDS to dst (the frame's [S, K + CP, 2] rows, or crop: its [S, K, 2] rows behind
+// each symbol's prefix): two complex samples per 16-byte store, each read at its own (shifted) place
+template <class At>
+__device__ __forceinline__ void sync_store(const At at, const float2* y, float* dst_, const int theta, const int lane, const int S,
+                                           const int K, const int CP, const int crop) {
     const int N = K + CP, T = S * N;
-    const int rot = (theta + T) % T;
+    const int rot = at.slot(theta);
     float4* dst = reinterpret_cast<float4*>(dst_);
     if (crop) {
         const int M = S * K;
         for (int i = lane; i < M / 2; i += kSyncLanes) {
             const int m0 = 2 * i, m1 = 2 * i + 1;
-            const float2 u = y[((m0 / K) * N + CP + m0 % K + rot) % T];
-            const float2 v = y[((m1 / K) * N + CP + m1 % K + rot) % T];
+            const float2 u = y[at.ahead(rot, (m0 / K) * N + CP + m0 % K)];
+            const float2 v = y[at.ahead(rot, (m1 / K) * N + CP + m1 % K)];
             dst[i] = make_float4(u.x, u.y, v.x, v.y);
         }
     } else {
         for (int i = lane; i < T / 2; i += kSyncLanes) {
-            const float2 u = y[(2 * i + rot) % T], v = y[(2 * i + 1 + rot) % T];
+            const float2 u = y[at.ahead(rot, 2 * i)], v = y[at.ahead(rot, 2 * i + 1)];
             dst[i] = make_float4(u.x, u.y, v.x, v.y);
         }
     }
+}
+__device__ __forceinline__ void frame_sync_store(const float2* y, float* dst_, const int theta, const int lane, const int S,
+                                                 const int K, const int CP, const int crop) {
+    sync_store(SyncCircular{S * (K + CP)}, y, dst_, theta, lane, S, K, CP, crop);
 }
 
 // Step 5 of the CFO variant: sample n of the ALIGNED frame leaves as aligned[n] * exp(-2 pi i cfo n / K).  The phase is taken in
@@ -131,19 +161,36 @@ __device__ __forceinline__ float2 frame_cfo_derotate(const float2 u, const float
     sincospif(2.0f * (turns - rintf(turns)), &sn, &cs);
     return make_float2(u.x * cs + u.y * sn, u.y * cs - u.x * sn);
 }
-__device__ __forceinline__ void frame_cfo_store(const float2* y, float* dst_, const int theta, const float cfo, const int lane,
-                                                const int S, const int K, const int CP, const int crop) {
+template <class At>
+__device__ __forceinline__ void sync_cfo_store(const At at, const float2* y, float* dst_, const int theta, const float cfo,
+                                               const int lane, const int S, const int K, const int CP, const int crop) {
     const int N = K + CP, T = S * N;
-    const int rot = (theta + T) % T;
+    const int rot = at.slot(theta);
     const float fK = (float)K;
     float4* dst = reinterpret_cast<float4*>(dst_);
     const int M = crop ? S * K : T;
     for (int i = lane; i < M / 2; i += kSyncLanes) {
         const int m0 = 2 * i, m1 = 2 * i + 1;
         const int n0 = crop ? (m0 / K) * N + CP + m0 % K : m0, n1 = crop ? (m1 / K) * N + CP + m1 % K : m1;
-        const float2 u = frame_cfo_derotate(y[(n0 + rot) % T], cfo, n0, fK);
-        const float2 v = frame_cfo_derotate(y[(n1 + rot) % T], cfo, n1, fK);
+        const float2 u = frame_cfo_derotate(y[at.ahead(rot, n0)], cfo, n0, fK);
+        const float2 v = frame_cfo_derotate(y[at.ahead(rot, n1)], cfo, n1, fK);
         dst[i] = make_float4(u.x, u.y, v.x, v.y);
+    }
+}
+
+// What follows the estimate, stated once: the offset, the CFO variant's estimate, and the frame on its way out.
+template <bool CFO, class At>
+__device__ __forceinline__ void sync_finish(const At at, const float2* y, const long long f, const int theta, const float2 gamma,
+                                            const int lane, float* x_out, int32_t* offset, float* cfo_out, const int S, const int K,
+                                            const int CP, const int crop) {
+    if (lane == 0) offset[f] = theta;
+    float* const dst = x_out + (size_t)f * S * (crop ? K : K + CP) * 2;
+    if constexpr (CFO) {
+        const float cfo = 0.f - atan2f(gamma.y, gamma.x) / 6.283185307179586f;     // (0 - a: +0 where the angle is 0)
+        if (lane == 0) cfo_out[f] = cfo;
+        if (x_out) sync_cfo_store(at, y, dst, theta, cfo, lane, S, K, CP, crop);
+    } else {
+        if (x_out) sync_store(at, y, dst, theta, lane, S, K, CP, crop);
     }
 }
 
@@ -164,19 +211,11 @@ __device__ __forceinline__ void frame_sync_body(const FrameSyncArgs& a, float* c
         const float4* src = reinterpret_cast<const float4*>(a.x + (size_t)f * T * 2);
         for (int i = lane; i < T / 2; i += kSyncLanes) region[i] = src[i];
     }
-    float2 gamma;
+    float2 gamma = make_float2(0.f, 0.f);
     const int theta = frame_sync_estimate(y, pe, lane, live, a.S, a.K, a.CP, W,
                                           (live && a.metric) ? a.metric + (size_t)f * (2 * W + 1) : nullptr, CFO ? &gamma : nullptr);
     if (!live) return;
-    if (lane == 0) a.offset[f] = theta;
-    float* const dst = a.x_out + (size_t)f * a.S * (a.crop ? a.K : a.K + a.CP) * 2;
-    if constexpr (CFO) {
-        const float cfo = 0.f - atan2f(gamma.y, gamma.x) / 6.283185307179586f;     // (0 - a: +0 where the angle is 0)
-        if (lane == 0) cfo_out[f] = cfo;
-        if (a.x_out) frame_cfo_store(y, dst, theta, cfo, lane, a.S, a.K, a.CP, a.crop);
-    } else {
-        if (a.x_out) frame_sync_store(y, dst, theta, lane, a.S, a.K, a.CP, a.crop);
-    }
+    sync_finish<CFO>(SyncCircular{T}, y, f, theta, gamma, lane, a.x_out, a.offset, cfo_out, a.S, a.K, a.CP, a.crop);
 }
 
 static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) frame_sync_kernel(const FrameSyncArgs a) {
@@ -189,6 +228,75 @@ struct FrameSyncCfoArgs {
 };
 static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) frame_sync_cfo_kernel(const FrameSyncCfoArgs a) {
     frame_sync_body<true>(a.s, a.cfo);
+}
+
+// ---- frames cut from a contiguous capture (dccn_capture_sync) -----------------------------------------------------------------
+// Frame f's window is the samples [b - W, b + T + W) of the capture, b = first + f * stride; it is all the wave reads.  The
+// capture's base is 16-byte aligned, so EVEN samples are: the wave's region starts at the even sample a0 = (b - W) & ~1 and holds
+// pairs (a0 + 2 i, a0 + 2 i + 1), one 16-byte load each.  A window that starts on an odd sample has its first sample in the
+// upper half of pair 0, and then (T + 2 W is even) its last sample in the lower half of the last pair: those two pairs are read
+// with one 8-byte load of the half that belongs to the window, so no lane reads a sample outside it -- the neighbour may lie
+// past either end of the capture.  The window then sits in the region from slot sh = (b - W) & 1 on; one spare pair per frame.
+__host__ __device__ static inline size_t capture_sync_lds_per_frame(int T, int W) {
+    return (size_t)(T + 2 * W + 2) * 8 + (size_t)kSyncLanes * 16;
+}
+
+static inline bool capture_sync_shape_ok(int S, int K, int CP, int W) {
+    if (!frame_sync_shape_ok(S, K, CP, W)) return false;
+    return kSyncWaves * capture_sync_lds_per_frame(S * (K + CP), W) <= kSyncLdsMax;
+}
+
+struct CaptureSyncArgs {
+    const float* cap;           // [n_samples, 2]
+    long long first, stride;    // frame f nominally starts at sample first + f * stride
+    float* x_out;               // nullable: [frames, S, out_kin, 2]
+    int32_t* offset;            // [frames]
+    float* metric;              // nullable: [frames, 2 W + 1]
+    float* cfo;                 // [frames], the CFO instantiation only
+    int frames, S, K, CP, W;
+    int crop;
+};
+
+template <bool CFO>
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_kernel(const CaptureSyncArgs a) {
+    extern __shared__ float4 sync_lds[];
+    const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
+    const int T = a.S * (a.K + a.CP), W = a.W;
+    const long long f = (long long)blockIdx.x * kSyncWaves + wave;
+    const bool live = f < a.frames;
+    const size_t per = capture_sync_lds_per_frame(T, W) / 16;
+    float4* const region = sync_lds + (size_t)wave * per;
+    float4* const pe = region + (per - kSyncLanes);
+    const long long start = live ? a.first + f * a.stride - W : 0;          // the window's first sample
+    const int sh = (int)(start & 1);
+    const float2* const y = reinterpret_cast<const float2*>(region) + sh;    // slot 0 = sample start
+
+    // 1. the window, once, into LDS
+    if (live) {
+        const int len = T + 2 * W;                       // even
+        const float2* const src2 = reinterpret_cast<const float2*>(a.cap) + (start - sh);
+        const float4* const src4 = reinterpret_cast<const float4*>(src2);
+        const int pairs = (len + 2 * sh) / 2;            // sh = 1: one more pair, the first and the last half inside
+        for (int i = lane; i < pairs; i += kSyncLanes) {
+            float4 v;
+            if (sh && i == 0) {
+                const float2 h = src2[1];
+                v = make_float4(0.f, 0.f, h.x, h.y);
+            } else if (sh && i == pairs - 1) {
+                const float2 h = src2[2 * i];
+                v = make_float4(h.x, h.y, 0.f, 0.f);
+            } else {
+                v = src4[i];
+            }
+            region[i] = v;
+        }
+    }
+    const SyncLinear at{W};
+    float2 gamma = make_float2(0.f, 0.f);
+    const int theta = sync_estimate(at, y, pe, lane, live, a.S, a.K, a.CP, W,
+                                    (live && a.metric) ? a.metric + (size_t)f * (2 * W + 1) : nullptr, CFO ? &gamma : nullptr);
+    if (!live) return;
+    sync_finish<CFO>(at, y, f, theta, gamma, lane, a.x_out, a.offset, a.cfo, a.S, a.K, a.CP, a.crop);
 }
 
 }  // namespace dccn

@@ -385,6 +385,13 @@ class EqualizerTrainer:
         from .receive import chain_receive
         return chain_receive(self, x, want_llr, want_prob, sync, cfo)
 
+    def receive_capture(self, cap, first: int, stride: Optional[int] = None, sync: int = 3, cfo: bool = False,
+                        want_llr: bool = False, want_prob: bool = False, frames: Optional[int] = None):
+        """:meth:`receive` on frames that still sit inside one contiguous capture ``cap [n, 2]``, cut at their estimated starts
+        by one launch in front of the step (:func:`dl_ofdm_amd.receive.chain_receive_capture`)."""
+        from .receive import chain_receive_capture
+        return chain_receive_capture(self, cap, first, stride, sync, cfo, want_llr, want_prob, frames)
+
     def adam(self) -> dict:
         s = self.adam_state.cpu().numpy()
         return dict(global_step=float(s[0]), beta1_power=float(s[1]), beta2_power=float(s[2]), alpha=float(s[3]))

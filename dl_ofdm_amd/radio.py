@@ -167,6 +167,56 @@ class rayleigh_chan_lte:
     def __call__(self, inputs):
         return self.run(inputs)
 
+    def run_stream(self, inputs: np.ndarray, lead: int):
+        """The frames of ``run`` as ONE contiguous capture, static channels only: ``(cap complex64 [lead + n_fr T + lead], H)``.
+
+        Frame ``f``'s transmitted samples go through frame ``f``'s impulse response as a FULL convolution (``T + L - 1``
+        samples), and the convolutions are overlap-added at ``lead + f T - (L - 1) // 2`` -- the centring of ``run``'s
+        ``mode='same'`` -- so a frame's tails fall into its neighbours, as they do on the air, instead of being cut off.
+        ``lead`` zero samples stand before the first frame and after the last (``lead >= L - 1``: room for the tails).  The
+        random stream is consumed exactly as ``run`` consumes it: the same seed gives the same taps and the same ``H``, and away
+        from a frame's borders the same samples.  A profile that would draw Doppler frames raises ``ValueError``."""
+        if not np.iscomplexobj(inputs):
+            raise AssertionError("complex baseband input expected")
+        n_fr, n_sym, n_sc = inputs.shape
+        T, lead = n_sym * n_sc, int(lead)
+        H = np.zeros((n_fr, n_sym, self.nfft), dtype=np.complex64)
+        flat_in = inputs.reshape(n_fr, T).astype(np.complex128)
+        n_prof = len(self.profiles)
+        if self.chan != "awgn" and self.mobile and any(p.Fd > 0.1 for p in self.profiles) and (n_prof == 1 or self.mix):
+            raise ValueError("run_stream handles static frames only (this profile draws Doppler frames)")
+        g_of = [np.ones(1, dtype=np.complex128)] * n_fr                  # identity where no taps are drawn
+        if self.chan == "awgn":
+            H[:] = 1.0
+        else:
+            static = {i: ([], []) for i in range(n_prof)}
+            for fr in range(n_fr):                                        # run's order of draws
+                pi = fr % n_prof if n_prof > 1 else 0
+                if self.chan == "mixall" and pi == 0:
+                    H[fr] = np.fft.fft(np.array([1 + 0j]), self.nfft)
+                    continue
+                static[pi][0].append(fr)
+                static[pi][1].append(self._static_taps(self.profiles[pi]))
+            for pi, (frames, taps) in static.items():                     # run's batched products: the same g, the same H
+                if not frames:
+                    continue
+                g = np.asarray(taps) @ self.profiles[pi].alpha            # [n, L]
+                H[frames] = np.fft.fft(g, self.nfft, axis=1)[:, None, :]
+                for i, fr in enumerate(frames):
+                    g_of[fr] = g[i]
+        need = max(len(g) for g in g_of) - 1
+        if lead < need:
+            raise ValueError("run_stream: lead = %d leaves no room for the %d-sample tails" % (lead, need))
+        cap = np.zeros(2 * lead + n_fr * T, dtype=np.complex128)
+        for fr, g in enumerate(g_of):
+            L = len(g)
+            full = np.zeros(T + L - 1, dtype=np.complex128)
+            for l in range(L):                                            # run's order of terms: full[t] = sum_l g[l] tx[t - l]
+                full[l:l + T] += g[l] * flat_in[fr]
+            at = lead + fr * T - (L - 1) // 2
+            cap[at:at + T + L - 1] += full
+        return cap.astype(np.complex64), H
+
 
 def apply_cfo(x: np.ndarray, eps, K: int) -> np.ndarray:
     """A carrier-frequency offset of ``eps`` subcarrier spacings (scalar or ``[frames]``) on frames ``x [frames, S, K + CP, 2]``:
@@ -178,6 +228,20 @@ def apply_cfo(x: np.ndarray, eps, K: int) -> np.ndarray:
     e = np.broadcast_to(np.asarray(eps, dtype=np.float64).reshape(-1, 1), (frames, 1))
     y = y * np.exp(2j * np.pi * e * np.arange(y.shape[1], dtype=np.float64)[None, :] / float(K))
     return np.stack([y.real, y.imag], axis=-1).reshape(x.shape).astype(np.float32)
+
+
+def apply_cfo_stream(cap: np.ndarray, eps: float, K: int) -> np.ndarray:
+    """A carrier-frequency offset of ``eps`` subcarrier spacings (a scalar) on a contiguous capture: ``cap[n] * exp(+2 pi i eps n
+    / K)`` with ``n`` running over the WHOLE capture -- the phase is continuous across frames, as a front end's is, where
+    :func:`apply_cfo` restarts it in every frame.  ``cap``: complex ``[n]`` -> complex128 ``[n]``, or float ``[n, 2]`` -> float32
+    ``[n, 2]``; multiplied in fp64."""
+    cap = np.asarray(cap)
+    pairs = not np.iscomplexobj(cap)
+    y = cap[..., 0].astype(np.float64) + 1j * cap[..., 1].astype(np.float64) if pairs else cap.astype(np.complex128)
+    if y.ndim != 1:
+        raise ValueError("apply_cfo_stream takes one capture: complex [n] or float [n, 2]")
+    y = y * np.exp(2j * np.pi * float(eps) * np.arange(y.shape[0], dtype=np.float64) / float(K))
+    return np.stack([y.real, y.imag], axis=-1).astype(np.float32) if pairs else y
 
 
 def AWGN_channel_np(inputs: np.ndarray, SNR):

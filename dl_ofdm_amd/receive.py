@@ -84,12 +84,15 @@ class RxReceiver:
     """
 
     def __init__(self, dims: RxDims, batch: int, params: Optional[Dict[str, np.ndarray]] = None, device="cuda",
-                 want_llr: bool = False, want_prob: bool = False, seed: int = 1, CP: Optional[int] = None):
+                 want_llr: bool = False, want_prob: bool = False, seed: int = 1, CP: Optional[int] = None,
+                 K: Optional[int] = None):
         """``CP``: the frames' cyclic-prefix length, for ``receive(x, sync=W)`` of a receiver that takes whole symbols
         (``dims.kin == K + CP``: K cannot be read off the shape).  A ``cp=False`` receiver (``dims.kin == K``) finds it from
-        the frames it is given."""
+        the frames it is given.  ``receive_capture`` has no frame shape to look at: it needs ``CP``, and takes ``K`` as
+        ``dims.kin - CP`` (whole symbols) unless ``K`` says otherwise (``K=dims.kin``: a ``cp=False`` receiver)."""
         self.lib = _lib.load()
         self.CP = None if CP is None else int(CP)
+        self.K = None if K is None else int(K)
         self._syncs: Dict[tuple, object] = {}
         self.dims, self.batch = dims, int(batch)
         self.device = torch.device(device)
@@ -176,6 +179,34 @@ class RxReceiver:
         check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
         return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, est)
 
+    def receive_capture(self, cap, first: int, stride: Optional[int] = None, sync: int = 3, cfo: bool = False) -> ReceiveResult:
+        """One receive step on ``batch`` frames that still sit inside one contiguous capture ``cap`` (device tensor ``float32
+        [n, 2]``): frame ``f`` nominally starts at sample ``first + f * stride`` (``None``: frames back to back) and may sit up to
+        ``sync = W > 0`` samples off.  One launch (:class:`~dl_ofdm_amd.sync.CaptureSync`) stands where ``receive(x, sync=W)``
+        has its alignment launch: it cuts each frame at its own estimated start -- linearly, the samples it brings in are the
+        capture's, not the frame's other end -- and writes it straight into ``self.x`` (only the K samples behind each prefix
+        when ``dims.kin == K``).  ``cfo=True`` takes each frame's carrier-frequency offset out on the way.  Needs
+        ``RxReceiver(..., CP=...)``, and ``K=dims.kin`` as well for a ``cp=False`` receiver: a capture has no shape to read them
+        off.  ``result.offset`` / ``result.cfo``."""
+        from .sync import CaptureSync
+        W = int(sync)
+        if W <= 0:
+            raise _lib.DccnError("receive_capture needs sync = W > 0")
+        if self.CP is None:
+            raise _lib.DccnError("receive_capture needs RxReceiver(..., CP=...)")
+        kin = self.dims.kin
+        K = kin - self.CP if self.K is None else self.K
+        if K < 1 or kin not in (K + self.CP, K):
+            raise _lib.DccnError("receive_capture: K = %d, CP = %d do not fit kin = %d" % (K, self.CP, kin))
+        key = ("capture", W, bool(cfo))
+        if key not in self._syncs:
+            self._syncs[key] = CaptureSync(self.dims.S, K, self.CP, W, self.batch, self.device, out_kin=kin, want_metric=False,
+                                           cfo=bool(cfo))
+        cs = self._syncs[key]
+        _, offset = cs.run(cap, first, stride, out=self.x)
+        check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
+        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, cs.cfo)
+
 
 def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: int = 0, cfo: bool = False) -> ReceiveResult:
     """Equaliser + frozen receiver chain (``EqualizerTrainer.receive``): ``dccn_eq_receive_step`` on the trainer's resident
@@ -205,6 +236,42 @@ def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: 
         pl.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(pl.x.shape), non_blocking=True)
     packed, llr, prob = pl.receive(want_llr, want_prob)
     return ReceiveResult(packed, llr, prob, int(tr.ofdmobj.frame_size), int(tr.FLAGS.nbits), offset, est)
+
+
+def chain_receive_capture(tr, cap, first: int, stride: Optional[int] = None, sync: int = 3, cfo: bool = False,
+                          want_llr: bool = False, want_prob: bool = False, frames: Optional[int] = None) -> ReceiveResult:
+    """:func:`chain_receive` on frames that still sit inside one contiguous capture ``cap`` (device tensor ``float32 [n, 2]``;
+    ``EqualizerTrainer.receive_capture``): as :meth:`RxReceiver.receive_capture`, one :class:`~dl_ofdm_amd.sync.CaptureSync`
+    launch cuts every frame at its estimated start -- linearly, up to ``sync = W > 0`` samples off ``first + f * stride`` -- and
+    writes it into the plan's ``x`` where ``chain_receive(x, sync=W)`` has its alignment launch.  ``frames`` (``None``: every
+    frame whose window ``[start - W, start + T + W)`` lies inside the capture) selects the resident plan."""
+    from .sync import CaptureSync
+    if not tr.fused_ok:
+        raise _lib.DccnError("the chain's receive path needs the fused equaliser step")
+    W = int(sync)
+    if W <= 0:
+        raise _lib.DccnError("chain_receive_capture needs sync = W > 0")
+    if not isinstance(cap, torch.Tensor) or cap.dim() != 2:
+        raise _lib.DccnError("chain_receive_capture takes a device tensor [n, 2]")
+    o = tr.ofdmobj
+    S, K, CP = int(tr.FLAGS.nsymbol), int(o.K), int(o.CP)
+    T = S * (K + CP)
+    step = T if stride is None else int(stride)
+    if frames is None:
+        room = int(cap.shape[0]) - int(first) - T - W
+        if room < 0 or step < T:
+            raise _lib.DccnError("chain_receive_capture: no frame at first = %d fits a capture of %d samples (stride %d)"
+                                 % (int(first), int(cap.shape[0]), step))
+        frames = room // step + 1
+    pl = tr.resident(int(frames))
+    syncs = pl.__dict__.setdefault("_capture_syncs", {})
+    key = (W, bool(cfo))
+    if key not in syncs:
+        syncs[key] = CaptureSync(S, K, CP, W, int(frames), tr.device, want_metric=False, cfo=bool(cfo))
+    cs = syncs[key]
+    _, offset = cs.run(cap, first, step, out=pl.x)
+    packed, llr, prob = pl.receive(want_llr, want_prob)
+    return ReceiveResult(packed, llr, prob, int(o.frame_size), int(tr.FLAGS.nbits), offset, cs.cfo)
 
 
 def group_receive(group, xs) -> list:

@@ -13,6 +13,10 @@ chosen lag estimates ``eps`` (in subcarrier spacings, unambiguous for ``|eps| < 
 leaves multiplied by ``exp(-2 pi i cfo n / K)``.  The frame is circular here too: the ``|offset|`` samples that wrap carry a phase
 step of ``2 pi eps T / K`` against their neighbours.
 
+:class:`CaptureSync` (``dccn_capture_sync``) lifts that limit where the frames still sit inside one contiguous capture: the same
+estimator over a window that extends ``W`` samples beyond the nominal frame on both sides, indexed linearly, and the frame cut at
+its estimated start -- the samples the alignment brings in are the frame's neighbours in the air.
+
 There is no CPU or PyTorch fallback: an unsupported shape or a tensor that is not on the GPU raises :class:`DccnError`.
 """
 from __future__ import annotations
@@ -110,4 +114,71 @@ class FrameSync:
     def offsets(self, x: torch.Tensor) -> torch.Tensor:
         """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``."""
         self._launch(self._device_frames(x), None)
+        return self.offset
+
+
+class CaptureSync:
+    """Frames cut from ONE CONTIGUOUS CAPTURE at their estimated starts (``dccn_capture_sync``): ``run(cap, first) -> (frames_out,
+    offset)``.
+
+    ``cap``: contiguous device tensor ``float32 [n, 2]``, what a front end hands over.  Frame ``f`` nominally starts at sample
+    ``first + f * stride`` (``stride=None``: ``T = S (K + CP)``, frames back to back).  The estimator is :class:`FrameSync`'s over
+    the window ``[start - W, start + T + W)``, indexed linearly: nothing wraps, so the samples the alignment brings in are the
+    frame's neighbours in the air, and with ``cfo=True`` they carry no phase step.  The caller leaves ``W`` samples of the capture
+    in front of the first frame and behind the last.  ``offset``, ``metric``, ``cfo`` and the output buffer are resident, as
+    :class:`FrameSync`'s are; ``out_kin`` as there.
+    """
+
+    def __init__(self, S: int, K: int, CP: int, W: int, frames: int, device="cuda", out_kin: Optional[int] = None,
+                 want_metric: bool = True, cfo: bool = False):
+        self.lib = _lib.load()
+        self.S, self.K, self.CP, self.W, self.frames = int(S), int(K), int(CP), int(W), int(frames)
+        self.T = self.S * (self.K + self.CP)
+        self.out_kin = self.K + self.CP if out_kin is None else int(out_kin)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise DccnError("CaptureSync needs a CUDA (ROCm) device; there is no CPU fallback")
+        if not self.lib.dccn_capture_sync_supported(self.S, self.K, self.CP, self.W):
+            raise DccnError("dccn_capture_sync_supported refused S=%d K=%d CP=%d W=%d (needs 1 <= W <= CP, 2 W + CP <= 64, an "
+                            "even frame length, four windows of T + 2 W samples within 64 KB)" % (self.S, self.K, self.CP, self.W))
+        if self.out_kin not in (self.K + self.CP, self.K) or self.frames <= 0:
+            raise DccnError("CaptureSync: out_kin must be K + CP or K and frames positive (got out_kin=%d, frames=%d)"
+                            % (self.out_kin, self.frames))
+        self.offset = torch.zeros(self.frames, dtype=torch.int32, device=self.device)
+        self.metric = (torch.zeros(self.frames, 2 * self.W + 1, dtype=torch.float32, device=self.device) if want_metric else None)
+        self.cfo = torch.zeros(self.frames, dtype=torch.float32, device=self.device) if cfo else None
+        self.out = None         # allocated by the first run() that is not given a destination
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _launch(self, cap, first, stride, out: Optional[torch.Tensor]) -> None:
+        if not isinstance(cap, torch.Tensor) or cap.device.type != "cuda":
+            raise DccnError("CaptureSync takes a device tensor; there is no CPU fallback")
+        if cap.dtype != torch.float32 or cap.dim() != 2 or cap.shape[1] != 2 or not cap.is_contiguous():
+            raise DccnError("CaptureSync: cap must be a contiguous float32 [n, 2] tensor, got %s %r" % (cap.dtype, tuple(cap.shape)))
+        stride = self.T if stride is None else int(stride)
+        p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        check(self.lib.dccn_capture_sync(cap.data_ptr(), int(cap.shape[0]), int(first), stride, self.frames, self.S, self.K,
+                                         self.CP, self.W, self.out_kin, p(out), self.offset.data_ptr(), p(self.cfo),
+                                         p(self.metric), self._stream()), "dccn_capture_sync")
+
+    def run(self, cap: torch.Tensor, first: int, stride: Optional[int] = None,
+            out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Estimate every frame's offset and write the frames, cut at their estimated starts (and with ``cfo=True`` derotated),
+        to ``out`` (``None``: this object's own buffer), on the current stream.  ``out`` must not overlap ``cap``."""
+        want = (self.frames, self.S, self.out_kin, 2)
+        if out is None:
+            if self.out is None:
+                self.out = torch.empty(*want, dtype=torch.float32, device=self.device)
+            out = self.out
+        elif (not isinstance(out, torch.Tensor) or out.device.type != "cuda" or out.dtype != torch.float32
+              or tuple(out.shape) != want or not out.is_contiguous()):
+            raise DccnError("CaptureSync.run: out must be a contiguous float32 %r device tensor" % (want,))
+        self._launch(cap, first, stride, out)
+        return out, self.offset
+
+    def offsets(self, cap: torch.Tensor, first: int, stride: Optional[int] = None) -> torch.Tensor:
+        """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``."""
+        self._launch(cap, first, stride, None)
         return self.offset

@@ -1048,6 +1048,29 @@ int dccn_frame_sync(const float* x, int frames, int S, int K, int CP, int W, int
  * chain group DCCN_ERR_UNSUPPORTED (the launch carries no chain table). */
 int dccn_frame_sync_cfo(const float* x, int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset,
                         float* cfo, float* metric, dccn_stream_t stream);
+/* The same estimator on frames that still sit inside ONE CONTIGUOUS CAPTURE cap [n_samples, 2] (what a front end hands over):
+ * frame f nominally starts at sample b_f = first + f*stride, nothing is circular, and the samples the alignment brings in are the
+ * frame's neighbours in the air.  With c = the capture indexed linearly, T = S*N:
+ *     p[n] = c[n] * conj(c[n+K])                 e[n] = (|c[n]|^2 + |c[n+K]|^2) / 2
+ *     Gamma_f(t) = sum_{s<S} sum_{n<CP} p[b_f + s*N + t + n]        Phi_f likewise        Lambda = |Gamma| - Phi
+ *     offset[f] = the smallest t in [-W, W] with the largest Lambda_f(t)
+ *     cfo[f] = -atan2(Im Gamma_f(offset), Re Gamma_f(offset)) / (2 pi)                    (only when cfo != NULL)
+ *     out[f][n] = c[b_f + offset[f] + n] * exp(-2 pi i cfo[f] n / K),  n = 0 .. T-1       (no factor when cfo == NULL: the capture's
+ *                                                                                          own bits)
+ * Frame f touches exactly the samples [b_f - W, b_f + T + W); nothing outside [0, n_samples) is read.  b_f - W may be odd (any
+ * first >= W, any stride >= T): a window that starts on an odd sample is read with 16-byte loads of the even-aligned pairs inside
+ * it and one 8-byte load at each end.  x_out, out_kin, offset, metric as dccn_frame_sync.  On a capture whose frames sit in slots
+ * [last W samples | frame | first W samples] (stride T + 2W, first W) the results are dccn_frame_sync's / dccn_frame_sync_cfo's bit
+ * for bit: the sums and their order are the same code.  One launch, no workspace, no atomics; two runs give the same bits.
+ * dccn_capture_sync_supported (host only): dccn_frame_sync_supported and four windows of T + 2W + 2 samples and their lag sums
+ * within 64 KB of LDS.
+ * Refused with DCCN_ERR_INVALID_ARG before anything is launched: an unsupported shape; frames <= 0; cap or offset NULL; cap, x_out
+ * or metric off a 16-byte boundary; out_kin neither K+CP nor K (nor K with S*K odd); stride < T; first < W;
+ * first + (frames-1)*stride + T + W > n_samples; x_out overlapping cap.  Inside a chain group DCCN_ERR_UNSUPPORTED. */
+int dccn_capture_sync_supported(int S, int K, int CP, int W);
+int dccn_capture_sync(const float* cap, long long n_samples, long long first, long long stride, int frames, int S, int K, int CP,
+                      int W, int out_kin, float* x_out, int32_t* offset, float* cfo /* nullable */, float* metric /* nullable */,
+                      dccn_stream_t stream);
 
 /* ==== host utility: CRC32C (Castagnoli), the checksum of TensorFlow's tensor-bundle checkpoints =========
  * (tf.train.Saver files the reference writes at dev/py/ofdmreceiver_np.py:271).

@@ -17,6 +17,9 @@
     python tools/rxbench.py --sync 3 --cfo [--out FILE]
         the same, plus (cfo) receive(x, sync=W, cfo=True): the launch that also estimates and removes the carrier-frequency
         offset (dccn_frame_sync_cfo) in the alignment launch's place, and that launch alone
+    python tools/rxbench.py --capture [--sync 3] [--out FILE]
+        receive_capture(cap, first, sync=W[, cfo=True]) on one contiguous capture (dccn_capture_sync) against receive(x, sync=W[,
+        cfo=True]) on the same frames cut in advance, and each launch alone; 1170 and 20 000 frames QPSK, same alternation
 
 Shapes: 1170 frames QPSK and 16-QAM, and one 20 000-frame QPSK sweep batch (N = 64).  Every shape runs in a child process of
 its own under a time limit; the parent never opens the GPU and stops at the first child that fails.  Times are medians over
@@ -164,6 +167,69 @@ def run_sync(frames, nbits, W, iters, repeats, cfo=False):
             "bytes_moved_by_copy_or_sync": moved, "build_id": _lib.load().dccn_build_id().decode()}
 
 
+def run_capture(frames, nbits, W, iters, repeats):
+    """receive_capture(cap, first, sync=W[, cfo=True]) on a contiguous capture against the path it replaces: receive(x, sync=W[,
+    cfo=True]) on the same frames cut in advance (both resident on the device), and each launch alone.  The frames carry a true
+    cyclic prefix, so every estimate is 0 and all four calls must return the same bits before anything is timed."""
+    import numpy as np
+    import torch
+    from dl_ofdm_amd import _lib
+    from dl_ofdm_amd.engine import RxDims, glorot_init
+    from dl_ofdm_amd.receive import RxReceiver
+    from dl_ofdm_amd.sync import CaptureSync, FrameSync
+    CP = KIN - F
+    T = S * KIN
+    dims = RxDims(S, KIN, F, D, nbits)
+    rc = RxReceiver(dims, frames, glorot_init(dims, 1), CP=CP)
+    rng = np.random.RandomState(0)
+    body = rng.randn(frames + 2, S, F, 2).astype(np.float32)
+    full = np.concatenate([body[:, :, F - CP:], body], axis=2)            # one frame in front of the cut ones and one behind
+    cap = torch.as_tensor(full.reshape(-1, 2), device="cuda")
+    x = torch.as_tensor(full[1:-1], device="cuda")
+    a = rc.receive(x).packed.clone()
+    for call in (lambda: rc.receive(x, sync=W), lambda: rc.receive(x, sync=W, cfo=True), lambda: rc.receive_capture(cap, T, sync=W),
+                 lambda: rc.receive_capture(cap, T, sync=W, cfo=True)):
+        r = call()
+        assert int(r.offset.abs().max()) == 0 and torch.equal(a, r.packed) and (r.cfo is None or float(r.cfo.abs().max()) == 0.0)
+    fs, fc = (FrameSync(S, F, CP, W, frames, "cuda", want_metric=False, cfo=c) for c in (False, True))
+    cs, cc = (CaptureSync(S, F, CP, W, frames, "cuda", want_metric=False, cfo=c) for c in (False, True))
+    variants = {"sync": lambda: rc.receive(x, sync=W), "capture": lambda: rc.receive_capture(cap, T, sync=W),
+                "cfo": lambda: rc.receive(x, sync=W, cfo=True), "capture_cfo": lambda: rc.receive_capture(cap, T, sync=W, cfo=True),
+                "sync_alone": lambda: fs.run(x), "capture_alone": lambda: cs.run(cap, T),
+                "cfo_alone": lambda: fc.run(x), "capture_cfo_alone": lambda: cc.run(cap, T)}
+    us, spread = timed(variants, iters, repeats)
+    return {"frames": frames, "nbits": nbits, "W": W, "iters": iters, "repeats": repeats, "us": us, "spread": spread,
+            "bytes_read_per_frame": {"sync": T * 8, "capture": (T + 2 * W) * 8}, "bytes_written_per_frame": T * 8,
+            "build_id": _lib.load().dccn_build_id().decode()}
+
+
+def main_capture(a):
+    """one child process per shape (1170 and 20 000 frames, QPSK), under a time limit; the parent never opens the GPU"""
+    res, W = [], a.sync or 3
+    for fr, nb in ((1170, 2), (20000, 2)):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--capture", "--one", "%d,%d" % (fr, nb),
+               "--sync", str(W), "--iters", str(a.iters if fr < 10000 else max(a.iters // 5, 10)), "--repeats", str(a.repeats)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        if r.returncode != 0:               # nothing more is started on the GPU after a failure
+            sys.stderr.write(r.stderr[-2000:])
+            print(json.dumps({"bench": "rxbench.capture", "failed": [fr, nb], "rc": r.returncode, "shapes": res}))
+            return 1
+        res.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    doc = {"bench": "rxbench.capture",
+           "variants": {"sync": "receive(x, sync=W) on frames cut in advance", "capture": "receive_capture(cap, first, sync=W)",
+                        "cfo": "receive(x, sync=W, cfo=True)", "capture_cfo": "receive_capture(cap, first, sync=W, cfo=True)",
+                        "sync_alone": "FrameSync.run(x)", "capture_alone": "CaptureSync.run(cap, first)",
+                        "cfo_alone": "FrameSync(cfo=True).run(x)", "capture_cfo_alone": "CaptureSync(cfo=True).run(cap, first)"},
+           "unit": "us per call (median over repeats of the mean of `iters` back-to-back calls); spread = (max - min) / median",
+           "shapes": res}
+    print(json.dumps(doc))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+    return 0
+
+
 def run_chains(mods, frames, iters, repeats):
     """G (equaliser -> frozen receiver) chains, one per link, `frames` frames each: (a) G solo receive calls back to back on one
     stream, (b) one grouped call -- same parameters, same frames, inputs resident; the two must agree before anything is timed"""
@@ -255,7 +321,15 @@ def main():
     ap.add_argument("--out", default=None, help="--chains / --sync: also write the result document to this file")
     ap.add_argument("--sync", type=int, default=0, help="W: time receive(x) against receive(x, sync=W) on every shape")
     ap.add_argument("--cfo", action="store_true", help="with --sync: also time receive(x, sync=W, cfo=True)")
+    ap.add_argument("--capture", action="store_true",
+                    help="time receive_capture against receive(x, sync=W[, cfo=True]) on the same frames cut in advance (W: --sync, default 3)")
     a = ap.parse_args()
+    if a.capture:
+        if a.one:
+            fr, nb = (int(v) for v in a.one.split(","))
+            print(json.dumps(run_capture(fr, nb, a.sync or 3, a.iters, a.repeats)))
+            return 0
+        return main_capture(a)
     if a.one_chains:
         print(json.dumps(run_chains([int(v) for v in a.one_chains.split(",")], a.frames, a.iters, a.repeats)))
         return 0

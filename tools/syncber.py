@@ -28,10 +28,19 @@ fp64), and the chain's BER is reported on AWGN / EPA / EVA / ETU for
 
 next to the median and the 95th percentile of |estimate - eps| over the frames.
 
+``--capture`` asks it of contiguous captures (the host model ``rayleigh_chan_lte.run_stream``: the frames' full convolutions
+overlap-added, one carrier phase running over the capture), EPA / EVA / ETU static, with eps = 0 and with one eps ~ U(-0.2, 0.2)
+per capture:
+
+    capture        receive_capture(cap, first, sync=W[, cfo=True]): frames cut linearly at their estimated starts
+    cut            receive(x, sync=W[, cfo=True]) on the same capture cut at the nominal starts (the circular frame)
+    baseline       receive(x) on the nominal cut of the capture before the carrier offset, no alignment
+
 No threshold: the numbers are the result.
 
     python tools/syncber.py --nbits 2 --out syncber_out [--load CKPT --rx_load CKPT] [--seeds 3] [--train_sync 3 [--rx_sync]]
     python tools/syncber.py --nbits 2 --cfo 0.05,0.2 --out syncber_out
+    python tools/syncber.py --nbits 2 --capture --snrs 5,29 --frames 2000 --out syncber_out
 """
 import argparse
 import copy
@@ -118,6 +127,78 @@ def cfo_rows(a, tr, hf, snrs, log):
                        cell(r["sync_cfo"]), r["cfo_abs_err"]["median"], r["cfo_abs_err"]["p95"]))
 
 
+CAPTURE_CHANNELS = ("EPA", "EVA", "ETU")
+
+
+def capture_rows(a, tr, hf, snrs, log):
+    """the --capture table: one row per (channel, SNR, eps = 0 | one eps ~ U(-0.2, 0.2) per capture).  Captures come from the host
+    model (radio.rayleigh_chan_lte.run_stream: every frame's full convolution overlap-added, so a frame's tails fall into its
+    neighbours; white noise over the whole capture; radio.apply_cfo_stream: one phase running over the capture)."""
+    import torch
+    from dl_ofdm_amd import ofdm, util
+    from dl_ofdm_amd.radio import apply_cfo_stream, rayleigh_chan_lte
+    n, W, lead, EPS = a.frames, a.W, 64, 0.2
+    rows = []
+    for ch in CAPTURE_CHANNELS:
+        fl = copy.deepcopy(hf)
+        fl.channel = ch
+        o = ofdm.ofdm_tx(fl)
+        S, K, CP = int(fl.nsymbol), int(o.K), int(o.CP)
+        T = S * (K + CP)
+        fading = rayleigh_chan_lte(fl, o.Fs)
+        for i, snr in enumerate(snrs):
+            for impaired in (False, True):
+                got = {"capture": [], "cut": [], "baseline": []}
+                hist, errs, eps_used = {}, [], []
+                for sd in range(a.seeds):
+                    np.random.seed(77 + 13 * i + 1009 * sd)
+                    bits = util.bit_source(fl.nbits, o.frame_size, n)
+                    iq, _, _ = o.ofdm_tx_frame_np(bits)
+                    c, _ = fading.run_stream(iq, lead)
+                    c = c.astype(np.complex128)
+                    c /= np.sqrt(np.mean(np.abs(c[lead:lead + n * T]) ** 2))          # unit mean power over the frames
+                    std = np.sqrt(0.5) * 10.0 ** (-snr / 20.0)
+                    c = c + std * (np.random.randn(c.shape[0]) + 1j * np.random.randn(c.shape[0]))
+                    eps = float(np.random.uniform(-EPS, EPS)) if impaired else 0.0
+                    eps_used.append(eps)
+                    clean = np.stack([c.real, c.imag], axis=-1).astype(np.float32)
+                    cap = torch.as_tensor(apply_cfo_stream(clean, eps, K) if impaired else clean, device=tr.device)
+                    lab = torch.as_tensor(bits.astype(np.int32), device=tr.device)
+                    ber = lambda res: float((res.bits().to(torch.int32) != lab).to(torch.float32).mean())   # noqa: E731
+                    res = tr.receive_capture(cap, lead, sync=W, cfo=impaired)
+                    got["capture"].append(ber(res))
+                    for v, cnt in zip(*[t.tolist() for t in torch.unique(res.offset, return_counts=True)]):
+                        hist[int(v)] = hist.get(int(v), 0) + int(cnt)
+                    if impaired:
+                        d = res.cfo.to(torch.float64) - eps
+                        errs.append((d - torch.round(d)).abs())
+                    x_nom = cap[lead:lead + n * T].view(n, S, K + CP, 2)              # the same capture cut at the nominal starts
+                    got["cut"].append(ber(tr.receive(x_nom, sync=W, cfo=impaired)))
+                    x_free = torch.as_tensor(clean[lead:lead + n * T], device=tr.device).view(n, S, K + CP, 2)
+                    got["baseline"].append(ber(tr.receive(x_free)))                   # no offset, no alignment
+                row = {"channel": ch, "snr_db": snr, "impaired": impaired, "eps": eps_used,
+                       "offset_share": {str(k): round(v / (n * a.seeds), 4) for k, v in sorted(hist.items())}}
+                if errs:
+                    e = torch.cat(errs)
+                    row["cfo_abs_err"] = {"median": float(e.median()), "p95": float(torch.quantile(e, 0.95))}
+                for k, v in got.items():
+                    row[k] = {"ber": float(np.mean(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    log["capture_rows"] = rows
+    with open(os.path.join(a.out, "syncber_capture_%dmod.json" % a.nbits), "w") as f:
+        json.dump(log, f, indent=1)
+        f.write("\n")
+    with open(os.path.join(a.out, "syncber_capture_%dmod.md" % a.nbits), "w") as f:
+        cell = lambda c: "%.3g (%.3g .. %.3g)" % (c["ber"], c["min"], c["max"])      # noqa: E731
+        f.write("| channel | SNR [dB] | eps | BER receive_capture | BER receive(sync=%d[, cfo]) on the nominal cut | BER baseline (no offset, "
+                "no alignment) | offsets (share of frames) |\n|---|---|---|---|---|---|---|\n" % a.W)
+        for r in rows:
+            f.write("| %s | %g | %s | %s | %s | %s | %s |\n"
+                    % (r["channel"], r["snr_db"], "U(-0.2, 0.2) per capture" if r["impaired"] else "0", cell(r["capture"]),
+                       cell(r["cut"]), cell(r["baseline"]), ", ".join("%s: %.1f %%" % (k, 100 * v) for k, v in r["offset_share"].items())))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nbits", type=int, default=2)
@@ -134,6 +215,9 @@ def main():
     ap.add_argument("--rx_sync", action="store_true", help="with --train_sync: the second chain's basic receiver trains on aligned frames too")
     ap.add_argument("--cfo", default=None, help="EPS[,EPS...]: per-frame carrier-frequency offsets ~ U(-EPS, EPS) subcarrier spacings "
                                                 "on the evaluation frames; reports the receive path with and without cfo=True")
+    ap.add_argument("--capture", action="store_true",
+                    help="contiguous captures from the host model (run_stream): receive_capture against receive(sync=W[, cfo=True]) on the "
+                         "same capture cut at the nominal starts, and the offset-free unaligned baseline; EPA / EVA / ETU at --snrs")
     ap.add_argument("--out", default="syncber_out")
     a = ap.parse_args()
     import torch
@@ -191,6 +275,9 @@ def main():
                                  "seconds": round(time.time() - t2, 1), "best_train_loss": best2["train_loss"],
                                  "best_epoch": best2["epoch"], "test_ber_at_best": best2["test_ber"]}
     print(json.dumps(log), flush=True)
+    if a.capture:
+        capture_rows(a, tr, hf, snrs, log)
+        return
     if a.cfo:
         cfo_rows(a, tr, hf, snrs, log)
         return
