@@ -228,6 +228,11 @@ SIGNATURES = {
     "dccn_frame_sync_cfo": (_i, [_vp] + [_i] * 6 + [_vp] * 5),
     "dccn_capture_sync_supported": (_i, [_i] * 4),
     "dccn_capture_sync": (_i, [_vp] + [c_longlong] * 3 + [_i] * 6 + [_vp] * 5),
+    "dccn_capture_sync_at": (_i, [_vp, c_longlong, _vp, c_longlong, c_longlong] + [_i] * 6 + [_vp] * 5),
+    # coarse acquisition inside a capture (the first frame's start, left on the device for dccn_capture_sync_at)
+    "dccn_capture_acquire_supported": (_i, [_i] * 5),
+    "dccn_capture_acquire_workspace_size": (_sz, [_i] * 5),
+    "dccn_capture_acquire": (_i, [_vp, c_longlong, c_longlong] + [_i] * 4 + [_vp, _i] + [_vp] * 5 + [_sz, _vp]),
     "dccn_rx_normalise": (_i, [POINTER(RxShape), POINTER(RxBuffers), _vp]),
     "dccn_rx_graph_create": (_i, [POINTER(RxShape), POINTER(RxBuffers), _i, AdamHParams, _vp, POINTER(c_void_p)]),
     "dccn_rx_graph_launch": (_i, [_vp, _vp]),

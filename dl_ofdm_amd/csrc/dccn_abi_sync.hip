@@ -1,6 +1,7 @@
 // libdccn.so -- per-frame timing alignment from the cyclic prefix (see abi_impl.h for how the library is cut into units)
 #include <math.h>
 
+#include "capture_acquire.h"
 #include "common.h"
 #include "frame_sync.h"
 
@@ -67,6 +68,54 @@ int capture_sync_launch(const CaptureSyncPlan& plan, dccn_stream_t stream) {
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
 }
+// dccn_capture_sync_at: the plan of dccn_capture_sync for the LAST start the kernel can clamp to (lo + T - 1: every earlier one
+// has its windows inside the capture too, down to lo, whose first window starts at lo - W >= 0)
+int capture_sync_at_plan(const float* cap, long long n_samples, const long long* first_dev, long long lo, long long stride,
+                         int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset, float* cfo,
+                         float* metric, CaptureSyncPlan* plan) {
+    if (!capture_sync_shape_ok(S, K, CP, W) || !first_dev || (reinterpret_cast<uintptr_t>(first_dev) & 7u) != 0) return DCCN_ERR_INVALID_ARG;
+    if (lo < W || n_samples <= 0 || lo > n_samples) return DCCN_ERR_INVALID_ARG;
+    const long long T = (long long)S * (K + CP);
+    return capture_sync_plan(cap, n_samples, lo + T - 1, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo, metric, plan);
+}
+
+template <bool CFO>
+int capture_sync_at_launch(const CaptureSyncPlan& plan, const long long* first_dev, long long lo, dccn_stream_t stream) {
+    DCCN_TRY(set_max_dynamic_smem((const void*)capture_sync_at_kernel<CFO>, plan.lds));
+    hipLaunchKernelGGL(capture_sync_at_kernel<CFO>, dim3(plan.blocks), dim3(kSyncWaves * kSyncLanes), plan.lds, (hipStream_t)stream,
+                       CaptureSyncAtArgs{plan.args, first_dev, lo});
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+// Everything dccn_capture_acquire decides, before its first launch.
+struct CaptureAcquirePlan {
+    AcqArgs args;
+    unsigned sum_blocks;
+    size_t lds;
+};
+
+int capture_acquire_plan(const float* cap, long long n_samples, long long lo, int J, int S, int K, int CP, const int* pilot_sc,
+                         int n_pilot, long long* first_out, float* cfo_out, float* sym_metric, float* phase_metric,
+                         void* workspace, size_t workspace_bytes, CaptureAcquirePlan* plan) {
+    if (!capture_acquire_shape_ok(S, K, CP, n_pilot, J)) return DCCN_ERR_INVALID_ARG;
+    if (!cap || !pilot_sc || !first_out || !cfo_out || !workspace) return DCCN_ERR_INVALID_ARG;
+    if (!aligned16(cap) || !aligned16(workspace) || (reinterpret_cast<uintptr_t>(first_out) & 7u) != 0) return DCCN_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(pilot_sc) & 3u) != 0 || (reinterpret_cast<uintptr_t>(cfo_out) & 3u) != 0 ||
+        (reinterpret_cast<uintptr_t>(sym_metric) & 3u) != 0 || (reinterpret_cast<uintptr_t>(phase_metric) & 3u) != 0)
+        return DCCN_ERR_INVALID_ARG;
+    // every read of both stages lies in [lo, lo + (J + 1) T); the documented bound leaves a frame to spare
+    const long long T = (long long)S * (K + CP);
+    if (lo < 0 || n_samples <= 0 || n_samples > (1LL << 58) || lo > n_samples || (J + 2) * T > n_samples - lo) return DCCN_ERR_INVALID_ARG;
+    const AcqWorkspace w = capture_acquire_layout(S, K, CP, J);
+    if (workspace_bytes < w.total) return DCCN_ERR_WORKSPACE;
+    char* const base = static_cast<char*>(workspace);
+    plan->args = AcqArgs{cap, lo, pilot_sc, reinterpret_cast<float4*>(base + w.pe), reinterpret_cast<float*>(base + w.partial),
+                         reinterpret_cast<int*>(base + w.rhat), first_out, cfo_out, sym_metric, phase_metric, S, K, CP, J, n_pilot};
+    plan->sum_blocks = (unsigned)ceil_div(K + 2 * CP - 1, kAcqSumThreads);
+    plan->lds = capture_acquire_lds(S, K, CP, n_pilot);
+    return DCCN_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -105,6 +154,40 @@ int dccn_capture_sync(const float* cap, long long n_samples, long long first, lo
     DCCN_TRY(capture_sync_plan(cap, n_samples, first, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo, metric, &plan));
     DCCN_NO_CHAINS();
     return cfo ? capture_sync_launch<true>(plan, stream) : capture_sync_launch<false>(plan, stream);
+}
+
+int dccn_capture_sync_at(const float* cap, long long n_samples, const long long* first_dev, long long lo, long long stride,
+                         int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset, float* cfo,
+                         float* metric, dccn_stream_t stream) {
+    CaptureSyncPlan plan;
+    DCCN_TRY(capture_sync_at_plan(cap, n_samples, first_dev, lo, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo, metric,
+                                  &plan));
+    DCCN_NO_CHAINS();
+    return cfo ? capture_sync_at_launch<true>(plan, first_dev, lo, stream) : capture_sync_at_launch<false>(plan, first_dev, lo, stream);
+}
+
+int dccn_capture_acquire_supported(int S, int K, int CP, int n_pilot, int J) {
+    return capture_acquire_shape_ok(S, K, CP, n_pilot, J) ? 1 : 0;
+}
+
+size_t dccn_capture_acquire_workspace_size(int S, int K, int CP, int n_pilot, int J) {
+    return capture_acquire_shape_ok(S, K, CP, n_pilot, J) ? capture_acquire_layout(S, K, CP, J).total : 0;
+}
+
+int dccn_capture_acquire(const float* cap, long long n_samples, long long lo, int J, int S, int K, int CP, const int* pilot_sc,
+                         int n_pilot, long long* first_out, float* cfo_out, float* sym_metric, float* phase_metric,
+                         void* workspace, size_t workspace_bytes, dccn_stream_t stream) {
+    CaptureAcquirePlan plan;
+    DCCN_TRY(capture_acquire_plan(cap, n_samples, lo, J, S, K, CP, pilot_sc, n_pilot, first_out, cfo_out, sym_metric, phase_metric,
+                                  workspace, workspace_bytes, &plan));
+    DCCN_NO_CHAINS();
+    hipLaunchKernelGGL(acq_symbol_sums_kernel, dim3(plan.sum_blocks), dim3(kAcqSumThreads), 0, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(acq_phase_kernel, dim3((unsigned)S, (unsigned)J), dim3(kAcqThreads), plan.lds, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(acq_decide_kernel, dim3(1), dim3(kAcqMaxS), 0, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
 }
 
 }  // extern "C"

@@ -257,8 +257,9 @@ struct CaptureSyncArgs {
     int crop;
 };
 
+// The launch, stated once; `first` is where frame 0 nominally starts (the argument, or what dccn_capture_sync_at read).
 template <bool CFO>
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_kernel(const CaptureSyncArgs a) {
+__device__ __forceinline__ void capture_sync_body(const CaptureSyncArgs& a, const long long first) {
     extern __shared__ float4 sync_lds[];
     const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
     const int T = a.S * (a.K + a.CP), W = a.W;
@@ -267,7 +268,7 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_k
     const size_t per = capture_sync_lds_per_frame(T, W) / 16;
     float4* const region = sync_lds + (size_t)wave * per;
     float4* const pe = region + (per - kSyncLanes);
-    const long long start = live ? a.first + f * a.stride - W : 0;          // the window's first sample
+    const long long start = live ? first + f * a.stride - W : 0;            // the window's first sample
     const int sh = (int)(start & 1);
     const float2* const y = reinterpret_cast<const float2*>(region) + sh;    // slot 0 = sample start
 
@@ -297,6 +298,25 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_k
                                     (live && a.metric) ? a.metric + (size_t)f * (2 * W + 1) : nullptr, CFO ? &gamma : nullptr);
     if (!live) return;
     sync_finish<CFO>(at, y, f, theta, gamma, lane, a.x_out, a.offset, a.cfo, a.S, a.K, a.CP, a.crop);
+}
+
+template <bool CFO>
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_kernel(const CaptureSyncArgs a) {
+    capture_sync_body<CFO>(a, a.first);
+}
+
+// dccn_capture_sync_at: the same launch with `first` read from device memory (what dccn_capture_acquire left there) and kept
+// inside [lo, lo + T - 1], the range the host checked every window against: a wrong value cannot read outside the capture.
+struct CaptureSyncAtArgs {
+    CaptureSyncArgs s;          // (s.first is not read)
+    const long long* first_dev; // [1]
+    long long lo;
+};
+template <bool CFO>
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_at_kernel(const CaptureSyncAtArgs a) {
+    const long long hi = a.lo + (long long)a.s.S * (a.s.K + a.s.CP) - 1;
+    const long long got = a.first_dev[0];
+    capture_sync_body<CFO>(a.s, got < a.lo ? a.lo : (got > hi ? hi : got));
 }
 
 }  // namespace dccn

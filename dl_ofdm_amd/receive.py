@@ -62,10 +62,13 @@ class ReceiveResult:
     """Device tensors of one receive call (they are the receiver's resident buffers: the next call overwrites them)."""
 
     def __init__(self, packed: torch.Tensor, llr: Optional[torch.Tensor], prob: Optional[torch.Tensor], D: int, nbits: int,
-                 offset: Optional[torch.Tensor] = None, cfo: Optional[torch.Tensor] = None):
+                 offset: Optional[torch.Tensor] = None, cfo: Optional[torch.Tensor] = None,
+                 first: Optional[torch.Tensor] = None, acquired_cfo: Optional[torch.Tensor] = None):
         self.packed, self.llr, self.prob, self.D, self.nbits = packed, llr, prob, int(D), int(nbits)
         self.offset = offset        # int32 [frames]: the timing offsets of a call with sync > 0 (None otherwise)
         self.cfo = cfo              # float32 [frames]: the carrier-frequency offsets of a call with cfo=True (None otherwise)
+        self.first = first          # int64 [1]: frame 0's start as receive_capture(first=None) acquired it (None otherwise)
+        self.acquired_cfo = acquired_cfo    # float32 [1]: the carrier-frequency offset acquisition estimated on the way
 
     def bits(self) -> torch.Tensor:
         """``uint8 [frames, D, nbits]``, unpacked on the device."""
@@ -85,14 +88,16 @@ class RxReceiver:
 
     def __init__(self, dims: RxDims, batch: int, params: Optional[Dict[str, np.ndarray]] = None, device="cuda",
                  want_llr: bool = False, want_prob: bool = False, seed: int = 1, CP: Optional[int] = None,
-                 K: Optional[int] = None):
+                 K: Optional[int] = None, pilot_sc=None):
         """``CP``: the frames' cyclic-prefix length, for ``receive(x, sync=W)`` of a receiver that takes whole symbols
         (``dims.kin == K + CP``: K cannot be read off the shape).  A ``cp=False`` receiver (``dims.kin == K``) finds it from
         the frames it is given.  ``receive_capture`` has no frame shape to look at: it needs ``CP``, and takes ``K`` as
-        ``dims.kin - CP`` (whole symbols) unless ``K`` says otherwise (``K=dims.kin``: a ``cp=False`` receiver)."""
+        ``dims.kin - CP`` (whole symbols) unless ``K`` says otherwise (``K=dims.kin``: a ``cp=False`` receiver).
+        ``pilot_sc``: the frame's pilot cells (``ofdm_tx.pilotSc``), for ``receive_capture(first=None, acquire=J)``."""
         self.lib = _lib.load()
         self.CP = None if CP is None else int(CP)
         self.K = None if K is None else int(K)
+        self.pilot_sc = None if pilot_sc is None else np.asarray(pilot_sc, dtype=np.int32).reshape(-1)
         self._syncs: Dict[tuple, object] = {}
         self.dims, self.batch = dims, int(batch)
         self.device = torch.device(device)
@@ -179,7 +184,8 @@ class RxReceiver:
         check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
         return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, est)
 
-    def receive_capture(self, cap, first: int, stride: Optional[int] = None, sync: int = 3, cfo: bool = False) -> ReceiveResult:
+    def receive_capture(self, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False, acquire: int = 0,
+                        lo: int = 0) -> ReceiveResult:
         """One receive step on ``batch`` frames that still sit inside one contiguous capture ``cap`` (device tensor ``float32
         [n, 2]``): frame ``f`` nominally starts at sample ``first + f * stride`` (``None``: frames back to back) and may sit up to
         ``sync = W > 0`` samples off.  One launch (:class:`~dl_ofdm_amd.sync.CaptureSync`) stands where ``receive(x, sync=W)``
@@ -187,7 +193,14 @@ class RxReceiver:
         capture's, not the frame's other end -- and writes it straight into ``self.x`` (only the K samples behind each prefix
         when ``dims.kin == K``).  ``cfo=True`` takes each frame's carrier-frequency offset out on the way.  Needs
         ``RxReceiver(..., CP=...)``, and ``K=dims.kin`` as well for a ``cp=False`` receiver: a capture has no shape to read them
-        off.  ``result.offset`` / ``result.cfo``."""
+        off.  ``result.offset`` / ``result.cfo``.
+
+        ``first=None, acquire=J, lo=...``: nobody knows where frame 0 starts.  Acquisition (:class:`~dl_ofdm_amd.sync.
+        CaptureAcquire`, ``J`` frames, needs ``RxReceiver(..., pilot_sc=...)``) finds the frame start inside ``[lo, lo + T)`` and
+        leaves it on the device, the cut reads it there (``dccn_capture_sync_at``), and the receive step follows: one launch
+        sequence, no host round trip.  ``lo >= sync``, and the capture must hold the ``batch`` frames from ``lo + T - 1`` on.
+        ``first`` may also be such a device ``int64`` tensor of one element itself (with ``lo``).  ``result.first`` /
+        ``result.acquired_cfo``."""
         from .sync import CaptureSync
         W = int(sync)
         if W <= 0:
@@ -203,9 +216,31 @@ class RxReceiver:
             self._syncs[key] = CaptureSync(self.dims.S, K, self.CP, W, self.batch, self.device, out_kin=kin, want_metric=False,
                                            cfo=bool(cfo))
         cs = self._syncs[key]
-        _, offset = cs.run(cap, first, stride, out=self.x)
+        first, est0 = _acquired_first(self._syncs, first, acquire, cap, lo, self.dims.S, K, self.CP, self.pilot_sc, self.device)
+        _, offset = cs.run(cap, first, stride, out=self.x, lo=lo)             # (lo matters to a device `first` only)
         check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
-        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, cs.cfo)
+        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, cs.cfo,
+                             first if isinstance(first, torch.Tensor) else None, est0)
+
+
+def _acquired_first(stages: dict, first, acquire: int, cap, lo: int, S: int, K: int, CP: int, pilot_sc, device):
+    """``first`` as the cut takes it, and the acquisition's carrier-frequency offset: an integer or a device tensor passes
+    through; ``None`` runs :class:`~dl_ofdm_amd.sync.CaptureAcquire` over ``acquire`` frames (kept in ``stages``)."""
+    from .sync import CaptureAcquire
+    if first is not None:
+        if acquire:
+            raise _lib.DccnError("receive_capture: give `first` or `acquire`, not both")
+        return first, None
+    J = int(acquire)
+    if J <= 0:
+        raise _lib.DccnError("receive_capture(first=None) needs acquire = J > 0, the number of frames acquisition may use")
+    if pilot_sc is None:
+        raise _lib.DccnError("receive_capture(first=None) needs the frame's pilot cells (RxReceiver(..., pilot_sc=...))")
+    key = ("acquire", J)
+    if key not in stages:
+        stages[key] = CaptureAcquire(S, K, CP, pilot_sc, J, device)
+    acq = stages[key]
+    return acq.run(cap, lo), acq.cfo
 
 
 def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: int = 0, cfo: bool = False) -> ReceiveResult:
@@ -238,13 +273,19 @@ def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: 
     return ReceiveResult(packed, llr, prob, int(tr.ofdmobj.frame_size), int(tr.FLAGS.nbits), offset, est)
 
 
-def chain_receive_capture(tr, cap, first: int, stride: Optional[int] = None, sync: int = 3, cfo: bool = False,
-                          want_llr: bool = False, want_prob: bool = False, frames: Optional[int] = None) -> ReceiveResult:
+def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False,
+                          want_llr: bool = False, want_prob: bool = False, frames: Optional[int] = None, acquire: int = 0,
+                          lo: int = 0) -> ReceiveResult:
     """:func:`chain_receive` on frames that still sit inside one contiguous capture ``cap`` (device tensor ``float32 [n, 2]``;
     ``EqualizerTrainer.receive_capture``): as :meth:`RxReceiver.receive_capture`, one :class:`~dl_ofdm_amd.sync.CaptureSync`
     launch cuts every frame at its estimated start -- linearly, up to ``sync = W > 0`` samples off ``first + f * stride`` -- and
     writes it into the plan's ``x`` where ``chain_receive(x, sync=W)`` has its alignment launch.  ``frames`` (``None``: every
-    frame whose window ``[start - W, start + T + W)`` lies inside the capture) selects the resident plan."""
+    frame whose window ``[start - W, start + T + W)`` lies inside the capture) selects the resident plan.
+
+    ``first=None, acquire=J, lo=...``: as :meth:`RxReceiver.receive_capture` -- acquisition over ``J`` frames (the pilot cells are
+    ``tr.ofdmobj.pilotSc``) leaves the frame start inside ``[lo, lo + T)`` on the device and the cut reads it there.  The host
+    then does not know the start: ``frames=None`` counts the frames that fit from the LAST start of that range on, and with a
+    device tensor ``first`` (and ``lo``) ``frames`` must be given."""
     from .sync import CaptureSync
     if not tr.fused_ok:
         raise _lib.DccnError("the chain's receive path needs the fused equaliser step")
@@ -257,11 +298,15 @@ def chain_receive_capture(tr, cap, first: int, stride: Optional[int] = None, syn
     S, K, CP = int(tr.FLAGS.nsymbol), int(o.K), int(o.CP)
     T = S * (K + CP)
     step = T if stride is None else int(stride)
+    on_device = first is None or isinstance(first, torch.Tensor)
     if frames is None:
-        room = int(cap.shape[0]) - int(first) - T - W
+        if isinstance(first, torch.Tensor):
+            raise _lib.DccnError("chain_receive_capture: a device tensor `first` needs frames=...")
+        latest = int(lo) + T - 1 if on_device else int(first)
+        room = int(cap.shape[0]) - latest - T - W
         if room < 0 or step < T:
             raise _lib.DccnError("chain_receive_capture: no frame at first = %d fits a capture of %d samples (stride %d)"
-                                 % (int(first), int(cap.shape[0]), step))
+                                 % (latest, int(cap.shape[0]), step))
         frames = room // step + 1
     pl = tr.resident(int(frames))
     syncs = pl.__dict__.setdefault("_capture_syncs", {})
@@ -269,9 +314,12 @@ def chain_receive_capture(tr, cap, first: int, stride: Optional[int] = None, syn
     if key not in syncs:
         syncs[key] = CaptureSync(S, K, CP, W, int(frames), tr.device, want_metric=False, cfo=bool(cfo))
     cs = syncs[key]
-    _, offset = cs.run(cap, first, step, out=pl.x)
+    first, est0 = _acquired_first(tr.__dict__.setdefault("_capture_acquires", {}), first, acquire, cap, lo, S, K, CP, o.pilotSc,
+                                  tr.device)
+    _, offset = cs.run(cap, first, step, out=pl.x, lo=lo)                     # (lo matters to a device `first` only)
     packed, llr, prob = pl.receive(want_llr, want_prob)
-    return ReceiveResult(packed, llr, prob, int(o.frame_size), int(tr.FLAGS.nbits), offset, cs.cfo)
+    return ReceiveResult(packed, llr, prob, int(o.frame_size), int(tr.FLAGS.nbits), offset, cs.cfo,
+                         first if on_device else None, est0)
 
 
 def group_receive(group, xs) -> list:

@@ -15,7 +15,9 @@ step of ``2 pi eps T / K`` against their neighbours.
 
 :class:`CaptureSync` (``dccn_capture_sync``) lifts that limit where the frames still sit inside one contiguous capture: the same
 estimator over a window that extends ``W`` samples beyond the nominal frame on both sides, indexed linearly, and the frame cut at
-its estimated start -- the samples the alignment brings in are the frame's neighbours in the air.
+its estimated start -- the samples the alignment brings in are the frame's neighbours in the air.  :class:`CaptureAcquire`
+(``dccn_capture_acquire``) finds the ``first`` that stage needs -- anywhere in a frame period, not within ``W`` -- and leaves it on
+the device, where ``CaptureSync.run(cap, first_tensor, lo=...)`` reads it.
 
 There is no CPU or PyTorch fallback: an unsupported shape or a tensor that is not on the GPU raises :class:`DccnError`.
 """
@@ -152,21 +154,34 @@ class CaptureSync:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _launch(self, cap, first, stride, out: Optional[torch.Tensor]) -> None:
+    def _launch(self, cap, first, stride, out: Optional[torch.Tensor], lo: Optional[int] = None) -> None:
         if not isinstance(cap, torch.Tensor) or cap.device.type != "cuda":
             raise DccnError("CaptureSync takes a device tensor; there is no CPU fallback")
         if cap.dtype != torch.float32 or cap.dim() != 2 or cap.shape[1] != 2 or not cap.is_contiguous():
             raise DccnError("CaptureSync: cap must be a contiguous float32 [n, 2] tensor, got %s %r" % (cap.dtype, tuple(cap.shape)))
         stride = self.T if stride is None else int(stride)
         p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
-        check(self.lib.dccn_capture_sync(cap.data_ptr(), int(cap.shape[0]), int(first), stride, self.frames, self.S, self.K,
-                                         self.CP, self.W, self.out_kin, p(out), self.offset.data_ptr(), p(self.cfo),
-                                         p(self.metric), self._stream()), "dccn_capture_sync")
+        tail = (stride, self.frames, self.S, self.K, self.CP, self.W, self.out_kin, p(out), self.offset.data_ptr(), p(self.cfo),
+                p(self.metric), self._stream())
+        if isinstance(first, torch.Tensor):
+            # the start is on the device (CaptureAcquire left it there): nothing is read back
+            if lo is None:
+                raise DccnError("CaptureSync: a device tensor `first` needs lo=..., the origin of the range [lo, lo + T) it lies in")
+            if first.device != cap.device or first.dtype != torch.int64 or first.numel() != 1 or not first.is_contiguous():
+                raise DccnError("CaptureSync: a device `first` must be an int64 tensor of one element on the capture's device")
+            check(self.lib.dccn_capture_sync_at(cap.data_ptr(), int(cap.shape[0]), first.data_ptr(), int(lo), *tail),
+                  "dccn_capture_sync_at")
+        else:
+            check(self.lib.dccn_capture_sync(cap.data_ptr(), int(cap.shape[0]), int(first), *tail), "dccn_capture_sync")
 
-    def run(self, cap: torch.Tensor, first: int, stride: Optional[int] = None,
-            out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def run(self, cap: torch.Tensor, first, stride: Optional[int] = None, out: Optional[torch.Tensor] = None,
+            lo: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Estimate every frame's offset and write the frames, cut at their estimated starts (and with ``cfo=True`` derotated),
-        to ``out`` (``None``: this object's own buffer), on the current stream.  ``out`` must not overlap ``cap``."""
+        to ``out`` (``None``: this object's own buffer), on the current stream.  ``out`` must not overlap ``cap``.
+
+        ``first``: an integer, or a device ``int64`` tensor of one element together with ``lo`` (``dccn_capture_sync_at``: the
+        launch reads the start from device memory and keeps it inside ``[lo, lo + T - 1]``; every window must lie inside the
+        capture for every start in that range)."""
         want = (self.frames, self.S, self.out_kin, 2)
         if out is None:
             if self.out is None:
@@ -175,10 +190,58 @@ class CaptureSync:
         elif (not isinstance(out, torch.Tensor) or out.device.type != "cuda" or out.dtype != torch.float32
               or tuple(out.shape) != want or not out.is_contiguous()):
             raise DccnError("CaptureSync.run: out must be a contiguous float32 %r device tensor" % (want,))
-        self._launch(cap, first, stride, out)
+        self._launch(cap, first, stride, out, lo)
         return out, self.offset
 
-    def offsets(self, cap: torch.Tensor, first: int, stride: Optional[int] = None) -> torch.Tensor:
-        """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``."""
-        self._launch(cap, first, stride, None)
+    def offsets(self, cap: torch.Tensor, first, stride: Optional[int] = None, lo: Optional[int] = None) -> torch.Tensor:
+        """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``.  ``first`` / ``lo`` as :meth:`run`."""
+        self._launch(cap, first, stride, None, lo)
         return self.offset
+
+
+class CaptureAcquire:
+    """Coarse acquisition inside a contiguous capture (``dccn_capture_acquire``): ``run(cap, lo) -> first``, the sample in
+    ``[lo, lo + T)`` at which a frame starts, as a device ``int64`` tensor of one element -- what :meth:`CaptureSync.run` takes
+    as ``first`` together with the same ``lo``.  Nothing is read back and nothing synchronises.
+
+    Stage A finds the symbol timing (any lag of a symbol period) and the carrier offset from the cyclic prefixes of ``J * S``
+    symbols; stage B finds which of the ``S`` symbol positions is the frame's first from the pilot symbols (``pilot_sc``:
+    ``ofdm_tx.pilotSc``, the pilot cells as sorted flat ``symbol * K + carrier`` indices).  The ``J`` frames are assumed back to
+    back (stride ``T``), and ``lo + (J + 2) T`` samples of the capture must exist.  ``first``, ``cfo`` (``float32 [1]``,
+    subcarrier spacings), ``sym_metric`` (``float32 [K + CP]``) and ``phase_metric`` (``float32 [S]``) are resident: the next
+    ``run`` overwrites them.  ``J = 1`` with BPSK data can tie exactly; a batch's worth of frames (``J = 16``) is the intended
+    setting (README)."""
+
+    def __init__(self, S: int, K: int, CP: int, pilot_sc, J: int, device="cuda"):
+        self.lib = _lib.load()
+        self.S, self.K, self.CP, self.J = int(S), int(K), int(CP), int(J)
+        self.T = self.S * (self.K + self.CP)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise DccnError("CaptureAcquire needs a CUDA (ROCm) device; there is no CPU fallback")
+        sc = torch.as_tensor(pilot_sc).reshape(-1).to(torch.int32)
+        self.n_pilot = int(sc.numel())
+        if not self.lib.dccn_capture_acquire_supported(self.S, self.K, self.CP, self.n_pilot, self.J):
+            raise DccnError("dccn_capture_acquire_supported refused S=%d K=%d CP=%d n_pilot=%d J=%d (needs S <= 64, CP <= K, "
+                            "K + CP <= 1024, 2 <= n_pilot <= 256, 1 <= J <= 256)" % (self.S, self.K, self.CP, self.n_pilot, self.J))
+        self.pilot_sc = sc.to(self.device).contiguous()
+        self.first = torch.zeros(1, dtype=torch.int64, device=self.device)
+        self.cfo = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.sym_metric = torch.zeros(self.K + self.CP, dtype=torch.float32, device=self.device)
+        self.phase_metric = torch.zeros(self.S, dtype=torch.float32, device=self.device)
+        nws = int(self.lib.dccn_capture_acquire_workspace_size(self.S, self.K, self.CP, self.n_pilot, self.J))
+        self.ws = torch.empty(nws, dtype=torch.uint8, device=self.device)
+
+    def run(self, cap: torch.Tensor, lo: int = 0) -> torch.Tensor:
+        """Three launches on the current stream; returns ``self.first``."""
+        if not isinstance(cap, torch.Tensor) or cap.device.type != "cuda":
+            raise DccnError("CaptureAcquire takes a device tensor; there is no CPU fallback")
+        if cap.dtype != torch.float32 or cap.dim() != 2 or cap.shape[1] != 2 or not cap.is_contiguous():
+            raise DccnError("CaptureAcquire: cap must be a contiguous float32 [n, 2] tensor, got %s %r"
+                            % (cap.dtype, tuple(cap.shape)))
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        check(self.lib.dccn_capture_acquire(cap.data_ptr(), int(cap.shape[0]), int(lo), self.J, self.S, self.K, self.CP,
+                                            self.pilot_sc.data_ptr(), self.n_pilot, self.first.data_ptr(), self.cfo.data_ptr(),
+                                            self.sym_metric.data_ptr(), self.phase_metric.data_ptr(), self.ws.data_ptr(),
+                                            int(self.ws.numel()), stream), "dccn_capture_acquire")
+        return self.first

@@ -1071,6 +1071,53 @@ int dccn_capture_sync_supported(int S, int K, int CP, int W);
 int dccn_capture_sync(const float* cap, long long n_samples, long long first, long long stride, int frames, int S, int K, int CP,
                       int W, int out_kin, float* x_out, int32_t* offset, float* cfo /* nullable */, float* metric /* nullable */,
                       dccn_stream_t stream);
+/* dccn_capture_sync with `first` read from DEVICE memory (first_dev, int64[1]: what dccn_capture_acquire left there), so that
+ * acquisition, cut and receive run as one launch sequence without a host round trip.  The kernel clamps the value it reads into
+ * [lo, lo + T - 1]; everything else -- the sums, their order, the stores -- is dccn_capture_sync's own code (the kernel is a
+ * second instantiation of the same body, dccn_capture_sync's instantiation is untouched): with first_dev holding `first` the
+ * two calls write the same bits.
+ * Refused with DCCN_ERR_INVALID_ARG before anything is launched wherever dccn_capture_sync refuses first = lo + T - 1, and for
+ * first_dev NULL or off an 8-byte boundary, lo < W, lo + T - 1 + (frames-1)*stride + T + W > n_samples: every window lies inside
+ * the capture for EVERY value the kernel can clamp to, so a wrong first_dev cannot read outside it.  Inside a chain group
+ * DCCN_ERR_UNSUPPORTED. */
+int dccn_capture_sync_at(const float* cap, long long n_samples, const long long* first_dev, long long lo, long long stride,
+                         int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset,
+                         float* cfo /* nullable */, float* metric /* nullable */, dccn_stream_t stream);
+
+/* ==== coarse acquisition inside a contiguous capture ============================
+ * dccn_capture_sync needs `first` to within W samples.  This stage finds it: the sample in [lo, lo + T) at which a frame starts,
+ * from J >= 1 frames that follow back to back (stride T).  c = the capture indexed linearly, N = K+CP, T = S*N, p and e as above.
+ * Stage A, symbol timing and carrier offset over a whole symbol period (the estimator above with J*S symbols, every lag of a period):
+ *     P[m] = sum_{u<J*S} p[lo + m + u*N]   (u ascending)        E[m] likewise over e                m in [0, N+CP-1)
+ *     Gamma(r) = sum_{n<CP} P[r + n]       (n ascending)        Phi(r) likewise over E              Lambda(r) = |Gamma(r)| - Phi(r)
+ *     r^ = the smallest r in [0, N) with the largest Lambda(r)          eps^ = -atan2(Im Gamma(r^), Re Gamma(r^)) / (2 pi)
+ * Stage B, the frame phase from the pilot symbols.  pilot_sc int32[n_pilot] (device): the frame's pilot cells as flat
+ * symbol*K + carrier indices, sorted (the carrier is the DFT bin, the generator's numbering); the pilot symbols are the symbols
+ * that hold at least two pilot cells, k_0 < k_1 < ... the pilot carriers of pilot symbol s.  For q in [0, S):
+ *     Y_{j,q,s}[k] = sum_{n<K} c[lo + r^ + (q+s)*N + j*T + CP + n] * exp(-2 pi i (k + eps^) n / K)                   (n ascending)
+ *     D_j(q) = sum_{pilot symbols s, ascending} | sum_{i ascending} Y_{j,q,s}[k_i] * conj(Y_{j,q,s}[k_{i+1}]) |
+ *     D(q) = sum_{j<J, ascending} D_j(q)        q^ = the smallest q with the largest D(q)        first = lo + r^ + q^*N  in [lo, lo+T)
+ * (equal pilot values on adjacent pilot carriers multiply coherently; the product is invariant to a residual timing offset
+ * and to the symbol's common phase).  The twiddle phase is taken in turns, ((k n mod K) + eps^ n) / K with k n mod K an exact
+ * integer.  Frames are assumed back to back at stride T during acquisition.  J = 1 with BPSK data can tie exactly (a data symbol
+ * whose adjacent cells happen to agree); a batch's worth of frames (J = 16) is the intended setting.
+ * first_out int64[1], cfo_out float32[1] (eps^, subcarrier spacings), sym_metric [N] nullable = Lambda(0 .. N-1), phase_metric
+ * [S] nullable = D(0 .. S-1): all device memory, written on the stream; nothing is read back.  Three launches (P, E per lag;
+ * Lambda, r^, eps^ and D_j(q), one block per (q, j); D, q^ and first), no host synchronisation, no atomics, every sum in the
+ * order stated: two runs give the same bits.  Every read lies in [lo, lo + (J+1)*T).  pilot_sc entries outside [0, S*K) are
+ * ignored; whatever the array holds, nothing outside the capture is read.
+ * dccn_capture_acquire_supported (host only): 1 <= S <= 64, K >= 2, 1 <= CP <= K, K+CP <= 1024 (a block's LDS holds P, E of
+ * N+CP-1 lags and one symbol), 2 <= n_pilot <= 256 (one thread per pilot carrier of a symbol), 1 <= J <= 256.
+ * dccn_capture_acquire_workspace_size: bytes of device workspace (P, E, D_j(q), r^), 0 for an unsupported shape.
+ * Refused with DCCN_ERR_INVALID_ARG before anything is launched: an unsupported shape; cap, pilot_sc, first_out, cfo_out or
+ * workspace NULL; cap or workspace off a 16-byte boundary, first_out off an 8-byte one, pilot_sc, cfo_out, sym_metric or
+ * phase_metric off a 4-byte one; lo < 0; lo + (J+2)*T > n_samples (conservative: it covers every read of both stages).  A
+ * workspace smaller than the size query's answer: DCCN_ERR_WORKSPACE.  Inside a chain group DCCN_ERR_UNSUPPORTED. */
+int dccn_capture_acquire_supported(int S, int K, int CP, int n_pilot, int J);
+size_t dccn_capture_acquire_workspace_size(int S, int K, int CP, int n_pilot, int J);
+int dccn_capture_acquire(const float* cap, long long n_samples, long long lo, int J, int S, int K, int CP, const int* pilot_sc,
+                         int n_pilot, long long* first_out, float* cfo_out, float* sym_metric /* nullable */,
+                         float* phase_metric /* nullable */, void* workspace, size_t workspace_bytes, dccn_stream_t stream);
 
 /* ==== host utility: CRC32C (Castagnoli), the checksum of TensorFlow's tensor-bundle checkpoints =========
  * (tf.train.Saver files the reference writes at dev/py/ofdmreceiver_np.py:271).

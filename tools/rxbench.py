@@ -20,6 +20,10 @@
     python tools/rxbench.py --capture [--sync 3] [--out FILE]
         receive_capture(cap, first, sync=W[, cfo=True]) on one contiguous capture (dccn_capture_sync) against receive(x, sync=W[,
         cfo=True]) on the same frames cut in advance, and each launch alone; 1170 and 20 000 frames QPSK, same alternation
+    python tools/rxbench.py --acquire [--sync 3] [--out FILE]
+        receive_capture(cap, first=None, acquire=J, lo=...) (dccn_capture_acquire + dccn_capture_sync_at + the step) against
+        receive_capture(cap, first) with the start known, J = 4 and 16, and the acquisition launches alone; 73 and 1170 frames
+        QPSK, same alternation
 
 Shapes: 1170 frames QPSK and 16-QAM, and one 20 000-frame QPSK sweep batch (N = 64).  Every shape runs in a child process of
 its own under a time limit; the parent never opens the GPU and stops at the first child that fails.  Times are medians over
@@ -230,6 +234,70 @@ def main_capture(a):
     return 0
 
 
+def run_acquire(frames, nbits, W, iters, repeats):
+    """receive_capture(cap, first=None, acquire=J, lo=...) (acquisition + cut + step) against receive_capture(cap, first) with the
+    start known on the host, on one clean transmitted capture that begins inside frame 0; and the acquisition launches alone at
+    J = 4 and J = 16.  Both calls must find the same start and return the same bits before anything is timed."""
+    import numpy as np
+    import torch
+    from dl_ofdm_amd import _lib, ofdm, util
+    from dl_ofdm_amd.engine import RxDims, glorot_init
+    from dl_ofdm_amd.receive import RxReceiver
+    from dl_ofdm_amd.receiver_mp import Flags
+    from dl_ofdm_amd.sync import CaptureAcquire
+    CP = KIN - F
+    T = S * KIN
+    Fl = Flags(channel="AWGN", nbits=nbits, nfft=F, nsymbol=S, longcp=True, nfilter=64)
+    o = ofdm.ofdm_tx(Fl)
+    np.random.seed(0)
+    _, iq, _ = o.ofdm_tx_frame_np(util.bit_source(nbits, o.frame_size, frames + 3))
+    cut, lo = 211, 5
+    cap = torch.as_tensor(np.ascontiguousarray(iq.reshape(-1, 2)[cut:]), device="cuda")
+    true = lo + (T - cut - lo) % T
+    dims = RxDims(S, KIN, F, D, nbits)
+    rc = RxReceiver(dims, frames, glorot_init(dims, 1), CP=CP, pilot_sc=o.pilotSc)
+    a = rc.receive_capture(cap, true, sync=W).packed.clone()
+    for J in (4, 16):
+        r = rc.receive_capture(cap, sync=W, acquire=J, lo=lo)
+        assert int(r.first[0]) == true and torch.equal(a, r.packed)
+    a4, a16 = (CaptureAcquire(S, F, CP, o.pilotSc, J, "cuda") for J in (4, 16))
+    variants = {"known": lambda: rc.receive_capture(cap, true, sync=W),
+                "acquire4": lambda: rc.receive_capture(cap, sync=W, acquire=4, lo=lo),
+                "acquire16": lambda: rc.receive_capture(cap, sync=W, acquire=16, lo=lo),
+                "acquire4_alone": lambda: a4.run(cap, lo), "acquire16_alone": lambda: a16.run(cap, lo)}
+    us, spread = timed(variants, iters, repeats)
+    return {"frames": frames, "nbits": nbits, "W": W, "iters": iters, "repeats": repeats, "us": us, "spread": spread,
+            "build_id": _lib.load().dccn_build_id().decode()}
+
+
+def main_acquire(a):
+    """one child process per shape (73 and 1170 frames, QPSK), under a time limit; the parent never opens the GPU"""
+    res, W = [], a.sync or 3
+    for fr, nb in ((73, 2), (1170, 2)):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--acquire", "--one", "%d,%d" % (fr, nb),
+               "--sync", str(W), "--iters", str(a.iters), "--repeats", str(a.repeats)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        if r.returncode != 0:               # nothing more is started on the GPU after a failure
+            sys.stderr.write(r.stderr[-2000:])
+            print(json.dumps({"bench": "rxbench.acquire", "failed": [fr, nb], "rc": r.returncode, "shapes": res}))
+            return 1
+        res.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    doc = {"bench": "rxbench.acquire",
+           "variants": {"known": "receive_capture(cap, first, sync=W), first an integer",
+                        "acquire4": "receive_capture(cap, first=None, sync=W, acquire=4, lo=5)",
+                        "acquire16": "receive_capture(cap, first=None, sync=W, acquire=16, lo=5)",
+                        "acquire4_alone": "CaptureAcquire(J=4).run(cap, lo): the three acquisition launches",
+                        "acquire16_alone": "CaptureAcquire(J=16).run(cap, lo)"},
+           "unit": "us per call (median over repeats of the mean of `iters` back-to-back calls); spread = (max - min) / median",
+           "shapes": res}
+    print(json.dumps(doc))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+    return 0
+
+
 def run_chains(mods, frames, iters, repeats):
     """G (equaliser -> frozen receiver) chains, one per link, `frames` frames each: (a) G solo receive calls back to back on one
     stream, (b) one grouped call -- same parameters, same frames, inputs resident; the two must agree before anything is timed"""
@@ -323,7 +391,15 @@ def main():
     ap.add_argument("--cfo", action="store_true", help="with --sync: also time receive(x, sync=W, cfo=True)")
     ap.add_argument("--capture", action="store_true",
                     help="time receive_capture against receive(x, sync=W[, cfo=True]) on the same frames cut in advance (W: --sync, default 3)")
+    ap.add_argument("--acquire", action="store_true",
+                    help="time receive_capture(first=None, acquire=J) against receive_capture(first=int), and the acquisition launches alone")
     a = ap.parse_args()
+    if a.acquire:
+        if a.one:
+            fr, nb = (int(v) for v in a.one.split(","))
+            print(json.dumps(run_acquire(fr, nb, a.sync or 3, a.iters, a.repeats)))
+            return 0
+        return main_acquire(a)
     if a.capture:
         if a.one:
             fr, nb = (int(v) for v in a.one.split(","))

@@ -36,11 +36,16 @@ per capture:
     cut            receive(x, sync=W[, cfo=True]) on the same capture cut at the nominal starts (the circular frame)
     baseline       receive(x) on the nominal cut of the capture before the carrier offset, no alignment
 
+``--acquire J[,J...]`` begins each such capture at a random sample inside frame 0 and asks how often
+``receive_capture(first=None, acquire=J, lo=W)`` finds the frame start (within W samples: the refinement behind it absorbs that),
+and what the chain's BER is behind it, next to the BER with the start known.
+
 No threshold: the numbers are the result.
 
     python tools/syncber.py --nbits 2 --out syncber_out [--load CKPT --rx_load CKPT] [--seeds 3] [--train_sync 3 [--rx_sync]]
     python tools/syncber.py --nbits 2 --cfo 0.05,0.2 --out syncber_out
     python tools/syncber.py --nbits 2 --capture --snrs 5,29 --frames 2000 --out syncber_out
+    python tools/syncber.py --nbits 2 --acquire 4,8,16 --snrs 5,30 --frames 73 --captures 30 --out syncber_out
 """
 import argparse
 import copy
@@ -199,6 +204,83 @@ def capture_rows(a, tr, hf, snrs, log):
                        cell(r["cut"]), cell(r["baseline"]), ", ".join("%s: %.1f %%" % (k, 100 * v) for k, v in r["offset_share"].items())))
 
 
+def acquire_rows(a, tr, hf, snrs, log):
+    """the --acquire table: one row per (channel, SNR): the share of captures whose start acquisition finds (within W samples of
+    the true frame start: the refinement behind it absorbs that) at each J, and the chain's BER behind it against the BER with the
+    start known.  Captures as in capture_rows (run_stream, white noise, one eps ~ U(-0.2, 0.2) per capture), each beginning at a
+    random sample inside frame 0; the search starts at lo = W."""
+    import torch
+    from dl_ofdm_amd import ofdm, util
+    from dl_ofdm_amd.radio import apply_cfo_stream, rayleigh_chan_lte
+    n, W, lead, EPS = a.frames, a.W, 64, 0.2
+    Js = [int(v) for v in a.acquire.split(",")]
+    lo = W
+    rows = []
+    for ch in CAPTURE_CHANNELS:
+        fl = copy.deepcopy(hf)
+        fl.channel = ch
+        o = ofdm.ofdm_tx(fl)
+        S, K, CP = int(fl.nsymbol), int(o.K), int(o.CP)
+        T = S * (K + CP)
+        n_tx = max(n, max(Js)) + 4
+        fading = rayleigh_chan_lte(fl, o.Fs)
+        for i, snr in enumerate(snrs):
+            right = {J: 0 for J in Js}
+            err = {J: {} for J in Js}
+            ber_right = {J: [] for J in Js}
+            ber_all = {J: [] for J in Js}
+            ber_known = []
+            for c_i in range(a.captures):
+                np.random.seed(177 + 13 * i + 1009 * c_i)
+                bits = util.bit_source(fl.nbits, o.frame_size, n_tx)
+                iq, _, _ = o.ofdm_tx_frame_np(bits)
+                c, _ = fading.run_stream(iq, lead)
+                c = c.astype(np.complex128)
+                c /= np.sqrt(np.mean(np.abs(c[lead:lead + n_tx * T]) ** 2))
+                std = np.sqrt(0.5) * 10.0 ** (-snr / 20.0)
+                c = c + std * (np.random.randn(c.shape[0]) + 1j * np.random.randn(c.shape[0]))
+                eps = float(np.random.uniform(-EPS, EPS))
+                cut = int(np.random.randint(0, T))
+                full = apply_cfo_stream(np.stack([c.real, c.imag], axis=-1).astype(np.float32), eps, K)
+                cap = torch.as_tensor(np.ascontiguousarray(full[lead + cut:]), device=tr.device)
+                m0 = -(-(lo + cut) // T)                                              # the first transmitted frame that starts at or after lo
+                true = m0 * T - cut
+                lab = torch.as_tensor(bits[m0:m0 + n].astype(np.int32), device=tr.device)
+                ber = lambda res: float((res.bits().to(torch.int32) != lab).to(torch.float32).mean())   # noqa: E731
+                ber_known.append(ber(tr.receive_capture(cap, true, sync=W, cfo=True, frames=n)))
+                for J in Js:
+                    res = tr.receive_capture(cap, sync=W, cfo=True, frames=n, acquire=J, lo=lo)
+                    d = (int(res.first[0]) - true + T // 2) % T - T // 2
+                    err[J][d] = err[J].get(d, 0) + 1
+                    b = ber(res)
+                    ber_all[J].append(b)
+                    if abs(d) <= W:
+                        right[J] += 1
+                        ber_right[J].append(b)
+            row = {"channel": ch, "snr_db": snr, "captures": a.captures, "frames": n,
+                   "ber_known": float(np.mean(ber_known)),
+                   "acquire": {str(J): {"share_right": right[J] / a.captures,
+                                        "first_minus_true": {str(k): v for k, v in sorted(err[J].items())},
+                                        "ber_where_right": float(np.mean(ber_right[J])) if ber_right[J] else None,
+                                        "ber_all": float(np.mean(ber_all[J]))} for J in Js}}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    log["acquire_rows"] = rows
+    with open(os.path.join(a.out, "syncber_acquire_%dmod.json" % a.nbits), "w") as f:
+        json.dump(log, f, indent=1)
+        f.write("\n")
+    with open(os.path.join(a.out, "syncber_acquire_%dmod.md" % a.nbits), "w") as f:
+        f.write("| channel | SNR [dB] | BER, start known | " + " | ".join("J = %d: acquired / BER where acquired / BER over all" % J for J in Js)
+                + " |\n|---|---|---|" + "---|" * len(Js) + "\n")
+        for r in rows:
+            cells = []
+            for J in Js:
+                q = r["acquire"][str(J)]
+                cells.append("%d of %d / %s / %.3g" % (round(q["share_right"] * r["captures"]), r["captures"],
+                                                      "-" if q["ber_where_right"] is None else "%.3g" % q["ber_where_right"], q["ber_all"]))
+            f.write("| %s | %g | %.3g | %s |\n" % (r["channel"], r["snr_db"], r["ber_known"], " | ".join(cells)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nbits", type=int, default=2)
@@ -218,6 +300,10 @@ def main():
     ap.add_argument("--capture", action="store_true",
                     help="contiguous captures from the host model (run_stream): receive_capture against receive(sync=W[, cfo=True]) on the "
                          "same capture cut at the nominal starts, and the offset-free unaligned baseline; EPA / EVA / ETU at --snrs")
+    ap.add_argument("--acquire", default=None,
+                    help="J[,J...]: captures that begin inside frame 0 (host model as --capture, one eps ~ U(-0.2, 0.2) each): the share "
+                         "whose start receive_capture(first=None, acquire=J) finds, and the chain's BER behind it; --frames per capture")
+    ap.add_argument("--captures", type=int, default=30, help="--acquire: captures per channel and SNR")
     ap.add_argument("--out", default="syncber_out")
     a = ap.parse_args()
     import torch
@@ -275,6 +361,9 @@ def main():
                                  "seconds": round(time.time() - t2, 1), "best_train_loss": best2["train_loss"],
                                  "best_epoch": best2["epoch"], "test_ber_at_best": best2["test_ber"]}
     print(json.dumps(log), flush=True)
+    if a.acquire:
+        acquire_rows(a, tr, hf, snrs, log)
+        return
     if a.capture:
         capture_rows(a, tr, hf, snrs, log)
         return
