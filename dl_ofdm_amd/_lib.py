@@ -56,6 +56,17 @@ ROUTE_FAMILIES = dict(generic=0, gemm16=1, skinny=2, fewrow=3, kmajor=4, staged=
                       two_launch=9, rx_fused=10)
 
 
+class CconvPatchPlan(C.Structure):
+    """dccn_cconv_patch_plan: what dccn_cconv_patch_plan_query reports (ops and kernels: the DCCN_PATCH_* ids of dccn.h)"""
+    _fields_ = [("kernel", c_int), ("tile_rows", c_int), ("tile_cols", c_int), ("tile_k", c_int), ("splits", c_int),
+                ("klen", c_int), ("col_tiles", c_int), ("depth", c_int), ("bt_lds", c_int), ("taps_fastest", c_int),
+                ("phases", c_int), ("tiles", c_int), ("positions", c_int), ("chunks", c_int), ("items", c_int), ("grid", c_int)]
+
+
+PATCH_OPS = dict(fwd=0, bwd_w=1, bwd_x=2, bwd_1d=3)
+PATCH_KERNELS = dict(gemm=0, kmajor=1, dx_narrow=2, conv1d_fused=3)
+
+
 class RxBuffers(C.Structure):
     """dccn_rx_buffers"""
     _fields_ = [("x", c_void_p), ("bits", c_void_p), ("params", c_void_p), ("grads", c_void_p),
@@ -189,6 +200,7 @@ SIGNATURES = {
     "dccn_cconv_patch_bwd_w": (_i, [_vp, _vp, _vp, _vp] + [_i] * 15 + [_vp, C.c_size_t, _vp]),
     "dccn_cconv_patch_bwd_x_workspace_size": (C.c_size_t, [_i] * 4),
     "dccn_cconv_patch_bwd_x": (_i, [_vp, _vp, _vp] + [_i] * 15 + [_vp, C.c_size_t, _vp]),
+    "dccn_cconv_patch_plan_query": (_i, [_i] * 12 + [POINTER(CconvPatchPlan)]),
     "dccn_metrics_table_add": (_i, [_vp, _vp, _vp]),
     "dccn_metrics_table_set": (_i, [_vp, _vp, _vp]),
     "dccn_ingraph_awgn_workspace_size": (_sz, [_i, _i]),

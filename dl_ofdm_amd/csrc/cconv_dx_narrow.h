@@ -200,37 +200,60 @@ static inline bool cconv_dx_narrow_ok(int C, int F, int sL, int sW) {
     return 2 * C <= 32 && (F % 2) == 0 && sL >= 1 && sW >= 1 && sL * sW <= kDxMaxPhases;
 }
 
-static int launch_cconv_dx_narrow(DxNarrowArgs a, hipStream_t s) {
-    a.nphase = a.sL * a.sW;
+// What a launch is made of, decided once: launch_cconv_dx_narrow issues exactly this, dccn_cconv_patch_plan_query reports it.
+struct DxNarrowPlan {
+    bool two, deep, blds, nmaj;         // column tiles of 16 (2: C2 > 16), float4s per lane and group, Bt in LDS, taps-fastest walk
+    int nphase, tiles, grid;            // stride phases, 64-position tiles over all phases, persistent blocks
+    int tile0[kDxMaxPhases + 1];        // first tile of every phase
+    int bstride;                        // row stride of the LDS copy of Bt (floats)
+    size_t smem;                        // its bytes (the LDS request when blds)
+};
+static inline DxNarrowPlan plan_cconv_dx_narrow(int B, int L, int Wd, int C2, int ntl, int ntw, int F2, int sL, int sW) {
+    DxNarrowPlan p;
+    p.nphase = sL * sW;
     int blocks = 0;
-    for (int ph = 0; ph < a.nphase; ++ph) {
-        const int pl = ph / a.sW, pw = ph % a.sW;
-        const int Lp = pl < a.L ? (a.L - pl + a.sL - 1) / a.sL : 0, Wp = pw < a.Wd ? (a.Wd - pw + a.sW - 1) / a.sW : 0;
-        a.tile0[ph] = blocks;
-        blocks += ceil_div(a.B * Lp * Wp, 64);
+    for (int ph = 0; ph < p.nphase; ++ph) {
+        const int pl = ph / sW, pw = ph % sW;
+        const int Lp = pl < L ? (L - pl + sL - 1) / sL : 0, Wp = pw < Wd ? (Wd - pw + sW - 1) / sW : 0;
+        p.tile0[ph] = blocks;
+        blocks += ceil_div(B * Lp * Wp, 64);
     }
-    for (int ph = a.nphase; ph <= kDxMaxPhases; ++ph) a.tile0[ph] = blocks;
-    if (blocks <= 0) return DCCN_ERR_INVALID_ARG;
-    DCCN_NO_CHAINS();
+    for (int ph = p.nphase; ph <= kDxMaxPhases; ++ph) p.tile0[ph] = blocks;
+    p.tiles = blocks;
     // Bt in LDS when it fits beside nothing else (<= 64 KB: two blocks per CU); rows 16 mod 32 floats apart
-    const int Kfull = a.ntl * a.ntw * a.F2;
-    a.bstride = (Kfull + 31) / 32 * 32 + 16;
-    const size_t smem = (size_t)a.C2 * a.bstride * sizeof(float);
-    const bool blds = smem <= 64 * 1024, deep = (a.F2 % 8) == 0, two = a.C2 > 16;
-    const bool nmaj = blds && (a.F2 % (deep ? 32 : 16)) == 0;
-    const int grid = blocks < 6 * kCUs ? blocks : 6 * kCUs;           // (6 blocks = 24 waves per CU: the occupancy the registers allow)
+    const int Kfull = ntl * ntw * F2;
+    p.bstride = (Kfull + 31) / 32 * 32 + 16;
+    p.smem = (size_t)C2 * p.bstride * sizeof(float);
+    p.blds = p.smem <= 64 * 1024;
+    p.deep = (F2 % 8) == 0;
+    p.two = C2 > 16;
+    p.nmaj = p.blds && (F2 % (p.deep ? 32 : 16)) == 0;
+    p.grid = blocks < 6 * kCUs ? blocks : 6 * kCUs;                   // (6 blocks = 24 waves per CU: the occupancy the registers allow)
+    return p;
+}
+
+static int launch_cconv_dx_narrow(DxNarrowArgs a, hipStream_t s) {
+    const DxNarrowPlan pl = plan_cconv_dx_narrow(a.B, a.L, a.Wd, a.C2, a.ntl, a.ntw, a.F2, a.sL, a.sW);
+    if (pl.tiles <= 0) return DCCN_ERR_INVALID_ARG;
+    a.nphase = pl.nphase;
+    for (int ph = 0; ph <= kDxMaxPhases; ++ph) a.tile0[ph] = pl.tile0[ph];
+    a.bstride = pl.bstride;
+    DCCN_NO_CHAINS();
+    const size_t smem = pl.smem;
+    const bool nmaj = pl.nmaj;
+    const int grid = pl.grid;
 #define DCCN_DXN_LAUNCH(NT, DP, BL)                                                                              \
     do {                                                                                                         \
         auto kern = (BL && nmaj) ? cconv_dx_narrow_kernel<NT, DP, BL, BL> : cconv_dx_narrow_kernel<NT, DP, BL, false>; \
         if (BL) DCCN_TRY(set_max_dynamic_smem(reinterpret_cast<const void*>(kern), smem));                       \
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), BL ? smem : 0, s, a);                                    \
     } while (0)
-    if (two) {
-        if (deep) { if (blds) DCCN_DXN_LAUNCH(2, 2, true); else DCCN_DXN_LAUNCH(2, 2, false); }
-        else { if (blds) DCCN_DXN_LAUNCH(2, 1, true); else DCCN_DXN_LAUNCH(2, 1, false); }
+    if (pl.two) {
+        if (pl.deep) { if (pl.blds) DCCN_DXN_LAUNCH(2, 2, true); else DCCN_DXN_LAUNCH(2, 2, false); }
+        else { if (pl.blds) DCCN_DXN_LAUNCH(2, 1, true); else DCCN_DXN_LAUNCH(2, 1, false); }
     } else {
-        if (deep) { if (blds) DCCN_DXN_LAUNCH(1, 2, true); else DCCN_DXN_LAUNCH(1, 2, false); }
-        else { if (blds) DCCN_DXN_LAUNCH(1, 1, true); else DCCN_DXN_LAUNCH(1, 1, false); }
+        if (pl.deep) { if (pl.blds) DCCN_DXN_LAUNCH(1, 2, true); else DCCN_DXN_LAUNCH(1, 2, false); }
+        else { if (pl.blds) DCCN_DXN_LAUNCH(1, 1, true); else DCCN_DXN_LAUNCH(1, 1, false); }
     }
 #undef DCCN_DXN_LAUNCH
     DCCN_LAUNCH_CHECK();

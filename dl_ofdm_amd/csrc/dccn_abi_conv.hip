@@ -29,6 +29,21 @@ int dccn_cconv_patch_supported(int B, int L, int Wd, int C, int Lo, int Wo, int 
     if ((long long)ntl * ntw * C * 2 * 2 * F * 4 >= (1LL << 31)) return 0;
     return 1;
 }
+// One description per launch of the general-k convolutions: the operator issues it, dccn_cconv_patch_plan_query (below) reads
+// the decisions of the same description (gemm_tile, plan_splitk, plan_cconv_dx_narrow, conv1d_bwd_plan) on null operands.
+static GemmParams patch_fwd_params(const float* x, const float* w, const float* bias, float* out, const Im2colGeom& g, int F) {
+    const int kin = g.ntl * g.ntw * g.C;
+    GemmParams p = gp_zero();                 // out[rows,2F] = patches[rows,2kin] . Weff[2kin,2F]
+    p.A = x; p.B = w; p.C = out; p.bias = bias; p.cbias = 1;
+    p.M = g.B * g.Lo * g.Wo; p.N = 2 * F; p.K = 2 * kin;
+    p.lda = 0; p.ldb = 2 * F; p.ldc = 2 * F;
+    p.klen = round_k(2 * kin);
+    p.cF = F;
+    p.vecA = 1; p.vecB = 1;
+    p.pg.L = g.L; p.pg.Wd = g.Wd; p.pg.c2 = 2 * g.C; p.pg.Lo = g.Lo; p.pg.Wo = g.Wo; p.pg.ntl = g.ntl; p.pg.ntw = g.ntw;
+    p.pg.sL = g.sL; p.pg.sW = g.sW; p.pg.l0 = g.tl0 - g.pl0; p.pg.w0 = g.tw0 - g.pw0;
+    return p;
+}
 int dccn_cconv_patch_fwd(const float* x, const float* w, const float* bias, float* out, int B, int L, int Wd, int C, int Lo,
                          int Wo, int ntl, int ntw, int tl0, int tw0, int sL, int sW, int pl0, int pw0, int F,
                          dccn_stream_t stream) {
@@ -36,17 +51,7 @@ int dccn_cconv_patch_fwd(const float* x, const float* w, const float* bias, floa
     if (!x || !w || !out || !im2col_geom_ok(g) || !dccn_cconv_patch_supported(B, L, Wd, C, Lo, Wo, ntl, ntw, F) ||
         !aligned16(x) || !aligned16(w))
         return DCCN_ERR_INVALID_ARG;
-    const int kin = ntl * ntw * C;
-    GemmParams p = gp_zero();                 // out[rows,2F] = patches[rows,2kin] . Weff[2kin,2F]
-    p.A = x; p.B = w; p.C = out; p.bias = bias; p.cbias = 1;
-    p.M = B * Lo * Wo; p.N = 2 * F; p.K = 2 * kin;
-    p.lda = 0; p.ldb = 2 * F; p.ldc = 2 * F;
-    p.klen = round_k(2 * kin);
-    p.cF = F;
-    p.vecA = 1; p.vecB = 1;
-    p.pg.L = L; p.pg.Wd = Wd; p.pg.c2 = 2 * C; p.pg.Lo = Lo; p.pg.Wo = Wo; p.pg.ntl = ntl; p.pg.ntw = ntw;
-    p.pg.sL = sL; p.pg.sW = sW; p.pg.l0 = tl0 - pl0; p.pg.w0 = tw0 - pw0;
-    return launch_gemm<OP_KPATCH, OP_CCONV_W, 0, TAG_CCONV_FWD>(p, 1, (hipStream_t)stream);
+    return launch_gemm<OP_KPATCH, OP_CCONV_W, 0, TAG_CCONV_FWD>(patch_fwd_params(x, w, bias, out, g, F), 1, (hipStream_t)stream);
 }
 // ---- the backward of the same convolutions without the patch tensor ---------------------------------------------
 // weight gradient: dWeff[(ti,tj,c,iq), n] = sum over output positions of patch(x)^T . dout -- the k-major weight-gradient
@@ -73,6 +78,23 @@ size_t dccn_cconv_patch_bwd_w_workspace_size(int B, int Lo, int Wo, int C, int n
     if (B <= 0 || Lo <= 0 || Wo <= 0 || C <= 0 || ntl <= 0 || ntw <= 0 || F <= 0) return 0;
     return cconv_bw_ws_bytes(B * Lo * Wo, ntl * ntw * C, F);
 }
+// (k ranges over the output positions: plan_splitk of the [2kin, 2F] output over B Lo Wo rows)
+static SplitPlan patch_bwd_w_plan(const Im2colGeom& g, int F) {
+    return plan_splitk(2 * g.ntl * g.ntw * g.C, 2 * F, g.B * g.Lo * g.Wo);
+}
+static GemmParams patch_bwd_w_params(const float* x, const float* dout, float* slabs, const Im2colGeom& g, int F) {
+    const int kin = g.ntl * g.ntw * g.C;
+    GemmParams p = gp_zero();                 // dWeff[2kin,2F] = patches(x)[rows,2kin]^T . dout[rows,2F]
+    p.A = x; p.B = dout; p.C = slabs;
+    p.M = 2 * kin; p.N = 2 * F; p.K = g.B * g.Lo * g.Wo;
+    p.lda = 0; p.ldb = 2 * F; p.ldc = 2 * F;
+    p.vecA = 1; p.vecB = 1;
+    p.pg.L = g.L; p.pg.Wd = g.Wd; p.pg.c2 = 2 * g.C; p.pg.Lo = g.Lo; p.pg.Wo = g.Wo; p.pg.ntl = g.ntl; p.pg.ntw = g.ntw;
+    p.pg.sL = g.sL; p.pg.sW = g.sW; p.pg.l0 = g.tl0 - g.pl0; p.pg.w0 = g.tw0 - g.pw0;
+    patch_div_magic(g.Lo * g.Wo, p.pg.per_mul, p.pg.per_shift);
+    patch_div_magic(g.Wo, p.pg.wo_mul, p.pg.wo_shift);
+    return p;
+}
 int dccn_cconv_patch_bwd_w(const float* x, const float* dout, float* dw, float* dbias, int B, int L, int Wd, int C, int Lo,
                            int Wo, int ntl, int ntw, int tl0, int tw0, int sL, int sW, int pl0, int pw0, int F,
                            void* workspace, size_t workspace_bytes, dccn_stream_t stream) {
@@ -83,22 +105,15 @@ int dccn_cconv_patch_bwd_w(const float* x, const float* dout, float* dw, float* 
     const int rows = B * Lo * Wo, kin = ntl * ntw * C;
     if (!workspace || workspace_bytes < cconv_bw_ws_bytes(rows, kin, F)) return DCCN_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const SplitPlan sp = plan_splitk(2 * kin, 2 * F, rows);
+    const SplitPlan sp = patch_bwd_w_plan(g, F);
     Carver c(workspace, workspace_bytes);
     SlabWs sw;
     if (!slab_carve(c, sp.splits, 2 * kin, 2 * F, &sw)) return DCCN_ERR_WORKSPACE;
     float *slabs = sw.slabs, *cs = sw.colsum;
-    GemmParams p = gp_zero();                 // dWeff[2kin,2F] = patches(x)[rows,2kin]^T . dout[rows,2F]
-    p.A = x; p.B = dout; p.C = slabs; p.colsum = cs;
-    p.M = 2 * kin; p.N = 2 * F; p.K = rows;
-    p.lda = 0; p.ldb = 2 * F; p.ldc = 2 * F;
+    GemmParams p = patch_bwd_w_params(x, dout, slabs, g, F);
+    p.colsum = cs;
     p.klen = sp.klen;
     p.slab = sw.slab;
-    p.vecA = 1; p.vecB = 1;
-    p.pg.L = L; p.pg.Wd = Wd; p.pg.c2 = 2 * C; p.pg.Lo = Lo; p.pg.Wo = Wo; p.pg.ntl = ntl; p.pg.ntw = ntw;
-    p.pg.sL = sL; p.pg.sW = sW; p.pg.l0 = tl0 - pl0; p.pg.w0 = tw0 - pw0;
-    patch_div_magic(Lo * Wo, p.pg.per_mul, p.pg.per_shift);
-    patch_div_magic(Wo, p.pg.wo_mul, p.pg.wo_shift);
     if (!kmajor_ok(p)) return DCCN_ERR_INVALID_ARG;
     DCCN_TRY((launch_kmajor<1, TAG_CCONV_BWD_W, true>(p, sp.splits, s)));
     const int fold_blocks = ceil_div(kin * F + F, kRedLanes);
@@ -133,6 +148,21 @@ size_t dccn_cconv_patch_bwd_x_workspace_size(int C, int ntl, int ntw, int F) {
     if (C <= 0 || ntl <= 0 || ntw <= 0 || F <= 0) return 0;
     return carved_bytes([&](Carver& c) { patch_bwd_x_carve(c, C, ntl, ntw, F); });
 }
+// the wide form (more than 32 columns, or more stride phases than cconv_dx_narrow.h walks): OP_KPATCH over dout
+static GemmParams patch_bwd_x_params(const float* dout, const float* bt, float* dx, const Im2colGeom& g, int F) {
+    GemmParams p = gp_zero();                 // dx[B*L*Wd, 2C] = patches'(dout)[., ntl*ntw*2F] . Bt^T
+    p.A = dout; p.B = bt; p.C = dx;
+    p.M = g.B * g.L * g.Wd; p.N = 2 * g.C; p.K = g.ntl * g.ntw * 2 * F;
+    p.lda = 0; p.ldb = p.K; p.ldc = 2 * g.C;
+    p.klen = round_k(p.K);
+    p.vecA = 1; p.vecB = 1;
+    p.pg.L = g.Lo; p.pg.Wd = g.Wo; p.pg.c2 = 2 * F; p.pg.Lo = g.L; p.pg.Wo = g.Wd; p.pg.ntl = g.ntl; p.pg.ntw = g.ntw;
+    p.pg.sL = 1; p.pg.sW = 1; p.pg.l0 = -(g.tl0 - g.pl0) - (g.ntl - 1); p.pg.w0 = -(g.tw0 - g.pw0) - (g.ntw - 1);
+    p.pg.isL = g.sL; p.pg.isW = g.sW;
+    patch_div_magic(g.sL, p.pg.il_mul, p.pg.il_shift);
+    patch_div_magic(g.sW, p.pg.iw_mul, p.pg.iw_shift);
+    return p;
+}
 int dccn_cconv_patch_bwd_x(const float* dout, const float* w, float* dx, int B, int L, int Wd, int C, int Lo, int Wo, int ntl,
                            int ntw, int tl0, int tw0, int sL, int sW, int pl0, int pw0, int F, void* workspace,
                            size_t workspace_bytes, dccn_stream_t stream) {
@@ -157,18 +187,7 @@ int dccn_cconv_patch_bwd_x(const float* dout, const float* w, float* dx, int B, 
         a.sL = sL; a.sW = sW;
         return launch_cconv_dx_narrow(a, s);
     }
-    GemmParams p = gp_zero();                 // dx[B*L*Wd, 2C] = patches'(dout)[., ntl*ntw*2F] . Bt^T
-    p.A = dout; p.B = bt; p.C = dx;
-    p.M = B * L * Wd; p.N = 2 * C; p.K = ntl * ntw * 2 * F;
-    p.lda = 0; p.ldb = p.K; p.ldc = 2 * C;
-    p.klen = round_k(p.K);
-    p.vecA = 1; p.vecB = 1;
-    p.pg.L = Lo; p.pg.Wd = Wo; p.pg.c2 = 2 * F; p.pg.Lo = L; p.pg.Wo = Wd; p.pg.ntl = ntl; p.pg.ntw = ntw;
-    p.pg.sL = 1; p.pg.sW = 1; p.pg.l0 = -(tl0 - pl0) - (ntl - 1); p.pg.w0 = -(tw0 - pw0) - (ntw - 1);
-    p.pg.isL = sL; p.pg.isW = sW;
-    patch_div_magic(sL, p.pg.il_mul, p.pg.il_shift);
-    patch_div_magic(sW, p.pg.iw_mul, p.pg.iw_shift);
-    return launch_gemm<OP_KPATCH, OP_KCONTIG, 0, TAG_CCONV_BWD_X>(p, 1, s);
+    return launch_gemm<OP_KPATCH, OP_KCONTIG, 0, TAG_CCONV_BWD_X>(patch_bwd_x_params(dout, bt, dx, g, F), 1, s);
 }
 // ---- few-channel 1-D C-Conv: input, weight and bias gradient in one pass over dout (cconv1d_bwd.h) -------------------------
 constexpr int kConv1dMaxBlocks = 1024;
@@ -178,6 +197,19 @@ int dccn_cconv1d_bwd_supported(int B, int L, int C, int Lo, int ntl, int sL, int
     if ((C % 2) != 0 || (F != 32 && F != 64) || 2 * ntl * C > 30 || conv1d_bwd_pl(ntl, sL) < 1) return 0;
     if ((long long)B * L * C * 2 >= (1LL << 31) || (long long)B * Lo * F * 2 >= (1LL << 31)) return 0;
     return 1;
+}
+// the launch, decided once (dccn_cconv1d_bwd issues it, dccn_cconv_patch_plan_query reports it): chunks of PL owned positions,
+// nch of them per batch item, B nch items in all on min(2 per CU, kConv1dMaxBlocks, items) persistent blocks
+struct Conv1dPlan { int PL, nch; long long items; int grid; };
+static Conv1dPlan conv1d_bwd_plan(int B, int L, int ntl, int sL) {
+    Conv1dPlan p;
+    p.PL = conv1d_bwd_pl(ntl, sL);
+    p.nch = ceil_div(L, p.PL);
+    p.items = (long long)B * p.nch;
+    p.grid = 2 * kCUs;
+    if (p.grid > kConv1dMaxBlocks) p.grid = kConv1dMaxBlocks;
+    if (p.grid > p.items) p.grid = (int)p.items;
+    return p;
 }
 // per-block weight-gradient slabs ([32][2F], the fold's k rows) and column sums of up to kConv1dMaxBlocks blocks
 struct Conv1dWs { float *slabs, *colsum; };
@@ -204,12 +236,10 @@ int dccn_cconv1d_bwd(const float* x, const float* dout, const float* w, float* d
     a.slabs = cw.slabs; a.colsum = cw.colsum;
     a.B = B; a.L = L; a.C2 = 2 * C; a.Lo = Lo; a.nt = ntl; a.F2 = 2 * F; a.NC = 2 * ntl * C;
     a.o = tl0 - pl0; a.s = sL;
-    a.PL = conv1d_bwd_pl(ntl, sL);
-    a.nch = ceil_div(L, a.PL);
-    const long long total = (long long)B * a.nch;
-    int grid = 2 * kCUs;
-    if (grid > kConv1dMaxBlocks) grid = kConv1dMaxBlocks;
-    if (grid > total) grid = (int)total;
+    const Conv1dPlan pl = conv1d_bwd_plan(B, L, ntl, sL);
+    a.PL = pl.PL;
+    a.nch = pl.nch;
+    const int grid = pl.grid;
     DCCN_NO_CHAINS();
     if (F == 64) {
         auto kern = cconv1d_bwd_fused_kernel<128>;
@@ -236,6 +266,56 @@ int dccn_cconv_col2im(const float* drows, float* dx, int B, int L, int Wd, int C
     hipLaunchKernelGGL(col2im_kernel, dim3((unsigned)ceil_div_ll(n, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float2*)drows, (float2*)dx, g, n);
     DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+// host only: what the four operators above are about to launch (the descriptions they build, on null -- 16-byte aligned --
+// inputs and an aligned output address that nothing dereferences; tap origins and pads move no decision and are left zero)
+int dccn_cconv_patch_plan_query(int op, int B, int L, int Wd, int C, int Lo, int Wo, int ntl, int ntw, int sL, int sW, int F,
+                                dccn_cconv_patch_plan* plan) {
+    float* const out = reinterpret_cast<float*>(static_cast<uintptr_t>(256));
+    const Im2colGeom g{B, L, Wd, C, Lo, Wo, ntl, ntw, 0, 0, sL, sW, 0, 0};
+    if (!plan || !im2col_geom_ok(g) || F <= 0) return DCCN_ERR_INVALID_ARG;
+    dccn_cconv_patch_plan r;
+    memset(&r, 0, sizeof(r));
+    auto tile = [&](const GemmTile t) { r.kernel = DCCN_PATCH_KERNEL_GEMM; r.tile_rows = t.bm; r.tile_cols = t.bn; r.tile_k = t.bk; };
+    switch (op) {
+        case DCCN_PATCH_FWD:
+            if (!dccn_cconv_patch_supported(B, L, Wd, C, Lo, Wo, ntl, ntw, F)) return DCCN_ERR_INVALID_ARG;
+            tile(gemm_tile<OP_KPATCH, OP_CCONV_W>(patch_fwd_params(nullptr, nullptr, nullptr, out, g, F), 1));
+            break;
+        case DCCN_PATCH_BWD_W: {
+            if (!(dccn_cconv_patch_bwd_supported(B, L, Wd, C, Lo, Wo, ntl, ntw, sL, sW, F) & 1)) return DCCN_ERR_INVALID_ARG;
+            const SplitPlan sp = patch_bwd_w_plan(g, F);
+            GemmParams p = patch_bwd_w_params(nullptr, nullptr, out, g, F);
+            p.klen = sp.klen;
+            if (!kmajor_ok(p)) return DCCN_ERR_INVALID_ARG;
+            r.kernel = DCCN_PATCH_KERNEL_KMAJOR; r.tile_rows = 64; r.tile_cols = 64; r.tile_k = 64;
+            r.splits = sp.splits; r.klen = sp.klen;
+            break;
+        }
+        case DCCN_PATCH_BWD_X:
+            if (!(dccn_cconv_patch_bwd_supported(B, L, Wd, C, Lo, Wo, ntl, ntw, sL, sW, F) & 2)) return DCCN_ERR_INVALID_ARG;
+            if (cconv_dx_narrow_ok(C, F, sL, sW)) {
+                const DxNarrowPlan pl = plan_cconv_dx_narrow(B, L, Wd, 2 * C, ntl, ntw, 2 * F, sL, sW);
+                if (pl.tiles <= 0) return DCCN_ERR_INVALID_ARG;
+                r.kernel = DCCN_PATCH_KERNEL_DX_NARROW; r.tile_rows = 64; r.tile_cols = pl.two ? 32 : 16; r.tile_k = pl.deep ? 32 : 16;
+                r.col_tiles = pl.two ? 2 : 1; r.depth = pl.deep ? 2 : 1; r.bt_lds = pl.blds ? 1 : 0; r.taps_fastest = pl.nmaj ? 1 : 0;
+                r.phases = pl.nphase; r.tiles = pl.tiles; r.grid = pl.grid;
+            } else {
+                tile(gemm_tile<OP_KPATCH, OP_KCONTIG>(patch_bwd_x_params(nullptr, nullptr, out, g, F), 1));
+            }
+            break;
+        case DCCN_PATCH_BWD_1D: {
+            if (Wd != 1 || Wo != 1 || ntw != 1 || sW != 1 || !dccn_cconv1d_bwd_supported(B, L, C, Lo, ntl, sL, F)) return DCCN_ERR_INVALID_ARG;
+            const Conv1dPlan pl = conv1d_bwd_plan(B, L, ntl, sL);
+            r.kernel = DCCN_PATCH_KERNEL_CONV1D_FUSED; r.tile_rows = 64; r.tile_cols = 32; r.tile_k = 2 * F;
+            r.positions = pl.PL; r.chunks = pl.nch; r.items = (int)pl.items; r.grid = pl.grid;
+            break;
+        }
+        default: return DCCN_ERR_INVALID_ARG;
+    }
+    *plan = r;
     return DCCN_OK;
 }
 

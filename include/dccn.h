@@ -221,6 +221,35 @@ int dccn_cconv1d_bwd(const float* x, const float* dout, const float* w, float* d
                      int Lo, int ntl, int tl0, int sL, int pl0, int F, void* workspace, size_t workspace_bytes,
                      dccn_stream_t stream);
 
+/* What the four operators above are about to launch for a geometry (host only, no device work; a sibling of
+ * dccn_gemm_route_query below).  The operators take these decisions from the functions the query calls, so a case that is
+ * written for one kernel variant can assert that the variant is what its shape runs.
+ *   op                      operator                   fields that carry the answer
+ *   DCCN_PATCH_FWD          dccn_cconv_patch_fwd       kernel = GEMM; tile_rows x tile_cols x tile_k
+ *   DCCN_PATCH_BWD_W        dccn_cconv_patch_bwd_w     kernel = KMAJOR (64x64x64 tiles); splits, klen (the last k range may be shorter)
+ *   DCCN_PATCH_BWD_X        dccn_cconv_patch_bwd_x     kernel = GEMM: the wide inverse-stride gather, tile_* as in the forward;
+ *                                                      kernel = DX_NARROW (csrc/cconv_dx_narrow.h): col_tiles (1 or 2 tiles of 16
+ *                                                      columns), depth (float4s per lane and k group: 1 or 2), bt_lds (1: the
+ *                                                      flipped weights staged in LDS, 0: read from global memory), taps_fastest
+ *                                                      (1: the k walk runs over the taps fastest), phases (sL * sW), tiles (64
+ *                                                      positions each, over all phases), grid (persistent blocks)
+ *   DCCN_PATCH_BWD_1D       dccn_cconv1d_bwd           kernel = CONV1D_FUSED: positions (owned per chunk), chunks (per batch
+ *                           (Wd = Wo = ntw = sW = 1)   item), items (B * chunks), grid (persistent blocks)
+ * Fields an operator does not decide are 0.  Returns DCCN_ERR_INVALID_ARG, *plan untouched, exactly where the operator refuses
+ * the geometry (tap origins and pads, which move none of these decisions, are not part of the query). */
+enum { DCCN_PATCH_FWD = 0, DCCN_PATCH_BWD_W = 1, DCCN_PATCH_BWD_X = 2, DCCN_PATCH_BWD_1D = 3 };
+enum { DCCN_PATCH_KERNEL_GEMM = 0, DCCN_PATCH_KERNEL_KMAJOR = 1, DCCN_PATCH_KERNEL_DX_NARROW = 2, DCCN_PATCH_KERNEL_CONV1D_FUSED = 3 };
+typedef struct dccn_cconv_patch_plan {
+    int kernel;
+    int tile_rows, tile_cols, tile_k;
+    int splits, klen;
+    int col_tiles, depth, bt_lds, taps_fastest, phases, tiles;
+    int positions, chunks, items;
+    int grid;
+} dccn_cconv_patch_plan;
+int dccn_cconv_patch_plan_query(int op, int B, int L, int Wd, int C, int Lo, int Wo, int ntl, int ntw, int sL, int sW, int F,
+                                dccn_cconv_patch_plan* plan);
+
 /* The in-graph AWGN monitor branch of the receiver graph (dev/py/radio.py:62-88 AWGN_channel, called at
  * dev/py/ofdmreceiver_np.py:136; tensors `tx_signal:0`, `iq_tx:0`, `iq_rx:0`, `noise_power:0`, :151-152,172-183):
  * tx_signal = complex_clip(x_norm, peak); xn = batch_norm(tx_signal, eps 1e-8)/sqrt(2);

@@ -43,6 +43,7 @@ def test_struct_sizes_match_header(lib):
     assert C.sizeof(_lib.RxBuffers) == 26 * 8          # ... + x_next_ready + gen_next + tuning
     assert C.sizeof(_lib.GenStatic) == 200             # (static_assert'ed against the C struct in csrc/dccn_abi.hip)
     assert C.sizeof(_lib.GenProfile) == 32
+    assert C.sizeof(_lib.CconvPatchPlan) == 16 * 4     # dccn_cconv_patch_plan: sixteen ints
 
 
 
