@@ -139,6 +139,24 @@ class ChannelGroup(C.Structure):
                 ("n_taps", c_int), ("L", c_int), ("identity", c_int), ("Fd", c_float)]
 
 
+class FrameLink(C.Structure):
+    """dccn_frame_link"""
+    _fields_ = [("x", c_void_p), ("x_out", c_void_p), ("offset", c_void_p), ("cfo", c_void_p), ("metric", c_void_p)]
+
+
+class CaptureLink(C.Structure):
+    """dccn_capture_link"""
+    _fields_ = [("cap", c_void_p), ("n_samples", c_longlong), ("first", c_longlong), ("first_dev", c_void_p), ("lo", c_longlong),
+                ("stride", c_longlong), ("x_out", c_void_p), ("offset", c_void_p), ("cfo", c_void_p), ("metric", c_void_p)]
+
+
+class AcquireLink(C.Structure):
+    """dccn_acquire_link"""
+    _fields_ = [("cap", c_void_p), ("n_samples", c_longlong), ("lo", c_longlong), ("pilot_sc", c_void_p), ("first_out", c_void_p),
+                ("cfo_out", c_void_p), ("sym_metric", c_void_p), ("phase_metric", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", c_size_t)]
+
+
 METRICS_BYTES = C.sizeof(Metrics)
 ADAM_STATE_BYTES = C.sizeof(AdamState)
 
@@ -245,6 +263,10 @@ SIGNATURES = {
     "dccn_capture_acquire_supported": (_i, [_i] * 5),
     "dccn_capture_acquire_workspace_size": (_sz, [_i] * 5),
     "dccn_capture_acquire": (_i, [_vp, c_longlong, c_longlong] + [_i] * 4 + [_vp, _i] + [_vp] * 5 + [_sz, _vp]),
+    # the same stages for several links per launch (a host table of per-link descriptors)
+    "dccn_frame_sync_grouped": (_i, [_i, POINTER(FrameLink)] + [_i] * 6 + [_vp]),
+    "dccn_capture_sync_grouped": (_i, [_i, POINTER(CaptureLink)] + [_i] * 6 + [_vp]),
+    "dccn_capture_acquire_grouped": (_i, [_i, POINTER(AcquireLink)] + [_i] * 5 + [_vp]),
     "dccn_rx_normalise": (_i, [POINTER(RxShape), POINTER(RxBuffers), _vp]),
     "dccn_rx_graph_create": (_i, [POINTER(RxShape), POINTER(RxBuffers), _i, AdamHParams, _vp, POINTER(c_void_p)]),
     "dccn_rx_graph_launch": (_i, [_vp, _vp]),

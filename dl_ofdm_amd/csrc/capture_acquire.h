@@ -28,6 +28,9 @@
 // q + s <= 2 S - 2).  pilot_sc is device data the host cannot look at: entries outside [0, S K) are ignored, a carrier is always
 // taken mod K, and a symbol's run is (first entry, count) within the array, so whatever the array holds nothing is read outside
 // it or outside the symbol's K samples.
+//
+// dccn_capture_acquire_grouped runs the same three launches for up to kMaxChains links at once: each kernel's code is a body over
+// one link's AcqArgs, and the grouped kernels (at the end) hand it the entry of a by-value link table.
 #pragma once
 #include <math.h>
 
@@ -80,7 +83,10 @@ __host__ __device__ static inline size_t capture_acquire_lds(int S, int K, int C
            (size_t)kAcqThreads * 16 + 16;
 }
 
-static __global__ void __launch_bounds__(kAcqSumThreads) acq_symbol_sums_kernel(const AcqArgs a) {
+// The three launches, each stated once as a body over one link's AcqArgs: the solo kernels pass their own argument, the grouped
+// ones (at the end) the entry of their link table.  A body reads blockIdx.x (and .y, acq_phase_body) as the solo grid lays them
+// out; the link index rides on a dimension the body does not look at.
+__device__ __forceinline__ void acq_symbol_sums_body(const AcqArgs& a) {
     const int N = a.K + a.CP;
     const int m = blockIdx.x * kAcqSumThreads + threadIdx.x;
     if (m >= N + a.CP - 1) return;
@@ -95,8 +101,9 @@ static __global__ void __launch_bounds__(kAcqSumThreads) acq_symbol_sums_kernel(
     }
     a.pe[m] = make_float4(pr, pi, e, 0.f);
 }
+static __global__ void __launch_bounds__(kAcqSumThreads) acq_symbol_sums_kernel(const AcqArgs a) { acq_symbol_sums_body(a); }
 
-static __global__ void __launch_bounds__(kAcqThreads) acq_phase_kernel(const AcqArgs a) {
+__device__ __forceinline__ void acq_phase_body(const AcqArgs& a) {
     extern __shared__ float4 acq_lds[];
     const int S = a.S, K = a.K, CP = a.CP, N = K + CP, J = a.J, n_pilot = a.n_pilot;
     const int tid = threadIdx.x;
@@ -212,8 +219,9 @@ static __global__ void __launch_bounds__(kAcqThreads) acq_phase_kernel(const Acq
     }
     if (tid == 0) a.partial[(size_t)q * J + j] = dj;
 }
+static __global__ void __launch_bounds__(kAcqThreads) acq_phase_kernel(const AcqArgs a) { acq_phase_body(a); }
 
-static __global__ void __launch_bounds__(kAcqMaxS) acq_decide_kernel(const AcqArgs a) {
+__device__ __forceinline__ void acq_decide_body(const AcqArgs& a) {
     __shared__ float d[kAcqMaxS];
     const int q = threadIdx.x, S = a.S, J = a.J;
     if (q < S) {
@@ -230,5 +238,37 @@ static __global__ void __launch_bounds__(kAcqMaxS) acq_decide_kernel(const AcqAr
         a.first_out[0] = a.lo + a.rhat[0] + (long long)qhat * (a.K + a.CP);
     }
 }
+static __global__ void __launch_bounds__(kAcqMaxS) acq_decide_kernel(const AcqArgs a) { acq_decide_body(a); }
+
+// ---- several links per launch (dccn_capture_acquire_grouped) --------------------------------------------------------------------
+// Each link has its own capture, origin, pilot cells, outputs and workspace; the shape, J and n_pilot are the call's.  The table
+// travels by value in the kernel arguments and is indexed by a block-uniform value (scalar loads, as ChainOffs is read); the link
+// index is grid dimension y of the symbol sums, z of the phase launch (whose grid is (q, j)) and x of the decision.
+struct AcqLink {
+    const float* cap;
+    long long lo;
+    const int* pilot_sc;
+    float4* pe;
+    float* partial;
+    int* rhat;
+    long long* first_out;
+    float* cfo_out;
+    float* sym_metric;
+    float* phase_metric;
+};
+struct AcqGroupArgs {
+    AcqLink link[kMaxChains];
+    int S, K, CP, J, n_pilot;
+    __device__ __forceinline__ AcqArgs of(const unsigned g) const {
+        const AcqLink& l = link[g];
+        return AcqArgs{l.cap, l.lo, l.pilot_sc, l.pe, l.partial, l.rhat, l.first_out, l.cfo_out, l.sym_metric, l.phase_metric,
+                       S, K, CP, J, n_pilot};
+    }
+};
+static __global__ void __launch_bounds__(kAcqSumThreads) acq_symbol_sums_grouped_kernel(const AcqGroupArgs g) {
+    acq_symbol_sums_body(g.of(blockIdx.y));
+}
+static __global__ void __launch_bounds__(kAcqThreads) acq_phase_grouped_kernel(const AcqGroupArgs g) { acq_phase_body(g.of(blockIdx.z)); }
+static __global__ void __launch_bounds__(kAcqMaxS) acq_decide_grouped_kernel(const AcqGroupArgs g) { acq_decide_body(g.of(blockIdx.x)); }
 
 }  // namespace dccn

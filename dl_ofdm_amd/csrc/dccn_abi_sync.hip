@@ -116,6 +116,171 @@ int capture_acquire_plan(const float* cap, long long n_samples, long long lo, in
     plan->lds = capture_acquire_lds(S, K, CP, n_pilot);
     return DCCN_OK;
 }
+
+// ---- the grouped entries: every link through the solo plan above, then what only a group can get wrong --------------------------
+// A link's byte ranges, outputs first: an output of one link must not meet ANY range of another (inputs may be shared).
+struct LinkRanges {
+    static constexpr int kMax = 8;
+    const void* p[kMax];
+    size_t n[kMax];
+    int count = 0, outputs = 0;
+    void out(const void* q, size_t bytes) { if (q) { p[count] = q; n[count++] = bytes; outputs = count; } }
+    void in(const void* q, size_t bytes) { if (q) { p[count] = q; n[count++] = bytes; } }
+};
+bool links_collide(const LinkRanges* r, int n_links) {
+    for (int i = 0; i < n_links; ++i)
+        for (int j = 0; j < n_links; ++j) {
+            if (i == j) continue;
+            for (int a = 0; a < r[i].outputs; ++a)
+                for (int b = 0; b < r[j].count; ++b)
+                    if (ranges_overlap(r[i].p[a], r[i].n[a], r[j].p[b], r[j].n[b])) return true;
+        }
+    return false;
+}
+// an optional output: given for every link or for none
+template <class Link, class T>
+bool mixed_nullability(const Link* links, int n_links, T* Link::*field) {
+    for (int i = 1; i < n_links; ++i)
+        if ((links[i].*field == nullptr) != (links[0].*field == nullptr)) return true;
+    return false;
+}
+bool group_count_ok(int n_links, const void* links) { return n_links >= 1 && n_links <= kMaxChains && links != nullptr; }
+
+struct FrameSyncGroupPlan {
+    FrameSyncGroupArgs args;
+    unsigned blocks;
+    size_t lds;
+    bool cfo;
+};
+int frame_sync_group_plan(int n_links, const dccn_frame_link* links, int frames, int S, int K, int CP, int W, int out_kin,
+                          FrameSyncGroupPlan* plan) {
+    if (!group_count_ok(n_links, links)) return DCCN_ERR_INVALID_ARG;
+    LinkRanges r[kMaxChains];
+    plan->args = FrameSyncGroupArgs{};
+    for (int i = 0; i < n_links; ++i) {
+        const dccn_frame_link& l = links[i];
+        FrameSyncPlan one;
+        DCCN_TRY(frame_sync_plan(l.x, frames, S, K, CP, W, out_kin, l.x_out, l.offset, l.metric, &one));
+        if ((reinterpret_cast<uintptr_t>(l.cfo) & 3u) != 0) return DCCN_ERR_INVALID_ARG;
+        plan->args.link[i] = FrameSyncLink{one.args.x, one.args.x_out, one.args.offset, one.args.metric, l.cfo};
+        if (i == 0) {
+            plan->args.frames = frames; plan->args.S = S; plan->args.K = K; plan->args.CP = CP; plan->args.W = W;
+            plan->args.crop = one.args.crop;
+            plan->blocks = one.blocks;
+            plan->lds = one.lds;
+        }
+        r[i].out(l.x_out, (size_t)frames * S * out_kin * 8);
+        r[i].out(l.offset, (size_t)frames * 4);
+        r[i].out(l.cfo, (size_t)frames * 4);
+        r[i].out(l.metric, (size_t)frames * (2 * W + 1) * 4);
+        r[i].in(l.x, (size_t)frames * S * (K + CP) * 8);
+    }
+    if (mixed_nullability(links, n_links, &dccn_frame_link::x_out) || mixed_nullability(links, n_links, &dccn_frame_link::cfo) ||
+        mixed_nullability(links, n_links, &dccn_frame_link::metric))
+        return DCCN_ERR_INVALID_ARG;
+    if (links_collide(r, n_links)) return DCCN_ERR_INVALID_ARG;
+    plan->cfo = links[0].cfo != nullptr;
+    return DCCN_OK;
+}
+
+struct CaptureSyncGroupPlan {
+    CaptureSyncGroupArgs args;
+    unsigned blocks;
+    size_t lds;
+    bool cfo;
+};
+int capture_sync_group_plan(int n_links, const dccn_capture_link* links, int frames, int S, int K, int CP, int W, int out_kin,
+                            CaptureSyncGroupPlan* plan) {
+    if (!group_count_ok(n_links, links)) return DCCN_ERR_INVALID_ARG;
+    LinkRanges r[kMaxChains];
+    plan->args = CaptureSyncGroupArgs{};
+    for (int i = 0; i < n_links; ++i) {
+        const dccn_capture_link& l = links[i];
+        CaptureSyncPlan one;
+        if (l.first_dev)
+            DCCN_TRY(capture_sync_at_plan(l.cap, l.n_samples, l.first_dev, l.lo, l.stride, frames, S, K, CP, W, out_kin, l.x_out,
+                                          l.offset, l.cfo, l.metric, &one));
+        else
+            DCCN_TRY(capture_sync_plan(l.cap, l.n_samples, l.first, l.stride, frames, S, K, CP, W, out_kin, l.x_out, l.offset, l.cfo,
+                                       l.metric, &one));
+        if ((reinterpret_cast<uintptr_t>(l.cfo) & 3u) != 0) return DCCN_ERR_INVALID_ARG;
+        plan->args.link[i] = CaptureSyncLink{one.args.cap, l.first_dev ? 0 : l.first, one.args.stride, l.first_dev,
+                                             l.first_dev ? l.lo : 0, one.args.x_out, one.args.offset, one.args.metric, one.args.cfo};
+        if (i == 0) {
+            plan->args.frames = frames; plan->args.S = S; plan->args.K = K; plan->args.CP = CP; plan->args.W = W;
+            plan->args.crop = one.args.crop;
+            plan->blocks = one.blocks;
+            plan->lds = one.lds;
+        }
+        r[i].out(l.x_out, (size_t)frames * S * out_kin * 8);
+        r[i].out(l.offset, (size_t)frames * 4);
+        r[i].out(l.cfo, (size_t)frames * 4);
+        r[i].out(l.metric, (size_t)frames * (2 * W + 1) * 4);
+        r[i].in(l.cap, (size_t)l.n_samples * 8);
+        r[i].in(l.first_dev, 8);
+    }
+    if (mixed_nullability(links, n_links, &dccn_capture_link::x_out) || mixed_nullability(links, n_links, &dccn_capture_link::cfo) ||
+        mixed_nullability(links, n_links, &dccn_capture_link::metric))
+        return DCCN_ERR_INVALID_ARG;
+    if (links_collide(r, n_links)) return DCCN_ERR_INVALID_ARG;
+    plan->cfo = links[0].cfo != nullptr;
+    return DCCN_OK;
+}
+
+struct CaptureAcquireGroupPlan {
+    AcqGroupArgs args;
+    unsigned sum_blocks;
+    size_t lds;
+};
+int capture_acquire_group_plan(int n_links, const dccn_acquire_link* links, int J, int S, int K, int CP, int n_pilot,
+                               CaptureAcquireGroupPlan* plan) {
+    if (!group_count_ok(n_links, links)) return DCCN_ERR_INVALID_ARG;
+    LinkRanges r[kMaxChains];
+    plan->args = AcqGroupArgs{};
+    for (int i = 0; i < n_links; ++i) {
+        const dccn_acquire_link& l = links[i];
+        CaptureAcquirePlan one;
+        DCCN_TRY(capture_acquire_plan(l.cap, l.n_samples, l.lo, J, S, K, CP, l.pilot_sc, n_pilot, l.first_out, l.cfo_out, l.sym_metric,
+                                      l.phase_metric, l.workspace, l.workspace_bytes, &one));
+        const AcqArgs& a = one.args;
+        plan->args.link[i] = AcqLink{a.cap, a.lo, a.pilot_sc, a.pe, a.partial, a.rhat, a.first_out, a.cfo_out, a.sym_metric,
+                                     a.phase_metric};
+        if (i == 0) {
+            plan->args.S = S; plan->args.K = K; plan->args.CP = CP; plan->args.J = J; plan->args.n_pilot = n_pilot;
+            plan->sum_blocks = one.sum_blocks;
+            plan->lds = one.lds;
+        }
+        r[i].out(l.first_out, 8);
+        r[i].out(l.cfo_out, 4);
+        r[i].out(l.sym_metric, (size_t)(K + CP) * 4);
+        r[i].out(l.phase_metric, (size_t)S * 4);
+        r[i].out(l.workspace, capture_acquire_layout(S, K, CP, J).total);
+        r[i].in(l.cap, (size_t)l.n_samples * 8);
+        r[i].in(l.pilot_sc, (size_t)n_pilot * 4);
+    }
+    if (mixed_nullability(links, n_links, &dccn_acquire_link::sym_metric) ||
+        mixed_nullability(links, n_links, &dccn_acquire_link::phase_metric))
+        return DCCN_ERR_INVALID_ARG;
+    if (links_collide(r, n_links)) return DCCN_ERR_INVALID_ARG;
+    return DCCN_OK;
+}
+
+template <bool CFO>
+int frame_sync_group_launch(const FrameSyncGroupPlan& plan, int n_links, dccn_stream_t stream) {
+    DCCN_TRY(set_max_dynamic_smem((const void*)frame_sync_grouped_kernel<CFO>, plan.lds));
+    hipLaunchKernelGGL(frame_sync_grouped_kernel<CFO>, dim3(plan.blocks, (unsigned)n_links), dim3(kSyncWaves * kSyncLanes), plan.lds,
+                       (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+template <bool CFO>
+int capture_sync_group_launch(const CaptureSyncGroupPlan& plan, int n_links, dccn_stream_t stream) {
+    DCCN_TRY(set_max_dynamic_smem((const void*)capture_sync_grouped_kernel<CFO>, plan.lds));
+    hipLaunchKernelGGL(capture_sync_grouped_kernel<CFO>, dim3(plan.blocks, (unsigned)n_links), dim3(kSyncWaves * kSyncLanes),
+                       plan.lds, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -186,6 +351,40 @@ int dccn_capture_acquire(const float* cap, long long n_samples, long long lo, in
     hipLaunchKernelGGL(acq_phase_kernel, dim3((unsigned)S, (unsigned)J), dim3(kAcqThreads), plan.lds, (hipStream_t)stream, plan.args);
     DCCN_LAUNCH_CHECK();
     hipLaunchKernelGGL(acq_decide_kernel, dim3(1), dim3(kAcqMaxS), 0, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+// ---- several links per launch: the link table is the call's own, so inside a ChainScope these refuse like the solo entries ----
+int dccn_frame_sync_grouped(int n_links, const dccn_frame_link* links, int frames, int S, int K, int CP, int W, int out_kin,
+                            dccn_stream_t stream) {
+    FrameSyncGroupPlan plan;
+    DCCN_TRY(frame_sync_group_plan(n_links, links, frames, S, K, CP, W, out_kin, &plan));
+    DCCN_NO_CHAINS();
+    return plan.cfo ? frame_sync_group_launch<true>(plan, n_links, stream) : frame_sync_group_launch<false>(plan, n_links, stream);
+}
+
+int dccn_capture_sync_grouped(int n_links, const dccn_capture_link* links, int frames, int S, int K, int CP, int W, int out_kin,
+                              dccn_stream_t stream) {
+    CaptureSyncGroupPlan plan;
+    DCCN_TRY(capture_sync_group_plan(n_links, links, frames, S, K, CP, W, out_kin, &plan));
+    DCCN_NO_CHAINS();
+    return plan.cfo ? capture_sync_group_launch<true>(plan, n_links, stream) : capture_sync_group_launch<false>(plan, n_links, stream);
+}
+
+int dccn_capture_acquire_grouped(int n_links, const dccn_acquire_link* links, int J, int S, int K, int CP, int n_pilot,
+                                 dccn_stream_t stream) {
+    CaptureAcquireGroupPlan plan;
+    DCCN_TRY(capture_acquire_group_plan(n_links, links, J, S, K, CP, n_pilot, &plan));
+    DCCN_NO_CHAINS();
+    const unsigned G = (unsigned)n_links;
+    hipLaunchKernelGGL(acq_symbol_sums_grouped_kernel, dim3(plan.sum_blocks, G), dim3(kAcqSumThreads), 0, (hipStream_t)stream,
+                       plan.args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(acq_phase_grouped_kernel, dim3((unsigned)S, (unsigned)J, G), dim3(kAcqThreads), plan.lds, (hipStream_t)stream,
+                       plan.args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(acq_decide_grouped_kernel, dim3(G), dim3(kAcqMaxS), 0, (hipStream_t)stream, plan.args);
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
 }

@@ -19,6 +19,9 @@
 // samples around the frame are its neighbours in the air), and out[n] = c[b + offset + n].  The sums, their order, the stores and
 // the derotation are stated once (sync_estimate, sync_store, sync_cfo_store); the two families differ in the index mapping alone
 // (SyncCircular, SyncLinear: where a sample of the frame sits in the wave's LDS region).
+//
+// dccn_frame_sync_grouped / dccn_capture_sync_grouped (at the end) run frame_sync_body / capture_sync_body for up to kMaxChains
+// links in one launch: a by-value table of per-link pointers, the link index on blockIdx.y.
 #pragma once
 #include "common.h"
 
@@ -317,6 +320,55 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_a
     const long long hi = a.lo + (long long)a.s.S * (a.s.K + a.s.CP) - 1;
     const long long got = a.first_dev[0];
     capture_sync_body<CFO>(a.s, got < a.lo ? a.lo : (got > hi ? hi : got));
+}
+
+// ---- several links per launch (dccn_frame_sync_grouped, dccn_capture_sync_grouped) ----------------------------------------------
+// Each link has its own frames (or capture, start and stride) and outputs; frames, the shape, W and out_kin are the call's.  The
+// table travels by value in the kernel arguments and is indexed by blockIdx.y, a block-uniform value (scalar loads, as ChainOffs
+// is read); blockIdx.x stays what the bodies take it for, so a link's blocks are the solo launch's.
+struct FrameSyncLink {
+    const float* x;
+    float* x_out;
+    int32_t* offset;
+    float* metric;
+    float* cfo;
+};
+struct FrameSyncGroupArgs {
+    FrameSyncLink link[kMaxChains];
+    int frames, S, K, CP, W, crop;
+};
+template <bool CFO>
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) frame_sync_grouped_kernel(const FrameSyncGroupArgs g) {
+    const FrameSyncLink& l = g.link[blockIdx.y];
+    frame_sync_body<CFO>(FrameSyncArgs{l.x, l.x_out, l.offset, l.metric, g.frames, g.S, g.K, g.CP, g.W, g.crop}, l.cfo);
+}
+
+struct CaptureSyncLink {
+    const float* cap;
+    long long first, stride;
+    const long long* first_dev; // nullable [1]: the start is read here and kept inside [lo, lo + T - 1] (capture_sync_at_kernel)
+    long long lo;
+    float* x_out;
+    int32_t* offset;
+    float* metric;
+    float* cfo;
+};
+struct CaptureSyncGroupArgs {
+    CaptureSyncLink link[kMaxChains];
+    int frames, S, K, CP, W, crop;
+};
+template <bool CFO>
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_grouped_kernel(const CaptureSyncGroupArgs g) {
+    const CaptureSyncLink& l = g.link[blockIdx.y];
+    long long first = l.first;
+    if (l.first_dev) {                                                      // (uniform over the block)
+        const long long hi = l.lo + (long long)g.S * (g.K + g.CP) - 1;
+        const long long got = l.first_dev[0];
+        first = got < l.lo ? l.lo : (got > hi ? hi : got);
+    }
+    capture_sync_body<CFO>(CaptureSyncArgs{l.cap, first, l.stride, l.x_out, l.offset, l.metric, l.cfo, g.frames, g.S, g.K, g.CP, g.W,
+                                           g.crop},
+                           first);
 }
 
 }  // namespace dccn

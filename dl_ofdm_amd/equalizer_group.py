@@ -266,6 +266,8 @@ class ChainReceiveGroup:
         group = ChainReceiveGroup([flags_bpsk, flags_16qam], [rx_bpsk, rx_16qam], batch=73, want_llr=True)
         receiver_mp.load_checkpoint(path, group.chains[0].tr)          # or .tr.load_params(...): the trained equaliser
         results = group.receive([frames_bpsk, frames_16qam])           # one ReceiveResult per chain
+        results = group.receive(device_frames, sync=3, cfo=True)       # + one alignment launch for all chains
+        results = group.receive_capture(captures, acquire=16, los=3)   # acquisition (3 launches) + cut (1) for all chains
 
     ``.chains[i].pl.out_eq`` / ``.chest`` / ``.snr_db`` hold what the chain's ``eval_step`` writes for the same frames."""
 
@@ -290,6 +292,7 @@ class ChainReceiveGroup:
         self._bufs = _ptr_array([c.pl.buffers for c in self.chains])
         self.want_llr, self.want_prob = bool(want_llr), bool(want_prob)
         self._outs = {}                                        # (llr, prob) asked for -> (the chains' dccn_receive_out, their table)
+        self._stages = {}                                      # the group's resident front-end stages (sync.py: the *Group classes)
 
     def _out_table(self, want_llr: bool, want_prob: bool):
         key = (want_llr, want_prob)
@@ -298,23 +301,114 @@ class ChainReceiveGroup:
             self._outs[key] = (structs, _ptr_array(structs))
         return self._outs[key][1]
 
-    def receive(self, xs: Sequence, want_llr: Optional[bool] = None, want_prob: Optional[bool] = None) -> list:
-        """``xs[i]``: chain i's frames ``[batch, S, K + CP, 2]`` (host array or device tensor; ``None``: what ``.chains[i].pl.x``
-        holds).  ``want_llr`` / ``want_prob``: as the group was built (default), or ``False`` to leave that output out of this
-        call.  Returns one :class:`~dl_ofdm_amd.receive.ReceiveResult` per chain -- the chains' resident buffers: the next
-        call overwrites them."""
-        from .receive import ReceiveResult
-        if len(xs) != len(self.chains):
-            raise ValueError("one batch of frames per chain")
+    def _wants(self, want_llr: Optional[bool], want_prob: Optional[bool]):
         want_llr = self.want_llr if want_llr is None else bool(want_llr)
         want_prob = self.want_prob if want_prob is None else bool(want_prob)
         if (want_llr and not self.want_llr) or (want_prob and not self.want_prob):
             raise ValueError("llr / prob were not set aside when the group was built (want_llr / want_prob)")
-        for c, x in zip(self.chains, xs):
-            if x is not None:
-                c.pl.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(c.pl.x.shape), non_blocking=True)
+        return want_llr, want_prob
+
+    def _step(self, want_llr: bool, want_prob: bool) -> None:
+        """the grouped receive step on what every chain's ``pl.x`` holds"""
+        for c in self.chains:
             c.pl._ahead()[c.pl.ws.data_ptr()] = None           # (the step normalises into the chain's workspace)
         st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         check(self.lib.dccn_eq_receive_step_grouped(len(self.chains), self._shapes, self._bufs, self._out_table(want_llr, want_prob), st),
               "dccn_eq_receive_step_grouped")
-        return [ReceiveResult(c.packed, c.llr if want_llr else None, c.prob if want_prob else None, c.D, c.nbits) for c in self.chains]
+
+    def _frame_shape(self):
+        c = self.chains[0]
+        return int(c.F.nsymbol), int(c.o.K), int(c.o.CP)
+
+    def _stage(self, kind: str, cls, W: int, cfo: bool):
+        """the resident front-end stage of this group: FrameSyncGroup / CaptureSyncGroup, writing the chains' ``pl.x``"""
+        key = (kind, int(W), bool(cfo))
+        if key not in self._stages:
+            S, K, CP = self._frame_shape()
+            self._stages[key] = cls(S, K, CP, int(W), self.batch, len(self.chains), self.device, want_metric=False, cfo=bool(cfo))
+        return self._stages[key]
+
+    def receive(self, xs: Sequence, want_llr: Optional[bool] = None, want_prob: Optional[bool] = None, sync: int = 0,
+                cfo: bool = False) -> list:
+        """``xs[i]``: chain i's frames ``[batch, S, K + CP, 2]`` (host array or device tensor; ``None``: what ``.chains[i].pl.x``
+        holds).  ``want_llr`` / ``want_prob``: as the group was built (default), or ``False`` to leave that output out of this
+        call.  Returns one :class:`~dl_ofdm_amd.receive.ReceiveResult` per chain -- the chains' resident buffers: the next
+        call overwrites them.
+
+        ``sync = W > 0``: as ``EqualizerTrainer.receive(x, sync=W)`` per chain -- every ``xs[i]`` is a device tensor of frames
+        that may sit up to ``W`` samples off the FFT window, and ONE alignment launch for all chains
+        (:class:`~dl_ofdm_amd.sync.FrameSyncGroup`) writes each chain's rotated frames into its ``pl.x`` in place of the
+        per-chain copies; ``result.offset``.  ``cfo=True`` (needs ``sync > 0``): that launch also takes each frame's
+        carrier-frequency offset out; ``result.cfo``."""
+        from .receive import ReceiveResult
+        from .sync import FrameSyncGroup
+        if len(xs) != len(self.chains):
+            raise ValueError("one batch of frames per chain")
+        want_llr, want_prob = self._wants(want_llr, want_prob)
+        if cfo and not sync:
+            raise _lib.DccnError("receive(cfo=True) needs sync = W > 0: the offset is read off the timing correlation")
+        offsets = ests = [None] * len(self.chains)
+        if sync:
+            if not all(isinstance(x, torch.Tensor) and x.device.type == "cuda" for x in xs):
+                raise _lib.DccnError("receive(sync=W) takes one device tensor [batch, S, K + CP, 2] per chain")
+            fs = self._stage("frames", FrameSyncGroup, sync, cfo)
+            _, offsets = fs.run(xs, outs=[c.pl.x for c in self.chains])
+            ests = fs.cfo if cfo else ests
+        else:
+            for c, x in zip(self.chains, xs):
+                if x is not None:
+                    c.pl.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(c.pl.x.shape), non_blocking=True)
+        self._step(want_llr, want_prob)
+        return [ReceiveResult(c.packed, c.llr if want_llr else None, c.prob if want_prob else None, c.D, c.nbits, offsets[i], ests[i])
+                for i, c in enumerate(self.chains)]
+
+    def receive_capture(self, caps: Sequence, firsts=None, strides=None, sync: int = 3, cfo: bool = False, acquire: int = 0, los=0,
+                        want_llr: Optional[bool] = None, want_prob: Optional[bool] = None) -> list:
+        """One round on ``batch`` frames per chain that still sit inside contiguous captures: ``caps[i]`` is chain i's capture
+        (device tensor ``float32 [n, 2]``; two chains may share one), as ``EqualizerTrainer.receive_capture(caps[i], firsts[i],
+        strides[i], sync, cfo, frames=batch, lo=los[i])`` per chain.  ``firsts[i]``: an integer, or a device ``int64`` tensor of
+        one element with ``los[i]``; the two mix.  ONE launch (:class:`~dl_ofdm_amd.sync.CaptureSyncGroup`) cuts every chain's
+        frames at their estimated starts into its ``pl.x``, then the grouped step runs.
+
+        ``firsts=None, acquire=J, los=...``: acquisition for all chains (:class:`~dl_ofdm_amd.sync.CaptureAcquireGroup`, three
+        launches, the pilot cells are each chain's ``pilotSc``) leaves every chain's start inside ``[los[i], los[i] + T)`` on the
+        device, where the cut reads it: four front-end launches for the whole group, no host round trip.  Each result carries
+        ``offset``, ``cfo``, ``first`` and ``acquired_cfo`` as the solo call returns them."""
+        from .receive import ReceiveResult
+        from .sync import CaptureAcquireGroup, CaptureSyncGroup, _per_link
+        n = len(self.chains)
+        if len(caps) != n:
+            raise ValueError("one capture per chain")
+        want_llr, want_prob = self._wants(want_llr, want_prob)
+        W = int(sync)
+        if W <= 0:
+            raise _lib.DccnError("receive_capture needs sync = W > 0")
+        if not all(isinstance(c, torch.Tensor) and c.device.type == "cuda" and c.dim() == 2 for c in caps):
+            raise _lib.DccnError("receive_capture takes one device tensor [n, 2] per chain")
+        los = _per_link(los, n, "receive_capture(los)")
+        strides = _per_link(strides, n, "receive_capture(strides)")
+        acq_cfo = [None] * n
+        if firsts is not None:
+            if acquire:
+                raise _lib.DccnError("receive_capture: give `firsts` or `acquire`, not both")
+            if not isinstance(firsts, (list, tuple)) or len(firsts) != n:
+                raise ValueError("receive_capture(firsts): one entry per chain (%d)" % n)
+            firsts = list(firsts)
+        else:
+            J = int(acquire)
+            if J <= 0:
+                raise _lib.DccnError("receive_capture(firsts=None) needs acquire = J > 0, the number of frames acquisition may use")
+            key = ("acquire", J)
+            if key not in self._stages:
+                S, K, CP = self._frame_shape()
+                self._stages[key] = CaptureAcquireGroup(S, K, CP, [np.asarray(c.o.pilotSc) for c in self.chains], J, n, self.device)
+            acq = self._stages[key]
+        cs = self._stage("capture", CaptureSyncGroup, W, cfo)
+        if firsts is None:
+            firsts = acq.run(caps, los)
+            acq_cfo = acq.cfo
+        _, offsets = cs.run(caps, firsts, strides, outs=[c.pl.x for c in self.chains], los=los)
+        self._step(want_llr, want_prob)
+        return [ReceiveResult(c.packed, c.llr if want_llr else None, c.prob if want_prob else None, c.D, c.nbits, offsets[i],
+                              cs.cfo[i] if cfo else None, firsts[i] if isinstance(firsts[i], torch.Tensor) else None, acq_cfo[i])
+                for i, c in enumerate(self.chains)]

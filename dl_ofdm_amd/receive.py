@@ -322,12 +322,20 @@ def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, syn
                          first if on_device else None, est0)
 
 
-def group_receive(group, xs) -> list:
+def group_receive(group, xs, sync: int = 0, cfo: bool = False) -> list:
     """Several links' chains in ONE launch sequence (``dccn_eq_receive_step_grouped``): ``group`` is a
     :class:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup`, ``xs`` one ``[batch, S, K + CP, 2]`` batch of frames per chain.
     One :class:`ReceiveResult` per chain, bit for bit what :func:`chain_receive` returns for that chain alone.
 
-    The grouped call has no ``sync`` argument: a caller whose links need timing alignment keeps one
-    :class:`~dl_ofdm_amd.sync.FrameSync` per link (``cfo=True`` where the link's carrier-frequency offset is to go as well) and
-    aligns each link's frames in front of this call."""
-    return group.receive(xs)
+    ``sync = W > 0`` (and ``cfo=True``) as :func:`chain_receive`: ``xs`` are device tensors, and one alignment launch for all
+    links (``dccn_frame_sync_grouped``, :class:`~dl_ofdm_amd.sync.FrameSyncGroup`) writes every chain's frames in place of the
+    per-chain copies; ``result.offset`` / ``result.cfo`` per chain."""
+    return group.receive(xs, sync=sync, cfo=cfo)
+
+
+def group_receive_capture(group, caps, firsts=None, strides=None, sync: int = 3, cfo: bool = False, acquire: int = 0, los=0) -> list:
+    """:func:`chain_receive_capture` for every chain of a :class:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup` at once
+    (``frames`` is the group's batch): one capture per chain, acquisition (``firsts=None, acquire=J``: three launches for all
+    links) and the cut (one launch for all links) in front of the grouped step.  ``ChainReceiveGroup.receive_capture`` says the
+    rest; one :class:`ReceiveResult` per chain, bit for bit what :func:`chain_receive_capture` returns for that chain alone."""
+    return group.receive_capture(caps, firsts, strides, sync=sync, cfo=cfo, acquire=acquire, los=los)

@@ -19,6 +19,10 @@ its estimated start -- the samples the alignment brings in are the frame's neigh
 (``dccn_capture_acquire``) finds the ``first`` that stage needs -- anywhere in a frame period, not within ``W`` -- and leaves it on
 the device, where ``CaptureSync.run(cap, first_tensor, lo=...)`` reads it.
 
+:class:`FrameSyncGroup`, :class:`CaptureSyncGroup` and :class:`CaptureAcquireGroup` run the same stages for several links at once
+(``dccn_frame_sync_grouped``, ``dccn_capture_sync_grouped``, ``dccn_capture_acquire_grouped``: one launch each, acquisition three), the
+front end of :class:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup`; link i's results are bit for bit the solo class's.
+
 There is no CPU or PyTorch fallback: an unsupported shape or a tensor that is not on the GPU raises :class:`DccnError`.
 """
 from __future__ import annotations
@@ -244,4 +248,208 @@ class CaptureAcquire:
                                             self.pilot_sc.data_ptr(), self.n_pilot, self.first.data_ptr(), self.cfo.data_ptr(),
                                             self.sym_metric.data_ptr(), self.phase_metric.data_ptr(), self.ws.data_ptr(),
                                             int(self.ws.numel()), stream), "dccn_capture_acquire")
+        return self.first
+
+
+# ---- the same stages for several links per launch (include/dccn.h "the receive front end for several links") -------------------
+def _group_size(lib, n_links: int, what: str) -> int:
+    gmax = int(lib.dccn_chain_group_max())
+    if not (1 <= int(n_links) <= gmax):
+        raise ValueError("%s: 1..%d links per group" % (what, gmax))
+    return int(n_links)
+
+
+def _per_link(v, n: int, what: str) -> list:
+    """one entry per link: a scalar (or ``None``) serves every link, a list or tuple must have ``n`` entries"""
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise ValueError("%s: one entry per link (%d), got %d" % (what, n, len(v)))
+        return list(v)
+    return [v] * n
+
+
+def _device_capture(cap, what: str) -> torch.Tensor:
+    if not isinstance(cap, torch.Tensor) or cap.device.type != "cuda":
+        raise DccnError("%s takes device tensors; there is no CPU fallback" % what)
+    if cap.dtype != torch.float32 or cap.dim() != 2 or cap.shape[1] != 2 or not cap.is_contiguous():
+        raise DccnError("%s: a capture must be a contiguous float32 [n, 2] tensor, got %s %r" % (what, cap.dtype, tuple(cap.shape)))
+    return cap
+
+
+class _SyncGroupBase:
+    """what :class:`FrameSyncGroup` and :class:`CaptureSyncGroup` share: the shape, per-link resident ``offset`` / ``cfo`` /
+    ``metric`` (lists of tensors, entry i as the solo class keeps it for link i) and the output buffers"""
+
+    def __init__(self, supported, S, K, CP, W, frames, n_links, device, out_kin, want_metric, cfo):
+        self.lib = _lib.load()
+        name = type(self).__name__
+        self.n_links = _group_size(self.lib, n_links, name)
+        self.S, self.K, self.CP, self.W, self.frames = int(S), int(K), int(CP), int(W), int(frames)
+        self.T = self.S * (self.K + self.CP)
+        self.out_kin = self.K + self.CP if out_kin is None else int(out_kin)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise DccnError("%s needs a CUDA (ROCm) device; there is no CPU fallback" % name)
+        if not getattr(self.lib, supported)(self.S, self.K, self.CP, self.W):
+            raise DccnError("%s refused S=%d K=%d CP=%d W=%d" % (supported, self.S, self.K, self.CP, self.W))
+        if self.out_kin not in (self.K + self.CP, self.K) or self.frames <= 0:
+            raise DccnError("%s: out_kin must be K + CP or K and frames positive (got out_kin=%d, frames=%d)"
+                            % (name, self.out_kin, self.frames))
+        n, dev = self.n_links, self.device
+        self.offset = [torch.zeros(self.frames, dtype=torch.int32, device=dev) for _ in range(n)]
+        self.metric = ([torch.zeros(self.frames, 2 * self.W + 1, dtype=torch.float32, device=dev) for _ in range(n)]
+                       if want_metric else None)
+        self.cfo = [torch.zeros(self.frames, dtype=torch.float32, device=dev) for _ in range(n)] if cfo else None
+        self.out = None         # allocated by the first run() that is not given destinations
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _outs(self, outs) -> list:
+        want = (self.frames, self.S, self.out_kin, 2)
+        if outs is None:
+            if self.out is None:
+                self.out = [torch.empty(*want, dtype=torch.float32, device=self.device) for _ in range(self.n_links)]
+            return self.out
+        outs = _per_link(list(outs), self.n_links, type(self).__name__ + ".run(outs)")
+        for o in outs:
+            if (not isinstance(o, torch.Tensor) or o.device.type != "cuda" or o.dtype != torch.float32 or tuple(o.shape) != want
+                    or not o.is_contiguous()):
+                raise DccnError("%s.run: every out must be a contiguous float32 %r device tensor" % (type(self).__name__, want))
+        return outs
+
+    def _opt(self, tensors, i):
+        return None if tensors is None else tensors[i].data_ptr()
+
+
+class FrameSyncGroup(_SyncGroupBase):
+    """:class:`FrameSync` for up to ``dccn_chain_group_max()`` links in ONE launch (``dccn_frame_sync_grouped``):
+    ``run(xs) -> (aligned, offsets)``, lists with one entry per link, entry i bit for bit what ``FrameSync.run(xs[i])`` gives.
+    ``offset``, ``metric``, ``cfo`` and the output buffers are resident per link (lists of tensors)."""
+
+    def __init__(self, S: int, K: int, CP: int, W: int, frames: int, n_links: int, device="cuda", out_kin: Optional[int] = None,
+                 want_metric: bool = True, cfo: bool = False):
+        super().__init__("dccn_frame_sync_supported", S, K, CP, W, frames, n_links, device, out_kin, want_metric, cfo)
+        self._table = (_lib.FrameLink * self.n_links)()
+
+    def _launch(self, xs, outs) -> None:
+        xs = _per_link(list(xs), self.n_links, "FrameSyncGroup.run(xs)")
+        want = (self.frames, self.S, self.K + self.CP, 2)
+        for x in xs:
+            if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+                raise DccnError("FrameSyncGroup.run takes device tensors; there is no CPU fallback")
+            if x.dtype != torch.float32 or tuple(x.shape) != want or not x.is_contiguous():
+                raise DccnError("FrameSyncGroup.run: every x must be a contiguous float32 %r tensor, got %s %r"
+                                % (want, x.dtype, tuple(x.shape)))
+        for i, x in enumerate(xs):
+            self._table[i] = _lib.FrameLink(x.data_ptr(), None if outs is None else outs[i].data_ptr(), self.offset[i].data_ptr(),
+                                            self._opt(self.cfo, i), self._opt(self.metric, i))
+        check(self.lib.dccn_frame_sync_grouped(self.n_links, self._table, self.frames, self.S, self.K, self.CP, self.W,
+                                               self.out_kin, self._stream()), "dccn_frame_sync_grouped")
+
+    def run(self, xs, outs=None):
+        """One launch on the current stream.  ``outs``: one destination per link (``None``: this object's own buffers); no
+        destination may overlap another link's frames or outputs."""
+        outs = self._outs(outs)
+        self._launch(xs, outs)
+        return outs, self.offset
+
+    def offsets(self, xs):
+        """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``."""
+        self._launch(xs, None)
+        return self.offset
+
+
+class CaptureSyncGroup(_SyncGroupBase):
+    """:class:`CaptureSync` for up to ``dccn_chain_group_max()`` links in ONE launch (``dccn_capture_sync_grouped``):
+    ``run(caps, firsts) -> (frames_out, offsets)``, lists with one entry per link.  ``caps[i]``: link i's capture (two links may
+    share one); ``firsts[i]``: an integer, or a device ``int64`` tensor of one element together with ``los[i]`` (what
+    :class:`CaptureAcquireGroup` left there) -- known and acquired starts mix in one call; ``strides[i]``: ``None`` = ``T``.
+    Entry i of every result is bit for bit what ``CaptureSync.run(caps[i], firsts[i], strides[i], lo=los[i])`` gives."""
+
+    def __init__(self, S: int, K: int, CP: int, W: int, frames: int, n_links: int, device="cuda", out_kin: Optional[int] = None,
+                 want_metric: bool = True, cfo: bool = False):
+        super().__init__("dccn_capture_sync_supported", S, K, CP, W, frames, n_links, device, out_kin, want_metric, cfo)
+        self._table = (_lib.CaptureLink * self.n_links)()
+
+    def _launch(self, caps, firsts, strides, outs, los) -> None:
+        n = self.n_links
+        caps = [_device_capture(c, "CaptureSyncGroup") for c in _per_link(list(caps), n, "CaptureSyncGroup.run(caps)")]
+        firsts = _per_link(list(firsts), n, "CaptureSyncGroup.run(firsts)")
+        strides = _per_link(strides, n, "CaptureSyncGroup.run(strides)")
+        los = _per_link(los, n, "CaptureSyncGroup.run(los)")
+        for i, (cap, first) in enumerate(zip(caps, firsts)):
+            if isinstance(first, torch.Tensor):
+                if los[i] is None:
+                    raise DccnError("CaptureSyncGroup: a device tensor `first` needs los[i], the origin of the range [lo, lo + T) "
+                                    "it lies in")
+                if first.device != cap.device or first.dtype != torch.int64 or first.numel() != 1 or not first.is_contiguous():
+                    raise DccnError("CaptureSyncGroup: a device `first` must be an int64 tensor of one element on the capture's device")
+        for i, (cap, first) in enumerate(zip(caps, firsts)):
+            on_dev = isinstance(first, torch.Tensor)
+            self._table[i] = _lib.CaptureLink(cap.data_ptr(), int(cap.shape[0]), 0 if on_dev else int(first),
+                                              first.data_ptr() if on_dev else None, int(los[i]) if on_dev else 0,
+                                              self.T if strides[i] is None else int(strides[i]),
+                                              None if outs is None else outs[i].data_ptr(), self.offset[i].data_ptr(),
+                                              self._opt(self.cfo, i), self._opt(self.metric, i))
+        check(self.lib.dccn_capture_sync_grouped(n, self._table, self.frames, self.S, self.K, self.CP, self.W, self.out_kin,
+                                                 self._stream()), "dccn_capture_sync_grouped")
+
+    def run(self, caps, firsts, strides=None, outs=None, los=None):
+        """One launch on the current stream.  ``strides`` / ``los``: one value for every link or one per link."""
+        outs = self._outs(outs)
+        self._launch(caps, firsts, strides, outs, los)
+        return outs, self.offset
+
+    def offsets(self, caps, firsts, strides=None, los=None):
+        """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``."""
+        self._launch(caps, firsts, strides, None, los)
+        return self.offset
+
+
+class CaptureAcquireGroup:
+    """:class:`CaptureAcquire` for up to ``dccn_chain_group_max()`` links in THREE launches (``dccn_capture_acquire_grouped``):
+    ``run(caps, los) -> firsts``, one device ``int64`` tensor of one element per link -- what :meth:`CaptureSyncGroup.run` takes
+    as ``firsts`` together with the same ``los``.  ``pilot_sc``: the pilot cells of every link, or a list of one array per link
+    (of one length).  ``first``, ``cfo``, ``sym_metric``, ``phase_metric`` and the workspaces are resident per link (lists)."""
+
+    def __init__(self, S: int, K: int, CP: int, pilot_sc, J: int, n_links: int, device="cuda"):
+        self.lib = _lib.load()
+        self.n_links = n = _group_size(self.lib, n_links, "CaptureAcquireGroup")
+        self.S, self.K, self.CP, self.J = int(S), int(K), int(CP), int(J)
+        self.T = self.S * (self.K + self.CP)
+        self.device = dev = torch.device(device)
+        if dev.type != "cuda":
+            raise DccnError("CaptureAcquireGroup needs a CUDA (ROCm) device; there is no CPU fallback")
+        per_link = isinstance(pilot_sc, (list, tuple)) and len(pilot_sc) > 0 and hasattr(pilot_sc[0], "__len__")
+        scs = [torch.as_tensor(sc).reshape(-1).to(torch.int32) for sc in (_per_link(list(pilot_sc), n, "pilot_sc") if per_link
+                                                                          else [pilot_sc])]
+        self.n_pilot = int(scs[0].numel())
+        if any(int(sc.numel()) != self.n_pilot for sc in scs):
+            raise DccnError("CaptureAcquireGroup: the links' pilot cells must be of one length (n_pilot is the call's)")
+        if not self.lib.dccn_capture_acquire_supported(self.S, self.K, self.CP, self.n_pilot, self.J):
+            raise DccnError("dccn_capture_acquire_supported refused S=%d K=%d CP=%d n_pilot=%d J=%d"
+                            % (self.S, self.K, self.CP, self.n_pilot, self.J))
+        scs = [sc.to(dev).contiguous() for sc in scs]
+        self.pilot_sc = scs if per_link else scs * n
+        self.first = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(n)]
+        self.cfo = [torch.zeros(1, dtype=torch.float32, device=dev) for _ in range(n)]
+        self.sym_metric = [torch.zeros(self.K + self.CP, dtype=torch.float32, device=dev) for _ in range(n)]
+        self.phase_metric = [torch.zeros(self.S, dtype=torch.float32, device=dev) for _ in range(n)]
+        nws = int(self.lib.dccn_capture_acquire_workspace_size(self.S, self.K, self.CP, self.n_pilot, self.J))
+        self.ws = [torch.empty(nws, dtype=torch.uint8, device=dev) for _ in range(n)]
+        self._table = (_lib.AcquireLink * n)()
+
+    def run(self, caps, los=0):
+        """Three launches on the current stream; returns ``self.first``."""
+        n = self.n_links
+        caps = [_device_capture(c, "CaptureAcquireGroup") for c in _per_link(list(caps), n, "CaptureAcquireGroup.run(caps)")]
+        los = _per_link(los, n, "CaptureAcquireGroup.run(los)")
+        for i, cap in enumerate(caps):
+            self._table[i] = _lib.AcquireLink(cap.data_ptr(), int(cap.shape[0]), int(los[i]), self.pilot_sc[i].data_ptr(),
+                                              self.first[i].data_ptr(), self.cfo[i].data_ptr(), self.sym_metric[i].data_ptr(),
+                                              self.phase_metric[i].data_ptr(), self.ws[i].data_ptr(), int(self.ws[i].numel()))
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        check(self.lib.dccn_capture_acquire_grouped(n, self._table, self.J, self.S, self.K, self.CP, self.n_pilot, stream),
+              "dccn_capture_acquire_grouped")
         return self.first

@@ -1074,7 +1074,7 @@ int dccn_frame_sync(const float* x, int frames, int S, int K, int CP, int W, int
  * not fault: its offset stays inside [-W, W] and its cfo is whatever atan2f returns.  One launch, no workspace, no atomics, the
  * sums and the phase in a fixed order (two runs give the same bits).
  * Refused with DCCN_ERR_INVALID_ARG before anything is launched wherever dccn_frame_sync refuses, and for cfo NULL; inside a
- * chain group DCCN_ERR_UNSUPPORTED (the launch carries no chain table). */
+ * chain group DCCN_ERR_UNSUPPORTED (the launch carries no chain table; several links per launch: dccn_frame_sync_grouped below). */
 int dccn_frame_sync_cfo(const float* x, int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset,
                         float* cfo, float* metric, dccn_stream_t stream);
 /* The same estimator on frames that still sit inside ONE CONTIGUOUS CAPTURE cap [n_samples, 2] (what a front end hands over):
@@ -1141,12 +1141,74 @@ int dccn_capture_sync_at(const float* cap, long long n_samples, const long long*
  * Refused with DCCN_ERR_INVALID_ARG before anything is launched: an unsupported shape; cap, pilot_sc, first_out, cfo_out or
  * workspace NULL; cap or workspace off a 16-byte boundary, first_out off an 8-byte one, pilot_sc, cfo_out, sym_metric or
  * phase_metric off a 4-byte one; lo < 0; lo + (J+2)*T > n_samples (conservative: it covers every read of both stages).  A
- * workspace smaller than the size query's answer: DCCN_ERR_WORKSPACE.  Inside a chain group DCCN_ERR_UNSUPPORTED. */
+ * workspace smaller than the size query's answer: DCCN_ERR_WORKSPACE.  Inside a chain group DCCN_ERR_UNSUPPORTED (several links
+ * per launch: the grouped entries below, which take their own link table). */
 int dccn_capture_acquire_supported(int S, int K, int CP, int n_pilot, int J);
 size_t dccn_capture_acquire_workspace_size(int S, int K, int CP, int n_pilot, int J);
 int dccn_capture_acquire(const float* cap, long long n_samples, long long lo, int J, int S, int K, int CP, const int* pilot_sc,
                          int n_pilot, long long* first_out, float* cfo_out, float* sym_metric /* nullable */,
                          float* phase_metric /* nullable */, void* workspace, size_t workspace_bytes, dccn_stream_t stream);
+
+/* ==== the receive front end for several links: alignment, capture cut and acquisition as shared launches ====
+ * dccn_eq_receive_step_grouped carries up to dccn_chain_group_max() links through one launch sequence; these entries do the same
+ * for what runs in front of it.  Each runs the solo entry's kernel body for n_links links in ONE launch (acquisition: its three
+ * launches), the link index on a grid dimension and a link's blocks laid out as the solo launch lays them out: link i's outputs
+ * are bit for bit what the solo entry writes for link i's arguments, and n_links == 1 writes what the solo entry writes.
+ * A capture comes from a front end and does not live in a chain's arena, so the links travel as a table of per-link descriptors
+ * (a HOST array of n_links entries, copied by value into the kernel arguments), not as arena offsets.
+ *   common to the call: frames, S, K, CP, W, out_kin (J, n_pilot for acquisition);
+ *   per link: every pointer, the capture's length, first or first_dev + lo, stride, pilot_sc, the workspace.
+ * dccn_frame_sync_grouped:      link i as dccn_frame_sync(x, ..., x_out, offset, metric), or dccn_frame_sync_cfo where cfo is given.
+ * dccn_capture_sync_grouped:    link i as dccn_capture_sync(cap, n_samples, first, stride, ...) where first_dev == NULL, as
+ *                               dccn_capture_sync_at(cap, n_samples, first_dev, lo, stride, ...) otherwise (first_dev is read, never
+ *                               written; the value is clamped into [lo, lo + T - 1]).  Known and acquired starts mix in one call.
+ * dccn_capture_acquire_grouped: link i as dccn_capture_acquire(cap, n_samples, lo, J, ..., pilot_sc, ..., workspace, workspace_bytes).
+ * Two links may read the same capture (or frames, or pilot_sc).  x_out, cfo and metric (sym_metric and phase_metric) are each NULL
+ * for every link or for none; with cfo given the CFO instantiation runs.
+ * Plan first, then issue: every link is checked by the solo entry's own rules, and the call adds: n_links outside
+ * 1 .. dccn_chain_group_max(); links NULL; an output given for some links only; any output range of one link (x_out, offset,
+ * cfo, metric; first_out, cfo_out, sym_metric, phase_metric, workspace) overlapping an output range or an input (x, cap,
+ * first_dev, pilot_sc) of ANOTHER link -- all DCCN_ERR_INVALID_ARG; a short acquisition workspace on any link DCCN_ERR_WORKSPACE.
+ * A refused call launches nothing and writes nothing for any link.  Inside a chain group DCCN_ERR_UNSUPPORTED, as the solo
+ * entries: the link table is the call's own, not the group's chain table.  No atomics, no workspace beyond each link's own, every
+ * sum in the solo entry's order: two runs give the same bits. */
+typedef struct dccn_frame_link {
+    const float* x;            /* [frames,S,K+CP,2] */
+    float* x_out;              /* nullable (for all links or none) */
+    int32_t* offset;           /* [frames] */
+    float* cfo;                /* nullable (all or none): [frames] */
+    float* metric;             /* nullable (all or none): [frames, 2W+1] */
+} dccn_frame_link;
+typedef struct dccn_capture_link {
+    const float* cap;          /* [n_samples,2] */
+    long long n_samples;
+    long long first;           /* used when first_dev == NULL */
+    const long long* first_dev;/* nullable: device int64[1], clamped into [lo, lo + T - 1] */
+    long long lo;              /* read with first_dev only */
+    long long stride;
+    float* x_out;              /* nullable (all or none) */
+    int32_t* offset;           /* [frames] */
+    float* cfo;                /* nullable (all or none) */
+    float* metric;             /* nullable (all or none) */
+} dccn_capture_link;
+typedef struct dccn_acquire_link {
+    const float* cap;          /* [n_samples,2] */
+    long long n_samples;
+    long long lo;
+    const int* pilot_sc;       /* [n_pilot] */
+    long long* first_out;      /* [1] */
+    float* cfo_out;            /* [1] */
+    float* sym_metric;         /* nullable (all or none): [K+CP] */
+    float* phase_metric;       /* nullable (all or none): [S] */
+    void* workspace;           /* dccn_capture_acquire_workspace_size bytes, the link's own */
+    size_t workspace_bytes;
+} dccn_acquire_link;
+int dccn_frame_sync_grouped(int n_links, const dccn_frame_link* links, int frames, int S, int K, int CP, int W, int out_kin,
+                            dccn_stream_t stream);
+int dccn_capture_sync_grouped(int n_links, const dccn_capture_link* links, int frames, int S, int K, int CP, int W, int out_kin,
+                              dccn_stream_t stream);
+int dccn_capture_acquire_grouped(int n_links, const dccn_acquire_link* links, int J, int S, int K, int CP, int n_pilot,
+                                 dccn_stream_t stream);
 
 /* ==== host utility: CRC32C (Castagnoli), the checksum of TensorFlow's tensor-bundle checkpoints =========
  * (tf.train.Saver files the reference writes at dev/py/ofdmreceiver_np.py:271).

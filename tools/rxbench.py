@@ -10,6 +10,10 @@
     python tools/rxbench.py --chains 2 4 8 [--mods 1 2 3 4] [--frames 73] [--out FILE]
         several links, each with its own (equaliser -> frozen receiver) chain: (a) G solo receive calls back to back on one
         stream against (b) ONE grouped call (dccn_eq_receive_step_grouped), per group size G; same alternation and repeats
+    python tools/rxbench.py --chains 2 4 8 [--sync 3] [--cfo] [--capture] [--acquire] [--out FILE]
+        the front end of a multi-link round: (a) FrameSync / CaptureSync / CaptureAcquire issued per link in front of ONE grouped
+        step against (b) the grouped front end (dccn_frame_sync_grouped, dccn_capture_sync_grouped,
+        dccn_capture_acquire_grouped) in front of the same step, and the front-end launches alone; same alternation and repeats
     python tools/rxbench.py --sync 3 [--out FILE]
         the same receive call on full frames resident on the device: (copy) receive(x), whose first launch copies the frames
         into the receiver, against (sync) receive(x, sync=W), where the alignment launch (dccn_frame_sync) takes the copy's
@@ -375,6 +379,128 @@ def main_chains(a):
     return 0
 
 
+def run_group_front(mods, frames, W, cfo, want_sync, want_capture, want_acquire, iters, repeats, solo_only=False):
+    """G links, each with its own chain and its own clean transmitted capture: a round of the front end + ONE grouped step, with
+    (a) the front end issued per link -- FrameSync.run / CaptureSync.run(out=chain.pl.x) / CaptureAcquire.run + CaptureSync.run,
+        what a caller of the solo stages does in front of the grouped step -- against
+    (b) the grouped front end (group.receive(xs, sync=W) / group.receive_capture(...)): one alignment or cut launch, three
+        acquisition launches, for all links;
+    and the front-end launches alone (`*_front`).  (a) and (b) must return the same bits before anything is timed.
+    ``solo_only``: the (a) variants alone -- they use nothing an older build of the library lacks, so with DCCN_LIB_PATH naming
+    the parent's build (tools/build_rev.sh, DCCN_LIB_ALLOW_MISSING=1) this times (a) on the parent's kernels."""
+    import numpy as np
+    import torch
+    from dl_ofdm_amd import _lib, ofdm, receiver as R, receiver_mp as H, util
+    from dl_ofdm_amd.engine import glorot_init
+    from dl_ofdm_amd.equalizer_group import ChainReceiveGroup
+    from dl_ofdm_amd.sync import CaptureAcquire, CaptureAcquireGroup, CaptureSync, CaptureSyncGroup, FrameSync, FrameSyncGroup
+    both = not solo_only
+    G = len(mods)
+    fl = [H.Flags(nbits=nb, nfilter=F, seed=10 + i) for i, nb in enumerate(mods)]
+    tx = [ofdm.ofdm_tx(f) for f in fl]
+    rx = [glorot_init(R.rx_dims(f, o), 3 + i) for i, (f, o) in enumerate(zip(fl, tx))]
+    grp = ChainReceiveGroup(fl, rx, frames)
+    CP = KIN - F
+    T = S * KIN
+    lo, cut = 5, 211
+    caps, xs, true = [], [], []
+    for i, (nb, o) in enumerate(zip(mods, tx)):
+        assert (o.K, o.CP) == (F, CP)
+        np.random.seed(100 + i)
+        _, iq, _ = o.ofdm_tx_frame_np(util.bit_source(nb, o.frame_size, frames + 3))
+        c = cut + 37 * i                                                  # every link's capture begins somewhere else in its frame 0
+        cap = torch.as_tensor(np.ascontiguousarray(iq.reshape(-1, 2)[c:]), device="cuda")
+        first = lo + (T - c - lo) % T
+        caps.append(cap)
+        true.append(first)
+        xs.append(cap[first:first + frames * T].reshape(frames, S, KIN, 2).clone())
+    outs = [ch.pl.x for ch in grp.chains]
+    none = [None] * G
+    step = lambda: grp.receive(none)                                     # noqa: E731
+    packed = lambda res: [r.packed.clone() for r in res]                 # noqa: E731
+    variants = {"step": step}
+
+    def agree(a, b):
+        pa = packed(a())
+        assert all(torch.equal(p, q) for p, q in zip(pa, packed(b())))
+
+    if want_sync:
+        fs = [FrameSync(S, F, CP, W, frames, "cuda", want_metric=False, cfo=cfo) for _ in range(G)]
+        fg = FrameSyncGroup(S, F, CP, W, frames, G, "cuda", want_metric=False, cfo=cfo) if both else None
+
+        def a_sync_front():
+            for s, x, o in zip(fs, xs, outs):
+                s.run(x, out=o)
+        variants.update(a_sync=lambda: (a_sync_front(), step())[1], a_sync_front=a_sync_front)
+        if both:
+            variants.update(b_sync=lambda: grp.receive(xs, sync=W, cfo=cfo), b_sync_front=lambda: fg.run(xs, outs=outs))
+            agree(variants["a_sync"], variants["b_sync"])
+    if want_capture:
+        cs = [CaptureSync(S, F, CP, W, frames, "cuda", want_metric=False, cfo=cfo) for _ in range(G)]
+        cg = CaptureSyncGroup(S, F, CP, W, frames, G, "cuda", want_metric=False, cfo=cfo) if both else None
+
+        def a_cut_front():
+            for s, c, f, o in zip(cs, caps, true, outs):
+                s.run(c, f, out=o)
+        variants.update(a_cut=lambda: (a_cut_front(), step())[1], a_cut_front=a_cut_front)
+        if both:
+            variants.update(b_cut=lambda: grp.receive_capture(caps, firsts=true, sync=W, cfo=cfo),
+                            b_cut_front=lambda: cg.run(caps, true, outs=outs))
+            agree(variants["a_cut"], variants["b_cut"])
+        for J in (want_acquire or ()):
+            acq = [CaptureAcquire(S, F, CP, o.pilotSc, J, "cuda") for o in tx]
+            ag = CaptureAcquireGroup(S, F, CP, [np.asarray(o.pilotSc) for o in tx], J, G, "cuda") if both else None
+
+            def a_front(acq=acq):
+                for q, s, c, o in zip(acq, cs, caps, outs):
+                    s.run(c, q.run(c, lo), out=o, lo=lo)
+
+            def b_front(ag=ag):
+                cg.run(caps, ag.run(caps, lo), outs=outs, los=lo)
+            variants.update({"a_acquire%d" % J: lambda f=a_front: (f(), step())[1], "a_acquire%d_front" % J: a_front})
+            if both:
+                variants.update({"b_acquire%d" % J: lambda J=J: grp.receive_capture(caps, acquire=J, los=lo, sync=W, cfo=cfo),
+                                 "b_acquire%d_front" % J: b_front})
+                agree(variants["a_acquire%d" % J], variants["b_acquire%d" % J])
+                b_front()
+                assert [int(t[0]) for t in ag.first] == [int(q.first[0]) for q in acq]
+    us, spread = timed(variants, iters, repeats)
+    return {"chains": G, "mods": list(mods), "frames": frames, "W": W, "cfo": bool(cfo), "iters": iters, "repeats": repeats, "us": us,
+            "spread": spread, "solo_only": bool(solo_only), "build_id": _lib.load().dccn_build_id().decode()}
+
+
+def main_group_front(a):
+    """--chains with --sync / --capture / --acquire: one child process per group size, under a time limit"""
+    res, W = [], a.sync or 3
+    for G in a.chains:
+        mods = [a.mods[i % len(a.mods)] for i in range(G)]
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--one-chains", ",".join(map(str, mods)),
+               "--frames", str(a.frames), "--iters", str(a.iters), "--repeats", str(a.repeats), "--sync", str(W)]
+        cmd += (["--cfo"] if a.cfo else []) + (["--capture"] if a.capture or a.acquire else []) + (["--acquire"] if a.acquire else [])
+        cmd += (["--front-sync"] if a.sync else []) + (["--front-solo-only"] if a.front_solo_only else [])
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        if r.returncode != 0:               # nothing more is started on the GPU after a failure
+            sys.stderr.write(r.stderr[-2000:])
+            print(json.dumps({"bench": "rxbench.group_front", "failed": G, "rc": r.returncode, "groups": res}))
+            return 1
+        res.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    doc = {"bench": "rxbench.group_front",
+           "variants": {"step": "the grouped receive step alone (frames resident)",
+                        "a_*": "the front end issued per link (FrameSync / CaptureSync / CaptureAcquire + CaptureSync, out=chain.pl.x), "
+                               "then ONE grouped step",
+                        "b_*": "the grouped front end (one alignment or cut launch, three acquisition launches) + the same grouped step",
+                        "*_front": "the front-end launches alone",
+                        "sync": "frames cut in advance, alignment", "cut": "captures, starts known", "acquireJ": "captures, starts acquired from J frames"},
+           "unit": "us per round of G links (median over repeats of the mean of `iters` back-to-back rounds); spread = (max - min) / median",
+           "groups": res}
+    print(json.dumps(doc))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=200)
@@ -393,7 +519,18 @@ def main():
                     help="time receive_capture against receive(x, sync=W[, cfo=True]) on the same frames cut in advance (W: --sync, default 3)")
     ap.add_argument("--acquire", action="store_true",
                     help="time receive_capture(first=None, acquire=J) against receive_capture(first=int), and the acquisition launches alone")
+    ap.add_argument("--front-sync", action="store_true", help="(internal, with --one-chains: time the alignment of frames cut in advance)")
+    ap.add_argument("--front-solo-only", action="store_true",
+                    help="--chains with a front end: only the per-link variants (for DCCN_LIB_PATH = the parent's build)")
+    ap.add_argument("--acquire-frames", type=int, nargs="+", default=[4, 16], help="--chains --acquire: the J to time")
     a = ap.parse_args()
+    if a.one_chains and (a.front_sync or a.capture or a.acquire):
+        print(json.dumps(run_group_front([int(v) for v in a.one_chains.split(",")], a.frames, a.sync or 3, a.cfo, a.front_sync,
+                                         a.capture or a.acquire, a.acquire_frames if a.acquire else None, a.iters, a.repeats,
+                                         a.front_solo_only)))
+        return 0
+    if a.chains and (a.sync or a.capture or a.acquire):
+        return main_group_front(a)
     if a.acquire:
         if a.one:
             fr, nb = (int(v) for v in a.one.split(","))
