@@ -157,6 +157,11 @@ class AcquireLink(C.Structure):
                 ("workspace_bytes", c_size_t)]
 
 
+class PooledLink(C.Structure):
+    """dccn_pooled_link"""
+    _fields_ = CaptureLink._fields_ + [("workspace", c_void_p), ("workspace_bytes", c_size_t)]
+
+
 METRICS_BYTES = C.sizeof(Metrics)
 ADAM_STATE_BYTES = C.sizeof(AdamState)
 
@@ -267,6 +272,10 @@ SIGNATURES = {
     "dccn_frame_sync_grouped": (_i, [_i, POINTER(FrameLink)] + [_i] * 6 + [_vp]),
     "dccn_capture_sync_grouped": (_i, [_i, POINTER(CaptureLink)] + [_i] * 6 + [_vp]),
     "dccn_capture_acquire_grouped": (_i, [_i, POINTER(AcquireLink)] + [_i] * 5 + [_vp]),
+    # one carrier offset per capture, pooled over its frames (three launches, a caller-owned workspace per link)
+    "dccn_capture_sync_pooled_workspace_size": (_sz, [_i]),
+    "dccn_capture_sync_pooled": (_i, [_vp, c_longlong, c_longlong, _vp, c_longlong, c_longlong] + [_i] * 6 + [_vp] * 5 + [_sz, _vp]),
+    "dccn_capture_sync_pooled_grouped": (_i, [_i, POINTER(PooledLink)] + [_i] * 6 + [_vp]),
     "dccn_rx_normalise": (_i, [POINTER(RxShape), POINTER(RxBuffers), _vp]),
     "dccn_rx_graph_create": (_i, [POINTER(RxShape), POINTER(RxBuffers), _i, AdamHParams, _vp, POINTER(c_void_p)]),
     "dccn_rx_graph_launch": (_i, [_vp, _vp]),

@@ -227,6 +227,69 @@ int capture_sync_group_plan(int n_links, const dccn_capture_link* links, int fra
     return DCCN_OK;
 }
 
+// dccn_capture_sync_pooled(_grouped): every link through the per-frame entry's own plan (so the windows, the alignment and the
+// cap / x_out overlap are judged by the same code), then what the pooled call adds.
+size_t pooled_workspace_bytes(int frames) { return frames > 0 ? ((size_t)frames * sizeof(float2) + 15) & ~(size_t)15 : 0; }
+
+struct PooledGroupPlan {
+    PooledGroupArgs args;
+    unsigned blocks;
+    size_t lds_estimate, lds_cut;
+};
+int pooled_group_plan(int n_links, const dccn_pooled_link* links, int frames, int S, int K, int CP, int W, int out_kin,
+                      PooledGroupPlan* plan) {
+    if (!group_count_ok(n_links, links)) return DCCN_ERR_INVALID_ARG;
+    LinkRanges r[kMaxChains];
+    plan->args = PooledGroupArgs{};
+    for (int i = 0; i < n_links; ++i) {
+        const dccn_pooled_link& l = links[i];
+        CaptureSyncPlan one;
+        if (l.first_dev)
+            DCCN_TRY(capture_sync_at_plan(l.cap, l.n_samples, l.first_dev, l.lo, l.stride, frames, S, K, CP, W, out_kin, l.x_out,
+                                          l.offset, l.cfo, l.metric, &one));
+        else
+            DCCN_TRY(capture_sync_plan(l.cap, l.n_samples, l.first, l.stride, frames, S, K, CP, W, out_kin, l.x_out, l.offset, l.cfo,
+                                       l.metric, &one));
+        if (!l.x_out || !l.cfo || (reinterpret_cast<uintptr_t>(l.cfo) & 3u) != 0) return DCCN_ERR_INVALID_ARG;
+        if (!l.workspace || !aligned16(l.workspace)) return DCCN_ERR_INVALID_ARG;
+        plan->args.link[i] = PooledLink{CaptureSyncLink{one.args.cap, l.first_dev ? 0 : l.first, one.args.stride, l.first_dev,
+                                                        l.first_dev ? l.lo : 0, one.args.x_out, one.args.offset, one.args.metric,
+                                                        one.args.cfo},
+                                        static_cast<float2*>(l.workspace)};
+        if (i == 0) {
+            plan->args.frames = frames; plan->args.S = S; plan->args.K = K; plan->args.CP = CP; plan->args.W = W;
+            plan->args.crop = one.args.crop;
+            plan->blocks = one.blocks;
+            plan->lds_estimate = one.lds;
+            plan->lds_cut = kSyncWaves * capture_cut_lds_per_frame(S * (K + CP));
+        }
+        r[i].out(l.x_out, (size_t)frames * S * out_kin * 8);
+        r[i].out(l.offset, (size_t)frames * 4);
+        r[i].out(l.cfo, 4);
+        r[i].out(l.metric, (size_t)frames * (2 * W + 1) * 4);
+        r[i].out(l.workspace, pooled_workspace_bytes(frames));
+        r[i].in(l.cap, (size_t)l.n_samples * 8);
+        r[i].in(l.first_dev, 8);
+    }
+    if (mixed_nullability(links, n_links, &dccn_pooled_link::metric)) return DCCN_ERR_INVALID_ARG;
+    if (links_collide(r, n_links)) return DCCN_ERR_INVALID_ARG;
+    for (int i = 0; i < n_links; ++i)
+        if (links[i].workspace_bytes < pooled_workspace_bytes(frames)) return DCCN_ERR_WORKSPACE;
+    return DCCN_OK;
+}
+int pooled_group_launch(const PooledGroupPlan& plan, int n_links, dccn_stream_t stream) {
+    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_estimate_kernel, plan.lds_estimate));
+    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_cut_kernel, plan.lds_cut));
+    const dim3 grid(plan.blocks, (unsigned)n_links), block(kSyncWaves * kSyncLanes);
+    hipLaunchKernelGGL(capture_pool_estimate_kernel, grid, block, plan.lds_estimate, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(capture_pool_reduce_kernel, dim3((unsigned)n_links), dim3(kSyncLanes), 0, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(capture_pool_cut_kernel, grid, block, plan.lds_cut, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
 struct CaptureAcquireGroupPlan {
     AcqGroupArgs args;
     unsigned sum_blocks;
@@ -387,6 +450,24 @@ int dccn_capture_acquire_grouped(int n_links, const dccn_acquire_link* links, in
     hipLaunchKernelGGL(acq_decide_grouped_kernel, dim3(G), dim3(kAcqMaxS), 0, (hipStream_t)stream, plan.args);
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
+}
+
+// ---- one carrier offset per capture: the solo entry is the grouped one with one link -----------------------------------------
+size_t dccn_capture_sync_pooled_workspace_size(int frames) { return pooled_workspace_bytes(frames); }
+
+int dccn_capture_sync_pooled_grouped(int n_links, const dccn_pooled_link* links, int frames, int S, int K, int CP, int W,
+                                     int out_kin, dccn_stream_t stream) {
+    PooledGroupPlan plan;
+    DCCN_TRY(pooled_group_plan(n_links, links, frames, S, K, CP, W, out_kin, &plan));
+    DCCN_NO_CHAINS();
+    return pooled_group_launch(plan, n_links, stream);
+}
+
+int dccn_capture_sync_pooled(const float* cap, long long n_samples, long long first, const long long* first_dev, long long lo,
+                             long long stride, int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset,
+                             float* cfo_out, float* metric, void* workspace, size_t workspace_bytes, dccn_stream_t stream) {
+    const dccn_pooled_link link{cap, n_samples, first, first_dev, lo, stride, x_out, offset, cfo_out, metric, workspace, workspace_bytes};
+    return dccn_capture_sync_pooled_grouped(1, &link, frames, S, K, CP, W, out_kin, stream);
 }
 
 }  // extern "C"

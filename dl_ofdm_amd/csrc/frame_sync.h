@@ -22,6 +22,10 @@
 //
 // dccn_frame_sync_grouped / dccn_capture_sync_grouped (at the end) run frame_sync_body / capture_sync_body for up to kMaxChains
 // links in one launch: a by-value table of per-link pointers, the link index on blockIdx.y.
+//
+// dccn_capture_sync_pooled(_grouped) (at the end) estimate ONE carrier offset per capture from the sum of the frames' Gamma_f: the
+// same estimate body with a finish that stores Gamma_f, a one-wave sum in a stated order, and a cut pass that derotates every
+// frame with the common value -- three launches, new instantiations only.
 #pragma once
 #include "common.h"
 
@@ -181,6 +185,9 @@ __device__ __forceinline__ void sync_cfo_store(const At at, const float2* y, flo
     }
 }
 
+// The estimate read off a correlation sum, in subcarrier spacings (0 - a: +0 where the angle is 0)
+__device__ __forceinline__ float cfo_of_gamma(const float2 gamma) { return 0.f - atan2f(gamma.y, gamma.x) / 6.283185307179586f; }
+
 // What follows the estimate, stated once: the offset, the CFO variant's estimate, and the frame on its way out.
 template <bool CFO, class At>
 __device__ __forceinline__ void sync_finish(const At at, const float2* y, const long long f, const int theta, const float2 gamma,
@@ -189,7 +196,7 @@ __device__ __forceinline__ void sync_finish(const At at, const float2* y, const 
     if (lane == 0) offset[f] = theta;
     float* const dst = x_out + (size_t)f * S * (crop ? K : K + CP) * 2;
     if constexpr (CFO) {
-        const float cfo = 0.f - atan2f(gamma.y, gamma.x) / 6.283185307179586f;     // (0 - a: +0 where the angle is 0)
+        const float cfo = cfo_of_gamma(gamma);
         if (lane == 0) cfo_out[f] = cfo;
         if (x_out) sync_cfo_store(at, y, dst, theta, cfo, lane, S, K, CP, crop);
     } else {
@@ -260,9 +267,34 @@ struct CaptureSyncArgs {
     int crop;
 };
 
+// The samples [start, start + len) of the capture (len even) into a wave's region, as stated above: the region's pair i holds the
+// samples (a0 + 2 i, a0 + 2 i + 1), a0 = start & ~1, so sample `start` sits in slot start & 1.
+__device__ __forceinline__ void capture_window_load(float4* region, const float* cap, const long long start, const int len,
+                                                    const int lane) {
+    const int sh = (int)(start & 1);
+    const float2* const src2 = reinterpret_cast<const float2*>(cap) + (start - sh);
+    const float4* const src4 = reinterpret_cast<const float4*>(src2);
+    const int pairs = (len + 2 * sh) / 2;            // sh = 1: one more pair, the first and the last half inside
+    for (int i = lane; i < pairs; i += kSyncLanes) {
+        float4 v;
+        if (sh && i == 0) {
+            const float2 h = src2[1];
+            v = make_float4(0.f, 0.f, h.x, h.y);
+        } else if (sh && i == pairs - 1) {
+            const float2 h = src2[2 * i];
+            v = make_float4(h.x, h.y, 0.f, 0.f);
+        } else {
+            v = src4[i];
+        }
+        region[i] = v;
+    }
+}
+
 // The launch, stated once; `first` is where frame 0 nominally starts (the argument, or what dccn_capture_sync_at read).
-template <bool CFO>
-__device__ __forceinline__ void capture_sync_body(const CaptureSyncArgs& a, const long long first) {
+// POOL (dccn_capture_sync_pooled's estimate pass, below): the same estimate with another finish -- the frame's offset and
+// Gamma_f(offset) go to offset[f] and gamma_ws[f], and no frame is written.
+template <bool CFO, bool POOL = false>
+__device__ __forceinline__ void capture_sync_body(const CaptureSyncArgs& a, const long long first, float2* gamma_ws = nullptr) {
     extern __shared__ float4 sync_lds[];
     const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
     const int T = a.S * (a.K + a.CP), W = a.W;
@@ -276,31 +308,21 @@ __device__ __forceinline__ void capture_sync_body(const CaptureSyncArgs& a, cons
     const float2* const y = reinterpret_cast<const float2*>(region) + sh;    // slot 0 = sample start
 
     // 1. the window, once, into LDS
-    if (live) {
-        const int len = T + 2 * W;                       // even
-        const float2* const src2 = reinterpret_cast<const float2*>(a.cap) + (start - sh);
-        const float4* const src4 = reinterpret_cast<const float4*>(src2);
-        const int pairs = (len + 2 * sh) / 2;            // sh = 1: one more pair, the first and the last half inside
-        for (int i = lane; i < pairs; i += kSyncLanes) {
-            float4 v;
-            if (sh && i == 0) {
-                const float2 h = src2[1];
-                v = make_float4(0.f, 0.f, h.x, h.y);
-            } else if (sh && i == pairs - 1) {
-                const float2 h = src2[2 * i];
-                v = make_float4(h.x, h.y, 0.f, 0.f);
-            } else {
-                v = src4[i];
-            }
-            region[i] = v;
-        }
-    }
+    if (live) capture_window_load(region, a.cap, start, T + 2 * W, lane);
     const SyncLinear at{W};
     float2 gamma = make_float2(0.f, 0.f);
     const int theta = sync_estimate(at, y, pe, lane, live, a.S, a.K, a.CP, W,
-                                    (live && a.metric) ? a.metric + (size_t)f * (2 * W + 1) : nullptr, CFO ? &gamma : nullptr);
+                                    (live && a.metric) ? a.metric + (size_t)f * (2 * W + 1) : nullptr,
+                                    (CFO || POOL) ? &gamma : nullptr);
     if (!live) return;
-    sync_finish<CFO>(at, y, f, theta, gamma, lane, a.x_out, a.offset, a.cfo, a.S, a.K, a.CP, a.crop);
+    if constexpr (POOL) {
+        if (lane == 0) {
+            a.offset[f] = theta;
+            gamma_ws[f] = gamma;
+        }
+    } else {
+        sync_finish<CFO>(at, y, f, theta, gamma, lane, a.x_out, a.offset, a.cfo, a.S, a.K, a.CP, a.crop);
+    }
 }
 
 template <bool CFO>
@@ -369,6 +391,97 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_g
     capture_sync_body<CFO>(CaptureSyncArgs{l.cap, first, l.stride, l.x_out, l.offset, l.metric, l.cfo, g.frames, g.S, g.K, g.CP, g.W,
                                            g.crop},
                            first);
+}
+
+// ---- one carrier offset per capture, pooled over its frames (dccn_capture_sync_pooled, dccn_capture_sync_pooled_grouped) -------
+// A capture comes from one front end with one oscillator: its frames share one offset, so the estimate is taken from
+//     Gamma = sum_{f < frames} Gamma_f(offset[f]),    cfo = 0 - atan2(Im Gamma, Re Gamma) / (2 pi)
+// and every frame is derotated with that one value.  No frame can leave before every frame's Gamma_f is known, so the call is
+// three launches on the stream, each complete before the next starts (no block waits for another, no atomics, no host round trip):
+//   estimate  capture_sync_body<.., POOL>: the solo estimate, offset[f] and Gamma_f(offset[f]) stored (workspace: float2 [frames])
+//   reduce    one wave per link.  THE ORDER OF THE SUM: lane l adds Gamma_l, Gamma_{l+64}, Gamma_{l+128}, ... in ascending
+//             order onto +0; then a butterfly over the 64 lanes, d = 1, 2, 4, 8, 16, 32: every lane adds the value of lane
+//             (l xor d) to its own (both partners add the same two numbers, so all lanes hold the same bits).  Real and
+//             imaginary parts are summed separately.  The order depends on `frames` alone -- not on a grid, the link count or
+//             whether the call is grouped.  A Gamma_f passes through at most ceil(frames / 64) - 1 + 6 rounded additions.
+//   cut       one wave per frame, four per block: offset[f] is read back and CLAMPED into [-W, W] before it indexes (the frame
+//             [b_f + offset, b_f + offset + T) then lies inside the window [b_f - W, b_f + T + W) the host checked), the frame is
+//             loaded as the window is (aligned 16-byte pairs, one 8-byte half at each end when it starts on an odd sample) and
+//             leaves through sync_cfo_store with the capture's cfo: the derotation and the 16-byte stores of the per-frame path.
+// The solo entry is the grouped one with one link: the link index rides on blockIdx.y (reduce: blockIdx.x).
+__host__ __device__ static inline size_t capture_cut_lds_per_frame(int T) { return (size_t)(T + 2) * 8; }
+constexpr int kPoolAhead = 16;              // the reduce launch's loads in flight per lane
+
+struct PooledLink {
+    CaptureSyncLink s;          // s.cfo: [1], the capture's estimate
+    float2* gamma;              // [frames]: Gamma_f(offset[f])
+};
+struct PooledGroupArgs {
+    PooledLink link[kMaxChains];
+    int frames, S, K, CP, W, crop;
+};
+__device__ __forceinline__ long long pooled_first(const CaptureSyncLink& l, const int T) {     // as capture_sync_grouped_kernel
+    if (!l.first_dev) return l.first;
+    const long long hi = l.lo + T - 1;
+    const long long got = l.first_dev[0];
+    return got < l.lo ? l.lo : (got > hi ? hi : got);
+}
+
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_estimate_kernel(const PooledGroupArgs g) {
+    const PooledLink& l = g.link[blockIdx.y];
+    const long long first = pooled_first(l.s, g.S * (g.K + g.CP));
+    capture_sync_body<false, true>(CaptureSyncArgs{l.s.cap, first, l.s.stride, nullptr, l.s.offset, l.s.metric, nullptr, g.frames, g.S,
+                                                   g.K, g.CP, g.W, g.crop},
+                                   first, l.gamma);
+}
+
+static __global__ void __launch_bounds__(kSyncLanes) capture_pool_reduce_kernel(const PooledGroupArgs g) {
+    const PooledLink& l = g.link[blockIdx.x];
+    const int lane = threadIdx.x;
+    float gr = 0.f, gi = 0.f;
+    // the lane's terms, kPoolAhead loads in flight at a time (their latency is all this launch waits for); added in the stated order
+    for (int f0 = lane; f0 < g.frames; f0 += kSyncLanes * kPoolAhead) {
+        float2 t[kPoolAhead];
+#pragma unroll
+        for (int u = 0; u < kPoolAhead; ++u) {
+            const int f = f0 + u * kSyncLanes;
+            t[u] = f < g.frames ? l.gamma[f] : make_float2(0.f, 0.f);
+        }
+#pragma unroll
+        for (int u = 0; u < kPoolAhead; ++u) {
+            if (f0 + u * kSyncLanes < g.frames) {
+                gr += t[u].x;
+                gi += t[u].y;
+            }
+        }
+    }
+    for (int d = 1; d < kSyncLanes; d <<= 1) {
+        gr += __shfl_xor(gr, d);
+        gi += __shfl_xor(gi, d);
+    }
+    if (lane == 0) l.s.cfo[0] = cfo_of_gamma(make_float2(gr, gi));
+}
+
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_cut_kernel(const PooledGroupArgs g) {
+    extern __shared__ float4 sync_lds[];
+    const PooledLink& l = g.link[blockIdx.y];
+    const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
+    const int T = g.S * (g.K + g.CP), W = g.W;
+    const long long f = (long long)blockIdx.x * kSyncWaves + wave;
+    const bool live = f < g.frames;
+    float4* const region = sync_lds + (size_t)wave * (capture_cut_lds_per_frame(T) / 16);
+    long long start = 0;
+    if (live) {
+        const int got = l.s.offset[f];
+        start = pooled_first(l.s, T) + f * l.s.stride + (got < -W ? -W : (got > W ? W : got));
+    }
+    const float2* const y = reinterpret_cast<const float2*>(region) + (int)(start & 1);      // slot 0 = sample start
+    if (live) capture_window_load(region, l.s.cap, start, T, lane);
+    __syncthreads();                                    // (the frame is complete in LDS)
+    if (!live) return;
+    const float cfo = l.s.cfo[0];
+    sync_cfo_store(SyncLinear{0}, y, l.s.x_out + (size_t)f * g.S * (g.crop ? g.K : g.K + g.CP) * 2, 0, cfo, lane, g.S, g.K, g.CP,
+                   g.crop);
 }
 
 }  // namespace dccn

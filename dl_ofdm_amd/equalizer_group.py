@@ -320,12 +320,14 @@ class ChainReceiveGroup:
         c = self.chains[0]
         return int(c.F.nsymbol), int(c.o.K), int(c.o.CP)
 
-    def _stage(self, kind: str, cls, W: int, cfo: bool):
-        """the resident front-end stage of this group: FrameSyncGroup / CaptureSyncGroup, writing the chains' ``pl.x``"""
-        key = (kind, int(W), bool(cfo))
+    def _stage(self, kind: str, cls, W: int, cfo: bool, **scope):
+        """the resident front-end stage of this group: FrameSyncGroup / CaptureSyncGroup, writing the chains' ``pl.x``
+        (``scope``: ``cfo_scope="capture"`` of a pooled CaptureSyncGroup)"""
+        key = (kind, int(W), bool(cfo)) + tuple(scope.values())
         if key not in self._stages:
             S, K, CP = self._frame_shape()
-            self._stages[key] = cls(S, K, CP, int(W), self.batch, len(self.chains), self.device, want_metric=False, cfo=bool(cfo))
+            self._stages[key] = cls(S, K, CP, int(W), self.batch, len(self.chains), self.device, want_metric=False, cfo=bool(cfo),
+                                    **scope)
         return self._stages[key]
 
     def receive(self, xs: Sequence, want_llr: Optional[bool] = None, want_prob: Optional[bool] = None, sync: int = 0,
@@ -363,7 +365,7 @@ class ChainReceiveGroup:
                 for i, c in enumerate(self.chains)]
 
     def receive_capture(self, caps: Sequence, firsts=None, strides=None, sync: int = 3, cfo: bool = False, acquire: int = 0, los=0,
-                        want_llr: Optional[bool] = None, want_prob: Optional[bool] = None) -> list:
+                        want_llr: Optional[bool] = None, want_prob: Optional[bool] = None, cfo_scope: str = "frame") -> list:
         """One round on ``batch`` frames per chain that still sit inside contiguous captures: ``caps[i]`` is chain i's capture
         (device tensor ``float32 [n, 2]``; two chains may share one), as ``EqualizerTrainer.receive_capture(caps[i], firsts[i],
         strides[i], sync, cfo, frames=batch, lo=los[i])`` per chain.  ``firsts[i]``: an integer, or a device ``int64`` tensor of
@@ -373,9 +375,13 @@ class ChainReceiveGroup:
         ``firsts=None, acquire=J, los=...``: acquisition for all chains (:class:`~dl_ofdm_amd.sync.CaptureAcquireGroup`, three
         launches, the pilot cells are each chain's ``pilotSc``) leaves every chain's start inside ``[los[i], los[i] + T)`` on the
         device, where the cut reads it: four front-end launches for the whole group, no host round trip.  Each result carries
-        ``offset``, ``cfo``, ``first`` and ``acquired_cfo`` as the solo call returns them."""
+        ``offset``, ``cfo``, ``first`` and ``acquired_cfo`` as the solo call returns them.
+
+        ``cfo=True, cfo_scope="capture"``: one carrier offset per chain's capture, pooled over its frames
+        (``CaptureSyncGroup(..., cfo_scope="capture")``: three launches for all chains in place of the one)."""
         from .receive import ReceiveResult
-        from .sync import CaptureAcquireGroup, CaptureSyncGroup, _per_link
+        from .sync import CaptureAcquireGroup, CaptureSyncGroup, _per_link, check_cfo_scope
+        pooled = check_cfo_scope(cfo, cfo_scope)
         n = len(self.chains)
         if len(caps) != n:
             raise ValueError("one capture per chain")
@@ -403,7 +409,7 @@ class ChainReceiveGroup:
                 S, K, CP = self._frame_shape()
                 self._stages[key] = CaptureAcquireGroup(S, K, CP, [np.asarray(c.o.pilotSc) for c in self.chains], J, n, self.device)
             acq = self._stages[key]
-        cs = self._stage("capture", CaptureSyncGroup, W, cfo)
+        cs = self._stage("capture", CaptureSyncGroup, W, cfo, **({"cfo_scope": cfo_scope} if pooled else {}))
         if firsts is None:
             firsts = acq.run(caps, los)
             acq_cfo = acq.cfo

@@ -66,7 +66,8 @@ class ReceiveResult:
                  first: Optional[torch.Tensor] = None, acquired_cfo: Optional[torch.Tensor] = None):
         self.packed, self.llr, self.prob, self.D, self.nbits = packed, llr, prob, int(D), int(nbits)
         self.offset = offset        # int32 [frames]: the timing offsets of a call with sync > 0 (None otherwise)
-        self.cfo = cfo              # float32 [frames]: the carrier-frequency offsets of a call with cfo=True (None otherwise)
+        self.cfo = cfo              # float32 [frames]: the carrier-frequency offsets of a call with cfo=True (None otherwise);
+                                    # float32 [1] from receive_capture(cfo_scope="capture"): the capture's one offset
         self.first = first          # int64 [1]: frame 0's start as receive_capture(first=None) acquired it (None otherwise)
         self.acquired_cfo = acquired_cfo    # float32 [1]: the carrier-frequency offset acquisition estimated on the way
 
@@ -185,7 +186,7 @@ class RxReceiver:
         return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, est)
 
     def receive_capture(self, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False, acquire: int = 0,
-                        lo: int = 0) -> ReceiveResult:
+                        lo: int = 0, cfo_scope: str = "frame") -> ReceiveResult:
         """One receive step on ``batch`` frames that still sit inside one contiguous capture ``cap`` (device tensor ``float32
         [n, 2]``): frame ``f`` nominally starts at sample ``first + f * stride`` (``None``: frames back to back) and may sit up to
         ``sync = W > 0`` samples off.  One launch (:class:`~dl_ofdm_amd.sync.CaptureSync`) stands where ``receive(x, sync=W)``
@@ -193,7 +194,9 @@ class RxReceiver:
         capture's, not the frame's other end -- and writes it straight into ``self.x`` (only the K samples behind each prefix
         when ``dims.kin == K``).  ``cfo=True`` takes each frame's carrier-frequency offset out on the way.  Needs
         ``RxReceiver(..., CP=...)``, and ``K=dims.kin`` as well for a ``cp=False`` receiver: a capture has no shape to read them
-        off.  ``result.offset`` / ``result.cfo``.
+        off.  ``result.offset`` / ``result.cfo``.  ``cfo=True, cfo_scope="capture"``: ONE offset for the whole capture, pooled
+        over its frames (``CaptureSync(..., cfo_scope="capture")``: three launches in place of the one), ``result.cfo`` a
+        one-element tensor; with any ``first``, acquisition included.
 
         ``first=None, acquire=J, lo=...``: nobody knows where frame 0 starts.  Acquisition (:class:`~dl_ofdm_amd.sync.
         CaptureAcquire`, ``J`` frames, needs ``RxReceiver(..., pilot_sc=...)``) finds the frame start inside ``[lo, lo + T)`` and
@@ -201,7 +204,8 @@ class RxReceiver:
         sequence, no host round trip.  ``lo >= sync``, and the capture must hold the ``batch`` frames from ``lo + T - 1`` on.
         ``first`` may also be such a device ``int64`` tensor of one element itself (with ``lo``).  ``result.first`` /
         ``result.acquired_cfo``."""
-        from .sync import CaptureSync
+        from .sync import CaptureSync, check_cfo_scope
+        check_cfo_scope(cfo, cfo_scope)
         W = int(sync)
         if W <= 0:
             raise _lib.DccnError("receive_capture needs sync = W > 0")
@@ -211,10 +215,10 @@ class RxReceiver:
         K = kin - self.CP if self.K is None else self.K
         if K < 1 or kin not in (K + self.CP, K):
             raise _lib.DccnError("receive_capture: K = %d, CP = %d do not fit kin = %d" % (K, self.CP, kin))
-        key = ("capture", W, bool(cfo))
+        key = ("capture", W, bool(cfo)) if cfo_scope == "frame" else ("capture", W, True, cfo_scope)
         if key not in self._syncs:
             self._syncs[key] = CaptureSync(self.dims.S, K, self.CP, W, self.batch, self.device, out_kin=kin, want_metric=False,
-                                           cfo=bool(cfo))
+                                           cfo=bool(cfo), cfo_scope=cfo_scope)
         cs = self._syncs[key]
         first, est0 = _acquired_first(self._syncs, first, acquire, cap, lo, self.dims.S, K, self.CP, self.pilot_sc, self.device)
         _, offset = cs.run(cap, first, stride, out=self.x, lo=lo)             # (lo matters to a device `first` only)
@@ -275,7 +279,7 @@ def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: 
 
 def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False,
                           want_llr: bool = False, want_prob: bool = False, frames: Optional[int] = None, acquire: int = 0,
-                          lo: int = 0) -> ReceiveResult:
+                          lo: int = 0, cfo_scope: str = "frame") -> ReceiveResult:
     """:func:`chain_receive` on frames that still sit inside one contiguous capture ``cap`` (device tensor ``float32 [n, 2]``;
     ``EqualizerTrainer.receive_capture``): as :meth:`RxReceiver.receive_capture`, one :class:`~dl_ofdm_amd.sync.CaptureSync`
     launch cuts every frame at its estimated start -- linearly, up to ``sync = W > 0`` samples off ``first + f * stride`` -- and
@@ -285,8 +289,11 @@ def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, syn
     ``first=None, acquire=J, lo=...``: as :meth:`RxReceiver.receive_capture` -- acquisition over ``J`` frames (the pilot cells are
     ``tr.ofdmobj.pilotSc``) leaves the frame start inside ``[lo, lo + T)`` on the device and the cut reads it there.  The host
     then does not know the start: ``frames=None`` counts the frames that fit from the LAST start of that range on, and with a
-    device tensor ``first`` (and ``lo``) ``frames`` must be given."""
-    from .sync import CaptureSync
+    device tensor ``first`` (and ``lo``) ``frames`` must be given.
+
+    ``cfo=True, cfo_scope="capture"``: one carrier offset for the whole capture, as :meth:`RxReceiver.receive_capture`."""
+    from .sync import CaptureSync, check_cfo_scope
+    check_cfo_scope(cfo, cfo_scope)
     if not tr.fused_ok:
         raise _lib.DccnError("the chain's receive path needs the fused equaliser step")
     W = int(sync)
@@ -310,9 +317,9 @@ def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, syn
         frames = room // step + 1
     pl = tr.resident(int(frames))
     syncs = pl.__dict__.setdefault("_capture_syncs", {})
-    key = (W, bool(cfo))
+    key = (W, bool(cfo)) if cfo_scope == "frame" else (W, True, cfo_scope)
     if key not in syncs:
-        syncs[key] = CaptureSync(S, K, CP, W, int(frames), tr.device, want_metric=False, cfo=bool(cfo))
+        syncs[key] = CaptureSync(S, K, CP, W, int(frames), tr.device, want_metric=False, cfo=bool(cfo), cfo_scope=cfo_scope)
     cs = syncs[key]
     first, est0 = _acquired_first(tr.__dict__.setdefault("_capture_acquires", {}), first, acquire, cap, lo, S, K, CP, o.pilotSc,
                                   tr.device)
@@ -333,9 +340,10 @@ def group_receive(group, xs, sync: int = 0, cfo: bool = False) -> list:
     return group.receive(xs, sync=sync, cfo=cfo)
 
 
-def group_receive_capture(group, caps, firsts=None, strides=None, sync: int = 3, cfo: bool = False, acquire: int = 0, los=0) -> list:
+def group_receive_capture(group, caps, firsts=None, strides=None, sync: int = 3, cfo: bool = False, acquire: int = 0, los=0,
+                          cfo_scope: str = "frame") -> list:
     """:func:`chain_receive_capture` for every chain of a :class:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup` at once
     (``frames`` is the group's batch): one capture per chain, acquisition (``firsts=None, acquire=J``: three launches for all
     links) and the cut (one launch for all links) in front of the grouped step.  ``ChainReceiveGroup.receive_capture`` says the
     rest; one :class:`ReceiveResult` per chain, bit for bit what :func:`chain_receive_capture` returns for that chain alone."""
-    return group.receive_capture(caps, firsts, strides, sync=sync, cfo=cfo, acquire=acquire, los=los)
+    return group.receive_capture(caps, firsts, strides, sync=sync, cfo=cfo, acquire=acquire, los=los, cfo_scope=cfo_scope)

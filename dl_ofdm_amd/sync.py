@@ -51,6 +51,19 @@ def rotate_response_(H: torch.Tensor, offset: torch.Tensor) -> torch.Tensor:
     return H
 
 
+CFO_SCOPES = ("frame", "capture")
+
+
+def check_cfo_scope(cfo, cfo_scope) -> bool:
+    """``True`` where the carrier offset is pooled over the capture (``cfo_scope="capture"``).  ``ValueError``, before anything is
+    launched, for an unknown scope and for ``"capture"`` without ``cfo``: there is no offset to pool."""
+    if cfo_scope not in CFO_SCOPES:
+        raise ValueError("cfo_scope must be one of %r, got %r" % (CFO_SCOPES, cfo_scope))
+    if cfo_scope == "capture" and not cfo:
+        raise ValueError('cfo_scope="capture" needs cfo=True: there is no carrier offset to pool without it')
+    return cfo_scope == "capture"
+
+
 class FrameSync:
     """Fixed-shape alignment stage on one GPU: ``run(x) -> (aligned, offset)``.
 
@@ -133,10 +146,17 @@ class CaptureSync:
     frame's neighbours in the air, and with ``cfo=True`` they carry no phase step.  The caller leaves ``W`` samples of the capture
     in front of the first frame and behind the last.  ``offset``, ``metric``, ``cfo`` and the output buffer are resident, as
     :class:`FrameSync`'s are; ``out_kin`` as there.
+
+    ``cfo=True, cfo_scope="capture"`` (``dccn_capture_sync_pooled``): a capture comes from one front end with one oscillator, so
+    ONE carrier offset is estimated for the whole call -- from the sum over the frames of each frame's prefix correlation at its own
+    lag -- and every frame is derotated with it; timing stays per frame.  ``self.cfo`` is then ``float32 [1]``.  Three launches
+    (estimate, sum, cut) instead of one, no host round trip; ``offsets`` is not offered.  The default ``"frame"`` is the
+    per-frame estimate above.
     """
 
     def __init__(self, S: int, K: int, CP: int, W: int, frames: int, device="cuda", out_kin: Optional[int] = None,
-                 want_metric: bool = True, cfo: bool = False):
+                 want_metric: bool = True, cfo: bool = False, cfo_scope: str = "frame"):
+        self.pooled = check_cfo_scope(cfo, cfo_scope)
         self.lib = _lib.load()
         self.S, self.K, self.CP, self.W, self.frames = int(S), int(K), int(CP), int(W), int(frames)
         self.T = self.S * (self.K + self.CP)
@@ -152,7 +172,11 @@ class CaptureSync:
                             % (self.out_kin, self.frames))
         self.offset = torch.zeros(self.frames, dtype=torch.int32, device=self.device)
         self.metric = (torch.zeros(self.frames, 2 * self.W + 1, dtype=torch.float32, device=self.device) if want_metric else None)
-        self.cfo = torch.zeros(self.frames, dtype=torch.float32, device=self.device) if cfo else None
+        self.cfo = torch.zeros(1 if self.pooled else self.frames, dtype=torch.float32, device=self.device) if cfo else None
+        self.ws = None
+        if self.pooled:
+            self.ws = torch.empty(int(self.lib.dccn_capture_sync_pooled_workspace_size(self.frames)), dtype=torch.uint8,
+                                  device=self.device)
         self.out = None         # allocated by the first run() that is not given a destination
 
     def _stream(self):
@@ -165,6 +189,8 @@ class CaptureSync:
             raise DccnError("CaptureSync: cap must be a contiguous float32 [n, 2] tensor, got %s %r" % (cap.dtype, tuple(cap.shape)))
         stride = self.T if stride is None else int(stride)
         p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        if self.pooled:
+            return self._launch_pooled(cap, first, stride, out, lo)
         tail = (stride, self.frames, self.S, self.K, self.CP, self.W, self.out_kin, p(out), self.offset.data_ptr(), p(self.cfo),
                 p(self.metric), self._stream())
         if isinstance(first, torch.Tensor):
@@ -177,6 +203,23 @@ class CaptureSync:
                   "dccn_capture_sync_at")
         else:
             check(self.lib.dccn_capture_sync(cap.data_ptr(), int(cap.shape[0]), int(first), *tail), "dccn_capture_sync")
+
+    def _launch_pooled(self, cap, first, stride: int, out: Optional[torch.Tensor], lo: Optional[int]) -> None:
+        """``dccn_capture_sync_pooled``: estimate, sum and cut, three launches on the current stream"""
+        if out is None:
+            raise DccnError('CaptureSync(cfo_scope="capture") has no offsets-only call: the pooled entry writes the frames')
+        on_dev = isinstance(first, torch.Tensor)
+        if on_dev:
+            if lo is None:
+                raise DccnError("CaptureSync: a device tensor `first` needs lo=..., the origin of the range [lo, lo + T) it lies in")
+            if first.device != cap.device or first.dtype != torch.int64 or first.numel() != 1 or not first.is_contiguous():
+                raise DccnError("CaptureSync: a device `first` must be an int64 tensor of one element on the capture's device")
+        check(self.lib.dccn_capture_sync_pooled(cap.data_ptr(), int(cap.shape[0]), 0 if on_dev else int(first),
+                                                first.data_ptr() if on_dev else None, int(lo) if on_dev else 0, stride,
+                                                self.frames, self.S, self.K, self.CP, self.W, self.out_kin, out.data_ptr(),
+                                                self.offset.data_ptr(), self.cfo.data_ptr(),
+                                                None if self.metric is None else self.metric.data_ptr(), self.ws.data_ptr(),
+                                                int(self.ws.numel()), self._stream()), "dccn_capture_sync_pooled")
 
     def run(self, cap: torch.Tensor, first, stride: Optional[int] = None, out: Optional[torch.Tensor] = None,
             lo: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -280,7 +323,7 @@ class _SyncGroupBase:
     """what :class:`FrameSyncGroup` and :class:`CaptureSyncGroup` share: the shape, per-link resident ``offset`` / ``cfo`` /
     ``metric`` (lists of tensors, entry i as the solo class keeps it for link i) and the output buffers"""
 
-    def __init__(self, supported, S, K, CP, W, frames, n_links, device, out_kin, want_metric, cfo):
+    def __init__(self, supported, S, K, CP, W, frames, n_links, device, out_kin, want_metric, cfo, cfo_len=None):
         self.lib = _lib.load()
         name = type(self).__name__
         self.n_links = _group_size(self.lib, n_links, name)
@@ -299,7 +342,8 @@ class _SyncGroupBase:
         self.offset = [torch.zeros(self.frames, dtype=torch.int32, device=dev) for _ in range(n)]
         self.metric = ([torch.zeros(self.frames, 2 * self.W + 1, dtype=torch.float32, device=dev) for _ in range(n)]
                        if want_metric else None)
-        self.cfo = [torch.zeros(self.frames, dtype=torch.float32, device=dev) for _ in range(n)] if cfo else None
+        ncfo = self.frames if cfo_len is None else int(cfo_len)
+        self.cfo = [torch.zeros(ncfo, dtype=torch.float32, device=dev) for _ in range(n)] if cfo else None
         self.out = None         # allocated by the first run() that is not given destinations
 
     def _stream(self):
@@ -365,12 +409,21 @@ class CaptureSyncGroup(_SyncGroupBase):
     ``run(caps, firsts) -> (frames_out, offsets)``, lists with one entry per link.  ``caps[i]``: link i's capture (two links may
     share one); ``firsts[i]``: an integer, or a device ``int64`` tensor of one element together with ``los[i]`` (what
     :class:`CaptureAcquireGroup` left there) -- known and acquired starts mix in one call; ``strides[i]``: ``None`` = ``T``.
-    Entry i of every result is bit for bit what ``CaptureSync.run(caps[i], firsts[i], strides[i], lo=los[i])`` gives."""
+    Entry i of every result is bit for bit what ``CaptureSync.run(caps[i], firsts[i], strides[i], lo=los[i])`` gives.
+
+    ``cfo=True, cfo_scope="capture"`` (``dccn_capture_sync_pooled_grouped``): one carrier offset per link's capture, as
+    :class:`CaptureSync` describes it -- three launches for all links, ``cfo[i]`` is ``float32 [1]``, ``offsets`` is not offered."""
 
     def __init__(self, S: int, K: int, CP: int, W: int, frames: int, n_links: int, device="cuda", out_kin: Optional[int] = None,
-                 want_metric: bool = True, cfo: bool = False):
-        super().__init__("dccn_capture_sync_supported", S, K, CP, W, frames, n_links, device, out_kin, want_metric, cfo)
-        self._table = (_lib.CaptureLink * self.n_links)()
+                 want_metric: bool = True, cfo: bool = False, cfo_scope: str = "frame"):
+        self.pooled = check_cfo_scope(cfo, cfo_scope)
+        super().__init__("dccn_capture_sync_supported", S, K, CP, W, frames, n_links, device, out_kin, want_metric, cfo,
+                         cfo_len=1 if self.pooled else None)
+        self._table = ((_lib.PooledLink if self.pooled else _lib.CaptureLink) * self.n_links)()
+        self.ws = None
+        if self.pooled:
+            nws = int(self.lib.dccn_capture_sync_pooled_workspace_size(self.frames))
+            self.ws = [torch.empty(nws, dtype=torch.uint8, device=self.device) for _ in range(self.n_links)]
 
     def _launch(self, caps, firsts, strides, outs, los) -> None:
         n = self.n_links
@@ -385,13 +438,23 @@ class CaptureSyncGroup(_SyncGroupBase):
                                     "it lies in")
                 if first.device != cap.device or first.dtype != torch.int64 or first.numel() != 1 or not first.is_contiguous():
                     raise DccnError("CaptureSyncGroup: a device `first` must be an int64 tensor of one element on the capture's device")
+        if self.pooled and outs is None:
+            raise DccnError('CaptureSyncGroup(cfo_scope="capture") has no offsets-only call: the pooled entry writes the frames')
         for i, (cap, first) in enumerate(zip(caps, firsts)):
             on_dev = isinstance(first, torch.Tensor)
-            self._table[i] = _lib.CaptureLink(cap.data_ptr(), int(cap.shape[0]), 0 if on_dev else int(first),
-                                              first.data_ptr() if on_dev else None, int(los[i]) if on_dev else 0,
-                                              self.T if strides[i] is None else int(strides[i]),
-                                              None if outs is None else outs[i].data_ptr(), self.offset[i].data_ptr(),
-                                              self._opt(self.cfo, i), self._opt(self.metric, i))
+            link = (cap.data_ptr(), int(cap.shape[0]), 0 if on_dev else int(first),
+                    first.data_ptr() if on_dev else None, int(los[i]) if on_dev else 0,
+                    self.T if strides[i] is None else int(strides[i]),
+                    None if outs is None else outs[i].data_ptr(), self.offset[i].data_ptr(),
+                    self._opt(self.cfo, i), self._opt(self.metric, i))
+            if self.pooled:
+                self._table[i] = _lib.PooledLink(*link, self.ws[i].data_ptr(), int(self.ws[i].numel()))
+            else:
+                self._table[i] = _lib.CaptureLink(*link)
+        if self.pooled:
+            check(self.lib.dccn_capture_sync_pooled_grouped(n, self._table, self.frames, self.S, self.K, self.CP, self.W,
+                                                            self.out_kin, self._stream()), "dccn_capture_sync_pooled_grouped")
+            return
         check(self.lib.dccn_capture_sync_grouped(n, self._table, self.frames, self.S, self.K, self.CP, self.W, self.out_kin,
                                                  self._stream()), "dccn_capture_sync_grouped")
 

@@ -1210,6 +1210,55 @@ int dccn_capture_sync_grouped(int n_links, const dccn_capture_link* links, int f
 int dccn_capture_acquire_grouped(int n_links, const dccn_acquire_link* links, int J, int S, int K, int CP, int n_pilot,
                                  dccn_stream_t stream);
 
+/* ==== one carrier offset per capture, pooled over its frames ====================
+ * dccn_capture_sync estimates the carrier-frequency offset once per frame, from that frame's own S*CP prefix products.  A capture
+ * comes from one front end with one oscillator, so its frames share one offset.  With b_f, offset[f] (theta_f below), Gamma_f,
+ * Lambda_f and metric dccn_capture_sync's, bit for bit:
+ *     Gamma = sum_{f < frames} Gamma_f(theta_f)                          (the plain sum: |Gamma_f| weights a frame by its prefix
+ *                                                                         energy, the ML combination for a common offset)
+ *     cfo   = 0 - atan2(Im Gamma, Re Gamma) / (2 pi)                     (ONE value per call, cfo_out float32[1]; +0 where Gamma = 0)
+ *     out[f][n] = c[b_f + theta_f + n] * exp(-2 pi i cfo n / K),  n = 0 .. T-1     (the phase counted inside the frame, as above)
+ * Timing stays per frame.  ORDER OF THE SUM (real and imaginary parts separately, fp32): 64 partial sums, partial l adding
+ * Gamma_l, Gamma_{l+64}, Gamma_{l+128}, ... in ascending order onto +0; then a butterfly over the partials, d = 1, 2, 4, 8, 16,
+ * 32: partial l becomes partial l + partial (l xor d), every l at once; partial 0 is Gamma.  A Gamma_f passes through at most
+ * ceil(frames/64) - 1 + 6 rounded additions.  The order depends on `frames` alone, not on a grid, the link count or the entry.
+ * Three launches on the stream (the estimate, storing theta_f and Gamma_f; the sum, one wave per link; the cut, which reads
+ * offset[f] and cfo back from device memory, clamps the offset into [-W, W] before it indexes and so touches nothing outside
+ * [b_f - W, b_f + T + W)).  No block waits for another, no atomics, no host round trip; two runs give the same bits.  With
+ * frames == 1, cfo_out[0] and x_out are dccn_capture_sync's (cfo given) bit for bit.
+ * workspace: caller-owned device memory, 16-byte aligned, dccn_capture_sync_pooled_workspace_size(frames) bytes (Gamma_f as
+ * float2 [frames]; 0 for frames <= 0); it holds nothing between calls.
+ * dccn_capture_sync_pooled: first_dev == NULL follows dccn_capture_sync's rules for `first` (lo is ignored); otherwise
+ * dccn_capture_sync_at's for first_dev and lo (`first` is ignored).  x_out and cfo_out are required.  Accepted exactly where
+ * dccn_capture_sync_supported says so.  Refused with DCCN_ERR_INVALID_ARG before anything is launched wherever that entry refuses,
+ * and for x_out, cfo_out or workspace NULL, cfo_out off a 4-byte boundary, workspace off a 16-byte one; a workspace smaller than
+ * the size query's answer: DCCN_ERR_WORKSPACE.  Inside a chain group DCCN_ERR_UNSUPPORTED.
+ * dccn_capture_sync_pooled_grouped: the same three launches for n_links links (the link index on a grid dimension), each with its
+ * own workspace; link i's outputs are bit for bit the solo call's, n_links == 1 is the solo call.  The rules of the grouped entries
+ * above apply: metric for every link or for none; no output range of one link (x_out, offset, cfo, metric, workspace) may overlap
+ * an output or an input (cap, first_dev) of another; a refused call launches nothing and writes nothing for any link. */
+typedef struct dccn_pooled_link {
+    const float* cap;          /* [n_samples,2] */
+    long long n_samples;
+    long long first;           /* used when first_dev == NULL */
+    const long long* first_dev;/* nullable: device int64[1], clamped into [lo, lo + T - 1] */
+    long long lo;              /* read with first_dev only */
+    long long stride;
+    float* x_out;              /* [frames,S,out_kin,2] */
+    int32_t* offset;           /* [frames] */
+    float* cfo;                /* [1]: the capture's estimate */
+    float* metric;             /* nullable (all or none) */
+    void* workspace;           /* dccn_capture_sync_pooled_workspace_size bytes, the link's own */
+    size_t workspace_bytes;
+} dccn_pooled_link;
+size_t dccn_capture_sync_pooled_workspace_size(int frames);
+int dccn_capture_sync_pooled(const float* cap, long long n_samples, long long first, const long long* first_dev /* nullable */,
+                             long long lo, long long stride, int frames, int S, int K, int CP, int W, int out_kin, float* x_out,
+                             int32_t* offset, float* cfo_out, float* metric /* nullable */, void* workspace,
+                             size_t workspace_bytes, dccn_stream_t stream);
+int dccn_capture_sync_pooled_grouped(int n_links, const dccn_pooled_link* links, int frames, int S, int K, int CP, int W,
+                                     int out_kin, dccn_stream_t stream);
+
 /* ==== host utility: CRC32C (Castagnoli), the checksum of TensorFlow's tensor-bundle checkpoints =========
  * (tf.train.Saver files the reference writes at dev/py/ofdmreceiver_np.py:271).
  * Returns the CRC of (previous data ++ data) given the CRC of the previous data (0 to start).  Host code. */

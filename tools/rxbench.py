@@ -24,6 +24,10 @@
     python tools/rxbench.py --capture [--sync 3] [--out FILE]
         receive_capture(cap, first, sync=W[, cfo=True]) on one contiguous capture (dccn_capture_sync) against receive(x, sync=W[,
         cfo=True]) on the same frames cut in advance, and each launch alone; 1170 and 20 000 frames QPSK, same alternation
+    python tools/rxbench.py --capture --cfo --cfo_scope capture [--chains 2 4 8] [--out FILE]
+        the same with receive_capture(..., cfo=True, cfo_scope="capture") added: one carrier offset per capture, pooled over its
+        frames (dccn_capture_sync_pooled: three launches in place of the one), at 73, 1170 and 20 000 frames; with --chains the
+        grouped round with the pooled cut against the per-frame one
     python tools/rxbench.py --acquire [--sync 3] [--out FILE]
         receive_capture(cap, first=None, acquire=J, lo=...) (dccn_capture_acquire + dccn_capture_sync_at + the step) against
         receive_capture(cap, first) with the start known, J = 4 and 16, and the acquisition launches alone; 73 and 1170 frames
@@ -175,10 +179,12 @@ def run_sync(frames, nbits, W, iters, repeats, cfo=False):
             "bytes_moved_by_copy_or_sync": moved, "build_id": _lib.load().dccn_build_id().decode()}
 
 
-def run_capture(frames, nbits, W, iters, repeats):
+def run_capture(frames, nbits, W, iters, repeats, pooled=False):
     """receive_capture(cap, first, sync=W[, cfo=True]) on a contiguous capture against the path it replaces: receive(x, sync=W[,
     cfo=True]) on the same frames cut in advance (both resident on the device), and each launch alone.  The frames carry a true
-    cyclic prefix, so every estimate is 0 and all four calls must return the same bits before anything is timed."""
+    cyclic prefix, so every estimate is 0 and all four calls must return the same bits before anything is timed.
+    ``pooled``: also receive_capture(..., cfo=True, cfo_scope="capture") -- one offset per capture, three launches in place of the
+    one -- and those launches alone; it must return the same bits too."""
     import numpy as np
     import torch
     from dl_ofdm_amd import _lib
@@ -205,18 +211,28 @@ def run_capture(frames, nbits, W, iters, repeats):
                 "cfo": lambda: rc.receive(x, sync=W, cfo=True), "capture_cfo": lambda: rc.receive_capture(cap, T, sync=W, cfo=True),
                 "sync_alone": lambda: fs.run(x), "capture_alone": lambda: cs.run(cap, T),
                 "cfo_alone": lambda: fc.run(x), "capture_cfo_alone": lambda: cc.run(cap, T)}
+    if pooled:
+        r = rc.receive_capture(cap, T, sync=W, cfo=True, cfo_scope="capture")
+        assert int(r.offset.abs().max()) == 0 and torch.equal(a, r.packed) and float(r.cfo.abs().max()) == 0.0 and r.cfo.numel() == 1
+        cp = CaptureSync(S, F, CP, W, frames, "cuda", want_metric=False, cfo=True, cfo_scope="capture")
+        variants["capture_cfo_pooled"] = lambda: rc.receive_capture(cap, T, sync=W, cfo=True, cfo_scope="capture")
+        variants["capture_cfo_pooled_alone"] = lambda: cp.run(cap, T)
     us, spread = timed(variants, iters, repeats)
     return {"frames": frames, "nbits": nbits, "W": W, "iters": iters, "repeats": repeats, "us": us, "spread": spread,
-            "bytes_read_per_frame": {"sync": T * 8, "capture": (T + 2 * W) * 8}, "bytes_written_per_frame": T * 8,
+            "bytes_read_per_frame": {"sync": T * 8, "capture": (T + 2 * W) * 8, "capture_cfo_pooled": (2 * T + 2 * W) * 8},
+            "bytes_written_per_frame": T * 8,
             "build_id": _lib.load().dccn_build_id().decode()}
 
 
 def main_capture(a):
-    """one child process per shape (1170 and 20 000 frames, QPSK), under a time limit; the parent never opens the GPU"""
+    """one child process per shape (1170 and 20 000 frames, QPSK; 73 as well with --cfo_scope capture), under a time limit; the
+    parent never opens the GPU"""
     res, W = [], a.sync or 3
-    for fr, nb in ((1170, 2), (20000, 2)):
+    pooled = a.cfo_scope == "capture"
+    for fr, nb in (((73, 2),) if pooled else ()) + ((1170, 2), (20000, 2)):
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--capture", "--one", "%d,%d" % (fr, nb),
                "--sync", str(W), "--iters", str(a.iters if fr < 10000 else max(a.iters // 5, 10)), "--repeats", str(a.repeats)]
+        cmd += ["--cfo", "--cfo_scope", "capture"] if pooled else []
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         if r.returncode != 0:               # nothing more is started on the GPU after a failure
             sys.stderr.write(r.stderr[-2000:])
@@ -227,7 +243,9 @@ def main_capture(a):
            "variants": {"sync": "receive(x, sync=W) on frames cut in advance", "capture": "receive_capture(cap, first, sync=W)",
                         "cfo": "receive(x, sync=W, cfo=True)", "capture_cfo": "receive_capture(cap, first, sync=W, cfo=True)",
                         "sync_alone": "FrameSync.run(x)", "capture_alone": "CaptureSync.run(cap, first)",
-                        "cfo_alone": "FrameSync(cfo=True).run(x)", "capture_cfo_alone": "CaptureSync(cfo=True).run(cap, first)"},
+                        "cfo_alone": "FrameSync(cfo=True).run(x)", "capture_cfo_alone": "CaptureSync(cfo=True).run(cap, first)",
+                        "capture_cfo_pooled": "receive_capture(cap, first, sync=W, cfo=True, cfo_scope='capture') (--cfo_scope capture)",
+                        "capture_cfo_pooled_alone": "CaptureSync(cfo=True, cfo_scope='capture').run(cap, first) (--cfo_scope capture)"},
            "unit": "us per call (median over repeats of the mean of `iters` back-to-back calls); spread = (max - min) / median",
            "shapes": res}
     print(json.dumps(doc))
@@ -379,7 +397,7 @@ def main_chains(a):
     return 0
 
 
-def run_group_front(mods, frames, W, cfo, want_sync, want_capture, want_acquire, iters, repeats, solo_only=False):
+def run_group_front(mods, frames, W, cfo, want_sync, want_capture, want_acquire, iters, repeats, solo_only=False, pooled=False):
     """G links, each with its own chain and its own clean transmitted capture: a round of the front end + ONE grouped step, with
     (a) the front end issued per link -- FrameSync.run / CaptureSync.run(out=chain.pl.x) / CaptureAcquire.run + CaptureSync.run,
         what a caller of the solo stages does in front of the grouped step -- against
@@ -387,7 +405,9 @@ def run_group_front(mods, frames, W, cfo, want_sync, want_capture, want_acquire,
         acquisition launches, for all links;
     and the front-end launches alone (`*_front`).  (a) and (b) must return the same bits before anything is timed.
     ``solo_only``: the (a) variants alone -- they use nothing an older build of the library lacks, so with DCCN_LIB_PATH naming
-    the parent's build (tools/build_rev.sh, DCCN_LIB_ALLOW_MISSING=1) this times (a) on the parent's kernels."""
+    the parent's build (tools/build_rev.sh, DCCN_LIB_ALLOW_MISSING=1) this times (a) on the parent's kernels.
+    ``pooled`` (with ``cfo`` and ``want_capture``): also the cut with one carrier offset per capture (cfo_scope="capture": three
+    launches per link in (a), three for all links in (b)), as ``*_cut_pooled``."""
     import numpy as np
     import torch
     from dl_ofdm_amd import _lib, ofdm, receiver as R, receiver_mp as H, util
@@ -447,6 +467,17 @@ def run_group_front(mods, frames, W, cfo, want_sync, want_capture, want_acquire,
             variants.update(b_cut=lambda: grp.receive_capture(caps, firsts=true, sync=W, cfo=cfo),
                             b_cut_front=lambda: cg.run(caps, true, outs=outs))
             agree(variants["a_cut"], variants["b_cut"])
+        if pooled and cfo and both:
+            ps = [CaptureSync(S, F, CP, W, frames, "cuda", want_metric=False, cfo=True, cfo_scope="capture") for _ in range(G)]
+            pg = CaptureSyncGroup(S, F, CP, W, frames, G, "cuda", want_metric=False, cfo=True, cfo_scope="capture")
+
+            def a_pooled_front():
+                for s, c, f, o in zip(ps, caps, true, outs):
+                    s.run(c, f, out=o)
+            variants.update(a_cut_pooled=lambda: (a_pooled_front(), step())[1], a_cut_pooled_front=a_pooled_front,
+                            b_cut_pooled=lambda: grp.receive_capture(caps, firsts=true, sync=W, cfo=True, cfo_scope="capture"),
+                            b_cut_pooled_front=lambda: pg.run(caps, true, outs=outs))
+            agree(variants["a_cut_pooled"], variants["b_cut_pooled"])
         for J in (want_acquire or ()):
             acq = [CaptureAcquire(S, F, CP, o.pilotSc, J, "cuda") for o in tx]
             ag = CaptureAcquireGroup(S, F, CP, [np.asarray(o.pilotSc) for o in tx], J, G, "cuda") if both else None
@@ -478,6 +509,7 @@ def main_group_front(a):
                "--frames", str(a.frames), "--iters", str(a.iters), "--repeats", str(a.repeats), "--sync", str(W)]
         cmd += (["--cfo"] if a.cfo else []) + (["--capture"] if a.capture or a.acquire else []) + (["--acquire"] if a.acquire else [])
         cmd += (["--front-sync"] if a.sync else []) + (["--front-solo-only"] if a.front_solo_only else [])
+        cmd += ["--cfo_scope", a.cfo_scope] if a.cfo_scope != "frame" else []
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         if r.returncode != 0:               # nothing more is started on the GPU after a failure
             sys.stderr.write(r.stderr[-2000:])
@@ -490,7 +522,8 @@ def main_group_front(a):
                                "then ONE grouped step",
                         "b_*": "the grouped front end (one alignment or cut launch, three acquisition launches) + the same grouped step",
                         "*_front": "the front-end launches alone",
-                        "sync": "frames cut in advance, alignment", "cut": "captures, starts known", "acquireJ": "captures, starts acquired from J frames"},
+                        "sync": "frames cut in advance, alignment", "cut": "captures, starts known", "acquireJ": "captures, starts acquired from J frames",
+                        "cut_pooled": "captures, starts known, one carrier offset per capture (--cfo --cfo_scope capture)"},
            "unit": "us per round of G links (median over repeats of the mean of `iters` back-to-back rounds); spread = (max - min) / median",
            "groups": res}
     print(json.dumps(doc))
@@ -515,6 +548,8 @@ def main():
     ap.add_argument("--out", default=None, help="--chains / --sync: also write the result document to this file")
     ap.add_argument("--sync", type=int, default=0, help="W: time receive(x) against receive(x, sync=W) on every shape")
     ap.add_argument("--cfo", action="store_true", help="with --sync: also time receive(x, sync=W, cfo=True)")
+    ap.add_argument("--cfo_scope", "--cfo-scope", default="frame", choices=["frame", "capture"],
+                    help="with --capture --cfo: capture also times the offset pooled over the capture (cfo_scope='capture')")
     ap.add_argument("--capture", action="store_true",
                     help="time receive_capture against receive(x, sync=W[, cfo=True]) on the same frames cut in advance (W: --sync, default 3)")
     ap.add_argument("--acquire", action="store_true",
@@ -524,10 +559,12 @@ def main():
                     help="--chains with a front end: only the per-link variants (for DCCN_LIB_PATH = the parent's build)")
     ap.add_argument("--acquire-frames", type=int, nargs="+", default=[4, 16], help="--chains --acquire: the J to time")
     a = ap.parse_args()
+    if a.cfo_scope == "capture" and not (a.cfo and a.capture):
+        ap.error("--cfo_scope capture needs --capture --cfo")
     if a.one_chains and (a.front_sync or a.capture or a.acquire):
         print(json.dumps(run_group_front([int(v) for v in a.one_chains.split(",")], a.frames, a.sync or 3, a.cfo, a.front_sync,
                                          a.capture or a.acquire, a.acquire_frames if a.acquire else None, a.iters, a.repeats,
-                                         a.front_solo_only)))
+                                         a.front_solo_only, a.cfo_scope == "capture")))
         return 0
     if a.chains and (a.sync or a.capture or a.acquire):
         return main_group_front(a)
@@ -540,7 +577,7 @@ def main():
     if a.capture:
         if a.one:
             fr, nb = (int(v) for v in a.one.split(","))
-            print(json.dumps(run_capture(fr, nb, a.sync or 3, a.iters, a.repeats)))
+            print(json.dumps(run_capture(fr, nb, a.sync or 3, a.iters, a.repeats, a.cfo_scope == "capture")))
             return 0
         return main_capture(a)
     if a.one_chains:

@@ -36,6 +36,16 @@ per capture:
     cut            receive(x, sync=W[, cfo=True]) on the same capture cut at the nominal starts (the circular frame)
     baseline       receive(x) on the nominal cut of the capture before the carrier offset, no alignment
 
+``--capture --cfo_scope capture`` (or ``--cfo EPS --cfo_scope capture``: eps ~ U(-EPS, EPS) per capture) adds to every impaired
+row the estimate pooled over the capture's frames (``receive_capture(..., cfo=True, cfo_scope="capture")``: one offset per
+capture, dccn_capture_sync_pooled) next to the per-frame one, and the offset-free arm on the same aligned path:
+
+    capture_pooled       receive_capture(cap, first, sync=W, cfo=True, cfo_scope="capture")
+    capture_offset_free  receive_capture(the capture before the carrier offset, first, sync=W)
+
+with |estimate - eps| of the per-frame estimates (median, p95, worst over the frames) and of the pooled one (median, worst over
+the captures).
+
 ``--acquire J[,J...]`` begins each such capture at a random sample inside frame 0 and asks how often
 ``receive_capture(first=None, acquire=J, lo=W)`` finds the frame start (within W samples: the refinement behind it absorbs that),
 and what the chain's BER is behind it, next to the BER with the start known.
@@ -45,6 +55,7 @@ No threshold: the numbers are the result.
     python tools/syncber.py --nbits 2 --out syncber_out [--load CKPT --rx_load CKPT] [--seeds 3] [--train_sync 3 [--rx_sync]]
     python tools/syncber.py --nbits 2 --cfo 0.05,0.2 --out syncber_out
     python tools/syncber.py --nbits 2 --capture --snrs 5,29 --frames 2000 --out syncber_out
+    python tools/syncber.py --nbits 2 --cfo 0.2 --cfo_scope capture --snrs 5,29 --frames 2000 --out syncber_out
     python tools/syncber.py --nbits 2 --acquire 4,8,16 --snrs 5,30 --frames 73 --captures 30 --out syncber_out
 """
 import argparse
@@ -142,7 +153,9 @@ def capture_rows(a, tr, hf, snrs, log):
     import torch
     from dl_ofdm_amd import ofdm, util
     from dl_ofdm_amd.radio import apply_cfo_stream, rayleigh_chan_lte
-    n, W, lead, EPS = a.frames, a.W, 64, 0.2
+    n, W, lead = a.frames, a.W, 64
+    EPS = float(a.cfo.split(",")[0]) if a.cfo else 0.2
+    pooled = a.cfo_scope == "capture"
     rows = []
     for ch in CAPTURE_CHANNELS:
         fl = copy.deepcopy(hf)
@@ -154,7 +167,9 @@ def capture_rows(a, tr, hf, snrs, log):
         for i, snr in enumerate(snrs):
             for impaired in (False, True):
                 got = {"capture": [], "cut": [], "baseline": []}
-                hist, errs, eps_used = {}, [], []
+                if pooled and impaired:
+                    got.update(capture_pooled=[], capture_offset_free=[])
+                hist, errs, eps_used, pooled_errs = {}, [], [], []
                 for sd in range(a.seeds):
                     np.random.seed(77 + 13 * i + 1009 * sd)
                     bits = util.bit_source(fl.nbits, o.frame_size, n)
@@ -177,6 +192,12 @@ def capture_rows(a, tr, hf, snrs, log):
                     if impaired:
                         d = res.cfo.to(torch.float64) - eps
                         errs.append((d - torch.round(d)).abs())
+                    if pooled and impaired:
+                        resp = tr.receive_capture(cap, lead, sync=W, cfo=True, cfo_scope="capture")
+                        got["capture_pooled"].append(ber(resp))
+                        d = float(resp.cfo[0]) - eps
+                        pooled_errs.append(abs(d - round(d)))
+                        got["capture_offset_free"].append(ber(tr.receive_capture(torch.as_tensor(clean, device=tr.device), lead, sync=W)))
                     x_nom = cap[lead:lead + n * T].view(n, S, K + CP, 2)              # the same capture cut at the nominal starts
                     got["cut"].append(ber(tr.receive(x_nom, sync=W, cfo=impaired)))
                     x_free = torch.as_tensor(clean[lead:lead + n * T], device=tr.device).view(n, S, K + CP, 2)
@@ -185,12 +206,16 @@ def capture_rows(a, tr, hf, snrs, log):
                        "offset_share": {str(k): round(v / (n * a.seeds), 4) for k, v in sorted(hist.items())}}
                 if errs:
                     e = torch.cat(errs)
-                    row["cfo_abs_err"] = {"median": float(e.median()), "p95": float(torch.quantile(e, 0.95))}
+                    row["cfo_abs_err"] = {"median": float(e.median()), "p95": float(torch.quantile(e, 0.95)), "max": float(e.max())}
+                if pooled_errs:
+                    row["cfo_pooled_abs_err"] = {"median": float(np.median(pooled_errs)), "max": float(np.max(pooled_errs)),
+                                                 "per_capture": pooled_errs}
                 for k, v in got.items():
                     row[k] = {"ber": float(np.mean(v)), "min": float(np.min(v)), "max": float(np.max(v))}
                 rows.append(row)
                 print(json.dumps(row), flush=True)
     log["capture_rows"] = rows
+    log["eps_max"] = EPS
     with open(os.path.join(a.out, "syncber_capture_%dmod.json" % a.nbits), "w") as f:
         json.dump(log, f, indent=1)
         f.write("\n")
@@ -202,6 +227,16 @@ def capture_rows(a, tr, hf, snrs, log):
             f.write("| %s | %g | %s | %s | %s | %s | %s |\n"
                     % (r["channel"], r["snr_db"], "U(-0.2, 0.2) per capture" if r["impaired"] else "0", cell(r["capture"]),
                        cell(r["cut"]), cell(r["baseline"]), ", ".join("%s: %.1f %%" % (k, 100 * v) for k, v in r["offset_share"].items())))
+        if pooled:
+            f.write("\n| channel | SNR [dB] | BER offset-free (receive_capture, eps = 0) | BER per-frame estimate | BER pooled estimate | "
+                    "abs(est - eps) per frame: median, p95, worst | abs(est - eps) pooled: median, worst over the captures |\n"
+                    "|---|---|---|---|---|---|---|\n")
+            for r in rows:
+                if r["impaired"]:
+                    e, q = r["cfo_abs_err"], r["cfo_pooled_abs_err"]
+                    f.write("| %s | %g | %s | %s | %s | %.2g, %.2g, %.2g | %.2g, %.2g |\n"
+                            % (r["channel"], r["snr_db"], cell(r["capture_offset_free"]), cell(r["capture"]), cell(r["capture_pooled"]),
+                               e["median"], e["p95"], e["max"], q["median"], q["max"]))
 
 
 def acquire_rows(a, tr, hf, snrs, log):
@@ -300,12 +335,19 @@ def main():
     ap.add_argument("--capture", action="store_true",
                     help="contiguous captures from the host model (run_stream): receive_capture against receive(sync=W[, cfo=True]) on the "
                          "same capture cut at the nominal starts, and the offset-free unaligned baseline; EPA / EVA / ETU at --snrs")
+    ap.add_argument("--cfo_scope", "--cfo-scope", default="frame", choices=["frame", "capture"],
+                    help="capture: the --capture table (also selected by --cfo EPS --cfo_scope capture, eps ~ U(-EPS, EPS) per capture) "
+                         "with the estimate pooled over each capture next to the per-frame one")
     ap.add_argument("--acquire", default=None,
                     help="J[,J...]: captures that begin inside frame 0 (host model as --capture, one eps ~ U(-0.2, 0.2) each): the share "
                          "whose start receive_capture(first=None, acquire=J) finds, and the chain's BER behind it; --frames per capture")
     ap.add_argument("--captures", type=int, default=30, help="--acquire: captures per channel and SNR")
     ap.add_argument("--out", default="syncber_out")
     a = ap.parse_args()
+    if a.cfo_scope == "capture":
+        if not (a.capture or a.cfo) or a.acquire:
+            ap.error("--cfo_scope capture goes with --capture or --cfo EPS")
+        a.capture = True
     import torch
     from dl_ofdm_amd import _lib, ofdm, receiver as R, receiver_mp as H
     from dl_ofdm_amd.datagen import DeviceDataGen
