@@ -276,6 +276,14 @@ SIGNATURES = {
     "dccn_capture_sync_pooled_workspace_size": (_sz, [_i]),
     "dccn_capture_sync_pooled": (_i, [_vp, c_longlong, c_longlong, _vp, c_longlong, c_longlong] + [_i] * 6 + [_vp] * 5 + [_sz, _vp]),
     "dccn_capture_sync_pooled_grouped": (_i, [_i, POINTER(PooledLink)] + [_i] * 6 + [_vp]),
+    # carrier offsets beyond half a subcarrier spacing: acquisition over (q, m), the cuts with the whole offset taken out
+    "dccn_capture_acquire_wide_supported": (_i, [_i] * 6),
+    "dccn_capture_acquire_wide_workspace_size": (_sz, [_i] * 6),
+    "dccn_capture_acquire_wide": (_i, [_vp, c_longlong, c_longlong] + [_i] * 4 + [_vp, _i, _i] + [_vp] * 6 + [_sz, _vp]),
+    "dccn_capture_sync_wide": (_i, [_vp, c_longlong, _vp, c_longlong, c_longlong] + [_i] * 6 + [_vp] * 7),
+    "dccn_capture_sync_pooled_wide_workspace_size": (_sz, [_i]),
+    "dccn_capture_sync_pooled_wide": (_i, [_vp, c_longlong, c_longlong, _vp, c_longlong, c_longlong] + [_i] * 6 + [_vp] * 7
+                                      + [_sz, _vp]),
     "dccn_rx_normalise": (_i, [POINTER(RxShape), POINTER(RxBuffers), _vp]),
     "dccn_rx_graph_create": (_i, [POINTER(RxShape), POINTER(RxBuffers), _i, AdamHParams, _vp, POINTER(c_void_p)]),
     "dccn_rx_graph_launch": (_i, [_vp, _vp]),

@@ -88,6 +88,12 @@ int capture_sync_at_launch(const CaptureSyncPlan& plan, const long long* first_d
     return DCCN_OK;
 }
 
+// the wide cuts' two device inputs (acquisition's m^ and eps^): given, on 4-byte boundaries
+bool wide_inputs_ok(const int32_t* cfo_int_dev, const float* cfo_frac_dev) {
+    return cfo_int_dev && cfo_frac_dev && (reinterpret_cast<uintptr_t>(cfo_int_dev) & 3u) == 0 &&
+           (reinterpret_cast<uintptr_t>(cfo_frac_dev) & 3u) == 0;
+}
+
 // Everything dccn_capture_acquire decides, before its first launch.
 struct CaptureAcquirePlan {
     AcqArgs args;
@@ -468,6 +474,83 @@ int dccn_capture_sync_pooled(const float* cap, long long n_samples, long long fi
                              float* cfo_out, float* metric, void* workspace, size_t workspace_bytes, dccn_stream_t stream) {
     const dccn_pooled_link link{cap, n_samples, first, first_dev, lo, stride, x_out, offset, cfo_out, metric, workspace, workspace_bytes};
     return dccn_capture_sync_pooled_grouped(1, &link, frames, S, K, CP, W, out_kin, stream);
+}
+
+// ---- carrier offsets beyond half a subcarrier spacing: acquisition over (q, m), the cut with the whole offset taken out ---------
+int dccn_capture_acquire_wide_supported(int S, int K, int CP, int n_pilot, int J, int M) {
+    return capture_acquire_wide_shape_ok(S, K, CP, n_pilot, J, M) ? 1 : 0;
+}
+
+size_t dccn_capture_acquire_wide_workspace_size(int S, int K, int CP, int n_pilot, int J, int M) {
+    return capture_acquire_wide_shape_ok(S, K, CP, n_pilot, J, M) ? capture_acquire_wide_layout(S, K, CP, J, M).total : 0;
+}
+
+int dccn_capture_acquire_wide(const float* cap, long long n_samples, long long lo, int J, int S, int K, int CP, const int* pilot_sc,
+                              int n_pilot, int M, long long* first_out, float* cfo_out, int32_t* cfo_int_out, float* sym_metric,
+                              float* phase_metric, void* workspace, size_t workspace_bytes, dccn_stream_t stream) {
+    if (!capture_acquire_wide_shape_ok(S, K, CP, n_pilot, J, M)) return DCCN_ERR_INVALID_ARG;
+    if (!cfo_int_out || (reinterpret_cast<uintptr_t>(cfo_int_out) & 3u) != 0) return DCCN_ERR_INVALID_ARG;
+    const AcqWorkspace w = capture_acquire_wide_layout(S, K, CP, J, M);
+    // the narrow call's checks (the samples read are the same); its workspace is the M = 0 layout, a prefix of this one
+    CaptureAcquirePlan plan;
+    DCCN_TRY(capture_acquire_plan(cap, n_samples, lo, J, S, K, CP, pilot_sc, n_pilot, first_out, cfo_out, sym_metric, phase_metric,
+                                  workspace, workspace_bytes, &plan));
+    if (workspace_bytes < w.total) return DCCN_ERR_WORKSPACE;
+    DCCN_NO_CHAINS();
+    AcqWideArgs args{plan.args, cfo_int_out, M};
+    args.a.rhat = reinterpret_cast<int*>(static_cast<char*>(workspace) + w.rhat);
+    const size_t lds = capture_acquire_wide_lds(S, K, CP, n_pilot, M);
+    DCCN_TRY(set_max_dynamic_smem((const void*)acq_phase_wide_kernel, lds));
+    hipLaunchKernelGGL(acq_symbol_sums_kernel, dim3(plan.sum_blocks), dim3(kAcqSumThreads), 0, (hipStream_t)stream, args.a);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(acq_phase_wide_kernel, dim3((unsigned)S, (unsigned)J), dim3(kAcqThreads), lds, (hipStream_t)stream, args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(acq_decide_wide_kernel, dim3(1), dim3(kAcqWideThreads), 0, (hipStream_t)stream, args);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+int dccn_capture_sync_wide(const float* cap, long long n_samples, const long long* first_dev, long long lo, long long stride,
+                           int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset, float* cfo,
+                           float* metric, const int32_t* cfo_int_dev, const float* cfo_frac_dev, dccn_stream_t stream) {
+    CaptureSyncPlan plan;
+    DCCN_TRY(capture_sync_at_plan(cap, n_samples, first_dev, lo, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo, metric,
+                                  &plan));
+    if (!cfo || !wide_inputs_ok(cfo_int_dev, cfo_frac_dev)) return DCCN_ERR_INVALID_ARG;
+    DCCN_NO_CHAINS();
+    DCCN_TRY(set_max_dynamic_smem((const void*)capture_sync_wide_kernel, plan.lds));
+    hipLaunchKernelGGL(capture_sync_wide_kernel, dim3(plan.blocks), dim3(kSyncWaves * kSyncLanes), plan.lds, (hipStream_t)stream,
+                       CaptureSyncWideArgs{CaptureSyncAtArgs{plan.args, first_dev, lo}, CfoWide{cfo_int_dev, cfo_frac_dev}});
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+size_t dccn_capture_sync_pooled_wide_workspace_size(int frames) { return frames > 0 ? pooled_workspace_bytes(frames) + 16 : 0; }
+
+int dccn_capture_sync_pooled_wide(const float* cap, long long n_samples, long long first, const long long* first_dev, long long lo,
+                                  long long stride, int frames, int S, int K, int CP, int W, int out_kin, float* x_out,
+                                  int32_t* offset, float* cfo_out, float* metric, const int32_t* cfo_int_dev,
+                                  const float* cfo_frac_dev, void* workspace, size_t workspace_bytes, dccn_stream_t stream) {
+    // the pooled call's plan with the fraction's slot (behind Gamma_f in the workspace) where it has cfo_out
+    const size_t gamma_bytes = pooled_workspace_bytes(frames);
+    const dccn_pooled_link link{cap, n_samples, first, first_dev, lo, stride, x_out, offset, cfo_out, metric, workspace, workspace_bytes};
+    PooledGroupPlan plan;
+    DCCN_TRY(pooled_group_plan(1, &link, frames, S, K, CP, W, out_kin, &plan));
+    if (!wide_inputs_ok(cfo_int_dev, cfo_frac_dev)) return DCCN_ERR_INVALID_ARG;
+    if (workspace_bytes < gamma_bytes + 16) return DCCN_ERR_WORKSPACE;
+    DCCN_NO_CHAINS();
+    plan.args.link[0].s.cfo = reinterpret_cast<float*>(static_cast<char*>(workspace) + gamma_bytes);
+    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_estimate_kernel, plan.lds_estimate));
+    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_cut_wide_kernel, plan.lds_cut));
+    const dim3 grid(plan.blocks, 1), block(kSyncWaves * kSyncLanes);
+    hipLaunchKernelGGL(capture_pool_estimate_kernel, grid, block, plan.lds_estimate, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(capture_pool_reduce_kernel, dim3(1), dim3(kSyncLanes), 0, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(capture_pool_cut_wide_kernel, grid, block, plan.lds_cut, (hipStream_t)stream,
+                       PooledWideArgs{plan.args, CfoWide{cfo_int_dev, cfo_frac_dev}, cfo_out});
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
 }
 
 }  // extern "C"

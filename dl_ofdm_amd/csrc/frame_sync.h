@@ -26,6 +26,11 @@
 // dccn_capture_sync_pooled(_grouped) (at the end) estimate ONE carrier offset per capture from the sum of the frames' Gamma_f: the
 // same estimate body with a finish that stores Gamma_f, a one-wave sum in a stated order, and a cut pass that derotates every
 // frame with the common value -- three launches, new instantiations only.
+//
+// dccn_capture_sync_wide / dccn_capture_sync_pooled_wide (at the end) take the WHOLE offset out where it exceeds half a spacing:
+// the prefix's fraction is unwrapped against the pair (m^, eps^) dccn_capture_acquire_wide left on the device (cfo_unwrap), and
+// the frame is derotated with the integer part's turns reduced exactly (frame_cfo_derotate_wide) -- a WIDE instantiation of
+// capture_sync_body, and a pooled cut kernel of its own.
 #pragma once
 #include "common.h"
 
@@ -168,9 +173,21 @@ __device__ __forceinline__ float2 frame_cfo_derotate(const float2 u, const float
     sincospif(2.0f * (turns - rintf(turns)), &sn, &cs);
     return make_float2(u.x * cs + u.y * sn, u.y * cs - u.x * sn);
 }
-template <class At>
+// The wide variant (dccn_capture_sync_wide, at the end): the offset is I + cfo with I a whole number of spacings, 0 <= ipos < K
+// its residue mod K.  I n / K turns are whole but for (ipos n mod K) / K, an exact integer over K, so the phase keeps the
+// roundings above however large I is; with ipos = 0 the turns are the expression above, bit for bit (0 + a = a).  ipos n stays
+// below K T < 2^22: four frames of T samples fit a block's LDS (frame_sync_shape_ok), so T <= 1920.
+__device__ __forceinline__ float2 frame_cfo_derotate_wide(const float2 u, const unsigned ipos, const float cfo, const int n,
+                                                          const int K, const float fK) {
+    const float turns = ((float)(ipos * (unsigned)n % (unsigned)K) + cfo * (float)n) / fK;
+    float sn, cs;
+    sincospif(2.0f * (turns - rintf(turns)), &sn, &cs);
+    return make_float2(u.x * cs + u.y * sn, u.y * cs - u.x * sn);
+}
+template <class At, bool WIDE = false>
 __device__ __forceinline__ void sync_cfo_store(const At at, const float2* y, float* dst_, const int theta, const float cfo,
-                                               const int lane, const int S, const int K, const int CP, const int crop) {
+                                               const int lane, const int S, const int K, const int CP, const int crop,
+                                               const unsigned ipos = 0) {
     const int N = K + CP, T = S * N;
     const int rot = at.slot(theta);
     const float fK = (float)K;
@@ -179,8 +196,14 @@ __device__ __forceinline__ void sync_cfo_store(const At at, const float2* y, flo
     for (int i = lane; i < M / 2; i += kSyncLanes) {
         const int m0 = 2 * i, m1 = 2 * i + 1;
         const int n0 = crop ? (m0 / K) * N + CP + m0 % K : m0, n1 = crop ? (m1 / K) * N + CP + m1 % K : m1;
-        const float2 u = frame_cfo_derotate(y[at.ahead(rot, n0)], cfo, n0, fK);
-        const float2 v = frame_cfo_derotate(y[at.ahead(rot, n1)], cfo, n1, fK);
+        float2 u, v;
+        if constexpr (WIDE) {
+            u = frame_cfo_derotate_wide(y[at.ahead(rot, n0)], ipos, cfo, n0, K, fK);
+            v = frame_cfo_derotate_wide(y[at.ahead(rot, n1)], ipos, cfo, n1, K, fK);
+        } else {
+            u = frame_cfo_derotate(y[at.ahead(rot, n0)], cfo, n0, fK);
+            v = frame_cfo_derotate(y[at.ahead(rot, n1)], cfo, n1, fK);
+        }
         dst[i] = make_float4(u.x, u.y, v.x, v.y);
     }
 }
@@ -202,6 +225,34 @@ __device__ __forceinline__ void sync_finish(const At at, const float2* y, const 
     } else {
         if (x_out) sync_store(at, y, dst, theta, lane, S, K, CP, crop);
     }
+}
+
+// The prefix's fraction unwrapped against what acquisition left on the device (dccn_capture_acquire_wide: m^ and eps^_acq):
+//     ref = (float)m^ + eps^_acq       I = rint(ref - frac), kept inside [-K/2, K/2] (a NaN difference: 0)
+// so a wild device value costs a wrong derotation and nothing else.  ipos = I mod K in [0, K).
+struct CfoWide {
+    const int32_t* cfo_int;     // [1]
+    const float* cfo_frac;      // [1]
+};
+__device__ __forceinline__ int cfo_unwrap(const float frac, const CfoWide w, const int K, unsigned* ipos) {
+    const float lim = (float)(K / 2);
+    const float d = rintf(((float)w.cfo_int[0] + w.cfo_frac[0]) - frac);
+    const int I = d > lim ? K / 2 : (d < -lim ? -(K / 2) : (d == d ? (int)d : 0));
+    *ipos = (unsigned)((I % K + K) % K);
+    return I;
+}
+// sync_finish of the wide variant: cfo_out[f] holds the total, the frame leaves with the whole offset taken out
+template <class At>
+__device__ __forceinline__ void sync_finish_wide(const At at, const float2* y, const long long f, const int theta, const float2 gamma,
+                                                 const int lane, float* x_out, int32_t* offset, float* cfo_out, const int S,
+                                                 const int K, const int CP, const int crop, const CfoWide w) {
+    if (lane == 0) offset[f] = theta;
+    const float frac = cfo_of_gamma(gamma);
+    unsigned ipos;
+    const int I = cfo_unwrap(frac, w, K, &ipos);
+    if (lane == 0) cfo_out[f] = (float)I + frac;
+    if (x_out)
+        sync_cfo_store<At, true>(at, y, x_out + (size_t)f * S * (crop ? K : K + CP) * 2, theta, frac, lane, S, K, CP, crop, ipos);
 }
 
 // The launch, stated once; CFO selects the variant (cfo_out [frames] is written by that variant only).
@@ -293,8 +344,10 @@ __device__ __forceinline__ void capture_window_load(float4* region, const float*
 // The launch, stated once; `first` is where frame 0 nominally starts (the argument, or what dccn_capture_sync_at read).
 // POOL (dccn_capture_sync_pooled's estimate pass, below): the same estimate with another finish -- the frame's offset and
 // Gamma_f(offset) go to offset[f] and gamma_ws[f], and no frame is written.
-template <bool CFO, bool POOL = false>
-__device__ __forceinline__ void capture_sync_body(const CaptureSyncArgs& a, const long long first, float2* gamma_ws = nullptr) {
+// WIDE (dccn_capture_sync_wide, at the end): the CFO variant with sync_finish_wide in place of sync_finish.
+template <bool CFO, bool POOL = false, bool WIDE = false>
+__device__ __forceinline__ void capture_sync_body(const CaptureSyncArgs& a, const long long first, float2* gamma_ws = nullptr,
+                                                  const CfoWide wide = CfoWide{nullptr, nullptr}) {
     extern __shared__ float4 sync_lds[];
     const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
     const int T = a.S * (a.K + a.CP), W = a.W;
@@ -320,6 +373,8 @@ __device__ __forceinline__ void capture_sync_body(const CaptureSyncArgs& a, cons
             a.offset[f] = theta;
             gamma_ws[f] = gamma;
         }
+    } else if constexpr (WIDE) {
+        sync_finish_wide(at, y, f, theta, gamma, lane, a.x_out, a.offset, a.cfo, a.S, a.K, a.CP, a.crop, wide);
     } else {
         sync_finish<CFO>(at, y, f, theta, gamma, lane, a.x_out, a.offset, a.cfo, a.S, a.K, a.CP, a.crop);
     }
@@ -482,6 +537,52 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_c
     const float cfo = l.s.cfo[0];
     sync_cfo_store(SyncLinear{0}, y, l.s.x_out + (size_t)f * g.S * (g.crop ? g.K : g.K + g.CP) * 2, 0, cfo, lane, g.S, g.K, g.CP,
                    g.crop);
+}
+
+// ---- the whole offset taken out: the prefix's fraction unwrapped against acquisition's (m^, eps^_acq) ---------------------------
+// dccn_capture_sync_wide: dccn_capture_sync_at's CFO launch with sync_finish_wide.  dccn_capture_sync_pooled_wide: the pooled
+// call's estimate and reduce launches as they are (the reduce writes the capture's fraction to a workspace slot), then a cut
+// of its own.  Timing, offsets and metric are the existing calls' bits; with m^ = 0 and eps^_acq = 0 so are cfo and the frames.
+struct CaptureSyncWideArgs {
+    CaptureSyncAtArgs at;
+    CfoWide wide;
+};
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_wide_kernel(const CaptureSyncWideArgs a) {
+    const long long hi = a.at.lo + (long long)a.at.s.S * (a.at.s.K + a.at.s.CP) - 1;
+    const long long got = a.at.first_dev[0];
+    capture_sync_body<true, false, true>(a.at.s, got < a.at.lo ? a.at.lo : (got > hi ? hi : got), nullptr, a.wide);
+}
+struct PooledWideArgs {
+    PooledGroupArgs g;          // one link; link[0].s.cfo: the workspace slot of the capture's fraction
+    CfoWide wide;
+    float* total_out;           // [1]
+};
+// capture_pool_cut_kernel's statements (that kernel keeps its own text and instruction stream) with the unwrap in front of the store:
+// link[0].s.cfo holds the capture's fraction, which every block reads; frame 0's wave writes the total to total_out.
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_cut_wide_kernel(const PooledWideArgs a) {
+    extern __shared__ float4 sync_lds[];
+    const PooledGroupArgs& g = a.g;
+    const PooledLink& l = g.link[blockIdx.y];
+    const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
+    const int T = g.S * (g.K + g.CP), W = g.W;
+    const long long f = (long long)blockIdx.x * kSyncWaves + wave;
+    const bool live = f < g.frames;
+    float4* const region = sync_lds + (size_t)wave * (capture_cut_lds_per_frame(T) / 16);
+    long long start = 0;
+    if (live) {
+        const int got = l.s.offset[f];
+        start = pooled_first(l.s, T) + f * l.s.stride + (got < -W ? -W : (got > W ? W : got));
+    }
+    const float2* const y = reinterpret_cast<const float2*>(region) + (int)(start & 1);      // slot 0 = sample start
+    if (live) capture_window_load(region, l.s.cap, start, T, lane);
+    __syncthreads();                                    // (the frame is complete in LDS)
+    if (!live) return;
+    const float cfo = l.s.cfo[0];
+    unsigned ipos;
+    const int I = cfo_unwrap(cfo, a.wide, g.K, &ipos);
+    if (f == 0 && lane == 0) a.total_out[0] = (float)I + cfo;
+    sync_cfo_store<SyncLinear, true>(SyncLinear{0}, y, l.s.x_out + (size_t)f * g.S * (g.crop ? g.K : g.K + g.CP) * 2, 0, cfo, lane,
+                                     g.S, g.K, g.CP, g.crop, ipos);
 }
 
 }  // namespace dccn

@@ -365,7 +365,8 @@ class ChainReceiveGroup:
                 for i, c in enumerate(self.chains)]
 
     def receive_capture(self, caps: Sequence, firsts=None, strides=None, sync: int = 3, cfo: bool = False, acquire: int = 0, los=0,
-                        want_llr: Optional[bool] = None, want_prob: Optional[bool] = None, cfo_scope: str = "frame") -> list:
+                        want_llr: Optional[bool] = None, want_prob: Optional[bool] = None, cfo_scope: str = "frame",
+                        cfo_span: int = 0) -> list:
         """One round on ``batch`` frames per chain that still sit inside contiguous captures: ``caps[i]`` is chain i's capture
         (device tensor ``float32 [n, 2]``; two chains may share one), as ``EqualizerTrainer.receive_capture(caps[i], firsts[i],
         strides[i], sync, cfo, frames=batch, lo=los[i])`` per chain.  ``firsts[i]``: an integer, or a device ``int64`` tensor of
@@ -378,9 +379,15 @@ class ChainReceiveGroup:
         ``offset``, ``cfo``, ``first`` and ``acquired_cfo`` as the solo call returns them.
 
         ``cfo=True, cfo_scope="capture"``: one carrier offset per chain's capture, pooled over its frames
-        (``CaptureSyncGroup(..., cfo_scope="capture")``: three launches for all chains in place of the one)."""
+        (``CaptureSyncGroup(..., cfo_scope="capture")``: three launches for all chains in place of the one).
+
+        ``cfo_span > 0`` is refused (:class:`DccnError`): the grouped link tables carry no integer offset, so carrier offsets
+        beyond half a subcarrier spacing go through the solo calls (``EqualizerTrainer.receive_capture(..., cfo_span=M)``)."""
         from .receive import ReceiveResult
         from .sync import CaptureAcquireGroup, CaptureSyncGroup, _per_link, check_cfo_scope
+        if int(cfo_span) != 0:
+            raise _lib.DccnError("ChainReceiveGroup.receive_capture: cfo_span > 0 is not offered for groups (the grouped entries "
+                                 "have no wide variant); use EqualizerTrainer.receive_capture(..., cfo_span=M) per chain")
         pooled = check_cfo_scope(cfo, cfo_scope)
         n = len(self.chains)
         if len(caps) != n:

@@ -63,13 +63,17 @@ class ReceiveResult:
 
     def __init__(self, packed: torch.Tensor, llr: Optional[torch.Tensor], prob: Optional[torch.Tensor], D: int, nbits: int,
                  offset: Optional[torch.Tensor] = None, cfo: Optional[torch.Tensor] = None,
-                 first: Optional[torch.Tensor] = None, acquired_cfo: Optional[torch.Tensor] = None):
+                 first: Optional[torch.Tensor] = None, acquired_cfo: Optional[torch.Tensor] = None,
+                 acquired_cfo_int: Optional[torch.Tensor] = None):
         self.packed, self.llr, self.prob, self.D, self.nbits = packed, llr, prob, int(D), int(nbits)
         self.offset = offset        # int32 [frames]: the timing offsets of a call with sync > 0 (None otherwise)
         self.cfo = cfo              # float32 [frames]: the carrier-frequency offsets of a call with cfo=True (None otherwise);
                                     # float32 [1] from receive_capture(cfo_scope="capture"): the capture's one offset
         self.first = first          # int64 [1]: frame 0's start as receive_capture(first=None) acquired it (None otherwise)
         self.acquired_cfo = acquired_cfo    # float32 [1]: the carrier-frequency offset acquisition estimated on the way
+        # int32 [1]: the whole subcarrier spacings acquisition found (receive_capture(cfo_span=M > 0); None otherwise).  The
+        # acquired offset is acquired_cfo_int + acquired_cfo, and `cfo` then holds totals.
+        self.acquired_cfo_int = acquired_cfo_int
 
     def bits(self) -> torch.Tensor:
         """``uint8 [frames, D, nbits]``, unpacked on the device."""
@@ -186,7 +190,7 @@ class RxReceiver:
         return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, est)
 
     def receive_capture(self, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False, acquire: int = 0,
-                        lo: int = 0, cfo_scope: str = "frame") -> ReceiveResult:
+                        lo: int = 0, cfo_scope: str = "frame", cfo_span: int = 0) -> ReceiveResult:
         """One receive step on ``batch`` frames that still sit inside one contiguous capture ``cap`` (device tensor ``float32
         [n, 2]``): frame ``f`` nominally starts at sample ``first + f * stride`` (``None``: frames back to back) and may sit up to
         ``sync = W > 0`` samples off.  One launch (:class:`~dl_ofdm_amd.sync.CaptureSync`) stands where ``receive(x, sync=W)``
@@ -203,9 +207,16 @@ class RxReceiver:
         leaves it on the device, the cut reads it there (``dccn_capture_sync_at``), and the receive step follows: one launch
         sequence, no host round trip.  ``lo >= sync``, and the capture must hold the ``batch`` frames from ``lo + T - 1`` on.
         ``first`` may also be such a device ``int64`` tensor of one element itself (with ``lo``).  ``result.first`` /
-        ``result.acquired_cfo``."""
+        ``result.acquired_cfo``.
+
+        ``cfo_span = M > 0`` (needs ``first=None, acquire=J, cfo=True``): nobody knows the oscillator either -- the carrier
+        offset may be up to ``M + 1/2`` subcarrier spacings.  Acquisition decides the frame start and the whole spacings
+        together (``CaptureAcquire(..., cfo_span=M)``), the cut unwraps the prefix's fraction against that and takes the whole
+        offset out (``CaptureSync(..., cfo_span=M)``, either ``cfo_scope``): the same number of launches, no host round trip.
+        ``result.cfo`` holds totals, ``result.acquired_cfo_int`` the acquired integer."""
         from .sync import CaptureSync, check_cfo_scope
         check_cfo_scope(cfo, cfo_scope)
+        M = _checked_cfo_span(cfo_span, first, acquire, cfo)
         W = int(sync)
         if W <= 0:
             raise _lib.DccnError("receive_capture needs sync = W > 0")
@@ -216,35 +227,51 @@ class RxReceiver:
         if K < 1 or kin not in (K + self.CP, K):
             raise _lib.DccnError("receive_capture: K = %d, CP = %d do not fit kin = %d" % (K, self.CP, kin))
         key = ("capture", W, bool(cfo)) if cfo_scope == "frame" else ("capture", W, True, cfo_scope)
+        key += (("span", M),) if M else ()
         if key not in self._syncs:
             self._syncs[key] = CaptureSync(self.dims.S, K, self.CP, W, self.batch, self.device, out_kin=kin, want_metric=False,
-                                           cfo=bool(cfo), cfo_scope=cfo_scope)
+                                           cfo=bool(cfo), cfo_scope=cfo_scope, cfo_span=M)
         cs = self._syncs[key]
-        first, est0 = _acquired_first(self._syncs, first, acquire, cap, lo, self.dims.S, K, self.CP, self.pilot_sc, self.device)
-        _, offset = cs.run(cap, first, stride, out=self.x, lo=lo)             # (lo matters to a device `first` only)
+        first, est0, est_int = _acquired_first(self._syncs, first, acquire, cap, lo, self.dims.S, K, self.CP, self.pilot_sc,
+                                               self.device, M)
+        _, offset = cs.run(cap, first, stride, out=self.x, lo=lo,             # (lo matters to a device `first` only)
+                           acquired=(est_int, est0) if M else None)
         check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
         return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, cs.cfo,
-                             first if isinstance(first, torch.Tensor) else None, est0)
+                             first if isinstance(first, torch.Tensor) else None, est0, est_int)
 
 
-def _acquired_first(stages: dict, first, acquire: int, cap, lo: int, S: int, K: int, CP: int, pilot_sc, device):
-    """``first`` as the cut takes it, and the acquisition's carrier-frequency offset: an integer or a device tensor passes
-    through; ``None`` runs :class:`~dl_ofdm_amd.sync.CaptureAcquire` over ``acquire`` frames (kept in ``stages``)."""
+def _checked_cfo_span(cfo_span, first, acquire, cfo) -> int:
+    """``cfo_span`` as an integer; above 0 it needs acquisition and the carrier offset taken out (the integer is only known
+    through acquisition)"""
+    M = int(cfo_span)
+    if M < 0:
+        raise _lib.DccnError("receive_capture: cfo_span must not be negative")
+    if M and (first is not None or not acquire or not cfo):
+        raise _lib.DccnError("receive_capture(cfo_span=M > 0) needs first=None, acquire=J and cfo=True: the whole subcarrier "
+                             "spacings of the offset are only known through acquisition")
+    return M
+
+
+def _acquired_first(stages: dict, first, acquire: int, cap, lo: int, S: int, K: int, CP: int, pilot_sc, device, cfo_span: int = 0):
+    """``first`` as the cut takes it, and the acquisition's carrier-frequency offset (the fraction, and with ``cfo_span > 0``
+    the integer): an integer or a device tensor passes through; ``None`` runs :class:`~dl_ofdm_amd.sync.CaptureAcquire` over
+    ``acquire`` frames (kept in ``stages``)."""
     from .sync import CaptureAcquire
     if first is not None:
         if acquire:
             raise _lib.DccnError("receive_capture: give `first` or `acquire`, not both")
-        return first, None
+        return first, None, None
     J = int(acquire)
     if J <= 0:
         raise _lib.DccnError("receive_capture(first=None) needs acquire = J > 0, the number of frames acquisition may use")
     if pilot_sc is None:
         raise _lib.DccnError("receive_capture(first=None) needs the frame's pilot cells (RxReceiver(..., pilot_sc=...))")
-    key = ("acquire", J)
+    key = ("acquire", J, cfo_span) if cfo_span else ("acquire", J)
     if key not in stages:
-        stages[key] = CaptureAcquire(S, K, CP, pilot_sc, J, device)
+        stages[key] = CaptureAcquire(S, K, CP, pilot_sc, J, device, cfo_span=cfo_span)
     acq = stages[key]
-    return acq.run(cap, lo), acq.cfo
+    return acq.run(cap, lo), acq.cfo, (acq.cfo_int if cfo_span else None)
 
 
 def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: int = 0, cfo: bool = False) -> ReceiveResult:
@@ -279,7 +306,7 @@ def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: 
 
 def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False,
                           want_llr: bool = False, want_prob: bool = False, frames: Optional[int] = None, acquire: int = 0,
-                          lo: int = 0, cfo_scope: str = "frame") -> ReceiveResult:
+                          lo: int = 0, cfo_scope: str = "frame", cfo_span: int = 0) -> ReceiveResult:
     """:func:`chain_receive` on frames that still sit inside one contiguous capture ``cap`` (device tensor ``float32 [n, 2]``;
     ``EqualizerTrainer.receive_capture``): as :meth:`RxReceiver.receive_capture`, one :class:`~dl_ofdm_amd.sync.CaptureSync`
     launch cuts every frame at its estimated start -- linearly, up to ``sync = W > 0`` samples off ``first + f * stride`` -- and
@@ -291,9 +318,11 @@ def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, syn
     then does not know the start: ``frames=None`` counts the frames that fit from the LAST start of that range on, and with a
     device tensor ``first`` (and ``lo``) ``frames`` must be given.
 
-    ``cfo=True, cfo_scope="capture"``: one carrier offset for the whole capture, as :meth:`RxReceiver.receive_capture`."""
+    ``cfo=True, cfo_scope="capture"``: one carrier offset for the whole capture, as :meth:`RxReceiver.receive_capture`.
+    ``cfo_span = M > 0``: offsets beyond half a subcarrier spacing, as there."""
     from .sync import CaptureSync, check_cfo_scope
     check_cfo_scope(cfo, cfo_scope)
+    M = _checked_cfo_span(cfo_span, first, acquire, cfo)
     if not tr.fused_ok:
         raise _lib.DccnError("the chain's receive path needs the fused equaliser step")
     W = int(sync)
@@ -318,15 +347,18 @@ def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, syn
     pl = tr.resident(int(frames))
     syncs = pl.__dict__.setdefault("_capture_syncs", {})
     key = (W, bool(cfo)) if cfo_scope == "frame" else (W, True, cfo_scope)
+    key += (("span", M),) if M else ()
     if key not in syncs:
-        syncs[key] = CaptureSync(S, K, CP, W, int(frames), tr.device, want_metric=False, cfo=bool(cfo), cfo_scope=cfo_scope)
+        syncs[key] = CaptureSync(S, K, CP, W, int(frames), tr.device, want_metric=False, cfo=bool(cfo), cfo_scope=cfo_scope,
+                                 cfo_span=M)
     cs = syncs[key]
-    first, est0 = _acquired_first(tr.__dict__.setdefault("_capture_acquires", {}), first, acquire, cap, lo, S, K, CP, o.pilotSc,
-                                  tr.device)
-    _, offset = cs.run(cap, first, step, out=pl.x, lo=lo)                     # (lo matters to a device `first` only)
+    first, est0, est_int = _acquired_first(tr.__dict__.setdefault("_capture_acquires", {}), first, acquire, cap, lo, S, K, CP,
+                                           o.pilotSc, tr.device, M)
+    _, offset = cs.run(cap, first, step, out=pl.x, lo=lo,                     # (lo matters to a device `first` only)
+                       acquired=(est_int, est0) if M else None)
     packed, llr, prob = pl.receive(want_llr, want_prob)
     return ReceiveResult(packed, llr, prob, int(o.frame_size), int(tr.FLAGS.nbits), offset, cs.cfo,
-                         first if on_device else None, est0)
+                         first if on_device else None, est0, est_int)
 
 
 def group_receive(group, xs, sync: int = 0, cfo: bool = False) -> list:
@@ -341,9 +373,10 @@ def group_receive(group, xs, sync: int = 0, cfo: bool = False) -> list:
 
 
 def group_receive_capture(group, caps, firsts=None, strides=None, sync: int = 3, cfo: bool = False, acquire: int = 0, los=0,
-                          cfo_scope: str = "frame") -> list:
+                          cfo_scope: str = "frame", cfo_span: int = 0) -> list:
     """:func:`chain_receive_capture` for every chain of a :class:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup` at once
     (``frames`` is the group's batch): one capture per chain, acquisition (``firsts=None, acquire=J``: three launches for all
     links) and the cut (one launch for all links) in front of the grouped step.  ``ChainReceiveGroup.receive_capture`` says the
     rest; one :class:`ReceiveResult` per chain, bit for bit what :func:`chain_receive_capture` returns for that chain alone."""
-    return group.receive_capture(caps, firsts, strides, sync=sync, cfo=cfo, acquire=acquire, los=los, cfo_scope=cfo_scope)
+    return group.receive_capture(caps, firsts, strides, sync=sync, cfo=cfo, acquire=acquire, los=los, cfo_scope=cfo_scope,
+                                 cfo_span=cfo_span)

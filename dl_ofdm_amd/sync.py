@@ -17,7 +17,10 @@ step of ``2 pi eps T / K`` against their neighbours.
 estimator over a window that extends ``W`` samples beyond the nominal frame on both sides, indexed linearly, and the frame cut at
 its estimated start -- the samples the alignment brings in are the frame's neighbours in the air.  :class:`CaptureAcquire`
 (``dccn_capture_acquire``) finds the ``first`` that stage needs -- anywhere in a frame period, not within ``W`` -- and leaves it on
-the device, where ``CaptureSync.run(cap, first_tensor, lo=...)`` reads it.
+the device, where ``CaptureSync.run(cap, first_tensor, lo=...)`` reads it.  ``cfo_span=M`` on both lifts the half-spacing limit
+of the carrier offset: acquisition decides the whole number of spacings together with the frame start
+(``dccn_capture_acquire_wide``), and the cut unwraps the prefix's fraction against it and takes the whole offset out
+(``dccn_capture_sync_wide``, ``dccn_capture_sync_pooled_wide``).
 
 :class:`FrameSyncGroup`, :class:`CaptureSyncGroup` and :class:`CaptureAcquireGroup` run the same stages for several links at once
 (``dccn_frame_sync_grouped``, ``dccn_capture_sync_grouped``, ``dccn_capture_acquire_grouped``: one launch each, acquisition three), the
@@ -152,13 +155,24 @@ class CaptureSync:
     lag -- and every frame is derotated with it; timing stays per frame.  ``self.cfo`` is then ``float32 [1]``.  Three launches
     (estimate, sum, cut) instead of one, no host round trip; ``offsets`` is not offered.  The default ``"frame"`` is the
     per-frame estimate above.
+
+    ``cfo=True, cfo_span=M > 0`` (``dccn_capture_sync_wide``, ``dccn_capture_sync_pooled_wide``; either scope): the offset may
+    exceed half a subcarrier spacing.  ``run(..., acquired=(cfo_int, cfo_frac))`` takes the pair that
+    ``CaptureAcquire(..., cfo_span=M)`` left on the device (``.cfo_int``, ``.cfo``); the prefix's fraction is unwrapped against it,
+    the whole offset is taken out and ``self.cfo`` holds totals.  The integer is only known through acquisition, so with
+    ``cfo_scope="frame"`` the start is a device tensor too.  ``cfo_span=0``, the default, is the calls above.
     """
 
     def __init__(self, S: int, K: int, CP: int, W: int, frames: int, device="cuda", out_kin: Optional[int] = None,
-                 want_metric: bool = True, cfo: bool = False, cfo_scope: str = "frame"):
+                 want_metric: bool = True, cfo: bool = False, cfo_scope: str = "frame", cfo_span: int = 0):
         self.pooled = check_cfo_scope(cfo, cfo_scope)
         self.lib = _lib.load()
         self.S, self.K, self.CP, self.W, self.frames = int(S), int(K), int(CP), int(W), int(frames)
+        self.cfo_span = int(cfo_span)
+        if self.cfo_span and not cfo:
+            raise DccnError("CaptureSync(cfo_span=M > 0) needs cfo=True: there is no carrier offset to unwrap without it")
+        if not (0 <= self.cfo_span <= max(self.K // 2 - 1, 0)):
+            raise DccnError("CaptureSync: cfo_span must lie in [0, K / 2 - 1], got %d at K=%d" % (self.cfo_span, self.K))
         self.T = self.S * (self.K + self.CP)
         self.out_kin = self.K + self.CP if out_kin is None else int(out_kin)
         self.device = torch.device(device)
@@ -175,37 +189,56 @@ class CaptureSync:
         self.cfo = torch.zeros(1 if self.pooled else self.frames, dtype=torch.float32, device=self.device) if cfo else None
         self.ws = None
         if self.pooled:
-            self.ws = torch.empty(int(self.lib.dccn_capture_sync_pooled_workspace_size(self.frames)), dtype=torch.uint8,
-                                  device=self.device)
+            size = (self.lib.dccn_capture_sync_pooled_wide_workspace_size if self.cfo_span
+                    else self.lib.dccn_capture_sync_pooled_workspace_size)
+            self.ws = torch.empty(int(size(self.frames)), dtype=torch.uint8, device=self.device)
         self.out = None         # allocated by the first run() that is not given a destination
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _launch(self, cap, first, stride, out: Optional[torch.Tensor], lo: Optional[int] = None) -> None:
+    def _acquired_pair(self, acquired, cap) -> tuple:
+        """the pointers of ``(cfo_int, cfo_frac)``: ``()`` for a stage built with ``cfo_span=0``, which takes none"""
+        if not self.cfo_span:
+            if acquired is not None:
+                raise DccnError("CaptureSync: `acquired` belongs to a stage built with cfo_span = M > 0")
+            return ()
+        ok = isinstance(acquired, (tuple, list)) and len(acquired) == 2 and all(
+            isinstance(t, torch.Tensor) and t.device == cap.device and t.numel() == 1 and t.is_contiguous() for t in acquired)
+        if not ok or acquired[0].dtype != torch.int32 or acquired[1].dtype != torch.float32:
+            raise DccnError("CaptureSync(cfo_span=M > 0) needs acquired=(cfo_int, cfo_frac): an int32 and a float32 tensor of one "
+                            "element on the capture's device, what CaptureAcquire(cfo_span=M) left there")
+        return (acquired[0].data_ptr(), acquired[1].data_ptr())
+
+    def _launch(self, cap, first, stride, out: Optional[torch.Tensor], lo: Optional[int] = None, acquired=None) -> None:
         if not isinstance(cap, torch.Tensor) or cap.device.type != "cuda":
             raise DccnError("CaptureSync takes a device tensor; there is no CPU fallback")
         if cap.dtype != torch.float32 or cap.dim() != 2 or cap.shape[1] != 2 or not cap.is_contiguous():
             raise DccnError("CaptureSync: cap must be a contiguous float32 [n, 2] tensor, got %s %r" % (cap.dtype, tuple(cap.shape)))
         stride = self.T if stride is None else int(stride)
         p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        pair = self._acquired_pair(acquired, cap)
         if self.pooled:
-            return self._launch_pooled(cap, first, stride, out, lo)
+            return self._launch_pooled(cap, first, stride, out, lo, pair)
+        if pair and not isinstance(first, torch.Tensor):
+            raise DccnError("CaptureSync(cfo_span=M > 0): the per-frame cut reads the start where acquisition left it, a device "
+                            "tensor `first` with lo=...")
         tail = (stride, self.frames, self.S, self.K, self.CP, self.W, self.out_kin, p(out), self.offset.data_ptr(), p(self.cfo),
-                p(self.metric), self._stream())
+                p(self.metric), *pair, self._stream())
         if isinstance(first, torch.Tensor):
             # the start is on the device (CaptureAcquire left it there): nothing is read back
             if lo is None:
                 raise DccnError("CaptureSync: a device tensor `first` needs lo=..., the origin of the range [lo, lo + T) it lies in")
             if first.device != cap.device or first.dtype != torch.int64 or first.numel() != 1 or not first.is_contiguous():
                 raise DccnError("CaptureSync: a device `first` must be an int64 tensor of one element on the capture's device")
-            check(self.lib.dccn_capture_sync_at(cap.data_ptr(), int(cap.shape[0]), first.data_ptr(), int(lo), *tail),
-                  "dccn_capture_sync_at")
+            entry = "dccn_capture_sync_wide" if pair else "dccn_capture_sync_at"
+            check(getattr(self.lib, entry)(cap.data_ptr(), int(cap.shape[0]), first.data_ptr(), int(lo), *tail), entry)
         else:
             check(self.lib.dccn_capture_sync(cap.data_ptr(), int(cap.shape[0]), int(first), *tail), "dccn_capture_sync")
 
-    def _launch_pooled(self, cap, first, stride: int, out: Optional[torch.Tensor], lo: Optional[int]) -> None:
-        """``dccn_capture_sync_pooled``: estimate, sum and cut, three launches on the current stream"""
+    def _launch_pooled(self, cap, first, stride: int, out: Optional[torch.Tensor], lo: Optional[int], pair: tuple = ()) -> None:
+        """``dccn_capture_sync_pooled`` (``pair``: ``dccn_capture_sync_pooled_wide``): estimate, sum and cut, three launches on the
+        current stream"""
         if out is None:
             raise DccnError('CaptureSync(cfo_scope="capture") has no offsets-only call: the pooled entry writes the frames')
         on_dev = isinstance(first, torch.Tensor)
@@ -214,21 +247,22 @@ class CaptureSync:
                 raise DccnError("CaptureSync: a device tensor `first` needs lo=..., the origin of the range [lo, lo + T) it lies in")
             if first.device != cap.device or first.dtype != torch.int64 or first.numel() != 1 or not first.is_contiguous():
                 raise DccnError("CaptureSync: a device `first` must be an int64 tensor of one element on the capture's device")
-        check(self.lib.dccn_capture_sync_pooled(cap.data_ptr(), int(cap.shape[0]), 0 if on_dev else int(first),
-                                                first.data_ptr() if on_dev else None, int(lo) if on_dev else 0, stride,
-                                                self.frames, self.S, self.K, self.CP, self.W, self.out_kin, out.data_ptr(),
-                                                self.offset.data_ptr(), self.cfo.data_ptr(),
-                                                None if self.metric is None else self.metric.data_ptr(), self.ws.data_ptr(),
-                                                int(self.ws.numel()), self._stream()), "dccn_capture_sync_pooled")
+        entry = "dccn_capture_sync_pooled_wide" if pair else "dccn_capture_sync_pooled"
+        check(getattr(self.lib, entry)(cap.data_ptr(), int(cap.shape[0]), 0 if on_dev else int(first),
+                                       first.data_ptr() if on_dev else None, int(lo) if on_dev else 0, stride,
+                                       self.frames, self.S, self.K, self.CP, self.W, self.out_kin, out.data_ptr(),
+                                       self.offset.data_ptr(), self.cfo.data_ptr(),
+                                       None if self.metric is None else self.metric.data_ptr(), *pair, self.ws.data_ptr(),
+                                       int(self.ws.numel()), self._stream()), entry)
 
     def run(self, cap: torch.Tensor, first, stride: Optional[int] = None, out: Optional[torch.Tensor] = None,
-            lo: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+            lo: Optional[int] = None, acquired=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Estimate every frame's offset and write the frames, cut at their estimated starts (and with ``cfo=True`` derotated),
         to ``out`` (``None``: this object's own buffer), on the current stream.  ``out`` must not overlap ``cap``.
 
         ``first``: an integer, or a device ``int64`` tensor of one element together with ``lo`` (``dccn_capture_sync_at``: the
         launch reads the start from device memory and keeps it inside ``[lo, lo + T - 1]``; every window must lie inside the
-        capture for every start in that range)."""
+        capture for every start in that range).  ``acquired``: the pair of a stage built with ``cfo_span = M > 0``."""
         want = (self.frames, self.S, self.out_kin, 2)
         if out is None:
             if self.out is None:
@@ -237,12 +271,13 @@ class CaptureSync:
         elif (not isinstance(out, torch.Tensor) or out.device.type != "cuda" or out.dtype != torch.float32
               or tuple(out.shape) != want or not out.is_contiguous()):
             raise DccnError("CaptureSync.run: out must be a contiguous float32 %r device tensor" % (want,))
-        self._launch(cap, first, stride, out, lo)
+        self._launch(cap, first, stride, out, lo, acquired)
         return out, self.offset
 
-    def offsets(self, cap: torch.Tensor, first, stride: Optional[int] = None, lo: Optional[int] = None) -> torch.Tensor:
-        """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``.  ``first`` / ``lo`` as :meth:`run`."""
-        self._launch(cap, first, stride, None, lo)
+    def offsets(self, cap: torch.Tensor, first, stride: Optional[int] = None, lo: Optional[int] = None, acquired=None) -> torch.Tensor:
+        """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``.  ``first`` / ``lo`` / ``acquired`` as
+        :meth:`run`."""
+        self._launch(cap, first, stride, None, lo, acquired)
         return self.offset
 
 
@@ -257,11 +292,18 @@ class CaptureAcquire:
     back (stride ``T``), and ``lo + (J + 2) T`` samples of the capture must exist.  ``first``, ``cfo`` (``float32 [1]``,
     subcarrier spacings), ``sym_metric`` (``float32 [K + CP]``) and ``phase_metric`` (``float32 [S]``) are resident: the next
     ``run`` overwrites them.  ``J = 1`` with BPSK data can tie exactly; a batch's worth of frames (``J = 16``) is the intended
-    setting (README)."""
+    setting (README).
 
-    def __init__(self, S: int, K: int, CP: int, pilot_sc, J: int, device="cuda"):
+    ``cfo_span = M > 0`` (``dccn_capture_acquire_wide``): the carrier offset may exceed half a subcarrier spacing.  Stage B then
+    decides the symbol position and the whole number of spacings ``m`` in ``[-M, M]`` together, from the pilots' bins shifted by
+    ``m``; ``cfo`` stays the fraction, ``cfo_int`` (``int32 [1]``, resident) is ``m``, the offset is their sum, and
+    ``phase_metric`` is ``float32 [S, 2 M + 1]``.  ``M <= K / 2 - 1``; the shift is circular in ``K``, so on the reference grid
+    ``M <= 7`` is the span a real channel filter supports.  ``cfo_span=0``, the default, is the narrow call (``cfo_int`` stays 0)."""
+
+    def __init__(self, S: int, K: int, CP: int, pilot_sc, J: int, device="cuda", cfo_span: int = 0):
         self.lib = _lib.load()
         self.S, self.K, self.CP, self.J = int(S), int(K), int(CP), int(J)
+        self.cfo_span = int(cfo_span)
         self.T = self.S * (self.K + self.CP)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -276,7 +318,16 @@ class CaptureAcquire:
         self.cfo = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.sym_metric = torch.zeros(self.K + self.CP, dtype=torch.float32, device=self.device)
         self.phase_metric = torch.zeros(self.S, dtype=torch.float32, device=self.device)
-        nws = int(self.lib.dccn_capture_acquire_workspace_size(self.S, self.K, self.CP, self.n_pilot, self.J))
+        self.cfo_int = torch.zeros(1, dtype=torch.int32, device=self.device)
+        M = self.cfo_span
+        if M:
+            if not self.lib.dccn_capture_acquire_wide_supported(self.S, self.K, self.CP, self.n_pilot, self.J, M):
+                raise DccnError("dccn_capture_acquire_wide_supported refused cfo_span=%d at K=%d (needs 0 <= cfo_span <= K / 2 - 1)"
+                                % (M, self.K))
+            self.phase_metric = torch.zeros(self.S, 2 * M + 1, dtype=torch.float32, device=self.device)
+            nws = int(self.lib.dccn_capture_acquire_wide_workspace_size(self.S, self.K, self.CP, self.n_pilot, self.J, M))
+        else:
+            nws = int(self.lib.dccn_capture_acquire_workspace_size(self.S, self.K, self.CP, self.n_pilot, self.J))
         self.ws = torch.empty(nws, dtype=torch.uint8, device=self.device)
 
     def run(self, cap: torch.Tensor, lo: int = 0) -> torch.Tensor:
@@ -287,6 +338,13 @@ class CaptureAcquire:
             raise DccnError("CaptureAcquire: cap must be a contiguous float32 [n, 2] tensor, got %s %r"
                             % (cap.dtype, tuple(cap.shape)))
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if self.cfo_span:
+            check(self.lib.dccn_capture_acquire_wide(cap.data_ptr(), int(cap.shape[0]), int(lo), self.J, self.S, self.K, self.CP,
+                                                     self.pilot_sc.data_ptr(), self.n_pilot, self.cfo_span, self.first.data_ptr(),
+                                                     self.cfo.data_ptr(), self.cfo_int.data_ptr(), self.sym_metric.data_ptr(),
+                                                     self.phase_metric.data_ptr(), self.ws.data_ptr(), int(self.ws.numel()),
+                                                     stream), "dccn_capture_acquire_wide")
+            return self.first
         check(self.lib.dccn_capture_acquire(cap.data_ptr(), int(cap.shape[0]), int(lo), self.J, self.S, self.K, self.CP,
                                             self.pilot_sc.data_ptr(), self.n_pilot, self.first.data_ptr(), self.cfo.data_ptr(),
                                             self.sym_metric.data_ptr(), self.phase_metric.data_ptr(), self.ws.data_ptr(),

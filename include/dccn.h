@@ -1259,6 +1259,66 @@ int dccn_capture_sync_pooled(const float* cap, long long n_samples, long long fi
 int dccn_capture_sync_pooled_grouped(int n_links, const dccn_pooled_link* links, int frames, int S, int K, int CP, int W,
                                      int out_kin, dccn_stream_t stream);
 
+/* ==== carrier offsets beyond half a subcarrier spacing ==========================
+ * The prefix correlation gives the offset modulo one subcarrier spacing.  An offset eps = m + f (m whole, |f| < 1/2) moves the
+ * pilots from the bins k_i to k_i + m; they are boosted, their comb is broken by the DC gap and guard carriers surround the
+ * band, so stage B's metric evaluated at shifted bins has one clear maximum over (symbol position q, integer shift m).
+ * dccn_capture_acquire_wide: stage A as dccn_capture_acquire (r^, and eps^ = the fraction).  Stage B over both:
+ *     Y_{j,q,s}[k] as above (twiddle turns ((k n mod K) + eps^ n) / K, n ascending)
+ *     D_j(q,m) = sum_{pilot symbols s, ascending} | sum_{i ascending} Y_{j,q,s}[(k_i+m) mod K] * conj(Y_{j,q,s}[(k_{i+1}+m) mod K]) |
+ *     D(q,m) = sum_{j<J, ascending} D_j(q,m)      m in [-M, M]
+ *     (q^, m^) = the first maximum of D in row-major order of [S, 2M+1]
+ *     first = lo + r^ + q^*N        cfo_out = eps^ (the fraction)        cfo_int_out = m^ (int32[1])
+ * The total offset is m^ + eps^.  phase_metric (nullable) is [S, 2M+1].  M is the search span in subcarrier spacings,
+ * 0 <= M <= K/2 - 1 (the 2M+1 shifts of a carrier are distinct bins); no tighter cap: the block's LDS (the narrow block's plus
+ * Y of all K bins, K marks and 2M+1 sums) stays under 64 KB for every shape dccn_capture_acquire accepts.  The shift is
+ * circular in K: the model is a pure rotation, and on the reference grid (K = 64, 14 guard carriers around the band) M <= 7 keeps the
+ * occupied carriers inside [0, K); beyond that the search wraps, which a real channel filter does not.
+ * At M == 0, first_out, cfo_out, sym_metric and phase_metric are dccn_capture_acquire's, bit for bit; at any M, sym_metric and
+ * cfo_out are, and so is column m = 0 of phase_metric (the same sums in the same order).
+ * Three launches: dccn_capture_acquire's first as it is; Lambda, r^, eps^ and D_j(q,m), one block per (q, j) -- per pilot symbol
+ * every bin some (pilot, m) pair reads is computed once, one thread per bin, then one thread per m forms the modulus; D, (q^, m^),
+ * first and m^, one block.  No atomics, no host round trip, the sums in the order stated: two runs give the same bits.  The
+ * samples read are dccn_capture_acquire's; pilot_sc is untrusted as there, every bin taken mod K.
+ * dccn_capture_acquire_wide_workspace_size: the narrow layout with D_j(q,m) [S, 2M+1, J]; 0 for an unsupported shape.
+ * Refused before anything is launched: wherever dccn_capture_acquire refuses; M < 0 or M > K/2 - 1; cfo_int_out NULL or off a
+ * 4-byte boundary -- DCCN_ERR_INVALID_ARG; a short workspace DCCN_ERR_WORKSPACE; inside a chain group DCCN_ERR_UNSUPPORTED. */
+int dccn_capture_acquire_wide_supported(int S, int K, int CP, int n_pilot, int J, int M);
+size_t dccn_capture_acquire_wide_workspace_size(int S, int K, int CP, int n_pilot, int J, int M);
+int dccn_capture_acquire_wide(const float* cap, long long n_samples, long long lo, int J, int S, int K, int CP, const int* pilot_sc,
+                              int n_pilot, int M, long long* first_out, float* cfo_out, int32_t* cfo_int_out,
+                              float* sym_metric /* nullable */, float* phase_metric /* nullable */, void* workspace,
+                              size_t workspace_bytes, dccn_stream_t stream);
+/* The cut with the whole offset taken out.  cfo_int_dev int32[1] and cfo_frac_dev float32[1] are device memory, what
+ * dccn_capture_acquire_wide left in cfo_int_out and cfo_out.  The fraction the prefix gives (eps_f per frame; the pooled eps for
+ * the pooled entry) is unwrapped against them:
+ *     ref = (float)m^ + eps^_acq        I = rint(ref - eps_f), kept inside [-K/2, K/2] (0 where the difference is NaN)
+ *     cfo[f] = (float)I + eps_f
+ *     out[f][n] = c[b_f + offset[f] + n] * exp(-2 pi i ((I n mod K) + eps_f n) / K)
+ * The whole turns of I n / K drop out exactly ((I n mod K) is an integer), so the phase carries the roundings of the narrow
+ * derotation however large I is; cfo * n is never formed with the total.  A frame whose own fraction lands on the other side
+ * of +-1/2 from acquisition's still gets the right total (2.49 read as -0.49 gives I = 3).  A wild device value costs a wrong
+ * derotation, nothing else.
+ * dccn_capture_sync_wide: dccn_capture_sync_at with cfo given, plus the two inputs; offset and metric are that call's bits, and
+ * with m^ = 0, eps^_acq = 0 so are cfo and x_out.  One launch.  Refused wherever dccn_capture_sync_at refuses, and for cfo,
+ * cfo_int_dev or cfo_frac_dev NULL or the latter two off a 4-byte boundary.
+ * dccn_capture_sync_pooled_wide: dccn_capture_sync_pooled plus the two inputs; first / first_dev / lo as there.  Its estimate and
+ * sum launches as they are (the capture's fraction goes to a workspace slot), then a cut that unwraps it; cfo_out[0] is the
+ * total.  With m^ = 0, eps^_acq = 0 every output is dccn_capture_sync_pooled's, bit for bit.  workspace:
+ * dccn_capture_sync_pooled_wide_workspace_size(frames) bytes (16 more than the pooled call's).  Refused wherever
+ * dccn_capture_sync_pooled refuses, and for the two inputs as above; a short workspace DCCN_ERR_WORKSPACE.
+ * Both: a refused call launches nothing; inside a chain group DCCN_ERR_UNSUPPORTED; two runs give the same bits. */
+int dccn_capture_sync_wide(const float* cap, long long n_samples, const long long* first_dev, long long lo, long long stride,
+                           int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset, float* cfo,
+                           float* metric /* nullable */, const int32_t* cfo_int_dev, const float* cfo_frac_dev,
+                           dccn_stream_t stream);
+size_t dccn_capture_sync_pooled_wide_workspace_size(int frames);
+int dccn_capture_sync_pooled_wide(const float* cap, long long n_samples, long long first, const long long* first_dev /* nullable */,
+                                  long long lo, long long stride, int frames, int S, int K, int CP, int W, int out_kin,
+                                  float* x_out, int32_t* offset, float* cfo_out, float* metric /* nullable */,
+                                  const int32_t* cfo_int_dev, const float* cfo_frac_dev, void* workspace, size_t workspace_bytes,
+                                  dccn_stream_t stream);
+
 /* ==== host utility: CRC32C (Castagnoli), the checksum of TensorFlow's tensor-bundle checkpoints =========
  * (tf.train.Saver files the reference writes at dev/py/ofdmreceiver_np.py:271).
  * Returns the CRC of (previous data ++ data) given the CRC of the previous data (0 to start).  Host code. */

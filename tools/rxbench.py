@@ -28,10 +28,11 @@
         the same with receive_capture(..., cfo=True, cfo_scope="capture") added: one carrier offset per capture, pooled over its
         frames (dccn_capture_sync_pooled: three launches in place of the one), at 73, 1170 and 20 000 frames; with --chains the
         grouped round with the pooled cut against the per-frame one
-    python tools/rxbench.py --acquire [--sync 3] [--out FILE]
+    python tools/rxbench.py --acquire [--sync 3] [--cfo_span 7 31] [--out FILE]
         receive_capture(cap, first=None, acquire=J, lo=...) (dccn_capture_acquire + dccn_capture_sync_at + the step) against
         receive_capture(cap, first) with the start known, J = 4 and 16, and the acquisition launches alone; 73 and 1170 frames
-        QPSK, same alternation
+        QPSK, same alternation.  --cfo_span M ...: also dccn_capture_acquire_wide alone at every M against dccn_capture_acquire of
+        the same build, and receive_capture(..., cfo=True, acquire=16, cfo_span=M) against cfo_span=0, per frame and pooled
 
 Shapes: 1170 frames QPSK and 16-QAM, and one 20 000-frame QPSK sweep batch (N = 64).  Every shape runs in a child process of
 its own under a time limit; the parent never opens the GPU and stops at the first child that fails.  Times are medians over
@@ -256,10 +257,13 @@ def main_capture(a):
     return 0
 
 
-def run_acquire(frames, nbits, W, iters, repeats):
+def run_acquire(frames, nbits, W, iters, repeats, spans=()):
     """receive_capture(cap, first=None, acquire=J, lo=...) (acquisition + cut + step) against receive_capture(cap, first) with the
     start known on the host, on one clean transmitted capture that begins inside frame 0; and the acquisition launches alone at
-    J = 4 and J = 16.  Both calls must find the same start and return the same bits before anything is timed."""
+    J = 4 and J = 16.  Both calls must find the same start and return the same bits before anything is timed.
+    ``spans`` (--cfo_span M ...): also the wide acquisition launches alone at every M (dccn_capture_acquire_wide against
+    dccn_capture_acquire of the same build), and receive_capture(..., cfo=True, acquire=16, cfo_span=M) against cfo_span=0, per
+    frame and pooled; the capture carries no offset, so every call must find m^ = 0."""
     import numpy as np
     import torch
     from dl_ofdm_amd import _lib, ofdm, util
@@ -287,9 +291,22 @@ def run_acquire(frames, nbits, W, iters, repeats):
                 "acquire4": lambda: rc.receive_capture(cap, sync=W, acquire=4, lo=lo),
                 "acquire16": lambda: rc.receive_capture(cap, sync=W, acquire=16, lo=lo),
                 "acquire4_alone": lambda: a4.run(cap, lo), "acquire16_alone": lambda: a16.run(cap, lo)}
+    if spans:
+        for scope, tag in (("frame", ""), ("capture", "_pooled")):
+            variants["acquire16_cfo" + tag] = lambda sc=scope: rc.receive_capture(cap, sync=W, cfo=True, acquire=16, lo=lo, cfo_scope=sc)
+    for M in spans:
+        for J in (4, 16):
+            wide = CaptureAcquire(S, F, CP, o.pilotSc, J, "cuda", cfo_span=M)
+            assert int(wide.run(cap, lo)[0]) == true and int(wide.cfo_int[0]) == 0
+            variants["acquire%d_span%d_alone" % (J, M)] = lambda w=wide: w.run(cap, lo)
+        for scope, tag in (("frame", ""), ("capture", "_pooled")):
+            call = lambda sc=scope, M=M: rc.receive_capture(cap, sync=W, cfo=True, acquire=16, lo=lo, cfo_scope=sc, cfo_span=M)  # noqa: E731
+            r = call()
+            assert int(r.first[0]) == true and int(r.acquired_cfo_int[0]) == 0 and float(r.cfo.abs().max()) < 1e-3
+            variants["acquire16_cfo%s_span%d" % (tag, M)] = call
     us, spread = timed(variants, iters, repeats)
-    return {"frames": frames, "nbits": nbits, "W": W, "iters": iters, "repeats": repeats, "us": us, "spread": spread,
-            "build_id": _lib.load().dccn_build_id().decode()}
+    return {"frames": frames, "nbits": nbits, "W": W, "iters": iters, "repeats": repeats, "spans": list(spans), "us": us,
+            "spread": spread, "build_id": _lib.load().dccn_build_id().decode()}
 
 
 def main_acquire(a):
@@ -298,6 +315,7 @@ def main_acquire(a):
     for fr, nb in ((73, 2), (1170, 2)):
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--acquire", "--one", "%d,%d" % (fr, nb),
                "--sync", str(W), "--iters", str(a.iters), "--repeats", str(a.repeats)]
+        cmd += ["--cfo_span"] + [str(M) for M in a.cfo_span] if a.cfo_span else []
         r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         if r.returncode != 0:               # nothing more is started on the GPU after a failure
             sys.stderr.write(r.stderr[-2000:])
@@ -309,7 +327,11 @@ def main_acquire(a):
                         "acquire4": "receive_capture(cap, first=None, sync=W, acquire=4, lo=5)",
                         "acquire16": "receive_capture(cap, first=None, sync=W, acquire=16, lo=5)",
                         "acquire4_alone": "CaptureAcquire(J=4).run(cap, lo): the three acquisition launches",
-                        "acquire16_alone": "CaptureAcquire(J=16).run(cap, lo)"},
+                        "acquire16_alone": "CaptureAcquire(J=16).run(cap, lo)",
+                        "acquireJ_spanM_alone": "CaptureAcquire(J, cfo_span=M).run(cap, lo): dccn_capture_acquire_wide (--cfo_span)",
+                        "acquire16_cfo[_pooled]": "receive_capture(cap, first=None, sync=W, cfo=True, acquire=16, lo=5[, "
+                                                  "cfo_scope='capture']) (--cfo_span)",
+                        "acquire16_cfo[_pooled]_spanM": "the same with cfo_span=M (--cfo_span)"},
            "unit": "us per call (median over repeats of the mean of `iters` back-to-back calls); spread = (max - min) / median",
            "shapes": res}
     print(json.dumps(doc))
@@ -554,6 +576,9 @@ def main():
                     help="time receive_capture against receive(x, sync=W[, cfo=True]) on the same frames cut in advance (W: --sync, default 3)")
     ap.add_argument("--acquire", action="store_true",
                     help="time receive_capture(first=None, acquire=J) against receive_capture(first=int), and the acquisition launches alone")
+    ap.add_argument("--cfo_span", "--cfo-span", type=int, nargs="+", default=[],
+                    help="with --acquire: also time the wide acquisition (dccn_capture_acquire_wide) at these spans M, and "
+                         "receive_capture(..., cfo=True, cfo_span=M) against cfo_span=0")
     ap.add_argument("--front-sync", action="store_true", help="(internal, with --one-chains: time the alignment of frames cut in advance)")
     ap.add_argument("--front-solo-only", action="store_true",
                     help="--chains with a front end: only the per-link variants (for DCCN_LIB_PATH = the parent's build)")
@@ -571,7 +596,7 @@ def main():
     if a.acquire:
         if a.one:
             fr, nb = (int(v) for v in a.one.split(","))
-            print(json.dumps(run_acquire(fr, nb, a.sync or 3, a.iters, a.repeats)))
+            print(json.dumps(run_acquire(fr, nb, a.sync or 3, a.iters, a.repeats, a.cfo_span)))
             return 0
         return main_acquire(a)
     if a.capture:

@@ -48,7 +48,9 @@ the captures).
 
 ``--acquire J[,J...]`` begins each such capture at a random sample inside frame 0 and asks how often
 ``receive_capture(first=None, acquire=J, lo=W)`` finds the frame start (within W samples: the refinement behind it absorbs that),
-and what the chain's BER is behind it, next to the BER with the start known.
+and what the chain's BER is behind it, next to the BER with the start known.  ``--cfo_span M`` draws the fraction from
+U(-1/2, 1/2) and adds every capture under eps = m + f, m uniform in [-M, M]: how often ``receive_capture(..., acquire=J,
+cfo_span=M)`` finds the start and the whole offset, the BER behind it, and the BER of the narrow call on the same captures.
 
 No threshold: the numbers are the result.
 
@@ -57,6 +59,7 @@ No threshold: the numbers are the result.
     python tools/syncber.py --nbits 2 --capture --snrs 5,29 --frames 2000 --out syncber_out
     python tools/syncber.py --nbits 2 --cfo 0.2 --cfo_scope capture --snrs 5,29 --frames 2000 --out syncber_out
     python tools/syncber.py --nbits 2 --acquire 4,8,16 --snrs 5,30 --frames 73 --captures 30 --out syncber_out
+    python tools/syncber.py --nbits 2 --acquire 4,8,16 --cfo_span 7 --snrs 5,30 --frames 73 --captures 30 --out syncber_out
 """
 import argparse
 import copy
@@ -243,11 +246,16 @@ def acquire_rows(a, tr, hf, snrs, log):
     """the --acquire table: one row per (channel, SNR): the share of captures whose start acquisition finds (within W samples of
     the true frame start: the refinement behind it absorbs that) at each J, and the chain's BER behind it against the BER with the
     start known.  Captures as in capture_rows (run_stream, white noise, one eps ~ U(-0.2, 0.2) per capture), each beginning at a
-    random sample inside frame 0; the search starts at lo = W."""
+    random sample inside frame 0; the search starts at lo = W.
+
+    ``--cfo_span M``: the fraction is drawn from U(-1/2, 1/2) and every capture exists twice, under eps = f (the columns above, the
+    narrow path) and under eps = m + f, m uniform in [-M, M]: there ``receive_capture(..., acquire=J, cfo_span=M)`` must find the
+    start and the whole offset (|m^ + eps^ - eps| < 0.1), and the narrow call at the largest J shows what the offset costs it."""
     import torch
     from dl_ofdm_amd import ofdm, util
     from dl_ofdm_amd.radio import apply_cfo_stream, rayleigh_chan_lte
-    n, W, lead, EPS = a.frames, a.W, 64, 0.2
+    M = int(a.cfo_span)
+    n, W, lead, EPS = a.frames, a.W, 64, (0.5 if M else 0.2)
     Js = [int(v) for v in a.acquire.split(",")]
     lo = W
     rows = []
@@ -265,6 +273,8 @@ def acquire_rows(a, tr, hf, snrs, log):
             ber_right = {J: [] for J in Js}
             ber_all = {J: [] for J in Js}
             ber_known = []
+            wide = {J: {"right": 0, "int_right": 0, "ber_right": [], "ber_all": []} for J in Js}
+            ber_narrow_on_wide = []
             for c_i in range(a.captures):
                 np.random.seed(177 + 13 * i + 1009 * c_i)
                 bits = util.bit_source(fl.nbits, o.frame_size, n_tx)
@@ -292,12 +302,33 @@ def acquire_rows(a, tr, hf, snrs, log):
                     if abs(d) <= W:
                         right[J] += 1
                         ber_right[J].append(b)
+                if M:
+                    m = int(np.random.randint(-M, M + 1))
+                    full = apply_cfo_stream(np.stack([c.real, c.imag], axis=-1).astype(np.float32), m + eps, K)
+                    capw = torch.as_tensor(np.ascontiguousarray(full[lead + cut:]), device=tr.device)
+                    for J in Js:
+                        res = tr.receive_capture(capw, sync=W, cfo=True, frames=n, acquire=J, lo=lo, cfo_span=M)
+                        d = (int(res.first[0]) - true + T // 2) % T - T // 2
+                        whole = abs(int(res.acquired_cfo_int[0]) + float(res.acquired_cfo[0]) - (m + eps)) < 0.1
+                        b = ber(res)
+                        wide[J]["ber_all"].append(b)
+                        wide[J]["int_right"] += bool(whole)
+                        if abs(d) <= W and whole:
+                            wide[J]["right"] += 1
+                            wide[J]["ber_right"].append(b)
+                    ber_narrow_on_wide.append(ber(tr.receive_capture(capw, sync=W, cfo=True, frames=n, acquire=max(Js), lo=lo)))
             row = {"channel": ch, "snr_db": snr, "captures": a.captures, "frames": n,
                    "ber_known": float(np.mean(ber_known)),
                    "acquire": {str(J): {"share_right": right[J] / a.captures,
                                         "first_minus_true": {str(k): v for k, v in sorted(err[J].items())},
                                         "ber_where_right": float(np.mean(ber_right[J])) if ber_right[J] else None,
                                         "ber_all": float(np.mean(ber_all[J]))} for J in Js}}
+            if M:
+                row["cfo_span"] = M
+                row["wide"] = {str(J): {"share_right": q["right"] / a.captures, "share_offset_right": q["int_right"] / a.captures,
+                                        "ber_where_right": float(np.mean(q["ber_right"])) if q["ber_right"] else None,
+                                        "ber_all": float(np.mean(q["ber_all"]))} for J, q in wide.items()}
+                row["ber_narrow_on_wide_offsets"] = float(np.mean(ber_narrow_on_wide))
             rows.append(row)
             print(json.dumps(row), flush=True)
     log["acquire_rows"] = rows
@@ -314,6 +345,18 @@ def acquire_rows(a, tr, hf, snrs, log):
                 cells.append("%d of %d / %s / %.3g" % (round(q["share_right"] * r["captures"]), r["captures"],
                                                       "-" if q["ber_where_right"] is None else "%.3g" % q["ber_where_right"], q["ber_all"]))
             f.write("| %s | %g | %.3g | %s |\n" % (r["channel"], r["snr_db"], r["ber_known"], " | ".join(cells)))
+        if M:
+            f.write("\neps = m + f, |m| <= %d, cfo_span = %d\n\n| channel | SNR [dB] | " % (M, M)
+                    + " | ".join("J = %d: start and offset found / BER where found / BER over all" % J for J in Js)
+                    + " | BER, cfo_span = 0 at J = %d |\n|---|---|" % max(Js) + "---|" * (len(Js) + 1) + "\n")
+            for r in rows:
+                cells = []
+                for J in Js:
+                    q = r["wide"][str(J)]
+                    cells.append("%d of %d / %s / %.3g" % (round(q["share_right"] * r["captures"]), r["captures"],
+                                                          "-" if q["ber_where_right"] is None else "%.3g" % q["ber_where_right"],
+                                                          q["ber_all"]))
+                f.write("| %s | %g | %s | %.3g |\n" % (r["channel"], r["snr_db"], " | ".join(cells), r["ber_narrow_on_wide_offsets"]))
 
 
 def main():
@@ -342,8 +385,13 @@ def main():
                     help="J[,J...]: captures that begin inside frame 0 (host model as --capture, one eps ~ U(-0.2, 0.2) each): the share "
                          "whose start receive_capture(first=None, acquire=J) finds, and the chain's BER behind it; --frames per capture")
     ap.add_argument("--captures", type=int, default=30, help="--acquire: captures per channel and SNR")
+    ap.add_argument("--cfo_span", "--cfo-span", type=int, default=0,
+                    help="M, with --acquire: every capture also under eps = m + f, m uniform in [-M, M], f ~ U(-1/2, 1/2), received "
+                         "with receive_capture(..., acquire=J, cfo_span=M), next to the narrow path on eps = f and on eps = m + f")
     ap.add_argument("--out", default="syncber_out")
     a = ap.parse_args()
+    if a.cfo_span and not a.acquire:
+        ap.error("--cfo_span M goes with --acquire J[,J...]: the whole spacings are only known through acquisition")
     if a.cfo_scope == "capture":
         if not (a.capture or a.cfo) or a.acquire:
             ap.error("--cfo_scope capture goes with --capture or --cfo EPS")
