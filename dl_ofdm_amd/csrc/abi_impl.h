@@ -265,7 +265,8 @@ struct dccn_rx_graph {
 
 namespace dccn {
 // One step captured into an instantiated graph: the handle and its capture stream, the side stream and the fork / join events
-// when the step forks, then issue(handle) -- the step's launches on handle.cap -- between begin and end of the capture.  Whatever
+// when the step forks, then issue(handle) -- the step's launches on handle.cap -- between begin and end of the capture (never
+// instrumented: the step timeline's stamp pointers must not outlive the call that took them).  Whatever
 // fails, the handle is destroyed and the step's own status (if it has one) is the one returned.
 template <typename Issue>
 static int graph_capture(bool fork, dccn_rx_graph** out, Issue&& issue) {
@@ -282,7 +283,9 @@ static int graph_capture(bool fork, dccn_rx_graph** out, Issue&& issue) {
         return fail(DCCN_ERR_LAUNCH);
     hipError_t e = hipStreamBeginCapture(g->cap, hipStreamCaptureModeRelaxed);
     if (e != hipSuccess) return fail(hip_fail(e));
+    tl_graph_capture = true;            // (common.h: a captured step takes no timeline entry and carries no stamp pointer)
     const int st = issue(*g);
+    tl_graph_capture = false;
     e = hipStreamEndCapture(g->cap, &g->graph);
     if (st != DCCN_OK || e != hipSuccess) return fail(st != DCCN_OK ? st : hip_fail(e));
     e = hipGraphInstantiate(&g->exec, g->graph, nullptr, nullptr, 0);

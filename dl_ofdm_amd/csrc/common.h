@@ -78,6 +78,8 @@ static inline int set_max_dynamic_smem(const void* kern, size_t bytes) {
 // ---- step timeline stamps (dccn_step_trace_*: in-situ start/end of every instrumented launch, bench.py `step.boundaries`) ---
 // A launch whose parameter block carries a non-null `stamp` pointer leaves, per workgroup (blockIdx.x < kStampBlocks, y = z = 0),
 // four 64-bit words: {s_memrealtime at entry, s_memtime at entry, s_memrealtime at exit, s_memtime at exit} written by thread 0.
+// Only blockIdx.y == 0 and blockIdx.z == 0 mark: a split-K launch (z = the k range) leaves the stamps of its first range, a
+// chain-group launch those of chain 0, so the block count of such a slot is gridDim.x, not the number of workgroups.
 // s_memrealtime ticks at a constant 100 MHz, s_memtime once per shader cycle: the ratio is the clock the CU really ran at.
 // Null pointer (every normal launch): one scalar compare and a branch per mark.
 constexpr int kStampBlocks = 4096, kStampWords = 4, kStampLaunches = 8;
@@ -98,12 +100,16 @@ struct StepTraceState {
 };
 extern StepTraceState g_step_trace;
 extern thread_local unsigned long long* tl_stamp;
+// A step issued into a stream capture is never instrumented: a pointer baked into a captured kernel would be written by every
+// replay, long after the trace was switched off or its ring released.  graph_capture (abi_impl.h) raises this around the issue;
+// a scope opened meanwhile takes no ring entry, counts no step and hands out no pointer.
+extern thread_local bool tl_graph_capture;
 struct StepTraceScope {
     unsigned long long* base;
     StepTraceScope() : base(nullptr) {
         unsigned long long* b = g_step_trace.buf.load(std::memory_order_relaxed);
         const int ring = g_step_trace.ring.load(std::memory_order_relaxed);
-        if (b != nullptr && ring > 0) {
+        if (b != nullptr && ring > 0 && !tl_graph_capture) {
             const long long st = g_step_trace.step.fetch_add(1, std::memory_order_relaxed);
             base = b + (size_t)(st % ring) * kStampLaunches * kStampBlocks * kStampWords;
         }

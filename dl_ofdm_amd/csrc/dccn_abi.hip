@@ -7,6 +7,7 @@ thread_local int g_last_hip_error = 0;
 thread_local ChainCtx tl_chain = {1, {{0, 0, 0, 0, 0, 0, 0, 0}}, {0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
 StepTraceState g_step_trace;
 thread_local unsigned long long* tl_stamp = nullptr;
+thread_local bool tl_graph_capture = false;
 
 thread_local int tl_whole_k = -1;
 thread_local int tl_tune_depth = 0;
@@ -640,11 +641,13 @@ template <bool VEC, int BK = 64, int NBUF = 2>
 __global__ __launch_bounds__(kGemmThreads) void cconv_bwd_w_finalize_kernel(const GemmParams p, int tiles, int gemm_blocks,
                                                                             TailFinalizeArgs a) {
     const int b = (int)blockIdx.x;
+    stamp_mark(p.stamp, 0);
     if (b < gemm_blocks) {
         gemm_block<OP_ICONTIG, OP_ICONTIG, 64, 64, BK, 1, VEC, NBUF>(p, b % tiles, tiles, b / tiles);
     } else {
         demod_tail_finalize_body(a, b - gemm_blocks);
     }
+    stamp_mark(p.stamp, 1);
 }
 
 // the same with the GEMM blocks in the k-major form (gemm_kmajor.h)
@@ -652,11 +655,13 @@ template <int BK>
 __global__ __launch_bounds__(kGemmThreads) void cconv_bwd_w_km_finalize_kernel(const GemmParams p, int tiles, int gemm_blocks,
                                                                                TailFinalizeArgs a) {
     const int b = (int)blockIdx.x;
+    stamp_mark(p.stamp, 0);
     if (b < gemm_blocks) {
         kmajor_block<1, BK>(p, b % tiles, tiles, b / tiles);
     } else {
         demod_tail_finalize_body(a, b - gemm_blocks);
     }
+    stamp_mark(p.stamp, 1);
 }
 
 constexpr int kCconvBwMaxSplits = 128;
@@ -1000,10 +1005,10 @@ static int tail_launch(bool bwd, const float* z, const int32_t* bits, const floa
                              cells, bm, bg, stamp);
     else if (bwd)
         DCCN_LAUNCH_CHAINS_Z((demod_tail_kernel<NB, true>), dim3(nblk), dim3(kTailThreads), 0, s, z, bits, tailp, prob,
-                             dz, cells, bm, bg);
+                             dz, cells, bm, bg, stamp);
     else
         DCCN_LAUNCH_CHAINS_Z((demod_tail_kernel<NB, false>), dim3(nblk), dim3(kTailThreads), 0, s, z, bits, tailp, prob,
-                             dz, cells, bm, bg);
+                             dz, cells, bm, bg, stamp);
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
 }
@@ -1562,16 +1567,15 @@ static int rx_step_plan(const dccn_rx_shape* sh, const dccn_rx_buffers* b, bool 
 }
 
 // step timeline (dccn_step_trace_enable): launch slots 1 C-Conv forward, 2 dense forward (+ tail), 3 tail (own launch),
-// 4 backward (fused, or grouped dX+dW), 5 C-Conv weight gradient (own launch), 6 optimizer, 7 generator of the next batch
+// 4 backward (fused, or grouped dX+dW), 5 C-Conv weight gradient (own launch), 6 optimizer; 0 and 7 are never written.
+// Launches issued while no slot is named carry no marks: R0, the generator of the next batch, the tail's slab reduction
+// where it is a launch of its own (evaluation steps, the Adam-overlap plan) and whatever runs on a second stream.
 static int rx_issue_forward(const dccn_rx_shape* sh, const dccn_rx_buffers* b, const RxStepPlan& p, dccn_adam_hparams hp,
                             hipStream_t s, const StepTraceScope& trace, TailFinalizeArgs* fin) {
     const RxLayout& L = p.L;
     const float* P = b->params;
     float* gtail = p.train ? b->grads + L.o_tail : nullptr;
-    if (p.gen != nullptr && b->x_next_ready == nullptr) {
-        trace.launch(7);
-        DCCN_TRY(gen_static_launch(p.gen, s));
-    }
+    if (p.gen != nullptr && b->x_next_ready == nullptr) DCCN_TRY(gen_static_launch(p.gen, s));
     // R0 (+R8 partial sums) -- unless the previous call already normalised this batch behind its Adam update
     PowerPartials pp;
     if (p.pre) norm_power_partials(sh->batch, L.cols, p.ws.norm, L.ws_norm, b->x_next ? b->x_next : b->x, b->x_norm, &pp, p.nslot);
@@ -1630,6 +1634,7 @@ static int rx_issue_backward(const dccn_rx_shape* sh, const dccn_rx_buffers* b, 
         // two-stream variant: dense dW/db on `side`, dX -> C-Conv dW on the main stream (joined in rx_issue_update)
         DCCN_HIP(hipEventRecord(p.branch.fork, s));
         DCCN_HIP(hipStreamWaitEvent(p.branch.side, p.branch.fork, 0));
+        // (only a captured step forks, and a captured step carries no timeline stamps: both launches are unmarked)
         DCCN_TRY(dense_bwd_w_impl(b->fft_out, b->dz, G + L.o_dense_w, G + L.o_dense_b, sh->batch, L.dK, L.dN, p.ws.dense_bw,
                                   L.ws_dense_bw, p.branch.side, &k->ds));
         DCCN_HIP(hipEventRecord(p.branch.join, p.branch.side));

@@ -949,6 +949,7 @@ __global__ __launch_bounds__(256) void dense_bwd16_kernel(const GemmParams px, c
                                                           const int tw) {
     const int b = (int)blockIdx.x;
     TailEpiParams none{};
+    stamp_mark(px.stamp, 0);
     if (b < nx) {
         gemm16_block<OP_KCONTIG, OP_KCONTIG, WGM, WGN, TM, TN, BK, 1, 0, EPI_STORE, ACTX, false>(px, none, b, nx, 0, 0);
     } else {
@@ -956,6 +957,7 @@ __global__ __launch_bounds__(256) void dense_bwd16_kernel(const GemmParams px, c
         gemm16_block<OP_ICONTIG, OP_ICONTIG, WWGM, WWGN, WTM, WTN, BK, 1, 1, EPI_STORE, 1, false>(pw, none, c % tw, tw,
                                                                                                  c / tw, 0);
     }
+    stamp_mark(px.stamp, 1);
 }
 
 // split-K weight-gradient GEMM (both operands i-contiguous, bias column sums) with the tail's slab reduction riding on
@@ -964,6 +966,7 @@ template <int WGM, int WGN, int TM, int TN, int BK>
 __global__ __launch_bounds__(256) void gemm16_bwd_w_finalize_kernel(const GemmParams p, int tiles, int gemm_blocks,
                                                                     TailFinalizeArgs a) {
     const int b = (int)blockIdx.x;
+    stamp_mark(p.stamp, 0);
     if (b < gemm_blocks) {
         TailEpiParams none{};
         gemm16_block<OP_ICONTIG, OP_ICONTIG, WGM, WGN, TM, TN, BK, 1, 1, EPI_STORE, 1, false>(p, none, b % tiles, tiles,
@@ -971,6 +974,7 @@ __global__ __launch_bounds__(256) void gemm16_bwd_w_finalize_kernel(const GemmPa
     } else {
         demod_tail_finalize_body(a, b - gemm_blocks);
     }
+    stamp_mark(p.stamp, 1);
 }
 
 template <typename K>
@@ -1014,8 +1018,10 @@ template <int TM1, int TM2, int BK, int NB, bool BWD, int PD>
 __global__ __launch_bounds__(256) void dense_tail_ragged_kernel(const GemmParams p1, const TailEpiParams t1, const GemmParams p2,
                                                                 const TailEpiParams t2, const int T1, const int T2) {
     const int b = (int)blockIdx.x;
+    stamp_mark(p1.stamp, 0);
     if (b < T1) gemm16_block<OP_KCONTIG, OP_ICONTIG, 1, 4, TM1, 1, BK, 1, 0, EPI_TAIL, NB, BWD, PD>(p1, t1, b, T1, 0, b);
     else gemm16_block<OP_KCONTIG, OP_ICONTIG, 1, 4, TM2, 1, BK, 1, 0, EPI_TAIL, NB, BWD, PD>(p2, t2, b - T1, T2, 0, b);
+    stamp_mark(p1.stamp, 1);
 }
 template <int TM, int BK, int NB, bool BWD>
 constexpr size_t dense_tail16_smem() {

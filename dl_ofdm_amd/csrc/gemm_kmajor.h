@@ -258,7 +258,9 @@ __global__ __launch_bounds__(kGemmThreads) void gemm_kmajor_kernel(const GemmPar
     // chain groups (common.h): y = the chain (z carries the k ranges); its arena offset enters as the block's operand
     // offsets -- a shifted copy of the parameter block would put the dynamically indexed koff[] into scratch memory
     const long long c4 = co.off[blockIdx.y] / 4;
+    stamp_mark(p0.stamp, 0);
     kmajor_block<COLSUM, 64, APATCH>(p0, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.z, c4, c4, c4, c4);
+    stamp_mark(p0.stamp, 1);
 }
 
 template <int COLSUM, int TAG, bool APATCH = false>
@@ -281,6 +283,7 @@ __global__ __launch_bounds__(kGemmThreads) void dense_bwd_grouped_km_kernel(cons
 #ifdef GROUPED_ABL          // timing experiments only: 1 = the dX blocks return at once, 2 = the dW blocks do
     if ((GROUPED_ABL == 1) == (b < nx)) return;
 #endif
+    stamp_mark(px0.stamp, 0);
     if (b < nx) {
         const GemmParams px = px0.at_chain(coff);
         gemm_block<OP_KCONTIG, OP_KCONTIG, 64, 64, BK, 0, true, 2, CMAP>(px, b, nx, 0);
@@ -289,6 +292,7 @@ __global__ __launch_bounds__(kGemmThreads) void dense_bwd_grouped_km_kernel(cons
         const long long c4 = coff / 4;                      // (kmajor_block: offsets, not a shifted copy -- koff[] is indexed)
         kmajor_block<1, BK>(pw0, c % tw, tw, c / tw, c4, c4, c4, c4);
     }
+    stamp_mark(px0.stamp, 1);
 }
 
 template <int BK, int CMAP = CMAP_NONE>

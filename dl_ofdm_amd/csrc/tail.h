@@ -424,7 +424,8 @@ __device__ __forceinline__ const float* tail_stage_weights(const float* __restri
 template <int NB, bool BWD>
 __global__ __launch_bounds__(kTailThreads) void demod_tail_kernel(
     const float* z_, const int32_t* bits_, const float* tailp_, float* prob_, float* dz_, long long cells,
-    TailBlockMetrics* blk_metrics_, float* blk_grads_, const ChainOffs co) {
+    TailBlockMetrics* blk_metrics_, float* blk_grads_, unsigned long long* stamp, const ChainOffs co) {
+    stamp_mark(stamp, 0);
     const long long coff = co.off[blockIdx.z];                     // chain groups (common.h)
     const float* __restrict__ z = chain_at(z_, coff);
     const int32_t* __restrict__ bits = chain_at(bits_, coff);
@@ -478,6 +479,7 @@ __global__ __launch_bounds__(kTailThreads) void demod_tail_kernel(
         cell += W * stride;
     }
     tail_block_reduce<NB, BWD, kTailThreads>(A, sred, blk_metrics, blk_grads, (int)blockIdx.x);
+    stamp_mark(stamp, 1);
 }
 
 // ---- nbits = 4 training: four lanes per cell ------------------------------------------------------------

@@ -19,8 +19,38 @@ import torch
 from . import _lib
 from ._lib import check
 
+# every slot the library writes (include/dccn.h: 0 and 7 are never written)
 SLOT_NAMES = {1: "cconv_fwd", 2: "dense_fwd_tail", 3: "tail", 4: "backward", 5: "cconv_bwd_w", 6: "optimizer"}
 WALL_HZ = 100e6        # s_memrealtime (hipDeviceAttributeWallClockRate = 100 000 kHz on gfx950)
+
+
+def decode_ring(words: np.ndarray, n: int, ring: int, geometry) -> List[Dict[int, dict]]:
+    """The step records of a ring read back from the device (no GPU involved): `words` are the ring's 64-bit words, `n` the
+    step calls counted since the trace was enabled, `geometry` = (launches, blocks, words) of dccn_step_trace_geometry.
+    Steps max(0, n - ring) .. n - 1, oldest first, step i from entry i % ring; a slot none of whose workgroups left an entry
+    stamp is absent from its step's record, a workgroup that entered and never left counts as a block and nowhere else."""
+    launches, blocks, nwords = geometry
+    t = np.asarray(words).view(np.uint64).reshape(ring, launches, blocks, nwords)
+    steps = []
+    for st in range(max(0, n - ring), n):
+        e = t[st % ring]
+        rec = {}
+        for slot in range(launches):
+            w0 = e[slot, :, 0]
+            m = w0 != 0
+            if not m.any():
+                continue
+            w0, c0, w1, c1 = (e[slot, m, k].astype(np.int64) for k in range(4))
+            done = w1 != 0
+            dur = (w1 - w0)[done]
+            cyc = (c1 - c0)[done]
+            long_ = dur >= 300                         # >= 3 us of wall time: +-1 tick is < 0.7 % of the ratio
+            sclk = float(np.median(cyc[long_] / dur[long_]) * WALL_HZ / 1e6) if long_.any() else None
+            rec[slot] = dict(start=int(w0.min()), end=int(w1[done].max()) if done.any() else int(w0.max()),
+                             blocks=int(m.sum()), sclk_mhz=sclk,
+                             block_us_median=float(np.median(dur)) * 1e6 / WALL_HZ if done.any() else None)
+        steps.append(rec)
+    return steps
 
 
 class StepTrace:
@@ -60,27 +90,7 @@ class StepTrace:
         slot -> {start, end (100 MHz ticks: first workgroup in, last workgroup out), blocks, sclk_mhz}."""
         torch.cuda.synchronize(self.device)
         n = int(self.lib.dccn_step_trace_steps())
-        t = self.buf.cpu().numpy().view(np.uint64).reshape(self.ring, self.launches, self.blocks, self.words)
-        steps = []
-        for st in range(max(0, n - self.ring), n):
-            e = t[st % self.ring]
-            rec = {}
-            for slot in range(self.launches):
-                w0 = e[slot, :, 0]
-                m = w0 != 0
-                if not m.any():
-                    continue
-                w0, c0, w1, c1 = (e[slot, m, k].astype(np.int64) for k in range(4))
-                done = w1 != 0
-                dur = (w1 - w0)[done]
-                cyc = (c1 - c0)[done]
-                long_ = dur >= 300                         # >= 3 us of wall time: +-1 tick is < 0.7 % of the ratio
-                sclk = float(np.median(cyc[long_] / dur[long_]) * WALL_HZ / 1e6) if long_.any() else None
-                rec[slot] = dict(start=int(w0.min()), end=int(w1[done].max()) if done.any() else int(w0.max()),
-                                 blocks=int(m.sum()), sclk_mhz=sclk,
-                                 block_us_median=float(np.median(dur)) * 1e6 / WALL_HZ if done.any() else None)
-            steps.append(rec)
-        return steps
+        return decode_ring(self.buf.cpu().numpy(), n, self.ring, (self.launches, self.blocks, self.words))
 
 
 def summarise(bursts: List[List[Dict[int, dict]]]) -> dict:

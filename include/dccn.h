@@ -747,8 +747,24 @@ int dccn_eq_monitor_accumulate(const float* chest, const float* chan, int chan_p
  * takes the next ring entry and thread 0 of each workgroup of its instrumented launches writes
  *   {s_memrealtime at entry (100 MHz), s_memtime at entry (shader cycles), the same two at exit}
  * into [step % ring][slot][blockIdx.x].  Slots: 1 C-Conv forward, 2 dense forward (+ tail), 3 tail (own launch),
- * 4 backward, 5 C-Conv weight gradient (own launch), 6 optimizer; 0 and 7 unused.  buf = NULL disables (the default: a
- * disabled mark is one scalar compare per workgroup).  Process-wide switch, meant for one measuring thread. */
+ * 4 backward, 5 C-Conv weight gradient (own launch), 6 optimizer; 0 and 7 are never written.  buf = NULL disables (the
+ * default: a disabled mark is one scalar compare per workgroup).  Process-wide switch, meant for one measuring thread.
+ *   Blocks.  Every workgroup with blockIdx.x < `blocks` and blockIdx.y == blockIdx.z == 0 marks, the workgroups that carry
+ *     the tail's slab reduction behind a weight-gradient grid included; the words of a block index at or above the launch's
+ *     grid stay as the caller zeroed them.  A split-K launch (z = the k range) therefore leaves gridDim.x stamps, those of
+ *     its first k range.  Where a plan issues two launches under one slot on the same stream (the dense weight gradient,
+ *     then dX, when they cannot share a grid) the later launch overwrites the block indices the two have in common.
+ *   Not instrumented (their time shows as the gap in front of the next slot): R0 and the generator of the next batch in
+ *     front of slot 1; the tail's slab reduction where it is a launch of its own (every evaluation step, and training
+ *     steps whose dense update runs on the second stream, knob 25) and that update itself; the fold launch behind a C-Conv
+ *     weight gradient whose operands are not vector-legal (slot 5 then holds the GEMM alone).
+ *   Captured steps are never instrumented: while dccn_rx_graph_create / dccn_eq_graph_create capture, a step takes no ring
+ *     entry, counts no step and bakes no pointer into the graph, so replays write nothing whether a trace is enabled at
+ *     capture time, at replay time or never.  Only the receiver's training and evaluation steps are traced at all:
+ *     dccn_rx_receive_step, the equaliser steps and the stand-alone operators never write.
+ *   dccn_step_trace_enable returns DCCN_ERR_WORKSPACE for ring_steps <= 0 or bytes < dccn_step_trace_bytes(ring_steps) (with
+ *     a non-null buf) and changes nothing: a trace already in force stays in force, its counter included.  A step call
+ *     that is refused (any status but DCCN_OK from its plan) takes no entry and counts nothing. */
 size_t dccn_step_trace_bytes(int ring_steps);
 int dccn_step_trace_enable(unsigned long long* buf, size_t bytes, int ring_steps);
 long long dccn_step_trace_steps(void);                 /* step calls recorded since the last enable */
