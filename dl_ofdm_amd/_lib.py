@@ -284,6 +284,11 @@ SIGNATURES = {
     "dccn_capture_sync_pooled_wide_workspace_size": (_sz, [_i]),
     "dccn_capture_sync_pooled_wide": (_i, [_vp, c_longlong, c_longlong, _vp, c_longlong, c_longlong] + [_i] * 6 + [_vp] * 7
                                       + [_sz, _vp]),
+    # 16-bit integer I/Q captures (int16 [n, 2] and a scale), converted inside the launches
+    "dccn_capture_sync_sc16": (_i, [_vp, c_longlong, _f, c_longlong, _vp, c_longlong, c_longlong] + [_i] * 6 + [_vp] * 5),
+    "dccn_capture_sync_pooled_sc16": (_i, [_vp, c_longlong, _f, c_longlong, _vp, c_longlong, c_longlong] + [_i] * 6 + [_vp] * 5
+                                      + [_sz, _vp]),
+    "dccn_capture_acquire_sc16": (_i, [_vp, c_longlong, _f, c_longlong] + [_i] * 4 + [_vp, _i] + [_vp] * 5 + [_sz, _vp]),
     "dccn_rx_normalise": (_i, [POINTER(RxShape), POINTER(RxBuffers), _vp]),
     "dccn_rx_graph_create": (_i, [POINTER(RxShape), POINTER(RxBuffers), _i, AdamHParams, _vp, POINTER(c_void_p)]),
     "dccn_rx_graph_launch": (_i, [_vp, _vp]),

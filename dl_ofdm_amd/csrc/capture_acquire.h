@@ -34,6 +34,7 @@
 #pragma once
 #include <math.h>
 
+#include "capture_source.h"
 #include "common.h"
 
 namespace dccn {
@@ -85,12 +86,14 @@ __host__ __device__ static inline size_t capture_acquire_lds(int S, int K, int C
 
 // The three launches, each stated once as a body over one link's AcqArgs: the solo kernels pass their own argument, the grouped
 // ones (at the end) the entry of their link table.  A body reads blockIdx.x (and .y, acq_phase_body) as the solo grid lays them
-// out; the link index rides on a dimension the body does not look at.
-__device__ __forceinline__ void acq_symbol_sums_body(const AcqArgs& a) {
+// out; the link index rides on a dimension the body does not look at.  The two bodies that read the capture take it from a capture
+// source (capture_source.h: float32, or 16-bit integer I/Q with its scale), one sample per load.
+template <class Src>
+__device__ __forceinline__ void acq_symbol_sums_body(const AcqArgs& a, const Src src) {
     const int N = a.K + a.CP;
     const int m = blockIdx.x * kAcqSumThreads + threadIdx.x;
     if (m >= N + a.CP - 1) return;
-    const float2* c = reinterpret_cast<const float2*>(a.cap) + a.lo + m;
+    const auto c = src.of(a) + a.lo + m;
     float pr = 0.f, pi = 0.f, e = 0.f;
 #pragma unroll 8                                                           // (loads of eight symbols in flight; the order of the sums stays)
     for (int u = 0; u < a.J * a.S; ++u) {
@@ -101,9 +104,12 @@ __device__ __forceinline__ void acq_symbol_sums_body(const AcqArgs& a) {
     }
     a.pe[m] = make_float4(pr, pi, e, 0.f);
 }
-static __global__ void __launch_bounds__(kAcqSumThreads) acq_symbol_sums_kernel(const AcqArgs a) { acq_symbol_sums_body(a); }
+static __global__ void __launch_bounds__(kAcqSumThreads) acq_symbol_sums_kernel(const AcqArgs a) {
+    acq_symbol_sums_body(a, CapOfArgs{});
+}
 
-__device__ __forceinline__ void acq_phase_body(const AcqArgs& a) {
+template <class Src>
+__device__ __forceinline__ void acq_phase_body(const AcqArgs& a, const Src src) {
     extern __shared__ float4 acq_lds[];
     const int S = a.S, K = a.K, CP = a.CP, N = K + CP, J = a.J, n_pilot = a.n_pilot;
     const int tid = threadIdx.x;
@@ -185,10 +191,9 @@ __device__ __forceinline__ void acq_phase_body(const AcqArgs& a) {
     for (int s = 0; s < S; ++s) {
         const int cnt = run_n[s];
         if (cnt < 2) continue;                                           // (uniform over the block)
-        const float2* src = reinterpret_cast<const float2*>(a.cap) + a.lo + rhat + (long long)(q + s) * N +
-                            (long long)j * S * N + CP;
+        const auto sym = src.of(a) + a.lo + rhat + (long long)(q + s) * N + (long long)j * S * N + CP;
         __syncthreads();                                                 // (the previous symbol's y and Y are done with)
-        for (int n = tid; n < K; n += kAcqThreads) y[n] = src[n];
+        for (int n = tid; n < K; n += kAcqThreads) y[n] = sym[n];
         __syncthreads();
         if (tid < cnt) {
             const int k = car[run_at[s] + tid];
@@ -219,7 +224,7 @@ __device__ __forceinline__ void acq_phase_body(const AcqArgs& a) {
     }
     if (tid == 0) a.partial[(size_t)q * J + j] = dj;
 }
-static __global__ void __launch_bounds__(kAcqThreads) acq_phase_kernel(const AcqArgs a) { acq_phase_body(a); }
+static __global__ void __launch_bounds__(kAcqThreads) acq_phase_kernel(const AcqArgs a) { acq_phase_body(a, CapOfArgs{}); }
 
 __device__ __forceinline__ void acq_decide_body(const AcqArgs& a) {
     __shared__ float d[kAcqMaxS];
@@ -466,9 +471,22 @@ struct AcqGroupArgs {
     }
 };
 static __global__ void __launch_bounds__(kAcqSumThreads) acq_symbol_sums_grouped_kernel(const AcqGroupArgs g) {
-    acq_symbol_sums_body(g.of(blockIdx.y));
+    acq_symbol_sums_body(g.of(blockIdx.y), CapOfArgs{});
 }
-static __global__ void __launch_bounds__(kAcqThreads) acq_phase_grouped_kernel(const AcqGroupArgs g) { acq_phase_body(g.of(blockIdx.z)); }
+static __global__ void __launch_bounds__(kAcqThreads) acq_phase_grouped_kernel(const AcqGroupArgs g) {
+    acq_phase_body(g.of(blockIdx.z), CapOfArgs{});
+}
 static __global__ void __launch_bounds__(kAcqMaxS) acq_decide_grouped_kernel(const AcqGroupArgs g) { acq_decide_body(g.of(blockIdx.x)); }
+
+// ---- 16-bit integer I/Q captures (dccn_capture_acquire_sc16) ----------------------------------------------------------------------
+// The two launches that read the capture, over CapSc16 (a.cap is not read); the decision is acq_decide_kernel itself.
+struct AcqSc16Args {
+    AcqArgs a;
+    CapSc16 src;
+};
+static __global__ void __launch_bounds__(kAcqSumThreads) acq_symbol_sums_sc16_kernel(const AcqSc16Args g) {
+    acq_symbol_sums_body(g.a, g.src);
+}
+static __global__ void __launch_bounds__(kAcqThreads) acq_phase_sc16_kernel(const AcqSc16Args g) { acq_phase_body(g.a, g.src); }
 
 }  // namespace dccn

@@ -41,8 +41,11 @@ struct CaptureSyncPlan {
     size_t lds;
 };
 
+// sample_bytes: 8 for a float32 capture; 4 for an sc16 one, whose entries pass the capture's address as `cap` for the checks (the
+// capture's extent is n_samples * sample_bytes) and launch kernels that do not read args.cap
 int capture_sync_plan(const float* cap, long long n_samples, long long first, long long stride, int frames, int S, int K, int CP,
-                      int W, int out_kin, float* x_out, int32_t* offset, float* cfo, float* metric, CaptureSyncPlan* plan) {
+                      int W, int out_kin, float* x_out, int32_t* offset, float* cfo, float* metric, CaptureSyncPlan* plan,
+                      size_t sample_bytes = 8) {
     if (!capture_sync_shape_ok(S, K, CP, W) || frames <= 0 || !cap || !offset) return DCCN_ERR_INVALID_ARG;
     if (out_kin != K + CP && out_kin != K) return DCCN_ERR_INVALID_ARG;
     if (!aligned16(cap) || !aligned16(x_out) || !aligned16(metric)) return DCCN_ERR_INVALID_ARG;
@@ -53,7 +56,8 @@ int capture_sync_plan(const float* cap, long long n_samples, long long first, lo
     if (n_samples <= 0 || n_samples > (1LL << 58) || stride < T || first < W || first > n_samples) return DCCN_ERR_INVALID_ARG;
     const long long room = n_samples - first - T - W;
     if (room < 0 || (frames > 1 && stride > room / (frames - 1))) return DCCN_ERR_INVALID_ARG;
-    if (x_out && ranges_overlap(cap, (size_t)n_samples * 8, x_out, (size_t)frames * S * out_kin * 8)) return DCCN_ERR_INVALID_ARG;
+    if (x_out && ranges_overlap(cap, (size_t)n_samples * sample_bytes, x_out, (size_t)frames * S * out_kin * 8))
+        return DCCN_ERR_INVALID_ARG;
     plan->args = CaptureSyncArgs{cap, first, stride, x_out, offset, metric, cfo, frames, S, K, CP, W, out_kin == K ? 1 : 0};
     plan->blocks = (unsigned)ceil_div(frames, kSyncWaves);
     plan->lds = kSyncWaves * capture_sync_lds_per_frame((int)T, W);
@@ -72,11 +76,12 @@ int capture_sync_launch(const CaptureSyncPlan& plan, dccn_stream_t stream) {
 // has its windows inside the capture too, down to lo, whose first window starts at lo - W >= 0)
 int capture_sync_at_plan(const float* cap, long long n_samples, const long long* first_dev, long long lo, long long stride,
                          int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset, float* cfo,
-                         float* metric, CaptureSyncPlan* plan) {
+                         float* metric, CaptureSyncPlan* plan, size_t sample_bytes = 8) {
     if (!capture_sync_shape_ok(S, K, CP, W) || !first_dev || (reinterpret_cast<uintptr_t>(first_dev) & 7u) != 0) return DCCN_ERR_INVALID_ARG;
     if (lo < W || n_samples <= 0 || lo > n_samples) return DCCN_ERR_INVALID_ARG;
     const long long T = (long long)S * (K + CP);
-    return capture_sync_plan(cap, n_samples, lo + T - 1, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo, metric, plan);
+    return capture_sync_plan(cap, n_samples, lo + T - 1, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo, metric, plan,
+                             sample_bytes);
 }
 
 template <bool CFO>
@@ -243,7 +248,7 @@ struct PooledGroupPlan {
     size_t lds_estimate, lds_cut;
 };
 int pooled_group_plan(int n_links, const dccn_pooled_link* links, int frames, int S, int K, int CP, int W, int out_kin,
-                      PooledGroupPlan* plan) {
+                      PooledGroupPlan* plan, size_t sample_bytes = 8) {
     if (!group_count_ok(n_links, links)) return DCCN_ERR_INVALID_ARG;
     LinkRanges r[kMaxChains];
     plan->args = PooledGroupArgs{};
@@ -252,10 +257,10 @@ int pooled_group_plan(int n_links, const dccn_pooled_link* links, int frames, in
         CaptureSyncPlan one;
         if (l.first_dev)
             DCCN_TRY(capture_sync_at_plan(l.cap, l.n_samples, l.first_dev, l.lo, l.stride, frames, S, K, CP, W, out_kin, l.x_out,
-                                          l.offset, l.cfo, l.metric, &one));
+                                          l.offset, l.cfo, l.metric, &one, sample_bytes));
         else
             DCCN_TRY(capture_sync_plan(l.cap, l.n_samples, l.first, l.stride, frames, S, K, CP, W, out_kin, l.x_out, l.offset, l.cfo,
-                                       l.metric, &one));
+                                       l.metric, &one, sample_bytes));
         if (!l.x_out || !l.cfo || (reinterpret_cast<uintptr_t>(l.cfo) & 3u) != 0) return DCCN_ERR_INVALID_ARG;
         if (!l.workspace || !aligned16(l.workspace)) return DCCN_ERR_INVALID_ARG;
         plan->args.link[i] = PooledLink{CaptureSyncLink{one.args.cap, l.first_dev ? 0 : l.first, one.args.stride, l.first_dev,
@@ -274,7 +279,7 @@ int pooled_group_plan(int n_links, const dccn_pooled_link* links, int frames, in
         r[i].out(l.cfo, 4);
         r[i].out(l.metric, (size_t)frames * (2 * W + 1) * 4);
         r[i].out(l.workspace, pooled_workspace_bytes(frames));
-        r[i].in(l.cap, (size_t)l.n_samples * 8);
+        r[i].in(l.cap, (size_t)l.n_samples * sample_bytes);
         r[i].in(l.first_dev, 8);
     }
     if (mixed_nullability(links, n_links, &dccn_pooled_link::metric)) return DCCN_ERR_INVALID_ARG;
@@ -285,13 +290,13 @@ int pooled_group_plan(int n_links, const dccn_pooled_link* links, int frames, in
 }
 int pooled_group_launch(const PooledGroupPlan& plan, int n_links, dccn_stream_t stream) {
     DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_estimate_kernel, plan.lds_estimate));
-    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_cut_kernel, plan.lds_cut));
+    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_cut_kernel<PooledGroupArgs>, plan.lds_cut));
     const dim3 grid(plan.blocks, (unsigned)n_links), block(kSyncWaves * kSyncLanes);
     hipLaunchKernelGGL(capture_pool_estimate_kernel, grid, block, plan.lds_estimate, (hipStream_t)stream, plan.args);
     DCCN_LAUNCH_CHECK();
     hipLaunchKernelGGL(capture_pool_reduce_kernel, dim3((unsigned)n_links), dim3(kSyncLanes), 0, (hipStream_t)stream, plan.args);
     DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(capture_pool_cut_kernel, grid, block, plan.lds_cut, (hipStream_t)stream, plan.args);
+    hipLaunchKernelGGL(capture_pool_cut_kernel<PooledGroupArgs>, grid, block, plan.lds_cut, (hipStream_t)stream, plan.args);
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
 }
@@ -350,6 +355,10 @@ int capture_sync_group_launch(const CaptureSyncGroupPlan& plan, int n_links, dcc
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
 }
+
+// ---- 16-bit integer I/Q captures: the float32 plans with the capture's extent taken as 4 bytes per sample -----------------------
+bool sc16_scale_ok(float scale) { return isfinite(scale) && scale > 0.f; }
+const float* sc16_as_checked(const int16_t* cap) { return reinterpret_cast<const float*>(cap); }    // (an address to check, never read)
 }  // namespace
 
 extern "C" {
@@ -474,6 +483,79 @@ int dccn_capture_sync_pooled(const float* cap, long long n_samples, long long fi
                              float* cfo_out, float* metric, void* workspace, size_t workspace_bytes, dccn_stream_t stream) {
     const dccn_pooled_link link{cap, n_samples, first, first_dev, lo, stride, x_out, offset, cfo_out, metric, workspace, workspace_bytes};
     return dccn_capture_sync_pooled_grouped(1, &link, frames, S, K, CP, W, out_kin, stream);
+}
+
+// ---- 16-bit integer I/Q captures, converted inside the launches ----------------------------------------------------------------
+int dccn_capture_sync_sc16(const int16_t* cap, long long n_samples, float scale, long long first, const long long* first_dev,
+                           long long lo, long long stride, int frames, int S, int K, int CP, int W, int out_kin, float* x_out,
+                           int32_t* offset, float* cfo, float* metric, dccn_stream_t stream) {
+    if (!sc16_scale_ok(scale)) return DCCN_ERR_INVALID_ARG;
+    CaptureSyncPlan plan;
+    if (first_dev)
+        DCCN_TRY(capture_sync_at_plan(sc16_as_checked(cap), n_samples, first_dev, lo, stride, frames, S, K, CP, W, out_kin, x_out,
+                                      offset, cfo, metric, &plan, 4));
+    else
+        DCCN_TRY(capture_sync_plan(sc16_as_checked(cap), n_samples, first, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo,
+                                   metric, &plan, 4));
+    DCCN_NO_CHAINS();
+    plan.args.cap = nullptr;
+    plan.args.first = first_dev ? 0 : first;
+    const CaptureSyncSc16Args args{plan.args, CapSc16{cap, scale}, first_dev, first_dev ? lo : 0};
+    const dim3 grid(plan.blocks), block(kSyncWaves * kSyncLanes);
+    if (cfo) {
+        DCCN_TRY(set_max_dynamic_smem((const void*)capture_sync_sc16_kernel<true>, plan.lds));
+        hipLaunchKernelGGL(capture_sync_sc16_kernel<true>, grid, block, plan.lds, (hipStream_t)stream, args);
+    } else {
+        DCCN_TRY(set_max_dynamic_smem((const void*)capture_sync_sc16_kernel<false>, plan.lds));
+        hipLaunchKernelGGL(capture_sync_sc16_kernel<false>, grid, block, plan.lds, (hipStream_t)stream, args);
+    }
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+int dccn_capture_sync_pooled_sc16(const int16_t* cap, long long n_samples, float scale, long long first, const long long* first_dev,
+                                  long long lo, long long stride, int frames, int S, int K, int CP, int W, int out_kin, float* x_out,
+                                  int32_t* offset, float* cfo_out, float* metric, void* workspace, size_t workspace_bytes,
+                                  dccn_stream_t stream) {
+    if (!sc16_scale_ok(scale)) return DCCN_ERR_INVALID_ARG;
+    // the pooled call's plan for one link; the link struct keeps its layout, its `cap` carries the address for the checks
+    const dccn_pooled_link link{sc16_as_checked(cap), n_samples, first, first_dev, lo, stride, x_out, offset, cfo_out, metric, workspace,
+                                workspace_bytes};
+    PooledGroupPlan plan;
+    DCCN_TRY(pooled_group_plan(1, &link, frames, S, K, CP, W, out_kin, &plan, 4));
+    DCCN_NO_CHAINS();
+    plan.args.link[0].s.cap = nullptr;
+    const PooledGroupArgs& g = plan.args;
+    const PooledSc16Args args{g.link[0], CapSc16{cap, scale}, g.frames, g.S, g.K, g.CP, g.W, g.crop};
+    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_estimate_sc16_kernel, plan.lds_estimate));
+    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_cut_kernel<PooledSc16Args>, plan.lds_cut));
+    const dim3 grid(plan.blocks, 1), block(kSyncWaves * kSyncLanes);
+    hipLaunchKernelGGL(capture_pool_estimate_sc16_kernel, grid, block, plan.lds_estimate, (hipStream_t)stream, args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(capture_pool_reduce_kernel, dim3(1), dim3(kSyncLanes), 0, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(capture_pool_cut_kernel<PooledSc16Args>, grid, block, plan.lds_cut, (hipStream_t)stream, args);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+int dccn_capture_acquire_sc16(const int16_t* cap, long long n_samples, float scale, long long lo, int J, int S, int K, int CP,
+                              const int* pilot_sc, int n_pilot, long long* first_out, float* cfo_out, float* sym_metric,
+                              float* phase_metric, void* workspace, size_t workspace_bytes, dccn_stream_t stream) {
+    if (!sc16_scale_ok(scale)) return DCCN_ERR_INVALID_ARG;
+    CaptureAcquirePlan plan;        // (the plan looks at sample counts and the base's alignment: nothing depends on the sample's size)
+    DCCN_TRY(capture_acquire_plan(sc16_as_checked(cap), n_samples, lo, J, S, K, CP, pilot_sc, n_pilot, first_out, cfo_out, sym_metric,
+                                  phase_metric, workspace, workspace_bytes, &plan));
+    DCCN_NO_CHAINS();
+    plan.args.cap = nullptr;
+    const AcqSc16Args args{plan.args, CapSc16{cap, scale}};
+    hipLaunchKernelGGL(acq_symbol_sums_sc16_kernel, dim3(plan.sum_blocks), dim3(kAcqSumThreads), 0, (hipStream_t)stream, args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(acq_phase_sc16_kernel, dim3((unsigned)S, (unsigned)J), dim3(kAcqThreads), plan.lds, (hipStream_t)stream, args);
+    DCCN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(acq_decide_kernel, dim3(1), dim3(kAcqMaxS), 0, (hipStream_t)stream, plan.args);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
 }
 
 // ---- carrier offsets beyond half a subcarrier spacing: acquisition over (q, m), the cut with the whole offset taken out ---------

@@ -31,7 +31,13 @@
 // the prefix's fraction is unwrapped against the pair (m^, eps^) dccn_capture_acquire_wide left on the device (cfo_unwrap), and
 // the frame is derotated with the integer part's turns reduced exactly (frame_cfo_derotate_wide) -- a WIDE instantiation of
 // capture_sync_body, and a pooled cut kernel of its own.
+//
+// dccn_capture_sync_sc16 / dccn_capture_sync_pooled_sc16 (at the end) read a capture of 16-bit integer I/Q (capture_source.h): the
+// window loader has an sc16 form that leaves in LDS, slot for slot, what the float32 loader leaves there for the converted
+// capture, and the cut, the pooled estimate and the pooled cut are instantiated over it -- new kernels only, every float32 kernel
+// keeps its code.
 #pragma once
+#include "capture_source.h"
 #include "common.h"
 
 namespace dccn {
@@ -341,13 +347,62 @@ __device__ __forceinline__ void capture_window_load(float4* region, const float*
     }
 }
 
+__device__ __forceinline__ void capture_window_load(float4* region, const CapF32 src, const long long start, const int len,
+                                                    const int lane) {
+    capture_window_load(region, reinterpret_cast<const float*>(src), start, len, lane);
+}
+// The sc16 form: the same samples into the same slots.  A sample is 4 bytes, so the capture's 16-byte units are QUADS of samples:
+// with r = start & 3 the window is the samples [r, r + len) counted from quad 0's first sample, a quad that lies inside it is one
+// 16-byte load (four samples: the region's pairs 2 j - h and 2 j + 1 - h, h = r >> 1 -- the region starts at the even sample
+// start & ~1, which is sample 2 h of quad 0), and the quads the window's head and tail cut through are read pair by pair: an
+// 8-byte load where both samples belong to the window, a 4-byte load of the one that does (the other half of the region's pair is
+// written as 0, as the float32 loader writes it), nothing where neither does.  No lane reads a sample outside the window: the 16
+// bytes of its last quad may reach past the capture's end, and are then not read whole.
+__device__ __forceinline__ void capture_window_load(float4* region, const CapSc16 src, const long long start, const int len,
+                                                    const int lane) {
+    const int r = (int)(start & 3), h = r >> 1, end = r + len;
+    const uint32_t* const s1 = reinterpret_cast<const uint32_t*>(src.cap) + (start - r);
+    const uint2* const s2 = reinterpret_cast<const uint2*>(s1);
+    const uint4* const s4 = reinterpret_cast<const uint4*>(s1);
+    const int quads = (end + 3) / 4;
+    for (int j = lane; j < quads; j += kSyncLanes) {
+        const int s = 4 * j;
+        if (s >= r && s + 4 <= end) {
+            const uint4 w = s4[j];
+            const float2 a = CapSc16::value(w.x, src.scale), b = CapSc16::value(w.y, src.scale);
+            const float2 c = CapSc16::value(w.z, src.scale), d = CapSc16::value(w.w, src.scale);
+            region[2 * j - h] = make_float4(a.x, a.y, b.x, b.y);
+            region[2 * j + 1 - h] = make_float4(c.x, c.y, d.x, d.y);
+        } else {
+#pragma unroll
+            for (int p = 0; p < 2; ++p) {
+                const int s0 = s + 2 * p;
+                const bool in0 = s0 >= r && s0 < end, in1 = s0 + 1 >= r && s0 + 1 < end;
+                if (!in0 && !in1) continue;
+                float2 u = make_float2(0.f, 0.f), v = make_float2(0.f, 0.f);
+                if (in0 && in1) {
+                    const uint2 w = s2[2 * j + p];
+                    u = CapSc16::value(w.x, src.scale);
+                    v = CapSc16::value(w.y, src.scale);
+                } else if (in0) {
+                    u = CapSc16::value(s1[s0], src.scale);
+                } else {
+                    v = CapSc16::value(s1[s0 + 1], src.scale);
+                }
+                region[2 * j + p - h] = make_float4(u.x, u.y, v.x, v.y);
+            }
+        }
+    }
+}
+
 // The launch, stated once; `first` is where frame 0 nominally starts (the argument, or what dccn_capture_sync_at read).
 // POOL (dccn_capture_sync_pooled's estimate pass, below): the same estimate with another finish -- the frame's offset and
 // Gamma_f(offset) go to offset[f] and gamma_ws[f], and no frame is written.
 // WIDE (dccn_capture_sync_wide, at the end): the CFO variant with sync_finish_wide in place of sync_finish.
-template <bool CFO, bool POOL = false, bool WIDE = false>
-__device__ __forceinline__ void capture_sync_body(const CaptureSyncArgs& a, const long long first, float2* gamma_ws = nullptr,
-                                                  const CfoWide wide = CfoWide{nullptr, nullptr}) {
+// Src (capture_source.h): where the window comes from -- CapOfArgs{}: the float32 capture a.cap.
+template <bool CFO, bool POOL = false, bool WIDE = false, class Src>
+__device__ __forceinline__ void capture_sync_body(const CaptureSyncArgs& a, const Src src, const long long first,
+                                                  float2* gamma_ws = nullptr, const CfoWide wide = CfoWide{nullptr, nullptr}) {
     extern __shared__ float4 sync_lds[];
     const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
     const int T = a.S * (a.K + a.CP), W = a.W;
@@ -361,7 +416,7 @@ __device__ __forceinline__ void capture_sync_body(const CaptureSyncArgs& a, cons
     const float2* const y = reinterpret_cast<const float2*>(region) + sh;    // slot 0 = sample start
 
     // 1. the window, once, into LDS
-    if (live) capture_window_load(region, a.cap, start, T + 2 * W, lane);
+    if (live) capture_window_load(region, src.of(a), start, T + 2 * W, lane);
     const SyncLinear at{W};
     float2 gamma = make_float2(0.f, 0.f);
     const int theta = sync_estimate(at, y, pe, lane, live, a.S, a.K, a.CP, W,
@@ -382,7 +437,7 @@ __device__ __forceinline__ void capture_sync_body(const CaptureSyncArgs& a, cons
 
 template <bool CFO>
 static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_kernel(const CaptureSyncArgs a) {
-    capture_sync_body<CFO>(a, a.first);
+    capture_sync_body<CFO>(a, CapOfArgs{}, a.first);
 }
 
 // dccn_capture_sync_at: the same launch with `first` read from device memory (what dccn_capture_acquire left there) and kept
@@ -396,7 +451,7 @@ template <bool CFO>
 static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_at_kernel(const CaptureSyncAtArgs a) {
     const long long hi = a.lo + (long long)a.s.S * (a.s.K + a.s.CP) - 1;
     const long long got = a.first_dev[0];
-    capture_sync_body<CFO>(a.s, got < a.lo ? a.lo : (got > hi ? hi : got));
+    capture_sync_body<CFO>(a.s, CapOfArgs{}, got < a.lo ? a.lo : (got > hi ? hi : got));
 }
 
 // ---- several links per launch (dccn_frame_sync_grouped, dccn_capture_sync_grouped) ----------------------------------------------
@@ -445,7 +500,7 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_g
     }
     capture_sync_body<CFO>(CaptureSyncArgs{l.cap, first, l.stride, l.x_out, l.offset, l.metric, l.cfo, g.frames, g.S, g.K, g.CP, g.W,
                                            g.crop},
-                           first);
+                           CapOfArgs{}, first);
 }
 
 // ---- one carrier offset per capture, pooled over its frames (dccn_capture_sync_pooled, dccn_capture_sync_pooled_grouped) -------
@@ -474,6 +529,8 @@ struct PooledLink {
 struct PooledGroupArgs {
     PooledLink link[kMaxChains];
     int frames, S, K, CP, W, crop;
+    __device__ __forceinline__ const PooledLink& at(const unsigned y) const { return link[y]; }
+    __device__ __forceinline__ CapOfArgs source() const { return CapOfArgs{}; }
 };
 __device__ __forceinline__ long long pooled_first(const CaptureSyncLink& l, const int T) {     // as capture_sync_grouped_kernel
     if (!l.first_dev) return l.first;
@@ -487,7 +544,7 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_e
     const long long first = pooled_first(l.s, g.S * (g.K + g.CP));
     capture_sync_body<false, true>(CaptureSyncArgs{l.s.cap, first, l.s.stride, nullptr, l.s.offset, l.s.metric, nullptr, g.frames, g.S,
                                                    g.K, g.CP, g.W, g.crop},
-                                   first, l.gamma);
+                                   CapOfArgs{}, first, l.gamma);
 }
 
 static __global__ void __launch_bounds__(kSyncLanes) capture_pool_reduce_kernel(const PooledGroupArgs g) {
@@ -517,9 +574,11 @@ static __global__ void __launch_bounds__(kSyncLanes) capture_pool_reduce_kernel(
     if (lane == 0) l.s.cfo[0] = cfo_of_gamma(make_float2(gr, gi));
 }
 
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_cut_kernel(const PooledGroupArgs g) {
+// The cut, over the launch's argument block: PooledGroupArgs (the float32 capture each link names), or PooledSc16Args (at the end).
+template <class Args>
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_cut_kernel(const Args g) {
     extern __shared__ float4 sync_lds[];
-    const PooledLink& l = g.link[blockIdx.y];
+    const PooledLink& l = g.at(blockIdx.y);
     const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
     const int T = g.S * (g.K + g.CP), W = g.W;
     const long long f = (long long)blockIdx.x * kSyncWaves + wave;
@@ -531,7 +590,7 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_c
         start = pooled_first(l.s, T) + f * l.s.stride + (got < -W ? -W : (got > W ? W : got));
     }
     const float2* const y = reinterpret_cast<const float2*>(region) + (int)(start & 1);      // slot 0 = sample start
-    if (live) capture_window_load(region, l.s.cap, start, T, lane);
+    if (live) capture_window_load(region, g.source().of(l.s), start, T, lane);
     __syncthreads();                                    // (the frame is complete in LDS)
     if (!live) return;
     const float cfo = l.s.cfo[0];
@@ -550,7 +609,7 @@ struct CaptureSyncWideArgs {
 static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_wide_kernel(const CaptureSyncWideArgs a) {
     const long long hi = a.at.lo + (long long)a.at.s.S * (a.at.s.K + a.at.s.CP) - 1;
     const long long got = a.at.first_dev[0];
-    capture_sync_body<true, false, true>(a.at.s, got < a.at.lo ? a.at.lo : (got > hi ? hi : got), nullptr, a.wide);
+    capture_sync_body<true, false, true>(a.at.s, CapOfArgs{}, got < a.at.lo ? a.at.lo : (got > hi ? hi : got), nullptr, a.wide);
 }
 struct PooledWideArgs {
     PooledGroupArgs g;          // one link; link[0].s.cfo: the workspace slot of the capture's fraction
@@ -584,5 +643,43 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_c
     sync_cfo_store<SyncLinear, true>(SyncLinear{0}, y, l.s.x_out + (size_t)f * g.S * (g.crop ? g.K : g.K + g.CP) * 2, 0, cfo, lane,
                                      g.S, g.K, g.CP, g.crop, ipos);
 }
+
+// ---- 16-bit integer I/Q captures (dccn_capture_sync_sc16, dccn_capture_sync_pooled_sc16) ----------------------------------------
+// The cut, the pooled estimate and the pooled cut over CapSc16: argument blocks of their own (the public link structs and the
+// float32 kernels' arguments keep their layout), s.cap / link.s.cap unused.  One cut kernel serves a host `first` and a device
+// one (first_dev: clamped into [lo, lo + T - 1], as capture_sync_at_kernel does); the pooled sum is capture_pool_reduce_kernel
+// itself, which reads no capture; the pooled cut is capture_pool_cut_kernel over PooledSc16Args.
+struct CaptureSyncSc16Args {
+    CaptureSyncArgs s;          // (s.cap is not read; s.first: the start when first_dev is null)
+    CapSc16 src;
+    const long long* first_dev; // nullable [1]
+    long long lo;
+};
+template <bool CFO>
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_sc16_kernel(const CaptureSyncSc16Args a) {
+    long long first = a.s.first;
+    if (a.first_dev) {                                                      // (uniform over the launch)
+        const long long hi = a.lo + (long long)a.s.S * (a.s.K + a.s.CP) - 1;
+        const long long got = a.first_dev[0];
+        first = got < a.lo ? a.lo : (got > hi ? hi : got);
+    }
+    capture_sync_body<CFO>(a.s, a.src, first);
+}
+
+struct PooledSc16Args {
+    PooledLink link;            // (link.s.cap is not read)
+    CapSc16 src;
+    int frames, S, K, CP, W, crop;
+    __device__ __forceinline__ const PooledLink& at(const unsigned) const { return link; }
+    __device__ __forceinline__ CapSc16 source() const { return src; }
+};
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_estimate_sc16_kernel(const PooledSc16Args g) {
+    const PooledLink& l = g.link;
+    const long long first = pooled_first(l.s, g.S * (g.K + g.CP));
+    capture_sync_body<false, true>(CaptureSyncArgs{nullptr, first, l.s.stride, nullptr, l.s.offset, l.s.metric, nullptr, g.frames, g.S,
+                                                   g.K, g.CP, g.W, g.crop},
+                                   g.src, first, l.gamma);
+}
+// (the cut: capture_pool_cut_kernel<PooledSc16Args>)
 
 }  // namespace dccn

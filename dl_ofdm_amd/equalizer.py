@@ -387,15 +387,16 @@ class EqualizerTrainer:
 
     def receive_capture(self, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False,
                         want_llr: bool = False, want_prob: bool = False, frames: Optional[int] = None, acquire: int = 0,
-                        lo: int = 0, cfo_scope: str = "frame", cfo_span: int = 0):
-        """:meth:`receive` on frames that still sit inside one contiguous capture ``cap [n, 2]``, cut at their estimated starts
+                        lo: int = 0, cfo_scope: str = "frame", cfo_span: int = 0, scale: Optional[float] = None):
+        """:meth:`receive` on frames that still sit inside one contiguous capture ``cap [n, 2]`` (float32, or int16 I/Q whose
+        counts are worth ``scale``, ``None``: ``2**-15`` -- converted inside the launches, bit for bit the float32 call), cut at their estimated starts
         by one launch in front of the step (:func:`dl_ofdm_amd.receive.chain_receive_capture`).  ``first=None, acquire=J,
         lo=...``: the frame start inside ``[lo, lo + T)`` is acquired on the device first, from ``J`` frames.  ``cfo=True,
         cfo_scope="capture"``: one carrier offset for the whole capture, pooled over its frames.  ``cfo_span = M > 0`` (with
         ``first=None, acquire=J, cfo=True``): carrier offsets up to ``M + 1/2`` subcarrier spacings; ``result.cfo`` holds totals."""
         from .receive import chain_receive_capture
         return chain_receive_capture(self, cap, first, stride, sync, cfo, want_llr, want_prob, frames, acquire, lo, cfo_scope,
-                                     cfo_span)
+                                     cfo_span, scale)
 
     def adam(self) -> dict:
         s = self.adam_state.cpu().numpy()

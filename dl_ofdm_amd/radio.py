@@ -244,6 +244,32 @@ def apply_cfo_stream(cap: np.ndarray, eps: float, K: int) -> np.ndarray:
     return np.stack([y.real, y.imag], axis=-1).astype(np.float32) if pairs else y
 
 
+def quantize_sc16(cap: np.ndarray, scale) -> np.ndarray:
+    """A capture as a 16-bit front end delivers it: ``rint(cap / scale)`` saturated to ``[-32768, 32767]``, ``int16 [n, 2]``
+    (I, Q interleaved, contiguous).  ``cap``: complex ``[n]`` or float ``[n, 2]``; ``scale``: the value of one count, finite and
+    positive.  The division is taken in fp64."""
+    cap = np.asarray(cap)
+    scale = float(scale)
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError("quantize_sc16: scale must be finite and positive, got %r" % (scale,))
+    pairs = np.stack([cap.real, cap.imag], axis=-1) if np.iscomplexobj(cap) else cap
+    if pairs.ndim != 2 or pairs.shape[1] != 2:
+        raise ValueError("quantize_sc16 takes one capture: complex [n] or float [n, 2]")
+    q = np.rint(pairs.astype(np.float64) / scale)
+    return np.ascontiguousarray(np.clip(q, -32768.0, 32767.0).astype(np.int16))
+
+
+def sc16_to_float(q: np.ndarray, scale) -> np.ndarray:
+    """The value of an ``int16 [n, 2]`` capture, the definition the sc16 entries of the library implement (include/dccn.h):
+    ``float32(q) * float32(scale)`` -- an exact conversion and ONE fp32 multiply per component -- as float32 ``[n, 2]``.  The
+    host model to hold ``dccn_capture_sync_sc16`` and its kin to: they write, bit for bit, what the float32 entries write for
+    this array."""
+    q = np.asarray(q)
+    if q.dtype != np.int16 or q.ndim != 2 or q.shape[1] != 2:
+        raise ValueError("sc16_to_float takes an int16 [n, 2] capture, got %s %r" % (q.dtype, q.shape))
+    return np.ascontiguousarray(q.astype(np.float32) * np.float32(scale))
+
+
 def AWGN_channel_np(inputs: np.ndarray, SNR):
     """Normalise the batch to unit mean IQ power, add complex white noise at ``SNR`` dB
     (per frame, [n,1]); returns (noisy float64 [n,S,n_sc,2], mean noise power)  (radio.py:513-526)."""

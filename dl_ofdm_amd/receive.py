@@ -190,9 +190,9 @@ class RxReceiver:
         return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, est)
 
     def receive_capture(self, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False, acquire: int = 0,
-                        lo: int = 0, cfo_scope: str = "frame", cfo_span: int = 0) -> ReceiveResult:
+                        lo: int = 0, cfo_scope: str = "frame", cfo_span: int = 0, scale: Optional[float] = None) -> ReceiveResult:
         """One receive step on ``batch`` frames that still sit inside one contiguous capture ``cap`` (device tensor ``float32
-        [n, 2]``): frame ``f`` nominally starts at sample ``first + f * stride`` (``None``: frames back to back) and may sit up to
+        [n, 2]``, or ``int16 [n, 2]`` as a front end delivers it -- see ``scale`` below): frame ``f`` nominally starts at sample ``first + f * stride`` (``None``: frames back to back) and may sit up to
         ``sync = W > 0`` samples off.  One launch (:class:`~dl_ofdm_amd.sync.CaptureSync`) stands where ``receive(x, sync=W)``
         has its alignment launch: it cuts each frame at its own estimated start -- linearly, the samples it brings in are the
         capture's, not the frame's other end -- and writes it straight into ``self.x`` (only the K samples behind each prefix
@@ -213,9 +213,15 @@ class RxReceiver:
         offset may be up to ``M + 1/2`` subcarrier spacings.  Acquisition decides the frame start and the whole spacings
         together (``CaptureAcquire(..., cfo_span=M)``), the cut unwraps the prefix's fraction against that and takes the whole
         offset out (``CaptureSync(..., cfo_span=M)``, either ``cfo_scope``): the same number of launches, no host round trip.
-        ``result.cfo`` holds totals, ``result.acquired_cfo_int`` the acquired integer."""
+        ``result.cfo`` holds totals, ``result.acquired_cfo_int`` the acquired integer.
+
+        ``cap`` of dtype ``int16`` (interleaved 16-bit I/Q): sample ``n`` is ``(float(I) * scale, float(Q) * scale)``
+        (``scale=None``: ``2**-15``), converted inside the acquisition and cut launches -- no conversion launch, no float copy --
+        and every result is bit for bit that of the float32 capture ``radio.sc16_to_float(cap, scale)``.  Every combination
+        above at ``cfo_span=0``; ``cfo_span > 0`` with an int16 capture, and ``scale`` with a float32 one, raise."""
         from .sync import CaptureSync, check_cfo_scope
         check_cfo_scope(cfo, cfo_scope)
+        _checked_sc16(cap, scale, cfo_span, "receive_capture")
         M = _checked_cfo_span(cfo_span, first, acquire, cfo)
         W = int(sync)
         if W <= 0:
@@ -233,12 +239,21 @@ class RxReceiver:
                                            cfo=bool(cfo), cfo_scope=cfo_scope, cfo_span=M)
         cs = self._syncs[key]
         first, est0, est_int = _acquired_first(self._syncs, first, acquire, cap, lo, self.dims.S, K, self.CP, self.pilot_sc,
-                                               self.device, M)
+                                               self.device, M, scale)
         _, offset = cs.run(cap, first, stride, out=self.x, lo=lo,             # (lo matters to a device `first` only)
-                           acquired=(est_int, est0) if M else None)
+                           acquired=(est_int, est0) if M else None, scale=scale)
         check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
         return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, cs.cfo,
                              first if isinstance(first, torch.Tensor) else None, est0, est_int)
+
+
+def _checked_sc16(cap, scale, cfo_span, what: str) -> None:
+    """an int16 capture, or a ``scale``, judged before anything is launched (acquisition runs ahead of the cut, which would
+    otherwise be the first to look): :func:`~dl_ofdm_amd.sync.capture_format`'s refusals.  A float32 capture without ``scale``
+    passes through untouched."""
+    if scale is not None or (isinstance(cap, torch.Tensor) and cap.dtype == torch.int16):
+        from .sync import capture_format
+        capture_format(cap, scale, what, int(cfo_span))
 
 
 def _checked_cfo_span(cfo_span, first, acquire, cfo) -> int:
@@ -253,7 +268,8 @@ def _checked_cfo_span(cfo_span, first, acquire, cfo) -> int:
     return M
 
 
-def _acquired_first(stages: dict, first, acquire: int, cap, lo: int, S: int, K: int, CP: int, pilot_sc, device, cfo_span: int = 0):
+def _acquired_first(stages: dict, first, acquire: int, cap, lo: int, S: int, K: int, CP: int, pilot_sc, device, cfo_span: int = 0,
+                    scale: Optional[float] = None):
     """``first`` as the cut takes it, and the acquisition's carrier-frequency offset (the fraction, and with ``cfo_span > 0``
     the integer): an integer or a device tensor passes through; ``None`` runs :class:`~dl_ofdm_amd.sync.CaptureAcquire` over
     ``acquire`` frames (kept in ``stages``)."""
@@ -271,7 +287,7 @@ def _acquired_first(stages: dict, first, acquire: int, cap, lo: int, S: int, K: 
     if key not in stages:
         stages[key] = CaptureAcquire(S, K, CP, pilot_sc, J, device, cfo_span=cfo_span)
     acq = stages[key]
-    return acq.run(cap, lo), acq.cfo, (acq.cfo_int if cfo_span else None)
+    return acq.run(cap, lo, scale=scale), acq.cfo, (acq.cfo_int if cfo_span else None)
 
 
 def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: int = 0, cfo: bool = False) -> ReceiveResult:
@@ -306,8 +322,9 @@ def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: 
 
 def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False,
                           want_llr: bool = False, want_prob: bool = False, frames: Optional[int] = None, acquire: int = 0,
-                          lo: int = 0, cfo_scope: str = "frame", cfo_span: int = 0) -> ReceiveResult:
-    """:func:`chain_receive` on frames that still sit inside one contiguous capture ``cap`` (device tensor ``float32 [n, 2]``;
+                          lo: int = 0, cfo_scope: str = "frame", cfo_span: int = 0, scale: Optional[float] = None) -> ReceiveResult:
+    """:func:`chain_receive` on frames that still sit inside one contiguous capture ``cap`` (device tensor ``float32 [n, 2]``, or
+    ``int16 [n, 2]`` with ``scale`` as :meth:`RxReceiver.receive_capture` takes it;
     ``EqualizerTrainer.receive_capture``): as :meth:`RxReceiver.receive_capture`, one :class:`~dl_ofdm_amd.sync.CaptureSync`
     launch cuts every frame at its estimated start -- linearly, up to ``sync = W > 0`` samples off ``first + f * stride`` -- and
     writes it into the plan's ``x`` where ``chain_receive(x, sync=W)`` has its alignment launch.  ``frames`` (``None``: every
@@ -322,6 +339,7 @@ def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, syn
     ``cfo_span = M > 0``: offsets beyond half a subcarrier spacing, as there."""
     from .sync import CaptureSync, check_cfo_scope
     check_cfo_scope(cfo, cfo_scope)
+    _checked_sc16(cap, scale, cfo_span, "chain_receive_capture")
     M = _checked_cfo_span(cfo_span, first, acquire, cfo)
     if not tr.fused_ok:
         raise _lib.DccnError("the chain's receive path needs the fused equaliser step")
@@ -353,9 +371,9 @@ def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, syn
                                  cfo_span=M)
     cs = syncs[key]
     first, est0, est_int = _acquired_first(tr.__dict__.setdefault("_capture_acquires", {}), first, acquire, cap, lo, S, K, CP,
-                                           o.pilotSc, tr.device, M)
+                                           o.pilotSc, tr.device, M, scale)
     _, offset = cs.run(cap, first, step, out=pl.x, lo=lo,                     # (lo matters to a device `first` only)
-                       acquired=(est_int, est0) if M else None)
+                       acquired=(est_int, est0) if M else None, scale=scale)
     packed, llr, prob = pl.receive(want_llr, want_prob)
     return ReceiveResult(packed, llr, prob, int(o.frame_size), int(tr.FLAGS.nbits), offset, cs.cfo,
                          first if on_device else None, est0, est_int)

@@ -26,6 +26,12 @@ of the carrier offset: acquisition decides the whole number of spacings together
 (``dccn_frame_sync_grouped``, ``dccn_capture_sync_grouped``, ``dccn_capture_acquire_grouped``: one launch each, acquisition three), the
 front end of :class:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup`; link i's results are bit for bit the solo class's.
 
+:class:`CaptureSync` and :class:`CaptureAcquire` also take the capture as a front end delivers it, ``int16 [n, 2]`` ("sc16":
+interleaved 16-bit integer I/Q) with a ``scale`` (``dccn_capture_sync_sc16``, ``dccn_capture_sync_pooled_sc16``,
+``dccn_capture_acquire_sc16``): sample ``n`` is ``(float(I) * scale, float(Q) * scale)``, converted inside the launches, and every
+output is bit for bit what the float32 call writes for ``radio.sc16_to_float(cap, scale)``.  ``cfo_span > 0`` and the group
+classes stay float32-only.
+
 There is no CPU or PyTorch fallback: an unsupported shape or a tensor that is not on the GPU raises :class:`DccnError`.
 """
 from __future__ import annotations
@@ -55,6 +61,33 @@ def rotate_response_(H: torch.Tensor, offset: torch.Tensor) -> torch.Tensor:
 
 
 CFO_SCOPES = ("frame", "capture")
+SC16_DEFAULT_SCALE = 2.0 ** -15     # full scale onto [-1, 1)
+
+
+def capture_format(cap, scale, what: str, cfo_span: int = 0):
+    """``(is_sc16, scale)`` of a capture handed to ``what``: a contiguous device tensor ``float32 [n, 2]`` (``scale`` must be
+    ``None``) or ``int16 [n, 2]`` (``scale=None``: ``2**-15``; otherwise finite and positive).  :class:`DccnError` for anything
+    else, and for an int16 capture where ``cfo_span > 0``: the wide entries are float32-only."""
+    if not isinstance(cap, torch.Tensor) or cap.device.type != "cuda":
+        raise DccnError("%s takes a device tensor; there is no CPU fallback" % what)
+    if cap.dtype not in (torch.float32, torch.int16) or cap.dim() != 2 or cap.shape[1] != 2 or not cap.is_contiguous():
+        raise DccnError("%s: cap must be a contiguous float32 [n, 2] or int16 [n, 2] tensor, got %s %r"
+                        % (what, cap.dtype, tuple(cap.shape)))
+    if cap.dtype == torch.float32:
+        if scale is not None:
+            raise DccnError("%s: `scale` belongs to an int16 capture; a float32 capture is taken as it is" % what)
+        return False, None
+    if cfo_span:
+        raise DccnError("%s: an int16 capture cannot be combined with cfo_span > 0 (the wide entries are float32-only)" % what)
+    try:
+        value = SC16_DEFAULT_SCALE if scale is None else float(scale)
+    except (TypeError, ValueError):
+        raise DccnError("%s: scale must be a finite, positive number, got %r" % (what, scale))
+    # the library takes an fp32: judge the value it will see
+    value = C.c_float(value).value
+    if not (value > 0.0) or value == float("inf"):
+        raise DccnError("%s: scale must be a finite, positive fp32 number, got %r" % (what, scale))
+    return True, value
 
 
 def check_cfo_scope(cfo, cfo_scope) -> bool:
@@ -143,7 +176,9 @@ class CaptureSync:
     """Frames cut from ONE CONTIGUOUS CAPTURE at their estimated starts (``dccn_capture_sync``): ``run(cap, first) -> (frames_out,
     offset)``.
 
-    ``cap``: contiguous device tensor ``float32 [n, 2]``, what a front end hands over.  Frame ``f`` nominally starts at sample
+    ``cap``: contiguous device tensor ``float32 [n, 2]``, or ``int16 [n, 2]`` with ``scale`` -- what a front end hands over
+    (``dccn_capture_sync_sc16`` / ``dccn_capture_sync_pooled_sc16``: converted inside the launch, the results bit for bit those of
+    the float32 capture ``radio.sc16_to_float(cap, scale)``; one object serves both dtypes call by call).  Frame ``f`` nominally starts at sample
     ``first + f * stride`` (``stride=None``: ``T = S (K + CP)``, frames back to back).  The estimator is :class:`FrameSync`'s over
     the window ``[start - W, start + T + W)``, indexed linearly: nothing wraps, so the samples the alignment brings in are the
     frame's neighbours in the air, and with ``cfo=True`` they carry no phase step.  The caller leaves ``W`` samples of the capture
@@ -160,7 +195,8 @@ class CaptureSync:
     exceed half a subcarrier spacing.  ``run(..., acquired=(cfo_int, cfo_frac))`` takes the pair that
     ``CaptureAcquire(..., cfo_span=M)`` left on the device (``.cfo_int``, ``.cfo``); the prefix's fraction is unwrapped against it,
     the whole offset is taken out and ``self.cfo`` holds totals.  The integer is only known through acquisition, so with
-    ``cfo_scope="frame"`` the start is a device tensor too.  ``cfo_span=0``, the default, is the calls above.
+    ``cfo_scope="frame"`` the start is a device tensor too.  ``cfo_span=0``, the default, is the calls above.  float32 captures
+    only: an int16 capture raises :class:`DccnError`.
     """
 
     def __init__(self, S: int, K: int, CP: int, W: int, frames: int, device="cuda", out_kin: Optional[int] = None,
@@ -210,35 +246,39 @@ class CaptureSync:
                             "element on the capture's device, what CaptureAcquire(cfo_span=M) left there")
         return (acquired[0].data_ptr(), acquired[1].data_ptr())
 
-    def _launch(self, cap, first, stride, out: Optional[torch.Tensor], lo: Optional[int] = None, acquired=None) -> None:
-        if not isinstance(cap, torch.Tensor) or cap.device.type != "cuda":
-            raise DccnError("CaptureSync takes a device tensor; there is no CPU fallback")
-        if cap.dtype != torch.float32 or cap.dim() != 2 or cap.shape[1] != 2 or not cap.is_contiguous():
-            raise DccnError("CaptureSync: cap must be a contiguous float32 [n, 2] tensor, got %s %r" % (cap.dtype, tuple(cap.shape)))
+    def _launch(self, cap, first, stride, out: Optional[torch.Tensor], lo: Optional[int] = None, acquired=None, scale=None) -> None:
+        sc16, scale = capture_format(cap, scale, "CaptureSync", self.cfo_span)
         stride = self.T if stride is None else int(stride)
         p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         pair = self._acquired_pair(acquired, cap)
         if self.pooled:
-            return self._launch_pooled(cap, first, stride, out, lo, pair)
+            return self._launch_pooled(cap, first, stride, out, lo, pair, scale if sc16 else None)
         if pair and not isinstance(first, torch.Tensor):
             raise DccnError("CaptureSync(cfo_span=M > 0): the per-frame cut reads the start where acquisition left it, a device "
                             "tensor `first` with lo=...")
         tail = (stride, self.frames, self.S, self.K, self.CP, self.W, self.out_kin, p(out), self.offset.data_ptr(), p(self.cfo),
                 p(self.metric), *pair, self._stream())
-        if isinstance(first, torch.Tensor):
+        on_dev = isinstance(first, torch.Tensor)
+        if on_dev:
             # the start is on the device (CaptureAcquire left it there): nothing is read back
             if lo is None:
                 raise DccnError("CaptureSync: a device tensor `first` needs lo=..., the origin of the range [lo, lo + T) it lies in")
             if first.device != cap.device or first.dtype != torch.int64 or first.numel() != 1 or not first.is_contiguous():
                 raise DccnError("CaptureSync: a device `first` must be an int64 tensor of one element on the capture's device")
+        if sc16:
+            check(self.lib.dccn_capture_sync_sc16(cap.data_ptr(), int(cap.shape[0]), scale, 0 if on_dev else int(first),
+                                                  first.data_ptr() if on_dev else None, int(lo) if on_dev else 0, *tail),
+                  "dccn_capture_sync_sc16")
+        elif on_dev:
             entry = "dccn_capture_sync_wide" if pair else "dccn_capture_sync_at"
             check(getattr(self.lib, entry)(cap.data_ptr(), int(cap.shape[0]), first.data_ptr(), int(lo), *tail), entry)
         else:
             check(self.lib.dccn_capture_sync(cap.data_ptr(), int(cap.shape[0]), int(first), *tail), "dccn_capture_sync")
 
-    def _launch_pooled(self, cap, first, stride: int, out: Optional[torch.Tensor], lo: Optional[int], pair: tuple = ()) -> None:
-        """``dccn_capture_sync_pooled`` (``pair``: ``dccn_capture_sync_pooled_wide``): estimate, sum and cut, three launches on the
-        current stream"""
+    def _launch_pooled(self, cap, first, stride: int, out: Optional[torch.Tensor], lo: Optional[int], pair: tuple = (),
+                       scale: Optional[float] = None) -> None:
+        """``dccn_capture_sync_pooled`` (``pair``: ``dccn_capture_sync_pooled_wide``; ``scale``: ``dccn_capture_sync_pooled_sc16``
+        on an int16 capture): estimate, sum and cut, three launches on the current stream"""
         if out is None:
             raise DccnError('CaptureSync(cfo_scope="capture") has no offsets-only call: the pooled entry writes the frames')
         on_dev = isinstance(first, torch.Tensor)
@@ -248,7 +288,10 @@ class CaptureSync:
             if first.device != cap.device or first.dtype != torch.int64 or first.numel() != 1 or not first.is_contiguous():
                 raise DccnError("CaptureSync: a device `first` must be an int64 tensor of one element on the capture's device")
         entry = "dccn_capture_sync_pooled_wide" if pair else "dccn_capture_sync_pooled"
-        check(getattr(self.lib, entry)(cap.data_ptr(), int(cap.shape[0]), 0 if on_dev else int(first),
+        if scale is not None:
+            entry = "dccn_capture_sync_pooled_sc16"
+        fmt = () if scale is None else (scale,)
+        check(getattr(self.lib, entry)(cap.data_ptr(), int(cap.shape[0]), *fmt, 0 if on_dev else int(first),
                                        first.data_ptr() if on_dev else None, int(lo) if on_dev else 0, stride,
                                        self.frames, self.S, self.K, self.CP, self.W, self.out_kin, out.data_ptr(),
                                        self.offset.data_ptr(), self.cfo.data_ptr(),
@@ -256,13 +299,14 @@ class CaptureSync:
                                        int(self.ws.numel()), self._stream()), entry)
 
     def run(self, cap: torch.Tensor, first, stride: Optional[int] = None, out: Optional[torch.Tensor] = None,
-            lo: Optional[int] = None, acquired=None) -> Tuple[torch.Tensor, torch.Tensor]:
+            lo: Optional[int] = None, acquired=None, scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Estimate every frame's offset and write the frames, cut at their estimated starts (and with ``cfo=True`` derotated),
         to ``out`` (``None``: this object's own buffer), on the current stream.  ``out`` must not overlap ``cap``.
 
         ``first``: an integer, or a device ``int64`` tensor of one element together with ``lo`` (``dccn_capture_sync_at``: the
         launch reads the start from device memory and keeps it inside ``[lo, lo + T - 1]``; every window must lie inside the
-        capture for every start in that range).  ``acquired``: the pair of a stage built with ``cfo_span = M > 0``."""
+        capture for every start in that range).  ``acquired``: the pair of a stage built with ``cfo_span = M > 0``.
+        ``scale``: the value of one count of an ``int16`` capture (``None``: ``2**-15``); not given with a float32 capture."""
         want = (self.frames, self.S, self.out_kin, 2)
         if out is None:
             if self.out is None:
@@ -271,13 +315,14 @@ class CaptureSync:
         elif (not isinstance(out, torch.Tensor) or out.device.type != "cuda" or out.dtype != torch.float32
               or tuple(out.shape) != want or not out.is_contiguous()):
             raise DccnError("CaptureSync.run: out must be a contiguous float32 %r device tensor" % (want,))
-        self._launch(cap, first, stride, out, lo, acquired)
+        self._launch(cap, first, stride, out, lo, acquired, scale)
         return out, self.offset
 
-    def offsets(self, cap: torch.Tensor, first, stride: Optional[int] = None, lo: Optional[int] = None, acquired=None) -> torch.Tensor:
-        """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``.  ``first`` / ``lo`` / ``acquired`` as
-        :meth:`run`."""
-        self._launch(cap, first, stride, None, lo, acquired)
+    def offsets(self, cap: torch.Tensor, first, stride: Optional[int] = None, lo: Optional[int] = None, acquired=None,
+                scale: Optional[float] = None) -> torch.Tensor:
+        """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``.  ``first`` / ``lo`` / ``acquired`` /
+        ``scale`` as :meth:`run`."""
+        self._launch(cap, first, stride, None, lo, acquired, scale)
         return self.offset
 
 
@@ -298,7 +343,10 @@ class CaptureAcquire:
     decides the symbol position and the whole number of spacings ``m`` in ``[-M, M]`` together, from the pilots' bins shifted by
     ``m``; ``cfo`` stays the fraction, ``cfo_int`` (``int32 [1]``, resident) is ``m``, the offset is their sum, and
     ``phase_metric`` is ``float32 [S, 2 M + 1]``.  ``M <= K / 2 - 1``; the shift is circular in ``K``, so on the reference grid
-    ``M <= 7`` is the span a real channel filter supports.  ``cfo_span=0``, the default, is the narrow call (``cfo_int`` stays 0)."""
+    ``M <= 7`` is the span a real channel filter supports.  ``cfo_span=0``, the default, is the narrow call (``cfo_int`` stays 0).
+
+    ``cap`` may be ``int16 [n, 2]`` with ``scale`` (``dccn_capture_acquire_sc16``; as :class:`CaptureSync`, bit for bit the float32
+    call on the converted capture, one object for both dtypes); not with ``cfo_span > 0``."""
 
     def __init__(self, S: int, K: int, CP: int, pilot_sc, J: int, device="cuda", cfo_span: int = 0):
         self.lib = _lib.load()
@@ -330,14 +378,17 @@ class CaptureAcquire:
             nws = int(self.lib.dccn_capture_acquire_workspace_size(self.S, self.K, self.CP, self.n_pilot, self.J))
         self.ws = torch.empty(nws, dtype=torch.uint8, device=self.device)
 
-    def run(self, cap: torch.Tensor, lo: int = 0) -> torch.Tensor:
-        """Three launches on the current stream; returns ``self.first``."""
-        if not isinstance(cap, torch.Tensor) or cap.device.type != "cuda":
-            raise DccnError("CaptureAcquire takes a device tensor; there is no CPU fallback")
-        if cap.dtype != torch.float32 or cap.dim() != 2 or cap.shape[1] != 2 or not cap.is_contiguous():
-            raise DccnError("CaptureAcquire: cap must be a contiguous float32 [n, 2] tensor, got %s %r"
-                            % (cap.dtype, tuple(cap.shape)))
+    def run(self, cap: torch.Tensor, lo: int = 0, scale: Optional[float] = None) -> torch.Tensor:
+        """Three launches on the current stream; returns ``self.first``.  ``scale``: the value of one count of an ``int16``
+        capture (``None``: ``2**-15``); not given with a float32 capture."""
+        sc16, scale = capture_format(cap, scale, "CaptureAcquire", self.cfo_span)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if sc16:
+            check(self.lib.dccn_capture_acquire_sc16(cap.data_ptr(), int(cap.shape[0]), scale, int(lo), self.J, self.S, self.K,
+                                                     self.CP, self.pilot_sc.data_ptr(), self.n_pilot, self.first.data_ptr(),
+                                                     self.cfo.data_ptr(), self.sym_metric.data_ptr(), self.phase_metric.data_ptr(),
+                                                     self.ws.data_ptr(), int(self.ws.numel()), stream), "dccn_capture_acquire_sc16")
+            return self.first
         if self.cfo_span:
             check(self.lib.dccn_capture_acquire_wide(cap.data_ptr(), int(cap.shape[0]), int(lo), self.J, self.S, self.K, self.CP,
                                                      self.pilot_sc.data_ptr(), self.n_pilot, self.cfo_span, self.first.data_ptr(),

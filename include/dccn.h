@@ -1335,6 +1335,45 @@ int dccn_capture_sync_pooled_wide(const float* cap, long long n_samples, long lo
                                   const int32_t* cfo_int_dev, const float* cfo_frac_dev, void* workspace, size_t workspace_bytes,
                                   dccn_stream_t stream);
 
+/* ==== 16-bit integer I/Q captures, converted inside the launches =================
+ * A front end (an ADC, an SDR driver) delivers interleaved 16-bit integer I/Q ("sc16"), not float32.  These entries take the
+ * capture as it arrives: cap int16 [n_samples, 2], contiguous, (I, Q) interleaved, native byte order, the base on a 16-byte boundary.
+ * The value of sample n is
+ *     ( (float)I[n] * scale, (float)Q[n] * scale )
+ * -- the int16 -> fp32 conversion is exact and each component gets ONE fp32 multiply, rounded to nearest.  scale is a finite,
+ * positive host value (2^-15 maps full scale onto [-1, 1)).  The receiver and the chain normalise their input by batch moments, so
+ * scale moves no decision; it sets the magnitude of the metrics and keeps the samples out of the denormals.
+ * THE CONTRACT: every output of an sc16 entry equals, bit for bit, what the float32 entry writes when it is given the converted
+ * capture c[n] = the value above (frames, offset, metric, per-frame and pooled cfo; first_out, cfo_out, sym_metric, phase_metric).
+ * Only the loads differ: a window is read four samples per 16-byte load, its head and tail with 8- or 4-byte loads (no lane reads a
+ * sample outside [b_f - W, b_f + T + W): nothing at or beyond cap + 4*n_samples bytes is touched, whatever n_samples mod 4 is),
+ * and lands in LDS where the float32 loader puts it; acquisition reads one 4-byte sample per load.  Everything behind the load is
+ * the float32 entry's code, the kernels are new instantiations and the float32 kernels are untouched.  No conversion launch, no
+ * float copy of the capture, half the capture bytes per launch.
+ * dccn_capture_sync_sc16:        first_dev == NULL: dccn_capture_sync (lo is ignored); otherwise dccn_capture_sync_at, `first`
+ *                                ignored, the value read clamped into [lo, lo + T - 1].  One launch.
+ * dccn_capture_sync_pooled_sc16: dccn_capture_sync_pooled (first / first_dev / lo as there); three launches, the same workspace.
+ * dccn_capture_acquire_sc16:     dccn_capture_acquire; three launches, the same workspace.
+ * dccn_capture_sync_supported, dccn_capture_acquire_supported, dccn_capture_acquire_workspace_size and
+ * dccn_capture_sync_pooled_workspace_size answer for both formats.
+ * Plan first, then launch: refused before anything is launched (nothing is written) wherever the float32 entry refuses, with the
+ * capture's extent taken as 4*n_samples bytes (so an x_out that starts at cap + 4*n_samples is accepted), and for a scale that is
+ * not finite or not > 0 -- DCCN_ERR_INVALID_ARG; a short workspace DCCN_ERR_WORKSPACE; inside a chain group DCCN_ERR_UNSUPPORTED.
+ * float32 only: the wide entries (dccn_capture_acquire_wide, dccn_capture_sync_wide, dccn_capture_sync_pooled_wide) and every
+ * grouped entry. */
+int dccn_capture_sync_sc16(const int16_t* cap, long long n_samples, float scale, long long first,
+                           const long long* first_dev /* nullable */, long long lo, long long stride, int frames, int S, int K, int CP,
+                           int W, int out_kin, float* x_out, int32_t* offset, float* cfo /* nullable */, float* metric /* nullable */,
+                           dccn_stream_t stream);
+int dccn_capture_sync_pooled_sc16(const int16_t* cap, long long n_samples, float scale, long long first,
+                                  const long long* first_dev /* nullable */, long long lo, long long stride, int frames, int S, int K,
+                                  int CP, int W, int out_kin, float* x_out, int32_t* offset, float* cfo_out,
+                                  float* metric /* nullable */, void* workspace, size_t workspace_bytes, dccn_stream_t stream);
+int dccn_capture_acquire_sc16(const int16_t* cap, long long n_samples, float scale, long long lo, int J, int S, int K, int CP,
+                              const int* pilot_sc, int n_pilot, long long* first_out, float* cfo_out,
+                              float* sym_metric /* nullable */, float* phase_metric /* nullable */, void* workspace,
+                              size_t workspace_bytes, dccn_stream_t stream);
+
 /* ==== host utility: CRC32C (Castagnoli), the checksum of TensorFlow's tensor-bundle checkpoints =========
  * (tf.train.Saver files the reference writes at dev/py/ofdmreceiver_np.py:271).
  * Returns the CRC of (previous data ++ data) given the CRC of the previous data (0 to start).  Host code. */

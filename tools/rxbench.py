@@ -33,6 +33,11 @@
         receive_capture(cap, first) with the start known, J = 4 and 16, and the acquisition launches alone; 73 and 1170 frames
         QPSK, same alternation.  --cfo_span M ...: also dccn_capture_acquire_wide alone at every M against dccn_capture_acquire of
         the same build, and receive_capture(..., cfo=True, acquire=16, cfo_span=M) against cfo_span=0, per frame and pooled
+    python tools/rxbench.py --sc16 [--sync 3] [--out FILE]
+        receive_capture on a 16-bit integer I/Q capture (dccn_capture_sync_sc16, dccn_capture_sync_pooled_sc16,
+        dccn_capture_acquire_sc16) against (f32) the same call on the same values as float32 and (conv) cap.to(float32) * scale
+        followed by (f32), what a caller without the sc16 entries does; cfo=True under both cfo_scopes and acquire=16; 73, 1170 and
+        20 000 frames QPSK on run_stream captures quantised with radio.quantize_sc16, same alternation
 
 Shapes: 1170 frames QPSK and 16-QAM, and one 20 000-frame QPSK sweep batch (N = 64).  Every shape runs in a child process of
 its own under a time limit; the parent never opens the GPU and stops at the first child that fails.  Times are medians over
@@ -342,6 +347,90 @@ def main_acquire(a):
     return 0
 
 
+def run_sc16(frames, nbits, W, iters, repeats):
+    """receive_capture(int16 capture, scale) against (f32) receive_capture on sc16_to_float of the same capture and (conv) the
+    conversion a caller writes in torch, cap.to(float32) * scale, followed by (f32) -- on one run_stream capture (ETU, static),
+    quantised with scale = max|component| / 16384.  Three settings: cfo=True per frame, cfo=True pooled over the capture, and
+    acquire=16 (the start unknown).  sc16 and f32 must return the same bits, offsets and estimates before anything is timed; the
+    cut launches alone as well."""
+    import numpy as np
+    import torch
+    from dl_ofdm_amd import _lib, ofdm, util
+    from dl_ofdm_amd.engine import RxDims, glorot_init
+    from dl_ofdm_amd.radio import quantize_sc16, rayleigh_chan_lte, sc16_to_float
+    from dl_ofdm_amd.receive import RxReceiver
+    from dl_ofdm_amd.receiver_mp import Flags
+    from dl_ofdm_amd.sync import CaptureSync
+    CP = KIN - F
+    T = S * KIN
+    Fl = Flags(channel="ETU", nbits=nbits, nfft=F, nsymbol=S, longcp=True, nfilter=64)
+    o = ofdm.ofdm_tx(Fl)
+    np.random.seed(0)
+    iq, _, _ = o.ofdm_tx_frame_np(util.bit_source(nbits, o.frame_size, frames + 3))
+    lead, cut, lo = 40, 211, 5
+    stream, _ = rayleigh_chan_lte(Fl, o.Fs).run_stream(iq, lead)
+    stream = stream[lead + cut:]                                          # the capture begins inside frame 0
+    pairs = np.stack([stream.real, stream.imag], axis=-1).astype(np.float32)
+    scale = float(np.float32(np.abs(pairs).max() / 16384.0))
+    q_np = quantize_sc16(pairs, scale)
+    q = torch.as_tensor(q_np, device="cuda")
+    f = torch.as_tensor(sc16_to_float(q_np, scale), device="cuda")
+    true = lo + (T - cut - lo) % T
+    dims = RxDims(S, KIN, F, D, nbits)
+    rc = RxReceiver(dims, frames, glorot_init(dims, 1), CP=CP, pilot_sc=o.pilotSc)
+    settings = {"cfo": dict(first=true, cfo=True), "cfo_pooled": dict(first=true, cfo=True, cfo_scope="capture"),
+                "acquire16": dict(acquire=16, lo=lo)}
+    variants = {}
+    for name, kw in settings.items():
+        want = rc.receive_capture(f, sync=W, **kw)
+        want = [None if t is None else t.clone() for t in (want.packed, want.offset, want.cfo, want.first, want.acquired_cfo)]
+        got = rc.receive_capture(q, sync=W, scale=scale, **kw)
+        got = (got.packed, got.offset, got.cfo, got.first, got.acquired_cfo)
+        assert all((a is None and b is None) or torch.equal(a, b) for a, b in zip(want, got)), name
+        assert torch.equal(q.to(torch.float32) * scale, f)
+        variants[name + "_sc16"] = lambda kw=kw: rc.receive_capture(q, sync=W, scale=scale, **kw)
+        variants[name + "_f32"] = lambda kw=kw: rc.receive_capture(f, sync=W, **kw)
+        variants[name + "_conv"] = lambda kw=kw: rc.receive_capture(q.to(torch.float32) * scale, sync=W, **kw)
+    for name, kw in (("cfo", {}), ("cfo_pooled", dict(cfo_scope="capture"))):
+        cs = CaptureSync(S, F, CP, W, frames, "cuda", want_metric=False, cfo=True, **kw)
+        variants[name + "_cut_sc16"] = lambda cs=cs: cs.run(q, true, scale=scale)
+        variants[name + "_cut_f32"] = lambda cs=cs: cs.run(f, true)
+    variants["conv_alone"] = lambda: q.to(torch.float32) * scale
+    us, spread = timed(variants, iters, repeats)
+    n = int(q.shape[0])
+    return {"frames": frames, "nbits": nbits, "W": W, "iters": iters, "repeats": repeats, "us": us, "spread": spread,
+            "capture_samples": n, "capture_bytes": {"sc16": 4 * n, "f32": 8 * n}, "frames_bytes_written": frames * T * 8,
+            "scale": scale, "build_id": _lib.load().dccn_build_id().decode()}
+
+
+def main_sc16(a):
+    """one child process per shape (73, 1170 and 20 000 frames, QPSK), under a time limit; the parent never opens the GPU"""
+    res, W = [], a.sync or 3
+    for fr, nb in ((73, 2), (1170, 2), (20000, 2)):
+        cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, os.path.abspath(__file__), "--sc16", "--one", "%d,%d" % (fr, nb),
+               "--sync", str(W), "--iters", str(a.iters if fr < 10000 else max(a.iters // 5, 10)), "--repeats", str(a.repeats)]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        if r.returncode != 0:               # nothing more is started on the GPU after a failure
+            sys.stderr.write(r.stderr[-2000:])
+            print(json.dumps({"bench": "rxbench.sc16", "failed": [fr, nb], "rc": r.returncode, "shapes": res}))
+            return 1
+        res.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    doc = {"bench": "rxbench.sc16",
+           "variants": {"*_sc16": "receive_capture(int16 capture, scale=...)", "*_f32": "receive_capture(the same values as float32)",
+                        "*_conv": "receive_capture(cap.to(float32) * scale): the conversion launches, then the float32 call",
+                        "cfo": "first known, cfo=True (per frame)", "cfo_pooled": "first known, cfo=True, cfo_scope='capture'",
+                        "acquire16": "first=None, acquire=16, lo=5", "*_cut_*": "the CaptureSync launches alone",
+                        "conv_alone": "cap.to(float32) * scale alone"},
+           "unit": "us per call (median over repeats of the mean of `iters` back-to-back calls); spread = (max - min) / median",
+           "shapes": res}
+    print(json.dumps(doc))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+    return 0
+
+
 def run_chains(mods, frames, iters, repeats):
     """G (equaliser -> frozen receiver) chains, one per link, `frames` frames each: (a) G solo receive calls back to back on one
     stream, (b) one grouped call -- same parameters, same frames, inputs resident; the two must agree before anything is timed"""
@@ -579,6 +668,8 @@ def main():
     ap.add_argument("--cfo_span", "--cfo-span", type=int, nargs="+", default=[],
                     help="with --acquire: also time the wide acquisition (dccn_capture_acquire_wide) at these spans M, and "
                          "receive_capture(..., cfo=True, cfo_span=M) against cfo_span=0")
+    ap.add_argument("--sc16", action="store_true",
+                    help="time receive_capture on an int16 capture against the float32 call and against convert-then-call")
     ap.add_argument("--front-sync", action="store_true", help="(internal, with --one-chains: time the alignment of frames cut in advance)")
     ap.add_argument("--front-solo-only", action="store_true",
                     help="--chains with a front end: only the per-link variants (for DCCN_LIB_PATH = the parent's build)")
@@ -586,6 +677,12 @@ def main():
     a = ap.parse_args()
     if a.cfo_scope == "capture" and not (a.cfo and a.capture):
         ap.error("--cfo_scope capture needs --capture --cfo")
+    if a.sc16:
+        if a.one:
+            fr, nb = (int(v) for v in a.one.split(","))
+            print(json.dumps(run_sc16(fr, nb, a.sync or 3, a.iters, a.repeats)))
+            return 0
+        return main_sc16(a)
     if a.one_chains and (a.front_sync or a.capture or a.acquire):
         print(json.dumps(run_group_front([int(v) for v in a.one_chains.split(",")], a.frames, a.sync or 3, a.cfo, a.front_sync,
                                          a.capture or a.acquire, a.acquire_frames if a.acquire else None, a.iters, a.repeats,
