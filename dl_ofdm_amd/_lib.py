@@ -162,6 +162,14 @@ class PooledLink(C.Structure):
     _fields_ = CaptureLink._fields_ + [("workspace", c_void_p), ("workspace_bytes", c_size_t)]
 
 
+class ClassicalReceiveArgs(C.Structure):
+    """dccn_classical_receive_args"""
+    _fields_ = [(n, c_int) for n in ("frames", "S", "K", "CP", "P", "D", "E", "nbits", "m", "win", "mode")] + \
+               [(n, c_float) for n in ("noise_var", "pv_re", "pv_im")] + \
+               [(n, c_void_p) for n in ("dft", "w", "pil", "dat", "empty", "table", "labels", "x", "packed", "llr", "chest",
+                                        "y_freq", "noise")]
+
+
 METRICS_BYTES = C.sizeof(Metrics)
 ADAM_STATE_BYTES = C.sizeof(AdamState)
 
@@ -234,6 +242,8 @@ SIGNATURES = {
     "dccn_classical_gain": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _sz, _vp]),
     "dccn_classical_estimate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "dccn_classical_detect": (_i, [_vp] * 8 + [_i] * 7 + [_vp, _sz, _vp]),
+    "dccn_classical_receive_supported": (_i, [_i] * 7),
+    "dccn_classical_receive": (_i, [POINTER(ClassicalReceiveArgs), _vp]),
     "dccn_set_tuning": (_i, [_i, _i]),
     "dccn_get_tuning": (_i, [_i]),
     "dccn_dense_tail_supported": (_i, [_i, _i, _i, _i]),

@@ -1,0 +1,137 @@
+"""The label-free classical detector of the receive path: frames -> packed bits (and max-log LLRs) by the pilot-aided
+LS / ALMMSE receivers of :mod:`dl_ofdm_amd.benchmark_gpu`, as ONE launch (``dccn_classical_receive``, include/dccn.h
+"classical receive"; kernel: csrc/classical_receive.h).
+
+What it has that the BER-curve tool (``ClassicalReceiverGPU.receive``) lacks: it needs no transmitted bits and no true SNR
+(the noise variance is the mean power of the frame's own empty carriers), it returns the receive path's ``packed`` / ``llr``
+(:class:`~dl_ofdm_amd.receive.ReceiveResult`), and nothing crosses HBM or the host between its stages.  It needs no training:
+a fallback where the equaliser chain floors or was never trained, and the in-product baseline of that chain on real captures.
+
+:class:`ClassicalRxReceiver` takes the front-end arguments of :class:`~dl_ofdm_amd.receive.RxReceiver` with the same meanings,
+refusals and launch counts (the front end is that class's own code): the alignment / capture-cut stage writes whole symbols
+straight into ``self.x`` and the classical launch stands where ``dccn_rx_receive_step`` stands.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import ClassicalReceiveArgs, check
+from .receive import ReceiveResult, _FrontEnd, row_bytes
+
+METHODS = {"ALMMSE": 2, "LS-Spline": 0, "LS-Linear": 0}      # -> dccn_classical_receive's mode
+
+
+class ClassicalRxReceiver(_FrontEnd):
+    """Fixed-shape classical receive engine on one GPU: ``receive(x)`` / ``receive_capture(cap, ...)`` ->
+    :class:`~dl_ofdm_amd.receive.ReceiveResult` (``prob`` is ``None``).
+
+    ``method``: ``"ALMMSE"``, ``"LS-Spline"`` or ``"LS-Linear"`` (the estimators that need neither the true channel nor a
+    long-term profile).  ``advance``: the FFT window starts ``advance`` samples inside the prefix (``ClassicalReceiver``'s
+    aligned window for a channel whose centre tap sits that far out), its phase ramp folded into the DFT matrix.
+    ``noise_var``: the FFT-domain noise variance per cell (``K * 10**(-snr/10)`` on the generator's frames) when it is known;
+    ``None``: estimated per frame from the empty carriers (``ofdm_tx.guardSc``).  ``interp``: any ``[S*K, P]`` interpolation
+    matrix in place of the method's own.  Resident buffers: ``x``, ``packed``, ``llr`` (``want_llr``), ``chest``, ``noise``."""
+
+    def __init__(self, FLAGS, batch: int, method: str = "ALMMSE", advance: int = 0, noise_var: Optional[float] = None,
+                 interp=None, want_llr: bool = False, mapping: str = "table", device="cuda"):
+        from .benchmark import ClassicalReceiver
+        from .benchmark_gpu import _cexpand, linear_weights, spline_weights
+        if method not in METHODS:
+            raise ValueError("method must be one of %s: the other estimators need the true channel or a long-term profile"
+                             % ", ".join(METHODS))
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.DccnError("ClassicalRxReceiver needs a CUDA (ROCm) device; there is no CPU fallback")
+        self.FLAGS, self.method, self.batch = FLAGS, method, int(batch)
+        self.host = h = ClassicalReceiver(FLAGS, mapping=mapping)
+        o = self.o = h.o
+        S, K, CP = int(h.S), int(h.K), int(h.CP)
+        self.S, self.K, self.CP, self.nbits = S, K, CP, int(h.nbits)
+        self.advance = int(advance)
+        if not (0 <= self.advance <= CP):
+            raise ValueError("advance must lie in [0, CP = %d]: the FFT window starts inside the prefix" % CP)
+        if noise_var is not None and not (np.isfinite(noise_var) and noise_var > 0):
+            raise ValueError("noise_var must be finite and > 0 (None: estimated from the empty carriers)")
+        self.noise_var = None if noise_var is None else float(noise_var)
+        self.pilot_sc = np.asarray(o.pilotSc, dtype=np.int32).reshape(-1)
+        self._syncs = {}
+        self.P, self.D, self.E = len(h.pil), len(h.dat), len(o.guardSc)
+        if not self.lib.dccn_classical_receive_supported(S, K, CP, self.P, self.D, self.E, self.nbits):
+            raise _lib.DccnError("dccn_classical_receive_supported refused S=%d K=%d CP=%d P=%d D=%d E=%d nbits=%d"
+                                 % (S, K, CP, self.P, self.D, self.E, self.nbits))
+        f32 = dict(dtype=torch.float32, device=self.device)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        self.pil = torch.as_tensor(h.pil.astype(np.int32), **i32)
+        self.dat = torch.as_tensor(h.dat.astype(np.int32), **i32)
+        self.empty = torch.as_tensor(np.asarray(o.guardSc).astype(np.int32), **i32)
+        self.table = torch.as_tensor(np.stack([h.table.real, h.table.imag], -1).astype(np.float32), **f32)
+        self.labels = torch.as_tensor(np.ascontiguousarray(h.labels, dtype=np.int32), **i32)
+        if interp is not None:
+            Wm = torch.as_tensor(np.asarray(interp, dtype=np.float64) if not isinstance(interp, torch.Tensor) else interp)
+            if tuple(Wm.shape) != (S * K, self.P):
+                raise ValueError("interp must be [S*K, P] = [%d, %d]" % (S * K, self.P))
+            self.w = Wm.to(self.device).T.contiguous().to(torch.float32)
+        elif method == "LS-Linear":
+            self.w = torch.as_tensor(np.ascontiguousarray(linear_weights(h.pil, S, K).T, dtype=np.float32), **f32)
+        else:
+            self.w = spline_weights(h.pil, S, K, self.device).T.contiguous().to(torch.float32)
+        F = np.exp(-2j * np.pi * np.outer(np.arange(K), np.arange(K)) / K)                          # F[t, k]
+        if self.advance > 0:
+            F = F * np.exp(2j * np.pi * np.arange(K) * self.advance / K)[None, :]
+        self.dft = torch.as_tensor(_cexpand(F).astype(np.float32), device=self.device)
+        B = self.batch
+        self.x = torch.zeros(B, S, K + CP, 2, **f32)
+        self.packed = torch.zeros(B, row_bytes(self.D, self.nbits), dtype=torch.uint8, device=self.device)
+        self.llr = torch.empty(B, self.D, self.nbits, **f32) if want_llr else None
+        self.chest = torch.empty(B, S * K, 2, **f32)
+        self.noise = torch.empty(B, **f32)
+        self.y_freq = None
+        pv = complex(h.pilot_value)
+        p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        self.args = ClassicalReceiveArgs(B, S, K, CP, self.P, self.D, self.E, self.nbits, int(self.table.shape[0]),
+                                         CP - self.advance, METHODS[method], 0.0 if self.noise_var is None else self.noise_var,
+                                         pv.real, pv.imag, p(self.dft), p(self.w), p(self.pil), p(self.dat), p(self.empty),
+                                         p(self.table), p(self.labels), p(self.x), p(self.packed), p(self.llr), p(self.chest),
+                                         None, p(self.noise))
+
+    # (the shape the shared front end writes for: whole symbols)
+    @property
+    def _kin(self) -> int:
+        return self.K + self.CP
+
+    @property
+    def _S(self) -> int:
+        return self.S
+
+    def want_y_freq(self) -> torch.Tensor:
+        """from now on the launch also writes the frequency-domain frames: the resident ``y_freq [batch, S*K, 2]``"""
+        if self.y_freq is None:
+            self.y_freq = torch.empty(self.batch, self.S * self.K, 2, dtype=torch.float32, device=self.device)
+            self.args.y_freq = self.y_freq.data_ptr()
+        return self.y_freq
+
+    def close_graph(self):
+        """(nothing captured: lets a :class:`~dl_ofdm_amd.session.Session` keep receivers next to its engines)"""
+
+    def _detect(self, offset=None, est=None, first=None, est0=None, est_int=None) -> ReceiveResult:
+        check(self.lib.dccn_classical_receive(C.byref(self.args), self._stream()), "dccn_classical_receive")
+        return ReceiveResult(self.packed, self.llr, None, self.D, self.nbits, offset, est, first, est0, est_int)
+
+    def receive(self, x=None, sync: int = 0, cfo: bool = False) -> ReceiveResult:
+        """Stage ``x`` (``None``: whatever ``self.x`` holds; whole symbols ``[batch, S, K + CP, 2]``) and run the classical
+        launch on the current stream.  ``sync = W > 0`` / ``cfo=True``: as :meth:`RxReceiver.receive` -- the alignment launch
+        takes the place of the copy and writes the aligned frames straight into ``self.x``."""
+        return self._detect(*self._stage_frames(x, sync, cfo))
+
+    def receive_capture(self, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False, acquire: int = 0,
+                        lo: int = 0, cfo_scope: str = "frame", cfo_span: int = 0, scale: Optional[float] = None) -> ReceiveResult:
+        """The classical launch on ``batch`` frames that still sit inside one contiguous capture: every argument as
+        :meth:`RxReceiver.receive_capture` takes it (acquisition, the cut at each frame's estimated start, per-frame or pooled
+        carrier offset, offsets beyond half a spacing, int16 captures), with the same refusals and launch counts."""
+        return self._detect(*self._stage_capture(cap, first, stride, sync, cfo, acquire, lo, cfo_scope, cfo_span, scale))

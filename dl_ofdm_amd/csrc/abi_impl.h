@@ -28,6 +28,7 @@
 #include "cconv_dx_narrow.h"
 #include "cconv1d_bwd.h"
 #include "classical.h"
+#include "classical_receive.h"
 
 
 namespace dccn {

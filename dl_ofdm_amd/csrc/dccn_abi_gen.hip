@@ -380,6 +380,49 @@ int dccn_classical_detect(const float* Y, const float* G, const int* dat, const 
     return DCCN_OK;
 }
 
+// ---- classical receive: the label-free detector of the receive path as one launch (classical_receive.h) -----------------
+static_assert(sizeof(dccn_classical_receive_args) == 160, "dccn.h states the size; dl_ofdm_amd/_lib.py mirrors the layout");
+int dccn_classical_receive_supported(int S, int K, int CP, int P, int D, int E, int nbits) {
+    if (S < 1 || S > kClsRxRows || K < 16 || K % 16 != 0 || K > 4096 || CP < 0 || CP > 4096 || (K + CP) % 2 != 0) return 0;
+    if (P < 1 || P > (1 << 16) || D < 1 || D > (1 << 24) || E < 1 || E > (1 << 24) || nbits < 1 || nbits > 4) return 0;
+    return clsrx_lds_floats(S, K, P) * sizeof(float) <= kClsRxMaxLds ? 1 : 0;
+}
+static bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+int dccn_classical_receive(const dccn_classical_receive_args* a, dccn_stream_t stream) {
+    if (!a) return DCCN_ERR_INVALID_ARG;
+    if (!dccn_classical_receive_supported(a->S, a->K, a->CP, a->P, a->D, a->E, a->nbits)) return DCCN_ERR_INVALID_ARG;
+    if (a->frames < 1 || a->frames > (1 << 24) || a->win < 0 || a->win > a->CP || a->m != (1 << a->nbits)) return DCCN_ERR_INVALID_ARG;
+    if (a->mode != CE_LS && a->mode != CE_ALMMSE) return DCCN_ERR_INVALID_ARG;
+    if (!isfinite(a->noise_var) || a->noise_var < 0.f) return DCCN_ERR_INVALID_ARG;
+    const float pd = a->pv_re * a->pv_re + a->pv_im * a->pv_im;
+    if (!isfinite(pd) || !(pd > 0.f)) return DCCN_ERR_INVALID_ARG;
+    if (!a->dft || !a->w || !a->pil || !a->dat || !a->empty || !a->table || !a->labels || !a->x || !a->packed)
+        return DCCN_ERR_INVALID_ARG;
+    if (!aligned16(a->x) || !aligned_to(a->dft, 4) || !aligned_to(a->w, 4) || !aligned_to(a->pil, 4) || !aligned_to(a->dat, 4) ||
+        !aligned_to(a->empty, 4) || !aligned_to(a->table, 8) || !aligned_to(a->labels, 4) || !aligned_to(a->llr, 4) ||
+        !aligned_to(a->chest, 8) || !aligned_to(a->y_freq, 8) || !aligned_to(a->noise, 4))
+        return DCCN_ERR_INVALID_ARG;
+    DCCN_NO_CHAINS();
+    ClsRxParams p;
+    p.frames = a->frames; p.S = a->S; p.K = a->K; p.CP = a->CP; p.P = a->P; p.D = a->D; p.E = a->E; p.win = a->win;
+    p.mode = a->mode; p.RB = (a->D * a->nbits + 7) / 8; p.fpb = kClsRxRows / a->S;
+    p.noise_var = a->noise_var; p.pv = make_float2(a->pv_re, a->pv_im);
+    p.dft = a->dft; p.w = a->w; p.pil = a->pil; p.dat = a->dat; p.empty = a->empty;
+    p.table = (const float2*)a->table; p.labels = a->labels; p.x = a->x;
+    p.packed = a->packed; p.llr = a->llr; p.chest = (float2*)a->chest; p.y_freq = (float2*)a->y_freq; p.noise = a->noise;
+    const size_t lds = clsrx_lds_floats(a->S, a->K, a->P) * sizeof(float);
+    const dim3 grid((unsigned)ceil_div(a->frames, p.fpb)), block(kClsRxThreads);
+    hipStream_t s = (hipStream_t)stream;
+    switch (a->nbits) {
+        case 1: hipLaunchKernelGGL(classical_receive_kernel<1>, grid, block, lds, s, p); break;
+        case 2: hipLaunchKernelGGL(classical_receive_kernel<2>, grid, block, lds, s, p); break;
+        case 3: hipLaunchKernelGGL(classical_receive_kernel<3>, grid, block, lds, s, p); break;
+        default: hipLaunchKernelGGL(classical_receive_kernel<4>, grid, block, lds, s, p); break;
+    }
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
 // ---- in-graph AWGN monitor branch (`iq_tx:0`, `iq_rx:0`, `noise_power:0`) -----------------------------------
 // clipped / xn: the clipped and the re-normalised signal; norm / clip: the two operators' own workspaces; partial: noise-power
 // partials, gx per frame; scratch_pw: complex_clip's power output is `tx_power:0`, served elsewhere

@@ -84,7 +84,88 @@ class ReceiveResult:
         return b.reshape(p.shape[0], -1)[:, :n].reshape(p.shape[0], self.D, self.nbits).to(torch.uint8)
 
 
-class RxReceiver:
+class _FrontEnd:
+    """What the receive engines share: the stages in front of the detector, each writing this engine's resident ``x`` --
+    the copy, the alignment launch (``sync=W``), and the capture cut with acquisition.  The engine provides ``lib``,
+    ``device``, ``batch``, ``x``, ``CP``, ``K``, ``pilot_sc``, ``_syncs`` and the two shape properties below."""
+
+    @property
+    def _kin(self) -> int:          # samples per symbol the detector takes (K + CP: whole symbols; K: a cp=False receiver)
+        return self.dims.kin
+
+    @property
+    def _S(self) -> int:
+        return self.dims.S
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _frame_sync(self, n_sc: int, W: int, cfo: bool = False):
+        """the alignment stage (``cfo``: with the carrier-frequency offset taken out) for full frames of ``n_sc`` samples per
+        symbol, writing this receiver's ``x``"""
+        from .sync import FrameSync
+        kin = self._kin
+        if self.CP is not None:
+            CP = self.CP
+        elif n_sc > kin:
+            CP = n_sc - kin
+        else:
+            raise _lib.DccnError("receive(sync=W) of a receiver that takes whole symbols needs %s(..., CP=...)"
+                                 % type(self).__name__)
+        K = n_sc - CP
+        if kin not in (n_sc, K):
+            raise _lib.DccnError("receive(sync=W): frames of %d samples per symbol (CP = %d) do not fit kin = %d" % (n_sc, CP, kin))
+        key = (K, CP, W, bool(cfo))
+        if key not in self._syncs:
+            self._syncs[key] = FrameSync(self._S, K, CP, W, self.batch, self.device, out_kin=kin, want_metric=False, cfo=cfo)
+        return self._syncs[key]
+
+    def _stage_frames(self, x, sync: int, cfo: bool):
+        """``receive``'s front end: ``x`` into ``self.x`` by the copy or the alignment launch -> ``(offset, cfo estimates)``"""
+        offset = est = None
+        if cfo and not sync:
+            raise _lib.DccnError("receive(cfo=True) needs sync = W > 0: the offset is read off the timing correlation")
+        if sync:
+            if not isinstance(x, torch.Tensor) or x.dim() != 4:
+                raise _lib.DccnError("receive(sync=W) takes a device tensor [batch, S, K + CP, 2]")
+            fs = self._frame_sync(int(x.shape[2]), int(sync), bool(cfo))
+            _, offset = fs.run(x, out=self.x)
+            est = fs.cfo
+        elif x is not None:
+            self.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(self.x.shape), non_blocking=True)
+        return offset, est
+
+    def _stage_capture(self, cap, first, stride, sync, cfo, acquire, lo, cfo_scope, cfo_span, scale):
+        """``receive_capture``'s front end: acquisition (``first=None``) and the cut, writing ``self.x`` ->
+        ``(offset, cfo estimates, first, acquired_cfo, acquired_cfo_int)`` as :class:`ReceiveResult` takes them"""
+        from .sync import CaptureSync, check_cfo_scope
+        name = type(self).__name__
+        check_cfo_scope(cfo, cfo_scope)
+        _checked_sc16(cap, scale, cfo_span, "receive_capture")
+        M = _checked_cfo_span(cfo_span, first, acquire, cfo)
+        W = int(sync)
+        if W <= 0:
+            raise _lib.DccnError("receive_capture needs sync = W > 0")
+        if self.CP is None:
+            raise _lib.DccnError("receive_capture needs %s(..., CP=...)" % name)
+        kin = self._kin
+        K = kin - self.CP if self.K is None else self.K
+        if K < 1 or kin not in (K + self.CP, K):
+            raise _lib.DccnError("receive_capture: K = %d, CP = %d do not fit kin = %d" % (K, self.CP, kin))
+        key = ("capture", W, bool(cfo)) if cfo_scope == "frame" else ("capture", W, True, cfo_scope)
+        key += (("span", M),) if M else ()
+        if key not in self._syncs:
+            self._syncs[key] = CaptureSync(self._S, K, self.CP, W, self.batch, self.device, out_kin=kin, want_metric=False,
+                                           cfo=bool(cfo), cfo_scope=cfo_scope, cfo_span=M)
+        cs = self._syncs[key]
+        first, est0, est_int = _acquired_first(self._syncs, first, acquire, cap, lo, self._S, K, self.CP, self.pilot_sc,
+                                               self.device, M, scale, name)
+        _, offset = cs.run(cap, first, stride, out=self.x, lo=lo,             # (lo matters to a device `first` only)
+                           acquired=(est_int, est0) if M else None, scale=scale)
+        return offset, cs.cfo, (first if isinstance(first, torch.Tensor) else None), est0, est_int
+
+
+class RxReceiver(_FrontEnd):
     """Fixed-shape receive engine of the basic receiver on one GPU: ``receive(x)`` -> :class:`ReceiveResult`.
 
     ``x``: host array or device tensor ``[batch, S, kin, 2]`` (as ``RxEngine.set_batch`` takes it).  ``x_norm`` (``input:0``)
@@ -139,30 +220,8 @@ class RxReceiver:
         for n in PARAM_NAMES:
             self.view(n).copy_(torch.as_tensor(np.asarray(params[n], dtype=np.float32)).reshape(self.layout[n][1]))
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def close_graph(self):
         """(nothing captured: lets a :class:`~dl_ofdm_amd.session.Session` keep receivers next to its engines)"""
-
-    def _frame_sync(self, n_sc: int, W: int, cfo: bool = False):
-        """the alignment stage (``cfo``: with the carrier-frequency offset taken out) for full frames of ``n_sc`` samples per
-        symbol, writing this receiver's ``x``"""
-        from .sync import FrameSync
-        kin = self.dims.kin
-        if self.CP is not None:
-            CP = self.CP
-        elif n_sc > kin:
-            CP = n_sc - kin
-        else:
-            raise _lib.DccnError("receive(sync=W) of a receiver that takes whole symbols needs RxReceiver(..., CP=...)")
-        K = n_sc - CP
-        if kin not in (n_sc, K):
-            raise _lib.DccnError("receive(sync=W): frames of %d samples per symbol (CP = %d) do not fit kin = %d" % (n_sc, CP, kin))
-        key = (K, CP, W, bool(cfo))
-        if key not in self._syncs:
-            self._syncs[key] = FrameSync(self.dims.S, K, CP, W, self.batch, self.device, out_kin=kin, want_metric=False, cfo=cfo)
-        return self._syncs[key]
 
     def receive(self, x=None, sync: int = 0, cfo: bool = False) -> ReceiveResult:
         """Stage ``x`` (``None``: whatever ``self.x`` holds) and run one receive step on the current stream.
@@ -175,17 +234,7 @@ class RxReceiver:
         ``cfo=True`` (needs ``sync > 0``): the same launch also estimates each frame's carrier-frequency offset from its prefix
         and writes the frames with it taken out (``FrameSync(..., cfo=True)``); ``result.cfo`` holds the estimates, in
         subcarrier spacings."""
-        offset = est = None
-        if cfo and not sync:
-            raise _lib.DccnError("receive(cfo=True) needs sync = W > 0: the offset is read off the timing correlation")
-        if sync:
-            if not isinstance(x, torch.Tensor) or x.dim() != 4:
-                raise _lib.DccnError("receive(sync=W) takes a device tensor [batch, S, K + CP, 2]")
-            fs = self._frame_sync(int(x.shape[2]), int(sync), bool(cfo))
-            _, offset = fs.run(x, out=self.x)
-            est = fs.cfo
-        elif x is not None:
-            self.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(self.x.shape), non_blocking=True)
+        offset, est = self._stage_frames(x, sync, cfo)
         check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
         return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, est)
 
@@ -219,32 +268,10 @@ class RxReceiver:
         (``scale=None``: ``2**-15``), converted inside the acquisition and cut launches -- no conversion launch, no float copy --
         and every result is bit for bit that of the float32 capture ``radio.sc16_to_float(cap, scale)``.  Every combination
         above at ``cfo_span=0``; ``cfo_span > 0`` with an int16 capture, and ``scale`` with a float32 one, raise."""
-        from .sync import CaptureSync, check_cfo_scope
-        check_cfo_scope(cfo, cfo_scope)
-        _checked_sc16(cap, scale, cfo_span, "receive_capture")
-        M = _checked_cfo_span(cfo_span, first, acquire, cfo)
-        W = int(sync)
-        if W <= 0:
-            raise _lib.DccnError("receive_capture needs sync = W > 0")
-        if self.CP is None:
-            raise _lib.DccnError("receive_capture needs RxReceiver(..., CP=...)")
-        kin = self.dims.kin
-        K = kin - self.CP if self.K is None else self.K
-        if K < 1 or kin not in (K + self.CP, K):
-            raise _lib.DccnError("receive_capture: K = %d, CP = %d do not fit kin = %d" % (K, self.CP, kin))
-        key = ("capture", W, bool(cfo)) if cfo_scope == "frame" else ("capture", W, True, cfo_scope)
-        key += (("span", M),) if M else ()
-        if key not in self._syncs:
-            self._syncs[key] = CaptureSync(self.dims.S, K, self.CP, W, self.batch, self.device, out_kin=kin, want_metric=False,
-                                           cfo=bool(cfo), cfo_scope=cfo_scope, cfo_span=M)
-        cs = self._syncs[key]
-        first, est0, est_int = _acquired_first(self._syncs, first, acquire, cap, lo, self.dims.S, K, self.CP, self.pilot_sc,
-                                               self.device, M, scale)
-        _, offset = cs.run(cap, first, stride, out=self.x, lo=lo,             # (lo matters to a device `first` only)
-                           acquired=(est_int, est0) if M else None, scale=scale)
+        offset, est, first, est0, est_int = self._stage_capture(cap, first, stride, sync, cfo, acquire, lo, cfo_scope,
+                                                                cfo_span, scale)
         check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
-        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, cs.cfo,
-                             first if isinstance(first, torch.Tensor) else None, est0, est_int)
+        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, est, first, est0, est_int)
 
 
 def _checked_sc16(cap, scale, cfo_span, what: str) -> None:
@@ -269,7 +296,7 @@ def _checked_cfo_span(cfo_span, first, acquire, cfo) -> int:
 
 
 def _acquired_first(stages: dict, first, acquire: int, cap, lo: int, S: int, K: int, CP: int, pilot_sc, device, cfo_span: int = 0,
-                    scale: Optional[float] = None):
+                    scale: Optional[float] = None, engine: str = "RxReceiver"):
     """``first`` as the cut takes it, and the acquisition's carrier-frequency offset (the fraction, and with ``cfo_span > 0``
     the integer): an integer or a device tensor passes through; ``None`` runs :class:`~dl_ofdm_amd.sync.CaptureAcquire` over
     ``acquire`` frames (kept in ``stages``)."""
@@ -282,7 +309,7 @@ def _acquired_first(stages: dict, first, acquire: int, cap, lo: int, S: int, K: 
     if J <= 0:
         raise _lib.DccnError("receive_capture(first=None) needs acquire = J > 0, the number of frames acquisition may use")
     if pilot_sc is None:
-        raise _lib.DccnError("receive_capture(first=None) needs the frame's pilot cells (RxReceiver(..., pilot_sc=...))")
+        raise _lib.DccnError("receive_capture(first=None) needs the frame's pilot cells (%s(..., pilot_sc=...))" % engine)
     key = ("acquire", J, cfo_span) if cfo_span else ("acquire", J)
     if key not in stages:
         stages[key] = CaptureAcquire(S, K, CP, pilot_sc, J, device, cfo_span=cfo_span)
@@ -398,3 +425,11 @@ def group_receive_capture(group, caps, firsts=None, strides=None, sync: int = 3,
     rest; one :class:`ReceiveResult` per chain, bit for bit what :func:`chain_receive_capture` returns for that chain alone."""
     return group.receive_capture(caps, firsts, strides, sync=sync, cfo=cfo, acquire=acquire, los=los, cfo_scope=cfo_scope,
                                  cfo_span=cfo_span)
+
+
+def __getattr__(name):
+    # ClassicalRxReceiver lives in classical_receive.py (which imports this module): exported here on first use
+    if name == "ClassicalRxReceiver":
+        from .classical_receive import ClassicalRxReceiver
+        return ClassicalRxReceiver
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

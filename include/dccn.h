@@ -295,6 +295,58 @@ int dccn_classical_detect(const float* Y, const float* G, const int* dat, const 
                           const int32_t* bits, int32_t* det, long long* errors, int n, int SK, int D, int m, int nbits,
                           int g_row, int g_mod, void* workspace, size_t workspace_bytes, dccn_stream_t stream);
 
+/* ---- classical receive: the label-free pilot-aided detector of the receive path as ONE launch -------------------------
+ * Frames as the front end writes them -> FFT window -> pilot LS -> interpolation -> (ALMMSE) -> one-tap equalisation -> hard
+ * bits packed as the receive path packs them (see "receive path"), plus max-log LLRs.  No labels, no true SNR, no workspace, no
+ * atomics; no frame depends on another, a frame's outputs do not depend on how many frames the call carries, and two runs give
+ * the same bits (every sum runs in the fixed order dl_ofdm_amd/csrc/classical_receive.h states).  Host mirror:
+ * dl_ofdm_amd/classical_receive.py.  Per frame f of x [frames, S, K+CP, 2] (fp32):
+ *   1. FFT window  xw[s, t] = x[f, s, win + t], t < K, 0 <= win <= CP;  Y[s] = xw[s] . dft with the caller's real-expanded
+ *      matrix dft [2K, 2K] (rows / columns 2t, 2t+1 = I, Q; the phase ramp of the window position folded in by the host)
+ *   2. LS at the pilots  gp[j] = Y[pil[j]] / pv                      (the expressions of dccn_classical_pilot_ls)
+ *   3. interpolation     Gls[c] = sum_j gp[j] w[j, c],  w [P, S*K] real (any such matrix)
+ *   4. noise             noise_var > 0: that value for every frame;  noise_var == 0: nv[f] = max(mean_{c in empty} |Y[c]|^2,
+ *      1e-20) over the caller's list empty [E] (the guard and DC cells of the reference grid).  The floor keeps the LLRs of a
+ *      noise-free frame finite while |G|^2 (d0 - d1) < 3e18.  c = nv / |pv|^2.  (With a prefix shorter than the channel the
+ *      empty cells also hold the inter-symbol interference: the estimate then reads high -- 1.8x at CP = 4 on ETU, 30 dB.)
+ *   5. estimate          mode 0 (LS): G = Gls;  mode 2 (ALMMSE): v[k] = mean_s Gls[s, k], e = sum_k |v[k]|^2 / S,
+ *      G[s, k] = v[k] e / (e + c)                                    (the expressions of dccn_classical_estimate)
+ *   6. decision at dat [D]: xh = Y / G, d_q = |xh - table[q]|^2 (the expressions of dccn_classical_detect: the hard decision
+ *      is bit for bit that entry's on this call's y_freq and chest), best = first minimum, hard = labels[best];
+ *      llr[b] = (|G|^2 / nv) (min_{labels[q,b]=0} d_q - min_{labels[q,b]=1} d_q), positive = bit 1, from the same d_q values
+ *      that pick best: llr > 0 => bit 1 and llr < 0 => bit 0 exactly
+ *   7. packed uint8 [frames, ceil(D*nbits/8)] in the receive path's row layout; rows need no alignment, padding bits are 0
+ * Outputs: packed (required); llr [frames, D, nbits], chest [frames, S*K, 2] (= G), y_freq [frames, S*K, 2] (= Y),
+ * noise [frames] (= nv): each nullable.  table [m, 2], labels [m, nbits] (0 / non-zero), m = 2^nbits.
+ * pil / dat / empty are device lists the host cannot look into: every entry is clamped to [0, S*K).
+ * sizeof(dccn_classical_receive_args) == 160.
+ * dccn_classical_receive_supported: 1 exactly where the call is accepted for the shape with 16-byte aligned buffers and valid
+ * scalars: 1 <= S <= 16, K a multiple of 16, K + CP even, P, D, E >= 1, nbits 1..4, and the block's LDS (16 (4K + 4) + 2 (16/S) P
+ * + 32 floats) within 48 KB -- the reference grids at N = 64 (CP 16 and 4) and N = 128 (CP 32) among them.
+ * Refused with DCCN_ERR_INVALID_ARG before anything is launched, nothing written: an unsupported shape; frames < 1; win outside
+ * [0, CP]; mode other than 0 / 2 (the other estimators need the true channel); noise_var negative or not finite; pv zero or not
+ * finite; m != 2^nbits; a NULL dft, w, pil, dat, empty, table, labels, x or packed; x off a 16-byte boundary, chest / y_freq /
+ * table off an 8-byte one, any other pointer off a 4-byte one.  Inside a chain group DCCN_ERR_UNSUPPORTED. */
+typedef struct dccn_classical_receive_args {
+    int frames, S, K, CP, P, D, E, nbits, m, win, mode;
+    float noise_var, pv_re, pv_im;
+    const float* dft;
+    const float* w;
+    const int* pil;
+    const int* dat;
+    const int* empty;
+    const float* table;
+    const int* labels;
+    const float* x;
+    unsigned char* packed;
+    float* llr;
+    float* chest;
+    float* y_freq;
+    float* noise;
+} dccn_classical_receive_args;
+int dccn_classical_receive_supported(int S, int K, int CP, int P, int D, int E, int nbits);
+int dccn_classical_receive(const dccn_classical_receive_args* args, dccn_stream_t stream);
+
 /* One row of the sweep table {c00,c01,c10,c11,ce_sum,count} (float64, device): row6 += the metrics record of the
  * last step, stream-ordered, no host round trip (dev/py/ofdmreceiver_np.py:80-85 accumulates the same on the host). */
 int dccn_metrics_table_add(const dccn_metrics* metrics, double* row6, dccn_stream_t stream);

@@ -52,6 +52,10 @@ and what the chain's BER is behind it, next to the BER with the start known.  ``
 U(-1/2, 1/2) and adds every capture under eps = m + f, m uniform in [-M, M]: how often ``receive_capture(..., acquire=J,
 cfo_span=M)`` finds the start and the whole offset, the BER behind it, and the BER of the narrow call on the same captures.
 
+``--classical METHOD`` (ALMMSE | LS-Spline | LS-Linear) adds rows of the label-free classical detector
+(``ClassicalRxReceiver.receive_capture``, pooled offset, ``acquire=16``) on the ``--acquire`` table's captures, with the noise
+variance estimated from the empty carriers and with the true one given.  It trains nothing.
+
 No threshold: the numbers are the result.
 
     python tools/syncber.py --nbits 2 --out syncber_out [--load CKPT --rx_load CKPT] [--seeds 3] [--train_sync 3 [--rx_sync]]
@@ -60,6 +64,7 @@ No threshold: the numbers are the result.
     python tools/syncber.py --nbits 2 --cfo 0.2 --cfo_scope capture --snrs 5,29 --frames 2000 --out syncber_out
     python tools/syncber.py --nbits 2 --acquire 4,8,16 --snrs 5,30 --frames 73 --captures 30 --out syncber_out
     python tools/syncber.py --nbits 2 --acquire 4,8,16 --cfo_span 7 --snrs 5,30 --frames 73 --captures 30 --out syncber_out
+    python tools/syncber.py --nbits 2 --classical ALMMSE --snrs 5,29 --frames 73 --captures 30 --out syncber_out
 """
 import argparse
 import copy
@@ -242,6 +247,82 @@ def capture_rows(a, tr, hf, snrs, log):
                                e["median"], e["p95"], e["max"], q["median"], q["max"]))
 
 
+def noisy_stream(fl, o, fading, n_tx, T, lead, snr, seed, EPS):
+    """one capture of the --acquire / --classical tables: ``n_tx`` frames through ``fading.run_stream``, unit mean power over the
+    frames, white noise at ``snr`` dB, one carrier offset eps ~ U(-EPS, EPS) -> (bits, the noisy stream before the offset, eps,
+    a random cut inside frame 0, the stream float32 [n, 2] under the offset)"""
+    from dl_ofdm_amd import util
+    from dl_ofdm_amd.radio import apply_cfo_stream
+    np.random.seed(seed)
+    bits = util.bit_source(fl.nbits, o.frame_size, n_tx)
+    iq, _, _ = o.ofdm_tx_frame_np(bits)
+    c, _ = fading.run_stream(iq, lead)
+    c = c.astype(np.complex128)
+    c /= np.sqrt(np.mean(np.abs(c[lead:lead + n_tx * T]) ** 2))
+    std = np.sqrt(0.5) * 10.0 ** (-snr / 20.0)
+    c = c + std * (np.random.randn(c.shape[0]) + 1j * np.random.randn(c.shape[0]))
+    eps = float(np.random.uniform(-EPS, EPS))
+    cut = int(np.random.randint(0, T))
+    full = apply_cfo_stream(np.stack([c.real, c.imag], axis=-1).astype(np.float32), eps, int(o.K))
+    return bits, c, eps, cut, full
+
+
+def classical_rows(a, hf, snrs, log):
+    """the --classical table: the label-free classical detector (``ClassicalRxReceiver``, method --classical) behind the SAME
+    front end on the SAME captures as the --acquire table (noisy_stream: same seeds; ``receive_capture(first=None, acquire=16,
+    cfo=True, cfo_scope="capture")``), one row per (channel, SNR): BER with the start known and behind acquisition, with the
+    noise variance estimated from the empty carriers and with the true one given.  No training."""
+    import torch
+    from dl_ofdm_amd import ofdm
+    from dl_ofdm_amd.benchmark import ClassicalReceiver
+    from dl_ofdm_amd.classical_receive import ClassicalRxReceiver
+    from dl_ofdm_amd.radio import rayleigh_chan_lte
+    n, W, lead, J = a.frames, a.W, 64, 16
+    lo = W
+    rows = []
+    for ch in CAPTURE_CHANNELS:
+        fl = copy.deepcopy(hf)
+        fl.channel = ch
+        o = ofdm.ofdm_tx(fl)
+        S, K, CP = int(fl.nsymbol), int(o.K), int(o.CP)
+        T = S * (K + CP)
+        n_tx = max(n, J) + 4
+        fading = rayleigh_chan_lte(fl, o.Fs)
+        adv = min(ClassicalReceiver.advance_of(fading), CP)
+        for i, snr in enumerate(snrs):
+            rx = {"estimated": ClassicalRxReceiver(fl, n, a.classical, advance=adv),
+                  "given": ClassicalRxReceiver(fl, n, a.classical, advance=adv, noise_var=K * 10.0 ** (-snr / 10.0))}
+            got = {k: {"known": [], "acquired": []} for k in rx}
+            nv = []
+            for c_i in range(a.captures):
+                bits, _, _, cut, full = noisy_stream(fl, o, fading, n_tx, T, lead, snr, 177 + 13 * i + 1009 * c_i, 0.2)
+                cap = torch.as_tensor(np.ascontiguousarray(full[lead + cut:]), device="cuda")
+                m0 = -(-(lo + cut) // T)
+                true = m0 * T - cut
+                lab = torch.as_tensor(bits[m0:m0 + n].astype(np.int32), device="cuda")
+                ber = lambda res: float((res.bits().to(torch.int32) != lab).to(torch.float32).mean())   # noqa: E731
+                for k, r in rx.items():
+                    got[k]["known"].append(ber(r.receive_capture(cap, true, sync=W, cfo=True, cfo_scope="capture")))
+                    got[k]["acquired"].append(ber(r.receive_capture(cap, sync=W, cfo=True, cfo_scope="capture", acquire=J, lo=lo)))
+                nv.append(float(rx["estimated"].noise.median()) / (K * 10.0 ** (-snr / 10.0)))
+            row = {"channel": ch, "snr_db": snr, "captures": a.captures, "frames": n, "method": a.classical, "advance": adv,
+                   "noise_estimate_over_true": float(np.median(nv)),
+                   "ber": {k: {q: float(np.mean(v)) for q, v in g.items()} for k, g in got.items()}}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    log["classical_rows"] = rows
+    with open(os.path.join(a.out, "syncber_classical_%dmod.json" % a.nbits), "w") as f:
+        json.dump(log, f, indent=1)
+        f.write("\n")
+    with open(os.path.join(a.out, "syncber_classical_%dmod.md" % a.nbits), "w") as f:
+        f.write("| channel | SNR [dB] | BER %s, start known | BER behind acquire = 16 | BER, true noise variance given, start known | "
+                "median noise estimate / true |\n|---|---|---|---|---|---|\n" % a.classical)
+        for r in rows:
+            f.write("| %s | %g | %.3g | %.3g | %.3g | %.3f |\n" % (r["channel"], r["snr_db"], r["ber"]["estimated"]["known"],
+                                                                r["ber"]["estimated"]["acquired"], r["ber"]["given"]["known"],
+                                                                r["noise_estimate_over_true"]))
+
+
 def acquire_rows(a, tr, hf, snrs, log):
     """the --acquire table: one row per (channel, SNR): the share of captures whose start acquisition finds (within W samples of
     the true frame start: the refinement behind it absorbs that) at each J, and the chain's BER behind it against the BER with the
@@ -276,17 +357,7 @@ def acquire_rows(a, tr, hf, snrs, log):
             wide = {J: {"right": 0, "int_right": 0, "ber_right": [], "ber_all": []} for J in Js}
             ber_narrow_on_wide = []
             for c_i in range(a.captures):
-                np.random.seed(177 + 13 * i + 1009 * c_i)
-                bits = util.bit_source(fl.nbits, o.frame_size, n_tx)
-                iq, _, _ = o.ofdm_tx_frame_np(bits)
-                c, _ = fading.run_stream(iq, lead)
-                c = c.astype(np.complex128)
-                c /= np.sqrt(np.mean(np.abs(c[lead:lead + n_tx * T]) ** 2))
-                std = np.sqrt(0.5) * 10.0 ** (-snr / 20.0)
-                c = c + std * (np.random.randn(c.shape[0]) + 1j * np.random.randn(c.shape[0]))
-                eps = float(np.random.uniform(-EPS, EPS))
-                cut = int(np.random.randint(0, T))
-                full = apply_cfo_stream(np.stack([c.real, c.imag], axis=-1).astype(np.float32), eps, K)
+                bits, c, eps, cut, full = noisy_stream(fl, o, fading, n_tx, T, lead, snr, 177 + 13 * i + 1009 * c_i, EPS)
                 cap = torch.as_tensor(np.ascontiguousarray(full[lead + cut:]), device=tr.device)
                 m0 = -(-(lo + cut) // T)                                              # the first transmitted frame that starts at or after lo
                 true = m0 * T - cut
@@ -388,6 +459,9 @@ def main():
     ap.add_argument("--cfo_span", "--cfo-span", type=int, default=0,
                     help="M, with --acquire: every capture also under eps = m + f, m uniform in [-M, M], f ~ U(-1/2, 1/2), received "
                          "with receive_capture(..., acquire=J, cfo_span=M), next to the narrow path on eps = f and on eps = m + f")
+    ap.add_argument("--classical", default=None, metavar="METHOD",
+                    help="ALMMSE | LS-Spline | LS-Linear: the classical detector (ClassicalRxReceiver) behind the same front end on the "
+                         "--acquire table's captures (receive_capture, pooled offset, acquire = 16); trains nothing; --frames per capture")
     ap.add_argument("--out", default="syncber_out")
     a = ap.parse_args()
     if a.cfo_span and not a.acquire:
@@ -408,6 +482,9 @@ def main():
            "train_channel": a.train_channel, "snrs": snrs}
     hf = H.Flags(nbits=nb, nfilter=64, channel=a.train_channel, max_epoch_num=a.eq_epochs if a.eq_epochs > 0 else 4000 * nb,
                  early_stop=200, token="syncber", save_dir=save, device_data=True, seed=10 + nb, test_frames=a.frames)
+    if a.classical:
+        classical_rows(a, hf, snrs, log)
+        return
     if a.load:
         from dl_ofdm_amd.equalizer import EqualizerTrainer
         from dl_ofdm_amd.session import Session, load_model_np
