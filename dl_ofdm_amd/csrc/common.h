@@ -40,6 +40,8 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline long long ceil_div_ll(long long a, long long b) { return (a + b - 1) / b; }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+template <unsigned N>
+static inline bool aligned_to(const void* p) { return (reinterpret_cast<uintptr_t>(p) & (N - 1u)) == 0; }     // (null passes)
 
 constexpr int kWave = 64;          // CDNA wavefront
 // compute units of the current device (MI355X: 256; fewer in the partitioned CPX/DPX modes): asked once PER DEVICE

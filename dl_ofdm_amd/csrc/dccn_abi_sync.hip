@@ -8,17 +8,28 @@
 using namespace dccn;
 
 namespace {
-// Everything a call decides, before its one launch: a refused call launches nothing.
-struct FrameSyncPlan {
-    FrameSyncArgs args;
-    unsigned blocks;
-    size_t lds;
-};
+constexpr unsigned kSyncThreads = kSyncWaves * kSyncLanes;
+
+// Every launch of this unit: the kernel's dynamic-LDS limit raised where `lds` needs it, the launch, its check.
+template <class Kernel, class Args>
+int launch(Kernel kernel, dim3 grid, unsigned threads, size_t lds, dccn_stream_t stream, const Args& args) {
+    DCCN_TRY(set_max_dynamic_smem((const void*)kernel, lds));
+    hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, (hipStream_t)stream, args);
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
 
 bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
     return a0 < b0 + nb && b0 < a0 + na;
 }
+
+// Everything a call decides, before its first launch: a refused call launches nothing.
+struct FrameSyncPlan {
+    FrameSyncArgs args;
+    unsigned blocks;
+    size_t lds;
+};
 
 int frame_sync_plan(const float* x, int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset,
                     float* metric, FrameSyncPlan* plan) {
@@ -35,68 +46,67 @@ int frame_sync_plan(const float* x, int frames, int S, int K, int CP, int W, int
     return DCCN_OK;
 }
 
+// One link of a capture cut.  Where frame 0 starts: `first`, or (first_dev given) what the device holds, which the kernel keeps
+// inside [lo, lo + T - 1].
+struct CaptureStart {
+    long long first;
+    const long long* first_dev;     // nullable
+    long long lo;
+};
 struct CaptureSyncPlan {
-    CaptureSyncArgs args;
+    CaptureSyncLink link;
+    SyncShape shape;
     unsigned blocks;
     size_t lds;
 };
-
 // sample_bytes: 8 for a float32 capture; 4 for an sc16 one, whose entries pass the capture's address as `cap` for the checks (the
-// capture's extent is n_samples * sample_bytes) and launch kernels that do not read args.cap
-int capture_sync_plan(const float* cap, long long n_samples, long long first, long long stride, int frames, int S, int K, int CP,
-                      int W, int out_kin, float* x_out, int32_t* offset, float* cfo, float* metric, CaptureSyncPlan* plan,
-                      size_t sample_bytes = 8) {
+// capture's extent is n_samples * sample_bytes) and launch kernels that do not read link.cap
+int capture_sync_plan(const float* cap, long long n_samples, size_t sample_bytes, CaptureStart at, long long stride, int frames,
+                      int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset, float* cfo, float* metric,
+                      CaptureSyncPlan* plan) {
     if (!capture_sync_shape_ok(S, K, CP, W) || frames <= 0 || !cap || !offset) return DCCN_ERR_INVALID_ARG;
     if (out_kin != K + CP && out_kin != K) return DCCN_ERR_INVALID_ARG;
     if (!aligned16(cap) || !aligned16(x_out) || !aligned16(metric)) return DCCN_ERR_INVALID_ARG;
     const long long T = (long long)S * (K + CP);
     if (x_out && out_kin == K && (S * K) % 2 != 0) return DCCN_ERR_INVALID_ARG;
-    // every window [b_f - W, b_f + T + W) inside the capture, frames not overlapping: first - W >= 0 and
-    // first + (frames - 1) stride + T + W <= n_samples, the product taken as a quotient so nothing overflows
-    if (n_samples <= 0 || n_samples > (1LL << 58) || stride < T || first < W || first > n_samples) return DCCN_ERR_INVALID_ARG;
-    const long long room = n_samples - first - T - W;
+    if (n_samples <= 0 || n_samples > (1LL << 58) || stride < T) return DCCN_ERR_INVALID_ARG;
+    // The start the windows are checked for.  A device start: the LAST one the kernel can clamp to, lo + T - 1 -- every earlier
+    // one has its windows inside the capture too, down to lo, whose first window starts at lo - W >= 0.
+    long long last = at.first;
+    if (at.first_dev) {
+        if (!aligned_to<8>(at.first_dev) || at.lo < W || at.lo > n_samples) return DCCN_ERR_INVALID_ARG;
+        last = at.lo + T - 1;
+    }
+    // every window [b_f - W, b_f + T + W) inside the capture, frames not overlapping: last - W >= 0 and
+    // last + (frames - 1) stride + T + W <= n_samples, the product taken as a quotient so nothing overflows
+    if (last < W || last > n_samples) return DCCN_ERR_INVALID_ARG;
+    const long long room = n_samples - last - T - W;
     if (room < 0 || (frames > 1 && stride > room / (frames - 1))) return DCCN_ERR_INVALID_ARG;
     if (x_out && ranges_overlap(cap, (size_t)n_samples * sample_bytes, x_out, (size_t)frames * S * out_kin * 8))
         return DCCN_ERR_INVALID_ARG;
-    plan->args = CaptureSyncArgs{cap, first, stride, x_out, offset, metric, cfo, frames, S, K, CP, W, out_kin == K ? 1 : 0};
+    plan->link = CaptureSyncLink{cap, at.first_dev ? 0 : at.first, stride, at.first_dev, at.first_dev ? at.lo : 0, x_out, offset,
+                                 metric, cfo};
+    plan->shape = SyncShape{frames, S, K, CP, W, out_kin == K ? 1 : 0};
     plan->blocks = (unsigned)ceil_div(frames, kSyncWaves);
     plan->lds = kSyncWaves * capture_sync_lds_per_frame((int)T, W);
     return DCCN_OK;
 }
 
-template <bool CFO>
-int capture_sync_launch(const CaptureSyncPlan& plan, dccn_stream_t stream) {
-    DCCN_TRY(set_max_dynamic_smem((const void*)capture_sync_kernel<CFO>, plan.lds));
-    hipLaunchKernelGGL(capture_sync_kernel<CFO>, dim3(plan.blocks), dim3(kSyncWaves * kSyncLanes), plan.lds, (hipStream_t)stream,
-                       plan.args);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+// The per-frame cut over any of its argument blocks: the frame's own cfo taken out where `cfo` is given.
+template <class Args>
+int capture_sync_launch(const CaptureSyncPlan& plan, int n_links, bool cfo, const Args& args, dccn_stream_t stream) {
+    const dim3 grid(plan.blocks, (unsigned)n_links);
+    return cfo ? launch(capture_sync_kernel<SyncFinish::kFrameCfo, Args>, grid, kSyncThreads, plan.lds, stream, args)
+               : launch(capture_sync_kernel<SyncFinish::kOffset, Args>, grid, kSyncThreads, plan.lds, stream, args);
 }
-// dccn_capture_sync_at: the plan of dccn_capture_sync for the LAST start the kernel can clamp to (lo + T - 1: every earlier one
-// has its windows inside the capture too, down to lo, whose first window starts at lo - W >= 0)
-int capture_sync_at_plan(const float* cap, long long n_samples, const long long* first_dev, long long lo, long long stride,
-                         int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset, float* cfo,
-                         float* metric, CaptureSyncPlan* plan, size_t sample_bytes = 8) {
-    if (!capture_sync_shape_ok(S, K, CP, W) || !first_dev || (reinterpret_cast<uintptr_t>(first_dev) & 7u) != 0) return DCCN_ERR_INVALID_ARG;
-    if (lo < W || n_samples <= 0 || lo > n_samples) return DCCN_ERR_INVALID_ARG;
-    const long long T = (long long)S * (K + CP);
-    return capture_sync_plan(cap, n_samples, lo + T - 1, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo, metric, plan,
-                             sample_bytes);
-}
-
-template <bool CFO>
-int capture_sync_at_launch(const CaptureSyncPlan& plan, const long long* first_dev, long long lo, dccn_stream_t stream) {
-    DCCN_TRY(set_max_dynamic_smem((const void*)capture_sync_at_kernel<CFO>, plan.lds));
-    hipLaunchKernelGGL(capture_sync_at_kernel<CFO>, dim3(plan.blocks), dim3(kSyncWaves * kSyncLanes), plan.lds, (hipStream_t)stream,
-                       CaptureSyncAtArgs{plan.args, first_dev, lo});
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+// the float32 solo cut, from a host start or a device one
+int capture_sync_solo_launch(const CaptureSyncPlan& plan, dccn_stream_t stream) {
+    return capture_sync_launch(plan, 1, plan.link.cfo != nullptr, CaptureSyncSoloArgs{plan.link, CapOfArgs{}, plan.shape}, stream);
 }
 
 // the wide cuts' two device inputs (acquisition's m^ and eps^): given, on 4-byte boundaries
 bool wide_inputs_ok(const int32_t* cfo_int_dev, const float* cfo_frac_dev) {
-    return cfo_int_dev && cfo_frac_dev && (reinterpret_cast<uintptr_t>(cfo_int_dev) & 3u) == 0 &&
-           (reinterpret_cast<uintptr_t>(cfo_frac_dev) & 3u) == 0;
+    return cfo_int_dev && cfo_frac_dev && aligned_to<4>(cfo_int_dev) && aligned_to<4>(cfo_frac_dev);
 }
 
 // Everything dccn_capture_acquire decides, before its first launch.
@@ -111,9 +121,8 @@ int capture_acquire_plan(const float* cap, long long n_samples, long long lo, in
                          void* workspace, size_t workspace_bytes, CaptureAcquirePlan* plan) {
     if (!capture_acquire_shape_ok(S, K, CP, n_pilot, J)) return DCCN_ERR_INVALID_ARG;
     if (!cap || !pilot_sc || !first_out || !cfo_out || !workspace) return DCCN_ERR_INVALID_ARG;
-    if (!aligned16(cap) || !aligned16(workspace) || (reinterpret_cast<uintptr_t>(first_out) & 7u) != 0) return DCCN_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(pilot_sc) & 3u) != 0 || (reinterpret_cast<uintptr_t>(cfo_out) & 3u) != 0 ||
-        (reinterpret_cast<uintptr_t>(sym_metric) & 3u) != 0 || (reinterpret_cast<uintptr_t>(phase_metric) & 3u) != 0)
+    if (!aligned16(cap) || !aligned16(workspace) || !aligned_to<8>(first_out)) return DCCN_ERR_INVALID_ARG;
+    if (!aligned_to<4>(pilot_sc) || !aligned_to<4>(cfo_out) || !aligned_to<4>(sym_metric) || !aligned_to<4>(phase_metric))
         return DCCN_ERR_INVALID_ARG;
     // every read of both stages lies in [lo, lo + (J + 1) T); the documented bound leaves a frame to spare
     const long long T = (long long)S * (K + CP);
@@ -126,6 +135,16 @@ int capture_acquire_plan(const float* cap, long long n_samples, long long lo, in
     plan->sum_blocks = (unsigned)ceil_div(K + 2 * CP - 1, kAcqSumThreads);
     plan->lds = capture_acquire_lds(S, K, CP, n_pilot);
     return DCCN_OK;
+}
+// Acquisition's three launches (symbol sums, phase, decision) for n_links links: each kernel with its own argument block.
+template <class Sums, class SumsArgs, class Phase, class PhaseArgs, class Decide, class DecideArgs>
+int acquire_launch(unsigned sum_blocks, int S, int J, int n_links, size_t phase_lds, unsigned decide_threads, dccn_stream_t stream,
+                   Sums sums, const SumsArgs& sums_args, Phase phase, const PhaseArgs& phase_args, Decide decide,
+                   const DecideArgs& decide_args) {
+    const unsigned G = (unsigned)n_links;
+    DCCN_TRY(launch(sums, dim3(sum_blocks, G), kAcqSumThreads, 0, stream, sums_args));
+    DCCN_TRY(launch(phase, dim3((unsigned)S, (unsigned)J, G), kAcqThreads, phase_lds, stream, phase_args));
+    return launch(decide, dim3(G), decide_threads, 0, stream, decide_args);
 }
 
 // ---- the grouped entries: every link through the solo plan above, then what only a group can get wrong --------------------------
@@ -155,87 +174,66 @@ bool mixed_nullability(const Link* links, int n_links, T* Link::*field) {
         if ((links[i].*field == nullptr) != (links[0].*field == nullptr)) return true;
     return false;
 }
-bool group_count_ok(int n_links, const void* links) { return n_links >= 1 && n_links <= kMaxChains && links != nullptr; }
+// The plan of a group, stated once: the count, then per_link(i, link, ranges) for every link in order -- the link's solo plan, its
+// entry of the launch's table, its byte ranges; the shape and the launch geometry are the call's, so every link's plan holds the
+// same ones -- then the optional outputs (all links or none) and the collisions.
+template <class Link, class PerLink, class... Optional>
+int group_plan(int n_links, const Link* links, PerLink per_link, Optional... optional) {
+    if (n_links < 1 || n_links > kMaxChains || !links) return DCCN_ERR_INVALID_ARG;
+    LinkRanges r[kMaxChains];
+    for (int i = 0; i < n_links; ++i) DCCN_TRY(per_link(i, links[i], &r[i]));
+    if ((mixed_nullability(links, n_links, optional) || ...)) return DCCN_ERR_INVALID_ARG;
+    return links_collide(r, n_links) ? DCCN_ERR_INVALID_ARG : DCCN_OK;
+}
 
 struct FrameSyncGroupPlan {
     FrameSyncGroupArgs args;
     unsigned blocks;
     size_t lds;
-    bool cfo;
 };
 int frame_sync_group_plan(int n_links, const dccn_frame_link* links, int frames, int S, int K, int CP, int W, int out_kin,
                           FrameSyncGroupPlan* plan) {
-    if (!group_count_ok(n_links, links)) return DCCN_ERR_INVALID_ARG;
-    LinkRanges r[kMaxChains];
     plan->args = FrameSyncGroupArgs{};
-    for (int i = 0; i < n_links; ++i) {
-        const dccn_frame_link& l = links[i];
+    return group_plan(n_links, links, [&](int i, const dccn_frame_link& l, LinkRanges* r) -> int {
         FrameSyncPlan one;
         DCCN_TRY(frame_sync_plan(l.x, frames, S, K, CP, W, out_kin, l.x_out, l.offset, l.metric, &one));
-        if ((reinterpret_cast<uintptr_t>(l.cfo) & 3u) != 0) return DCCN_ERR_INVALID_ARG;
-        plan->args.link[i] = FrameSyncLink{one.args.x, one.args.x_out, one.args.offset, one.args.metric, l.cfo};
-        if (i == 0) {
-            plan->args.frames = frames; plan->args.S = S; plan->args.K = K; plan->args.CP = CP; plan->args.W = W;
-            plan->args.crop = one.args.crop;
-            plan->blocks = one.blocks;
-            plan->lds = one.lds;
-        }
-        r[i].out(l.x_out, (size_t)frames * S * out_kin * 8);
-        r[i].out(l.offset, (size_t)frames * 4);
-        r[i].out(l.cfo, (size_t)frames * 4);
-        r[i].out(l.metric, (size_t)frames * (2 * W + 1) * 4);
-        r[i].in(l.x, (size_t)frames * S * (K + CP) * 8);
-    }
-    if (mixed_nullability(links, n_links, &dccn_frame_link::x_out) || mixed_nullability(links, n_links, &dccn_frame_link::cfo) ||
-        mixed_nullability(links, n_links, &dccn_frame_link::metric))
-        return DCCN_ERR_INVALID_ARG;
-    if (links_collide(r, n_links)) return DCCN_ERR_INVALID_ARG;
-    plan->cfo = links[0].cfo != nullptr;
-    return DCCN_OK;
+        if (!aligned_to<4>(l.cfo)) return DCCN_ERR_INVALID_ARG;
+        const FrameSyncArgs& a = one.args;
+        plan->args.link[i] = FrameSyncLink{a.x, a.x_out, a.offset, a.metric, l.cfo};
+        plan->args.frames = a.frames; plan->args.S = a.S; plan->args.K = a.K; plan->args.CP = a.CP; plan->args.W = a.W;
+        plan->args.crop = a.crop;
+        plan->blocks = one.blocks;
+        plan->lds = one.lds;
+        r->out(l.x_out, (size_t)frames * S * out_kin * 8);
+        r->out(l.offset, (size_t)frames * 4);
+        r->out(l.cfo, (size_t)frames * 4);
+        r->out(l.metric, (size_t)frames * (2 * W + 1) * 4);
+        r->in(l.x, (size_t)frames * S * (K + CP) * 8);
+        return DCCN_OK;
+    }, &dccn_frame_link::x_out, &dccn_frame_link::cfo, &dccn_frame_link::metric);
 }
 
 struct CaptureSyncGroupPlan {
     CaptureSyncGroupArgs args;
-    unsigned blocks;
-    size_t lds;
-    bool cfo;
+    CaptureSyncPlan one;        // the shape and the geometry: any link's
 };
 int capture_sync_group_plan(int n_links, const dccn_capture_link* links, int frames, int S, int K, int CP, int W, int out_kin,
                             CaptureSyncGroupPlan* plan) {
-    if (!group_count_ok(n_links, links)) return DCCN_ERR_INVALID_ARG;
-    LinkRanges r[kMaxChains];
     plan->args = CaptureSyncGroupArgs{};
-    for (int i = 0; i < n_links; ++i) {
-        const dccn_capture_link& l = links[i];
-        CaptureSyncPlan one;
-        if (l.first_dev)
-            DCCN_TRY(capture_sync_at_plan(l.cap, l.n_samples, l.first_dev, l.lo, l.stride, frames, S, K, CP, W, out_kin, l.x_out,
-                                          l.offset, l.cfo, l.metric, &one));
-        else
-            DCCN_TRY(capture_sync_plan(l.cap, l.n_samples, l.first, l.stride, frames, S, K, CP, W, out_kin, l.x_out, l.offset, l.cfo,
-                                       l.metric, &one));
-        if ((reinterpret_cast<uintptr_t>(l.cfo) & 3u) != 0) return DCCN_ERR_INVALID_ARG;
-        plan->args.link[i] = CaptureSyncLink{one.args.cap, l.first_dev ? 0 : l.first, one.args.stride, l.first_dev,
-                                             l.first_dev ? l.lo : 0, one.args.x_out, one.args.offset, one.args.metric, one.args.cfo};
-        if (i == 0) {
-            plan->args.frames = frames; plan->args.S = S; plan->args.K = K; plan->args.CP = CP; plan->args.W = W;
-            plan->args.crop = one.args.crop;
-            plan->blocks = one.blocks;
-            plan->lds = one.lds;
-        }
-        r[i].out(l.x_out, (size_t)frames * S * out_kin * 8);
-        r[i].out(l.offset, (size_t)frames * 4);
-        r[i].out(l.cfo, (size_t)frames * 4);
-        r[i].out(l.metric, (size_t)frames * (2 * W + 1) * 4);
-        r[i].in(l.cap, (size_t)l.n_samples * 8);
-        r[i].in(l.first_dev, 8);
-    }
-    if (mixed_nullability(links, n_links, &dccn_capture_link::x_out) || mixed_nullability(links, n_links, &dccn_capture_link::cfo) ||
-        mixed_nullability(links, n_links, &dccn_capture_link::metric))
-        return DCCN_ERR_INVALID_ARG;
-    if (links_collide(r, n_links)) return DCCN_ERR_INVALID_ARG;
-    plan->cfo = links[0].cfo != nullptr;
-    return DCCN_OK;
+    return group_plan(n_links, links, [&](int i, const dccn_capture_link& l, LinkRanges* r) -> int {
+        DCCN_TRY(capture_sync_plan(l.cap, l.n_samples, 8, CaptureStart{l.first, l.first_dev, l.lo}, l.stride, frames, S, K, CP, W,
+                                   out_kin, l.x_out, l.offset, l.cfo, l.metric, &plan->one));
+        if (!aligned_to<4>(l.cfo)) return DCCN_ERR_INVALID_ARG;
+        plan->args.link[i] = plan->one.link;
+        plan->args.shape = plan->one.shape;
+        r->out(l.x_out, (size_t)frames * S * out_kin * 8);
+        r->out(l.offset, (size_t)frames * 4);
+        r->out(l.cfo, (size_t)frames * 4);
+        r->out(l.metric, (size_t)frames * (2 * W + 1) * 4);
+        r->in(l.cap, (size_t)l.n_samples * 8);
+        r->in(l.first_dev, 8);
+        return DCCN_OK;
+    }, &dccn_capture_link::x_out, &dccn_capture_link::cfo, &dccn_capture_link::metric);
 }
 
 // dccn_capture_sync_pooled(_grouped): every link through the per-frame entry's own plan (so the windows, the alignment and the
@@ -249,56 +247,40 @@ struct PooledGroupPlan {
 };
 int pooled_group_plan(int n_links, const dccn_pooled_link* links, int frames, int S, int K, int CP, int W, int out_kin,
                       PooledGroupPlan* plan, size_t sample_bytes = 8) {
-    if (!group_count_ok(n_links, links)) return DCCN_ERR_INVALID_ARG;
-    LinkRanges r[kMaxChains];
     plan->args = PooledGroupArgs{};
-    for (int i = 0; i < n_links; ++i) {
-        const dccn_pooled_link& l = links[i];
+    DCCN_TRY(group_plan(n_links, links, [&](int i, const dccn_pooled_link& l, LinkRanges* r) -> int {
         CaptureSyncPlan one;
-        if (l.first_dev)
-            DCCN_TRY(capture_sync_at_plan(l.cap, l.n_samples, l.first_dev, l.lo, l.stride, frames, S, K, CP, W, out_kin, l.x_out,
-                                          l.offset, l.cfo, l.metric, &one, sample_bytes));
-        else
-            DCCN_TRY(capture_sync_plan(l.cap, l.n_samples, l.first, l.stride, frames, S, K, CP, W, out_kin, l.x_out, l.offset, l.cfo,
-                                       l.metric, &one, sample_bytes));
-        if (!l.x_out || !l.cfo || (reinterpret_cast<uintptr_t>(l.cfo) & 3u) != 0) return DCCN_ERR_INVALID_ARG;
+        DCCN_TRY(capture_sync_plan(l.cap, l.n_samples, sample_bytes, CaptureStart{l.first, l.first_dev, l.lo}, l.stride, frames, S, K,
+                                   CP, W, out_kin, l.x_out, l.offset, l.cfo, l.metric, &one));
+        if (!l.x_out || !l.cfo || !aligned_to<4>(l.cfo)) return DCCN_ERR_INVALID_ARG;
         if (!l.workspace || !aligned16(l.workspace)) return DCCN_ERR_INVALID_ARG;
-        plan->args.link[i] = PooledLink{CaptureSyncLink{one.args.cap, l.first_dev ? 0 : l.first, one.args.stride, l.first_dev,
-                                                        l.first_dev ? l.lo : 0, one.args.x_out, one.args.offset, one.args.metric,
-                                                        one.args.cfo},
-                                        static_cast<float2*>(l.workspace)};
-        if (i == 0) {
-            plan->args.frames = frames; plan->args.S = S; plan->args.K = K; plan->args.CP = CP; plan->args.W = W;
-            plan->args.crop = one.args.crop;
-            plan->blocks = one.blocks;
-            plan->lds_estimate = one.lds;
-            plan->lds_cut = kSyncWaves * capture_cut_lds_per_frame(S * (K + CP));
-        }
-        r[i].out(l.x_out, (size_t)frames * S * out_kin * 8);
-        r[i].out(l.offset, (size_t)frames * 4);
-        r[i].out(l.cfo, 4);
-        r[i].out(l.metric, (size_t)frames * (2 * W + 1) * 4);
-        r[i].out(l.workspace, pooled_workspace_bytes(frames));
-        r[i].in(l.cap, (size_t)l.n_samples * sample_bytes);
-        r[i].in(l.first_dev, 8);
-    }
-    if (mixed_nullability(links, n_links, &dccn_pooled_link::metric)) return DCCN_ERR_INVALID_ARG;
-    if (links_collide(r, n_links)) return DCCN_ERR_INVALID_ARG;
+        plan->args.link[i] = PooledLink{one.link, static_cast<float2*>(l.workspace)};
+        plan->args.shape = one.shape;
+        plan->blocks = one.blocks;
+        plan->lds_estimate = one.lds;
+        plan->lds_cut = kSyncWaves * capture_cut_lds_per_frame(S * (K + CP));
+        r->out(l.x_out, (size_t)frames * S * out_kin * 8);
+        r->out(l.offset, (size_t)frames * 4);
+        r->out(l.cfo, 4);
+        r->out(l.metric, (size_t)frames * (2 * W + 1) * 4);
+        r->out(l.workspace, pooled_workspace_bytes(frames));
+        r->in(l.cap, (size_t)l.n_samples * sample_bytes);
+        r->in(l.first_dev, 8);
+        return DCCN_OK;
+    }, &dccn_pooled_link::metric));
     for (int i = 0; i < n_links; ++i)
         if (links[i].workspace_bytes < pooled_workspace_bytes(frames)) return DCCN_ERR_WORKSPACE;
     return DCCN_OK;
 }
-int pooled_group_launch(const PooledGroupPlan& plan, int n_links, dccn_stream_t stream) {
-    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_estimate_kernel, plan.lds_estimate));
-    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_cut_kernel<PooledGroupArgs>, plan.lds_cut));
-    const dim3 grid(plan.blocks, (unsigned)n_links), block(kSyncWaves * kSyncLanes);
-    hipLaunchKernelGGL(capture_pool_estimate_kernel, grid, block, plan.lds_estimate, (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(capture_pool_reduce_kernel, dim3((unsigned)n_links), dim3(kSyncLanes), 0, (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(capture_pool_cut_kernel<PooledGroupArgs>, grid, block, plan.lds_cut, (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+// The pooled call's three launches: the estimate and the cut with their argument blocks, the sum between them over the plan's own
+// table (it reads no capture).
+template <class Estimate, class EstimateArgs, class Cut, class CutArgs>
+int pooled_launch(const PooledGroupPlan& plan, int n_links, dccn_stream_t stream, Estimate estimate, const EstimateArgs& estimate_args,
+                  Cut cut, const CutArgs& cut_args) {
+    const dim3 grid(plan.blocks, (unsigned)n_links);
+    DCCN_TRY(launch(estimate, grid, kSyncThreads, plan.lds_estimate, stream, estimate_args));
+    DCCN_TRY(launch(capture_pool_reduce_kernel, dim3((unsigned)n_links), kSyncLanes, 0, stream, plan.args));
+    return launch(cut, grid, kSyncThreads, plan.lds_cut, stream, cut_args);
 }
 
 struct CaptureAcquireGroupPlan {
@@ -308,52 +290,26 @@ struct CaptureAcquireGroupPlan {
 };
 int capture_acquire_group_plan(int n_links, const dccn_acquire_link* links, int J, int S, int K, int CP, int n_pilot,
                                CaptureAcquireGroupPlan* plan) {
-    if (!group_count_ok(n_links, links)) return DCCN_ERR_INVALID_ARG;
-    LinkRanges r[kMaxChains];
     plan->args = AcqGroupArgs{};
-    for (int i = 0; i < n_links; ++i) {
-        const dccn_acquire_link& l = links[i];
+    return group_plan(n_links, links, [&](int i, const dccn_acquire_link& l, LinkRanges* r) -> int {
         CaptureAcquirePlan one;
         DCCN_TRY(capture_acquire_plan(l.cap, l.n_samples, l.lo, J, S, K, CP, l.pilot_sc, n_pilot, l.first_out, l.cfo_out, l.sym_metric,
                                       l.phase_metric, l.workspace, l.workspace_bytes, &one));
         const AcqArgs& a = one.args;
         plan->args.link[i] = AcqLink{a.cap, a.lo, a.pilot_sc, a.pe, a.partial, a.rhat, a.first_out, a.cfo_out, a.sym_metric,
                                      a.phase_metric};
-        if (i == 0) {
-            plan->args.S = S; plan->args.K = K; plan->args.CP = CP; plan->args.J = J; plan->args.n_pilot = n_pilot;
-            plan->sum_blocks = one.sum_blocks;
-            plan->lds = one.lds;
-        }
-        r[i].out(l.first_out, 8);
-        r[i].out(l.cfo_out, 4);
-        r[i].out(l.sym_metric, (size_t)(K + CP) * 4);
-        r[i].out(l.phase_metric, (size_t)S * 4);
-        r[i].out(l.workspace, capture_acquire_layout(S, K, CP, J).total);
-        r[i].in(l.cap, (size_t)l.n_samples * 8);
-        r[i].in(l.pilot_sc, (size_t)n_pilot * 4);
-    }
-    if (mixed_nullability(links, n_links, &dccn_acquire_link::sym_metric) ||
-        mixed_nullability(links, n_links, &dccn_acquire_link::phase_metric))
-        return DCCN_ERR_INVALID_ARG;
-    if (links_collide(r, n_links)) return DCCN_ERR_INVALID_ARG;
-    return DCCN_OK;
-}
-
-template <bool CFO>
-int frame_sync_group_launch(const FrameSyncGroupPlan& plan, int n_links, dccn_stream_t stream) {
-    DCCN_TRY(set_max_dynamic_smem((const void*)frame_sync_grouped_kernel<CFO>, plan.lds));
-    hipLaunchKernelGGL(frame_sync_grouped_kernel<CFO>, dim3(plan.blocks, (unsigned)n_links), dim3(kSyncWaves * kSyncLanes), plan.lds,
-                       (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
-}
-template <bool CFO>
-int capture_sync_group_launch(const CaptureSyncGroupPlan& plan, int n_links, dccn_stream_t stream) {
-    DCCN_TRY(set_max_dynamic_smem((const void*)capture_sync_grouped_kernel<CFO>, plan.lds));
-    hipLaunchKernelGGL(capture_sync_grouped_kernel<CFO>, dim3(plan.blocks, (unsigned)n_links), dim3(kSyncWaves * kSyncLanes),
-                       plan.lds, (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+        plan->args.S = S; plan->args.K = K; plan->args.CP = CP; plan->args.J = J; plan->args.n_pilot = n_pilot;
+        plan->sum_blocks = one.sum_blocks;
+        plan->lds = one.lds;
+        r->out(l.first_out, 8);
+        r->out(l.cfo_out, 4);
+        r->out(l.sym_metric, (size_t)(K + CP) * 4);
+        r->out(l.phase_metric, (size_t)S * 4);
+        r->out(l.workspace, capture_acquire_layout(S, K, CP, J).total);
+        r->in(l.cap, (size_t)l.n_samples * 8);
+        r->in(l.pilot_sc, (size_t)n_pilot * 4);
+        return DCCN_OK;
+    }, &dccn_acquire_link::sym_metric, &dccn_acquire_link::phase_metric);
 }
 
 // ---- 16-bit integer I/Q captures: the float32 plans with the capture's extent taken as 4 bytes per sample -----------------------
@@ -369,11 +325,7 @@ int dccn_frame_sync(const float* x, int frames, int S, int K, int CP, int W, int
                     float* metric, dccn_stream_t stream) {
     FrameSyncPlan plan;
     DCCN_TRY(frame_sync_plan(x, frames, S, K, CP, W, out_kin, x_out, offset, metric, &plan));
-    DCCN_TRY(set_max_dynamic_smem((const void*)frame_sync_kernel, plan.lds));
-    hipLaunchKernelGGL(frame_sync_kernel, dim3(plan.blocks), dim3(kSyncWaves * kSyncLanes), plan.lds, (hipStream_t)stream,
-                       plan.args);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return launch(frame_sync_kernel, dim3(plan.blocks), kSyncThreads, plan.lds, stream, plan.args);
 }
 
 int dccn_frame_sync_cfo(const float* x, int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset,
@@ -382,11 +334,7 @@ int dccn_frame_sync_cfo(const float* x, int frames, int S, int K, int CP, int W,
     DCCN_TRY(frame_sync_plan(x, frames, S, K, CP, W, out_kin, x_out, offset, metric, &plan));
     if (!cfo) return DCCN_ERR_INVALID_ARG;
     DCCN_NO_CHAINS();                         // (the launch carries no chain table: inside a group it would serve chain 0 only)
-    DCCN_TRY(set_max_dynamic_smem((const void*)frame_sync_cfo_kernel, plan.lds));
-    hipLaunchKernelGGL(frame_sync_cfo_kernel, dim3(plan.blocks), dim3(kSyncWaves * kSyncLanes), plan.lds, (hipStream_t)stream,
-                       FrameSyncCfoArgs{plan.args, cfo});
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return launch(frame_sync_cfo_kernel, dim3(plan.blocks), kSyncThreads, plan.lds, stream, FrameSyncCfoArgs{plan.args, cfo});
 }
 
 int dccn_capture_sync_supported(int S, int K, int CP, int W) { return capture_sync_shape_ok(S, K, CP, W) ? 1 : 0; }
@@ -394,19 +342,21 @@ int dccn_capture_sync_supported(int S, int K, int CP, int W) { return capture_sy
 int dccn_capture_sync(const float* cap, long long n_samples, long long first, long long stride, int frames, int S, int K, int CP,
                       int W, int out_kin, float* x_out, int32_t* offset, float* cfo, float* metric, dccn_stream_t stream) {
     CaptureSyncPlan plan;
-    DCCN_TRY(capture_sync_plan(cap, n_samples, first, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo, metric, &plan));
+    DCCN_TRY(capture_sync_plan(cap, n_samples, 8, CaptureStart{first, nullptr, 0}, stride, frames, S, K, CP, W, out_kin, x_out, offset,
+                               cfo, metric, &plan));
     DCCN_NO_CHAINS();
-    return cfo ? capture_sync_launch<true>(plan, stream) : capture_sync_launch<false>(plan, stream);
+    return capture_sync_solo_launch(plan, stream);
 }
 
 int dccn_capture_sync_at(const float* cap, long long n_samples, const long long* first_dev, long long lo, long long stride,
                          int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset, float* cfo,
                          float* metric, dccn_stream_t stream) {
+    if (!first_dev) return DCCN_ERR_INVALID_ARG;
     CaptureSyncPlan plan;
-    DCCN_TRY(capture_sync_at_plan(cap, n_samples, first_dev, lo, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo, metric,
-                                  &plan));
+    DCCN_TRY(capture_sync_plan(cap, n_samples, 8, CaptureStart{0, first_dev, lo}, stride, frames, S, K, CP, W, out_kin, x_out, offset,
+                               cfo, metric, &plan));
     DCCN_NO_CHAINS();
-    return cfo ? capture_sync_at_launch<true>(plan, first_dev, lo, stream) : capture_sync_at_launch<false>(plan, first_dev, lo, stream);
+    return capture_sync_solo_launch(plan, stream);
 }
 
 int dccn_capture_acquire_supported(int S, int K, int CP, int n_pilot, int J) {
@@ -424,13 +374,8 @@ int dccn_capture_acquire(const float* cap, long long n_samples, long long lo, in
     DCCN_TRY(capture_acquire_plan(cap, n_samples, lo, J, S, K, CP, pilot_sc, n_pilot, first_out, cfo_out, sym_metric, phase_metric,
                                   workspace, workspace_bytes, &plan));
     DCCN_NO_CHAINS();
-    hipLaunchKernelGGL(acq_symbol_sums_kernel, dim3(plan.sum_blocks), dim3(kAcqSumThreads), 0, (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(acq_phase_kernel, dim3((unsigned)S, (unsigned)J), dim3(kAcqThreads), plan.lds, (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(acq_decide_kernel, dim3(1), dim3(kAcqMaxS), 0, (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return acquire_launch(plan.sum_blocks, S, J, 1, plan.lds, kAcqMaxS, stream, acq_symbol_sums_kernel, plan.args, acq_phase_kernel,
+                          plan.args, acq_decide_kernel, plan.args);
 }
 
 // ---- several links per launch: the link table is the call's own, so inside a ChainScope these refuse like the solo entries ----
@@ -439,7 +384,9 @@ int dccn_frame_sync_grouped(int n_links, const dccn_frame_link* links, int frame
     FrameSyncGroupPlan plan;
     DCCN_TRY(frame_sync_group_plan(n_links, links, frames, S, K, CP, W, out_kin, &plan));
     DCCN_NO_CHAINS();
-    return plan.cfo ? frame_sync_group_launch<true>(plan, n_links, stream) : frame_sync_group_launch<false>(plan, n_links, stream);
+    const dim3 grid(plan.blocks, (unsigned)n_links);
+    return links[0].cfo ? launch(frame_sync_grouped_kernel<true>, grid, kSyncThreads, plan.lds, stream, plan.args)
+                        : launch(frame_sync_grouped_kernel<false>, grid, kSyncThreads, plan.lds, stream, plan.args);
 }
 
 int dccn_capture_sync_grouped(int n_links, const dccn_capture_link* links, int frames, int S, int K, int CP, int W, int out_kin,
@@ -447,7 +394,7 @@ int dccn_capture_sync_grouped(int n_links, const dccn_capture_link* links, int f
     CaptureSyncGroupPlan plan;
     DCCN_TRY(capture_sync_group_plan(n_links, links, frames, S, K, CP, W, out_kin, &plan));
     DCCN_NO_CHAINS();
-    return plan.cfo ? capture_sync_group_launch<true>(plan, n_links, stream) : capture_sync_group_launch<false>(plan, n_links, stream);
+    return capture_sync_launch(plan.one, n_links, links[0].cfo != nullptr, plan.args, stream);
 }
 
 int dccn_capture_acquire_grouped(int n_links, const dccn_acquire_link* links, int J, int S, int K, int CP, int n_pilot,
@@ -455,16 +402,8 @@ int dccn_capture_acquire_grouped(int n_links, const dccn_acquire_link* links, in
     CaptureAcquireGroupPlan plan;
     DCCN_TRY(capture_acquire_group_plan(n_links, links, J, S, K, CP, n_pilot, &plan));
     DCCN_NO_CHAINS();
-    const unsigned G = (unsigned)n_links;
-    hipLaunchKernelGGL(acq_symbol_sums_grouped_kernel, dim3(plan.sum_blocks, G), dim3(kAcqSumThreads), 0, (hipStream_t)stream,
-                       plan.args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(acq_phase_grouped_kernel, dim3((unsigned)S, (unsigned)J, G), dim3(kAcqThreads), plan.lds, (hipStream_t)stream,
-                       plan.args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(acq_decide_grouped_kernel, dim3(G), dim3(kAcqMaxS), 0, (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return acquire_launch(plan.sum_blocks, S, J, n_links, plan.lds, kAcqMaxS, stream, acq_symbol_sums_grouped_kernel, plan.args,
+                          acq_phase_grouped_kernel, plan.args, acq_decide_grouped_kernel, plan.args);
 }
 
 // ---- one carrier offset per capture: the solo entry is the grouped one with one link -----------------------------------------
@@ -475,7 +414,8 @@ int dccn_capture_sync_pooled_grouped(int n_links, const dccn_pooled_link* links,
     PooledGroupPlan plan;
     DCCN_TRY(pooled_group_plan(n_links, links, frames, S, K, CP, W, out_kin, &plan));
     DCCN_NO_CHAINS();
-    return pooled_group_launch(plan, n_links, stream);
+    return pooled_launch(plan, n_links, stream, capture_pool_estimate_kernel<PooledGroupArgs>, plan.args,
+                         capture_pool_cut_kernel<false, PooledGroupArgs>, plan.args);
 }
 
 int dccn_capture_sync_pooled(const float* cap, long long n_samples, long long first, const long long* first_dev, long long lo,
@@ -491,26 +431,11 @@ int dccn_capture_sync_sc16(const int16_t* cap, long long n_samples, float scale,
                            int32_t* offset, float* cfo, float* metric, dccn_stream_t stream) {
     if (!sc16_scale_ok(scale)) return DCCN_ERR_INVALID_ARG;
     CaptureSyncPlan plan;
-    if (first_dev)
-        DCCN_TRY(capture_sync_at_plan(sc16_as_checked(cap), n_samples, first_dev, lo, stride, frames, S, K, CP, W, out_kin, x_out,
-                                      offset, cfo, metric, &plan, 4));
-    else
-        DCCN_TRY(capture_sync_plan(sc16_as_checked(cap), n_samples, first, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo,
-                                   metric, &plan, 4));
+    DCCN_TRY(capture_sync_plan(sc16_as_checked(cap), n_samples, 4, CaptureStart{first, first_dev, lo}, stride, frames, S, K, CP, W,
+                               out_kin, x_out, offset, cfo, metric, &plan));
     DCCN_NO_CHAINS();
-    plan.args.cap = nullptr;
-    plan.args.first = first_dev ? 0 : first;
-    const CaptureSyncSc16Args args{plan.args, CapSc16{cap, scale}, first_dev, first_dev ? lo : 0};
-    const dim3 grid(plan.blocks), block(kSyncWaves * kSyncLanes);
-    if (cfo) {
-        DCCN_TRY(set_max_dynamic_smem((const void*)capture_sync_sc16_kernel<true>, plan.lds));
-        hipLaunchKernelGGL(capture_sync_sc16_kernel<true>, grid, block, plan.lds, (hipStream_t)stream, args);
-    } else {
-        DCCN_TRY(set_max_dynamic_smem((const void*)capture_sync_sc16_kernel<false>, plan.lds));
-        hipLaunchKernelGGL(capture_sync_sc16_kernel<false>, grid, block, plan.lds, (hipStream_t)stream, args);
-    }
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    plan.link.cap = nullptr;
+    return capture_sync_launch(plan, 1, cfo != nullptr, CaptureSyncSc16Args{plan.link, CapSc16{cap, scale}, plan.shape}, stream);
 }
 
 int dccn_capture_sync_pooled_sc16(const int16_t* cap, long long n_samples, float scale, long long first, const long long* first_dev,
@@ -525,18 +450,9 @@ int dccn_capture_sync_pooled_sc16(const int16_t* cap, long long n_samples, float
     DCCN_TRY(pooled_group_plan(1, &link, frames, S, K, CP, W, out_kin, &plan, 4));
     DCCN_NO_CHAINS();
     plan.args.link[0].s.cap = nullptr;
-    const PooledGroupArgs& g = plan.args;
-    const PooledSc16Args args{g.link[0], CapSc16{cap, scale}, g.frames, g.S, g.K, g.CP, g.W, g.crop};
-    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_estimate_sc16_kernel, plan.lds_estimate));
-    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_cut_kernel<PooledSc16Args>, plan.lds_cut));
-    const dim3 grid(plan.blocks, 1), block(kSyncWaves * kSyncLanes);
-    hipLaunchKernelGGL(capture_pool_estimate_sc16_kernel, grid, block, plan.lds_estimate, (hipStream_t)stream, args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(capture_pool_reduce_kernel, dim3(1), dim3(kSyncLanes), 0, (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(capture_pool_cut_kernel<PooledSc16Args>, grid, block, plan.lds_cut, (hipStream_t)stream, args);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    const PooledSc16Args args{plan.args.link[0], CapSc16{cap, scale}, plan.args.shape};
+    return pooled_launch(plan, 1, stream, capture_pool_estimate_kernel<PooledSc16Args>, args,
+                         capture_pool_cut_kernel<false, PooledSc16Args>, args);
 }
 
 int dccn_capture_acquire_sc16(const int16_t* cap, long long n_samples, float scale, long long lo, int J, int S, int K, int CP,
@@ -549,13 +465,8 @@ int dccn_capture_acquire_sc16(const int16_t* cap, long long n_samples, float sca
     DCCN_NO_CHAINS();
     plan.args.cap = nullptr;
     const AcqSc16Args args{plan.args, CapSc16{cap, scale}};
-    hipLaunchKernelGGL(acq_symbol_sums_sc16_kernel, dim3(plan.sum_blocks), dim3(kAcqSumThreads), 0, (hipStream_t)stream, args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(acq_phase_sc16_kernel, dim3((unsigned)S, (unsigned)J), dim3(kAcqThreads), plan.lds, (hipStream_t)stream, args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(acq_decide_kernel, dim3(1), dim3(kAcqMaxS), 0, (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return acquire_launch(plan.sum_blocks, S, J, 1, plan.lds, kAcqMaxS, stream, acq_symbol_sums_sc16_kernel, args, acq_phase_sc16_kernel,
+                          args, acq_decide_kernel, plan.args);
 }
 
 // ---- carrier offsets beyond half a subcarrier spacing: acquisition over (q, m), the cut with the whole offset taken out ---------
@@ -571,7 +482,7 @@ int dccn_capture_acquire_wide(const float* cap, long long n_samples, long long l
                               int n_pilot, int M, long long* first_out, float* cfo_out, int32_t* cfo_int_out, float* sym_metric,
                               float* phase_metric, void* workspace, size_t workspace_bytes, dccn_stream_t stream) {
     if (!capture_acquire_wide_shape_ok(S, K, CP, n_pilot, J, M)) return DCCN_ERR_INVALID_ARG;
-    if (!cfo_int_out || (reinterpret_cast<uintptr_t>(cfo_int_out) & 3u) != 0) return DCCN_ERR_INVALID_ARG;
+    if (!cfo_int_out || !aligned_to<4>(cfo_int_out)) return DCCN_ERR_INVALID_ARG;
     const AcqWorkspace w = capture_acquire_wide_layout(S, K, CP, J, M);
     // the narrow call's checks (the samples read are the same); its workspace is the M = 0 layout, a prefix of this one
     CaptureAcquirePlan plan;
@@ -581,30 +492,21 @@ int dccn_capture_acquire_wide(const float* cap, long long n_samples, long long l
     DCCN_NO_CHAINS();
     AcqWideArgs args{plan.args, cfo_int_out, M};
     args.a.rhat = reinterpret_cast<int*>(static_cast<char*>(workspace) + w.rhat);
-    const size_t lds = capture_acquire_wide_lds(S, K, CP, n_pilot, M);
-    DCCN_TRY(set_max_dynamic_smem((const void*)acq_phase_wide_kernel, lds));
-    hipLaunchKernelGGL(acq_symbol_sums_kernel, dim3(plan.sum_blocks), dim3(kAcqSumThreads), 0, (hipStream_t)stream, args.a);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(acq_phase_wide_kernel, dim3((unsigned)S, (unsigned)J), dim3(kAcqThreads), lds, (hipStream_t)stream, args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(acq_decide_wide_kernel, dim3(1), dim3(kAcqWideThreads), 0, (hipStream_t)stream, args);
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return acquire_launch(plan.sum_blocks, S, J, 1, capture_acquire_wide_lds(S, K, CP, n_pilot, M), kAcqWideThreads, stream,
+                          acq_symbol_sums_kernel, args.a, acq_phase_wide_kernel, args, acq_decide_wide_kernel, args);
 }
 
 int dccn_capture_sync_wide(const float* cap, long long n_samples, const long long* first_dev, long long lo, long long stride,
                            int frames, int S, int K, int CP, int W, int out_kin, float* x_out, int32_t* offset, float* cfo,
                            float* metric, const int32_t* cfo_int_dev, const float* cfo_frac_dev, dccn_stream_t stream) {
+    if (!first_dev) return DCCN_ERR_INVALID_ARG;
     CaptureSyncPlan plan;
-    DCCN_TRY(capture_sync_at_plan(cap, n_samples, first_dev, lo, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo, metric,
-                                  &plan));
+    DCCN_TRY(capture_sync_plan(cap, n_samples, 8, CaptureStart{0, first_dev, lo}, stride, frames, S, K, CP, W, out_kin, x_out, offset,
+                               cfo, metric, &plan));
     if (!cfo || !wide_inputs_ok(cfo_int_dev, cfo_frac_dev)) return DCCN_ERR_INVALID_ARG;
     DCCN_NO_CHAINS();
-    DCCN_TRY(set_max_dynamic_smem((const void*)capture_sync_wide_kernel, plan.lds));
-    hipLaunchKernelGGL(capture_sync_wide_kernel, dim3(plan.blocks), dim3(kSyncWaves * kSyncLanes), plan.lds, (hipStream_t)stream,
-                       CaptureSyncWideArgs{CaptureSyncAtArgs{plan.args, first_dev, lo}, CfoWide{cfo_int_dev, cfo_frac_dev}});
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return launch(capture_sync_kernel<SyncFinish::kWide, CaptureSyncWideArgs>, dim3(plan.blocks), kSyncThreads, plan.lds, stream,
+                  CaptureSyncWideArgs{{plan.link, CapOfArgs{}, plan.shape}, CfoWide{cfo_int_dev, cfo_frac_dev}});
 }
 
 size_t dccn_capture_sync_pooled_wide_workspace_size(int frames) { return frames > 0 ? pooled_workspace_bytes(frames) + 16 : 0; }
@@ -622,17 +524,9 @@ int dccn_capture_sync_pooled_wide(const float* cap, long long n_samples, long lo
     if (workspace_bytes < gamma_bytes + 16) return DCCN_ERR_WORKSPACE;
     DCCN_NO_CHAINS();
     plan.args.link[0].s.cfo = reinterpret_cast<float*>(static_cast<char*>(workspace) + gamma_bytes);
-    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_estimate_kernel, plan.lds_estimate));
-    DCCN_TRY(set_max_dynamic_smem((const void*)capture_pool_cut_wide_kernel, plan.lds_cut));
-    const dim3 grid(plan.blocks, 1), block(kSyncWaves * kSyncLanes);
-    hipLaunchKernelGGL(capture_pool_estimate_kernel, grid, block, plan.lds_estimate, (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(capture_pool_reduce_kernel, dim3(1), dim3(kSyncLanes), 0, (hipStream_t)stream, plan.args);
-    DCCN_LAUNCH_CHECK();
-    hipLaunchKernelGGL(capture_pool_cut_wide_kernel, grid, block, plan.lds_cut, (hipStream_t)stream,
-                       PooledWideArgs{plan.args, CfoWide{cfo_int_dev, cfo_frac_dev}, cfo_out});
-    DCCN_LAUNCH_CHECK();
-    return DCCN_OK;
+    return pooled_launch(plan, 1, stream, capture_pool_estimate_kernel<PooledGroupArgs>, plan.args,
+                         capture_pool_cut_kernel<true, PooledWideArgs>,
+                         PooledWideArgs{{plan.args.link[0], CapOfArgs{}, plan.args.shape}, CfoWide{cfo_int_dev, cfo_frac_dev}, cfo_out});
 }
 
 }  // extern "C"

@@ -1,41 +1,49 @@
-// Per-frame timing alignment from the cyclic prefix (dccn_frame_sync), and its variant that also estimates
-// and removes the carrier-frequency offset (dccn_frame_sync_cfo).
+// Per-frame timing alignment from the cyclic prefix, with or without the carrier-frequency offset taken out.
 //
-// A frame is T = S * (K + CP) complex samples y[n], taken as circular (indices mod T).  With N = K + CP:
+// A frame is T = S * (K + CP) complex samples y[n].  With N = K + CP:
 //     p[n] = y[n] * conj(y[n + K])                  e[n] = (|y[n]|^2 + |y[n + K]|^2) / 2
 //     Gamma(t) = sum_{s < S} sum_{n < CP} p[s N + t + n]      Phi(t) likewise over e
 //     Lambda(t) = |Gamma(t)| - Phi(t)               (<= 0: the rho = 1 form of the ML cyclic-prefix estimator)
-//     offset = the smallest t in [-W, W] with the largest Lambda(t);  aligned[n] = y[(n + offset) mod T]
-// CFO variant: a frame s[n] exp(+2 pi i eps n / K) has p = |s|^2 exp(-2 pi i eps), so the angle of Gamma(offset) is the ML estimate
-// of eps (in subcarrier spacings, unambiguous for |eps| < 1/2):
+//     offset = the smallest t in [-W, W] with the largest Lambda(t);  aligned[n] = y[n + offset]
+// A frame s[n] exp(+2 pi i eps n / K) has p = |s|^2 exp(-2 pi i eps), so the angle of Gamma(offset) is the ML estimate of eps (in
+// subcarrier spacings, unambiguous for |eps| < 1/2):
 //     cfo = -atan2(Im Gamma(offset), Re Gamma(offset)) / (2 pi);  out[n] = aligned[n] exp(-2 pi i cfo n / K),  n = 0 .. T-1
 //
-// One wave per frame, four frames per 256-thread block; no atomics, no workspace, every sum in a fixed order (two runs give
-// the same bits).  The frame is read once (16-byte loads) into the wave's own LDS region, every later step reads LDS, and the
-// rotated frame leaves with 16-byte stores: the traffic of the copy the launch stands in for.
+// One wave per frame, four frames per 256-thread block; no atomics, every sum in a fixed order (two runs give the same bits).
+// The frame is read once (16-byte loads) into the wave's own LDS region, every later step reads LDS, and the frame leaves with
+// 16-byte stores: the traffic of the copy the launch stands in for.  The sums, their order, the stores and the derotation are
+// stated once (sync_estimate, sync_store, sync_cfo_store); a kernel of this file is a choice along five axes:
 //
-// dccn_capture_sync (capture_sync_kernel, at the end) is the same estimator on frames that still sit inside one contiguous capture
-// c[n]: frame f nominally starts at b = first + f * stride, its window [b - W, b + T + W) is indexed linearly (nothing wraps: the
-// samples around the frame are its neighbours in the air), and out[n] = c[b + offset + n].  The sums, their order, the stores and
-// the derotation are stated once (sync_estimate, sync_store, sync_cfo_store); the two families differ in the index mapping alone
-// (SyncCircular, SyncLinear: where a sample of the frame sits in the wave's LDS region).
+//   index mapping  where a sample of the frame sits in the wave's LDS region.  SyncCircular: the frame is given on its own and
+//                  taken as circular (indices mod T) -- frame_sync_body, gen_apply_sync_kernel (datagen.h).  SyncLinear: the
+//                  frame still sits inside one contiguous capture c[n]; frame f nominally starts at b = start + f * stride, its
+//                  window [b - W, b + T + W) is indexed linearly (nothing wraps: the samples around the frame are its neighbours
+//                  in the air) and out[n] = c[b + offset + n] -- capture_sync_body, capture_pool_cut_kernel.
+//   source         the capture's sample format (capture_source.h): CapOfArgs, the float32 capture a link names, or CapSc16, 16-bit
+//                  integer I/Q and a scale.  The window loader has one form per format; the sc16 form leaves in LDS, slot for slot,
+//                  what the float32 form leaves there for the converted capture, and everything behind the load is the same code.
+//   start          capture_start: a link's `first`, or, where first_dev is given, the value read there (what acquisition left on
+//                  the device) kept inside [lo, lo + T - 1], the range the host checked every window against.
+//   finish         SyncFinish, what follows the estimate: the offset alone; the frame's own cfo taken out; Gamma_f stored for the
+//                  pooled sum (one cfo per capture: estimate, capture_pool_reduce_kernel, capture_pool_cut_kernel); or the whole
+//                  offset taken out where it exceeds half a spacing (the fraction unwrapped against acquisition's (m^, eps^)).
+//   links          one link or up to kMaxChains per launch: the kernels are templates over their argument block (LinkGroup: a
+//                  by-value table, the link index on blockIdx.y; OneLink: one link and its source).
 //
-// dccn_frame_sync_grouped / dccn_capture_sync_grouped (at the end) run frame_sync_body / capture_sync_body for up to kMaxChains
-// links in one launch: a by-value table of per-link pointers, the link index on blockIdx.y.
-//
-// dccn_capture_sync_pooled(_grouped) (at the end) estimate ONE carrier offset per capture from the sum of the frames' Gamma_f: the
-// same estimate body with a finish that stores Gamma_f, a one-wave sum in a stated order, and a cut pass that derotates every
-// frame with the common value -- three launches, new instantiations only.
-//
-// dccn_capture_sync_wide / dccn_capture_sync_pooled_wide (at the end) take the WHOLE offset out where it exceeds half a spacing:
-// the prefix's fraction is unwrapped against the pair (m^, eps^) dccn_capture_acquire_wide left on the device (cfo_unwrap), and
-// the frame is derotated with the integer part's turns reduced exactly (frame_cfo_derotate_wide) -- a WIDE instantiation of
-// capture_sync_body, and a pooled cut kernel of its own.
-//
-// dccn_capture_sync_sc16 / dccn_capture_sync_pooled_sc16 (at the end) read a capture of 16-bit integer I/Q (capture_source.h): the
-// window loader has an sc16 form that leaves in LDS, slot for slot, what the float32 loader leaves there for the converted
-// capture, and the cut, the pooled estimate and the pooled cut are instantiated over it -- new kernels only, every float32 kernel
-// keeps its code.
+// The instantiations that exist (the sync unit; gen_apply_sync_kernel is datagen.h's):
+//   kernel                                  argument block         entry points
+//   frame_sync_kernel, frame_sync_cfo_kernel                       dccn_frame_sync, dccn_frame_sync_cfo
+//   frame_sync_grouped_kernel<CFO>          FrameSyncGroupArgs     dccn_frame_sync_grouped
+//   capture_sync_kernel<kOffset|kFrameCfo>  CaptureSyncSoloArgs    dccn_capture_sync, dccn_capture_sync_at
+//   capture_sync_kernel<kOffset|kFrameCfo>  CaptureSyncGroupArgs   dccn_capture_sync_grouped
+//   capture_sync_kernel<kOffset|kFrameCfo>  CaptureSyncSc16Args    dccn_capture_sync_sc16
+//   capture_sync_kernel<kWide>              CaptureSyncWideArgs    dccn_capture_sync_wide
+//   capture_pool_estimate_kernel            PooledGroupArgs        dccn_capture_sync_pooled(_grouped), dccn_capture_sync_pooled_wide
+//   capture_pool_estimate_kernel            PooledSc16Args         dccn_capture_sync_pooled_sc16
+//   capture_pool_reduce_kernel              PooledGroupArgs        every pooled entry (it reads no capture)
+//   capture_pool_cut_kernel<false>          PooledGroupArgs        dccn_capture_sync_pooled(_grouped)
+//   capture_pool_cut_kernel<false>          PooledSc16Args         dccn_capture_sync_pooled_sc16
+//   capture_pool_cut_kernel<true>           PooledWideArgs         dccn_capture_sync_pooled_wide
 #pragma once
 #include "capture_source.h"
 #include "common.h"
@@ -80,7 +88,7 @@ struct FrameSyncArgs {
 
 // Steps 2-4 on a frame that sits in the wave's LDS region (y: its samples, placed as `at` says; pe: the kSyncLanes (P, E) slots
 // behind them): the frame's offset, the same value in every lane.  The block's barriers are inside: every wave of the block calls
-// this, live or not.  Shared by the frame_sync kernels, capture_sync_kernel and gen_apply_sync_kernel (datagen.h): one statement
+// this, live or not.  Shared by the frame_sync kernels, the capture kernels and gen_apply_sync_kernel (datagen.h): one statement
 // of the sums and their order.  gamma_out (nullable): Gamma at the returned offset, the winning lane's sums handed to every lane.
 template <class At>
 __device__ __forceinline__ int sync_estimate(const At at, const float2* y, float4* pe, const int lane, const bool live, const int S,
@@ -179,10 +187,10 @@ __device__ __forceinline__ float2 frame_cfo_derotate(const float2 u, const float
     sincospif(2.0f * (turns - rintf(turns)), &sn, &cs);
     return make_float2(u.x * cs + u.y * sn, u.y * cs - u.x * sn);
 }
-// The wide variant (dccn_capture_sync_wide, at the end): the offset is I + cfo with I a whole number of spacings, 0 <= ipos < K
-// its residue mod K.  I n / K turns are whole but for (ipos n mod K) / K, an exact integer over K, so the phase keeps the
-// roundings above however large I is; with ipos = 0 the turns are the expression above, bit for bit (0 + a = a).  ipos n stays
-// below K T < 2^22: four frames of T samples fit a block's LDS (frame_sync_shape_ok), so T <= 1920.
+// The wide finish: the offset is I + cfo with I a whole number of spacings, 0 <= ipos < K its residue mod K.  I n / K turns are
+// whole but for (ipos n mod K) / K, an exact integer over K, so the phase keeps the roundings above however large I is; with
+// ipos = 0 the turns are the expression above, bit for bit (0 + a = a).  ipos n stays below K T < 2^22: four frames of T samples
+// fit a block's LDS (frame_sync_shape_ok), so T <= 1920.
 __device__ __forceinline__ float2 frame_cfo_derotate_wide(const float2 u, const unsigned ipos, const float cfo, const int n,
                                                           const int K, const float fK) {
     const float turns = ((float)(ipos * (unsigned)n % (unsigned)K) + cfo * (float)n) / fK;
@@ -261,7 +269,7 @@ __device__ __forceinline__ void sync_finish_wide(const At at, const float2* y, c
         sync_cfo_store<At, true>(at, y, x_out + (size_t)f * S * (crop ? K : K + CP) * 2, theta, frac, lane, S, K, CP, crop, ipos);
 }
 
-// The launch, stated once; CFO selects the variant (cfo_out [frames] is written by that variant only).
+// The launch on frames given on their own, stated once; CFO selects the variant (cfo_out [frames] is written by that variant only).
 template <bool CFO>
 __device__ __forceinline__ void frame_sync_body(const FrameSyncArgs& a, float* cfo_out) {
     extern __shared__ float4 sync_lds[];
@@ -297,8 +305,28 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) frame_sync_cfo
     frame_sync_body<true>(a.s, a.cfo);
 }
 
-// ---- frames cut from a contiguous capture (dccn_capture_sync) -----------------------------------------------------------------
-// Frame f's window is the samples [b - W, b + T + W) of the capture, b = first + f * stride; it is all the wave reads.  The
+// Several links per launch (dccn_frame_sync_grouped): each link has its own frames and outputs; frames, the shape, W and out_kin
+// are the call's.  The table travels by value in the kernel arguments and is indexed by blockIdx.y, a block-uniform value (scalar
+// loads, as ChainOffs is read); blockIdx.x stays what the body takes it for, so a link's blocks are the solo launch's.
+struct FrameSyncLink {
+    const float* x;
+    float* x_out;
+    int32_t* offset;
+    float* metric;
+    float* cfo;
+};
+struct FrameSyncGroupArgs {
+    FrameSyncLink link[kMaxChains];
+    int frames, S, K, CP, W, crop;
+};
+template <bool CFO>
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) frame_sync_grouped_kernel(const FrameSyncGroupArgs g) {
+    const FrameSyncLink& l = g.link[blockIdx.y];
+    frame_sync_body<CFO>(FrameSyncArgs{l.x, l.x_out, l.offset, l.metric, g.frames, g.S, g.K, g.CP, g.W, g.crop}, l.cfo);
+}
+
+// ---- frames cut from a contiguous capture ---------------------------------------------------------------------------------------
+// Frame f's window is the samples [b - W, b + T + W) of the capture, b = start + f * stride; it is all the wave reads.  The
 // capture's base is 16-byte aligned, so EVEN samples are: the wave's region starts at the even sample a0 = (b - W) & ~1 and holds
 // pairs (a0 + 2 i, a0 + 2 i + 1), one 16-byte load each.  A window that starts on an odd sample has its first sample in the
 // upper half of pair 0, and then (T + 2 W is even) its last sample in the lower half of the last pair: those two pairs are read
@@ -313,15 +341,45 @@ static inline bool capture_sync_shape_ok(int S, int K, int CP, int W) {
     return kSyncWaves * capture_sync_lds_per_frame(S * (K + CP), W) <= kSyncLdsMax;
 }
 
-struct CaptureSyncArgs {
-    const float* cap;           // [n_samples, 2]
-    long long first, stride;    // frame f nominally starts at sample first + f * stride
+// What a launch's links share, and what one link of a capture cut is.
+struct SyncShape {
+    int frames, S, K, CP, W;
+    int crop;                   // 1: x_out rows are the K samples behind each symbol's prefix (out_kin == K)
+};
+struct CaptureSyncLink {
+    const float* cap;           // [n_samples, 2]; not read where the argument block names another source
+    long long first, stride;    // frame f nominally starts at sample start + f * stride
+    const long long* first_dev; // nullable [1]: the start is read here and kept inside [lo, lo + T - 1]
+    long long lo;
     float* x_out;               // nullable: [frames, S, out_kin, 2]
     int32_t* offset;            // [frames]
     float* metric;              // nullable: [frames, 2 W + 1]
-    float* cfo;                 // [frames], the CFO instantiation only
-    int frames, S, K, CP, W;
-    int crop;
+    float* cfo;                 // per-frame finishes: [frames]; pooled: [1], the capture's estimate
+};
+// Where frame 0 nominally starts: `first`, or what the device holds kept inside the range the host checked every window against,
+// so a wrong value cannot read outside the capture.  first_dev is the same for every thread of a block.
+__device__ __forceinline__ long long capture_start(const CaptureSyncLink& l, const int T) {
+    if (!l.first_dev) return l.first;
+    const long long hi = l.lo + T - 1;
+    const long long got = l.first_dev[0];
+    return got < l.lo ? l.lo : (got > hi ? hi : got);
+}
+
+// The argument blocks the capture kernels are templates over: at(y) the link of grid row y, source() where its samples come from.
+template <class Link>
+struct LinkGroup {              // up to kMaxChains links, each naming its own float32 capture
+    Link link[kMaxChains];
+    SyncShape shape;
+    __device__ __forceinline__ const Link& at(const unsigned y) const { return link[y]; }
+    __device__ __forceinline__ CapOfArgs source() const { return CapOfArgs{}; }
+};
+template <class Link, class Src>
+struct OneLink {                // one link and its source
+    Link link;
+    Src src;
+    SyncShape shape;
+    __device__ __forceinline__ const Link& at(const unsigned) const { return link; }
+    __device__ __forceinline__ Src source() const { return src; }
 };
 
 // The samples [start, start + len) of the capture (len even) into a wave's region, as stated above: the region's pair i holds the
@@ -395,120 +453,75 @@ __device__ __forceinline__ void capture_window_load(float4* region, const CapSc1
     }
 }
 
-// The launch, stated once; `first` is where frame 0 nominally starts (the argument, or what dccn_capture_sync_at read).
-// POOL (dccn_capture_sync_pooled's estimate pass, below): the same estimate with another finish -- the frame's offset and
-// Gamma_f(offset) go to offset[f] and gamma_ws[f], and no frame is written.
-// WIDE (dccn_capture_sync_wide, at the end): the CFO variant with sync_finish_wide in place of sync_finish.
-// Src (capture_source.h): where the window comes from -- CapOfArgs{}: the float32 capture a.cap.
-template <bool CFO, bool POOL = false, bool WIDE = false, class Src>
-__device__ __forceinline__ void capture_sync_body(const CaptureSyncArgs& a, const Src src, const long long first,
+// What follows the estimate of a capture's frame.
+enum class SyncFinish {
+    kOffset,        // offset[f]; the aligned frame leaves as it is
+    kFrameCfo,      // and cfo[f], the frame's own estimate, taken out of the frame
+    kPool,          // offset[f] and Gamma_f(offset[f]) to gamma_ws[f]; no frame is written (the pooled call's estimate pass)
+    kWide,          // kFrameCfo with the fraction unwrapped against `wide`: cfo[f] holds the total, which is taken out
+};
+
+// The launch, stated once: link l's frames of shape g from the source src.  gamma_ws: kPool's store; wide: kWide's device inputs.
+template <SyncFinish FIN, class Src>
+__device__ __forceinline__ void capture_sync_body(const CaptureSyncLink& l, const SyncShape& g, const Src src,
                                                   float2* gamma_ws = nullptr, const CfoWide wide = CfoWide{nullptr, nullptr}) {
     extern __shared__ float4 sync_lds[];
     const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
-    const int T = a.S * (a.K + a.CP), W = a.W;
+    const int T = g.S * (g.K + g.CP), W = g.W;
+    const long long first = capture_start(l, T);
     const long long f = (long long)blockIdx.x * kSyncWaves + wave;
-    const bool live = f < a.frames;
+    const bool live = f < g.frames;          // (a ragged last block: the wave still meets the block's barriers)
     const size_t per = capture_sync_lds_per_frame(T, W) / 16;
     float4* const region = sync_lds + (size_t)wave * per;
     float4* const pe = region + (per - kSyncLanes);
-    const long long start = live ? first + f * a.stride - W : 0;            // the window's first sample
+    const long long start = live ? first + f * l.stride - W : 0;            // the window's first sample
     const int sh = (int)(start & 1);
     const float2* const y = reinterpret_cast<const float2*>(region) + sh;    // slot 0 = sample start
 
     // 1. the window, once, into LDS
-    if (live) capture_window_load(region, src.of(a), start, T + 2 * W, lane);
+    if (live) capture_window_load(region, src.of(l), start, T + 2 * W, lane);
     const SyncLinear at{W};
     float2 gamma = make_float2(0.f, 0.f);
-    const int theta = sync_estimate(at, y, pe, lane, live, a.S, a.K, a.CP, W,
-                                    (live && a.metric) ? a.metric + (size_t)f * (2 * W + 1) : nullptr,
-                                    (CFO || POOL) ? &gamma : nullptr);
+    const int theta = sync_estimate(at, y, pe, lane, live, g.S, g.K, g.CP, W,
+                                    (live && l.metric) ? l.metric + (size_t)f * (2 * W + 1) : nullptr,
+                                    FIN != SyncFinish::kOffset ? &gamma : nullptr);
     if (!live) return;
-    if constexpr (POOL) {
+    if constexpr (FIN == SyncFinish::kPool) {
         if (lane == 0) {
-            a.offset[f] = theta;
+            l.offset[f] = theta;
             gamma_ws[f] = gamma;
         }
-    } else if constexpr (WIDE) {
-        sync_finish_wide(at, y, f, theta, gamma, lane, a.x_out, a.offset, a.cfo, a.S, a.K, a.CP, a.crop, wide);
+    } else if constexpr (FIN == SyncFinish::kWide) {
+        sync_finish_wide(at, y, f, theta, gamma, lane, l.x_out, l.offset, l.cfo, g.S, g.K, g.CP, g.crop, wide);
     } else {
-        sync_finish<CFO>(at, y, f, theta, gamma, lane, a.x_out, a.offset, a.cfo, a.S, a.K, a.CP, a.crop);
+        sync_finish<FIN == SyncFinish::kFrameCfo>(at, y, f, theta, gamma, lane, l.x_out, l.offset, l.cfo, g.S, g.K, g.CP, g.crop);
     }
 }
 
-template <bool CFO>
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_kernel(const CaptureSyncArgs a) {
-    capture_sync_body<CFO>(a, CapOfArgs{}, a.first);
+// The per-frame cut over its argument block: one kernel text serves a host start and a device one, one link and several, both
+// sample formats.  The float32 solo calls have a one-link block of their own: as the one-link case of the group block (8 links by
+// value, 600 bytes of kernel arguments) the call measured 0.3 - 0.6 us longer on the host (profiles/capture_front_once.md).
+using CaptureSyncGroupArgs = LinkGroup<CaptureSyncLink>;
+using CaptureSyncSoloArgs = OneLink<CaptureSyncLink, CapOfArgs>;
+using CaptureSyncSc16Args = OneLink<CaptureSyncLink, CapSc16>;
+struct CaptureSyncWideArgs : CaptureSyncSoloArgs {
+    CfoWide wide;
+};
+template <SyncFinish FIN, class Args>
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_kernel(const Args g) {
+    static_assert(FIN != SyncFinish::kPool, "the pooled estimate is capture_pool_estimate_kernel");
+    if constexpr (FIN == SyncFinish::kWide)
+        capture_sync_body<FIN>(g.at(blockIdx.y), g.shape, g.source(), nullptr, g.wide);
+    else
+        capture_sync_body<FIN>(g.at(blockIdx.y), g.shape, g.source());
 }
 
-// dccn_capture_sync_at: the same launch with `first` read from device memory (what dccn_capture_acquire left there) and kept
-// inside [lo, lo + T - 1], the range the host checked every window against: a wrong value cannot read outside the capture.
-struct CaptureSyncAtArgs {
-    CaptureSyncArgs s;          // (s.first is not read)
-    const long long* first_dev; // [1]
-    long long lo;
-};
-template <bool CFO>
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_at_kernel(const CaptureSyncAtArgs a) {
-    const long long hi = a.lo + (long long)a.s.S * (a.s.K + a.s.CP) - 1;
-    const long long got = a.first_dev[0];
-    capture_sync_body<CFO>(a.s, CapOfArgs{}, got < a.lo ? a.lo : (got > hi ? hi : got));
-}
-
-// ---- several links per launch (dccn_frame_sync_grouped, dccn_capture_sync_grouped) ----------------------------------------------
-// Each link has its own frames (or capture, start and stride) and outputs; frames, the shape, W and out_kin are the call's.  The
-// table travels by value in the kernel arguments and is indexed by blockIdx.y, a block-uniform value (scalar loads, as ChainOffs
-// is read); blockIdx.x stays what the bodies take it for, so a link's blocks are the solo launch's.
-struct FrameSyncLink {
-    const float* x;
-    float* x_out;
-    int32_t* offset;
-    float* metric;
-    float* cfo;
-};
-struct FrameSyncGroupArgs {
-    FrameSyncLink link[kMaxChains];
-    int frames, S, K, CP, W, crop;
-};
-template <bool CFO>
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) frame_sync_grouped_kernel(const FrameSyncGroupArgs g) {
-    const FrameSyncLink& l = g.link[blockIdx.y];
-    frame_sync_body<CFO>(FrameSyncArgs{l.x, l.x_out, l.offset, l.metric, g.frames, g.S, g.K, g.CP, g.W, g.crop}, l.cfo);
-}
-
-struct CaptureSyncLink {
-    const float* cap;
-    long long first, stride;
-    const long long* first_dev; // nullable [1]: the start is read here and kept inside [lo, lo + T - 1] (capture_sync_at_kernel)
-    long long lo;
-    float* x_out;
-    int32_t* offset;
-    float* metric;
-    float* cfo;
-};
-struct CaptureSyncGroupArgs {
-    CaptureSyncLink link[kMaxChains];
-    int frames, S, K, CP, W, crop;
-};
-template <bool CFO>
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_grouped_kernel(const CaptureSyncGroupArgs g) {
-    const CaptureSyncLink& l = g.link[blockIdx.y];
-    long long first = l.first;
-    if (l.first_dev) {                                                      // (uniform over the block)
-        const long long hi = l.lo + (long long)g.S * (g.K + g.CP) - 1;
-        const long long got = l.first_dev[0];
-        first = got < l.lo ? l.lo : (got > hi ? hi : got);
-    }
-    capture_sync_body<CFO>(CaptureSyncArgs{l.cap, first, l.stride, l.x_out, l.offset, l.metric, l.cfo, g.frames, g.S, g.K, g.CP, g.W,
-                                           g.crop},
-                           CapOfArgs{}, first);
-}
-
-// ---- one carrier offset per capture, pooled over its frames (dccn_capture_sync_pooled, dccn_capture_sync_pooled_grouped) -------
+// ---- one carrier offset per capture, pooled over its frames -----------------------------------------------------------------------
 // A capture comes from one front end with one oscillator: its frames share one offset, so the estimate is taken from
 //     Gamma = sum_{f < frames} Gamma_f(offset[f]),    cfo = 0 - atan2(Im Gamma, Re Gamma) / (2 pi)
 // and every frame is derotated with that one value.  No frame can leave before every frame's Gamma_f is known, so the call is
 // three launches on the stream, each complete before the next starts (no block waits for another, no atomics, no host round trip):
-//   estimate  capture_sync_body<.., POOL>: the solo estimate, offset[f] and Gamma_f(offset[f]) stored (workspace: float2 [frames])
+//   estimate  capture_sync_body<kPool>: the per-frame estimate, offset[f] and Gamma_f(offset[f]) stored (workspace: float2 [frames])
 //   reduce    one wave per link.  THE ORDER OF THE SUM: lane l adds Gamma_l, Gamma_{l+64}, Gamma_{l+128}, ... in ascending
 //             order onto +0; then a butterfly over the 64 lanes, d = 1, 2, 4, 8, 16, 32: every lane adds the value of lane
 //             (l xor d) to its own (both partners add the same two numbers, so all lanes hold the same bits).  Real and
@@ -518,6 +531,8 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_g
 //             [b_f + offset, b_f + offset + T) then lies inside the window [b_f - W, b_f + T + W) the host checked), the frame is
 //             loaded as the window is (aligned 16-byte pairs, one 8-byte half at each end when it starts on an odd sample) and
 //             leaves through sync_cfo_store with the capture's cfo: the derotation and the 16-byte stores of the per-frame path.
+//             WIDE: the reduce left the capture's FRACTION in link.s.cfo (a workspace slot every block reads); it is unwrapped
+//             in front of the store and frame 0's wave writes the total to total_out.
 // The solo entry is the grouped one with one link: the link index rides on blockIdx.y (reduce: blockIdx.x).
 __host__ __device__ static inline size_t capture_cut_lds_per_frame(int T) { return (size_t)(T + 2) * 8; }
 constexpr int kPoolAhead = 16;              // the reduce launch's loads in flight per lane
@@ -526,42 +541,35 @@ struct PooledLink {
     CaptureSyncLink s;          // s.cfo: [1], the capture's estimate
     float2* gamma;              // [frames]: Gamma_f(offset[f])
 };
-struct PooledGroupArgs {
-    PooledLink link[kMaxChains];
-    int frames, S, K, CP, W, crop;
-    __device__ __forceinline__ const PooledLink& at(const unsigned y) const { return link[y]; }
-    __device__ __forceinline__ CapOfArgs source() const { return CapOfArgs{}; }
+struct PooledGroupArgs : LinkGroup<PooledLink> {};     // (a type of its own: capture_pool_reduce_kernel keeps its symbol)
+using PooledSc16Args = OneLink<PooledLink, CapSc16>;
+struct PooledWideArgs : OneLink<PooledLink, CapOfArgs> {
+    CfoWide wide;
+    float* total_out;           // [1]
 };
-__device__ __forceinline__ long long pooled_first(const CaptureSyncLink& l, const int T) {     // as capture_sync_grouped_kernel
-    if (!l.first_dev) return l.first;
-    const long long hi = l.lo + T - 1;
-    const long long got = l.first_dev[0];
-    return got < l.lo ? l.lo : (got > hi ? hi : got);
-}
 
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_estimate_kernel(const PooledGroupArgs g) {
-    const PooledLink& l = g.link[blockIdx.y];
-    const long long first = pooled_first(l.s, g.S * (g.K + g.CP));
-    capture_sync_body<false, true>(CaptureSyncArgs{l.s.cap, first, l.s.stride, nullptr, l.s.offset, l.s.metric, nullptr, g.frames, g.S,
-                                                   g.K, g.CP, g.W, g.crop},
-                                   CapOfArgs{}, first, l.gamma);
+template <class Args>
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_estimate_kernel(const Args g) {
+    const PooledLink& l = g.at(blockIdx.y);
+    capture_sync_body<SyncFinish::kPool>(l.s, g.shape, g.source(), l.gamma);
 }
 
 static __global__ void __launch_bounds__(kSyncLanes) capture_pool_reduce_kernel(const PooledGroupArgs g) {
     const PooledLink& l = g.link[blockIdx.x];
     const int lane = threadIdx.x;
+    const int frames = g.shape.frames;
     float gr = 0.f, gi = 0.f;
     // the lane's terms, kPoolAhead loads in flight at a time (their latency is all this launch waits for); added in the stated order
-    for (int f0 = lane; f0 < g.frames; f0 += kSyncLanes * kPoolAhead) {
+    for (int f0 = lane; f0 < frames; f0 += kSyncLanes * kPoolAhead) {
         float2 t[kPoolAhead];
 #pragma unroll
         for (int u = 0; u < kPoolAhead; ++u) {
             const int f = f0 + u * kSyncLanes;
-            t[u] = f < g.frames ? l.gamma[f] : make_float2(0.f, 0.f);
+            t[u] = f < frames ? l.gamma[f] : make_float2(0.f, 0.f);
         }
 #pragma unroll
         for (int u = 0; u < kPoolAhead; ++u) {
-            if (f0 + u * kSyncLanes < g.frames) {
+            if (f0 + u * kSyncLanes < frames) {
                 gr += t[u].x;
                 gi += t[u].y;
             }
@@ -574,11 +582,11 @@ static __global__ void __launch_bounds__(kSyncLanes) capture_pool_reduce_kernel(
     if (lane == 0) l.s.cfo[0] = cfo_of_gamma(make_float2(gr, gi));
 }
 
-// The cut, over the launch's argument block: PooledGroupArgs (the float32 capture each link names), or PooledSc16Args (at the end).
-template <class Args>
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_cut_kernel(const Args g) {
+template <bool WIDE, class Args>
+static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_cut_kernel(const Args a) {
     extern __shared__ float4 sync_lds[];
-    const PooledLink& l = g.at(blockIdx.y);
+    const PooledLink& l = a.at(blockIdx.y);
+    const SyncShape& g = a.shape;
     const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
     const int T = g.S * (g.K + g.CP), W = g.W;
     const long long f = (long long)blockIdx.x * kSyncWaves + wave;
@@ -587,99 +595,20 @@ static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_c
     long long start = 0;
     if (live) {
         const int got = l.s.offset[f];
-        start = pooled_first(l.s, T) + f * l.s.stride + (got < -W ? -W : (got > W ? W : got));
+        start = capture_start(l.s, T) + f * l.s.stride + (got < -W ? -W : (got > W ? W : got));
     }
     const float2* const y = reinterpret_cast<const float2*>(region) + (int)(start & 1);      // slot 0 = sample start
-    if (live) capture_window_load(region, g.source().of(l.s), start, T, lane);
+    if (live) capture_window_load(region, a.source().of(l.s), start, T, lane);
     __syncthreads();                                    // (the frame is complete in LDS)
     if (!live) return;
     const float cfo = l.s.cfo[0];
-    sync_cfo_store(SyncLinear{0}, y, l.s.x_out + (size_t)f * g.S * (g.crop ? g.K : g.K + g.CP) * 2, 0, cfo, lane, g.S, g.K, g.CP,
-                   g.crop);
-}
-
-// ---- the whole offset taken out: the prefix's fraction unwrapped against acquisition's (m^, eps^_acq) ---------------------------
-// dccn_capture_sync_wide: dccn_capture_sync_at's CFO launch with sync_finish_wide.  dccn_capture_sync_pooled_wide: the pooled
-// call's estimate and reduce launches as they are (the reduce writes the capture's fraction to a workspace slot), then a cut
-// of its own.  Timing, offsets and metric are the existing calls' bits; with m^ = 0 and eps^_acq = 0 so are cfo and the frames.
-struct CaptureSyncWideArgs {
-    CaptureSyncAtArgs at;
-    CfoWide wide;
-};
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_wide_kernel(const CaptureSyncWideArgs a) {
-    const long long hi = a.at.lo + (long long)a.at.s.S * (a.at.s.K + a.at.s.CP) - 1;
-    const long long got = a.at.first_dev[0];
-    capture_sync_body<true, false, true>(a.at.s, CapOfArgs{}, got < a.at.lo ? a.at.lo : (got > hi ? hi : got), nullptr, a.wide);
-}
-struct PooledWideArgs {
-    PooledGroupArgs g;          // one link; link[0].s.cfo: the workspace slot of the capture's fraction
-    CfoWide wide;
-    float* total_out;           // [1]
-};
-// capture_pool_cut_kernel's statements (that kernel keeps its own text and instruction stream) with the unwrap in front of the store:
-// link[0].s.cfo holds the capture's fraction, which every block reads; frame 0's wave writes the total to total_out.
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_cut_wide_kernel(const PooledWideArgs a) {
-    extern __shared__ float4 sync_lds[];
-    const PooledGroupArgs& g = a.g;
-    const PooledLink& l = g.link[blockIdx.y];
-    const int lane = threadIdx.x & (kSyncLanes - 1), wave = threadIdx.x / kSyncLanes;
-    const int T = g.S * (g.K + g.CP), W = g.W;
-    const long long f = (long long)blockIdx.x * kSyncWaves + wave;
-    const bool live = f < g.frames;
-    float4* const region = sync_lds + (size_t)wave * (capture_cut_lds_per_frame(T) / 16);
-    long long start = 0;
-    if (live) {
-        const int got = l.s.offset[f];
-        start = pooled_first(l.s, T) + f * l.s.stride + (got < -W ? -W : (got > W ? W : got));
+    unsigned ipos = 0;
+    if constexpr (WIDE) {
+        const int I = cfo_unwrap(cfo, a.wide, g.K, &ipos);
+        if (f == 0 && lane == 0) a.total_out[0] = (float)I + cfo;
     }
-    const float2* const y = reinterpret_cast<const float2*>(region) + (int)(start & 1);      // slot 0 = sample start
-    if (live) capture_window_load(region, l.s.cap, start, T, lane);
-    __syncthreads();                                    // (the frame is complete in LDS)
-    if (!live) return;
-    const float cfo = l.s.cfo[0];
-    unsigned ipos;
-    const int I = cfo_unwrap(cfo, a.wide, g.K, &ipos);
-    if (f == 0 && lane == 0) a.total_out[0] = (float)I + cfo;
-    sync_cfo_store<SyncLinear, true>(SyncLinear{0}, y, l.s.x_out + (size_t)f * g.S * (g.crop ? g.K : g.K + g.CP) * 2, 0, cfo, lane,
+    sync_cfo_store<SyncLinear, WIDE>(SyncLinear{0}, y, l.s.x_out + (size_t)f * g.S * (g.crop ? g.K : g.K + g.CP) * 2, 0, cfo, lane,
                                      g.S, g.K, g.CP, g.crop, ipos);
 }
-
-// ---- 16-bit integer I/Q captures (dccn_capture_sync_sc16, dccn_capture_sync_pooled_sc16) ----------------------------------------
-// The cut, the pooled estimate and the pooled cut over CapSc16: argument blocks of their own (the public link structs and the
-// float32 kernels' arguments keep their layout), s.cap / link.s.cap unused.  One cut kernel serves a host `first` and a device
-// one (first_dev: clamped into [lo, lo + T - 1], as capture_sync_at_kernel does); the pooled sum is capture_pool_reduce_kernel
-// itself, which reads no capture; the pooled cut is capture_pool_cut_kernel over PooledSc16Args.
-struct CaptureSyncSc16Args {
-    CaptureSyncArgs s;          // (s.cap is not read; s.first: the start when first_dev is null)
-    CapSc16 src;
-    const long long* first_dev; // nullable [1]
-    long long lo;
-};
-template <bool CFO>
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_sync_sc16_kernel(const CaptureSyncSc16Args a) {
-    long long first = a.s.first;
-    if (a.first_dev) {                                                      // (uniform over the launch)
-        const long long hi = a.lo + (long long)a.s.S * (a.s.K + a.s.CP) - 1;
-        const long long got = a.first_dev[0];
-        first = got < a.lo ? a.lo : (got > hi ? hi : got);
-    }
-    capture_sync_body<CFO>(a.s, a.src, first);
-}
-
-struct PooledSc16Args {
-    PooledLink link;            // (link.s.cap is not read)
-    CapSc16 src;
-    int frames, S, K, CP, W, crop;
-    __device__ __forceinline__ const PooledLink& at(const unsigned) const { return link; }
-    __device__ __forceinline__ CapSc16 source() const { return src; }
-};
-static __global__ void __launch_bounds__(kSyncWaves * kSyncLanes) capture_pool_estimate_sc16_kernel(const PooledSc16Args g) {
-    const PooledLink& l = g.link;
-    const long long first = pooled_first(l.s, g.S * (g.K + g.CP));
-    capture_sync_body<false, true>(CaptureSyncArgs{nullptr, first, l.s.stride, nullptr, l.s.offset, l.s.metric, nullptr, g.frames, g.S,
-                                                   g.K, g.CP, g.W, g.crop},
-                                   g.src, first, l.gamma);
-}
-// (the cut: capture_pool_cut_kernel<PooledSc16Args>)
 
 }  // namespace dccn

@@ -212,6 +212,41 @@ def test_starts_on_the_device_mix_with_known_starts(lib, shape):
         assert outs[i].same(ref), i
 
 
+SMALL = (2, 8, 4, 2)                                                     # T = 24: every load loop has a ragged end
+
+
+@pytest.mark.parametrize("parity", [0, 1])
+def test_known_start_device_start_and_group_links_agree(lib, parity):
+    """dccn_capture_sync(first = F), dccn_capture_sync_at(first_dev -> F) and each link of a grouped call that holds a known-start
+    link and a device-start link side by side: the same frames, offsets, cfo and metric, bit for bit.  F even and odd (the
+    half-pair loads at the window's ends), 5 frames (a dead wave in the last block), full and cropped rows, with and without cfo."""
+    S, K, CP, W = SMALL
+    T, frames = S * (K + CP), 5
+    assert lib.dccn_capture_sync_supported(*SMALL) == 1
+    cap = dev_capture(SMALL, 0)
+    F = A.true_first(host_capture(SMALL, 0)[1], W + 4, T)
+    F += (F & 1) ^ parity
+    lo = F - 3
+    assert F & 1 == parity and W <= lo <= F <= lo + T - 1
+    first_dev = torch.tensor([F], dtype=torch.int64, device=DEV)
+    known = CutLink(cap, int(cap.shape[0]), F, T)
+    on_device = CutLink(cap, int(cap.shape[0]), F, T, first_dev, lo)
+    for out_kin in (K + CP, K):
+        for cfo in (False, True):
+            want, at = Outs(SMALL, frames, out_kin), Outs(SMALL, frames, out_kin)
+            assert known.solo(lib, SMALL, frames, out_kin, want, cfo, True) == 0
+            assert on_device.solo(lib, SMALL, frames, out_kin, at, cfo, True) == 0
+            torch.cuda.synchronize()
+            assert at.same(want), (out_kin, cfo)
+            assert bool((want.offset != -99).all()) and bool((want.out != SENT).all()) and bool((want.metric != SENT).all())
+            assert bool((want.cfo != SENT).all()) == cfo
+            for links in ([known, on_device], [on_device, known]):
+                st, outs = run_cut_group(lib, SMALL, frames, out_kin, links, cfo, True)
+                assert st == 0
+                assert all(o.same(want) for o in outs), (out_kin, cfo)
+    assert int(first_dev[0]) == F                                           # (read, never written)
+
+
 # ---- frames already cut ------------------------------------------------------------------------------------------------------------
 def frame_links_of(shape, n_links, frames):
     """link i's frames: cut back to back from its capture at a start up to W samples off a true one"""
