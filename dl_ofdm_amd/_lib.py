@@ -170,6 +170,14 @@ class ClassicalReceiveArgs(C.Structure):
                                         "y_freq", "noise")]
 
 
+class ClassicalLink(C.Structure):
+    """dccn_classical_link"""
+    _fields_ = [(n, c_int) for n in ("nbits", "m", "mode", "win")] + \
+               [(n, c_float) for n in ("noise_var", "pv_re", "pv_im")] + \
+               [(n, c_void_p) for n in ("dft", "w", "pil", "dat", "empty", "table", "labels", "x", "packed", "llr", "chest",
+                                        "y_freq", "noise")]
+
+
 METRICS_BYTES = C.sizeof(Metrics)
 ADAM_STATE_BYTES = C.sizeof(AdamState)
 
@@ -244,6 +252,7 @@ SIGNATURES = {
     "dccn_classical_detect": (_i, [_vp] * 8 + [_i] * 7 + [_vp, _sz, _vp]),
     "dccn_classical_receive_supported": (_i, [_i] * 7),
     "dccn_classical_receive": (_i, [POINTER(ClassicalReceiveArgs), _vp]),
+    "dccn_classical_receive_grouped": (_i, [_i, POINTER(ClassicalLink)] + [_i] * 7 + [_vp]),
     "dccn_set_tuning": (_i, [_i, _i]),
     "dccn_get_tuning": (_i, [_i]),
     "dccn_dense_tail_supported": (_i, [_i, _i, _i, _i]),

@@ -10,6 +10,9 @@ a fallback where the equaliser chain floors or was never trained, and the in-pro
 :class:`ClassicalRxReceiver` takes the front-end arguments of :class:`~dl_ofdm_amd.receive.RxReceiver` with the same meanings,
 refusals and launch counts (the front end is that class's own code): the alignment / capture-cut stage writes whole symbols
 straight into ``self.x`` and the classical launch stands where ``dccn_rx_receive_step`` stands.
+
+:class:`ClassicalReceiveGroup` carries up to ``dccn_chain_group_max()`` links of one grid through ONE classical launch
+(``dccn_classical_receive_grouped``), behind the grouped front end :class:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup` uses.
 """
 from __future__ import annotations
 
@@ -21,7 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import ClassicalReceiveArgs, check
-from .receive import ReceiveResult, _FrontEnd, row_bytes
+from .receive import ReceiveResult, _FrontEnd, _GroupFrontEnd, row_bytes
 
 METHODS = {"ALMMSE": 2, "LS-Spline": 0, "LS-Linear": 0}      # -> dccn_classical_receive's mode
 
@@ -135,3 +138,115 @@ class ClassicalRxReceiver(_FrontEnd):
         :meth:`RxReceiver.receive_capture` takes it (acquisition, the cut at each frame's estimated start, per-frame or pooled
         carrier offset, offsets beyond half a spacing, int16 captures), with the same refusals and launch counts."""
         return self._detect(*self._stage_capture(cap, first, stride, sync, cfo, acquire, lo, cfo_scope, cfo_span, scale))
+
+
+GRID_FIELDS = ("S", "K", "CP", "P", "D", "E")                 # what dccn_classical_receive_grouped takes once for every link
+
+
+class _HostGrid:
+    """the grid a link's flags give, before any device work (what :class:`ClassicalRxReceiver` will find for them)"""
+
+    def __init__(self, FLAGS):
+        from . import ofdm
+        o = ofdm.ofdm_tx(FLAGS)
+        self.S, self.K, self.CP = int(o.nSymbol), int(o.K), int(o.CP)
+        self.P, self.D, self.E = len(np.asarray(o.pilotSc)), len(np.asarray(o.dataSc)), len(o.guardSc)
+
+
+def _same_grid(links) -> None:
+    """the links of a group share the call's shape; the first field that differs is named"""
+    for f in GRID_FIELDS:
+        vals = [getattr(l, f) for l in links]
+        if any(v != vals[0] for v in vals):
+            raise ValueError("ClassicalReceiveGroup: every link must have the same %s (got %s); S, K, CP, P, D and E are the "
+                             "call's, not a link's" % (f, vals))
+
+
+class ClassicalReceiveGroup(_GroupFrontEnd):
+    """Up to ``dccn_chain_group_max()`` links of one grid ``(S, K, CP, P, D, E)`` and any mix of modulations, methods, window
+    positions and noise sources whose classical detectors share ONE launch (``dccn_classical_receive_grouped``): a host that
+    serves several links issues one call per round of frames.  Link i's results are bit for bit what ``.links[i]`` (a
+    :class:`ClassicalRxReceiver`, usable on its own) returns for it alone.
+
+        group = ClassicalReceiveGroup([flags_bpsk, flags_16qam], batch=73, methods=["LS-Spline", "ALMMSE"], want_llr=True)
+        results = group.receive([frames_bpsk, frames_16qam])           # one ReceiveResult per link
+        results = group.receive(device_frames, sync=3, cfo=True)       # + one alignment launch for all links
+        results = group.receive_capture(captures, acquire=16, los=3)   # acquisition (3 launches) + cut (1) for all links
+
+    ``methods`` / ``advances`` / ``noise_vars`` / ``interps``: one value for every link, or a list with one entry per link."""
+
+    _solo = "ClassicalRxReceiver.receive_capture"
+
+    def __init__(self, flags_list, batch: int, methods="ALMMSE", advances=0, noise_vars=None, interps=None,
+                 want_llr: bool = False, device="cuda"):
+        from .sync import _per_link
+        n = len(flags_list)
+        self.lib = _lib.load()
+        gmax = int(self.lib.dccn_chain_group_max())
+        if not (1 <= n <= gmax):
+            raise ValueError("ClassicalReceiveGroup: 1..%d links per group" % gmax)
+        # (an interpolation matrix is array-like itself: only a list or tuple of them is one entry per link)
+        per = {k: _per_link(v, n, "ClassicalReceiveGroup(%s)" % k)
+               for k, v in (("methods", methods), ("advances", advances), ("noise_vars", noise_vars), ("interps", interps))}
+        _same_grid([_HostGrid(F) for F in flags_list])         # (before any engine is built: the refusal needs no device)
+        self.batch = int(batch)
+        self.links = [ClassicalRxReceiver(F, self.batch, method=per["methods"][i], advance=per["advances"][i],
+                                          noise_var=per["noise_vars"][i], interp=per["interps"][i], want_llr=want_llr, device=device)
+                      for i, F in enumerate(flags_list)]
+        self.device = self.links[0].device
+        self._stages = {}                                      # the group's resident front-end stages (sync.py: the *Group classes)
+        self._table, self._table_key = (_lib.ClassicalLink * n)(), None
+
+    def _frame_shape(self):
+        l = self.links[0]
+        return l.S, l.K, l.CP
+
+    def _link_x(self) -> list:
+        return [l.x for l in self.links]
+
+    def _link_pilots(self) -> list:
+        return [l.pilot_sc for l in self.links]
+
+    def want_y_freq(self) -> list:
+        """from now on the launch also writes every link's frequency-domain frames (``.links[i].y_freq``)"""
+        return [l.want_y_freq() for l in self.links]
+
+    def _detect(self, offsets, ests, firsts=None, acq_cfo=None) -> list:
+        """the one classical launch on what every link's ``x`` holds.  The table restates the links' own argument blocks, and is
+        rebuilt only when one of them has changed (``links[i].want_y_freq()`` since the last call, say)"""
+        key = b"".join(bytes(l.args) for l in self.links)
+        if key != self._table_key:
+            for i, l in enumerate(self.links):
+                a = l.args
+                self._table[i] = _lib.ClassicalLink(a.nbits, a.m, a.mode, a.win, a.noise_var, a.pv_re, a.pv_im, a.dft, a.w, a.pil,
+                                                    a.dat, a.empty, a.table, a.labels, a.x, a.packed, a.llr, a.chest, a.y_freq, a.noise)
+            self._table_key = key
+        l = self.links[0]
+        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        check(self.lib.dccn_classical_receive_grouped(len(self.links), self._table, self.batch, l.S, l.K, l.CP, l.P, l.D, l.E, st),
+              "dccn_classical_receive_grouped")
+        none = [None] * len(self.links)
+        firsts, acq_cfo = firsts or none, acq_cfo or none
+        return [ReceiveResult(l.packed, l.llr, None, l.D, l.nbits, offsets[i], ests[i], firsts[i], acq_cfo[i])
+                for i, l in enumerate(self.links)]
+
+    def receive(self, xs, sync: int = 0, cfo: bool = False) -> list:
+        """``xs[i]``: link i's frames ``[batch, S, K + CP, 2]`` (host array or device tensor; ``None``: what ``.links[i].x``
+        holds): the per-link copies, then ONE classical launch.  ``sync = W > 0`` / ``cfo=True``: as
+        :meth:`ClassicalRxReceiver.receive` per link -- every ``xs[i]`` is a device tensor, and ONE alignment launch for all links
+        (:class:`~dl_ofdm_amd.sync.FrameSyncGroup`) writes each link's frames into its ``x`` in place of the copies.  One
+        :class:`~dl_ofdm_amd.receive.ReceiveResult` per link (``prob`` is ``None``; the links' resident buffers)."""
+        if len(xs) != len(self.links):
+            raise ValueError("one batch of frames per link")
+        return self._detect(*self._stage_frames_group(xs, sync, cfo))
+
+    def receive_capture(self, caps, firsts=None, strides=None, sync: int = 3, cfo: bool = False, acquire: int = 0, los=0,
+                        cfo_scope: str = "frame", cfo_span: int = 0) -> list:
+        """One round on ``batch`` frames per link that still sit inside contiguous captures, with the meanings and refusals of
+        :meth:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup.receive_capture`: acquisition for all links (``firsts=None,
+        acquire=J``: three launches, each link's own ``pilotSc``), the cut for all links (one launch; three with
+        ``cfo_scope="capture"``), then the ONE classical launch.  ``firsts[i]``: an integer, or a device ``int64`` tensor of one
+        element with ``los[i]``; the two mix.  ``cfo_span > 0`` and int16 captures are refused (:class:`DccnError`): the
+        grouped front end is float32-only and has no wide variant -- those go through ``.links[i].receive_capture``."""
+        self._refuse_cfo_span(cfo_span)
+        return self._detect(*self._stage_captures_group(caps, firsts, strides, sync, cfo, acquire, los, cfo_scope))

@@ -50,13 +50,21 @@ constexpr int kClsRxPad = 4;               // floats between the rows of the win
 constexpr float kClsRxTinyNoise = 1e-20f;
 constexpr size_t kClsRxMaxLds = 48 * 1024;
 
-struct ClsRxParams {
-    int frames, S, K, CP, P, D, E, win, mode, RB, fpb;
+// What a launch's links share, and what one link is (the solo launch has one; dccn_classical_receive_grouped a table of them).
+struct ClsRxShape {
+    int frames, S, K, CP, P, D, E, fpb;
+};
+struct ClsRxLink {
+    int nbits, win, mode, RB;                                      // RB: bytes of a packed row, ceil(D nbits / 8)
     float noise_var;
     float2 pv;
     const float* dft; const float* w; const int* pil; const int* dat; const int* empty;
     const float2* table; const int* labels; const float* x;
     unsigned char* packed; float* llr; float2* chest; float2* y_freq; float* noise;
+};
+struct ClsRxParams {
+    ClsRxLink l;
+    ClsRxShape s;
 };
 
 // floats of dynamic LDS (host and device agree on the layout through this and the kernel's carving)
@@ -67,28 +75,29 @@ static inline size_t clsrx_lds_floats(int S, int K, int P) {
 
 typedef float clsrx_f32x4 __attribute__((ext_vector_type(4)));
 
+// One tile of one link: block blockIdx.x of the link's ceil(frames / fpb) blocks, whatever else the grid carries.
 template <int NB>
-__global__ __launch_bounds__(kClsRxThreads) void classical_receive_kernel(const ClsRxParams p) {
+__device__ __forceinline__ void classical_receive_body(const ClsRxLink& p, const ClsRxShape& sh) {
     extern __shared__ __align__(16) float clsrx_smem[];
     constexpr int M = 1 << NB;
-    const int K = p.K, S = p.S, K2 = 2 * K, SK = S * K, ldx = K2 + kClsRxPad, P = p.P;
+    const int K = sh.K, S = sh.S, K2 = 2 * K, SK = S * K, ldx = K2 + kClsRxPad, P = sh.P;
     float* xs = clsrx_smem;                                        // [16][ldx]   FFT windows (dead after the DFT)
     float2* G = reinterpret_cast<float2*>(clsrx_smem);            // [fpb][SK]   Gls, then G
     float* Yf = clsrx_smem + kClsRxRows * ldx;                    // [16][2K]
     float2* Y = reinterpret_cast<float2*>(Yf);                    // [fpb][SK]: row fi S + s of the tile is symbol s of frame fi
     float2* gp = reinterpret_cast<float2*>(Yf + kClsRxRows * K2); // [fpb][P]
-    float* s_nv = reinterpret_cast<float*>(gp + p.fpb * P);       // [16]
+    float* s_nv = reinterpret_cast<float*>(gp + sh.fpb * P);       // [16]
     int* s_lab = reinterpret_cast<int*>(s_nv + 16);               // [16]  labels of point q, bit b at position NB-1-b
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int c = lane & 15, kq = lane >> 4;
-    const long long f0 = (long long)blockIdx.x * p.fpb;
-    const int nf = (int)min((long long)p.fpb, (long long)p.frames - f0);
+    const long long f0 = (long long)blockIdx.x * sh.fpb;
+    const int nf = (int)min((long long)sh.fpb, (long long)sh.frames - f0);
     const int rows = nf * S;
     const int last_cell = SK - 1;
 
     // ---- the frames' FFT windows -> LDS (rows past the block's frames are zero) ----
     {
-        const int n_sc = K + p.CP;
+        const int n_sc = K + sh.CP;
         const bool odd = (p.win & 1) != 0;
         const int cpr = K2 / 4 + (odd ? 1 : 0);                    // chunks per row
         const float* src0 = p.x + ((size_t)f0 * S * n_sc + p.win) * 2;
@@ -164,11 +173,11 @@ __global__ __launch_bounds__(kClsRxThreads) void classical_receive_kernel(const 
         float nv = p.noise_var;
         if (!(nv > 0.f)) {
             float a = 0.f;
-            for (int e = lane; e < p.E; e += 64) {
+            for (int e = lane; e < sh.E; e += 64) {
                 const float2 y = Y[fi * SK + min(max(p.empty[e], 0), last_cell)];
                 a += y.x * y.x + y.y * y.y;
             }
-            nv = fmaxf(wave_sum(a) / (float)p.E, kClsRxTinyNoise);
+            nv = fmaxf(wave_sum(a) / (float)sh.E, kClsRxTinyNoise);
         }
         if (lane == 0) {
             s_nv[fi] = nv;
@@ -225,7 +234,7 @@ __global__ __launch_bounds__(kClsRxThreads) void classical_receive_kernel(const 
         for (int i = tid; i < nf * SK; i += kClsRxThreads) p.chest[(size_t)f0 * SK + i] = G[i];
 
     // ---- decision: a lane per data cell, eight lanes = NB whole bytes of a row (decide.h) ----
-    const int gpr = (p.D + 7) / 8;
+    const int gpr = (sh.D + 7) / 8;
     const int total = nf * gpr * 8;
     for (int base = 0; base < total; base += kClsRxThreads) {
         const int t = base + tid;
@@ -233,7 +242,7 @@ __global__ __launch_bounds__(kClsRxThreads) void classical_receive_kernel(const 
         const int fi = grp_all / gpr, grp = grp_all - fi * gpr;
         const int d = grp * 8 + ci;
         const bool in_frame = fi < nf;
-        const bool valid = in_frame && d < p.D;
+        const bool valid = in_frame && d < sh.D;
         const int fiv = valid ? fi : 0;
         const int cell = valid ? min(max(p.dat[d], 0), last_cell) : 0;
         const float2 y = Y[fiv * SK + cell], g = G[fiv * SK + cell];
@@ -253,7 +262,7 @@ __global__ __launch_bounds__(kClsRxThreads) void classical_receive_kernel(const 
         const unsigned hard = (unsigned)s_lab[best];
         if (p.llr != nullptr && valid) {
             const float scale = gd / s_nv[fiv];
-            float* dst = p.llr + ((size_t)(f0 + fi) * p.D + d) * NB;
+            float* dst = p.llr + ((size_t)(f0 + fi) * sh.D + d) * NB;
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
                 float m0 = 3.0e38f, m1 = 3.0e38f;
@@ -273,6 +282,30 @@ __global__ __launch_bounds__(kClsRxThreads) void classical_receive_kernel(const 
             const unsigned word[2] = {__builtin_bswap32(v << (32 - 8 * NB)), 0u};
             store_row_bytes(p.packed + (size_t)(f0 + fi) * p.RB + b0, word, n);
         }
+    }
+}
+
+template <int NB>
+__global__ __launch_bounds__(kClsRxThreads) void classical_receive_kernel(const ClsRxParams p) {
+    classical_receive_body<NB>(p.l, p.s);
+}
+
+// Several links per launch (dccn_classical_receive_grouped): each link has its own tables, frames and outputs -- and its own
+// modulation; the shape is the call's.  The table travels by value in the kernel arguments and is indexed by blockIdx.y, a
+// block-uniform value (scalar loads, as frame_sync.h's link table is read); blockIdx.x stays what the body takes it for, so a
+// link's blocks are the solo launch's and no tile holds frames of two links.  The switch on the link's nbits is block-uniform:
+// every wave of a block runs one NB body, the solo kernel's, with its expressions and orders.
+struct ClsRxGroupArgs {
+    ClsRxLink link[kMaxChains];
+    ClsRxShape s;
+};
+static __global__ __launch_bounds__(kClsRxThreads) void classical_receive_grouped_kernel(const ClsRxGroupArgs g) {
+    const ClsRxLink& l = g.link[blockIdx.y];
+    switch (l.nbits) {
+        case 1: classical_receive_body<1>(l, g.s); break;
+        case 2: classical_receive_body<2>(l, g.s); break;
+        case 3: classical_receive_body<3>(l, g.s); break;
+        default: classical_receive_body<4>(l, g.s); break;
     }
 }
 

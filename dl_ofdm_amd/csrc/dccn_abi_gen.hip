@@ -1,5 +1,6 @@
 // libdccn.so -- device-side generator, classical receivers, in-graph AWGN branch (see abi_impl.h for how the library is cut into units)
 #include "abi_impl.h"
+#include "link_group.h"
 
 using namespace dccn;
 
@@ -170,10 +171,6 @@ struct GenApplySyncPlan {
     unsigned blocks;
     size_t lds;
 };
-static bool byte_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a0 < b0 + nb && b0 < a0 + na;
-}
 static int gen_apply_sync_plan(const dccn_gen_static* g, int W, int out_kin, float* x_out, int32_t* offset, float* H_inout, int h_rep,
                                float* noise_power, GenApplySyncPlan* plan) {
     if (!gen_static_ok(g) || !frame_sync_shape_ok(g->S, g->K, g->CP, W)) return DCCN_ERR_INVALID_ARG;
@@ -183,7 +180,7 @@ static int gen_apply_sync_plan(const dccn_gen_static* g, int W, int out_kin, flo
     if (H_inout && ((h_rep != 1 && h_rep != g->S) || reinterpret_cast<uintptr_t>(H_inout) % 8 != 0)) return DCCN_ERR_INVALID_ARG;
     const int T = g->S * (g->K + g->CP);
     const size_t in_bytes = (size_t)g->frames * T * 8, out_bytes = (size_t)g->frames * g->S * out_kin * 8;
-    if (byte_ranges_overlap(g->y, in_bytes, x_out, out_bytes) || byte_ranges_overlap(g->noise, in_bytes, x_out, out_bytes))
+    if (ranges_overlap(g->y, in_bytes, x_out, out_bytes) || ranges_overlap(g->noise, in_bytes, x_out, out_bytes))
         return DCCN_ERR_INVALID_ARG;
     const int np = dccn_gen_static_partials(g->frames);
     const bool want_np = noise_power && g->noise_partial;
@@ -388,30 +385,40 @@ int dccn_classical_receive_supported(int S, int K, int CP, int P, int D, int E, 
     return clsrx_lds_floats(S, K, P) * sizeof(float) <= kClsRxMaxLds ? 1 : 0;
 }
 static bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+// One link of a classical receive call, judged by the rules dccn.h states -> its entry of the launch's table and the shape.  Both
+// entries judge a link here, so a link the grouped call accepts is one the solo call accepts.
+static int clsrx_link_plan(const dccn_classical_link& a, int frames, int S, int K, int CP, int P, int D, int E, ClsRxLink* l,
+                           ClsRxShape* sh) {
+    if (!dccn_classical_receive_supported(S, K, CP, P, D, E, a.nbits)) return DCCN_ERR_INVALID_ARG;
+    if (frames < 1 || frames > (1 << 24) || a.win < 0 || a.win > CP || a.m != (1 << a.nbits)) return DCCN_ERR_INVALID_ARG;
+    if (a.mode != CE_LS && a.mode != CE_ALMMSE) return DCCN_ERR_INVALID_ARG;
+    if (!isfinite(a.noise_var) || a.noise_var < 0.f) return DCCN_ERR_INVALID_ARG;
+    const float pd = a.pv_re * a.pv_re + a.pv_im * a.pv_im;
+    if (!isfinite(pd) || !(pd > 0.f)) return DCCN_ERR_INVALID_ARG;
+    if (!a.dft || !a.w || !a.pil || !a.dat || !a.empty || !a.table || !a.labels || !a.x || !a.packed) return DCCN_ERR_INVALID_ARG;
+    if (!aligned16(a.x) || !aligned_to(a.dft, 4) || !aligned_to(a.w, 4) || !aligned_to(a.pil, 4) || !aligned_to(a.dat, 4) ||
+        !aligned_to(a.empty, 4) || !aligned_to(a.table, 8) || !aligned_to(a.labels, 4) || !aligned_to(a.llr, 4) ||
+        !aligned_to(a.chest, 8) || !aligned_to(a.y_freq, 8) || !aligned_to(a.noise, 4))
+        return DCCN_ERR_INVALID_ARG;
+    *sh = ClsRxShape{frames, S, K, CP, P, D, E, kClsRxRows / S};
+    *l = ClsRxLink{a.nbits, a.win, a.mode, (D * a.nbits + 7) / 8, a.noise_var, make_float2(a.pv_re, a.pv_im), a.dft, a.w, a.pil,
+                   a.dat, a.empty, (const float2*)a.table, a.labels, a.x, a.packed, a.llr, (float2*)a.chest, (float2*)a.y_freq,
+                   a.noise};
+    return DCCN_OK;
+}
+// the launch geometry of a shape: a link's tiles on x (the grouped launch: the links on y)
+static dim3 clsrx_grid(const ClsRxShape& sh, int n_links) { return dim3((unsigned)ceil_div(sh.frames, sh.fpb), (unsigned)n_links); }
+static size_t clsrx_lds(const ClsRxShape& sh) { return clsrx_lds_floats(sh.S, sh.K, sh.P) * sizeof(float); }
+
 int dccn_classical_receive(const dccn_classical_receive_args* a, dccn_stream_t stream) {
     if (!a) return DCCN_ERR_INVALID_ARG;
-    if (!dccn_classical_receive_supported(a->S, a->K, a->CP, a->P, a->D, a->E, a->nbits)) return DCCN_ERR_INVALID_ARG;
-    if (a->frames < 1 || a->frames > (1 << 24) || a->win < 0 || a->win > a->CP || a->m != (1 << a->nbits)) return DCCN_ERR_INVALID_ARG;
-    if (a->mode != CE_LS && a->mode != CE_ALMMSE) return DCCN_ERR_INVALID_ARG;
-    if (!isfinite(a->noise_var) || a->noise_var < 0.f) return DCCN_ERR_INVALID_ARG;
-    const float pd = a->pv_re * a->pv_re + a->pv_im * a->pv_im;
-    if (!isfinite(pd) || !(pd > 0.f)) return DCCN_ERR_INVALID_ARG;
-    if (!a->dft || !a->w || !a->pil || !a->dat || !a->empty || !a->table || !a->labels || !a->x || !a->packed)
-        return DCCN_ERR_INVALID_ARG;
-    if (!aligned16(a->x) || !aligned_to(a->dft, 4) || !aligned_to(a->w, 4) || !aligned_to(a->pil, 4) || !aligned_to(a->dat, 4) ||
-        !aligned_to(a->empty, 4) || !aligned_to(a->table, 8) || !aligned_to(a->labels, 4) || !aligned_to(a->llr, 4) ||
-        !aligned_to(a->chest, 8) || !aligned_to(a->y_freq, 8) || !aligned_to(a->noise, 4))
-        return DCCN_ERR_INVALID_ARG;
-    DCCN_NO_CHAINS();
+    const dccn_classical_link link{a->nbits, a->m, a->mode, a->win, a->noise_var, a->pv_re, a->pv_im, a->dft, a->w, a->pil, a->dat,
+                                   a->empty, a->table, a->labels, a->x, a->packed, a->llr, a->chest, a->y_freq, a->noise};
     ClsRxParams p;
-    p.frames = a->frames; p.S = a->S; p.K = a->K; p.CP = a->CP; p.P = a->P; p.D = a->D; p.E = a->E; p.win = a->win;
-    p.mode = a->mode; p.RB = (a->D * a->nbits + 7) / 8; p.fpb = kClsRxRows / a->S;
-    p.noise_var = a->noise_var; p.pv = make_float2(a->pv_re, a->pv_im);
-    p.dft = a->dft; p.w = a->w; p.pil = a->pil; p.dat = a->dat; p.empty = a->empty;
-    p.table = (const float2*)a->table; p.labels = a->labels; p.x = a->x;
-    p.packed = a->packed; p.llr = a->llr; p.chest = (float2*)a->chest; p.y_freq = (float2*)a->y_freq; p.noise = a->noise;
-    const size_t lds = clsrx_lds_floats(a->S, a->K, a->P) * sizeof(float);
-    const dim3 grid((unsigned)ceil_div(a->frames, p.fpb)), block(kClsRxThreads);
+    DCCN_TRY(clsrx_link_plan(link, a->frames, a->S, a->K, a->CP, a->P, a->D, a->E, &p.l, &p.s));
+    DCCN_NO_CHAINS();
+    const size_t lds = clsrx_lds(p.s);
+    const dim3 grid = clsrx_grid(p.s, 1), block(kClsRxThreads);
     hipStream_t s = (hipStream_t)stream;
     switch (a->nbits) {
         case 1: hipLaunchKernelGGL(classical_receive_kernel<1>, grid, block, lds, s, p); break;
@@ -419,6 +426,36 @@ int dccn_classical_receive(const dccn_classical_receive_args* a, dccn_stream_t s
         case 3: hipLaunchKernelGGL(classical_receive_kernel<3>, grid, block, lds, s, p); break;
         default: hipLaunchKernelGGL(classical_receive_kernel<4>, grid, block, lds, s, p); break;
     }
+    DCCN_LAUNCH_CHECK();
+    return DCCN_OK;
+}
+
+// Several links in ONE launch: everything decided before it, so a refused call launches nothing.
+static_assert(sizeof(dccn_classical_link) == 136, "dccn.h states the size; dl_ofdm_amd/_lib.py mirrors the layout");
+int dccn_classical_receive_grouped(int n_links, const dccn_classical_link* links, int frames, int S, int K, int CP, int P, int D,
+                                   int E, dccn_stream_t stream) {
+    ClsRxGroupArgs g{};
+    DCCN_TRY(group_plan(n_links, links, [&](int i, const dccn_classical_link& a, LinkRanges* r) -> int {
+        DCCN_TRY(clsrx_link_plan(a, frames, S, K, CP, P, D, E, &g.link[i], &g.s));
+        const size_t n = (size_t)frames, SK = (size_t)S * K;
+        r->out(a.packed, n * g.link[i].RB);
+        r->out(a.llr, n * D * a.nbits * 4);
+        r->out(a.chest, n * SK * 8);
+        r->out(a.y_freq, n * SK * 8);
+        r->out(a.noise, n * 4);
+        r->in(a.x, n * S * (K + CP) * 8);
+        r->in(a.dft, (size_t)4 * K * K * 4);
+        r->in(a.w, (size_t)P * SK * 4);
+        r->in(a.pil, (size_t)P * 4);
+        r->in(a.dat, (size_t)D * 4);
+        r->in(a.empty, (size_t)E * 4);
+        r->in(a.table, (size_t)a.m * 8);
+        r->in(a.labels, (size_t)a.m * a.nbits * 4);
+        return DCCN_OK;
+    }, &dccn_classical_link::llr, &dccn_classical_link::chest, &dccn_classical_link::y_freq, &dccn_classical_link::noise));
+    DCCN_NO_CHAINS();                         // (the link table is the call's own, not the group's chain table)
+    hipLaunchKernelGGL(classical_receive_grouped_kernel, clsrx_grid(g.s, n_links), dim3(kClsRxThreads), clsrx_lds(g.s),
+                       (hipStream_t)stream, g);
     DCCN_LAUNCH_CHECK();
     return DCCN_OK;
 }

@@ -26,6 +26,7 @@ from . import _lib, epochs, ofdm
 from . import receiver_mp as H
 from ._lib import check
 from .arena import ChainArena, check_same_layout
+from .receive import ReceiveResult, _GroupFrontEnd
 
 
 def _ptr_array(structs):
@@ -257,7 +258,7 @@ class _ReceiveChain:
                                self.prob.data_ptr() if want_prob else None)
 
 
-class ChainReceiveGroup:
+class ChainReceiveGroup(_GroupFrontEnd):
     """Up to ``dccn_chain_group_max()`` (equaliser -> frozen receiver) chains of one shape and any mix of modulations whose
     receive steps share ONE launch sequence (``dccn_eq_receive_step_grouped``): a host that serves several links, each with its
     own trained chain, issues one call per round of frames.  Chain i's results are bit for bit what
@@ -270,6 +271,8 @@ class ChainReceiveGroup:
         results = group.receive_capture(captures, acquire=16, los=3)   # acquisition (3 launches) + cut (1) for all chains
 
     ``.chains[i].pl.out_eq`` / ``.chest`` / ``.snr_db`` hold what the chain's ``eval_step`` writes for the same frames."""
+
+    _solo = "EqualizerTrainer.receive_capture"
 
     def __init__(self, flags_list: Sequence, rx_params_list: Sequence[Dict[str, np.ndarray]], batch: int, device="cuda",
                  want_llr: bool = False, want_prob: bool = False):
@@ -320,15 +323,11 @@ class ChainReceiveGroup:
         c = self.chains[0]
         return int(c.F.nsymbol), int(c.o.K), int(c.o.CP)
 
-    def _stage(self, kind: str, cls, W: int, cfo: bool, **scope):
-        """the resident front-end stage of this group: FrameSyncGroup / CaptureSyncGroup, writing the chains' ``pl.x``
-        (``scope``: ``cfo_scope="capture"`` of a pooled CaptureSyncGroup)"""
-        key = (kind, int(W), bool(cfo)) + tuple(scope.values())
-        if key not in self._stages:
-            S, K, CP = self._frame_shape()
-            self._stages[key] = cls(S, K, CP, int(W), self.batch, len(self.chains), self.device, want_metric=False, cfo=bool(cfo),
-                                    **scope)
-        return self._stages[key]
+    def _link_x(self) -> list:
+        return [c.pl.x for c in self.chains]
+
+    def _link_pilots(self) -> list:
+        return [c.o.pilotSc for c in self.chains]
 
     def receive(self, xs: Sequence, want_llr: Optional[bool] = None, want_prob: Optional[bool] = None, sync: int = 0,
                 cfo: bool = False) -> list:
@@ -342,24 +341,10 @@ class ChainReceiveGroup:
         (:class:`~dl_ofdm_amd.sync.FrameSyncGroup`) writes each chain's rotated frames into its ``pl.x`` in place of the
         per-chain copies; ``result.offset``.  ``cfo=True`` (needs ``sync > 0``): that launch also takes each frame's
         carrier-frequency offset out; ``result.cfo``."""
-        from .receive import ReceiveResult
-        from .sync import FrameSyncGroup
         if len(xs) != len(self.chains):
             raise ValueError("one batch of frames per chain")
         want_llr, want_prob = self._wants(want_llr, want_prob)
-        if cfo and not sync:
-            raise _lib.DccnError("receive(cfo=True) needs sync = W > 0: the offset is read off the timing correlation")
-        offsets = ests = [None] * len(self.chains)
-        if sync:
-            if not all(isinstance(x, torch.Tensor) and x.device.type == "cuda" for x in xs):
-                raise _lib.DccnError("receive(sync=W) takes one device tensor [batch, S, K + CP, 2] per chain")
-            fs = self._stage("frames", FrameSyncGroup, sync, cfo)
-            _, offsets = fs.run(xs, outs=[c.pl.x for c in self.chains])
-            ests = fs.cfo if cfo else ests
-        else:
-            for c, x in zip(self.chains, xs):
-                if x is not None:
-                    c.pl.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(c.pl.x.shape), non_blocking=True)
+        offsets, ests = self._stage_frames_group(xs, sync, cfo)
         self._step(want_llr, want_prob)
         return [ReceiveResult(c.packed, c.llr if want_llr else None, c.prob if want_prob else None, c.D, c.nbits, offsets[i], ests[i])
                 for i, c in enumerate(self.chains)]
@@ -383,45 +368,10 @@ class ChainReceiveGroup:
 
         ``cfo_span > 0`` is refused (:class:`DccnError`): the grouped link tables carry no integer offset, so carrier offsets
         beyond half a subcarrier spacing go through the solo calls (``EqualizerTrainer.receive_capture(..., cfo_span=M)``)."""
-        from .receive import ReceiveResult
-        from .sync import CaptureAcquireGroup, CaptureSyncGroup, _per_link, check_cfo_scope
-        if int(cfo_span) != 0:
-            raise _lib.DccnError("ChainReceiveGroup.receive_capture: cfo_span > 0 is not offered for groups (the grouped entries "
-                                 "have no wide variant); use EqualizerTrainer.receive_capture(..., cfo_span=M) per chain")
-        pooled = check_cfo_scope(cfo, cfo_scope)
-        n = len(self.chains)
-        if len(caps) != n:
-            raise ValueError("one capture per chain")
+        self._refuse_cfo_span(cfo_span)
         want_llr, want_prob = self._wants(want_llr, want_prob)
-        W = int(sync)
-        if W <= 0:
-            raise _lib.DccnError("receive_capture needs sync = W > 0")
-        if not all(isinstance(c, torch.Tensor) and c.device.type == "cuda" and c.dim() == 2 for c in caps):
-            raise _lib.DccnError("receive_capture takes one device tensor [n, 2] per chain")
-        los = _per_link(los, n, "receive_capture(los)")
-        strides = _per_link(strides, n, "receive_capture(strides)")
-        acq_cfo = [None] * n
-        if firsts is not None:
-            if acquire:
-                raise _lib.DccnError("receive_capture: give `firsts` or `acquire`, not both")
-            if not isinstance(firsts, (list, tuple)) or len(firsts) != n:
-                raise ValueError("receive_capture(firsts): one entry per chain (%d)" % n)
-            firsts = list(firsts)
-        else:
-            J = int(acquire)
-            if J <= 0:
-                raise _lib.DccnError("receive_capture(firsts=None) needs acquire = J > 0, the number of frames acquisition may use")
-            key = ("acquire", J)
-            if key not in self._stages:
-                S, K, CP = self._frame_shape()
-                self._stages[key] = CaptureAcquireGroup(S, K, CP, [np.asarray(c.o.pilotSc) for c in self.chains], J, n, self.device)
-            acq = self._stages[key]
-        cs = self._stage("capture", CaptureSyncGroup, W, cfo, **({"cfo_scope": cfo_scope} if pooled else {}))
-        if firsts is None:
-            firsts = acq.run(caps, los)
-            acq_cfo = acq.cfo
-        _, offsets = cs.run(caps, firsts, strides, outs=[c.pl.x for c in self.chains], los=los)
+        offsets, cfos, firsts, acq_cfo = self._stage_captures_group(caps, firsts, strides, sync, cfo, acquire, los, cfo_scope)
         self._step(want_llr, want_prob)
         return [ReceiveResult(c.packed, c.llr if want_llr else None, c.prob if want_prob else None, c.D, c.nbits, offsets[i],
-                              cs.cfo[i] if cfo else None, firsts[i] if isinstance(firsts[i], torch.Tensor) else None, acq_cfo[i])
+                              cfos[i], firsts[i], acq_cfo[i])
                 for i, c in enumerate(self.chains)]

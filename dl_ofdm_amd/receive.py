@@ -165,6 +165,104 @@ class _FrontEnd:
         return offset, cs.cfo, (first if isinstance(first, torch.Tensor) else None), est0, est_int
 
 
+class _GroupFrontEnd:
+    """What the group engines share (:class:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup`,
+    :class:`~dl_ofdm_amd.classical_receive.ClassicalReceiveGroup`): the stages in front of a grouped detector, each ONE launch
+    sequence for all links (sync.py: the ``*Group`` classes), writing every link's resident ``x``.  The engine provides ``lib``,
+    ``device``, ``batch``, ``_stages`` (a dict), ``_solo`` (a class attribute: the call that serves one link, for the refusals) and
+    the three below."""
+
+    def _frame_shape(self):         # (S, K, CP) of every link
+        raise NotImplementedError
+
+    def _link_x(self) -> list:      # the links' resident frame buffers, [batch, S, K + CP, 2] each
+        raise NotImplementedError
+
+    def _link_pilots(self) -> list:  # the links' pilot cells (``ofdm_tx.pilotSc``)
+        raise NotImplementedError
+
+    def _stage(self, kind: str, cls, W: int, cfo: bool, **scope):
+        """the resident front-end stage of this group: FrameSyncGroup / CaptureSyncGroup, writing the links' ``x``
+        (``scope``: ``cfo_scope="capture"`` of a pooled CaptureSyncGroup)"""
+        key = (kind, int(W), bool(cfo)) + tuple(scope.values())
+        if key not in self._stages:
+            S, K, CP = self._frame_shape()
+            self._stages[key] = cls(S, K, CP, int(W), self.batch, len(self._link_x()), self.device, want_metric=False,
+                                    cfo=bool(cfo), **scope)
+        return self._stages[key]
+
+    def _stage_frames_group(self, xs, sync: int, cfo: bool):
+        """``receive``'s front end for every link: the per-link copies, or (``sync = W > 0``) one alignment launch ->
+        ``(offsets, cfo estimates)``, one entry per link (``None`` where the call has none)"""
+        from .sync import FrameSyncGroup
+        dests = self._link_x()
+        if cfo and not sync:
+            raise _lib.DccnError("receive(cfo=True) needs sync = W > 0: the offset is read off the timing correlation")
+        offsets = ests = [None] * len(dests)
+        if sync:
+            if not all(isinstance(x, torch.Tensor) and x.device.type == "cuda" for x in xs):
+                raise _lib.DccnError("receive(sync=W) takes one device tensor [batch, S, K + CP, 2] per link")
+            fs = self._stage("frames", FrameSyncGroup, sync, cfo)
+            _, offsets = fs.run(xs, outs=dests)
+            ests = fs.cfo if cfo else ests
+        else:
+            for dst, x in zip(dests, xs):
+                if x is not None:
+                    dst.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(dst.shape), non_blocking=True)
+        return offsets, ests
+
+    def _refuse_cfo_span(self, cfo_span) -> None:
+        """``receive_capture``'s first check (it needs nothing of the engine but its class)"""
+        if int(cfo_span) != 0:
+            raise _lib.DccnError("%s.receive_capture: cfo_span > 0 is not offered for groups (the grouped entries have no wide "
+                                 "variant); use %s(..., cfo_span=M) per link" % (type(self).__name__, self._solo))
+
+    def _stage_captures_group(self, caps, firsts, strides, sync, cfo, acquire, los, cfo_scope):
+        """``receive_capture``'s front end for every link: acquisition (``firsts=None``: three launches) and the cut (one launch,
+        three when pooled) -> ``(offsets, cfo estimates, firsts, acquired cfo)``, one entry per link as
+        :class:`ReceiveResult` takes them"""
+        from .sync import CaptureAcquireGroup, CaptureSyncGroup, _per_link, check_cfo_scope
+        name = type(self).__name__
+        pooled = check_cfo_scope(cfo, cfo_scope)
+        dests = self._link_x()
+        n = len(dests)
+        if len(caps) != n:
+            raise ValueError("one capture per link")
+        W = int(sync)
+        if W <= 0:
+            raise _lib.DccnError("receive_capture needs sync = W > 0")
+        if any(isinstance(c, torch.Tensor) and c.dtype == torch.int16 for c in caps):
+            raise _lib.DccnError("%s.receive_capture: int16 captures are not offered for groups (the grouped entries read float32 "
+                                 "captures only); use %s per link, or radio.sc16_to_float" % (name, self._solo))
+        if not all(isinstance(c, torch.Tensor) and c.device.type == "cuda" and c.dim() == 2 for c in caps):
+            raise _lib.DccnError("receive_capture takes one device tensor [n, 2] per link")
+        los = _per_link(los, n, "receive_capture(los)")
+        strides = _per_link(strides, n, "receive_capture(strides)")
+        acq_cfo = [None] * n
+        if firsts is not None:
+            if acquire:
+                raise _lib.DccnError("receive_capture: give `firsts` or `acquire`, not both")
+            if not isinstance(firsts, (list, tuple)) or len(firsts) != n:
+                raise ValueError("receive_capture(firsts): one entry per link (%d)" % n)
+            firsts = list(firsts)
+        else:
+            J = int(acquire)
+            if J <= 0:
+                raise _lib.DccnError("receive_capture(firsts=None) needs acquire = J > 0, the number of frames acquisition may use")
+            key = ("acquire", J)
+            if key not in self._stages:
+                S, K, CP = self._frame_shape()
+                self._stages[key] = CaptureAcquireGroup(S, K, CP, [np.asarray(sc) for sc in self._link_pilots()], J, n, self.device)
+            acq = self._stages[key]
+        cs = self._stage("capture", CaptureSyncGroup, W, cfo, **({"cfo_scope": cfo_scope} if pooled else {}))
+        if firsts is None:
+            firsts = acq.run(caps, los)
+            acq_cfo = acq.cfo
+        _, offsets = cs.run(caps, firsts, strides, outs=dests, los=los)
+        return (offsets, [cs.cfo[i] if cfo else None for i in range(n)],
+                [f if isinstance(f, torch.Tensor) else None for f in firsts], acq_cfo)
+
+
 class RxReceiver(_FrontEnd):
     """Fixed-shape receive engine of the basic receiver on one GPU: ``receive(x)`` -> :class:`ReceiveResult`.
 
@@ -428,8 +526,8 @@ def group_receive_capture(group, caps, firsts=None, strides=None, sync: int = 3,
 
 
 def __getattr__(name):
-    # ClassicalRxReceiver lives in classical_receive.py (which imports this module): exported here on first use
-    if name == "ClassicalRxReceiver":
-        from .classical_receive import ClassicalRxReceiver
-        return ClassicalRxReceiver
+    # the classical engines live in classical_receive.py (which imports this module): exported here on first use
+    if name in ("ClassicalRxReceiver", "ClassicalReceiveGroup"):
+        from . import classical_receive
+        return getattr(classical_receive, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

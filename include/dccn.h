@@ -347,6 +347,43 @@ typedef struct dccn_classical_receive_args {
 int dccn_classical_receive_supported(int S, int K, int CP, int P, int D, int E, int nbits);
 int dccn_classical_receive(const dccn_classical_receive_args* args, dccn_stream_t stream);
 
+/* ---- classical receive for several links: up to dccn_chain_group_max() links' detectors in ONE launch ------
+ * What dccn_frame_sync_grouped and its kin are for the front end, for the detector behind it: the solo entry's kernel body runs for
+ * n_links links in one launch, the link index on a grid dimension and a link's blocks laid out as the solo launch lays them out
+ * (ceil(frames / (16 / S)) tiles of whole frames of THAT link; no tile holds frames of two links).  Link i's packed / llr / chest /
+ * y_freq / noise are bit for bit what dccn_classical_receive writes for link i's arguments, and n_links == 1 writes what the solo
+ * entry writes.  The links travel as a HOST array of n_links descriptors, copied by value into the kernel arguments.
+ *   common to the call: frames, S, K, CP, P, D, E;
+ *   per link: nbits and m (any mix of BPSK .. 16-QAM in one launch: the kernel switches block-uniformly on the link's nbits),
+ *             mode, win, noise_var, pv, and every pointer.  Link i's packed row is ceil(D * nbits_i / 8) bytes.
+ * Two links may share any input (x, dft, w, the index lists, the tables).  llr, chest, y_freq and noise are each given for every
+ * link or for none.  sizeof(dccn_classical_link) == 136.
+ * Plan first, then issue: every link is checked by the solo entry's own rules (dccn_classical_receive_supported(S, K, CP, P, D, E,
+ * nbits_i), then win, mode, noise_var, pv, m, NULLs and alignments), and the call adds: n_links outside
+ * 1 .. dccn_chain_group_max(); links NULL; frames < 1; an output given for some links only; any output range of one link (packed,
+ * llr, chest, y_freq, noise) overlapping an output range or an input range of ANOTHER link -- all DCCN_ERR_INVALID_ARG.  A refused
+ * call launches nothing and writes nothing for any link.  Inside a chain group DCCN_ERR_UNSUPPORTED, as the solo entry.  No
+ * workspace, no atomics, every sum in the solo entry's order: two runs give the same bits. */
+typedef struct dccn_classical_link {
+    int nbits, m, mode, win;
+    float noise_var, pv_re, pv_im;
+    const float* dft;
+    const float* w;
+    const int* pil;
+    const int* dat;
+    const int* empty;
+    const float* table;
+    const int* labels;
+    const float* x;
+    unsigned char* packed;
+    float* llr;                /* nullable (for all links or none) */
+    float* chest;              /* nullable (all or none) */
+    float* y_freq;             /* nullable (all or none) */
+    float* noise;              /* nullable (all or none) */
+} dccn_classical_link;
+int dccn_classical_receive_grouped(int n_links, const dccn_classical_link* links, int frames, int S, int K, int CP, int P, int D,
+                                   int E, dccn_stream_t stream);
+
 /* One row of the sweep table {c00,c01,c10,c11,ce_sum,count} (float64, device): row6 += the metrics record of the
  * last step, stream-ordered, no host round trip (dev/py/ofdmreceiver_np.py:80-85 accumulates the same on the host). */
 int dccn_metrics_table_add(const dccn_metrics* metrics, double* row6, dccn_stream_t stream);

@@ -14,6 +14,17 @@ median and the repeat-to-repeat spread (max - min) / median.  One JSON line per 
   dccn       RxReceiver.receive(x) of the basic receiver at the same frame count (cp=True, whole symbols)
 
     python tools/clsrxbench.py [--repeats 7] [--calls 200] [--frames 73,1170,20000] [--out FILE]
+
+``--links G [G ...]`` asks the other question instead: what does ONE grouped launch for G links
+(``ClassicalReceiveGroup.receive``, ``dccn_classical_receive_grouped``) cost against the same G links as solo calls back to back
+on one stream (``ClassicalRxReceiver.receive`` G times)?  Frames resident in both arms (no staging copies: launches only), ALMMSE,
+the same alternation, repeats and spreads; per G and frame count one pair with every link QPSK and one with the links' modulations
+cycling through ``--mods`` (default 1 2 3 4).  ``--variants solo`` restricts the first table to the listed variants (an A/B of two
+builds of the library runs ``--variants one`` once per build, ``DCCN_LIB_PATH`` selecting it).
+
+  solo_xG    G ClassicalRxReceiver.receive() calls, one per link       grouped    ClassicalReceiveGroup.receive([None] * G)
+
+    python tools/clsrxbench.py --links 2 4 8 [--mods 1 2 3 4] [--frames 73,1170] [--repeats 7] [--out FILE]
 """
 import argparse
 import ctypes as C
@@ -39,6 +50,9 @@ def main():
     ap.add_argument("--nbits", default="2,4")
     ap.add_argument("--snr", type=float, default=20.0)
     ap.add_argument("--out", default="")
+    ap.add_argument("--links", type=int, nargs="+", default=[], help="group sizes: time G solo calls against one grouped call")
+    ap.add_argument("--mods", type=int, nargs="+", default=[1, 2, 3, 4], help="with --links: the mixed arm's modulations (nbits)")
+    ap.add_argument("--variants", default="", help="without --links: only these variants (comma separated)")
     a = ap.parse_args()
     import torch
     from dl_ofdm_amd import _lib, ofdm, receiver as R
@@ -68,6 +82,44 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / calls * 1e3                   # us per call
 
+    def alternate(variants, calls):
+        """every variant warmed up, then --repeats rounds with the variants alternating -> {variant: [us per call]}"""
+        times = {k: [] for k in variants}
+        for fn in variants.values():
+            timed(fn, 5)
+        for _ in range(a.repeats):
+            for k, fn in variants.items():
+                times[k].append(timed(fn, calls))
+        return times
+
+    if a.links:
+        from dl_ofdm_amd.classical_receive import ClassicalReceiveGroup
+        for n in (int(v) for v in a.frames.split(",")):
+            calls = max(10, min(a.calls, 2_000_000 // n))
+            for G in a.links:
+                for arm, mods in (("qpsk", [2] * G), ("mixed", [a.mods[i % len(a.mods)] for i in range(G)])):
+                    flags = [R.Flags(nbits=nb, channel="EPA", nfilter=64) for nb in mods]
+                    grp = ClassicalReceiveGroup(flags, n, "ALMMSE")
+                    solos = [ClassicalRxReceiver(F, n, "ALMMSE") for F in flags]
+                    for i, F in enumerate(flags):                              # every link its own frames, the same in both arms
+                        x = DeviceDataGen(F, ofdm.ofdm_tx(F), device="cuda", seed=1 + i).make_batch(n, a.snr)[0]
+                        grp.links[i].x.copy_(x.reshape(grp.links[i].x.shape))
+                        solos[i].x.copy_(grp.links[i].x)
+                    none = [None] * G
+
+                    def solo_calls():
+                        for rx in solos:
+                            rx.receive()
+
+                    times = alternate({"solo_x%d" % G: solo_calls, "grouped": lambda: grp.receive(none)}, calls)
+                    torch.cuda.synchronize()
+                    same = all(torch.equal(l.packed, rx.packed) and torch.equal(l.chest, rx.chest) for l, rx in zip(grp.links, solos))
+                    for k, v in times.items():
+                        emit(dict(kind="clsrx_group", variant=k, arm=arm, links=G, mods=mods, frames=n, calls=calls,
+                                  unit="us per round of %d links" % G, grouped_equals_solo=bool(same), **stats(v)))
+        return
+
+    only = [v for v in a.variants.split(",") if v]
     for nbits in (int(v) for v in a.nbits.split(",")):
         for n in (int(v) for v in a.frames.split(",")):
             F = R.Flags(nbits=nbits, channel="EPA", nfilter=64)
@@ -107,13 +159,10 @@ def main():
             variants = {"one": lambda: one.receive(x), "one_llr": lambda: one_llr.receive(x),
                         "sequence": lambda: old.receive(x, bits, "ALMMSE", a.snr, want_bits=True), "launches": launches,
                         "dccn": lambda: dccn.receive(x)}
+            if only:
+                variants = {k: variants[k] for k in only}
             calls = max(10, min(a.calls, 2_000_000 // n))
-            times = {k: [] for k in variants}
-            for fn in variants.values():
-                timed(fn, 5)                                                # warm-up of every shape in the window
-            for _ in range(a.repeats):
-                for k, fn in variants.items():
-                    times[k].append(timed(fn, calls))
+            times = alternate(variants, calls)                              # (warm-up of every shape in the window first)
             # the two classical paths decide alike (a few cells within rounding of a boundary aside)
             one.receive(x)
             _, _, ref = old.receive(x, bits, "ALMMSE", a.snr, want_bits=True)
