@@ -10,6 +10,8 @@ import os
 import threading
 from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_longlong, c_size_t, c_void_p
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DCCN_LIB_PATH") or os.path.join(_HERE, "lib", "libdccn.so")     # override: kernel experiments
 
@@ -410,6 +412,16 @@ def check(status: int, what: str = "dccn call") -> None:
         lib = load()
         msg = lib.dccn_strerror(status).decode()
         raise DccnError("%s failed: %s (status %d, hipError %d)" % (what, msg, status, lib.dccn_last_hip_error()))
+
+
+def ptr(t):
+    """``t.data_ptr()``; ``None`` (a NULL pointer) for a tensor the call does without"""
+    return None if t is None else t.data_ptr()
+
+
+def stream_ptr(device) -> c_void_p:
+    """the current stream of ``device``, as the ``dccn_stream_t`` every launch entry takes last"""
+    return c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def device_info():

@@ -23,13 +23,14 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ClassicalReceiveArgs, check
-from .receive import ReceiveResult, _FrontEnd, _GroupFrontEnd, row_bytes
+from ._lib import ClassicalReceiveArgs, check, ptr, stream_ptr
+from .receive import ReceiveResult, _FrontEnd, _GroupFrontEnd, _refuse_group_span, row_bytes
+from .sync import _per_link, group_size
 
 METHODS = {"ALMMSE": 2, "LS-Spline": 0, "LS-Linear": 0}      # -> dccn_classical_receive's mode
 
 
-class ClassicalRxReceiver(_FrontEnd):
+class ClassicalRxReceiver:
     """Fixed-shape classical receive engine on one GPU: ``receive(x)`` / ``receive_capture(cap, ...)`` ->
     :class:`~dl_ofdm_amd.receive.ReceiveResult` (``prob`` is ``None``).
 
@@ -63,7 +64,6 @@ class ClassicalRxReceiver(_FrontEnd):
             raise ValueError("noise_var must be finite and > 0 (None: estimated from the empty carriers)")
         self.noise_var = None if noise_var is None else float(noise_var)
         self.pilot_sc = np.asarray(o.pilotSc, dtype=np.int32).reshape(-1)
-        self._syncs = {}
         self.P, self.D, self.E = len(h.pil), len(h.dat), len(o.guardSc)
         if not self.lib.dccn_classical_receive_supported(S, K, CP, self.P, self.D, self.E, self.nbits):
             raise _lib.DccnError("dccn_classical_receive_supported refused S=%d K=%d CP=%d P=%d D=%d E=%d nbits=%d"
@@ -95,22 +95,13 @@ class ClassicalRxReceiver(_FrontEnd):
         self.chest = torch.empty(B, S * K, 2, **f32)
         self.noise = torch.empty(B, **f32)
         self.y_freq = None
+        self._front = _FrontEnd(type(self).__name__, self.device, self.x, CP, K, self.pilot_sc)    # (it writes whole symbols)
         pv = complex(h.pilot_value)
-        p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
         self.args = ClassicalReceiveArgs(B, S, K, CP, self.P, self.D, self.E, self.nbits, int(self.table.shape[0]),
                                          CP - self.advance, METHODS[method], 0.0 if self.noise_var is None else self.noise_var,
-                                         pv.real, pv.imag, p(self.dft), p(self.w), p(self.pil), p(self.dat), p(self.empty),
-                                         p(self.table), p(self.labels), p(self.x), p(self.packed), p(self.llr), p(self.chest),
-                                         None, p(self.noise))
-
-    # (the shape the shared front end writes for: whole symbols)
-    @property
-    def _kin(self) -> int:
-        return self.K + self.CP
-
-    @property
-    def _S(self) -> int:
-        return self.S
+                                         pv.real, pv.imag,
+                                         *map(ptr, (self.dft, self.w, self.pil, self.dat, self.empty, self.table, self.labels,
+                                                    self.x, self.packed, self.llr, self.chest, self.y_freq, self.noise)))
 
     def want_y_freq(self) -> torch.Tensor:
         """from now on the launch also writes the frequency-domain frames: the resident ``y_freq [batch, S*K, 2]``"""
@@ -123,21 +114,21 @@ class ClassicalRxReceiver(_FrontEnd):
         """(nothing captured: lets a :class:`~dl_ofdm_amd.session.Session` keep receivers next to its engines)"""
 
     def _detect(self, offset=None, est=None, first=None, est0=None, est_int=None) -> ReceiveResult:
-        check(self.lib.dccn_classical_receive(C.byref(self.args), self._stream()), "dccn_classical_receive")
+        check(self.lib.dccn_classical_receive(C.byref(self.args), stream_ptr(self.device)), "dccn_classical_receive")
         return ReceiveResult(self.packed, self.llr, None, self.D, self.nbits, offset, est, first, est0, est_int)
 
     def receive(self, x=None, sync: int = 0, cfo: bool = False) -> ReceiveResult:
         """Stage ``x`` (``None``: whatever ``self.x`` holds; whole symbols ``[batch, S, K + CP, 2]``) and run the classical
         launch on the current stream.  ``sync = W > 0`` / ``cfo=True``: as :meth:`RxReceiver.receive` -- the alignment launch
         takes the place of the copy and writes the aligned frames straight into ``self.x``."""
-        return self._detect(*self._stage_frames(x, sync, cfo))
+        return self._detect(*self._front.frames(x, sync, cfo))
 
     def receive_capture(self, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False, acquire: int = 0,
                         lo: int = 0, cfo_scope: str = "frame", cfo_span: int = 0, scale: Optional[float] = None) -> ReceiveResult:
         """The classical launch on ``batch`` frames that still sit inside one contiguous capture: every argument as
         :meth:`RxReceiver.receive_capture` takes it (acquisition, the cut at each frame's estimated start, per-frame or pooled
         carrier offset, offsets beyond half a spacing, int16 captures), with the same refusals and launch counts."""
-        return self._detect(*self._stage_capture(cap, first, stride, sync, cfo, acquire, lo, cfo_scope, cfo_span, scale))
+        return self._detect(*self._front.capture(cap, first, stride, sync, cfo, acquire, lo, cfo_scope, cfo_span, scale))
 
 
 GRID_FIELDS = ("S", "K", "CP", "P", "D", "E")                 # what dccn_classical_receive_grouped takes once for every link
@@ -162,7 +153,7 @@ def _same_grid(links) -> None:
                              "call's, not a link's" % (f, vals))
 
 
-class ClassicalReceiveGroup(_GroupFrontEnd):
+class ClassicalReceiveGroup:
     """Up to ``dccn_chain_group_max()`` links of one grid ``(S, K, CP, P, D, E)`` and any mix of modulations, methods, window
     positions and noise sources whose classical detectors share ONE launch (``dccn_classical_receive_grouped``): a host that
     serves several links issues one call per round of frames.  Link i's results are bit for bit what ``.links[i]`` (a
@@ -175,16 +166,12 @@ class ClassicalReceiveGroup(_GroupFrontEnd):
 
     ``methods`` / ``advances`` / ``noise_vars`` / ``interps``: one value for every link, or a list with one entry per link."""
 
-    _solo = "ClassicalRxReceiver.receive_capture"
+    _solo_call = "ClassicalRxReceiver.receive_capture"                  # the call that serves one link, for the refusals
 
     def __init__(self, flags_list, batch: int, methods="ALMMSE", advances=0, noise_vars=None, interps=None,
                  want_llr: bool = False, device="cuda"):
-        from .sync import _per_link
-        n = len(flags_list)
         self.lib = _lib.load()
-        gmax = int(self.lib.dccn_chain_group_max())
-        if not (1 <= n <= gmax):
-            raise ValueError("ClassicalReceiveGroup: 1..%d links per group" % gmax)
+        n = group_size(self.lib, len(flags_list), "ClassicalReceiveGroup")
         # (an interpolation matrix is array-like itself: only a list or tuple of them is one entry per link)
         per = {k: _per_link(v, n, "ClassicalReceiveGroup(%s)" % k)
                for k, v in (("methods", methods), ("advances", advances), ("noise_vars", noise_vars), ("interps", interps))}
@@ -193,19 +180,10 @@ class ClassicalReceiveGroup(_GroupFrontEnd):
         self.links = [ClassicalRxReceiver(F, self.batch, method=per["methods"][i], advance=per["advances"][i],
                                           noise_var=per["noise_vars"][i], interp=per["interps"][i], want_llr=want_llr, device=device)
                       for i, F in enumerate(flags_list)]
-        self.device = self.links[0].device
-        self._stages = {}                                      # the group's resident front-end stages (sync.py: the *Group classes)
-        self._table, self._table_key = (_lib.ClassicalLink * n)(), None
-
-    def _frame_shape(self):
         l = self.links[0]
-        return l.S, l.K, l.CP
-
-    def _link_x(self) -> list:
-        return [l.x for l in self.links]
-
-    def _link_pilots(self) -> list:
-        return [l.pilot_sc for l in self.links]
+        self.device = l.device
+        self._front = _GroupFrontEnd(self, l.K, l.CP, [l.x for l in self.links], [l.pilot_sc for l in self.links])
+        self._table, self._table_key = (_lib.ClassicalLink * n)(), None
 
     def want_y_freq(self) -> list:
         """from now on the launch also writes every link's frequency-domain frames (``.links[i].y_freq``)"""
@@ -222,9 +200,8 @@ class ClassicalReceiveGroup(_GroupFrontEnd):
                                                     a.dat, a.empty, a.table, a.labels, a.x, a.packed, a.llr, a.chest, a.y_freq, a.noise)
             self._table_key = key
         l = self.links[0]
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        check(self.lib.dccn_classical_receive_grouped(len(self.links), self._table, self.batch, l.S, l.K, l.CP, l.P, l.D, l.E, st),
-              "dccn_classical_receive_grouped")
+        check(self.lib.dccn_classical_receive_grouped(len(self.links), self._table, self.batch, l.S, l.K, l.CP, l.P, l.D, l.E,
+                                                      stream_ptr(self.device)), "dccn_classical_receive_grouped")
         none = [None] * len(self.links)
         firsts, acq_cfo = firsts or none, acq_cfo or none
         return [ReceiveResult(l.packed, l.llr, None, l.D, l.nbits, offsets[i], ests[i], firsts[i], acq_cfo[i])
@@ -238,7 +215,7 @@ class ClassicalReceiveGroup(_GroupFrontEnd):
         :class:`~dl_ofdm_amd.receive.ReceiveResult` per link (``prob`` is ``None``; the links' resident buffers)."""
         if len(xs) != len(self.links):
             raise ValueError("one batch of frames per link")
-        return self._detect(*self._stage_frames_group(xs, sync, cfo))
+        return self._detect(*self._front.frames(xs, sync, cfo))
 
     def receive_capture(self, caps, firsts=None, strides=None, sync: int = 3, cfo: bool = False, acquire: int = 0, los=0,
                         cfo_scope: str = "frame", cfo_span: int = 0) -> list:
@@ -248,5 +225,5 @@ class ClassicalReceiveGroup(_GroupFrontEnd):
         ``cfo_scope="capture"``), then the ONE classical launch.  ``firsts[i]``: an integer, or a device ``int64`` tensor of one
         element with ``los[i]``; the two mix.  ``cfo_span > 0`` and int16 captures are refused (:class:`DccnError`): the
         grouped front end is float32-only and has no wide variant -- those go through ``.links[i].receive_capture``."""
-        self._refuse_cfo_span(cfo_span)
-        return self._detect(*self._stage_captures_group(caps, firsts, strides, sync, cfo, acquire, los, cfo_scope))
+        _refuse_group_span(self, cfo_span)
+        return self._detect(*self._front.capture(caps, firsts, strides, sync, cfo, acquire, los, cfo_scope))

@@ -82,7 +82,7 @@ class DeviceDataGen:
         if self.identity:
             self.L = 1
         self._ws = {}
-        self._syncs, self.sync_offset = {}, None      # make_batch(sync=W): alignment stages per (frames, W, out_kin), last offsets
+        self._syncs, self.sync_offset = {}, None      # make_batch(sync=W): alignment stages (sync.resident_stage), last offsets
 
     @staticmethod
     def idft_cp_matrix(K: int, CP: int) -> np.ndarray:
@@ -252,14 +252,13 @@ class DeviceDataGen:
             x, npow, H = self.channel(tx, snr_db, out_x=out_x, want_H=want_H, out_H=out_H, out_npow=out_npow)
             self.offset = (self.offset + 1) & 0xFFFFFFFF
             return (x, bits, npow, H) if (want_H or out_H is not None) else (x, bits, npow)
-        from .sync import FrameSync, rotate_response_
+        from .sync import FrameSync, resident_stage, rotate_response_
         if self.align_window:
             raise ValueError("sync > 0 and align_window both move the frames: choose one")
         kin = self.n_sc if out_kin is None else int(out_kin)
-        key = (n_frames, int(sync), kin)
-        if key not in self._syncs:          # (refuses a bad W / out_kin before anything is launched)
-            self._syncs[key] = FrameSync(self.S, self.K, self.CP, int(sync), n_frames, self.device, out_kin=kin, want_metric=False)
-        fs, w = self._syncs[key], self._workspace(n_frames)
+        # (refuses a bad W / out_kin before anything is launched)
+        fs = resident_stage(self._syncs, FrameSync, self.S, self.K, self.CP, int(sync), n_frames, self.device, kin, False)
+        w = self._workspace(n_frames)
         if "stage" not in w:
             w["stage"] = torch.empty(n_frames, self.S, self.n_sc, 2, dtype=torch.float32, device=self.device)
         tx, bits = self.transmit(n_frames, out_bits=out_bits)

@@ -70,6 +70,7 @@ class _FusedPlan:
         self.buffers = self._buffers()
         self._partner = None
         self._receive_out: Dict[str, torch.Tensor] = {}      # receive(): packed / llr / prob, allocated on first use
+        self.front = None                                    # receive.py: the front end that writes this plan's x, built on first use
         self.graphs: Dict[object, C.c_void_p] = {}
 
     def _buffers(self, x_next=None, pre: int = 0, slot: int = 0, virt: int = 0, gen_rides: bool = False, monitor: int = 0) -> EqBuffers:
@@ -223,6 +224,7 @@ class EqualizerTrainer:
         self.pilot_carriers = A.place(arena, torch.as_tensor(np.asarray(ofdmobj.pilotCarriers, dtype=np.int32)).to(self.device))
         self.fused_ok = True
         self._plans: Dict[int, _FusedPlan] = {}
+        self.acquire_stages: dict = {}                       # receive_capture: the acquisition stages every plan's front end shares
         self._rx_folded = None
 
     def pin_tuning(self):

@@ -24,9 +24,10 @@ import torch
 
 from . import _lib, epochs, ofdm
 from . import receiver_mp as H
-from ._lib import check
+from ._lib import check, stream_ptr
 from .arena import ChainArena, check_same_layout
-from .receive import ReceiveResult, _GroupFrontEnd
+from .receive import ReceiveResult, _GroupFrontEnd, _refuse_group_span
+from .sync import group_size
 
 
 def _ptr_array(structs):
@@ -146,7 +147,7 @@ class EqualizerChainGroup:
         return t
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return stream_ptr(self.device)
 
     def _generate(self, act, t, i: int, q: int, materialise: bool):
         """batch i of the epoch for every chain: ONE fused generator launch (+ one that forms x for an epoch's first batch) -- or
@@ -258,7 +259,7 @@ class _ReceiveChain:
                                self.prob.data_ptr() if want_prob else None)
 
 
-class ChainReceiveGroup(_GroupFrontEnd):
+class ChainReceiveGroup:
     """Up to ``dccn_chain_group_max()`` (equaliser -> frozen receiver) chains of one shape and any mix of modulations whose
     receive steps share ONE launch sequence (``dccn_eq_receive_step_grouped``): a host that serves several links, each with its
     own trained chain, issues one call per round of frames.  Chain i's results are bit for bit what
@@ -272,14 +273,13 @@ class ChainReceiveGroup(_GroupFrontEnd):
 
     ``.chains[i].pl.out_eq`` / ``.chest`` / ``.snr_db`` hold what the chain's ``eval_step`` writes for the same frames."""
 
-    _solo = "EqualizerTrainer.receive_capture"
+    _solo_call = "EqualizerTrainer.receive_capture"                     # the call that serves one link, for the refusals
 
     def __init__(self, flags_list: Sequence, rx_params_list: Sequence[Dict[str, np.ndarray]], batch: int, device="cuda",
                  want_llr: bool = False, want_prob: bool = False):
         self.lib = _lib.load()
-        gmax = int(self.lib.dccn_chain_group_max())
-        if not (1 <= len(flags_list) <= gmax) or len(rx_params_list) != len(flags_list):
-            raise ValueError("1..%d chains per group, one receiver per chain" % gmax)
+        if group_size(self.lib, len(flags_list), "ChainReceiveGroup") != len(rx_params_list):
+            raise ValueError("ChainReceiveGroup: one receiver per chain")
         self.batch = int(batch)
         F0 = flags_list[0]
         if len(flags_list) > 1 and not bool(self.lib.dccn_eq_receive_group_supported(
@@ -295,7 +295,8 @@ class ChainReceiveGroup(_GroupFrontEnd):
         self._bufs = _ptr_array([c.pl.buffers for c in self.chains])
         self.want_llr, self.want_prob = bool(want_llr), bool(want_prob)
         self._outs = {}                                        # (llr, prob) asked for -> (the chains' dccn_receive_out, their table)
-        self._stages = {}                                      # the group's resident front-end stages (sync.py: the *Group classes)
+        o = self.chains[0].o
+        self._front = _GroupFrontEnd(self, o.K, o.CP, [c.pl.x for c in self.chains], [c.o.pilotSc for c in self.chains])
 
     def _out_table(self, want_llr: bool, want_prob: bool):
         key = (want_llr, want_prob)
@@ -315,19 +316,8 @@ class ChainReceiveGroup(_GroupFrontEnd):
         """the grouped receive step on what every chain's ``pl.x`` holds"""
         for c in self.chains:
             c.pl._ahead()[c.pl.ws.data_ptr()] = None           # (the step normalises into the chain's workspace)
-        st = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        check(self.lib.dccn_eq_receive_step_grouped(len(self.chains), self._shapes, self._bufs, self._out_table(want_llr, want_prob), st),
-              "dccn_eq_receive_step_grouped")
-
-    def _frame_shape(self):
-        c = self.chains[0]
-        return int(c.F.nsymbol), int(c.o.K), int(c.o.CP)
-
-    def _link_x(self) -> list:
-        return [c.pl.x for c in self.chains]
-
-    def _link_pilots(self) -> list:
-        return [c.o.pilotSc for c in self.chains]
+        check(self.lib.dccn_eq_receive_step_grouped(len(self.chains), self._shapes, self._bufs, self._out_table(want_llr, want_prob),
+                                                    stream_ptr(self.device)), "dccn_eq_receive_step_grouped")
 
     def receive(self, xs: Sequence, want_llr: Optional[bool] = None, want_prob: Optional[bool] = None, sync: int = 0,
                 cfo: bool = False) -> list:
@@ -344,7 +334,7 @@ class ChainReceiveGroup(_GroupFrontEnd):
         if len(xs) != len(self.chains):
             raise ValueError("one batch of frames per chain")
         want_llr, want_prob = self._wants(want_llr, want_prob)
-        offsets, ests = self._stage_frames_group(xs, sync, cfo)
+        offsets, ests = self._front.frames(xs, sync, cfo)
         self._step(want_llr, want_prob)
         return [ReceiveResult(c.packed, c.llr if want_llr else None, c.prob if want_prob else None, c.D, c.nbits, offsets[i], ests[i])
                 for i, c in enumerate(self.chains)]
@@ -368,9 +358,9 @@ class ChainReceiveGroup(_GroupFrontEnd):
 
         ``cfo_span > 0`` is refused (:class:`DccnError`): the grouped link tables carry no integer offset, so carrier offsets
         beyond half a subcarrier spacing go through the solo calls (``EqualizerTrainer.receive_capture(..., cfo_span=M)``)."""
-        self._refuse_cfo_span(cfo_span)
+        _refuse_group_span(self, cfo_span)
         want_llr, want_prob = self._wants(want_llr, want_prob)
-        offsets, cfos, firsts, acq_cfo = self._stage_captures_group(caps, firsts, strides, sync, cfo, acquire, los, cfo_scope)
+        offsets, cfos, firsts, acq_cfo = self._front.capture(caps, firsts, strides, sync, cfo, acquire, los, cfo_scope)
         self._step(want_llr, want_prob)
         return [ReceiveResult(c.packed, c.llr if want_llr else None, c.prob if want_prob else None, c.D, c.nbits, offsets[i],
                               cfos[i], firsts[i], acq_cfo[i])

@@ -22,8 +22,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import RxReceiveBuffers, RxShape, check
+from ._lib import RxReceiveBuffers, RxShape, check, ptr, stream_ptr
 from .engine import PARAM_NAMES, RxDims, glorot_init, param_layout
+from .sync import (CaptureAcquire, CaptureAcquireGroup, CaptureSync, CaptureSyncGroup, FrameSync, FrameSyncGroup, _per_link,
+                   capture_format, check_cfo_scope, resident_stage)
 
 
 def row_bytes(D: int, nbits: int) -> int:
@@ -84,186 +86,185 @@ class ReceiveResult:
         return b.reshape(p.shape[0], -1)[:, :n].reshape(p.shape[0], self.D, self.nbits).to(torch.uint8)
 
 
+# ---- what every receive call refuses before anything is sized or launched (`what`: the call the user made) ---------------------------
+def _checked_alignment(what: str, sync, cfo) -> None:
+    if cfo and not sync:
+        raise _lib.DccnError("%s(cfo=True) needs sync = W > 0: the offset is read off the timing correlation" % what)
+
+
+def _checked_capture_call(what: str, cap, first, sync, cfo, acquire, cfo_scope, cfo_span, scale):
+    """``(W, M)`` of a solo ``receive_capture``.  Acquisition runs ahead of the cut, which would otherwise be the first to look:
+    so the cut's refusals of the scope, of an int16 capture or a ``scale`` (:func:`~dl_ofdm_amd.sync.capture_format`) and of the
+    window are made here.  ``cfo_span = M > 0`` needs acquisition and the carrier offset taken out: the integer is only known
+    through acquisition."""
+    check_cfo_scope(cfo, cfo_scope)
+    M = int(cfo_span)
+    if scale is not None or (isinstance(cap, torch.Tensor) and cap.dtype == torch.int16):
+        capture_format(cap, scale, what, M)
+    if M < 0:
+        raise _lib.DccnError("%s: cfo_span must not be negative" % what)
+    if M and (first is not None or not acquire or not cfo):
+        raise _lib.DccnError("%s(cfo_span=M > 0) needs first=None, acquire=J and cfo=True: the whole subcarrier spacings of the "
+                             "offset are only known through acquisition" % what)
+    return _checked_window(what, sync), M
+
+
+def _checked_window(what: str, sync) -> int:
+    if int(sync) <= 0:
+        raise _lib.DccnError("%s needs sync = W > 0" % what)
+    return int(sync)
+
+
+def _acquisition_frames(what: str, first, acquire, s: str = "") -> int:
+    """``J > 0``: acquisition over ``J`` frames finds the start; 0: the caller gave it"""
+    if first is not None:
+        if acquire:
+            raise _lib.DccnError("%s: give `first%s` or `acquire`, not both" % (what, s))
+        return 0
+    if int(acquire) <= 0:
+        raise _lib.DccnError("%s(first%s=None) needs acquire = J > 0, the number of frames acquisition may use" % (what, s))
+    return int(acquire)
+
+
+def _pilot_cells(pilot_sc) -> tuple:
+    """pilot cells as a stage's cache key takes them"""
+    return tuple(int(v) for v in np.asarray(pilot_sc).reshape(-1))
+
+
 class _FrontEnd:
-    """What the receive engines share: the stages in front of the detector, each writing this engine's resident ``x`` --
-    the copy, the alignment launch (``sync=W``), and the capture cut with acquisition.  The engine provides ``lib``,
-    ``device``, ``batch``, ``x``, ``CP``, ``K``, ``pilot_sc``, ``_syncs`` and the two shape properties below."""
+    """The stages in front of a solo detector, each writing the detector's resident ``x`` (``[batch, S, kin, 2]``): the copy, the
+    alignment launch (``sync=W``), and the capture cut with acquisition.  Every solo engine owns one -- :class:`RxReceiver`,
+    :class:`~dl_ofdm_amd.classical_receive.ClassicalRxReceiver`, and each resident plan of an ``EqualizerTrainer`` (whose plans
+    share their acquisition stages: ``acquires``).  ``kin``: samples per symbol the detector takes (``K + CP``: whole symbols;
+    ``K``: a ``cp=False`` receiver).  ``prefix``: what stands in front of ``receive`` / ``receive_capture`` in a refusal."""
 
-    @property
-    def _kin(self) -> int:          # samples per symbol the detector takes (K + CP: whole symbols; K: a cp=False receiver)
-        return self.dims.kin
+    def __init__(self, owner: str, device, x: torch.Tensor, CP=None, K=None, pilot_sc=None, acquires=None, prefix: str = ""):
+        self.owner, self.device, self.x, self.CP, self.K, self.prefix = owner, device, x, CP, K, prefix
+        self.batch, self.S, self.kin = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+        self.pilots = None if pilot_sc is None else _pilot_cells(pilot_sc)
+        self.stages = {}                                       # resident: sync.resident_stage
+        self.acquires = self.stages if acquires is None else acquires
 
-    @property
-    def _S(self) -> int:
-        return self.dims.S
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _frame_sync(self, n_sc: int, W: int, cfo: bool = False):
-        """the alignment stage (``cfo``: with the carrier-frequency offset taken out) for full frames of ``n_sc`` samples per
-        symbol, writing this receiver's ``x``"""
-        from .sync import FrameSync
-        kin = self._kin
+    def frames(self, x, sync: int, cfo: bool):
+        """``receive``'s front end: ``x`` into ``self.x`` by the copy or the alignment launch -> ``(offset, cfo estimates)``"""
+        what, kin = self.prefix + "receive", self.kin
+        _checked_alignment(what, sync, cfo)
+        if not sync:
+            if x is not None:
+                self.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(self.x.shape), non_blocking=True)
+            return None, None
+        if not isinstance(x, torch.Tensor) or x.dim() != 4:
+            raise _lib.DccnError("%s(sync=W) takes a device tensor [batch, S, K + CP, 2]" % what)
+        n_sc = int(x.shape[2])
         if self.CP is not None:
             CP = self.CP
         elif n_sc > kin:
             CP = n_sc - kin
         else:
-            raise _lib.DccnError("receive(sync=W) of a receiver that takes whole symbols needs %s(..., CP=...)"
-                                 % type(self).__name__)
+            raise _lib.DccnError("%s(sync=W) of a receiver that takes whole symbols needs %s(..., CP=...)" % (what, self.owner))
         K = n_sc - CP
         if kin not in (n_sc, K):
-            raise _lib.DccnError("receive(sync=W): frames of %d samples per symbol (CP = %d) do not fit kin = %d" % (n_sc, CP, kin))
-        key = (K, CP, W, bool(cfo))
-        if key not in self._syncs:
-            self._syncs[key] = FrameSync(self._S, K, CP, W, self.batch, self.device, out_kin=kin, want_metric=False, cfo=cfo)
-        return self._syncs[key]
+            raise _lib.DccnError("%s(sync=W): frames of %d samples per symbol (CP = %d) do not fit kin = %d" % (what, n_sc, CP, kin))
+        fs = resident_stage(self.stages, FrameSync, self.S, K, CP, int(sync), self.batch, self.device, kin, False, bool(cfo))
+        _, offset = fs.run(x, out=self.x)
+        return offset, fs.cfo
 
-    def _stage_frames(self, x, sync: int, cfo: bool):
-        """``receive``'s front end: ``x`` into ``self.x`` by the copy or the alignment launch -> ``(offset, cfo estimates)``"""
-        offset = est = None
-        if cfo and not sync:
-            raise _lib.DccnError("receive(cfo=True) needs sync = W > 0: the offset is read off the timing correlation")
-        if sync:
-            if not isinstance(x, torch.Tensor) or x.dim() != 4:
-                raise _lib.DccnError("receive(sync=W) takes a device tensor [batch, S, K + CP, 2]")
-            fs = self._frame_sync(int(x.shape[2]), int(sync), bool(cfo))
-            _, offset = fs.run(x, out=self.x)
-            est = fs.cfo
-        elif x is not None:
-            self.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(self.x.shape), non_blocking=True)
-        return offset, est
+    def capture(self, cap, first, stride, sync, cfo, acquire, lo, cfo_scope, cfo_span, scale):
+        """``receive_capture``'s front end: the refusals, then :meth:`cut`"""
+        what = self.prefix + "receive_capture"
+        W, M = _checked_capture_call(what, cap, first, sync, cfo, acquire, cfo_scope, cfo_span, scale)
+        return self.cut(what, cap, first, stride, W, cfo, acquire, lo, cfo_scope, M, scale)
 
-    def _stage_capture(self, cap, first, stride, sync, cfo, acquire, lo, cfo_scope, cfo_span, scale):
-        """``receive_capture``'s front end: acquisition (``first=None``) and the cut, writing ``self.x`` ->
-        ``(offset, cfo estimates, first, acquired_cfo, acquired_cfo_int)`` as :class:`ReceiveResult` takes them"""
-        from .sync import CaptureSync, check_cfo_scope
-        name = type(self).__name__
-        check_cfo_scope(cfo, cfo_scope)
-        _checked_sc16(cap, scale, cfo_span, "receive_capture")
-        M = _checked_cfo_span(cfo_span, first, acquire, cfo)
-        W = int(sync)
-        if W <= 0:
-            raise _lib.DccnError("receive_capture needs sync = W > 0")
+    def cut(self, what, cap, first, stride, W, cfo, acquire, lo, cfo_scope, M, scale):
+        """acquisition (``first=None``) and the cut, writing ``self.x`` -> ``(offset, cfo estimates, first, acquired_cfo,
+        acquired_cfo_int)`` as :class:`ReceiveResult` takes them"""
         if self.CP is None:
-            raise _lib.DccnError("receive_capture needs %s(..., CP=...)" % name)
-        kin = self._kin
+            raise _lib.DccnError("%s needs %s(..., CP=...)" % (what, self.owner))
+        kin = self.kin
         K = kin - self.CP if self.K is None else self.K
         if K < 1 or kin not in (K + self.CP, K):
-            raise _lib.DccnError("receive_capture: K = %d, CP = %d do not fit kin = %d" % (K, self.CP, kin))
-        key = ("capture", W, bool(cfo)) if cfo_scope == "frame" else ("capture", W, True, cfo_scope)
-        key += (("span", M),) if M else ()
-        if key not in self._syncs:
-            self._syncs[key] = CaptureSync(self._S, K, self.CP, W, self.batch, self.device, out_kin=kin, want_metric=False,
-                                           cfo=bool(cfo), cfo_scope=cfo_scope, cfo_span=M)
-        cs = self._syncs[key]
-        first, est0, est_int = _acquired_first(self._syncs, first, acquire, cap, lo, self._S, K, self.CP, self.pilot_sc,
-                                               self.device, M, scale, name)
+            raise _lib.DccnError("%s: K = %d, CP = %d do not fit kin = %d" % (what, K, self.CP, kin))
+        cs = resident_stage(self.stages, CaptureSync, self.S, K, self.CP, W, self.batch, self.device, kin, False, bool(cfo),
+                            cfo_scope, M)
+        est0 = est_int = None
+        J = _acquisition_frames(what, first, acquire)
+        if J:
+            if self.pilots is None:
+                raise _lib.DccnError("%s(first=None) needs the frame's pilot cells (%s(..., pilot_sc=...))" % (what, self.owner))
+            acq = resident_stage(self.acquires, CaptureAcquire, self.S, K, self.CP, self.pilots, J, self.device, M)
+            first, est0, est_int = acq.run(cap, lo, scale=scale), acq.cfo, (acq.cfo_int if M else None)
         _, offset = cs.run(cap, first, stride, out=self.x, lo=lo,             # (lo matters to a device `first` only)
                            acquired=(est_int, est0) if M else None, scale=scale)
         return offset, cs.cfo, (first if isinstance(first, torch.Tensor) else None), est0, est_int
 
 
+def _refuse_group_span(engine, cfo_span) -> None:
+    """what a group's ``receive_capture`` begins with (it needs nothing of the engine but its class)"""
+    if int(cfo_span) != 0:
+        raise _lib.DccnError("%s.receive_capture: cfo_span > 0 is not offered for groups (the grouped entries have no wide "
+                             "variant); use %s(..., cfo_span=M) per link" % (type(engine).__name__, engine._solo_call))
+
+
 class _GroupFrontEnd:
-    """What the group engines share (:class:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup`,
-    :class:`~dl_ofdm_amd.classical_receive.ClassicalReceiveGroup`): the stages in front of a grouped detector, each ONE launch
-    sequence for all links (sync.py: the ``*Group`` classes), writing every link's resident ``x``.  The engine provides ``lib``,
-    ``device``, ``batch``, ``_stages`` (a dict), ``_solo`` (a class attribute: the call that serves one link, for the refusals) and
-    the three below."""
+    """The stages in front of a grouped detector (:class:`~dl_ofdm_amd.equalizer_group.ChainReceiveGroup`,
+    :class:`~dl_ofdm_amd.classical_receive.ClassicalReceiveGroup`), each ONE launch sequence for all links (sync.py: the
+    ``*Group`` classes), writing every link's resident ``x`` (``xs[i]``: ``[batch, S, K + CP, 2]``).  The engine that owns it
+    provides ``device`` and ``_solo_call`` (a class attribute: the call that serves one link, for the refusals).  What the ``*Group``
+    stage behind a call checks anyway is left to it."""
 
-    def _frame_shape(self):         # (S, K, CP) of every link
-        raise NotImplementedError
+    def __init__(self, engine, K: int, CP: int, xs: list, pilots: list):
+        self.owner, self.solo, self.device, self.xs = type(engine).__name__, engine._solo_call, engine.device, xs
+        self.shape = (int(xs[0].shape[1]), int(K), int(CP))    # (S, K, CP) of every link
+        self.batch = int(xs[0].shape[0])
+        self.pilots = tuple(_pilot_cells(sc) for sc in pilots)
+        self.stages = {}                                       # resident: sync.resident_stage
 
-    def _link_x(self) -> list:      # the links' resident frame buffers, [batch, S, K + CP, 2] each
-        raise NotImplementedError
+    def _stage(self, cls, W: int, cfo: bool, *scope):
+        """FrameSyncGroup / CaptureSyncGroup writing the links' ``x`` (``scope``: the latter's ``cfo_scope``); no ``out_kin``, no
+        metric"""
+        return resident_stage(self.stages, cls, *self.shape, int(W), self.batch, len(self.xs), self.device, None, False,
+                              bool(cfo), *scope)
 
-    def _link_pilots(self) -> list:  # the links' pilot cells (``ofdm_tx.pilotSc``)
-        raise NotImplementedError
-
-    def _stage(self, kind: str, cls, W: int, cfo: bool, **scope):
-        """the resident front-end stage of this group: FrameSyncGroup / CaptureSyncGroup, writing the links' ``x``
-        (``scope``: ``cfo_scope="capture"`` of a pooled CaptureSyncGroup)"""
-        key = (kind, int(W), bool(cfo)) + tuple(scope.values())
-        if key not in self._stages:
-            S, K, CP = self._frame_shape()
-            self._stages[key] = cls(S, K, CP, int(W), self.batch, len(self._link_x()), self.device, want_metric=False,
-                                    cfo=bool(cfo), **scope)
-        return self._stages[key]
-
-    def _stage_frames_group(self, xs, sync: int, cfo: bool):
+    def frames(self, xs, sync: int, cfo: bool):
         """``receive``'s front end for every link: the per-link copies, or (``sync = W > 0``) one alignment launch ->
         ``(offsets, cfo estimates)``, one entry per link (``None`` where the call has none)"""
-        from .sync import FrameSyncGroup
-        dests = self._link_x()
-        if cfo and not sync:
-            raise _lib.DccnError("receive(cfo=True) needs sync = W > 0: the offset is read off the timing correlation")
-        offsets = ests = [None] * len(dests)
+        _checked_alignment("receive", sync, cfo)
+        offsets = ests = [None] * len(self.xs)
         if sync:
-            if not all(isinstance(x, torch.Tensor) and x.device.type == "cuda" for x in xs):
-                raise _lib.DccnError("receive(sync=W) takes one device tensor [batch, S, K + CP, 2] per link")
-            fs = self._stage("frames", FrameSyncGroup, sync, cfo)
-            _, offsets = fs.run(xs, outs=dests)
+            fs = self._stage(FrameSyncGroup, sync, cfo)
+            _, offsets = fs.run(xs, outs=self.xs)
             ests = fs.cfo if cfo else ests
         else:
-            for dst, x in zip(dests, xs):
+            for dst, x in zip(self.xs, xs):
                 if x is not None:
                     dst.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(dst.shape), non_blocking=True)
         return offsets, ests
 
-    def _refuse_cfo_span(self, cfo_span) -> None:
-        """``receive_capture``'s first check (it needs nothing of the engine but its class)"""
-        if int(cfo_span) != 0:
-            raise _lib.DccnError("%s.receive_capture: cfo_span > 0 is not offered for groups (the grouped entries have no wide "
-                                 "variant); use %s(..., cfo_span=M) per link" % (type(self).__name__, self._solo))
-
-    def _stage_captures_group(self, caps, firsts, strides, sync, cfo, acquire, los, cfo_scope):
+    def capture(self, caps, firsts, strides, sync, cfo, acquire, los, cfo_scope):
         """``receive_capture``'s front end for every link: acquisition (``firsts=None``: three launches) and the cut (one launch,
         three when pooled) -> ``(offsets, cfo estimates, firsts, acquired cfo)``, one entry per link as
         :class:`ReceiveResult` takes them"""
-        from .sync import CaptureAcquireGroup, CaptureSyncGroup, _per_link, check_cfo_scope
-        name = type(self).__name__
-        pooled = check_cfo_scope(cfo, cfo_scope)
-        dests = self._link_x()
-        n = len(dests)
-        if len(caps) != n:
-            raise ValueError("one capture per link")
-        W = int(sync)
-        if W <= 0:
-            raise _lib.DccnError("receive_capture needs sync = W > 0")
+        what, n = self.owner + ".receive_capture", len(self.xs)
+        check_cfo_scope(cfo, cfo_scope)
+        W = _checked_window("receive_capture", sync)
         if any(isinstance(c, torch.Tensor) and c.dtype == torch.int16 for c in caps):
-            raise _lib.DccnError("%s.receive_capture: int16 captures are not offered for groups (the grouped entries read float32 "
-                                 "captures only); use %s per link, or radio.sc16_to_float" % (name, self._solo))
-        if not all(isinstance(c, torch.Tensor) and c.device.type == "cuda" and c.dim() == 2 for c in caps):
-            raise _lib.DccnError("receive_capture takes one device tensor [n, 2] per link")
-        los = _per_link(los, n, "receive_capture(los)")
-        strides = _per_link(strides, n, "receive_capture(strides)")
+            raise _lib.DccnError("%s: int16 captures are not offered for groups (the grouped entries read float32 captures only); "
+                                 "use %s per link, or radio.sc16_to_float" % (what, self.solo))
+        strides = _per_link(strides, n, "receive_capture(strides)")     # (ahead of acquisition, which takes none)
+        J = _acquisition_frames("receive_capture", firsts, acquire, "s")
+        if not J and (not isinstance(firsts, (list, tuple)) or len(firsts) != n):
+            raise ValueError("receive_capture(firsts): one entry per link (%d)" % n)
+        cs = self._stage(CaptureSyncGroup, W, cfo, cfo_scope)
         acq_cfo = [None] * n
-        if firsts is not None:
-            if acquire:
-                raise _lib.DccnError("receive_capture: give `firsts` or `acquire`, not both")
-            if not isinstance(firsts, (list, tuple)) or len(firsts) != n:
-                raise ValueError("receive_capture(firsts): one entry per link (%d)" % n)
-            firsts = list(firsts)
-        else:
-            J = int(acquire)
-            if J <= 0:
-                raise _lib.DccnError("receive_capture(firsts=None) needs acquire = J > 0, the number of frames acquisition may use")
-            key = ("acquire", J)
-            if key not in self._stages:
-                S, K, CP = self._frame_shape()
-                self._stages[key] = CaptureAcquireGroup(S, K, CP, [np.asarray(sc) for sc in self._link_pilots()], J, n, self.device)
-            acq = self._stages[key]
-        cs = self._stage("capture", CaptureSyncGroup, W, cfo, **({"cfo_scope": cfo_scope} if pooled else {}))
-        if firsts is None:
-            firsts = acq.run(caps, los)
-            acq_cfo = acq.cfo
-        _, offsets = cs.run(caps, firsts, strides, outs=dests, los=los)
+        if J:
+            acq = resident_stage(self.stages, CaptureAcquireGroup, *self.shape, self.pilots, J, n, self.device)
+            firsts, acq_cfo = acq.run(caps, los), acq.cfo
+        _, offsets = cs.run(caps, firsts, strides, outs=self.xs, los=los)
         return (offsets, [cs.cfo[i] if cfo else None for i in range(n)],
                 [f if isinstance(f, torch.Tensor) else None for f in firsts], acq_cfo)
 
 
-class RxReceiver(_FrontEnd):
+class RxReceiver:
     """Fixed-shape receive engine of the basic receiver on one GPU: ``receive(x)`` -> :class:`ReceiveResult`.
 
     ``x``: host array or device tensor ``[batch, S, kin, 2]`` (as ``RxEngine.set_batch`` takes it).  ``x_norm`` (``input:0``)
@@ -282,7 +283,6 @@ class RxReceiver(_FrontEnd):
         self.CP = None if CP is None else int(CP)
         self.K = None if K is None else int(K)
         self.pilot_sc = None if pilot_sc is None else np.asarray(pilot_sc, dtype=np.int32).reshape(-1)
-        self._syncs: Dict[tuple, object] = {}
         self.dims, self.batch = dims, int(batch)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -305,9 +305,9 @@ class RxReceiver(_FrontEnd):
         if nws == 0:
             raise _lib.DccnError("dccn_rx_receive_workspace_size refused the shape %r" % (dims,))
         self.ws = torch.empty(nws, dtype=torch.uint8, device=self.device)
-        p = lambda t: 0 if t is None else t.data_ptr()   # noqa: E731
-        self.buffers = RxReceiveBuffers(p(self.x), p(self.params), p(self.x_norm), p(self.fft_out), p(self.z), p(self.packed),
-                                        p(self.llr), p(self.prob), p(self.ws), nws, None)
+        self.buffers = RxReceiveBuffers(*map(ptr, (self.x, self.params, self.x_norm, self.fft_out, self.z, self.packed, self.llr,
+                                                   self.prob, self.ws)), nws, None)
+        self._front = _FrontEnd(type(self).__name__, self.device, self.x, self.CP, self.K, self.pilot_sc)
         self.load_params(params if params is not None else glorot_init(dims, seed))
 
     def view(self, name: str) -> torch.Tensor:
@@ -321,6 +321,13 @@ class RxReceiver(_FrontEnd):
     def close_graph(self):
         """(nothing captured: lets a :class:`~dl_ofdm_amd.session.Session` keep receivers next to its engines)"""
 
+    def _stream(self):
+        return stream_ptr(self.device)
+
+    def _detect(self, offset=None, est=None, first=None, est0=None, est_int=None) -> ReceiveResult:
+        check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
+        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, est, first, est0, est_int)
+
     def receive(self, x=None, sync: int = 0, cfo: bool = False) -> ReceiveResult:
         """Stage ``x`` (``None``: whatever ``self.x`` holds) and run one receive step on the current stream.
 
@@ -332,9 +339,7 @@ class RxReceiver(_FrontEnd):
         ``cfo=True`` (needs ``sync > 0``): the same launch also estimates each frame's carrier-frequency offset from its prefix
         and writes the frames with it taken out (``FrameSync(..., cfo=True)``); ``result.cfo`` holds the estimates, in
         subcarrier spacings."""
-        offset, est = self._stage_frames(x, sync, cfo)
-        check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
-        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, est)
+        return self._detect(*self._front.frames(x, sync, cfo))
 
     def receive_capture(self, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False, acquire: int = 0,
                         lo: int = 0, cfo_scope: str = "frame", cfo_span: int = 0, scale: Optional[float] = None) -> ReceiveResult:
@@ -366,53 +371,21 @@ class RxReceiver(_FrontEnd):
         (``scale=None``: ``2**-15``), converted inside the acquisition and cut launches -- no conversion launch, no float copy --
         and every result is bit for bit that of the float32 capture ``radio.sc16_to_float(cap, scale)``.  Every combination
         above at ``cfo_span=0``; ``cfo_span > 0`` with an int16 capture, and ``scale`` with a float32 one, raise."""
-        offset, est, first, est0, est_int = self._stage_capture(cap, first, stride, sync, cfo, acquire, lo, cfo_scope,
-                                                                cfo_span, scale)
-        check(self.lib.dccn_rx_receive_step(C.byref(self.shape), C.byref(self.buffers), self._stream()), "dccn_rx_receive_step")
-        return ReceiveResult(self.packed, self.llr, self.prob, self.dims.D, self.dims.nbits, offset, est, first, est0, est_int)
+        return self._detect(*self._front.capture(cap, first, stride, sync, cfo, acquire, lo, cfo_scope, cfo_span, scale))
 
 
-def _checked_sc16(cap, scale, cfo_span, what: str) -> None:
-    """an int16 capture, or a ``scale``, judged before anything is launched (acquisition runs ahead of the cut, which would
-    otherwise be the first to look): :func:`~dl_ofdm_amd.sync.capture_format`'s refusals.  A float32 capture without ``scale``
-    passes through untouched."""
-    if scale is not None or (isinstance(cap, torch.Tensor) and cap.dtype == torch.int16):
-        from .sync import capture_format
-        capture_format(cap, scale, what, int(cfo_span))
+def _chain_front(tr, pl) -> _FrontEnd:
+    """the front end of a trainer's resident plan, writing the plan's ``x``; the trainer's plans share their acquisition stages"""
+    if pl.front is None:
+        o = tr.ofdmobj
+        pl.front = _FrontEnd("EqualizerTrainer", tr.device, pl.x, int(o.CP), int(o.K), o.pilotSc, acquires=tr.acquire_stages,
+                             prefix="chain_")
+    return pl.front
 
 
-def _checked_cfo_span(cfo_span, first, acquire, cfo) -> int:
-    """``cfo_span`` as an integer; above 0 it needs acquisition and the carrier offset taken out (the integer is only known
-    through acquisition)"""
-    M = int(cfo_span)
-    if M < 0:
-        raise _lib.DccnError("receive_capture: cfo_span must not be negative")
-    if M and (first is not None or not acquire or not cfo):
-        raise _lib.DccnError("receive_capture(cfo_span=M > 0) needs first=None, acquire=J and cfo=True: the whole subcarrier "
-                             "spacings of the offset are only known through acquisition")
-    return M
-
-
-def _acquired_first(stages: dict, first, acquire: int, cap, lo: int, S: int, K: int, CP: int, pilot_sc, device, cfo_span: int = 0,
-                    scale: Optional[float] = None, engine: str = "RxReceiver"):
-    """``first`` as the cut takes it, and the acquisition's carrier-frequency offset (the fraction, and with ``cfo_span > 0``
-    the integer): an integer or a device tensor passes through; ``None`` runs :class:`~dl_ofdm_amd.sync.CaptureAcquire` over
-    ``acquire`` frames (kept in ``stages``)."""
-    from .sync import CaptureAcquire
-    if first is not None:
-        if acquire:
-            raise _lib.DccnError("receive_capture: give `first` or `acquire`, not both")
-        return first, None, None
-    J = int(acquire)
-    if J <= 0:
-        raise _lib.DccnError("receive_capture(first=None) needs acquire = J > 0, the number of frames acquisition may use")
-    if pilot_sc is None:
-        raise _lib.DccnError("receive_capture(first=None) needs the frame's pilot cells (%s(..., pilot_sc=...))" % engine)
-    key = ("acquire", J, cfo_span) if cfo_span else ("acquire", J)
-    if key not in stages:
-        stages[key] = CaptureAcquire(S, K, CP, pilot_sc, J, device, cfo_span=cfo_span)
-    acq = stages[key]
-    return acq.run(cap, lo, scale=scale), acq.cfo, (acq.cfo_int if cfo_span else None)
+def _chain_result(tr, pl, want_llr, want_prob, *front) -> ReceiveResult:
+    packed, llr, prob = pl.receive(want_llr, want_prob)
+    return ReceiveResult(packed, llr, prob, int(tr.ofdmobj.frame_size), int(tr.FLAGS.nbits), *front)
 
 
 def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: int = 0, cfo: bool = False) -> ReceiveResult:
@@ -424,25 +397,9 @@ def chain_receive(tr, x, want_llr: bool = False, want_prob: bool = False, sync: 
     ``cfo=True`` (needs ``sync > 0``): that launch also takes each frame's carrier-frequency offset out; ``result.cfo``."""
     if not tr.fused_ok:
         raise _lib.DccnError("the chain's receive path needs the fused equaliser step")
-    if cfo and not sync:
-        raise _lib.DccnError("chain_receive(cfo=True) needs sync = W > 0: the offset is read off the timing correlation")
-    batch = int(x.shape[0]) if isinstance(x, torch.Tensor) else int(np.shape(x)[0])
-    pl = tr.resident(batch)
-    offset = est = None
-    if sync:
-        from .sync import FrameSync
-        syncs = pl.__dict__.setdefault("_frame_syncs", {})
-        key = (int(sync), True) if cfo else int(sync)
-        if key not in syncs:
-            o = tr.ofdmobj
-            syncs[key] = FrameSync(int(tr.FLAGS.nsymbol), int(o.K), int(o.CP), int(sync), batch, tr.device, want_metric=False,
-                                   cfo=bool(cfo))
-        _, offset = syncs[key].run(x, out=pl.x)
-        est = syncs[key].cfo
-    else:
-        pl.x.copy_(torch.as_tensor(x, dtype=torch.float32).reshape(pl.x.shape), non_blocking=True)
-    packed, llr, prob = pl.receive(want_llr, want_prob)
-    return ReceiveResult(packed, llr, prob, int(tr.ofdmobj.frame_size), int(tr.FLAGS.nbits), offset, est)
+    _checked_alignment("chain_receive", sync, cfo)             # (ahead of the plan, which this call may be the first to build)
+    pl = tr.resident(int(x.shape[0]) if isinstance(x, torch.Tensor) else int(np.shape(x)[0]))
+    return _chain_result(tr, pl, want_llr, want_prob, *_chain_front(tr, pl).frames(x, sync, cfo))
 
 
 def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, sync: int = 3, cfo: bool = False,
@@ -462,46 +419,27 @@ def chain_receive_capture(tr, cap, first=None, stride: Optional[int] = None, syn
 
     ``cfo=True, cfo_scope="capture"``: one carrier offset for the whole capture, as :meth:`RxReceiver.receive_capture`.
     ``cfo_span = M > 0``: offsets beyond half a subcarrier spacing, as there."""
-    from .sync import CaptureSync, check_cfo_scope
-    check_cfo_scope(cfo, cfo_scope)
-    _checked_sc16(cap, scale, cfo_span, "chain_receive_capture")
-    M = _checked_cfo_span(cfo_span, first, acquire, cfo)
+    what = "chain_receive_capture"
+    W, M = _checked_capture_call(what, cap, first, sync, cfo, acquire, cfo_scope, cfo_span, scale)
     if not tr.fused_ok:
         raise _lib.DccnError("the chain's receive path needs the fused equaliser step")
-    W = int(sync)
-    if W <= 0:
-        raise _lib.DccnError("chain_receive_capture needs sync = W > 0")
     if not isinstance(cap, torch.Tensor) or cap.dim() != 2:
         raise _lib.DccnError("chain_receive_capture takes a device tensor [n, 2]")
-    o = tr.ofdmobj
-    S, K, CP = int(tr.FLAGS.nsymbol), int(o.K), int(o.CP)
-    T = S * (K + CP)
-    step = T if stride is None else int(stride)
-    on_device = first is None or isinstance(first, torch.Tensor)
     if frames is None:
         if isinstance(first, torch.Tensor):
             raise _lib.DccnError("chain_receive_capture: a device tensor `first` needs frames=...")
-        latest = int(lo) + T - 1 if on_device else int(first)
+        o = tr.ofdmobj
+        T = int(tr.FLAGS.nsymbol) * (int(o.K) + int(o.CP))
+        step = T if stride is None else int(stride)
+        latest = int(lo) + T - 1 if first is None else int(first)   # (acquisition: the LAST start of the range)
         room = int(cap.shape[0]) - latest - T - W
         if room < 0 or step < T:
             raise _lib.DccnError("chain_receive_capture: no frame at first = %d fits a capture of %d samples (stride %d)"
                                  % (latest, int(cap.shape[0]), step))
         frames = room // step + 1
     pl = tr.resident(int(frames))
-    syncs = pl.__dict__.setdefault("_capture_syncs", {})
-    key = (W, bool(cfo)) if cfo_scope == "frame" else (W, True, cfo_scope)
-    key += (("span", M),) if M else ()
-    if key not in syncs:
-        syncs[key] = CaptureSync(S, K, CP, W, int(frames), tr.device, want_metric=False, cfo=bool(cfo), cfo_scope=cfo_scope,
-                                 cfo_span=M)
-    cs = syncs[key]
-    first, est0, est_int = _acquired_first(tr.__dict__.setdefault("_capture_acquires", {}), first, acquire, cap, lo, S, K, CP,
-                                           o.pilotSc, tr.device, M, scale)
-    _, offset = cs.run(cap, first, step, out=pl.x, lo=lo,                     # (lo matters to a device `first` only)
-                       acquired=(est_int, est0) if M else None, scale=scale)
-    packed, llr, prob = pl.receive(want_llr, want_prob)
-    return ReceiveResult(packed, llr, prob, int(o.frame_size), int(tr.FLAGS.nbits), offset, cs.cfo,
-                         first if on_device else None, est0, est_int)
+    front = _chain_front(tr, pl).cut(what, cap, first, stride, W, cfo, acquire, lo, cfo_scope, M, scale)
+    return _chain_result(tr, pl, want_llr, want_prob, *front)
 
 
 def group_receive(group, xs, sync: int = 0, cfo: bool = False) -> list:

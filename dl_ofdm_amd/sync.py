@@ -42,7 +42,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import DccnError, check
+from ._lib import DccnError, check, ptr, stream_ptr
 
 
 def rotate_response_(H: torch.Tensor, offset: torch.Tensor) -> torch.Tensor:
@@ -68,11 +68,22 @@ def capture_format(cap, scale, what: str, cfo_span: int = 0):
     """``(is_sc16, scale)`` of a capture handed to ``what``: a contiguous device tensor ``float32 [n, 2]`` (``scale`` must be
     ``None``) or ``int16 [n, 2]`` (``scale=None``: ``2**-15``; otherwise finite and positive).  :class:`DccnError` for anything
     else, and for an int16 capture where ``cfo_span > 0``: the wide entries are float32-only."""
-    if not isinstance(cap, torch.Tensor) or cap.device.type != "cuda":
+    return _checked_capture(cap, scale, what, cfo_span)
+
+
+def _on_device(t) -> bool:
+    return isinstance(t, torch.Tensor) and t.device.type == "cuda"
+
+
+def _checked_capture(cap, scale, what: str, cfo_span: int = 0, float32_only: bool = False):
+    """:func:`capture_format`, the one statement of what a capture is; ``float32_only``: for the group classes, whose entries
+    read no int16"""
+    if not _on_device(cap):
         raise DccnError("%s takes a device tensor; there is no CPU fallback" % what)
-    if cap.dtype not in (torch.float32, torch.int16) or cap.dim() != 2 or cap.shape[1] != 2 or not cap.is_contiguous():
-        raise DccnError("%s: cap must be a contiguous float32 [n, 2] or int16 [n, 2] tensor, got %s %r"
-                        % (what, cap.dtype, tuple(cap.shape)))
+    dtypes = (torch.float32,) if float32_only else (torch.float32, torch.int16)
+    if cap.dtype not in dtypes or cap.dim() != 2 or cap.shape[1] != 2 or not cap.is_contiguous():
+        raise DccnError("%s: cap must be a contiguous float32 [n, 2]%s tensor, got %s %r"
+                        % (what, "" if float32_only else " or int16 [n, 2]", cap.dtype, tuple(cap.shape)))
     if cap.dtype == torch.float32:
         if scale is not None:
             raise DccnError("%s: `scale` belongs to an int16 capture; a float32 capture is taken as it is" % what)
@@ -100,7 +111,125 @@ def check_cfo_scope(cfo, cfo_scope) -> bool:
     return cfo_scope == "capture"
 
 
-class FrameSync:
+def resident_stage(cache: dict, cls, *args):
+    """The stage ``cls(*args)``, built on first use and kept in ``cache`` from then on: the key is the class and the constructor
+    arguments themselves (hashable ones: pilot cells as tuples).  Positional only: every receive call comes through here, and a
+    lookup is then one small tuple and one dictionary access."""
+    key = (cls, args)
+    stage = cache.get(key)
+    if stage is None:
+        stage = cache[key] = cls(*args)
+    return stage
+
+
+def group_size(lib, n_links: int, what: str) -> int:
+    gmax = int(lib.dccn_chain_group_max())
+    if not (1 <= int(n_links) <= gmax):
+        raise ValueError("%s: 1..%d links per group" % (what, gmax))
+    return int(n_links)
+
+
+def _per_link(v, n: int, what: str) -> list:
+    """one entry per link: a scalar (or ``None``) serves every link, a list or tuple must have ``n`` entries"""
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise ValueError("%s: one entry per link (%d), got %d" % (what, n, len(v)))
+        return list(v)
+    return [v] * n
+
+
+def _checked_frames(x, want: tuple, what: str) -> torch.Tensor:
+    if not _on_device(x):
+        raise DccnError("%s takes a device tensor; there is no CPU fallback" % what)
+    if x.dtype != torch.float32 or tuple(x.shape) != want or not x.is_contiguous():
+        raise DccnError("%s: x must be a contiguous float32 %r tensor, got %s %r" % (what, want, x.dtype, tuple(x.shape)))
+    return x
+
+
+def _start(first, lo, cap: torch.Tensor, what: str) -> tuple:
+    """The start of a cut as every call and link table states it, ``(first, first_dev, lo)``: an integer ``first``, or a device
+    tensor (where :class:`CaptureAcquire` left it: nothing is read back) with the origin of the range it lies in."""
+    if not isinstance(first, torch.Tensor):
+        return int(first), None, 0
+    if lo is None:
+        raise DccnError("%s: a device tensor `first` needs its lo, the origin of the range [lo, lo + T) it lies in" % what)
+    if first.device != cap.device or first.dtype != torch.int64 or first.numel() != 1 or not first.is_contiguous():
+        raise DccnError("%s: a device `first` must be an int64 tensor of one element on the capture's device" % what)
+    return 0, first.data_ptr(), int(lo)
+
+
+class _Stage:
+    """What every stage of this module is built on, stated once: the library handle, the device refusal, the frame shape, the
+    ``*_supported`` refusal and the resident tensors.  A group (``n_links`` given) keeps a list with one tensor per link where a
+    solo stage keeps the tensor."""
+
+    def __init__(self, S, K, CP, device, n_links=None):
+        self.lib = _lib.load()
+        name = type(self).__name__
+        if n_links is not None:
+            self.n_links = group_size(self.lib, n_links, name)
+        self._solo = n_links is None
+        self.S, self.K, self.CP = int(S), int(K), int(CP)
+        self.T = self.S * (self.K + self.CP)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise DccnError("%s needs a CUDA (ROCm) device; there is no CPU fallback" % name)
+
+    def _require(self, query: str, needs: str, **shape) -> None:
+        if not getattr(self.lib, query)(*shape.values()):
+            raise DccnError("%s refused %s (needs %s)" % (query, " ".join("%s=%d" % kv for kv in shape.items()), needs))
+
+    def _resident(self, *shape, dtype=torch.float32, make=torch.zeros):
+        if self._solo:
+            return make(*shape, dtype=dtype, device=self.device)
+        return [make(*shape, dtype=dtype, device=self.device) for _ in range(self.n_links)]
+
+    def _stream(self):
+        return stream_ptr(self.device)
+
+
+def _link_ptr(tensors, i: int):
+    """link i's pointer of a per-link list the stage may have been built without"""
+    return None if tensors is None else tensors[i].data_ptr()
+
+
+ALIGN_NEEDS = "1 <= W <= CP, 2 W + CP <= 64, an even frame length"
+CUT_NEEDS = ALIGN_NEEDS + ", four windows of T + 2 W samples within 64 KB"
+
+
+class _SyncStage(_Stage):
+    """the alignment and cut stages: the window, the frame count, resident ``offset`` / ``metric`` / ``cfo`` and the checked
+    destination"""
+
+    def __init__(self, query, needs, S, K, CP, W, frames, device, out_kin, want_metric, cfo, n_links=None, cfo_len=None):
+        super().__init__(S, K, CP, device, n_links)
+        self.W, self.frames = int(W), int(frames)
+        self.out_kin = self.K + self.CP if out_kin is None else int(out_kin)
+        self._require(query, needs, S=self.S, K=self.K, CP=self.CP, W=self.W)
+        if self.out_kin not in (self.K + self.CP, self.K) or self.frames <= 0:
+            raise DccnError("%s: out_kin must be K + CP or K and frames positive (got out_kin=%d, frames=%d)"
+                            % (type(self).__name__, self.out_kin, self.frames))
+        self.offset = self._resident(self.frames, dtype=torch.int32)
+        self.metric = self._resident(self.frames, 2 * self.W + 1) if want_metric else None
+        self.cfo = self._resident(self.frames if cfo_len is None else cfo_len) if cfo else None
+        self.out = None         # allocated by the first run() that is not given a destination
+
+    def _dest(self, out, device, what: str):
+        """where ``run`` writes: this stage's own buffer(s), allocated on first use, or the caller's ``out``, checked -- per link
+        in a group.  ``device``: the input's."""
+        want = (self.frames, self.S, self.out_kin, 2)
+        if out is None:
+            if self.out is None:
+                self.out = self._resident(*want, make=torch.empty)
+            return self.out
+        outs = [out] if self._solo else _per_link(list(out), self.n_links, what + "(outs)")
+        for o in outs:
+            if not _on_device(o) or o.device != device or o.dtype != torch.float32 or tuple(o.shape) != want or not o.is_contiguous():
+                raise DccnError("%s: out must be a contiguous float32 %r tensor on %s" % (what, want, device))
+        return out if self._solo else outs
+
+
+class FrameSync(_SyncStage):
     """Fixed-shape alignment stage on one GPU: ``run(x) -> (aligned, offset)``.
 
     ``x``: device tensor ``float32 [frames, S, K + CP, 2]``.  ``out_kin``: ``K + CP`` (default: the aligned frames) or ``K`` (the
@@ -113,66 +242,47 @@ class FrameSync:
 
     def __init__(self, S: int, K: int, CP: int, W: int, frames: int, device="cuda", out_kin: Optional[int] = None,
                  want_metric: bool = True, cfo: bool = False):
-        self.lib = _lib.load()
-        self.S, self.K, self.CP, self.W, self.frames = int(S), int(K), int(CP), int(W), int(frames)
-        self.out_kin = self.K + self.CP if out_kin is None else int(out_kin)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise DccnError("FrameSync needs a CUDA (ROCm) device; there is no CPU fallback")
-        if not self.lib.dccn_frame_sync_supported(self.S, self.K, self.CP, self.W):
-            raise DccnError("dccn_frame_sync_supported refused S=%d K=%d CP=%d W=%d (needs 1 <= W <= CP, 2 W + CP <= 64, an even "
-                            "frame length)" % (self.S, self.K, self.CP, self.W))
-        if self.out_kin not in (self.K + self.CP, self.K) or self.frames <= 0:
-            raise DccnError("FrameSync: out_kin must be K + CP or K and frames positive (got out_kin=%d, frames=%d)"
-                            % (self.out_kin, self.frames))
-        self.offset = torch.zeros(self.frames, dtype=torch.int32, device=self.device)
-        self.metric = (torch.zeros(self.frames, 2 * self.W + 1, dtype=torch.float32, device=self.device) if want_metric else None)
-        self.cfo = torch.zeros(self.frames, dtype=torch.float32, device=self.device) if cfo else None
-        self.out = None         # allocated by the first run() that is not given a destination
+        super().__init__("dccn_frame_sync_supported", ALIGN_NEEDS, S, K, CP, W, frames, device, out_kin, want_metric, cfo)
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _device_frames(self, x) -> torch.Tensor:
-        if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
-            raise DccnError("FrameSync.run takes a device tensor; there is no CPU fallback")
-        want = (self.frames, self.S, self.K + self.CP, 2)
-        if x.dtype != torch.float32 or tuple(x.shape) != want or not x.is_contiguous():
-            raise DccnError("FrameSync.run: x must be a contiguous float32 %r tensor, got %s %r" % (want, x.dtype, tuple(x.shape)))
-        return x
-
-    def _launch(self, x: torch.Tensor, out: Optional[torch.Tensor]) -> None:
+    def _launch(self, x, out, write: bool):
         """the one launch: ``dccn_frame_sync``, or ``dccn_frame_sync_cfo`` of a stage built with ``cfo=True``"""
-        head = (x.data_ptr(), self.frames, self.S, self.K, self.CP, self.W, self.out_kin, None if out is None else out.data_ptr(),
-                self.offset.data_ptr())
-        tail = (None if self.metric is None else self.metric.data_ptr(), self._stream())
-        if self.cfo is None:
-            check(self.lib.dccn_frame_sync(*head, *tail), "dccn_frame_sync")
-        else:
-            check(self.lib.dccn_frame_sync_cfo(*head, self.cfo.data_ptr(), *tail), "dccn_frame_sync_cfo")
+        x = _checked_frames(x, (self.frames, self.S, self.K + self.CP, 2), "FrameSync.run")
+        out = self._dest(out, x.device, "FrameSync.run") if write else None
+        entry = "dccn_frame_sync" if self.cfo is None else "dccn_frame_sync_cfo"
+        check(getattr(self.lib, entry)(x.data_ptr(), self.frames, self.S, self.K, self.CP, self.W, self.out_kin, ptr(out),
+                                       self.offset.data_ptr(), *(() if self.cfo is None else (self.cfo.data_ptr(),)),
+                                       ptr(self.metric), self._stream()), entry)
+        return out
 
     def run(self, x: torch.Tensor, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Estimate every frame's offset and write the aligned frames to ``out`` (``None``: this object's own buffer), on the
         current stream.  ``out`` must not overlap ``x``."""
-        x = self._device_frames(x)
-        want = (self.frames, self.S, self.out_kin, 2)
-        if out is None:
-            if self.out is None:
-                self.out = torch.empty(*want, dtype=torch.float32, device=self.device)
-            out = self.out
-        elif (not isinstance(out, torch.Tensor) or out.device != x.device or out.dtype != torch.float32
-              or tuple(out.shape) != want or not out.is_contiguous()):
-            raise DccnError("FrameSync.run: out must be a contiguous float32 %r tensor on %s" % (want, x.device))
-        self._launch(x, out)
-        return out, self.offset
+        return self._launch(x, out, True), self.offset
 
     def offsets(self, x: torch.Tensor) -> torch.Tensor:
         """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``."""
-        self._launch(self._device_frames(x), None)
+        self._launch(x, None, False)
         return self.offset
 
 
-class CaptureSync:
+# (pooled, cfo_span > 0, int16 capture, start on the device; None: either) -> the entry, and which of the start fields
+# (first, first_dev, lo) it takes.  Every argument list is regular (include/dccn.h):
+#   cap, n_samples, [scale], start, stride, frames, S, K, CP, W, out_kin, x_out, offset, cfo, metric, [cfo_int_dev, cfo_frac_dev],
+#   [workspace, workspace_bytes], stream
+_CUT_ROWS = (
+    (False, False, False, False, "dccn_capture_sync", slice(0, 1)),
+    (False, False, False, True, "dccn_capture_sync_at", slice(1, 3)),
+    (False, True, False, True, "dccn_capture_sync_wide", slice(1, 3)),      # (the integer is only known through acquisition)
+    (False, False, True, None, "dccn_capture_sync_sc16", slice(0, 3)),
+    (True, False, False, None, "dccn_capture_sync_pooled", slice(0, 3)),
+    (True, True, False, None, "dccn_capture_sync_pooled_wide", slice(0, 3)),
+    (True, False, True, None, "dccn_capture_sync_pooled_sc16", slice(0, 3)),
+)
+CUT_ENTRIES = {(pooled, wide, sc16, on_dev): (entry, fields) for pooled, wide, sc16, either, entry, fields in _CUT_ROWS
+               for on_dev in ((False, True) if either is None else (either,))}
+
+
+class CaptureSync(_SyncStage):
     """Frames cut from ONE CONTIGUOUS CAPTURE at their estimated starts (``dccn_capture_sync``): ``run(cap, first) -> (frames_out,
     offset)``.
 
@@ -202,36 +312,18 @@ class CaptureSync:
     def __init__(self, S: int, K: int, CP: int, W: int, frames: int, device="cuda", out_kin: Optional[int] = None,
                  want_metric: bool = True, cfo: bool = False, cfo_scope: str = "frame", cfo_span: int = 0):
         self.pooled = check_cfo_scope(cfo, cfo_scope)
-        self.lib = _lib.load()
-        self.S, self.K, self.CP, self.W, self.frames = int(S), int(K), int(CP), int(W), int(frames)
         self.cfo_span = int(cfo_span)
         if self.cfo_span and not cfo:
             raise DccnError("CaptureSync(cfo_span=M > 0) needs cfo=True: there is no carrier offset to unwrap without it")
-        if not (0 <= self.cfo_span <= max(self.K // 2 - 1, 0)):
-            raise DccnError("CaptureSync: cfo_span must lie in [0, K / 2 - 1], got %d at K=%d" % (self.cfo_span, self.K))
-        self.T = self.S * (self.K + self.CP)
-        self.out_kin = self.K + self.CP if out_kin is None else int(out_kin)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise DccnError("CaptureSync needs a CUDA (ROCm) device; there is no CPU fallback")
-        if not self.lib.dccn_capture_sync_supported(self.S, self.K, self.CP, self.W):
-            raise DccnError("dccn_capture_sync_supported refused S=%d K=%d CP=%d W=%d (needs 1 <= W <= CP, 2 W + CP <= 64, an "
-                            "even frame length, four windows of T + 2 W samples within 64 KB)" % (self.S, self.K, self.CP, self.W))
-        if self.out_kin not in (self.K + self.CP, self.K) or self.frames <= 0:
-            raise DccnError("CaptureSync: out_kin must be K + CP or K and frames positive (got out_kin=%d, frames=%d)"
-                            % (self.out_kin, self.frames))
-        self.offset = torch.zeros(self.frames, dtype=torch.int32, device=self.device)
-        self.metric = (torch.zeros(self.frames, 2 * self.W + 1, dtype=torch.float32, device=self.device) if want_metric else None)
-        self.cfo = torch.zeros(1 if self.pooled else self.frames, dtype=torch.float32, device=self.device) if cfo else None
+        if not (0 <= self.cfo_span <= max(int(K) // 2 - 1, 0)):
+            raise DccnError("CaptureSync: cfo_span must lie in [0, K / 2 - 1], got %d at K=%d" % (self.cfo_span, int(K)))
+        super().__init__("dccn_capture_sync_supported", CUT_NEEDS, S, K, CP, W, frames, device, out_kin, want_metric, cfo,
+                         cfo_len=1 if self.pooled else None)
         self.ws = None
         if self.pooled:
             size = (self.lib.dccn_capture_sync_pooled_wide_workspace_size if self.cfo_span
                     else self.lib.dccn_capture_sync_pooled_workspace_size)
-            self.ws = torch.empty(int(size(self.frames)), dtype=torch.uint8, device=self.device)
-        self.out = None         # allocated by the first run() that is not given a destination
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            self.ws = self._resident(int(size(self.frames)), dtype=torch.uint8, make=torch.empty)
 
     def _acquired_pair(self, acquired, cap) -> tuple:
         """the pointers of ``(cfo_int, cfo_frac)``: ``()`` for a stage built with ``cfo_span=0``, which takes none"""
@@ -246,57 +338,25 @@ class CaptureSync:
                             "element on the capture's device, what CaptureAcquire(cfo_span=M) left there")
         return (acquired[0].data_ptr(), acquired[1].data_ptr())
 
-    def _launch(self, cap, first, stride, out: Optional[torch.Tensor], lo: Optional[int] = None, acquired=None, scale=None) -> None:
-        sc16, scale = capture_format(cap, scale, "CaptureSync", self.cfo_span)
-        stride = self.T if stride is None else int(stride)
-        p = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+    def _launch(self, cap, first, stride, out, write: bool, lo, acquired, scale):
+        """the one call: the entry of :data:`CUT_ENTRIES` (one launch; the pooled ones estimate, sum and cut: three)"""
+        sc16, scale = _checked_capture(cap, scale, "CaptureSync", self.cfo_span)
         pair = self._acquired_pair(acquired, cap)
-        if self.pooled:
-            return self._launch_pooled(cap, first, stride, out, lo, pair, scale if sc16 else None)
-        if pair and not isinstance(first, torch.Tensor):
+        start = _start(first, lo, cap, "CaptureSync")
+        if self.pooled and not write:
+            raise DccnError('CaptureSync(cfo_scope="capture") has no offsets-only call: the pooled entry writes the frames')
+        row = CUT_ENTRIES.get((self.pooled, bool(pair), sc16, start[1] is not None))
+        if row is None:
             raise DccnError("CaptureSync(cfo_span=M > 0): the per-frame cut reads the start where acquisition left it, a device "
                             "tensor `first` with lo=...")
-        tail = (stride, self.frames, self.S, self.K, self.CP, self.W, self.out_kin, p(out), self.offset.data_ptr(), p(self.cfo),
-                p(self.metric), *pair, self._stream())
-        on_dev = isinstance(first, torch.Tensor)
-        if on_dev:
-            # the start is on the device (CaptureAcquire left it there): nothing is read back
-            if lo is None:
-                raise DccnError("CaptureSync: a device tensor `first` needs lo=..., the origin of the range [lo, lo + T) it lies in")
-            if first.device != cap.device or first.dtype != torch.int64 or first.numel() != 1 or not first.is_contiguous():
-                raise DccnError("CaptureSync: a device `first` must be an int64 tensor of one element on the capture's device")
-        if sc16:
-            check(self.lib.dccn_capture_sync_sc16(cap.data_ptr(), int(cap.shape[0]), scale, 0 if on_dev else int(first),
-                                                  first.data_ptr() if on_dev else None, int(lo) if on_dev else 0, *tail),
-                  "dccn_capture_sync_sc16")
-        elif on_dev:
-            entry = "dccn_capture_sync_wide" if pair else "dccn_capture_sync_at"
-            check(getattr(self.lib, entry)(cap.data_ptr(), int(cap.shape[0]), first.data_ptr(), int(lo), *tail), entry)
-        else:
-            check(self.lib.dccn_capture_sync(cap.data_ptr(), int(cap.shape[0]), int(first), *tail), "dccn_capture_sync")
-
-    def _launch_pooled(self, cap, first, stride: int, out: Optional[torch.Tensor], lo: Optional[int], pair: tuple = (),
-                       scale: Optional[float] = None) -> None:
-        """``dccn_capture_sync_pooled`` (``pair``: ``dccn_capture_sync_pooled_wide``; ``scale``: ``dccn_capture_sync_pooled_sc16``
-        on an int16 capture): estimate, sum and cut, three launches on the current stream"""
-        if out is None:
-            raise DccnError('CaptureSync(cfo_scope="capture") has no offsets-only call: the pooled entry writes the frames')
-        on_dev = isinstance(first, torch.Tensor)
-        if on_dev:
-            if lo is None:
-                raise DccnError("CaptureSync: a device tensor `first` needs lo=..., the origin of the range [lo, lo + T) it lies in")
-            if first.device != cap.device or first.dtype != torch.int64 or first.numel() != 1 or not first.is_contiguous():
-                raise DccnError("CaptureSync: a device `first` must be an int64 tensor of one element on the capture's device")
-        entry = "dccn_capture_sync_pooled_wide" if pair else "dccn_capture_sync_pooled"
-        if scale is not None:
-            entry = "dccn_capture_sync_pooled_sc16"
-        fmt = () if scale is None else (scale,)
-        check(getattr(self.lib, entry)(cap.data_ptr(), int(cap.shape[0]), *fmt, 0 if on_dev else int(first),
-                                       first.data_ptr() if on_dev else None, int(lo) if on_dev else 0, stride,
-                                       self.frames, self.S, self.K, self.CP, self.W, self.out_kin, out.data_ptr(),
-                                       self.offset.data_ptr(), self.cfo.data_ptr(),
-                                       None if self.metric is None else self.metric.data_ptr(), *pair, self.ws.data_ptr(),
-                                       int(self.ws.numel()), self._stream()), entry)
+        out = self._dest(out, cap.device, "CaptureSync.run") if write else None
+        entry, fields = row
+        check(getattr(self.lib, entry)(cap.data_ptr(), int(cap.shape[0]), *((scale,) if sc16 else ()), *start[fields],
+                                       self.T if stride is None else int(stride), self.frames, self.S, self.K, self.CP, self.W,
+                                       self.out_kin, ptr(out), self.offset.data_ptr(), ptr(self.cfo), ptr(self.metric), *pair,
+                                       *(() if self.ws is None else (self.ws.data_ptr(), int(self.ws.numel()))), self._stream()),
+              entry)
+        return out
 
     def run(self, cap: torch.Tensor, first, stride: Optional[int] = None, out: Optional[torch.Tensor] = None,
             lo: Optional[int] = None, acquired=None, scale: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -307,26 +367,46 @@ class CaptureSync:
         launch reads the start from device memory and keeps it inside ``[lo, lo + T - 1]``; every window must lie inside the
         capture for every start in that range).  ``acquired``: the pair of a stage built with ``cfo_span = M > 0``.
         ``scale``: the value of one count of an ``int16`` capture (``None``: ``2**-15``); not given with a float32 capture."""
-        want = (self.frames, self.S, self.out_kin, 2)
-        if out is None:
-            if self.out is None:
-                self.out = torch.empty(*want, dtype=torch.float32, device=self.device)
-            out = self.out
-        elif (not isinstance(out, torch.Tensor) or out.device.type != "cuda" or out.dtype != torch.float32
-              or tuple(out.shape) != want or not out.is_contiguous()):
-            raise DccnError("CaptureSync.run: out must be a contiguous float32 %r device tensor" % (want,))
-        self._launch(cap, first, stride, out, lo, acquired, scale)
-        return out, self.offset
+        return self._launch(cap, first, stride, out, True, lo, acquired, scale), self.offset
 
     def offsets(self, cap: torch.Tensor, first, stride: Optional[int] = None, lo: Optional[int] = None, acquired=None,
                 scale: Optional[float] = None) -> torch.Tensor:
         """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``.  ``first`` / ``lo`` / ``acquired`` /
         ``scale`` as :meth:`run`."""
-        self._launch(cap, first, stride, None, lo, acquired, scale)
+        self._launch(cap, first, stride, None, False, lo, acquired, scale)
         return self.offset
 
 
-class CaptureAcquire:
+class _AcquireStage(_Stage):
+    """the acquisition stages: the pilot cells (per link in a group, of one length), the ``*_supported`` refusals, resident
+    ``first`` / ``cfo`` / ``sym_metric`` / ``phase_metric`` and the workspace"""
+
+    def __init__(self, S, K, CP, pilot_sc, J, device, n_links=None, cfo_span=0):
+        super().__init__(S, K, CP, device, n_links)
+        self.J, self.cfo_span = int(J), int(cfo_span)
+        per_link = (not self._solo and isinstance(pilot_sc, (list, tuple)) and len(pilot_sc) > 0
+                    and hasattr(pilot_sc[0], "__len__"))
+        scs = [torch.as_tensor(sc).reshape(-1).to(torch.int32)
+               for sc in (_per_link(list(pilot_sc), self.n_links, "pilot_sc") if per_link else [pilot_sc])]
+        self.n_pilot = int(scs[0].numel())
+        if any(int(sc.numel()) != self.n_pilot for sc in scs):
+            raise DccnError("%s: the links' pilot cells must be of one length (n_pilot is the call's)" % type(self).__name__)
+        shape, M = dict(S=self.S, K=self.K, CP=self.CP, n_pilot=self.n_pilot, J=self.J), self.cfo_span
+        self._require("dccn_capture_acquire_supported", "S <= 64, CP <= K, K + CP <= 1024, 2 <= n_pilot <= 256, 1 <= J <= 256",
+                      **shape)
+        if M:
+            self._require("dccn_capture_acquire_wide_supported", "0 <= cfo_span <= K / 2 - 1", **shape, cfo_span=M)
+        scs = [sc.to(self.device).contiguous() for sc in scs]
+        self.pilot_sc = scs[0] if self._solo else (scs if per_link else scs * self.n_links)
+        self.first = self._resident(1, dtype=torch.int64)
+        self.cfo = self._resident(1)
+        self.sym_metric = self._resident(self.K + self.CP)
+        self.phase_metric = self._resident(self.S, 2 * M + 1) if M else self._resident(self.S)
+        size = self.lib.dccn_capture_acquire_wide_workspace_size if M else self.lib.dccn_capture_acquire_workspace_size
+        self.ws = self._resident(int(size(*shape.values(), *((M,) if M else ()))), dtype=torch.uint8, make=torch.empty)
+
+
+class CaptureAcquire(_AcquireStage):
     """Coarse acquisition inside a contiguous capture (``dccn_capture_acquire``): ``run(cap, lo) -> first``, the sample in
     ``[lo, lo + T)`` at which a frame starts, as a device ``int64`` tensor of one element -- what :meth:`CaptureSync.run` takes
     as ``first`` together with the same ``lo``.  Nothing is read back and nothing synchronises.
@@ -349,171 +429,57 @@ class CaptureAcquire:
     call on the converted capture, one object for both dtypes); not with ``cfo_span > 0``."""
 
     def __init__(self, S: int, K: int, CP: int, pilot_sc, J: int, device="cuda", cfo_span: int = 0):
-        self.lib = _lib.load()
-        self.S, self.K, self.CP, self.J = int(S), int(K), int(CP), int(J)
-        self.cfo_span = int(cfo_span)
-        self.T = self.S * (self.K + self.CP)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise DccnError("CaptureAcquire needs a CUDA (ROCm) device; there is no CPU fallback")
-        sc = torch.as_tensor(pilot_sc).reshape(-1).to(torch.int32)
-        self.n_pilot = int(sc.numel())
-        if not self.lib.dccn_capture_acquire_supported(self.S, self.K, self.CP, self.n_pilot, self.J):
-            raise DccnError("dccn_capture_acquire_supported refused S=%d K=%d CP=%d n_pilot=%d J=%d (needs S <= 64, CP <= K, "
-                            "K + CP <= 1024, 2 <= n_pilot <= 256, 1 <= J <= 256)" % (self.S, self.K, self.CP, self.n_pilot, self.J))
-        self.pilot_sc = sc.to(self.device).contiguous()
-        self.first = torch.zeros(1, dtype=torch.int64, device=self.device)
-        self.cfo = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.sym_metric = torch.zeros(self.K + self.CP, dtype=torch.float32, device=self.device)
-        self.phase_metric = torch.zeros(self.S, dtype=torch.float32, device=self.device)
-        self.cfo_int = torch.zeros(1, dtype=torch.int32, device=self.device)
-        M = self.cfo_span
-        if M:
-            if not self.lib.dccn_capture_acquire_wide_supported(self.S, self.K, self.CP, self.n_pilot, self.J, M):
-                raise DccnError("dccn_capture_acquire_wide_supported refused cfo_span=%d at K=%d (needs 0 <= cfo_span <= K / 2 - 1)"
-                                % (M, self.K))
-            self.phase_metric = torch.zeros(self.S, 2 * M + 1, dtype=torch.float32, device=self.device)
-            nws = int(self.lib.dccn_capture_acquire_wide_workspace_size(self.S, self.K, self.CP, self.n_pilot, self.J, M))
-        else:
-            nws = int(self.lib.dccn_capture_acquire_workspace_size(self.S, self.K, self.CP, self.n_pilot, self.J))
-        self.ws = torch.empty(nws, dtype=torch.uint8, device=self.device)
+        super().__init__(S, K, CP, pilot_sc, J, device, cfo_span=cfo_span)
+        self.cfo_int = self._resident(1, dtype=torch.int32)
 
     def run(self, cap: torch.Tensor, lo: int = 0, scale: Optional[float] = None) -> torch.Tensor:
         """Three launches on the current stream; returns ``self.first``.  ``scale``: the value of one count of an ``int16``
         capture (``None``: ``2**-15``); not given with a float32 capture."""
-        sc16, scale = capture_format(cap, scale, "CaptureAcquire", self.cfo_span)
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        if sc16:
-            check(self.lib.dccn_capture_acquire_sc16(cap.data_ptr(), int(cap.shape[0]), scale, int(lo), self.J, self.S, self.K,
-                                                     self.CP, self.pilot_sc.data_ptr(), self.n_pilot, self.first.data_ptr(),
-                                                     self.cfo.data_ptr(), self.sym_metric.data_ptr(), self.phase_metric.data_ptr(),
-                                                     self.ws.data_ptr(), int(self.ws.numel()), stream), "dccn_capture_acquire_sc16")
-            return self.first
-        if self.cfo_span:
-            check(self.lib.dccn_capture_acquire_wide(cap.data_ptr(), int(cap.shape[0]), int(lo), self.J, self.S, self.K, self.CP,
-                                                     self.pilot_sc.data_ptr(), self.n_pilot, self.cfo_span, self.first.data_ptr(),
-                                                     self.cfo.data_ptr(), self.cfo_int.data_ptr(), self.sym_metric.data_ptr(),
-                                                     self.phase_metric.data_ptr(), self.ws.data_ptr(), int(self.ws.numel()),
-                                                     stream), "dccn_capture_acquire_wide")
-            return self.first
-        check(self.lib.dccn_capture_acquire(cap.data_ptr(), int(cap.shape[0]), int(lo), self.J, self.S, self.K, self.CP,
-                                            self.pilot_sc.data_ptr(), self.n_pilot, self.first.data_ptr(), self.cfo.data_ptr(),
-                                            self.sym_metric.data_ptr(), self.phase_metric.data_ptr(), self.ws.data_ptr(),
-                                            int(self.ws.numel()), stream), "dccn_capture_acquire")
+        sc16, scale = _checked_capture(cap, scale, "CaptureAcquire", self.cfo_span)
+        M = self.cfo_span
+        entry = "dccn_capture_acquire" + ("_sc16" if sc16 else "_wide" if M else "")
+        check(getattr(self.lib, entry)(cap.data_ptr(), int(cap.shape[0]), *((scale,) if sc16 else ()), int(lo), self.J, self.S,
+                                       self.K, self.CP, self.pilot_sc.data_ptr(), self.n_pilot, *((M,) if M else ()),
+                                       self.first.data_ptr(), self.cfo.data_ptr(), *((self.cfo_int.data_ptr(),) if M else ()),
+                                       self.sym_metric.data_ptr(), self.phase_metric.data_ptr(), self.ws.data_ptr(),
+                                       int(self.ws.numel()), self._stream()), entry)
         return self.first
 
 
 # ---- the same stages for several links per launch (include/dccn.h "the receive front end for several links") -------------------
-def _group_size(lib, n_links: int, what: str) -> int:
-    gmax = int(lib.dccn_chain_group_max())
-    if not (1 <= int(n_links) <= gmax):
-        raise ValueError("%s: 1..%d links per group" % (what, gmax))
-    return int(n_links)
-
-
-def _per_link(v, n: int, what: str) -> list:
-    """one entry per link: a scalar (or ``None``) serves every link, a list or tuple must have ``n`` entries"""
-    if isinstance(v, (list, tuple)):
-        if len(v) != n:
-            raise ValueError("%s: one entry per link (%d), got %d" % (what, n, len(v)))
-        return list(v)
-    return [v] * n
-
-
-def _device_capture(cap, what: str) -> torch.Tensor:
-    if not isinstance(cap, torch.Tensor) or cap.device.type != "cuda":
-        raise DccnError("%s takes device tensors; there is no CPU fallback" % what)
-    if cap.dtype != torch.float32 or cap.dim() != 2 or cap.shape[1] != 2 or not cap.is_contiguous():
-        raise DccnError("%s: a capture must be a contiguous float32 [n, 2] tensor, got %s %r" % (what, cap.dtype, tuple(cap.shape)))
-    return cap
-
-
-class _SyncGroupBase:
-    """what :class:`FrameSyncGroup` and :class:`CaptureSyncGroup` share: the shape, per-link resident ``offset`` / ``cfo`` /
-    ``metric`` (lists of tensors, entry i as the solo class keeps it for link i) and the output buffers"""
-
-    def __init__(self, supported, S, K, CP, W, frames, n_links, device, out_kin, want_metric, cfo, cfo_len=None):
-        self.lib = _lib.load()
-        name = type(self).__name__
-        self.n_links = _group_size(self.lib, n_links, name)
-        self.S, self.K, self.CP, self.W, self.frames = int(S), int(K), int(CP), int(W), int(frames)
-        self.T = self.S * (self.K + self.CP)
-        self.out_kin = self.K + self.CP if out_kin is None else int(out_kin)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise DccnError("%s needs a CUDA (ROCm) device; there is no CPU fallback" % name)
-        if not getattr(self.lib, supported)(self.S, self.K, self.CP, self.W):
-            raise DccnError("%s refused S=%d K=%d CP=%d W=%d" % (supported, self.S, self.K, self.CP, self.W))
-        if self.out_kin not in (self.K + self.CP, self.K) or self.frames <= 0:
-            raise DccnError("%s: out_kin must be K + CP or K and frames positive (got out_kin=%d, frames=%d)"
-                            % (name, self.out_kin, self.frames))
-        n, dev = self.n_links, self.device
-        self.offset = [torch.zeros(self.frames, dtype=torch.int32, device=dev) for _ in range(n)]
-        self.metric = ([torch.zeros(self.frames, 2 * self.W + 1, dtype=torch.float32, device=dev) for _ in range(n)]
-                       if want_metric else None)
-        ncfo = self.frames if cfo_len is None else int(cfo_len)
-        self.cfo = [torch.zeros(ncfo, dtype=torch.float32, device=dev) for _ in range(n)] if cfo else None
-        self.out = None         # allocated by the first run() that is not given destinations
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _outs(self, outs) -> list:
-        want = (self.frames, self.S, self.out_kin, 2)
-        if outs is None:
-            if self.out is None:
-                self.out = [torch.empty(*want, dtype=torch.float32, device=self.device) for _ in range(self.n_links)]
-            return self.out
-        outs = _per_link(list(outs), self.n_links, type(self).__name__ + ".run(outs)")
-        for o in outs:
-            if (not isinstance(o, torch.Tensor) or o.device.type != "cuda" or o.dtype != torch.float32 or tuple(o.shape) != want
-                    or not o.is_contiguous()):
-                raise DccnError("%s.run: every out must be a contiguous float32 %r device tensor" % (type(self).__name__, want))
-        return outs
-
-    def _opt(self, tensors, i):
-        return None if tensors is None else tensors[i].data_ptr()
-
-
-class FrameSyncGroup(_SyncGroupBase):
+class FrameSyncGroup(_SyncStage):
     """:class:`FrameSync` for up to ``dccn_chain_group_max()`` links in ONE launch (``dccn_frame_sync_grouped``):
     ``run(xs) -> (aligned, offsets)``, lists with one entry per link, entry i bit for bit what ``FrameSync.run(xs[i])`` gives.
     ``offset``, ``metric``, ``cfo`` and the output buffers are resident per link (lists of tensors)."""
 
     def __init__(self, S: int, K: int, CP: int, W: int, frames: int, n_links: int, device="cuda", out_kin: Optional[int] = None,
                  want_metric: bool = True, cfo: bool = False):
-        super().__init__("dccn_frame_sync_supported", S, K, CP, W, frames, n_links, device, out_kin, want_metric, cfo)
+        super().__init__("dccn_frame_sync_supported", ALIGN_NEEDS, S, K, CP, W, frames, device, out_kin, want_metric, cfo, n_links)
         self._table = (_lib.FrameLink * self.n_links)()
 
-    def _launch(self, xs, outs) -> None:
-        xs = _per_link(list(xs), self.n_links, "FrameSyncGroup.run(xs)")
-        want = (self.frames, self.S, self.K + self.CP, 2)
-        for x in xs:
-            if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
-                raise DccnError("FrameSyncGroup.run takes device tensors; there is no CPU fallback")
-            if x.dtype != torch.float32 or tuple(x.shape) != want or not x.is_contiguous():
-                raise DccnError("FrameSyncGroup.run: every x must be a contiguous float32 %r tensor, got %s %r"
-                                % (want, x.dtype, tuple(x.shape)))
+    def _launch(self, xs, outs, write: bool):
+        what, want = "FrameSyncGroup.run", (self.frames, self.S, self.K + self.CP, 2)
+        xs = [_checked_frames(x, want, what) for x in _per_link(list(xs), self.n_links, what + "(xs)")]
+        outs = self._dest(outs, xs[0].device, what) if write else None
         for i, x in enumerate(xs):
-            self._table[i] = _lib.FrameLink(x.data_ptr(), None if outs is None else outs[i].data_ptr(), self.offset[i].data_ptr(),
-                                            self._opt(self.cfo, i), self._opt(self.metric, i))
+            self._table[i] = _lib.FrameLink(x.data_ptr(), _link_ptr(outs, i), self.offset[i].data_ptr(), _link_ptr(self.cfo, i),
+                                            _link_ptr(self.metric, i))
         check(self.lib.dccn_frame_sync_grouped(self.n_links, self._table, self.frames, self.S, self.K, self.CP, self.W,
                                                self.out_kin, self._stream()), "dccn_frame_sync_grouped")
+        return outs
 
     def run(self, xs, outs=None):
         """One launch on the current stream.  ``outs``: one destination per link (``None``: this object's own buffers); no
         destination may overlap another link's frames or outputs."""
-        outs = self._outs(outs)
-        self._launch(xs, outs)
-        return outs, self.offset
+        return self._launch(xs, outs, True), self.offset
 
     def offsets(self, xs):
         """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``."""
-        self._launch(xs, None)
+        self._launch(xs, None, False)
         return self.offset
 
 
-class CaptureSyncGroup(_SyncGroupBase):
+class CaptureSyncGroup(_SyncStage):
     """:class:`CaptureSync` for up to ``dccn_chain_group_max()`` links in ONE launch (``dccn_capture_sync_grouped``):
     ``run(caps, firsts) -> (frames_out, offsets)``, lists with one entry per link.  ``caps[i]``: link i's capture (two links may
     share one); ``firsts[i]``: an integer, or a device ``int64`` tensor of one element together with ``los[i]`` (what
@@ -526,102 +492,73 @@ class CaptureSyncGroup(_SyncGroupBase):
     def __init__(self, S: int, K: int, CP: int, W: int, frames: int, n_links: int, device="cuda", out_kin: Optional[int] = None,
                  want_metric: bool = True, cfo: bool = False, cfo_scope: str = "frame"):
         self.pooled = check_cfo_scope(cfo, cfo_scope)
-        super().__init__("dccn_capture_sync_supported", S, K, CP, W, frames, n_links, device, out_kin, want_metric, cfo,
+        super().__init__("dccn_capture_sync_supported", CUT_NEEDS, S, K, CP, W, frames, device, out_kin, want_metric, cfo, n_links,
                          cfo_len=1 if self.pooled else None)
         self._table = ((_lib.PooledLink if self.pooled else _lib.CaptureLink) * self.n_links)()
         self.ws = None
         if self.pooled:
-            nws = int(self.lib.dccn_capture_sync_pooled_workspace_size(self.frames))
-            self.ws = [torch.empty(nws, dtype=torch.uint8, device=self.device) for _ in range(self.n_links)]
+            self.ws = self._resident(int(self.lib.dccn_capture_sync_pooled_workspace_size(self.frames)), dtype=torch.uint8,
+                                     make=torch.empty)
 
-    def _launch(self, caps, firsts, strides, outs, los) -> None:
-        n = self.n_links
-        caps = [_device_capture(c, "CaptureSyncGroup") for c in _per_link(list(caps), n, "CaptureSyncGroup.run(caps)")]
-        firsts = _per_link(list(firsts), n, "CaptureSyncGroup.run(firsts)")
-        strides = _per_link(strides, n, "CaptureSyncGroup.run(strides)")
-        los = _per_link(los, n, "CaptureSyncGroup.run(los)")
-        for i, (cap, first) in enumerate(zip(caps, firsts)):
-            if isinstance(first, torch.Tensor):
-                if los[i] is None:
-                    raise DccnError("CaptureSyncGroup: a device tensor `first` needs los[i], the origin of the range [lo, lo + T) "
-                                    "it lies in")
-                if first.device != cap.device or first.dtype != torch.int64 or first.numel() != 1 or not first.is_contiguous():
-                    raise DccnError("CaptureSyncGroup: a device `first` must be an int64 tensor of one element on the capture's device")
-        if self.pooled and outs is None:
+    def _launch(self, caps, firsts, strides, outs, write: bool, los):
+        n, what = self.n_links, "CaptureSyncGroup"
+        caps = _link_captures(caps, n, what)
+        firsts = _per_link(list(firsts), n, what + ".run(firsts)")
+        strides = _per_link(strides, n, what + ".run(strides)")
+        los = _per_link(los, n, what + ".run(los)")
+        starts = [_start(first, lo, cap, what) for first, lo, cap in zip(firsts, los, caps)]
+        if self.pooled and not write:
             raise DccnError('CaptureSyncGroup(cfo_scope="capture") has no offsets-only call: the pooled entry writes the frames')
-        for i, (cap, first) in enumerate(zip(caps, firsts)):
-            on_dev = isinstance(first, torch.Tensor)
-            link = (cap.data_ptr(), int(cap.shape[0]), 0 if on_dev else int(first),
-                    first.data_ptr() if on_dev else None, int(los[i]) if on_dev else 0,
-                    self.T if strides[i] is None else int(strides[i]),
-                    None if outs is None else outs[i].data_ptr(), self.offset[i].data_ptr(),
-                    self._opt(self.cfo, i), self._opt(self.metric, i))
+        outs = self._dest(outs, caps[0].device, what + ".run") if write else None
+        for i, cap in enumerate(caps):
+            link = (cap.data_ptr(), int(cap.shape[0]), *starts[i], self.T if strides[i] is None else int(strides[i]),
+                    _link_ptr(outs, i), self.offset[i].data_ptr(), _link_ptr(self.cfo, i), _link_ptr(self.metric, i))
             if self.pooled:
                 self._table[i] = _lib.PooledLink(*link, self.ws[i].data_ptr(), int(self.ws[i].numel()))
             else:
                 self._table[i] = _lib.CaptureLink(*link)
-        if self.pooled:
-            check(self.lib.dccn_capture_sync_pooled_grouped(n, self._table, self.frames, self.S, self.K, self.CP, self.W,
-                                                            self.out_kin, self._stream()), "dccn_capture_sync_pooled_grouped")
-            return
-        check(self.lib.dccn_capture_sync_grouped(n, self._table, self.frames, self.S, self.K, self.CP, self.W, self.out_kin,
-                                                 self._stream()), "dccn_capture_sync_grouped")
+        entry = "dccn_capture_sync_pooled_grouped" if self.pooled else "dccn_capture_sync_grouped"
+        check(getattr(self.lib, entry)(n, self._table, self.frames, self.S, self.K, self.CP, self.W, self.out_kin, self._stream()),
+              entry)
+        return outs
 
     def run(self, caps, firsts, strides=None, outs=None, los=None):
         """One launch on the current stream.  ``strides`` / ``los``: one value for every link or one per link."""
-        outs = self._outs(outs)
-        self._launch(caps, firsts, strides, outs, los)
-        return outs, self.offset
+        return self._launch(caps, firsts, strides, outs, True, los), self.offset
 
     def offsets(self, caps, firsts, strides=None, los=None):
         """The offsets alone (no frame is written); with ``cfo=True`` also ``self.cfo``."""
-        self._launch(caps, firsts, strides, None, los)
+        self._launch(caps, firsts, strides, None, False, los)
         return self.offset
 
 
-class CaptureAcquireGroup:
+def _link_captures(caps, n: int, what: str) -> list:
+    """one float32 capture per link (two links may share one)"""
+    caps = _per_link(list(caps), n, what + ".run(caps)")
+    for cap in caps:
+        _checked_capture(cap, None, what, float32_only=True)
+    return caps
+
+
+class CaptureAcquireGroup(_AcquireStage):
     """:class:`CaptureAcquire` for up to ``dccn_chain_group_max()`` links in THREE launches (``dccn_capture_acquire_grouped``):
     ``run(caps, los) -> firsts``, one device ``int64`` tensor of one element per link -- what :meth:`CaptureSyncGroup.run` takes
     as ``firsts`` together with the same ``los``.  ``pilot_sc``: the pilot cells of every link, or a list of one array per link
     (of one length).  ``first``, ``cfo``, ``sym_metric``, ``phase_metric`` and the workspaces are resident per link (lists)."""
 
     def __init__(self, S: int, K: int, CP: int, pilot_sc, J: int, n_links: int, device="cuda"):
-        self.lib = _lib.load()
-        self.n_links = n = _group_size(self.lib, n_links, "CaptureAcquireGroup")
-        self.S, self.K, self.CP, self.J = int(S), int(K), int(CP), int(J)
-        self.T = self.S * (self.K + self.CP)
-        self.device = dev = torch.device(device)
-        if dev.type != "cuda":
-            raise DccnError("CaptureAcquireGroup needs a CUDA (ROCm) device; there is no CPU fallback")
-        per_link = isinstance(pilot_sc, (list, tuple)) and len(pilot_sc) > 0 and hasattr(pilot_sc[0], "__len__")
-        scs = [torch.as_tensor(sc).reshape(-1).to(torch.int32) for sc in (_per_link(list(pilot_sc), n, "pilot_sc") if per_link
-                                                                          else [pilot_sc])]
-        self.n_pilot = int(scs[0].numel())
-        if any(int(sc.numel()) != self.n_pilot for sc in scs):
-            raise DccnError("CaptureAcquireGroup: the links' pilot cells must be of one length (n_pilot is the call's)")
-        if not self.lib.dccn_capture_acquire_supported(self.S, self.K, self.CP, self.n_pilot, self.J):
-            raise DccnError("dccn_capture_acquire_supported refused S=%d K=%d CP=%d n_pilot=%d J=%d"
-                            % (self.S, self.K, self.CP, self.n_pilot, self.J))
-        scs = [sc.to(dev).contiguous() for sc in scs]
-        self.pilot_sc = scs if per_link else scs * n
-        self.first = [torch.zeros(1, dtype=torch.int64, device=dev) for _ in range(n)]
-        self.cfo = [torch.zeros(1, dtype=torch.float32, device=dev) for _ in range(n)]
-        self.sym_metric = [torch.zeros(self.K + self.CP, dtype=torch.float32, device=dev) for _ in range(n)]
-        self.phase_metric = [torch.zeros(self.S, dtype=torch.float32, device=dev) for _ in range(n)]
-        nws = int(self.lib.dccn_capture_acquire_workspace_size(self.S, self.K, self.CP, self.n_pilot, self.J))
-        self.ws = [torch.empty(nws, dtype=torch.uint8, device=dev) for _ in range(n)]
-        self._table = (_lib.AcquireLink * n)()
+        super().__init__(S, K, CP, pilot_sc, J, device, n_links)
+        self._table = (_lib.AcquireLink * self.n_links)()
 
     def run(self, caps, los=0):
         """Three launches on the current stream; returns ``self.first``."""
         n = self.n_links
-        caps = [_device_capture(c, "CaptureAcquireGroup") for c in _per_link(list(caps), n, "CaptureAcquireGroup.run(caps)")]
+        caps = _link_captures(caps, n, "CaptureAcquireGroup")
         los = _per_link(los, n, "CaptureAcquireGroup.run(los)")
         for i, cap in enumerate(caps):
             self._table[i] = _lib.AcquireLink(cap.data_ptr(), int(cap.shape[0]), int(los[i]), self.pilot_sc[i].data_ptr(),
                                               self.first[i].data_ptr(), self.cfo[i].data_ptr(), self.sym_metric[i].data_ptr(),
                                               self.phase_metric[i].data_ptr(), self.ws[i].data_ptr(), int(self.ws[i].numel()))
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        check(self.lib.dccn_capture_acquire_grouped(n, self._table, self.J, self.S, self.K, self.CP, self.n_pilot, stream),
+        check(self.lib.dccn_capture_acquire_grouped(n, self._table, self.J, self.S, self.K, self.CP, self.n_pilot, self._stream()),
               "dccn_capture_acquire_grouped")
         return self.first
